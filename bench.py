@@ -16,7 +16,21 @@
   cpu_baseline : the scalar C++ oracle re-tracing the SAME BVH arrays on the host cores, bounded sample (rank 0, N=1 only):
              all threads, and one thread
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--width 1920 --height 1080 --mesh bunny.obj]
+A plain run does what the headline figure needs and no more: set-up (priming frames included), the W warm-up steps, the K timed
+steps, the outputs of the last step if --dump-outputs is given, and the result line (metric, value, unit, ms_per_step, config).
+--full adds everything else, as before: the measured copy bandwidth, the per-kernel timing of the timed region, `roofline`,
+`instrumented_frame_ms`, `cpu_baseline` and `sustained`.
+
+--dump-outputs DIR: after the timed steps, what the last of them computed, as float32 .npy files (about 50 MB at 1920x1080):
+  backbuffer.npy  [H, W, 4]  the tone-mapped RGBA8 back buffer the frame presents (rank 0 holds the whole frame), bytes in memory order
+  hdr_sample.npy  [n, 4]     the denoised HDR image (temporal pass output, RGBA16F) at n = min(2^20, H*W) pixels drawn without
+                             replacement by numpy's default_rng(0), in ascending row-major order (N = 1 only)
+  rays.npy        [1]        (float64) rays traced in that frame by all ranks
+  (--stub: backbuffer.npy is the stand-in's assembled [H, W] frame of int32 words, as float64)
+The inputs depend on the arguments alone, so two builds run with the same arguments can be compared output for output.  (--full
+renders 16 more frames before the warm-up, to refill the caches after the copy-bandwidth kernel: its last step is a later frame.)
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--width 1920 --height 1080 --mesh bunny.obj] [--dump-outputs DIR] [--full]
 """
 import argparse
 import json
@@ -52,10 +66,13 @@ def parse_args(argv=None):
     ap.add_argument("--collapse-weights", type=float, nargs=2, default=None, help="weights (area, triangle count) of the 4-wide collapse's objective (measurement; rtggx_debug_collapse_weights)")
     ap.add_argument("--tile-words", choices=["on", "off"], default="on", help="off: every tile of the visibility target counts as drawn, as in rounds 1-3 (measurement)")
     ap.add_argument("--tone-map", choices=["auto", "fused", "two"], default="auto", help="temporal pass + tone map as one kernel or two (measurement; auto: the library's choice, fused on small launches)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--sustained-frames", type=int, default=1024, help="N = 1: frames of a second, longer window after the timed one, reported as `sustained` (0: none)")
-    ap.add_argument("--cpu-threads", type=int, default=0, help="host threads of the cpu_baseline leg (default: the job's CPU share, at most 16)")
-    ap.add_argument("--cpu-frames", type=int, default=8, help="timed oracle frames on all threads (one more, untimed, first); the single-thread leg times 1")
+    ap.add_argument("--full", action="store_true", help="besides the headline figure: measured copy bandwidth, per-kernel timing, roofline, instrumented frame, "
+                    "cpu_baseline and sustained (off: the headline figure alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no cpu_baseline leg")
+    ap.add_argument("--sustained-frames", type=int, default=1024, help="--full, N = 1: frames of a second, longer window after the timed one, reported as `sustained` (0: none)")
+    ap.add_argument("--cpu-threads", type=int, default=0, help="--full: host threads of the cpu_baseline leg (default: the job's CPU share, at most 16)")
+    ap.add_argument("--cpu-frames", type=int, default=8, help="--full: timed oracle frames on all threads (one more, untimed, first); the single-thread leg times 1")
     ap.add_argument("--prime-frames", type=int, default=256, help="frames rendered during SET-UP, before the warm-up steps: the GPU's compute clock ramps for "
                     "30-50 ms after any idle period (profiles/r02_b_clock_ramp.txt), and the renderer's adaptive state settles over its first frames; 0 = none")
     ap.add_argument("--no-balance", action="store_true", help="N > 1: equal strips instead of strips balanced by covered pixels")
@@ -213,7 +230,7 @@ def main():
         ctx.fuse_tone_map(args.tone_map == "fused")
     for _ in range(0 if args.stub else args.prime_frames):
         r.frame()
-    if not args.stub:
+    if args.full and not args.stub:
         # the box's attainable HBM bandwidth, quoted beside the vendor peak: a float4 copy kernel, 2 x 1 GiB per launch, 128 launches
         # (>= 50 ms) AFTER the priming frames -- i.e. with the compute clock ramped like the timed region's (round 2 measured 8 launches
         # right after set-up, inside the clock ramp, and read 4.6 TB/s)
@@ -224,7 +241,7 @@ def main():
             r.frame()
     for _ in range(args.warmup):
         r.frame()
-    if not args.stub:
+    if args.full and not args.stub:
         ctx.enable_timing(3)        # a HIP event pair around the ray-trace kernel of every 8th frame, no host sync
     r.rays_traced_since_reset()     # zero the running ray total
     barrier()
@@ -236,6 +253,8 @@ def main():
     # per-frame ray counts and kernel durations were recorded without host synchronisation; collect them now
     rays_total = r.rays_traced_since_reset()
     own_rays = rays_total
+    if args.dump_outputs:
+        dump_outputs(r, args, W, H, rank, world, dist, device, np, torch)      # before anything else renders a frame
     overreach = 0 if args.stub else r.history_overreach()
     if world > 1:
         t = torch.tensor([dt, float(rays_total), float(overreach)], dtype=torch.float64, device=device)
@@ -255,6 +274,8 @@ def main():
         if args.stub:
             out["config"] = {"workload": "STUB: no rendering -- launcher / rank-protocol rehearsal over gloo, %dx%d" % (W, H), "parallelism": "row strips x%d" % world}
             out["data"] = "none (stub)"
+        elif not args.full:
+            out["config"] = run_config(r, args, W, H, world, rays_total, overreach)
         else:
             out.update(report(r, args, W, H, world, ms_per_step, rays_total, own_rays, overreach, peak_measured, np))
             # One more figure beside the contract's (N = 1 only; after everything above has been read): 1024 more frames.  The pipeline has
@@ -272,6 +293,46 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(r, args, W, H, rank, world, dist, device, np, torch):
+    """--dump-outputs DIR: what the last timed step computed, as the module docstring lists it (rank 0 writes)."""
+    back, hdr = None, None
+    if args.stub:
+        back = r.back.numpy().astype(np.float64)         # the stand-in's frame [H, W]: int32 words, exact in float64
+        rays = float((r.e - r.b) * W // 4)
+    else:
+        from raytracedggx_amd import capi
+        if rank == 0:
+            back = np.ascontiguousarray(r.context.readback(capi.BUF_BACKBUFFER), np.uint32).view(np.uint8).reshape(H, W, 4).astype(np.float32)
+        if world == 1:
+            words = np.ascontiguousarray(r.context.readback(capi.BUF_TSS0 + r.context.frame_parity()), np.uint64)
+            pick = np.sort(np.random.default_rng(0).choice(H * W, size=min(1 << 20, H * W), replace=False))
+            hdr = words.reshape(-1)[pick].view(np.float16).reshape(-1, 4).astype(np.float32)
+        rays = float(r.context.ray_count())
+    if world > 1:
+        t = torch.tensor([rays], dtype=torch.float64, device=device)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        rays = float(t[0].item())
+    if rank != 0:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    np.save(os.path.join(args.dump_outputs, "backbuffer.npy"), back)
+    if hdr is not None:
+        np.save(os.path.join(args.dump_outputs, "hdr_sample.npy"), hdr)
+    np.save(os.path.join(args.dump_outputs, "rays.npy"), np.array([rays], np.float64))
+
+
+def run_config(r, args, W, H, world, rays_total, overreach):
+    """The result line's `config`: what was run.  Read from the host side only (no frame, no GPU work)."""
+    residency = None if args.stub else r.context.trace_residency(args.trace_waves)
+    return {"workload": "configs[1]: %s + rnl_cross env, %dx%d, 1spp GGX reflection + full denoise chain (refl H,V; diff H,V, shared-memory variant; temporal; tone map), "
+                        "%s, dt=1/60%s" % (args.mesh, W, H, "metallic %g %g" % tuple(args.metallic) if args.metallic else "all-metal default materials",
+                                           ", model deforming every frame (amplitude %g, asynchronous BVH refit)" % args.deform if args.deform else ""),
+            "rays_per_frame": round(rays_total / args.steps, 1), "parallelism": "row strips x%d" % world, "strip_bounds": r.bounds,
+            "history_apron_rows": r.apron, "history_overreach_rows": overreach,
+            "setup_priming_frames": args.prime_frames,
+            "trace_workgroup_waves": None if residency is None else residency[0], "trace_share_of_period": None if residency is None else round(residency[1], 3)}
 
 
 def report(r, args, W, H, world, ms_per_step, rays_total, own_rays, overreach, peak_measured, np):
@@ -300,7 +361,7 @@ def report(r, args, W, H, world, ms_per_step, rays_total, own_rays, overreach, p
     achieved = alg_bytes / (k_ms * 1e-3) / 1e9 if k_ms == k_ms and k_ms > 0 else None
     # The same kernel with nothing beside it (after the timed region: 32 frames issued to ONE stream, rtggx_set_async_compute(0)): in the
     # timed region it shares the chip with two other stages at low stream priority, and its duration there is not its speed.
-    residency = None if args.stub else r.context.trace_residency(args.trace_waves)
+    config = run_config(r, args, W, H, world, rays_total, overreach)
     k_alone = float("nan")
     if world == 1:
         r.context.set_async_compute(False)
@@ -315,13 +376,7 @@ def report(r, args, W, H, world, ms_per_step, rays_total, own_rays, overreach, p
         k_alone = float(np.mean(alone)) if len(alone) else float("nan")
     frame_gbs = frame_bytes / (ms_per_step * 1e-3) / 1e9
     out = {
-        "config": {"workload": "configs[1]: %s + rnl_cross env, %dx%d, 1spp GGX reflection + full denoise chain (refl H,V; diff H,V, shared-memory variant; temporal; tone map), "
-                               "%s, dt=1/60%s" % (args.mesh, W, H, "metallic %g %g" % tuple(args.metallic) if args.metallic else "all-metal default materials",
-                                                  ", model deforming every frame (amplitude %g, asynchronous BVH refit)" % args.deform if args.deform else ""),
-                   "rays_per_frame": round(rays_total / args.steps, 1), "parallelism": "row strips x%d" % world, "strip_bounds": r.bounds,
-                   "history_apron_rows": r.apron, "history_overreach_rows": overreach,
-                   "setup_priming_frames": args.prime_frames,
-                   "trace_workgroup_waves": None if residency is None else residency[0], "trace_share_of_period": None if residency is None else round(residency[1], 3)},
+        "config": config,
         "roofline": {"bound": "hbm", "kernel": "rt::traceKernel", "achieved": None if achieved is None else round(achieved, 2),
                      "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None if achieved is None else round(achieved / HBM_PEAK_GBS, 5),
                      "traffic": traffic, "traffic_source": traffic_source, "algorithmic_bytes_per_launch": int(alg_bytes),

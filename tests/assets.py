@@ -1,12 +1,12 @@
 """Test/bench inputs: writes .obj / .dds files equivalent to the reference's assets from
-tests/golden/assets.npz into a cache directory (the GPU box has no /root/reference)."""
+tests/golden/assets/ (one compressed .npz per array) into a cache directory, so that nothing outside the repository is read."""
 import os
 import tempfile
 
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_NPZ = os.path.join(_HERE, "golden", "assets.npz")
+_ARRAYS = os.path.join(_HERE, "golden", "assets")
 _CACHE = os.environ.get("RTGGX_ASSET_CACHE", os.path.join(tempfile.gettempdir(), "rtggx_assets_%d" % os.getuid()))
 
 _SINGLE_TRIANGLE_OBJ = "v -1 0 0\nv 1 0 0\nv 0 2 0\nf 1 2 3\n"
@@ -19,18 +19,28 @@ def _write_atomic(path, data, mode):
     os.replace(tmp, path)
 
 
+def _load_arrays():
+    """name -> array of every tests/golden/assets/<name>.npz (written by tests/golden/make_assets.py)."""
+    z = {}
+    for f in sorted(os.listdir(_ARRAYS)):
+        if f.endswith(".npz"):
+            with np.load(os.path.join(_ARRAYS, f)) as part:
+                z.update((k, part[k]) for k in part.files)
+    return z
+
+
 def asset_dir():
     """Directory laid out like the reference's Bin/: Assets/bunny.obj, Assets/dragon.obj, Assets/TuringBowl.obj, Assets/rnl_cross.dds."""
     d = os.path.join(_CACHE, "Assets")
     os.makedirs(d, exist_ok=True)
     need = [n for n in ("bunny.obj", "dragon.obj", "TuringBowl.obj", "rnl_cross.dds", "triangle.obj") if not os.path.exists(os.path.join(d, n))]
     if need:
-        z = np.load(_NPZ)
+        z = _load_arrays()
         for name in ("bunny", "dragon", "TuringBowl"):
             if name + ".obj" in need:
                 v, f = z[name + "_v"], z[name + "_f"]
                 lines = ["v %.9g %.9g %.9g" % tuple(float(x) for x in row) for row in v]
-                if name + "_vn" in z.files:          # "f a//na b//nb c//nc" (TuringBowl: per-corner normals, vertex splitting)
+                if name + "_vn" in z:          # "f a//na b//nb c//nc" (TuringBowl: per-corner normals, vertex splitting)
                     lines += ["vn %.9g %.9g %.9g" % tuple(float(x) for x in row) for row in z[name + "_vn"]]
                     lines += ["f %d//%d %d//%d %d//%d" % tuple(int(x) for x in row.reshape(-1)) for row in f]
                 else:

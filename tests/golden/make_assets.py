@@ -1,5 +1,5 @@
-"""Generates tests/golden/assets.npz from the data assets of the reference (run in the build
-container only; /root/reference does not exist on the GPU box).
+"""Generates tests/golden/assets/ from the data assets of the reference: one compressed .npz per array, so that every
+committed file stays small.  Run where the reference's Bin/Assets directory is at hand; the tests read only the arrays.
 
 What is stored is data, not source: for each mesh the raw `v` (and `vn`) records (float32) and the 1-based `f`
 triangles of the OBJ file, and the bytes of the DDS cube map -- the inputs BASELINE.json's configs and the
@@ -52,7 +52,9 @@ def main():
             out[name + "_f"] = np.ascontiguousarray(f[:, :, 0])     # [T, 3]
         print(name, v.shape, vn.shape, f.shape)
     out["rnl_cross_dds"] = np.fromfile(os.path.join(REF, "rnl_cross.dds"), np.uint8)
-    np.savez_compressed(os.path.join(HERE, "assets.npz"), **out)
+    os.makedirs(os.path.join(HERE, "assets"), exist_ok=True)
+    for name, a in out.items():
+        np.savez_compressed(os.path.join(HERE, "assets", name + ".npz"), **{name: a})
 
 
 if __name__ == "__main__":

@@ -43,3 +43,28 @@ def test_a_failing_rank_fails_the_launcher():
     # strips thinner than the history apron: every rank raises; the launcher must not report success
     r = _run(["--gpus", "2", "--stub", "--steps", "1", "--warmup", "0", "--width", "16", "--height", "20"])
     assert r.returncode != 0
+
+
+@pytest.mark.parametrize("world", [1, 2])
+def test_bench_dump_outputs_is_the_last_step_and_repeats(world, tmp_path):
+    """--dump-outputs DIR writes what the last timed step computed, the same from run to run; --full is accepted beside it.
+    The stand-in's frame is known: row y, column x of step f holds y * 1000 + x + f + 7 (StubRenderer._truth)."""
+    import numpy as np
+    steps, warmup, W, H = 3, 2, 16, 60
+    dumps = []
+    for k, extra in enumerate(([], ["--full"])):
+        d = tmp_path / ("out%d" % k)
+        r = _run(["--gpus", str(world), "--stub", "--steps", str(steps), "--warmup", str(warmup), "--width", str(W), "--height", str(H),
+                  "--dump-outputs", str(d)] + extra)
+        assert r.returncode == 0, r.stdout + r.stderr
+        assert json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])["steps"] == steps
+        assert sorted(os.listdir(d)) == ["backbuffer.npy", "rays.npy"]
+        dumps.append({n: np.load(d / (n + ".npy")) for n in ("backbuffer", "rays")})
+    last = warmup + steps - 1
+    truth = np.arange(H)[:, None] * 1000 + np.arange(W)[None, :] + last + 7
+    for dump in dumps:
+        assert dump["backbuffer"].dtype == np.float64 and dump["backbuffer"].shape == (H, W)
+        np.testing.assert_array_equal(dump["backbuffer"], truth)
+        assert dump["rays"].dtype == np.float64 and dump["rays"].tolist() == [H * W // 4]      # every rank: its rows x W / 4 (W = 16)
+    for n in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][n], dumps[1][n])

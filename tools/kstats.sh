@@ -4,7 +4,8 @@ tag=$1; tree=$2; shift 2
 root=$GRAFT_REPO_ROOT; out=$root/gpurun_out/r04/ks_$tag; mkdir -p $out
 dir=$root; [ "$tree" != "." ] && dir=$root/_ab/$tree
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $out -o ks -- python3 $dir/bench.py --steps 256 --warmup 64 --no-cpu-baseline "$@" > $out/bench.log 2>&1
+full=$(grep -q -- '"--full"' $dir/bench.py && echo --full)      # (trees older than the option print the full line by default)
+rocprofv3 --kernel-trace --stats --output-format csv -d $out -o ks -- python3 $dir/bench.py $full --steps 256 --warmup 64 --no-cpu-baseline "$@" > $out/bench.log 2>&1
 cd $root
 python - $out/ks_kernel_stats.csv $tag <<'PY'
 import csv, sys

@@ -71,8 +71,8 @@ json.dump(out, open("profiles/%s_pmc_traffic.json" % tag, "w"), indent=1)
 print("trace kernel traffic:", out["kernels"].get("rt::traceKernel"))
 EOF
 if [ "$summaries_only" != "--summaries-only" ]; then
-python3 bench.py > "$out/bench.log" 2>&1
-rocprofv3 --kernel-trace --stats -d "$out/trace" -o run --output-format csv -- python3 bench.py --no-cpu-baseline > "$out/trace.log" 2>&1
+python3 bench.py --full > "$out/bench.log" 2>&1
+rocprofv3 --kernel-trace --stats -d "$out/trace" -o run --output-format csv -- python3 bench.py --full --no-cpu-baseline > "$out/trace.log" 2>&1
 fi
 grep '^{' "$out/bench.log" | tail -n 1 > "profiles/${tag}_bench.json"
 cp "$out/trace/run_kernel_stats.csv" "profiles/${tag}_kernel_stats.csv"

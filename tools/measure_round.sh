@@ -14,7 +14,7 @@ fi
 mkdir -p $out
 tools/make_profiles.sh $tag > $out/make_profiles.log 2>&1; echo "profiles done"
 for i in 1 2 3 4 5 6 7 8 9 10; do python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' >> $out/bench_driver_settings.jsonl; done; echo "driver settings done"
-o="--steps 128 --warmup 48 --no-cpu-baseline"
+o="--full --steps 128 --warmup 48 --no-cpu-baseline"
 { python bench.py $o --mesh dragon.obj; python bench.py $o --width 3840 --height 2160; python bench.py $o --mesh dragon.obj --width 3840 --height 2160
   python bench.py $o --metallic 0.25 0.5; python bench.py $o --mesh dragon.obj --metallic 0.25 0.5; python bench.py $o --width 1920 --height 171 --steps 512
   python bench.py $o --width 256 --height 144 --steps 512; python bench.py $o --deform 0.3; python bench.py $o --mesh dragon.obj --width 3840 --height 2160 --deform 0.3; } 2>/dev/null | grep '^{' > $out/other_configs.jsonl

@@ -25,6 +25,6 @@ i=0
 for g in "${groups[@]}"; do
   i=$((i + 1))
   if [ $i -lt $first ] || [ $i -gt $last ]; then continue; fi
-  rocprofv3 --pmc $g -d "$out/g$i" -o run --output-format csv -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline > "$out/g$i.log" 2>&1 || echo "group $i failed (see $out/g$i.log)"
+  rocprofv3 --pmc $g -d "$out/g$i" -o run --output-format csv -- python3 bench.py --full --steps 4 --warmup 2 --no-cpu-baseline > "$out/g$i.log" 2>&1 || echo "group $i failed (see $out/g$i.log)"
   echo "group $i done"
 done
