@@ -175,7 +175,8 @@ int  rtggx_history_ipc_open(rtggx_context* ctx, const void* handles, size_t byte
  * stream B / C, no overlap between frames); 1 (default): the multi-stream frame.  Results are bit-identical; synchronises. */
 int  rtggx_set_async_compute(rtggx_context* ctx, int enable);
 
-/* Vertex = {float3 Pos; float3 Nrm} (24 bytes), 32-bit indices, triangle list. */
+/* Vertex = {float3 Pos; float3 Nrm} (24 bytes), 32-bit indices, triangle list of at most 2^24 triangles (a primitive id has 24 bits;
+ * a larger mesh is refused and the slot keeps what it held). */
 int  rtggx_set_mesh(rtggx_context* ctx, uint32_t slot, const float* verts, uint32_t num_verts,
                     const uint32_t* indices, uint32_t num_indices);
 /* Cube map: `size` x `size` faces, `mips` levels, `data` laid out as in a DDS file (face-major,

@@ -59,7 +59,7 @@ def lib():
                      "orc_set_frame_constants", "orc_get_frame_constants", "orc_halton", "orc_update_as",
                      "orc_get_inv_worlds", "orc_transform_sh", "orc_set_sh", "orc_render_visibility", "orc_set_visibility",
                      "orc_ray_trace", "orc_denoise", "orc_tone_map", "orc_flip_parity", "orc_get_parity", "orc_trace_rays",
-                     "orc_environment"):
+                     "orc_environment", "orc_mesh_info", "orc_mesh_copy"):
             fn = getattr(L, name)
             if fn.argtypes is None:
                 fn.argtypes = None  # first arg is the handle: always pass C.c_void_p explicitly
@@ -129,6 +129,15 @@ class Oracle:
         verts = np.ascontiguousarray(verts, np.float32)
         idx = np.ascontiguousarray(idx, np.uint32)
         self.L.orc_set_mesh(self.h, C.c_uint32(slot), _fp(verts), C.c_uint32(verts.shape[0]), _fp(idx), C.c_uint32(idx.size))
+
+    def mesh(self, slot):
+        """The slot's mesh as the oracle holds it: (verts[nv, 6] float32, indices[ni] uint32)."""
+        nv, ni = C.c_uint32(), C.c_uint32()
+        self.L.orc_mesh_info(self.h, C.c_uint32(slot), C.byref(nv), C.byref(ni))
+        verts = np.zeros((nv.value, 6), np.float32)
+        idx = np.zeros(ni.value, np.uint32)
+        self.L.orc_mesh_copy(self.h, C.c_uint32(slot), _fp(verts), _fp(idx))
+        return verts, idx
 
     def set_pos_scale(self, ps):
         self.L.orc_set_pos_scale(self.h, _fp(np.asarray(ps, np.float32)))

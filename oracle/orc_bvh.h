@@ -18,6 +18,8 @@
 #pragma once
 #include <algorithm>
 #include <cfloat>
+#include <limits>
+#include <vector>
 #include "orc_scene.h"
 
 namespace orc {
@@ -35,7 +37,8 @@ static inline RayXform ray_to_object(const float3 o, const float3 d, const M4& i
   const float3 dd = mul_dir(d, inv);
   r.o[0] = oo.x; r.o[1] = oo.y; r.o[2] = oo.z;
   r.d[0] = dd.x; r.d[1] = dd.y; r.d[2] = dd.z;
-  for (int k = 0; k < 3; ++k) r.invd[k] = 1.0f / r.d[k];
+  // zero component: NaN, which slab()'s fmin / fmax drop -- with +-inf a ray lying in a box's face plane missed the box (0 x inf)
+  for (int k = 0; k < 3; ++k) r.invd[k] = r.d[k] != 0.0f ? 1.0f / r.d[k] : std::numeric_limits<float>::quiet_NaN();
   const float ax = std::fabs(r.d[0]), ay = std::fabs(r.d[1]), az = std::fabs(r.d[2]);
   r.kz = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
   r.kx = (r.kz + 1) % 3; r.ky = (r.kx + 1) % 3;
@@ -91,31 +94,34 @@ static inline void slab(const RayXform& r, const float* bmin, const float* bmax,
 struct TraverseStats { uint64_t nodes = 0, leaves = 0, rays = 0; int maxStack = 0; };
 static thread_local TraverseStats g_tstats;
 
+// The stack grows with the tree: a binary tree can be as deep as it has triangles (the device accepts depths up to 128; a
+// caterpillar whose nearer child is always the subtree pushes one entry per level).  One per thread, reused from ray to ray.
 static inline void traverse_blas(const Bvh& bvh, const RayXform& r, float tmin, uint32_t inst, Hit& best,
                                  uint32_t skipInst, uint32_t skipPrim) {
   if (bvh.tris.empty()) return;
-  int32_t stack[64]; int sp = 0;
+  static thread_local std::vector<int32_t> stack;
+  stack.clear();
   int32_t cur = bvh.root;
   for (;;) {
     if (cur < 0) {
       ++g_tstats.leaves;
       consider(best, tmin, inst, bvh.tris[(size_t)~cur], r, skipInst, skipPrim);
-      if (sp == 0) break;
-      cur = stack[--sp];
+      if (stack.empty()) break;
+      cur = stack.back(); stack.pop_back();
       continue;
     }
     const BvhNode& n = bvh.nodes[(size_t)cur];
     ++g_tstats.nodes;
-    if (sp > g_tstats.maxStack) g_tstats.maxStack = sp;
+    if ((int)stack.size() > g_tstats.maxStack) g_tstats.maxStack = (int)stack.size();
     float ln, lf, rn, rf;
     slab(r, n.lmin, n.lmax, tmin, best.t, ln, lf);
     slab(r, n.rmin, n.rmax, tmin, best.t, rn, rf);
     const bool hl = ln <= lf * 1.0000004f, hr = rn <= rf * 1.0000004f;
     if (hl && hr) {
-      if (ln <= rn) { stack[sp++] = n.right; cur = n.left; } else { stack[sp++] = n.left; cur = n.right; }
+      if (ln <= rn) { stack.push_back(n.right); cur = n.left; } else { stack.push_back(n.left); cur = n.right; }
     } else if (hl) cur = n.left;
     else if (hr) cur = n.right;
-    else { if (sp == 0) break; cur = stack[--sp]; }
+    else { if (stack.empty()) break; cur = stack.back(); stack.pop_back(); }
   }
 }
 

@@ -68,6 +68,14 @@ int orc_set_mesh(void* h, uint32_t slot, const float* verts, uint32_t nv, const 
   m.verts.assign(verts, verts + 6 * (size_t)nv); m.idx.assign(idx, idx + ni); m.bvh = Bvh{};
   return 0;
 }
+// The mesh of a slot as the oracle holds it (two-call protocol: counts, then copy out).
+void orc_mesh_info(void* h, uint32_t slot, uint32_t* numVerts, uint32_t* numIndices) {
+  const Mesh& m = ((Ctx*)h)->mesh[slot]; *numVerts = (uint32_t)(m.verts.size() / 6); *numIndices = (uint32_t)m.idx.size();
+}
+void orc_mesh_copy(void* h, uint32_t slot, float* verts, uint32_t* idx) {
+  const Mesh& m = ((Ctx*)h)->mesh[slot];
+  std::memcpy(verts, m.verts.data(), m.verts.size() * 4); std::memcpy(idx, m.idx.data(), m.idx.size() * 4);
+}
 void orc_set_pos_scale(void* h, const float* ps) { std::memcpy(((Ctx*)h)->posScale, ps, 16); }
 void orc_set_sampler(void* h, int vndf) { ((Ctx*)h)->vndf = vndf != 0; }
 void orc_set_normal_weight(int variant) { g_normalWeightVariant = variant; }      // orc_denoise.h normal_weight: 0 exact, 1 libm fp32, 2 round 3's squarings (process-wide)

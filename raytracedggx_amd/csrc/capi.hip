@@ -126,7 +126,11 @@ static void freeMeshVerts(MeshDev& m) {
   m.verts = nullptr; m.deforming = false; m.pendingStage = -1; m.version = 0; m.latestSet = 0;
   for (auto& v : m.vertsVersion) v = 0;
 }
+// Hit keys and visibility words carry the primitive in their low 24 bits, the instance above it (trace.hip, raytrace.hip,
+// visibility.hip): a mesh of more triangles would alias primitive ids without a trace of it.
+#define RT_MAX_TRIANGLES (1u << 24)
 static int setMeshImpl(rtggx_context* c, uint32_t slot, const float* verts, uint32_t nv, const uint32_t* idx, uint32_t ni) {
+  if (ni / 3u > RT_MAX_TRIANGLES) { setError("rtggx_set_mesh: %u triangles, more than the %u a 24-bit primitive id can tell apart", ni / 3u, RT_MAX_TRIANGLES); return -1; }
   MeshDev& m = c->mesh[slot];
   RT_HIP(syncStreams(c));       // frames in flight on any of the streams still read the buffers freed below
   abandonRebuild(c, slot); m.wantRebuild = false;

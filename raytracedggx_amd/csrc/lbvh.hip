@@ -147,7 +147,7 @@ __global__ void __launch_bounds__(256) radixScatter(const uint32_t* __restrict__
 // for the partner that gives the smallest merged box; mutual choices merge into a new node; the survivors are
 // compacted (order kept) and the step repeats until one cluster is left.  Trees come out close to a SAH sweep
 // build -- on the bunny a third fewer traversal steps per ray than the Karras radix tree (profiles/r01_d).
-// Everything is deterministic: ties go to the lower position, node indices come from prefix sums.
+// Everything is deterministic: candidates are ranked by plocPairKey below, node indices come from prefix sums.
 //
 // Device-driven (round 3).  How many clusters a round leaves is known on the device only, so nothing on the host depends on it:
 // the host issues a FIXED number of rounds sized from the triangle count (each round: plocNearest, plocScatter, both with
@@ -176,6 +176,19 @@ RT_DEV float mergedArea(const float* a, const float* b) {
   const float ex = fmaxf(a[3], b[3]) - fminf(a[0], b[0]), ey = fmaxf(a[4], b[4]) - fminf(a[1], b[1]), ez = fmaxf(a[5], b[5]) - fminf(a[2], b[2]);
   return (ex * ey + ey * ez) + ez * ex;
 }
+// How the nearest-neighbour searches rank the partners j of position i: least merged area, then least key (|i - j|, parity of
+// min(i, j), min(i, j)).  Every part depends on the unordered pair {i, j} only -- the merged box is the same from both ends (fminf and
+// fmaxf commute) -- and (|i - j|, min(i, j)) names the pair, so this is a strict total order on pairs: the best pair of the list is the
+// choice of both its ends, and every round merges.  ("Ties to the lower position" was not: it depends on which end asks.  In a run of
+// equal boxes -- coincident triangles, the quads of a flat grid -- every position chose the lowest in its reach and ONE pair was mutual
+// per round: n identical triangles took n - 1 rounds and made a tree n levels deep.)  The parity makes such a run pair up (2k, 2k + 1)
+// in one round.  j < 0: no candidate, after every real one.
+RT_DEV uint64_t plocPairKey(int i, int j) {
+  if (j < 0) return ~0ull;
+  const uint32_t lo = (uint32_t)min(i, j);
+  return ((uint64_t)(uint32_t)abs(i - j) << 33) | ((uint64_t)(lo & 1u) << 32) | (uint64_t)lo;
+}
+RT_DEV bool plocCloser(float d, uint64_t key, float bestD, uint64_t bestKey) { return d < bestD || (d == bestD && key < bestKey); }
 // first kernel of a build: the device records start clean
 __global__ void buildBegin(uint32_t n, PlocState* state, BuildResult* res, uint32_t* bounds) {
   if (threadIdx.x == 0) {
@@ -193,12 +206,13 @@ __global__ void plocInit(int n, const uint32_t* __restrict__ order, const float*
 RT_DEV int plocNearestOf(int i, int m, int radius, const float* __restrict__ clBox) {
   float mine[6];
   for (int k = 0; k < 6; ++k) mine[k] = clBox[6 * (size_t)i + k];
-  float best = __builtin_inff(); int bj = -1;
+  float best = __builtin_inff(); int bj = -1; uint64_t bk = ~0ull;
   const int lo = max(i - radius, 0), hi = min(i + radius, m - 1);
   for (int j = lo; j <= hi; ++j) {
     if (j == i) continue;
     const float d = mergedArea(mine, clBox + 6 * (size_t)j);
-    if (d < best) { best = d; bj = j; }
+    const uint64_t k = plocPairKey(i, j);
+    if (plocCloser(d, k, best, bk)) { best = d; bj = j; bk = k; }
   }
   return bj;
 }
@@ -210,9 +224,9 @@ RT_DEV int plocNearestOf(int i, int m, int radius, const float* __restrict__ clB
 #define RT_PLOC_LANES 4      // lanes that share one position's search (each a quarter of the neighbourhood): there are only ~1000 waves of work in
                              // the largest round, one per SIMD, and a wave's search is a chain of dependent LDS reads -- four times the waves, each a quarter as long
 // The nearest neighbour of position i among [i - radius, i + radius] (boxes in LDS, entry e = position lo + e): smallest merged box, ties
-// to the lower position.  RT_PLOC_LANES consecutive lanes call it together for the same i, `sub` = the caller's share.
+// by plocPairKey.  RT_PLOC_LANES consecutive lanes call it together for the same i, `sub` = the caller's share.
 RT_DEV int plocNearestShared(const float (*box)[256 + 2 * RT_PLOC_APRON], int i, int lo, int m, int radius, uint32_t sub) {
-  float best = __builtin_inff(); int bj = 0x7FFFFFFF;
+  float best = __builtin_inff(); int bj = -1; uint64_t bk = ~0ull;
   if (i >= 0 && i < m) {
     const int ei = i - lo;
     float mine[6];
@@ -223,14 +237,16 @@ RT_DEV int plocNearestShared(const float (*box)[256 + 2 * RT_PLOC_APRON], int i,
       const int ej = j - lo;
       const float ex = fmaxf(mine[3], box[3][ej]) - fminf(mine[0], box[0][ej]), ey = fmaxf(mine[4], box[4][ej]) - fminf(mine[1], box[1][ej]), ez = fmaxf(mine[5], box[5][ej]) - fminf(mine[2], box[2][ej]);
       const float d = (ex * ey + ey * ez) + ez * ex;
-      if (d < best) { best = d; bj = j; }      // (ascending j: the first of equal distances stays)
+      const uint64_t k = plocPairKey(i, j);
+      if (plocCloser(d, k, best, bk)) { best = d; bj = j; bk = k; }
     }
   }
-  for (int o = 1; o < RT_PLOC_LANES; o <<= 1) {      // the best of the group's shares: smaller distance, then lower position
+  for (int o = 1; o < RT_PLOC_LANES; o <<= 1) {      // the best of the group's shares, by the whole rank (the lanes share i: the key follows from j)
     const float od = __shfl_xor(best, o); const int oj = __shfl_xor(bj, o);
-    if (od < best || (od == best && oj < bj)) { best = od; bj = oj; }
+    const uint64_t ok = plocPairKey(i, oj);
+    if (plocCloser(od, ok, best, bk)) { best = od; bj = oj; bk = ok; }
   }
-  return bj == 0x7FFFFFFF ? -1 : bj;
+  return bj;
 }
 __global__ void __launch_bounds__(256 * RT_PLOC_LANES) plocNearest(const PlocState* __restrict__ state, uint32_t r, int radius, PlocArrays A, uint2* __restrict__ blockCounts) {
   __shared__ float box[6][256 + 2 * RT_PLOC_APRON];
@@ -378,7 +394,7 @@ __global__ void __launch_bounds__(1024) plocFinal(const PlocState* __restrict__ 
   }
   __syncthreads();
   while (m > 1u) {
-    // nearest neighbour within the radius: smallest merged box, ties to the lower position.  As the list shrinks, more lanes share one
+    // nearest neighbour within the radius: smallest merged box, ties by plocPairKey.  As the list shrinks, more lanes share one
     // position's search (`group` consecutive lanes, each every group-th neighbour, then the best of the group): the rounds of the tail
     // are chains of dependent LDS reads, and a thousand threads are there anyway
     uint32_t group = 1u;
@@ -386,19 +402,21 @@ __global__ void __launch_bounds__(1024) plocFinal(const PlocState* __restrict__ 
     for (uint32_t i = threadIdx.x / group; i < m; i += 1024u / group) {      // (uniform per wave: m and group are)
       float mine[6];
       for (int k = 0; k < 6; ++k) mine[k] = L.box[k][i];
-      float best = __builtin_inff(); int bj = 0x7FFFFFFF;
+      float best = __builtin_inff(); int bj = -1; uint64_t bk = ~0ull;
       const int lo = max((int)i - radius, 0), hi = min((int)i + radius, (int)m - 1);
       for (int j = lo + (int)(threadIdx.x % group); j <= hi; j += (int)group) {
         if (j == (int)i) continue;
         const float ex = fmaxf(mine[3], L.box[3][j]) - fminf(mine[0], L.box[0][j]), ey = fmaxf(mine[4], L.box[4][j]) - fminf(mine[1], L.box[1][j]), ez = fmaxf(mine[5], L.box[5][j]) - fminf(mine[2], L.box[2][j]);
         const float d = (ex * ey + ey * ez) + ez * ex;
-        if (d < best) { best = d; bj = j; }
+        const uint64_t k = plocPairKey((int)i, j);
+        if (plocCloser(d, k, best, bk)) { best = d; bj = j; bk = k; }
       }
-      for (uint32_t o = 1u; o < group; o <<= 1) {
+      for (uint32_t o = 1u; o < group; o <<= 1) {      // (the group shares i: the whole rank follows from the other lane's j)
         const float od = __shfl_xor(best, (int)o); const int oj = __shfl_xor(bj, (int)o);
-        if (od < best || (od == best && oj < bj)) { best = od; bj = oj; }
+        const uint64_t ok = plocPairKey((int)i, oj);
+        if (plocCloser(od, ok, best, bk)) { best = od; bj = oj; bk = ok; }
       }
-      if (threadIdx.x % group == 0u) L.nn[i] = bj == 0x7FFFFFFF ? -1 : bj;
+      if (threadIdx.x % group == 0u) L.nn[i] = bj;
     }
     __syncthreads();
     // flags, ranks and everything a surviving position needs, into registers (two positions per thread) ...

@@ -21,7 +21,11 @@ RT_DEV LaneRay toObject(float wox, float woy, float woz, float wdx, float wdy, f
   const float dx = (wdx * inv[0] + wdy * inv[4]) + wdz * inv[8];
   const float dy = (wdx * inv[1] + wdy * inv[5]) + wdz * inv[9];
   const float dz = (wdx * inv[2] + wdy * inv[6]) + wdz * inv[10];
-  r.ix = 1.0f / dx; r.iy = 1.0f / dy; r.iz = 1.0f / dz;
+  // A zero component gets NaN, not +-inf: slabTest's fminf / fmaxf then drop that axis (the ray stays in one plane of it).  With
+  // +-inf, a ray lying IN a face plane of a box -- (face - origin) = 0, 0 x inf = NaN on one side only -- came out as missing the
+  // box, and hits on that face were lost (axis-aligned rays along a flat grid's lines: tests/test_gpu_bvh_meshes.py).  Dropping the
+  // axis is conservative; the triangle test decides.
+  r.ix = dx != 0.0f ? 1.0f / dx : __builtin_nanf(""); r.iy = dy != 0.0f ? 1.0f / dy : __builtin_nanf(""); r.iz = dz != 0.0f ? 1.0f / dz : __builtin_nanf("");
   const float ax = fabsf(dx), ay = fabsf(dy), az = fabsf(dz);
   r.kz = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
   r.kx = (r.kz + 1) % 3; r.ky = (r.kx + 1) % 3;

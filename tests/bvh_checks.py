@@ -5,13 +5,22 @@ every parity test (both sides would walk the same broken tree), so every tree an
 import numpy as np
 
 
-def bvh_check(nodes_u32, tris_u32, root, num_tris):
+def bvh_check(nodes_u32, tris_u32, root, num_tris, verts=None, idx=None):
     """Binary tree (RTGGX_BUF_BVH_NODES*, 64-byte nodes: child-0 box min/max, child-1 box min/max, child refs at words 12, 13;
     ref >= 0: node, < 0: ~leaf slot) over the leaf triangles (RTGGX_BUF_BVH_TRIS*, 64 bytes: v0 v1 v2, primitive id at word 12).
     Asserts: every primitive in exactly one leaf slot, every leaf slot and every node reachable exactly once from the root, every
-    child box contains -- and is tight around -- everything below it.  Returns the depth of the deepest leaf."""
+    child box contains -- and is tight around -- everything below it.  Given the mesh (verts: [nv, 6] position + normal, idx: the index
+    buffer), also that every leaf record holds, bit for bit, the three vertices of its primitive: boxes tight around a wrong triangle
+    would pass the rest.  Returns the depth of the deepest leaf."""
     prims = tris_u32.reshape(-1, 16)[:, 12]
     assert prims.size == num_tris and np.array_equal(np.sort(prims), np.arange(num_tris, dtype=prims.dtype)), "every primitive in exactly one leaf"
+    if verts is not None:
+        pos = np.ascontiguousarray(np.asarray(verts, np.float32).reshape(-1, 6)[:, :3]).view(np.uint32)
+        tri_idx = np.asarray(idx, np.int64).reshape(-1, 3)
+        want = pos[tri_idx[prims.astype(np.int64)]].reshape(-1, 9)
+        got = tris_u32.reshape(-1, 16)[:, :9]
+        bad = np.nonzero((got != want).any(axis=1))[0]
+        assert bad.size == 0, "leaf slot %d (primitive %d) does not hold its primitive's vertices" % (bad[0], prims[bad[0]])
     if num_tris == 1:
         assert root == -1                                  # ~0: the root is the only leaf
         return 1

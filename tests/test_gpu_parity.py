@@ -71,13 +71,13 @@ class Pair:
 
     def give_oracle_the_device_trees(self, refitted=False):
         """The CPU re-traces the same BVH arrays the HIP kernels use -- after checking them: every primitive in exactly one
-        leaf, every box tight around what is below it, the 4-wide collapse equal to the binary tree and chosen by the surface-area
+        leaf with its own vertices (the oracle's copy of the mesh), every box tight around what is below it, the 4-wide collapse equal to the binary tree and chosen by the surface-area
         rule (tests/bvh_checks.py; refitted: the model's tree keeps the choice its build made for another shape)."""
         capi = self.capi
         for slot, (bn, bt, b4, btop, cap) in enumerate(((capi.BUF_BVH_NODES0, capi.BUF_BVH_TRIS0, capi.BUF_BVH4_NODES0, capi.BUF_BVH4_TOP0, 16),
                                                         (capi.BUF_BVH_NODES1, capi.BUF_BVH_TRIS1, capi.BUF_BVH4_NODES1, capi.BUF_BVH4_TOP1, 96))):
             nodes, tris, root = self.ctx.readback(bn), self.ctx.readback(bt), self.ctx.bvh_root(slot)
-            bvh_checks.bvh_check(nodes, tris, root, self.num_tris[slot])
+            bvh_checks.bvh_check(nodes, tris, root, self.num_tris[slot], *self.o.mesh(slot))
             nodes4 = self.ctx.readback(b4)
             bvh_checks.bvh4_check(nodes, nodes4, root, built_shape=not (refitted and slot == 1), weights=self.ctx.collapse_weights())
             bvh_checks.bvh4_top_check(nodes4, self.ctx.readback(btop), root, cap)
@@ -902,6 +902,9 @@ def test_c_abi_error_behaviour(built):
         with pytest.raises(capi.RtggxError, match="not writable"):
             ctx.upload(capi.BUF_TLAS, np.zeros((2, 4, 4), np.float32))
         assert L.rtggx_sync(None) == -1 and b"null context" in L.rtggx_last_error()
+        # one triangle more than a 24-bit primitive id can name (hit keys, visibility words): refused before anything is read or allocated
+        with pytest.raises(capi.RtggxError, match="24-bit primitive id"):
+            ctx.set_mesh(1, np.zeros((3, 6), np.float32), np.zeros(3 * ((1 << 24) + 1), np.uint32))
         # and the context is still usable afterwards
         ctx.set_mesh(1, np.array([[-1, 0, 0, 0, 0, 1], [1, 0, 0, 0, 0, 1], [0, 2, 0, 0, 0, 1]], np.float32), np.array([0, 1, 2], np.uint32))
         ctx.build_as(); ctx.sync()

@@ -331,6 +331,50 @@ def test_bvh_trace_equals_brute_force(built):
     assert not o.trace_rays(rays)["valid"].any()
 
 
+def test_deep_caterpillar_tree_walk_equals_brute_force(built):
+    """A binary tree far deeper than any the product's builder aims for, handed to the oracle through set_bvh: N triangles stacked
+    along the rays, node k = (leaf of triangle N - 1 - k, the subtree of the N - 1 - k nearer ones).  The subtree is always the nearer
+    child, so the walk pushes the leaf at every level before it tests a triangle: N - 1 entries on the stack at once.  The device
+    accepts trees up to 128 levels deep, and every one of them reaches this walk (tests/test_gpu_parity.py Pair)."""
+    import bvh_checks
+    N = 160
+    z = (1.0 + 0.5 * np.arange(N)).astype(np.float32)                   # triangle k in the plane z_k: k = 0 is the nearest
+    verts = np.zeros((3 * N, 6), np.float32)
+    verts[:, 5] = -1.0
+    verts[:, :2] = np.tile(np.array([[-40.0, -40.0], [40.0, -40.0], [0.0, 40.0]], np.float32), (N, 1))
+    verts[:, 2] = np.repeat(z, 3)
+    idx = np.arange(3 * N, dtype=np.uint32)
+    tris = np.zeros((N, 16), np.uint32)                                  # leaf slot s = triangle s
+    tris[:, :9] = verts[:, :3].reshape(N, 9).view(np.uint32)
+    tris[:, 9] = tris[:, 12] = np.arange(N, dtype=np.uint32)
+    tri_lo, tri_hi = verts[:, :3].reshape(N, 3, 3).min(axis=1), verts[:, :3].reshape(N, 3, 3).max(axis=1)
+    nodes = np.zeros((N - 1, 16), np.uint32)
+    f, ref = nodes.view(np.float32), nodes.view(np.int32)
+    for k in range(N - 1):
+        far, rest = N - 1 - k, N - 2 - k                                 # node k: triangle `far` and the subtree of triangles 0 .. rest
+        f[k, 0:3], f[k, 3:6] = tri_lo[far], tri_hi[far]
+        f[k, 6:9], f[k, 9:12] = tri_lo[:rest + 1].min(axis=0), tri_hi[:rest + 1].max(axis=0)
+        ref[k, 12] = ~far
+        ref[k, 13] = k + 1 if rest > 0 else ~0
+    assert bvh_checks.bvh_check(nodes, tris, 0, N, verts, idx) == N      # the deepest leaf has N - 1 ancestors
+    o = O.Oracle(16, 16, threads=1)
+    o.set_mesh(0, np.zeros((0, 6), np.float32), np.zeros(0, np.uint32))
+    o.set_mesh(1, verts, idx)
+    o.set_bvh(1, nodes, tris, 0)
+    rng = np.random.default_rng(5)
+    n = 256
+    org = np.concatenate([rng.uniform(-2, 2, (n, 2)), np.full((n, 1), -10.0)], 1)
+    dirs = np.concatenate([rng.uniform(-0.05, 0.05, (n, 2)), np.ones((n, 1))], 1)
+    rays = np.concatenate([org, dirs, np.full((n, 1), 1e-4), np.full((n, 1), 1e4)], 1).astype(np.float32)
+    rays[n // 2:, 6] = 10.0 + z[N // 3]                                  # (half of them start beyond the first N / 3 triangles)
+    walk, brute = o.trace_rays(rays), o.trace_rays(rays, brute=True)
+    assert brute["valid"].all()
+    for k in ("valid", "inst", "prim", "t", "b1", "b2"):
+        np.testing.assert_array_equal(walk[k], brute[k], err_msg=k)
+    assert (brute["prim"][:n // 2] == 0).all() and (brute["prim"][n // 2:] > N // 3).all()
+    o.close()
+
+
 def test_config_c1_single_triangle_constant_env(built):
     """BASELINE.json configs[0]: single triangle + constant environment, 256x256, 1 frame, CPU only."""
     W = H = 256
