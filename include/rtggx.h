@@ -189,6 +189,22 @@ int  rtggx_set_metallic(rtggx_context* ctx, uint32_t mesh, float metallic);
  * of VISIBLE normals (Heitz 2018), weight F G1(L): no sample is wasted below the horizon of the view direction, less variance at
  * grazing angles for the same one sample per pixel.  Takes effect with the next rtggx_update_frame. */
 int  rtggx_set_sampler(rtggx_context* ctx, int vndf);
+/* Ray rate: pixels per traced ray, 1 (default: every covered pixel traces its reflection ray, and its diffuse ray where metallic < 1 --
+ * DispatchRays(W,H,1) of the reference) or 4 (opt-in, no counterpart in the reference; DESIGN.md "Quarter-rate tracing"):
+ *   - traced pixel: with F = FrameIndex & 3 and o = {(0,0), (1,1), (1,0), (0,1)}[F], pixel (x, y) traces iff (x & 1, y & 1) == o --
+ *     every pixel once in any four consecutive frames (FrameIndex wraps at 256).  Its RayTracingOut0/1 words are bit-identical to the
+ *     full-rate frame's (same sample, ray and shading);
+ *   - at every pixel as at rate 1, bit for bit: visibility, depth, normal, rough/metal, velocity, and background pixels (environment
+ *     along -V, no ray);
+ *   - an untraced covered pixel c is reconstructed before the spatial filters from the traced pixels q at Chebyshev distance 1 that
+ *     are covered by c's instance: RayTracingOut0 = sum w L(q) / sum w with w = NormalWeight(nc, nq, 32) DepthWeight(zc, zq, 4)
+ *     RoughnessWeight(rc, rq, 0, 0.5) (FilterCommon.hlsli:34-47 on the G-buffer words); RayTracingOut1, where c's metallic < 1, with
+ *     w = NormalWeight(nc, nq, 32) DepthWeight(zc, zq, 4).  sum w = 0: the plain mean of those q; none: the plain mean of c's instance's
+ *     traced pixels within distance 2; none: 0.  Where metallic >= 1 RayTracingOut1 keeps what it held, as at rate 1;
+ *   - rtggx_ray_count / rtggx_ray_total count the rays traced.
+ * Whole frames only: rate 4 on a context with a strip (rtggx_set_strip), and a strip on a rate-4 context, are refused.  Takes effect
+ * from the next rtggx_render_visibility; synchronises. */
+int  rtggx_set_ray_rate(rtggx_context* ctx, uint32_t pixels_per_ray);
 
 /* Build of both bottom-level structures (RayTracer::buildAccelerationStructures / BuildAccelerationStructures, RayTracer.cpp:676-716,
  * 158-233; the sample records the builds on the GPU timeline and waits once, RayTracedGGX.cpp:236): every step of the build --

@@ -318,6 +318,7 @@ void rtggx_destroy(rtggx_context* c) {
 int rtggx_set_strip(rtggx_context* c, uint32_t rowBegin, uint32_t rowEnd) {
   RT_CHECK_CTX(c);
   if (rowBegin > rowEnd || rowEnd > c->H) { setError("rtggx_set_strip: bad rows [%u,%u) for height %u", rowBegin, rowEnd, c->H); return -1; }
+  if (c->rayRate != 1u && (rowBegin > 0u || rowEnd < c->H)) { setError("rtggx_set_strip: rows [%u,%u) of %u: a context tracing one pixel in %u renders whole frames", rowBegin, rowEnd, c->H, c->rayRate); return -1; }
   c->rowBegin = rowBegin; c->rowEnd = rowEnd; c->toneMapDone = false;
   return 0;
 }
@@ -422,6 +423,22 @@ int rtggx_set_async_compute(rtggx_context* c, int enable) {
   c->streamAS = c->asyncCompute ? c->ownAS : c->streamMain;
   c->streamVis = c->asyncCompute ? c->ownVis : nullptr;
   c->evVisStream = nullptr; c->genStream = nullptr; for (auto& f : c->genFrame) f = 0u;
+  return 0;
+}
+
+// Quarter-rate tracing (raytrace.hip rayGenKernel, reconstructKernel; DESIGN.md "Quarter-rate tracing").  Whole frames only: a strip's
+// apron rows and the exchanged history are not defined for it (yet).  A bin covers other pixels at the other rate, so what the adaptive
+// split knows about its bins -- the cost record, the demand that sizes the split list, the ray count behind the placement -- starts afresh.
+int rtggx_set_ray_rate(rtggx_context* c, uint32_t pixelsPerRay) {
+  RT_CHECK_CTX(c);
+  if (pixelsPerRay != 1u && pixelsPerRay != 4u) { setError("rtggx_set_ray_rate: %u pixels per ray: 1 or 4", pixelsPerRay); return -1; }
+  if (pixelsPerRay != 1u && (c->rowBegin > 0u || c->rowEnd < c->H)) { setError("rtggx_set_ray_rate: rate %u on a strip (rows [%u,%u) of %u): whole frames only", pixelsPerRay, c->rowBegin, c->rowEnd, c->H); return -1; }
+  if (pixelsPerRay == c->rayRate) return 0;
+  RT_HIP(syncStreams(c));
+  c->rayRate = pixelsPerRay;
+  for (auto b : c->binWorkBuf) RT_HIP(hipMemset(b, 0, (size_t)c->numBinsMax * 4));
+  RT_HIP(hipDeviceSynchronize());
+  c->splitDemand = 0u; c->rayCountersInFlight = false; c->lastFrameRays = 0xFFFFFFFFu; c->traceLaunches = 0u;
   return 0;
 }
 
@@ -847,8 +864,8 @@ int rtggx_ray_trace(rtggx_context* c) {
   // who carries RayTracingOut1 over from the previous set where this frame traces no diffuse ray (raytrace.hip launchShade): ray
   // generation, unless the previous frame's shading kernel wrote into that set's image -- then, once, ray generation waits for it
   // (one bubble in the pipeline), so that the previous set's image is final when it reads it
-  if (c->shadeWroteDiff && !P.diffuse && !c->lastFrameDiffuse && c->shadeStream) {
-    if (c->shadeStream != sGen) { RT_HIP(hipEventRecord(c->evRT, c->shadeStream)); RT_HIP(hipStreamWaitEvent(sGen, c->evRT, 0)); }
+  if (c->shadeWroteDiff && !P.diffuse && !c->lastFrameDiffuse && c->diffStream) {
+    if (c->diffStream != sGen) { RT_HIP(hipEventRecord(c->evRT, c->diffStream)); RT_HIP(hipStreamWaitEvent(sGen, c->evRT, 0)); }
     c->shadeWroteDiff = false;
   }
   c->lastFrameDiffuse = P.diffuse;
@@ -877,6 +894,13 @@ int rtggx_ray_trace(rtggx_context* c) {
     RT_HIP(hipStreamWaitEvent(c->streamMain, evDone, 0));
     if (!r) r = launchShade(c, fp, c->streamMain, c->attachEvents ? nullptr : c->evSetRead[c->setIndex]);
     c->shadeStream = c->streamMain;
+  }
+  // rate 4: the untraced pixels, on the main stream behind the hit shading (raytrace.hip reconstructKernel)
+  c->diffStream = c->shadeStream;
+  if (c->rayRate == 4u) {
+    if (!r) r = launchReconstruct(c, fp, c->streamMain);
+    if (!r && !c->attachEvents) RT_HIP(hipEventRecord(c->evSetRead[c->setIndex], c->streamMain));      // (it reads the set after the shading's event)
+    c->diffStream = c->streamMain;
   }
   // the main stream has now been given work that reads the current input set: that set may not be overwritten (four frames from now)
   // before evSetRead, which rides on the LAST kernel the main stream gets for this frame (settleSetRead)

@@ -30,6 +30,7 @@
 namespace rt {
 
 #define RT_PI 3.1415926535897f   // BRDFModels.hlsli:5
+#define RT_SGPR(v) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(v)))      // a workgroup-uniform value the compiler may have computed in vector registers
 
 // ---- environment (RayTracing.hlsl:167-180; D3D cube sampling restated) --------------
 struct EnvRef { const uint2* __restrict__ texels; uint32_t size, mips; const uint32_t* __restrict__ mipOffset; };
@@ -255,16 +256,74 @@ struct GenArgs {
 #ifndef RT_GEN_MIN_BLOCKS
 #define RT_GEN_MIN_BLOCKS 1
 #endif
+// Quarter-rate tracing (rtggx_set_ray_rate(ctx, 4); DESIGN.md "Quarter-rate tracing"): with F = FrameIndex & 3 a frame traces the pixel
+// o = {(0,0), (1,1), (1,0), (0,1)}[F] of every 2x2 quad, so that four consecutive frames trace every pixel once.
+RT_DEV bool quadTraced(uint32_t px, uint32_t py, uint32_t frameIndex) {
+  const uint32_t f = frameIndex & 3u;
+  return (px & 1u) == ((0x6u >> f) & 1u) && (py & 1u) == ((0xAu >> f) & 1u);
+}
+// Rate 4: the workgroup's rays into its one bin, reflection rays first, then diffuse rays, each in wave order; the adaptive split's
+// decision (rayGenKernel) once per bin.  At most 64 reflection rays (one per quad) and 64 diffuse rays: the bin's slots as at rate 1.
+RT_DEV void rayGenQuadBin(const GenArgs& A, bool wantRefl, bool wantDiff, const RayRec& rr, const RayRec& rd) {
+  __shared__ uint32_t waveRays[2][4];
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, bin = blockIdx.x;
+  const unsigned long long maskR = __ballot(wantRefl), maskD = __ballot(wantDiff), below = (1ull << lane) - 1ull;
+  if (lane == 0) { waveRays[0][wave] = (uint32_t)__popcll(maskR); waveRays[1][wave] = (uint32_t)__popcll(maskD); }
+  __syncthreads();
+  uint32_t baseR = 0u, baseD = 0u, nR = 0u, nD = 0u;
+  for (uint32_t k = 0; k < 4u; ++k) {
+    const uint32_t r = waveRays[0][k], d = waveRays[1][k];
+    if (k < wave) { baseR += r; baseD += d; }
+    nR += r; nD += d;
+  }
+  RayRec* dst = A.rays + (size_t)bin * A.binSlots;
+  HitKey* keys = A.hits + (size_t)bin * A.binSlots;
+  if (wantRefl) { const uint32_t k = baseR + (uint32_t)__popcll(maskR & below); dst[k] = rr; keys[k] = hitKey(RT_RAY_TMAX, 0xFFFFFFFFu); }
+  const uint32_t kD = nR + baseD + (uint32_t)__popcll(maskD & below);
+  if (wantDiff && kD < A.binSlots) { dst[kD] = rd; keys[kD] = hitKey(RT_RAY_TMAX, 0xFFFFFFFFu); }
+  if (threadIdx.x != 0) return;
+  const uint32_t nRaysInBin = min(nR + nD, A.binSlots);
+  uint32_t mark = 0u;
+  if (A.binWork != nullptr) {      // the adaptive split as in rayGenKernel<1>, for one bin
+    const uint32_t w = A.binWork[bin];
+    A.binWork[bin] = 0u;
+    uint32_t shift = 0u;
+    while (shift < A.splitMaxShift && (w >> shift) > A.splitWork) ++shift;
+    const uint32_t n = (shift || w > A.frontWork) ? 1u << shift : 0u;
+    if (n) {
+      const uint32_t base = atomicAdd(A.splitCount, n);
+      const bool fits = base + n <= A.splitCap;
+      for (uint32_t k = 0; k < n && base + k < A.splitCap; ++k) A.splitList[base + k] = fits ? ((shift << 28) | (k << 24) | bin) : 0xFFFFFFFFu;
+      mark = fits ? (shift << 1) | 1u : 0u;
+    }
+  }
+  A.binCount[bin] = nRaysInBin | (mark << 8);
+}
+// RATE 1: every covered pixel traces (the reference's DispatchRays(W,H,1)); workgroup b <-> 16x16 tile b, its wave w <-> bin 4b + w.
+// RATE 4: one pixel per quad traces, and the workgroup's (at most 64 + 64) rays go to ONE bin, compacted over its four waves through LDS,
+// so that the traversal's waves stay as full as at rate 1.  Workgroup b <-> bin b; four consecutive bins are the four 16x16 tiles of a
+// 32x32 tile (launchTrace gets the 32x32 grid).  A bin whose 16x16 tile lies outside the frame is written empty.
+template <int RATE>
 __global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) rayGenKernel(const FrameParams* __restrict__ fpp, GenArgs A) {
   const FrameParams& fp = *fpp;
   if (blockIdx.x == 0) A.frameRays[threadIdx.x] = 0u;
   if (blockIdx.x == 0 && threadIdx.x == 0 && A.visNext != nullptr) { *A.zeroNext0 = 0u; *A.zeroNext1 = 0u; }      // the next frame's large-triangle list, the next set's split list
   // 16x16 pixel tile per workgroup, 8x8 per wave: the 64 rays a wave appends are neighbours on screen
-  const uint32_t tile = blockIdx.x;
+  uint32_t tile = blockIdx.x;
+  if constexpr (RATE == 4) {
+    const uint32_t superX = (A.tilesX + 1u) >> 1, sup = blockIdx.x >> 2;
+    const uint32_t tx = (sup % superX) * 2u + (blockIdx.x & 1u), ty = (sup / superX) * 2u + ((blockIdx.x >> 1) & 1u);
+    tile = ty * A.tilesX + tx;
+    if (tx >= A.tilesX || tile >= A.numTiles) {      // (uniform)
+      if (threadIdx.x == 0) { A.binCount[blockIdx.x] = 0u; if (A.binWork != nullptr) A.binWork[blockIdx.x] = 0u; }
+      return;
+    }
+  }
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
   const uint32_t px = (tile % A.tilesX) * 16 + (wave & 1u) * 8 + (lane & 7u);
   const uint32_t py = A.rowBegin + (tile / A.tilesX) * 16 + (wave >> 1) * 8 + (lane >> 3);
   const bool inside = px < fp.W && py < A.rowEnd;
+  const bool traced = RATE == 1 || quadTraced(px, py, fp.g.FrameIndex);
   // (two scalar loads, one wait: as two vector loads in front of the kernel's first fetch they cost ray generation 10 us in the frame)
   uint32_t wordHere, wordNext;
   asm volatile("s_load_dword %0, %2, %4\n\ts_load_dword %1, %3, %4\n\ts_waitcnt lgkmcnt(0)" : "=&s"(wordHere), "=&s"(wordNext) : "s"(A.visDirty), "s"(A.visDirtyNext), "s"(tile * 4u) : "memory");
@@ -338,7 +397,7 @@ __global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) rayGenKernel(const Fra
       A.diffOut[pix] = c;
     } else {
       const uint32_t skip = (inst << 24) | prim;
-      {  // computeReflection depth 0 :424-484
+      if (traced) {  // computeReflection depth 0 :424-484 (an untraced pixel's RayTracingOut0 is reconstructed: reconstructKernel)
         const float a = rghMtl.x * rghMtl.x;
         const bool vndf = (fp.flags & RT_FLAG_VNDF) != 0u;      // uniform
         f3 Hh;
@@ -372,18 +431,21 @@ __global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) rayGenKernel(const Fra
         }
       }
       if (rghMtl.y < 1.0f) {   // :559-564, computeDiffuse depth 0 :486-535
-        const float cosTheta = 1.0f - 2.0f * xiY;
-        const float sinTheta = sqrtf(1.0f - cosTheta * cosTheta);
-        const f3 dir = normalize3(N + mk3(cosPhi * sinTheta, sinPhi * sinTheta, cosTheta));
-        wantDiff = true;
-        rd.ox = P.x; rd.oy = P.y; rd.oz = P.z;
-        rd.dx = dir.x; rd.dy = dir.y; rd.dz = dir.z;
-        rd.pixel = (uint32_t)pix; rd.skip = skip; rd.flags = 1u;
-        rd.wx = color.x * (1.0f - 0.04f); rd.wy = color.y * (1.0f - 0.04f); rd.wz = color.z * (1.0f - 0.04f);   // :532
+        if (traced) {
+          const float cosTheta = 1.0f - 2.0f * xiY;
+          const float sinTheta = sqrtf(1.0f - cosTheta * cosTheta);
+          const f3 dir = normalize3(N + mk3(cosPhi * sinTheta, sinPhi * sinTheta, cosTheta));
+          wantDiff = true;
+          rd.ox = P.x; rd.oy = P.y; rd.oz = P.z;
+          rd.dx = dir.x; rd.dy = dir.y; rd.dz = dir.z;
+          rd.pixel = (uint32_t)pix; rd.skip = skip; rd.flags = 1u;
+          rd.wx = color.x * (1.0f - 0.04f); rd.wy = color.y * (1.0f - 0.04f); rd.wz = color.z * (1.0f - 0.04f);   // :532
+        }
       } else if (A.diffPrev != nullptr) A.diffOut[pix] = A.diffPrev[pix];      // RayTracingOut1 keeps what it held: carried over from the previous frame's set, here or by shadeKernel (launchShade)
     }
   }
   if (clearNext && threadIdx.x == 0) A.visDirtyNextOut[tile] = 0u;      // (read above by this workgroup only)
+  if constexpr (RATE == 4) { rayGenQuadBin(A, wantRefl, wantDiff, rr, rd); return; }
 
   // wave-level compaction into this wave's own bin (rt_queue.h): reflection rays first, then diffuse rays
   const uint32_t bin = blockIdx.x * 4u + wave;
@@ -457,6 +519,20 @@ RT_DEV f3 reflectionDepth1(const EnvRef& env, f2 rghMtl, f3 N, f3 V, f3 color) {
   return e * envBRDFApprox(f0, rghMtl.x, NoV);
 }
 
+// Rate 4: workgroup b shades the four bins of 32x32 tile b (rayGenKernel), one per wave as at rate 1; its tile word is the OR of the words of
+// the 16x16 tiles in it.  RayTracingOut1 is carried over by reconstructKernel instead, which visits every covered pixel anyway.
+RT_DEV uint32_t quadTileWord(const uint32_t* words, uint32_t tile32, uint32_t tilesX, uint32_t tilesY) {
+  const uint32_t superX = (tilesX + 1u) >> 1, tx = (tile32 % superX) * 2u, ty = (tile32 / superX) * 2u;
+  const uint32_t i0 = ty * tilesX + tx;
+  const bool right = tx + 1u < tilesX, down = ty + 1u < tilesY;
+  const uint32_t i1 = right ? i0 + 1u : i0, i2 = down ? i0 + tilesX : i0, i3 = right && down ? i0 + tilesX + 1u : i0;
+  uint32_t a, b, c, d;
+  asm volatile("s_load_dword %0, %4, %5\n\ts_load_dword %1, %4, %6\n\ts_load_dword %2, %4, %7\n\ts_load_dword %3, %4, %8\n\ts_waitcnt lgkmcnt(0)"
+               : "=&s"(a), "=&s"(b), "=&s"(c), "=&s"(d)
+               : "s"(words), "s"(RT_SGPR(i0 * 4u)), "s"(RT_SGPR(i1 * 4u)), "s"(RT_SGPR(i2 * 4u)), "s"(RT_SGPR(i3 * 4u)) : "memory");
+  return a | b | c | d;
+}
+template <int RATE>
 __global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) shadeKernel(const FrameParams* __restrict__ fpp, ShadeArgs A) {
   const FrameParams& fp = *fpp;
   const EnvRef env{A.env, A.envSize, A.envMips, A.envMipOffset};
@@ -467,7 +543,8 @@ __global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) shadeKernel(const Fram
   // 0.185 -> 0.266 ms; one per tile behind a workgroup barrier: ray generation 80 -> 91 us, the frame +1.3 %.  profiles/r04_j_tile_words.txt)
   const uint32_t tile = blockIdx.x;
   { uint32_t word;      // three quarters of the bunny frame's workgroups leave here, after one scalar load (before: a vector load of the bin's count each)
-    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(word) : "s"(A.tileWords), "s"(tile * 4u) : "memory");
+    if constexpr (RATE == 1) asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(word) : "s"(A.tileWords), "s"(tile * 4u) : "memory");
+    else word = quadTileWord(A.tileWords, tile, A.tilesX, (A.rowEnd - A.rowBegin + 15u) / 16u);
     if (word == 0u) return; }
   const uint32_t bin = tile * 4u + (threadIdx.x >> 6);
   // Carry-over of RayTracingOut1.  The reference has ONE such texture and leaves it untouched where no diffuse ray is traced
@@ -475,7 +552,7 @@ __global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) shadeKernel(const Fram
   // input sets that is the word of the previous frame's set -- final only once that frame's shading has run, which is earlier
   // on THIS stream; ray generation (stream C, a frame ahead of this stream) must not read it.  The wave's bin is its 8x8 pixel
   // sub-tile, so it walks those pixels: covered by an instance with metallic >= 1 (carryMask bit per instance) -> copy.
-  if (A.carryMask != 0u) {
+  if (RATE == 1 && A.carryMask != 0u) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t px = (tile % A.tilesX) * 16u + (wave & 1u) * 8u + (lane & 7u);
     const uint32_t py = A.rowBegin + (tile / A.tilesX) * 16u + (wave >> 1) * 8u + (lane >> 3);
@@ -533,6 +610,101 @@ __global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) shadeKernel(const Fram
 }
 
 // =========================================================================================================
+// Kernel 4 (rate 4 only): reconstruction of the untraced pixels, in place (DESIGN.md "Quarter-rate tracing")
+// =========================================================================================================
+// It reads only traced pixels and writes only untraced covered ones, so RayTracingOut0/1 serve as input and output.  For an untraced covered
+// pixel c the candidates are the traced pixels q at Chebyshev distance 1, inside the frame, covered by c's instance (2 or 4 of them):
+//   RayTracingOut0 = sum w L(q) / sum w,  w = NormalWeight(nc, nq, 32) DepthWeight(zc, zq, 4) RoughnessWeight(rc, rq, 0, 0.5)
+//   RayTracingOut1 = the same with w = NormalWeight(nc, nq, 32) DepthWeight(zc, zq, 4) (DiffuseWeight), where c's metallic < 1
+// (FilterCommon.hlsli:34-47, SpatialFilter.hlsli:69-75) on the G-buffer words the filters read: normals 10-bit UNORM x 2 - 1, not
+// renormalised; D24 depth / (2^24 - 1); R8 roughness.  sum w = 0: the plain mean of the candidates; no candidate: the plain mean of c's
+// instance's traced pixels within Chebyshev distance 2; none: 0.  The normal weight's 32nd power is five squarings of the fp32 dot product
+// (its integer numerator is exact); the depth weight's exp and the final divisions are evaluated in fp64 and rounded once to fp32, i.e.
+// correctly rounded; everything else is fp32 without contraction (Makefile).  So tests/ray_rate_ref.py restates it bit for bit in numpy:
+// reconstructed values often lie next to a rounding tie of R11G11B10 (the mean of two codes), and an ulp of a weight would decide the side.
+// Where c's metallic >= 1 RayTracingOut1 is carried over from the previous set (carryMask), at traced pixels as well (the rate-1 rule).
+struct ReconArgs {
+  const unsigned long long* visDepth; const uint32_t* normal; const uint16_t* roughMetal; const uint32_t* depth32;
+  uint32_t* reflOut; uint32_t* diffOut;       // read at traced pixels, written at the others
+  const uint32_t* diffPrev; uint32_t carryMask, diffMask;      // bit per instance: metallic >= 1 (carry RayTracingOut1 over) / < 1 (reconstruct it)
+  const uint32_t* tileWords; uint32_t tilesX, rowBegin, rowEnd;
+};
+struct ReconTexel { float nx, ny, nz, depth, rough; };
+RT_DEV ReconTexel reconTexel(const ReconArgs& A, size_t i) {
+  const uint32_t n = A.normal[i];
+  ReconTexel t;
+  t.nx = (float)(2 * (int)(n & 1023u) - 1023); t.ny = (float)(2 * (int)((n >> 10) & 1023u) - 1023); t.nz = (float)(2 * (int)((n >> 20) & 1023u) - 1023);
+  t.depth = (float)A.depth32[i] * (1.0f / 16777215.0f);
+  t.rough = (float)(A.roughMetal[i] & 0xFFu) * (1.0f / 255.0f);
+  return t;
+}
+RT_DEV float reconNormalDepthWeight(const ReconTexel& c, const ReconTexel& q) {
+  const float I = (c.nx * q.nx + c.ny * q.ny) + c.nz * q.nz;            // integers below 2^24: exact
+  float x = fmaxf(I * (1.0f / 1046529.0f), 0.0f);                       // dot(nc, nq) = I / 1023^2, one rounding
+  x = x * x; x = x * x; x = x * x; x = x * x; x = x * x;                 // ^32
+  return x * (float)exp((double)(-fabsf(c.depth - q.depth) * c.depth * 4.0f));      // SIGMA_Z = 4; fp64: correctly rounded
+}
+RT_DEV f3 reconDivide(f3 s, float w) {      // correctly rounded (fp64 quotient, one rounding to fp32), whatever the fp32 division lowers to
+  const double d = (double)w;
+  return mk3((float)((double)s.x / d), (float)((double)s.y / d), (float)((double)s.z / d));
+}
+__global__ void __launch_bounds__(256) reconstructKernel(const FrameParams* __restrict__ fpp, ReconArgs A) {
+  const FrameParams& fp = *fpp;
+  const uint32_t tile = blockIdx.x;
+  { uint32_t word;      // a 16x16 tile of ray generation's grid: nothing drawn there, nothing to do
+    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(word) : "s"(A.tileWords), "s"(tile * 4u) : "memory");
+    if (word == 0u) return; }
+  const uint32_t W = fp.W;
+  const uint32_t px = (tile % A.tilesX) * 16u + (threadIdx.x & 15u), py = A.rowBegin + (tile / A.tilesX) * 16u + (threadIdx.x >> 4);
+  if (px >= W || py >= A.rowEnd) return;
+  const size_t pix = (size_t)py * W + px;
+  const uint32_t vis = (uint32_t)A.visDepth[pix];
+  if (vis == 0u) return;      // background: both images were written by ray generation
+  const uint32_t inst = (vis - 1u) >> 24;
+  if ((A.carryMask >> inst) & 1u) A.diffOut[pix] = A.diffPrev[pix];
+  const uint32_t f = fp.g.FrameIndex & 3u, ox = (0x6u >> f) & 1u, oy = (0xAu >> f) & 1u;
+  if ((px & 1u) == ox && (py & 1u) == oy) return;      // traced
+  const bool diffuse = ((A.diffMask >> inst) & 1u) != 0u;
+  const ReconTexel c = reconTexel(A, pix);
+  f3 sumR = mk3(0.0f, 0.0f, 0.0f), sumD = sumR, meanR = sumR, meanD = sumR;
+  float wR = 0.0f, wD = 0.0f;
+  uint32_t n = 0u;
+  for (int dy = -1; dy <= 1; ++dy)
+    for (int dx = -1; dx <= 1; ++dx) {
+      const int qx = (int)px + dx, qy = (int)py + dy;
+      if (qx < 0 || qy < 0 || qx >= (int)W || qy >= (int)fp.H || ((uint32_t)qx & 1u) != ox || ((uint32_t)qy & 1u) != oy) continue;
+      const size_t q = (size_t)qy * W + (uint32_t)qx;
+      const uint32_t vq = (uint32_t)A.visDepth[q];
+      if (vq == 0u || ((vq - 1u) >> 24) != inst) continue;
+      const ReconTexel t = reconTexel(A, q);
+      const float wnd = reconNormalDepthWeight(c, t);
+      const float ts = saturatef(fabsf(t.rough - c.rough) * 2.0f);
+      const float w = wnd * (1.0f - ts * ts * (3.0f - 2.0f * ts));
+      const f3 L = unpackR11G11B10F(A.reflOut[q]);
+      sumR = sumR + L * w; wR += w; meanR = meanR + L;
+      if (diffuse) { const f3 Ld = unpackR11G11B10F(A.diffOut[q]); sumD = sumD + Ld * wnd; wD += wnd; meanD = meanD + Ld; }
+      ++n;
+    }
+  if (n == 0u) {      // no candidate at distance 1: the traced pixels of c's instance within distance 2
+#pragma unroll 1
+    for (int dy = -2; dy <= 2; ++dy)
+#pragma unroll 1
+      for (int dx = -2; dx <= 2; ++dx) {
+        const int qx = (int)px + dx, qy = (int)py + dy;
+        if (qx < 0 || qy < 0 || qx >= (int)W || qy >= (int)fp.H || ((uint32_t)qx & 1u) != ox || ((uint32_t)qy & 1u) != oy) continue;
+        const size_t q = (size_t)qy * W + (uint32_t)qx;
+        const uint32_t vq = (uint32_t)A.visDepth[q];
+        if (vq == 0u || ((vq - 1u) >> 24) != inst) continue;
+        meanR = meanR + unpackR11G11B10F(A.reflOut[q]);
+        if (diffuse) meanD = meanD + unpackR11G11B10F(A.diffOut[q]);
+        ++n;
+      }
+  }
+  A.reflOut[pix] = packR11G11B10F(wR > 0.0f ? reconDivide(sumR, wR) : n ? reconDivide(meanR, (float)n) : meanR);
+  if (diffuse) A.diffOut[pix] = packR11G11B10F(wD > 0.0f ? reconDivide(sumD, wD) : n ? reconDivide(meanD, (float)n) : meanD);
+}
+
+// =========================================================================================================
 // host side
 // =========================================================================================================
 int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hipStream_t s, hipEvent_t done) {
@@ -540,6 +712,9 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
   passRows(fp, ROWS_GBUFFER, rb, re);
   if (re <= rb) return 0;
   const uint32_t tilesX = (fp.W + 15) / 16, tilesY = (re - rb + 15) / 16;
+  // rate 4 (rayGenKernel): one bin per 16x16 tile, numbered by 32x32 tile, and the traversal's grid of 32x32 tiles
+  const bool quad = c->rayRate == 4u;
+  const uint32_t quadX = (tilesX + 1u) / 2u, quadY = (tilesY + 1u) / 2u;
   if ((fp.mat.RoughMetals[0][1] < 1.0f || fp.mat.RoughMetals[1][1] < 1.0f) && c->binSlots < RT_BIN) {
     setError("rtggx_ray_trace: a material with metallic below 1 (a diffuse ray per pixel as well) but ray bins of %u slots: rtggx_update_frame sizes them", c->binSlots); return -1;
   }
@@ -551,7 +726,8 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
     auto& vc = c->visClearedAt[thenFrame % RT_VIS_RING]; vc.frame = thenFrame; vc.rows[0] = rb; vc.rows[1] = re;
     // the tiles' words (rtggx_context.h visDirtyBuf): usable where they were kept for these very rows
     if (c->traceShare > 0.93f) c->traversalBound = true; else if (c->traceShare < 0.89f) c->traversalBound = false;
-    G.visDirty = c->traceTileWords = c->tileWords(rb, re);
+    // (rate 4: the trace kernel's grid is of 32x32 tiles, which these words do not describe -- it is given words that are all ones)
+    G.visDirty = c->tileWords(rb, re); c->traceTileWords = quad ? c->visDirtyOnes : G.visDirty;
     auto& vn = c->visFlags[thenFrame % RT_VIS_RING];
     G.visDirtyNextOut = c->visDirtyBuf[thenFrame % RT_VIS_RING];
     G.visDirtyNext = c->useTileWords && !c->traversalBound && vn.rows[0] == rb && vn.rows[1] == re ? G.visDirtyNextOut : c->visDirtyOnes;
@@ -565,7 +741,8 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
   G.rays = (RayRec*)c->rayQueue; G.hits = (HitKey*)c->hitQueue; G.binCount = c->binCount; G.binSlots = c->binSlots; G.frameRays = c->rayCounter32;
   G.tilesX = tilesX; G.numTiles = tilesX * tilesY; G.rowBegin = rb; G.rowEnd = re;
   const uint32_t splitWork = c->splitWork, splitMaxShift = c->splitMaxShift;
-  const uint32_t sliceShift = chooseSliceShift(c, true, G.numTiles * 4u);
+  const uint32_t numBins = quad ? quadX * quadY * 4u : G.numTiles * 4u;
+  const uint32_t sliceShift = chooseSliceShift(c, true, numBins);
   // "wide" launches: few enough rays that the traversal does not fill the chip for long (trace.hip launchTrace, capi.hip rtggx_ray_trace)
   c->lastTraceSmall = c->forcePlacement >= 0 ? c->forcePlacement == 1 : (sliceShift > 0u || c->lastFrameRays < RT_WIDE_RAYS);
   const bool adaptive = splitWork != 0u && sliceShift == 0u;
@@ -577,8 +754,11 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
   G.frontWork = RT_SPLIT_FRONT < splitWork ? RT_SPLIT_FRONT : splitWork;
   G.splitWork = splitWork; G.splitMaxShift = splitMaxShift < 3u ? splitMaxShift : 3u; G.splitCap = splitCap < RT_SPLIT_CAP ? splitCap : RT_SPLIT_CAP;
   const hipEvent_t evGen = c->evGenRing[c->frameCounter & 3u];
-  if (sGen != s && c->attachEvents) hipExtLaunchKernelGGL(rayGenKernel, dim3(G.numTiles), dim3(256), 0, sGen, nullptr, evGen, 0, (const FrameParams*)(c->dParams + c->slot), G);
-  else hipLaunchKernelGGL(rayGenKernel, dim3(G.numTiles), dim3(256), 0, sGen, c->dParams + c->slot, G);
+  if (quad) {
+    if (sGen != s && c->attachEvents) hipExtLaunchKernelGGL(rayGenKernel<4>, dim3(numBins), dim3(256), 0, sGen, nullptr, evGen, 0, (const FrameParams*)(c->dParams + c->slot), G);
+    else hipLaunchKernelGGL(rayGenKernel<4>, dim3(numBins), dim3(256), 0, sGen, c->dParams + c->slot, G);
+  } else if (sGen != s && c->attachEvents) hipExtLaunchKernelGGL(rayGenKernel<1>, dim3(G.numTiles), dim3(256), 0, sGen, nullptr, evGen, 0, (const FrameParams*)(c->dParams + c->slot), G);
+  else hipLaunchKernelGGL(rayGenKernel<1>, dim3(G.numTiles), dim3(256), 0, sGen, c->dParams + c->slot, G);
   c->genFrame[c->frameCounter & 3u] = 0u; c->genStreamOf[c->frameCounter & 3u] = sGen;
   if (sGen != s) {      // ray generation on stream C, the traversal on stream B behind it
     if (!c->attachEvents) RT_HIP(hipEventRecord(evGen, sGen));
@@ -590,7 +770,7 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
   // a sampled frame: the event pair of the kernel ring rides on the dispatch (and `done` is recorded behind it)
   const bool attach = c->attachEvents;
   if (ring && !attach) hipEventRecord(c->kevBegin[c->kevCount], s);
-  { const int r = launchTrace(c, fp, s, G.numTiles * 4u, true, tilesX, tilesY, sliceShift, adaptive ? (int)G.splitCap : -1,
+  { const int r = launchTrace(c, fp, s, numBins, true, quad ? quadX : tilesX, quad ? quadY : tilesY, sliceShift, adaptive ? (int)G.splitCap : -1,
                               ring && attach ? c->kevBegin[c->kevCount] : nullptr, !attach ? nullptr : ring ? c->kevEnd[c->kevCount] : done); if (r) return r; }
   if (c->timing) hipEventRecord(c->tev[12], s);
   if (ring && !attach) hipEventRecord(c->kevEnd[c->kevCount], s);
@@ -614,15 +794,38 @@ int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent
   // again), and no dependency between the shading kernels of consecutive frames (capi.hip rtggx_ray_trace).
   if (c->genCarriesDiff) S.carryMask = 0u;
   S.tileWords = c->tileWords(rb, re);
+  const bool quad = c->rayRate == 4u;      // (rate 4: 32x32 tiles, and RayTracingOut1 is carried over by launchReconstruct)
+  const uint32_t grid = quad ? ((tilesX + 1u) / 2u) * ((re - rb + 31u) / 32u) : numTiles;
+  if (quad) S.carryMask = 0u;
   S.rays = (const RayRec*)c->rayQueue; S.hits = (const HitKey*)c->hitQueue; S.binCount = c->binCount; S.binSlots = c->binSlots;
   S.fat0 = c->mesh[0].fat; S.fat1 = c->mesh[1].fat;
   S.env = c->env.texels; S.envMipOffset = c->dEnvMipOffset; S.envSize = c->env.size; S.envMips = c->env.mips; S.sh = c->sh;
   S.reflOut = c->rtRefl; S.diffOut = c->rtDiff;
-  if (done && c->attachEvents) hipExtLaunchKernelGGL(shadeKernel, dim3(numTiles), dim3(256), 0, s, nullptr, done, 0, (const FrameParams*)(c->dParams + c->slot), S);
-  else {
-    hipLaunchKernelGGL(shadeKernel, dim3(numTiles), dim3(256), 0, s, c->dParams + c->slot, S);
+  if (done && c->attachEvents) {
+    if (quad) hipExtLaunchKernelGGL(shadeKernel<4>, dim3(grid), dim3(256), 0, s, nullptr, done, 0, (const FrameParams*)(c->dParams + c->slot), S);
+    else hipExtLaunchKernelGGL(shadeKernel<1>, dim3(numTiles), dim3(256), 0, s, nullptr, done, 0, (const FrameParams*)(c->dParams + c->slot), S);
+  } else {
+    if (quad) hipLaunchKernelGGL(shadeKernel<4>, dim3(grid), dim3(256), 0, s, c->dParams + c->slot, S);
+    else hipLaunchKernelGGL(shadeKernel<1>, dim3(numTiles), dim3(256), 0, s, c->dParams + c->slot, S);
     if (done) hipEventRecord(done, s);
   }
+  RT_HIP(hipGetLastError());
+  return 0;
+}
+
+int launchReconstruct(rtggx_context* c, const FrameParams& fp, hipStream_t s) {
+  uint32_t rb, re;
+  passRows(fp, ROWS_GBUFFER, rb, re);
+  if (re <= rb) return 0;
+  const uint32_t tilesX = (fp.W + 15) / 16, numTiles = tilesX * ((re - rb + 15) / 16);
+  ReconArgs R;
+  R.visDepth = c->visDepth; R.normal = c->normal; R.roughMetal = c->roughMetal; R.depth32 = c->depth32;
+  R.reflOut = c->rtRefl; R.diffOut = c->rtDiff;
+  R.diffPrev = c->rtDiffBuf[(c->setIndex + RT_SETS - 1u) % RT_SETS];
+  const uint32_t metal = (fp.mat.RoughMetals[0][1] >= 1.0f ? 1u : 0u) | (fp.mat.RoughMetals[1][1] >= 1.0f ? 2u : 0u);      // as launchShade's carryMask
+  R.carryMask = c->genCarriesDiff ? 0u : metal; R.diffMask = ~metal & 3u;
+  R.tileWords = c->tileWords(rb, re); R.tilesX = tilesX; R.rowBegin = rb; R.rowEnd = re;
+  hipLaunchKernelGGL(reconstructKernel, dim3(numTiles), dim3(256), 0, s, c->dParams + c->slot, R);
   RT_HIP(hipGetLastError());
   return 0;
 }

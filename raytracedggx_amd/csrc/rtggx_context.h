@@ -206,6 +206,7 @@ struct rtggx_context {
   bool externalStream = false;
 
   bool vndf = false;             // rtggx_set_sampler
+  uint32_t rayRate = 1;          // rtggx_set_ray_rate: pixels per traced ray, 1 or 4 (raytrace.hip rayGenKernel, reconstructKernel)
   float rebuildRatio = 1.2f; uint32_t rebuildSteps = 16;      // rtggx_set_refit_policy
   rt::MeshDev mesh[2];
   rt::EnvDev env;
@@ -294,6 +295,7 @@ struct rtggx_context {
   // RayTracingOut1 keeps what it held where no diffuse ray is traced: with several input sets, carried over from the previous set -- by ray
   // generation when the previous frame's shading kernel wrote nothing into that set (genCarriesDiff), else by the shading kernel (raytrace.hip)
   bool genCarriesDiff = false, shadeWroteDiff = false, lastFrameDiffuse = false;
+  hipStream_t diffStream = nullptr;      // the stream of the most recent frame's last writer of RayTracingOut1: the hit shading's, or at rate 4 the main stream (reconstruction)
   uint32_t numCUs = 256;
   // the trace kernel's workgroup size (full-size launches) and the time stamps it takes of itself (trace.hip): stamps = 3 x (start, end) + (sum of durations, latest start)
   uint32_t traceWaves = 12, traceWavesForced = 0; float traceShare = 0.0f; unsigned long long* traceStamps = nullptr; uint32_t traceStampLaunch = 0;
@@ -369,6 +371,7 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
 // kernel's own completion signal (hipExtLaunchKernelGGL) instead of a marker packet behind it: a marker costs its queue
 // 5-7 us, and the frame's two chains had four of them (rocprofv3 kernel trace, profiles/).
 int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent_t done = nullptr);      // hit / miss shading of the traced bins
+int launchReconstruct(rtggx_context* c, const FrameParams& fp, hipStream_t s);      // rate 4: the untraced pixels of RayTracingOut0/1, after the hit shading
 int launchTraceRays(rtggx_context* c, const FrameParams& fp, const float* dRays, uint32_t n, float* dOut, hipStream_t s);
 int launchDenoise(rtggx_context* c, const FrameParams& fp, int useLds, hipStream_t s, hipEvent_t done = nullptr, bool fuseToneMap = false);      // fuseToneMap: the last kernel also writes the back buffer
 int launchToneMap(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent_t done = nullptr);

@@ -67,6 +67,8 @@ void RayTracer::SetMetallic(uint32_t meshIdx, float metallic) { check(rtggx_set_
 
 void RayTracer::SetSampler(bool vndf) { check(rtggx_set_sampler(m_ctx, vndf ? 1 : 0), "rtggx_set_sampler"); }
 
+bool RayTracer::SetRayRate(uint32_t pixelsPerRay) { return check(rtggx_set_ray_rate(m_ctx, pixelsPerRay), "rtggx_set_ray_rate"); }
+
 void RayTracer::SetAsyncCompute(bool asyncCompute) { check(rtggx_set_async_compute(m_ctx, asyncCompute ? 1 : 0), "rtggx_set_async_compute"); }
 
 void RayTracer::UpdateFrame(uint8_t frameIndex, const xm::Float3& eyePt, const xm::Matrix& viewProj, float timeStep) {

@@ -40,6 +40,7 @@ class RayTracer {
   // submission order (its single command list, RayTracedGGX.cpp:513-556)
   void SetAsyncCompute(bool asyncCompute);
   void SetSampler(bool vndf);            // rtggx_set_sampler: visible-normal (Heitz 2018) sampling of the reflection lobe, opt-in (-vndf)
+  bool SetRayRate(uint32_t pixelsPerRay);   // rtggx_set_ray_rate: 1 (default) or 4 -- one pixel of each 2x2 quad traced per frame, the rest reconstructed (-rayrate)
   void UpdateFrame(uint8_t frameIndex, const xm::Float3& eyePt, const xm::Matrix& viewProj, float timeStep);
   void TransformSH();
   void Render(uint8_t frameIndex);
