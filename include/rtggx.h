@@ -205,6 +205,28 @@ int  rtggx_set_sampler(rtggx_context* ctx, int vndf);
  * Whole frames only: rate 4 on a context with a strip (rtggx_set_strip), and a strip on a rate-4 context, are refused.  Takes effect
  * from the next rtggx_render_visibility; synchronises. */
 int  rtggx_set_ray_rate(rtggx_context* ctx, uint32_t pixels_per_ray);
+/* Recursion depth (RayTracer::SetMaxRecursionDepth; RayTracer.cpp:605 and RayTracing.hlsl:11 fix it at 1): D levels of rays per path,
+ * 1 (default: the reference's renderer, bit for bit) to RTGGX_MAX_RECURSION_DEPTH; anything else is refused and the depth kept.  Depth D is
+ * the reference's shaders with the closest hits passing payload.RecursionDepth + 1 (DESIGN.md "Recursion depth").  For the reflection path
+ * and the diffuse path of a pixel:
+ *   - level 0 is the depth-1 frame's: the ray, its weight w0, the G-buffer, the background, NoL <= 0 -> 0;
+ *   - a level-d ray carries the throughput T_d: T_0 = w0, T_{d+1} = T_d * w_{d+1} per component (fp32); the pixel's word is
+ *     pack_r11g11b10(c * T) with c the value at the end of the path (the throughput is multiplied forward, not on the way back);
+ *   - a miss ends the path with c = environment(dir, level 0);
+ *   - a hit of a level-d ray with d + 1 == D ends it with the depth-1 shading: reflectionDepth1, or SH irradiance / pi x colour;
+ *   - a hit with d + 1 < D follows closestHitReflection / closestHitDiffuse (:571-614) at depth d + 1: a reflection-group ray whose
+ *     preset (colour x metallic of the surface it left) is <= 0 in every component ends with c = preset; else, with P = o + t dir (fp32,
+ *     per component), V = -dir and the surface's normal and material, metallic > 0.5: computeReflection with the PIXEL's xi
+ *     (getSampleParam(DispatchRaysIndex())) at every level, GGX or VNDF (rtggx_set_sampler), R = reflect(-V, H); NoL <= 0 ends the path
+ *     with c = 0, else a reflection-group ray from P along R (skip: the hit's (inst << 24) | prim; interval (1e-5, 1e4)) of weight
+ *     ((NoL F) vis) k, or F G1(L) with VNDF; otherwise computeDiffuse: a diffuse-group ray multiplies the colour by (1 - metallic) (:607),
+ *     and a diffuse-group ray along normalize(N + uniformSphere(xi)) follows with weight = that colour (no x 0.96 at depth >= 1, :532);
+ *   - the image a path writes, RayTracingOut0 or RayTracingOut1, is its level-0 ray's;
+ *   - rtggx_ray_count / rtggx_ray_total count the rays of every level, RtggxTimings.ray_trace covers every level, ray_trace_kernel is
+ *     the level-0 traversal.
+ * Works with quarter-rate tracing (only traced pixels start paths) and on strips.  Takes effect from the next rtggx_render_visibility. */
+#define RTGGX_MAX_RECURSION_DEPTH 4u
+int  rtggx_set_max_recursion_depth(rtggx_context* ctx, uint32_t depth);
 
 /* Build of both bottom-level structures (RayTracer::buildAccelerationStructures / BuildAccelerationStructures, RayTracer.cpp:676-716,
  * 158-233; the sample records the builds on the GPU timeline and waits once, RayTracedGGX.cpp:236): every step of the build --

@@ -442,6 +442,15 @@ int rtggx_set_ray_rate(rtggx_context* c, uint32_t pixelsPerRay) {
   return 0;
 }
 
+// Recursion depth (raytrace.hip launchShade; DESIGN.md "Recursion depth"): 1..4 levels of rays per path.  The levels after the first reuse
+// the frame's bins in place and its trace kernel; nothing is allocated.  Taken over by the next rtggx_render_visibility.
+int rtggx_set_max_recursion_depth(rtggx_context* c, uint32_t depth) {
+  RT_CHECK_CTX(c);
+  if (depth < 1u || depth > RTGGX_MAX_RECURSION_DEPTH) { setError("rtggx_set_max_recursion_depth: depth %u: 1 to %u", depth, RTGGX_MAX_RECURSION_DEPTH); return -1; }
+  c->depthRequested = depth;
+  return 0;
+}
+
 int rtggx_set_mesh(rtggx_context* c, uint32_t slot, const float* verts, uint32_t nv, const uint32_t* idx, uint32_t ni) {
   RT_CHECK_CTX(c);
   if (slot >= RTGGX_NUM_MESH || !verts || !idx || ni % 3 != 0) { setError("rtggx_set_mesh: bad arguments"); return -1; }
@@ -801,6 +810,7 @@ int rtggx_render_visibility(rtggx_context* c) {
   if (!c->shDone && c->env.texels) { const int r = projectSH(c, c->streamAS); if (r) return r; }   // first frame only, RayTracer.cpp:345-350
   settleSetRead(c);      // (the previous frame ended without the kernel that would have carried its set's event)
   ++c->frameCounter;
+  c->maxDepth = c->depthRequested;
   c->denoiseIssued = false; c->toneMapDone = false;
   c->selectSet((c->setIndex + 1u) % RT_SETS);
   // the set was last read four frames ago: normally long done; a host that has run further ahead than that waits here (also what makes

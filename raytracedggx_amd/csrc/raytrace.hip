@@ -189,6 +189,38 @@ RT_DEV f3 vndfHalfVector(f3 n, f3 v, float alpha, float cosPhi, float sinPhi, fl
   const f3 hl = normalize3(mk3(alpha * nh.x, alpha * nh.y, fmaxf(0.0f, nh.z)));
   return (xAxis * hl.x + yAxis * hl.y) + n * hl.z;
 }
+// computeReflection (:424-484) at a depth that traces (the shading pass that spawns rays, shadeKernel): the same arithmetic as ray
+// generation's depth-0 code -- which stays written out, so that its ISA is the one it was before recursion existed --: the half vector -- the reference's GGX NDF sample (computeDirectionGGX :92-101),
+// or VNDF with rtggx_set_sampler --, and, where NoL = dot(N, reflect(-V, H)) > 0, the ray's weight (:477)
+RT_DEV f3 reflectionHalfVector(bool vndf, f3 N, f3 V, float a, float cosPhi, float sinPhi, float xiY) {
+  if (vndf) return vndfHalfVector(N, V, a, cosPhi, sinPhi, xiY);
+  const float cosTheta = sqrtf((1.0f - xiY) / (1.0f + (a * a - 1.0f) * xiY));
+  const float sinTheta = sqrtf(1.0f - cosTheta * cosTheta);
+  return localToWorld(N, mk3(cosPhi * sinTheta, sinPhi * sinTheta, cosTheta));
+}
+RT_DEV f3 reflectionWeight(bool vndf, f3 N, f3 V, f3 Hh, float NoL, f2 rghMtl, f3 color) {
+  const float a = rghMtl.x * rghMtl.x;
+  const f3 f0 = mk3(lerpf(0.04f, color.x, rghMtl.y), lerpf(0.04f, color.y, rghMtl.y), lerpf(0.04f, color.z, rghMtl.y));
+  const float NoV = saturatef(dot3(N, V));
+  const float VoH = saturatef(dot3(V, Hh));
+  const f3 F = fSchlick(f0, VoH);
+  const float vis = visSmith(rghMtl.x, NoV, NoL);
+  const float NoH = saturatef(dot3(N, Hh));
+  const float k = 4.0f * VoH / NoH;
+  f3 w = mk3(((NoL * F.x) * vis) * k, ((NoL * F.y) * vis) * k, ((NoL * F.z) * vis) * k);
+  if (vndf) {      // BRDF x NoL / pdf of the visible-normal sampler = F x G2 / G1(V) = F x G1(L), with the separable Smith terms of Vis_Smith
+    const float a2 = a * a;
+    const float g1l = (2.0f * NoL) / (NoL + sqrtf(NoL * (NoL - NoL * a2) + a2));
+    w = mk3(F.x * g1l, F.y * g1l, F.z * g1l);
+  }
+  return w;
+}
+// computeDiffuse's ray (computeDirectionCos :150-162, the uniform-sphere branch), as in ray generation
+RT_DEV f3 diffuseDirection(f3 N, float cosPhi, float sinPhi, float xiY) {
+  const float cosTheta = 1.0f - 2.0f * xiY;
+  const float sinTheta = sqrtf(1.0f - cosTheta * cosTheta);
+  return normalize3(N + mk3(cosPhi * sinTheta, sinPhi * sinTheta, cosTheta));
+}
 struct Tri3 { f3 pos[3], nrm[3]; };
 RT_DEV Tri3 getVertices(const float4* __restrict__ fat, uint32_t prim) {   // :230-244, from the primitive's fat triangle (rtggx_context.h): five 16-byte loads, one dependent step
   const float4* p = fat + 5 * (size_t)prim;
@@ -503,7 +535,16 @@ struct ShadeArgs {
   // carry-over of RayTracingOut1 (see the kernel)
   const uint32_t* diffPrev; const unsigned long long* visDepth; uint32_t tilesX, rowBegin, rowEnd, carryMask;
   const uint32_t* tileWords;      // one word per tile of this kernel, 0 = nothing was drawn there (rtggx_context.h visDirtyBuf): no rays, nothing to carry
+  // the spawning pass (SHADE_SPAWN): each ray's child goes back into the ray's own bin, in place (the same arrays as rays / hits / binCount)
+  RayRec* spawnRays; HitKey* spawnHits; uint32_t* spawnCount; const float* cosSin;
 };
+
+// The shading passes of a path of recursion depth D (rtggx_set_max_recursion_depth; DESIGN.md "Recursion depth"): level d < D - 1 shades
+// its hits by spawning the next level's rays (SHADE_SPAWN), level D - 1 finishes every path (SHADE_FINAL at D = 1 -- the code of the depth-1
+// renderer, unchanged --, SHADE_FINAL_DEEP after it).  A path ends in the spawning pass where its ray misses, where a reflection-group
+// ray's preset is <= 0, and where NoL <= 0.  Ray flags: bit 0 the hit group (1: diffuse); bit 1 set where the image the path writes --
+// that of its level-0 ray's group -- differs from the group of the ray in hand (never at level 0).
+enum ShadePass { SHADE_FINAL = 0, SHADE_SPAWN = 1, SHADE_FINAL_DEEP = 2 };
 
 // computeReflection at recursion depth 1 (:424-484)
 RT_DEV f3 reflectionDepth1(const EnvRef& env, f2 rghMtl, f3 N, f3 V, f3 color) {
@@ -532,7 +573,7 @@ RT_DEV uint32_t quadTileWord(const uint32_t* words, uint32_t tile32, uint32_t ti
                : "s"(words), "s"(RT_SGPR(i0 * 4u)), "s"(RT_SGPR(i1 * 4u)), "s"(RT_SGPR(i2 * 4u)), "s"(RT_SGPR(i3 * 4u)) : "memory");
   return a | b | c | d;
 }
-template <int RATE>
+template <int RATE, int PASS>
 __global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) shadeKernel(const FrameParams* __restrict__ fpp, ShadeArgs A) {
   const FrameParams& fp = *fpp;
   const EnvRef env{A.env, A.envSize, A.envMips, A.envMipOffset};
@@ -563,6 +604,7 @@ __global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) shadeKernel(const Fram
     }
   }
   const uint32_t count = min(A.binCount[bin] & 0xFFu, A.binSlots);
+  uint32_t spawned = 0u;      // SHADE_SPAWN: children written to the front of the bin so far (a child's slot is never above its parent's)
   for (uint32_t i = threadIdx.x & 63u; i < count; i += 64u) {
     const size_t slot = (size_t)bin * A.binSlots + i;
     const float4* rp = reinterpret_cast<const float4*>(A.rays + slot);
@@ -575,6 +617,7 @@ __global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) shadeKernel(const Fram
     const bool diffuseGroup = (rc.z & 1u) != 0u;
     const uint32_t srcInst = rc.y >> 24;
     f3 col;
+    bool child = false; RayRec cr;      // SHADE_SPAWN: the path goes on with this ray
     if (hitId == 0xFFFFFFFFu) col = environmentLevel0(env, dir);   // missMain :620-625
     else {
       // payload preset = color * metallic of the surface the ray left (:456); closestHitReflection returns it untouched when <= 0 (:573)
@@ -596,17 +639,56 @@ __global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) shadeKernel(const Fram
         const f2 rm = getRoughMetal(fp.mat, hInst, a.UV);
         f3 color = mk3(fp.mat.BaseColors[hInst][0], fp.mat.BaseColors[hInst][1], fp.mat.BaseColors[hInst][2]);
         const f3 V = -dir;
-        if (rm.y > 0.5f) col = reflectionDepth1(env, rm, N, V, color);
-        else {
-          if (diffuseGroup) color = color * (1.0f - rm.y);                 // :607
-          const f3 irr = evaluateSHIrradiance(A.sh, N);                    // computeDiffuse depth 1 :513,532
-          col = mk3(irr.x / RT_PI, irr.y / RT_PI, irr.z / RT_PI) * color;
+        if constexpr (PASS != SHADE_SPAWN) {
+          if (rm.y > 0.5f) col = reflectionDepth1(env, rm, N, V, color);
+          else {
+            if (diffuseGroup) color = color * (1.0f - rm.y);                 // :607
+            const f3 irr = evaluateSHIrradiance(A.sh, N);                    // computeDiffuse depth 1 :513,532
+            col = mk3(irr.x / RT_PI, irr.y / RT_PI, irr.z / RT_PI) * color;
+          }
+        } else {
+          // the closest-hit shaders at depth d + 1 < D (:571-614): hitWorldPosition (:338-341), getSampleParam(DispatchRaysIndex()) -- the
+          // pixel's xi at every level --, then computeReflection / computeDiffuse up to their TraceRay
+          const f3 P = mk3(ra.x + ht * rb.x, ra.y + ht * rb.y, ra.z + ht * rb.z);
+          uint32_t s = rng(rc.x); s += fp.g.FrameIndex; s = rng(s); s %= 256u;
+          const float xiY = (float)(rng(s) & 0xffffu) / 65536.0f, cosPhi = A.cosSin[s], sinPhi = A.cosSin[256 + s];
+          const uint32_t toDiffImage = (rc.z ^ (rc.z >> 1)) & 1u;
+          f3 w, L;
+          if (rm.y > 0.5f) {
+            const bool vndf = (fp.flags & RT_FLAG_VNDF) != 0u;
+            const f3 Hh = reflectionHalfVector(vndf, N, V, rm.x * rm.x, cosPhi, sinPhi, xiY);
+            L = reflect3(-V, Hh);
+            const float NoL = dot3(N, L);
+            if (NoL <= 0.0f) col = mk3(0.0f, 0.0f, 0.0f);                // :459
+            else { w = reflectionWeight(vndf, N, V, Hh, NoL, rm, color); child = true; cr.flags = toDiffImage << 1; }
+          } else {
+            if (diffuseGroup) color = color * (1.0f - rm.y);                 // :607
+            L = diffuseDirection(N, cosPhi, sinPhi, xiY);
+            w = color; child = true; cr.flags = 1u | ((toDiffImage ^ 1u) << 1);      // no x (1 - 0.04) at depth >= 1 (:532)
+          }
+          if (child) {
+            cr.ox = P.x; cr.oy = P.y; cr.oz = P.z; cr.dx = L.x; cr.dy = L.y; cr.dz = L.z;
+            cr.pixel = rc.x; cr.skip = hitId;
+            cr.wx = rw.x * w.x; cr.wy = rw.y * w.y; cr.wz = rw.z * w.z;      // the path's throughput
+          }
         }
       }
     }
+    if constexpr (PASS == SHADE_SPAWN) {
+      // compaction into the bin, in place: this round's records have been read (and waited for) before any lane writes
+      const unsigned long long mask = __ballot(child);
+      if (child) {
+        const size_t k = (size_t)bin * A.binSlots + spawned + (uint32_t)__popcll(mask & ((1ull << (threadIdx.x & 63u)) - 1ull));
+        A.spawnRays[k] = cr; A.spawnHits[k] = hitKey(RT_RAY_TMAX, 0xFFFFFFFFu);
+      }
+      spawned += (uint32_t)__popcll(mask);
+      if (child) continue;
+    }
     const uint32_t packed = packR11G11B10F(mk3(col.x * rw.x, col.y * rw.y, col.z * rw.z));
-    if (diffuseGroup) A.diffOut[rc.x] = packed; else A.reflOut[rc.x] = packed;
+    const bool toDiff = PASS == SHADE_FINAL ? diffuseGroup : ((rc.z ^ (rc.z >> 1)) & 1u) != 0u;
+    if (toDiff) A.diffOut[rc.x] = packed; else A.reflOut[rc.x] = packed;
   }
+  if constexpr (PASS == SHADE_SPAWN) { if ((threadIdx.x & 63u) == 0u) A.spawnCount[bin] = spawned; }
 }
 
 // =========================================================================================================
@@ -770,7 +852,9 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
   // a sampled frame: the event pair of the kernel ring rides on the dispatch (and `done` is recorded behind it)
   const bool attach = c->attachEvents;
   if (ring && !attach) hipEventRecord(c->kevBegin[c->kevCount], s);
-  { const int r = launchTrace(c, fp, s, numBins, true, quad ? quadX : tilesX, quad ? quadY : tilesY, sliceShift, adaptive ? (int)G.splitCap : -1,
+  const TraceQueue q{G.rays, G.hits, G.binCount};
+  c->traceGrid[0] = numBins; c->traceGrid[1] = quad ? quadX : tilesX; c->traceGrid[2] = quad ? quadY : tilesY; c->traceGrid[3] = sliceShift;      // (the later levels' launches: launchShade)
+  { const int r = launchTrace(c, fp, s, q, numBins, true, quad ? quadX : tilesX, quad ? quadY : tilesY, sliceShift, adaptive ? (int)G.splitCap : -1,
                               ring && attach ? c->kevBegin[c->kevCount] : nullptr, !attach ? nullptr : ring ? c->kevEnd[c->kevCount] : done); if (r) return r; }
   if (c->timing) hipEventRecord(c->tev[12], s);
   if (ring && !attach) hipEventRecord(c->kevEnd[c->kevCount], s);
@@ -780,6 +864,8 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
   return 0;
 }
 
+// The shading of the frame's traced bins: at recursion depth D (rtggx_set_max_recursion_depth) D passes, each but the last spawning the next
+// level's rays into the bins they shade and tracing them with the trace kernel on this stream (ShadePass).  `done` rides on the last pass.
 int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent_t done) {
   uint32_t rb, re;
   passRows(fp, ROWS_GBUFFER, rb, re);
@@ -801,15 +887,44 @@ int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent
   S.fat0 = c->mesh[0].fat; S.fat1 = c->mesh[1].fat;
   S.env = c->env.texels; S.envMipOffset = c->dEnvMipOffset; S.envSize = c->env.size; S.envMips = c->env.mips; S.sh = c->sh;
   S.reflOut = c->rtRefl; S.diffOut = c->rtDiff;
-  if (done && c->attachEvents) {
-    if (quad) hipExtLaunchKernelGGL(shadeKernel<4>, dim3(grid), dim3(256), 0, s, nullptr, done, 0, (const FrameParams*)(c->dParams + c->slot), S);
-    else hipExtLaunchKernelGGL(shadeKernel<1>, dim3(numTiles), dim3(256), 0, s, nullptr, done, 0, (const FrameParams*)(c->dParams + c->slot), S);
-  } else {
-    if (quad) hipLaunchKernelGGL(shadeKernel<4>, dim3(grid), dim3(256), 0, s, c->dParams + c->slot, S);
-    else hipLaunchKernelGGL(shadeKernel<1>, dim3(numTiles), dim3(256), 0, s, c->dParams + c->slot, S);
-    if (done) hipEventRecord(done, s);
+  S.spawnRays = (RayRec*)c->rayQueue; S.spawnHits = (HitKey*)c->hitQueue; S.spawnCount = c->binCount; S.cosSin = c->cosSinTab;
+  const FrameParams* const dfp = c->dParams + c->slot;
+  const uint32_t depth = c->maxDepth;
+  // Levels 1.. run behind this stream's shading of the level before, beside the next frame's level-0 traversal (stream B): a part of the
+  // spill area of their own on the main stream; on a traversal stream (small launches, capi.hip) that stream's own, in stream order
+  const int spillPart = s == c->streamMain ? 2 : (int)c->traceSpillHalf;
+  for (uint32_t level = 0; level < depth; ++level) {
+    if (level > 0) {
+      const TraceQueue q{S.rays, S.spawnHits, S.binCount};
+      const int r = launchTrace(c, fp, s, q, c->traceGrid[0], true, c->traceGrid[1], c->traceGrid[2], c->traceGrid[3], -1, nullptr, nullptr, spillPart);
+      if (r) return r;
+      S.carryMask = 0u;      // (carried over once, by the first pass)
+    }
+    const bool last = level + 1u == depth;
+    const dim3 blocks(quad ? grid : numTiles);
+    if (!last) {
+      if (quad) hipLaunchKernelGGL((shadeKernel<4, SHADE_SPAWN>), blocks, dim3(256), 0, s, dfp, S);
+      else hipLaunchKernelGGL((shadeKernel<1, SHADE_SPAWN>), blocks, dim3(256), 0, s, dfp, S);
+    } else if (done && c->attachEvents) {
+      if (level == 0) {
+        if (quad) hipExtLaunchKernelGGL((shadeKernel<4, SHADE_FINAL>), blocks, dim3(256), 0, s, nullptr, done, 0, dfp, S);
+        else hipExtLaunchKernelGGL((shadeKernel<1, SHADE_FINAL>), blocks, dim3(256), 0, s, nullptr, done, 0, dfp, S);
+      } else {
+        if (quad) hipExtLaunchKernelGGL((shadeKernel<4, SHADE_FINAL_DEEP>), blocks, dim3(256), 0, s, nullptr, done, 0, dfp, S);
+        else hipExtLaunchKernelGGL((shadeKernel<1, SHADE_FINAL_DEEP>), blocks, dim3(256), 0, s, nullptr, done, 0, dfp, S);
+      }
+    } else {
+      if (level == 0) {
+        if (quad) hipLaunchKernelGGL((shadeKernel<4, SHADE_FINAL>), blocks, dim3(256), 0, s, dfp, S);
+        else hipLaunchKernelGGL((shadeKernel<1, SHADE_FINAL>), blocks, dim3(256), 0, s, dfp, S);
+      } else {
+        if (quad) hipLaunchKernelGGL((shadeKernel<4, SHADE_FINAL_DEEP>), blocks, dim3(256), 0, s, dfp, S);
+        else hipLaunchKernelGGL((shadeKernel<1, SHADE_FINAL_DEEP>), blocks, dim3(256), 0, s, dfp, S);
+      }
+      if (done) hipEventRecord(done, s);
+    }
+    RT_HIP(hipGetLastError());
   }
-  RT_HIP(hipGetLastError());
   return 0;
 }
 
@@ -872,7 +987,8 @@ int launchTraceRays(rtggx_context* c, const FrameParams& fp, const float* dRays,
   if (!c->testRayRange) RT_HIP(hipMalloc(&c->testRayRange, (size_t)c->numBinsMax * RT_BIN * sizeof(float2)));
   hipLaunchKernelGGL(fillTestQueue, dim3((n + 255) / 256), dim3(256), 0, s, dRays, n, c->binSlots, (RayRec*)c->rayQueue, (HitKey*)c->hitQueue, c->binCount, (float2*)c->testRayRange);
   c->traceRayRange = c->testRayRange;
-  { const int r = launchTrace(c, fp, s, numBins, false, 0u, 0u, chooseSliceShift(c, false, numBins), -1); c->traceRayRange = nullptr; if (r) return r; }
+  const TraceQueue q{(const RayRec*)c->rayQueue, (HitKey*)c->hitQueue, c->binCount};
+  { const int r = launchTrace(c, fp, s, q, numBins, false, 0u, 0u, chooseSliceShift(c, false, numBins), -1); c->traceRayRange = nullptr; if (r) return r; }
   hipLaunchKernelGGL(exportTestHits, dim3((n + 255) / 256), dim3(256), 0, s, c->dParams + c->slot, (const RayRec*)c->rayQueue, (const HitKey*)c->hitQueue, n,
                      (const float4*)c->mesh[0].fat, (const float4*)c->mesh[1].fat, dOut);
   RT_HIP(hipGetLastError());

@@ -67,8 +67,13 @@ RT_HD uint32_t hitKeyId(HitKey k) { return (uint32_t)k; }
 // the bins rayGenKernel marked (bits 8.. of binCount, c->splitList with room for splitCap waves) are traced by several
 // waves, and the kernel records what each bin cost (c->binWork) for the next frame's decision; -1: off.
 uint32_t chooseSliceShift(rtggx_context* c, bool countRays, uint32_t numBins);
-// start / stop (may be null): events attached to the kernel's dispatch (begin of execution / completion).
-int launchTrace(rtggx_context* c, const FrameParams& fp, hipStream_t s, uint32_t numBins, bool countRays, uint32_t tilesX, uint32_t tilesY, uint32_t sliceShift, int splitCap,
-                hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
+// start / stop (may be null): events attached to the kernel's dispatch (begin of execution / completion).  q: the bins (a frame's input
+// set, or the list of rtggx_trace_rays).  spillPart: -1 for a frame's level-0 traversal and for a list -- the part of the stack spill area
+// given by c->traceSpillHalf, the kernel's time stamps and the ray-counter read-backs --; 0..RT_SPILL_PARTS-1 for a later level of the
+// frame's paths (rtggx_set_max_recursion_depth): that part of the spill area, and none of the rest.
+struct TraceQueue { const RayRec* rays; HitKey* hits; const uint32_t* binCount; };
+#define RT_SPILL_PARTS 3u
+int launchTrace(rtggx_context* c, const FrameParams& fp, hipStream_t s, const TraceQueue& q, uint32_t numBins, bool countRays, uint32_t tilesX, uint32_t tilesY, uint32_t sliceShift,
+                int splitCap, hipEvent_t start = nullptr, hipEvent_t stop = nullptr, int spillPart = -1);
 
 }  // namespace rt

@@ -475,8 +475,9 @@ uint32_t chooseSliceShift(rtggx_context* c, bool countRays, uint32_t numBins) {
   return raysGuess < 25000u ? 3u : raysGuess < 60000u ? 2u : raysGuess < 110000u ? 1u : 0u;
 }
 
-int launchTrace(rtggx_context* c, const FrameParams& fp, hipStream_t s, uint32_t numBins, bool countRays, uint32_t tilesX, uint32_t tilesY, uint32_t sliceShift, int splitCap,
-                hipEvent_t start, hipEvent_t stop) {
+int launchTrace(rtggx_context* c, const FrameParams& fp, hipStream_t s, const TraceQueue& q, uint32_t numBins, bool countRays, uint32_t tilesX, uint32_t tilesY, uint32_t sliceShift,
+                int splitCap, hipEvent_t start, hipEvent_t stop, int spillPart) {
+  const bool deeper = spillPart >= 0;      // a later level of the frame's paths: shares no per-launch state with the next frame's level 0 (rt_queue.h)
   TraceArgs T;
   if (numBins == 0) return 0;
   if (numBins > c->numBinsMax) { setError("launchTrace: %u bins exceed the %u allocated", numBins, c->numBinsMax); return -1; }
@@ -487,8 +488,8 @@ int launchTrace(rtggx_context* c, const FrameParams& fp, hipStream_t s, uint32_t
   T.nodes1 = (const float4*)(have1 && c->mesh[1].nodes4 ? (const void*)c->mesh[1].nodes4 : c->dummyRecord);
   T.tris1 = (const float4*)(have1 ? (const void*)c->mesh[1].tris : c->dummyRecord);
   T.root0 = c->mesh[0].root; T.root1 = c->mesh[1].root; T.haveMesh0 = have0; T.haveMesh1 = have1;
-  T.rays = (const RayRec*)c->rayQueue; T.hits = (HitKey*)c->hitQueue; T.tRange = (const float2*)c->traceRayRange;
-  T.binCount = c->binCount; T.numBins = numBins; T.binSlots = c->binSlots;
+  T.rays = q.rays; T.hits = q.hits; T.tRange = (const float2*)c->traceRayRange;
+  T.binCount = q.binCount; T.numBins = numBins; T.binSlots = c->binSlots;
   // Stacks deeper than the LDS part spill to global memory; the built trees say how deep they can get (a 4-wide node leaves its other
   // entries behind: the build adds them up along every path, BuildResult::stack4).  The spill area belongs to the launch's WAVES, not to the bins
   // (round 3; per bin it was 2 x 20 entries x 32 640 bins x 2 KB = 2.7 GB for the bunny at 1080p, 4.3 GB for the dragon, four times
@@ -499,9 +500,11 @@ int launchTrace(rtggx_context* c, const FrameParams& fp, hipStream_t s, uint32_t
     RT_HIP(hipDeviceSynchronize());
     if (c->stackOverflow) { RT_HIP(hipFree(c->stackOverflow)); c->stackOverflow = nullptr; }
     c->spillEntries = deepest - RT_STACK;
-    RT_HIP(hipMalloc(&c->stackOverflow, (size_t)2 * c->spillEntries * RT_SPILL_WAVES * 64 * 4));      // twice: two traversals can be in flight (traceSpillHalf)
+    // three times: two level-0 traversals can be in flight (traceSpillHalf), and beside them the later levels of a frame's paths on the main stream
+    RT_HIP(hipMalloc(&c->stackOverflow, (size_t)RT_SPILL_PARTS * c->spillEntries * RT_SPILL_WAVES * 64 * 4));
   }
-  T.overflow = c->stackOverflow + (size_t)c->traceSpillHalf * c->spillEntries * RT_SPILL_WAVES * 64; T.rayTotals = c->rayCounter32; T.stats = c->rayCounterBuf + 1024; T.runTotals = c->rayCounter + 256;
+  T.overflow = c->stackOverflow + (size_t)(deeper ? (uint32_t)spillPart : c->traceSpillHalf) * c->spillEntries * RT_SPILL_WAVES * 64;
+  T.rayTotals = c->rayCounter32; T.stats = c->rayCounterBuf + 1024; T.runTotals = c->rayCounter + 256;
   T.spillStride = (size_t)RT_SPILL_WAVES * 64;
   T.countRowBegin = countRays ? fp.rowBegin : 0u; T.countRowEnd = countRays ? fp.rowEnd : 0u; T.width = fp.W;
 #ifdef RT_TRACE_STATS
@@ -529,7 +532,7 @@ int launchTrace(rtggx_context* c, const FrameParams& fp, hipStream_t s, uint32_t
   const uint32_t perCu = waves == 1u ? RT_SPILL_WAVES / 256u : 1u;      // single-wave workgroups: one per item, the dispatcher deals them -- up to RT_SPILL_WAVES of them (three times the
                                                                          // wave slots the chip offers this kernel); beyond that they take a second item, a third, ... (the loop in the kernel)
   if (waves == 1u) T.topCount0 = T.topCount1 = 0u;
-  T.stamps = waves == 1u ? nullptr : c->traceStamps; T.launch = c->traceStampLaunch++;      // (thousands of workgroups stamping one word would take longer than the launch)
+  T.stamps = waves == 1u || deeper ? nullptr : c->traceStamps; T.launch = deeper ? 0u : c->traceStampLaunch++;      // (thousands of workgroups stamping one word would take longer than the launch)
   // as many workgroups as stay resident, a multiple of 8 so that every XCD gets its share; fewer when there is less to do
   const uint32_t wanted = (T.totalItems + waves - 1u) / waves;
   uint32_t blocks = c->numCUs * perCu < wanted ? c->numCUs * perCu : wanted;
@@ -548,7 +551,7 @@ int launchTrace(rtggx_context* c, const FrameParams& fp, hipStream_t s, uint32_t
   }
 #undef RT_LAUNCH_TRACE
   const uint32_t counterMask = 15u;
-  if (countRays && !c->rayCountersInFlight && (c->traceLaunches < 8u || (c->traceLaunches & counterMask) == 0u)) {     // the first frames, then every 16th: ray counters and split demand, for later launches
+  if (countRays && !deeper && !c->rayCountersInFlight && (c->traceLaunches < 8u || (c->traceLaunches & counterMask) == 0u)) {     // the first frames, then every 16th: ray counters and split demand, for later launches
     RT_HIP(hipMemcpyAsync(c->hostRayCounters, c->rayCounter32, 256 * 4, hipMemcpyDeviceToHost, s));
     RT_HIP(hipMemcpyAsync(c->hostRayCounters + 256, c->splitCount, 4, hipMemcpyDeviceToHost, s));
     RT_HIP(hipMemcpyAsync(c->hostRayCounters + 258, c->traceStamps + 6, 16, hipMemcpyDeviceToHost, s)); c->traceSampleLaunch = c->traceLaunches;      // sum of the kernel's durations so far, start of this launch
@@ -559,7 +562,7 @@ int launchTrace(rtggx_context* c, const FrameParams& fp, hipStream_t s, uint32_t
     // whenever the copies happen to arrive on a host that runs three frames ahead.
     if (c->traceLaunches < RT_PRIME_LAUNCHES) RT_HIP(hipEventSynchronize(c->evRayCounters));
   }
-  if (countRays) ++c->traceLaunches;
+  if (countRays && !deeper) ++c->traceLaunches;
   RT_HIP(hipGetLastError());
   return 0;
 }

@@ -33,6 +33,7 @@ void RayTracedGGX::OnInit() {
   if (m_hasMetallicOverride) for (uint32_t i = 0; i < RayTracer::NUM_MESH; ++i) m_rayTracer->SetMetallic(i, m_metallics[i]);
   if (m_vndf) m_rayTracer->SetSampler(true);            // -vndf: visible-normal sampling of the reflection lobe (opt-in; the reference samples the NDF)
   if (m_rayRate != 1u && !m_rayTracer->SetRayRate(m_rayRate)) throw std::runtime_error("-rayrate: " + m_rayTracer->GetLastError());      // -rayrate 4: one ray per 2x2 quad (opt-in)
+  if (m_recursionDepth != 1u && !m_rayTracer->SetMaxRecursionDepth(m_recursionDepth)) throw std::runtime_error("-recursion: " + m_rayTracer->GetLastError());      // -recursion N: multi-bounce paths (opt-in)
   m_rayTracer->SetAsyncCompute(m_asyncCompute != 0);   // -sync: one stream, submission order (the sample's single command list)
 
   if (m_deformAmplitude != 0.0f) {       // key shapes of the breathing model: x and z displaced by a wave travelling up the y axis
@@ -192,7 +193,7 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
     return (arg[0] == '-' || arg[0] == '/') && lower(arg + 1) == lower(name);
   };
   // On POSIX an absolute path also starts with '/': such a token is a flag only when it names one.
-  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate"};
+  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "recursion"};
   const auto isFlagName = [&](const char* name) { for (const char* f : kFlags) if (lower(name) == f) return true; return false; };
   const auto hasNextArgValue = [&](int i) {
     if (i + 1 >= argc) return false;
@@ -220,6 +221,11 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
       const int rate = hasNextArgValue(i) ? std::atoi(argv[++i]) : 0;
       if (rate != 1 && rate != 4) throw std::runtime_error("-rayrate: 1 or 4 pixels per traced ray");
       m_rayRate = (uint32_t)rate;
+    }
+    else if (isArgMatched(i, "recursion")) {
+      const int depth = hasNextArgValue(i) ? std::atoi(argv[++i]) : 0;
+      if (depth < 1 || depth > (int)RTGGX_MAX_RECURSION_DEPTH) throw std::runtime_error("-recursion: 1 to 4 levels of rays per path");
+      m_recursionDepth = (uint32_t)depth;
     }
     else if (isArgMatched(i, "device")) { if (hasNextArgValue(i)) m_device = std::atoi(argv[++i]); }
     else if (isArgMatched(i, "dump")) { if (hasNextArgValue(i)) m_dumpPrefix = argv[++i]; }

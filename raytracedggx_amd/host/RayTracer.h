@@ -40,7 +40,8 @@ class RayTracer {
   // submission order (its single command list, RayTracedGGX.cpp:513-556)
   void SetAsyncCompute(bool asyncCompute);
   void SetSampler(bool vndf);            // rtggx_set_sampler: visible-normal (Heitz 2018) sampling of the reflection lobe, opt-in (-vndf)
-  bool SetRayRate(uint32_t pixelsPerRay);   // rtggx_set_ray_rate: 1 (default) or 4 -- one pixel of each 2x2 quad traced per frame, the rest reconstructed (-rayrate)
+  bool SetRayRate(uint32_t pixelsPerRay);
+  bool SetMaxRecursionDepth(uint32_t depth);   // rtggx_set_max_recursion_depth: 1 (default; RayTracer.cpp:605 SetMaxRecursionDepth(1)) to 4 levels of rays per path (-recursion)   // rtggx_set_ray_rate: 1 (default) or 4 -- one pixel of each 2x2 quad traced per frame, the rest reconstructed (-rayrate)
   void UpdateFrame(uint8_t frameIndex, const xm::Float3& eyePt, const xm::Matrix& viewProj, float timeStep);
   void TransformSH();
   void Render(uint8_t frameIndex);
