@@ -43,18 +43,6 @@ int uploadParams(rtggx_context* c, uint32_t slot, hipStream_t s) {
   RT_HIP(hipGetLastError());
   return 0;
 }
-int uploadScene(rtggx_context* c, hipStream_t s) {
-  Scene sc;
-  for (int i = 0; i < 2; ++i) { sc.verts[i] = c->mesh[i].verts; sc.idx[i] = c->mesh[i].indices; sc.nodes[i] = c->mesh[i].nodes; sc.tris[i] = c->mesh[i].tris; sc.root[i] = c->mesh[i].root; }
-  sc.env = c->env.texels; sc.envSize = c->env.size; sc.envMips = c->env.mips;
-  for (int m = 0; m < 16; ++m) sc.mipOffset[m] = c->env.mipOffset[m];
-  sc.sh = c->sh; sc.cosSin = c->cosSinTab;
-  RT_HIP(hipMemcpyAsync(c->dScene, &sc, sizeof sc, hipMemcpyHostToDevice, s));
-  RT_HIP(hipStreamSynchronize(s));
-  c->sceneDirty = false;
-  return 0;
-}
-
 // world -> object matrices of the two instances: general 4x4 inverse by cofactors in double,
 // rounded once (the software TLAS; DESIGN.md "TLAS").
 static void invert4x4(const float* a /*row-major*/, float* out) {
@@ -81,14 +69,15 @@ static void invert4x4(const float* a /*row-major*/, float* out) {
   for (int i = 0; i < 16; ++i) out[i] = (float)(inv[i] * rdet);
 }
 
-// The frames-in-flight fence (evSetRead[set]: the last reader of an input set has ended) rides on a kernel's completion signal, and a
+// The frames-in-flight fence (InputSet::evRead: the last reader of an input set has ended) rides on a kernel's completion signal, and a
 // kernel that carries an event leaves its queue idle for ~5 us behind it (profiles/r03_c_strip_chain.txt).  So it rides on the LAST
 // kernel the main stream gets for the frame: the fused temporal + tone-map kernel, or the tone map where that is a kernel of its own.
 // A frame that ends earlier -- the caller traces without denoising -- gets the event recorded explicitly by the next frame (settleSetRead).
 static void settleSetRead(rtggx_context* c) {
   if (c->setReadDeferred < 0) return;
-  hipEventRecord(c->evSetRead[c->setReadDeferred], c->streamMain);
-  c->setReadRecorded[c->setReadDeferred] = true; c->setReadDeferred = -1;
+  InputSet& set = c->sets[c->setReadDeferred];
+  hipEventRecord(set.evRead, c->streamMain);
+  set.readRecorded = true; c->setReadDeferred = -1;
 }
 static hipError_t syncStreams(rtggx_context* c) {
   hipError_t e = c->ownVis ? hipStreamSynchronize(c->ownVis) : hipSuccess;
@@ -152,7 +141,7 @@ static int setMeshImpl(rtggx_context* c, uint32_t slot, const float* verts, uint
     { const int r = buildFatTris(c, slot, 0, c->streamMain); if (r) return r; }
     RT_HIP(hipStreamSynchronize(c->streamMain));
   }
-  c->asBuilt = false; c->sceneDirty = true;
+  c->asBuilt = false;
   return 0;
 }
 
@@ -165,6 +154,108 @@ static const float kGroundVerts[24][6] = {   // RayTracer::createGroundMesh, Ray
   {-1, -1, 1, 0, 0, 1}, {1, -1, 1, 0, 0, 1}, {1, 1, 1, 0, 0, 1}, {-1, 1, 1, 0, 0, 1}};
 static const uint32_t kGroundIdx[36] = {3, 1, 0, 2, 1, 3, 6, 4, 5, 7, 4, 6, 11, 9, 8, 10, 9, 11,   // :477-496
                                         14, 12, 13, 15, 12, 14, 19, 17, 16, 18, 17, 19, 22, 20, 21, 23, 20, 22};
+
+// The buffers of input set i (rtggx_context.h InputSet) that it does not have yet: all of them at creation, the ray bins again after
+// growBins has freed them.  The G-buffer words and the traced images start cleared.
+static int allocSet(rtggx_context* c, uint32_t i) {
+  InputSet& s = c->sets[i];
+  const size_t n = (size_t)c->W * c->H, slots = (size_t)c->numBinsMax * c->binSlots;
+  for (uint32_t** p : {&s.normal, &s.depth32, &s.velocity, &s.rtRefl, &s.rtDiff}) if (!*p) { RT_HIP(hipMalloc(p, n * 4)); RT_HIP(hipMemset(*p, 0, n * 4)); }
+  if (!s.roughMetal) { RT_HIP(hipMalloc(&s.roughMetal, n * 2)); RT_HIP(hipMemset(s.roughMetal, 0, n * 2)); }
+  if (!s.rayQueue) RT_HIP(hipMalloc(&s.rayQueue, slots * sizeof(rt::RayRec)));
+  if (!s.hitQueue) RT_HIP(hipMalloc(&s.hitQueue, slots * 8));
+  if (!s.binCount) { RT_HIP(hipMalloc(&s.binCount, (size_t)c->numBinsMax * 4)); RT_HIP(hipMemset(s.binCount, 0, (size_t)c->numBinsMax * 4)); }
+  if (!s.splitList) RT_HIP(hipMalloc(&s.splitList, (size_t)RT_SPLIT_CAP * 4));
+  s.splitCount = c->largeCountBase + 2 + i;
+  if (!s.evRead) RT_HIP(hipEventCreateWithFlags(&s.evRead, RT_EVENT_FLAGS));
+  return 0;
+}
+static void freeSet(InputSet& s) {
+  for (void* p : {(void*)s.normal, (void*)s.depth32, (void*)s.velocity, (void*)s.rtRefl, (void*)s.rtDiff, (void*)s.roughMetal, s.rayQueue, s.hitQueue,
+                  (void*)s.binCount, (void*)s.splitList}) hipFree(p);
+  if (s.evRead) hipEventDestroy(s.evRead);
+  s = InputSet{};
+}
+
+// rtggx_create's work.  On failure it returns at once and leaves what it created to rtggx_destroy.
+static int initContext(rtggx_context* c, uint32_t width, uint32_t height, int device) {
+  c->device = device; c->W = width; c->H = height; c->rowBegin = 0; c->rowEnd = height;
+  const size_t n = (size_t)width * height;
+  // Streams and priorities (measured in rounds 1-3, profiles/r02_c_ab_pipeline.txt; the switches that chose between them are gone):
+  //   main  high   hit shading, spatial filters, temporal pass + tone map: the longest chain of the three, and the one the others slow down most
+  //   B     low    the traversal (one resident workgroup per CU)
+  //   C     low    visibility pass + ray generation of the next frame
+  //   R     middle vertex upload + tree refit of a deforming mesh; the traversals of odd frames where launches are small
+  int prioLeast = 0, prioGreatest = 0;
+  RT_HIP(hipDeviceGetStreamPriorityRange(&prioLeast, &prioGreatest));
+  const int prioMid = (prioLeast + prioGreatest) / 2;
+  RT_HIP(hipStreamCreateWithPriority(&c->ownMain, hipStreamNonBlocking, prioGreatest));
+  RT_HIP(hipStreamCreateWithPriority(&c->ownAS, hipStreamNonBlocking, prioLeast));
+  c->streamMain = c->ownMain; c->streamAS = c->ownAS;
+  RT_HIP(hipStreamCreateWithPriority(&c->ownVis, hipStreamNonBlocking, prioLeast)); c->streamVis = c->ownVis;
+  RT_HIP(hipStreamCreateWithPriority(&c->streamRefit, hipStreamNonBlocking, prioMid));
+  for (hipEvent_t* e : {&c->evVis, &c->evRefit, &c->evAS, &c->evRT}) RT_HIP(hipEventCreateWithFlags(e, RT_EVENT_FLAGS));
+  for (auto& f : c->frames) { RT_HIP(hipEventCreateWithFlags(&f.gen, RT_EVENT_FLAGS)); RT_HIP(hipEventCreateWithFlags(&f.trace, RT_EVENT_FLAGS)); }
+  for (auto& e : c->tev) RT_HIP(hipEventCreate(&e));
+  c->rebuildRatio = RT_REFIT_REBUILD_RATIO; c->rebuildSteps = RT_REBUILD_STEPS;      // rtggx_set_refit_policy
+  {
+    hipDeviceProp_t prop;
+    RT_HIP(hipGetDeviceProperties(&prop, device));
+    c->numCUs = prop.multiProcessorCount > 0 ? (uint32_t)prop.multiProcessorCount : 256u;
+  }
+  // one bin of 128 ray slots per 8x8 pixel sub-tile (4 per 16x16 tile): at most 2 rays per pixel
+  c->numBinsMax = ((width + 15) / 16) * ((height + 15) / 16) * 4u;
+  if (c->numBinsMax < 64u) c->numBinsMax = 64u;            // room for rtggx_trace_rays batches on tiny frames
+  c->binSlots = RT_BIN_MIN;      // (all-metal default materials: one ray per pixel; rtggx_update_frame grows the bins with the first metallic below 1)
+  c->largeCapacity = 1u << 16;
+  for (auto& b : c->largeTrisBuf) RT_HIP(hipMalloc(&b, (size_t)c->largeCapacity * 56));
+  RT_HIP(hipMalloc(&c->largeCountBase, 4 * (2 + RT_SETS))); RT_HIP(hipMemset(c->largeCountBase, 0, 4 * (2 + RT_SETS)));
+  for (uint32_t i = 0; i < RT_SETS; ++i) { const int r = allocSet(c, i); if (r) return r; }
+  { const size_t tiles = (size_t)((width + 15) / 16) * ((height + 15) / 16 + 1);      // (+ a row: a strip's tiles start at its first row)
+    for (auto& v : c->vis) {
+      RT_HIP(hipMalloc(&v.depth, n * 8)); RT_HIP(hipMemset(v.depth, 0, n * 8));
+      RT_HIP(hipMalloc(&v.dirty, tiles * 4)); RT_HIP(hipMemset(v.dirty, 0xFF, tiles * 4));
+    }
+    RT_HIP(hipMalloc(&c->visDirtyOnes, tiles * 4)); RT_HIP(hipMemset(c->visDirtyOnes, 0xFF, tiles * 4)); }
+  RT_HIP(hipMalloc(&c->backbuffer, n * 4));
+  RT_HIP(hipMalloc(&c->tss[0], n * 8)); RT_HIP(hipMalloc(&c->tss[1], n * 8)); RT_HIP(hipMalloc(&c->fltRfl, n * 8)); RT_HIP(hipMalloc(&c->fltDff, n * 8));
+  RT_HIP(hipMemset(c->backbuffer, 0, n * 4));
+  RT_HIP(hipMemset(c->tss[0], 0, n * 8)); RT_HIP(hipMemset(c->tss[1], 0, n * 8)); RT_HIP(hipMemset(c->fltRfl, 0, n * 8)); RT_HIP(hipMemset(c->fltDff, 0, n * 8));
+  RT_HIP(hipMalloc(&c->rayCounter, 512 * 8)); RT_HIP(hipMemset(c->rayCounter, 0, 512 * 8));
+  RT_HIP(hipMalloc(&c->rayCounterBuf, 1792 * 4)); RT_HIP(hipMemset(c->rayCounterBuf, 0, 1792 * 4));      // [4][256] per-frame counters + 768 statistics words
+  c->lastRayCounter32 = c->rayCounterBuf;
+  RT_HIP(hipMalloc(&c->traceStamps, 8 * 8)); RT_HIP(hipMemset(c->traceStamps, 0, 8 * 8));
+  RT_HIP(hipHostMalloc(&c->hostRayCounters, 264 * 4)); memset(c->hostRayCounters, 0, 264 * 4); RT_HIP(hipEventCreateWithFlags(&c->evRayCounters, hipEventDisableTiming));   // [0..255] rays; [256] split demand; [258..261] duration and period of a trace launch (two 64-bit words)
+  for (auto& b : c->binWorkBuf) { RT_HIP(hipMalloc(&b, (size_t)c->numBinsMax * 4)); RT_HIP(hipMemset(b, 0, (size_t)c->numBinsMax * 4)); }
+  c->selectSet(0);
+  c->splitWork = RT_SPLIT_WORK; c->splitMaxShift = RT_SPLIT_MAX_SHIFT;      // rtggx_debug_trace_split
+  RT_HIP(hipMalloc(&c->dEnvMipOffset, 16 * 4)); RT_HIP(hipMemset(c->dEnvMipOffset, 0, 16 * 4));
+  RT_HIP(hipMalloc(&c->dummyRecord, 128)); RT_HIP(hipMemset(c->dummyRecord, 0, 128));
+  RT_HIP(hipMalloc(&c->histReach, 4)); RT_HIP(hipMemset(c->histReach, 0, 4));
+  RT_HIP(hipMalloc(&c->exchangeTokens, 4 * 2 * RT_MAX_PEERS)); RT_HIP(hipMemset(c->exchangeTokens, 0, 4 * 2 * RT_MAX_PEERS));
+  RT_HIP(hipMalloc(&c->dPeerTable, sizeof(void*) * 2 * RT_MAX_PEERS + 4 * (RT_MAX_PEERS + 1))); RT_HIP(hipMemset(c->dPeerTable, 0, sizeof(void*) * 2 * RT_MAX_PEERS + 4 * (RT_MAX_PEERS + 1)));
+  RT_HIP(hipMalloc(&c->sh, 27 * 4)); RT_HIP(hipMemset(c->sh, 0, 27 * 4));
+  RT_HIP(hipMalloc(&c->cosSinTab, 512 * 4));
+  RT_HIP(hipMalloc(&c->dParams, RT_SLOTS * sizeof(FrameParams)));
+  {  // cos/sin(2*pi*s/256): double libm, rounded once (RayTracing.hlsl:94,100 with xi.x = s/256, :391)
+    float tab[512];
+    for (int s = 0; s < 256; ++s) { const double phi = 2.0 * 3.14159265358979323846 * (double)s / 256.0; tab[s] = (float)cos(phi); tab[256 + s] = (float)sin(phi); }
+    RT_HIP(hipMemcpy(c->cosSinTab, tab, sizeof tab, hipMemcpyHostToDevice));
+  }
+  // default materials, RayTracer.cpp:134-139
+  const float bc0[4] = {0.95f, 0.93f, 0.88f, 1.0f}, bc1[4] = {1.0f, 0.71f, 0.29f, 1.0f};
+  const float rm0[4] = {0.5f, 1.0f, 0.0f, 0.0f}, rm1[4] = {0.16f, 1.0f, 0.0f, 0.0f};
+  memcpy(c->material.BaseColors[0], bc0, 16); memcpy(c->material.BaseColors[1], bc1, 16);
+  memcpy(c->material.RoughMetals[0], rm0, 16); memcpy(c->material.RoughMetals[1], rm1, 16);
+  memset(c->invWorld, 0, sizeof c->invWorld);
+  for (int i = 0; i < 2; ++i) for (int k = 0; k < 4; ++k) c->invWorld[i][k * 5] = 1.0f;
+  memset(c->slots, 0, sizeof c->slots);
+  { const int r = setMeshImpl(c, RTGGX_GROUND, &kGroundVerts[0][0], 24, kGroundIdx, 36); if (r) return r; }
+  // hipMemset of device memory does not wait on the host, and the null stream it runs on is not ordered against this context's
+  // (non-blocking) streams: nothing of the first frame may overtake a clear
+  RT_HIP(hipStreamSynchronize(nullptr));
+  return 0;
+}
 }  // namespace rt
 
 using namespace rt;
@@ -182,136 +273,40 @@ int rtggx_create(rtggx_context** out, uint32_t width, uint32_t height, int devic
   if (device < 0 || device >= count) { setError("rtggx_create: device %d out of range (%d devices)", device, count); return -1; }
   RT_HIP(hipSetDevice(device));
   rtggx_context* c = new rtggx_context();
-  c->device = device; c->W = width; c->H = height; c->rowBegin = 0; c->rowEnd = height;
-  const size_t n = (size_t)width * height;
-  // Streams and priorities (measured in rounds 1-3, profiles/r02_c_ab_pipeline.txt; the switches that chose between them are gone):
-  //   main  high   hit shading, spatial filters, temporal pass + tone map: the longest chain of the three, and the one the others slow down most
-  //   B     low    the traversal (one resident workgroup per CU)
-  //   C     low    visibility pass + ray generation of the next frame
-  //   R     middle vertex upload + tree refit of a deforming mesh; the traversals of odd frames where launches are small
-  int prioLeast = 0, prioGreatest = 0;
-  RT_HIP(hipDeviceGetStreamPriorityRange(&prioLeast, &prioGreatest));
-  const int prioMid = (prioLeast + prioGreatest) / 2;
-  RT_HIP(hipStreamCreateWithPriority(&c->ownMain, hipStreamNonBlocking, prioGreatest));
-  RT_HIP(hipStreamCreateWithPriority(&c->ownAS, hipStreamNonBlocking, prioLeast));
-  c->streamMain = c->ownMain; c->streamAS = c->ownAS;
-  c->attachEvents = !(getenv("RTGGX_ATTACH_EVENTS") && atoi(getenv("RTGGX_ATTACH_EVENTS")) == 0);      // 0: marker packets (hipEventRecord) instead of events riding on kernels
-  RT_HIP(hipStreamCreateWithPriority(&c->ownVis, hipStreamNonBlocking, prioLeast)); c->streamVis = c->ownVis;
-  RT_HIP(hipEventCreateWithFlags(&c->evVis, RT_EVENT_FLAGS));
-  RT_HIP(hipEventCreateWithFlags(&c->evRefit, RT_EVENT_FLAGS));
-  for (auto& e : c->evGenRing) RT_HIP(hipEventCreateWithFlags(&e, RT_EVENT_FLAGS));
-  for (auto& e : c->evTraceRing) RT_HIP(hipEventCreateWithFlags(&e, RT_EVENT_FLAGS));
-  RT_HIP(hipStreamCreateWithPriority(&c->streamRefit, hipStreamNonBlocking, prioMid));
-  c->rebuildRatio = RT_REFIT_REBUILD_RATIO; c->rebuildSteps = RT_REBUILD_STEPS;      // rtggx_set_refit_policy
-  RT_HIP(hipEventCreateWithFlags(&c->evAS, RT_EVENT_FLAGS));
-  RT_HIP(hipEventCreateWithFlags(&c->evRT, RT_EVENT_FLAGS));
-  for (auto& e : c->evSetRead) RT_HIP(hipEventCreateWithFlags(&e, RT_EVENT_FLAGS));
-  for (auto& e : c->tev) RT_HIP(hipEventCreate(&e));
-  for (int i = 0; i < RT_SETS; ++i) {
-    RT_HIP(hipMalloc(&c->normalBuf[i], n * 4)); RT_HIP(hipMemset(c->normalBuf[i], 0, n * 4));
-    RT_HIP(hipMalloc(&c->depth32Buf[i], n * 4)); RT_HIP(hipMemset(c->depth32Buf[i], 0, n * 4));
-    RT_HIP(hipMalloc(&c->velocityBuf[i], n * 4)); RT_HIP(hipMemset(c->velocityBuf[i], 0, n * 4));
-    RT_HIP(hipMalloc(&c->rtReflBuf[i], n * 4)); RT_HIP(hipMemset(c->rtReflBuf[i], 0, n * 4));
-    RT_HIP(hipMalloc(&c->rtDiffBuf[i], n * 4)); RT_HIP(hipMemset(c->rtDiffBuf[i], 0, n * 4));
-    RT_HIP(hipMalloc(&c->roughMetalBuf[i], n * 2)); RT_HIP(hipMemset(c->roughMetalBuf[i], 0, n * 2));
-  }
-  for (auto& b : c->visDepthBuf) { RT_HIP(hipMalloc(&b, n * 8)); RT_HIP(hipMemset(b, 0, n * 8)); }
-  { const size_t tiles = (size_t)((width + 15) / 16) * ((height + 15) / 16 + 1);      // (+ a row: a strip's tiles start at its first row)
-    for (auto& b : c->visDirtyBuf) { RT_HIP(hipMalloc(&b, tiles * 4)); RT_HIP(hipMemset(b, 0xFF, tiles * 4)); }
-    RT_HIP(hipMalloc(&c->visDirtyOnes, tiles * 4)); RT_HIP(hipMemset(c->visDirtyOnes, 0xFF, tiles * 4)); }
-  c->selectSet(0);
-  RT_HIP(hipMalloc(&c->backbuffer, n * 4));
-  RT_HIP(hipMalloc(&c->tss[0], n * 8)); RT_HIP(hipMalloc(&c->tss[1], n * 8)); RT_HIP(hipMalloc(&c->fltRfl, n * 8)); RT_HIP(hipMalloc(&c->fltDff, n * 8));
-  RT_HIP(hipMemset(c->backbuffer, 0, n * 4));
-  RT_HIP(hipMemset(c->tss[0], 0, n * 8)); RT_HIP(hipMemset(c->tss[1], 0, n * 8)); RT_HIP(hipMemset(c->fltRfl, 0, n * 8)); RT_HIP(hipMemset(c->fltDff, 0, n * 8));
-  c->largeCapacity = 1u << 16;
-  for (auto& b : c->largeTrisBuf) RT_HIP(hipMalloc(&b, (size_t)c->largeCapacity * 56));
-  RT_HIP(hipMalloc(&c->largeCountBase, 4 * (2 + RT_SETS))); RT_HIP(hipMemset(c->largeCountBase, 0, 4 * (2 + RT_SETS)));
-  RT_HIP(hipMalloc(&c->rayCounter, 512 * 8)); RT_HIP(hipMemset(c->rayCounter, 0, 512 * 8));
-  RT_HIP(hipMalloc(&c->rayCounterBuf, 1792 * 4)); RT_HIP(hipMemset(c->rayCounterBuf, 0, 1792 * 4));      // [4][256] per-frame counters + 768 statistics words
-  c->rayCounter32 = c->lastRayCounter32 = c->rayCounterBuf;
-  RT_HIP(hipMalloc(&c->traceStamps, 8 * 8)); RT_HIP(hipMemset(c->traceStamps, 0, 8 * 8));
-  RT_HIP(hipHostMalloc(&c->hostRayCounters, 264 * 4)); memset(c->hostRayCounters, 0, 264 * 4); RT_HIP(hipEventCreateWithFlags(&c->evRayCounters, hipEventDisableTiming));   // [0..255] rays; [256] split demand; [258..261] duration and period of a trace launch (two 64-bit words)
-  {
-    hipDeviceProp_t prop;
-    RT_HIP(hipGetDeviceProperties(&prop, device));
-    c->numCUs = prop.multiProcessorCount > 0 ? (uint32_t)prop.multiProcessorCount : 256u;
-    // one bin of 128 ray slots per 8x8 pixel sub-tile (4 per 16x16 tile): at most 2 rays per pixel
-    const uint32_t tiles = ((width + 15) / 16) * ((height + 15) / 16);
-    c->numBinsMax = tiles * 4u;
-    if (c->numBinsMax < 64u) c->numBinsMax = 64u;            // room for rtggx_trace_rays batches on tiny frames
-    c->binSlots = RT_BIN_MIN;      // (all-metal default materials: one ray per pixel; rtggx_update_frame grows the bins with the first metallic below 1)
-    for (int i = 0; i < RT_SETS; ++i) {
-      RT_HIP(hipMalloc(&c->rayQueueBuf[i], (size_t)c->numBinsMax * c->binSlots * sizeof(rt::RayRec)));
-      RT_HIP(hipMalloc(&c->hitQueueBuf[i], (size_t)c->numBinsMax * c->binSlots * 8));
-      RT_HIP(hipMalloc(&c->binCountBuf[i], (size_t)c->numBinsMax * 4)); RT_HIP(hipMemset(c->binCountBuf[i], 0, (size_t)c->numBinsMax * 4));
-    }
-    c->selectSet(0);
-    for (auto& b : c->binWorkBuf) { RT_HIP(hipMalloc(&b, (size_t)c->numBinsMax * 4)); RT_HIP(hipMemset(b, 0, (size_t)c->numBinsMax * 4)); }
-    c->binWork = c->binWorkBuf[0];
-    for (int i = 0; i < RT_SETS; ++i) RT_HIP(hipMalloc(&c->splitListBuf[i], (size_t)RT_SPLIT_CAP * 4));
-    c->selectSet(0);
-    c->splitWork = RT_SPLIT_WORK; c->splitMaxShift = RT_SPLIT_MAX_SHIFT;      // rtggx_debug_trace_split
-    RT_HIP(hipMalloc(&c->dEnvMipOffset, 16 * 4)); RT_HIP(hipMemset(c->dEnvMipOffset, 0, 16 * 4));
-    RT_HIP(hipMalloc(&c->dummyRecord, 128)); RT_HIP(hipMemset(c->dummyRecord, 0, 128));
-  }
-  RT_HIP(hipMalloc(&c->histReach, 4)); RT_HIP(hipMemset(c->histReach, 0, 4));
-  RT_HIP(hipMalloc(&c->exchangeTokens, 4 * 2 * RT_MAX_PEERS)); RT_HIP(hipMemset(c->exchangeTokens, 0, 4 * 2 * RT_MAX_PEERS));
-  RT_HIP(hipMalloc(&c->dPeerTable, sizeof(void*) * 2 * RT_MAX_PEERS + 4 * (RT_MAX_PEERS + 1))); RT_HIP(hipMemset(c->dPeerTable, 0, sizeof(void*) * 2 * RT_MAX_PEERS + 4 * (RT_MAX_PEERS + 1)));
-  RT_HIP(hipMalloc(&c->sh, 27 * 4)); RT_HIP(hipMemset(c->sh, 0, 27 * 4));
-  RT_HIP(hipMalloc(&c->cosSinTab, 512 * 4));
-  RT_HIP(hipMalloc(&c->dParams, RT_SLOTS * sizeof(FrameParams)));
-  RT_HIP(hipMalloc(&c->dScene, sizeof(Scene)));
-  {  // cos/sin(2*pi*s/256): double libm, rounded once (RayTracing.hlsl:94,100 with xi.x = s/256, :391)
-    float tab[512];
-    for (int s = 0; s < 256; ++s) { const double phi = 2.0 * 3.14159265358979323846 * (double)s / 256.0; tab[s] = (float)cos(phi); tab[256 + s] = (float)sin(phi); }
-    RT_HIP(hipMemcpy(c->cosSinTab, tab, sizeof tab, hipMemcpyHostToDevice));
-  }
-  // default materials, RayTracer.cpp:134-139
-  const float bc0[4] = {0.95f, 0.93f, 0.88f, 1.0f}, bc1[4] = {1.0f, 0.71f, 0.29f, 1.0f};
-  const float rm0[4] = {0.5f, 1.0f, 0.0f, 0.0f}, rm1[4] = {0.16f, 1.0f, 0.0f, 0.0f};
-  memcpy(c->material.BaseColors[0], bc0, 16); memcpy(c->material.BaseColors[1], bc1, 16);
-  memcpy(c->material.RoughMetals[0], rm0, 16); memcpy(c->material.RoughMetals[1], rm1, 16);
-  memset(c->invWorld, 0, sizeof c->invWorld);
-  for (int i = 0; i < 2; ++i) for (int k = 0; k < 4; ++k) c->invWorld[i][k * 5] = 1.0f;
-  memset(c->slots, 0, sizeof c->slots);
-  const int r = setMeshImpl(c, RTGGX_GROUND, &kGroundVerts[0][0], 24, kGroundIdx, 36);
-  if (r) { return r; }
-  // hipMemset of device memory does not wait on the host, and the null stream it runs on is not ordered against this context's
-  // (non-blocking) streams: nothing of the first frame may overtake a clear
-  RT_HIP(hipStreamSynchronize(nullptr));
+  const int r = initContext(c, width, height, device);
+  if (r) { rtggx_destroy(c); return r; }      // (releases what was created)
   *out = c;
   return 0;
 }
 
+// Also the release of a partly created context (rtggx_create): every member may still be null.
 void rtggx_destroy(rtggx_context* c) {
   if (!c) return;
+  const auto destroyEvent = [](hipEvent_t e) { if (e) hipEventDestroy(e); };
+  const auto destroyStream = [](hipStream_t s) { if (s) hipStreamDestroy(s); };
   hipSetDevice(c->device);
   hipDeviceSynchronize();
   for (void* p : c->ipcMapped) hipIpcCloseMemHandle(p);
   hipFree(c->dPeerTable); hipFree(c->exchangeTokens);
   for (auto& m : c->mesh) {
     freeMeshVerts(m); freeBuildProducts(m);
-    hipFree(m.indices); hipFree(m.dCost); if (m.hCost) hipHostFree(m.hCost); if (m.evCost) hipEventDestroy(m.evCost);
+    hipFree(m.indices); hipFree(m.dCost); if (m.hCost) hipHostFree(m.hCost); destroyEvent(m.evCost);
   }
   hipFree(c->env.texels); hipFree(c->sh); hipFree(c->cosSinTab); hipFree(c->backbuffer);
-  for (auto b : c->visDepthBuf) hipFree(b);
-  for (auto b : c->visDirtyBuf) hipFree(b);
+  for (auto& s : c->sets) freeSet(s);
+  for (auto& v : c->vis) { hipFree(v.depth); hipFree(v.dirty); }
   hipFree(c->visDirtyOnes);
-  for (int i = 0; i < RT_SETS; ++i) { hipFree(c->depth32Buf[i]); hipFree(c->normalBuf[i]); hipFree(c->velocityBuf[i]); hipFree(c->rtReflBuf[i]); hipFree(c->rtDiffBuf[i]); hipFree(c->roughMetalBuf[i]); }
   hipFree(c->tss[0]); hipFree(c->tss[1]);
-  hipFree(c->fltRfl); hipFree(c->fltDff); hipFree(c->largeTrisBuf[0]); hipFree(c->largeTrisBuf[1]); hipFree(c->largeCountBase); hipFree(c->rayCounter); hipFree(c->dParams); hipFree(c->dScene);
-  for (int i = 0; i < RT_SETS; ++i) { hipFree(c->rayQueueBuf[i]); hipFree(c->hitQueueBuf[i]); hipFree(c->binCountBuf[i]); }
-  for (auto b : c->binWorkBuf) hipFree(b); for (int i = 0; i < RT_SETS; ++i) hipFree(c->splitListBuf[i]);
+  hipFree(c->fltRfl); hipFree(c->fltDff); hipFree(c->largeTrisBuf[0]); hipFree(c->largeTrisBuf[1]); hipFree(c->largeCountBase); hipFree(c->rayCounter); hipFree(c->dParams);
+  for (auto b : c->binWorkBuf) hipFree(b);
   hipFree(c->stackOverflow); hipFree(c->testRayRange); hipFree(c->dummyRecord); hipFree(c->histReach);
-  hipFree(c->dEnvMipOffset); hipFree(c->rayCounterBuf); hipFree(c->traceStamps); hipHostFree(c->hostRayCounters); hipEventDestroy(c->evRayCounters);
-  for (auto& e : c->kevBegin) hipEventDestroy(e);
-  for (auto& e : c->kevEnd) hipEventDestroy(e);
-  for (auto& e : c->tev) hipEventDestroy(e);
-  hipEventDestroy(c->evAS); hipEventDestroy(c->evRT); for (auto e : c->evSetRead) hipEventDestroy(e);
-  hipStreamDestroy(c->ownMain); hipStreamDestroy(c->ownAS); if (c->ownVis) hipStreamDestroy(c->ownVis);
-  hipEventDestroy(c->evVis); hipEventDestroy(c->evRefit); for (auto e : c->evGenRing) hipEventDestroy(e); for (auto e : c->evTraceRing) hipEventDestroy(e);
-  if (c->streamRefit) hipStreamDestroy(c->streamRefit);
+  hipFree(c->dEnvMipOffset); hipFree(c->rayCounterBuf); hipFree(c->traceStamps); if (c->hostRayCounters) hipHostFree(c->hostRayCounters); destroyEvent(c->evRayCounters);
+  for (auto e : c->kevBegin) destroyEvent(e);
+  for (auto e : c->kevEnd) destroyEvent(e);
+  for (auto e : c->tev) destroyEvent(e);
+  for (auto& f : c->frames) { destroyEvent(f.gen); destroyEvent(f.trace); }
+  destroyEvent(c->evAS); destroyEvent(c->evRT); destroyEvent(c->evVis); destroyEvent(c->evRefit);
+  destroyStream(c->ownMain); destroyStream(c->ownAS); destroyStream(c->ownVis); destroyStream(c->streamRefit);
   delete c;
 }
 
@@ -422,7 +417,7 @@ int rtggx_set_async_compute(rtggx_context* c, int enable) {
   c->asyncCompute = enable != 0;
   c->streamAS = c->asyncCompute ? c->ownAS : c->streamMain;
   c->streamVis = c->asyncCompute ? c->ownVis : nullptr;
-  c->evVisStream = nullptr; c->genStream = nullptr; for (auto& f : c->genFrame) f = 0u;
+  c->evVisStream = nullptr; for (auto& f : c->frames) f.genFrame = 0u;
   return 0;
 }
 
@@ -490,7 +485,7 @@ int rtggx_build_as(rtggx_context* c) {
   // that set's own vertices -- lbvh.hip buildLbvh; a rebuild in progress beside the frames is dropped)
   for (uint32_t i = 0; i < 2; ++i) { abandonRebuild(c, i); c->mesh[i].wantRebuild = false; const int r = buildLbvh(c, i, c->streamAS); if (r) return r; }
   c->selectSet(c->setIndex);
-  c->asBuilt = true; c->sceneDirty = true;
+  c->asBuilt = true;
   return 0;
 }
 
@@ -574,9 +569,19 @@ int rtggx_refit_as_device(rtggx_context* c, uint32_t slot, const float* dverts, 
   { const int r = beginDeforming(c, slot); if (r) return r; }
   MeshDev& m = c->mesh[slot];
   const size_t bytes = sizeof(float) * 6 * (size_t)nv;
-  if (!m.deviceStage[0]) {
-    for (auto& p : m.deviceStage) RT_HIP(hipMalloc(&p, bytes));
-    RT_HIP(hipEventCreateWithFlags(&m.evProduced, hipEventDisableTiming)); RT_HIP(hipEventCreateWithFlags(&m.evStaged, hipEventDisableTiming));
+  if (!m.deviceStage[0]) {      // the staging ring and its two events: all of them, or nothing half-done is left behind
+    float* st[RT_SLOTS] = {}; hipEvent_t produced = nullptr, staged = nullptr;
+    bool ok = true;
+    for (int i = 0; i < RT_SLOTS && ok; ++i) ok = hipMalloc(&st[i], bytes) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&produced, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&staged, hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+      for (auto p : st) hipFree(p);
+      if (produced) hipEventDestroy(produced);
+      if (staged) hipEventDestroy(staged);
+      setError("rtggx_refit_as_device: out of memory for the staging ring of mesh %u", slot); return -2;
+    }
+    for (int i = 0; i < RT_SLOTS; ++i) m.deviceStage[i] = st[i];
+    m.evProduced = produced; m.evStaged = staged;
   }
   pollTreeCost(c, m);
   const hipStream_t s = c->asyncCompute ? c->streamRefit : c->streamMain, producer = (hipStream_t)stream;
@@ -683,14 +688,10 @@ static int issueRebuildSteps(rtggx_context* c) {
 // the first such frame (the frames in flight are waited for: the old bins are theirs).
 static int growBins(rtggx_context* c) {
   RT_HIP(syncStreams(c));
-  for (int i = 0; i < RT_SETS; ++i) {
-    RT_HIP(hipFree(c->rayQueueBuf[i])); RT_HIP(hipFree(c->hitQueueBuf[i])); c->rayQueueBuf[i] = c->hitQueueBuf[i] = nullptr;
-    RT_HIP(hipMalloc(&c->rayQueueBuf[i], (size_t)c->numBinsMax * RT_BIN * sizeof(rt::RayRec)));
-    RT_HIP(hipMalloc(&c->hitQueueBuf[i], (size_t)c->numBinsMax * RT_BIN * 8));
-  }
-  if (c->testRayRange) { RT_HIP(hipFree(c->testRayRange)); c->testRayRange = nullptr; }
+  for (auto& set : c->sets) { RT_HIP(hipFree(set.rayQueue)); RT_HIP(hipFree(set.hitQueue)); set.rayQueue = set.hitQueue = nullptr; }
   c->binSlots = RT_BIN;
-  c->selectSet(c->setIndex);
+  for (uint32_t i = 0; i < RT_SETS; ++i) { const int r = allocSet(c, i); if (r) return r; }      // (the bins, at the new size)
+  if (c->testRayRange) { RT_HIP(hipFree(c->testRayRange)); c->testRayRange = nullptr; }
   return 0;
 }
 int rtggx_update_frame(rtggx_context* c, const RtggxFrameConstants* k) {
@@ -723,7 +724,6 @@ int rtggx_update_as(rtggx_context* c) {
   // the visibility pass has then carried this slot to the device with the PREVIOUS frame's TLAS.  Mark it stale, so that
   // rtggx_ray_trace (ensureParams) sends it again, behind the visibility pass, before anything reads invWorld.
   c->slotUploaded = false;
-  if (c->sceneDirty) { const int r = uploadScene(c, c->streamAS); if (r) return r; }
   // The constants (with the refreshed TLAS) ride to the device with the first kernel of the visibility pass, which
   // follows on stream B (rtggx_render_visibility); a caller that traces without a visibility pass gets them through
   // ensureParams.  In timing mode they are uploaded here, so that the pass has a duration of its own.
@@ -750,13 +750,13 @@ int rtggx_transform_sh(rtggx_context* c) {
 // is a latency-bound chain of dependent gathers: profiles/r02_*_limiter.txt), so the three overlap; what each stage hands to the next
 // exists four times (the input sets), and the events are
 //     evVis                  visibility f        -> ray generation f           (R -> C; stream order where both are on C)
-//     evGenRing[f & 3]       ray generation f    -> traversal f                (C -> B)
+//     frameEvents(f).gen     ray generation f    -> traversal f                (C -> B)
 //                            ray generation f    -> visibility f + 2           (C -> R: the target and the list it cleared)
-//     evTraceRing[f & 3]     traversal f         -> shading f                  (B -> main)
+//     frameEvents(f).trace   traversal f         -> shading f                  (B -> main)
 //                            traversal f - 2     -> ray generation f           (B -> C: the bins' cost record and the ray counters
 //                                                                               exist twice, by frame parity)
 //     evRefit                refit f             -> visibility f, traversal f  (R -> C, B)
-//     evSetRead[set]         last reader of a set -> the HOST, four frames later (the sample's frames-in-flight fence)
+//     sets[set].evRead       last reader of a set -> the HOST, four frames later (the sample's frames-in-flight fence)
 // rtggx_set_async_compute(0) (the sample's [A] toggle) puts everything on the main stream.
 //
 // WHERE a frame's kernels go is decided in ONE place, placeFrame, from a key of five facts (round 4: rounds 2-3 had grown nine
@@ -789,16 +789,16 @@ static Placement placeFrame(const rtggx_context* c, const FrameParams& fp, uint3
   P.raster = P.gen;
   P.alternate = async && c->streamRefit != nullptr && P.small && !P.deforming && (frame & 1u) != 0u;
   P.trace = !async ? c->streamMain : P.alternate ? c->streamRefit : c->streamAS;
-  P.shadeWithTrace = async && c->attachEvents && !c->timing && P.small && !P.deforming;
+  P.shadeWithTrace = async && !c->timing && P.small && !P.deforming;
   P.shade = P.shadeWithTrace ? P.trace : c->streamMain;
   P.framesInFlight = async && !P.small && (P.deforming || P.diffuse) ? RT_SETS - 1u : RT_SETS;
   return P;
 }
 
-static int waitForSet(rtggx_context* c, uint32_t set) {
-  if (c->setReadRecorded[set] && hipEventQuery(c->evSetRead[set]) != hipSuccess) {
+static int waitForSet(rtggx_context* c, const InputSet& set) {
+  if (set.readRecorded && hipEventQuery(set.evRead) != hipSuccess) {
     const auto t0 = std::chrono::steady_clock::now();
-    RT_HIP(hipEventSynchronize(c->evSetRead[set]));
+    RT_HIP(hipEventSynchronize(set.evRead));
     c->fenceWaitUs += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); ++c->fenceWaits;      // rtggx_debug_fence_wait
   }
   return 0;
@@ -812,21 +812,21 @@ int rtggx_render_visibility(rtggx_context* c) {
   ++c->frameCounter;
   c->maxDepth = c->depthRequested;
   c->denoiseIssued = false; c->toneMapDone = false;
-  c->selectSet((c->setIndex + 1u) % RT_SETS);
+  c->selectSet(c->setAhead(1u));
   // the set was last read four frames ago: normally long done; a host that has run further ahead than that waits here (also what makes
   // it safe for this frame's ray generation to clear the NEXT frame's visibility target: rtggx_context.h RT_VIS_RING)
-  { const int r = waitForSet(c, c->setIndex); if (r) return r; }
+  { const int r = waitForSet(c, c->cur()); if (r) return r; }
   const Placement P = placeFrame(c, c->slots[c->slot], c->frameCounter);
   // THREE frames in flight where the table says so: the host also waits for the end of frame f - 3 (profiles/r03_i_deform_states.txt:
   // with four, the deforming bunny at 1080p ran at 0.212-0.219 or 0.26-0.30 ms per frame, a run fell into one state; with three 0.220-0.238)
-  if (P.framesInFlight < RT_SETS) { const int r = waitForSet(c, (c->setIndex + RT_SETS - P.framesInFlight) % RT_SETS); if (r) return r; }
+  if (P.framesInFlight < RT_SETS) { const int r = waitForSet(c, c->sets[c->setAhead(RT_SETS - P.framesInFlight)]); if (r) return r; }
   c->refitIssued = false;
   { const int r = issuePendingRefits(c, &c->refitIssued); if (r) return r; }
   const hipStream_t s = P.raster;
   if (c->evVisStream && c->evVisStream != s) RT_HIP(hipStreamWaitEvent(s, c->evVis, 0));      // the previous pass ran on another stream
   // this frame's target and list of large triangles were cleared by the ray generation two frames back: on another stream, mostly
-  { const uint32_t k = (c->frameCounter + 2u) & 3u;
-    if (c->frameCounter >= 2u && c->genFrame[k] == c->frameCounter - 2u && c->genStreamOf[k] != s) RT_HIP(hipStreamWaitEvent(s, c->evGenRing[k], 0)); }
+  { const FrameEvents& g = c->frameEvents(c->frameCounter + 2u);
+    if (c->frameCounter >= 2u && g.genFrame == c->frameCounter - 2u && g.genStream != s) RT_HIP(hipStreamWaitEvent(s, g.gen, 0)); }
   // constants already on their way on stream B (timing mode uploads them in rtggx_update_as): the pass reads dParams[slot] and has to be
   // ordered behind that upload (evAS); on stream B it follows it anyway
   if (c->slotUploaded && s != c->streamAS) RT_HIP(hipStreamWaitEvent(s, c->evAS, 0));
@@ -835,7 +835,6 @@ int rtggx_render_visibility(rtggx_context* c) {
   int r = launchVisibility(c, c->slots[c->slot], s, c->streamVis ? c->evVis : nullptr);
   if (c->streamVis) c->evVisStream = s;
   if (c->timing) hipEventRecord(c->tev[13], s);
-  c->genStream = P.gen;
   if (!r) r = issueRebuildSteps(c);
   return r;
 }
@@ -844,7 +843,6 @@ int rtggx_ray_trace(rtggx_context* c) {
   RT_CHECK_CTX(c);
   if (!c->haveConstants || !c->asBuilt) { setError("rtggx_ray_trace: %s", c->asBuilt ? "no frame constants" : "rtggx_build_as has not been called"); return -1; }
   if (!c->env.texels) { setError("rtggx_ray_trace: no environment map"); return -1; }
-  if (c->sceneDirty) { const int r = uploadScene(c, c->streamAS); if (r) return r; }
   { const int r = ensureParams(c); if (r) return r; }
   const uint32_t f = c->frameCounter;
   const FrameParams& fp = c->slots[c->slot];
@@ -863,13 +861,13 @@ int rtggx_ray_trace(rtggx_context* c) {
   c->traceSpillHalf = P.alternate ? 1u : 0u;
   if (sGen != sTrace) {
     // ray generation reads the cost record of the traversal two frames back and resets that frame's ray counters (frame parity)
-    if (c->traceRecorded[(f + 2u) & 3u]) RT_HIP(hipStreamWaitEvent(sGen, c->evTraceRing[(f + 2u) & 3u], 0));
+    if (c->frameEvents(f + 2u).traceRecorded) RT_HIP(hipStreamWaitEvent(sGen, c->frameEvents(f + 2u).trace, 0));
     // a caller that skipped the visibility pass (or uploaded constants on stream B): order ray generation behind the upload
     if (c->slotUploaded) RT_HIP(hipStreamWaitEvent(sGen, c->evAS, 0));
   }
   if (c->refitIssued && c->asyncCompute) RT_HIP(hipStreamWaitEvent(sTrace, c->evRefit, 0));      // this set's tree
   if (c->timing) hipEventRecord(c->tev[3], sGen);
-  hipEvent_t evDone = c->evTraceRing[f & 3u];
+  FrameEvents& ev = c->frameEvents(f);
   const bool shadeWithTrace = P.shadeWithTrace && sGen != sTrace && sTrace != c->streamMain;
   // who carries RayTracingOut1 over from the previous set where this frame traces no diffuse ray (raytrace.hip launchShade): ray
   // generation, unless the previous frame's shading kernel wrote into that set's image -- then, once, ray generation waits for it
@@ -880,8 +878,8 @@ int rtggx_ray_trace(rtggx_context* c) {
   }
   c->lastFrameDiffuse = P.diffuse;
   c->genCarriesDiff = !c->shadeWroteDiff;
-  int r = launchRayTrace(c, fp, sGen, sTrace, shadeWithTrace ? nullptr : evDone);
-  c->traceRecorded[f & 3u] = true;
+  int r = launchRayTrace(c, fp, sGen, sTrace, shadeWithTrace ? nullptr : ev.trace);
+  ev.traceRecorded = true;
   c->lastRayCounter32 = c->rayCounter32;
   c->shadeWroteDiff = !c->genCarriesDiff || P.diffuse;
   if (shadeWithTrace) {
@@ -892,29 +890,28 @@ int rtggx_ray_trace(rtggx_context* c) {
     // f - 1, which the other traversal stream's shading kernel wrote, or the main stream's if this is the first frame shaded here.
     if (!c->genCarriesDiff && c->shadeStream && c->shadeStream != sTrace) {
       if (c->shadeStream == c->streamMain) { RT_HIP(hipEventRecord(c->evRT, c->streamMain)); RT_HIP(hipStreamWaitEvent(sTrace, c->evRT, 0)); }
-      else if (c->traceRecorded[(f + 3u) & 3u]) RT_HIP(hipStreamWaitEvent(sTrace, c->evTraceRing[(f + 3u) & 3u], 0));
+      else if (c->frameEvents(f + 3u).traceRecorded) RT_HIP(hipStreamWaitEvent(sTrace, c->frameEvents(f + 3u).trace, 0));
     }
-    if (!r) r = launchShade(c, fp, sTrace, evDone);
+    if (!r) r = launchShade(c, fp, sTrace, ev.trace);
     c->shadeStream = sTrace;
-    RT_HIP(hipStreamWaitEvent(c->streamMain, evDone, 0));
+    RT_HIP(hipStreamWaitEvent(c->streamMain, ev.trace, 0));
   } else {
     // stream B runs ahead with the traversal; shading and the denoiser consume the bins, the G-buffer and the traced images on the main
     // stream (the event completes with the trace kernel; a shading kernel of the frame before on a traversal stream has been waited for
     // by the main stream in its own frame)
-    RT_HIP(hipStreamWaitEvent(c->streamMain, evDone, 0));
-    if (!r) r = launchShade(c, fp, c->streamMain, c->attachEvents ? nullptr : c->evSetRead[c->setIndex]);
+    RT_HIP(hipStreamWaitEvent(c->streamMain, ev.trace, 0));
+    if (!r) r = launchShade(c, fp, c->streamMain);
     c->shadeStream = c->streamMain;
   }
   // rate 4: the untraced pixels, on the main stream behind the hit shading (raytrace.hip reconstructKernel)
   c->diffStream = c->shadeStream;
   if (c->rayRate == 4u) {
     if (!r) r = launchReconstruct(c, fp, c->streamMain);
-    if (!r && !c->attachEvents) RT_HIP(hipEventRecord(c->evSetRead[c->setIndex], c->streamMain));      // (it reads the set after the shading's event)
     c->diffStream = c->streamMain;
   }
   // the main stream has now been given work that reads the current input set: that set may not be overwritten (four frames from now)
-  // before evSetRead, which rides on the LAST kernel the main stream gets for this frame (settleSetRead)
-  if (c->attachEvents) c->setReadDeferred = (int)c->setIndex; else { c->setReadRecorded[c->setIndex] = true; c->setReadDeferred = -1; }
+  // before its evRead, which rides on the LAST kernel the main stream gets for this frame (settleSetRead)
+  c->setReadDeferred = (int)c->setIndex;
   if (c->timing) hipEventRecord(c->tev[14], c->streamMain);
   return r;
 }
@@ -931,9 +928,9 @@ int rtggx_denoise(rtggx_context* c, int useSharedMem) {
   // generation later than four small ones do (1080p 0.186 -> 0.204 ms; 512 threads: 0.199).  So it follows the placement's `small`; not in
   // the per-pass timing mode (the tone map keeps a duration of its own); rtggx_debug_fuse_tone_map pins it either way.
   const bool fuse = !c->timing && (c->fuseToneMap > 0 || (c->fuseToneMap < 0 && c->lastTraceSmall));
-  const bool carry = fuse || !c->attachEvents;      // the frame's last kernel on this stream carries the set's event; else the tone map will
-  const int r = launchDenoise(c, c->slots[c->slot], useSharedMem, c->streamMain, carry ? c->evSetRead[c->setIndex] : nullptr, fuse);
-  if (carry) { c->setReadRecorded[c->setIndex] = true; c->setReadDeferred = -1; } else c->setReadDeferred = (int)c->setIndex;
+  // the fused kernel is the frame's last on this stream and carries the set's event; else the tone map will
+  const int r = launchDenoise(c, c->slots[c->slot], useSharedMem, c->streamMain, fuse ? c->cur().evRead : nullptr, fuse);
+  if (fuse) { c->cur().readRecorded = true; c->setReadDeferred = -1; } else c->setReadDeferred = (int)c->setIndex;
   c->denoiseIssued = true; c->toneMapDone = fuse && c->slots[c->slot].rowEnd > c->slots[c->slot].rowBegin;
   return r;
 }
@@ -944,9 +941,9 @@ int rtggx_tone_map(rtggx_context* c) {
   int r = 0;
   if (c->toneMapDone) c->toneMapDone = false;      // this frame's rtggx_denoise wrote the back buffer as well
   else {
-    const bool carry = c->setReadDeferred >= 0 && c->attachEvents;
-    r = launchToneMap(c, c->slots[c->slot], c->streamMain, carry ? c->evSetRead[c->setReadDeferred] : nullptr);
-    if (carry && c->slots[c->slot].rowEnd > c->slots[c->slot].rowBegin) { c->setReadRecorded[c->setReadDeferred] = true; c->setReadDeferred = -1; }
+    const bool carry = c->setReadDeferred >= 0;
+    r = launchToneMap(c, c->slots[c->slot], c->streamMain, carry ? c->sets[c->setReadDeferred].evRead : nullptr);
+    if (carry && c->slots[c->slot].rowEnd > c->slots[c->slot].rowBegin) { c->sets[c->setReadDeferred].readRecorded = true; c->setReadDeferred = -1; }
   }
   settleSetRead(c);
   if (c->timing) { hipEventRecord(c->tev[10], c->streamMain); c->timingsPending = true; }
@@ -1032,7 +1029,7 @@ int rtggx_debug_trace_split(rtggx_context* c, uint32_t workPerWave, uint32_t max
   if (maxShift > 3u) { setError("rtggx_debug_trace_split: max_shift %u > 3", maxShift); return -1; }
   if (capacity > (int)RT_SPLIT_CAP) { setError("rtggx_debug_trace_split: capacity %d > %u", capacity, RT_SPLIT_CAP); return -1; }
   RT_HIP(syncStreams(c));
-  if (lastDemand) RT_HIP(hipMemcpy(lastDemand, c->splitCount, 4, hipMemcpyDeviceToHost));
+  if (lastDemand) RT_HIP(hipMemcpy(lastDemand, c->cur().splitCount, 4, hipMemcpyDeviceToHost));
   c->splitWork = workPerWave; c->splitMaxShift = maxShift;
   c->splitCapForced = capacity < 0 ? 0xFFFFFFFFu : ((uint32_t)capacity / 32u) * 32u;
   return 0;
@@ -1079,7 +1076,7 @@ int rtggx_get_timings(rtggx_context* c, RtggxTimings* out) {
   t.update_as = ms(0, 1); t.visibility = ms(2, 13); t.ray_trace = ms(3, 14); t.spatial_refl_h = ms(9, 4); t.spatial_refl_v = ms(4, 5);
   t.spatial_diff_h = ms(5, 6); t.spatial_diff_v = ms(6, 7); t.temporal = ms(7, 8); t.tone_map = ms(8, 10); t.frame = ms(2, 10);
   t.ray_trace_kernel = ms(11, 12);
-  *out = t; c->lastTimings = t;
+  *out = t;
   return 0;
 }
 
@@ -1087,11 +1084,11 @@ static int bufferInfo(rtggx_context* c, int id, void** ptr, size_t* bytes) {
   const size_t n = (size_t)c->W * c->H;
   switch (id) {
     case RTGGX_BUF_VISIBILITY: case RTGGX_BUF_DEPTH: *ptr = nullptr; *bytes = n * 4; return 0;   // halves of visDepth: staged
-    case RTGGX_BUF_NORMAL: *ptr = c->normal; *bytes = n * 4; return 0;
-    case RTGGX_BUF_ROUGH_METAL: *ptr = c->roughMetal; *bytes = n * 2; return 0;
-    case RTGGX_BUF_VELOCITY: *ptr = c->velocity; *bytes = n * 4; return 0;
-    case RTGGX_BUF_RT_REFL: *ptr = c->rtRefl; *bytes = n * 4; return 0;
-    case RTGGX_BUF_RT_DIFF: *ptr = c->rtDiff; *bytes = n * 4; return 0;
+    case RTGGX_BUF_NORMAL: *ptr = c->cur().normal; *bytes = n * 4; return 0;
+    case RTGGX_BUF_ROUGH_METAL: *ptr = c->cur().roughMetal; *bytes = n * 2; return 0;
+    case RTGGX_BUF_VELOCITY: *ptr = c->cur().velocity; *bytes = n * 4; return 0;
+    case RTGGX_BUF_RT_REFL: *ptr = c->cur().rtRefl; *bytes = n * 4; return 0;
+    case RTGGX_BUF_RT_DIFF: *ptr = c->cur().rtDiff; *bytes = n * 4; return 0;
     case RTGGX_BUF_TSS0: *ptr = c->tss[0]; *bytes = n * 8; return 0;
     case RTGGX_BUF_TSS1: *ptr = c->tss[1]; *bytes = n * 8; return 0;
     case RTGGX_BUF_FLT_RFL: *ptr = c->fltRflIsFltDff ? c->fltDff : c->fltRfl; *bytes = n * 8; return 0;      // identical images when no diffuse pass ran: only one was written (denoise.hip launchDenoise)
@@ -1117,7 +1114,7 @@ int rtggx_buffer_ptr(rtggx_context* c, int id, void** dptr) {
   size_t bytes;
   const int r = bufferInfo(c, id, dptr, &bytes);
   if (r) return r;
-  if (id == RTGGX_BUF_VISIBILITY || id == RTGGX_BUF_DEPTH) *dptr = c->visDepth;   // packed u64: (depth << 32) | visibility
+  if (id == RTGGX_BUF_VISIBILITY || id == RTGGX_BUF_DEPTH) *dptr = c->curVis().depth;   // packed u64: (depth << 32) | visibility
   if (!*dptr) { setError("buffer %d has no device storage", id); return -1; }
   return 0;
 }
@@ -1152,7 +1149,7 @@ int rtggx_upload(rtggx_context* c, int id, const void* src, size_t bytes) {
   if (bytes != need) { setError("rtggx_upload: buffer %d is %zu bytes, %zu given", id, need, bytes); return -1; }
   RT_HIP(syncStreams(c));
   c->toneMapDone = false;      // (a tone map after an upload reads what was uploaded)
-  c->visFlags[c->frameCounter % RT_VIS_RING].rasterFrame = 0u;      // ... and the tiles' words of this frame's visibility pass do not describe it (rtggx_context.h visDirtyBuf)
+  c->curVis().flags.rasterFrame = 0u;      // ... and the tiles' words of this frame's visibility pass do not describe it (rtggx_context.h VisTarget::dirty)
   if (id == RTGGX_BUF_VISIBILITY || id == RTGGX_BUF_DEPTH) {
     // replace one half of the packed buffer
     uint32_t *dVis, *dDepth;
@@ -1161,7 +1158,7 @@ int rtggx_upload(rtggx_context* c, int id, const void* src, size_t bytes) {
     if (!r && hipStreamSynchronize(c->streamMain) != hipSuccess) { setError("upload: stream sync failed"); r = -2; }
     if (!r) { hipError_t e = hipMemcpy(id == RTGGX_BUF_VISIBILITY ? dVis : dDepth, src, need, hipMemcpyHostToDevice); if (e != hipSuccess) { setError("hipMemcpy: %s", hipGetErrorString(e)); r = -2; } }
     if (!r) r = packVisDepth(c, dVis, dDepth, c->streamMain);
-    if (!r && id == RTGGX_BUF_DEPTH && hipMemcpy(c->depth32, src, need, hipMemcpyHostToDevice) != hipSuccess) { setError("upload: depth copy failed"); r = -2; }      // the filters' copy (ray generation writes it otherwise)
+    if (!r && id == RTGGX_BUF_DEPTH && hipMemcpy(c->cur().depth32, src, need, hipMemcpyHostToDevice) != hipSuccess) { setError("upload: depth copy failed"); r = -2; }      // the filters' copy (ray generation writes it otherwise)
     hipStreamSynchronize(c->streamMain);
     hipFree(dVis); hipFree(dDepth);
     return r;
@@ -1245,7 +1242,6 @@ int rtggx_trace_rays(rtggx_context* c, const float* rays, uint32_t n, float* out
   RT_CHECK_CTX(c);
   if (!c->asBuilt || !c->haveConstants) { setError("rtggx_trace_rays: build_as / update_frame / update_as first"); return -1; }
   RT_HIP(syncStreams(c));   // the ray bins are shared with the frame path on stream B
-  if (c->sceneDirty) { const int r = uploadScene(c, c->streamMain); if (r) return r; }
   { const int r = ensureParams(c); if (r) return r; }
   float *dR, *dO;
   RT_HIP(hipMalloc(&dR, (size_t)n * 32)); RT_HIP(hipMalloc(&dO, (size_t)n * 24));

@@ -18,7 +18,6 @@
 // time.  Out-of-range texels are the zeros D3D returns.
 #include <cstring>
 #include <type_traits>
-#include <hip/hip_ext.h>
 #include "rtggx_context.h"
 
 namespace rt {
@@ -71,7 +70,7 @@ struct Targets {
   const uint2* const* peerHist; const uint32_t* peerBounds; int peerWorld;
   int outBegin, outEnd;      // rows of the back buffer (the strip itself): the fused temporal + tone-map kernel
   // one word per 16x16 tile, counted from row tileRow0, tilesX to a row: 0 = the visibility pass drew nothing there, no pixel of it has a surface
-  // (rtggx_context.h visDirtyBuf; all ones where that is not known)
+  // (rtggx_context.h VisTarget::dirty; all ones where that is not known)
   const uint32_t* tileWords; int tilesX, tileRow0;
 };
 #define RT_SGPR(v) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(v)))      // a workgroup-uniform value the compiler may have computed in vector registers
@@ -639,8 +638,9 @@ __global__ void __launch_bounds__(256) toneMapKernel(Targets T) {
 
 static Targets makeTargets(rtggx_context* c, const FrameParams& fp, RowPass pass) {
   Targets T;
-  T.normal = c->normal; T.roughMetal = c->roughMetal; T.depth32 = c->depth32; T.velocity = c->velocity;
-  T.rtRefl = c->rtRefl; T.rtDiff = c->rtDiff;
+  const InputSet& set = c->cur();
+  T.normal = set.normal; T.roughMetal = set.roughMetal; T.depth32 = set.depth32; T.velocity = set.velocity;
+  T.rtRefl = set.rtRefl; T.rtDiff = set.rtDiff;
   T.scratch = c->tss[c->frameParity]; T.history = c->tss[c->frameParity ^ 1u]; T.fltRfl = c->fltRfl; T.fltDff = c->fltDff; T.backbuffer = c->backbuffer;
   T.W = (int)fp.W; T.H = (int)fp.H;
   uint32_t rb, re; passRows(fp, pass, rb, re);
@@ -694,10 +694,8 @@ int launchDenoise(rtggx_context* c, const FrameParams& fp, int useLds, hipStream
   }
   if (fuseToneMap) {      // the temporal pass and the tone map of its result in one kernel: workgroups of 62 x 14 back-buffer pixels over the strip's own rows
     const dim3 g((fp.W + RT_TT_W - 1) / RT_TT_W, (uint32_t)(TT.outEnd - TT.outBegin + RT_TT_H - 1) / RT_TT_H), b(RT_TT_TW * RT_TT_TH);
-    if (done && c->attachEvents) hipExtLaunchKernelGGL(temporalToneKernel, g, b, 0, s, nullptr, done, 0, TT);
-    else { hipLaunchKernelGGL(temporalToneKernel, g, b, 0, s, TT); if (done) hipEventRecord(done, s); }
-  } else if (done && c->attachEvents) hipExtLaunchKernelGGL(temporalKernel, grid(TT, 64, RT_TP_ROWS), block, 0, s, nullptr, done, 0, TT);
-  else { hipLaunchKernelGGL(temporalKernel, grid(TT, 64, RT_TP_ROWS), block, 0, s, TT); if (done) hipEventRecord(done, s); }
+    launch(temporalToneKernel, g, b, s, nullptr, done, TT);
+  } else launch(temporalKernel, grid(TT, 64, RT_TP_ROWS), block, s, nullptr, done, TT);
   mark(8);
   RT_HIP(hipGetLastError());
   return 0;
@@ -709,8 +707,7 @@ int launchToneMap(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEve
   if (fp.rowEnd <= fp.rowBegin) return 0;
   const Targets T = makeTargets(c, fp, ROWS_FINAL);
   const dim3 grid((fp.W + 63) / 64, (uint32_t)(T.rowEnd - T.rowBegin + RT_TM_ROWS - 1) / RT_TM_ROWS), block(256);
-  if (done && c->attachEvents) hipExtLaunchKernelGGL(toneMapKernel, grid, block, 0, s, nullptr, done, 0, T);
-  else { hipLaunchKernelGGL(toneMapKernel, grid, block, 0, s, T); if (done) RT_HIP(hipEventRecord(done, s)); }
+  launch(toneMapKernel, grid, block, s, nullptr, done, T);
   RT_HIP(hipGetLastError());
   return 0;
 }

@@ -1188,7 +1188,7 @@ int refitLbvh(rtggx_context* c, uint32_t slot, uint32_t set, hipStream_t s) {
   const uint32_t n = m.numTris;
   if (n == 0 || !m.trisBuf[set]) return 0;
   const uint32_t nb = (n + 255) / 256;
-  if (!t.triBox || (n > 1 && !t.refittable)) { setError("rtggx_refit_as: mesh %u has no PLOC build to refit (RTGGX_BVH_RADIX_TREE builds cannot be refitted)", slot); return -1; }
+  if (!t.triBox || (n > 1 && !t.refittable)) { setError("rtggx_refit_as: mesh %u has no PLOC build to refit", slot); return -1; }
   { const int r = buildFatTris(c, slot, set, s); if (r) return r; }
   hipLaunchKernelGGL(refitTris, dim3(nb), dim3(256), 0, s, (int)n, (const uint32_t*)t.order, (const float*)m.vertsBuf[set], (const uint32_t*)m.indices, m.trisBuf[set], t.triBox);
   if (n > 1) {

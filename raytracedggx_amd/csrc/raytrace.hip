@@ -23,7 +23,6 @@
 // rayGen 18 B/pixel (+64 B per queued ray); trace 64 B ray + 16 B hit per ray + the scene arrays
 // once; shade 64+16 B in, 4 B out per ray.  The BVH (<= 14 MB) is L2/MALL resident, so traversal is
 // bound by L1 request rate, issue and latency, not by HBM (DESIGN.md "Roofline").
-#include <hip/hip_ext.h>
 #include "rt_queue.h"
 #include "rt_traverse.h"
 
@@ -268,7 +267,7 @@ struct GenArgs {
   // front of every wave's first dependent fetch: rayGenKernel 85 -> 169 us per launch, the 1080p frame 0.190 -> 0.243 ms, 4K 0.715 ->
   // 0.980; with the records in LDS no different.  profiles/r03_b_visibility_merge.txt)
   unsigned long long* visNext; uint32_t* zeroNext0; uint32_t* zeroNext1;
-  // one word per tile of this kernel (rtggx_context.h visDirtyBuf): 0 = the tile of the target holds the clear value only.  visDirty: of the
+  // one word per tile of this kernel (rtggx_context.h VisTarget::dirty): 0 = the tile of the target holds the clear value only.  visDirty: of the
   // target read here; visDirtyNext: of visNext; where the words are not known both point at words that are all ones (read / clear every
   // tile).  The words of visNext's tiles end as 0 (visDirtyNextOut: the target's own words)
   const uint32_t* visDirty; const uint32_t* visDirtyNext; uint32_t* visDirtyNextOut;
@@ -534,7 +533,7 @@ struct ShadeArgs {
   uint32_t* reflOut; uint32_t* diffOut;
   // carry-over of RayTracingOut1 (see the kernel)
   const uint32_t* diffPrev; const unsigned long long* visDepth; uint32_t tilesX, rowBegin, rowEnd, carryMask;
-  const uint32_t* tileWords;      // one word per tile of this kernel, 0 = nothing was drawn there (rtggx_context.h visDirtyBuf): no rays, nothing to carry
+  const uint32_t* tileWords;      // one word per tile of this kernel, 0 = nothing was drawn there (rtggx_context.h VisTarget::dirty): no rays, nothing to carry
   // the spawning pass (SHADE_SPAWN): each ray's child goes back into the ray's own bin, in place (the same arrays as rays / hits / binCount)
   RayRec* spawnRays; HitKey* spawnHits; uint32_t* spawnCount; const float* cosSin;
 };
@@ -801,26 +800,27 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
     setError("rtggx_ray_trace: a material with metallic below 1 (a diffuse ray per pixel as well) but ray bins of %u slots: rtggx_update_frame sizes them", c->binSlots); return -1;
   }
   GenArgs G;
+  const InputSet& set = c->cur();
   // ray generation starts the visibility pass of the frame after next (GenArgs): its target cleared, its list of large triangles emptied
   // (the list by frame parity: the one this frame's visibility pass has just used up), and the next set's split list
-  { const uint32_t thenFrame = c->frameCounter + 2u, nextSet = (c->setIndex + 1u) % RT_SETS;
-    G.visNext = c->visDepthBuf[thenFrame % RT_VIS_RING]; G.zeroNext0 = c->largeCountBase + (thenFrame & 1u); G.zeroNext1 = c->largeCountBase + 2u + nextSet;
-    auto& vc = c->visClearedAt[thenFrame % RT_VIS_RING]; vc.frame = thenFrame; vc.rows[0] = rb; vc.rows[1] = re;
-    // the tiles' words (rtggx_context.h visDirtyBuf): usable where they were kept for these very rows
+  { const uint32_t thenFrame = c->frameCounter + 2u;
+    VisTarget& vn = c->visOf(thenFrame);
+    G.visNext = vn.depth; G.zeroNext0 = c->largeCountBase + (thenFrame & 1u); G.zeroNext1 = c->next().splitCount;
+    vn.cleared.frame = thenFrame; vn.cleared.rows[0] = rb; vn.cleared.rows[1] = re;
+    // the tiles' words (VisTarget::dirty): usable where they were kept for these very rows
     if (c->traceShare > 0.93f) c->traversalBound = true; else if (c->traceShare < 0.89f) c->traversalBound = false;
     // (rate 4: the trace kernel's grid is of 32x32 tiles, which these words do not describe -- it is given words that are all ones)
     G.visDirty = c->tileWords(rb, re); c->traceTileWords = quad ? c->visDirtyOnes : G.visDirty;
-    auto& vn = c->visFlags[thenFrame % RT_VIS_RING];
-    G.visDirtyNextOut = c->visDirtyBuf[thenFrame % RT_VIS_RING];
-    G.visDirtyNext = c->useTileWords && !c->traversalBound && vn.rows[0] == rb && vn.rows[1] == re ? G.visDirtyNextOut : c->visDirtyOnes;
-    vn.rows[0] = rb; vn.rows[1] = re;
+    G.visDirtyNextOut = vn.dirty;
+    G.visDirtyNext = c->useTileWords && !c->traversalBound && vn.flags.rows[0] == rb && vn.flags.rows[1] == re ? vn.dirty : c->visDirtyOnes;
+    vn.flags.rows[0] = rb; vn.flags.rows[1] = re;
   }
-  G.visDepth = c->visDepth; G.depthOut = c->depth32; G.normalOut = c->normal; G.roughMetalOut = c->roughMetal; G.velocityOut = c->velocity; G.reflOut = c->rtRefl; G.diffOut = c->rtDiff;
-  G.roughMetalPrev = c->roughMetalBuf[(c->setIndex + RT_SETS - 1u) % RT_SETS];   // the previous frame's set
-  G.diffPrev = c->genCarriesDiff ? c->rtDiffBuf[(c->setIndex + RT_SETS - 1u) % RT_SETS] : nullptr;
+  G.visDepth = c->curVis().depth; G.depthOut = set.depth32; G.normalOut = set.normal; G.roughMetalOut = set.roughMetal; G.velocityOut = set.velocity; G.reflOut = set.rtRefl; G.diffOut = set.rtDiff;
+  G.roughMetalPrev = c->prev().roughMetal;
+  G.diffPrev = c->genCarriesDiff ? c->prev().rtDiff : nullptr;
   G.fat0 = c->mesh[0].fat; G.fat1 = c->mesh[1].fat;
   G.env = c->env.texels; G.envMipOffset = c->dEnvMipOffset; G.envSize = c->env.size; G.envMips = c->env.mips; G.cosSin = c->cosSinTab;
-  G.rays = (RayRec*)c->rayQueue; G.hits = (HitKey*)c->hitQueue; G.binCount = c->binCount; G.binSlots = c->binSlots; G.frameRays = c->rayCounter32;
+  G.rays = (RayRec*)set.rayQueue; G.hits = (HitKey*)set.hitQueue; G.binCount = set.binCount; G.binSlots = c->binSlots; G.frameRays = c->rayCounter32;
   G.tilesX = tilesX; G.numTiles = tilesX * tilesY; G.rowBegin = rb; G.rowEnd = re;
   const uint32_t splitWork = c->splitWork, splitMaxShift = c->splitMaxShift;
   const uint32_t numBins = quad ? quadX * quadY * 4u : G.numTiles * 4u;
@@ -828,51 +828,47 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
   // "wide" launches: few enough rays that the traversal does not fill the chip for long (trace.hip launchTrace, capi.hip rtggx_ray_trace)
   c->lastTraceSmall = c->forcePlacement >= 0 ? c->forcePlacement == 1 : (sliceShift > 0u || c->lastFrameRays < RT_WIDE_RAYS);
   const bool adaptive = splitWork != 0u && sliceShift == 0u;
-  c->lastTraceAdaptive = adaptive;
   // the split list is sized from the demand of an earlier frame (copied back asynchronously, like the ray counters)
   const uint32_t splitCap = !adaptive ? 0u : c->splitCapForced != 0xFFFFFFFFu ? c->splitCapForced
                           : c->splitDemand == 0u ? 0u : ((c->splitDemand + c->splitDemand / 8u + 64u + 31u) / 32u) * 32u;
-  G.binWork = adaptive ? c->binWork : nullptr; G.splitList = c->splitList; G.splitCount = c->splitCount;
+  G.binWork = adaptive ? c->binWork : nullptr; G.splitList = set.splitList; G.splitCount = set.splitCount;
   G.frontWork = RT_SPLIT_FRONT < splitWork ? RT_SPLIT_FRONT : splitWork;
   G.splitWork = splitWork; G.splitMaxShift = splitMaxShift < 3u ? splitMaxShift : 3u; G.splitCap = splitCap < RT_SPLIT_CAP ? splitCap : RT_SPLIT_CAP;
-  const hipEvent_t evGen = c->evGenRing[c->frameCounter & 3u];
-  if (quad) {
-    if (sGen != s && c->attachEvents) hipExtLaunchKernelGGL(rayGenKernel<4>, dim3(numBins), dim3(256), 0, sGen, nullptr, evGen, 0, (const FrameParams*)(c->dParams + c->slot), G);
-    else hipLaunchKernelGGL(rayGenKernel<4>, dim3(numBins), dim3(256), 0, sGen, c->dParams + c->slot, G);
-  } else if (sGen != s && c->attachEvents) hipExtLaunchKernelGGL(rayGenKernel<1>, dim3(G.numTiles), dim3(256), 0, sGen, nullptr, evGen, 0, (const FrameParams*)(c->dParams + c->slot), G);
-  else hipLaunchKernelGGL(rayGenKernel<1>, dim3(G.numTiles), dim3(256), 0, sGen, c->dParams + c->slot, G);
-  c->genFrame[c->frameCounter & 3u] = 0u; c->genStreamOf[c->frameCounter & 3u] = sGen;
-  if (sGen != s) {      // ray generation on stream C, the traversal on stream B behind it
-    if (!c->attachEvents) RT_HIP(hipEventRecord(evGen, sGen));
-    RT_HIP(hipStreamWaitEvent(s, evGen, 0));
-    c->genFrame[c->frameCounter & 3u] = c->frameCounter;      // (the event exists: a visibility pass on another stream two frames on waits for it)
+  // ray generation on stream C, the traversal on stream B behind it: the event rides on ray generation
+  FrameEvents& ev = c->frameEvents(c->frameCounter);
+  launch(quad ? rayGenKernel<4> : rayGenKernel<1>, dim3(quad ? numBins : G.numTiles), dim3(256), sGen, nullptr, sGen != s ? ev.gen : nullptr, c->dParams + c->slot, G);
+  ev.genFrame = 0u; ev.genStream = sGen;
+  if (sGen != s) {
+    RT_HIP(hipStreamWaitEvent(s, ev.gen, 0));
+    ev.genFrame = c->frameCounter;      // (the event exists: a visibility pass on another stream two frames on waits for it)
   }
   if (c->timing) hipEventRecord(c->tev[11], s);
   const bool ring = c->kernelRing && c->kevCount < c->kevBegin.size() && (c->ringTick++ % c->ringStride) == 0u;
   // a sampled frame: the event pair of the kernel ring rides on the dispatch (and `done` is recorded behind it)
-  const bool attach = c->attachEvents;
-  if (ring && !attach) hipEventRecord(c->kevBegin[c->kevCount], s);
   const TraceQueue q{G.rays, G.hits, G.binCount};
   c->traceGrid[0] = numBins; c->traceGrid[1] = quad ? quadX : tilesX; c->traceGrid[2] = quad ? quadY : tilesY; c->traceGrid[3] = sliceShift;      // (the later levels' launches: launchShade)
   { const int r = launchTrace(c, fp, s, q, numBins, true, quad ? quadX : tilesX, quad ? quadY : tilesY, sliceShift, adaptive ? (int)G.splitCap : -1,
-                              ring && attach ? c->kevBegin[c->kevCount] : nullptr, !attach ? nullptr : ring ? c->kevEnd[c->kevCount] : done); if (r) return r; }
+                              ring ? c->kevBegin[c->kevCount] : nullptr, ring ? c->kevEnd[c->kevCount] : done); if (r) return r; }
   if (c->timing) hipEventRecord(c->tev[12], s);
-  if (ring && !attach) hipEventRecord(c->kevEnd[c->kevCount], s);
   if (ring) ++c->kevCount;
-  if (done && (ring || !attach)) hipEventRecord(done, s);
+  if (done && ring) hipEventRecord(done, s);
   RT_HIP(hipGetLastError());
   return 0;
 }
 
 // The shading of the frame's traced bins: at recursion depth D (rtggx_set_max_recursion_depth) D passes, each but the last spawning the next
 // level's rays into the bins they shade and tracing them with the trace kernel on this stream (ShadePass).  `done` rides on the last pass.
+static void (*const kShade[3][2])(const FrameParams*, ShadeArgs) = {      // [ShadePass][rate 4]
+    {shadeKernel<1, SHADE_FINAL>, shadeKernel<4, SHADE_FINAL>}, {shadeKernel<1, SHADE_SPAWN>, shadeKernel<4, SHADE_SPAWN>},
+    {shadeKernel<1, SHADE_FINAL_DEEP>, shadeKernel<4, SHADE_FINAL_DEEP>}};
 int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent_t done) {
   uint32_t rb, re;
   passRows(fp, ROWS_GBUFFER, rb, re);
   if (re <= rb) return 0;
   const uint32_t tilesX = (fp.W + 15) / 16, numTiles = tilesX * ((re - rb + 15) / 16);
+  const InputSet& set = c->cur();
   ShadeArgs S;
-  S.diffPrev = c->rtDiffBuf[(c->setIndex + RT_SETS - 1u) % RT_SETS]; S.visDepth = c->visDepth; S.tilesX = tilesX; S.rowBegin = rb; S.rowEnd = re;
+  S.diffPrev = c->prev().rtDiff; S.visDepth = c->curVis().depth; S.tilesX = tilesX; S.rowBegin = rb; S.rowEnd = re;
   S.carryMask = (fp.mat.RoughMetals[0][1] >= 1.0f ? 1u : 0u) | (fp.mat.RoughMetals[1][1] >= 1.0f ? 2u : 0u);      // rghMtl.y < 1 is the test of :559; it is the instance's constant
   // ... unless ray generation has carried those pixels over already.  It can when the previous frame's shading kernel wrote nothing
   // into the previous set's image (no diffuse rays, no carrying): that image was final when the previous ray generation ended, earlier
@@ -883,11 +879,11 @@ int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent
   const bool quad = c->rayRate == 4u;      // (rate 4: 32x32 tiles, and RayTracingOut1 is carried over by launchReconstruct)
   const uint32_t grid = quad ? ((tilesX + 1u) / 2u) * ((re - rb + 31u) / 32u) : numTiles;
   if (quad) S.carryMask = 0u;
-  S.rays = (const RayRec*)c->rayQueue; S.hits = (const HitKey*)c->hitQueue; S.binCount = c->binCount; S.binSlots = c->binSlots;
+  S.rays = (const RayRec*)set.rayQueue; S.hits = (const HitKey*)set.hitQueue; S.binCount = set.binCount; S.binSlots = c->binSlots;
   S.fat0 = c->mesh[0].fat; S.fat1 = c->mesh[1].fat;
   S.env = c->env.texels; S.envMipOffset = c->dEnvMipOffset; S.envSize = c->env.size; S.envMips = c->env.mips; S.sh = c->sh;
-  S.reflOut = c->rtRefl; S.diffOut = c->rtDiff;
-  S.spawnRays = (RayRec*)c->rayQueue; S.spawnHits = (HitKey*)c->hitQueue; S.spawnCount = c->binCount; S.cosSin = c->cosSinTab;
+  S.reflOut = set.rtRefl; S.diffOut = set.rtDiff;
+  S.spawnRays = (RayRec*)set.rayQueue; S.spawnHits = (HitKey*)set.hitQueue; S.spawnCount = set.binCount; S.cosSin = c->cosSinTab;
   const FrameParams* const dfp = c->dParams + c->slot;
   const uint32_t depth = c->maxDepth;
   // Levels 1.. run behind this stream's shading of the level before, beside the next frame's level-0 traversal (stream B): a part of the
@@ -900,29 +896,8 @@ int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent
       if (r) return r;
       S.carryMask = 0u;      // (carried over once, by the first pass)
     }
-    const bool last = level + 1u == depth;
-    const dim3 blocks(quad ? grid : numTiles);
-    if (!last) {
-      if (quad) hipLaunchKernelGGL((shadeKernel<4, SHADE_SPAWN>), blocks, dim3(256), 0, s, dfp, S);
-      else hipLaunchKernelGGL((shadeKernel<1, SHADE_SPAWN>), blocks, dim3(256), 0, s, dfp, S);
-    } else if (done && c->attachEvents) {
-      if (level == 0) {
-        if (quad) hipExtLaunchKernelGGL((shadeKernel<4, SHADE_FINAL>), blocks, dim3(256), 0, s, nullptr, done, 0, dfp, S);
-        else hipExtLaunchKernelGGL((shadeKernel<1, SHADE_FINAL>), blocks, dim3(256), 0, s, nullptr, done, 0, dfp, S);
-      } else {
-        if (quad) hipExtLaunchKernelGGL((shadeKernel<4, SHADE_FINAL_DEEP>), blocks, dim3(256), 0, s, nullptr, done, 0, dfp, S);
-        else hipExtLaunchKernelGGL((shadeKernel<1, SHADE_FINAL_DEEP>), blocks, dim3(256), 0, s, nullptr, done, 0, dfp, S);
-      }
-    } else {
-      if (level == 0) {
-        if (quad) hipLaunchKernelGGL((shadeKernel<4, SHADE_FINAL>), blocks, dim3(256), 0, s, dfp, S);
-        else hipLaunchKernelGGL((shadeKernel<1, SHADE_FINAL>), blocks, dim3(256), 0, s, dfp, S);
-      } else {
-        if (quad) hipLaunchKernelGGL((shadeKernel<4, SHADE_FINAL_DEEP>), blocks, dim3(256), 0, s, dfp, S);
-        else hipLaunchKernelGGL((shadeKernel<1, SHADE_FINAL_DEEP>), blocks, dim3(256), 0, s, dfp, S);
-      }
-      if (done) hipEventRecord(done, s);
-    }
+    const int pass = level + 1u < depth ? SHADE_SPAWN : level == 0 ? SHADE_FINAL : SHADE_FINAL_DEEP;
+    launch(kShade[pass][quad], dim3(grid), dim3(256), s, nullptr, pass == SHADE_SPAWN ? nullptr : done, dfp, S);
     RT_HIP(hipGetLastError());
   }
   return 0;
@@ -933,10 +908,11 @@ int launchReconstruct(rtggx_context* c, const FrameParams& fp, hipStream_t s) {
   passRows(fp, ROWS_GBUFFER, rb, re);
   if (re <= rb) return 0;
   const uint32_t tilesX = (fp.W + 15) / 16, numTiles = tilesX * ((re - rb + 15) / 16);
+  const InputSet& set = c->cur();
   ReconArgs R;
-  R.visDepth = c->visDepth; R.normal = c->normal; R.roughMetal = c->roughMetal; R.depth32 = c->depth32;
-  R.reflOut = c->rtRefl; R.diffOut = c->rtDiff;
-  R.diffPrev = c->rtDiffBuf[(c->setIndex + RT_SETS - 1u) % RT_SETS];
+  R.visDepth = c->curVis().depth; R.normal = set.normal; R.roughMetal = set.roughMetal; R.depth32 = set.depth32;
+  R.reflOut = set.rtRefl; R.diffOut = set.rtDiff;
+  R.diffPrev = c->prev().rtDiff;
   const uint32_t metal = (fp.mat.RoughMetals[0][1] >= 1.0f ? 1u : 0u) | (fp.mat.RoughMetals[1][1] >= 1.0f ? 2u : 0u);      // as launchShade's carryMask
   R.carryMask = c->genCarriesDiff ? 0u : metal; R.diffMask = ~metal & 3u;
   R.tileWords = c->tileWords(rb, re); R.tilesX = tilesX; R.rowBegin = rb; R.rowEnd = re;
@@ -982,14 +958,15 @@ int launchTraceRays(rtggx_context* c, const FrameParams& fp, const float* dRays,
   if (!n) return 0;
   if (n > c->numBinsMax * c->binSlots) { setError("rtggx_trace_rays: at most %u rays per launch", c->numBinsMax * c->binSlots); return -1; }
   const uint32_t numBins = (((n + c->binSlots - 1u) / c->binSlots) + 3u) & ~3u;   // whole tiles of four bins
-  RT_HIP(hipMemsetAsync(c->binCount, 0, (size_t)numBins * 4, s));
+  const InputSet& set = c->cur();
+  RT_HIP(hipMemsetAsync(set.binCount, 0, (size_t)numBins * 4, s));
   // the rays' own (TMin, TMax): one float2 per slot, kept for the context's lifetime once a caller has used this entry point
   if (!c->testRayRange) RT_HIP(hipMalloc(&c->testRayRange, (size_t)c->numBinsMax * RT_BIN * sizeof(float2)));
-  hipLaunchKernelGGL(fillTestQueue, dim3((n + 255) / 256), dim3(256), 0, s, dRays, n, c->binSlots, (RayRec*)c->rayQueue, (HitKey*)c->hitQueue, c->binCount, (float2*)c->testRayRange);
+  hipLaunchKernelGGL(fillTestQueue, dim3((n + 255) / 256), dim3(256), 0, s, dRays, n, c->binSlots, (RayRec*)set.rayQueue, (HitKey*)set.hitQueue, set.binCount, (float2*)c->testRayRange);
   c->traceRayRange = c->testRayRange;
-  const TraceQueue q{(const RayRec*)c->rayQueue, (HitKey*)c->hitQueue, c->binCount};
+  const TraceQueue q{(const RayRec*)set.rayQueue, (HitKey*)set.hitQueue, set.binCount};
   { const int r = launchTrace(c, fp, s, q, numBins, false, 0u, 0u, chooseSliceShift(c, false, numBins), -1); c->traceRayRange = nullptr; if (r) return r; }
-  hipLaunchKernelGGL(exportTestHits, dim3((n + 255) / 256), dim3(256), 0, s, c->dParams + c->slot, (const RayRec*)c->rayQueue, (const HitKey*)c->hitQueue, n,
+  hipLaunchKernelGGL(exportTestHits, dim3((n + 255) / 256), dim3(256), 0, s, c->dParams + c->slot, (const RayRec*)set.rayQueue, (const HitKey*)set.hitQueue, n,
                      (const float4*)c->mesh[0].fat, (const float4*)c->mesh[1].fat, dOut);
   RT_HIP(hipGetLastError());
   return 0;

@@ -21,9 +21,6 @@ namespace rt {
 // Adaptive split of the trace launch (trace.hip): what a bin cost in the previous frame, in lane-steps, decides where and
 // how it is traced in this one.  Tuned on the 1080p bunny frame (mean bin: ~700 lane-steps, 14 steps of a wave):
 #define RT_SPLIT_CAP 16384u  // entries of the split list
-#ifndef RT_VIS_STREAM_RAYS
-#define RT_VIS_STREAM_RAYS 800000u   // below this many rays per frame the visibility pass runs on its own stream (capi.hip: all-metal frames; measured: -4.6 % at 0.52 M rays, +0.8 % at 2 M)
-#endif
 // Round 2 (three-stage pipeline, profiles/r02_c_ab_pipeline.txt block 5): with the traversal no longer the frame's longest chain,
 // what pays is STARTING the dearer bins first (a lower threshold: 1000 -> 300, the mean bin costs ~700) and splitting fewer of them
 // (2400 -> 3200): every extra wave of a split bin is wave-slot time the other two stages want.  The trace kernel alone gets slower

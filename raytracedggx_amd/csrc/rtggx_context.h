@@ -6,13 +6,14 @@
 //   normal     u32   R10G10B10A2_UNORM      roughMetal u16 R8G8_UNORM     velocity u32 R16G16_FLOAT
 //   rtRefl/rtDiff u32 R11G11B10_FLOAT       tss[2], fltRfl, fltDff u64 R16G16B16A16_FLOAT
 //   backbuffer u32   R8G8B8A8_UNORM
-// visDepth, normal, roughMetal, velocity, rtRefl, rtDiff and the ray bins exist RT_SETS times ("input sets"): stream B
-// (visibility, ray generation, traversal) fills one set while the main stream (shading, denoise, tone map) still
-// reads an earlier one.
+// normal, roughMetal, velocity, rtRefl, rtDiff and the ray bins exist RT_SETS times (rt::InputSet, "input sets"): streams C and B
+// (visibility, ray generation, traversal) fill one set while the main stream (shading, denoise, tone map) still reads an earlier
+// one.  visDepth exists RT_VIS_RING times (rt::VisTarget).
 // Scene: per mesh 24-byte vertices, u32 indices, 64-byte binary BVH nodes, their 128-byte 4-wide collapse,
 // 64-byte leaf triangles; environment as RGBA16F mip-major (6 faces per mip); 9 float3 SH coefficients.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string>
@@ -35,9 +36,7 @@
 #define RT_SLOTS (RT_SETS + 1)
 // The visibility target (visDepth) exists twice more than the other members of an input set: ray generation of frame f clears the
 // target of frame f + 2 on its way (raytrace.hip) -- one kernel launch and one pass over 8 bytes per pixel less per frame --, and the
-// target it clears must be one nobody reads any more: frame f + 2 - RT_VIS_RING's, whose last reader the host has waited for (evSetRead).
-// (Round 3 cleared the target of frame f + 1, which chained the visibility pass of frame f + 1 behind ray generation f on one stream;
-// round 4 runs the visibility pass on the geometry stream beside it: capi.hip placeFrame.)
+// target it clears must be one nobody reads any more: frame f + 2 - RT_VIS_RING's, whose last reader the host has waited for (InputSet::evRead).
 #define RT_VIS_RING (RT_SETS + 2)
 #define RT_VIS_CLEAR 0x00FFFFFF00000000ull      // (D24 = 1.0) << 32 | nothing drawn
 namespace rt {
@@ -73,7 +72,7 @@ struct BvhTopo {
   BuildResult* dResult = nullptr; BuildResult* hResult = nullptr;      // device record, pinned copy
   BuildResult result{};                      // the host's copy, valid once the build has ended
   uint32_t numTris = 0; int32_t root = -1;
-  bool refittable = false;                   // a PLOC build (the Karras radix tree of RTGGX_BVH_RADIX_TREE has no rounds)
+  bool refittable = false;                   // a PLOC build of more than one triangle (the refit needs its rounds)
 };
 
 struct MeshDev {
@@ -141,12 +140,41 @@ struct FrameParams {
 };
 #define RT_FLAG_VNDF 1u          // rtggx_set_sampler: visible-normal sampling of the reflection lobe instead of the reference's NDF sampling
 
-// Scene pointers as the trace/shade kernels see them (device-resident copy in rtggx_context::dScene).
-struct Scene {
-  const float* verts[2]; const uint32_t* idx[2];
-  const BvhNode* nodes[2]; const BvhTri* tris[2]; int32_t root[2];
-  const uint2* env; uint32_t envSize, envMips; uint32_t mipOffset[16];
-  const float* sh; const float* cosSin;
+// One input set: everything stream B's stages write for a frame and the main stream reads (allocated and freed by capi.hip allocSet / freeSet).
+struct InputSet {
+  uint32_t *normal = nullptr, *velocity = nullptr, *rtRefl = nullptr, *rtDiff = nullptr;
+  uint16_t* roughMetal = nullptr;
+  uint32_t* depth32 = nullptr;       // the D24 word of visDepth once more, 4 bytes per pixel, for the spatial filters (written by ray generation)
+  // ray bins of the trace pass (rt_queue.h): numBinsMax bins of binSlots ray records and hit keys, and the rays in each bin
+  void *rayQueue = nullptr, *hitQueue = nullptr;
+  uint32_t* binCount = nullptr;
+  // Bins whose traversal was expensive in the previous frame are traced by 2, 4 or 8 waves (trace.hip "adaptive split"): [RT_SPLIT_CAP]
+  // (shift << 28) | (slice << 24) | bin, one entry per wave of a listed bin.  Per set: the visibility pass of the next frame, which empties
+  // its set's list, may run beside this frame's traversal.  The count is a word of largeCountBase (zeroed by the previous frame's ray generation).
+  uint32_t* splitList = nullptr; uint32_t* splitCount = nullptr;
+  hipEvent_t evRead = nullptr;       // the set's last reader done: the HOST waits for it before stream B is given work that overwrites the set
+  bool readRecorded = false;
+};
+
+// One visibility target (RT_VIS_RING above), by frame number.
+struct VisTarget {
+  unsigned long long* depth = nullptr;      // visDepth
+  // One word per 16x16 tile, set by the rasterisers where they draw: a tile whose word is 0 holds nothing but the clear value, and ray
+  // generation neither reads nor re-clears it (three quarters of the bunny frame: 16 bytes per pixel and the first of its dependent
+  // fetches).  Tiles are ray generation's, counted from the pass's first row: the words mean something only for the rows they were kept
+  // under (flags.rows; another strip: everything is read and cleared, which also resets the words).
+  uint32_t* dirty = nullptr;
+  struct { uint32_t frame = 0, rows[2] = {0, 0}; } cleared;      // a ray generation has cleared the target, over these rows, FOR this frame (0: not)
+  struct { uint32_t rows[2] = {0, 0}; uint32_t rasterFrame = 0; } flags;      // word 0 => tile clear, for tiles counted from rows[0]; rasterFrame: the frame whose visibility pass drew into the target last
+};
+
+// What the stages of frame f tell the streams of later frames, by f & 3 (capi.hip rtggx_render_visibility).
+struct FrameEvents {
+  hipEvent_t gen = nullptr;          // ray generation of frame f done (C -> B: traversal f; C -> R: the visibility pass of frame f + 2, whose target and lists it cleared)
+  uint32_t genFrame = 0;             // the frame it belongs to (0: none)
+  hipStream_t genStream = nullptr;   // and its stream
+  hipEvent_t trace = nullptr;        // traversal of frame f done (B -> main; B -> C two frames later: binWork)
+  bool traceRecorded = false;
 };
 
 }  // namespace rt
@@ -166,15 +194,12 @@ struct rtggx_context {
   uint32_t* histReach = nullptr;        // device word: the furthest a history tap reached beyond them, in rows (temporalKernel)
   hipStream_t streamMain = nullptr, streamAS = nullptr, ownMain = nullptr;
   hipStream_t streamRefit = nullptr;               // stream R: vertex uploads and tree refits of deforming meshes (rtggx_refit_as)
-  // Frame pipeline (capi.hip): 1 = three stages on three streams -- C: visibility + ray generation, B: traversal, main: shading +
-  // denoiser + tone map -- so that ray generation of frame f + 1 runs beside the traversal of frame f; 0 = the round-1 arrangement
-  // (ray generation and traversal on B; the visibility pass on C only where launches are small).  RTGGX_PIPELINE overrides.
-  int pipeline = 1;
-  bool refitIssued = false; bool traceRecorded[4] = {}; hipStream_t genStream = nullptr;   // per-frame issue state (capi.hip)
+  // Frame pipeline (capi.hip): three stages on three streams -- C: visibility + ray generation, B: traversal, main: shading + denoiser +
+  // tone map -- so that ray generation of frame f + 1 runs beside the traversal of frame f.
+  bool refitIssued = false;                        // per-frame issue state (capi.hip)
   uint32_t frameCounter = 0;                       // frames started (rtggx_render_visibility); parity selects binWork / ray counters
-  hipEvent_t evGenRing[4] = {};                    // ray generation of frame f done: [f & 3] (C -> B: traversal f; C -> R: the visibility pass of frame f + 2, whose target and lists it cleared)
-  uint32_t genFrame[4] = {}; hipStream_t genStreamOf[4] = {};      // the frame whose ray generation evGenRing[k] belongs to (0: none), and its stream
-  hipEvent_t evTraceRing[4] = {};                  // traversal of frame f done: [f & 3] (B -> main; B -> C two frames later: binWork)
+  rt::FrameEvents frames[4];                       // by frame & 3
+  rt::FrameEvents& frameEvents(uint32_t f) { return frames[f & 3u]; }
   hipStream_t ownAS = nullptr, ownVis = nullptr;   // the context's own stream B / stream C; streamAS / streamVis alias streamMain / null while
   bool asyncCompute = true;                        // rtggx_set_async_compute(0) is in force (the sample's [A] toggle: one queue, submission order)
   // Launches with few rays (thin strips, small frames) leave most of the machine idle and last as long as stream B's chain
@@ -183,13 +208,10 @@ struct rtggx_context {
   hipStream_t streamVis = nullptr;
   hipEvent_t evVis = nullptr;           // completes with the last kernel of the most recent visibility pass, on either stream
   hipStream_t evVisStream = nullptr;    // the stream the most recent visibility pass ran on (null: none yet)
-  bool lastTraceAdaptive = false;
-  bool attachEvents = true;             // RTGGX_ATTACH_EVENTS=0: record the cross-stream events with hipEventRecord instead
   hipEvent_t evAS = nullptr;      // constants uploaded (stream B -> main)
   hipEvent_t evRefit = nullptr;   // vertices of the current set uploaded and the tree refitted (stream B -> stream C)
-  hipEvent_t evRT = nullptr, evSetRead[RT_SETS] = {};   // ray trace done (stream B -> main); last reader of input set i done (the HOST waits for it before stream B is given work that overwrites the set)
-  bool setReadRecorded[RT_SETS] = {};
-  int setReadDeferred = -1;      // the set whose event is still to ride on a later kernel of this frame (capi.hip settleSetRead)
+  hipEvent_t evRT = nullptr;      // ray trace done (stream B -> main)
+  int setReadDeferred = -1;       // the set whose evRead is still to ride on a later kernel of this frame (capi.hip settleSetRead)
   double fenceWaitUs = 0.0; uint32_t fenceWaits = 0;      // host time spent waiting at the frames-in-flight fence (rtggx_render_visibility; rtggx_debug_fence_wait)
   // The temporal pass and the tone map as one kernel (denoise.hip temporalToneKernel): rtggx_denoise then writes the back buffer as well and
   // the rtggx_tone_map that follows it in the same frame has nothing left to launch.  -1: where it pays -- small launches (capi.hip
@@ -216,37 +238,26 @@ struct rtggx_context {
   float* cosSinTab = nullptr;    // 512 floats: cos[256], sin[256]
 
   // render targets
-  // Everything the visibility and ray-tracing passes (stream B) write and the denoiser (main stream) reads exists
-  // RT_SETS times, so that frame N+1's visibility + ray trace overlap frame N's denoise + tone map.  The unsuffixed
-  // pointers are set `setIndex`, the frame being rendered (advanced by rtggx_render_visibility).
-  unsigned long long* visDepth = nullptr;
-  uint32_t *normal = nullptr, *velocity = nullptr, *rtRefl = nullptr, *rtDiff = nullptr, *backbuffer = nullptr;
-  uint16_t* roughMetal = nullptr;
-  unsigned long long* visDepthBuf[RT_VIS_RING] = {};      // by frameCounter % RT_VIS_RING
-  // which target the last ray generation cleared for the next frame's visibility pass, and over which rows (visibility.hip)
-  struct VisCleared { uint32_t frame = 0, rows[2] = {0, 0}; } visClearedAt[RT_VIS_RING];      // target k has been cleared, over these rows, FOR this frame (0: not)
-  uint32_t visStandaloneClears = 0;
-  // Round 4: one word per 16x16 tile and target, set by the rasterisers where they draw: a tile whose word is 0 holds nothing but the clear
-  // value, and ray generation neither reads nor re-clears it (three quarters of the bunny frame: 16 bytes per pixel and the first of its
-  // dependent fetches).  Tiles are ray generation's, counted from the pass's first row: the words mean something only for the rows they
-  // were kept under (visFlags[k].rows; another strip: everything is read and cleared, which also resets the words).
-  uint32_t* visDirtyBuf[RT_VIS_RING] = {};
-  struct VisFlags { uint32_t rows[2] = {0, 0}; uint32_t rasterFrame = 0; } visFlags[RT_VIS_RING];      // word 0 => tile clear, for tiles counted from rows[0]; rasterFrame: the frame whose visibility pass drew into the target last
-  uint32_t* depth32 = nullptr; uint32_t* depth32Buf[RT_SETS] = {};      // the D24 word of visDepth once more, 4 bytes per pixel, for the spatial filters (written by ray generation)
-  uint32_t *normalBuf[RT_SETS] = {}, *velocityBuf[RT_SETS] = {}, *rtReflBuf[RT_SETS] = {}, *rtDiffBuf[RT_SETS] = {};
-  uint16_t* roughMetalBuf[RT_SETS] = {};
+  // Everything the visibility and ray-tracing passes write and the denoiser (main stream) reads exists RT_SETS times (the input sets), so
+  // that frame N+1's visibility + ray trace overlap frame N's denoise + tone map; the visibility target RT_VIS_RING times.  cur() is the
+  // set of the frame being rendered (advanced by rtggx_render_visibility), prev() / next() the sets of the frames before and after it;
+  // curVis() the frame's target.
+  rt::InputSet sets[RT_SETS];
   uint32_t setIndex = 0;
-  void *rayQueueBuf[RT_SETS] = {}, *hitQueueBuf[RT_SETS] = {};   // ray bins: written on stream B, shaded on the main stream
-  uint32_t* binCountBuf[RT_SETS] = {};
+  uint32_t setAhead(uint32_t k) const { return (setIndex + k) % RT_SETS; }      // the set of the frame k after this one (of RT_SETS - k before it)
+  rt::InputSet& cur() { return sets[setIndex]; }
+  rt::InputSet& prev() { return sets[setAhead(RT_SETS - 1u)]; }
+  rt::InputSet& next() { return sets[setAhead(1u)]; }
+  rt::VisTarget vis[RT_VIS_RING];
+  rt::VisTarget& visOf(uint32_t frame) { return vis[frame % RT_VIS_RING]; }
+  rt::VisTarget& curVis() { return visOf(frameCounter); }
   void selectSet(uint32_t i) {
-    setIndex = i; visDepth = visDepthBuf[frameCounter % RT_VIS_RING]; depth32 = depth32Buf[i]; normal = normalBuf[i]; velocity = velocityBuf[i]; rtRefl = rtReflBuf[i]; rtDiff = rtDiffBuf[i]; roughMetal = roughMetalBuf[i];
-    rayQueue = rayQueueBuf[i]; hitQueue = hitQueueBuf[i]; binCount = binCountBuf[i];
-    splitList = splitListBuf[i]; splitCount = largeCountBase ? largeCountBase + 2 + i : nullptr;
+    setIndex = i;
     largeTris = largeTrisBuf[frameCounter & 1u]; largeCount = largeCountBase ? largeCountBase + (frameCounter & 1u) : nullptr;
     for (auto& m : mesh) { m.verts = m.vertsBuf[i]; m.fat = m.fatBuf[i]; m.nodes = m.nodesBuf[i]; m.nodes4 = m.nodes4Buf[i]; m.top = m.topBuf[i]; m.topCount = m.topCountBuf[i]; m.tris = m.trisBuf[i]; }
-    const uint32_t par = pipeline != 0 ? (frameCounter & 1u) : 0u;
-    binWork = binWorkBuf[par]; rayCounter32 = rayCounterBuf + (pipeline != 0 ? (frameCounter & 3u) : 0u) * 256u;
+    binWork = binWorkBuf[frameCounter & 1u]; rayCounter32 = rayCounterBuf + (frameCounter & 3u) * 256u;
   }
+  uint32_t* backbuffer = nullptr;
   uint2 *tss[2] = {nullptr, nullptr}, *fltRfl = nullptr, *fltDff = nullptr;
   uint32_t frameParity = 0;
 
@@ -255,16 +266,15 @@ struct rtggx_context {
   // list of frame f + 1: the count it zeroes must not be the one a consumer of frame f could still read)
   void* largeTris = nullptr; void* largeTrisBuf[2] = {};
   uint32_t* largeCount = nullptr;       // the current frame's count (selectSet)
-  uint32_t* largeCountBase = nullptr;   // [0], [1] entries of largeTrisBuf[parity]; [2 + set] entries of splitList[set] (zeroed by the previous frame's ray generation)
-  // Bins whose traversal was expensive in the previous frame are traced by 2, 4 or 8 waves (trace.hip "adaptive split"):
+  uint32_t* largeCountBase = nullptr;   // [0], [1] entries of largeTrisBuf[parity]; [2 + i] sets[i].splitCount
+  // The adaptive split's record of what each bin cost (InputSet::splitList):
   uint32_t* binWork = nullptr;          // [numBinsMax] lane-steps the trace kernel spent on the bin (read and zeroed by rayGenKernel)
   uint32_t* binWorkBuf[2] = {};         // by frame parity: ray generation of frame f reads what the traversal of frame f - 2 recorded
                                         // (frame f - 1's may still be running beside it) and the traversal of frame f records anew
-  // per input set (the visibility pass of the next frame, which empties its set's list, may run beside this frame's traversal):
   // the words of the current frame's target, for the kernels that follow its visibility pass: the target's own where they describe rows [rb, re), else all ones
-  const uint32_t* tileWords(uint32_t rb, uint32_t re) const {
-    const VisFlags& vf = visFlags[frameCounter % RT_VIS_RING];
-    return useTileWords && !traversalBound && vf.rasterFrame == frameCounter && vf.rows[0] == rb && vf.rows[1] == re ? visDirtyBuf[frameCounter % RT_VIS_RING] : visDirtyOnes;
+  const uint32_t* tileWords(uint32_t rb, uint32_t re) {
+    const rt::VisTarget& v = curVis();
+    return useTileWords && !traversalBound && v.flags.rasterFrame == frameCounter && v.flags.rows[0] == rb && v.flags.rows[1] == re ? v.dirty : visDirtyOnes;
   }
   bool useTileWords = true;      // rtggx_debug_tile_words
   // Where the TRAVERSAL is the frame's period (two rays per pixel into a large mesh: it runs 96 % of the time) nobody asks the words:
@@ -274,18 +284,12 @@ struct rtggx_context {
   // measure (trace.hip steerTraceWaves), with hysteresis; the words themselves are kept either way.
   bool traversalBound = false;
   const uint32_t* traceTileWords = nullptr;      // launchRayTrace -> launchTrace: tileWords() of the frame's G-buffer rows
-  uint32_t* visDirtyOnes = nullptr;      // as many words as a visDirtyBuf, all ones: "every tile may hold something" (raytrace.hip GenArgs)
-  uint32_t* splitListBuf[RT_SETS] = {}; // [RT_SPLIT_CAP] (shift << 28) | (slice << 24) | bin, one entry per wave of a listed bin
-  uint32_t* splitList = nullptr; uint32_t* splitCount = nullptr;     // the current set's (selectSet)
+  uint32_t* visDirtyOnes = nullptr;      // as many words as a VisTarget's, all ones: "every tile may hold something" (raytrace.hip GenArgs)
   uint32_t splitDemand = 0;             // entries the most recent frame whose count has arrived wanted (hostRayCounters[256])
   uint32_t splitCapForced = 0xFFFFFFFFu;   // rtggx_debug_trace_split: fixed capacity instead of the demand-driven one
   uint32_t splitWork = 0, splitMaxShift = 0;   // set at creation (RT_SPLIT_WORK, or RTGGX_SPLIT_WORK / RTGGX_SPLIT_MAX_SHIFT)
   uint32_t largeCapacity = 0;
 
-  // ray bins of the trace pass (rt_queue.h): numBinsMax bins of 128 64-byte ray records + 16-byte hit records
-  void* rayQueue = nullptr;
-  void* hitQueue = nullptr;
-  uint32_t* binCount = nullptr;         // rays in each bin
   uint32_t numBinsMax = 0, binSlots = 64;      // bins per set; ray slots per bin (rt_queue.h RT_BIN_MIN / RT_BIN)
   void *testRayRange = nullptr, *traceRayRange = nullptr;      // rtggx_trace_rays: the rays' own (TMin, TMax); set only around that entry point's launch
   int32_t* stackOverflow = nullptr;     // traversal-stack spill area (entries beyond the LDS stack), sized from
@@ -319,8 +323,7 @@ struct rtggx_context {
   rt::FrameParams slots[RT_SLOTS];
   uint32_t slot = 0;
   rt::FrameParams* dParams = nullptr;   // device ring, 3 slots; kernels read their constants from here
-  rt::Scene* dScene = nullptr;          // device copy of the scene pointers
-  bool sceneDirty = true, slotUploaded = false;
+  bool slotUploaded = false;
   RtggxCBMaterial material;
   float invWorld[2][16];
   bool haveConstants = false, asBuilt = false, shDone = false;
@@ -331,8 +334,7 @@ struct rtggx_context {
   uint32_t ringStride = 1, ringTick = 0;   // every ringStride-th frame is sampled
   std::vector<hipEvent_t> kevBegin, kevEnd;
   uint32_t kevCount = 0;
-  hipEvent_t tev[16];
-  RtggxTimings lastTimings{};
+  hipEvent_t tev[16] = {};
   bool timingsPending = false;
 };
 
@@ -350,10 +352,17 @@ inline void passRows(const FrameParams& fp, RowPass pass, uint32_t& b, uint32_t&
 }
 void setError(const char* fmt, ...);
 #define RT_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { rt::setError("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); return -2; } } while (0)
+// Launches kernel k on stream s.  An event given as start or stop rides on the kernel's dispatch (hipExtLaunchKernelGGL; see `done`
+// below).  hipExtLaunchKernelGGL packs the arguments by the types of the expressions it is given, so they are converted to the kernel's
+// parameter types first.
+template <class... P, class... A>
+inline void launch(void (*k)(P...), dim3 grid, dim3 block, hipStream_t s, hipEvent_t start, hipEvent_t stop, A&&... a) {
+  if (start || stop) hipExtLaunchKernelGGL(k, grid, block, 0, s, start, stop, 0, static_cast<P>(a)...);
+  else hipLaunchKernelGGL(k, grid, block, 0, s, static_cast<P>(a)...);
+}
 
 // kernels / launchers implemented in the .hip files
 int uploadParams(rtggx_context* c, uint32_t slot, hipStream_t s);
-int uploadScene(rtggx_context* c, hipStream_t s);
 int launchVisibility(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent_t done = nullptr);
 // Acceleration-structure builds (lbvh.hip).  A build is a fixed sequence of kernel launches on one stream, no host round trip in it:
 //   buildLbvh          all of it at once, then ONE wait (rtggx_build_as; the sample: BuildAccelerationStructures + one WaitForGpu)

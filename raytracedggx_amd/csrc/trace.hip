@@ -24,7 +24,6 @@
 // order in which boxes are visited, so the 4-wide collapse, the work sharing and the postponed triangle tests
 // leave every hit record bit-identical to the oracle's binary-tree walk (tests/test_gpu_parity.py).
 #include <type_traits>
-#include <hip/hip_ext.h>
 #include "rt_queue.h"
 #include "rt_traverse.h"
 
@@ -51,7 +50,7 @@ struct TraceArgs {
   size_t spillStride;
   uint32_t sliceShift;       // 0..3: a wave starts with 64, 32, 16, 8 rays of its bin (1, 2, 4, 8 waves per bin; the other lanes start as helpers)
   uint32_t tilesX, tilesY;   // tile grid of the frame (4 bins per 16x16 tile); tilesX == 0: bins are a plain list (rtggx_trace_rays)
-  const uint32_t* tileWords; // one word per tile, 0 = nothing drawn there, no rays (rtggx_context.h visDirtyBuf); null with a plain list
+  const uint32_t* tileWords; // one word per tile, 0 = nothing drawn there, no rays (rtggx_context.h VisTarget::dirty); null with a plain list
   // adaptive split: the first splitBlocks workgroups take their (bin, slice) from the split list; a bin marked as split
   // (binCount bits 8..) is left to them.  binWork: lane-steps spent per bin, for the next frame's decision; null when off.
   const uint32_t* splitList; const uint32_t* splitCount; uint32_t* binWork; uint32_t splitBlocks;
@@ -513,7 +512,7 @@ int launchTrace(rtggx_context* c, const FrameParams& fp, hipStream_t s, const Tr
   T.tilesX = tilesX; T.tilesY = tilesY; T.tileWords = tilesX ? c->traceTileWords : nullptr;
   T.sliceShift = sliceShift;
   const bool adaptive = splitCap >= 0 && sliceShift == 0u && tilesX != 0u;
-  T.splitList = c->splitList; T.splitCount = c->splitCount;
+  T.splitList = c->cur().splitList; T.splitCount = c->cur().splitCount;
   T.binWork = adaptive ? c->binWork : nullptr; T.splitBlocks = adaptive ? (uint32_t)splitCap / 4u : 0u;
   const uint32_t superTiles = ((tilesX + 7u) / 8u) * ((tilesY + 7u) / 8u);
   const uint32_t grid = T.splitBlocks + ((tilesX ? ((superTiles + 7u) / 8u) * 8u * 64u : (((numBins + 3u) / 4u + 7u) / 8u) * 8u) << T.sliceShift);   // virtual blocks, a multiple of 8
@@ -538,22 +537,20 @@ int launchTrace(rtggx_context* c, const FrameParams& fp, hipStream_t s, const Tr
   uint32_t blocks = c->numCUs * perCu < wanted ? c->numCUs * perCu : wanted;
   blocks = (blocks + 7u) & ~7u;
   if (blocks * waves > RT_SPILL_WAVES) blocks = (RT_SPILL_WAVES / waves) & ~7u;      // (every wave of the launch owns a piece of the spill area)
-  const FrameParams* const dfp = c->dParams + c->slot;
-#define RT_LAUNCH_TRACE(W, PER_SIMD, TOP) { if (start || stop) hipExtLaunchKernelGGL((traceKernel<W, PER_SIMD, TOP>), dim3(blocks), dim3(64 * W), 0, s, start, stop, 0, dfp, T); \
-                                            else hipLaunchKernelGGL((traceKernel<W, PER_SIMD, TOP>), dim3(blocks), dim3(64 * W), 0, s, dfp, T); }
+  void (*kernel)(const FrameParams*, TraceArgs);
   switch (waves) {
-    case 1u: RT_LAUNCH_TRACE(1, 5, 0) break;
-    case 10u: RT_LAUNCH_TRACE(10, 4, 1) break;
-    case 12u: RT_LAUNCH_TRACE(12, 4, 1) break;
-    case 14u: RT_LAUNCH_TRACE(14, 4, 1) break;
-    case 16u: RT_LAUNCH_TRACE(16, 4, 1) break;
+    case 1u: kernel = traceKernel<1, 5, 0>; break;
+    case 10u: kernel = traceKernel<10, 4, 1>; break;
+    case 12u: kernel = traceKernel<12, 4, 1>; break;
+    case 14u: kernel = traceKernel<14, 4, 1>; break;
+    case 16u: kernel = traceKernel<16, 4, 1>; break;
     default: setError("launchTrace: no kernel variant with %u waves", waves); return -1;
   }
-#undef RT_LAUNCH_TRACE
+  launch(kernel, dim3(blocks), dim3(64 * waves), s, start, stop, c->dParams + c->slot, T);
   const uint32_t counterMask = 15u;
   if (countRays && !deeper && !c->rayCountersInFlight && (c->traceLaunches < 8u || (c->traceLaunches & counterMask) == 0u)) {     // the first frames, then every 16th: ray counters and split demand, for later launches
     RT_HIP(hipMemcpyAsync(c->hostRayCounters, c->rayCounter32, 256 * 4, hipMemcpyDeviceToHost, s));
-    RT_HIP(hipMemcpyAsync(c->hostRayCounters + 256, c->splitCount, 4, hipMemcpyDeviceToHost, s));
+    RT_HIP(hipMemcpyAsync(c->hostRayCounters + 256, c->cur().splitCount, 4, hipMemcpyDeviceToHost, s));
     RT_HIP(hipMemcpyAsync(c->hostRayCounters + 258, c->traceStamps + 6, 16, hipMemcpyDeviceToHost, s)); c->traceSampleLaunch = c->traceLaunches;      // sum of the kernel's durations so far, start of this launch
     RT_HIP(hipEventRecord(c->evRayCounters, s));
     c->rayCountersInFlight = true;

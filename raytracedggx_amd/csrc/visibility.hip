@@ -14,7 +14,6 @@
 // rasterLarge -- one 64x4 pixel tile per workgroup, one pixel per lane, loops over the queued
 // large triangles (the ground slab's faces) and merges with a plain read-min-write.
 // Roofline: HBM; algorithmic bytes 8 B/pixel (clear) + 8 B/covered fragment.
-#include <hip/hip_ext.h>
 #include "rtggx_context.h"
 #include "rt_raster.h"
 
@@ -249,7 +248,7 @@ __global__ void __launch_bounds__(256) rasterSmall(const FrameParams fp, FramePa
     if (key == ~0ull) continue;
     unsigned long long* dst = vd + (size_t)py * fp.W + (size_t)px;
 #if RT_RASTER_PREREAD
-    // (the tile's word, rtggx_context.h visDirtyBuf: set by whoever finds the pixel still clear -- the first atomic on a pixel comes from such a lane)
+    // (the tile's word, rtggx_context.h VisTarget::dirty: set by whoever finds the pixel still clear -- the first atomic on a pixel comes from such a lane)
     const unsigned long long before = *dst;
     if (key < before) { atomicMin(dst, key); if (before == RT_VIS_CLEAR) dirty[(((uint32_t)py - rowBegin) >> 4) * tilesX + ((uint32_t)px >> 4)] = 1u; }
 #else
@@ -313,49 +312,42 @@ int launchVisibility(rtggx_context* c, const FrameParams& fp, hipStream_t s, hip
   const uint32_t begin = rb * fp.W, end = re * fp.W;
   if (end <= begin) return 0;
   // the target was cleared for this frame by the ray generation two frames back -- unless it was not (see clearVisDepth)
-  const uint32_t target = c->frameCounter % RT_VIS_RING;
-  auto& vc = c->visClearedAt[target];
-  auto& vf = c->visFlags[target];
-  uint32_t* const dirty = c->visDirtyBuf[target];
+  VisTarget& v = c->curVis();
+  uint32_t* const dirty = v.dirty;
   const uint32_t tilesX = (fp.W + 15) / 16, tilesY = (re - rb + 15) / 16;
-  if (!(vc.frame == c->frameCounter && vc.rows[0] <= rb && vc.rows[1] >= re)) {
-    hipLaunchKernelGGL(clearVisDepth, dim3((end - begin + 1023) / 1024), dim3(256), 0, s, c->visDepth, begin, end, c->largeCount, c->splitCount);
+  if (!(v.cleared.frame == c->frameCounter && v.cleared.rows[0] <= rb && v.cleared.rows[1] >= re)) {
+    hipLaunchKernelGGL(clearVisDepth, dim3((end - begin + 1023) / 1024), dim3(256), 0, s, v.depth, begin, end, c->largeCount, c->cur().splitCount);
     RT_HIP(hipMemsetAsync(dirty, 0, (size_t)tilesX * tilesY * 4, s));
-    ++c->visStandaloneClears;
   }
   // (cleared ahead over a superset of these rows: every word the clear knew of is 0 and every pixel clear, whatever the tiles' origin)
-  vf.rows[0] = rb; vf.rows[1] = re; vf.rasterFrame = c->frameCounter;
-  vc.frame = 0u;
+  v.flags.rows[0] = rb; v.flags.rows[1] = re; v.flags.rasterFrame = c->frameCounter;
+  v.cleared.frame = 0u;
   const uint32_t nt = c->mesh[0].numTris + c->mesh[1].numTris;
   FrameParams* const dst = c->slotUploaded ? (FrameParams*)nullptr : c->dParams + c->slot;
   c->slotUploaded = true;
   // (with no triangles at all the kernel still runs, for the constants)
   const dim3 grid(nt ? (nt + 4u * RT_RASTER_TPW - 1u) / (4u * RT_RASTER_TPW) : 1u);
   hipLaunchKernelGGL(rasterSmall, grid, dim3(256), 0, s, fp, dst, rb, re, (const float*)c->mesh[0].verts, (const uint32_t*)c->mesh[0].indices, c->mesh[0].numTris,
-                     (const float*)c->mesh[1].verts, (const uint32_t*)c->mesh[1].indices, c->mesh[1].numTris, c->visDepth, (LargeTri*)c->largeTris, c->largeCount, c->largeCapacity, dirty, tilesX);
-  if (nt) {
+                     (const float*)c->mesh[1].verts, (const uint32_t*)c->mesh[1].indices, c->mesh[1].numTris, v.depth, (LargeTri*)c->largeTris, c->largeCount, c->largeCapacity, dirty, tilesX);
+  if (nt) {      // the event rides on the pass's last kernel (rtggx_context.h)
     const dim3 lgrid((fp.W + 63) / 64, (re - rb + RT_LARGE_ROWS - 1) / RT_LARGE_ROWS);
-    if (done && c->attachEvents) {      // the event rides on the pass's last kernel (rtggx_context.h)
-      hipExtLaunchKernelGGL(rasterLarge, lgrid, dim3(256), 0, s, nullptr, done, 0, fp.W, rb, re, c->visDepth, (const LargeTri*)c->largeTris, (const uint32_t*)c->largeCount, c->largeCapacity, dirty, tilesX);
-      done = nullptr;
-    } else hipLaunchKernelGGL(rasterLarge, lgrid, dim3(256), 0, s, fp.W, rb, re, c->visDepth, (const LargeTri*)c->largeTris, (const uint32_t*)c->largeCount, c->largeCapacity, dirty, tilesX);
-  }
-  if (done) hipEventRecord(done, s);
+    launch(rasterLarge, lgrid, dim3(256), s, nullptr, done, fp.W, rb, re, v.depth, c->largeTris, c->largeCount, c->largeCapacity, dirty, tilesX);
+  } else if (done) hipEventRecord(done, s);
   RT_HIP(hipGetLastError());
   return 0;
 }
 
 int unpackVisDepth(rtggx_context* c, uint32_t* dVis, uint32_t* dDepth, hipStream_t s) {
   const uint32_t n = c->W * c->H;
-  hipLaunchKernelGGL(unpackVisDepthKernel, dim3((n + 255) / 256), dim3(256), 0, s, c->visDepth, dVis, dDepth, n);
+  hipLaunchKernelGGL(unpackVisDepthKernel, dim3((n + 255) / 256), dim3(256), 0, s, c->curVis().depth, dVis, dDepth, n);
   RT_HIP(hipGetLastError());
   return 0;
 }
 int packVisDepth(rtggx_context* c, const uint32_t* dVis, const uint32_t* dDepth, hipStream_t s) {
   const uint32_t n = c->W * c->H;
   // a caller's visibility: every tile may hold something
-  RT_HIP(hipMemsetAsync(c->visDirtyBuf[c->frameCounter % RT_VIS_RING], 0xFF, (size_t)((c->W + 15) / 16) * ((c->H + 15) / 16 + 1) * 4, s));
-  hipLaunchKernelGGL(packVisDepthKernel, dim3((n + 255) / 256), dim3(256), 0, s, c->visDepth, dVis, dDepth, n);
+  RT_HIP(hipMemsetAsync(c->curVis().dirty, 0xFF, (size_t)((c->W + 15) / 16) * ((c->H + 15) / 16 + 1) * 4, s));
+  hipLaunchKernelGGL(packVisDepthKernel, dim3((n + 255) / 256), dim3(256), 0, s, c->curVis().depth, dVis, dDepth, n);
   RT_HIP(hipGetLastError());
   return 0;
 }

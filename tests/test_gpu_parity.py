@@ -1212,7 +1212,7 @@ def test_every_stream_placement_free_running_equals_synchronised(built):
 
 def test_tile_words_follow_strips_uploads_and_skipped_passes(built):
     """Round 4: the visibility pass keeps a word per 16x16 tile of its target ("something was drawn here") and the kernels behind it leave
-    tiles whose word is 0 after a scalar load (rtggx_debug_tile_words; rtggx_context.h visDirtyBuf).  The words are only as good as their
+    tiles whose word is 0 after a scalar load (rtggx_debug_tile_words; rtggx_context.h VisTarget::dirty).  The words are only as good as their
     bookkeeping: tiles are counted from the pass's first row, the target is cleared two frames ahead by another frame's ray generation, a
     caller may upload a visibility buffer or skip a pass.  One context with the words, one without, through the same schedule of strip
     changes (rows that are no multiple of 16, growing and shrinking), a frame without ray tracing and an uploaded visibility buffer, and a model that changes shape -- every target of every frame identical inside the strip."""
