@@ -290,6 +290,15 @@ int  rtggx_debug_placement(rtggx_context* ctx, int force_small, uint32_t* key, u
  * fetching pixels to find that out; ray generation neither reads nor re-clears such a tile of the target (RayTracer.cpp:751-791 clears and
  * reads the whole target every frame).  enable = 0: every tile is treated as drawn, as in rounds 1-3.  Same images either way. */
 int  rtggx_debug_tile_words(rtggx_context* ctx, int enable);
+/* Diagnostic (still sky): per input set and 16x16 tile, ray generation counts the consecutive frames in which it found the tile's word 0
+ * while nothing a sky pixel's outputs depend on changed (camera, environment, rows, uploads ...: an "epoch").  A tile whose run is long enough
+ * holds, in that set, everything ray generation would store there, and is left alone; the reflection V pass leaves blocks alone whose sky
+ * texels it converted into the same image the frame before.  enable = 0: the runs are counted and nothing is left alone.  Same images
+ * either way. */
+int  rtggx_debug_static_sky(rtggx_context* ctx, int enable);
+/* ... and the current input set's runs under the current epoch, one word per tile of the most recent ray generation's grid (row-major,
+ * *tiles_x by *tiles_y; capacity in words).  *threshold: the run from which that ray generation left a tile alone.  Synchronises. */
+int  rtggx_debug_sky_runs(rtggx_context* ctx, uint32_t* runs, uint32_t capacity, uint32_t* tiles_x, uint32_t* tiles_y, uint32_t* threshold);
 /* Diagnostic: the two weights of the 4-wide collapse's objective (lbvh.hip "the 4-wide collapse"): a 4-wide node costs
  * area_weight x (its half-area / the root's) + tris_weight x (its triangles / all triangles) -- the chance that a random ray enters it,
  * and the chance that a ray STARTING on the mesh's surface (every ray of this path does) starts inside it.  set (may be null): weights for

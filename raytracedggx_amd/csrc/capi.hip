@@ -166,13 +166,16 @@ static int allocSet(rtggx_context* c, uint32_t i) {
   if (!s.hitQueue) RT_HIP(hipMalloc(&s.hitQueue, slots * 8));
   if (!s.binCount) { RT_HIP(hipMalloc(&s.binCount, (size_t)c->numBinsMax * 4)); RT_HIP(hipMemset(s.binCount, 0, (size_t)c->numBinsMax * 4)); }
   if (!s.splitList) RT_HIP(hipMalloc(&s.splitList, (size_t)RT_SPLIT_CAP * 4));
+  c->skyTiles = (size_t)((c->W + 15) / 16) * ((c->H + 15) / 16 + 1);      // (as many as a VisTarget has words: initContext)
+  if (!s.skyRun) { RT_HIP(hipMalloc(&s.skyRun, c->skyTiles * 4)); RT_HIP(hipMemset(s.skyRun, 0, c->skyTiles * 4)); }
+  c->breakSkyRuns();      // (a set with new buffers: nothing is in place in it)
   s.splitCount = c->largeCountBase + 2 + i;
   if (!s.evRead) RT_HIP(hipEventCreateWithFlags(&s.evRead, RT_EVENT_FLAGS));
   return 0;
 }
 static void freeSet(InputSet& s) {
   for (void* p : {(void*)s.normal, (void*)s.depth32, (void*)s.velocity, (void*)s.rtRefl, (void*)s.rtDiff, (void*)s.roughMetal, s.rayQueue, s.hitQueue,
-                  (void*)s.binCount, (void*)s.splitList}) hipFree(p);
+                  (void*)s.binCount, (void*)s.splitList, (void*)s.skyRun}) hipFree(p);
   if (s.evRead) hipEventDestroy(s.evRead);
   s = InputSet{};
 }
@@ -315,6 +318,7 @@ int rtggx_set_strip(rtggx_context* c, uint32_t rowBegin, uint32_t rowEnd) {
   if (rowBegin > rowEnd || rowEnd > c->H) { setError("rtggx_set_strip: bad rows [%u,%u) for height %u", rowBegin, rowEnd, c->H); return -1; }
   if (c->rayRate != 1u && (rowBegin > 0u || rowEnd < c->H)) { setError("rtggx_set_strip: rows [%u,%u) of %u: a context tracing one pixel in %u renders whole frames", rowBegin, rowEnd, c->H, c->rayRate); return -1; }
   c->rowBegin = rowBegin; c->rowEnd = rowEnd; c->toneMapDone = false;
+  c->breakSkyRuns();
   return 0;
 }
 
@@ -456,6 +460,7 @@ int rtggx_set_env(rtggx_context* c, int format, uint32_t size, uint32_t mips, co
   RT_CHECK_CTX(c);
   if (!data) { setError("rtggx_set_env: null data"); return -1; }
   RT_HIP(syncStreams(c));
+  c->breakSkyRuns();      // the sky behind every pixel is another one
   return decodeEnv(c, format, size, mips, data, bytes, c->streamMain);
 }
 
@@ -996,6 +1001,28 @@ int rtggx_debug_fuse_tone_map(rtggx_context* c, int mode) {
 int rtggx_debug_tile_words(rtggx_context* c, int enable) {
   RT_CHECK_CTX(c);
   c->useTileWords = enable != 0;
+  c->breakSkyRuns();
+  return 0;
+}
+// Still sky (rtggx_context.h InputSet::skyRun): enable = 0 -- the runs are still counted, but no tile is left alone for them.
+int rtggx_debug_static_sky(rtggx_context* c, int enable) {
+  RT_CHECK_CTX(c);
+  c->staticSky = enable != 0;
+  c->breakSkyRuns();
+  return 0;
+}
+// The current set's runs (0 where a word was written under another epoch than the current one), tile by tile of the most recent ray
+// generation's grid; *threshold: the run from which that ray generation left a tile alone.
+int rtggx_debug_sky_runs(rtggx_context* c, uint32_t* runs, uint32_t capacity, uint32_t* tilesX, uint32_t* tilesY, uint32_t* threshold) {
+  RT_CHECK_CTX(c);
+  const uint32_t n = c->skyGen.tilesX * c->skyGen.tilesY;
+  if (!runs || capacity < n || n > c->skyTiles) { setError("rtggx_debug_sky_runs: room for %u words", n); return -1; }
+  RT_HIP(syncStreams(c));
+  if (n) RT_HIP(hipMemcpy(runs, c->cur().skyRun, (size_t)n * 4, hipMemcpyDeviceToHost));
+  for (uint32_t i = 0; i < n; ++i) runs[i] = (runs[i] >> 8) == c->skyEpoch ? runs[i] & 0xFFu : 0u;
+  if (tilesX) *tilesX = c->skyGen.tilesX;
+  if (tilesY) *tilesY = c->skyGen.tilesY;
+  if (threshold) *threshold = RT_SKY_PREV_RUN + 1u;
   return 0;
 }
 int rtggx_debug_placement(rtggx_context* c, int forceSmall, uint32_t* key, uint32_t* where) {
@@ -1150,6 +1177,7 @@ int rtggx_upload(rtggx_context* c, int id, const void* src, size_t bytes) {
   RT_HIP(syncStreams(c));
   c->toneMapDone = false;      // (a tone map after an upload reads what was uploaded)
   c->curVis().flags.rasterFrame = 0u;      // ... and the tiles' words of this frame's visibility pass do not describe it (rtggx_context.h VisTarget::dirty)
+  c->breakSkyRuns();      // ... and what a still-sky tile relies on being in place may just have been replaced
   if (id == RTGGX_BUF_VISIBILITY || id == RTGGX_BUF_DEPTH) {
     // replace one half of the packed buffer
     uint32_t *dVis, *dDepth;
@@ -1242,6 +1270,7 @@ int rtggx_trace_rays(rtggx_context* c, const float* rays, uint32_t n, float* out
   RT_CHECK_CTX(c);
   if (!c->asBuilt || !c->haveConstants) { setError("rtggx_trace_rays: build_as / update_frame / update_as first"); return -1; }
   RT_HIP(syncStreams(c));   // the ray bins are shared with the frame path on stream B
+  c->breakSkyRuns();        // (... and a still-sky tile relies on its bins' counts being 0)
   { const int r = ensureParams(c); if (r) return r; }
   float *dR, *dO;
   RT_HIP(hipMalloc(&dR, (size_t)n * 32)); RT_HIP(hipMalloc(&dO, (size_t)n * 24));

@@ -72,6 +72,9 @@ struct Targets {
   // one word per 16x16 tile, counted from row tileRow0, tilesX to a row: 0 = the visibility pass drew nothing there, no pixel of it has a surface
   // (rtggx_context.h VisTarget::dirty; all ones where that is not known)
   const uint32_t* tileWords; int tilesX, tileRow0;
+  // still sky (rtggx_context.h InputSet::skyRun, RT_SKY_V_RUN): the set's run words, indexed like tileWords, and the epoch they count under;
+  // null: the reflection V pass converts every sky texel (launchDenoise decides)
+  const uint32_t* skyRun; uint32_t skyEpoch;
 };
 #define RT_SGPR(v) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(v)))      // a workgroup-uniform value the compiler may have computed in vector registers
 // Four of those words OR-ed together: scalar loads, one wait (the indices are uniform over the workgroup).
@@ -88,6 +91,17 @@ RT_DEV uint32_t tileWordsOr6(const uint32_t* words, uint32_t i0, uint32_t i1, ui
                : "=&s"(a), "=&s"(b), "=&s"(c), "=&s"(d), "=&s"(e), "=&s"(f)
                : "s"(words), "s"(RT_SGPR(i0 * 4u)), "s"(RT_SGPR(i1 * 4u)), "s"(RT_SGPR(i2 * 4u)), "s"(RT_SGPR(i3 * 4u)), "s"(RT_SGPR(i4 * 4u)), "s"(RT_SGPR(i5 * 4u)) : "memory");
   return a | b | c | d | e | f;
+}
+// The shortest run among six tiles' still-sky words (a word of another epoch: run 0): scalar loads again, one wait.
+RT_DEV uint32_t skyRunMin6(const uint32_t* words, uint32_t epoch, uint32_t i0, uint32_t i1, uint32_t i2, uint32_t i3, uint32_t i4, uint32_t i5) {
+  uint32_t w[6];
+  asm volatile("s_load_dword %0, %6, %7\n\ts_load_dword %1, %6, %8\n\ts_load_dword %2, %6, %9\n\ts_load_dword %3, %6, %10\n\ts_load_dword %4, %6, %11\n\ts_load_dword %5, %6, %12\n\ts_waitcnt lgkmcnt(0)"
+               : "=&s"(w[0]), "=&s"(w[1]), "=&s"(w[2]), "=&s"(w[3]), "=&s"(w[4]), "=&s"(w[5])
+               : "s"(words), "s"(RT_SGPR(i0 * 4u)), "s"(RT_SGPR(i1 * 4u)), "s"(RT_SGPR(i2 * 4u)), "s"(RT_SGPR(i3 * 4u)), "s"(RT_SGPR(i4 * 4u)), "s"(RT_SGPR(i5 * 4u)) : "memory");
+  uint32_t run = 0xFFu;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) run = min(run, (w[k] >> 8) == epoch ? w[k] & 0xFFu : 0u);
+  return run;
 }
 
 #define RT_LOG2E 1.44269504088896341f
@@ -231,6 +245,10 @@ __global__ void __launch_bounds__(256) spatialTiledKernel(Targets T) {
   { const uint32_t txLast = (uint32_t)T.tilesX - 1u, tx0 = (uint32_t)bx0 >> 4, tx1 = min(tx0 + 1u, txLast);
     const uint32_t ty0 = (uint32_t)(by0 - T.tileRow0) >> 4, ty1 = (uint32_t)(min(by0 + BH, T.rowEnd) - 1 - T.tileRow0) >> 4;
     const uint32_t r0 = ty0 * (uint32_t)T.tilesX, r1 = ty1 * (uint32_t)T.tilesX, rm = ((ty0 + ty1) >> 1) * (uint32_t)T.tilesX;
+    // Still sky: in all these tiles ray generation found nothing in this frame and in the one before it, under one epoch -- the sky texels
+    // this block would convert are the ones the previous frame's V pass converted, into the same image.  (The run words first, the tile
+    // words only where they do not settle it: a block over sky costs six scalar loads, as it did.)
+    if (MODE == 1 && T.skyRun != nullptr && skyRunMin6(T.skyRun, T.skyEpoch, r0 + tx0, r0 + tx1, rm + tx0, rm + tx1, r1 + tx0, r1 + tx1) >= RT_SKY_V_RUN) return;
     nothingDrawn = vertical ? tileWordsOr6(T.tileWords, r0 + tx0, r0 + tx1, rm + tx0, rm + tx1, r1 + tx0, r1 + tx1) == 0u
                             : tileWordsOr(T.tileWords, r0 + tx0, r0 + tx1, r0 + min(tx0 + 2u, txLast), r0 + min(tx0 + 3u, txLast)) == 0u; }
   if (nothingDrawn) {
@@ -658,7 +676,29 @@ static Targets makeTargets(rtggx_context* c, const FrameParams& fp, RowPass pass
   T.peerWorld = peers ? (int)c->peerWorld : 0;
   { uint32_t gb, ge; passRows(fp, ROWS_GBUFFER, gb, ge);      // the tiles are ray generation's
     T.tileWords = c->tileWords(gb, ge); T.tilesX = (int)((fp.W + 15) / 16); T.tileRow0 = (int)gb; }
+  T.skyRun = nullptr; T.skyEpoch = 0u;
   return T;
+}
+
+// Still sky in the reflection V pass (spatialTiledKernel<1>): may this frame's pass leave blocks over still sky alone?  It may when what it
+// would store there is what the PREVIOUS reflection V pass stored, into the same image:
+//     this frame's ray generation has run, under the epoch that is still current (nothing has broken the runs since: an upload, another
+//       environment, ...), over the rows the run words are indexed by -- the words in this set are this frame's;
+//     the previous reflection V pass was this frame's or the frame before's (a frame without rtggx_denoise leaves FilteredOut1 a frame old),
+//       had ray generation's results of its own frame under the same epoch, covered the same rows and wrote the same images
+//       (FilteredOut as well, or FilteredOut1 alone: fltRflIsFltDff).
+// Records this pass as the previous one of the next.
+static bool skyVPassMaySkip(rtggx_context* c, const Targets& TV, uint32_t gbufferRow0, uint32_t* epoch) {
+  rtggx_context::SkyV now;
+  const bool genValid = c->skyGen.any && c->skyGen.frame == c->frameCounter && c->skyGen.epoch == c->skyEpoch && c->skyGen.rows[0] == gbufferRow0;
+  now.any = true; now.fltRflNull = TV.fltRfl == nullptr; now.frame = c->frameCounter; now.genEpoch = genValid ? c->skyGen.epoch : 0xFFFFFFFFu;
+  now.rows[0] = (uint32_t)TV.rowBegin; now.rows[1] = (uint32_t)TV.rowEnd;
+  const rtggx_context::SkyV& was = c->skyV;
+  const bool may = c->staticSky && genValid && was.any && (was.frame == now.frame || was.frame + 1u == now.frame) && was.genEpoch == now.genEpoch
+                   && was.rows[0] == now.rows[0] && was.rows[1] == now.rows[1] && was.fltRflNull == now.fltRflNull;
+  c->skyV = now;
+  *epoch = c->skyEpoch;
+  return may;
 }
 
 int launchDenoise(rtggx_context* c, const FrameParams& fp, int useLds, hipStream_t s, hipEvent_t done, bool fuseToneMap) {
@@ -676,6 +716,8 @@ int launchDenoise(rtggx_context* c, const FrameParams& fp, int useLds, hipStream
   // images would be identical, 8 bytes per pixel each); rtggx_readback(RTGGX_BUF_FLT_RFL) then returns FilteredOut1 (capi.hip).
   c->fltRflIsFltDff = !anyDiffuse;
   Targets TVr = TV; if (!anyDiffuse) TVr.fltRfl = nullptr;
+  { uint32_t epoch;      // (the direct-access variant converts every sky texel; it counts as the previous pass all the same)
+    if (skyVPassMaySkip(c, TVr, (uint32_t)TV.tileRow0, &epoch) && useLds) { TVr.skyRun = c->cur().skyRun; TVr.skyEpoch = epoch; } }
   if (useLds) {
     hipLaunchKernelGGL(spatialTiledKernel<0>, grid(TH, 64, 4), block, 0, s, TH); mark(4);
     hipLaunchKernelGGL(spatialTiledKernel<1>, grid(TV, RT_VBW, RT_VBH), block, 0, s, TVr); mark(5);

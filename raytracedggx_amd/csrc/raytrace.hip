@@ -23,6 +23,7 @@
 // rayGen 18 B/pixel (+64 B per queued ray); trace 64 B ray + 16 B hit per ray + the scene arrays
 // once; shade 64+16 B in, 4 B out per ray.  The BVH (<= 14 MB) is L2/MALL resident, so traversal is
 // bound by L1 request rate, issue and latency, not by HBM (DESIGN.md "Roofline").
+#include <cstring>
 #include "rt_queue.h"
 #include "rt_traverse.h"
 
@@ -271,6 +272,9 @@ struct GenArgs {
   // target read here; visDirtyNext: of visNext; where the words are not known both point at words that are all ones (read / clear every
   // tile).  The words of visNext's tiles end as 0 (visDirtyNextOut: the target's own words)
   const uint32_t* visDirty; const uint32_t* visDirtyNext; uint32_t* visDirtyNextOut;
+  // still sky (rtggx_context.h InputSet::skyRun, RT_SKY_PREV_RUN): the previous set's run words, this set's, the epoch (24 bits) they count
+  // under, and the previous run from which a tile without a surface is left alone (above RT_SKY_RUN_CAP: never)
+  const uint32_t* skyPrev; uint32_t* skyOut; uint32_t skyEpoch, skyPrevRun;
   uint32_t* normalOut; uint16_t* roughMetalOut; uint32_t* velocityOut; uint32_t* reflOut; uint32_t* diffOut;
   const uint16_t* roughMetalPrev;   // the previous frame's input set = what this target held before this frame
   const uint32_t* diffPrev;         // likewise RayTracingOut1, or null: the hit shading carries it over (launchShade)
@@ -355,11 +359,23 @@ __global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) rayGenKernel(const Fra
   const uint32_t py = A.rowBegin + (tile / A.tilesX) * 16 + (wave >> 1) * 8 + (lane >> 3);
   const bool inside = px < fp.W && py < A.rowEnd;
   const bool traced = RATE == 1 || quadTraced(px, py, fp.g.FrameIndex);
-  // (two scalar loads, one wait: as two vector loads in front of the kernel's first fetch they cost ray generation 10 us in the frame)
-  uint32_t wordHere, wordNext;
-  asm volatile("s_load_dword %0, %2, %4\n\ts_load_dword %1, %3, %4\n\ts_waitcnt lgkmcnt(0)" : "=&s"(wordHere), "=&s"(wordNext) : "s"(A.visDirty), "s"(A.visDirtyNext), "s"(tile * 4u) : "memory");
+  // (three scalar loads, one wait: as vector loads in front of the kernel's first fetch two of them cost ray generation 10 us in the frame)
+  uint32_t wordHere, wordNext, skyWord;
+  asm volatile("s_load_dword %0, %3, %6\n\ts_load_dword %1, %4, %6\n\ts_load_dword %2, %5, %6\n\ts_waitcnt lgkmcnt(0)"
+               : "=&s"(wordHere), "=&s"(wordNext), "=&s"(skyWord) : "s"(A.visDirty), "s"(A.visDirtyNext), "s"(A.skyPrev), "s"(tile * 4u) : "memory");
   const bool drawn = wordHere != 0u;                                    // uniform over the workgroup
   const bool clearNext = A.visNext != nullptr && wordNext != 0u;
+  // Still sky: the tile's run of frames without a surface under this epoch goes on or ends (a plain store from one lane; at rate 4 it
+  // always ends: this path is rate 1's).  A tile whose run is long enough holds, in this set, everything the rest of this kernel would
+  // store there (RT_SKY_PREV_RUN).  Not where the target two frames on wants clearing: its word is 0 wherever this tile's run can be long
+  // enough (that target was drawn into RT_VIS_RING - 2 = RT_SETS frames ago), unless the words are not known -- such a tile takes the long
+  // path, whose registers a second copy of that clear in here would raise by two (a wave per SIMD less).  Uniform over the workgroup.
+  const uint32_t skyPrevRun = (skyWord >> 8) == A.skyEpoch ? skyWord & 0xFFu : 0u;
+  const uint32_t skyWordOut = (A.skyEpoch << 8) | (drawn || RATE != 1 ? 0u : min(skyPrevRun + 1u, RT_SKY_RUN_CAP));      // (stored below, beside the other word)
+  if (RATE == 1 && !drawn && !clearNext && skyPrevRun >= A.skyPrevRun) {
+    if (threadIdx.x == 0) A.skyOut[tile] = skyWordOut;
+    return;
+  }
   const EnvRef env{A.env, A.envSize, A.envMips, A.envMipOffset};
   bool wantRefl = false, wantDiff = false;
   RayRec rr, rd;
@@ -475,7 +491,7 @@ __global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) rayGenKernel(const Fra
       } else if (A.diffPrev != nullptr) A.diffOut[pix] = A.diffPrev[pix];      // RayTracingOut1 keeps what it held: carried over from the previous frame's set, here or by shadeKernel (launchShade)
     }
   }
-  if (clearNext && threadIdx.x == 0) A.visDirtyNextOut[tile] = 0u;      // (read above by this workgroup only)
+  if (threadIdx.x == 0) { A.skyOut[tile] = skyWordOut; if (clearNext) A.visDirtyNextOut[tile] = 0u; }      // (visDirtyNext: read above by this workgroup only)
   if constexpr (RATE == 4) { rayGenQuadBin(A, wantRefl, wantDiff, rr, rd); return; }
 
   // wave-level compaction into this wave's own bin (rt_queue.h): reflection rays first, then diffuse rays
@@ -788,6 +804,38 @@ __global__ void __launch_bounds__(256) reconstructKernel(const FrameParams* __re
 // =========================================================================================================
 // host side
 // =========================================================================================================
+// Still sky: the epoch this frame's ray generation counts its tiles' runs under (rtggx_context.h InputSet::skyRun, RT_SKY_PREV_RUN).  A run
+// says "the tile had no surface in so many consecutive ray generations, and nothing its outputs depend on changed meanwhile": the epoch is
+// bumped -- every run starts again from 0, every tile is written in full for RT_SKY_PREV_RUN frames -- when this ray generation differs
+// from the one before it in anything that enters a sky pixel's outputs or the bookkeeping the skipped epilogue keeps:
+//     the camera        rg.ProjToWorld, rg.EyePt, compared bit for bit (the sample rebuilds them from the same matrices every frame and
+//                       changes them when the user drags the mouse; the jitter, the frame index and the model's turn do not enter)
+//     the frame before  was not a ray generation's: a set in the ring went by without one (rtggx_render_visibility alone), so "the
+//                       previous set" is not the previous ray generation's
+//     the rows          another strip: tiles count from the pass's first row
+//     the bins          ray rate, adaptive split on / off, slice shift: which bins a tile has, and whether the cost records are kept
+//     the stream        the previous set's words are ordered before this kernel by stream order only
+// and by breakSkyRuns() where an entry point changes the rest: rtggx_set_env, rtggx_upload, rtggx_set_strip, rtggx_trace_rays (it refills a
+// set's bins), growBins, rtggx_debug_tile_words, rtggx_debug_static_sky.  Tile words that fall back to "all ones" (a foreign or uploaded
+// visibility buffer, a traversal-bound frame) need nothing: every tile reads as drawn, which ends its run.
+// -DRT_SKY_NO_CAMERA_CHECK leaves the camera out: tests/test_gpu_static_sky.py must fail with it (and does).
+static uint32_t skyEpochForGen(rtggx_context* c, const FrameParams& fp, uint32_t rb, uint32_t re, hipStream_t sGen, bool adaptive, uint32_t sliceShift) {
+  rtggx_context::SkyGen now;
+  now.any = true; now.adaptive = adaptive; now.frame = c->frameCounter; now.rows[0] = rb; now.rows[1] = re; now.rate = c->rayRate; now.sliceShift = sliceShift; now.stream = sGen;
+  now.tilesX = (fp.W + 15u) / 16u; now.tilesY = (re - rb + 15u) / 16u;
+  memcpy(now.camera, fp.rg.ProjToWorld, 64); memcpy(now.camera + 16, fp.rg.EyePt, 16);
+  const rtggx_context::SkyGen& was = c->skyGen;
+  bool same = was.any && (was.frame == now.frame || was.frame + 1u == now.frame) && was.rows[0] == rb && was.rows[1] == re && was.rate == now.rate
+              && was.adaptive == adaptive && was.sliceShift == sliceShift && was.stream == sGen;
+#ifndef RT_SKY_NO_CAMERA_CHECK
+  same = same && memcmp(was.camera, now.camera, sizeof now.camera) == 0;
+#endif
+  if (!same) c->breakSkyRuns();
+  now.epoch = c->skyEpoch;
+  c->skyGen = now;
+  return now.epoch;
+}
+
 int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hipStream_t s, hipEvent_t done) {
   uint32_t rb, re;
   passRows(fp, ROWS_GBUFFER, rb, re);
@@ -834,6 +882,15 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
   G.binWork = adaptive ? c->binWork : nullptr; G.splitList = set.splitList; G.splitCount = set.splitCount;
   G.frontWork = RT_SPLIT_FRONT < splitWork ? RT_SPLIT_FRONT : splitWork;
   G.splitWork = splitWork; G.splitMaxShift = splitMaxShift < 3u ? splitMaxShift : 3u; G.splitCap = splitCap < RT_SPLIT_CAP ? splitCap : RT_SPLIT_CAP;
+  // still sky: the runs are kept either way; with rtggx_debug_static_sky(ctx, 0) no run is ever long enough
+  G.skyEpoch = skyEpochForGen(c, fp, rb, re, sGen, adaptive, sliceShift);
+  if (c->skyEpochWrapped) {      // once in 2^24 bumps: no word of an earlier time round may meet its epoch again
+    RT_HIP(hipDeviceSynchronize());
+    for (auto& st : c->sets) RT_HIP(hipMemset(st.skyRun, 0, c->skyTiles * 4));
+    RT_HIP(hipStreamSynchronize(nullptr));
+    c->skyEpochWrapped = false;
+  }
+  G.skyPrev = c->prev().skyRun; G.skyOut = set.skyRun; G.skyPrevRun = c->staticSky ? RT_SKY_PREV_RUN : RT_SKY_RUN_CAP + 1u;
   // ray generation on stream C, the traversal on stream B behind it: the event rides on ray generation
   FrameEvents& ev = c->frameEvents(c->frameCounter);
   launch(quad ? rayGenKernel<4> : rayGenKernel<1>, dim3(quad ? numBins : G.numTiles), dim3(256), sGen, nullptr, sGen != s ? ev.gen : nullptr, c->dParams + c->slot, G);

@@ -39,6 +39,21 @@
 // target it clears must be one nobody reads any more: frame f + 2 - RT_VIS_RING's, whose last reader the host has waited for (InputSet::evRead).
 #define RT_VIS_RING (RT_SETS + 2)
 #define RT_VIS_CLEAR 0x00FFFFFF00000000ull      // (D24 = 1.0) << 32 | nothing drawn
+// Still sky (InputSet::skyRun): ray generation of frame f leaves a tile alone when the tile's word was 0, under one epoch, in frame f and
+// in the RT_SKY_PREV_RUN frames before it.  Derived, not tuned -- everything the kernel would store there must be in place already:
+//   * this set's G-buffer and traced texels were written in frame f - RT_SETS: that frame found the tile without a surface under this
+//     epoch (same camera, same environment) -- frames f - 1 .. f - RT_SETS in the run;
+//   * RoughMetal is carried from set to set where nothing is hit: all RT_SETS sets hold one value once the tile has had no surface
+//     in RT_SETS consecutive frames -- the same frames;
+//   * this set's bin counts are 0 WITHOUT a split mark: frame f - RT_SETS wrote them from the cost record (binWork, two of them by frame
+//     parity) that the traversal of frame f - RT_SETS - 2 left: that frame had no rays here either -- f - RT_SETS - 1, f - RT_SETS - 2 in
+//     the run as well; both cost records then read 0 (zeroed by the ray generations of frames f - 1 and f - 2 or found 0 by them, and
+//     the traversal does not touch the bins of a tile whose word is 0).
+// The reflection V pass (denoise.hip) leaves a block alone when all its tiles have a run of RT_SKY_V_RUN: FilteredOut1 exists once, and the
+// previous frame's V pass stored the same conversion of the same sky texels there.
+#define RT_SKY_PREV_RUN (RT_SETS + 2)
+#define RT_SKY_V_RUN 2u
+#define RT_SKY_RUN_CAP 255u
 namespace rt {
 
 // What a build tells the host: written by the build's kernels, copied to pinned memory behind its last one.
@@ -152,7 +167,12 @@ struct InputSet {
   // (shift << 28) | (slice << 24) | bin, one entry per wave of a listed bin.  Per set: the visibility pass of the next frame, which empties
   // its set's list, may run beside this frame's traversal.  The count is a word of largeCountBase (zeroed by the previous frame's ray generation).
   uint32_t* splitList = nullptr; uint32_t* splitCount = nullptr;
-  hipEvent_t evRead = nullptr;       // the set's last reader done: the HOST waits for it before stream B is given work that overwrites the set
+  // "Still sky" (raytrace.hip rayGenKernel): one word per 16x16 tile of ray generation's grid, epoch << 8 | run.  run: the consecutive frames,
+  // this set's included and saturating at RT_SKY_RUN_CAP, in which ray generation found the tile's word 0 under one epoch (rtggx_context
+  // skyEpoch).  Written by the set's ray generation, read by the next frame's (earlier on the same stream, like roughMetalPrev) and by the
+  // set's own reflection V pass behind the traversal's event; protected by evRead like the set's other members.
+  uint32_t* skyRun = nullptr;
+  hipEvent_t evRead = nullptr;      // the set's last reader done: the HOST waits for it before stream B is given work that overwrites the set
   bool readRecorded = false;
 };
 
@@ -276,6 +296,15 @@ struct rtggx_context {
     const rt::VisTarget& v = curVis();
     return useTileWords && !traversalBound && v.flags.rasterFrame == frameCounter && v.flags.rows[0] == rb && v.flags.rows[1] == re ? v.dirty : visDirtyOnes;
   }
+  // Still sky (InputSet::skyRun; raytrace.hip skyEpochForGen is where the epoch is decided).  skyEpoch: 24 bits, bumped
+  // whenever something a sky tile's outputs depend on changes or the chain of consecutive ray generations breaks -- by skyEpochForGen from
+  // what it can compare frame to frame, by breakSkyRuns() from the entry points that change the rest.  skyGen: the facts of the most recent
+  // ray generation; skyV: of the most recent reflection V pass (denoise.hip launchDenoise decides from them whether this frame's may skip).
+  bool staticSky = true;         // rtggx_debug_static_sky
+  uint32_t skyEpoch = 1u; bool skyEpochWrapped = false; size_t skyTiles = 0;      // (skyTiles: words of a set's skyRun, as many as a VisTarget's)
+  void breakSkyRuns() { skyEpoch = (skyEpoch + 1u) & 0xFFFFFFu; if (skyEpoch == 0u) skyEpochWrapped = true; }
+  struct SkyGen { bool any = false, adaptive = false; uint32_t frame = 0, epoch = 0, rows[2] = {0, 0}, rate = 0, sliceShift = 0, tilesX = 0, tilesY = 0; hipStream_t stream = nullptr; float camera[20] = {}; } skyGen;
+  struct SkyV { bool any = false, fltRflNull = false; uint32_t frame = 0, genEpoch = 0, rows[2] = {0, 0}; } skyV;
   bool useTileWords = true;      // rtggx_debug_tile_words
   // Where the TRAVERSAL is the frame's period (two rays per pixel into a large mesh: it runs 96 % of the time) nobody asks the words:
   // workgroups over empty tiles that leave at once make the other stages' kernels run denser beside the traversal and stretch it -- dragon,

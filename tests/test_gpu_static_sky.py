@@ -1,0 +1,157 @@
+"""Still sky (rtggx_context.h InputSet::skyRun): ray generation leaves a 16x16 tile alone once the tile has had no surface
+for RT_SETS + 2 frames before this one while nothing a sky pixel's outputs depend on changed, and the reflection V pass leaves a block alone
+whose sky texels it converted into the same image the frame before.  Nothing a frame computes may change: one context with the feature
+beside one with rtggx_debug_static_sky(ctx, 0), every target of every frame bit for bit -- every frame, so that every input set is seen."""
+import numpy as np
+import pytest
+
+import assets
+from oracle import oracle as O
+
+pytestmark = pytest.mark.gpu
+
+RT_SETS = 4
+VK_UP, VK_DOWN = 0x26, 0x28
+
+
+def _targets(capi):
+    return (capi.BUF_VISIBILITY, capi.BUF_DEPTH, capi.BUF_NORMAL, capi.BUF_ROUGH_METAL, capi.BUF_VELOCITY, capi.BUF_RT_REFL, capi.BUF_RT_DIFF,
+            capi.BUF_FLT_RFL, capi.BUF_FLT_DFF, capi.BUF_TSS0, capi.BUF_TSS1, capi.BUF_BACKBUFFER)
+
+
+def test_static_sky_changes_no_buffer_through_every_event_that_ends_a_run(built):
+    """320x180, -dt 0.25: the bunny turns fast enough that tiles on its silhouette go sky -> drawn -> sky.  Stretches of still frames (long enough
+    for tiles to be left alone in every input set) between the events that must end the runs: a camera drag over several frames, diffuse
+    rays appearing and going (the bins grow, FilteredOut appears and goes), a strip whose rows are no multiple of 16, a frame with a
+    visibility pass only, a frame without the denoiser, an uploaded G-buffer target, the tile words off and on, ray rate 4 and back, another
+    environment.  Every target of both contexts is compared after every frame.
+    The test can fail: built with -DRT_SKY_NO_CAMERA_CHECK (raytrace.hip skyEpochForGen: the camera left out of the epoch; `EXTRA=-DRT_SKY_NO_CAMERA_CHECK`
+    in the environment of the build) it fails at the first frame of the drag -- `drag 1 (frame 12): buffer 5`, 35 515 of 57 600 texels of
+    RayTracingOut0: the sky of the tiles left alone still shows the old view.  Run once that way on an MI355X."""
+    from raytracedggx_amd import app, capi
+    W, H = 320, 180
+    args = ["-mesh", assets.path("bunny.obj"), "-env", assets.path("rnl_cross.dds"), "-width", W, "-height", H, "-sharedmem", "-dt", 0.25]
+    a, b = app.RayTracedGGX(args), app.RayTracedGGX(args)
+    targets = _targets(capi)
+    count = [0]
+
+    def check(label):
+        a.context.sync(); b.context.sync()
+        for bid in targets:
+            np.testing.assert_array_equal(a.context.readback(bid), b.context.readback(bid), err_msg="%s (frame %d): buffer %d" % (label, count[0], bid))
+        count[0] += 1
+
+    def frame(label, before=None, render=None):
+        for x in (a, b):
+            if before is not None:
+                before(x)
+            x.OnUpdate()
+            if render is not None:
+                render(x.context)
+            else:
+                x.OnRender()
+        check(label)
+
+    def still(label, n):
+        for k in range(n):
+            frame("%s, still %d" % (label, k))
+
+    def left_alone():
+        runs, threshold = a.context.sky_runs()
+        return int((runs >= threshold).sum())
+
+    try:
+        b.context.static_sky(False)
+        still("start", 3 * RT_SETS)
+        assert left_alone() > 0                                             # (the comparison is not vacuous here either; the 1080p test counts exactly)
+        # a camera drag over several frames (the events of test_scripted_camera_and_material_track)
+        frame("drag 1", lambda x: (x.OnLButtonDown(160, 90), x.OnMouseMove(150, 86)))
+        assert left_alone() == 0
+        frame("drag 2", lambda x: x.OnMouseMove(128, 80))
+        frame("drag 3", lambda x: (x.OnMouseMove(100, 84), x.OnMouseWheel(2.0)))
+        frame("drag 4", lambda x: (x.OnLButtonUp(0, 0), x.OnMouseMove(10, 10)))
+        still("after the drag", 3 * RT_SETS)
+        assert left_alone() > 0
+        # the ground's metallic below 1 and back: diffuse rays, larger bins, the diffuse filter passes and FilteredOut come and go
+        frame("metallic down", lambda x: x.OnKeyUp(VK_DOWN))
+        still("diffuse", RT_SETS + 1)
+        frame("metallic up", lambda x: x.OnKeyUp(VK_UP))
+        still("all metal again", 3 * RT_SETS)
+        assert left_alone() > 0
+        # a strip whose rows are no multiple of 16, and back
+        frame("strip", lambda x: x.context.set_strip(37, 150))
+        still("strip", 3 * RT_SETS)
+        frame("whole frame", lambda x: x.context.set_strip(0, H))
+        still("whole frame", 3 * RT_SETS)
+        assert left_alone() > 0
+        # a frame with a visibility pass and nothing behind it: a set of the ring goes by without a ray generation
+        frame("visibility only", render=lambda c: c.render_visibility())
+        still("after visibility only", 3 * RT_SETS)
+        # a frame without the denoiser: FilteredOut1 is a frame old for the next V pass
+        frame("no denoise", render=lambda c: (c.render_visibility(), c.update_as(), c.ray_trace(), c.tone_map()))
+        still("after no denoise", 3 * RT_SETS)
+
+        # an uploaded G-buffer target: between ray generation and the denoiser the caller changes the normals (their low bit, the surface flag stays)
+        def uploaded(c):
+            c.render_visibility(); c.update_as(); c.ray_trace(); c.sync()
+            c.upload(capi.BUF_NORMAL, c.readback(capi.BUF_NORMAL) ^ np.uint32(1))
+            c.denoise(True); c.tone_map()
+        frame("upload", render=uploaded)
+        still("after the upload", 3 * RT_SETS)
+        assert left_alone() > 0
+        # the tile words off (every tile reads as drawn) and on again
+        frame("tile words off", lambda x: x.context.tile_words(False))
+        still("tile words off", 2)
+        assert left_alone() == 0
+        frame("tile words on", lambda x: x.context.tile_words(True))
+        still("tile words on", 3 * RT_SETS)
+        # one ray per 2x2 quad and back
+        frame("rate 4", lambda x: x.context.set_ray_rate(4))
+        still("rate 4", RT_SETS + 2)
+        frame("rate 1", lambda x: x.context.set_ray_rate(1))
+        still("rate 1", 3 * RT_SETS)
+        assert left_alone() > 0
+        # another (constant) environment map
+        env = assets.constant_env_rgba16f(0.5)
+        frame("environment", lambda x: x.context.set_env(capi.FORMAT_RGBA16F, 1, 1, env))
+        assert left_alone() == 0
+        still("after the environment", 3 * RT_SETS)
+        assert left_alone() > 0
+    finally:
+        a.OnDestroy(); b.OnDestroy()
+
+
+def test_static_sky_leaves_the_sky_tiles_of_the_1080p_frame_alone(built):
+    """The path is taken, and exactly where it should be: 1920x1080, 2 x RT_SETS still frames; the run words of the current set are at or
+    above the threshold in exactly the tiles where the oracle's visibility buffer has nothing in each of the last `threshold` frames -- at
+    least half of the frame's tiles (the bunny frame is about three quarters sky) -- and nowhere in the first frame after a camera move."""
+    from raytracedggx_amd import app
+    W, H = 1920, 1080
+    tx, ty = (W + 15) // 16, (H + 15) // 16
+    a = app.RayTracedGGX(["-mesh", assets.path("bunny.obj"), "-env", assets.path("rnl_cross.dds"), "-width", W, "-height", H, "-sharedmem"])
+    o = O.Oracle(W, H)
+    try:
+        v, i, _ = O.obj_import(assets.path("bunny.obj"))
+        o.set_mesh(1, v, i)
+        sky = []                                                            # per frame: the tiles without a covered pixel
+        for f in range(2 * RT_SETS):
+            a.OnUpdate(); a.OnRender(); a.context.sync()
+            o.set_frame_constants(a.frame_constants().tobytes()[:704] + o.get_frame_constants().tobytes()[704:])
+            o.update_as(); o.render_visibility()
+            vis = np.zeros((ty * 16, tx * 16), np.uint32)
+            vis[:H, :W] = o.buffer(O.BUF_VISIBILITY).reshape(H, W)
+            sky.append(~(vis.reshape(ty, 16, tx, 16) != 0).any(axis=(1, 3)))
+        runs, threshold = a.context.sky_runs()
+        assert runs.shape == (ty, tx) and RT_SETS < threshold <= 2 * RT_SETS
+        want = np.logical_and.reduce(sky[-threshold:])
+        print("tiles %d, without a surface in the last frame %d, in each of the last %d frames %d, run >= %d in %d"
+              % (tx * ty, int(sky[-1].sum()), threshold, int(want.sum()), threshold, int((runs >= threshold).sum())))
+        np.testing.assert_array_equal(runs >= threshold, want)
+        assert int(want.sum()) >= tx * ty // 2
+        a.OnLButtonDown(960, 540); a.OnMouseMove(900, 520)
+        a.OnUpdate(); a.OnRender()
+        a.OnLButtonUp(900, 520)
+        runs, threshold = a.context.sky_runs()
+        assert int((runs >= threshold).sum()) == 0 and int(runs.max()) == 1
+    finally:
+        a.OnDestroy(); o.close()
