@@ -58,7 +58,7 @@ def lib():
                      "orc_env_copy", "orc_build_as", "orc_set_bvh", "orc_bvh_info", "orc_bvh_copy", "orc_update_frame",
                      "orc_set_frame_constants", "orc_get_frame_constants", "orc_halton", "orc_update_as",
                      "orc_get_inv_worlds", "orc_transform_sh", "orc_set_sh", "orc_render_visibility", "orc_set_visibility",
-                     "orc_ray_trace", "orc_denoise", "orc_tone_map", "orc_flip_parity", "orc_get_parity", "orc_trace_rays",
+                     "orc_ray_trace", "orc_denoise", "orc_denoise_pass", "orc_tone_map", "orc_flip_parity", "orc_get_parity", "orc_trace_rays",
                      "orc_environment", "orc_mesh_info", "orc_mesh_copy"):
             fn = getattr(L, name)
             if fn.argtypes is None:
@@ -237,6 +237,17 @@ class Oracle:
 
     def tone_map(self):
         self.L.orc_tone_map(self.h)
+
+    DENOISE_PASSES = {"h_refl": 0, "v_refl": 1, "h_diff": 2, "v_diff": 3, "temporal": 4}
+
+    def denoise_pass(self, which):
+        """One pass of the chain on the buffers as they stand (orc_denoise_pass): "h_refl", "v_refl", "h_diff", "v_diff" or
+        "temporal".  The parity is the caller's (flip_parity); inputs are written through buffer(id, copy=False)."""
+        if self.L.orc_denoise_pass(self.h, C.c_int(self.DENOISE_PASSES[which])) != 0:
+            raise ValueError("orc_denoise_pass: bad pass %r" % (which,))
+
+    def flip_parity(self):
+        self.L.orc_flip_parity(self.h)
 
     def render(self, eye, view_proj, dt):
         """OnUpdate + OnRender of the reference for one frame; returns the non-degenerate ray count."""

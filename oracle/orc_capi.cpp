@@ -176,7 +176,25 @@ void orc_tone_map(void* h) {   // Denoiser::ToneMap (Denoiser.cpp:77-103)
   const std::vector<uint64_t>& src = c->tss[c->frameParity];
   parallel_rows(c->threads, c->H, [&](uint32_t y) { for (uint32_t x = 0; x < c->W; ++x) tonemap_pixel(*c, (int)x, (int)y, src); });
 }
-// Single passes for isolated parity tests: 0 H_Refl, 1 V_Refl, 2 H_Diff, 3 V_Diff, 4 Temporal (parity must be set by caller)
+// Single passes for isolated parity tests: 0 H_Refl, 1 V_Refl, 2 H_Diff, 3 V_Diff, 4 Temporal (parity must be set by caller:
+// orc_flip_parity; no pass flips it).  Each reads and writes the buffers orc_denoise gives it -- the H passes write the scratch
+// TSS[parity], the V passes read it; the temporal pass reads FilteredOut1, velocity and the history TSS[!parity] and overwrites
+// TSS[parity] -- so a test that writes FilteredOut1 through orc_buffer and runs pass 4 alone isolates the temporal arithmetic.
+int orc_denoise_pass(void* h, int pass) {
+  Ctx* c = (Ctx*)h;
+  if (pass < 0 || pass > 4) return -1;
+  std::vector<uint64_t>& scratch = c->tss[c->frameParity];
+  const std::vector<uint64_t>& hist = c->tss[c->frameParity ^ 1u];
+  const int T = c->threads; const uint32_t W = c->W, H = c->H;
+  if (pass < 2) parallel_rows(T, H, [&](uint32_t y) { for (uint32_t x = 0; x < W; ++x) spatial_refl_pixel(*c, (int)x, (int)y, pass == 1, scratch); });
+  else if (pass < 4) parallel_rows(T, H, [&](uint32_t y) { for (uint32_t x = 0; x < W; ++x) spatial_diff_pixel(*c, (int)x, (int)y, pass == 3, scratch); });
+  else {
+    std::vector<uint64_t> out((size_t)W * H);
+    parallel_rows(T, H, [&](uint32_t y) { for (uint32_t x = 0; x < W; ++x) temporal_pixel(*c, (int)x, (int)y, hist, out); });
+    scratch.swap(out);
+  }
+  return 0;
+}
 void orc_flip_parity(void* h) { ((Ctx*)h)->frameParity ^= 1u; }
 uint32_t orc_get_parity(void* h) { return ((Ctx*)h)->frameParity; }
 

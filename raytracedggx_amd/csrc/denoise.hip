@@ -12,8 +12,9 @@
 //     structure-of-arrays, so that the lanes of a wave read consecutive words: conflict-free).  H pass: 64x4 pixels
 //     from a 96x4 tile (12 KB); V pass: 16x16 pixels from a 16x48 tile (24 KB).
 //   direct access (0): every tap fetches and unpacks its texel from global memory (L1/L2 hits).
-// Both evaluate the same weights: pow(x, 512) / pow(x, 32) as 9 / 5 squarings, and the Gaussian and depth
-// exponentials merged into one exp2 -- ~35 VALU instructions per tap instead of ~400 with libm calls.  The passes
+// Both evaluate the same weights, to the bit (tests/test_gpu_denoise_synthetic.py compares their words): pow(x, 512) / pow(x, 32) as
+// exp2(n log2 x) on an exact dot product (log2OfDot below), with the Gaussian and the depth exponential folded into the same
+// v_exp_f32 -- ~35 VALU instructions per tap instead of ~400 with libm calls.  The passes
 // are VALU-bound (33 taps per covered pixel); their HBM traffic (22-30 B/pixel/pass) is ~5% of the
 // time.  Out-of-range texels are the zeros D3D returns.
 #include <cstring>
