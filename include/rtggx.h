@@ -227,6 +227,26 @@ int  rtggx_set_ray_rate(rtggx_context* ctx, uint32_t pixels_per_ray);
  * Works with quarter-rate tracing (only traced pixels start paths) and on strips.  Takes effect from the next rtggx_render_visibility. */
 #define RTGGX_MAX_RECURSION_DEPTH 4u
 int  rtggx_set_max_recursion_depth(rtggx_context* ctx, uint32_t depth);
+/* Samples per pixel (RayTracer::SetSamplesPerPixel; the reference traces one): N = 1 (default: the reference's renderer, bit for bit), 2, 4
+ * or RTGGX_MAX_SAMPLES_PER_PIXEL; anything else is refused and the setting kept (DESIGN.md "Samples per pixel").
+ *   - at every pixel as at N = 1, bit for bit: visibility, depth, normal, rough/metal, velocity; background pixels (the environment along
+ *     -V, no ray and no averaging); RayTracingOut1 where metallic >= 1 (it keeps what it held);
+ *   - sample k = 0 .. N - 1 of a covered pixel is the one-sample frame's level-0 code -- computeReflection / computeDiffuse at depth 0, GGX
+ *     or VNDF (rtggx_set_sampler) -- with xi = getSampleParam(pixel, FrameIndex * N + k) in place of getSampleParam(pixel, FrameIndex)
+ *     (not wrapped: FrameIndex < 256).  At recursion depth D the whole path of D levels carries that sample's xi at every level, the
+ *     throughput multiplied forward as at N = 1.  So the samples of frame F are exactly those of N consecutive one-sample frames with the
+ *     frame indices F * N .. F * N + N - 1, and consecutive frames never repeat a sample inside the 256-frame period;
+ *   - the pixel's word, per image and component, in fp32 without contraction: acc = 0, then acc = acc + v_k for k = 0, 1, ..., N - 1 in
+ *     that order, v_k = c_k * T_k the value a one-sample frame packs (0 where sample k traces nothing: NoL <= 0); the word is
+ *     pack_r11g11b10(acc * (1 / N)) -- N is a power of two, the scaling exact.  RayTracingOut1 likewise where the pixel's metallic < 1.
+ *     No atomics and no order that depends on scheduling: the image is a pure function of the inputs;
+ *   - rtggx_ray_count / rtggx_ray_total count the rays of every sample and level, RtggxTimings.ray_trace covers all of them,
+ *     ray_trace_kernel is the first sample's level-0 traversal.
+ * Works at every recursion depth, with both samplers, on strips and with a deforming mesh.  N > 1 on a context at ray rate 4, and rate 4 on
+ * a context with N > 1, are refused (one asks for more rays, the other for fewer) and the context keeps what it had.  The first N > 1
+ * allocates 24 bytes per pixel of the full frame, released by rtggx_destroy.  Takes effect from the next rtggx_render_visibility. */
+#define RTGGX_MAX_SAMPLES_PER_PIXEL 8u
+int  rtggx_set_samples_per_pixel(rtggx_context* ctx, uint32_t samples);
 
 /* Build of both bottom-level structures (RayTracer::buildAccelerationStructures / BuildAccelerationStructures, RayTracer.cpp:676-716,
  * 158-233; the sample records the builds on the GPU timeline and waits once, RayTracedGGX.cpp:236): every step of the build --

@@ -259,6 +259,19 @@ static int initContext(rtggx_context* c, uint32_t width, uint32_t height, int de
   RT_HIP(hipStreamSynchronize(nullptr));
   return 0;
 }
+// What N > 1 samples per pixel need (rtggx_set_samples_per_pixel): allocated with the first N > 1, released by rtggx_destroy.
+int allocSamples(rtggx_context* c) {
+  if (c->sppAcc && c->sppParams) return 0;
+  const size_t n = (size_t)c->W * c->H;
+  if (!c->evSpp) RT_HIP(hipEventCreateWithFlags(&c->evSpp, hipEventDisableTiming));
+  if (!c->sppParams) RT_HIP(hipMalloc(&c->sppParams, sizeof(FrameParams) * RT_SLOTS * RTGGX_MAX_SAMPLES_PER_PIXEL));
+  if (!c->sppAcc) {
+    RT_HIP(hipMalloc(&c->sppAcc, n * 2u * 3u * sizeof(float)));
+    RT_HIP(hipMemset(c->sppAcc, 0, n * 2u * 3u * sizeof(float)));
+    RT_HIP(hipStreamSynchronize(nullptr));      // (the clear runs on the null stream, which this context's streams are not ordered against)
+  }
+  return 0;
+}
 }  // namespace rt
 
 using namespace rt;
@@ -299,6 +312,7 @@ void rtggx_destroy(rtggx_context* c) {
   for (auto& s : c->sets) freeSet(s);
   for (auto& v : c->vis) { hipFree(v.depth); hipFree(v.dirty); }
   hipFree(c->visDirtyOnes);
+  hipFree(c->sppAcc); hipFree(c->sppParams); destroyEvent(c->evSpp);
   hipFree(c->tss[0]); hipFree(c->tss[1]);
   hipFree(c->fltRfl); hipFree(c->fltDff); hipFree(c->largeTrisBuf[0]); hipFree(c->largeTrisBuf[1]); hipFree(c->largeCountBase); hipFree(c->rayCounter); hipFree(c->dParams);
   for (auto b : c->binWorkBuf) hipFree(b);
@@ -344,6 +358,7 @@ int rtggx_set_stream(rtggx_context* c, void* stream) {
   RT_HIP(syncStreams(c));
   if (stream) { c->streamMain = (hipStream_t)stream; c->externalStream = true; }
   else { c->streamMain = c->ownMain; c->externalStream = false; }
+  c->sppStream = nullptr;      // (everything has ended; the stream given up may not outlive this call)
   if (!c->asyncCompute) c->streamAS = c->streamMain;
   return 0;
 }
@@ -418,7 +433,7 @@ int rtggx_set_async_compute(rtggx_context* c, int enable) {
   RT_CHECK_CTX(c);
   if ((enable != 0) == c->asyncCompute) return 0;
   RT_HIP(syncStreams(c));
-  c->asyncCompute = enable != 0;
+  c->asyncCompute = enable != 0; c->sppStream = nullptr;
   c->streamAS = c->asyncCompute ? c->ownAS : c->streamMain;
   c->streamVis = c->asyncCompute ? c->ownVis : nullptr;
   c->evVisStream = nullptr; for (auto& f : c->frames) f.genFrame = 0u;
@@ -431,6 +446,7 @@ int rtggx_set_async_compute(rtggx_context* c, int enable) {
 int rtggx_set_ray_rate(rtggx_context* c, uint32_t pixelsPerRay) {
   RT_CHECK_CTX(c);
   if (pixelsPerRay != 1u && pixelsPerRay != 4u) { setError("rtggx_set_ray_rate: %u pixels per ray: 1 or 4", pixelsPerRay); return -1; }
+  if (pixelsPerRay != 1u && c->samplesRequested > 1u) { setError("rtggx_set_ray_rate: rate %u on a context tracing %u samples per pixel (rtggx_set_samples_per_pixel): one asks for fewer rays, the other for more", pixelsPerRay, c->samplesRequested); return -1; }
   if (pixelsPerRay != 1u && (c->rowBegin > 0u || c->rowEnd < c->H)) { setError("rtggx_set_ray_rate: rate %u on a strip (rows [%u,%u) of %u): whole frames only", pixelsPerRay, c->rowBegin, c->rowEnd, c->H); return -1; }
   if (pixelsPerRay == c->rayRate) return 0;
   RT_HIP(syncStreams(c));
@@ -447,6 +463,23 @@ int rtggx_set_max_recursion_depth(rtggx_context* c, uint32_t depth) {
   RT_CHECK_CTX(c);
   if (depth < 1u || depth > RTGGX_MAX_RECURSION_DEPTH) { setError("rtggx_set_max_recursion_depth: depth %u: 1 to %u", depth, RTGGX_MAX_RECURSION_DEPTH); return -1; }
   c->depthRequested = depth;
+  return 0;
+}
+
+// Samples per pixel (raytrace.hip launchShadeSamples; DESIGN.md "Samples per pixel"): 1, 2, 4 or 8.  Taken over by the next
+// rtggx_render_visibility.  The first N > 1 allocates the sums and the samples' constants (allocSamples); N = 1 never does.
+// No synchronisation and no end of the still-sky runs (rtggx_context.h RT_SKY_PREV_RUN): nothing a run vouches for changes with N.  A tile
+// without a surface has no covered pixel, so no sample pass stores anything in it -- its G-buffer and image words are ray generation's at
+// every N (background: the environment, no ray, no averaging); its bins are never written by a sample pass (the sample generation, the
+// shading passes and the resolve leave at the tile's word like every kernel behind the visibility pass; where the words read "all ones"
+// a bin without a covered pixel gets the count 0 without a mark -- the value the run vouches for); and the cost records and split lists
+// are ray generation's and the level-0 traversal's alone, which N does not touch.
+int rtggx_set_samples_per_pixel(rtggx_context* c, uint32_t samples) {
+  RT_CHECK_CTX(c);
+  if (samples != 1u && samples != 2u && samples != 4u && samples != 8u) { setError("rtggx_set_samples_per_pixel: %u samples per pixel: 1, 2, 4 or %u", samples, RTGGX_MAX_SAMPLES_PER_PIXEL); return -1; }
+  if (samples > 1u && c->rayRate != 1u) { setError("rtggx_set_samples_per_pixel: %u samples per pixel on a context tracing one pixel in %u (rtggx_set_ray_rate): one asks for more rays, the other for fewer", samples, c->rayRate); return -1; }
+  if (samples > 1u) { const int r = allocSamples(c); if (r) return r; }
+  c->samplesRequested = samples;
   return 0;
 }
 
@@ -815,7 +848,7 @@ int rtggx_render_visibility(rtggx_context* c) {
   if (!c->shDone && c->env.texels) { const int r = projectSH(c, c->streamAS); if (r) return r; }   // first frame only, RayTracer.cpp:345-350
   settleSetRead(c);      // (the previous frame ended without the kernel that would have carried its set's event)
   ++c->frameCounter;
-  c->maxDepth = c->depthRequested;
+  c->maxDepth = c->depthRequested; c->samples = c->samplesRequested;
   c->denoiseIssued = false; c->toneMapDone = false;
   c->selectSet(c->setAhead(1u));
   // the set was last read four frames ago: normally long done; a host that has run further ahead than that waits here (also what makes

@@ -552,6 +552,8 @@ struct ShadeArgs {
   const uint32_t* tileWords;      // one word per tile of this kernel, 0 = nothing was drawn there (rtggx_context.h VisTarget::dirty): no rays, nothing to carry
   // the spawning pass (SHADE_SPAWN): each ray's child goes back into the ray's own bin, in place (the same arrays as rays / hits / binCount)
   RayRec* spawnRays; HitKey* spawnHits; uint32_t* spawnCount; const float* cosSin;
+  // the accumulating passes (SHADE_ACCUM, SHADE_SPAWN_ACCUM): the fp32 sums of the two images, three floats per pixel
+  float* accRefl; float* accDiff;
 };
 
 // The shading passes of a path of recursion depth D (rtggx_set_max_recursion_depth; DESIGN.md "Recursion depth"): level d < D - 1 shades
@@ -559,7 +561,14 @@ struct ShadeArgs {
 // renderer, unchanged --, SHADE_FINAL_DEEP after it).  A path ends in the spawning pass where its ray misses, where a reflection-group
 // ray's preset is <= 0, and where NoL <= 0.  Ray flags: bit 0 the hit group (1: diffuse); bit 1 set where the image the path writes --
 // that of its level-0 ray's group -- differs from the group of the ray in hand (never at level 0).
-enum ShadePass { SHADE_FINAL = 0, SHADE_SPAWN = 1, SHADE_FINAL_DEEP = 2 };
+// With N > 1 samples per pixel (rtggx_set_samples_per_pixel; DESIGN.md "Samples per pixel") a path's value c * T is ADDED to the pixel's fp32
+// sum instead of being packed into the image: SHADE_ACCUM ends every path (the image from the ray's flags, as SHADE_FINAL_DEEP -- at level 0
+// bit 1 is clear), SHADE_SPAWN_ACCUM is SHADE_SPAWN for the paths that end in it.  One lane per (pixel, image) and pass, the passes in
+// stream order, sample after sample: the sum's order is k = 0, 1, ..., N - 1 whatever the scheduling (no atomics).  A sample that traces
+// nothing adds nothing: acc + 0 = acc.  resolveSamplesKernel packs the sums.
+enum ShadePass { SHADE_FINAL = 0, SHADE_SPAWN = 1, SHADE_FINAL_DEEP = 2, SHADE_ACCUM = 3, SHADE_SPAWN_ACCUM = 4 };
+constexpr bool shadeSpawns(int pass) { return pass == SHADE_SPAWN || pass == SHADE_SPAWN_ACCUM; }
+constexpr bool shadeAccumulates(int pass) { return pass == SHADE_ACCUM || pass == SHADE_SPAWN_ACCUM; }
 
 // computeReflection at recursion depth 1 (:424-484)
 RT_DEV f3 reflectionDepth1(const EnvRef& env, f2 rghMtl, f3 N, f3 V, f3 color) {
@@ -654,7 +663,7 @@ __global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) shadeKernel(const Fram
         const f2 rm = getRoughMetal(fp.mat, hInst, a.UV);
         f3 color = mk3(fp.mat.BaseColors[hInst][0], fp.mat.BaseColors[hInst][1], fp.mat.BaseColors[hInst][2]);
         const f3 V = -dir;
-        if constexpr (PASS != SHADE_SPAWN) {
+        if constexpr (!shadeSpawns(PASS)) {
           if (rm.y > 0.5f) col = reflectionDepth1(env, rm, N, V, color);
           else {
             if (diffuseGroup) color = color * (1.0f - rm.y);                 // :607
@@ -689,7 +698,7 @@ __global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) shadeKernel(const Fram
         }
       }
     }
-    if constexpr (PASS == SHADE_SPAWN) {
+    if constexpr (shadeSpawns(PASS)) {
       // compaction into the bin, in place: this round's records have been read (and waited for) before any lane writes
       const unsigned long long mask = __ballot(child);
       if (child) {
@@ -699,11 +708,16 @@ __global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) shadeKernel(const Fram
       spawned += (uint32_t)__popcll(mask);
       if (child) continue;
     }
+    if constexpr (shadeAccumulates(PASS)) {
+      float* acc = (((rc.z ^ (rc.z >> 1)) & 1u) != 0u ? A.accDiff : A.accRefl) + 3u * (size_t)rc.x;
+      acc[0] = acc[0] + col.x * rw.x; acc[1] = acc[1] + col.y * rw.y; acc[2] = acc[2] + col.z * rw.z;
+      continue;
+    }
     const uint32_t packed = packR11G11B10F(mk3(col.x * rw.x, col.y * rw.y, col.z * rw.z));
     const bool toDiff = PASS == SHADE_FINAL ? diffuseGroup : ((rc.z ^ (rc.z >> 1)) & 1u) != 0u;
     if (toDiff) A.diffOut[rc.x] = packed; else A.reflOut[rc.x] = packed;
   }
-  if constexpr (PASS == SHADE_SPAWN) { if ((threadIdx.x & 63u) == 0u) A.spawnCount[bin] = spawned; }
+  if constexpr (shadeSpawns(PASS)) { if ((threadIdx.x & 63u) == 0u) A.spawnCount[bin] = spawned; }
 }
 
 // =========================================================================================================
@@ -802,6 +816,132 @@ __global__ void __launch_bounds__(256) reconstructKernel(const FrameParams* __re
 }
 
 // =========================================================================================================
+// Kernels 5-7 (N > 1 samples per pixel only; rtggx_set_samples_per_pixel, DESIGN.md "Samples per pixel")
+// =========================================================================================================
+// Sample k of frame F is the sample of a one-sample frame with FrameIndex F * N + k (include/rtggx.h), and the frame index enters a frame
+// nowhere but getSampleParam -- in ray generation, in the spawning shading pass and below.  So sample k's kernels are given a COPY of the
+// frame's constants with that index, and ray generation (sample 0) and the spawning pass serve every sample as they are.
+__global__ void sampleParamsKernel(const FrameParams* __restrict__ src, FrameParams* __restrict__ dst, uint32_t samples) {
+  constexpr uint32_t words = sizeof(FrameParams) / 4u, indexWord = (offsetof(FrameParams, g) + offsetof(RtggxCBGlobal, FrameIndex)) / 4u;
+  for (uint32_t i = threadIdx.x; i < words * samples; i += blockDim.x) {
+    const uint32_t k = i / words, w = i % words, v = reinterpret_cast<const uint32_t*>(src)[w];
+    reinterpret_cast<uint32_t*>(dst + k)[w] = w == indexWord ? v * samples + k : v;
+  }
+}
+
+// Sample k > 0: the rays ray generation would queue for a frame with sample k's index, into the same bins -- whose rays of the sample
+// before have been shaded.  The primary surface comes from the visibility word again (rayGenKernel's arithmetic); nothing of the G-buffer,
+// the images, the sky runs, the next frame's target or the adaptive split is touched: a bin's count is written without a mark, and the
+// traversal of these rays (launchTrace with a spill part) neither splits nor records costs.  A tile whose word is 0 has no bin with a ray
+// in it, now as before.
+struct SampleGenArgs {
+  const unsigned long long* visDepth; const float4* fat0; const float4* fat1; const float* cosSin;
+  RayRec* rays; HitKey* hits; uint32_t* binCount; uint32_t binSlots;
+  const uint32_t* tileWords; uint32_t tilesX, rowBegin, rowEnd;
+};
+__global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) sampleGenKernel(const FrameParams* __restrict__ fpp, SampleGenArgs A) {
+  const FrameParams& fp = *fpp;
+  const uint32_t tile = blockIdx.x;
+  { uint32_t word;
+    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(word) : "s"(A.tileWords), "s"(tile * 4u) : "memory");
+    if (word == 0u) return; }
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const uint32_t px = (tile % A.tilesX) * 16 + (wave & 1u) * 8 + (lane & 7u);
+  const uint32_t py = A.rowBegin + (tile / A.tilesX) * 16 + (wave >> 1) * 8 + (lane >> 3);
+  bool wantRefl = false, wantDiff = false;
+  RayRec rr, rd;
+  if (px < fp.W && py < A.rowEnd) {
+    const uint32_t W = fp.W, H = fp.H;
+    const size_t pix = (size_t)py * W + px;
+    uint32_t visibility = (uint32_t)A.visDepth[pix];
+    uint32_t s = py * W + px;      // getSampleParam :394-406
+    s = rng(s); s += fp.g.FrameIndex; s = rng(s); s %= 256u;
+    const float xiY = (float)(rng(s) & 0xffffu) / 65536.0f, cosPhi = A.cosSin[s], sinPhi = A.cosSin[256 + s];
+    if (visibility > 0) {      // getPrimarySurface :277-333, the covered branch
+      --visibility;
+      const uint32_t inst = visibility >> 24;
+      uint32_t prim = visibility & 0xFFFFFFu;
+      asm volatile("" : "+v"(prim));      // see shadeKernel
+      f2 screenPos; screenPos.x = ((float)px + 0.5f) / (float)W * 2.0f - 1.0f; screenPos.y = ((float)py + 0.5f) / (float)H * 2.0f - 1.0f;
+      screenPos.y = -screenPos.y;
+      const f3 eye = mk3(fp.rg.EyePt[0], fp.rg.EyePt[1], fp.rg.EyePt[2]);
+      const Tri3 v = getVertices(inst ? A.fat1 : A.fat0, prim);
+      const M4 wvp = cbLoad4x4(fp.g.WorldViewProjs[inst]);
+      f4 p[3];
+      for (int k = 0; k < 3; ++k) p[k] = mulPoint(v.pos[k], wvp);
+      screenPos.x -= fp.rg.ProjBias[0]; screenPos.y -= fp.rg.ProjBias[1];
+      const f2 bary = calcBarycentrics(p, screenPos);
+      const Attrib a = interpAttrib(v, bary.x, bary.y);
+      const f3 color = mk3(fp.mat.BaseColors[inst][0], fp.mat.BaseColors[inst][1], fp.mat.BaseColors[inst][2]);
+      const f2 rghMtl = getRoughMetal(fp.mat, inst, a.UV);
+      const f4 P4 = mulPoint(a.Pos, cbLoad4x3(fp.g.Worlds[inst]));
+      const f3 P = mk3(P4.x, P4.y, P4.z);
+      const f3 N = normalize3(mulDir(a.Nrm, cbLoad3x3(inst ? fp.g.WorldIT1 : fp.g.WorldITs0)));
+      const f3 V = normalize3(eye - P);
+      const uint32_t skip = (inst << 24) | prim;
+      {  // computeReflection depth 0 :424-484
+        const bool vndf = (fp.flags & RT_FLAG_VNDF) != 0u;      // uniform
+        const f3 Hh = reflectionHalfVector(vndf, N, V, rghMtl.x * rghMtl.x, cosPhi, sinPhi, xiY);
+        const f3 R = reflect3(-V, Hh);
+        const float NoL = dot3(N, R);
+        if (NoL > 0.0f) {   // :459
+          const f3 w = reflectionWeight(vndf, N, V, Hh, NoL, rghMtl, color);
+          wantRefl = true;
+          rr.ox = P.x; rr.oy = P.y; rr.oz = P.z; rr.dx = R.x; rr.dy = R.y; rr.dz = R.z;
+          rr.pixel = (uint32_t)pix; rr.skip = skip; rr.flags = 0u;
+          rr.wx = w.x; rr.wy = w.y; rr.wz = w.z;
+        }
+      }
+      if (rghMtl.y < 1.0f) {   // :559-564, computeDiffuse depth 0 :486-535
+        const f3 dir = diffuseDirection(N, cosPhi, sinPhi, xiY);
+        wantDiff = true;
+        rd.ox = P.x; rd.oy = P.y; rd.oz = P.z; rd.dx = dir.x; rd.dy = dir.y; rd.dz = dir.z;
+        rd.pixel = (uint32_t)pix; rd.skip = skip; rd.flags = 1u;
+        rd.wx = color.x * (1.0f - 0.04f); rd.wy = color.y * (1.0f - 0.04f); rd.wz = color.z * (1.0f - 0.04f);   // :532
+      }
+    }
+  }
+  // wave-level compaction into this wave's own bin, as in rayGenKernel<1>: reflection rays first, then diffuse rays
+  const uint32_t bin = blockIdx.x * 4u + wave;
+  const unsigned long long maskR = __ballot(wantRefl), maskD = __ballot(wantDiff), below = (1ull << lane) - 1ull;
+  const uint32_t nR = (uint32_t)__popcll(maskR);
+  RayRec* dst = A.rays + (size_t)bin * A.binSlots;
+  HitKey* keys = A.hits + (size_t)bin * A.binSlots;
+  if (wantRefl) { const uint32_t k = (uint32_t)__popcll(maskR & below); dst[k] = rr; keys[k] = hitKey(RT_RAY_TMAX, 0xFFFFFFFFu); }
+  const uint32_t kD = nR + (uint32_t)__popcll(maskD & below);
+  if (wantDiff && kD < A.binSlots) { dst[kD] = rd; keys[kD] = hitKey(RT_RAY_TMAX, 0xFFFFFFFFu); }      // (never beyond the bin: rayGenKernel)
+  if (lane == 0) A.binCount[bin] = min(nR + (uint32_t)__popcll(maskD), A.binSlots);
+}
+
+// After the last sample: the word of every covered pixel from its sums, pack_r11g11b10(acc * (1 / N)) -- N is a power of two, the scaling
+// exact --, RayTracingOut1 where the pixel's metallic < 1 (diffMask, bit per instance; elsewhere it keeps what was carried over).  The sums
+// are left zero for the next frame.  Background pixels hold the environment from ray generation: no ray, no averaging.
+struct ResolveArgs {
+  const unsigned long long* visDepth; float* accRefl; float* accDiff; uint32_t* reflOut; uint32_t* diffOut;
+  const uint32_t* tileWords; uint32_t tilesX, rowBegin, rowEnd, diffMask; float scale;
+};
+__global__ void __launch_bounds__(256) resolveSamplesKernel(const FrameParams* __restrict__ fpp, ResolveArgs A) {
+  const FrameParams& fp = *fpp;
+  const uint32_t tile = blockIdx.x;
+  { uint32_t word;
+    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(word) : "s"(A.tileWords), "s"(tile * 4u) : "memory");
+    if (word == 0u) return; }
+  const uint32_t px = (tile % A.tilesX) * 16u + (threadIdx.x & 15u), py = A.rowBegin + (tile / A.tilesX) * 16u + (threadIdx.x >> 4);
+  if (px >= fp.W || py >= A.rowEnd) return;
+  const size_t pix = (size_t)py * fp.W + px;
+  const uint32_t vis = (uint32_t)A.visDepth[pix];
+  if (vis == 0u) return;
+  float* r = A.accRefl + 3u * pix;
+  A.reflOut[pix] = packR11G11B10F(mk3(r[0] * A.scale, r[1] * A.scale, r[2] * A.scale));
+  r[0] = 0.0f; r[1] = 0.0f; r[2] = 0.0f;
+  if ((A.diffMask >> ((vis - 1u) >> 24)) & 1u) {
+    float* d = A.accDiff + 3u * pix;
+    A.diffOut[pix] = packR11G11B10F(mk3(d[0] * A.scale, d[1] * A.scale, d[2] * A.scale));
+    d[0] = 0.0f; d[1] = 0.0f; d[2] = 0.0f;
+  }
+}
+
+// =========================================================================================================
 // host side
 // =========================================================================================================
 // Still sky: the epoch this frame's ray generation counts its tiles' runs under (rtggx_context.h InputSet::skyRun, RT_SKY_PREV_RUN).  A run
@@ -893,7 +1033,14 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
   G.skyPrev = c->prev().skyRun; G.skyOut = set.skyRun; G.skyPrevRun = c->staticSky ? RT_SKY_PREV_RUN : RT_SKY_RUN_CAP + 1u;
   // ray generation on stream C, the traversal on stream B behind it: the event rides on ray generation
   FrameEvents& ev = c->frameEvents(c->frameCounter);
-  launch(quad ? rayGenKernel<4> : rayGenKernel<1>, dim3(quad ? numBins : G.numTiles), dim3(256), sGen, nullptr, sGen != s ? ev.gen : nullptr, c->dParams + c->slot, G);
+  // N > 1 samples per pixel: the samples' copies of the frame constants (sampleParamsKernel), and ray generation traces sample 0
+  const FrameParams* genParams = c->dParams + c->slot;
+  if (c->samples > 1u) {
+    FrameParams* const sp = c->sppParams + (size_t)c->slot * RTGGX_MAX_SAMPLES_PER_PIXEL;
+    hipLaunchKernelGGL(sampleParamsKernel, dim3(1), dim3(256), 0, sGen, genParams, sp, c->samples);
+    genParams = sp;
+  }
+  launch(quad ? rayGenKernel<4> : rayGenKernel<1>, dim3(quad ? numBins : G.numTiles), dim3(256), sGen, nullptr, sGen != s ? ev.gen : nullptr, genParams, G);
   ev.genFrame = 0u; ev.genStream = sGen;
   if (sGen != s) {
     RT_HIP(hipStreamWaitEvent(s, ev.gen, 0));
@@ -918,6 +1065,46 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
 static void (*const kShade[3][2])(const FrameParams*, ShadeArgs) = {      // [ShadePass][rate 4]
     {shadeKernel<1, SHADE_FINAL>, shadeKernel<4, SHADE_FINAL>}, {shadeKernel<1, SHADE_SPAWN>, shadeKernel<4, SHADE_SPAWN>},
     {shadeKernel<1, SHADE_FINAL_DEEP>, shadeKernel<4, SHADE_FINAL_DEEP>}};
+// N > 1 samples per pixel (rate 1 only), depth D: per sample D shading passes that add to the sums, in front of every sample but the first
+// its rays' generation and their traversal, behind the last one the resolve -- N * D shading passes, N * D - 1 traversals, N - 1 sample
+// generations and the resolve on this stream, the frame's bins reused in place throughout.  Every traversal here is a later level's in launchTrace's terms: a spill part of its
+// own, no stamps, no cost record, no split list, no counter read-back -- nothing the next frame's level-0 traversal (stream B) also uses.
+// `done` rides on the resolve, the last kernel of the frame that reads the bins.
+static int launchShadeSamples(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent_t done, ShadeArgs S, uint32_t numTiles, int spillPart) {
+  const uint32_t N = c->samples, depth = c->maxDepth;
+  if (!c->sppAcc || !c->sppParams) { setError("rtggx_ray_trace: %u samples per pixel without their buffers", N); return -1; }
+  // the sums exist once: the previous frame's passes may have run on another stream (small launches alternate two; capi.hip rtggx_ray_trace)
+  if (c->sppStream && c->sppStream != s) { RT_HIP(hipEventRecord(c->evSpp, c->sppStream)); RT_HIP(hipStreamWaitEvent(s, c->evSpp, 0)); }
+  c->sppStream = s;
+  const InputSet& set = c->cur();
+  const FrameParams* const sp = c->sppParams + (size_t)c->slot * RTGGX_MAX_SAMPLES_PER_PIXEL;
+  S.accRefl = c->sppAcc; S.accDiff = c->sppAcc + 3u * (size_t)c->W * c->H;
+  SampleGenArgs G;
+  G.visDepth = S.visDepth; G.fat0 = S.fat0; G.fat1 = S.fat1; G.cosSin = S.cosSin;
+  G.rays = S.spawnRays; G.hits = S.spawnHits; G.binCount = S.spawnCount; G.binSlots = S.binSlots;
+  G.tileWords = S.tileWords; G.tilesX = S.tilesX; G.rowBegin = S.rowBegin; G.rowEnd = S.rowEnd;
+  const TraceQueue q{S.rays, S.spawnHits, S.binCount};
+  for (uint32_t k = 0; k < N; ++k) {
+    for (uint32_t level = 0; level < depth; ++level) {
+      if (k > 0 && level == 0) launch(sampleGenKernel, dim3(numTiles), dim3(256), s, nullptr, nullptr, sp + k, G);
+      if (k > 0 || level > 0) {
+        const int r = launchTrace(c, fp, s, q, c->traceGrid[0], true, c->traceGrid[1], c->traceGrid[2], c->traceGrid[3], -1, nullptr, nullptr, spillPart);
+        if (r) return r;
+      }
+      launch(level + 1u < depth ? shadeKernel<1, SHADE_SPAWN_ACCUM> : shadeKernel<1, SHADE_ACCUM>, dim3(numTiles), dim3(256), s, nullptr, nullptr, sp + k, S);
+      S.carryMask = 0u;      // (carried over once, by the first pass)
+      RT_HIP(hipGetLastError());
+    }
+  }
+  ResolveArgs R;
+  R.visDepth = S.visDepth; R.accRefl = S.accRefl; R.accDiff = S.accDiff; R.reflOut = set.rtRefl; R.diffOut = set.rtDiff;
+  R.tileWords = S.tileWords; R.tilesX = S.tilesX; R.rowBegin = S.rowBegin; R.rowEnd = S.rowEnd;
+  R.diffMask = (fp.mat.RoughMetals[0][1] < 1.0f ? 1u : 0u) | (fp.mat.RoughMetals[1][1] < 1.0f ? 2u : 0u);      // rghMtl.y < 1 (:559) is the instance's constant
+  R.scale = 1.0f / (float)N;
+  launch(resolveSamplesKernel, dim3(numTiles), dim3(256), s, nullptr, done, c->dParams + c->slot, R);
+  RT_HIP(hipGetLastError());
+  return 0;
+}
 int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent_t done) {
   uint32_t rb, re;
   passRows(fp, ROWS_GBUFFER, rb, re);
@@ -941,11 +1128,13 @@ int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent
   S.env = c->env.texels; S.envMipOffset = c->dEnvMipOffset; S.envSize = c->env.size; S.envMips = c->env.mips; S.sh = c->sh;
   S.reflOut = set.rtRefl; S.diffOut = set.rtDiff;
   S.spawnRays = (RayRec*)set.rayQueue; S.spawnHits = (HitKey*)set.hitQueue; S.spawnCount = set.binCount; S.cosSin = c->cosSinTab;
+  S.accRefl = nullptr; S.accDiff = nullptr;
   const FrameParams* const dfp = c->dParams + c->slot;
   const uint32_t depth = c->maxDepth;
   // Levels 1.. run behind this stream's shading of the level before, beside the next frame's level-0 traversal (stream B): a part of the
   // spill area of their own on the main stream; on a traversal stream (small launches, capi.hip) that stream's own, in stream order
   const int spillPart = s == c->streamMain ? 2 : (int)c->traceSpillHalf;
+  if (c->samples > 1u && !quad) return launchShadeSamples(c, fp, s, done, S, numTiles, spillPart);
   for (uint32_t level = 0; level < depth; ++level) {
     if (level > 0) {
       const TraceQueue q{S.rays, S.spawnHits, S.binCount};

@@ -250,6 +250,14 @@ struct rtggx_context {
   bool vndf = false;             // rtggx_set_sampler
   uint32_t rayRate = 1;          // rtggx_set_ray_rate: pixels per traced ray, 1 or 4 (raytrace.hip rayGenKernel, reconstructKernel)
   uint32_t maxDepth = 1, depthRequested = 1;      // rtggx_set_max_recursion_depth: 1..4 levels of rays per path (raytrace.hip launchShade); the frame's, the next frame's
+  // rtggx_set_samples_per_pixel: 1, 2, 4 or 8 samples per covered pixel (raytrace.hip launchShade; DESIGN.md "Samples per pixel"); the
+  // frame's, the next frame's.  Everything below exists from the first N > 1 on (capi.hip allocSamples) and is released by rtggx_destroy:
+  //   sppAcc     the fp32 sums of RayTracingOut0 / RayTracingOut1, [2][W * H][3] floats, all zero between frames (the resolve leaves them so).
+  //              ONE pair for all input sets: the frames' shading passes follow each other in stream order, or by evSpp where the stream changes
+  //   sppParams  [RT_SLOTS][RTGGX_MAX_SAMPLES_PER_PIXEL] copies of the slot's frame constants, sample k's with FrameIndex * N + k
+  uint32_t samples = 1, samplesRequested = 1;
+  float* sppAcc = nullptr; rt::FrameParams* sppParams = nullptr;
+  hipStream_t sppStream = nullptr; hipEvent_t evSpp = nullptr;      // the stream of the most recent frame that used sppAcc
   uint32_t traceGrid[4] = {};    // the frame's level-0 trace launch -- bins, tile grid x / y, slice shift --, which the later levels repeat
   float rebuildRatio = 1.2f; uint32_t rebuildSteps = 16;      // rtggx_set_refit_policy
   rt::MeshDev mesh[2];
@@ -411,7 +419,8 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
 // kernel's own completion signal (hipExtLaunchKernelGGL) instead of a marker packet behind it: a marker costs its queue
 // 5-7 us, and the frame's two chains had four of them (rocprofv3 kernel trace, profiles/).
 int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent_t done = nullptr);      // hit / miss shading of the traced bins
-int launchReconstruct(rtggx_context* c, const FrameParams& fp, hipStream_t s);      // rate 4: the untraced pixels of RayTracingOut0/1, after the hit shading
+int launchReconstruct(rtggx_context* c, const FrameParams& fp, hipStream_t s);
+int allocSamples(rtggx_context* c);      // what N > 1 samples per pixel need (rtggx_context::sppAcc, sppParams), once      // rate 4: the untraced pixels of RayTracingOut0/1, after the hit shading
 int launchTraceRays(rtggx_context* c, const FrameParams& fp, const float* dRays, uint32_t n, float* dOut, hipStream_t s);
 int launchDenoise(rtggx_context* c, const FrameParams& fp, int useLds, hipStream_t s, hipEvent_t done = nullptr, bool fuseToneMap = false);      // fuseToneMap: the last kernel also writes the back buffer
 int launchToneMap(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent_t done = nullptr);

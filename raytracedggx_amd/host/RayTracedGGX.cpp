@@ -34,6 +34,7 @@ void RayTracedGGX::OnInit() {
   if (m_vndf) m_rayTracer->SetSampler(true);            // -vndf: visible-normal sampling of the reflection lobe (opt-in; the reference samples the NDF)
   if (m_rayRate != 1u && !m_rayTracer->SetRayRate(m_rayRate)) throw std::runtime_error("-rayrate: " + m_rayTracer->GetLastError());      // -rayrate 4: one ray per 2x2 quad (opt-in)
   if (m_recursionDepth != 1u && !m_rayTracer->SetMaxRecursionDepth(m_recursionDepth)) throw std::runtime_error("-recursion: " + m_rayTracer->GetLastError());      // -recursion N: multi-bounce paths (opt-in)
+  if (m_samplesPerPixel != 1u && !m_rayTracer->SetSamplesPerPixel(m_samplesPerPixel)) throw std::runtime_error("-spp: " + m_rayTracer->GetLastError());      // -spp N: multi-sample tracing (opt-in)
   m_rayTracer->SetAsyncCompute(m_asyncCompute != 0);   // -sync: one stream, submission order (the sample's single command list)
 
   if (m_deformAmplitude != 0.0f) {       // key shapes of the breathing model: x and z displaced by a wave travelling up the y axis
@@ -193,7 +194,7 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
     return (arg[0] == '-' || arg[0] == '/') && lower(arg + 1) == lower(name);
   };
   // On POSIX an absolute path also starts with '/': such a token is a flag only when it names one.
-  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "recursion"};
+  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "recursion", "spp"};
   const auto isFlagName = [&](const char* name) { for (const char* f : kFlags) if (lower(name) == f) return true; return false; };
   const auto hasNextArgValue = [&](int i) {
     if (i + 1 >= argc) return false;
@@ -227,6 +228,11 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
       if (depth < 1 || depth > (int)RTGGX_MAX_RECURSION_DEPTH) throw std::runtime_error("-recursion: 1 to 4 levels of rays per path");
       m_recursionDepth = (uint32_t)depth;
     }
+    else if (isArgMatched(i, "spp")) {
+      const int samples = hasNextArgValue(i) ? std::atoi(argv[++i]) : 0;
+      if (samples != 1 && samples != 2 && samples != 4 && samples != 8) throw std::runtime_error("-spp: 1, 2, 4 or 8 samples per pixel");
+      m_samplesPerPixel = (uint32_t)samples;
+    }
     else if (isArgMatched(i, "device")) { if (hasNextArgValue(i)) m_device = std::atoi(argv[++i]); }
     else if (isArgMatched(i, "dump")) { if (hasNextArgValue(i)) m_dumpPrefix = argv[++i]; }
     else if (isArgMatched(i, "deform")) { nextFloat(i, m_deformAmplitude); }
@@ -241,6 +247,8 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
     else if (isArgMatched(i, "balance")) { if (hasNextArgValue(i)) m_balance = std::atoi(argv[++i]) != 0; }
   }
   // quarter-rate tracing renders whole frames only (rtggx_set_ray_rate): refused here, before anything has touched a GPU
+  // one knob asks for fewer rays, the other for more (rtggx_set_samples_per_pixel)
+  if (m_rayRate != 1u && m_samplesPerPixel != 1u) throw std::runtime_error("-spp N > 1 together with -rayrate 4: refused");
   if (m_rayRate != 1u && (m_gpus > 1 || m_strips > 1)) throw std::runtime_error("-rayrate 4: whole frames only, not with -gpus N > 1 or -strips N > 1");
 }
 

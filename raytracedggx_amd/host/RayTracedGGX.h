@@ -2,7 +2,7 @@
 // DXFramework virtuals RayTracedGGX/Common/DXFramework.h:23-26): OnInit / OnUpdate / OnRender /
 // OnDestroy, the same command line (RayTracedGGX.cpp:462-511) and the same defaults
 // (RayTracedGGX.cpp:37-39, camera :19-23, 267-277).  What the window supplied interactively is
-// supplied by extra flags: -width -height -frames -dt -metallic -sharedmem -sync -vndf -rayrate -recursion -device -dump -track -deform -gpus -strips -balance.
+// supplied by extra flags: -width -height -frames -dt -metallic -sharedmem -sync -vndf -rayrate -recursion -spp -device -dump -track -deform -gpus -strips -balance.
 #pragma once
 #include <vector>
 #include <cstdint>
@@ -99,6 +99,7 @@ class RayTracedGGX {
   bool m_hasMetallicOverride = false;
   bool m_vndf = false;                 // -vndf
   uint32_t m_recursionDepth = 1;       // -recursion <1..4>: levels of rays per path (RayTracer::SetMaxRecursionDepth)
+  uint32_t m_samplesPerPixel = 1;      // -spp <1|2|4|8>: samples per covered pixel (RayTracer::SetSamplesPerPixel); not together with -rayrate 4
   uint32_t m_rayRate = 1;              // -rayrate <1|4>: pixels per traced ray (RayTracer::SetRayRate); 4 renders whole frames only: not with -gpus / -strips
   // -deform <amplitude>: the model breathes -- a travelling sine wave through its vertices, DeformPeriod key shapes computed once
   // at start-up and handed to RayTracer::UpdateMesh one per frame (per-frame host cost: one copy of the vertex array)
