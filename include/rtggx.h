@@ -347,6 +347,12 @@ int  rtggx_debug_trace_split(rtggx_context* ctx, uint32_t work_per_wave, uint32_
    the frame period the traversal takes (DESIGN.md "The trace kernel").  Reports the size and the share last sampled (0 before the
    first sample).  force_waves: 0 leaves the choice to the library, 10/12/14/16 pins it (measurement). */
 int  rtggx_debug_trace_residency(rtggx_context* ctx, uint32_t force_waves, uint32_t* waves, float* share);
+/* Diagnostic / test hook: the environment sampler alone.  rgb3[3 i ..] = the filtered cube map in direction dirs3[3 i ..] (any length but 0;
+ * no NaN or infinity) at mip level levels[i] -- clamped to [0, mips - 1], trilinear --, computed on the device by the very functions ray
+ * generation and hit shading call (D3D cube sampling restated: DESIGN.md).  level0_path != 0: through the folded level-0 path those kernels
+ * use for the sky behind a pixel and for a ray that misses; levels is then not read and may be null.  Fails when no environment is set or
+ * n == 0.  Reads the decoded cube only: no frame state, no input set and no still-sky run is touched.  Synchronises the main stream. */
+int  rtggx_debug_environment(rtggx_context* ctx, const float* dirs3, const float* levels, uint32_t n, int level0_path, float* rgb3);
 int  rtggx_get_timings(rtggx_context* ctx, RtggxTimings* out);
 /* mode 0 off, 1 every pass (rtggx_get_timings), 2 only the ray-trace kernel: one HIP event pair per frame,
  * recorded on the launching stream right around the kernel, kept for up to RTGGX_KERNEL_RING frames; 3 like 2 for

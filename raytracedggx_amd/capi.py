@@ -31,7 +31,7 @@ EXPORTS = ["rtggx_last_error", "rtggx_create", "rtggx_destroy", "rtggx_set_strip
            "rtggx_transform_sh", "rtggx_render_visibility", "rtggx_ray_trace", "rtggx_denoise", "rtggx_tone_map", "rtggx_sync",
            "rtggx_ray_count", "rtggx_get_timings", "rtggx_enable_timing", "rtggx_buffer_size", "rtggx_readback", "rtggx_buffer_ptr",
            "rtggx_upload", "rtggx_frame_parity", "rtggx_bvh_root", "rtggx_trace_rays", "rtggx_ray_total", "rtggx_kernel_times", "rtggx_debug_counters", "rtggx_debug_trace_split", "rtggx_debug_trace_residency", "rtggx_get_stream", "rtggx_set_history_peers", "rtggx_history_ipc_export", "rtggx_history_ipc_open",
-           "rtggx_set_async_compute", "rtggx_set_history_apron", "rtggx_history_overreach", "rtggx_copy_bandwidth", "rtggx_refit_as", "rtggx_refit_as_device", "rtggx_refit_stats", "rtggx_set_refit_policy", "rtggx_set_sampler", "rtggx_set_ray_rate", "rtggx_set_max_recursion_depth", "rtggx_set_samples_per_pixel", "rtggx_debug_fuse_tone_map", "rtggx_debug_placement", "rtggx_debug_tile_words", "rtggx_debug_static_sky", "rtggx_debug_sky_runs", "rtggx_debug_collapse_weights", "rtggx_debug_fence_wait", "rtggx_debug_shader_clock"]
+           "rtggx_set_async_compute", "rtggx_set_history_apron", "rtggx_history_overreach", "rtggx_copy_bandwidth", "rtggx_refit_as", "rtggx_refit_as_device", "rtggx_refit_stats", "rtggx_set_refit_policy", "rtggx_set_sampler", "rtggx_set_ray_rate", "rtggx_set_max_recursion_depth", "rtggx_set_samples_per_pixel", "rtggx_debug_fuse_tone_map", "rtggx_debug_placement", "rtggx_debug_tile_words", "rtggx_debug_static_sky", "rtggx_debug_sky_runs", "rtggx_debug_collapse_weights", "rtggx_debug_fence_wait", "rtggx_debug_shader_clock", "rtggx_debug_environment"]
 
 
 class Timings(C.Structure):
@@ -348,6 +348,16 @@ class Context:
         out = np.zeros(n, np.uint32)
         self.L.rtggx_debug_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int]
         self._check(self.L.rtggx_debug_counters(self.h, _p(out), n, 1 if reset else 0))
+        return out
+
+    def debug_environment(self, dirs, levels, level0=False):
+        """The filtered environment in each of dirs[n, 3] at mip level levels[n] (a scalar serves all), through the device functions the frame
+        kernels call; level0: through their folded level-0 path, which ignores the level (include/rtggx.h).  Returns float32 [n, 3]."""
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        lv = np.ascontiguousarray(np.broadcast_to(np.asarray(levels, np.float32), (d.shape[0],)))
+        out = np.zeros((d.shape[0], 3), np.float32)
+        self.L.rtggx_debug_environment.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
+        self._check(self.L.rtggx_debug_environment(self.h, _p(d), _p(lv), d.shape[0], 1 if level0 else 0, _p(out)))
         return out
 
     def enable_timing(self, mode=1):

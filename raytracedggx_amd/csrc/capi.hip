@@ -1084,6 +1084,27 @@ int rtggx_debug_trace_residency(rtggx_context* c, uint32_t forceWaves, uint32_t*
   return 0;
 }
 
+// The environment sampler by itself: n directions (and levels) through the device functions the frame kernels call.  Reads the decoded
+// cube and its offset table, nothing else: no frame state, no sky runs, no input set.
+int rtggx_debug_environment(rtggx_context* c, const float* dirs3, const float* levels, uint32_t n, int level0Path, float* rgb3) {
+  RT_CHECK_CTX(c);
+  if (!c->env.texels) { setError("rtggx_debug_environment: no environment map"); return -1; }
+  if (n == 0 || !dirs3 || !rgb3 || (!levels && !level0Path)) { setError("rtggx_debug_environment: no directions, levels or result (n %u)", n); return -1; }
+  float *dD = nullptr, *dL = nullptr, *dO = nullptr;
+  hipError_t e = hipMalloc(&dD, (size_t)n * 12);
+  if (e == hipSuccess) e = hipMalloc(&dO, (size_t)n * 12);
+  if (e == hipSuccess && levels) e = hipMalloc(&dL, (size_t)n * 4);
+  if (e == hipSuccess) e = hipMemcpy(dD, dirs3, (size_t)n * 12, hipMemcpyHostToDevice);
+  if (e == hipSuccess && levels) e = hipMemcpy(dL, levels, (size_t)n * 4, hipMemcpyHostToDevice);
+  int r = 0;
+  if (e == hipSuccess) r = launchDebugEnvironment(c, dD, dL, n, level0Path, dO, c->streamMain);
+  if (e == hipSuccess && !r) e = hipStreamSynchronize(c->streamMain);
+  if (e == hipSuccess && !r) e = hipMemcpy(rgb3, dO, (size_t)n * 12, hipMemcpyDeviceToHost);
+  hipFree(dD); hipFree(dL); hipFree(dO);
+  if (e != hipSuccess) { setError("rtggx_debug_environment: %s", hipGetErrorString(e)); return -2; }
+  return r;
+}
+
 int rtggx_debug_trace_split(rtggx_context* c, uint32_t workPerWave, uint32_t maxShift, int capacity, uint32_t* lastDemand) {
   RT_CHECK_CTX(c);
   if (maxShift > 3u) { setError("rtggx_debug_trace_split: max_shift %u > 3", maxShift); return -1; }

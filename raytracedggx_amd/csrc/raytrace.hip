@@ -1218,4 +1218,19 @@ int launchTraceRays(rtggx_context* c, const FrameParams& fp, const float* dRays,
   return 0;
 }
 
+// ---- test entry: the environment sampler alone (the frame kernels' own device functions, one lane per direction) ------
+__global__ void debugEnvironmentKernel(EnvRef env, const float* __restrict__ dirs, const float* __restrict__ levels, uint32_t n, int level0, float* __restrict__ rgb) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const f3 d = mk3(dirs[3 * (size_t)i], dirs[3 * (size_t)i + 1], dirs[3 * (size_t)i + 2]);
+  const f3 c = level0 ? environmentLevel0(env, d) : environment(env, d, levels[i]);
+  rgb[3 * (size_t)i] = c.x; rgb[3 * (size_t)i + 1] = c.y; rgb[3 * (size_t)i + 2] = c.z;
+}
+int launchDebugEnvironment(rtggx_context* c, const float* dDirs, const float* dLevels, uint32_t n, int level0, float* dOut, hipStream_t s) {
+  const EnvRef env{c->env.texels, c->env.size, c->env.mips, c->dEnvMipOffset};
+  hipLaunchKernelGGL(debugEnvironmentKernel, dim3((n + 255) / 256), dim3(256), 0, s, env, dDirs, dLevels, n, level0, dOut);
+  RT_HIP(hipGetLastError());
+  return 0;
+}
+
 }  // namespace rt

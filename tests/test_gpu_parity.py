@@ -9,6 +9,7 @@ import pytest
 
 import assets
 import bvh_checks
+import env_cases
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -36,7 +37,7 @@ def rel_l2(a, b):
 class Pair:
     """The product's RayTracedGGX application object and an oracle on the same scene."""
 
-    def __init__(self, W, H, mesh="bunny.obj", metallic=None, pos_scale=None, env_const=None, shared_mem=False, normal_weight="exact"):
+    def __init__(self, W, H, mesh="bunny.obj", metallic=None, pos_scale=None, env_const=None, shared_mem=False, normal_weight="exact", env=None):
         from raytracedggx_amd import app, capi
         self.capi = capi
         args = ["-mesh", assets.path(mesh)] + ([str(x) for x in pos_scale] if pos_scale else []) + \
@@ -59,6 +60,10 @@ class Pair:
             env = assets.constant_env_rgba16f(env_const)
             self.ctx.set_env(capi.FORMAT_RGBA16F, 1, 1, env)
             self.o.set_env_rgba16f(1, 1, env)
+        elif env is not None:      # (size, mips, per level the RGBA16F codes [6, s, s, 4]): tests/env_cases.py
+            cube = env_cases.Cube(env[0], env[1], env[2], "env")
+            self.ctx.set_env(capi.FORMAT_RGBA16F, cube.size, cube.mips, cube.dds_order())
+            self.o.set_env_rgba16f(cube.size, cube.mips, cube.mip_major())
         else:
             self.o.set_env_dds(assets.path("rnl_cross.dds"))
         if metallic is not None:
@@ -140,6 +145,26 @@ def test_bunny_three_frames(built, shared_mem):
             p.frame(); p.check_frame("bunny frame %d" % f)
         np.testing.assert_allclose(p.ctx.readback(p.capi.BUF_SH_COEFFS), p.o.buffer(O.BUF_SH_COEFFS), rtol=1e-5, atol=1e-6)
         assert p.rays > 50000
+    finally:
+        p.close()
+
+
+@pytest.mark.parametrize("size,mips", [(12, 3), (7, 1)], ids=["12x12_3mips", "7x7_1mips"])
+def test_bunny_under_a_small_synthetic_cube(built, size, mips):
+    """The sampler where the frame uses it -- sky pixels, misses and rough reflections (metallic 0.25 / 0.5: every level of the chain) -- on
+    cubes whose sides are no powers of two (tests/test_gpu_env.py samples them direction by direction); with one level every roughness clamps
+    to level 0.  Between the frames the sampler's test entry runs: it must leave the frame's state, the still-sky runs included, as they are."""
+    cube = env_cases.random_cube(size, mips)
+    p = Pair(96, 54, metallic=(0.25, 0.5), env=(cube.size, cube.mips, cube.codes))
+    try:
+        np.testing.assert_array_equal(p.ctx.readback(p.capi.BUF_ENV), cube.mip_major())
+        for f in range(2):
+            p.frame(); p.check_frame("bunny, %s, frame %d" % (cube.name, f))
+            runs = p.ctx.sky_runs()[0].copy()
+            p.ctx.debug_environment(env_cases.directions(size).d[:256], 0.5)
+            np.testing.assert_array_equal(p.ctx.sky_runs()[0], runs)
+        np.testing.assert_allclose(p.ctx.readback(p.capi.BUF_SH_COEFFS), p.o.buffer(O.BUF_SH_COEFFS), rtol=1e-5, atol=1e-6)
+        assert p.rays > 0
     finally:
         p.close()
 
