@@ -108,7 +108,10 @@ enum {
   RTGGX_BUF_BVH4_TOP1 = 23,   /*   a node that is in the table itself reads 0x40000000 | position (the copy the trace kernel keeps in LDS) */
   RTGGX_BUF_EXCHANGE_TOKENS = 24, /* 2 x RTGGX_MAX_PEERS uint32: words a multi-GPU host may send from ([rank]) and receive into ([RTGGX_MAX_PEERS + peer]) --
                                      the 4-byte messages that order two ranks without a neighbour's history rows between them (rtggx_set_history_peers) */
-  RTGGX_BUF_COUNT = 25
+  RTGGX_BUF_ACC_REFL = 25,   /* 4 floats per pixel: sum r, sum g, sum b, sum Y^2 of RayTracingOut0 over the accumulated frames (rtggx_set_accumulation) */
+  RTGGX_BUF_ACC_DIFF = 26,   /* the same of RayTracingOut1, where a diffuse path contributed; zero elsewhere */
+  RTGGX_BUF_CONVERGED = 27,  /* uint64  R16G16B16A16_FLOAT, the mean image of the most recent rtggx_present_accumulation */
+  RTGGX_BUF_COUNT = 28
 };
 
 /* Per-pass GPU timings of the last completed frame, in milliseconds (hipEvent based). */
@@ -247,6 +250,36 @@ int  rtggx_set_max_recursion_depth(rtggx_context* ctx, uint32_t depth);
  * allocates 24 bytes per pixel of the full frame, released by rtggx_destroy.  Takes effect from the next rtggx_render_visibility. */
 #define RTGGX_MAX_SAMPLES_PER_PIXEL 8u
 int  rtggx_set_samples_per_pixel(rtggx_context* ctx, uint32_t samples);
+/* Progressive accumulation (opt-in, no counterpart in the reference; DESIGN.md "Progressive accumulation"): the long-run mean of the
+ * denoiser's INPUT, kept on the device.  Off (default): nothing is allocated and a frame launches what it always did.  enable = 1 takes
+ * effect from the next rtggx_render_visibility; the first one allocates 2 x 16 + 8 bytes per pixel of the full frame, zeroed, released by
+ * rtggx_destroy.  Enabling does not reset; disabling keeps the sums and the count.
+ *   - while on, every rtggx_ray_trace ends with one more kernel on the main stream, behind the hit shading and the sample resolve and in
+ *     front of rtggx_denoise (RtggxTimings.ray_trace covers it), and the frame count n grows by one.  For every pixel of the context's own
+ *     rows [row_begin, row_end) -- no apron --, in fp32 without contraction, one lane per pixel, no atomics, frames in main-stream order:
+ *         (r, g, b) = unpack_r11g11b10(RayTracingOut0);  A0.xyz += (r, g, b);  Y = (0.25 r + 0.5 g) + 0.25 b;  A0.w += Y * Y
+ *     -- background pixels too: they hold the environment --, and the same into A1 from RayTracingOut1 where the pixel is covered and its
+ *     instance's metallic in that frame's constants is < 1 (elsewhere RayTracingOut1 holds a carry-over nobody reads, and A1 is not
+ *     touched).  Non-finite words add as they are.  The sums are a pure function of the frames: RTGGX_BUF_ACC_REFL / _DIFF can be restated
+ *     bit for bit from the frames' words (tests/accum_ref.py);
+ *   - the sums exist once, not per input set.  A moving camera or a changed material is the caller's to reset:
+ *     rtggx_reset_accumulation zeroes the sums and the count, enqueued on the main stream without waiting;
+ *   - rtggx_accumulated_frames: n.  With a still camera the sequence of frames repeats after 256: the sample set of the reference has 256
+ *     members (getSampleParam) and FrameIndex wraps there -- an accumulation cannot converge past the mean of those 256;
+ *   - rtggx_present_accumulation (whole frames and n > 0; refused on a strip and at n = 0): per pixel and component
+ *     m0 = (float)((double)A0.c / (double)n), m1 likewise, RTGGX_BUF_CONVERGED = pack_rgba16f(m0.r + m1.r, m0.g + m1.g, m0.b + m1.b, 1)
+ *     with fp32 adds -- the denoiser's composition dest + diffuse of the two means, A1 being zero where no diffuse path ever contributed --,
+ *     then the tone map of that image into RTGGX_BUF_BACKBUFFER.  Both on the main stream; the next frame's tone map overwrites the back
+ *     buffer as always, and no other image is touched;
+ *   - works with both samplers, every recursion depth and sample count (the word accumulated is the resolved one), a deforming mesh and on
+ *     strips (rows outside the strip stay zero).  Three quarters of a rate-4 frame are interpolations: rtggx_set_accumulation(1) on a
+ *     context at ray rate 4, and rate 4 on an accumulating context, are refused and the context keeps what it had;
+ *   - rtggx_readback / rtggx_buffer_size / rtggx_buffer_ptr of RTGGX_BUF_ACC_REFL, _ACC_DIFF and _CONVERGED fail on a context that never
+ *     enabled accumulation. */
+int  rtggx_set_accumulation(rtggx_context* ctx, int enable);
+int  rtggx_reset_accumulation(rtggx_context* ctx);
+int  rtggx_accumulated_frames(rtggx_context* ctx, uint32_t* frames);
+int  rtggx_present_accumulation(rtggx_context* ctx);
 
 /* Build of both bottom-level structures (RayTracer::buildAccelerationStructures / BuildAccelerationStructures, RayTracer.cpp:676-716,
  * 158-233; the sample records the builds on the GPU timeline and waits once, RayTracedGGX.cpp:236): every step of the build --

@@ -15,7 +15,8 @@ LIB_PATH = os.path.join(_HERE, "librtggx.so")
 # buffer ids (rtggx.h)
 BUF_VISIBILITY, BUF_DEPTH, BUF_NORMAL, BUF_ROUGH_METAL, BUF_VELOCITY, BUF_RT_REFL, BUF_RT_DIFF, BUF_TSS0, BUF_TSS1, \
     BUF_FLT_RFL, BUF_FLT_DFF, BUF_BACKBUFFER, BUF_SH_COEFFS, BUF_BVH_NODES0, BUF_BVH_TRIS0, BUF_BVH_NODES1, BUF_BVH_TRIS1, \
-    BUF_TLAS, BUF_ENV, BUF_BVH4_NODES0, BUF_BVH4_NODES1, BUF_BIN_WORK, BUF_BVH4_TOP0, BUF_BVH4_TOP1, BUF_EXCHANGE_TOKENS = range(25)
+    BUF_TLAS, BUF_ENV, BUF_BVH4_NODES0, BUF_BVH4_NODES1, BUF_BIN_WORK, BUF_BVH4_TOP0, BUF_BVH4_TOP1, BUF_EXCHANGE_TOKENS, \
+    BUF_ACC_REFL, BUF_ACC_DIFF, BUF_CONVERGED = range(28)
 MAX_PEERS, IPC_HANDLE_BYTES = 16, 64
 FORMAT_RGBA32F, FORMAT_RGBA16F, FORMAT_BC6H_UF16, FORMAT_BC6H_SF16 = 2, 10, 95, 96
 
@@ -24,14 +25,16 @@ _BUF_DTYPE = {BUF_VISIBILITY: np.uint32, BUF_DEPTH: np.uint32, BUF_NORMAL: np.ui
               BUF_FLT_RFL: np.uint64, BUF_FLT_DFF: np.uint64, BUF_BACKBUFFER: np.uint32, BUF_SH_COEFFS: np.float32,
               BUF_BVH_NODES0: np.uint32, BUF_BVH_TRIS0: np.uint32, BUF_BVH_NODES1: np.uint32, BUF_BVH_TRIS1: np.uint32,
               BUF_TLAS: np.float32, BUF_ENV: np.uint16, BUF_BVH4_NODES0: np.uint32, BUF_BVH4_NODES1: np.uint32, BUF_BIN_WORK: np.uint32,
-              BUF_BVH4_TOP0: np.uint32, BUF_BVH4_TOP1: np.uint32, BUF_EXCHANGE_TOKENS: np.uint32}
+              BUF_BVH4_TOP0: np.uint32, BUF_BVH4_TOP1: np.uint32, BUF_EXCHANGE_TOKENS: np.uint32,
+              BUF_ACC_REFL: np.float32, BUF_ACC_DIFF: np.float32, BUF_CONVERGED: np.uint64}
 
 EXPORTS = ["rtggx_last_error", "rtggx_create", "rtggx_destroy", "rtggx_set_strip", "rtggx_set_stream", "rtggx_set_mesh",
            "rtggx_set_env", "rtggx_set_material", "rtggx_set_metallic", "rtggx_build_as", "rtggx_update_frame", "rtggx_update_as",
            "rtggx_transform_sh", "rtggx_render_visibility", "rtggx_ray_trace", "rtggx_denoise", "rtggx_tone_map", "rtggx_sync",
            "rtggx_ray_count", "rtggx_get_timings", "rtggx_enable_timing", "rtggx_buffer_size", "rtggx_readback", "rtggx_buffer_ptr",
            "rtggx_upload", "rtggx_frame_parity", "rtggx_bvh_root", "rtggx_trace_rays", "rtggx_ray_total", "rtggx_kernel_times", "rtggx_debug_counters", "rtggx_debug_trace_split", "rtggx_debug_trace_residency", "rtggx_get_stream", "rtggx_set_history_peers", "rtggx_history_ipc_export", "rtggx_history_ipc_open",
-           "rtggx_set_async_compute", "rtggx_set_history_apron", "rtggx_history_overreach", "rtggx_copy_bandwidth", "rtggx_refit_as", "rtggx_refit_as_device", "rtggx_refit_stats", "rtggx_set_refit_policy", "rtggx_set_sampler", "rtggx_set_ray_rate", "rtggx_set_max_recursion_depth", "rtggx_set_samples_per_pixel", "rtggx_debug_fuse_tone_map", "rtggx_debug_placement", "rtggx_debug_tile_words", "rtggx_debug_static_sky", "rtggx_debug_sky_runs", "rtggx_debug_collapse_weights", "rtggx_debug_fence_wait", "rtggx_debug_shader_clock", "rtggx_debug_environment"]
+           "rtggx_set_async_compute", "rtggx_set_history_apron", "rtggx_history_overreach", "rtggx_copy_bandwidth", "rtggx_refit_as", "rtggx_refit_as_device", "rtggx_refit_stats", "rtggx_set_refit_policy", "rtggx_set_sampler", "rtggx_set_ray_rate", "rtggx_set_max_recursion_depth", "rtggx_set_samples_per_pixel", "rtggx_debug_fuse_tone_map", "rtggx_debug_placement", "rtggx_debug_tile_words", "rtggx_debug_static_sky", "rtggx_debug_sky_runs", "rtggx_debug_collapse_weights", "rtggx_debug_fence_wait", "rtggx_debug_shader_clock", "rtggx_debug_environment",
+           "rtggx_set_accumulation", "rtggx_reset_accumulation", "rtggx_accumulated_frames", "rtggx_present_accumulation"]
 
 
 class Timings(C.Structure):
@@ -62,6 +65,10 @@ def load():
     L.rtggx_set_ray_rate.argtypes = [vp, C.c_uint32]
     L.rtggx_set_max_recursion_depth.argtypes = [vp, C.c_uint32]
     L.rtggx_set_samples_per_pixel.argtypes = [vp, C.c_uint32]
+    L.rtggx_set_accumulation.argtypes = [vp, C.c_int]
+    L.rtggx_reset_accumulation.argtypes = [vp]
+    L.rtggx_accumulated_frames.argtypes = [vp, C.POINTER(C.c_uint32)]
+    L.rtggx_present_accumulation.argtypes = [vp]
     L.rtggx_set_history_apron.argtypes = [vp, C.c_uint32]
     L.rtggx_debug_shader_clock.argtypes = [vp, C.POINTER(C.c_double)]
     L.rtggx_refit_as.argtypes = [vp, C.c_uint32, vp, C.c_uint32]
@@ -264,6 +271,24 @@ class Context:
         """1 (default), 2, 4 or 8 samples per covered pixel (include/rtggx.h); taken over by the next frame; not together with ray rate 4."""
         self._check(self.L.rtggx_set_samples_per_pixel(self.h, int(samples)))
 
+    def set_accumulation(self, enable):
+        """Progressive accumulation of the raw traced images (include/rtggx.h): on from the next frame; the first enable allocates 40 bytes
+        per pixel; not together with ray rate 4.  Enabling does not reset, disabling keeps the sums and the count."""
+        self._check(self.L.rtggx_set_accumulation(self.h, 1 if enable else 0))
+
+    def reset_accumulation(self):
+        """Sums and frame count back to zero, enqueued on the main stream (no wait)."""
+        self._check(self.L.rtggx_reset_accumulation(self.h))
+
+    def accumulated_frames(self):
+        n = C.c_uint32()
+        self._check(self.L.rtggx_accumulated_frames(self.h, C.byref(n)))
+        return int(n.value)
+
+    def present_accumulation(self):
+        """BUF_CONVERGED = the mean of the accumulated frames, and its tone map in BUF_BACKBUFFER (whole frames, at least one frame)."""
+        self._check(self.L.rtggx_present_accumulation(self.h))
+
     def set_refit_policy(self, rebuild_ratio=1.2, steps_per_frame=16):
         self._check(self.L.rtggx_set_refit_policy(self.h, rebuild_ratio, steps_per_frame))
 
@@ -391,8 +416,10 @@ class Context:
         out = np.zeros(max(n // dt.itemsize, 0), dt)
         if n:
             self._check(self.L.rtggx_readback(self.h, bid, _p(out), n))
-        if bid <= BUF_BACKBUFFER:
+        if bid <= BUF_BACKBUFFER or bid == BUF_CONVERGED:
             return out.reshape(self.H, self.W)
+        if bid in (BUF_ACC_REFL, BUF_ACC_DIFF):
+            return out.reshape(self.H, self.W, 4)
         if bid == BUF_SH_COEFFS:
             return out.reshape(9, 3)
         if bid in (BUF_BVH_NODES0, BUF_BVH_NODES1):

@@ -272,6 +272,23 @@ int allocSamples(rtggx_context* c) {
   }
   return 0;
 }
+// What accumulation needs (rtggx_set_accumulation): the two sums and the mean image, 2 x 16 + 8 bytes per pixel of the full frame, zeroed;
+// allocated with the first enable -- all three or none --, released by rtggx_destroy.
+int allocAccumulation(rtggx_context* c) {
+  if (c->accRefl) return 0;
+  const size_t n = (size_t)c->W * c->H;
+  float4 *a0 = nullptr, *a1 = nullptr; uint2* cv = nullptr;
+  hipError_t e = hipMalloc(&a0, n * 16);
+  if (e == hipSuccess) e = hipMalloc(&a1, n * 16);
+  if (e == hipSuccess) e = hipMalloc(&cv, n * 8);
+  if (e == hipSuccess) e = hipMemset(a0, 0, n * 16);
+  if (e == hipSuccess) e = hipMemset(a1, 0, n * 16);
+  if (e == hipSuccess) e = hipMemset(cv, 0, n * 8);
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);      // (the clears run on the null stream, which this context's streams are not ordered against)
+  if (e != hipSuccess) { hipFree(a0); hipFree(a1); hipFree(cv); setError("rtggx_set_accumulation: %s (%zu bytes for the sums and the mean image)", hipGetErrorString(e), n * 40); return -2; }
+  c->accRefl = a0; c->accDiff = a1; c->converged = cv;
+  return 0;
+}
 }  // namespace rt
 
 using namespace rt;
@@ -313,6 +330,7 @@ void rtggx_destroy(rtggx_context* c) {
   for (auto& v : c->vis) { hipFree(v.depth); hipFree(v.dirty); }
   hipFree(c->visDirtyOnes);
   hipFree(c->sppAcc); hipFree(c->sppParams); destroyEvent(c->evSpp);
+  hipFree(c->accRefl); hipFree(c->accDiff); hipFree(c->converged);
   hipFree(c->tss[0]); hipFree(c->tss[1]);
   hipFree(c->fltRfl); hipFree(c->fltDff); hipFree(c->largeTrisBuf[0]); hipFree(c->largeTrisBuf[1]); hipFree(c->largeCountBase); hipFree(c->rayCounter); hipFree(c->dParams);
   for (auto b : c->binWorkBuf) hipFree(b);
@@ -447,6 +465,7 @@ int rtggx_set_ray_rate(rtggx_context* c, uint32_t pixelsPerRay) {
   RT_CHECK_CTX(c);
   if (pixelsPerRay != 1u && pixelsPerRay != 4u) { setError("rtggx_set_ray_rate: %u pixels per ray: 1 or 4", pixelsPerRay); return -1; }
   if (pixelsPerRay != 1u && c->samplesRequested > 1u) { setError("rtggx_set_ray_rate: rate %u on a context tracing %u samples per pixel (rtggx_set_samples_per_pixel): one asks for fewer rays, the other for more", pixelsPerRay, c->samplesRequested); return -1; }
+  if (pixelsPerRay != 1u && c->accumulateRequested) { setError("rtggx_set_ray_rate: rate %u on an accumulating context (rtggx_set_accumulation): three quarters of such a frame are interpolations", pixelsPerRay); return -1; }
   if (pixelsPerRay != 1u && (c->rowBegin > 0u || c->rowEnd < c->H)) { setError("rtggx_set_ray_rate: rate %u on a strip (rows [%u,%u) of %u): whole frames only", pixelsPerRay, c->rowBegin, c->rowEnd, c->H); return -1; }
   if (pixelsPerRay == c->rayRate) return 0;
   RT_HIP(syncStreams(c));
@@ -481,6 +500,49 @@ int rtggx_set_samples_per_pixel(rtggx_context* c, uint32_t samples) {
   if (samples > 1u) { const int r = allocSamples(c); if (r) return r; }
   c->samplesRequested = samples;
   return 0;
+}
+
+// Progressive accumulation (raytrace.hip accumulateKernel; DESIGN.md "Progressive accumulation").  Taken over by the next
+// rtggx_render_visibility; the first enable allocates (allocAccumulation), off never does.  No synchronisation and no end of the still-sky
+// runs: the kernel only reads the current set's traced images and the frame's visibility words, behind everything that writes them.
+int rtggx_set_accumulation(rtggx_context* c, int enable) {
+  RT_CHECK_CTX(c);
+  if (enable && c->rayRate != 1u) { setError("rtggx_set_accumulation: on a context tracing one pixel in %u (rtggx_set_ray_rate): three quarters of such a frame are interpolations", c->rayRate); return -1; }
+  if (enable) { const int r = allocAccumulation(c); if (r) return r; }
+  c->accumulateRequested = enable != 0;
+  return 0;
+}
+// Sums and count back to zero: two clears on the main stream, behind the frames it holds and in front of the next one; nothing waits.
+int rtggx_reset_accumulation(rtggx_context* c) {
+  RT_CHECK_CTX(c);
+  if (c->accRefl) {
+    const size_t n = (size_t)c->W * c->H;
+    RT_HIP(hipMemsetAsync(c->accRefl, 0, n * 16, c->streamMain));
+    RT_HIP(hipMemsetAsync(c->accDiff, 0, n * 16, c->streamMain));
+  }
+  c->accumFrames = 0u;
+  return 0;
+}
+int rtggx_accumulated_frames(rtggx_context* c, uint32_t* frames) {
+  RT_CHECK_CTX(c);
+  if (!frames) { setError("rtggx_accumulated_frames: null result"); return -1; }
+  *frames = c->accumFrames;      // (counted as the frames are enqueued: no wait)
+  return 0;
+}
+// The mean image, then the tone map of it (the frame's own kernel, reading RTGGX_BUF_CONVERGED instead of TemporalSSOut), both on the main
+// stream.  Between a frame's rtggx_denoise and its rtggx_tone_map it takes the back buffer from a fused temporal pass: that tone map then
+// runs as a kernel of its own again.
+int rtggx_present_accumulation(rtggx_context* c) {
+  RT_CHECK_CTX(c);
+  if (!c->accRefl) { setError("rtggx_present_accumulation: accumulation was never enabled (rtggx_set_accumulation)"); return -1; }
+  if (c->rowBegin > 0u || c->rowEnd < c->H) { setError("rtggx_present_accumulation: on a strip (rows [%u,%u) of %u): whole frames only", c->rowBegin, c->rowEnd, c->H); return -1; }
+  if (c->accumFrames == 0u) { setError("rtggx_present_accumulation: no frame has been accumulated"); return -1; }
+  FrameParams fp = c->slots[c->slot];      // (only the size and the rows enter the tone map)
+  fp.W = c->W; fp.H = c->H; fp.rowBegin = 0u; fp.rowEnd = c->H;
+  int r = launchPresentAccumulation(c, c->streamMain);
+  if (!r) r = launchToneMap(c, fp, c->streamMain, nullptr, c->converged);
+  c->toneMapDone = false;
+  return r;
 }
 
 int rtggx_set_mesh(rtggx_context* c, uint32_t slot, const float* verts, uint32_t nv, const uint32_t* idx, uint32_t ni) {
@@ -848,7 +910,7 @@ int rtggx_render_visibility(rtggx_context* c) {
   if (!c->shDone && c->env.texels) { const int r = projectSH(c, c->streamAS); if (r) return r; }   // first frame only, RayTracer.cpp:345-350
   settleSetRead(c);      // (the previous frame ended without the kernel that would have carried its set's event)
   ++c->frameCounter;
-  c->maxDepth = c->depthRequested; c->samples = c->samplesRequested;
+  c->maxDepth = c->depthRequested; c->samples = c->samplesRequested; c->accumulate = c->accumulateRequested;
   c->denoiseIssued = false; c->toneMapDone = false;
   c->selectSet(c->setAhead(1u));
   // the set was last read four frames ago: normally long done; a host that has run further ahead than that waits here (also what makes
@@ -946,6 +1008,16 @@ int rtggx_ray_trace(rtggx_context* c) {
   if (c->rayRate == 4u) {
     if (!r) r = launchReconstruct(c, fp, c->streamMain);
     c->diffStream = c->streamMain;
+  }
+  // accumulation (rtggx_set_accumulation): the frame's two traced images into the running sums, on the main stream.  Both images are
+  // complete where the main stream stands: it has passed ev.trace, which rides on the traversal with the shading (and the resolve of N
+  // samples) following on the main stream itself, or -- small launches -- on the LAST kernel of the shading on the traversal's stream
+  // (launchShade's `done`: the final pass, or the resolve); ray generation, which writes the background words, precedes the traversal.
+  // The sums exist once: consecutive frames' kernels follow each other on the main stream, whichever stream shaded them.  The kernel
+  // reads the current set in front of the denoiser, so the set's evRead -- recorded behind it on this stream -- covers it.
+  if (c->accumulate) {
+    if (!r) r = launchAccumulate(c, fp, c->streamMain);
+    if (!r) ++c->accumFrames;
   }
   // the main stream has now been given work that reads the current input set: that set may not be overwritten (four frames from now)
   // before its evRead, which rides on the LAST kernel the main stream gets for this frame (settleSetRead)
@@ -1184,6 +1256,10 @@ static int bufferInfo(rtggx_context* c, int id, void** ptr, size_t* bytes) {
     case RTGGX_BUF_BIN_WORK: *ptr = c->binWork; *bytes = (size_t)(((c->W + 15) / 16) * ((c->H + 15) / 16)) * 4u * 4u; return 0;
     case RTGGX_BUF_ENV: *ptr = c->env.texels; *bytes = (size_t)c->env.totalTexels * 8; return 0;
     case RTGGX_BUF_EXCHANGE_TOKENS: *ptr = c->exchangeTokens; *bytes = 4 * 2 * RT_MAX_PEERS; return 0;
+    case RTGGX_BUF_ACC_REFL: case RTGGX_BUF_ACC_DIFF: case RTGGX_BUF_CONVERGED:
+      if (!c->accRefl) { setError("buffer %d exists once accumulation has been enabled (rtggx_set_accumulation)", id); return -1; }
+      *ptr = id == RTGGX_BUF_ACC_REFL ? (void*)c->accRefl : id == RTGGX_BUF_ACC_DIFF ? (void*)c->accDiff : (void*)c->converged;
+      *bytes = n * (id == RTGGX_BUF_CONVERGED ? 8u : 16u); return 0;
     default: setError("unknown buffer id %d", id); return -1;
   }
 }

@@ -746,9 +746,11 @@ int launchDenoise(rtggx_context* c, const FrameParams& fp, int useLds, hipStream
 
 // The tone map as a kernel of its own: a caller that tone-maps without having denoised in this frame, the per-pass timing mode, and
 // rtggx_debug_fuse_tone_map(ctx, 0) -- the two-kernel path of rounds 1-3, kept for comparison with the fused one.
-int launchToneMap(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent_t done) {
+// `source`: another RGBA16F image in place of TSS[parity] (rtggx_present_accumulation: the mean image); the kernel only reads it.
+int launchToneMap(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent_t done, const uint2* source) {
   if (fp.rowEnd <= fp.rowBegin) return 0;
-  const Targets T = makeTargets(c, fp, ROWS_FINAL);
+  Targets T = makeTargets(c, fp, ROWS_FINAL);
+  if (source) T.scratch = const_cast<uint2*>(source);
   const dim3 grid((fp.W + 63) / 64, (uint32_t)(T.rowEnd - T.rowBegin + RT_TM_ROWS - 1) / RT_TM_ROWS), block(256);
   launch(toneMapKernel, grid, block, s, nullptr, done, T);
   RT_HIP(hipGetLastError());

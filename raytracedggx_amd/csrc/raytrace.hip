@@ -1233,4 +1233,63 @@ int launchDebugEnvironment(rtggx_context* c, const float* dDirs, const float* dL
   return 0;
 }
 
+// ---- progressive accumulation (rtggx_set_accumulation; include/rtggx.h, DESIGN.md "Progressive accumulation") ---------------------
+// The frame's two traced images added to the running sums: one lane per pixel of the strip's own rows -- whole rows, so the pixels are
+// one contiguous range [first, first + count) of every image --, a streaming pass of 8 + 4 (+ 4) bytes read and 16 (+ 16) read and
+// written per pixel.  It visits every pixel and asks no tile word: a sky tile holds its environment words in every input set, whoever
+// wrote them (ray generation this frame, or an earlier one where a still sky was left alone).  The diffuse image is added where a diffuse
+// path wrote it this frame: a covered pixel whose instance's metallic is below 1 (diffMask, bit per instance: resolveSamplesKernel's rule).
+// fp32, every operation rounded on its own (no contraction), the order of the sum is the order of the launches on the stream.
+struct AccumArgs {
+  const unsigned long long* visDepth; const uint32_t* refl; const uint32_t* diff; float4* accRefl; float4* accDiff;
+  uint32_t first, count, diffMask;
+};
+RT_DEV float4 accumulateWord(float4 a, uint32_t word) {
+#pragma clang fp contract(off)
+  const f3 c = unpackR11G11B10F(word);
+  const float y = (0.25f * c.x + 0.5f * c.y) + 0.25f * c.z;      // the luma of the temporal pass's YCoCg
+  return make_float4(a.x + c.x, a.y + c.y, a.z + c.z, a.w + y * y);
+}
+__global__ void __launch_bounds__(256) accumulateKernel(AccumArgs A) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= A.count) return;
+  const size_t pix = (size_t)A.first + i;
+  const uint32_t vis = (uint32_t)A.visDepth[pix];
+  A.accRefl[pix] = accumulateWord(A.accRefl[pix], A.refl[pix]);
+  const uint32_t inst = (vis - 1u) >> 24;      // (two instances: an uploaded word that names another has no material)
+  if (vis != 0u && inst < 2u && ((A.diffMask >> inst) & 1u)) A.accDiff[pix] = accumulateWord(A.accDiff[pix], A.diff[pix]);
+}
+int launchAccumulate(rtggx_context* c, const FrameParams& fp, hipStream_t s) {
+  if (!c->accRefl || !c->accDiff) { setError("rtggx_ray_trace: accumulation without its buffers"); return -1; }
+  if (fp.rowEnd <= fp.rowBegin) return 0;
+  const InputSet& set = c->cur();
+  AccumArgs A;
+  A.visDepth = c->curVis().depth; A.refl = set.rtRefl; A.diff = set.rtDiff; A.accRefl = c->accRefl; A.accDiff = c->accDiff;
+  A.first = fp.rowBegin * fp.W; A.count = (fp.rowEnd - fp.rowBegin) * fp.W;
+  A.diffMask = (fp.mat.RoughMetals[0][1] < 1.0f ? 1u : 0u) | (fp.mat.RoughMetals[1][1] < 1.0f ? 2u : 0u);
+  hipLaunchKernelGGL(accumulateKernel, dim3((A.count + 255u) / 256u), dim3(256), 0, s, A);
+  RT_HIP(hipGetLastError());
+  return 0;
+}
+
+// The mean image of rtggx_present_accumulation: per component (float)((double)sum / (double)n) of each image, the two means added in
+// fp32 -- the denoiser's composition dest + diffuse (denoise.hip spatialTiledKernel<3>); A1 is zero where no diffuse path contributed.
+__global__ void __launch_bounds__(256) presentAccumulationKernel(const float4* __restrict__ accRefl, const float4* __restrict__ accDiff, uint2* __restrict__ out, uint32_t count, uint32_t frames) {
+#pragma clang fp contract(off)
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= count) return;
+  const double n = (double)frames;
+  const float4 a = accRefl[i], d = accDiff[i];
+  const float r = (float)((double)a.x / n) + (float)((double)d.x / n);
+  const float g = (float)((double)a.y / n) + (float)((double)d.y / n);
+  const float b = (float)((double)a.z / n) + (float)((double)d.z / n);
+  out[i] = packRGBA16F(r, g, b, 1.0f);
+}
+int launchPresentAccumulation(rtggx_context* c, hipStream_t s) {
+  const uint32_t count = c->W * c->H;
+  hipLaunchKernelGGL(presentAccumulationKernel, dim3((count + 255u) / 256u), dim3(256), 0, s, (const float4*)c->accRefl, (const float4*)c->accDiff, c->converged, count, c->accumFrames);
+  RT_HIP(hipGetLastError());
+  return 0;
+}
+
 }  // namespace rt

@@ -258,6 +258,13 @@ struct rtggx_context {
   uint32_t samples = 1, samplesRequested = 1;
   float* sppAcc = nullptr; rt::FrameParams* sppParams = nullptr;
   hipStream_t sppStream = nullptr; hipEvent_t evSpp = nullptr;      // the stream of the most recent frame that used sppAcc
+  // rtggx_set_accumulation (raytrace.hip accumulateKernel; DESIGN.md "Progressive accumulation"): the frame's, the next frame's.  The sums
+  // exist ONCE, from the first enable on (capi.hip allocAccumulation), [W * H] float4 each -- sum r, g, b, Y^2 of RayTracingOut0 / 1 --, and
+  // are touched by the main stream alone (the kernel behind the hit shading, the reset's clears, the present): stream order is the order of
+  // the frames.  accumFrames: frames added since the last reset, counted by the host as it enqueues them.
+  bool accumulate = false, accumulateRequested = false;
+  uint32_t accumFrames = 0;
+  float4 *accRefl = nullptr, *accDiff = nullptr; uint2* converged = nullptr;      // converged: RTGGX_BUF_CONVERGED (rtggx_present_accumulation)
   uint32_t traceGrid[4] = {};    // the frame's level-0 trace launch -- bins, tile grid x / y, slice shift --, which the later levels repeat
   float rebuildRatio = 1.2f; uint32_t rebuildSteps = 16;      // rtggx_set_refit_policy
   rt::MeshDev mesh[2];
@@ -421,10 +428,13 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
 int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent_t done = nullptr);      // hit / miss shading of the traced bins
 int launchReconstruct(rtggx_context* c, const FrameParams& fp, hipStream_t s);
 int allocSamples(rtggx_context* c);      // what N > 1 samples per pixel need (rtggx_context::sppAcc, sppParams), once      // rate 4: the untraced pixels of RayTracingOut0/1, after the hit shading
+int allocAccumulation(rtggx_context* c);      // what rtggx_set_accumulation needs (rtggx_context::accRefl, accDiff, converged), once
+int launchAccumulate(rtggx_context* c, const FrameParams& fp, hipStream_t s);      // the frame's traced images added to the sums, the strip's own rows
+int launchPresentAccumulation(rtggx_context* c, hipStream_t s);      // RTGGX_BUF_CONVERGED from the sums and accumFrames
 int launchTraceRays(rtggx_context* c, const FrameParams& fp, const float* dRays, uint32_t n, float* dOut, hipStream_t s);
 int launchDebugEnvironment(rtggx_context* c, const float* dDirs, const float* dLevels, uint32_t n, int level0, float* dOut, hipStream_t s);      // rtggx_debug_environment: reads the environment only
 int launchDenoise(rtggx_context* c, const FrameParams& fp, int useLds, hipStream_t s, hipEvent_t done = nullptr, bool fuseToneMap = false);      // fuseToneMap: the last kernel also writes the back buffer
-int launchToneMap(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent_t done = nullptr);
+int launchToneMap(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent_t done = nullptr, const uint2* source = nullptr);      // source: an RGBA16F image to tone-map instead of TemporalSSOut[parity]
 int decodeEnv(rtggx_context* c, int format, uint32_t size, uint32_t mips, const void* hostData, size_t bytes, hipStream_t s);
 int projectSH(rtggx_context* c, hipStream_t s);
 int unpackVisDepth(rtggx_context* c, uint32_t* dVis, uint32_t* dDepth, hipStream_t s);

@@ -35,6 +35,11 @@ int main(int argc, char* argv[]) {
       if (!hasExt) name += ".ppm";
       if (app.SaveImage(name.c_str())) std::printf("wrote %s\n", name.c_str());
     }
+    if (app.GetAccumulate()) {      // -accumulate N: the mean of the accumulated frames, <prefix>_converged.png (after the -dump image: it takes the back buffer)
+      std::string stem = app.GetDumpPrefix().empty() ? std::string("RayTracedGGX") : app.GetDumpPrefix();
+      if (stem.size() >= 4 && (stem.compare(stem.size() - 4, 4, ".png") == 0 || stem.compare(stem.size() - 4, 4, ".ppm") == 0)) stem.resize(stem.size() - 4);
+      if (!app.SaveConverged((stem + "_converged.png").c_str())) { app.OnDestroy(); return 1; }
+    }
     app.OnDestroy();
   } catch (const std::exception& e) {
     std::fprintf(stderr, "RayTracedGGX: %s\n", e.what());

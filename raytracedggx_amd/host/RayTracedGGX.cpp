@@ -76,6 +76,9 @@ void RayTracedGGX::OnUpdate() {
       default: OnMouseLeave(); break;
     }
   }
+  // -accumulate N: on from the frame that leaves N frames of the run (from the first one when the run is no longer than N)
+  if (m_accumulate != 0u && m_frameNumber == (m_numFrames > m_accumulate ? m_numFrames - m_accumulate : 0u) && !m_rayTracer->SetAccumulation(true))
+    throw std::runtime_error("-accumulate: " + m_rayTracer->GetLastError());
   if (!m_deformShapes.empty() && !m_isPaused) {
     const std::vector<float>& shape = m_deformShapes[m_frameNumber % DeformPeriod];
     m_rayTracer->UpdateMesh(shape.data(), (uint32_t)(shape.size() / 6));
@@ -194,7 +197,7 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
     return (arg[0] == '-' || arg[0] == '/') && lower(arg + 1) == lower(name);
   };
   // On POSIX an absolute path also starts with '/': such a token is a flag only when it names one.
-  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "recursion", "spp"};
+  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "recursion", "spp", "accumulate"};
   const auto isFlagName = [&](const char* name) { for (const char* f : kFlags) if (lower(name) == f) return true; return false; };
   const auto hasNextArgValue = [&](int i) {
     if (i + 1 >= argc) return false;
@@ -233,6 +236,11 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
       if (samples != 1 && samples != 2 && samples != 4 && samples != 8) throw std::runtime_error("-spp: 1, 2, 4 or 8 samples per pixel");
       m_samplesPerPixel = (uint32_t)samples;
     }
+    else if (isArgMatched(i, "accumulate")) {
+      const int frames = hasNextArgValue(i) ? std::atoi(argv[++i]) : 0;
+      if (frames < 1) throw std::runtime_error("-accumulate: a number of frames, 1 or more");
+      m_accumulate = (uint32_t)frames;
+    }
     else if (isArgMatched(i, "device")) { if (hasNextArgValue(i)) m_device = std::atoi(argv[++i]); }
     else if (isArgMatched(i, "dump")) { if (hasNextArgValue(i)) m_dumpPrefix = argv[++i]; }
     else if (isArgMatched(i, "deform")) { nextFloat(i, m_deformAmplitude); }
@@ -246,6 +254,9 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
     else if (isArgMatched(i, "strips")) { if (hasNextArgValue(i)) m_strips = std::atoi(argv[++i]); if (m_strips < 1 || m_strips > 64) throw std::runtime_error("-strips: 1 .. 64"); }
     else if (isArgMatched(i, "balance")) { if (hasNextArgValue(i)) m_balance = std::atoi(argv[++i]) != 0; }
   }
+  // three quarters of a rate-4 frame are interpolations (rtggx_set_accumulation); the sums of several strips are not gathered
+  if (m_accumulate != 0u && m_rayRate != 1u) throw std::runtime_error("-accumulate together with -rayrate 4: refused");
+  if (m_accumulate != 0u && (m_gpus > 1 || m_strips > 1)) throw std::runtime_error("-accumulate: whole frames on one GPU only, not with -gpus N > 1 or -strips N > 1");
   // quarter-rate tracing renders whole frames only (rtggx_set_ray_rate): refused here, before anything has touched a GPU
   // one knob asks for fewer rays, the other for more (rtggx_set_samples_per_pixel)
   if (m_rayRate != 1u && m_samplesPerPixel != 1u) throw std::runtime_error("-spp N > 1 together with -rayrate 4: refused");
@@ -293,6 +304,43 @@ bool WritePng(const char* fileName, uint32_t w, uint32_t h, uint32_t comp, const
   const bool ok = std::fwrite(file.data(), 1, file.size(), f) == file.size();
   std::fclose(f);
   return ok;
+}
+
+// The mean relative standard error of Y over covered pixels of one accumulated image, from its sums (4 floats per pixel: sum r, g, b, Y^2):
+// per pixel mean = (0.25 sum r + 0.5 sum g + 0.25 sum b) / n, variance = (sum Y^2 / n - mean^2) n / (n - 1), error = sqrt(variance / n) / mean;
+// pixels the image never received anything at (all four sums zero) and pixels of mean 0 are left out.  Negative: no pixel counted.
+// n is the count of ALL accumulated frames: the figure assumes what -accumulate provides, materials and coverage that stay as they are over
+// those frames.  Where fewer than n frames contributed to a pixel of the diffuse image (metallic changed in mid-run, the model turned under
+// it), mean and variance are those of a sum diluted by the missing frames, not the diffuse image's own: reset after such a change.
+static double meanRelativeStdError(const std::vector<float>& sums, const std::vector<uint32_t>& visibility, uint32_t n) {
+  double total = 0.0; size_t counted = 0;
+  for (size_t i = 0; i < visibility.size(); ++i) {
+    if (!visibility[i]) continue;
+    const double r = sums[4 * i], g = sums[4 * i + 1], b = sums[4 * i + 2], yy = sums[4 * i + 3];
+    const double mean = (0.25 * r + 0.5 * g + 0.25 * b) / n;
+    if (!(mean > 0.0) || !std::isfinite(mean) || !std::isfinite(yy)) continue;
+    const double var = std::max(yy / n - mean * mean, 0.0) * (n > 1u ? (double)n / (n - 1u) : 1.0);
+    total += std::sqrt(var / n) / mean; ++counted;
+  }
+  return counted ? total / (double)counted : -1.0;
+}
+
+bool RayTracedGGX::SaveConverged(const char* fileName) {
+  rtggx_context* ctx = GetContext();
+  if (!ctx) return false;
+  uint32_t n = 0;
+  if (rtggx_present_accumulation(ctx) != 0 || rtggx_accumulated_frames(ctx, &n) != 0) { std::fprintf(stderr, "SaveConverged: %s\n", rtggx_last_error()); return false; }
+  if (!SaveImage(fileName)) return false;
+  const size_t pixels = (size_t)m_width * m_height;
+  std::vector<uint32_t> vis(pixels); std::vector<float> refl(4 * pixels), diff(4 * pixels);
+  if (rtggx_readback(ctx, RTGGX_BUF_VISIBILITY, vis.data(), pixels * 4) != 0 || rtggx_readback(ctx, RTGGX_BUF_ACC_REFL, refl.data(), pixels * 16) != 0 ||
+      rtggx_readback(ctx, RTGGX_BUF_ACC_DIFF, diff.data(), pixels * 16) != 0) { std::fprintf(stderr, "SaveConverged: %s\n", rtggx_last_error()); return false; }
+  const double eR = meanRelativeStdError(refl, vis, n), eD = meanRelativeStdError(diff, vis, n);
+  std::printf("accumulated %u frames: mean relative standard error of Y over covered pixels, reflection %.5f", n, eR);
+  if (eD >= 0.0) std::printf(", diffuse %.5f", eD);
+  std::printf("\nwrote %s\n", fileName);
+  std::fflush(stdout);
+  return true;
 }
 
 bool RayTracedGGX::SaveImage(const char* fileName) {

@@ -2,7 +2,7 @@
 // DXFramework virtuals RayTracedGGX/Common/DXFramework.h:23-26): OnInit / OnUpdate / OnRender /
 // OnDestroy, the same command line (RayTracedGGX.cpp:462-511) and the same defaults
 // (RayTracedGGX.cpp:37-39, camera :19-23, 267-277).  What the window supplied interactively is
-// supplied by extra flags: -width -height -frames -dt -metallic -sharedmem -sync -vndf -rayrate -recursion -spp -device -dump -track -deform -gpus -strips -balance.
+// supplied by extra flags: -width -height -frames -dt -metallic -sharedmem -sync -vndf -rayrate -recursion -spp -accumulate -device -dump -track -deform -gpus -strips -balance.
 #pragma once
 #include <vector>
 #include <cstdint>
@@ -55,6 +55,11 @@ class RayTracedGGX {
   RayTracer* GetRayTracer() const { return m_rayTracer.get(); }
   rtggx_context* GetContext() const { return m_rayTracer ? m_rayTracer->GetContext() : nullptr; }
   void SetFixedTimeStep(float dt) { m_fixedTimeStep = dt; }
+  // -accumulate N: the mean of the accumulated frames presented (rtggx_present_accumulation) and its tone map written like SaveImage's; one
+  // line on stdout: the frame count and the mean relative standard error of Y over covered pixels, from the sums, in double (per image;
+  // it divides by the count of all accumulated frames, so it assumes materials that did not change since the last reset)
+  uint32_t GetAccumulate() const { return m_accumulate; }
+  bool SaveConverged(const char* fileName);
   bool SaveImage(const char* fileName);   // tone-mapped back buffer as PNG (name ends in .png) or binary PPM (screenshot, RayTracedGGX.cpp:719-739)
 
  protected:
@@ -100,6 +105,7 @@ class RayTracedGGX {
   bool m_vndf = false;                 // -vndf
   uint32_t m_recursionDepth = 1;       // -recursion <1..4>: levels of rays per path (RayTracer::SetMaxRecursionDepth)
   uint32_t m_samplesPerPixel = 1;      // -spp <1|2|4|8>: samples per covered pixel (RayTracer::SetSamplesPerPixel); not together with -rayrate 4
+  uint32_t m_accumulate = 0;           // -accumulate <N>: accumulation on for the last N frames of the run (all of them when N >= -frames); not with -rayrate 4, -gpus, -strips
   uint32_t m_rayRate = 1;              // -rayrate <1|4>: pixels per traced ray (RayTracer::SetRayRate); 4 renders whole frames only: not with -gpus / -strips
   // -deform <amplitude>: the model breathes -- a travelling sine wave through its vertices, DeformPeriod key shapes computed once
   // at start-up and handed to RayTracer::UpdateMesh one per frame (per-frame host cost: one copy of the vertex array)

@@ -72,6 +72,9 @@ bool RayTracer::SetRayRate(uint32_t pixelsPerRay) { return check(rtggx_set_ray_r
 bool RayTracer::SetSamplesPerPixel(uint32_t samples) { return check(rtggx_set_samples_per_pixel(m_ctx, samples), "rtggx_set_samples_per_pixel"); }
 bool RayTracer::SetMaxRecursionDepth(uint32_t depth) { return check(rtggx_set_max_recursion_depth(m_ctx, depth), "rtggx_set_max_recursion_depth"); }
 
+bool RayTracer::SetAccumulation(bool enable) { return check(rtggx_set_accumulation(m_ctx, enable ? 1 : 0), "rtggx_set_accumulation"); }
+bool RayTracer::ResetAccumulation() { return check(rtggx_reset_accumulation(m_ctx), "rtggx_reset_accumulation"); }
+
 void RayTracer::SetAsyncCompute(bool asyncCompute) { check(rtggx_set_async_compute(m_ctx, asyncCompute ? 1 : 0), "rtggx_set_async_compute"); }
 
 void RayTracer::UpdateFrame(uint8_t frameIndex, const xm::Float3& eyePt, const xm::Matrix& viewProj, float timeStep) {

@@ -43,6 +43,10 @@ class RayTracer {
   bool SetRayRate(uint32_t pixelsPerRay);
   bool SetSamplesPerPixel(uint32_t samples);   // rtggx_set_samples_per_pixel: 1 (default), 2, 4 or 8 samples per covered pixel (-spp); not together with ray rate 4
   bool SetMaxRecursionDepth(uint32_t depth);   // rtggx_set_max_recursion_depth: 1 (default; RayTracer.cpp:605 SetMaxRecursionDepth(1)) to 4 levels of rays per path (-recursion)   // rtggx_set_ray_rate: 1 (default) or 4 -- one pixel of each 2x2 quad traced per frame, the rest reconstructed (-rayrate)
+  // rtggx_set_accumulation / rtggx_reset_accumulation: the running sums of the raw traced images, on from the next frame (-accumulate);
+  // not together with ray rate 4.  A moving camera or a changed material is the caller's to reset.
+  bool SetAccumulation(bool enable);
+  bool ResetAccumulation();
   void UpdateFrame(uint8_t frameIndex, const xm::Float3& eyePt, const xm::Matrix& viewProj, float timeStep);
   void TransformSH();
   void Render(uint8_t frameIndex);

@@ -8,7 +8,8 @@ import assets
 from raytracedggx_amd import app
 torch.cuda.init()
 for mesh, W, H, extra in (("bunny.obj", 1920, 1080, ()), ("bunny.obj", 1920, 1080, ("-metallic", 1.0, 0.5)), ("dragon.obj", 1920, 1080, ()), ("bunny.obj", 3840, 2160, ()), ("bunny.obj", 1920, 171, ()),
-                             ("bunny.obj", 1920, 1080, ("-spp", 2)), ("bunny.obj", 3840, 2160, ("-spp", 2)), ("bunny.obj", 3840, 2160, ("-spp", 8))):
+                             ("bunny.obj", 1920, 1080, ("-spp", 2)), ("bunny.obj", 3840, 2160, ("-spp", 2)), ("bunny.obj", 3840, 2160, ("-spp", 8)),
+                             ("bunny.obj", 1920, 1080, ("-accumulate", 16)), ("bunny.obj", 3840, 2160, ("-accumulate", 16))):
     torch.cuda.synchronize()
     free0, _ = torch.cuda.mem_get_info()
     a = app.RayTracedGGX(["-mesh", assets.path(mesh), "-env", assets.path("rnl_cross.dds"), "-width", W, "-height", H, "-sharedmem"] + list(extra))
