@@ -250,6 +250,29 @@ int  rtggx_set_max_recursion_depth(rtggx_context* ctx, uint32_t depth);
  * allocates 24 bytes per pixel of the full frame, released by rtggx_destroy.  Takes effect from the next rtggx_render_visibility. */
 #define RTGGX_MAX_SAMPLES_PER_PIXEL 8u
 int  rtggx_set_samples_per_pixel(rtggx_context* ctx, uint32_t samples);
+/* Sample-set size (RayTracer::SetSampleSetSize; the reference's shader declares getSampleParam(index, dim, numSamples = 256) and never
+ * passes another size): M = RTGGX_MIN_SAMPLE_SET (default: the reference's renderer, bit for bit) or a power of two up to
+ * RTGGX_MAX_SAMPLE_SET; anything else is refused and the context keeps what it had (DESIGN.md "Sample-set size").
+ *   - the sample with index i at pixel (x, y) of a frame W pixels wide: s = rng(rng(y W + x) + i) & (M - 1); xi.x = s / M;
+ *     xi.y = (rng(s) & 0xffff) / 65536; (cosPhi, sinPhi) = ((float)cos(phi), (float)sin(phi)) with
+ *     phi = 2.0 * 3.14159265358979323846 * (double)s / (double)M -- double libm, rounded once: the table rule of the 256-member set with M
+ *     in place of 256, so entry k M / 256 of the M-table equals entry k of that one;
+ *   - i is what it is at M = 256: FrameIndex at one sample per pixel, FrameIndex * N + k at N samples; the same pixel's xi at every level of
+ *     a path of depth D; both samplers, GGX and VNDF (rtggx_set_sampler), take it;
+ *   - nothing else of a frame depends on M: G-buffer, visibility, background words, still-sky runs, tile words, the rate-4 pattern
+ *     (FrameIndex & 3) and the denoiser;
+ *   - the caller's FrameIndex should count modulo M (RayTracer::UpdateFrame does): the library does not wrap it.  With a still camera the
+ *     frames then repeat after M instead of 256, and an accumulation converges that much further;
+ *   - works at every recursion depth and sample count, at ray rate 4, on strips, with a deforming mesh, accumulation and a still sky.  It
+ *     ends no still-sky run (a pixel without a surface takes no sample) and resets no accumulation: like a changed material that is the
+ *     caller's to do.
+ * Every size M > 256 allocates, the first time it is set, a table of 2 M floats (512 KB at 65536), released by rtggx_destroy; a context that
+ * never calls this allocates and launches exactly what it always did.  Takes effect from the next rtggx_render_visibility; synchronises --
+ * and where that rtggx_render_visibility renders from the constants of an earlier frame (no rtggx_update_frame in between) it waits for that
+ * frame first. */
+#define RTGGX_MIN_SAMPLE_SET 256u
+#define RTGGX_MAX_SAMPLE_SET 65536u
+int  rtggx_set_sample_set(rtggx_context* ctx, uint32_t size);
 /* Progressive accumulation (opt-in, no counterpart in the reference; DESIGN.md "Progressive accumulation"): the long-run mean of the
  * denoiser's INPUT, kept on the device.  Off (default): nothing is allocated and a frame launches what it always did.  enable = 1 takes
  * effect from the next rtggx_render_visibility; the first one allocates 2 x 16 + 8 bytes per pixel of the full frame, zeroed, released by
@@ -265,7 +288,8 @@ int  rtggx_set_samples_per_pixel(rtggx_context* ctx, uint32_t samples);
  *   - the sums exist once, not per input set.  A moving camera or a changed material is the caller's to reset:
  *     rtggx_reset_accumulation zeroes the sums and the count, enqueued on the main stream without waiting;
  *   - rtggx_accumulated_frames: n.  With a still camera the sequence of frames repeats after 256: the sample set of the reference has 256
- *     members (getSampleParam) and FrameIndex wraps there -- an accumulation cannot converge past the mean of those 256;
+ *     members (getSampleParam) and FrameIndex wraps there -- an accumulation cannot converge past the mean of those 256 (a larger set:
+ *     rtggx_set_sample_set);
  *   - rtggx_present_accumulation (whole frames and n > 0; refused on a strip and at n = 0): per pixel and component
  *     m0 = (float)((double)A0.c / (double)n), m1 likewise, RTGGX_BUF_CONVERGED = pack_rgba16f(m0.r + m1.r, m0.g + m1.g, m0.b + m1.b, 1)
  *     with fp32 adds -- the denoiser's composition dest + diffuse of the two means, A1 being zero where no diffuse path ever contributed --,

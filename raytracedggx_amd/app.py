@@ -16,7 +16,8 @@ HOST_EXPORTS = ["rtggx_app_last_error", "rtggx_app_create", "rtggx_app_destroy",
                 "rtggx_app_frame_constants", "rtggx_app_save_image", "rtggx_host_obj_import", "rtggx_host_obj_copy",
                 "rtggx_host_halton", "rtggx_host_frame_constants", "rtggx_host_write_png", "rtggx_host_camera",
                 "rtggx_app_on_lbutton_down", "rtggx_app_on_lbutton_up", "rtggx_app_on_mouse_move", "rtggx_app_on_mouse_wheel", "rtggx_app_load_track",
-                "rtggx_host_exchange_plan", "rtggx_host_balanced_bounds", "rtggx_app_set_dump_prefix", "rtggx_app_last_screen_shot", "rtggx_app_save_converged"]
+                "rtggx_host_exchange_plan", "rtggx_host_balanced_bounds", "rtggx_app_set_dump_prefix", "rtggx_app_last_screen_shot", "rtggx_app_save_converged",
+                "rtggx_host_frame_indices", "rtggx_host_accumulation_note"]
 
 _lib = None
 
@@ -57,6 +58,8 @@ def load():
         L.rtggx_app_load_track.argtypes = [C.c_void_p, C.c_char_p]
         L.rtggx_host_camera.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         L.rtggx_host_camera.restype = None
+        L.rtggx_host_frame_indices.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p]
+        L.rtggx_host_frame_indices.restype = C.c_uint32
         L.rtggx_host_write_png.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         _lib = L
     return _lib
@@ -97,6 +100,24 @@ def frame_constants(width, height, frames, dt=1.0 / 60.0, pos_scale=(0, 0, 0, 1)
     load().rtggx_host_frame_constants(width, height, ps.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p),
                                       f.ctypes.data_as(C.c_void_p), dt, frames, out.ctypes.data_as(C.c_void_p))
     return out
+
+
+def frame_indices(sample_set, frames):
+    """RayTracer::SetSampleSetSize(sample_set) and `frames` consecutive UpdateFrame calls of the host layer -> (the size the RayTracer holds
+    -- 256 where the setter refused --, FrameIndex[frames])."""
+    out = np.zeros(frames, np.uint32)
+    held = load().rtggx_host_frame_indices(int(sample_set), frames, out.ctypes.data_as(C.c_void_p))
+    return held, out
+
+
+def accumulation_note(frames, samples, sample_set):
+    """What the line -accumulate prints says about the sample set after `frames` frames of `samples` samples (no device)."""
+    L = load()
+    buf = C.create_string_buffer(512)
+    L.rtggx_host_accumulation_note.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int]
+    if L.rtggx_host_accumulation_note(int(frames), int(samples), int(sample_set), buf, 512) < 0:
+        raise ValueError("rtggx_host_accumulation_note: capacity")
+    return buf.value.decode()
 
 
 class BorrowedContext(capi.Context):

@@ -34,7 +34,7 @@ EXPORTS = ["rtggx_last_error", "rtggx_create", "rtggx_destroy", "rtggx_set_strip
            "rtggx_ray_count", "rtggx_get_timings", "rtggx_enable_timing", "rtggx_buffer_size", "rtggx_readback", "rtggx_buffer_ptr",
            "rtggx_upload", "rtggx_frame_parity", "rtggx_bvh_root", "rtggx_trace_rays", "rtggx_ray_total", "rtggx_kernel_times", "rtggx_debug_counters", "rtggx_debug_trace_split", "rtggx_debug_trace_residency", "rtggx_get_stream", "rtggx_set_history_peers", "rtggx_history_ipc_export", "rtggx_history_ipc_open",
            "rtggx_set_async_compute", "rtggx_set_history_apron", "rtggx_history_overreach", "rtggx_copy_bandwidth", "rtggx_refit_as", "rtggx_refit_as_device", "rtggx_refit_stats", "rtggx_set_refit_policy", "rtggx_set_sampler", "rtggx_set_ray_rate", "rtggx_set_max_recursion_depth", "rtggx_set_samples_per_pixel", "rtggx_debug_fuse_tone_map", "rtggx_debug_placement", "rtggx_debug_tile_words", "rtggx_debug_static_sky", "rtggx_debug_sky_runs", "rtggx_debug_collapse_weights", "rtggx_debug_fence_wait", "rtggx_debug_shader_clock", "rtggx_debug_environment",
-           "rtggx_set_accumulation", "rtggx_reset_accumulation", "rtggx_accumulated_frames", "rtggx_present_accumulation"]
+           "rtggx_set_accumulation", "rtggx_reset_accumulation", "rtggx_accumulated_frames", "rtggx_present_accumulation", "rtggx_set_sample_set"]
 
 
 class Timings(C.Structure):
@@ -65,6 +65,7 @@ def load():
     L.rtggx_set_ray_rate.argtypes = [vp, C.c_uint32]
     L.rtggx_set_max_recursion_depth.argtypes = [vp, C.c_uint32]
     L.rtggx_set_samples_per_pixel.argtypes = [vp, C.c_uint32]
+    L.rtggx_set_sample_set.argtypes = [vp, C.c_uint32]
     L.rtggx_set_accumulation.argtypes = [vp, C.c_int]
     L.rtggx_reset_accumulation.argtypes = [vp]
     L.rtggx_accumulated_frames.argtypes = [vp, C.POINTER(C.c_uint32)]
@@ -270,6 +271,11 @@ class Context:
     def set_samples_per_pixel(self, samples):
         """1 (default), 2, 4 or 8 samples per covered pixel (include/rtggx.h); taken over by the next frame; not together with ray rate 4."""
         self._check(self.L.rtggx_set_samples_per_pixel(self.h, int(samples)))
+
+    def set_sample_set(self, size):
+        """The size of the sample set: 256 (default) or a power of two up to 65536 (include/rtggx.h); taken over by the next frame;
+        synchronises.  The caller's FrameIndex should count modulo it."""
+        self._check(self.L.rtggx_set_sample_set(self.h, int(size)))
 
     def set_accumulation(self, enable):
         """Progressive accumulation of the raw traced images (include/rtggx.h): on from the next frame; the first enable allocates 40 bytes

@@ -272,6 +272,20 @@ int allocSamples(rtggx_context* c) {
   }
   return 0;
 }
+// The table of a sample set of M > 256 members (rtggx_set_sample_set): M pairs {cos, sin}(2 pi s / M), double libm rounded once -- the rule of
+// the 256-entry table, whose entry k is this one's entry k M / 256 bit for bit (the quotient s / M is the same double).  Made once per size.
+int allocSampleTable(rtggx_context* c, uint32_t m) {
+  float*& tab = c->cosSinWide[rtggx_context::sampleSetSlot(m)];
+  if (tab) return 0;
+  std::vector<float> host(2u * (size_t)m);
+  for (uint32_t s = 0; s < m; ++s) { const double phi = 2.0 * 3.14159265358979323846 * (double)s / (double)m; host[2u * s] = (float)cos(phi); host[2u * s + 1u] = (float)sin(phi); }
+  float* d = nullptr;
+  hipError_t e = hipMalloc(&d, host.size() * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(d, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { hipFree(d); setError("rtggx_set_sample_set: %s (%zu bytes for the table of %u samples)", hipGetErrorString(e), host.size() * sizeof(float), m); return -2; }
+  tab = d;
+  return 0;
+}
 // What accumulation needs (rtggx_set_accumulation): the two sums and the mean image, 2 x 16 + 8 bytes per pixel of the full frame, zeroed;
 // allocated with the first enable -- all three or none --, released by rtggx_destroy.
 int allocAccumulation(rtggx_context* c) {
@@ -326,6 +340,7 @@ void rtggx_destroy(rtggx_context* c) {
     hipFree(m.indices); hipFree(m.dCost); if (m.hCost) hipHostFree(m.hCost); destroyEvent(m.evCost);
   }
   hipFree(c->env.texels); hipFree(c->sh); hipFree(c->cosSinTab); hipFree(c->backbuffer);
+  for (float* t : c->cosSinWide) hipFree(t);
   for (auto& s : c->sets) freeSet(s);
   for (auto& v : c->vis) { hipFree(v.depth); hipFree(v.dirty); }
   hipFree(c->visDirtyOnes);
@@ -499,6 +514,21 @@ int rtggx_set_samples_per_pixel(rtggx_context* c, uint32_t samples) {
   if (samples > 1u && c->rayRate != 1u) { setError("rtggx_set_samples_per_pixel: %u samples per pixel on a context tracing one pixel in %u (rtggx_set_ray_rate): one asks for more rays, the other for fewer", samples, c->rayRate); return -1; }
   if (samples > 1u) { const int r = allocSamples(c); if (r) return r; }
   c->samplesRequested = samples;
+  return 0;
+}
+
+// Sample-set size (raytrace.hip sampleParamWide; DESIGN.md "Sample-set size"): M = 256 (the reference's set: the kernels and the table of a
+// context that never calls this) or a power of two up to 65536, which selects the set-size-aware variants of the three kernels that take a
+// sample and a table of M {cos, sin} pairs (allocSampleTable).  Taken over by the next rtggx_render_visibility; synchronises like
+// rtggx_set_ray_rate.  No end of the still-sky runs -- a pixel without a surface takes no sample, and bins, cost records and split lists
+// do not depend on M -- and no reset of an accumulation.
+int rtggx_set_sample_set(rtggx_context* c, uint32_t size) {
+  RT_CHECK_CTX(c);
+  if (size < RTGGX_MIN_SAMPLE_SET || size > RTGGX_MAX_SAMPLE_SET || (size & (size - 1u)) != 0u) { setError("rtggx_set_sample_set: %u samples: a power of two from %u to %u", size, RTGGX_MIN_SAMPLE_SET, RTGGX_MAX_SAMPLE_SET); return -1; }
+  if (size == c->sampleSetRequested) return 0;
+  RT_HIP(syncStreams(c));
+  if (size > RTGGX_MIN_SAMPLE_SET) { const int r = allocSampleTable(c, size); if (r) return r; }
+  c->sampleSetRequested = size;
   return 0;
 }
 
@@ -803,9 +833,9 @@ int rtggx_update_frame(rtggx_context* c, const RtggxFrameConstants* k) {
   fp.g = k->global; fp.rg = k->rayGen; fp.po[0] = k->perObject[0]; fp.po[1] = k->perObject[1];
   fp.mat = c->material;
   fp.W = c->W; fp.H = c->H; fp.rowBegin = c->rowBegin; fp.rowEnd = c->rowEnd;
-  fp.flags = c->vndf ? RT_FLAG_VNDF : 0u; fp.pad[0] = fp.pad[1] = fp.pad[2] = 0u;
+  fp.flags = c->vndf ? RT_FLAG_VNDF : 0u; fp.sampleMask = c->sampleSet - 1u; fp.pad[0] = fp.pad[1] = 0u;      // (the mask: once more in rtggx_render_visibility, where a new set size takes over)
   memcpy(fp.invWorld, c->invWorld, sizeof fp.invWorld);
-  c->haveConstants = true; c->slotUploaded = false;
+  c->haveConstants = true; c->slotUploaded = false; c->slotRendered = false;
   return 0;
 }
 
@@ -911,6 +941,15 @@ int rtggx_render_visibility(rtggx_context* c) {
   settleSetRead(c);      // (the previous frame ended without the kernel that would have carried its set's event)
   ++c->frameCounter;
   c->maxDepth = c->depthRequested; c->samples = c->samplesRequested; c->accumulate = c->accumulateRequested;
+  bool resendConstants = false;
+  if (c->sampleSet != c->sampleSetRequested) {      // rtggx_set_sample_set: the kernels' variant, the table and the constants' mask change together
+    // several frames from one rtggx_update_frame share the slot's device copy: the frame before may still read the mask that goes with ITS
+    // table (a larger mask on a smaller table would read beyond it) -- wait for it.  One update per frame, the normal order, never waits.
+    if (c->slotRendered) RT_HIP(syncStreams(c));
+    c->sampleSet = c->sampleSetRequested;
+    c->slots[c->slot].sampleMask = c->sampleSet - 1u;
+    resendConstants = c->slotUploaded;      // constants already on their way (timing mode) go again behind this pass, as after a late rtggx_update_as
+  }
   c->denoiseIssued = false; c->toneMapDone = false;
   c->selectSet(c->setAhead(1u));
   // the set was last read four frames ago: normally long done; a host that has run further ahead than that waits here (also what makes
@@ -933,6 +972,8 @@ int rtggx_render_visibility(rtggx_context* c) {
   if (c->refitIssued && c->asyncCompute && s != c->streamRefit) RT_HIP(hipStreamWaitEvent(s, c->evRefit, 0));       // the rasteriser reads this set's vertices (on R it follows the refit anyway)
   if (c->timing) hipEventRecord(c->tev[2], s);
   int r = launchVisibility(c, c->slots[c->slot], s, c->streamVis ? c->evVis : nullptr);
+  c->slotRendered = true;
+  if (resendConstants) c->slotUploaded = false;      // (rtggx_ray_trace's ensureParams; nothing in front of it reads the mask)
   if (c->streamVis) c->evVisStream = s;
   if (c->timing) hipEventRecord(c->tev[13], s);
   if (!r) r = issueRebuildSteps(c);

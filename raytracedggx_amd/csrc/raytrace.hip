@@ -288,6 +288,17 @@ struct GenArgs {
   uint32_t* binWork; uint32_t* splitList; uint32_t* splitCount; uint32_t splitWork, frontWork, splitMaxShift, splitCap;
 };
 
+// Sample-set size M > 256 (rtggx_set_sample_set; DESIGN.md "Sample-set size"): getSampleParam with numSamples = M.  The slot is the low bits
+// of the same word (M is a power of two: % M), xi.y the same hash of the slot, and the table -- handed over in the kernels' cosSin pointer --
+// holds M interleaved {cos, sin} pairs: one 8-byte load per lane (two 4-byte loads half a table apart would each take a cache line of
+// their own per lane at 65536 entries).  The mask is the frame constants' (uniform): every sample's copy carries it (sampleParamsKernel).
+// WIDE = false is the code of the 256-member set as it was, the kernels' bodies unchanged (profiles/r10_a_sampleset_isa.txt).
+RT_DEV void sampleParamWide(const FrameParams& fp, const float* table, uint32_t pixel, float& xiY, float& cosPhi, float& sinPhi) {
+  uint32_t s = rng(pixel); s += fp.g.FrameIndex; s = rng(s); s &= fp.sampleMask;
+  xiY = (float)(rng(s) & 0xffffu) / 65536.0f;
+  const float2 cs = reinterpret_cast<const float2*>(table)[s];
+  cosPhi = cs.x; sinPhi = cs.y;
+}
 #ifndef RT_GEN_MIN_BLOCKS
 #define RT_GEN_MIN_BLOCKS 1
 #endif
@@ -338,7 +349,7 @@ RT_DEV void rayGenQuadBin(const GenArgs& A, bool wantRefl, bool wantDiff, const 
 // RATE 4: one pixel per quad traces, and the workgroup's (at most 64 + 64) rays go to ONE bin, compacted over its four waves through LDS,
 // so that the traversal's waves stay as full as at rate 1.  Workgroup b <-> bin b; four consecutive bins are the four 16x16 tiles of a
 // 32x32 tile (launchTrace gets the 32x32 grid).  A bin whose 16x16 tile lies outside the frame is written empty.
-template <int RATE>
+template <int RATE, bool WIDE = false>
 __global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) rayGenKernel(const FrameParams* __restrict__ fpp, GenArgs A) {
   const FrameParams& fp = *fpp;
   if (blockIdx.x == 0) A.frameRays[threadIdx.x] = 0u;
@@ -388,7 +399,8 @@ __global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) rayGenKernel(const Fra
     // getSampleParam :394-406 -- of every pixel of a tile with something in it, before the visibility word is back: the table fetch then
     // travels beside that word instead of behind the triangle's
     float xiY = 0.0f, cosPhi = 0.0f, sinPhi = 0.0f;
-    if (drawn) {
+    if constexpr (WIDE) { if (drawn) sampleParamWide(fp, A.cosSin, py * W + px, xiY, cosPhi, sinPhi); }
+    else if (drawn) {
       uint32_t s = py * W + px;
       s = rng(s); s += fp.g.FrameIndex; s = rng(s); s %= 256u;
       xiY = (float)(rng(s) & 0xffffu) / 65536.0f;
@@ -597,7 +609,7 @@ RT_DEV uint32_t quadTileWord(const uint32_t* words, uint32_t tile32, uint32_t ti
                : "s"(words), "s"(RT_SGPR(i0 * 4u)), "s"(RT_SGPR(i1 * 4u)), "s"(RT_SGPR(i2 * 4u)), "s"(RT_SGPR(i3 * 4u)) : "memory");
   return a | b | c | d;
 }
-template <int RATE, int PASS>
+template <int RATE, int PASS, bool WIDE = false>
 __global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) shadeKernel(const FrameParams* __restrict__ fpp, ShadeArgs A) {
   const FrameParams& fp = *fpp;
   const EnvRef env{A.env, A.envSize, A.envMips, A.envMipOffset};
@@ -674,8 +686,12 @@ __global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) shadeKernel(const Fram
           // the closest-hit shaders at depth d + 1 < D (:571-614): hitWorldPosition (:338-341), getSampleParam(DispatchRaysIndex()) -- the
           // pixel's xi at every level --, then computeReflection / computeDiffuse up to their TraceRay
           const f3 P = mk3(ra.x + ht * rb.x, ra.y + ht * rb.y, ra.z + ht * rb.z);
-          uint32_t s = rng(rc.x); s += fp.g.FrameIndex; s = rng(s); s %= 256u;
-          const float xiY = (float)(rng(s) & 0xffffu) / 65536.0f, cosPhi = A.cosSin[s], sinPhi = A.cosSin[256 + s];
+          float xiY, cosPhi, sinPhi;
+          if constexpr (WIDE) sampleParamWide(fp, A.cosSin, rc.x, xiY, cosPhi, sinPhi);
+          else {
+            uint32_t s = rng(rc.x); s += fp.g.FrameIndex; s = rng(s); s %= 256u;
+            xiY = (float)(rng(s) & 0xffffu) / 65536.0f; cosPhi = A.cosSin[s]; sinPhi = A.cosSin[256 + s];
+          }
           const uint32_t toDiffImage = (rc.z ^ (rc.z >> 1)) & 1u;
           f3 w, L;
           if (rm.y > 0.5f) {
@@ -839,6 +855,7 @@ struct SampleGenArgs {
   RayRec* rays; HitKey* hits; uint32_t* binCount; uint32_t binSlots;
   const uint32_t* tileWords; uint32_t tilesX, rowBegin, rowEnd;
 };
+template <bool WIDE>
 __global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) sampleGenKernel(const FrameParams* __restrict__ fpp, SampleGenArgs A) {
   const FrameParams& fp = *fpp;
   const uint32_t tile = blockIdx.x;
@@ -854,9 +871,13 @@ __global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) sampleGenKernel(const 
     const uint32_t W = fp.W, H = fp.H;
     const size_t pix = (size_t)py * W + px;
     uint32_t visibility = (uint32_t)A.visDepth[pix];
-    uint32_t s = py * W + px;      // getSampleParam :394-406
-    s = rng(s); s += fp.g.FrameIndex; s = rng(s); s %= 256u;
-    const float xiY = (float)(rng(s) & 0xffffu) / 65536.0f, cosPhi = A.cosSin[s], sinPhi = A.cosSin[256 + s];
+    float xiY, cosPhi, sinPhi;      // getSampleParam :394-406
+    if constexpr (WIDE) sampleParamWide(fp, A.cosSin, py * W + px, xiY, cosPhi, sinPhi);
+    else {
+      uint32_t s = py * W + px;
+      s = rng(s); s += fp.g.FrameIndex; s = rng(s); s %= 256u;
+      xiY = (float)(rng(s) & 0xffffu) / 65536.0f; cosPhi = A.cosSin[s]; sinPhi = A.cosSin[256 + s];
+    }
     if (visibility > 0) {      // getPrimarySurface :277-333, the covered branch
       --visibility;
       const uint32_t inst = visibility >> 24;
@@ -1007,7 +1028,7 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
   G.roughMetalPrev = c->prev().roughMetal;
   G.diffPrev = c->genCarriesDiff ? c->prev().rtDiff : nullptr;
   G.fat0 = c->mesh[0].fat; G.fat1 = c->mesh[1].fat;
-  G.env = c->env.texels; G.envMipOffset = c->dEnvMipOffset; G.envSize = c->env.size; G.envMips = c->env.mips; G.cosSin = c->cosSinTab;
+  G.env = c->env.texels; G.envMipOffset = c->dEnvMipOffset; G.envSize = c->env.size; G.envMips = c->env.mips; G.cosSin = c->sampleTable();
   G.rays = (RayRec*)set.rayQueue; G.hits = (HitKey*)set.hitQueue; G.binCount = set.binCount; G.binSlots = c->binSlots; G.frameRays = c->rayCounter32;
   G.tilesX = tilesX; G.numTiles = tilesX * tilesY; G.rowBegin = rb; G.rowEnd = re;
   const uint32_t splitWork = c->splitWork, splitMaxShift = c->splitMaxShift;
@@ -1040,7 +1061,8 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
     hipLaunchKernelGGL(sampleParamsKernel, dim3(1), dim3(256), 0, sGen, genParams, sp, c->samples);
     genParams = sp;
   }
-  launch(quad ? rayGenKernel<4> : rayGenKernel<1>, dim3(quad ? numBins : G.numTiles), dim3(256), sGen, nullptr, sGen != s ? ev.gen : nullptr, genParams, G);
+  const bool wide = c->sampleSet > RTGGX_MIN_SAMPLE_SET;      // rtggx_set_sample_set: the kernels that take a sample in their set-size-aware variant
+  launch(wide ? (quad ? rayGenKernel<4, true> : rayGenKernel<1, true>) : quad ? rayGenKernel<4> : rayGenKernel<1>, dim3(quad ? numBins : G.numTiles), dim3(256), sGen, nullptr, sGen != s ? ev.gen : nullptr, genParams, G);
   ev.genFrame = 0u; ev.genStream = sGen;
   if (sGen != s) {
     RT_HIP(hipStreamWaitEvent(s, ev.gen, 0));
@@ -1065,6 +1087,7 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
 static void (*const kShade[3][2])(const FrameParams*, ShadeArgs) = {      // [ShadePass][rate 4]
     {shadeKernel<1, SHADE_FINAL>, shadeKernel<4, SHADE_FINAL>}, {shadeKernel<1, SHADE_SPAWN>, shadeKernel<4, SHADE_SPAWN>},
     {shadeKernel<1, SHADE_FINAL_DEEP>, shadeKernel<4, SHADE_FINAL_DEEP>}};
+static void (*const kShadeSpawnWide[2])(const FrameParams*, ShadeArgs) = {shadeKernel<1, SHADE_SPAWN, true>, shadeKernel<4, SHADE_SPAWN, true>};      // sample-set size > 256
 // N > 1 samples per pixel (rate 1 only), depth D: per sample D shading passes that add to the sums, in front of every sample but the first
 // its rays' generation and their traversal, behind the last one the resolve -- N * D shading passes, N * D - 1 traversals, N - 1 sample
 // generations and the resolve on this stream, the frame's bins reused in place throughout.  Every traversal here is a later level's in launchTrace's terms: a spill part of its
@@ -1072,6 +1095,7 @@ static void (*const kShade[3][2])(const FrameParams*, ShadeArgs) = {      // [Sh
 // `done` rides on the resolve, the last kernel of the frame that reads the bins.
 static int launchShadeSamples(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent_t done, ShadeArgs S, uint32_t numTiles, int spillPart) {
   const uint32_t N = c->samples, depth = c->maxDepth;
+  const bool wide = c->sampleSet > RTGGX_MIN_SAMPLE_SET;
   if (!c->sppAcc || !c->sppParams) { setError("rtggx_ray_trace: %u samples per pixel without their buffers", N); return -1; }
   // the sums exist once: the previous frame's passes may have run on another stream (small launches alternate two; capi.hip rtggx_ray_trace)
   if (c->sppStream && c->sppStream != s) { RT_HIP(hipEventRecord(c->evSpp, c->sppStream)); RT_HIP(hipStreamWaitEvent(s, c->evSpp, 0)); }
@@ -1086,12 +1110,12 @@ static int launchShadeSamples(rtggx_context* c, const FrameParams& fp, hipStream
   const TraceQueue q{S.rays, S.spawnHits, S.binCount};
   for (uint32_t k = 0; k < N; ++k) {
     for (uint32_t level = 0; level < depth; ++level) {
-      if (k > 0 && level == 0) launch(sampleGenKernel, dim3(numTiles), dim3(256), s, nullptr, nullptr, sp + k, G);
+      if (k > 0 && level == 0) launch(wide ? sampleGenKernel<true> : sampleGenKernel<false>, dim3(numTiles), dim3(256), s, nullptr, nullptr, sp + k, G);
       if (k > 0 || level > 0) {
         const int r = launchTrace(c, fp, s, q, c->traceGrid[0], true, c->traceGrid[1], c->traceGrid[2], c->traceGrid[3], -1, nullptr, nullptr, spillPart);
         if (r) return r;
       }
-      launch(level + 1u < depth ? shadeKernel<1, SHADE_SPAWN_ACCUM> : shadeKernel<1, SHADE_ACCUM>, dim3(numTiles), dim3(256), s, nullptr, nullptr, sp + k, S);
+      launch(level + 1u < depth ? (wide ? shadeKernel<1, SHADE_SPAWN_ACCUM, true> : shadeKernel<1, SHADE_SPAWN_ACCUM>) : shadeKernel<1, SHADE_ACCUM>, dim3(numTiles), dim3(256), s, nullptr, nullptr, sp + k, S);
       S.carryMask = 0u;      // (carried over once, by the first pass)
       RT_HIP(hipGetLastError());
     }
@@ -1127,7 +1151,7 @@ int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent
   S.fat0 = c->mesh[0].fat; S.fat1 = c->mesh[1].fat;
   S.env = c->env.texels; S.envMipOffset = c->dEnvMipOffset; S.envSize = c->env.size; S.envMips = c->env.mips; S.sh = c->sh;
   S.reflOut = set.rtRefl; S.diffOut = set.rtDiff;
-  S.spawnRays = (RayRec*)set.rayQueue; S.spawnHits = (HitKey*)set.hitQueue; S.spawnCount = set.binCount; S.cosSin = c->cosSinTab;
+  S.spawnRays = (RayRec*)set.rayQueue; S.spawnHits = (HitKey*)set.hitQueue; S.spawnCount = set.binCount; S.cosSin = c->sampleTable();
   S.accRefl = nullptr; S.accDiff = nullptr;
   const FrameParams* const dfp = c->dParams + c->slot;
   const uint32_t depth = c->maxDepth;
@@ -1143,7 +1167,7 @@ int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent
       S.carryMask = 0u;      // (carried over once, by the first pass)
     }
     const int pass = level + 1u < depth ? SHADE_SPAWN : level == 0 ? SHADE_FINAL : SHADE_FINAL_DEEP;
-    launch(kShade[pass][quad], dim3(grid), dim3(256), s, nullptr, pass == SHADE_SPAWN ? nullptr : done, dfp, S);
+    launch(pass == SHADE_SPAWN && c->sampleSet > RTGGX_MIN_SAMPLE_SET ? kShadeSpawnWide[quad] : kShade[pass][quad], dim3(grid), dim3(256), s, nullptr, pass == SHADE_SPAWN ? nullptr : done, dfp, S);
     RT_HIP(hipGetLastError());
   }
   return 0;

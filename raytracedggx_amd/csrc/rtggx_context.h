@@ -151,7 +151,9 @@ struct FrameParams {
   float invWorld[2][16];         // TLAS: world -> object, row-vector row-major
   uint32_t W, H;
   uint32_t rowBegin, rowEnd;     // strip of the frame this context renders
-  uint32_t flags, pad[3];        // RT_FLAG_*
+  uint32_t flags;                // RT_FLAG_*
+  uint32_t sampleMask;           // rtggx_set_sample_set: M - 1 of the frame's sample set (raytrace.hip sampleParamWide; the 256-member code does not read it)
+  uint32_t pad[2];
 };
 #define RT_FLAG_VNDF 1u          // rtggx_set_sampler: visible-normal sampling of the reflection lobe instead of the reference's NDF sampling
 
@@ -271,6 +273,13 @@ struct rtggx_context {
   rt::EnvDev env;
   float* sh = nullptr;           // 27 floats
   float* cosSinTab = nullptr;    // 512 floats: cos[256], sin[256]
+  // rtggx_set_sample_set (raytrace.hip sampleParamWide; DESIGN.md "Sample-set size"): M of the frame, of the next frame; 256 = the reference's.
+  // One table per size M = 512 << k ever asked for, M {cos, sin} pairs, made by the setter and kept until rtggx_destroy: a frame in flight
+  // and a frame whose visibility pass has run keep the table they were launched with whatever the caller sets next.
+  uint32_t sampleSet = RTGGX_MIN_SAMPLE_SET, sampleSetRequested = RTGGX_MIN_SAMPLE_SET;
+  float* cosSinWide[8] = {};
+  static uint32_t sampleSetSlot(uint32_t m) { uint32_t k = 0; while ((512u << k) < m) ++k; return k; }
+  const float* sampleTable() const { return sampleSet > RTGGX_MIN_SAMPLE_SET ? cosSinWide[sampleSetSlot(sampleSet)] : cosSinTab; }
 
   // render targets
   // Everything the visibility and ray-tracing passes write and the denoiser (main stream) reads exists RT_SETS times (the input sets), so
@@ -368,6 +377,7 @@ struct rtggx_context {
   uint32_t slot = 0;
   rt::FrameParams* dParams = nullptr;   // device ring, 3 slots; kernels read their constants from here
   bool slotUploaded = false;
+  bool slotRendered = false;     // a frame has been rendered from this slot since rtggx_update_frame filled it: its kernels may still read the device copy
   RtggxCBMaterial material;
   float invWorld[2][16];
   bool haveConstants = false, asBuilt = false, shDone = false;

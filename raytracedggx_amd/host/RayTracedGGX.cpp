@@ -35,6 +35,7 @@ void RayTracedGGX::OnInit() {
   if (m_rayRate != 1u && !m_rayTracer->SetRayRate(m_rayRate)) throw std::runtime_error("-rayrate: " + m_rayTracer->GetLastError());      // -rayrate 4: one ray per 2x2 quad (opt-in)
   if (m_recursionDepth != 1u && !m_rayTracer->SetMaxRecursionDepth(m_recursionDepth)) throw std::runtime_error("-recursion: " + m_rayTracer->GetLastError());      // -recursion N: multi-bounce paths (opt-in)
   if (m_samplesPerPixel != 1u && !m_rayTracer->SetSamplesPerPixel(m_samplesPerPixel)) throw std::runtime_error("-spp: " + m_rayTracer->GetLastError());      // -spp N: multi-sample tracing (opt-in)
+  if (m_sampleSet != RTGGX_MIN_SAMPLE_SET && !m_rayTracer->SetSampleSetSize(m_sampleSet)) throw std::runtime_error("-sampleset: " + m_rayTracer->GetLastError());      // -sampleset M: a larger sample set (opt-in)
   m_rayTracer->SetAsyncCompute(m_asyncCompute != 0);   // -sync: one stream, submission order (the sample's single command list)
 
   if (m_deformAmplitude != 0.0f) {       // key shapes of the breathing model: x and z displaced by a wave travelling up the y axis
@@ -197,7 +198,7 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
     return (arg[0] == '-' || arg[0] == '/') && lower(arg + 1) == lower(name);
   };
   // On POSIX an absolute path also starts with '/': such a token is a flag only when it names one.
-  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "recursion", "spp", "accumulate"};
+  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "recursion", "spp", "accumulate", "sampleset"};
   const auto isFlagName = [&](const char* name) { for (const char* f : kFlags) if (lower(name) == f) return true; return false; };
   const auto hasNextArgValue = [&](int i) {
     if (i + 1 >= argc) return false;
@@ -235,6 +236,11 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
       const int samples = hasNextArgValue(i) ? std::atoi(argv[++i]) : 0;
       if (samples != 1 && samples != 2 && samples != 4 && samples != 8) throw std::runtime_error("-spp: 1, 2, 4 or 8 samples per pixel");
       m_samplesPerPixel = (uint32_t)samples;
+    }
+    else if (isArgMatched(i, "sampleset")) {
+      const long size = hasNextArgValue(i) ? std::atol(argv[++i]) : 0;
+      if (size < (long)RTGGX_MIN_SAMPLE_SET || size > (long)RTGGX_MAX_SAMPLE_SET || (size & (size - 1)) != 0) throw std::runtime_error("-sampleset: a power of two from 256 to 65536");
+      m_sampleSet = (uint32_t)size;
     }
     else if (isArgMatched(i, "accumulate")) {
       const int frames = hasNextArgValue(i) ? std::atoi(argv[++i]) : 0;
@@ -325,6 +331,18 @@ static double meanRelativeStdError(const std::vector<float>& sums, const std::ve
   return counted ? total / (double)counted : -1.0;
 }
 
+// What the -accumulate line says about the sample set.  FrameIndex counts modulo M (RayTracer::UpdateFrame), and frame F at N samples takes
+// the indices F N .. F N + N - 1: the still camera's frames repeat after M FRAMES whatever N is -- M N samples --, so the warning is for
+// n > M frames.
+std::string AccumulationSampleSetNote(uint32_t frames, uint32_t samplesPerPixel, uint32_t sampleSet) {
+  char text[256];
+  int len = std::snprintf(text, sizeof text, "; sample set of %u", sampleSet);
+  if (frames > sampleSet)
+    std::snprintf(text + len, sizeof text - (size_t)len, "\nwarning: %u frames of %u samples from a set of %u: the frames repeat after %u (%llu samples), -sampleset M up to %u extends it",
+                  frames, samplesPerPixel, sampleSet, sampleSet, (unsigned long long)sampleSet * samplesPerPixel, RTGGX_MAX_SAMPLE_SET);
+  return text;
+}
+
 bool RayTracedGGX::SaveConverged(const char* fileName) {
   rtggx_context* ctx = GetContext();
   if (!ctx) return false;
@@ -338,6 +356,7 @@ bool RayTracedGGX::SaveConverged(const char* fileName) {
   const double eR = meanRelativeStdError(refl, vis, n), eD = meanRelativeStdError(diff, vis, n);
   std::printf("accumulated %u frames: mean relative standard error of Y over covered pixels, reflection %.5f", n, eR);
   if (eD >= 0.0) std::printf(", diffuse %.5f", eD);
+  std::printf("%s", AccumulationSampleSetNote(n, m_samplesPerPixel, m_rayTracer->GetSampleSetSize()).c_str());
   std::printf("\nwrote %s\n", fileName);
   std::fflush(stdout);
   return true;

@@ -2,7 +2,7 @@
 // DXFramework virtuals RayTracedGGX/Common/DXFramework.h:23-26): OnInit / OnUpdate / OnRender /
 // OnDestroy, the same command line (RayTracedGGX.cpp:462-511) and the same defaults
 // (RayTracedGGX.cpp:37-39, camera :19-23, 267-277).  What the window supplied interactively is
-// supplied by extra flags: -width -height -frames -dt -metallic -sharedmem -sync -vndf -rayrate -recursion -spp -accumulate -device -dump -track -deform -gpus -strips -balance.
+// supplied by extra flags: -width -height -frames -dt -metallic -sharedmem -sync -vndf -rayrate -recursion -spp -sampleset -accumulate -device -dump -track -deform -gpus -strips -balance.
 #pragma once
 #include <vector>
 #include <cstdint>
@@ -13,6 +13,9 @@
 #include "XMath.h"
 
 bool WritePng(const char* fileName, uint32_t w, uint32_t h, uint32_t comp, const uint8_t* pixels);   // comp 3 (RGB) or 4 (RGBA), 8 bits
+
+// the tail of the line -accumulate prints: "; sample set of M", and a warning once more than M frames were accumulated (they repeat)
+std::string AccumulationSampleSetNote(uint32_t frames, uint32_t samplesPerPixel, uint32_t sampleSet);
 
 class RayTracedGGX {
  public:
@@ -105,6 +108,7 @@ class RayTracedGGX {
   bool m_vndf = false;                 // -vndf
   uint32_t m_recursionDepth = 1;       // -recursion <1..4>: levels of rays per path (RayTracer::SetMaxRecursionDepth)
   uint32_t m_samplesPerPixel = 1;      // -spp <1|2|4|8>: samples per covered pixel (RayTracer::SetSamplesPerPixel); not together with -rayrate 4
+  uint32_t m_sampleSet = RTGGX_MIN_SAMPLE_SET;      // -sampleset <256..65536, a power of two>: the size of the sample set (RayTracer::SetSampleSetSize); every rank of -gpus / -strips gets it
   uint32_t m_accumulate = 0;           // -accumulate <N>: accumulation on for the last N frames of the run (all of them when N >= -frames); not with -rayrate 4, -gpus, -strips
   uint32_t m_rayRate = 1;              // -rayrate <1|4>: pixels per traced ray (RayTracer::SetRayRate); 4 renders whole frames only: not with -gpus / -strips
   // -deform <amplitude>: the model breathes -- a travelling sine wave through its vertices, DeformPeriod key shapes computed once

@@ -72,6 +72,15 @@ bool RayTracer::SetRayRate(uint32_t pixelsPerRay) { return check(rtggx_set_ray_r
 bool RayTracer::SetSamplesPerPixel(uint32_t samples) { return check(rtggx_set_samples_per_pixel(m_ctx, samples), "rtggx_set_samples_per_pixel"); }
 bool RayTracer::SetMaxRecursionDepth(uint32_t depth) { return check(rtggx_set_max_recursion_depth(m_ctx, depth), "rtggx_set_max_recursion_depth"); }
 
+bool RayTracer::SetSampleSetSize(uint32_t size) {
+  // (without a context -- constants only -- the rule is rtggx_set_sample_set's own)
+  if (!m_ctx && (size < RTGGX_MIN_SAMPLE_SET || size > RTGGX_MAX_SAMPLE_SET || (size & (size - 1u)) != 0u)) { m_error = "SetSampleSetSize: a power of two from 256 to 65536"; return false; }
+  if (m_ctx && !check(rtggx_set_sample_set(m_ctx, size), "rtggx_set_sample_set")) return false;
+  m_sampleSet = size;      // UpdateFrame counts modulo it from here on
+  m_frameCounter %= m_sampleSet;
+  return true;
+}
+
 bool RayTracer::SetAccumulation(bool enable) { return check(rtggx_set_accumulation(m_ctx, enable ? 1 : 0), "rtggx_set_accumulation"); }
 bool RayTracer::ResetAccumulation() { return check(rtggx_reset_accumulation(m_ctx), "rtggx_reset_accumulation"); }
 
@@ -114,7 +123,7 @@ void RayTracer::UpdateFrame(uint8_t frameIndex, const xm::Float3& eyePt, const x
     StoreFloat3x4(cb.global.WorldIT1, rot, 11);
     m_hasPrev = true;
     cb.global.FrameIndex = m_frameCounter++;
-    m_frameCounter %= 256u;
+    m_frameCounter %= m_sampleSet;      // n = 256 beside s_frameIndex (RayTracer.cpp:282), a setting here: the size of the sample set
   }
   std::memset(&cb.material, 0, sizeof cb.material);   // CBMaterial is persistent on the device (rtggx_set_material)
   if (m_ctx) check(rtggx_update_frame(m_ctx, &cb), "rtggx_update_frame");

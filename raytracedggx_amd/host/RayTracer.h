@@ -43,6 +43,10 @@ class RayTracer {
   bool SetRayRate(uint32_t pixelsPerRay);
   bool SetSamplesPerPixel(uint32_t samples);   // rtggx_set_samples_per_pixel: 1 (default), 2, 4 or 8 samples per covered pixel (-spp); not together with ray rate 4
   bool SetMaxRecursionDepth(uint32_t depth);   // rtggx_set_max_recursion_depth: 1 (default; RayTracer.cpp:605 SetMaxRecursionDepth(1)) to 4 levels of rays per path (-recursion)   // rtggx_set_ray_rate: 1 (default) or 4 -- one pixel of each 2x2 quad traced per frame, the rest reconstructed (-rayrate)
+  // rtggx_set_sample_set: the size of the sample set getSampleParam draws from, 256 (default, the reference's) or a power of two up to
+  // 65536 (-sampleset); UpdateFrame's frame index counts modulo it.  A refused size leaves both as they were.
+  bool SetSampleSetSize(uint32_t size);
+  uint32_t GetSampleSetSize() const { return m_sampleSet; }
   // rtggx_set_accumulation / rtggx_reset_accumulation: the running sums of the raw traced images, on from the next frame (-accumulate);
   // not together with ray rate 4.  A moving camera or a changed material is the caller's to reset.
   bool SetAccumulation(bool enable);
@@ -77,6 +81,7 @@ class RayTracer {
   HaltonSequence m_halton;
   float m_angle = 0.0f;            // RayTracer.cpp:270
   uint32_t m_frameCounter = 0;     // s_frameIndex, RayTracer.cpp:282
+  uint32_t m_sampleSet = RTGGX_MIN_SAMPLE_SET;      // const auto n = 256u beside it
   bool m_hasPrev = false;
   float m_worldViewProjs[NUM_MESH][16];   // RayTracer.h:131
   RtggxFrameConstants m_constants{};

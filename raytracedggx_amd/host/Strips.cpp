@@ -340,7 +340,7 @@ int RunStripsInOneProcess(RayTracedGGX& first, int world, bool balance, int argc
   std::vector<RayTracedGGX*> apps{&first};
   for (int r = 1; r < world; ++r) {
     owned.emplace_back(new RayTracedGGX(first.GetWidth(), first.GetHeight(), "strip"));
-    owned.back()->ParseCommandLineArgs(argv, argc);
+    owned.back()->ParseCommandLineArgs(argv, argc);      // every strip its own parse of the one command line: the same -sampleset, -spp, -recursion, ... (LaunchRanks: the same argv per rank)
     apps.push_back(owned.back().get());
   }
   for (RayTracedGGX* a : apps) a->OnInit();

@@ -92,6 +92,25 @@ extern "C" void rtggx_host_frame_constants(uint32_t width, uint32_t height, cons
   }
 }
 
+// RayTracer::SetSampleSetSize and the frame counter behind it (no device): the FrameIndex of `frames` consecutive UpdateFrame calls after
+// SetSampleSetSize(size); returns the size the RayTracer then holds (a refused size leaves 256).
+extern "C" uint32_t rtggx_host_frame_indices(uint32_t size, uint32_t frames, uint32_t* out) {
+  ConstantsOnlyRayTracer rt; const float ps[4] = {0.0f, 0.0f, 0.0f, 1.0f}; rt.Setup(64, 36, ps);
+  rt.SetSampleSetSize(size);
+  const xm::Float3 eye{10.0f, 10.0f, -24.0f};
+  const xm::Matrix viewProj = xm::LookAtLH(eye, xm::Float3{0.0f, 3.0f, 0.0f}, xm::Float3{0.0f, 1.0f, 0.0f}) * xm::PerspectiveFovLH(0.785398163f, 64.0f / 36.0f, 1.0f, 1000.0f);
+  for (uint32_t f = 0; f < frames; ++f) { rt.UpdateFrame((uint8_t)(f % 3), eye, viewProj, 0.0f); out[f] = rt.GetFrameConstants().global.FrameIndex; }
+  return rt.GetSampleSetSize();
+}
+
+// The tail of the -accumulate line (AccumulationSampleSetNote) for `frames` accumulated frames of `samples` samples from a set of `sampleSet`.
+extern "C" int rtggx_host_accumulation_note(uint32_t frames, uint32_t samples, uint32_t sampleSet, char* out, int capacity) {
+  const std::string s = AccumulationSampleSetNote(frames, samples, sampleSet);
+  if ((int)s.size() + 1 > capacity) return -1;
+  std::memcpy(out, s.c_str(), s.size() + 1);
+  return (int)s.size();
+}
+
 // The multi-GPU host's plan functions (host/Strips.cpp), for the tests that compare them with raytracedggx_amd/strips.py.
 // bounds: nullptr / 0 for equal strips, else world + 1 row numbers.  ops: 5 int32 per transfer (send, buffer: 1 history / 0 back buffer / 2 token, rowBegin, rowEnd, peer);
 // returns the number of transfers, or -1 with rtggx_app_last_error set.

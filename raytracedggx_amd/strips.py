@@ -149,7 +149,9 @@ class StripRenderer:
         connected by connect_peers(all_of_them) once they exist.
         apron: history rows exchanged beyond each strip edge (HISTORY_APRON = 18 covers 16 px of vertical reprojection per
         frame).  A faster motion -- an orbit drag of a -track script -- makes the strips differ from the single-GPU frame:
-        the temporal pass detects that (history_overreach() > 0), and a wider apron, the same on every rank, is the remedy."""
+        the temporal pass detects that (history_overreach() > 0), and a wider apron, the same on every rank, is the remedy.
+        extra_args: further flags of the executable for this rank's context, the same on every rank -- among them -sampleset M
+        (rtggx_set_sample_set): a strip's pixels draw the samples the whole frame's draw only under one M."""
         self.W, self.H, self.rank, self.world, self.dist, self.transport = width, height, rank, world, dist, transport
         self.apron = int(apron)
         self.peers = bool(peers) and world > 1

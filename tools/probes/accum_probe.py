@@ -2,7 +2,7 @@
 3840x2160, the default metallic (1 1) and 0.25 0.5: free-running frames after a warm-up, both settings alive in the same process and
 measured in alternation, `--rounds` times, as tools/probes/ray_rate_probe.py does.  Prints one JSON line per (workload, setting, round):
 ms/frame and, for the accumulating context, the frames it has accumulated.
-    python tools/probes/accum_probe.py [--frames 256] [--warmup 64] [--rounds 3] [--only bunny-1080] [--settings off on]
+    python tools/probes/accum_probe.py [--frames 256] [--warmup 64] [--rounds 3] [--only bunny-1080] [--settings off on] [--sampleset 256]
 With --settings on and --rounds 1 it is the workload of a `rocprofv3 --kernel-trace --stats` run (accumulateKernel's own time)."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -24,6 +24,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--settings", nargs="+", default=["off", "on"], choices=["off", "on"])
     ap.add_argument("--only", nargs="*", default=None, help="workload names (bunny-1080, bunny-2160-m0.25-0.5, ...)")
+    ap.add_argument("--sampleset", type=int, default=256, help="-sampleset M of every context (rtggx_set_sample_set)")
     a = ap.parse_args()
     for m, w, h, met in WORKLOADS:
         label = name(m, w, h, met)
@@ -34,6 +35,8 @@ def main():
             args = ["-mesh", assets.path(m + ".obj"), "-env", assets.path("rnl_cross.dds"), "-width", w, "-height", h]
             if met is not None:
                 args += ["-metallic", met[0], met[1]]
+            if a.sampleset != 256:
+                args += ["-sampleset", a.sampleset]
             apps[s] = app.RayTracedGGX(args)
             apps[s].context.set_accumulation(s == "on")
         for x in apps.values():
@@ -52,7 +55,7 @@ def main():
                 c.sync()
                 dt = time.perf_counter() - t0
                 print(json.dumps({"workload": label, "accumulate": s, "round": rnd, "frames": a.frames, "ms_per_frame": round(dt / a.frames * 1e3, 4),
-                                  "accumulated_frames": c.accumulated_frames()}), flush=True)
+                                  "sample_set": a.sampleset, "accumulated_frames": c.accumulated_frames()}), flush=True)
         for x in apps.values():
             x.OnDestroy()
 

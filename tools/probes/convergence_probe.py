@@ -3,8 +3,10 @@
 presented (RTGGX_BUF_CONVERGED), at recursion depth 1 and, for the depth-2 row, at depth 2.  Then 32 frames of each of rate 1 with the NDF
 sampler, rate 1 with the VNDF sampler, rate 4, -spp 2 / 4 / 8 and rate 1 at depth 2: the relative L2 distance of TemporalSSOut's rgb (what
 the denoiser shows) and of the last frame's raw image (RayTracingOut0 + RayTracingOut1 where a diffuse path wrote it) from the reference.
-One JSON line per row.
-    python tools/probes/convergence_probe.py [--frames 32] [--reference-frames 256] [--metallic 0.25 0.5] [--out rows.jsonl]"""
+One JSON line per row.  --sampleset M (rtggx_set_sample_set; DESIGN.md "Sample-set size") gives the reference a sample set of M members:
+at the default 256 its -spp 8 x 256 frames are 2048 draws from the same 256 points, with M = 65536 and --reference-frames 4096 it is the
+ground truth the section asks for.  --rows-sampleset M gives the rows' contexts a set of their own (default: 256, the renderer as shipped).
+    python tools/probes/convergence_probe.py [--frames 32] [--reference-frames 256] [--sampleset 256] [--rows-sampleset 256] [--metallic 0.25 0.5] [--out rows.jsonl]"""
 import argparse, json, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -38,12 +40,14 @@ def main():
     ap.add_argument("--frames", type=int, default=32)
     ap.add_argument("--reference-frames", type=int, default=256)
     ap.add_argument("--metallic", type=float, nargs=2, default=None)
+    ap.add_argument("--sampleset", type=int, default=256, help="-sampleset M of the reference")
+    ap.add_argument("--rows-sampleset", type=int, default=256, help="-sampleset M of the rows")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     met = tuple(a.metallic) if a.metallic else (1.0, 1.0)
     reference = {}
     for depth in sorted({d for _, d, _ in ROWS}):
-        x = make(["-spp", 8, "-recursion", depth], a.metallic)
+        x = make(["-spp", 8, "-recursion", depth] + (["-sampleset", a.sampleset] if a.sampleset != 256 else []), a.metallic)
         x.context.set_accumulation(True)
         for _ in range(a.reference_frames):
             x.OnUpdate(); x.OnRender()
@@ -53,7 +57,7 @@ def main():
         x.OnDestroy()
     out = open(a.out, "w") if a.out else None
     for label, depth, extra in ROWS:
-        x = make(extra, a.metallic)
+        x = make(extra + (["-sampleset", a.rows_sampleset] if a.rows_sampleset != 256 else []), a.metallic)
         c = x.context
         for _ in range(a.frames):
             x.OnUpdate(); x.OnRender()
@@ -61,7 +65,7 @@ def main():
         raw = AR.unpack_r11g11b10f(c.readback(capi.BUF_RT_REFL)).astype(np.float64)
         mask = AR.diffuse_mask(c.readback(capi.BUF_VISIBILITY), met)
         raw += np.where(mask[..., None], AR.unpack_r11g11b10f(c.readback(capi.BUF_RT_DIFF)).astype(np.float64), 0.0)
-        row = {"estimator": label, "depth": depth, "frames": a.frames, "reference": "spp8 x %d frames, depth %d" % (a.reference_frames, depth),
+        row = {"estimator": label, "depth": depth, "frames": a.frames, "reference": "spp8 x %d frames, depth %d, sample set %d" % (a.reference_frames, depth, a.sampleset), "sample_set": a.rows_sampleset,
                "metallic": list(met), "rel_l2_temporal_ss_out": round(rel_l2(tss, reference[depth]), 5), "rel_l2_raw_frame": round(rel_l2(raw, reference[depth]), 5)}
         line = json.dumps(row)
         print(line, flush=True)

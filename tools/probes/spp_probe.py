@@ -2,7 +2,7 @@
 1920x1080 and 3840x2160, the default metallic (1 1: reflection paths only) and 0.25 0.5 (a diffuse path per pixel as well): free-running
 frames after a warm-up, every setting alive in the same process and measured in alternation, `--rounds` times.  Prints one JSON line per
 (workload, N, round): ms/frame, rays per frame (all samples), rays per sample, Mrays/s, and the placement key of the last frame.
-    python tools/probes/spp_probe.py [--frames 256] [--warmup 64] [--rounds 3] [--only bunny-1080] [--samples 1 2 4 8] [--force-small -1|0|1]
+    python tools/probes/spp_probe.py [--frames 256] [--warmup 64] [--rounds 3] [--only bunny-1080] [--samples 1 2 4 8] [--force-small -1|0|1] [--sampleset 256]
 With --samples N and --rounds 1 it is the workload of a `rocprofv3 --kernel-trace --stats` run of one setting."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -25,6 +25,7 @@ def main():
     ap.add_argument("--samples", type=int, nargs="+", default=[1, 2, 4, 8])
     ap.add_argument("--only", nargs="*", default=None, help="workload names (bunny-1080, dragon-2160-m0.25-0.5, ...)")
     ap.add_argument("--force-small", type=int, default=-1, help="rtggx_debug_placement: -1 by the ray count, 0 / 1 the full-size / small-launch placement")
+    ap.add_argument("--sampleset", type=int, default=256, help="-sampleset M of every context (rtggx_set_sample_set)")
     a = ap.parse_args()
     for m, w, h, met in WORKLOADS:
         label = name(m, w, h, met)
@@ -35,6 +36,8 @@ def main():
             args = ["-mesh", assets.path(m + ".obj"), "-env", assets.path("rnl_cross.dds"), "-width", w, "-height", h, "-spp", n]
             if met is not None:
                 args += ["-metallic", met[0], met[1]]
+            if a.sampleset != 256:
+                args += ["-sampleset", a.sampleset]
             apps[n] = app.RayTracedGGX(args)
             apps[n].context.placement(a.force_small)
         for x in apps.values():
@@ -56,7 +59,7 @@ def main():
                 key, where = c.placement(a.force_small)
                 print(json.dumps({"workload": label, "samples": n, "round": rnd, "frames": a.frames, "ms_per_frame": round(dt / a.frames * 1e3, 4),
                                   "rays_per_frame": rays // a.frames, "rays_per_sample": rays // a.frames // n, "mrays_per_s": round(rays / dt / 1e6, 1), "small": key["small"],
-                                  "force_small": a.force_small}), flush=True)
+                                  "force_small": a.force_small, "sample_set": a.sampleset}), flush=True)
         for x in apps.values():
             x.OnDestroy()
 
