@@ -9,10 +9,11 @@
 // so equal depth keeps the fragment drawn first (lower instance, then lower primitive), exactly
 // what LESS does for two ordered draws.  The cleared key is (0xFFFFFF << 32) | 0.
 //
-// Two kernels: rasterSmall -- one lane per triangle, walks its own bounding box when it covers
-// <= 256 pixels (almost every model triangle), otherwise appends a setup record to a queue;
-// rasterLarge -- one 64x4 pixel tile per workgroup, one pixel per lane, loops over the queued
-// large triangles (the ground slab's faces) and merges with a plain read-min-write.
+// Two kernels: rasterSmall -- one lane per triangle for the set-up; a bounding box of <= RT_SMALL_BOX
+// = 1024 candidate pixels (almost every model triangle) is walked by the lanes of the wave together,
+// a larger one (and every clipped triangle) appends a set-up record to a queue; rasterLarge -- one
+// 64x16 pixel block per workgroup, four pixels per lane (rows y, y + 4, y + 8, y + 12), loops over the
+// queued large triangles (the ground slab's faces) and merges with a plain read-min-write.
 // Roofline: HBM; algorithmic bytes 8 B/pixel (clear) + 8 B/covered fragment.
 #include "rtggx_context.h"
 #include "rt_raster.h"
@@ -129,7 +130,7 @@ __global__ void clearVisDepth(unsigned long long* __restrict__ vd, uint32_t begi
 #define RT_SMALL_BOX 1024
 struct __attribute__((aligned(16))) TriSetup {
   int32_t X[3], Y[3]; float z[3]; uint32_t word;
-  int32_t px0, py0; uint32_t bwTl /* box width | top-left flags << 16 */, magic /* ceil(2^24 / box width) */;
+  int32_t px0, py0; uint32_t bwTl /* box width | top-left flags << 16 */, magic /* ceil(2^20 / box width) */;
   double invA;
 };
 // The pass's first kernel also carries the frame's constants to the device: `fp` arrives by value (912 bytes of kernel argument, read
@@ -204,7 +205,7 @@ __global__ void __launch_bounds__(256) rasterSmall(const FrameParams fp, FramePa
         ts.word = word; ts.px0 = (int32_t)px0; ts.py0 = (int32_t)py0;
         const uint32_t bw = (uint32_t)(px1 - px0 + 1);
         ts.bwTl = bw | (tl0 ? 1u << 16 : 0u) | (tl1 ? 1u << 17 : 0u) | (tl2 ? 1u << 18 : 0u);
-        ts.magic = ((1u << 24) + bw - 1u) / bw;
+        ts.magic = ((1u << 20) + bw - 1u) / bw;
         ts.invA = invA;
         setup[lane] = ts;
         cnt = (uint32_t)area;
@@ -239,7 +240,9 @@ __global__ void __launch_bounds__(256) rasterSmall(const FrameParams fp, FramePa
     for (uint32_t step = TPW / 2u; step > 0u; step >>= 1) if (prefix[lo + step] <= w) lo += step;
     const TriSetup& S = setup[lo];
     const uint32_t q = w - prefix[lo], bw = S.bwTl & 0xFFFFu;
-    const uint32_t ry = (q * S.magic) >> 24, rx = q - ry * bw;       // q / bw exactly: q < 1024, bw <= 1024
+    // q / bw exactly for q < 1024, bw <= 1024: the multiplier's excess e = magic * bw - 2^20 < bw gives q * e < 2^20, and the product stays
+    // below 2^30
+    const uint32_t ry = (q * S.magic) >> 20, rx = q - ry * bw;
     const int32_t px = S.px0 + (int32_t)rx, py = S.py0 + (int32_t)ry;
     const int32_t X[3] = {S.X[0], S.X[1], S.X[2]}, Y[3] = {S.Y[0], S.Y[1], S.Y[2]};
     const double z0 = (double)S.z[0], dz1 = (double)S.z[1] - z0, dz2 = (double)S.z[2] - z0;
