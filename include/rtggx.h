@@ -305,6 +305,56 @@ int  rtggx_reset_accumulation(rtggx_context* ctx);
 int  rtggx_accumulated_frames(rtggx_context* ctx, uint32_t* frames);
 int  rtggx_present_accumulation(rtggx_context* ctx);
 
+/* Scoring against a reference image (opt-in, no counterpart in the reference; DESIGN.md "Scoring against a reference"): every frame's
+ * distance from a reference image, reduced on the device inside the frame, the records collected by the host whenever it likes.  A
+ * context that never calls any of the four functions below allocates and launches exactly what it always did.
+ *   - rtggx_set_reference: W * H RGBA16F words (`bytes` = W * H * 8, anything else is refused), the layout rtggx_readback of
+ *     RTGGX_BUF_CONVERGED gives; the alpha half is not read.  Synchronises and copies before it returns; may replace a reference in
+ *     mid-run.  (NULL, 0) releases the image and turns scoring off.  The first call allocates 8 bytes per pixel of the full frame;
+ *   - rtggx_reference_from_accumulation: the reference becomes the mean image rtggx_present_accumulation computes -- same arithmetic,
+ *     on the main stream, no wait -- without touching RTGGX_BUF_CONVERGED or the back buffer.  Whole frames and n > 0, as there;
+ *   - rtggx_set_scoring(1) is refused without a reference.  It takes effect from the next rtggx_render_visibility; the first enable
+ *     allocates the ring of RTGGX_SCORE_RING records and the tree's partial sums (about 108 bytes per 1024 pixels of the full frame);
+ *   - while scoring is on, rtggx_denoise ends with two more kernels on the main stream, behind the temporal pass and in front of the tone
+ *     map, which then always runs as a kernel of its own (as in the per-pass timing mode; the images are the same either way).  They
+ *     write one RtggxScore into slot index % RTGGX_SCORE_RING of the ring;
+ *   - rtggx_read_scores waits for the main stream only and copies the unread records, oldest first, up to `capacity`; the rest stay
+ *     unread.  When more than RTGGX_SCORE_RING frames were scored since the last read the oldest are gone: the gap in `index` shows it.
+ * Per pixel of the context's own rows [row_begin, row_end) -- no apron --, every quantity converted to double (exact) and every operation
+ * a double operation rounded on its own (no contraction):
+ *     ref = the reference's rgb;   out = the rgb of TemporalSSOut[parity] of the frame just denoised;
+ *     raw = unpack_r11g11b10(RayTracingOut0) + (diff ? unpack_r11g11b10(RayTracingOut1) : nothing), diff as in rtggx_set_accumulation:
+ *           the pixel is covered (visibility word != 0) and its instance's metallic in that frame's constants is < 1;
+ *     Y(c) = (0.25 c.r + 0.5 c.g) + 0.25 c.b;   E(c) = (c.r c.r + c.g c.g) + c.b c.b;
+ *     se_out_rgb += E(out - ref), se_out_luma += (Y(out) - Y(ref))^2, ref_rgb2 += E(ref), ref_luma2 += Y(ref)^2 -- unless a component
+ *     of out or ref is not finite: then the pixel adds +0.0 to these four and to the three *_cov sums' out and ref terms, and counts
+ *     in skipped_out;  se_raw_rgb += E(raw - ref), se_raw_luma += (Y(raw) - Y(ref))^2 -- unless a component of raw or ref is not finite:
+ *     +0.0 and skipped_raw;  se_out_rgb_cov, se_raw_rgb_cov, ref_rgb2_cov: the terms of se_out_rgb, se_raw_rgb, ref_rgb2 where the
+ *     pixel is covered, +0.0 elsewhere.
+ * THE ORDER OF EVERY SUM IS FIXED.  The P pixels of the context's own rows are numbered p = 0 .. P - 1, row-major from row_begin; the
+ * sequence of a sum's terms is padded with +0.0 to the next power of two and added pairwise, adjacent pairs first: x[2 i] + x[2 i + 1],
+ * level by level, until one value is left (P = 0: +0.0).  The result depends on P and on nothing else -- not on the grid, the workgroup
+ * size, the stream placement or how many pixels a lane takes; tests/score_ref.py restates it bit for bit.  Counts are integers.
+ * Works at every ray rate (4 included), with both samplers, every depth, sample count and sample-set size, a deforming mesh, a
+ * caller-owned stream, rtggx_set_async_compute(0) and on strips: a strip scores its own rows, and adding the strips' records is the
+ * caller's.  Refusals (wrong `bytes`, scoring without a reference, null results) leave the context as it was. */
+typedef struct RtggxScore {            /* 120 bytes (6 x 8 of counts, 9 x 8 of sums), all sums in fp64 */
+  uint64_t index;        /* frames scored by this context before this one (monotonic over off/on): a gap = records overwritten unread */
+  uint32_t frame_index;  /* RtggxCBGlobal::FrameIndex of the scored frame */
+  uint32_t pad;
+  uint64_t pixels, covered;            /* the context's own rows x W; of those, visibility word != 0 */
+  uint64_t skipped_out, skipped_raw;   /* pixels left out of the *_out / *_raw sums: a non-finite rgb component in the image or the reference */
+  double se_out_rgb, se_out_luma;      /* TemporalSSOut[parity] against the reference, all pixels */
+  double se_raw_rgb, se_raw_luma;      /* the raw frame against the reference, all pixels */
+  double ref_rgb2, ref_luma2;          /* the reference's own energy over the pixels of the *_out sums */
+  double se_out_rgb_cov, se_raw_rgb_cov, ref_rgb2_cov;   /* covered pixels only */
+} RtggxScore;
+enum { RTGGX_SCORE_RING = 256 };
+int  rtggx_set_reference(rtggx_context* ctx, const void* rgba16f, size_t bytes);
+int  rtggx_reference_from_accumulation(rtggx_context* ctx);
+int  rtggx_set_scoring(rtggx_context* ctx, int enable);
+int  rtggx_read_scores(rtggx_context* ctx, RtggxScore* out, uint32_t capacity, uint32_t* count);
+
 /* Build of both bottom-level structures (RayTracer::buildAccelerationStructures / BuildAccelerationStructures, RayTracer.cpp:676-716,
  * 158-233; the sample records the builds on the GPU timeline and waits once, RayTracedGGX.cpp:236): every step of the build --
  * Morton codes, sort, PLOC clustering, the refit schedule, the node arrays -- is a kernel launch on the context's build stream

@@ -17,7 +17,9 @@ HOST_EXPORTS = ["rtggx_app_last_error", "rtggx_app_create", "rtggx_app_destroy",
                 "rtggx_host_halton", "rtggx_host_frame_constants", "rtggx_host_write_png", "rtggx_host_camera",
                 "rtggx_app_on_lbutton_down", "rtggx_app_on_lbutton_up", "rtggx_app_on_mouse_move", "rtggx_app_on_mouse_wheel", "rtggx_app_load_track",
                 "rtggx_host_exchange_plan", "rtggx_host_balanced_bounds", "rtggx_app_set_dump_prefix", "rtggx_app_last_screen_shot", "rtggx_app_save_converged",
-                "rtggx_host_frame_indices", "rtggx_host_accumulation_note"]
+                "rtggx_host_frame_indices", "rtggx_host_accumulation_note",
+                "rtggx_app_save_reference", "rtggx_app_flush_scores", "rtggx_app_set_reference", "rtggx_app_set_scoring", "rtggx_app_read_scores",
+                "rtggx_host_write_pfm", "rtggx_host_read_pfm"]
 
 _lib = None
 
@@ -44,6 +46,13 @@ def load():
         L.rtggx_app_save_image.argtypes = [C.c_void_p, C.c_char_p]
         L.rtggx_app_save_converged.argtypes = [C.c_void_p, C.c_char_p]
         L.rtggx_app_set_dump_prefix.argtypes = [C.c_void_p, C.c_char_p]
+        L.rtggx_app_save_reference.argtypes = [C.c_void_p, C.c_char_p]
+        L.rtggx_app_flush_scores.argtypes = [C.c_void_p]
+        L.rtggx_app_set_reference.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rtggx_app_set_scoring.argtypes = [C.c_void_p, C.c_int]
+        L.rtggx_app_read_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.rtggx_host_write_pfm.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.rtggx_host_read_pfm.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.rtggx_app_last_screen_shot.argtypes = [C.c_void_p]
         L.rtggx_app_last_screen_shot.restype = C.c_char_p
         L.rtggx_host_obj_import.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p]
@@ -108,6 +117,26 @@ def frame_indices(sample_set, frames):
     out = np.zeros(frames, np.uint32)
     held = load().rtggx_host_frame_indices(int(sample_set), frames, out.ctypes.data_as(C.c_void_p))
     return held, out
+
+
+def write_pfm(path, rgba16f):
+    """The host layer's PFM writer (no device): rgba16f = uint16[H, W, 4] (or uint64[H, W]) RGBA16F words -> "PF", fp32 rgb, rows bottom to top."""
+    a = np.ascontiguousarray(rgba16f)
+    if a.dtype == np.uint64:
+        a = a.view(np.uint16).reshape(a.shape[0], a.shape[1], 4)
+    a = np.ascontiguousarray(a, np.uint16)
+    if load().rtggx_host_write_pfm(str(path).encode(), a.shape[1], a.shape[0], a.ctypes.data_as(C.c_void_p)) != 0:
+        raise IOError("cannot write " + str(path))
+
+
+def read_pfm(path, width, height):
+    """The host layer's PFM reader (no device) -> uint16[height, width, 4] RGBA16F words, every fp32 value rounded to nearest even, alpha 1.
+    Raises IOError for what the reader refuses: a missing, malformed or truncated file, another size, a non-negative scale."""
+    L = load()
+    out = np.zeros((height, width, 4), np.uint16)
+    if L.rtggx_host_read_pfm(str(path).encode(), int(width), int(height), out.ctypes.data_as(C.c_void_p)) != 0:
+        raise IOError(L.rtggx_app_last_error().decode())
+    return out
 
 
 def accumulation_note(frames, samples, sample_set):
@@ -187,6 +216,45 @@ class RayTracedGGX:
         """The mean of the accumulated frames (-accumulate N, or context.set_accumulation) presented and its tone map written to `path`;
         prints the frame count and the mean relative standard error of Y.  False when nothing was accumulated."""
         return self.L.rtggx_app_save_converged(self.h, path.encode()) == 0
+
+    def save_reference(self, path):
+        """BUF_CONVERGED as the last save_converged / present_accumulation left it, written as a PFM file (-savereference)."""
+        return self.L.rtggx_app_save_reference(self.h, path.encode()) == 0
+
+    def set_reference(self, rgba16f):
+        """RayTracer::SetReference: H x W RGBA16F words (uint64[H, W] as readback(BUF_CONVERGED) gives them); None releases the image."""
+        if rgba16f is None:
+            rc = self.L.rtggx_app_set_reference(self.h, None, 0)
+        else:
+            a = np.ascontiguousarray(rgba16f)
+            rc = self.L.rtggx_app_set_reference(self.h, a.ctypes.data_as(C.c_void_p), a.nbytes)
+        if rc != 0:
+            raise capi.RtggxError(self.L.rtggx_app_last_error().decode())
+
+    def reference_from_accumulation(self):
+        self.context.reference_from_accumulation()
+
+    def set_scoring(self, enable):
+        """RayTracer::SetScoring: every frame from the next one on is scored against the reference; refused without one."""
+        if self.L.rtggx_app_set_scoring(self.h, 1 if enable else 0) != 0:
+            raise capi.RtggxError(self.L.rtggx_app_last_error().decode())
+
+    def read_scores(self, capacity=None):
+        """RayTracer::ReadScores: the unread records, oldest first, as a list of dicts."""
+        out = []
+        while capacity is None or len(out) < capacity:
+            room = capi.SCORE_RING if capacity is None else min(capi.SCORE_RING, capacity - len(out))
+            buf, n = (capi.Score * room)(), C.c_uint32()
+            if self.L.rtggx_app_read_scores(self.h, buf, room, C.byref(n)) != 0:
+                raise capi.RtggxError(self.L.rtggx_app_last_error().decode())
+            out += [buf[i].as_dict() for i in range(n.value)]
+            if n.value < room:
+                break
+        return out
+
+    def flush_scores(self):
+        """Appends the unread records to the -score file as JSON lines (the executable does so every capi.SCORE_RING frames and at the end)."""
+        return self.L.rtggx_app_flush_scores(self.h) == 0
 
     def set_dump_prefix(self, prefix):
         """Where [F11] screen shots go: <prefix>_f<frame>.png (the -dump flag)."""

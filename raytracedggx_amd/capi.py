@@ -34,12 +34,25 @@ EXPORTS = ["rtggx_last_error", "rtggx_create", "rtggx_destroy", "rtggx_set_strip
            "rtggx_ray_count", "rtggx_get_timings", "rtggx_enable_timing", "rtggx_buffer_size", "rtggx_readback", "rtggx_buffer_ptr",
            "rtggx_upload", "rtggx_frame_parity", "rtggx_bvh_root", "rtggx_trace_rays", "rtggx_ray_total", "rtggx_kernel_times", "rtggx_debug_counters", "rtggx_debug_trace_split", "rtggx_debug_trace_residency", "rtggx_get_stream", "rtggx_set_history_peers", "rtggx_history_ipc_export", "rtggx_history_ipc_open",
            "rtggx_set_async_compute", "rtggx_set_history_apron", "rtggx_history_overreach", "rtggx_copy_bandwidth", "rtggx_refit_as", "rtggx_refit_as_device", "rtggx_refit_stats", "rtggx_set_refit_policy", "rtggx_set_sampler", "rtggx_set_ray_rate", "rtggx_set_max_recursion_depth", "rtggx_set_samples_per_pixel", "rtggx_debug_fuse_tone_map", "rtggx_debug_placement", "rtggx_debug_tile_words", "rtggx_debug_static_sky", "rtggx_debug_sky_runs", "rtggx_debug_collapse_weights", "rtggx_debug_fence_wait", "rtggx_debug_shader_clock", "rtggx_debug_environment",
-           "rtggx_set_accumulation", "rtggx_reset_accumulation", "rtggx_accumulated_frames", "rtggx_present_accumulation", "rtggx_set_sample_set"]
+           "rtggx_set_accumulation", "rtggx_reset_accumulation", "rtggx_accumulated_frames", "rtggx_present_accumulation", "rtggx_set_sample_set",
+           "rtggx_set_reference", "rtggx_reference_from_accumulation", "rtggx_set_scoring", "rtggx_read_scores"]
+SCORE_RING = 256
 
 
 class Timings(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("update_as", "visibility", "ray_trace", "spatial_refl_h", "spatial_refl_v",
                                          "spatial_diff_h", "spatial_diff_v", "temporal", "tone_map", "frame", "ray_trace_kernel")]
+
+
+class Score(C.Structure):
+    """RtggxScore (rtggx.h): one scored frame -- counts, then nine fp64 sums in the contract's pairwise order."""
+    _fields_ = [("index", C.c_uint64), ("frame_index", C.c_uint32), ("pad", C.c_uint32), ("pixels", C.c_uint64), ("covered", C.c_uint64),
+                ("skipped_out", C.c_uint64), ("skipped_raw", C.c_uint64)] + \
+               [(n, C.c_double) for n in ("se_out_rgb", "se_out_luma", "se_raw_rgb", "se_raw_luma", "ref_rgb2", "ref_luma2",
+                                          "se_out_rgb_cov", "se_raw_rgb_cov", "ref_rgb2_cov")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad"}
 
 
 _lib = None
@@ -70,6 +83,10 @@ def load():
     L.rtggx_reset_accumulation.argtypes = [vp]
     L.rtggx_accumulated_frames.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.rtggx_present_accumulation.argtypes = [vp]
+    L.rtggx_set_reference.argtypes = [vp, vp, C.c_size_t]
+    L.rtggx_reference_from_accumulation.argtypes = [vp]
+    L.rtggx_set_scoring.argtypes = [vp, C.c_int]
+    L.rtggx_read_scores.argtypes = [vp, C.POINTER(Score), C.c_uint32, C.POINTER(C.c_uint32)]
     L.rtggx_set_history_apron.argtypes = [vp, C.c_uint32]
     L.rtggx_debug_shader_clock.argtypes = [vp, C.POINTER(C.c_double)]
     L.rtggx_refit_as.argtypes = [vp, C.c_uint32, vp, C.c_uint32]
@@ -294,6 +311,35 @@ class Context:
     def present_accumulation(self):
         """BUF_CONVERGED = the mean of the accumulated frames, and its tone map in BUF_BACKBUFFER (whole frames, at least one frame)."""
         self._check(self.L.rtggx_present_accumulation(self.h))
+
+    def set_reference(self, rgba16f):
+        """The image every frame is scored against: H x W RGBA16F words as readback(BUF_CONVERGED) gives them (uint64[H, W], or any array of
+        W * H * 8 bytes); None releases it and turns scoring off.  Synchronises; may replace a reference in mid-run (include/rtggx.h)."""
+        if rgba16f is None:
+            self._check(self.L.rtggx_set_reference(self.h, None, 0))
+            return
+        a = np.ascontiguousarray(rgba16f)
+        self._check(self.L.rtggx_set_reference(self.h, _p(a), a.nbytes))
+
+    def reference_from_accumulation(self):
+        """The reference becomes the mean of the accumulated frames (present_accumulation's image) without touching the back buffer."""
+        self._check(self.L.rtggx_reference_from_accumulation(self.h))
+
+    def set_scoring(self, enable):
+        """Every frame from the next one on is scored against the reference inside the frame; refused without a reference."""
+        self._check(self.L.rtggx_set_scoring(self.h, 1 if enable else 0))
+
+    def read_scores(self, capacity=None):
+        """The unread records, oldest first, as a list of dicts (at most `capacity`; default: all of them).  Waits for the main stream only."""
+        out = []
+        while capacity is None or len(out) < capacity:
+            room = SCORE_RING if capacity is None else min(SCORE_RING, capacity - len(out))
+            buf, n = (Score * room)(), C.c_uint32()
+            self._check(self.L.rtggx_read_scores(self.h, buf, room, C.byref(n)))
+            out += [buf[i].as_dict() for i in range(n.value)]
+            if n.value < room:
+                break
+        return out
 
     def set_refit_policy(self, rebuild_ratio=1.2, steps_per_frame=16):
         self._check(self.L.rtggx_set_refit_policy(self.h, rebuild_ratio, steps_per_frame))

@@ -303,6 +303,32 @@ int allocAccumulation(rtggx_context* c) {
   c->accRefl = a0; c->accDiff = a1; c->converged = cv;
   return 0;
 }
+// What scoring needs (rtggx_set_reference, rtggx_set_scoring; score.hip): the reference image, 8 bytes per pixel of the full frame, with the
+// first reference; the ring of records and the tree's partial sums -- sized for the full frame, whatever strip is scored -- with the first
+// enable, all of them or none.  Released by rtggx_destroy.
+static int allocReference(rtggx_context* c, const char* who) {
+  if (c->reference) return 0;
+  const size_t n = (size_t)c->W * c->H;
+  const hipError_t e = hipMalloc(&c->reference, n * 8);
+  if (e != hipSuccess) { c->reference = nullptr; setError("%s: %s (%zu bytes for the reference image)", who, hipGetErrorString(e), n * 8); return -2; }
+  return 0;
+}
+static int allocScoring(rtggx_context* c) {
+  if (c->scoreRing) return 0;
+  const size_t chunks = ((size_t)c->W * c->H + RT_SCORE_CHUNK - 1u) / RT_SCORE_CHUNK;
+  uint32_t stride = 1u; while (stride < chunks) stride <<= 1;
+  const size_t half = stride > 1u ? stride / 2u : 1u;
+  double *p0 = nullptr, *p1 = nullptr; uint32_t* counts = nullptr; RtggxScore* ring = nullptr;
+  hipError_t e = hipMalloc(&p0, sizeof(double) * RT_SCORE_SUMS * stride);
+  if (e == hipSuccess) e = hipMalloc(&p1, sizeof(double) * RT_SCORE_SUMS * half);
+  if (e == hipSuccess) e = hipMalloc(&counts, sizeof(uint32_t) * 3u * stride);
+  if (e == hipSuccess) e = hipMalloc(&ring, sizeof(RtggxScore) * RTGGX_SCORE_RING);
+  if (e == hipSuccess) e = hipMemset(ring, 0, sizeof(RtggxScore) * RTGGX_SCORE_RING);
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);      // (the clear runs on the null stream, which this context's streams are not ordered against)
+  if (e != hipSuccess) { hipFree(p0); hipFree(p1); hipFree(counts); hipFree(ring); setError("rtggx_set_scoring: %s (the ring of records and the partial sums)", hipGetErrorString(e)); return -2; }
+  c->scorePartial[0] = p0; c->scorePartial[1] = p1; c->scoreCounts = counts; c->scoreRing = ring; c->scoreStride = stride;
+  return 0;
+}
 }  // namespace rt
 
 using namespace rt;
@@ -346,6 +372,7 @@ void rtggx_destroy(rtggx_context* c) {
   hipFree(c->visDirtyOnes);
   hipFree(c->sppAcc); hipFree(c->sppParams); destroyEvent(c->evSpp);
   hipFree(c->accRefl); hipFree(c->accDiff); hipFree(c->converged);
+  hipFree(c->reference); hipFree(c->scorePartial[0]); hipFree(c->scorePartial[1]); hipFree(c->scoreCounts); hipFree(c->scoreRing);
   hipFree(c->tss[0]); hipFree(c->tss[1]);
   hipFree(c->fltRfl); hipFree(c->fltDff); hipFree(c->largeTrisBuf[0]); hipFree(c->largeTrisBuf[1]); hipFree(c->largeCountBase); hipFree(c->rayCounter); hipFree(c->dParams);
   for (auto b : c->binWorkBuf) hipFree(b);
@@ -573,6 +600,61 @@ int rtggx_present_accumulation(rtggx_context* c) {
   if (!r) r = launchToneMap(c, fp, c->streamMain, nullptr, c->converged);
   c->toneMapDone = false;
   return r;
+}
+
+// Scoring against a reference (score.hip; DESIGN.md "Scoring against a reference").  The reference is read by the scoring kernels on the
+// main stream alone.  rtggx_set_reference copies from the host: it waits for every stream first (frames in flight still read the image it
+// replaces or frees) and copies before it returns; rtggx_reference_from_accumulation writes it by a kernel on the main stream, behind the
+// scores already enqueued there and in front of the later ones -- no wait.
+int rtggx_set_reference(rtggx_context* c, const void* rgba16f, size_t bytes) {
+  RT_CHECK_CTX(c);
+  const size_t want = (size_t)c->W * c->H * 8u;
+  if (!rgba16f && bytes == 0u) {      // release: scoring ends with it
+    RT_HIP(syncStreams(c));
+    if (c->reference) RT_HIP(hipFree(c->reference));
+    c->reference = nullptr; c->scoring = c->scoringRequested = false;
+    return 0;
+  }
+  if (!rgba16f || bytes != want) { setError("rtggx_set_reference: %zu bytes for a %u x %u RGBA16F image of %zu", bytes, c->W, c->H, want); return -1; }
+  RT_HIP(syncStreams(c));
+  { const int r = allocReference(c, "rtggx_set_reference"); if (r) return r; }
+  RT_HIP(hipMemcpy(c->reference, rgba16f, want, hipMemcpyHostToDevice));
+  return 0;
+}
+int rtggx_reference_from_accumulation(rtggx_context* c) {
+  RT_CHECK_CTX(c);
+  if (!c->accRefl) { setError("rtggx_reference_from_accumulation: accumulation was never enabled (rtggx_set_accumulation)"); return -1; }
+  if (c->rowBegin > 0u || c->rowEnd < c->H) { setError("rtggx_reference_from_accumulation: on a strip (rows [%u,%u) of %u): whole frames only", c->rowBegin, c->rowEnd, c->H); return -1; }
+  if (c->accumFrames == 0u) { setError("rtggx_reference_from_accumulation: no frame has been accumulated"); return -1; }
+  { const int r = allocReference(c, "rtggx_reference_from_accumulation"); if (r) return r; }
+  return launchReferenceFromAccumulation(c, c->streamMain);
+}
+// Taken over by the next rtggx_render_visibility, like accumulation; off allocates nothing.  `index` goes on counting over off and on.
+int rtggx_set_scoring(rtggx_context* c, int enable) {
+  RT_CHECK_CTX(c);
+  if (enable && !c->reference) { setError("rtggx_set_scoring: no reference image (rtggx_set_reference, rtggx_reference_from_accumulation)"); return -1; }
+  if (enable) { const int r = allocScoring(c); if (r) return r; }
+  c->scoringRequested = enable != 0;
+  return 0;
+}
+// The unread records, oldest first.  Waits for the main stream alone: every record is written by the last kernel rtggx_denoise put there.
+int rtggx_read_scores(rtggx_context* c, RtggxScore* out, uint32_t capacity, uint32_t* count) {
+  RT_CHECK_CTX(c);
+  if (!count || (!out && capacity > 0u)) { setError("rtggx_read_scores: null result"); return -1; }
+  *count = 0u;
+  if (!c->scoreRing || c->scoreIndex == c->scoreRead) return 0;
+  RT_HIP(hipStreamSynchronize(c->streamMain));
+  if (c->scoreIndex - c->scoreRead > (uint64_t)RTGGX_SCORE_RING) c->scoreRead = c->scoreIndex - (uint64_t)RTGGX_SCORE_RING;      // the older ones have been overwritten
+  const uint64_t unread = c->scoreIndex - c->scoreRead;
+  const uint32_t n = unread < capacity ? (uint32_t)unread : capacity;
+  for (uint32_t done = 0; done < n;) {      // at most two runs of slots: the ring wraps once
+    const uint32_t slot = (uint32_t)((c->scoreRead + done) % (uint64_t)RTGGX_SCORE_RING);
+    const uint32_t run = n - done < (uint32_t)RTGGX_SCORE_RING - slot ? n - done : (uint32_t)RTGGX_SCORE_RING - slot;
+    RT_HIP(hipMemcpy(out + done, c->scoreRing + slot, sizeof(RtggxScore) * run, hipMemcpyDeviceToHost));
+    done += run;
+  }
+  c->scoreRead += n; *count = n;
+  return 0;
 }
 
 int rtggx_set_mesh(rtggx_context* c, uint32_t slot, const float* verts, uint32_t nv, const uint32_t* idx, uint32_t ni) {
@@ -941,6 +1023,7 @@ int rtggx_render_visibility(rtggx_context* c) {
   settleSetRead(c);      // (the previous frame ended without the kernel that would have carried its set's event)
   ++c->frameCounter;
   c->maxDepth = c->depthRequested; c->samples = c->samplesRequested; c->accumulate = c->accumulateRequested;
+  c->scoring = c->scoringRequested && c->reference != nullptr;
   bool resendConstants = false;
   if (c->sampleSet != c->sampleSetRequested) {      // rtggx_set_sample_set: the kernels' variant, the table and the constants' mask change together
     // several frames from one rtggx_update_frame share the slot's device copy: the frame before may still read the mask that goes with ITS
@@ -1078,10 +1161,15 @@ int rtggx_denoise(rtggx_context* c, int useSharedMem) {
   // kernel's workgroups of 1024 threads and 45 KB of LDS find room on a CU shared with the traversal's resident workgroup and ray
   // generation later than four small ones do (1080p 0.186 -> 0.204 ms; 512 threads: 0.199).  So it follows the placement's `small`; not in
   // the per-pass timing mode (the tone map keeps a duration of its own); rtggx_debug_fuse_tone_map pins it either way.
-  const bool fuse = !c->timing && (c->fuseToneMap > 0 || (c->fuseToneMap < 0 && c->lastTraceSmall));
+  // While scoring is on (rtggx_set_scoring) the tone map is never fused either: the scoring kernels go behind the temporal pass and in FRONT
+  // of the kernel that carries the set's evRead -- they read the set's traced images and the frame's visibility target.
+  const bool fuse = !c->timing && !c->scoring && (c->fuseToneMap > 0 || (c->fuseToneMap < 0 && c->lastTraceSmall));
   // the fused kernel is the frame's last on this stream and carries the set's event; else the tone map will
   const int r = launchDenoise(c, c->slots[c->slot], useSharedMem, c->streamMain, fuse ? c->cur().evRead : nullptr, fuse);
   if (fuse) { c->cur().readRecorded = true; c->setReadDeferred = -1; } else c->setReadDeferred = (int)c->setIndex;
+  // the frame's score (score.hip): TemporalSSOut[parity] is complete where the main stream stands, the set's evRead still to come -- on the
+  // tone map, or recorded by settleSetRead -- behind these two kernels
+  if (!r && c->scoring && c->reference) { const int rs = launchScore(c, c->slots[c->slot], c->streamMain); if (rs) return rs; }
   c->denoiseIssued = true; c->toneMapDone = fuse && c->slots[c->slot].rowEnd > c->slots[c->slot].rowBegin;
   return r;
 }

@@ -267,6 +267,19 @@ struct rtggx_context {
   bool accumulate = false, accumulateRequested = false;
   uint32_t accumFrames = 0;
   float4 *accRefl = nullptr, *accDiff = nullptr; uint2* converged = nullptr;      // converged: RTGGX_BUF_CONVERGED (rtggx_present_accumulation)
+  // rtggx_set_reference / rtggx_set_scoring (score.hip; DESIGN.md "Scoring against a reference"): the frame's, the next frame's.  Nothing
+  // below exists on a context that never calls them (capi.hip allocReference, allocScoring); all of it is released by rtggx_destroy.
+  //   reference      W * H RGBA16F words, written by rtggx_set_reference (host copy) or rtggx_reference_from_accumulation (main stream)
+  //   scorePartial   the tree's levels, ping-pong: [0] RT_SCORE_SUMS x scoreStride doubles -- one per sum and chunk of RT_SCORE_CHUNK pixels,
+  //                  sum-major --, [1] half of that; scoreCounts: 3 words per chunk (covered, skipped_out, skipped_raw)
+  //   scoreRing      RTGGX_SCORE_RING records, slot = index % RTGGX_SCORE_RING
+  // ONE set of partials for all frames: both stages of every frame run on the main stream, in its order.  scoreIndex: frames scored so
+  // far, counted by the host as it enqueues them; scoreRead: the first record rtggx_read_scores has not handed out yet.
+  bool scoring = false, scoringRequested = false;
+  uint2* reference = nullptr;
+  double* scorePartial[2] = {nullptr, nullptr}; uint32_t* scoreCounts = nullptr; uint32_t scoreStride = 0;
+  RtggxScore* scoreRing = nullptr;
+  uint64_t scoreIndex = 0, scoreRead = 0;
   uint32_t traceGrid[4] = {};    // the frame's level-0 trace launch -- bins, tile grid x / y, slice shift --, which the later levels repeat
   float rebuildRatio = 1.2f; uint32_t rebuildSteps = 16;      // rtggx_set_refit_policy
   rt::MeshDev mesh[2];
@@ -441,6 +454,11 @@ int allocSamples(rtggx_context* c);      // what N > 1 samples per pixel need (r
 int allocAccumulation(rtggx_context* c);      // what rtggx_set_accumulation needs (rtggx_context::accRefl, accDiff, converged), once
 int launchAccumulate(rtggx_context* c, const FrameParams& fp, hipStream_t s);      // the frame's traced images added to the sums, the strip's own rows
 int launchPresentAccumulation(rtggx_context* c, hipStream_t s);      // RTGGX_BUF_CONVERGED from the sums and accumFrames
+// Scoring against a reference (score.hip): a chunk is the run of pixels one workgroup reduces to one partial per sum.
+#define RT_SCORE_CHUNK 1024u
+#define RT_SCORE_SUMS 9u
+int launchScore(rtggx_context* c, const FrameParams& fp, hipStream_t s);      // the frame's record into slot scoreIndex % RTGGX_SCORE_RING: two kernels
+int launchReferenceFromAccumulation(rtggx_context* c, hipStream_t s);      // rtggx_context::reference = the mean image of the sums and accumFrames
 int launchTraceRays(rtggx_context* c, const FrameParams& fp, const float* dRays, uint32_t n, float* dOut, hipStream_t s);
 int launchDebugEnvironment(rtggx_context* c, const float* dDirs, const float* dLevels, uint32_t n, int level0, float* dOut, hipStream_t s);      // rtggx_debug_environment: reads the environment only
 int launchDenoise(rtggx_context* c, const FrameParams& fp, int useLds, hipStream_t s, hipEvent_t done = nullptr, bool fuseToneMap = false);      // fuseToneMap: the last kernel also writes the back buffer

@@ -39,6 +39,8 @@ int main(int argc, char* argv[]) {
       std::string stem = app.GetDumpPrefix().empty() ? std::string("RayTracedGGX") : app.GetDumpPrefix();
       if (stem.size() >= 4 && (stem.compare(stem.size() - 4, 4, ".png") == 0 || stem.compare(stem.size() - 4, 4, ".ppm") == 0)) stem.resize(stem.size() - 4);
       if (!app.SaveConverged((stem + "_converged.png").c_str())) { app.OnDestroy(); return 1; }
+      // -savereference: the same image, unquantised, beside it
+      if (!app.GetSaveReference().empty() && !app.SaveReference(app.GetSaveReference().c_str())) { app.OnDestroy(); return 1; }
     }
     app.OnDestroy();
   } catch (const std::exception& e) {

@@ -37,6 +37,9 @@ void RayTracedGGX::OnInit() {
   if (m_samplesPerPixel != 1u && !m_rayTracer->SetSamplesPerPixel(m_samplesPerPixel)) throw std::runtime_error("-spp: " + m_rayTracer->GetLastError());      // -spp N: multi-sample tracing (opt-in)
   if (m_sampleSet != RTGGX_MIN_SAMPLE_SET && !m_rayTracer->SetSampleSetSize(m_sampleSet)) throw std::runtime_error("-sampleset: " + m_rayTracer->GetLastError());      // -sampleset M: a larger sample set (opt-in)
   m_rayTracer->SetAsyncCompute(m_asyncCompute != 0);   // -sync: one stream, submission order (the sample's single command list)
+  // -reference: the image read while the command line was parsed goes to the device; -score: every frame from the first one is scored
+  if (!m_referenceImage.empty() && !m_rayTracer->SetReference(m_referenceImage.data(), m_referenceImage.size() * 2)) throw std::runtime_error("-reference: " + m_rayTracer->GetLastError());
+  if (!m_scoreFile.empty() && !m_rayTracer->SetScoring(true)) throw std::runtime_error("-score: " + m_rayTracer->GetLastError());
 
   if (m_deformAmplitude != 0.0f) {       // key shapes of the breathing model: x and z displaced by a wave travelling up the y axis
     const std::vector<float>& base = m_rayTracer->GetModelVertices();
@@ -98,6 +101,8 @@ void RayTracedGGX::OnRender() {
   m_denoiser->Denoise(m_useSharedMem, m_asyncCompute != 0);
   m_denoiser->ToneMap();
   m_frameIndex = (uint8_t)((m_frameIndex + 1) % FrameCount);   // MoveToNextFrame :684-701
+  // -score: the ring holds RTGGX_SCORE_RING records; it is read that often (one wait for the main stream) and once more at the end
+  if (!m_scoreFile.empty() && m_frameNumber % (uint32_t)RTGGX_SCORE_RING == 0u && !FlushScores()) throw std::runtime_error("-score: cannot write " + m_scoreFile);
   // Screen-shot helper (MoveToNextFrame :703-717: the sample copies the back buffer of the frame rendered after [F11] and writes
   // "RayTracedGGX_<time stamp>.png" FrameCount frames later).  Headless runs want reproducible names: <-dump prefix or RayTracedGGX>
   // _f<frame number, 6 digits>.png, written at once (the read-back waits for the frame).
@@ -112,6 +117,7 @@ void RayTracedGGX::OnRender() {
 }
 
 void RayTracedGGX::OnDestroy() {
+  if (!m_scoreFile.empty() && m_rayTracer && m_rayTracer->GetContext()) FlushScores();
   if (m_rayTracer && m_rayTracer->GetContext()) rtggx_sync(m_rayTracer->GetContext());   // WaitForGpu
   m_denoiser.reset();
   m_rayTracer.reset();
@@ -198,7 +204,7 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
     return (arg[0] == '-' || arg[0] == '/') && lower(arg + 1) == lower(name);
   };
   // On POSIX an absolute path also starts with '/': such a token is a flag only when it names one.
-  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "recursion", "spp", "accumulate", "sampleset"};
+  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "recursion", "spp", "accumulate", "sampleset", "savereference", "reference", "score"};
   const auto isFlagName = [&](const char* name) { for (const char* f : kFlags) if (lower(name) == f) return true; return false; };
   const auto hasNextArgValue = [&](int i) {
     if (i + 1 >= argc) return false;
@@ -247,6 +253,9 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
       if (frames < 1) throw std::runtime_error("-accumulate: a number of frames, 1 or more");
       m_accumulate = (uint32_t)frames;
     }
+    else if (isArgMatched(i, "savereference")) { if (hasNextArgValue(i)) m_saveReferenceFile = argv[++i]; else throw std::runtime_error("-savereference: a file name"); }
+    else if (isArgMatched(i, "reference")) { if (hasNextArgValue(i)) m_referenceFile = argv[++i]; else throw std::runtime_error("-reference: a file name"); }
+    else if (isArgMatched(i, "score")) { if (hasNextArgValue(i)) m_scoreFile = argv[++i]; else throw std::runtime_error("-score: a file name"); }
     else if (isArgMatched(i, "device")) { if (hasNextArgValue(i)) m_device = std::atoi(argv[++i]); }
     else if (isArgMatched(i, "dump")) { if (hasNextArgValue(i)) m_dumpPrefix = argv[++i]; }
     else if (isArgMatched(i, "deform")) { nextFloat(i, m_deformAmplitude); }
@@ -263,6 +272,12 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
   // three quarters of a rate-4 frame are interpolations (rtggx_set_accumulation); the sums of several strips are not gathered
   if (m_accumulate != 0u && m_rayRate != 1u) throw std::runtime_error("-accumulate together with -rayrate 4: refused");
   if (m_accumulate != 0u && (m_gpus > 1 || m_strips > 1)) throw std::runtime_error("-accumulate: whole frames on one GPU only, not with -gpus N > 1 or -strips N > 1");
+  // scoring against a reference (rtggx_set_scoring): a strip scores its own rows and nobody adds the records of several; the file is read
+  // -- and a bad one refused -- here, before anything has touched a GPU
+  if (!m_saveReferenceFile.empty() && m_accumulate == 0u) throw std::runtime_error("-savereference: needs -accumulate N (the converged image is what it writes)");
+  if (!m_scoreFile.empty() && m_referenceFile.empty()) throw std::runtime_error("-score: needs -reference <file.pfm>");
+  if ((!m_scoreFile.empty() || !m_referenceFile.empty()) && (m_gpus > 1 || m_strips > 1)) throw std::runtime_error("-reference / -score: whole frames on one GPU only, not with -gpus N > 1 or -strips N > 1");
+  if (!m_referenceFile.empty()) { std::string why; if (!ReadPfm(m_referenceFile.c_str(), m_width, m_height, m_referenceImage, why)) throw std::runtime_error("-reference: " + why); }
   // quarter-rate tracing renders whole frames only (rtggx_set_ray_rate): refused here, before anything has touched a GPU
   // one knob asks for fewer rays, the other for more (rtggx_set_samples_per_pixel)
   if (m_rayRate != 1u && m_samplesPerPixel != 1u) throw std::runtime_error("-spp N > 1 together with -rayrate 4: refused");
@@ -310,6 +325,102 @@ bool WritePng(const char* fileName, uint32_t w, uint32_t h, uint32_t comp, const
   const bool ok = std::fwrite(file.data(), 1, file.size(), f) == file.size();
   std::fclose(f);
   return ok;
+}
+
+// fp16 <-> fp32 on the host, bit by bit: every half is exact in fp32; fp32 to half rounds to nearest even, overflows to infinity, keeps NaN.
+static float halfToFloat(uint16_t h) {
+  const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3FFu;
+  uint32_t u;
+  if (e == 0u) {
+    if (m == 0u) u = sign;
+    else { int shift = 0; uint32_t mm = m; while (!(mm & 0x400u)) { mm <<= 1; ++shift; } u = sign | ((uint32_t)(113 - shift) << 23) | ((mm & 0x3FFu) << 13); }
+  } else if (e == 31u) u = sign | 0x7F800000u | (m << 13);
+  else u = sign | ((e + 112u) << 23) | (m << 13);
+  float f; std::memcpy(&f, &u, 4); return f;
+}
+static uint16_t floatToHalf(float f) {
+  uint32_t u; std::memcpy(&u, &f, 4);
+  const uint16_t sign = (uint16_t)((u >> 16) & 0x8000u);
+  const uint32_t a = u & 0x7FFFFFFFu;
+  if (a > 0x7F800000u) return (uint16_t)(sign | 0x7E00u | ((a >> 13) & 0x3FFu));      // NaN
+  if (a >= 0x47800000u) return (uint16_t)(sign | 0x7C00u);                              // 65536 and beyond, infinity
+  if (a < 0x38800000u) {                                                               // below the smallest normal half: a multiple of 2^-24
+    if (a < 0x33000000u) return sign;                                                  // below 2^-25: zero (2^-25 itself is a tie, to even: zero)
+    const uint32_t e = a >> 23, mant = (a & 0x7FFFFFu) | 0x800000u, sh = 126u - e;     // value = mant * 2^(e - 150); in units of 2^-24: mant >> (126 - e)
+    const uint32_t q = mant >> sh, rem = mant & ((1u << sh) - 1u), half = 1u << (sh - 1u);
+    return (uint16_t)(sign | (q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u)));
+  }
+  uint32_t r = a - 0x38000000u;                                                        // rebias, then round the 13 dropped bits to even; a carry walks into the exponent
+  r += 0xFFFu + ((r >> 13) & 1u);
+  return (uint16_t)(sign | (r >> 13));
+}
+
+bool WritePfm(const char* fileName, uint32_t w, uint32_t h, const uint16_t* rgba16f) {
+  if (!fileName || !rgba16f || w == 0u || h == 0u) return false;
+  FILE* f = std::fopen(fileName, "wb");
+  if (!f) return false;
+  std::fprintf(f, "PF\n%u %u\n-1.0\n", w, h);
+  std::vector<float> row((size_t)w * 3);
+  bool ok = true;
+  for (uint32_t y = h; y-- > 0u && ok;) {      // bottom row first
+    for (uint32_t x = 0; x < w; ++x) for (int k = 0; k < 3; ++k) row[3 * (size_t)x + k] = halfToFloat(rgba16f[4 * ((size_t)y * w + x) + k]);
+    ok = std::fwrite(row.data(), 4, row.size(), f) == row.size();
+  }
+  return std::fclose(f) == 0 && ok;
+}
+
+bool ReadPfm(const char* fileName, uint32_t w, uint32_t h, std::vector<uint16_t>& rgba16f, std::string& error) {
+  const std::string name = fileName ? fileName : "";
+  FILE* f = std::fopen(name.c_str(), "rb");
+  if (!f) { error = "cannot open " + name; return false; }
+  const auto fail = [&](const std::string& why) { std::fclose(f); error = name + ": " + why; return false; };
+  // the header: three tokens lines "PF", "<w> <h>", "<scale>", separated by white space, ONE white-space byte behind the scale
+  char magic[3] = {0, 0, 0}; unsigned fw = 0, fh = 0; double scale = 0.0; char sep = 0;
+  if (std::fscanf(f, "%2s", magic) != 1 || std::strcmp(magic, "PF") != 0) return fail("not a colour PFM file (no \"PF\")");
+  if (std::fscanf(f, "%u %u", &fw, &fh) != 2) return fail("malformed PFM header (width and height)");
+  if (std::fscanf(f, "%lf", &scale) != 1 || std::fread(&sep, 1, 1, f) != 1 || !std::isspace((unsigned char)sep)) return fail("malformed PFM header (scale)");
+  if (!(scale < 0.0)) return fail("a non-negative scale: big-endian PFM files are not read");
+  if (fw != w || fh != h) { char t[96]; std::snprintf(t, sizeof t, "%u x %u pixels, the frame has %u x %u", fw, fh, w, h); return fail(t); }
+  std::vector<float> row((size_t)w * 3);
+  rgba16f.assign((size_t)w * h * 4, 0x3C00u);      // alpha 1
+  for (uint32_t y = h; y-- > 0u;) {
+    if (std::fread(row.data(), 4, row.size(), f) != row.size()) { rgba16f.clear(); return fail("truncated PFM file"); }
+    for (uint32_t x = 0; x < w; ++x) for (int k = 0; k < 3; ++k) rgba16f[4 * ((size_t)y * w + x) + k] = floatToHalf(row[3 * (size_t)x + k]);
+  }
+  std::fclose(f);
+  return true;
+}
+
+bool RayTracedGGX::SaveReference(const char* fileName) {
+  rtggx_context* ctx = GetContext();
+  if (!ctx) return false;
+  std::vector<uint16_t> image((size_t)m_width * m_height * 4);
+  if (rtggx_readback(ctx, RTGGX_BUF_CONVERGED, image.data(), image.size() * 2) != 0) { std::fprintf(stderr, "SaveReference: %s\n", rtggx_last_error()); return false; }
+  if (!WritePfm(fileName, m_width, m_height, image.data())) { std::fprintf(stderr, "SaveReference: cannot write %s\n", fileName); return false; }
+  std::printf("wrote %s\n", fileName);
+  return true;
+}
+
+// One JSON line per record: the relative L2 distances sqrt(se / ref2) -- null where the reference's energy is 0 --, %.17g: the double itself.
+bool RayTracedGGX::FlushScores() {
+  if (m_scoreFile.empty() || !m_rayTracer) return false;
+  std::vector<RtggxScore> scores;
+  if (!m_rayTracer->ReadScores(scores)) { std::fprintf(stderr, "FlushScores: %s\n", m_rayTracer->GetLastError().c_str()); return false; }
+  FILE* f = std::fopen(m_scoreFile.c_str(), m_scoreFileStarted ? "ab" : "wb");
+  if (!f) return false;
+  m_scoreFileStarted = true;
+  const auto rel = [&](const char* key, double se, double ref2) {
+    if (ref2 > 0.0 && std::isfinite(se)) std::fprintf(f, ", \"%s\": %.17g", key, std::sqrt(se / ref2)); else std::fprintf(f, ", \"%s\": null", key);
+  };
+  for (const RtggxScore& s : scores) {
+    std::fprintf(f, "{\"index\": %llu, \"frame_index\": %u", (unsigned long long)s.index, s.frame_index);
+    rel("rel_l2_out", s.se_out_rgb, s.ref_rgb2); rel("rel_l2_raw", s.se_raw_rgb, s.ref_rgb2);
+    rel("rel_l2_out_cov", s.se_out_rgb_cov, s.ref_rgb2_cov); rel("rel_l2_raw_cov", s.se_raw_rgb_cov, s.ref_rgb2_cov);
+    rel("rel_l2_out_luma", s.se_out_luma, s.ref_luma2); rel("rel_l2_raw_luma", s.se_raw_luma, s.ref_luma2);
+    std::fprintf(f, ", \"pixels\": %llu, \"covered\": %llu, \"skipped_out\": %llu, \"skipped_raw\": %llu}\n", (unsigned long long)s.pixels,
+                 (unsigned long long)s.covered, (unsigned long long)s.skipped_out, (unsigned long long)s.skipped_raw);
+  }
+  return std::fclose(f) == 0;
 }
 
 // The mean relative standard error of Y over covered pixels of one accumulated image, from its sums (4 floats per pixel: sum r, g, b, Y^2):

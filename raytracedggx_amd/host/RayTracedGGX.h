@@ -2,7 +2,7 @@
 // DXFramework virtuals RayTracedGGX/Common/DXFramework.h:23-26): OnInit / OnUpdate / OnRender /
 // OnDestroy, the same command line (RayTracedGGX.cpp:462-511) and the same defaults
 // (RayTracedGGX.cpp:37-39, camera :19-23, 267-277).  What the window supplied interactively is
-// supplied by extra flags: -width -height -frames -dt -metallic -sharedmem -sync -vndf -rayrate -recursion -spp -sampleset -accumulate -device -dump -track -deform -gpus -strips -balance.
+// supplied by extra flags: -width -height -frames -dt -metallic -sharedmem -sync -vndf -rayrate -recursion -spp -sampleset -accumulate -savereference -reference -score -device -dump -track -deform -gpus -strips -balance.
 #pragma once
 #include <vector>
 #include <cstdint>
@@ -13,6 +13,13 @@
 #include "XMath.h"
 
 bool WritePng(const char* fileName, uint32_t w, uint32_t h, uint32_t comp, const uint8_t* pixels);   // comp 3 (RGB) or 4 (RGBA), 8 bits
+
+// PFM, the float container of a reference image (-savereference / -reference): "PF", width and height, scale -1.0 (little-endian), then rows
+// bottom to top of fp32 rgb.  The images here are RGBA16F words (the layout of RTGGX_BUF_CONVERGED): every half is exact in fp32, so writing
+// and reading gives the halves back; on load any fp32 value is rounded to nearest even into a half and alpha is 1.  ReadPfm refuses a missing,
+// malformed or truncated file, a size other than w x h and a non-negative (big-endian) scale, and says why in `error`.
+bool WritePfm(const char* fileName, uint32_t w, uint32_t h, const uint16_t* rgba16f);
+bool ReadPfm(const char* fileName, uint32_t w, uint32_t h, std::vector<uint16_t>& rgba16f, std::string& error);
 
 // the tail of the line -accumulate prints: "; sample set of M", and a warning once more than M frames were accumulated (they repeat)
 std::string AccumulationSampleSetNote(uint32_t frames, uint32_t samplesPerPixel, uint32_t sampleSet);
@@ -63,6 +70,12 @@ class RayTracedGGX {
   // it divides by the count of all accumulated frames, so it assumes materials that did not change since the last reset)
   uint32_t GetAccumulate() const { return m_accumulate; }
   bool SaveConverged(const char* fileName);
+  // -savereference <file.pfm>: RTGGX_BUF_CONVERGED as SaveConverged left it, as a PFM file
+  const std::string& GetSaveReference() const { return m_saveReferenceFile; }
+  bool SaveReference(const char* fileName);
+  // -score <file.jsonl>: the records rtggx_read_scores hands out, one JSON line per frame appended to the file; OnRender calls it every
+  // RTGGX_SCORE_RING frames, the caller once more at the end of the run (OnDestroy does)
+  bool FlushScores();
   bool SaveImage(const char* fileName);   // tone-mapped back buffer as PNG (name ends in .png) or binary PPM (screenshot, RayTracedGGX.cpp:719-739)
 
  protected:
@@ -110,6 +123,12 @@ class RayTracedGGX {
   uint32_t m_samplesPerPixel = 1;      // -spp <1|2|4|8>: samples per covered pixel (RayTracer::SetSamplesPerPixel); not together with -rayrate 4
   uint32_t m_sampleSet = RTGGX_MIN_SAMPLE_SET;      // -sampleset <256..65536, a power of two>: the size of the sample set (RayTracer::SetSampleSetSize); every rank of -gpus / -strips gets it
   uint32_t m_accumulate = 0;           // -accumulate <N>: accumulation on for the last N frames of the run (all of them when N >= -frames); not with -rayrate 4, -gpus, -strips
+  // -reference <file.pfm>: the image every frame is scored against (RayTracer::SetReference), read -- and refused -- while the command line is
+  // parsed; -score <file.jsonl>: scoring on from frame 0 (needs -reference); -savereference <file.pfm>: needs -accumulate.  -reference and
+  // -score: whole frames on one GPU only, not with -gpus / -strips
+  std::string m_referenceFile, m_scoreFile, m_saveReferenceFile;
+  std::vector<uint16_t> m_referenceImage;
+  bool m_scoreFileStarted = false;
   uint32_t m_rayRate = 1;              // -rayrate <1|4>: pixels per traced ray (RayTracer::SetRayRate); 4 renders whole frames only: not with -gpus / -strips
   // -deform <amplitude>: the model breathes -- a travelling sine wave through its vertices, DeformPeriod key shapes computed once
   // at start-up and handed to RayTracer::UpdateMesh one per frame (per-frame host cost: one copy of the vertex array)

@@ -84,6 +84,20 @@ bool RayTracer::SetSampleSetSize(uint32_t size) {
 bool RayTracer::SetAccumulation(bool enable) { return check(rtggx_set_accumulation(m_ctx, enable ? 1 : 0), "rtggx_set_accumulation"); }
 bool RayTracer::ResetAccumulation() { return check(rtggx_reset_accumulation(m_ctx), "rtggx_reset_accumulation"); }
 
+bool RayTracer::SetReference(const void* rgba16f, size_t bytes) { return check(rtggx_set_reference(m_ctx, rgba16f, bytes), "rtggx_set_reference"); }
+bool RayTracer::SetScoring(bool enable) { return check(rtggx_set_scoring(m_ctx, enable ? 1 : 0), "rtggx_set_scoring"); }
+bool RayTracer::ReadScores(std::vector<RtggxScore>& out) {
+  for (;;) {      // a ring's worth at a time until nothing is left unread
+    const size_t have = out.size();
+    out.resize(have + RTGGX_SCORE_RING);
+    uint32_t n = 0;
+    const bool ok = check(rtggx_read_scores(m_ctx, out.data() + have, RTGGX_SCORE_RING, &n), "rtggx_read_scores");
+    out.resize(have + (ok ? n : 0u));
+    if (!ok) return false;
+    if (n < (uint32_t)RTGGX_SCORE_RING) return true;
+  }
+}
+
 void RayTracer::SetAsyncCompute(bool asyncCompute) { check(rtggx_set_async_compute(m_ctx, asyncCompute ? 1 : 0), "rtggx_set_async_compute"); }
 
 void RayTracer::UpdateFrame(uint8_t frameIndex, const xm::Float3& eyePt, const xm::Matrix& viewProj, float timeStep) {

@@ -51,6 +51,12 @@ class RayTracer {
   // not together with ray rate 4.  A moving camera or a changed material is the caller's to reset.
   bool SetAccumulation(bool enable);
   bool ResetAccumulation();
+  // rtggx_set_reference / rtggx_set_scoring / rtggx_read_scores: the image every frame is scored against on the device (W * H RGBA16F
+  // words; nullptr, 0 releases it), scoring on from the next frame (refused without a reference), and the records not yet read, oldest
+  // first, appended to `out` -- it waits for the main stream alone (-reference, -score)
+  bool SetReference(const void* rgba16f, size_t bytes);
+  bool SetScoring(bool enable);
+  bool ReadScores(std::vector<RtggxScore>& out);
   void UpdateFrame(uint8_t frameIndex, const xm::Float3& eyePt, const xm::Matrix& viewProj, float timeStep);
   void TransformSH();
   void Render(uint8_t frameIndex);

@@ -54,6 +54,34 @@ const char* rtggx_app_last_screen_shot(void* h) { return ((RayTracedGGX*)h)->Get
 int rtggx_app_save_converged(void* h, const char* path) { return ((RayTracedGGX*)h)->SaveConverged(path) ? 0 : -1; }
 int rtggx_app_save_image(void* h, const char* path) { return ((RayTracedGGX*)h)->SaveImage(path) ? 0 : -1; }
 
+int rtggx_app_save_reference(void* h, const char* path) { return ((RayTracedGGX*)h)->SaveReference(path) ? 0 : -1; }
+int rtggx_app_flush_scores(void* h) { return ((RayTracedGGX*)h)->FlushScores() ? 0 : -1; }
+// RayTracer::SetReference / SetScoring / ReadScores of the application's ray tracer (capacity records of 120 bytes at `out`)
+int rtggx_app_set_reference(void* h, const void* rgba16f, size_t bytes) {
+  RayTracer* rt = ((RayTracedGGX*)h)->GetRayTracer();
+  if (rt->SetReference(rgba16f, bytes)) return 0;
+  g_appError = rt->GetLastError(); return -1;
+}
+int rtggx_app_set_scoring(void* h, int enable) {
+  RayTracer* rt = ((RayTracedGGX*)h)->GetRayTracer();
+  if (rt->SetScoring(enable != 0)) return 0;
+  g_appError = rt->GetLastError(); return -1;
+}
+int rtggx_app_read_scores(void* h, void* out, uint32_t capacity, uint32_t* count) {
+  RayTracer* rt = ((RayTracedGGX*)h)->GetRayTracer();
+  if (!count || (!out && capacity)) { g_appError = "rtggx_app_read_scores: null result"; return -1; }
+  if (rtggx_read_scores(rt->GetContext(), (RtggxScore*)out, capacity, count) == 0) return 0;
+  g_appError = rtggx_last_error(); return -1;
+}
+// The PFM writer and reader on their own (no device): w x h RGBA16F words out of / into `rgba16f`.
+int rtggx_host_write_pfm(const char* path, uint32_t w, uint32_t h, const uint16_t* rgba16f) { return WritePfm(path, w, h, rgba16f) ? 0 : -1; }
+int rtggx_host_read_pfm(const char* path, uint32_t w, uint32_t h, uint16_t* rgba16f) {
+  std::vector<uint16_t> image; std::string error;
+  if (!ReadPfm(path, w, h, image, error)) { g_appError = error; return -1; }
+  std::memcpy(rgba16f, image.data(), image.size() * 2);
+  return 0;
+}
+
 int rtggx_host_write_png(const char* path, uint32_t w, uint32_t h, uint32_t comp, const uint8_t* pixels) { return WritePng(path, w, h, comp, pixels) ? 0 : -1; }
 
 // Host-only pieces, usable without a GPU: the OBJ importer and the Halton sequence.

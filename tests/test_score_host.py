@@ -1,0 +1,221 @@
+"""Scoring against a reference without a GPU (rtggx_set_reference, rtggx_set_scoring, -reference / -score / -savereference; include/rtggx.h,
+DESIGN.md "Scoring against a reference"): the ABI surface, the command line's refusals before any GPU is touched, the PFM reader and writer
+of the host layer, the numpy restatement's tree (tests/score_ref.py) against exact sums, and the restatement's figures on the CPU oracle's
+frames against the plain float64 relative L2 of tools/probes/convergence_probe.py."""
+import ctypes as C
+import math
+import os
+import re
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import accum_ref as AR
+import assets
+import score_ref as SR
+from oracle import oracle as O
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+# ---- surface ------------------------------------------------------------------------------------------------------------------------
+def test_scoring_is_declared_exported_and_bound(built):
+    from raytracedggx_amd import app, capi
+    header = open(os.path.join(ROOT, "include", "rtggx.h")).read()
+    assert re.search(r"\bint\s+rtggx_set_reference\s*\(\s*rtggx_context\s*\*\s*ctx\s*,\s*const\s+void\s*\*\s*rgba16f\s*,\s*size_t\s+bytes\s*\)", header)
+    assert re.search(r"\bint\s+rtggx_reference_from_accumulation\s*\(\s*rtggx_context\s*\*\s*ctx\s*\)", header)
+    assert re.search(r"\bint\s+rtggx_set_scoring\s*\(\s*rtggx_context\s*\*\s*ctx\s*,\s*int\s+enable\s*\)", header)
+    assert re.search(r"\bint\s+rtggx_read_scores\s*\(\s*rtggx_context\s*\*\s*ctx\s*,\s*RtggxScore\s*\*\s*out\s*,\s*uint32_t\s+capacity\s*,\s*uint32_t\s*\*\s*count\s*\)", header)
+    assert re.search(r"\bRTGGX_SCORE_RING\s*=\s*256\b", header) and capi.SCORE_RING == 256
+    assert re.search(r"\bRTGGX_BUF_COUNT\s*=\s*28\b", header), "scoring adds no buffer id"
+    # the record: the fields of the header's struct in its order; six 8-byte slots of counts and nine doubles.  (The issue that asked for
+    # the struct gives this field list and calls it 112 bytes; the fields it lists add up to 120 -- 48 + 72 -- and the list is what is kept.)
+    body = re.search(r"typedef struct RtggxScore \{(.*?)\} RtggxScore;", header, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    names = [n for decl in re.findall(r"(?:uint64_t|uint32_t|double)\s+([^;]+);", body) for n in re.split(r"\s*,\s*", decl.strip())]
+    assert names == [n for n, _ in capi.Score._fields_]
+    assert C.sizeof(capi.Score) == 120 == 6 * 8 + 9 * 8
+    assert [n for n, t in capi.Score._fields_ if t is C.c_double] == list(SR.SUMS)
+    lib = C.CDLL(capi.LIB_PATH)
+    for name, method in (("rtggx_set_reference", "set_reference"), ("rtggx_reference_from_accumulation", "reference_from_accumulation"),
+                         ("rtggx_set_scoring", "set_scoring"), ("rtggx_read_scores", "read_scores")):
+        assert hasattr(lib, name) and name in capi.EXPORTS
+        assert callable(getattr(capi.Context, method, None)) and callable(getattr(app.RayTracedGGX, method, None))
+    host = C.CDLL(app.HOST_LIB_PATH)
+    for name in ("rtggx_app_set_reference", "rtggx_app_set_scoring", "rtggx_app_read_scores", "rtggx_app_save_reference", "rtggx_app_flush_scores",
+                 "rtggx_host_write_pfm", "rtggx_host_read_pfm"):
+        assert name in app.HOST_EXPORTS and hasattr(host, name)
+    flags = open(os.path.join(ROOT, "raytracedggx_amd", "host", "RayTracedGGX.h")).read().split("#pragma once")[0]
+    for flag in ("-savereference", "-reference", "-score"):
+        assert flag in flags, "the header comment of RayTracedGGX.h lists " + flag
+
+
+# ---- refusals of the executable -----------------------------------------------------------------------------------------------------
+def _pfm_bytes(w, h, scale=b"-1.0", rows=None):
+    rows = h if rows is None else rows
+    return b"PF\n%d %d\n%s\n" % (w, h, scale) + np.linspace(0.0, 1.0, w * rows * 3, dtype="<f4").tobytes()
+
+
+def test_executable_refuses_bad_score_flags_before_touching_a_gpu(built, tmp_path):
+    exe = os.path.join(ROOT, "raytracedggx_amd", "RayTracedGGX")
+    scene = ["-mesh", assets.path("triangle.obj"), "-env", assets.path("rnl_cross.dds"), "-width", "64", "-height", "36"]
+    good, trunc, small, big_endian, junk = (str(tmp_path / n) for n in ("good.pfm", "trunc.pfm", "small.pfm", "be.pfm", "junk.pfm"))
+    open(good, "wb").write(_pfm_bytes(64, 36))
+    open(trunc, "wb").write(_pfm_bytes(64, 36, rows=35) + b"\0" * 100)
+    open(small, "wb").write(_pfm_bytes(32, 36))
+    open(big_endian, "wb").write(_pfm_bytes(64, 36, scale=b"1.0"))
+    open(junk, "wb").write(b"P6\n64 36\n255\n" + b"\0" * (64 * 36 * 3))
+    jsonl = str(tmp_path / "scores.jsonl")
+    cases = [(["-score", jsonl], "-score"), (["-score"], "-score"), (["-reference"], "-reference"),
+             (["-savereference", str(tmp_path / "out.pfm")], "-savereference"), (["-savereference", str(tmp_path / "out.pfm"), "-frames", "4"], "-savereference"),
+             (["-reference", str(tmp_path / "missing.pfm")], "cannot open"), (["-reference", trunc], "truncated"), (["-reference", small], "32 x 36"),
+             (["-reference", big_endian], "scale"), (["-reference", junk], "PF"),
+             (["-reference", good, "-gpus", "2"], "-gpus"), (["-reference", good, "-score", jsonl, "-gpus", "2"], "-gpus"),
+             (["-strips", "2", "-reference", good], "-strips"), (["-strips", "2", "-reference", good, "-score", jsonl], "-strips")]
+    for extra, word in cases:
+        r = subprocess.run([exe] + scene + extra, capture_output=True, text=True, timeout=60)
+        assert r.returncode == 1, (extra, r.returncode, r.stderr)
+        assert word in r.stderr, (extra, r.stderr)
+        assert "HIP device" not in r.stderr and "rank" not in r.stderr.lower(), (extra, r.stderr)
+    assert not os.path.exists(jsonl) and not os.path.exists(str(tmp_path / "out.pfm"))
+
+
+# ---- PFM -----------------------------------------------------------------------------------------------------------------------------
+def test_pfm_round_trip_keeps_every_finite_half_and_rounds_to_even(built, tmp_path):
+    from raytracedggx_amd import app
+    # every finite half pattern, both signs, in the three colour channels of a 256 x 84 image (64512 = 2 x 31 x 1024 + 2 x 512 patterns, padded)
+    patterns = np.array([h for h in range(1 << 16) if (h >> 10) & 31 != 31], np.uint16)
+    assert patterns.size == 63488
+    w, h = 256, 84
+    img = np.zeros((h, w, 4), np.uint16)
+    flat = img[..., :3].reshape(-1).copy()
+    flat[:patterns.size] = patterns
+    img[..., :3] = flat.reshape(h, w, 3)
+    img[..., 3] = 0x1234                                            # alpha is not stored: it comes back as 1
+    path = str(tmp_path / "halves.pfm")
+    app.write_pfm(path, img)
+    data = open(path, "rb").read()
+    assert data.startswith(b"PF\n256 84\n-1.0\n") and len(data) == len(b"PF\n256 84\n-1.0\n") + w * h * 12
+    # the file: fp32 rgb, rows bottom to top
+    body = np.frombuffer(data[len(b"PF\n256 84\n-1.0\n"):], "<f4").reshape(h, w, 3)
+    np.testing.assert_array_equal(body[::-1].view(np.uint32), img[..., :3].view(np.float16).astype(np.float32).view(np.uint32))
+    back = app.read_pfm(path, w, h)
+    np.testing.assert_array_equal(back[..., :3], img[..., :3])
+    assert (back[..., 3] == 0x3C00).all()
+    # a uint64 image, the layout readback(BUF_CONVERGED) gives, goes the same way
+    app.write_pfm(path, np.ascontiguousarray(img).view(np.uint64)[..., 0])
+    np.testing.assert_array_equal(app.read_pfm(path, w, h)[..., :3], img[..., :3])
+    # fp32 values between two halves: to nearest, ties to even -- numpy's float16 conversion is the same IEEE rounding
+    rng = np.random.default_rng(11)
+    lo = np.array([0x3C00, 0x3C01, 0x0001, 0x0000, 0x03FF, 0x7BFE, 0x7BFF, 0x8001, 0xBC01], np.uint16).view(np.float16).astype(np.float32)
+    hi = np.array([0x3C01, 0x3C02, 0x0002, 0x0001, 0x0400, 0x7BFF, 0x7C00, 0x8002, 0xBC02], np.uint16).view(np.float16).astype(np.float64)
+    hi[6] = 65536.0                                                  # the "half" beyond the largest finite one
+    ties = ((lo.astype(np.float64) + hi) / 2).astype(np.float32)
+    vals = np.concatenate([ties, np.nextafter(ties, np.float32(np.inf)), np.nextafter(ties, np.float32(-np.inf)),
+                           (rng.standard_normal(3000) * 10.0 ** rng.integers(-9, 6, 3000)).astype(np.float32),
+                           np.array([1e-8, 2.0 ** -25, 65519.99, 65520.0, 1e9, -1e9, np.inf, -np.inf, 0.0, -0.0], np.float32)])
+    vals = np.concatenate([vals, np.zeros((-vals.size) % 3, np.float32)])
+    n = vals.size // 3
+    open(path, "wb").write(b"PF\n%d 1\n-1.000000\n" % n + vals.astype("<f4").tobytes())
+    got = app.read_pfm(path, n, 1)[0, :, :3].reshape(-1)
+    with np.errstate(over="ignore"):
+        want = vals.astype(np.float16).view(np.uint16)
+    np.testing.assert_array_equal(got, want)
+    assert got[:9].tolist() == [0x3C00, 0x3C02, 0x0002, 0x0000, 0x0400, 0x7BFE, 0x7C00, 0x8002, 0xBC02], "ties go to the even half"
+    # what the reader refuses
+    for name, data, word in (("trunc", _pfm_bytes(8, 4)[:-1], "truncated"), ("size", _pfm_bytes(4, 8), "4 x 8"), ("scale", _pfm_bytes(8, 4, scale=b"1.0"), "scale"),
+                             ("zero", _pfm_bytes(8, 4, scale=b"0"), "scale"), ("grey", _pfm_bytes(8, 4).replace(b"PF", b"Pf", 1), "PF"),
+                             ("header", b"PF\n8 x\n-1.0\n" + b"\0" * 400, "header"), ("empty", b"", "PF")):
+        p = str(tmp_path / (name + ".pfm"))
+        open(p, "wb").write(data)
+        with pytest.raises(IOError, match=re.escape(word)):
+            app.read_pfm(p, 8, 4)
+    with pytest.raises(IOError, match="cannot open"):
+        app.read_pfm(str(tmp_path / "missing.pfm"), 8, 4)
+
+
+# ---- the restatement's tree ---------------------------------------------------------------------------------------------------------
+def test_tree_sum_is_exact_on_integers_and_within_its_bound_of_the_exact_sum():
+    rng = np.random.default_rng(7)
+    sizes = (0, 1, 2, 3, 5, 64, 100, 255, 256, 257, 1000, 1024, 1025, 5400, 5184, 65537, 230400)
+    for n in sizes:
+        x = rng.integers(0, 1 << 20, n).astype(np.float64)              # every partial sum is an integer below 2^53: no rounding anywhere
+        assert SR.tree_sum(x) == float(x.astype(np.int64).sum()), n
+    assert SR.tree_sum([]) == 0.0 and math.copysign(1.0, SR.tree_sum([])) == 1.0
+    # the order is the contract's: a case where a left-to-right sum and the pairwise tree differ
+    x = np.array([1.0, 2.0 ** -53, 2.0 ** -53, 0.0, 2.0 ** -52])
+    assert SR.tree_sum(x) == (((1.0 + 2.0 ** -53) + (2.0 ** -53 + 0.0)) + ((2.0 ** -52 + 0.0) + (0.0 + 0.0)))
+    assert [SR.tree_levels(n) for n in (0, 1, 2, 3, 4, 5, 1024, 1025, 5400)] == [0, 0, 1, 2, 2, 3, 10, 11, 13]
+    worst = 0.0
+    for n in sizes[2:]:
+        for scale in (1.0, 1e-12, 1e12):
+            x = (rng.random(n) ** 8) * scale                             # non-negative, like every term of a score; a long tail of small values
+            err, bound = abs(SR.tree_sum(x) - math.fsum(x)), SR.tree_bound(x)
+            worst = max(worst, err / bound)
+            assert err <= bound, (n, scale, err, bound)
+    print("tree_sum against math.fsum: worst error / bound %.3f" % worst)
+
+
+# ---- the restatement on the oracle's frames ----------------------------------------------------------------------------------------
+W, H = 96, 54
+
+
+def _probe_rel_l2(x, ref):
+    """tools/probes/convergence_probe.py rel_l2, as written there: plain float64, numpy's own summation."""
+    return float(np.sqrt(((x - ref) ** 2).sum() / max((ref ** 2).sum(), 1e-300)))
+
+
+@pytest.mark.parametrize("metallic", [(1.0, 1.0), (0.25, 0.5)], ids=["metal", "diffuse"])
+def test_restated_figures_equal_the_probes_relative_l2_on_oracle_frames(built, metallic):
+    """The CPU oracle renders 12 frames of the bunny at 96x54; the reference is the mean of their raw images (the restatement of
+    rtggx_present_accumulation); frames 10 .. 12 are scored.  sqrt(se / ref2) of the restatement against the probe's figure.
+
+    The bound.  With T the exact sum of the exact per-pixel terms, a tree sum is within (L + 2) 2^-53 T of it: two roundings inside a
+    pixel's (a + b) + c, each at most 2^-53 of the term, and L = ceil(log2 P) levels (score_ref.tree_bound).  The probe squares every
+    component (one rounding, 2^-53) and leaves the sum to numpy, whose pairwise summation adds along chains of at most 16 + 3 +
+    ceil(log2(n / 128)) additions for n values (blocks of 128 in 8 accumulators): D = that many roundings.  Quotient, square root:
+    one rounding each, and the square root halves the relative error of its argument.  So the two figures differ by at most
+    ((2 (L + 2) + 2 (D + 1)) / 2 + 4) 2^-53 relative: both quotients' errors halved, plus the division and the root on either side."""
+    o = O.Oracle(W, H)
+    try:
+        v, i, _ = O.obj_import(assets.path("bunny.obj"))
+        o.set_mesh(1, v, i)
+        o.set_env_dds(assets.path("rnl_cross.dds"))
+        o.set_metallic(0, metallic[0]); o.set_metallic(1, metallic[1])
+        o.build_as(); o.transform_sh()
+        acc = AR.Accumulator(H, W)
+        frames = []
+        for f in range(12):
+            o.update_frame((10, 10, -24), O.camera_view_proj(W, H), 0.0)
+            o.update_as(); o.render_visibility(); o.ray_trace(); o.denoise()
+            words = (o.buffer(O.BUF_TSS0 + o.parity()).copy(), o.buffer(O.BUF_RT_REFL).copy(), o.buffer(O.BUF_RT_DIFF).copy(), o.buffer(O.BUF_VISIBILITY).copy())
+            acc.add(words[1], words[2], words[3], metallic)
+            frames.append(words)
+    finally:
+        o.close()
+    reference = acc.converged()
+    ref = SR.unpack_rgba16f(reference)
+    P = W * H
+    L, D = SR.tree_levels(P), 16 + 3 + SR.tree_levels((3 * P + 127) // 128)
+    bound = ((L + 2) + (D + 1) + 4) * 2.0 ** -53
+    for tss, refl, diff, vis in frames[9:]:
+        rec = SR.score(tss, refl, diff, vis, metallic, reference)
+        assert rec["pixels"] == P and 500 < rec["covered"] < P and rec["skipped_out"] == 0 and rec["skipped_raw"] == 0
+        fig = SR.figures(rec)
+        raw = AR.unpack_r11g11b10f(refl).astype(np.float64)
+        raw += np.where(AR.diffuse_mask(vis, metallic)[..., None], AR.unpack_r11g11b10f(diff).astype(np.float64), 0.0)
+        for key, image in (("rel_l2_out", SR.unpack_rgba16f(tss)), ("rel_l2_raw", raw)):
+            want = _probe_rel_l2(image, ref)
+            print("%s %s: restatement %.17g, probe %.17g, difference / bound %.3f" % (metallic, key, fig[key], want, abs(fig[key] - want) / (bound * want)))
+            assert 0.0 < want < 10.0
+            assert abs(fig[key] - want) <= bound * want, (key, fig[key], want)
+        # the covered-only figures and the luma figures against their own plain float64 forms
+        cov = vis != 0
+        want = _probe_rel_l2(SR.unpack_rgba16f(tss)[cov], ref[cov])
+        assert abs(fig["rel_l2_out_cov"] - want) <= bound * want
+        y = lambda c: (0.25 * c[..., 0] + 0.5 * c[..., 1]) + 0.25 * c[..., 2]
+        want = _probe_rel_l2(y(SR.unpack_rgba16f(tss)), y(ref))
+        assert abs(fig["rel_l2_out_luma"] - want) <= bound * want
+        assert fig["rel_l2_raw"] > fig["rel_l2_out"], "the denoised image is closer to the mean than one raw frame"
