@@ -67,6 +67,9 @@ def lib():
     return _lib
 
 
+_own_lib = lib      # (Oracle.__init__ has a parameter of that name)
+
+
 def _fp(a):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -101,8 +104,9 @@ def camera_view_proj(width, height, eye=(10.0, 10.0, -24.0), focus=(0.0, 3.0, 0.
 class Oracle:
     """One scene + render-target set; methods follow RayTracer / Denoiser of the reference."""
 
-    def __init__(self, width, height, threads=None):
-        self.L = lib()
+    def __init__(self, width, height, threads=None, lib=None):
+        """lib: a library that holds the oracle's entry points with lib()'s signatures (tests/restatement.py); default: the oracle's own."""
+        self.L = lib if lib is not None else _own_lib()
         self.W, self.H = width, height
         self.h = C.c_void_p(self.L.orc_create(width, height))
         if not self.h:

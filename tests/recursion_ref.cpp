@@ -1,7 +1,7 @@
 // TEST INFRASTRUCTURE ONLY.  The CPU oracle (oracle/orc_capi.cpp, included whole) plus orc_ray_trace_depth(h, D): raygenMain
 // (RayTracing.hlsl:541-565) at recursion depth D, i.e. the reference's shaders with the closest hits (:571-614) passing
 // payload.RecursionDepth + 1 -- the semantics of rtggx_set_max_recursion_depth (include/rtggx.h, DESIGN.md "Recursion depth").  Built by
-// tests/recursion_ref.py with the oracle Makefile's flags.  At D = 1 it reproduces orc_ray_trace bit for bit through the same path loop
+// tests/restatement.py with the oracle Makefile's flags.  At D = 1 it reproduces orc_ray_trace bit for bit through the same path loop
 // (tests/test_recursion_host.py); D = 2..4 pin the product's multi-bounce frames.
 #include "../oracle/orc_capi.cpp"
 

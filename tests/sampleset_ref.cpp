@@ -1,13 +1,11 @@
-// TEST INFRASTRUCTURE ONLY.  The CPU oracle (oracle/orc_capi.cpp, included whole and unchanged: Ctx::cosTab keeps its 256 entries) plus
-// orc_ray_trace_sampleset(h, D, N, M): raygenMain at recursion depth D with N samples per covered pixel drawn from a sample set of M
-// members -- the semantics of rtggx_set_sample_set (include/rtggx.h, DESIGN.md "Sample-set size").  getSampleParam(index, dim, numSamples = M):
+// TEST INFRASTRUCTURE ONLY.  Part of tests/restatements.cpp, which has brought in the CPU oracle before this file (oracle/orc_capi.cpp, whole
+// and unchanged: Ctx::cosTab keeps its 256 entries).  orc_ray_trace_sampleset(h, D, N, M): raygenMain at recursion depth D with N samples
+// per covered pixel drawn from a sample set of M members -- the semantics of rtggx_set_sample_set (include/rtggx.h, DESIGN.md "Sample-set size").  getSampleParam(index, dim, numSamples = M):
 //     s = rng(rng(y W + x) + i) & (M - 1),  xi.x = s / M,  xi.y = (rng(s) & 0xffff) / 65536,
 //     (cosPhi, sinPhi) = ((float)cos(phi), (float)sin(phi)),  phi = 2.0 * 3.14159265358979323846 * (double)s / (double)M
 // with i = FrameIndex * N + k for sample k.  The path functions are those of tests/recursion_ref.cpp / tests/spp_ref.cpp once more, taking
-// their angle from this file's own M-entry table instead of the oracle's.  Built by tests/sampleset_ref.py with the oracle Makefile's flags.
+// their angle from this file's own M-entry table instead of the oracle's.  Built by tests/restatement.py with the oracle Makefile's flags.
 // At M = 256 it reproduces tests/spp_ref.cpp bit for bit (tests/test_sampleset_host.py); larger M pin the product's frames.
-#include "../oracle/orc_capi.cpp"
-
 #include <mutex>
 
 namespace orc {

@@ -2,7 +2,7 @@
 // recursion depth D with N samples per covered pixel -- the semantics of rtggx_set_samples_per_pixel (include/rtggx.h, DESIGN.md "Samples
 // per pixel").  It is raygen_pixel_depth with the sample loop: sample k takes xi = get_sample_param(pixel, FrameIndex * N + k), its value
 // v_k = c_k * T_k is what the one-sample frame packs (0 where NoL <= 0), and the pixel's word is pack_r11g11b10((0 + v_0 + ... + v_{N-1}) *
-// (1 / N)), summed in that order in fp32.  Built by tests/spp_ref.py with the oracle Makefile's flags.  At N = 1 it reproduces
+// (1 / N)), summed in that order in fp32.  Built by tests/restatement.py with the oracle Makefile's flags.  At N = 1 it reproduces
 // orc_ray_trace / orc_ray_trace_depth bit for bit (tests/test_spp_host.py); N = 2, 4, 8 pin the product's multi-sample frames.
 #include "recursion_ref.cpp"
 

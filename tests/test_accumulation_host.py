@@ -5,48 +5,35 @@ background, which holds one word in every frame."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import accum_ref as AR
-import assets
+import host_support as HS
 from oracle import oracle as O
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FRAME_INDEX_OFFSET = 444      # RtggxCBGlobal::FrameIndex in the 768 bytes of RtggxFrameConstants (include/rtggx.h): the last word of `global`
 
 
 def test_accumulation_is_declared_exported_and_bound(built):
     from raytracedggx_amd import app, capi
-    header = open(os.path.join(ROOT, "include", "rtggx.h")).read()
-    assert re.search(r"\bint\s+rtggx_set_accumulation\s*\(\s*rtggx_context\s*\*\s*ctx\s*,\s*int\s+enable\s*\)", header)
-    assert re.search(r"\bint\s+rtggx_reset_accumulation\s*\(\s*rtggx_context\s*\*\s*ctx\s*\)", header)
-    assert re.search(r"\bint\s+rtggx_accumulated_frames\s*\(\s*rtggx_context\s*\*\s*ctx\s*,\s*uint32_t\s*\*\s*frames\s*\)", header)
-    assert re.search(r"\bint\s+rtggx_present_accumulation\s*\(\s*rtggx_context\s*\*\s*ctx\s*\)", header)
+    for symbol, signature in (("rtggx_set_accumulation", r"\bint\s+rtggx_set_accumulation\s*\(\s*rtggx_context\s*\*\s*ctx\s*,\s*int\s+enable\s*\)"),
+                              ("rtggx_reset_accumulation", r"\bint\s+rtggx_reset_accumulation\s*\(\s*rtggx_context\s*\*\s*ctx\s*\)"),
+                              ("rtggx_accumulated_frames", r"\bint\s+rtggx_accumulated_frames\s*\(\s*rtggx_context\s*\*\s*ctx\s*,\s*uint32_t\s*\*\s*frames\s*\)"),
+                              ("rtggx_present_accumulation", r"\bint\s+rtggx_present_accumulation\s*\(\s*rtggx_context\s*\*\s*ctx\s*\)")):
+        HS.declared_exported_bound(symbol, signature)
+    header = open(os.path.join(HS.ROOT, "include", "rtggx.h")).read()
     for name, value in (("RTGGX_BUF_ACC_REFL", 25), ("RTGGX_BUF_ACC_DIFF", 26), ("RTGGX_BUF_CONVERGED", 27), ("RTGGX_BUF_COUNT", 28)):
         assert re.search(r"\b%s\s*=\s*%d\b" % (name, value), header), name
     assert (capi.BUF_ACC_REFL, capi.BUF_ACC_DIFF, capi.BUF_CONVERGED) == (25, 26, 27)
-    lib = C.CDLL(capi.LIB_PATH)
-    for name, method in (("rtggx_set_accumulation", "set_accumulation"), ("rtggx_reset_accumulation", "reset_accumulation"),
-                         ("rtggx_accumulated_frames", "accumulated_frames"), ("rtggx_present_accumulation", "present_accumulation")):
-        assert hasattr(lib, name) and name in capi.EXPORTS
-        assert callable(getattr(capi.Context, method, None))
     assert "rtggx_app_save_converged" in app.HOST_EXPORTS and hasattr(C.CDLL(app.HOST_LIB_PATH), "rtggx_app_save_converged")
     assert callable(getattr(app.RayTracedGGX, "save_converged", None))
 
 
 def test_executable_refuses_bad_accumulate_flags_before_touching_a_gpu(built):
-    exe = os.path.join(ROOT, "raytracedggx_amd", "RayTracedGGX")
-    scene = ["-mesh", assets.path("triangle.obj"), "-env", assets.path("rnl_cross.dds"), "-width", "64", "-height", "64"]
-    for extra in (["-accumulate", "0"], ["-accumulate", "-3"], ["-accumulate"], ["/ACCUMULATE", "x"], ["-Accumulate", "-frames", "4"],
-                  ["-accumulate", "8", "-rayrate", "4"], ["-rayrate", "4", "-accumulate", "8"], ["-accumulate", "8", "-gpus", "2"],
-                  ["-gpus", "2", "-accumulate", "8"], ["-accumulate", "8", "-strips", "2"], ["-strips", "3", "-accumulate", "2", "-frames", "4"]):
-        r = subprocess.run([exe] + scene + extra, capture_output=True, text=True, timeout=60)
-        assert r.returncode == 1, (extra, r.returncode, r.stderr)
-        assert "-accumulate" in r.stderr, (extra, r.stderr)
-        assert "HIP device" not in r.stderr and "rank" not in r.stderr.lower(), (extra, r.stderr)
+    HS.executable_refuses((["-accumulate", "0"], ["-accumulate", "-3"], ["-accumulate"], ["/ACCUMULATE", "x"], ["-Accumulate", "-frames", "4"],
+                           ["-accumulate", "8", "-rayrate", "4"], ["-rayrate", "4", "-accumulate", "8"], ["-accumulate", "8", "-gpus", "2"],
+                           ["-gpus", "2", "-accumulate", "8"], ["-accumulate", "8", "-strips", "2"], ["-strips", "3", "-accumulate", "2", "-frames", "4"]),
+                          "-accumulate")
 
 
 # ---- the restatement on the oracle's frames ----------------------------------------------------------------------------------------
@@ -58,20 +45,11 @@ def _frames(metallic):
     diff words [256, H, W])."""
     o = O.Oracle(W, H)
     try:
-        v, i, _ = O.obj_import(assets.path("bunny.obj"))
-        o.set_mesh(1, v, i)
-        o.set_env_dds(assets.path("rnl_cross.dds"))
-        o.set_metallic(0, metallic[0]); o.set_metallic(1, metallic[1])
-        o.build_as(); o.transform_sh()
-        for _ in range(2):
-            o.update_frame((10, 10, -24), O.camera_view_proj(W, H), 0.25)
-        o.update_as(); o.render_visibility()
+        HS.scene(o, "bunny.obj", metallic=metallic, frame=1)
         vis = o.buffer(O.BUF_VISIBILITY)
         refl, diff = np.zeros((FRAMES, H, W), np.uint32), np.zeros((FRAMES, H, W), np.uint32)
         for f in range(FRAMES):
-            fc = o.get_frame_constants()
-            fc[FRAME_INDEX_OFFSET:FRAME_INDEX_OFFSET + 4] = np.array([f], np.uint32).view(np.uint8)
-            o.set_frame_constants(fc.tobytes())
+            HS.set_frame_index(o, f)
             o.ray_trace()
             refl[f], diff[f] = o.buffer(O.BUF_RT_REFL), o.buffer(O.BUF_RT_DIFF)
         return vis, refl, diff

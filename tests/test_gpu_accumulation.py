@@ -7,17 +7,11 @@ import pytest
 
 import accum_ref as AR
 import assets
+import gpu_support as G
 
 pytestmark = pytest.mark.gpu
 
-
-def _app(W, H, extra=(), mesh="bunny.obj"):
-    from raytracedggx_amd import app
-    return app.RayTracedGGX(["-mesh", assets.path(mesh), "-env", assets.path("rnl_cross.dds"), "-width", W, "-height", H] + list(extra))
-
-
-def _frame(a):
-    a.OnUpdate(); a.OnRender()
+IMAGES = G.GBUFFER + G.RAW + G.DENOISED + G.RAYS
 
 
 def _words(a):
@@ -43,28 +37,11 @@ def _assert_sums(got, want, label):
             label, name, bad.sum(), bad.size, tuple(np.argwhere(bad)[0]), g[bad][0], w[bad][0])
 
 
-def _images(a):
-    from raytracedggx_amd import capi
-    c = a.context
-    c.sync()
-    ids = [("vis", capi.BUF_VISIBILITY), ("depth", capi.BUF_DEPTH), ("normal", capi.BUF_NORMAL), ("rm", capi.BUF_ROUGH_METAL), ("velocity", capi.BUF_VELOCITY),
-           ("refl", capi.BUF_RT_REFL), ("diff", capi.BUF_RT_DIFF), ("flt_rfl", capi.BUF_FLT_RFL), ("flt_dff", capi.BUF_FLT_DFF),
-           ("tss0", capi.BUF_TSS0), ("tss1", capi.BUF_TSS1), ("back", capi.BUF_BACKBUFFER)]
-    out = {n: c.readback(b) for n, b in ids}
-    out["rays"] = np.array([c.ray_count()])
-    return out
-
-
-def _assert_same(a, b, label):
-    for k in a:
-        np.testing.assert_array_equal(a[k], b[k], err_msg="%s: %s differs" % (label, k))
-
-
 def _restated_run(a, metallic, frames, acc=None):
     """`frames` frames of an accumulating app, each read back (synchronising) and added to the restatement."""
     acc = acc or AR.Accumulator(a.height, a.width)
     for _ in range(frames):
-        _frame(a)
+        G.frame(a)
         refl, diff, vis = _words(a)
         acc.add(refl, diff, vis, metallic)
     return acc
@@ -77,7 +54,7 @@ def _restated_run(a, metallic, frames, acc=None):
     ids=["metal", "diffuse", "metal-ground", "vndf", "spp4-depth2", "dragon"])
 def test_sums_equal_the_restatement(built, mesh, metallic, extra):
     """100x54, 6 frames: RTGGX_BUF_ACC_REFL, _ACC_DIFF and the count against the restatement after every frame, bit for bit."""
-    a = _app(100, 54, ["-metallic", metallic[0], metallic[1]] + extra, mesh=mesh)
+    a = G.app(100, 54, ["-metallic", metallic[0], metallic[1]] + extra, mesh=mesh)
     try:
         a.context.set_accumulation(True)
         assert a.context.accumulated_frames() == 0
@@ -97,16 +74,16 @@ def test_accumulating_changes_no_other_buffer(built):
     """320x180, 8 frames: an accumulating context, one that enabled and disabled before its first frame, one that never heard of it --
     G-buffer, raw images, filtered images, both TemporalSSOut, back buffer and ray count, every frame."""
     extra = ["-metallic", 0.25, 0.5]
-    a, b, c = _app(320, 180, extra), _app(320, 180, extra), _app(320, 180, extra)
+    a, b, c = G.app(320, 180, extra), G.app(320, 180, extra), G.app(320, 180, extra)
     try:
         a.context.set_accumulation(True)
         b.context.set_accumulation(True); b.context.set_accumulation(False)
         for f in range(8):
             for x in (a, b, c):
-                _frame(x)
-            ic = _images(c)
-            _assert_same(_images(a), ic, "accumulating, frame %d" % f)
-            _assert_same(_images(b), ic, "enabled and disabled, frame %d" % f)
+                G.frame(x)
+            ic = G.images(c, IMAGES)
+            G.assert_same(G.images(a, IMAGES), ic, "accumulating, frame %d" % f)
+            G.assert_same(G.images(b, IMAGES), ic, "enabled and disabled, frame %d" % f)
         assert a.context.accumulated_frames() == 8 and b.context.accumulated_frames() == 0
         assert not _sums(b)[0].any() and not _sums(b)[1].any(), "a context that never accumulated a frame holds zero sums"
     finally:
@@ -120,7 +97,7 @@ SCHED_EXTRA = ["-metallic", 1.0, 0.5]
 @pytest.fixture(scope="module")
 def synchronised_twin(built):
     """16 frames at 320x180 with a synchronising readback after each: its sums (checked against the restatement), shared by the variants."""
-    a = _app(320, 180, SCHED_EXTRA)
+    a = G.app(320, 180, SCHED_EXTRA)
     try:
         a.context.set_accumulation(True)
         acc = _restated_run(a, (1.0, 0.5), 16)
@@ -134,7 +111,7 @@ def synchronised_twin(built):
 @pytest.mark.parametrize("variant", ["small-placement", "full-size-placement", "sync-flag", "caller-stream"])
 def test_free_running_frames_accumulate_what_synchronised_ones_do(built, synchronised_twin, variant):
     import torch
-    b = _app(320, 180, SCHED_EXTRA + (["-sync"] if variant == "sync-flag" else []))
+    b = G.app(320, 180, SCHED_EXTRA + (["-sync"] if variant == "sync-flag" else []))
     stream = torch.cuda.Stream() if variant == "caller-stream" else None
     try:
         if variant == "small-placement":
@@ -145,7 +122,7 @@ def test_free_running_frames_accumulate_what_synchronised_ones_do(built, synchro
             b.context.set_stream(stream.cuda_stream)
         b.context.set_accumulation(True)
         for f in range(16):
-            _frame(b)
+            G.frame(b)
         _assert_sums(_sums(b), synchronised_twin, variant)
         if variant == "small-placement":
             assert b.context.placement(1)[1]["shade"] == "B", "small launches shade on the traversal's stream"
@@ -162,7 +139,7 @@ def test_still_sky_tiles_are_accumulated_like_any_other(built):
     """320x180, still camera, 12 frames (past the still-sky threshold: ray generation leaves the sky tiles alone, and the kernel adds the
     words they hold all the same): the restatement, and contexts with the still sky and the tile words off."""
     extra = ["-metallic", 1.0, 0.5]
-    a, b, c = _app(320, 180, extra), _app(320, 180, extra), _app(320, 180, extra)
+    a, b, c = G.app(320, 180, extra), G.app(320, 180, extra), G.app(320, 180, extra)
     try:
         b.context.static_sky(False)
         c.context.tile_words(False)
@@ -170,7 +147,7 @@ def test_still_sky_tiles_are_accumulated_like_any_other(built):
             x.context.set_accumulation(True)
         acc = AR.Accumulator(180, 320)
         for f in range(12):
-            _frame(b); _frame(c)
+            G.frame(b); G.frame(c)
             _restated_run(a, (1.0, 0.5), 1, acc)
         runs, threshold = a.context.sky_runs()
         assert (runs >= threshold).any(), "no sky tile is being left alone: the test does not test what it says"
@@ -185,12 +162,12 @@ def test_still_sky_tiles_are_accumulated_like_any_other(built):
 # ---- 5. strips ------------------------------------------------------------------------------------------------------------------------
 def test_a_strip_accumulates_its_own_rows(built):
     extra = ["-metallic", 0.25, 0.5]
-    a, b = _app(100, 54, extra), _app(100, 54, extra)
+    a, b = G.app(100, 54, extra), G.app(100, 54, extra)
     try:
         b.context.set_strip(10, 37)
         a.context.set_accumulation(True); b.context.set_accumulation(True)
         for f in range(3):
-            _frame(a); _frame(b)
+            G.frame(a); G.frame(b)
         ra, da, na = _sums(a)
         rb, db, nb = _sums(b)
         assert na == nb == 3
@@ -204,7 +181,7 @@ def test_a_strip_accumulates_its_own_rows(built):
 
 # ---- 6. control ------------------------------------------------------------------------------------------------------------------------
 def test_reset_disable_and_a_material_change_follow_the_restatement(built):
-    a = _app(100, 54)      # all metal: no diffuse path yet
+    a = G.app(100, 54)      # all metal: no diffuse path yet
     try:
         ctx = a.context
         ctx.set_accumulation(True)
@@ -212,7 +189,7 @@ def test_reset_disable_and_a_material_change_follow_the_restatement(built):
         _assert_sums(_sums(a), acc, "two frames")
         assert not acc.diff.any()
         # a reset in mid-run, enqueued behind a frame nobody has waited for
-        _frame(a); ctx.reset_accumulation()
+        G.frame(a); ctx.reset_accumulation()
         assert ctx.accumulated_frames() == 0
         acc.reset()
         _restated_run(a, (1.0, 1.0), 1, acc)
@@ -220,7 +197,7 @@ def test_reset_disable_and_a_material_change_follow_the_restatement(built):
         # off for two frames: sums and count stay
         ctx.set_accumulation(False)
         for f in range(2):
-            _frame(a)
+            G.frame(a)
         _assert_sums(_sums(a), acc, "off for two frames")
         ctx.set_accumulation(True)      # enabling does not reset
         _restated_run(a, (1.0, 1.0), 1, acc)
@@ -242,33 +219,33 @@ def test_reset_disable_and_a_material_change_follow_the_restatement(built):
 def test_present_writes_the_mean_and_its_tone_map_and_nothing_else(built):
     from raytracedggx_amd import capi
     extra, metallic = ["-metallic", 0.25, 0.5], (0.25, 0.5)
-    a, twin, fresh = _app(100, 54, extra), _app(100, 54, extra), _app(100, 54, extra)
+    a, twin, fresh = G.app(100, 54, extra), G.app(100, 54, extra), G.app(100, 54, extra)
     try:
         a.context.set_accumulation(True); twin.context.set_accumulation(True)
         acc = AR.Accumulator(54, 100)
         for f in range(3):
-            _restated_run(a, metallic, 1, acc); _frame(twin)
-        before = _images(a)
+            _restated_run(a, metallic, 1, acc); G.frame(twin)
+        before = G.images(a, IMAGES)
         a.context.present_accumulation()
         converged = a.context.readback(capi.BUF_CONVERGED)
         np.testing.assert_array_equal(converged, acc.converged(), err_msg="RTGGX_BUF_CONVERGED against the restatement")
         assert (converged >> np.uint64(48) == 0x3C00).all()      # alpha 1.0
         # the back buffer: the frame's own tone map over that image
-        _frame(fresh)
+        G.frame(fresh)
         fresh.context.upload(capi.BUF_TSS0 + fresh.context.frame_parity(), converged)
         fresh.context.tone_map()
         back = a.context.readback(capi.BUF_BACKBUFFER)
         np.testing.assert_array_equal(back, fresh.context.readback(capi.BUF_BACKBUFFER), err_msg="the presented back buffer")
         assert (back != before["back"]).any()
-        after = _images(a)
+        after = G.images(a, IMAGES)
         for k in before:
             if k != "back":
                 np.testing.assert_array_equal(after[k], before[k], err_msg="present touched " + k)
         _assert_sums(_sums(a), acc, "present leaves the sums alone")
         # the frames after it
         for f in range(3):
-            _restated_run(a, metallic, 1, acc); _frame(twin)
-            _assert_same(_images(a), _images(twin), "frame %d after the present" % f)
+            _restated_run(a, metallic, 1, acc); G.frame(twin)
+            G.assert_same(G.images(a, IMAGES), G.images(twin, IMAGES), "frame %d after the present" % f)
         _assert_sums(_sums(a), acc, "six frames")
         _assert_sums(_sums(twin), acc, "the twin's six frames")
         a.context.present_accumulation()
@@ -287,7 +264,7 @@ def test_save_converged_writes_the_tone_mapped_mean_and_reports_it(built, tmp_pa
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
     import imgdiff
     extra, metallic = ["-metallic", 0.25, 0.5], (0.25, 0.5)
-    a, fresh = _app(100, 54, extra + ["-accumulate", 4]), _app(100, 54, extra)
+    a, fresh = G.app(100, 54, extra + ["-accumulate", 4]), G.app(100, 54, extra)
     try:
         acc = _restated_run(a, metallic, 3)
         path = str(tmp_path / "still_converged.png")
@@ -298,7 +275,7 @@ def test_save_converged_writes_the_tone_mapped_mean_and_reports_it(built, tmp_pa
         assert m and 0.0 < float(m.group(1)) < 10.0 and 0.0 < float(m.group(2)) < 10.0, out
         converged = a.context.readback(capi.BUF_CONVERGED)
         np.testing.assert_array_equal(converged, acc.converged())
-        _frame(fresh)
+        G.frame(fresh)
         fresh.context.upload(capi.BUF_TSS0 + fresh.context.frame_parity(), converged)
         fresh.context.tone_map()
         back = fresh.context.readback(capi.BUF_BACKBUFFER)
@@ -306,9 +283,9 @@ def test_save_converged_writes_the_tone_mapped_mean_and_reports_it(built, tmp_pa
         _assert_sums(_sums(a), acc, "after SaveConverged")
     finally:
         a.OnDestroy(); fresh.OnDestroy()
-    b = _app(100, 54)      # nothing accumulated: refused, no file
+    b = G.app(100, 54)      # nothing accumulated: refused, no file
     try:
-        _frame(b)
+        G.frame(b)
         assert not b.save_converged(str(tmp_path / "none.png")) and not os.path.exists(str(tmp_path / "none.png"))
     finally:
         b.OnDestroy()
@@ -318,7 +295,7 @@ def test_non_finite_words_add_as_they_are(built):
     """An environment of +infinity: every background word, and the word of every reflection ray that misses, carries the exponent-31 code.
     The sums take them as the restatement does (infinity, and NaN where 0 x infinity arose; a NaN's payload is not compared)."""
     from raytracedggx_amd import capi
-    a = _app(100, 54, mesh="triangle.obj")
+    a = G.app(100, 54, mesh="triangle.obj")
     try:
         a.context.set_env(capi.FORMAT_RGBA16F, 1, 1, assets.constant_env_rgba16f(np.inf))
         a.context.set_accumulation(True)
@@ -336,7 +313,7 @@ def test_refusals_leave_the_context_rendering_the_same_frames(built):
     from raytracedggx_amd import capi
     new_buffers = (capi.BUF_ACC_REFL, capi.BUF_ACC_DIFF, capi.BUF_CONVERGED)
     # rate 4 on an accumulating context; present at n = 0; the new buffers before the first enable
-    a, twin = _app(320, 180, ["-metallic", 1.0, 0.5]), _app(320, 180, ["-metallic", 1.0, 0.5])
+    a, twin = G.app(320, 180, ["-metallic", 1.0, 0.5]), G.app(320, 180, ["-metallic", 1.0, 0.5])
     try:
         for bid in new_buffers:
             for call in (a.context.readback, a.context.buffer_size, a.context.buffer_ptr):
@@ -350,36 +327,36 @@ def test_refusals_leave_the_context_rendering_the_same_frames(built):
         for f in range(3):
             with pytest.raises(capi.RtggxError, match="rtggx_set_ray_rate"):
                 a.context.set_ray_rate(4)
-            _frame(a); _frame(twin)
-            _assert_same(_images(a), _images(twin), "accumulating, rate 4 refused, frame %d" % f)
+            G.frame(a); G.frame(twin)
+            G.assert_same(G.images(a, IMAGES), G.images(twin, IMAGES), "accumulating, rate 4 refused, frame %d" % f)
         _assert_sums(_sums(a), _sums(twin), "accumulating, rate 4 refused")
         assert a.context.buffer_size(capi.BUF_ACC_REFL) == 320 * 180 * 16 and a.context.buffer_size(capi.BUF_CONVERGED) == 320 * 180 * 8
         assert a.context.buffer_ptr(capi.BUF_ACC_DIFF) != 0
     finally:
         a.OnDestroy(); twin.OnDestroy()
     # accumulation on a rate-4 context
-    a, twin = _app(320, 180, ["-rayrate", 4]), _app(320, 180, ["-rayrate", 4])
+    a, twin = G.app(320, 180, ["-rayrate", 4]), G.app(320, 180, ["-rayrate", 4])
     try:
         for f in range(3):
             with pytest.raises(capi.RtggxError, match="rtggx_set_accumulation"):
                 a.context.set_accumulation(True)
-            _frame(a); _frame(twin)
-            _assert_same(_images(a), _images(twin), "rate 4, accumulation refused, frame %d" % f)
+            G.frame(a); G.frame(twin)
+            G.assert_same(G.images(a, IMAGES), G.images(twin, IMAGES), "rate 4, accumulation refused, frame %d" % f)
         assert a.context.accumulated_frames() == 0
         with pytest.raises(capi.RtggxError):
             a.context.readback(capi.BUF_ACC_REFL)      # the refused enable allocated nothing
     finally:
         a.OnDestroy(); twin.OnDestroy()
     # present on a strip
-    a, twin = _app(100, 54), _app(100, 54)
+    a, twin = G.app(100, 54), G.app(100, 54)
     try:
         for x in (a, twin):
             x.context.set_strip(10, 37); x.context.set_accumulation(True)
         for f in range(2):
-            _frame(a); _frame(twin)
+            G.frame(a); G.frame(twin)
             with pytest.raises(capi.RtggxError, match="rtggx_present_accumulation"):
                 a.context.present_accumulation()
-            ia, it = _images(a), _images(twin)
+            ia, it = G.images(a, IMAGES), G.images(twin, IMAGES)
             for k in ("refl", "diff", "tss0", "tss1", "back"):
                 np.testing.assert_array_equal(ia[k][10:37], it[k][10:37], err_msg="strip, present refused, frame %d: %s" % (f, k))
         _assert_sums(_sums(a), _sums(twin), "strip, present refused")

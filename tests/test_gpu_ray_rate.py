@@ -4,86 +4,19 @@ pinned to its numpy restatement (tests/ray_rate_ref.py); the denoiser pinned to 
 import numpy as np
 import pytest
 
-import assets
+import gpu_support as G
 import ray_rate_ref as R
+from gpu_support import Pair, check_quad_frame, quad_frame, rel_l2
 from oracle import oracle as O
-from test_gpu_parity import Pair, rel_l2
 
 pytestmark = pytest.mark.gpu
 
-FRAME_INDEX_OFFSET = 444      # RtggxCBGlobal::FrameIndex in the 768-byte frame constants
-
-
-def _frame_index(app):
-    return int(app.frame_constants()[FRAME_INDEX_OFFSET:FRAME_INDEX_OFFSET + 4].view(np.uint32)[0])
-
-
-def _app(W, H, extra=(), mesh="bunny.obj"):
-    from raytracedggx_amd import app
-    return app.RayTracedGGX(["-mesh", assets.path(mesh), "-env", assets.path("rnl_cross.dds"), "-width", W, "-height", H] + list(extra))
-
-
-def _gbuffer(ctx):
-    c = ctx_capi()
-    return {n: ctx.readback(b) for n, b in (("vis", c.BUF_VISIBILITY), ("depth", c.BUF_DEPTH), ("normal", c.BUF_NORMAL),
-                                             ("rm", c.BUF_ROUGH_METAL), ("velocity", c.BUF_VELOCITY))}
+IMAGES = G.RAW + G.DENOISED      # what this module's twins are compared in
 
 
 def ctx_capi():
     from raytracedggx_amd import capi
     return capi
-
-
-def quad_frame(p, give_oracle_raw=True):
-    """One frame of a rate-4 Pair: the product's frame, the oracle's full-rate frame up to its raw images (returned), which are then
-    replaced by the product's reconstructed ones before the oracle denoises and tone-maps."""
-    capi, ctx, o = p.capi, p.ctx, p.o
-    p.app.OnUpdate(); p.app.OnRender(); ctx.sync()
-    o.set_frame_constants(p.app.frame_constants().tobytes()[:704] + o.get_frame_constants().tobytes()[704:])
-    o.update_as(); o.render_visibility(); p.rays = o.ray_trace()
-    full = {"refl": o.buffer(O.BUF_RT_REFL), "diff": o.buffer(O.BUF_RT_DIFF)}
-    if give_oracle_raw:
-        o.buffer(O.BUF_RT_REFL, copy=False)[...] = ctx.readback(capi.BUF_RT_REFL)
-        o.buffer(O.BUF_RT_DIFF, copy=False)[...] = ctx.readback(capi.BUF_RT_DIFF)
-    o.denoise(); o.tone_map()
-    return full
-
-
-def check_quad_frame(p, full, label, prev_diff=None):
-    """Test 1 and 2 on one rate-4 frame: G-buffer bit-exact everywhere; raw images bit-exact at traced (where a ray of that kind is
-    traced) and background pixels; ray count a quarter; the untraced covered pixels equal their restatement to one code on <= 0.1 %;
-    carried-over RayTracingOut1 equal to the previous frame's."""
-    capi, ctx, o = p.capi, p.ctx, p.o
-    g = _gbuffer(ctx)
-    for name, oid in (("vis", O.BUF_VISIBILITY), ("depth", O.BUF_DEPTH), ("normal", O.BUF_NORMAL), ("rm", O.BUF_ROUGH_METAL), ("velocity", O.BUF_VELOCITY)):
-        np.testing.assert_array_equal(g[name], o.buffer(oid), err_msg="%s: %s not bit-exact" % (label, name))
-    H, W = g["vis"].shape
-    fi = _frame_index(p.app)
-    traced = R.traced_mask(W, H, fi)
-    covered = g["vis"] != 0
-    metal = (g["rm"] >> 8) >= 255
-    refl, diff = ctx.readback(capi.BUF_RT_REFL), ctx.readback(capi.BUF_RT_DIFF)
-    rays = ctx.ray_count()
-    assert 0.2 * p.rays <= rays <= 0.3 * p.rays, "%s: %d rays against %d at full rate" % (label, rays, p.rays)
-    at = traced | ~covered
-    np.testing.assert_array_equal(refl[at], full["refl"][at], err_msg="%s: RayTracingOut0 at traced / background pixels" % label)
-    at_d = (traced & covered & ~metal) | ~covered
-    np.testing.assert_array_equal(diff[at_d], full["diff"][at_d], err_msg="%s: RayTracingOut1 at traced / background pixels" % label)
-    inst = np.where(covered, (g["vis"].astype(np.int64) - 1) >> 24, -1)
-    diffuse_instances = sorted(set(inst[covered & ~metal].tolist()))
-    er, ed, target, dif = R.reconstruct(g["vis"], g["depth"], g["normal"], g["rm"], refl, diff, fi, diffuse_instances)
-    assert target.sum() > 0
-    for name, got, want, mask in (("RayTracingOut0", refl, er, target), ("RayTracingOut1", diff, ed, dif)):
-        if not mask.any():
-            continue
-        a, b = got[mask].astype(np.int64), want[mask].astype(np.int64)
-        d = np.stack([np.abs((a & 0x7FF) - (b & 0x7FF)), np.abs(((a >> 11) & 0x7FF) - ((b >> 11) & 0x7FF)), np.abs((a >> 22) - (b >> 22))])
-        assert d.max() <= 1 and (d.max(axis=0) > 0).mean() <= 1e-3, "%s: reconstructed %s: %d of %d pixels differ, by up to %d codes" % (
-            label, name, int((d.max(axis=0) > 0).sum()), a.size, int(d.max()))
-    if prev_diff is not None:
-        carry = covered & metal
-        np.testing.assert_array_equal(diff[carry], prev_diff[carry], err_msg="%s: RayTracingOut1 carried over" % label)
-    return diff
 
 
 def check_denoised(p, label):
@@ -137,28 +70,15 @@ def test_denoise_chain_on_quarter_rate_input(built, W, H, metallic, shared_mem):
         p.close()
 
 
-def _images(app):
-    capi, ctx = ctx_capi(), app.context
-    ctx.sync()
-    return {n: ctx.readback(b) for n, b in (("refl", capi.BUF_RT_REFL), ("diff", capi.BUF_RT_DIFF), ("flt_rfl", capi.BUF_FLT_RFL),
-                                             ("flt_dff", capi.BUF_FLT_DFF), ("tss0", capi.BUF_TSS0), ("tss1", capi.BUF_TSS0 + 1),
-                                             ("back", capi.BUF_BACKBUFFER))}
-
-
-def _assert_same(a, b, label):
-    for k in a:
-        np.testing.assert_array_equal(a[k], b[k], err_msg="%s: %s differs" % (label, k))
-
-
 @pytest.mark.parametrize("W,H", [(1920, 1080), (256, 144)], ids=["1080p", "256x144-small-launch"])
 def test_free_running_frames_equal_synchronised_ones(built, W, H):
     extra = ["-rayrate", 4, "-metallic", 1.0, 0.5]
-    a, b = _app(W, H, extra), _app(W, H, extra)
+    a, b = G.app(W, H, extra), G.app(W, H, extra)
     try:
         for f in range(30):
             a.OnUpdate(); a.OnRender()
             b.OnUpdate(); b.OnRender(); b.context.sync()
-        _assert_same(_images(a), _images(b), "%dx%d after 30 frames" % (W, H))
+        G.assert_same(G.images(a, IMAGES), G.images(b, IMAGES), "%dx%d after 30 frames" % (W, H))
         if W == 256:
             assert a.context.placement()[0]["small"], "the small-launch placement"
     finally:
@@ -167,11 +87,11 @@ def test_free_running_frames_equal_synchronised_ones(built, W, H):
 
 def test_async_compute_off_equals_on(built):
     extra = ["-rayrate", 4, "-metallic", 1.0, 0.5]
-    a, b = _app(640, 360, extra), _app(640, 360, extra + ["-sync"])
+    a, b = G.app(640, 360, extra), G.app(640, 360, extra + ["-sync"])
     try:
         for f in range(8):
             a.OnUpdate(); a.OnRender(); b.OnUpdate(); b.OnRender()
-            _assert_same(_images(a), _images(b), "frame %d" % f)
+            G.assert_same(G.images(a, IMAGES), G.images(b, IMAGES), "frame %d" % f)
     finally:
         a.OnDestroy(); b.OnDestroy()
 
@@ -179,14 +99,14 @@ def test_async_compute_off_equals_on(built):
 def test_deforming_mesh_at_rate_4_equals_rate_1_at_traced_pixels(built):
     capi = ctx_capi()
     extra = ["-deform", 0.3, "-metallic", 0.25, 0.5]
-    a, b = _app(640, 360, extra + ["-rayrate", 4]), _app(640, 360, extra)
+    a, b = G.app(640, 360, extra + ["-rayrate", 4]), G.app(640, 360, extra)
     try:
         for f in range(6):
             a.OnUpdate(); a.OnRender(); a.context.sync(); b.OnUpdate(); b.OnRender(); b.context.sync()
-            ga, gb = _gbuffer(a.context), _gbuffer(b.context)
+            ga, gb = G.gbuffer(a.context), G.gbuffer(b.context)
             for k in ga:
                 np.testing.assert_array_equal(ga[k], gb[k], err_msg="frame %d: %s" % (f, k))
-            traced = R.traced_mask(640, 360, _frame_index(a)) | (ga["vis"] == 0)
+            traced = R.traced_mask(640, 360, G.frame_index(a)) | (ga["vis"] == 0)
             for bid in (capi.BUF_RT_REFL, capi.BUF_RT_DIFF):
                 np.testing.assert_array_equal(a.context.readback(bid)[traced], b.context.readback(bid)[traced], err_msg="frame %d: buffer %d" % (f, bid))
     finally:
@@ -205,7 +125,7 @@ def test_switching_rate_between_frames(built, tile_words):
                 label = "rate %d frame %d" % (rate, f)
                 if rate == 1:
                     full = quad_frame(p, give_oracle_raw=False)
-                    g = _gbuffer(p.ctx)
+                    g = G.gbuffer(p.ctx)
                     for name, oid in (("vis", O.BUF_VISIBILITY), ("depth", O.BUF_DEPTH), ("normal", O.BUF_NORMAL), ("rm", O.BUF_ROUGH_METAL), ("velocity", O.BUF_VELOCITY)):
                         np.testing.assert_array_equal(g[name], p.o.buffer(oid), err_msg="%s: %s" % (label, name))
                     np.testing.assert_array_equal(p.ctx.readback(p.capi.BUF_RT_REFL), full["refl"], err_msg=label)
@@ -227,7 +147,7 @@ CONVERGENCE_BAR = 0.15
 
 def test_static_scene_converges_towards_the_full_rate_image(built):
     capi = ctx_capi()
-    a, b, v = _app(640, 360, ["-dt", 0, "-rayrate", 4]), _app(640, 360, ["-dt", 0]), _app(640, 360, ["-dt", 0, "-vndf"])
+    a, b, v = G.app(640, 360, ["-dt", 0, "-rayrate", 4]), G.app(640, 360, ["-dt", 0]), G.app(640, 360, ["-dt", 0, "-vndf"])
     try:
         for f in range(32):
             for x in (a, b, v):
@@ -273,14 +193,14 @@ def test_refusals(built):
     finally:
         c.close()
     # rate 1 on a strip still renders, and -rayrate 4 through the host layer refuses a strip
-    a = _app(320, 180)
+    a = G.app(320, 180)
     try:
         a.context.set_strip(0, 90)
         a.OnUpdate(); a.OnRender(); a.context.sync()
         assert a.context.ray_count() > 0
     finally:
         a.OnDestroy()
-    a = _app(320, 180, ["-rayrate", 4])
+    a = G.app(320, 180, ["-rayrate", 4])
     try:
         with pytest.raises(capi.RtggxError, match="rtggx_set_strip"):
             a.context.set_strip(0, 90)

@@ -6,61 +6,18 @@ import numpy as np
 import pytest
 
 import assets
-import recursion_ref as RR
-import test_gpu_parity as GP
-import test_gpu_ray_rate as QR
+import gpu_support as G
+from gpu_support import check_raw
 from oracle import oracle as O
-from test_gpu_parity import Pair
 
 pytestmark = pytest.mark.gpu
 
-def depth_pair(W, H, depth, mesh="bunny.obj", metallic=None, vndf=False, shared_mem=False):
-    """test_gpu_parity.Pair with the restatement as its oracle, both at `depth`."""
-    orig = GP.O.Oracle
-    GP.O.Oracle = lambda w, h: RR.Oracle(w, h, depth=depth)
-    try:
-        p = Pair(W, H, mesh=mesh, metallic=metallic, shared_mem=shared_mem)
-    finally:
-        GP.O.Oracle = orig
-    p.ctx.set_max_recursion_depth(depth)
-    if vndf:
-        p.ctx.set_sampler(True); p.o.set_sampler(True)
-    return p
+FRAME_WORDS = G.GBUFFER_MIN + G.RAW      # the frame's own words: what a strip, or a context with another history, shares with its twin
+IMAGES = FRAME_WORDS + G.DENOISED
 
 
 def set_depth(p, depth):
     p.ctx.set_max_recursion_depth(depth); p.o.set_max_recursion_depth(depth)
-
-
-def check_raw(p, label):
-    """G-buffer words, RayTracingOut0/1 and the ray count: bit for bit / equal."""
-    capi, ctx, o = p.capi, p.ctx, p.o
-    for name, gid, oid in (("visibility", capi.BUF_VISIBILITY, O.BUF_VISIBILITY), ("depth", capi.BUF_DEPTH, O.BUF_DEPTH),
-                           ("normal", capi.BUF_NORMAL, O.BUF_NORMAL), ("roughMetal", capi.BUF_ROUGH_METAL, O.BUF_ROUGH_METAL),
-                           ("velocity", capi.BUF_VELOCITY, O.BUF_VELOCITY), ("rt_refl", capi.BUF_RT_REFL, O.BUF_RT_REFL),
-                           ("rt_diff", capi.BUF_RT_DIFF, O.BUF_RT_DIFF)):
-        np.testing.assert_array_equal(ctx.readback(gid), o.buffer(oid), err_msg="%s: %s not bit-exact" % (label, name))
-    assert ctx.ray_count() == p.rays, "%s: ray count %d, restatement %d" % (label, ctx.ray_count(), p.rays)
-
-
-def _images(app, with_denoised=True):
-    from raytracedggx_amd import capi
-    ctx = app.context
-    ctx.sync()
-    ids = [("vis", capi.BUF_VISIBILITY), ("normal", capi.BUF_NORMAL), ("rm", capi.BUF_ROUGH_METAL), ("refl", capi.BUF_RT_REFL), ("diff", capi.BUF_RT_DIFF)]
-    if with_denoised:
-        ids += [("flt_rfl", capi.BUF_FLT_RFL), ("flt_dff", capi.BUF_FLT_DFF), ("tss0", capi.BUF_TSS0), ("tss1", capi.BUF_TSS0 + 1), ("back", capi.BUF_BACKBUFFER)]
-    return {n: ctx.readback(b) for n, b in ids}
-
-
-def _assert_same(a, b, label):
-    for k in a:
-        np.testing.assert_array_equal(a[k], b[k], err_msg="%s: %s differs" % (label, k))
-
-
-def _app(W, H, extra=(), mesh="bunny.obj"):
-    from raytracedggx_amd import app
-    return app.RayTracedGGX(["-mesh", assets.path(mesh), "-env", assets.path("rnl_cross.dds"), "-width", W, "-height", H] + list(extra))
 
 
 @pytest.mark.parametrize("vndf", [False, True], ids=["ndf", "vndf"])
@@ -69,7 +26,7 @@ def _app(W, H, extra=(), mesh="bunny.obj"):
 def test_depth_2_and_3_equal_the_restatement(built, mesh, metallic, vndf):
     """Three frames at depth 2, then three at depth 3, on one context: raw images and G-buffer bit-exact, the ray count equal, the denoised
     HDR within 1e-3 of the oracle's denoiser fed the restatement's raw images (test_gpu_parity's check_frame)."""
-    p = depth_pair(320, 180, 2, mesh=mesh, metallic=metallic, vndf=vndf)
+    p = G.restated_pair(320, 180, depth=2, entry="depth", mesh=mesh, metallic=metallic, vndf=vndf)
     try:
         rays = {}
         for depth in (2, 3):
@@ -83,7 +40,7 @@ def test_depth_2_and_3_equal_the_restatement(built, mesh, metallic, vndf):
 
 
 def test_full_size_frame_at_depth_2(built):
-    p = depth_pair(1920, 1080, 2)
+    p = G.restated_pair(1920, 1080, depth=2, entry="depth")
     try:
         p.frame(); check_raw(p, "1080p bunny depth 2")
     finally:
@@ -93,8 +50,8 @@ def test_full_size_frame_at_depth_2(built):
 def test_depth_4_and_back_to_1(built):
     """Depth 4 against the restatement, then depth 3 and back to 1: a context that went to depth 3 and returned renders the frames of one
     that never left depth 1 (raw images bit-identical, and the ray count), and depth 1 is the oracle's."""
-    p = depth_pair(320, 180, 4, metallic=(0.25, 0.5))
-    b = _app(320, 180, ["-metallic", 0.25, 0.5])
+    p = G.restated_pair(320, 180, depth=4, entry="depth", metallic=(0.25, 0.5))
+    b = G.app(320, 180, ["-metallic", 0.25, 0.5])
     try:
         p.frame(); check_raw(p, "depth 4")
         b.OnUpdate(); b.OnRender()
@@ -106,7 +63,7 @@ def test_depth_4_and_back_to_1(built):
         for f in range(3):
             p.frame(); check_raw(p, "back at depth 1, frame %d" % f)
             b.OnUpdate(); b.OnRender()
-            _assert_same(_images(p.app, with_denoised=False), _images(b, with_denoised=False), "back at depth 1, frame %d" % f)
+            G.assert_same(G.images(p.app, FRAME_WORDS), G.images(b, FRAME_WORDS), "back at depth 1, frame %d" % f)
             assert p.ctx.ray_count() == b.context.ray_count()
         # the oracle's own depth-1 renderer on the same frame
         p.o.ray_trace_depth1_oracle()
@@ -119,14 +76,14 @@ def test_depth_4_and_back_to_1(built):
 @pytest.mark.parametrize("W,H,force_small", [(640, 360, 0), (640, 360, 1), (1920, 1080, -1)], ids=["640x360-full-size-placement", "640x360-small-placement", "1080p"])
 def test_free_running_frames_equal_synchronised_ones(built, W, H, force_small):
     extra = ["-recursion", 2, "-metallic", 1.0, 0.5]
-    a, b = _app(W, H, extra), _app(W, H, extra)
+    a, b = G.app(W, H, extra), G.app(W, H, extra)
     try:
         for x in (a, b):
             x.context.placement(force_small)
         for f in range(16):
             a.OnUpdate(); a.OnRender(); a.context.sync()
             b.OnUpdate(); b.OnRender()
-        _assert_same(_images(a), _images(b), "%dx%d placement %d after 16 frames" % (W, H, force_small))
+        G.assert_same(G.images(a, IMAGES), G.images(b, IMAGES), "%dx%d placement %d after 16 frames" % (W, H, force_small))
         assert a.context.ray_count() == b.context.ray_count()
         if force_small == 1:
             assert a.context.placement(1)[1]["shade"] == "B", "small launches shade (and trace the later levels) on the traversal's stream"
@@ -137,7 +94,7 @@ def test_free_running_frames_equal_synchronised_ones(built, W, H, force_small):
 def test_async_compute_off_and_caller_owned_stream_change_nothing(built):
     import torch
     extra = ["-recursion", 2, "-metallic", 1.0, 0.5]
-    a, b, c = _app(640, 360, extra), _app(640, 360, extra + ["-sync"]), _app(640, 360, extra)
+    a, b, c = G.app(640, 360, extra), G.app(640, 360, extra + ["-sync"]), G.app(640, 360, extra)
     stream = torch.cuda.Stream()
     try:
         c.context.set_stream(stream.cuda_stream)
@@ -145,33 +102,33 @@ def test_async_compute_off_and_caller_owned_stream_change_nothing(built):
             for x in (a, b, c):
                 x.OnUpdate(); x.OnRender()
         torch.cuda.synchronize()
-        ia = _images(a)
-        _assert_same(ia, _images(b), "async compute off")
-        _assert_same(ia, _images(c), "caller-owned stream")
+        ia = G.images(a, IMAGES)
+        G.assert_same(ia, G.images(b, IMAGES), "async compute off")
+        G.assert_same(ia, G.images(c, IMAGES), "caller-owned stream")
     finally:
         a.OnDestroy(); b.OnDestroy(); c.OnDestroy()
 
 
 def test_quarter_rate_at_depth_2(built):
     """Rate 4 at depth 2: traced pixels equal the full-rate depth-2 frame (the restatement), the reconstructed ones their restatement."""
-    p = depth_pair(640, 360, 2, metallic=(1.0, 0.5))
+    p = G.restated_pair(640, 360, depth=2, entry="depth", metallic=(1.0, 0.5))
     try:
         p.ctx.set_ray_rate(4)
         prev = None
         for f in range(4):
-            full = QR.quad_frame(p)
-            prev = QR.check_quad_frame(p, full, "rate 4 depth 2 frame %d" % f, prev)
+            full = G.quad_frame(p)
+            prev = G.check_quad_frame(p, full, "rate 4 depth 2 frame %d" % f, prev)
     finally:
         p.close()
 
 
 def test_strip_rows_equal_the_full_frame(built):
-    a, b = _app(640, 360, ["-recursion", 3, "-metallic", 0.25, 0.5]), _app(640, 360, ["-recursion", 3, "-metallic", 0.25, 0.5])
+    a, b = G.app(640, 360, ["-recursion", 3, "-metallic", 0.25, 0.5]), G.app(640, 360, ["-recursion", 3, "-metallic", 0.25, 0.5])
     try:
         b.context.set_strip(100, 260)
         for f in range(3):
             a.OnUpdate(); a.OnRender(); b.OnUpdate(); b.OnRender()
-            ia, ib = _images(a, with_denoised=False), _images(b, with_denoised=False)
+            ia, ib = G.images(a, FRAME_WORDS), G.images(b, FRAME_WORDS)
             for k in ia:
                 np.testing.assert_array_equal(ia[k][100:260], ib[k][100:260], err_msg="frame %d: %s" % (f, k))
     finally:
@@ -179,16 +136,16 @@ def test_strip_rows_equal_the_full_frame(built):
 
 
 def test_strips_through_rccl_at_depth_2(built):
-    GP._strips_through_rccl_equal_the_full_frame(480, 272, 2, False, 3, extra=("-recursion", "2"))
+    G.strips_through_rccl_equal_the_full_frame(480, 272, 2, False, 3, extra=("-recursion", "2"))
 
 
 def test_deforming_mesh_at_depth_2(built):
     """One frame of a refitted (deformed) model at depth 2 against the restatement given the refitted tree."""
-    p = depth_pair(320, 180, 2, metallic=(1.0, 0.5))
+    p = G.restated_pair(320, 180, depth=2, entry="depth", metallic=(1.0, 0.5))
     try:
         p.frame(); check_raw(p, "before the deformation")
         v0, idx, _ = O.obj_import(assets.path("bunny.obj"))
-        v = GP._wave(v0, 1)
+        v = G.wave(v0, 1)
         p.ctx.refit_as(1, v)
         p.app.OnUpdate(); p.app.OnRender(); p.ctx.sync()
         p.o.set_mesh(1, v, idx)
@@ -202,7 +159,7 @@ def test_deforming_mesh_at_depth_2(built):
 
 
 def test_refusals_leave_the_depth_unchanged(built):
-    capi = QR.ctx_capi()
+    from raytracedggx_amd import capi
     c = capi.Context(64, 64)
     try:
         for bad in (0, 5, 100, 2 ** 32 - 1):
@@ -212,14 +169,14 @@ def test_refusals_leave_the_depth_unchanged(built):
             c.set_max_recursion_depth(good)
     finally:
         c.close()
-    a, b = _app(320, 180, ["-recursion", 2, "-metallic", 1.0, 0.5]), _app(320, 180, ["-recursion", 2, "-metallic", 1.0, 0.5])
+    a, b = G.app(320, 180, ["-recursion", 2, "-metallic", 1.0, 0.5]), G.app(320, 180, ["-recursion", 2, "-metallic", 1.0, 0.5])
     try:
         for f in range(2):
             for bad in (0, 5):
                 with pytest.raises(capi.RtggxError):
                     a.context.set_max_recursion_depth(bad)
             a.OnUpdate(); a.OnRender(); b.OnUpdate(); b.OnRender()
-            _assert_same(_images(a), _images(b), "frame %d" % f)
+            G.assert_same(G.images(a, IMAGES), G.images(b, IMAGES), "frame %d" % f)
             assert a.context.ray_count() == b.context.ray_count()
     finally:
         a.OnDestroy(); b.OnDestroy()

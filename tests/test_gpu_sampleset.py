@@ -7,46 +7,15 @@ import numpy as np
 import pytest
 
 import accum_ref as AR
-import assets
+import gpu_support as G
 import ray_rate_ref as R
-import sampleset_ref as MR
-import test_gpu_parity as GP
-from oracle import oracle as O
-from test_gpu_parity import Pair
+from gpu_support import FRAME_INDEX_OFFSET
 
 pytestmark = pytest.mark.gpu
 
-FRAME_INDEX_OFFSET = 444      # RtggxCBGlobal::FrameIndex in the 768-byte frame constants: word 111
 W, H = 100, 54
-
-
-def sampleset_pair(width, height, sample_set, samples=1, depth=1, mesh="bunny.obj", metallic=None, vndf=False):
-    """test_gpu_parity.Pair with the restatement as its oracle, both at `sample_set`, `samples` and `depth`."""
-    orig = GP.O.Oracle
-    GP.O.Oracle = lambda w, h: MR.Oracle(w, h, depth=depth, samples=samples, sample_set=sample_set)
-    try:
-        p = Pair(width, height, mesh=mesh, metallic=metallic)
-    finally:
-        GP.O.Oracle = orig
-    p.ctx.set_sample_set(sample_set)
-    if samples != 1:
-        p.ctx.set_samples_per_pixel(samples)
-    if depth != 1:
-        p.ctx.set_max_recursion_depth(depth)
-    if vndf:
-        p.ctx.set_sampler(True); p.o.set_sampler(True)
-    return p
-
-
-def check_raw(p, label):
-    """G-buffer words, RayTracingOut0/1 and the ray count: bit for bit / equal."""
-    capi, ctx, o = p.capi, p.ctx, p.o
-    for name, gid, oid in (("visibility", capi.BUF_VISIBILITY, O.BUF_VISIBILITY), ("depth", capi.BUF_DEPTH, O.BUF_DEPTH),
-                           ("normal", capi.BUF_NORMAL, O.BUF_NORMAL), ("roughMetal", capi.BUF_ROUGH_METAL, O.BUF_ROUGH_METAL),
-                           ("velocity", capi.BUF_VELOCITY, O.BUF_VELOCITY), ("rt_refl", capi.BUF_RT_REFL, O.BUF_RT_REFL),
-                           ("rt_diff", capi.BUF_RT_DIFF, O.BUF_RT_DIFF)):
-        np.testing.assert_array_equal(ctx.readback(gid), o.buffer(oid), err_msg="%s: %s not bit-exact" % (label, name))
-    assert ctx.ray_count() == p.rays > 0, "%s: ray count %d, restatement %d" % (label, ctx.ray_count(), p.rays)
+FRAME_WORDS = G.GBUFFER + G.RAW + G.RAYS
+IMAGES = G.GBUFFER + G.RAW + G.DENOISED + G.RAYS
 
 
 def frame_at_index(p, index):
@@ -60,37 +29,6 @@ def frame_at_index(p, index):
     p.o.update_as(); p.o.render_visibility(); p.rays = p.o.ray_trace()
 
 
-def _app(width, height, extra=(), mesh="bunny.obj"):
-    from raytracedggx_amd import app
-    return app.RayTracedGGX(["-mesh", assets.path(mesh), "-env", assets.path("rnl_cross.dds"), "-width", width, "-height", height] + list(extra))
-
-
-def _frame(a):
-    a.OnUpdate(); a.OnRender()
-
-
-def _frame_index(a):
-    return int(a.frame_constants()[FRAME_INDEX_OFFSET:FRAME_INDEX_OFFSET + 4].view(np.uint32)[0])
-
-
-def _images(a, denoised=True):
-    from raytracedggx_amd import capi
-    c = a.context
-    c.sync()
-    ids = [("vis", capi.BUF_VISIBILITY), ("depth", capi.BUF_DEPTH), ("normal", capi.BUF_NORMAL), ("rm", capi.BUF_ROUGH_METAL), ("velocity", capi.BUF_VELOCITY),
-           ("refl", capi.BUF_RT_REFL), ("diff", capi.BUF_RT_DIFF)]
-    if denoised:
-        ids += [("flt_rfl", capi.BUF_FLT_RFL), ("flt_dff", capi.BUF_FLT_DFF), ("tss0", capi.BUF_TSS0), ("tss1", capi.BUF_TSS1), ("back", capi.BUF_BACKBUFFER)]
-    out = {n: c.readback(b) for n, b in ids}
-    out["rays"] = np.array([c.ray_count()])
-    return out
-
-
-def _assert_same(a, b, label):
-    for k in a:
-        np.testing.assert_array_equal(a[k], b[k], err_msg="%s: %s differs" % (label, k))
-
-
 # ---- 1. raw frames -------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("sample_set", [1024, 65536])
 @pytest.mark.parametrize("vndf", [False, True], ids=["ndf", "vndf"])
@@ -98,11 +36,11 @@ def _assert_same(a, b, label):
 def test_raw_frames_equal_the_restatement(built, metallic, vndf, sample_set):
     """Bunny at 100x54, FrameIndex 0, 255, 256 and M - 1 patched into the constants: G-buffer, both raw images and the ray count.  At
     M = 1024 three quarters of the pixels draw a slot beyond the 256-entry table, at 65536 all but 0.4 %."""
-    p = sampleset_pair(W, H, sample_set, metallic=metallic, vndf=vndf)
+    p = G.restated_pair(W, H, sample_set=sample_set, entry="sampleset", metallic=metallic, vndf=vndf)
     try:
         for index in (0, 255, 256, sample_set - 1):
             frame_at_index(p, index)
-            check_raw(p, "M = %d index %d" % (sample_set, index))
+            G.check_raw(p, "M = %d index %d" % (sample_set, index), require_rays=True)
     finally:
         p.close()
 
@@ -111,10 +49,10 @@ def test_raw_frames_equal_the_restatement(built, metallic, vndf, sample_set):
 @pytest.mark.parametrize("mesh,samples,depth,vndf,metallic", [("bunny.obj", 4, 2, True, (0.25, 0.5)), ("bunny.obj", 8, 1, False, None), ("dragon.obj", 2, 1, False, None)],
                          ids=["spp4-depth2-vndf-diffuse", "spp8", "dragon-spp2"])
 def test_samples_and_depth_at_4096(built, mesh, samples, depth, vndf, metallic):
-    p = sampleset_pair(W, H, 4096, samples=samples, depth=depth, mesh=mesh, metallic=metallic, vndf=vndf)
+    p = G.restated_pair(W, H, sample_set=4096, entry="sampleset", samples=samples, depth=depth, mesh=mesh, metallic=metallic, vndf=vndf)
     try:
         for f in range(2):
-            p.frame(); check_raw(p, "%s M = 4096 N = %d depth %d frame %d" % (mesh, samples, depth, f))
+            p.frame(); G.check_raw(p, "%s M = 4096 N = %d depth %d frame %d" % (mesh, samples, depth, f), require_rays=True)
     finally:
         p.close()
 
@@ -123,14 +61,14 @@ def test_quarter_rate_at_4096_traces_the_full_rate_twins_pixels(built):
     """-rayrate 4 at M = 4096: the traced pixels' words are those of a rate-1 twin at the same M, the G-buffer is the twin's everywhere, and
     the rays are those of the traced covered pixels (one each: all metal)."""
     from raytracedggx_amd import capi
-    a, b = _app(W, H, ["-sampleset", 4096, "-rayrate", 4]), _app(W, H, ["-sampleset", 4096])
+    a, b = G.app(W, H, ["-sampleset", 4096, "-rayrate", 4]), G.app(W, H, ["-sampleset", 4096])
     try:
         for f in range(5):      # (every phase of FrameIndex & 3, and the first again)
-            _frame(a); _frame(b)
-            ia, ib = _images(a, denoised=False), _images(b, denoised=False)
+            G.frame(a); G.frame(b)
+            ia, ib = G.images(a, FRAME_WORDS), G.images(b, FRAME_WORDS)
             for k in ("vis", "depth", "normal", "rm", "velocity"):
                 np.testing.assert_array_equal(ia[k], ib[k], err_msg="frame %d: %s" % (f, k))
-            assert _frame_index(a) == _frame_index(b) == f
+            assert G.frame_index(a) == G.frame_index(b) == f
             traced = R.traced_mask(W, H, f)
             covered = ia["vis"] != 0
             at = traced | ~covered
@@ -145,35 +83,35 @@ def test_quarter_rate_at_4096_traces_the_full_rate_twins_pixels(built):
 
 # ---- 3. the default is untouched -----------------------------------------------------------------------------------------------------
 def test_setting_256_is_never_having_set_it(built):
-    a, b = _app(320, 180, ["-metallic", 0.25, 0.5]), _app(320, 180, ["-metallic", 0.25, 0.5])
+    a, b = G.app(320, 180, ["-metallic", 0.25, 0.5]), G.app(320, 180, ["-metallic", 0.25, 0.5])
     try:
         a.context.set_sample_set(256)
         for f in range(6):
             if f == 3:
                 a.context.set_sample_set(256)
-            _frame(a); _frame(b)
-            _assert_same(_images(a), _images(b), "frame %d" % f)
+            G.frame(a); G.frame(b)
+            G.assert_same(G.images(a, IMAGES), G.images(b, IMAGES), "frame %d" % f)
     finally:
         a.OnDestroy(); b.OnDestroy()
 
 
 def test_4096_and_back_renders_the_frames_of_a_twin_that_never_left(built):
-    a, b = _app(320, 180, ["-metallic", 0.25, 0.5]), _app(320, 180, ["-metallic", 0.25, 0.5])
+    a, b = G.app(320, 180, ["-metallic", 0.25, 0.5]), G.app(320, 180, ["-metallic", 0.25, 0.5])
     try:
-        _frame(a); _frame(b)
+        G.frame(a); G.frame(b)
         a.context.set_sample_set(4096)
         differed = False
         for f in range(3):
-            _frame(a); _frame(b)
-            ia, ib = _images(a, denoised=False), _images(b, denoised=False)
+            G.frame(a); G.frame(b)
+            ia, ib = G.images(a, FRAME_WORDS), G.images(b, FRAME_WORDS)
             for k in ("vis", "depth", "normal", "rm", "velocity"):      # nothing else of a frame depends on M
                 np.testing.assert_array_equal(ia[k], ib[k], err_msg="at 4096, frame %d: %s" % (f, k))
             differed = differed or not np.array_equal(ia["refl"], ib["refl"])
         assert differed, "the setting reached no frame"
         a.context.set_sample_set(256)
         for f in range(3):
-            _frame(a); _frame(b)
-            _assert_same(_images(a, denoised=False), _images(b, denoised=False), "back at 256, frame %d" % f)
+            G.frame(a); G.frame(b)
+            G.assert_same(G.images(a, FRAME_WORDS), G.images(b, FRAME_WORDS), "back at 256, frame %d" % f)
     finally:
         a.OnDestroy(); b.OnDestroy()
 
@@ -185,7 +123,7 @@ def test_free_running_frames_with_the_set_switched_equal_synchronised_ones(built
     free-running: a frame in flight keeps its table and its mask."""
     import torch
     extra = ["-metallic", 1.0, 0.5]
-    a, b = _app(320, 180, extra), _app(320, 180, extra)
+    a, b = G.app(320, 180, extra), G.app(320, 180, extra)
     stream = torch.cuda.Stream() if mode == "caller-stream" else None
     try:
         for x in (a, b):
@@ -199,12 +137,12 @@ def test_free_running_frames_with_the_set_switched_equal_synchronised_ones(built
                     x.context.set_sample_set(65536)
                 if f == 10:
                     x.context.set_sample_set(1024)
-                _frame(x)
+                G.frame(x)
             a.context.sync()
             if f in (4, 9):
-                _assert_same(_images(a, denoised=False), _images(b, denoised=False), "%s: frame %d" % (mode, f))
+                G.assert_same(G.images(a, FRAME_WORDS), G.images(b, FRAME_WORDS), "%s: frame %d" % (mode, f))
         torch.cuda.synchronize()
-        _assert_same(_images(a, denoised=False), _images(b, denoised=False), "%s: after 16 frames" % mode)
+        G.assert_same(G.images(a, FRAME_WORDS), G.images(b, FRAME_WORDS), "%s: after 16 frames" % mode)
     finally:
         a.OnDestroy(); b.OnDestroy()
 
@@ -213,16 +151,16 @@ def test_free_running_frames_with_the_set_switched_equal_synchronised_ones(built
 def test_host_frame_counter_wraps_at_the_set_size(built):
     """Word 111 of the frame constants (FrameIndex) through app with -sampleset 1024 -dt 0 at 64x36: 256 after 257 frames, 1023 after 1024,
     0 after 1025; the default app reads 0 after 257."""
-    a, b = _app(64, 36, ["-sampleset", 1024, "-dt", 0]), _app(64, 36, ["-dt", 0])
+    a, b = G.app(64, 36, ["-sampleset", 1024, "-dt", 0]), G.app(64, 36, ["-dt", 0])
     try:
         seen = {}
         for f in range(1, 1026):
-            _frame(a)
+            G.frame(a)
             if f in (257, 1024, 1025):
                 seen[f] = int(a.frame_constants().view(np.uint32)[111])
         assert seen == {257: 256, 1024: 1023, 1025: 0}
         for f in range(257):
-            _frame(b)
+            G.frame(b)
         assert int(b.frame_constants().view(np.uint32)[111]) == 0
         a.context.sync(); b.context.sync()
     finally:
@@ -232,13 +170,13 @@ def test_host_frame_counter_wraps_at_the_set_size(built):
 # ---- 6. strips -----------------------------------------------------------------------------------------------------------------------
 def test_two_strips_at_1024_equal_the_whole_frame(built):
     extra = ["-sampleset", 1024, "-metallic", 0.25, 0.5]
-    whole, top, bottom = _app(W, H, extra), _app(W, H, extra), _app(W, H, extra)
+    whole, top, bottom = G.app(W, H, extra), G.app(W, H, extra), G.app(W, H, extra)
     try:
         top.context.set_strip(0, 30); bottom.context.set_strip(30, H)
         for f in range(3):
             for x in (whole, top, bottom):
-                _frame(x)
-            iw, it, ib = (_images(x, denoised=False) for x in (whole, top, bottom))
+                G.frame(x)
+            iw, it, ib = (G.images(x, FRAME_WORDS) for x in (whole, top, bottom))
             for k in ("vis", "normal", "rm", "velocity", "refl", "diff"):
                 np.testing.assert_array_equal(it[k][:30], iw[k][:30], err_msg="frame %d: %s, rows 0..29" % (f, k))
                 np.testing.assert_array_equal(ib[k][30:], iw[k][30:], err_msg="frame %d: %s, rows 30..53" % (f, k))
@@ -250,7 +188,7 @@ def test_two_strips_at_1024_equal_the_whole_frame(built):
 def test_accumulation_at_4096_equals_its_restatement_and_survives_a_change_of_the_set(built):
     from raytracedggx_amd import capi
     metallic = (0.25, 0.5)
-    a = _app(W, H, ["-sampleset", 4096, "-metallic", metallic[0], metallic[1], "-accumulate", 64])
+    a = G.app(W, H, ["-sampleset", 4096, "-metallic", metallic[0], metallic[1], "-accumulate", 64])
     try:
         acc = AR.Accumulator(H, W)
 
@@ -263,7 +201,7 @@ def test_accumulation_at_4096_equals_its_restatement_and_survives_a_change_of_th
             if f == 3:      # in mid-run: count and sums stay as they are (the reset is the caller's)
                 a.context.set_sample_set(512)
                 check("after set_sample_set")
-            _frame(a)
+            G.frame(a)
             c = a.context
             acc.add(c.readback(capi.BUF_RT_REFL), c.readback(capi.BUF_RT_DIFF), c.readback(capi.BUF_VISIBILITY), metallic)
             check("frame %d" % f)
@@ -275,16 +213,16 @@ def test_accumulation_at_4096_equals_its_restatement_and_survives_a_change_of_th
 def test_accumulate_line_warns_past_m_frames_at_two_samples(built, tmp_path, capfd):
     """-spp 2 -accumulate through app at 64x36, M = 256: after 200 frames -- 400 samples, every index distinct -- the line states the set and
     does not warn; after 257 frames the first frame has come again and it does."""
-    a = _app(64, 36, ["-spp", 2, "-accumulate", 1000, "-dt", 0])
+    a = G.app(64, 36, ["-spp", 2, "-accumulate", 1000, "-dt", 0])
     try:
         for f in range(200):
-            _frame(a)
+            G.frame(a)
         capfd.readouterr()
         assert a.save_converged(str(tmp_path / "a.png"))
         out = capfd.readouterr().out
         assert "accumulated 200 frames" in out and "; sample set of 256" in out and "warning" not in out, out
         for f in range(57):
-            _frame(a)
+            G.frame(a)
         assert a.save_converged(str(tmp_path / "b.png"))
         out = capfd.readouterr().out
         assert "accumulated 257 frames" in out and "; sample set of 256\nwarning: 257 frames of 2 samples" in out and "repeat after 256 " in out, out
@@ -298,7 +236,7 @@ def test_still_sky_with_the_set_changed_in_mid_run(built):
     The change ends no run: the frame after it still leaves tiles alone (runs broken at frame 6 would stand at 2 there, below the
     threshold of RT_SETS + 2)."""
     from raytracedggx_amd import capi
-    a, b = _app(320, 180, ["-sharedmem"]), _app(320, 180, ["-sharedmem"])
+    a, b = G.app(320, 180, ["-sharedmem"]), G.app(320, 180, ["-sharedmem"])
     targets = (capi.BUF_VISIBILITY, capi.BUF_DEPTH, capi.BUF_NORMAL, capi.BUF_ROUGH_METAL, capi.BUF_VELOCITY, capi.BUF_RT_REFL, capi.BUF_RT_DIFF,
                capi.BUF_FLT_RFL, capi.BUF_FLT_DFF, capi.BUF_TSS0, capi.BUF_TSS1, capi.BUF_BACKBUFFER)
     try:
@@ -307,7 +245,7 @@ def test_still_sky_with_the_set_changed_in_mid_run(built):
             for x in (a, b):
                 if f == 6:
                     x.context.set_sample_set(8192)
-                _frame(x)
+                G.frame(x)
             a.context.sync(); b.context.sync()
             for bid in targets:
                 np.testing.assert_array_equal(a.context.readback(bid), b.context.readback(bid), err_msg="frame %d: buffer %d" % (f, bid))
@@ -332,13 +270,13 @@ def test_refusals_leave_the_context_unchanged(built):
             c.set_sample_set(good)
     finally:
         c.close()
-    a, b = _app(W, H, ["-sampleset", 2048]), _app(W, H, ["-sampleset", 2048])
+    a, b = G.app(W, H, ["-sampleset", 2048]), G.app(W, H, ["-sampleset", 2048])
     try:
         for f in range(3):
             for bad in (0, 128, 255, 257, 3000, 131072):
                 with pytest.raises(capi.RtggxError):
                     a.context.set_sample_set(bad)
-            _frame(a); _frame(b)
-            _assert_same(_images(a), _images(b), "frame %d" % f)
+            G.frame(a); G.frame(b)
+            G.assert_same(G.images(a, IMAGES), G.images(b, IMAGES), "frame %d" % f)
     finally:
         a.OnDestroy(); b.OnDestroy()

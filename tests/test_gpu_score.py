@@ -11,25 +11,13 @@ import numpy as np
 import pytest
 
 import assets
+import gpu_support as G
 import score_ref as SR
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FRAME_INDEX_OFFSET = 444      # RtggxCBGlobal::FrameIndex in the 768 bytes of RtggxFrameConstants
-
-
-def _app(W, H, extra=(), mesh="bunny.obj"):
-    from raytracedggx_amd import app
-    return app.RayTracedGGX(["-mesh", assets.path(mesh), "-env", assets.path("rnl_cross.dds"), "-width", W, "-height", H] + list(extra))
-
-
-def _frame(a):
-    a.OnUpdate(); a.OnRender()
-
-
-def _frame_index(a):
-    return int(a.frame_constants()[FRAME_INDEX_OFFSET:FRAME_INDEX_OFFSET + 4].view(np.uint32)[0])
+IMAGES = G.GBUFFER + G.RAW + G.DENOISED + G.RAYS
 
 
 def _words(a):
@@ -46,23 +34,6 @@ def _assert_record(got, words, metallic, reference, label, rows=(0, None)):
     return want
 
 
-def _images(a):
-    from raytracedggx_amd import capi
-    c = a.context
-    c.sync()
-    ids = [("vis", capi.BUF_VISIBILITY), ("depth", capi.BUF_DEPTH), ("normal", capi.BUF_NORMAL), ("rm", capi.BUF_ROUGH_METAL), ("velocity", capi.BUF_VELOCITY),
-           ("refl", capi.BUF_RT_REFL), ("diff", capi.BUF_RT_DIFF), ("flt_rfl", capi.BUF_FLT_RFL), ("flt_dff", capi.BUF_FLT_DFF),
-           ("tss0", capi.BUF_TSS0), ("tss1", capi.BUF_TSS1), ("back", capi.BUF_BACKBUFFER)]
-    out = {n: c.readback(b) for n, b in ids}
-    out["rays"] = np.array([c.ray_count()])
-    return out
-
-
-def _assert_same(a, b, label):
-    for k in a:
-        np.testing.assert_array_equal(a[k], b[k], err_msg="%s: %s differs" % (label, k))
-
-
 _REFERENCES = {}
 
 
@@ -71,11 +42,11 @@ def _reference(W, H, metallic, mesh="bunny.obj", frames=32):
     from raytracedggx_amd import capi
     key = (W, H, metallic, mesh, frames)
     if key not in _REFERENCES:
-        x = _app(W, H, ["-metallic", metallic[0], metallic[1], "-spp", 8], mesh=mesh)
+        x = G.app(W, H, ["-metallic", metallic[0], metallic[1], "-spp", 8], mesh=mesh)
         try:
             x.context.set_accumulation(True)
             for _ in range(frames):
-                _frame(x)
+                G.frame(x)
             x.context.present_accumulation()
             ref = x.context.readback(capi.BUF_CONVERGED)
         finally:
@@ -95,17 +66,17 @@ def _reference(W, H, metallic, mesh="bunny.obj", frames=32):
 def test_records_equal_the_restatement(built, mesh, metallic, extra):
     """100x54, 6 consecutive frames: every record against the restatement, bit for bit."""
     ref = _reference(100, 54, metallic, mesh)
-    a = _app(100, 54, ["-metallic", metallic[0], metallic[1]] + extra, mesh=mesh)
+    a = G.app(100, 54, ["-metallic", metallic[0], metallic[1]] + extra, mesh=mesh)
     try:
         c = a.context
         c.set_reference(ref)
         c.set_scoring(True)
         assert c.read_scores() == []
         for f in range(6):
-            _frame(a)
+            G.frame(a)
             words = _words(a)
             recs = c.read_scores()
-            assert len(recs) == 1 and recs[0]["index"] == f and recs[0]["frame_index"] == _frame_index(a), recs
+            assert len(recs) == 1 and recs[0]["index"] == f and recs[0]["frame_index"] == G.frame_index(a), recs
             want = _assert_record(recs[0], words, metallic, ref, "%s %s frame %d" % (mesh, extra, f))
             assert want["pixels"] == 5400 and 0 < want["covered"] < 5400
             assert want["se_out_rgb"] > 0.0 and want["se_raw_rgb"] > 0.0 and want["ref_rgb2"] > want["ref_rgb2_cov"] > 0.0 and want["se_out_luma"] > 0.0
@@ -118,12 +89,12 @@ def test_records_equal_the_restatement(built, mesh, metallic, extra):
 def test_one_pixel_and_a_strip_of_one_row(built):
     """P = 1: no addition at all in the contract's tree, ten levels of +0.0 padding on the device.  P = 100: one row of a 100x54 frame."""
     from raytracedggx_amd import capi
-    a = _app(1, 1)
+    a = G.app(1, 1)
     try:
         ref = np.array([[np.array([0.5, 0.25, 2.0, 1.0], np.float16).view(np.uint64)[0]]], np.uint64)
         a.context.set_reference(ref); a.context.set_scoring(True)
         for f in range(3):
-            _frame(a)
+            G.frame(a)
             words = _words(a)
             recs = a.context.read_scores()
             assert len(recs) == 1 and recs[0]["pixels"] == 1
@@ -132,12 +103,12 @@ def test_one_pixel_and_a_strip_of_one_row(built):
         a.OnDestroy()
     metallic = (0.25, 0.5)
     ref = _reference(100, 54, metallic)
-    a = _app(100, 54, ["-metallic", metallic[0], metallic[1]])
+    a = G.app(100, 54, ["-metallic", metallic[0], metallic[1]])
     try:
         a.context.set_strip(30, 31)
         a.context.set_reference(ref); a.context.set_scoring(True)
         for f in range(3):
-            _frame(a)
+            G.frame(a)
             words = _words(a)
             recs = a.context.read_scores()
             assert len(recs) == 1 and recs[0]["pixels"] == 100
@@ -155,10 +126,10 @@ def test_a_frame_with_more_chunks_than_the_second_stage_has_lanes(built):
     metallic = (0.25, 0.5)
     W, H = 1280, 820
     ref = _reference(W, H, metallic, frames=2)
-    a = _app(W, H, ["-metallic", metallic[0], metallic[1]])
+    a = G.app(W, H, ["-metallic", metallic[0], metallic[1]])
     try:
         a.context.set_reference(ref); a.context.set_scoring(True)
-        _frame(a)
+        G.frame(a)
         words = _words(a)
         recs = a.context.read_scores()
         assert len(recs) == 1 and recs[0]["pixels"] == W * H == 1025 * 1024
@@ -173,14 +144,14 @@ def test_three_strips_score_their_own_rows(built):
     W, H = 320, 180
     ref = _reference(W, H, metallic, frames=8)
     strips = [(0, 60), (60, 120), (120, 180)]
-    apps = [_app(W, H, ["-metallic", metallic[0], metallic[1]]) for _ in strips]
+    apps = [G.app(W, H, ["-metallic", metallic[0], metallic[1]]) for _ in strips]
     try:
         for a, (b, e) in zip(apps, strips):
             a.context.set_strip(b, e); a.context.set_reference(ref); a.context.set_scoring(True)
         for f in range(3):
             pixels = covered = 0
             for a, (b, e) in zip(apps, strips):
-                _frame(a)
+                G.frame(a)
                 words = _words(a)
                 recs = a.context.read_scores()
                 assert len(recs) == 1 and recs[0]["index"] == f
@@ -202,7 +173,7 @@ def test_a_scoring_context_renders_what_its_twin_renders(built, variant):
     metallic = (0.25, 0.5)
     extra = ["-metallic", metallic[0], metallic[1]] + (["-sync"] if variant == "sync-flag" else []) + (["-deform", 0.05] if variant == "deforming" else [])
     ref = _reference(100, 54, metallic)
-    a, twin = _app(100, 54, extra), _app(100, 54, extra)
+    a, twin = G.app(100, 54, extra), G.app(100, 54, extra)
     streams = [torch.cuda.Stream(), torch.cuda.Stream()] if variant == "caller-stream" else None
     try:
         for k, x in enumerate((a, twin)):
@@ -214,9 +185,9 @@ def test_a_scoring_context_renders_what_its_twin_renders(built, variant):
                 x.context.set_stream(streams[k].cuda_stream)
         a.context.set_reference(ref); a.context.set_scoring(True)
         for f in range(6):
-            _frame(a); _frame(twin)
-            ia = _images(a)
-            _assert_same(ia, _images(twin), "%s, frame %d" % (variant, f))
+            G.frame(a); G.frame(twin)
+            ia = G.images(a, IMAGES)
+            G.assert_same(ia, G.images(twin, IMAGES), "%s, frame %d" % (variant, f))
             recs = a.context.read_scores()
             assert len(recs) == 1
             _assert_record(recs[0], _words(a), metallic, ref, "%s, frame %d" % (variant, f))
@@ -237,20 +208,20 @@ def test_free_running_frames_score_what_synchronised_ones_do(built):
     metallic = (1.0, 0.5)
     extra = ["-metallic", metallic[0], metallic[1]]
     ref = _reference(100, 54, metallic)
-    a, twin = _app(100, 54, extra), _app(100, 54, extra)
+    a, twin = G.app(100, 54, extra), G.app(100, 54, extra)
     try:
         for x in (a, twin):
             x.context.set_reference(ref); x.context.set_scoring(True)
         want = []
         for f in range(16):
-            _frame(twin)
+            G.frame(twin)
             words = _words(twin)
             recs = twin.context.read_scores()
             assert len(recs) == 1
             _assert_record(recs[0], words, metallic, ref, "synchronised twin, frame %d" % f)
             want += recs
         for f in range(16):
-            _frame(a)
+            G.frame(a)
         got = a.context.read_scores()
         assert [r["index"] for r in got] == list(range(16))
         for f, (g, w) in enumerate(zip(got, want)):
@@ -264,15 +235,15 @@ def test_the_ring_keeps_the_last_records_and_hands_them_out_in_order(built):
     from raytracedggx_amd import capi
     metallic = (1.0, 1.0)
     ref = _reference(100, 54, metallic)
-    a = _app(100, 54)
+    a = G.app(100, 54)
     try:
         c = a.context
         c.set_reference(ref); c.set_scoring(True)
         n = capi.SCORE_RING + 5
         frame_indices = []
         for f in range(n):
-            _frame(a)
-            frame_indices.append(_frame_index(a))
+            G.frame(a)
+            frame_indices.append(G.frame_index(a))
         words = _words(a)
         recs = c.read_scores()
         assert [r["index"] for r in recs] == list(range(5, n)), "the five oldest are gone, and the gap in index shows it"
@@ -280,7 +251,7 @@ def test_the_ring_keeps_the_last_records_and_hands_them_out_in_order(built):
         _assert_record(recs[-1], words, metallic, ref, "the last of %d frames" % n)
         assert c.read_scores() == []
         for f in range(7):
-            _frame(a)
+            G.frame(a)
         words = _words(a)
         first = c.read_scores(capacity=3)
         assert [r["index"] for r in first] == [n, n + 1, n + 2], "the three oldest"
@@ -296,14 +267,14 @@ def test_a_frames_own_image_as_the_reference_scores_zero(built):
     """Two contexts render the same frames.  The twin's TemporalSSOut of frame 4 is the other's reference for ITS frame 4: se_out_* are +0.0."""
     metallic = (0.25, 0.5)
     extra = ["-metallic", metallic[0], metallic[1]]
-    a, twin = _app(100, 54, extra), _app(100, 54, extra)
+    a, twin = G.app(100, 54, extra), G.app(100, 54, extra)
     try:
         for f in range(4):
-            _frame(a); _frame(twin)
-        _frame(twin)
+            G.frame(a); G.frame(twin)
+        G.frame(twin)
         own = _words(twin)[0]
         a.context.set_reference(own); a.context.set_scoring(True)
-        _frame(a)
+        G.frame(a)
         words = _words(a)
         np.testing.assert_array_equal(words[0], own)
         rec = a.context.read_scores()[0]
@@ -319,14 +290,14 @@ def test_the_reference_can_be_replaced_in_mid_run(built):
     ref1 = _reference(100, 54, metallic)
     ref2 = _reference(100, 54, (1.0, 1.0))
     assert (ref1 != ref2).any()
-    a = _app(100, 54, ["-metallic", metallic[0], metallic[1]])
+    a = G.app(100, 54, ["-metallic", metallic[0], metallic[1]])
     try:
         c = a.context
         c.set_reference(ref1); c.set_scoring(True)
         for f in range(4):
             if f == 2:
                 c.set_reference(ref2)      # no read in between: the two records before it were computed against ref1
-            _frame(a)
+            G.frame(a)
             if f >= 2:
                 words = _words(a)
                 recs = c.read_scores()
@@ -342,16 +313,16 @@ def test_reference_from_accumulation_is_the_presented_mean_and_leaves_the_back_b
     from raytracedggx_amd import capi
     metallic = (0.25, 0.5)
     extra = ["-metallic", metallic[0], metallic[1]]
-    a, twin = _app(100, 54, extra), _app(100, 54, extra)
+    a, twin = G.app(100, 54, extra), G.app(100, 54, extra)
     try:
         for x in (a, twin):
             x.context.set_accumulation(True)
             for f in range(4):
-                _frame(x)
+                G.frame(x)
             x.context.set_accumulation(False)
-        before = _images(a)
+        before = G.images(a, IMAGES)
         a.context.reference_from_accumulation()
-        _assert_same(_images(a), before, "reference_from_accumulation")
+        G.assert_same(G.images(a, IMAGES), before, "reference_from_accumulation")
         assert not a.context.readback(capi.BUF_CONVERGED).any(), "RTGGX_BUF_CONVERGED is the present's"
         twin.context.present_accumulation()
         conv = twin.context.readback(capi.BUF_CONVERGED)
@@ -359,7 +330,7 @@ def test_reference_from_accumulation_is_the_presented_mean_and_leaves_the_back_b
         for x in (a, twin):
             x.context.set_scoring(True)
         for f in range(2):
-            _frame(a); _frame(twin)
+            G.frame(a); G.frame(twin)
             words = _words(a)
             ra, rt = a.context.read_scores(), twin.context.read_scores()
             assert len(ra) == len(rt) == 1 and not SR.same_record(ra[0], rt[0]), (ra, rt)
@@ -376,12 +347,12 @@ def test_non_finite_pixels_are_skipped_and_counted(built):
     ref = _reference(100, 54, (1.0, 1.0), mesh="triangle.obj", frames=8).copy()
     ref16 = ref.view(np.uint16).reshape(54, 100, 4)
     ref16[27, 50, 1] = 0x7C00; ref16[5, 5, 2] = 0x7E00      # +infinity under the model's row, a NaN in the sky
-    a = _app(100, 54, mesh="triangle.obj")
+    a = G.app(100, 54, mesh="triangle.obj")
     try:
         a.context.set_env(capi.FORMAT_RGBA16F, 1, 1, assets.constant_env_rgba16f(np.inf))
         a.context.set_reference(ref); a.context.set_scoring(True)
         for f in range(3):
-            _frame(a)
+            G.frame(a)
             words = _words(a)
             rec = a.context.read_scores()[0]
             want = _assert_record(rec, words, (1.0, 1.0), ref, "infinite environment, frame %d" % f)
@@ -398,7 +369,7 @@ def test_off_and_on_refusals_and_release(built):
     metallic = (0.25, 0.5)
     extra = ["-metallic", metallic[0], metallic[1]]
     ref = _reference(100, 54, metallic)
-    a, twin = _app(100, 54, extra), _app(100, 54, extra)
+    a, twin = G.app(100, 54, extra), G.app(100, 54, extra)
     try:
         c = a.context
         L = c.L
@@ -416,8 +387,8 @@ def test_off_and_on_refusals_and_release(built):
         assert L.rtggx_set_reference(c.h, None, 43200) == -1 and b"rtggx_set_reference" in L.rtggx_last_error()
         assert c.read_scores() == []
         c.set_scoring(False)      # off without a reference: nothing to refuse
-        _frame(a); _frame(twin)
-        _assert_same(_images(a), _images(twin), "after the refusals")
+        G.frame(a); G.frame(twin)
+        G.assert_same(G.images(a, IMAGES), G.images(twin, IMAGES), "after the refusals")
         # on, off for two frames, on again: index goes on counting, frame_index shows the frames in between
         c.set_reference(ref); c.set_scoring(True)
         shown = []
@@ -426,8 +397,8 @@ def test_off_and_on_refusals_and_release(built):
                 c.set_scoring(False)
             if f == 4:
                 c.set_scoring(True)
-            _frame(a); _frame(twin)
-            shown.append(_frame_index(a))
+            G.frame(a); G.frame(twin)
+            shown.append(G.frame_index(a))
         words = _words(a)
         buf = (capi.Score * 8)()
         assert L.rtggx_read_scores(c.h, buf, 8, None) == -1 and b"rtggx_read_scores" in L.rtggx_last_error()
@@ -438,7 +409,7 @@ def test_off_and_on_refusals_and_release(built):
         _assert_record(recs[-1], words, metallic, ref, "on again")
         with pytest.raises(capi.RtggxError, match="rtggx_set_reference"):
             c.set_reference(np.zeros((10, 10), np.uint64))      # a refused replacement keeps the reference
-        _frame(a); _frame(twin)
+        G.frame(a); G.frame(twin)
         words = _words(a)
         recs = c.read_scores()
         assert [r["index"] for r in recs] == [4]
@@ -446,13 +417,13 @@ def test_off_and_on_refusals_and_release(built):
         # releasing the reference turns scoring off
         c.set_reference(None)
         for f in range(2):
-            _frame(a); _frame(twin)
+            G.frame(a); G.frame(twin)
         assert c.read_scores() == []
         with pytest.raises(capi.RtggxError, match="rtggx_set_scoring"):
             c.set_scoring(True)
-        _assert_same(_images(a), _images(twin), "after the release")
+        G.assert_same(G.images(a, IMAGES), G.images(twin, IMAGES), "after the release")
         c.set_reference(ref); c.set_scoring(True)
-        _frame(a); _frame(twin)
+        G.frame(a); G.frame(twin)
         assert [r["index"] for r in c.read_scores()] == [5]
     finally:
         a.OnDestroy(); twin.OnDestroy()
@@ -470,10 +441,10 @@ def test_executable_saves_a_reference_and_scores_a_run_against_it(built, tmp_pat
     r = subprocess.run([exe] + scene + ["-spp", "8", "-frames", "8", "-accumulate", "8", "-savereference", pfm, "-dump", str(tmp_path / "shot.png")],
                        capture_output=True, text=True, timeout=120, cwd=str(tmp_path))
     assert r.returncode == 0 and "wrote " + pfm in r.stdout, (r.stdout, r.stderr)
-    x = _app(100, 54, ["-metallic", 0.25, 0.5, "-spp", 8, "-accumulate", 8])
+    x = G.app(100, 54, ["-metallic", 0.25, 0.5, "-spp", 8, "-accumulate", 8])
     try:
         for f in range(8):
-            _frame(x)
+            G.frame(x)
         x.context.present_accumulation()
         conv = x.context.readback(capi.BUF_CONVERGED)
         assert x.save_reference(str(tmp_path / "again.pfm"))
@@ -487,14 +458,14 @@ def test_executable_saves_a_reference_and_scores_a_run_against_it(built, tmp_pat
     assert r.returncode == 0, (r.stdout, r.stderr)
     lines = [json.loads(l) for l in open(jsonl)]
     assert [l["index"] for l in lines] == list(range(6))
-    a = _app(100, 54, ["-metallic", 0.25, 0.5, "-reference", pfm, "-score", str(tmp_path / "python.jsonl")])
+    a = G.app(100, 54, ["-metallic", 0.25, 0.5, "-reference", pfm, "-score", str(tmp_path / "python.jsonl")])
     try:
         for f, line in enumerate(lines):
-            _frame(a)
+            G.frame(a)
             words = _words(a)
             want = SR.score(*words, metallic, ref)
             fig = SR.figures(want)
-            assert line["frame_index"] == _frame_index(a)
+            assert line["frame_index"] == G.frame_index(a)
             for k in ("pixels", "covered", "skipped_out", "skipped_raw"):
                 assert line[k] == want[k], (f, k)
             for k, v in fig.items():

@@ -1,36 +1,18 @@
 """Quarter-rate tracing without a GPU: the ABI surface of rtggx_set_ray_rate, the command line's refusals (before any GPU is touched),
 and known answers of the reconstruction's numpy restatement (tests/ray_rate_ref.py) on synthetic G-buffers."""
-import ctypes as C
-import os
-import re
-import subprocess
-
 import numpy as np
 
-import assets
+import host_support as HS
 import ray_rate_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_set_ray_rate_is_declared_exported_and_bound(built):
-    from raytracedggx_amd import capi
-    header = open(os.path.join(ROOT, "include", "rtggx.h")).read()
-    assert re.search(r"\bint\s+rtggx_set_ray_rate\s*\(\s*rtggx_context\s*\*\s*ctx\s*,\s*uint32_t\s+pixels_per_ray\s*\)", header)
-    assert hasattr(C.CDLL(capi.LIB_PATH), "rtggx_set_ray_rate")
-    assert "rtggx_set_ray_rate" in capi.EXPORTS
-    assert callable(getattr(capi.Context, "set_ray_rate", None))
+    HS.declared_exported_bound("rtggx_set_ray_rate", r"\bint\s+rtggx_set_ray_rate\s*\(\s*rtggx_context\s*\*\s*ctx\s*,\s*uint32_t\s+pixels_per_ray\s*\)")
 
 
 def test_executable_refuses_bad_ray_rates_before_touching_a_gpu(built):
-    exe = os.path.join(ROOT, "raytracedggx_amd", "RayTracedGGX")
-    scene = ["-mesh", assets.path("triangle.obj"), "-env", assets.path("rnl_cross.dds"), "-width", "64", "-height", "64"]
-    for extra in (["-rayrate", "3"], ["-gpus", "2", "-rayrate", "4"], ["-strips", "2", "-rayrate", "4"], ["/RAYRATE", "4", "-Strips", "3"],
-                  ["-rayrate", "4", "-gpus", "2"], ["-rayrate"]):
-        r = subprocess.run([exe] + scene + extra, capture_output=True, text=True, timeout=60)
-        assert r.returncode == 1, (extra, r.returncode, r.stderr)
-        assert "-rayrate" in r.stderr, (extra, r.stderr)
-        assert "no HIP device" not in r.stderr and "rank" not in r.stderr.lower(), (extra, r.stderr)
+    HS.executable_refuses((["-rayrate", "3"], ["-gpus", "2", "-rayrate", "4"], ["-strips", "2", "-rayrate", "4"], ["/RAYRATE", "4", "-Strips", "3"],
+                           ["-rayrate", "4", "-gpus", "2"], ["-rayrate"]), "-rayrate", no_device_message="no HIP device")
 
 
 def test_traced_pixels_cover_every_pixel_in_four_frames():

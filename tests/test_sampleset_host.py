@@ -8,8 +8,6 @@ import ctypes as C
 import json
 import math
 import os
-import re
-import subprocess
 import sys
 
 import numpy as np
@@ -19,28 +17,22 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if __name__ == "__main__":
     sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
-import assets  # noqa: E402
+import host_support as HS  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 
-FRAME_INDEX_OFFSET = 444      # RtggxCBGlobal::FrameIndex in the 768 bytes of RtggxFrameConstants (include/rtggx.h): the last word of `global`
 GOLDEN = os.path.join(ROOT, "tests", "golden", "sampleset_convergence.json")
 
 
 def _ref():
-    import sampleset_ref as MR
-    return MR
+    import restatement as RS
+    return RS
 
 
 # ---- 1. surface and bindings ---------------------------------------------------------------------------------------------------------
 def test_set_sample_set_is_declared_exported_and_bound(built):
-    from raytracedggx_amd import app, capi
-    header = open(os.path.join(ROOT, "include", "rtggx.h")).read()
-    assert re.search(r"\bint\s+rtggx_set_sample_set\s*\(\s*rtggx_context\s*\*\s*ctx\s*,\s*uint32_t\s+size\s*\)", header)
-    assert re.search(r"#define\s+RTGGX_MIN_SAMPLE_SET\s+256u\b", header)
-    assert re.search(r"#define\s+RTGGX_MAX_SAMPLE_SET\s+65536u\b", header)
-    assert hasattr(C.CDLL(capi.LIB_PATH), "rtggx_set_sample_set")
-    assert "rtggx_set_sample_set" in capi.EXPORTS
-    assert callable(getattr(capi.Context, "set_sample_set", None))
+    from raytracedggx_amd import app
+    HS.declared_exported_bound("rtggx_set_sample_set", r"\bint\s+rtggx_set_sample_set\s*\(\s*rtggx_context\s*\*\s*ctx\s*,\s*uint32_t\s+size\s*\)",
+                               defines=[r"#define\s+RTGGX_MIN_SAMPLE_SET\s+256u\b", r"#define\s+RTGGX_MAX_SAMPLE_SET\s+65536u\b"])
     for name in ("rtggx_host_frame_indices", "rtggx_host_accumulation_note"):
         assert name in app.HOST_EXPORTS and hasattr(C.CDLL(app.HOST_LIB_PATH), name)
 
@@ -81,14 +73,9 @@ def test_accumulate_line_states_the_set_and_warns_past_m_frames_whatever_n(built
 
 # ---- 2. command line -----------------------------------------------------------------------------------------------------------------
 def test_executable_refuses_bad_sample_sets_before_touching_a_gpu(built):
-    exe = os.path.join(ROOT, "raytracedggx_amd", "RayTracedGGX")
-    scene = ["-mesh", assets.path("triangle.obj"), "-env", assets.path("rnl_cross.dds"), "-width", "64", "-height", "64"]
-    for extra in (["-sampleset", "0"], ["-sampleset", "255"], ["-sampleset", "300"], ["-sampleset", "131072"], ["-sampleset"],
-                  ["/SAMPLESET", "x"], ["-SampleSet", "-512"], ["-sampleset", "300", "-gpus", "2"], ["-strips", "2", "-sampleset", "1000"]):
-        r = subprocess.run([exe] + scene + extra, capture_output=True, text=True, timeout=60)
-        assert r.returncode == 1, (extra, r.returncode, r.stderr)
-        assert "-sampleset" in r.stderr, (extra, r.stderr)
-        assert "HIP device" not in r.stderr and "HIP device" not in r.stdout and "rank" not in r.stderr.lower(), (extra, r.stderr)
+    HS.executable_refuses((["-sampleset", "0"], ["-sampleset", "255"], ["-sampleset", "300"], ["-sampleset", "131072"], ["-sampleset"],
+                           ["/SAMPLESET", "x"], ["-SampleSet", "-512"], ["-sampleset", "300", "-gpus", "2"], ["-strips", "2", "-sampleset", "1000"]),
+                          "-sampleset", nor_on_stdout=True)
 
 
 # ---- 3. known answers ----------------------------------------------------------------------------------------------------------------
@@ -111,9 +98,8 @@ def _rng_numpy(seed):
 
 @pytest.mark.parametrize("W,pixel,index,M,s,y16,oracle", KNOWN)
 def test_known_answers_of_the_sample_parameter(built, W, pixel, index, M, s, y16, oracle):
-    MR = _ref()
     x, y = pixel
-    got_s, xi_x, xi_y = MR.sample_param(x, y, W, index, M)
+    got_s, xi_x, xi_y = _ref().sample_param(x, y, W, index, M)
     assert got_s == s
     assert float(xi_y) * 65536.0 == y16
     assert xi_x == np.float32(s) / np.float32(M) and float(xi_x) == s / M      # (exact: s < 2^16, M a power of two)
@@ -149,29 +135,7 @@ W, H = 96, 54
 
 def _scene(o, metallic, vndf):
     """Bunny, still camera and model, the visibility pass done: only FrameIndex changes from here on (tests/test_accumulation_host.py)."""
-    v, i, _ = O.obj_import(assets.path("bunny.obj"))
-    o.set_mesh(1, v, i)
-    o.set_env_dds(assets.path("rnl_cross.dds"))
-    o.set_metallic(0, metallic[0]); o.set_metallic(1, metallic[1])
-    o.set_sampler(vndf)
-    o.build_as(); o.transform_sh()
-    for _ in range(2):
-        o.update_frame((10, 10, -24), O.camera_view_proj(o.W, o.H), 0.25)
-    o.update_as(); o.render_visibility()
-
-
-def _set_frame_index(o, index):
-    fc = o.get_frame_constants()
-    fc[FRAME_INDEX_OFFSET:FRAME_INDEX_OFFSET + 4] = np.array([index], np.uint32).view(np.uint8)
-    o.set_frame_constants(fc.tobytes())
-
-
-_BUFS = (O.BUF_RT_REFL, O.BUF_RT_DIFF, O.BUF_NORMAL, O.BUF_ROUGH_METAL, O.BUF_VELOCITY)
-
-
-def _poison(o):      # (a word either renderer leaves alone stays poisoned in both)
-    for b in _BUFS:
-        o.buffer(b, copy=False)[...] = 0xBEEF if b == O.BUF_ROUGH_METAL else 0xDEADBEEF
+    HS.scene(o, "bunny.obj", metallic=metallic, vndf=vndf, frame=1)
 
 
 # ---- 4. equality at M = 256 ----------------------------------------------------------------------------------------------------------
@@ -180,9 +144,8 @@ def _poison(o):      # (a word either renderer leaves alone stays poisoned in bo
 def test_restatement_at_256_equals_the_spp_restatement(built, metallic, vndf):
     """M = 256: tests/spp_ref.cpp's orc_ray_trace_spp bit for bit -- both raw images, normal, rough/metal, velocity, the ray count -- at
     (N, D) = (1, 1) and (4, 2), FrameIndex 0, 100 and 255."""
-    import spp_ref as SR
-    MR = _ref()
-    a, b = SR.Oracle(W, H), MR.Oracle(W, H, sample_set=256)
+    RS = _ref()
+    a, b = RS.Oracle(W, H, entry="spp"), RS.Oracle(W, H, sample_set=256, entry="sampleset")
     try:
         _scene(a, metallic, vndf); _scene(b, metallic, vndf)
         np.testing.assert_array_equal(a.buffer(O.BUF_VISIBILITY), b.buffer(O.BUF_VISIBILITY))
@@ -191,10 +154,10 @@ def test_restatement_at_256_equals_the_spp_restatement(built, metallic, vndf):
                 o.set_samples_per_pixel(n); o.set_max_recursion_depth(d)
             for index in (0, 100, 255):
                 for o in (a, b):
-                    _set_frame_index(o, index); _poison(o)
+                    HS.set_frame_index(o, index); HS.poison(o)
                 rays_a, rays_b = a.ray_trace(), b.ray_trace()
                 assert rays_a == rays_b > 0, (n, d, index)
-                for buf in _BUFS:
+                for buf in HS.RAW_BUFS:
                     np.testing.assert_array_equal(b.buffer(buf), a.buffer(buf), err_msg="N %d depth %d index %d buffer %d" % (n, d, index, buf))
     finally:
         a.close(); b.close()
@@ -205,7 +168,7 @@ def _mean_reflection(o, indices):
     """float64 mean of the unpacked reflection image over the frames with these indices."""
     total = np.zeros((o.H, o.W, 3), np.float64)
     for index in indices:
-        _set_frame_index(o, int(index))
+        HS.set_frame_index(o, int(index))
         o.ray_trace()
         total += O.unpack_r11g11b10f(o.buffer(O.BUF_RT_REFL)).astype(np.float64)
     return total / len(indices)
@@ -216,8 +179,7 @@ def measure_convergence():
     both rows: other indices).  Returns the MSE against R of the M = 256 mean over one period, of the M = 65536 mean over 0..1023, the noise
     of R itself (its two halves against each other), and whether a second period at M = 256 reproduces the first mean exactly."""
     from raytracedggx_amd import app
-    MR = _ref()
-    o = MR.Oracle(W, H)
+    o = _ref().Oracle(W, H, entry="sampleset")
     try:
         _scene(o, (1.0, 1.0), False)
         covered = o.buffer(O.BUF_VISIBILITY) != 0

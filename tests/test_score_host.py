@@ -6,28 +6,29 @@ import ctypes as C
 import math
 import os
 import re
-import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 import accum_ref as AR
 import assets
+import host_support as HS
 import score_ref as SR
 from oracle import oracle as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROOT = HS.ROOT
 
 
 # ---- surface ------------------------------------------------------------------------------------------------------------------------
 def test_scoring_is_declared_exported_and_bound(built):
     from raytracedggx_amd import app, capi
     header = open(os.path.join(ROOT, "include", "rtggx.h")).read()
-    assert re.search(r"\bint\s+rtggx_set_reference\s*\(\s*rtggx_context\s*\*\s*ctx\s*,\s*const\s+void\s*\*\s*rgba16f\s*,\s*size_t\s+bytes\s*\)", header)
-    assert re.search(r"\bint\s+rtggx_reference_from_accumulation\s*\(\s*rtggx_context\s*\*\s*ctx\s*\)", header)
-    assert re.search(r"\bint\s+rtggx_set_scoring\s*\(\s*rtggx_context\s*\*\s*ctx\s*,\s*int\s+enable\s*\)", header)
-    assert re.search(r"\bint\s+rtggx_read_scores\s*\(\s*rtggx_context\s*\*\s*ctx\s*,\s*RtggxScore\s*\*\s*out\s*,\s*uint32_t\s+capacity\s*,\s*uint32_t\s*\*\s*count\s*\)", header)
+    for symbol, signature in (("rtggx_set_reference", r"\bint\s+rtggx_set_reference\s*\(\s*rtggx_context\s*\*\s*ctx\s*,\s*const\s+void\s*\*\s*rgba16f\s*,\s*size_t\s+bytes\s*\)"),
+                              ("rtggx_reference_from_accumulation", r"\bint\s+rtggx_reference_from_accumulation\s*\(\s*rtggx_context\s*\*\s*ctx\s*\)"),
+                              ("rtggx_set_scoring", r"\bint\s+rtggx_set_scoring\s*\(\s*rtggx_context\s*\*\s*ctx\s*,\s*int\s+enable\s*\)"),
+                              ("rtggx_read_scores", r"\bint\s+rtggx_read_scores\s*\(\s*rtggx_context\s*\*\s*ctx\s*,\s*RtggxScore\s*\*\s*out\s*,\s*uint32_t\s+capacity\s*,\s*uint32_t\s*\*\s*count\s*\)")):
+        HS.declared_exported_bound(symbol, signature)
+        assert callable(getattr(app.RayTracedGGX, symbol[len("rtggx_"):], None))
     assert re.search(r"\bRTGGX_SCORE_RING\s*=\s*256\b", header) and capi.SCORE_RING == 256
     assert re.search(r"\bRTGGX_BUF_COUNT\s*=\s*28\b", header), "scoring adds no buffer id"
     # the record: the fields of the header's struct in its order; six 8-byte slots of counts and nine doubles.  (The issue that asked for
@@ -38,11 +39,6 @@ def test_scoring_is_declared_exported_and_bound(built):
     assert names == [n for n, _ in capi.Score._fields_]
     assert C.sizeof(capi.Score) == 120 == 6 * 8 + 9 * 8
     assert [n for n, t in capi.Score._fields_ if t is C.c_double] == list(SR.SUMS)
-    lib = C.CDLL(capi.LIB_PATH)
-    for name, method in (("rtggx_set_reference", "set_reference"), ("rtggx_reference_from_accumulation", "reference_from_accumulation"),
-                         ("rtggx_set_scoring", "set_scoring"), ("rtggx_read_scores", "read_scores")):
-        assert hasattr(lib, name) and name in capi.EXPORTS
-        assert callable(getattr(capi.Context, method, None)) and callable(getattr(app.RayTracedGGX, method, None))
     host = C.CDLL(app.HOST_LIB_PATH)
     for name in ("rtggx_app_set_reference", "rtggx_app_set_scoring", "rtggx_app_read_scores", "rtggx_app_save_reference", "rtggx_app_flush_scores",
                  "rtggx_host_write_pfm", "rtggx_host_read_pfm"):
@@ -59,8 +55,6 @@ def _pfm_bytes(w, h, scale=b"-1.0", rows=None):
 
 
 def test_executable_refuses_bad_score_flags_before_touching_a_gpu(built, tmp_path):
-    exe = os.path.join(ROOT, "raytracedggx_amd", "RayTracedGGX")
-    scene = ["-mesh", assets.path("triangle.obj"), "-env", assets.path("rnl_cross.dds"), "-width", "64", "-height", "36"]
     good, trunc, small, big_endian, junk = (str(tmp_path / n) for n in ("good.pfm", "trunc.pfm", "small.pfm", "be.pfm", "junk.pfm"))
     open(good, "wb").write(_pfm_bytes(64, 36))
     open(trunc, "wb").write(_pfm_bytes(64, 36, rows=35) + b"\0" * 100)
@@ -74,11 +68,7 @@ def test_executable_refuses_bad_score_flags_before_touching_a_gpu(built, tmp_pat
              (["-reference", big_endian], "scale"), (["-reference", junk], "PF"),
              (["-reference", good, "-gpus", "2"], "-gpus"), (["-reference", good, "-score", jsonl, "-gpus", "2"], "-gpus"),
              (["-strips", "2", "-reference", good], "-strips"), (["-strips", "2", "-reference", good, "-score", jsonl], "-strips")]
-    for extra, word in cases:
-        r = subprocess.run([exe] + scene + extra, capture_output=True, text=True, timeout=60)
-        assert r.returncode == 1, (extra, r.returncode, r.stderr)
-        assert word in r.stderr, (extra, r.stderr)
-        assert "HIP device" not in r.stderr and "rank" not in r.stderr.lower(), (extra, r.stderr)
+    HS.executable_refuses(cases, scene=HS.SCENE[:-1] + ("36",))
     assert not os.path.exists(jsonl) and not os.path.exists(str(tmp_path / "out.pfm"))
 
 
