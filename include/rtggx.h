@@ -373,7 +373,9 @@ int  rtggx_build_as(rtggx_context* ctx);
  * rtggx_refit_as of a mesh allocates its per-set buffers).  While a mesh deforms on a full-size frame the context keeps three frames in
  * flight instead of four (rtggx_render_visibility waits for the end of frame f - 3): one frame time instead of two, DESIGN.md section 9.
  * rtggx_refit_stats: cost of the current tree relative to the last
- * build, refits and rebuilds so far; synchronises (a rebuild in progress stays in progress). */
+ * build, refits and rebuilds so far; synchronises (a rebuild in progress stays in progress).  A build whose cost is 0 -- one triangle, or
+ * every vertex on one axis-aligned line or at one point -- reports 1 while the cost stays 0 and +infinity once it is not: any growth of
+ * such a mesh asks for a rebuild. */
 int  rtggx_refit_as(rtggx_context* ctx, uint32_t slot, const float* verts, uint32_t num_verts);
 /* The same for a mesh animated ON the GPU (round 4): `device_verts` is a device pointer, `hip_stream` the stream that produces it (NULL: the
  * null stream).  Like a hipMemcpyAsync on that stream: the copy out of `device_verts` is ordered behind everything the stream holds at the

@@ -752,7 +752,8 @@ static int checkRefit(rtggx_context* c, uint32_t slot, const void* verts, uint32
 // the cost of the tree after an earlier refit has arrived: has the shape drifted too far from the one the topology was built for?
 static void pollTreeCost(rtggx_context* c, MeshDev& m) {
   if (m.costInFlight && hipEventQuery(m.evCost) == hipSuccess) { m.lastCost = *m.hCost; m.costInFlight = false; }
-  if (m.builtCost > 0.0f && m.lastCost > c->rebuildRatio * m.builtCost) m.wantRebuild = true;      // started by the next frame (issuePendingRefits)
+  // (a build of cost 0 -- every box without area: a mesh that starts collapsed onto an axis-aligned line or into a point -- is outgrown by any cost above 0)
+  if (m.lastCost > c->rebuildRatio * m.builtCost) m.wantRebuild = true;      // started by the next frame (issuePendingRefits)
 }
 int rtggx_refit_as(rtggx_context* c, uint32_t slot, const float* verts, uint32_t nv) {
   RT_CHECK_CTX(c);
@@ -816,7 +817,7 @@ int rtggx_refit_stats(rtggx_context* c, uint32_t slot, float* costRatio, uint32_
   MeshDev& m = c->mesh[slot];
   RT_HIP(syncStreams(c));
   if (m.costInFlight) { m.lastCost = *m.hCost; m.costInFlight = false; }
-  if (costRatio) *costRatio = m.builtCost > 0.0f ? m.lastCost / m.builtCost : 1.0f;
+  if (costRatio) *costRatio = m.builtCost > 0.0f ? m.lastCost / m.builtCost : m.lastCost > 0.0f ? __builtin_inff() : 1.0f;      // (0 / 0: one triangle, or still collapsed)
   if (refits) *refits = m.refits;
   if (rebuilds) *rebuilds = m.rebuilds;
   return 0;

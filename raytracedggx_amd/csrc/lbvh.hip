@@ -1201,6 +1201,9 @@ int refitLbvh(rtggx_context* c, uint32_t slot, uint32_t set, hipStream_t s) {
     }
   }
   emitTree(m, t, set, m.topoVersionOfSet[set] != m.topoVersion, s);
+  // (the current set's count was copied out when the frame selected the set, rtggx_context.h selectSet: a topology that takes over with
+  // this refit may have a table of another size -- trees of fewer 4-wide nodes than the table holds)
+  if (set == c->setIndex) m.topCount = m.topCountBuf[set];
   m.topoVersionOfSet[set] = m.topoVersion;
   if (n > 1 && !m.costInFlight && (m.refits & 3u) == 0u) {
     { const int r = launchTreeCost(m, s); if (r) return r; }

@@ -9,7 +9,7 @@ def bvh_check(nodes_u32, tris_u32, root, num_tris, verts=None, idx=None):
     """Binary tree (RTGGX_BUF_BVH_NODES*, 64-byte nodes: child-0 box min/max, child-1 box min/max, child refs at words 12, 13;
     ref >= 0: node, < 0: ~leaf slot) over the leaf triangles (RTGGX_BUF_BVH_TRIS*, 64 bytes: v0 v1 v2, primitive id at word 12).
     Asserts: every primitive in exactly one leaf slot, every leaf slot and every node reachable exactly once from the root, every
-    child box contains -- and is tight around -- everything below it.  Given the mesh (verts: [nv, 6] position + normal, idx: the index
+    child box contains -- and is exactly, as float values, the min / max of -- everything below it.  Given the mesh (verts: [nv, 6] position + normal, idx: the index
     buffer), also that every leaf record holds, bit for bit, the three vertices of its primitive: boxes tight around a wrong triangle
     would pass the rest.  Returns the depth of the deepest leaf."""
     prims = tris_u32.reshape(-1, 16)[:, 12]
@@ -57,7 +57,8 @@ def bvh_check(nodes_u32, tris_u32, root, num_tris, verts=None, idx=None):
             cM = np.where(isleaf[:, None], tmax[np.where(isleaf, ~c, 0)], bmax[np.where(isleaf, 0, c)])
             box_min, box_max = f[nodes_l, off:off + 3].astype(np.float64), f[nodes_l, off + 3:off + 6].astype(np.float64)
             assert (box_min <= cm).all() and (box_max >= cM).all(), "child box must contain the child"
-            assert np.allclose(box_min, cm) and np.allclose(box_max, cM), "child box is tight"
+            # min / max of fp32 values have no rounding: the box IS the min / max of what is below it (as values: -0.0 == 0.0)
+            assert (box_min == cm).all() and (box_max == cM).all(), "child box is tight"
             lo.append(cm); hi.append(cM)
         bmin[nodes_l], bmax[nodes_l] = np.minimum(lo[0], lo[1]), np.maximum(hi[0], hi[1])
     return len(levels) + 1

@@ -1,10 +1,12 @@
 """What the GPU tests share: the product's application object beside an oracle (Pair) and its frame check, the application-level helpers
 of the tests that compare two contexts (app, frame, images, assert_same), the raw check against a restatement (restated_pair, check_raw),
-a rate-4 frame against the full-rate one (quad_frame, check_quad_frame) and the strips exchanging through RCCL.  raytracedggx_amd is
-imported inside the functions: importing this module needs no GPU and no built library."""
+a rate-4 frame against the full-rate one (quad_frame, check_quad_frame), the strips exchanging through RCCL, and the bare context beside
+an oracle that the BVH tests trace rays through (Scene, model_box, interval_edges).  raytracedggx_amd is imported inside the functions:
+importing this module needs no GPU and no built library."""
 import numpy as np
 
 import assets
+import bvh_cases
 import bvh_checks
 import env_cases
 import ray_rate_ref as R
@@ -323,3 +325,117 @@ def wave(v0, f, amp=0.35):
     v[:, 0] += amp * np.sin(1.3 * v0[:, 1] + 0.9 * f)
     v[:, 2] += 0.7 * amp * np.cos(0.8 * v0[:, 1] - 0.7 * f)
     return v
+
+
+# ---- a bare context beside an oracle, for rays through synthetic meshes (tests/bvh_cases.py) -----------------------------------------
+BVH_SETS = ((("BUF_BVH_NODES0", "BUF_BVH_TRIS0", "BUF_BVH4_NODES0", "BUF_BVH4_TOP0"), 16), (("BUF_BVH_NODES1", "BUF_BVH_TRIS1", "BUF_BVH4_NODES1", "BUF_BVH4_TOP1"), 96))
+
+
+class Scene:
+    """A capi.Context and an oracle holding the same two meshes and instance transforms.  camera: the frame constants are an ordinary
+    camera's (the oracle's default one) with the scene's Worlds, for the tests that run frames (frame): the visibility pass then sees
+    ordinary input.  built_shape: see check_trees, for the check of the build."""
+
+    def __init__(self, mesh0, mesh1, world0=None, world1=None, camera=False, built_shape=True):
+        from raytracedggx_amd import capi
+        self.capi = capi
+        self.meshes = [mesh0, mesh1]
+        self.worlds = [bvh_cases.world(4.0, (0.0, -6.0, 0.0)) if world0 is None else world0, bvh_cases.world() if world1 is None else world1]
+        self.ctx = capi.Context(bvh_cases.W, bvh_cases.H)
+        self.o = O.Oracle(bvh_cases.W, bvh_cases.H)
+        try:
+            for slot, (v, i) in enumerate(self.meshes):
+                self.ctx.set_mesh(slot, v, i)
+                self.o.set_mesh(slot, v, i)
+            self.ctx.build_as()
+            base = None
+            if camera:
+                self.o.update_frame((10, 10, -24), O.camera_view_proj(bvh_cases.W, bvh_cases.H), 0.0)
+                base = self.o.get_frame_constants()
+            self.fc = bvh_cases.frame_constants(*self.worlds, base=base)
+            self.ctx.update_frame(self.fc); self.ctx.update_as()
+            self.o.set_frame_constants(self.fc); self.o.update_as()
+            np.testing.assert_array_equal(self.ctx.readback(capi.BUF_TLAS), self.o.inv_worlds())
+            self.depth = self.check_trees(built_shape)
+        except Exception:
+            self.close()
+            raise
+
+    def close(self):
+        self.ctx.close(); self.o.close()
+
+    def arrays(self, slot):
+        """(nodes, tris, nodes4, top) of the slot's tree in the current input set, and its root."""
+        return tuple(self.ctx.readback(getattr(self.capi, b)) for b in BVH_SETS[slot][0]), self.ctx.bvh_root(slot)
+
+    def check_trees(self, built_shape=True):
+        """Structure of both trees (leaf vertices, tight boxes, the 4-wide collapse, the LDS tables of 16 and 96 nodes); then the
+        oracle gets the device's arrays for the tree-walk comparison.  built_shape: the collapse is the one the surface-area rule gives
+        for this shape (a bool, or one per slot: a refitted tree keeps the choice its build made for another shape).  Returns the binary
+        depth of each tree (self.tops: the entries of each table)."""
+        depth, self.tops = [], []
+        built = (built_shape, built_shape) if isinstance(built_shape, bool) else built_shape
+        for slot in range(2):
+            v, i = self.meshes[slot]
+            (nodes, tris, nodes4, top), root = self.arrays(slot)
+            depth.append(bvh_checks.bvh_check(nodes, tris, root, i.size // 3, v, i))
+            bvh_checks.bvh4_check(nodes, nodes4, root, built_shape=built[slot], weights=self.ctx.collapse_weights())
+            self.tops.append(bvh_checks.bvh4_top_check(nodes4, top, root, BVH_SETS[slot][1]))
+            self.o.set_bvh(slot, nodes, tris, root)
+        return depth
+
+    def frame(self, shapes=None, device=False):
+        """One frame as far as a refit needs it: update_frame + update_as + render_visibility + sync (rtggx_render_visibility is where a
+        staged shape is uploaded and the tree refitted; a frame without the later passes is supported).  shapes: {slot: verts} handed to
+        refit_as first, and to the oracle as the slot's mesh."""
+        for slot, v in (shapes or {}).items():
+            self.ctx.refit_as(slot, v)
+            self.set_shape(slot, v)
+        self.ctx.update_frame(self.fc); self.ctx.update_as(); self.ctx.render_visibility(); self.ctx.sync()
+
+    def set_shape(self, slot, v):
+        """The oracle's (and the checks') copy of a slot's vertices."""
+        self.meshes[slot] = (np.array(v, np.float32), self.meshes[slot][1])
+        self.o.set_mesh(slot, *self.meshes[slot])
+
+    def compare(self, rays, label, min_hits=0):
+        """HIP traversal == oracle brute force == oracle walking the device tree, bit for bit."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        g = self.ctx.trace_rays(rays)
+        b = self.o.trace_rays(rays, brute=True)
+        w = self.o.trace_rays(rays)
+        for other, what in ((b, "brute force"), (w, "oracle walking the device tree")):
+            bad = np.nonzero(g["valid"] != other["valid"])[0]
+            assert bad.size == 0, "%s: %d rays hit on one side only (vs %s), first ray %d: %s, device %s" % (
+                label, bad.size, what, bad[0], rays[bad[0]].tolist(), bool(g["valid"][bad[0]]))
+            hit = other["valid"]
+            for k in ("inst", "prim", "t", "b1", "b2"):
+                a, c = g[k][hit].view(np.uint32), other[k][hit].view(np.uint32)
+                bad = np.nonzero(a != c)[0]
+                assert bad.size == 0, "%s: %s differs (vs %s) on %d rays, first ray %d: device %s, oracle %s" % (
+                    label, k, what, bad.size, np.nonzero(hit)[0][bad[0]], g[k][hit][bad[0]], other[k][hit][bad[0]])
+        assert b["valid"].sum() >= min_hits, "%s: only %d of %d rays hit" % (label, b["valid"].sum(), len(rays))
+        return b
+
+
+def model_box(scene, slot=1):
+    """World-space box of a mesh (the instance transforms here are scale, quarter turn and translation: corners suffice)."""
+    return bvh_cases.world_box(scene.meshes[slot][0], scene.worlds[slot])
+
+
+def interval_edges(scene, rays, label):
+    """Rays that hit again, with tmax, then tmin, set to the exact t of their closest hit (both bounds are exclusive: the hit at
+    that t must go, on both sides alike), and with empty intervals (tmin == tmax, tmin > tmax: nothing hits)."""
+    b = scene.o.trace_rays(rays, brute=True)
+    hit = rays[b["valid"]].copy()
+    t = b["t"][b["valid"]]
+    if hit.shape[0]:
+        at_tmax = hit.copy(); at_tmax[:, 7] = t
+        scene.compare(at_tmax, label + ", tmax = t of the closest hit")
+        at_tmin = hit.copy(); at_tmin[:, 6] = t
+        scene.compare(at_tmin, label + ", tmin = t of the closest hit")
+        empty = hit.copy(); empty[:, 6] = t; empty[:, 7] = t
+        g = scene.ctx.trace_rays(empty)
+        assert not g["valid"].any(), label + ": an empty interval hit"
+        rev = hit.copy(); rev[:, 6] = t; rev[:, 7] = t * np.float32(0.5)
+        assert not scene.ctx.trace_rays(rev)["valid"].any(), label + ": tmin > tmax hit"

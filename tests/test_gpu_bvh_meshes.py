@@ -13,157 +13,20 @@ import math
 import numpy as np
 import pytest
 
-import bvh_checks
-from oracle import oracle as O
+from bvh_cases import grid_mesh, mesh_from_tris, rays_through_box, soup, world
+from gpu_support import Scene, interval_edges, model_box
 
 pytestmark = pytest.mark.gpu
 
-W = H = 64
 RT_STACK = 16            # LDS entries of the trace kernel's per-lane stack (csrc/trace.hip); deeper entries spill to global memory
 EMPTY = 0x7FFFFFFF       # RT_BVH4_EMPTY
-
-
-# ---- scene ------------------------------------------------------------------------------------------------------------------------
-def world(scale=1.0, translate=(0.0, 0.0, 0.0), rot_y90=False):
-    """Row-vector 4x4 (p' = p M, as XMMATRIX): uniform scale, optional quarter turn about y, translation -- all exact in fp32."""
-    m = np.eye(4, dtype=np.float32) * np.float32(scale)
-    m[3, 3] = 1.0
-    if rot_y90:
-        m[:3, :3] = np.array([[0, 0, -1], [0, 1, 0], [1, 0, 0]], np.float32) * np.float32(scale)
-    m[3, :3] = translate
-    return m
-
-
-def frame_constants(world0, world1):
-    """The 768-byte RtggxFrameConstants with only Worlds[2] set (float4x3, XMStoreFloat3x4: f[j * 4 + i] = M[i][j], j < 3)."""
-    fc = np.zeros(192, np.float32)
-    for k, w in enumerate((world0, world1)):
-        fc[64 + 12 * k:76 + 12 * k] = np.asarray(w, np.float32)[:, :3].T.reshape(-1)
-    return fc.tobytes()
-
-
-def mesh_from_tris(tris):
-    """[n, 3, 3] triangles -> (verts [3n, 6] with a +y normal, idx [3n])."""
-    tris = np.asarray(tris, np.float32).reshape(-1, 3, 3)
-    v = np.zeros((tris.shape[0] * 3, 6), np.float32)
-    v[:, :3] = tris.reshape(-1, 3)
-    v[:, 4] = 1.0
-    return v, np.arange(v.shape[0], dtype=np.uint32)
-
-
-def soup(n, seed, extent=1.0, size=None):
-    rng = np.random.default_rng(seed)
-    size = size if size is not None else extent * 1.5 * max(n, 1) ** (-1.0 / 3.0)
-    c = rng.uniform(-extent, extent, (n, 1, 3))
-    return (c + rng.normal(0.0, size, (n, 3, 3))).astype(np.float32)
-
-
-class Scene:
-    """A capi.Context and an oracle holding the same two meshes and instance transforms."""
-
-    def __init__(self, mesh0, mesh1, world0=None, world1=None):
-        from raytracedggx_amd import capi
-        self.capi = capi
-        self.meshes = [mesh0, mesh1]
-        self.worlds = [world(4.0, (0.0, -6.0, 0.0)) if world0 is None else world0, world() if world1 is None else world1]
-        self.ctx = capi.Context(W, H)
-        self.o = O.Oracle(W, H)
-        try:
-            for slot, (v, i) in enumerate(self.meshes):
-                self.ctx.set_mesh(slot, v, i)
-                self.o.set_mesh(slot, v, i)
-            self.ctx.build_as()
-            fc = frame_constants(*self.worlds)
-            self.ctx.update_frame(fc); self.ctx.update_as()
-            self.o.set_frame_constants(fc); self.o.update_as()
-            np.testing.assert_array_equal(self.ctx.readback(capi.BUF_TLAS), self.o.inv_worlds())
-            self.depth = self.check_trees()
-        except Exception:
-            self.close()
-            raise
-
-    def close(self):
-        self.ctx.close(); self.o.close()
-
-    def check_trees(self):
-        """Structure of both trees (leaf vertices, tight boxes, the 4-wide collapse, the LDS tables of 16 and 96 nodes); then the
-        oracle gets the device's arrays for the tree-walk comparison.  Returns the binary depth of each tree (self.tops: the entries
-        of each table)."""
-        capi, depth, self.tops = self.capi, [], []
-        for slot, (bn, bt, b4, btop, cap) in enumerate(((capi.BUF_BVH_NODES0, capi.BUF_BVH_TRIS0, capi.BUF_BVH4_NODES0, capi.BUF_BVH4_TOP0, 16),
-                                                        (capi.BUF_BVH_NODES1, capi.BUF_BVH_TRIS1, capi.BUF_BVH4_NODES1, capi.BUF_BVH4_TOP1, 96))):
-            v, i = self.meshes[slot]
-            nodes, tris, root = self.ctx.readback(bn), self.ctx.readback(bt), self.ctx.bvh_root(slot)
-            depth.append(bvh_checks.bvh_check(nodes, tris, root, i.size // 3, v, i))
-            nodes4 = self.ctx.readback(b4)
-            bvh_checks.bvh4_check(nodes, nodes4, root, weights=self.ctx.collapse_weights())
-            self.tops.append(bvh_checks.bvh4_top_check(nodes4, self.ctx.readback(btop), root, cap))
-            self.o.set_bvh(slot, nodes, tris, root)
-        return depth
-
-    def compare(self, rays, label, min_hits=0):
-        """HIP traversal == oracle brute force == oracle walking the device tree, bit for bit."""
-        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
-        g = self.ctx.trace_rays(rays)
-        b = self.o.trace_rays(rays, brute=True)
-        w = self.o.trace_rays(rays)
-        for other, what in ((b, "brute force"), (w, "oracle walking the device tree")):
-            bad = np.nonzero(g["valid"] != other["valid"])[0]
-            assert bad.size == 0, "%s: %d rays hit on one side only (vs %s), first ray %d: %s, device %s" % (
-                label, bad.size, what, bad[0], rays[bad[0]].tolist(), bool(g["valid"][bad[0]]))
-            hit = other["valid"]
-            for k in ("inst", "prim", "t", "b1", "b2"):
-                a, c = g[k][hit].view(np.uint32), other[k][hit].view(np.uint32)
-                bad = np.nonzero(a != c)[0]
-                assert bad.size == 0, "%s: %s differs (vs %s) on %d rays, first ray %d: device %s, oracle %s" % (
-                    label, k, what, bad.size, np.nonzero(hit)[0][bad[0]], g[k][hit][bad[0]], other[k][hit][bad[0]])
-        assert b["valid"].sum() >= min_hits, "%s: only %d of %d rays hit" % (label, b["valid"].sum(), len(rays))
-        return b
-
-
-def rays_through_box(lo, hi, n, seed, tmin=0.0, tmax=1e30):
-    """Origins on a sphere around the box, targets uniform inside it; direction = target - origin (t = 1 at the target)."""
-    rng = np.random.default_rng(seed)
-    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
-    c, r = 0.5 * (lo + hi), max(float(np.linalg.norm(hi - lo)), 1e-3)
-    d = rng.normal(size=(n, 3)); d /= np.linalg.norm(d, axis=1, keepdims=True)
-    org = c + 1.5 * r * d
-    tgt = rng.uniform(lo, hi, (n, 3))
-    return np.concatenate([org, tgt - org, np.full((n, 1), tmin), np.full((n, 1), tmax)], 1).astype(np.float32)
-
-
-def model_box(scene, slot=1):
-    """World-space box of a mesh (the instance transforms here are scale, quarter turn and translation: corners suffice)."""
-    v = scene.meshes[slot][0][:, :3].astype(np.float64)
-    corners = np.array([[x, y, z] for x in (v[:, 0].min(), v[:, 0].max()) for y in (v[:, 1].min(), v[:, 1].max())
-                        for z in (v[:, 2].min(), v[:, 2].max())])
-    p = np.concatenate([corners, np.ones((8, 1))], 1) @ scene.worlds[slot].astype(np.float64)
-    return p[:, :3].min(axis=0), p[:, :3].max(axis=0)
-
-
-def interval_edges(scene, rays, label):
-    """Rays that hit again, with tmax, then tmin, set to the exact t of their closest hit (both bounds are exclusive: the hit at
-    that t must go, on both sides alike), and with empty intervals (tmin == tmax, tmin > tmax: nothing hits)."""
-    b = scene.o.trace_rays(rays, brute=True)
-    hit = rays[b["valid"]].copy()
-    t = b["t"][b["valid"]]
-    if hit.shape[0]:
-        at_tmax = hit.copy(); at_tmax[:, 7] = t
-        scene.compare(at_tmax, label + ", tmax = t of the closest hit")
-        at_tmin = hit.copy(); at_tmin[:, 6] = t
-        scene.compare(at_tmin, label + ", tmin = t of the closest hit")
-        empty = hit.copy(); empty[:, 6] = t; empty[:, 7] = t
-        g = scene.ctx.trace_rays(empty)
-        assert not g["valid"].any(), label + ": an empty interval hit"
-        rev = hit.copy(); rev[:, 6] = t; rev[:, 7] = t * np.float32(0.5)
-        assert not scene.ctx.trace_rays(rev)["valid"].any(), label + ": tmin > tmax hit"
 
 
 SMALL0 = mesh_from_tris(soup(12, seed=100))      # the ground slot's mesh where a case is about the model's
 
 
 # ---- triangle soups across the build's thresholds ------------------------------------------------------------------------------
-SIZES = [1, 2, 3, 5, 16, 17, 32, 33, 34, 96, 97, 255, 256, 257, 1024, 1025, 2048, 2049, 3072, 3073, 40000]
+SIZES = [1, 2, 3, 5, 16, 17, 32, 33, 34, 96, 97, 255, 256, 257, 1024, 1025, 1026, 2048, 2049, 3072, 3073, 40000]
 
 
 @pytest.mark.parametrize("n", SIZES)
@@ -234,17 +97,6 @@ def test_every_triangle_twice_with_reversed_winding(built):
         s.compare(rays_through_box(lo, hi, 3000, seed=9), "reversed winding", min_hits=300)
     finally:
         s.close()
-
-
-def grid_mesh(q=128, step=0.125):
-    """Flat grid of q x q quads in y = 0, two triangles each, shared vertices: zero Morton extent along y, equal boxes per quad."""
-    k = np.arange(q + 1, dtype=np.float32)
-    x, z = np.meshgrid((k - q / 2) * np.float32(step), (k - q / 2) * np.float32(step), indexing="ij")
-    v = np.zeros(((q + 1) ** 2, 6), np.float32)
-    v[:, 0], v[:, 2], v[:, 4] = x.reshape(-1), z.reshape(-1), 1.0
-    a = (np.arange(q)[:, None] * (q + 1) + np.arange(q)[None, :]).reshape(-1)
-    idx = np.stack([a, a + 1, a + q + 1, a + 1, a + q + 2, a + q + 1], 1).reshape(-1).astype(np.uint32)
-    return v, idx
 
 
 def test_flat_grid_shared_edges_vertices_and_axis_aligned_rays(built):
