@@ -185,6 +185,34 @@ int  rtggx_set_mesh(rtggx_context* ctx, uint32_t slot, const float* verts, uint3
 /* Cube map: `size` x `size` faces, `mips` levels, `data` laid out as in a DDS file (face-major,
  * full mip chain per face, faces +X -X +Y -Y +Z -Z).  BC6H blocks are decoded on the device. */
 int  rtggx_set_env(rtggx_context* ctx, int format, uint32_t size, uint32_t mips, const void* data, size_t bytes);
+/* Environments from images (no counterpart in the reference, whose probes were converted to BC6H cubes offline; DESIGN.md "Environments
+ * from images"): the cube and its whole mip chain built on the device from a cross or a latitude-longitude panorama.  A context that calls
+ * neither function allocates and launches what it always did.
+ *   - data: width x height pixels, rows top to bottom, RTGGX_PIXELS_RGBE8 (4 bytes r, g, b, e: e == 0 is black, otherwise
+ *     m 2^(e - 136) per channel) or RTGGX_PIXELS_RGB32F (3 floats).  Per channel v = x > 0 ? min(x, 65504) : 0: NaN and negatives become 0;
+ *   - a cross (RTGGX_ENV_VCROSS: 3 x 4 square cells, RTGGX_ENV_HCROSS: 4 x 3) is never resampled: level 0 is a copy of six cells, cell
+ *     (row, col) -> face; vertical: (0,1) +Y, (1,0) -X, (1,1) +Z, (1,2) +X, (2,1) -Y, (3,1) -Z turned by 180 degrees; horizontal: (0,1) +Y,
+ *     (1,0) -X, (1,1) +Z, (1,2) +X, (1,3) -Z, (2,1) -Y.  cube_size must be 0; a cell above 4096 is refused;
+ *   - a panorama (RTGGX_ENV_EQUIRECT, at most 16384 x 8192): cube_size 0 = the largest power of two <= width / 4, else any side from 1 to
+ *     4096.  Per cube texel: d = the normalised direction through its centre, lon = atan2(d.x, d.z), lat = asin(d.y),
+ *     s = (lon / 2 pi + 0.5) width - 0.5, t = (0.5 - lat / pi) height - 0.5 (+Z in the middle of the image, +X to its right, +Y in the
+ *     top row), one bilinear tap at (s, t), columns wrapping and rows clamping; coordinates and weights in fp64, rounded to fp32 once;
+ *   - the chain, for any side: floor(log2(size)) + 1 levels of side max(size >> m, 1), each face alone, separable, horizontal pass first.
+ *     One axis from a parent side p to q = p >> 1, child i: p even (t[2i] + t[2i+1]) / 2; p odd ((q - i) t[2i] + q t[2i+1]) + (i + 1) t[2i+2],
+ *     then / p -- the box of exact coverage.  Integer weights converted to float, every operation fp32 and rounded on its own in the order
+ *     written; level m + 1 from the fp32 level m, not from its halves; every level packed to RGBA16F once, alpha 1.  RTGGX_BUF_ENV can be
+ *     restated bit for bit (tests/envimage_ref.py);
+ *   - refused, the context keeping the environment it had: null data, too few bytes, a width or height of 0, a source that is too large, a
+ *     cross whose sides do not divide into square cells, an unknown layout or pixel format, cube_size with a cross or above 4096.
+ * rtggx_generate_env_mips: the full chain below the CURRENT level 0 by the same rule -- level 0 widened from its halves (exact) and left
+ * as it is, whatever levels the cube had below it replaced; fails when no environment is set.  For a cube uploaded with fewer levels than
+ * a full chain: the shader picks a level from the roughness and clamps it to the last one there is.
+ * Both synchronise, end the still-sky runs and invalidate the SH coefficients as rtggx_set_env does; the scratch is freed on return. */
+enum { RTGGX_ENV_EQUIRECT = 0, RTGGX_ENV_VCROSS = 1, RTGGX_ENV_HCROSS = 2 };
+enum { RTGGX_PIXELS_RGBE8 = 0, RTGGX_PIXELS_RGB32F = 1 };
+int  rtggx_set_env_image(rtggx_context* ctx, int layout, int pixels, uint32_t width, uint32_t height, const void* data, size_t bytes,
+                         uint32_t cube_size);
+int  rtggx_generate_env_mips(rtggx_context* ctx);
 int  rtggx_set_material(rtggx_context* ctx, uint32_t mesh, const float base_color[4], float roughness, float metallic);
 int  rtggx_set_metallic(rtggx_context* ctx, uint32_t mesh, float metallic);
 /* Sampler of the reflection lobe.  0 (default): the reference's -- the GGX normal distribution itself, computeLocalDirectionGGX /

@@ -19,7 +19,7 @@ HOST_EXPORTS = ["rtggx_app_last_error", "rtggx_app_create", "rtggx_app_destroy",
                 "rtggx_host_exchange_plan", "rtggx_host_balanced_bounds", "rtggx_app_set_dump_prefix", "rtggx_app_last_screen_shot", "rtggx_app_save_converged",
                 "rtggx_host_frame_indices", "rtggx_host_accumulation_note",
                 "rtggx_app_save_reference", "rtggx_app_flush_scores", "rtggx_app_set_reference", "rtggx_app_set_scoring", "rtggx_app_read_scores",
-                "rtggx_host_write_pfm", "rtggx_host_read_pfm"]
+                "rtggx_host_write_pfm", "rtggx_host_read_pfm", "rtggx_host_load_env_image"]
 
 _lib = None
 
@@ -53,6 +53,8 @@ def load():
         L.rtggx_app_read_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.rtggx_host_write_pfm.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.rtggx_host_read_pfm.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.rtggx_host_load_env_image.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int),
+                                                C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.rtggx_app_last_screen_shot.argtypes = [C.c_void_p]
         L.rtggx_app_last_screen_shot.restype = C.c_char_p
         L.rtggx_host_obj_import.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p]
@@ -137,6 +139,21 @@ def read_pfm(path, width, height):
     if L.rtggx_host_read_pfm(str(path).encode(), int(width), int(height), out.ctypes.data_as(C.c_void_p)) != 0:
         raise IOError(L.rtggx_app_last_error().decode())
     return out
+
+
+def load_env_image(path):
+    """The host layer's Radiance .hdr / .pfm readers (no device; told apart by the file's first bytes) -> (pixels, layout, image): pixels
+    capi.PIXELS_RGBE8 with image uint8[H, W, 4] or capi.PIXELS_RGB32F with image float32[H, W, 3], rows top to bottom; layout what the aspect
+    ratio tells (capi.ENV_EQUIRECT / ENV_VCROSS / ENV_HCROSS) or -1.  Raises IOError with the reader's reason for what it refuses."""
+    L = load()
+    px, lay, w, h, n = C.c_int(), C.c_int(), C.c_uint32(), C.c_uint32(), C.c_size_t()
+    if L.rtggx_host_load_env_image(str(path).encode(), C.byref(px), C.byref(w), C.byref(h), C.byref(lay), None, 0, C.byref(n)) != 0:
+        raise IOError(L.rtggx_app_last_error().decode())
+    raw = np.zeros(n.value, np.uint8)
+    if L.rtggx_host_load_env_image(str(path).encode(), None, None, None, None, raw.ctypes.data_as(C.c_void_p), raw.size, None) != 0:
+        raise IOError(L.rtggx_app_last_error().decode())
+    image = raw.reshape(h.value, w.value, 4) if px.value == capi.PIXELS_RGBE8 else raw.view(np.float32).reshape(h.value, w.value, 3)
+    return px.value, lay.value, image
 
 
 def accumulation_note(frames, samples, sample_set):

@@ -19,6 +19,8 @@ BUF_VISIBILITY, BUF_DEPTH, BUF_NORMAL, BUF_ROUGH_METAL, BUF_VELOCITY, BUF_RT_REF
     BUF_ACC_REFL, BUF_ACC_DIFF, BUF_CONVERGED = range(28)
 MAX_PEERS, IPC_HANDLE_BYTES = 16, 64
 FORMAT_RGBA32F, FORMAT_RGBA16F, FORMAT_BC6H_UF16, FORMAT_BC6H_SF16 = 2, 10, 95, 96
+ENV_EQUIRECT, ENV_VCROSS, ENV_HCROSS = 0, 1, 2      # layouts and pixel formats of rtggx_set_env_image
+PIXELS_RGBE8, PIXELS_RGB32F = 0, 1
 
 _BUF_DTYPE = {BUF_VISIBILITY: np.uint32, BUF_DEPTH: np.uint32, BUF_NORMAL: np.uint32, BUF_ROUGH_METAL: np.uint16,
               BUF_VELOCITY: np.uint32, BUF_RT_REFL: np.uint32, BUF_RT_DIFF: np.uint32, BUF_TSS0: np.uint64, BUF_TSS1: np.uint64,
@@ -35,7 +37,8 @@ EXPORTS = ["rtggx_last_error", "rtggx_create", "rtggx_destroy", "rtggx_set_strip
            "rtggx_upload", "rtggx_frame_parity", "rtggx_bvh_root", "rtggx_trace_rays", "rtggx_ray_total", "rtggx_kernel_times", "rtggx_debug_counters", "rtggx_debug_trace_split", "rtggx_debug_trace_residency", "rtggx_get_stream", "rtggx_set_history_peers", "rtggx_history_ipc_export", "rtggx_history_ipc_open",
            "rtggx_set_async_compute", "rtggx_set_history_apron", "rtggx_history_overreach", "rtggx_copy_bandwidth", "rtggx_refit_as", "rtggx_refit_as_device", "rtggx_refit_stats", "rtggx_set_refit_policy", "rtggx_set_sampler", "rtggx_set_ray_rate", "rtggx_set_max_recursion_depth", "rtggx_set_samples_per_pixel", "rtggx_debug_fuse_tone_map", "rtggx_debug_placement", "rtggx_debug_tile_words", "rtggx_debug_static_sky", "rtggx_debug_sky_runs", "rtggx_debug_collapse_weights", "rtggx_debug_fence_wait", "rtggx_debug_shader_clock", "rtggx_debug_environment",
            "rtggx_set_accumulation", "rtggx_reset_accumulation", "rtggx_accumulated_frames", "rtggx_present_accumulation", "rtggx_set_sample_set",
-           "rtggx_set_reference", "rtggx_reference_from_accumulation", "rtggx_set_scoring", "rtggx_read_scores"]
+           "rtggx_set_reference", "rtggx_reference_from_accumulation", "rtggx_set_scoring", "rtggx_read_scores",
+           "rtggx_set_env_image", "rtggx_generate_env_mips"]
 SCORE_RING = 256
 
 
@@ -96,6 +99,8 @@ def load():
     L.rtggx_history_overreach.argtypes = [vp, C.POINTER(C.c_uint32), C.c_int]
     L.rtggx_set_mesh.argtypes = [vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32]
     L.rtggx_set_env.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, vp, C.c_size_t]
+    L.rtggx_set_env_image.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, vp, C.c_size_t, C.c_uint32]
+    L.rtggx_generate_env_mips.argtypes = [vp]
     L.rtggx_set_material.argtypes = [vp, C.c_uint32, vp, C.c_float, C.c_float]
     L.rtggx_set_metallic.argtypes = [vp, C.c_uint32, C.c_float]
     for n in ("rtggx_build_as", "rtggx_update_as", "rtggx_transform_sh", "rtggx_render_visibility", "rtggx_ray_trace",
@@ -352,6 +357,20 @@ class Context:
     def set_env(self, fmt, size, mips, data):
         b = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data).view(np.uint8).reshape(-1)
         self._check(self.L.rtggx_set_env(self.h, fmt, size, mips, _p(b), b.size))
+
+    def set_env_image(self, layout, pixels, width, height, data, cube_size=0):
+        """The cube and its full mip chain built on the device from an image (include/rtggx.h): layout ENV_EQUIRECT / ENV_VCROSS / ENV_HCROSS,
+        pixels PIXELS_RGBE8 (uint8[H, W, 4]) or PIXELS_RGB32F (float32[H, W, 3]), rows top to bottom; cube_size for a panorama only (0: the
+        largest power of two <= width / 4).  data=None passes a null pointer (refused, like everything the header lists)."""
+        if data is None:
+            self._check(self.L.rtggx_set_env_image(self.h, int(layout), int(pixels), int(width), int(height), None, 0, int(cube_size)))
+            return
+        b = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+        self._check(self.L.rtggx_set_env_image(self.h, int(layout), int(pixels), int(width), int(height), _p(b), b.size, int(cube_size)))
+
+    def generate_env_mips(self):
+        """The full mip chain below the current level 0 of the environment, rebuilt on the device (include/rtggx.h)."""
+        self._check(self.L.rtggx_generate_env_mips(self.h))
 
     def set_material(self, mesh, base_color, roughness, metallic):
         bc = np.asarray(base_color, np.float32)

@@ -671,6 +671,45 @@ int rtggx_set_env(rtggx_context* c, int format, uint32_t size, uint32_t mips, co
   return decodeEnv(c, format, size, mips, data, bytes, c->streamMain);
 }
 
+// Everything is checked before anything is touched: a refused image leaves the environment, the still-sky runs and the frame as they were.
+int rtggx_set_env_image(rtggx_context* c, int layout, int pixels, uint32_t width, uint32_t height, const void* data, size_t bytes, uint32_t cubeSize) {
+  RT_CHECK_CTX(c);
+  if (!data) { setError("rtggx_set_env_image: null data"); return -1; }
+  if (layout != RTGGX_ENV_EQUIRECT && layout != RTGGX_ENV_VCROSS && layout != RTGGX_ENV_HCROSS) { setError("rtggx_set_env_image: unknown layout %d", layout); return -1; }
+  if (pixels != RTGGX_PIXELS_RGBE8 && pixels != RTGGX_PIXELS_RGB32F) { setError("rtggx_set_env_image: unknown pixel format %d", pixels); return -1; }
+  if (width == 0u || height == 0u) { setError("rtggx_set_env_image: an image of %u x %u pixels", width, height); return -1; }
+  uint32_t size;
+  if (layout == RTGGX_ENV_EQUIRECT) {
+    if (width > 16384u || height > 8192u) { setError("rtggx_set_env_image: a panorama of %u x %u pixels, more than 16384 x 8192", width, height); return -1; }
+    if (cubeSize > 4096u) { setError("rtggx_set_env_image: cube size %u, more than 4096", cubeSize); return -1; }
+    size = cubeSize;
+    if (!size) for (size = 1u; 2u * size <= width / 4u; size *= 2u) {}      // the largest power of two <= width / 4 (1 below 8 columns)
+  } else {
+    const uint32_t across = layout == RTGGX_ENV_VCROSS ? 3u : 4u, down = layout == RTGGX_ENV_VCROSS ? 4u : 3u;
+    if (width % across != 0u || height % down != 0u || width / across != height / down) {
+      setError("rtggx_set_env_image: %u x %u pixels are no %s cross (%u x %u square cells)", width, height, layout == RTGGX_ENV_VCROSS ? "vertical" : "horizontal", across, down); return -1;
+    }
+    size = width / across;
+    if (size > 4096u) { setError("rtggx_set_env_image: a cross of cell %u, more than 4096", size); return -1; }
+    if (cubeSize != 0u) { setError("rtggx_set_env_image: cube size %u given with a cross: its cells are the faces, a cross is never resampled", cubeSize); return -1; }
+  }
+  const size_t need = (size_t)width * height * (pixels == RTGGX_PIXELS_RGBE8 ? 4u : 12u);
+  if (bytes < need) { setError("rtggx_set_env_image: %zu bytes given, %zu needed", bytes, need); return -1; }
+  RT_HIP(syncStreams(c));
+  const int r = buildEnvFromImage(c, layout, pixels, width, height, data, size, c->streamMain);
+  if (r == 0) c->breakSkyRuns();      // the sky behind every pixel is another one (a failed build has left the old one)
+  return r;
+}
+
+int rtggx_generate_env_mips(rtggx_context* c) {
+  RT_CHECK_CTX(c);
+  if (!c->env.texels) { setError("rtggx_generate_env_mips: no environment map"); return -1; }
+  RT_HIP(syncStreams(c));
+  const int r = generateEnvMips(c, c->streamMain);
+  if (r == 0) c->breakSkyRuns();      // every level below the first is another one
+  return r;
+}
+
 int rtggx_set_material(rtggx_context* c, uint32_t mesh, const float baseColor[4], float roughness, float metallic) {
   RT_CHECK_CTX(c);
   if (mesh >= RTGGX_NUM_MESH) { setError("rtggx_set_material: bad mesh"); return -1; }

@@ -213,6 +213,193 @@ int decodeEnv(rtggx_context* c, int format, uint32_t size, uint32_t mips, const 
   return 0;
 }
 
+// ---- environments from images (rtggx_set_env_image, rtggx_generate_env_mips; DESIGN.md "Environments from images") -----------------------
+// Level 0 is built on the device from a cross (a copy of six cells) or a latitude-longitude panorama (one fp64 bilinear tap per cube texel),
+// the chain below it by an exact-coverage box filter, every level in fp32 from the fp32 level above and packed to RGBA16F once.  All of it
+// runs at initialisation only: plain streaming kernels, one lane per texel, 64-bit indices (6 x 4096^2 texels x 16 bytes pass 2^31).
+
+// One source pixel as fp32 rgb: RGBE8 is m 2^(e - 136) per channel (exact; e == 0: black), RGB32F the value as it is; then NaN, negatives and
+// zeros become +0 and everything above the largest finite half becomes it, so that whatever follows is finite and fits a half.
+RT_DEV f3 envPixel(const void* __restrict__ src, int pixels, size_t i) {
+  float r, g, b;
+  if (pixels == RTGGX_PIXELS_RGBE8) {
+    const uint32_t w = reinterpret_cast<const uint32_t*>(src)[i];
+    const int e = (int)(w >> 24);      // bytes r, g, b, e
+    r = e ? ldexpf((float)(w & 255u), e - 136) : 0.0f; g = e ? ldexpf((float)((w >> 8) & 255u), e - 136) : 0.0f; b = e ? ldexpf((float)((w >> 16) & 255u), e - 136) : 0.0f;
+  } else {
+    const float* p = reinterpret_cast<const float*>(src) + 3 * i;
+    r = p[0]; g = p[1]; b = p[2];
+  }
+  return mk3(r > 0.0f ? fminf(r, 65504.0f) : 0.0f, g > 0.0f ? fminf(g, 65504.0f) : 0.0f, b > 0.0f ? fminf(b, 65504.0f) : 0.0f);
+}
+
+// Level 0 from a cross: cube texel (face, y, x) is the pixel at (row c + y, col c + x) of the face's cell; the vertical cross stores -Z
+// turned by 180 degrees (it continues the column +Y, +Z, -Y downwards).
+__constant__ uint8_t kCrossCell[2][6][2] = {{{1, 2}, {1, 0}, {0, 1}, {2, 1}, {1, 1}, {3, 1}},      // vertical: (row, col) of +X -X +Y -Y +Z -Z
+                                            {{1, 2}, {1, 0}, {0, 1}, {2, 1}, {1, 1}, {1, 3}}};     // horizontal
+__global__ void __launch_bounds__(256) envCrossKernel(const void* __restrict__ src, int pixels, uint32_t width, uint32_t cell, int horizontal,
+                                                      float4* __restrict__ level0, uint2* __restrict__ dst) {
+  const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x, perFace = (size_t)cell * cell;
+  if (i >= 6u * perFace) return;
+  const uint32_t face = (uint32_t)(i / perFace), rem = (uint32_t)(i % perFace);
+  uint32_t y = rem / cell, x = rem % cell;
+  if (!horizontal && face == 5u) { y = cell - 1u - y; x = cell - 1u - x; }
+  const size_t row = (size_t)kCrossCell[horizontal][face][0] * cell + y, col = (size_t)kCrossCell[horizontal][face][1] * cell + x;
+  const f3 v = envPixel(src, pixels, row * width + col);
+  level0[i] = make_float4(v.x, v.y, v.z, 1.0f);
+  dst[i] = packRGBA16F(v.x, v.y, v.z, 1.0f);
+}
+
+// Level 0 from a panorama of width x height pixels, rows top to bottom: the direction through the texel's centre, its longitude and latitude
+// (+Z in the middle of the image, +X to its right, +Y in the top row), one bilinear tap -- columns wrap, rows clamp.  Coordinates and
+// weights in fp64, rounded once: the kernel runs once, and what it may differ from a float64 model by is a rounding of the result.
+__global__ void __launch_bounds__(256) envEquirectKernel(const void* __restrict__ src, int pixels, uint32_t width, uint32_t height, uint32_t size,
+                                                         float4* __restrict__ level0, uint2* __restrict__ dst) {
+  const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x, perFace = (size_t)size * size;
+  if (i >= 6u * perFace) return;
+  const uint32_t face = (uint32_t)(i / perFace), rem = (uint32_t)(i % perFace), y = rem / size, x = rem % size;
+  const double u = ((double)x + 0.5) / (double)size * 2.0 - 1.0, w = ((double)y + 0.5) / (double)size * 2.0 - 1.0;
+  double dx, dy, dz;
+  switch (face) {
+    case 0: dx = 1.0; dy = -w; dz = -u; break;
+    case 1: dx = -1.0; dy = -w; dz = u; break;
+    case 2: dx = u; dy = 1.0; dz = w; break;
+    case 3: dx = u; dy = -1.0; dz = -w; break;
+    case 4: dx = u; dy = -w; dz = 1.0; break;
+    default: dx = -u; dy = -w; dz = -1.0; break;
+  }
+  const double len = sqrt(dx * dx + dy * dy + dz * dz);
+  const double pi = 3.14159265358979323846;
+  const double lon = atan2(dx / len, dz / len), lat = asin(fmin(fmax(dy / len, -1.0), 1.0));
+  const double s = (lon / (2.0 * pi) + 0.5) * (double)width - 0.5, t = (0.5 - lat / pi) * (double)height - 0.5;
+  const double s0 = floor(s), t0 = floor(t), fx = s - s0, fy = t - t0;
+  const long long W = (long long)width, H = (long long)height;
+  const long long x0 = (((long long)s0 % W) + W) % W, x1 = (x0 + 1) % W;
+  const long long ty = (long long)t0;
+  const long long y0 = ty < 0 ? 0 : (ty > H - 1 ? H - 1 : ty), y1 = ty + 1 < 0 ? 0 : (ty + 1 > H - 1 ? H - 1 : ty + 1);
+  const f3 a = envPixel(src, pixels, (size_t)(y0 * W + x0)), b = envPixel(src, pixels, (size_t)(y0 * W + x1));
+  const f3 c = envPixel(src, pixels, (size_t)(y1 * W + x0)), d = envPixel(src, pixels, (size_t)(y1 * W + x1));
+  // (no term is negative: nothing cancels, and the sum is as accurate relative to itself as its terms)
+  const float r = (float)((1.0 - fy) * ((1.0 - fx) * (double)a.x + fx * (double)b.x) + fy * ((1.0 - fx) * (double)c.x + fx * (double)d.x));
+  const float g = (float)((1.0 - fy) * ((1.0 - fx) * (double)a.y + fx * (double)b.y) + fy * ((1.0 - fx) * (double)c.y + fx * (double)d.y));
+  const float bl = (float)((1.0 - fy) * ((1.0 - fx) * (double)a.z + fx * (double)b.z) + fy * ((1.0 - fx) * (double)c.z + fx * (double)d.z));
+  level0[i] = make_float4(r, g, bl, 1.0f);
+  dst[i] = packRGBA16F(r, g, bl, 1.0f);
+}
+
+// rtggx_generate_env_mips: the decoded level 0 back in fp32 (every half is one)
+__global__ void __launch_bounds__(256) envWidenKernel(const uint2* __restrict__ texels, float4* __restrict__ level0, size_t n) {
+  const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const f4 v = unpackRGBA16F(texels[i]);
+  level0[i] = make_float4(v.x, v.y, v.z, 1.0f);
+}
+
+// One axis of the box filter that halves a side p to q = p >> 1: child i covers parents 2 i, 2 i + 1 of an even side; of an odd one
+// (p = 2 q + 1) the span [i p / q, (i + 1) p / q), which is (q - i) / q of parent 2 i, all of 2 i + 1 and (i + 1) / q of 2 i + 2 -- integer
+// weights that sum to p.  Every operation is an fp32 operation of its own, in this order (tests/envimage_ref.py restates it bit for bit).
+RT_DEV float envBox(float t0, float t1, float t2, uint32_t i, uint32_t q, bool odd) {
+  if (!odd) return (t0 + t1) / 2.0f;
+  return (((float)(q - i) * t0 + (float)q * t1) + (float)(i + 1u) * t2) / (float)(2u * q + 1u);
+}
+// Level m + 1 from the fp32 level m, each face alone: the horizontal pass of the (up to three) parent rows, then the vertical one -- the
+// separable filter, the rows of its first pass recomputed by the lanes that share them instead of stored.
+__global__ void __launch_bounds__(256) envMipKernel(const float4* __restrict__ parent, uint32_t p, float4* __restrict__ child, uint2* __restrict__ dst) {
+  const uint32_t q = p >> 1;
+  const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x, perFace = (size_t)q * q;
+  if (i >= 6u * perFace) return;
+  const uint32_t face = (uint32_t)(i / perFace), rem = (uint32_t)(i % perFace), y = rem / q, x = rem % q;
+  const bool odd = (p & 1u) != 0u;
+  const float4* f = parent + (size_t)face * p * p;
+  float h[3][3];
+  for (uint32_t k = 0; k < (odd ? 3u : 2u); ++k) {
+    const float4* row = f + (size_t)(2u * y + k) * p + 2u * x;
+    const float4 a = row[0], b = row[1], c = odd ? row[2] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    h[k][0] = envBox(a.x, b.x, c.x, x, q, odd); h[k][1] = envBox(a.y, b.y, c.y, x, q, odd); h[k][2] = envBox(a.z, b.z, c.z, x, q, odd);
+  }
+  if (!odd) h[2][0] = h[2][1] = h[2][2] = 0.0f;
+  const float r = envBox(h[0][0], h[1][0], h[2][0], y, q, odd), g = envBox(h[0][1], h[1][1], h[2][1], y, q, odd), b = envBox(h[0][2], h[1][2], h[2][2], y, q, odd);
+  child[i] = make_float4(r, g, b, 1.0f);
+  dst[i] = packRGBA16F(r, g, b, 1.0f);
+}
+
+static uint32_t fullChain(uint32_t size) { uint32_t mips = 1; while ((size >> mips) != 0u) ++mips; return mips; }
+static uint32_t envBlocks(size_t n) { return (uint32_t)((n + 255u) / 256u); }
+
+// Levels 1 .. of `texels` from the fp32 level 0 in `ping` (`pong`: room for level 1), alternating between the two.
+static void launchEnvChain(uint2* texels, const uint32_t* mipOffset, uint32_t size, uint32_t mips, float4* ping, float4* pong, hipStream_t s) {
+  for (uint32_t m = 1; m < mips; ++m) {
+    const uint32_t p = size >> (m - 1u), q = p >> 1;
+    hipLaunchKernelGGL(envMipKernel, dim3(envBlocks(6u * (size_t)q * q)), dim3(256), 0, s, (const float4*)ping, p, pong, texels + mipOffset[m]);
+    float4* t = ping; ping = pong; pong = t;
+  }
+}
+
+// The new cube takes the context's place only when everything has been built and its mip offsets are on the device: a failure on the way
+// leaves the environment as it was (nothing runs between the copy of the offsets and the swap: the caller has waited for every stream).
+static int installEnv(rtggx_context* c, uint2* texels, uint32_t size, uint32_t mips, const uint32_t* mipOffset, uint64_t total) {
+  uint32_t offsets[16];
+  for (uint32_t m = 0; m < 16u; ++m) offsets[m] = m < mips ? mipOffset[m] : 0u;
+  const hipError_t e = hipMemcpy(c->dEnvMipOffset, offsets, sizeof offsets, hipMemcpyHostToDevice);
+  if (e != hipSuccess) { hipFree(texels); setError("environment: mip offsets: %s", hipGetErrorString(e)); return -2; }
+  if (c->env.texels) hipFree(c->env.texels);
+  c->env.texels = texels; c->env.size = size; c->env.mips = mips; c->env.totalTexels = total;
+  std::memcpy(c->env.mipOffset, offsets, sizeof offsets);
+  c->shDone = false;
+  return 0;
+}
+static uint64_t chainOffsets(uint32_t size, uint32_t mips, uint32_t* mipOffset) {
+  uint64_t texels = 0;
+  for (uint32_t m = 0; m < mips; ++m) { const uint32_t sz = size >> m; mipOffset[m] = (uint32_t)texels; texels += 6ull * sz * sz; }
+  return texels;
+}
+
+// The arguments have been checked by rtggx_set_env_image: the layout and pixel format are known ones, `size` is the cube's side (the cell of
+// a cross), the source holds width x height pixels.
+int buildEnvFromImage(rtggx_context* c, int layout, int pixels, uint32_t width, uint32_t height, const void* hostData, uint32_t size, hipStream_t s) {
+  const uint32_t mips = fullChain(size);
+  uint32_t mipOffset[16];
+  const uint64_t total = chainOffsets(size, mips, mipOffset);
+  const size_t srcBytes = (size_t)width * height * (pixels == RTGGX_PIXELS_RGBE8 ? 4u : 12u), n0 = 6u * (size_t)size * size, h = size >> 1, n1 = 6u * h * h;
+  void* dSrc = nullptr; uint2* texels = nullptr; float4* ping = nullptr; float4* pong = nullptr;
+  hipError_t e = hipMalloc(&dSrc, srcBytes);
+  if (e == hipSuccess) e = hipMalloc(&texels, total * sizeof(uint2));
+  if (e == hipSuccess) e = hipMalloc(&ping, n0 * sizeof(float4));
+  if (e == hipSuccess && n1) e = hipMalloc(&pong, n1 * sizeof(float4));
+  if (e == hipSuccess) e = hipMemcpyAsync(dSrc, hostData, srcBytes, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) {
+    if (layout == RTGGX_ENV_EQUIRECT) hipLaunchKernelGGL(envEquirectKernel, dim3(envBlocks(n0)), dim3(256), 0, s, (const void*)dSrc, pixels, width, height, size, ping, texels);
+    else hipLaunchKernelGGL(envCrossKernel, dim3(envBlocks(n0)), dim3(256), 0, s, (const void*)dSrc, pixels, width, size, layout == RTGGX_ENV_HCROSS ? 1 : 0, ping, texels);
+    launchEnvChain(texels, mipOffset, size, mips, ping, pong, s);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  hipFree(dSrc); hipFree(ping); hipFree(pong);      // (hipFree(nullptr) is a no-op)
+  if (e != hipSuccess) { hipFree(texels); setError("rtggx_set_env_image: %s", hipGetErrorString(e)); return -2; }
+  return installEnv(c, texels, size, mips, mipOffset, total);
+}
+
+int generateEnvMips(rtggx_context* c, hipStream_t s) {
+  const uint32_t size = c->env.size, mips = fullChain(size);
+  uint32_t mipOffset[16];
+  const uint64_t total = chainOffsets(size, mips, mipOffset);
+  const size_t n0 = 6u * (size_t)size * size, h = size >> 1, n1 = 6u * h * h;
+  uint2* texels = nullptr; float4* ping = nullptr; float4* pong = nullptr;
+  hipError_t e = hipMalloc(&texels, total * sizeof(uint2));
+  if (e == hipSuccess) e = hipMalloc(&ping, n0 * sizeof(float4));
+  if (e == hipSuccess && n1) e = hipMalloc(&pong, n1 * sizeof(float4));
+  if (e == hipSuccess) e = hipMemcpyAsync(texels, c->env.texels, n0 * sizeof(uint2), hipMemcpyDeviceToDevice, s);      // level 0 stays what it is
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(envWidenKernel, dim3(envBlocks(n0)), dim3(256), 0, s, (const uint2*)c->env.texels, ping, n0);
+    launchEnvChain(texels, mipOffset, size, mips, ping, pong, s);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  hipFree(ping); hipFree(pong);
+  if (e != hipSuccess) { hipFree(texels); setError("rtggx_generate_env_mips: %s", hipGetErrorString(e)); return -2; }
+  return installEnv(c, texels, size, mips, mipOffset, total);
+}
+
 // ---- SH projection ---------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) shProjectKernel(const uint2* __restrict__ texels, uint32_t size, double* __restrict__ acc) {
   __shared__ double red[256];

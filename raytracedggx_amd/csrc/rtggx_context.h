@@ -464,6 +464,8 @@ int launchDebugEnvironment(rtggx_context* c, const float* dDirs, const float* dL
 int launchDenoise(rtggx_context* c, const FrameParams& fp, int useLds, hipStream_t s, hipEvent_t done = nullptr, bool fuseToneMap = false);      // fuseToneMap: the last kernel also writes the back buffer
 int launchToneMap(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent_t done = nullptr, const uint2* source = nullptr);      // source: an RGBA16F image to tone-map instead of TemporalSSOut[parity]
 int decodeEnv(rtggx_context* c, int format, uint32_t size, uint32_t mips, const void* hostData, size_t bytes, hipStream_t s);
+int buildEnvFromImage(rtggx_context* c, int layout, int pixels, uint32_t width, uint32_t height, const void* hostData, uint32_t size, hipStream_t s);   // rtggx_set_env_image, arguments checked
+int generateEnvMips(rtggx_context* c, hipStream_t s);                                                                                                  // rtggx_generate_env_mips
 int projectSH(rtggx_context* c, hipStream_t s);
 int unpackVisDepth(rtggx_context* c, uint32_t* dVis, uint32_t* dDepth, hipStream_t s);
 int packVisDepth(rtggx_context* c, const uint32_t* dVis, const uint32_t* dDepth, hipStream_t s);

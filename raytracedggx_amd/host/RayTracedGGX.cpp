@@ -1,6 +1,7 @@
 #include <cmath>
 #include <cstring>
 #include "RayTracedGGX.h"
+#include "EnvImageLoader.h"
 
 #include <algorithm>
 #include <cctype>
@@ -24,6 +25,7 @@ RayTracedGGX::~RayTracedGGX() {}
 // LoadPipeline + LoadAssets (RayTracedGGX.cpp:61-279)
 void RayTracedGGX::OnInit() {
   m_rayTracer = std::make_unique<RayTracer>();
+  m_rayTracer->SetEnvOptions(m_envLayout, m_envSize, m_envMips);      // -envlayout, -envsize, -envmips: what Init does with the -env file
   if (!m_rayTracer->Init(m_width, m_height, m_meshFileName.c_str(), m_envFileName.c_str(), m_meshPosScale, m_device))
     throw std::runtime_error("RayTracer::Init failed: " + m_rayTracer->GetLastError());
   m_denoiser = std::make_unique<Denoiser>();
@@ -204,7 +206,7 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
     return (arg[0] == '-' || arg[0] == '/') && lower(arg + 1) == lower(name);
   };
   // On POSIX an absolute path also starts with '/': such a token is a flag only when it names one.
-  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "recursion", "spp", "accumulate", "sampleset", "savereference", "reference", "score"};
+  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "recursion", "spp", "accumulate", "sampleset", "savereference", "reference", "score", "envlayout", "envsize", "envmips"};
   const auto isFlagName = [&](const char* name) { for (const char* f : kFlags) if (lower(name) == f) return true; return false; };
   const auto hasNextArgValue = [&](int i) {
     if (i + 1 >= argc) return false;
@@ -219,6 +221,17 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
       if (hasNextArgValue(i)) m_meshFileName = argv[++i];
       nextFloat(i, m_meshPosScale[0]); nextFloat(i, m_meshPosScale[1]); nextFloat(i, m_meshPosScale[2]); nextFloat(i, m_meshPosScale[3]);
     } else if (isArgMatched(i, "env")) { if (hasNextArgValue(i)) m_envFileName = argv[++i]; }
+    // environments from images (RayTracer::SetEnvOptions): the layout of a .hdr / .pfm image whose aspect ratio does not tell, the side of
+    // the cube a panorama is resampled to, and the mip chain of a DDS cube that came without one built on the device
+    else if (isArgMatched(i, "envlayout")) {
+      if (!hasNextArgValue(i) || !EnvImage::ParseLayoutName(lower(argv[++i]), m_envLayout)) throw std::runtime_error("-envlayout: equirect, vcross or hcross");
+    }
+    else if (isArgMatched(i, "envsize")) {
+      const long size = hasNextArgValue(i) ? std::atol(argv[++i]) : 0;
+      if (size < 1 || size > 4096) throw std::runtime_error("-envsize: the side of the cube, 1 to 4096");
+      m_envSize = (uint32_t)size;
+    }
+    else if (isArgMatched(i, "envmips")) m_envMips = true;
     // extensions replacing the window / message loop
     else if (isArgMatched(i, "width")) { if (hasNextArgValue(i)) m_width = (uint32_t)std::atoi(argv[++i]); }
     else if (isArgMatched(i, "height")) { if (hasNextArgValue(i)) m_height = (uint32_t)std::atoi(argv[++i]); }
@@ -269,6 +282,8 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
     else if (isArgMatched(i, "strips")) { if (hasNextArgValue(i)) m_strips = std::atoi(argv[++i]); if (m_strips < 1 || m_strips > 64) throw std::runtime_error("-strips: 1 .. 64"); }
     else if (isArgMatched(i, "balance")) { if (hasNextArgValue(i)) m_balance = std::atoi(argv[++i]) != 0; }
   }
+  // a cross is never resampled (rtggx_set_env_image); where the layout comes from the image's aspect ratio RayTracer::Init refuses it
+  if (m_envSize != 0u && (m_envLayout == EnvImage::VCROSS || m_envLayout == EnvImage::HCROSS)) throw std::runtime_error("-envsize together with -envlayout vcross / hcross: a cross is never resampled, its cells are the cube's faces");
   // three quarters of a rate-4 frame are interpolations (rtggx_set_accumulation); the sums of several strips are not gathered
   if (m_accumulate != 0u && m_rayRate != 1u) throw std::runtime_error("-accumulate together with -rayrate 4: refused");
   if (m_accumulate != 0u && (m_gpus > 1 || m_strips > 1)) throw std::runtime_error("-accumulate: whole frames on one GPU only, not with -gpus N > 1 or -strips N > 1");

@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "DDSLoader.h"
+#include "EnvImageLoader.h"
 #include "ObjLoader.h"
 
 void HaltonSequence::Next(float& x, float& y) {
@@ -40,22 +41,47 @@ bool RayTracer::Init(uint32_t width, uint32_t height, const char* fileName, cons
                      const float posScale[4], int device) {
   m_width = width; m_height = height;
   std::memcpy(m_posScale, posScale, sizeof m_posScale);
+  const auto fail = [&](const std::string& why) { m_error = why; std::fprintf(stderr, "RayTracer: %s\n", why.c_str()); return false; };
+
+  // The environment file, by its first bytes: read and checked on the host before a device is asked for
+  DDS::CubeImage cube;
+  EnvImage::Image image;
+  int layout = m_envLayout;
+  bool isImage = false;
+  {
+    uint8_t magic[4] = {0, 0, 0, 0};
+    FILE* f = std::fopen(envFileName, "rb");
+    if (!f) return fail(std::string("cannot open ") + envFileName);
+    const size_t got = std::fread(magic, 1, 4, f);
+    std::fclose(f);
+    isImage = EnvImage::IsRadiance(magic, got) || EnvImage::IsPfm(magic, got);
+  }
+  std::string err;
+  if (isImage) {
+    if (!EnvImage::LoadFromFile(envFileName, image, err)) return fail(err);
+    if (layout < 0) layout = EnvImage::LayoutFromAspect(image.width, image.height);
+    if (layout < 0) return fail(std::string(envFileName) + ": " + std::to_string(image.width) + " x " + std::to_string(image.height) + " pixels are neither 3:4 (vertical cross), 4:3 (horizontal cross) nor 2:1 (panorama): name the layout with -envlayout equirect|vcross|hcross");
+    if (layout != EnvImage::EQUIRECT && m_envCubeSize != 0u) return fail("-envsize: a cross is never resampled, its cells are the cube's faces (" + std::string(envFileName) + " is a " + (layout == EnvImage::VCROSS ? "vertical" : "horizontal") + " cross)");
+    if (m_envGenerateMips) std::fprintf(stderr, "RayTracer: -envmips has no effect on %s: an image always gets its full mip chain\n", envFileName);
+  } else {
+    if (!DDS::Loader().LoadCubeFromFile(envFileName, cube, err)) return fail(err);      // (RayTracer.cpp:143-150)
+    if (m_envLayout >= 0 || m_envCubeSize != 0u) std::fprintf(stderr, "RayTracer: -envlayout / -envsize have no effect on %s: a DDS cube is taken as it is\n", envFileName);
+  }
+
   if (!check(rtggx_create(&m_ctx, width, height, device), "rtggx_create")) return false;   // render targets + ground mesh + materials
 
   // Load inputs (RayTracer.cpp:83-86)
   ObjLoader objLoader;
-  if (!objLoader.Import(fileName, true, true)) { m_error = std::string("cannot import ") + fileName; std::fprintf(stderr, "RayTracer: %s\n", m_error.c_str()); return false; }
+  if (!objLoader.Import(fileName, true, true)) return fail(std::string("cannot import ") + fileName);
   m_numVerts = objLoader.GetNumVertices(); m_numIndices = objLoader.GetNumIndices();
   m_modelVerts.assign(reinterpret_cast<const float*>(objLoader.GetVertices()), reinterpret_cast<const float*>(objLoader.GetVertices()) + 6 * (size_t)m_numVerts);
   if (!check(rtggx_set_mesh(m_ctx, MODEL_OBJ, reinterpret_cast<const float*>(objLoader.GetVertices()), m_numVerts,
                             objLoader.GetIndices(), m_numIndices), "rtggx_set_mesh")) return false;
 
-  // Load input image (RayTracer.cpp:143-150)
-  DDS::Loader textureLoader;
-  DDS::CubeImage cube;
-  std::string err;
-  if (!textureLoader.LoadCubeFromFile(envFileName, cube, err)) { m_error = err; std::fprintf(stderr, "RayTracer: %s\n", err.c_str()); return false; }
+  if (isImage) return check(rtggx_set_env_image(m_ctx, layout, image.pixels, image.width, image.height, image.data.data(), image.data.size(), m_envCubeSize), "rtggx_set_env_image");
   if (!check(rtggx_set_env(m_ctx, cube.format, cube.size, cube.mips, cube.payload.data(), cube.payload.size()), "rtggx_set_env")) return false;
+  uint32_t full = 1; while ((cube.size >> full) != 0u) ++full;
+  if (m_envGenerateMips && cube.mips < full && !check(rtggx_generate_env_mips(m_ctx), "rtggx_generate_env_mips")) return false;
   return true;
 }
 

@@ -28,10 +28,16 @@ class RayTracer {
   RayTracer();
   virtual ~RayTracer();
 
-  // Loads the mesh (OBJ) and the environment (DDS cube), creates the render targets and uploads
-  // everything.  posScale = (x, y, z, scale) of the model instance.
+  // Loads the mesh (OBJ) and the environment, creates the render targets and uploads everything.  posScale = (x, y, z, scale) of the
+  // model instance.  The environment is told by the file's first bytes: "DDS " a cube with its mip chain (rtggx_set_env), "#?" a Radiance
+  // .hdr and "PF" a .pfm image (EnvImageLoader.h, rtggx_set_env_image) -- read, and a bad one refused, before anything touches a GPU.
   bool Init(uint32_t width, uint32_t height, const char* fileName, const char* envFileName,
             const float posScale[4], int device = 0);
+  // What Init does with the environment file (-envlayout, -envsize, -envmips); to be called before it.  layout: RTGGX_ENV_* or -1 = by the
+  // image's aspect ratio (3:4 vertical cross, 4:3 horizontal cross, 2:1 panorama; anything else is refused).  cubeSize: the cube's side for a
+  // panorama (0: the largest power of two <= width / 4); refused with a cross, whose cells are the faces.  generateMips: a DDS cube with
+  // fewer levels than a full chain gets the chain built on the device (rtggx_generate_env_mips).
+  void SetEnvOptions(int layout, uint32_t cubeSize, bool generateMips) { m_envLayout = layout; m_envCubeSize = cubeSize; m_envGenerateMips = generateMips; }
   bool BuildAccelerationStructures();
   bool Postinit();
 
@@ -82,6 +88,7 @@ class RayTracer {
   float m_posScale[4] = {0.0f, 0.0f, 0.0f, 1.0f};
   uint32_t m_numVerts = 0, m_numIndices = 0;
   std::vector<float> m_modelVerts;
+  int m_envLayout = -1; uint32_t m_envCubeSize = 0; bool m_envGenerateMips = false;      // SetEnvOptions
 
   // state UpdateFrame keeps between frames (statics / members in the reference)
   HaltonSequence m_halton;

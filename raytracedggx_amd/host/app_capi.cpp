@@ -4,6 +4,7 @@
 #include <exception>
 #include <string>
 #include <vector>
+#include "EnvImageLoader.h"
 #include "ObjLoader.h"
 #include "RayTracedGGX.h"
 #include "Strips.h"
@@ -79,6 +80,21 @@ int rtggx_host_read_pfm(const char* path, uint32_t w, uint32_t h, uint16_t* rgba
   std::vector<uint16_t> image; std::string error;
   if (!ReadPfm(path, w, h, image, error)) { g_appError = error; return -1; }
   std::memcpy(rgba16f, image.data(), image.size() * 2);
+  return 0;
+}
+
+// The Radiance / PFM readers on their own (no device): the image's pixel format (0 RGBE8, 1 RGB32F), size, the layout its aspect ratio
+// tells (0 panorama, 1 vertical cross, 2 horizontal cross, -1 none) and the bytes it takes; the pixels, rows top to bottom, are copied
+// where `capacity` holds them (call once with 0 for the size).
+int rtggx_host_load_env_image(const char* path, int* pixels, uint32_t* width, uint32_t* height, int* layout, void* data, size_t capacity, size_t* bytes) {
+  EnvImage::Image image; std::string error;
+  if (!EnvImage::LoadFromFile(path, image, error)) { g_appError = error; return -1; }
+  if (pixels) *pixels = image.pixels;
+  if (width) *width = image.width;
+  if (height) *height = image.height;
+  if (layout) *layout = EnvImage::LayoutFromAspect(image.width, image.height);
+  if (bytes) *bytes = image.data.size();
+  if (data && capacity >= image.data.size()) std::memcpy(data, image.data.data(), image.data.size());
   return 0;
 }
 
