@@ -436,7 +436,7 @@ int  rtggx_tone_map(rtggx_context* ctx);
  * always runs as a kernel of its own.  Diagnostic: mode 0 = always two kernels, 1 = always fused, -1 = the library's choice again;
  * the back buffer and TemporalSSOut are bit-identical either way. */
 int  rtggx_debug_fuse_tone_map(rtggx_context* ctx, int mode);
-/* Diagnostic: which streams a frame's kernels go to is decided from five facts (capi.hip placeFrame: small launch, strip, deforming
+/* Diagnostic: which streams a frame's kernels go to is decided from five facts (frame.hip placeFrame: small launch, strip, deforming
  * mesh, diffuse rays, caller-owned main stream).  force_small = 0 / 1 pins the first of them whatever the ray count says (-1: by the
  * count again).  key / where (may be null): the most recent rtggx_ray_trace's key (bit 0 small, 1 strip, 2 deforming, 3 diffuse,
  * 4 caller-owned stream) and placement (bits 0-3 / 4-7 / 8-11 / 16-19: stream of ray generation / traversal / hit shading / the visibility pass --

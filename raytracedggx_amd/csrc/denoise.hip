@@ -672,8 +672,8 @@ static Targets makeTargets(rtggx_context* c, const FrameParams& fp, RowPass pass
   T.histReach = strip ? c->histReach : nullptr;
   // the other ranks' history images (rtggx_set_history_peers): the table lives in device memory, [parity][rank]
   const bool peers = strip && c->peerWorld > 1u && c->dPeerTable != nullptr;
-  T.peerHist = peers ? reinterpret_cast<const uint2* const*>(c->dPeerTable) + (c->frameParity ^ 1u) * RT_MAX_PEERS : nullptr;
-  T.peerBounds = peers ? reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint2* const*>(c->dPeerTable) + 2 * RT_MAX_PEERS) : nullptr;
+  T.peerHist = peers ? reinterpret_cast<const uint2* const*>(c->dPeerTable.get()) + (c->frameParity ^ 1u) * RT_MAX_PEERS : nullptr;
+  T.peerBounds = peers ? reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint2* const*>(c->dPeerTable.get()) + 2 * RT_MAX_PEERS) : nullptr;
   T.peerWorld = peers ? (int)c->peerWorld : 0;
   { uint32_t gb, ge; passRows(fp, ROWS_GBUFFER, gb, ge);      // the tiles are ray generation's
     T.tileWords = c->tileWords(gb, ge); T.tilesX = (int)((fp.W + 15) / 16); T.tileRow0 = (int)gb; }
@@ -714,7 +714,7 @@ int launchDenoise(rtggx_context* c, const FrameParams& fp, int useLds, hipStream
   // to do (the reflection V pass already wrote FilteredOut1) and are not launched.
   const bool anyDiffuse = fp.mat.RoughMetals[0][1] < 1.0f || fp.mat.RoughMetals[1][1] < 1.0f;
   // FilteredOut is read by the diffuse V pass only.  Without diffuse passes the reflection V pass writes FilteredOut1 alone (the two
-  // images would be identical, 8 bytes per pixel each); rtggx_readback(RTGGX_BUF_FLT_RFL) then returns FilteredOut1 (capi.hip).
+  // images would be identical, 8 bytes per pixel each); rtggx_readback(RTGGX_BUF_FLT_RFL) then returns FilteredOut1 (debug.hip).
   c->fltRflIsFltDff = !anyDiffuse;
   Targets TVr = TV; if (!anyDiffuse) TVr.fltRfl = nullptr;
   { uint32_t epoch;      // (the direct-access variant converts every sky texel; it counts as the previous pass all the same)

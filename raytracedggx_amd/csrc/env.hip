@@ -172,17 +172,17 @@ int decodeEnv(rtggx_context* c, int format, uint32_t size, uint32_t mips, const 
   }
   if (format != RTGGX_FORMAT_BC6H_UF16 && format != RTGGX_FORMAT_BC6H_SF16 && format != RTGGX_FORMAT_RGBA16F && format != RTGGX_FORMAT_RGBA32F) { setError("rtggx_set_env: unsupported format %d", format); return -1; }
   if (bytes < perFace * 6) { setError("rtggx_set_env: %zu bytes given, %zu needed", bytes, perFace * 6); return -1; }
-  if (c->env.texels) { RT_HIP(hipFree(c->env.texels)); c->env.texels = nullptr; }
-  RT_HIP(hipMalloc(&c->env.texels, texels * sizeof(uint2)));
+  c->env.texels.reset();
+  RT_HIP(alloc(c->env.texels, texels));
   c->env.size = size; c->env.mips = mips; c->env.totalTexels = texels;
-  void* dSrc = nullptr;
-  RT_HIP(hipMalloc(&dSrc, perFace * 6));
+  DevBuf<char> dSrc;
+  RT_HIP(alloc(dSrc, perFace * 6));
   RT_HIP(hipMemcpyAsync(dSrc, hostData, perFace * 6, hipMemcpyHostToDevice, s));
-  Bc6Mode* dModes = nullptr;
+  DevBuf<Bc6Mode> dModes;
   const bool bc6h = format == RTGGX_FORMAT_BC6H_UF16 || format == RTGGX_FORMAT_BC6H_SF16;
   if (bc6h) {
     std::vector<Bc6Mode> modes; buildModeTable(modes);
-    RT_HIP(hipMalloc(&dModes, sizeof(Bc6Mode) * 14));
+    RT_HIP(alloc(dModes, 14));
     RT_HIP(hipMemcpyAsync(dModes, modes.data(), sizeof(Bc6Mode) * 14, hipMemcpyHostToDevice, s));
     RT_HIP(hipStreamSynchronize(s));   // `modes` is about to go out of scope
   }
@@ -206,8 +206,6 @@ int decodeEnv(rtggx_context* c, int format, uint32_t size, uint32_t mips, const 
   }
   RT_HIP(hipGetLastError());
   RT_HIP(hipStreamSynchronize(s));
-  hipFree(dSrc);
-  if (dModes) hipFree(dModes);
   RT_HIP(hipMemcpy(c->dEnvMipOffset, c->env.mipOffset, 16 * sizeof(uint32_t), hipMemcpyHostToDevice));
   c->shDone = false;
   return 0;
@@ -337,13 +335,12 @@ static void launchEnvChain(uint2* texels, const uint32_t* mipOffset, uint32_t si
 
 // The new cube takes the context's place only when everything has been built and its mip offsets are on the device: a failure on the way
 // leaves the environment as it was (nothing runs between the copy of the offsets and the swap: the caller has waited for every stream).
-static int installEnv(rtggx_context* c, uint2* texels, uint32_t size, uint32_t mips, const uint32_t* mipOffset, uint64_t total) {
+static int installEnv(rtggx_context* c, DevBuf<uint2>& texels, uint32_t size, uint32_t mips, const uint32_t* mipOffset, uint64_t total) {
   uint32_t offsets[16];
   for (uint32_t m = 0; m < 16u; ++m) offsets[m] = m < mips ? mipOffset[m] : 0u;
   const hipError_t e = hipMemcpy(c->dEnvMipOffset, offsets, sizeof offsets, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { hipFree(texels); setError("environment: mip offsets: %s", hipGetErrorString(e)); return -2; }
-  if (c->env.texels) hipFree(c->env.texels);
-  c->env.texels = texels; c->env.size = size; c->env.mips = mips; c->env.totalTexels = total;
+  if (e != hipSuccess) { setError("environment: mip offsets: %s", hipGetErrorString(e)); return -2; }
+  c->env.texels = std::move(texels); c->env.size = size; c->env.mips = mips; c->env.totalTexels = total;
   std::memcpy(c->env.mipOffset, offsets, sizeof offsets);
   c->shDone = false;
   return 0;
@@ -361,11 +358,11 @@ int buildEnvFromImage(rtggx_context* c, int layout, int pixels, uint32_t width, 
   uint32_t mipOffset[16];
   const uint64_t total = chainOffsets(size, mips, mipOffset);
   const size_t srcBytes = (size_t)width * height * (pixels == RTGGX_PIXELS_RGBE8 ? 4u : 12u), n0 = 6u * (size_t)size * size, h = size >> 1, n1 = 6u * h * h;
-  void* dSrc = nullptr; uint2* texels = nullptr; float4* ping = nullptr; float4* pong = nullptr;
-  hipError_t e = hipMalloc(&dSrc, srcBytes);
-  if (e == hipSuccess) e = hipMalloc(&texels, total * sizeof(uint2));
-  if (e == hipSuccess) e = hipMalloc(&ping, n0 * sizeof(float4));
-  if (e == hipSuccess && n1) e = hipMalloc(&pong, n1 * sizeof(float4));
+  DevBuf<void> dSrc; DevBuf<uint2> texels; DevBuf<float4> ping, pong;
+  hipError_t e = alloc(dSrc, srcBytes);
+  if (e == hipSuccess) e = alloc(texels, total);
+  if (e == hipSuccess) e = alloc(ping, n0);
+  if (e == hipSuccess && n1) e = alloc(pong, n1);
   if (e == hipSuccess) e = hipMemcpyAsync(dSrc, hostData, srcBytes, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) {
     if (layout == RTGGX_ENV_EQUIRECT) hipLaunchKernelGGL(envEquirectKernel, dim3(envBlocks(n0)), dim3(256), 0, s, (const void*)dSrc, pixels, width, height, size, ping, texels);
@@ -374,8 +371,7 @@ int buildEnvFromImage(rtggx_context* c, int layout, int pixels, uint32_t width, 
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  hipFree(dSrc); hipFree(ping); hipFree(pong);      // (hipFree(nullptr) is a no-op)
-  if (e != hipSuccess) { hipFree(texels); setError("rtggx_set_env_image: %s", hipGetErrorString(e)); return -2; }
+  if (e != hipSuccess) { setError("rtggx_set_env_image: %s", hipGetErrorString(e)); return -2; }
   return installEnv(c, texels, size, mips, mipOffset, total);
 }
 
@@ -384,10 +380,10 @@ int generateEnvMips(rtggx_context* c, hipStream_t s) {
   uint32_t mipOffset[16];
   const uint64_t total = chainOffsets(size, mips, mipOffset);
   const size_t n0 = 6u * (size_t)size * size, h = size >> 1, n1 = 6u * h * h;
-  uint2* texels = nullptr; float4* ping = nullptr; float4* pong = nullptr;
-  hipError_t e = hipMalloc(&texels, total * sizeof(uint2));
-  if (e == hipSuccess) e = hipMalloc(&ping, n0 * sizeof(float4));
-  if (e == hipSuccess && n1) e = hipMalloc(&pong, n1 * sizeof(float4));
+  DevBuf<uint2> texels; DevBuf<float4> ping, pong;
+  hipError_t e = alloc(texels, total);
+  if (e == hipSuccess) e = alloc(ping, n0);
+  if (e == hipSuccess && n1) e = alloc(pong, n1);
   if (e == hipSuccess) e = hipMemcpyAsync(texels, c->env.texels, n0 * sizeof(uint2), hipMemcpyDeviceToDevice, s);      // level 0 stays what it is
   if (e == hipSuccess) {
     hipLaunchKernelGGL(envWidenKernel, dim3(envBlocks(n0)), dim3(256), 0, s, (const uint2*)c->env.texels, ping, n0);
@@ -395,8 +391,7 @@ int generateEnvMips(rtggx_context* c, hipStream_t s) {
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  hipFree(ping); hipFree(pong);
-  if (e != hipSuccess) { hipFree(texels); setError("rtggx_generate_env_mips: %s", hipGetErrorString(e)); return -2; }
+  if (e != hipSuccess) { setError("rtggx_generate_env_mips: %s", hipGetErrorString(e)); return -2; }
   return installEnv(c, texels, size, mips, mipOffset, total);
 }
 
@@ -445,15 +440,14 @@ __global__ void shFinalizeKernel(const double* __restrict__ acc, float* __restri
 
 int projectSH(rtggx_context* c, hipStream_t s) {
   if (!c->env.texels) { setError("rtggx_transform_sh: no environment map"); return -1; }
-  double* acc = nullptr;
-  RT_HIP(hipMalloc(&acc, 28 * sizeof(double)));
+  DevBuf<double> acc;
+  RT_HIP(alloc(acc, 28));
   RT_HIP(hipMemsetAsync(acc, 0, 28 * sizeof(double), s));
   const uint32_t n = 6u * c->env.size * c->env.size;
   hipLaunchKernelGGL(shProjectKernel, dim3((n + 255) / 256), dim3(256), 0, s, c->env.texels, c->env.size, acc);
   hipLaunchKernelGGL(shFinalizeKernel, dim3(1), dim3(64), 0, s, acc, c->sh);
   RT_HIP(hipGetLastError());
   RT_HIP(hipStreamSynchronize(s));
-  hipFree(acc);
   c->shDone = true;
   return 0;
 }

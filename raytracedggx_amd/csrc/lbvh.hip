@@ -821,7 +821,7 @@ __global__ void refitTris(int n, const uint32_t* __restrict__ order, const float
   for (int k = 0; k < 3; ++k) { triBox[6 * (size_t)prim + k] = mn[k]; triBox[6 * (size_t)prim + 3 + k] = mx[k]; }
 }
 // Sum of the half-areas of all node boxes: the tree's SAH cost up to constants.  A refit keeps the topology the build chose for
-// the OLD shape; when this sum has grown by RT_REFIT_REBUILD_RATIO the host rebuilds (capi.hip).
+// the OLD shape; when this sum has grown by RT_REFIT_REBUILD_RATIO the host rebuilds (mesh.hip).
 __global__ void __launch_bounds__(256) treeCostKernel(int numNodes, const float* __restrict__ nodeBox, float* __restrict__ cost) {
   __shared__ float red[4];
   float a = 0.0f;
@@ -882,70 +882,56 @@ int buildFatTris(rtggx_context* c, uint32_t slot, uint32_t set, hipStream_t s) {
   return 0;
 }
 
-// Buffers that exist once per input set when the mesh deforms and alias one allocation while it is static.
-template <typename T> static void freeAliased(T* (&buf)[RT_SETS]) {
-  for (int i = 0; i < RT_SETS; ++i) { bool dup = false; for (int j = 0; j < i; ++j) dup = dup || buf[j] == buf[i]; if (!dup && buf[i]) hipFree(buf[i]); }
-  for (auto& b : buf) b = nullptr;
-}
-static void freeTopo(BvhTopo& t) {
-  hipFree(t.order); hipFree(t.left); hipFree(t.right); hipFree(t.nodeParent); hipFree(t.leafParent); hipFree(t.nodeBox); hipFree(t.triBox);
-  for (auto& c : t.cnt) { hipFree(c); c = nullptr; }
-  hipFree(t.roundBase); hipFree(t.dTreelets); hipFree(t.dRefitItems); hipFree(t.dRefitRounds); hipFree(t.treeletRoots); hipFree(t.topList); hipFree(t.topRank); hipFree(t.ent4); hipFree(t.lvl4); hipFree(t.cost4); hipFree(t.dResult);
-  if (t.hResult) hipHostFree(t.hResult);
-  t = BvhTopo{};
-}
-
 // ---- a build as a list of launches ------------------------------------------------------------------------------------------------
 struct BuildScratch {
-  uint32_t *codes[2] = {}, *order2 = nullptr, *hist = nullptr, *chunkSums = nullptr, *bounds = nullptr;
-  int32_t *clRef[2] = {}, *nn = nullptr; float* clBox[2] = {}; uint2* blockCounts = nullptr; PlocState* state = nullptr;
-  float* vertsSnapshot = nullptr;      // a rebuild beside the frames works on a copy of the vertices it started from
+  DevBuf<uint32_t> codes[2], order2, hist, chunkSums, bounds;
+  DevBuf<int32_t> clRef[2], nn; DevBuf<float> clBox[2]; DevBuf<uint2> blockCounts; DevBuf<PlocState> state;
+  DevBuf<float> vertsSnapshot;         // a rebuild beside the frames works on a copy of the vertices it started from
 };
 struct BuildJob {
   BvhTopo topo;                        // what the build produces (swapped with the mesh's when it has ended)
   BuildScratch s;
   std::vector<std::function<void(hipStream_t)>> steps;      // one kernel launch (or copy) each
   size_t next = 0;
-  hipEvent_t done = nullptr;
+  Event done;
   bool active = false, allIssued = false;
   uint32_t numTris = 0, numVerts = 0;
 };
-static void freeScratch(BuildScratch& s) {
-  hipFree(s.codes[0]); hipFree(s.codes[1]); hipFree(s.order2); hipFree(s.hist); hipFree(s.chunkSums); hipFree(s.bounds);
-  hipFree(s.clRef[0]); hipFree(s.clRef[1]); hipFree(s.nn); hipFree(s.clBox[0]); hipFree(s.clBox[1]); hipFree(s.blockCounts); hipFree(s.state); hipFree(s.vertsSnapshot);
-  s = BuildScratch{};
-}
+MeshDev::MeshDev() = default; MeshDev::~MeshDev() = default;
+// The tree of every input set, the topology and a rebuild in progress go; the caller has synchronised.
 void freeBuildProducts(MeshDev& m) {
-  if (m.job) { if (m.job->done) hipEventDestroy(m.job->done); freeTopo(m.job->topo); freeScratch(m.job->s); delete m.job; m.job = nullptr; }
-  freeTopo(m.topo);
-  freeAliased(m.nodesBuf); freeAliased(m.nodes4Buf); freeAliased(m.trisBuf); freeAliased(m.topBuf);
+  m.job.reset();
+  m.topo = BvhTopo{};
+  for (int i = 0; i < RT_SETS; ++i) {
+    m.nodesOwn[i].reset(); m.nodes4Own[i].reset(); m.trisOwn[i].reset(); m.topOwn[i].reset();
+    m.nodesBuf[i] = nullptr; m.nodes4Buf[i] = nullptr; m.trisBuf[i] = nullptr; m.topBuf[i] = nullptr; m.topCountBuf[i] = 0;
+  }
   m.nodes = nullptr; m.nodes4 = nullptr; m.tris = nullptr; m.top = nullptr; m.topCount = 0;
-  for (auto& t : m.topCountBuf) t = 0;
 }
 static int allocTopo(BvhTopo& t, uint32_t n) {
   const size_t nn = n > 1 ? n : 2;
   t.numTris = n;
-  RT_HIP(hipMalloc(&t.order, 4 * nn)); RT_HIP(hipMalloc(&t.left, 4 * nn)); RT_HIP(hipMalloc(&t.right, 4 * nn));
-  RT_HIP(hipMalloc(&t.nodeParent, 4 * nn)); RT_HIP(hipMalloc(&t.leafParent, 4 * nn));
-  RT_HIP(hipMalloc(&t.nodeBox, 24 * nn)); RT_HIP(hipMalloc(&t.triBox, 24 * nn));
-  for (auto& c : t.cnt) RT_HIP(hipMalloc(&c, 4 * nn));
-  RT_HIP(hipMalloc(&t.roundBase, 4 * (RT_MAX_ROUNDS + 1)));
-  RT_HIP(hipMalloc(&t.dTreelets, sizeof(RefitTreelet) * nn)); RT_HIP(hipMalloc(&t.dRefitItems, sizeof(int4) * nn)); RT_HIP(hipMalloc(&t.dRefitRounds, 4 * (2 * nn + 64)));
-  RT_HIP(hipMalloc(&t.treeletRoots, 4 * nn));
-  RT_HIP(hipMalloc(&t.topList, 4 * 128)); RT_HIP(hipMalloc(&t.topRank, 4 * nn));
-  RT_HIP(hipMalloc(&t.ent4, sizeof(int4) * nn)); RT_HIP(hipMalloc(&t.lvl4, 4 * nn)); RT_HIP(hipMalloc(&t.cost4, sizeof(float4) * nn));
-  RT_HIP(hipMalloc(&t.dResult, sizeof(BuildResult))); RT_HIP(hipHostMalloc(&t.hResult, sizeof(BuildResult)));
+  RT_HIP(alloc(t.order, nn)); RT_HIP(alloc(t.left, nn)); RT_HIP(alloc(t.right, nn));
+  RT_HIP(alloc(t.nodeParent, nn)); RT_HIP(alloc(t.leafParent, nn));
+  RT_HIP(alloc(t.nodeBox, 6 * nn)); RT_HIP(alloc(t.triBox, 6 * nn));
+  for (auto& c : t.cnt) RT_HIP(alloc(c, nn));
+  RT_HIP(alloc(t.roundBase, RT_MAX_ROUNDS + 1));
+  RT_HIP(alloc(t.dTreelets, sizeof(RefitTreelet) * nn)); RT_HIP(alloc(t.dRefitItems, sizeof(int4) * nn)); RT_HIP(alloc(t.dRefitRounds, 2 * nn + 64));
+  RT_HIP(alloc(t.treeletRoots, nn));
+  RT_HIP(alloc(t.topList, 128)); RT_HIP(alloc(t.topRank, nn));
+  RT_HIP(alloc(t.ent4, nn)); RT_HIP(alloc(t.lvl4, nn)); RT_HIP(alloc(t.cost4, nn));
+  RT_HIP(alloc(t.dResult, 1)); RT_HIP(alloc(t.hResult, 1));
   memset(t.hResult, 0, sizeof(BuildResult));
   return 0;
 }
 static int allocScratch(BuildScratch& s, uint32_t n, uint32_t nv, bool snapshot) {
   const size_t nn = n > 1 ? n : 2, nb = (n + 255) / 256;
-  RT_HIP(hipMalloc(&s.codes[0], 4 * nn)); RT_HIP(hipMalloc(&s.codes[1], 4 * nn)); RT_HIP(hipMalloc(&s.order2, 4 * nn));
-  RT_HIP(hipMalloc(&s.hist, 4 * 256 * nb)); RT_HIP(hipMalloc(&s.chunkSums, 4 * ((256 * nb + 1023) / 1024 + 1))); RT_HIP(hipMalloc(&s.bounds, 4 * 8));
-  RT_HIP(hipMalloc(&s.clRef[0], 4 * nn)); RT_HIP(hipMalloc(&s.clRef[1], 4 * nn)); RT_HIP(hipMalloc(&s.nn, 4 * nn));
-  RT_HIP(hipMalloc(&s.clBox[0], 24 * nn)); RT_HIP(hipMalloc(&s.clBox[1], 24 * nn));
-  RT_HIP(hipMalloc(&s.blockCounts, sizeof(uint2) * nb)); RT_HIP(hipMalloc(&s.state, 2 * sizeof(PlocState)));
-  if (snapshot) RT_HIP(hipMalloc(&s.vertsSnapshot, sizeof(float) * 6 * (size_t)nv));
+  RT_HIP(alloc(s.codes[0], nn)); RT_HIP(alloc(s.codes[1], nn)); RT_HIP(alloc(s.order2, nn));
+  RT_HIP(alloc(s.hist, 256 * nb)); RT_HIP(alloc(s.chunkSums, (256 * nb + 1023) / 1024 + 1)); RT_HIP(alloc(s.bounds, 8));
+  RT_HIP(alloc(s.clRef[0], nn)); RT_HIP(alloc(s.clRef[1], nn)); RT_HIP(alloc(s.nn, nn));
+  RT_HIP(alloc(s.clBox[0], 6 * nn)); RT_HIP(alloc(s.clBox[1], 6 * nn));
+  RT_HIP(alloc(s.blockCounts, nb)); RT_HIP(alloc(s.state, 2));
+  if (snapshot) RT_HIP(alloc(s.vertsSnapshot, 6 * (size_t)nv));
   return 0;
 }
 // How many multi-workgroup rounds the host issues: until RT_PLOC_STOP clusters are expected to be left if every round kept RT_PLOC_KEEP of
@@ -963,72 +949,72 @@ static uint32_t plocRoundsFor(uint32_t n) {
 static void planBuildSteps(rtggx_context* c, uint32_t slot, BuildJob& job, const float* verts, const float* snapshotFrom) {
   MeshDev& m = c->mesh[slot];
   const uint32_t n = job.numTris, nv = job.numVerts, nb = (n + 255) / 256;
-  BvhTopo& t = job.topo; BuildScratch& s = job.s;
+  BvhTopo* const t = &job.topo; BuildScratch* const s = &job.s;      // (the steps read the job's arrays where they stand: they run while the job holds them)
   auto& steps = job.steps;
   steps.clear(); job.next = 0; job.allIssued = false;
   const uint32_t* indices = m.indices;
-  if (snapshotFrom) { steps.push_back([=](hipStream_t st) { hipMemcpyAsync(s.vertsSnapshot, snapshotFrom, sizeof(float) * 6 * (size_t)nv, hipMemcpyDeviceToDevice, st); }); verts = s.vertsSnapshot; }
-  steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(buildBegin, dim3(1), dim3(64), 0, st, n, s.state, t.dResult, s.bounds); });
-  steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(boundsKernel, dim3(std::min<uint32_t>((nv + 255) / 256, 64u)), dim3(256), 0, st, verts, nv, s.bounds); });
-  steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(mortonKernel, dim3(nb), dim3(256), 0, st, verts, indices, n, (const uint32_t*)s.bounds, s.codes[0], t.order, t.triBox); });
-  // radix sort: (codes[0], t.order) <-> (codes[1], s.order2); four passes end where they began
+  if (snapshotFrom) { steps.push_back([=](hipStream_t st) { hipMemcpyAsync(s->vertsSnapshot, snapshotFrom, sizeof(float) * 6 * (size_t)nv, hipMemcpyDeviceToDevice, st); }); verts = s->vertsSnapshot; }
+  steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(buildBegin, dim3(1), dim3(64), 0, st, n, s->state, t->dResult, s->bounds); });
+  steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(boundsKernel, dim3(std::min<uint32_t>((nv + 255) / 256, 64u)), dim3(256), 0, st, verts, nv, s->bounds); });
+  steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(mortonKernel, dim3(nb), dim3(256), 0, st, verts, indices, n, (const uint32_t*)s->bounds, s->codes[0], t->order, t->triBox); });
+  // radix sort: (codes[0], t->order) <-> (codes[1], s->order2); four passes end where they began
   for (int pass = 0; pass < 4; ++pass) {
     const int shift = pass * 8, cur = pass & 1;
-    uint32_t *kin = s.codes[cur], *kout = s.codes[cur ^ 1], *vin = cur ? s.order2 : t.order, *vout = cur ? t.order : s.order2;
-    steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(radixHist, dim3(nb), dim3(256), 0, st, (const uint32_t*)kin, n, shift, s.hist, nb); });
+    uint32_t *kin = s->codes[cur], *kout = s->codes[cur ^ 1], *vin = cur ? s->order2 : t->order, *vout = cur ? t->order : s->order2;
+    steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(radixHist, dim3(nb), dim3(256), 0, st, (const uint32_t*)kin, n, shift, s->hist, nb); });
     const uint32_t chunks = (256u * nb + 1023u) / 1024u;
-    steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(scanChunks, dim3(chunks), dim3(1024), 0, st, s.hist, 256u * nb, s.chunkSums); });
-    steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(scanTotals, dim3(1), dim3(1024), 0, st, s.chunkSums, chunks); });
-    steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(radixScatter, dim3(nb), dim3(256), 0, st, (const uint32_t*)kin, (const uint32_t*)vin, n, shift, (const uint32_t*)s.hist, (const uint32_t*)s.chunkSums, nb, kout, vout); });
+    steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(scanChunks, dim3(chunks), dim3(1024), 0, st, s->hist, 256u * nb, s->chunkSums); });
+    steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(scanTotals, dim3(1), dim3(1024), 0, st, s->chunkSums, chunks); });
+    steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(radixScatter, dim3(nb), dim3(256), 0, st, (const uint32_t*)kin, (const uint32_t*)vin, n, shift, (const uint32_t*)s->hist, (const uint32_t*)s->chunkSums, nb, kout, vout); });
   }
-  t.root = n == 1 ? ~0 : -1; t.refittable = false;
+  t->root = n == 1 ? ~0 : -1; t->refittable = false;
   if (n > 1) {
     const int radius = RT_PLOC_RADIUS;
     {
-      t.root = (int32_t)n - 2; t.refittable = true;      // the last node created
+      t->root = (int32_t)n - 2; t->refittable = true;      // the last node created
       PlocArrays A;
-      A.clRef[0] = s.clRef[0]; A.clRef[1] = s.clRef[1]; A.clBox[0] = s.clBox[0]; A.clBox[1] = s.clBox[1]; A.nn = s.nn;
-      A.left = t.left; A.right = t.right; A.nodeParent = t.nodeParent; A.leafParent = t.leafParent; A.nodeBox = t.nodeBox;
-      for (int l = 0; l < RT_TREELET_LEVELS; ++l) A.cnt[l] = t.cnt[l];
-      A.roundBase = t.roundBase; A.res = t.dResult;
-      steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(plocInit, dim3(nb), dim3(256), 0, st, (int)n, (const uint32_t*)t.order, (const float*)t.triBox, s.clRef[0], s.clBox[0]); });
+      A.clRef[0] = s->clRef[0]; A.clRef[1] = s->clRef[1]; A.clBox[0] = s->clBox[0]; A.clBox[1] = s->clBox[1]; A.nn = s->nn;
+      A.left = t->left; A.right = t->right; A.nodeParent = t->nodeParent; A.leafParent = t->leafParent; A.nodeBox = t->nodeBox;
+      for (int l = 0; l < RT_TREELET_LEVELS; ++l) A.cnt[l] = t->cnt[l];
+      A.roundBase = t->roundBase; A.res = t->dResult;
+      steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(plocInit, dim3(nb), dim3(256), 0, st, (int)n, (const uint32_t*)t->order, (const float*)t->triBox, s->clRef[0], s->clBox[0]); });
       const uint32_t rounds = plocRoundsFor(n);
       for (uint32_t r = 0; r < rounds; ++r) {
-        steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(plocNearest, dim3(nb), dim3(256 * RT_PLOC_LANES), 0, st, (const PlocState*)s.state, r, radius, A, s.blockCounts); });
-        steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(plocScatter, dim3(nb), dim3(256), 0, st, s.state, r, (const uint2*)s.blockCounts, A); });
+        steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(plocNearest, dim3(nb), dim3(256 * RT_PLOC_LANES), 0, st, (const PlocState*)s->state, r, radius, A, s->blockCounts); });
+        steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(plocScatter, dim3(nb), dim3(256), 0, st, s->state, r, (const uint2*)s->blockCounts, A); });
       }
-      steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(plocFinal, dim3(1), dim3(1024), 0, st, (const PlocState*)s.state, rounds, radius, n, A); });
+      steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(plocFinal, dim3(1), dim3(1024), 0, st, (const PlocState*)s->state, rounds, radius, n, A); });
       // leaf slots in depth-first order (a subtree's triangles are consecutive); scratch: codes[1] = ranks, order2 / clRef[0] = the moved arrays
-      steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(leafRankKernel, dim3(nb), dim3(256), 0, st, (int)n, (const int32_t*)t.left, (const int32_t*)t.right, (const int32_t*)t.nodeParent, (const int32_t*)t.leafParent,
-                                                               (const uint32_t*)t.cnt[0], s.codes[1]); });
-      steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(leafPermuteKernel, dim3(nb), dim3(256), 0, st, (int)n, (const uint32_t*)s.codes[1], (const uint32_t*)t.order, (const int32_t*)t.leafParent,
-                                                               s.order2, s.clRef[0], t.left, t.right); });
-      steps.push_back([=](hipStream_t st) { hipMemcpyAsync(t.order, s.order2, 4 * (size_t)n, hipMemcpyDeviceToDevice, st); });
-      steps.push_back([=](hipStream_t st) { hipMemcpyAsync(t.leafParent, s.clRef[0], 4 * (size_t)n, hipMemcpyDeviceToDevice, st); });
+      steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(leafRankKernel, dim3(nb), dim3(256), 0, st, (int)n, (const int32_t*)t->left, (const int32_t*)t->right, (const int32_t*)t->nodeParent, (const int32_t*)t->leafParent,
+                                                               (const uint32_t*)t->cnt[0], s->codes[1]); });
+      steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(leafPermuteKernel, dim3(nb), dim3(256), 0, st, (int)n, (const uint32_t*)s->codes[1], (const uint32_t*)t->order, (const int32_t*)t->leafParent,
+                                                               s->order2, s->clRef[0], t->left, t->right); });
+      steps.push_back([=](hipStream_t st) { hipMemcpyAsync(t->order, s->order2, 4 * (size_t)n, hipMemcpyDeviceToDevice, st); });
+      steps.push_back([=](hipStream_t st) { hipMemcpyAsync(t->leafParent, s->clRef[0], 4 * (size_t)n, hipMemcpyDeviceToDevice, st); });
       // the refit schedule
       const uint32_t treeletGrid = std::min<uint32_t>(std::max<uint32_t>((n + RT_TREELET_NODES / 4 - 1) / (RT_TREELET_NODES / 4), 1u), 2048u);
       for (int l = 0; l < RT_TREELET_LEVELS; ++l) {
-        const uint32_t* prev = l ? t.cnt[l - 1] : nullptr; const uint32_t* cur = t.cnt[l];
-        steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(treeletRootsKernel, dim3(nb), dim3(256), 0, st, (int)n - 1, l, prev, cur, (const int32_t*)t.nodeParent, t.treeletRoots, t.dResult); });
-        steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(buildTreeletsKernel, dim3(l ? 64u : treeletGrid), dim3(256), 0, st, l, prev, (const int32_t*)t.left, (const int32_t*)t.right,
-                                                                 (const int32_t*)t.treeletRoots, (RefitTreelet*)t.dTreelets, (int4*)t.dRefitItems, t.dRefitRounds, t.dResult); });
+        const uint32_t* prev = l ? t->cnt[l - 1] : nullptr; const uint32_t* cur = t->cnt[l];
+        steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(treeletRootsKernel, dim3(nb), dim3(256), 0, st, (int)n - 1, l, prev, cur, (const int32_t*)t->nodeParent, t->treeletRoots, t->dResult); });
+        steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(buildTreeletsKernel, dim3(l ? 64u : treeletGrid), dim3(256), 0, st, l, prev, (const int32_t*)t->left, (const int32_t*)t->right,
+                                                                 (const int32_t*)t->treeletRoots, (RefitTreelet*)t->dTreelets.get(), (int4*)t->dRefitItems.get(), t->dRefitRounds, t->dResult); });
       }
     }
     const uint32_t topCap = slot == 0 ? RT_TOP_SLOT0 : RT_TOP_SLOT1;
-    const int32_t root = t.root;
-    steps.push_back([=](hipStream_t st) { hipMemsetAsync(t.topRank, 0xFF, 4 * (size_t)(n - 1), st); });
+    const int32_t root = t->root;
+    steps.push_back([=](hipStream_t st) { hipMemsetAsync(t->topRank, 0xFF, 4 * (size_t)(n - 1), st); });
     // the 4-wide collapse (by surface area), then the table of its top
     const float wArea = c->collapseWeights[0], wTris = c->collapseWeights[1];
     for (int l = 0; l < RT_TREELET_LEVELS; ++l)
       steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(collapseCostTreelets, dim3(l ? 64u : std::min<uint32_t>(std::max<uint32_t>((n + RT_TREELET_NODES / 4 - 1) / (RT_TREELET_NODES / 4), 1u), 2048u)), dim3(256), 0, st, l,
-                                                               (const RefitTreelet*)t.dTreelets, (const int4*)t.dRefitItems, (const uint32_t*)t.dRefitRounds, (const float*)t.nodeBox, (const uint32_t*)t.cnt[0], root, wArea, wTris, t.cost4, (const BuildResult*)t.dResult); });
-    steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(entries4Kernel, dim3(nb), dim3(256), 0, st, (int)n - 1, (const int32_t*)t.left, (const int32_t*)t.right, (const float4*)t.cost4, t.ent4); });
-    steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(roots4Kernel, dim3(nb), dim3(256), 0, st, (int)n - 1, (const int32_t*)t.nodeParent, (const int4*)t.ent4, t.lvl4, t.dResult); });
-    steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(planTopKernel, dim3(1), dim3(128), 0, st, topCap, root, n - 1, (const int4*)t.ent4, t.topList, t.topRank, t.dResult); });
-    steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(depthKernel, dim3(nb), dim3(256), 0, st, (int)n, (const int32_t*)t.nodeParent, (const int32_t*)t.leafParent, &t.dResult->depth); });
-    steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(treeCostKernel, dim3(std::min<uint32_t>((n - 1 + 255) / 256, 48u)), dim3(256), 0, st, (int)n - 1, (const float*)t.nodeBox, &t.dResult->cost); });
+                                                               (const RefitTreelet*)t->dTreelets.get(), (const int4*)t->dRefitItems.get(), (const uint32_t*)t->dRefitRounds, (const float*)t->nodeBox, (const uint32_t*)t->cnt[0], root, wArea, wTris, t->cost4, (const BuildResult*)t->dResult); });
+    steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(entries4Kernel, dim3(nb), dim3(256), 0, st, (int)n - 1, (const int32_t*)t->left, (const int32_t*)t->right, (const float4*)t->cost4, t->ent4); });
+    steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(roots4Kernel, dim3(nb), dim3(256), 0, st, (int)n - 1, (const int32_t*)t->nodeParent, (const int4*)t->ent4, t->lvl4, t->dResult); });
+    steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(planTopKernel, dim3(1), dim3(128), 0, st, topCap, root, n - 1, (const int4*)t->ent4, t->topList, t->topRank, t->dResult); });
+    steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(depthKernel, dim3(nb), dim3(256), 0, st, (int)n, (const int32_t*)t->nodeParent, (const int32_t*)t->leafParent, &t->dResult->depth); });
+    steps.push_back([=](hipStream_t st) { hipLaunchKernelGGL(treeCostKernel, dim3(std::min<uint32_t>((n - 1 + 255) / 256, 48u)), dim3(256), 0, st, (int)n - 1, (const float*)t->nodeBox, &t->dResult->cost); });
   }
-  steps.push_back([=](hipStream_t st) { hipMemcpyAsync(t.hResult, t.dResult, sizeof(BuildResult), hipMemcpyDeviceToHost, st); });
+  steps.push_back([=](hipStream_t st) { hipMemcpyAsync(t->hResult, t->dResult, sizeof(BuildResult), hipMemcpyDeviceToHost, st); });
 }
 
 // The tree arrays of input set `set` from a topology and that set's vertices: leaf triangles, 64-byte binary nodes (for the oracle /
@@ -1083,8 +1069,8 @@ int buildLbvh(rtggx_context* c, uint32_t slot, hipStream_t s) {
   for (auto& step : job.steps) step(s);
   RT_HIP(hipGetLastError());
   RT_HIP(hipStreamSynchronize(s));
-  m.topo = job.topo; job.topo = BvhTopo{};
-  freeScratch(job.s);
+  m.topo = std::move(job.topo);
+  job.s = BuildScratch{};
   { const int r = harvest(m, m.topo, slot); if (r) return r; }
   m.root = m.topo.root;
   m.builtCost = m.lastCost = m.topo.result.cost; m.costInFlight = false;
@@ -1092,8 +1078,9 @@ int buildLbvh(rtggx_context* c, uint32_t slot, hipStream_t s) {
   const size_t nn = n > 1 ? n - 1 : 1, topCap = slot == 0 ? RT_TOP_SLOT0 : RT_TOP_SLOT1;
   const int sets = m.deforming ? RT_SETS : 1;
   for (int i = 0; i < sets; ++i) {
-    RT_HIP(hipMalloc(&m.trisBuf[i], sizeof(BvhTri) * (size_t)n)); RT_HIP(hipMalloc(&m.nodesBuf[i], sizeof(BvhNode) * nn)); RT_HIP(hipMalloc(&m.nodes4Buf[i], sizeof(Bvh4Node) * nn));
-    RT_HIP(hipMalloc(&m.topBuf[i], sizeof(Bvh4Node) * topCap));
+    RT_HIP(alloc(m.trisOwn[i], (size_t)n)); RT_HIP(alloc(m.nodesOwn[i], nn)); RT_HIP(alloc(m.nodes4Own[i], nn));
+    RT_HIP(alloc(m.topOwn[i], topCap));
+    m.trisBuf[i] = m.trisOwn[i]; m.nodesBuf[i] = m.nodesOwn[i]; m.nodes4Buf[i] = m.nodes4Own[i]; m.topBuf[i] = m.topOwn[i];
   }
   for (int i = sets; i < RT_SETS; ++i) { m.trisBuf[i] = m.trisBuf[0]; m.nodesBuf[i] = m.nodesBuf[0]; m.nodes4Buf[i] = m.nodes4Buf[0]; m.topBuf[i] = m.topBuf[0]; }
   ++m.topoVersion;
@@ -1113,7 +1100,7 @@ int buildLbvh(rtggx_context* c, uint32_t slot, hipStream_t s) {
 }
 
 // ---- a rebuild beside the frames (meshes that deform) -------------------------------------------------------------------------------
-// A refit keeps the topology the last build chose for ANOTHER shape; when the tree's cost has drifted (capi.hip rtggx_refit_as) the mesh
+// A refit keeps the topology the last build chose for ANOTHER shape; when the tree's cost has drifted (mesh.hip rtggx_refit_as) the mesh
 // is built anew from the vertices of input set `set` -- copied first: the set moves on --, a few launches per frame on the stream the
 // refits run on, behind the frame's refit.  When the last launch has ended (the host polls an event at the start of a frame) the new
 // topology replaces the old one: the frame's refit, a moment later on the same stream, is the first to use it.  The buffers of the two
@@ -1124,13 +1111,13 @@ int buildLbvh(rtggx_context* c, uint32_t slot, hipStream_t s) {
 int prepareRebuild(rtggx_context* c, uint32_t slot) {
   MeshDev& m = c->mesh[slot];
   if (m.job || !m.topo.refittable || m.numTris < 2) return 0;
-  BuildJob* job = new BuildJob();
+  std::unique_ptr<BuildJob> job(new BuildJob());
   job->numTris = m.numTris; job->numVerts = m.numVerts;
   int r = allocTopo(job->topo, m.numTris);
   if (!r) r = allocScratch(job->s, m.numTris, m.numVerts, true);
-  if (!r && hipEventCreateWithFlags(&job->done, hipEventDisableTiming) != hipSuccess) { setError("prepareRebuild: hipEventCreate failed"); r = -2; }
-  if (r) { if (job->done) hipEventDestroy(job->done); freeTopo(job->topo); freeScratch(job->s); delete job; return r; }
-  m.job = job;
+  if (!r && create(job->done, hipEventDisableTiming) != hipSuccess) { setError("prepareRebuild: hipEventCreate failed"); r = -2; }
+  if (r) return r;
+  m.job = std::move(job);
   return 0;
 }
 int startRebuild(rtggx_context* c, uint32_t slot, uint32_t set) {
@@ -1171,7 +1158,7 @@ void abandonRebuild(rtggx_context* c, uint32_t slot) {
 
 
 static int launchTreeCost(MeshDev& m, hipStream_t s) {
-  if (!m.dCost) { RT_HIP(hipMalloc(&m.dCost, 4)); RT_HIP(hipHostMalloc(&m.hCost, 4)); *m.hCost = 0.0f; RT_HIP(hipEventCreateWithFlags(&m.evCost, hipEventDisableTiming)); }
+  if (!m.dCost) { RT_HIP(alloc(m.dCost, 1)); RT_HIP(alloc(m.hCost, 1)); *m.hCost = 0.0f; RT_HIP(create(m.evCost, hipEventDisableTiming)); }
   RT_HIP(hipMemsetAsync(m.dCost, 0, 4, s));
   const int numNodes = (int)m.numTris - 1;
   hipLaunchKernelGGL(treeCostKernel, dim3(std::min((numNodes + 255) / 256, 48)), dim3(256), 0, s, numNodes, (const float*)m.topo.nodeBox, m.dCost);
@@ -1195,7 +1182,7 @@ int refitLbvh(rtggx_context* c, uint32_t slot, uint32_t set, hipStream_t s) {
     uint32_t first = 0;
     for (int l = 0; l < RT_TREELET_LEVELS; ++l) {      // level after level
       const uint32_t k = t.result.treelets[l];
-      if (k) hipLaunchKernelGGL(refitTreelets, dim3(k), dim3(256), 0, s, (const RefitTreelet*)t.dTreelets + first, (const int4*)t.dRefitItems, (const uint32_t*)t.dRefitRounds,
+      if (k) hipLaunchKernelGGL(refitTreelets, dim3(k), dim3(256), 0, s, (const RefitTreelet*)t.dTreelets.get() + first, (const int4*)t.dRefitItems.get(), (const uint32_t*)t.dRefitRounds,
                                 (const uint32_t*)t.order, (const float*)t.triBox, t.nodeBox);
       first += k;
     }

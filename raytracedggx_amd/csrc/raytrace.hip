@@ -18,7 +18,7 @@
 //                  the tail of computeReflection / computeDiffuse, with Material.hlsli,
 //                  BRDFModels.hlsli, SHIrradianceTypeless.hlsli:16-37; writes RayTracingOut0/1.
 //
-// rayGenKernel and traceKernel run on stream B, shadeKernel on the main stream one frame behind (capi.hip).
+// rayGenKernel and traceKernel run on stream B, shadeKernel on the main stream one frame behind (frame.hip).
 // Roofline: HBM by decree of the metric (no MFMA work exists here).  Algorithmic bytes:
 // rayGen 18 B/pixel (+64 B per queued ray); trace 64 B ray + 16 B hit per ray + the scene arrays
 // once; shade 64+16 B in, 4 B out per ray.  The BVH (<= 14 MB) is L2/MALL resident, so traversal is
@@ -1029,12 +1029,12 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
   G.diffPrev = c->genCarriesDiff ? c->prev().rtDiff : nullptr;
   G.fat0 = c->mesh[0].fat; G.fat1 = c->mesh[1].fat;
   G.env = c->env.texels; G.envMipOffset = c->dEnvMipOffset; G.envSize = c->env.size; G.envMips = c->env.mips; G.cosSin = c->sampleTable();
-  G.rays = (RayRec*)set.rayQueue; G.hits = (HitKey*)set.hitQueue; G.binCount = set.binCount; G.binSlots = c->binSlots; G.frameRays = c->rayCounter32;
+  G.rays = (RayRec*)set.rayQueue.get(); G.hits = (HitKey*)set.hitQueue.get(); G.binCount = set.binCount; G.binSlots = c->binSlots; G.frameRays = c->rayCounter32;
   G.tilesX = tilesX; G.numTiles = tilesX * tilesY; G.rowBegin = rb; G.rowEnd = re;
   const uint32_t splitWork = c->splitWork, splitMaxShift = c->splitMaxShift;
   const uint32_t numBins = quad ? quadX * quadY * 4u : G.numTiles * 4u;
   const uint32_t sliceShift = chooseSliceShift(c, true, numBins);
-  // "wide" launches: few enough rays that the traversal does not fill the chip for long (trace.hip launchTrace, capi.hip rtggx_ray_trace)
+  // "wide" launches: few enough rays that the traversal does not fill the chip for long (trace.hip launchTrace, frame.hip rtggx_ray_trace)
   c->lastTraceSmall = c->forcePlacement >= 0 ? c->forcePlacement == 1 : (sliceShift > 0u || c->lastFrameRays < RT_WIDE_RAYS);
   const bool adaptive = splitWork != 0u && sliceShift == 0u;
   // the split list is sized from the demand of an earlier frame (copied back asynchronously, like the ray counters)
@@ -1097,7 +1097,7 @@ static int launchShadeSamples(rtggx_context* c, const FrameParams& fp, hipStream
   const uint32_t N = c->samples, depth = c->maxDepth;
   const bool wide = c->sampleSet > RTGGX_MIN_SAMPLE_SET;
   if (!c->sppAcc || !c->sppParams) { setError("rtggx_ray_trace: %u samples per pixel without their buffers", N); return -1; }
-  // the sums exist once: the previous frame's passes may have run on another stream (small launches alternate two; capi.hip rtggx_ray_trace)
+  // the sums exist once: the previous frame's passes may have run on another stream (small launches alternate two; frame.hip rtggx_ray_trace)
   if (c->sppStream && c->sppStream != s) { RT_HIP(hipEventRecord(c->evSpp, c->sppStream)); RT_HIP(hipStreamWaitEvent(s, c->evSpp, 0)); }
   c->sppStream = s;
   const InputSet& set = c->cur();
@@ -1141,22 +1141,22 @@ int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent
   // ... unless ray generation has carried those pixels over already.  It can when the previous frame's shading kernel wrote nothing
   // into the previous set's image (no diffuse rays, no carrying): that image was final when the previous ray generation ended, earlier
   // on the same stream.  The steady state of an all-metal scene: 8 bytes per covered pixel less (this loop reads the visibility word
-  // again), and no dependency between the shading kernels of consecutive frames (capi.hip rtggx_ray_trace).
+  // again), and no dependency between the shading kernels of consecutive frames (frame.hip rtggx_ray_trace).
   if (c->genCarriesDiff) S.carryMask = 0u;
   S.tileWords = c->tileWords(rb, re);
   const bool quad = c->rayRate == 4u;      // (rate 4: 32x32 tiles, and RayTracingOut1 is carried over by launchReconstruct)
   const uint32_t grid = quad ? ((tilesX + 1u) / 2u) * ((re - rb + 31u) / 32u) : numTiles;
   if (quad) S.carryMask = 0u;
-  S.rays = (const RayRec*)set.rayQueue; S.hits = (const HitKey*)set.hitQueue; S.binCount = set.binCount; S.binSlots = c->binSlots;
+  S.rays = (const RayRec*)set.rayQueue.get(); S.hits = (const HitKey*)set.hitQueue.get(); S.binCount = set.binCount; S.binSlots = c->binSlots;
   S.fat0 = c->mesh[0].fat; S.fat1 = c->mesh[1].fat;
   S.env = c->env.texels; S.envMipOffset = c->dEnvMipOffset; S.envSize = c->env.size; S.envMips = c->env.mips; S.sh = c->sh;
   S.reflOut = set.rtRefl; S.diffOut = set.rtDiff;
-  S.spawnRays = (RayRec*)set.rayQueue; S.spawnHits = (HitKey*)set.hitQueue; S.spawnCount = set.binCount; S.cosSin = c->sampleTable();
+  S.spawnRays = (RayRec*)set.rayQueue.get(); S.spawnHits = (HitKey*)set.hitQueue.get(); S.spawnCount = set.binCount; S.cosSin = c->sampleTable();
   S.accRefl = nullptr; S.accDiff = nullptr;
   const FrameParams* const dfp = c->dParams + c->slot;
   const uint32_t depth = c->maxDepth;
   // Levels 1.. run behind this stream's shading of the level before, beside the next frame's level-0 traversal (stream B): a part of the
-  // spill area of their own on the main stream; on a traversal stream (small launches, capi.hip) that stream's own, in stream order
+  // spill area of their own on the main stream; on a traversal stream (small launches, frame.hip) that stream's own, in stream order
   const int spillPart = s == c->streamMain ? 2 : (int)c->traceSpillHalf;
   if (c->samples > 1u && !quad) return launchShadeSamples(c, fp, s, done, S, numTiles, spillPart);
   for (uint32_t level = 0; level < depth; ++level) {
@@ -1231,12 +1231,12 @@ int launchTraceRays(rtggx_context* c, const FrameParams& fp, const float* dRays,
   const InputSet& set = c->cur();
   RT_HIP(hipMemsetAsync(set.binCount, 0, (size_t)numBins * 4, s));
   // the rays' own (TMin, TMax): one float2 per slot, kept for the context's lifetime once a caller has used this entry point
-  if (!c->testRayRange) RT_HIP(hipMalloc(&c->testRayRange, (size_t)c->numBinsMax * RT_BIN * sizeof(float2)));
-  hipLaunchKernelGGL(fillTestQueue, dim3((n + 255) / 256), dim3(256), 0, s, dRays, n, c->binSlots, (RayRec*)set.rayQueue, (HitKey*)set.hitQueue, set.binCount, (float2*)c->testRayRange);
+  if (!c->testRayRange) RT_HIP(alloc(c->testRayRange, (size_t)c->numBinsMax * RT_BIN * sizeof(float2)));
+  hipLaunchKernelGGL(fillTestQueue, dim3((n + 255) / 256), dim3(256), 0, s, dRays, n, c->binSlots, (RayRec*)set.rayQueue.get(), (HitKey*)set.hitQueue.get(), set.binCount, (float2*)c->testRayRange.get());
   c->traceRayRange = c->testRayRange;
-  const TraceQueue q{(const RayRec*)set.rayQueue, (HitKey*)set.hitQueue, set.binCount};
+  const TraceQueue q{(const RayRec*)set.rayQueue.get(), (HitKey*)set.hitQueue.get(), set.binCount};
   { const int r = launchTrace(c, fp, s, q, numBins, false, 0u, 0u, chooseSliceShift(c, false, numBins), -1); c->traceRayRange = nullptr; if (r) return r; }
-  hipLaunchKernelGGL(exportTestHits, dim3((n + 255) / 256), dim3(256), 0, s, c->dParams + c->slot, (const RayRec*)set.rayQueue, (const HitKey*)set.hitQueue, n,
+  hipLaunchKernelGGL(exportTestHits, dim3((n + 255) / 256), dim3(256), 0, s, c->dParams + c->slot, (const RayRec*)set.rayQueue.get(), (const HitKey*)set.hitQueue.get(), n,
                      (const float4*)c->mesh[0].fat, (const float4*)c->mesh[1].fat, dOut);
   RT_HIP(hipGetLastError());
   return 0;

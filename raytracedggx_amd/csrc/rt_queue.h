@@ -14,7 +14,7 @@ namespace rt {
 // Ray slots per bin (48-byte ray record + 8-byte hit key per slot): a bin is a wave's 8x8 pixel sub-tile, at most one reflection ray per
 // pixel -- and one diffuse ray where a material's metallic is below 1.  The context allocates RT_BIN_MIN slots per bin while both
 // materials are fully metallic (the sample's default) and grows to RT_BIN with the first frame whose constants carry a metallic below 1
-// (capi.hip rtggx_update_frame; round 3: the bins are the largest allocation of an input set, and three kernels stride over them).
+// (frame.hip rtggx_update_frame; round 3: the bins are the largest allocation of an input set, and three kernels stride over them).
 #define RT_BIN 128u
 #define RT_BIN_MIN 64u
 
@@ -26,7 +26,7 @@ namespace rt {
 // (2400 -> 3200): every extra wave of a split bin is wave-slot time the other two stages want.  The trace kernel alone gets slower
 // (0.120 -> 0.134 ms), the frame faster (0.2207 -> 0.2119 ms; dragon -5 %, 4K -3 %).
 #ifndef RT_SPLIT_FRONT
-#define RT_WIDE_RAYS 200000u     // launches with fewer rays than this: two traversals in flight (capi.hip rtggx_ray_trace)
+#define RT_WIDE_RAYS 200000u     // launches with fewer rays than this: two traversals in flight (frame.hip rtggx_ray_trace)
 #define RT_TINY_RAYS 40000u      // ... and with fewer than this: single-wave workgroups, one per item (trace.hip launchTrace)
 #define RT_SPLIT_FRONT 300u  // above this a bin goes on the list: the launch starts with the listed bins
 #endif

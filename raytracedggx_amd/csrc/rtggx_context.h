@@ -19,7 +19,9 @@
 #include <string>
 #include <utility>
 #include <vector>
+#include <memory>
 #include "rtggx_device.h"
+#include "rt_owned_hip.h"
 
 // Input sets (G-buffer, traced images, ray bins): RT_SETS of them, used round-robin.  Stream B fills set i while the main stream
 // still consumes the set of the frame before; before stream B is given the work that overwrites a set, the HOST waits
@@ -75,60 +77,65 @@ struct BuildResult {
 // level), the list of nodes at the tree's top.  All of it is produced on the device without a host round trip; the host learns a
 // handful of counts (BuildResult) when the build has ended.
 struct BvhTopo {
-  uint32_t* order = nullptr;     // leaf slot -> primitive (Morton order)
-  int32_t *left = nullptr, *right = nullptr, *nodeParent = nullptr, *leafParent = nullptr;
-  float *nodeBox = nullptr, *triBox = nullptr;
-  uint32_t* cnt[RT_TREELET_LEVELS] = {};     // per node: nodes of its subtree that treelet level l still has to place
-  uint32_t* roundBase = nullptr;             // device: first node of PLOC round k
-  void *dTreelets = nullptr, *dRefitItems = nullptr; uint32_t* dRefitRounds = nullptr; int32_t* treeletRoots = nullptr;
-  int32_t *topList = nullptr, *topRank = nullptr;
-  float4* cost4 = nullptr;       // the collapse's dynamic programme per binary node: F(n, 1..3) and the choices (lbvh.hip collapseCostTreelets)
-  int4* ent4 = nullptr; uint32_t* lvl4 = nullptr;      // the 4-wide collapse: per binary node the entries it has as a 4-wide node, and its level there (~0: it is not one)
-  BuildResult* dResult = nullptr; BuildResult* hResult = nullptr;      // device record, pinned copy
+  DevBuf<uint32_t> order;        // leaf slot -> primitive (Morton order)
+  DevBuf<int32_t> left, right, nodeParent, leafParent;
+  DevBuf<float> nodeBox, triBox;
+  DevBuf<uint32_t> cnt[RT_TREELET_LEVELS];   // per node: nodes of its subtree that treelet level l still has to place
+  DevBuf<uint32_t> roundBase;                // device: first node of PLOC round k
+  DevBuf<void> dTreelets, dRefitItems; DevBuf<uint32_t> dRefitRounds; DevBuf<int32_t> treeletRoots;
+  DevBuf<int32_t> topList, topRank;
+  DevBuf<float4> cost4;          // the collapse's dynamic programme per binary node: F(n, 1..3) and the choices (lbvh.hip collapseCostTreelets)
+  DevBuf<int4> ent4; DevBuf<uint32_t> lvl4;            // the 4-wide collapse: per binary node the entries it has as a 4-wide node, and its level there (~0: it is not one)
+  DevBuf<BuildResult> dResult; PinnedBuf<BuildResult> hResult;         // device record, pinned copy
   BuildResult result{};                      // the host's copy, valid once the build has ended
   uint32_t numTris = 0; int32_t root = -1;
   bool refittable = false;                   // a PLOC build of more than one triangle (the refit needs its rounds)
 };
 
 struct MeshDev {
-  float* verts = nullptr;        // 6 floats per vertex: the buffer of the CURRENT input set (selectSet)
+  MeshDev(); ~MeshDev();         // (lbvh.hip, where BuildJob is complete)
+  // Owner and view: every array that exists once per input set when the mesh deforms and once while it is static is an array of owners
+  // (xOwn: a static mesh fills entry 0 alone) and an array of views (xBuf: what the kernels are given, all entries valid, all equal to entry
+  // 0 while the mesh is static).  verts, fat, nodes, nodes4, tris, top: views of the CURRENT input set's entry (selectSet).
+  float* verts = nullptr;        // view; 6 floats per vertex
   // A mesh whose vertices change per frame (rtggx_refit_as) keeps one vertex buffer per input set: the shading of frame f on the
   // main stream still reads the vertices of frame f while stream B already moves them for frame f + 1.  A static mesh has one
   // allocation, and the three pointers alias it.
-  float* vertsBuf[RT_SETS] = {};
+  DevBuf<float> vertsOwn[RT_SETS]; float* vertsBuf[RT_SETS] = {};
   // "Fat triangles": per primitive its three 24-byte vertices side by side (80 bytes = 5 x 16: p0 n0 p1 n1 p2 n2 + 8 pad), indexed by
   // primitive id.  Ray generation and hit shading fetch a triangle's vertices with five 16-byte loads in ONE dependent step instead of
   // three index loads followed by eighteen 4-byte loads (two steps): these kernels are latency-bound (profiles/r02_d_limiter.txt).
   // Per input set like the vertices; rebuilt from them by a refit.
-  float4* fat = nullptr; float4* fatBuf[RT_SETS] = {};
+  float4* fat = nullptr; DevBuf<float4> fatOwn[RT_SETS]; float4* fatBuf[RT_SETS] = {};
   uint32_t vertsVersion[RT_SETS] = {}, version = 0, latestSet = 0;
   bool deforming = false;
-  float* stage[RT_SLOTS] = {};   // pinned host staging ring for the vertices handed to rtggx_refit_as
+  PinnedBuf<float> stage[RT_SLOTS];   // pinned host staging ring for the vertices handed to rtggx_refit_as
   uint32_t stageNext = 0; int pendingStage = -1;
-  float* deviceStage[RT_SLOTS] = {};   // device-side staging ring of rtggx_refit_as_device; the events that order it against the caller's stream
-  uint32_t deviceStageNext = 0; int pendingDeviceStage = -1; hipEvent_t evProduced = nullptr, evStaged = nullptr;
+  DevBuf<float> deviceStage[RT_SLOTS];   // device-side staging ring of rtggx_refit_as_device; the events that order it against the caller's stream
+  uint32_t deviceStageNext = 0; int pendingDeviceStage = -1; Event evProduced, evStaged;
   // what a build derives from one vertex shape and a refit keeps: `topo` (BvhTopo above); `job`: a build in progress (lbvh.hip BuildJob)
   BvhTopo topo;
-  struct BuildJob* job = nullptr;
+  std::unique_ptr<struct BuildJob> job;
   bool wantRebuild = false;      // the refitted tree's cost has drifted: the next frame starts a rebuild
   uint32_t topoVersion = 0, topoVersionOfSet[RT_SETS] = {};      // a set whose tree arrays were emitted for an older topology is emitted in full by its next refit
-  float* dCost = nullptr;        // device: sum of the node-box half-areas of the current tree (SAH cost up to constants)
-  float* hCost = nullptr;        // pinned: its copy, refreshed asynchronously after every refit
-  hipEvent_t evCost = nullptr; bool costInFlight = false;
+  DevBuf<float> dCost;           // device: sum of the node-box half-areas of the current tree (SAH cost up to constants)
+  PinnedBuf<float> hCost;        // pinned: its copy, refreshed asynchronously after every refit
+  Event evCost; bool costInFlight = false;
   float builtCost = 0.0f, lastCost = 0.0f;
   uint32_t refits = 0, rebuilds = 0;
-  uint32_t* indices = nullptr;
+  DevBuf<uint32_t> indices;
   uint32_t numVerts = 0, numIndices = 0, numTris = 0;
-  BvhNode* nodes = nullptr;      // numTris - 1 (0 when numTris == 1): the binary LBVH as built
-  Bvh4Node* nodes4 = nullptr;    // same count, sparse: the 4-wide collapse the trace kernel walks
-  BvhTri* tris = nullptr;        // numTris, leaf (Morton) order
+  BvhNode* nodes = nullptr;      // view; numTris - 1 (0 when numTris == 1): the binary LBVH as built
+  Bvh4Node* nodes4 = nullptr;    // view; same count, sparse: the 4-wide collapse the trace kernel walks
+  BvhTri* tris = nullptr;        // view; numTris, leaf (Morton) order
   // the three above are those of the CURRENT input set: like the vertices, the boxes and leaf triangles of a deforming mesh exist
   // once per input set (frame f + 1's refit on stream R writes its set while frame f's traversal still walks the other)
+  DevBuf<BvhNode> nodesOwn[RT_SETS]; DevBuf<Bvh4Node> nodes4Own[RT_SETS]; DevBuf<BvhTri> trisOwn[RT_SETS];
   BvhNode* nodesBuf[RT_SETS] = {}; Bvh4Node* nodes4Buf[RT_SETS] = {}; BvhTri* trisBuf[RT_SETS] = {};
   // the top of the tree once more, breadth-first, for the trace kernel's LDS (rtggx_device.h RT_TOP_*; lbvh.hip planTopKernel / emitTop):
   // topo.topList[k] = node of rank k, topo.topRank[node] = its rank or -1; the table itself per input set like the nodes
   uint32_t topCount = 0; uint32_t topCountBuf[RT_SETS] = {};
-  Bvh4Node* top = nullptr; Bvh4Node* topBuf[RT_SETS] = {};
+  Bvh4Node* top = nullptr; DevBuf<Bvh4Node> topOwn[RT_SETS]; Bvh4Node* topBuf[RT_SETS] = {};
   int32_t root = -1;             // 0, or ~0 for a single-triangle mesh
   uint32_t depth = 0;            // deepest leaf (number of ancestors)
   uint32_t stack4 = 0;           // the most entries a traversal of the 4-wide tree can have on its stack (BuildResult::stack4 of the latest topology)
@@ -136,7 +143,7 @@ struct MeshDev {
 };
 
 struct EnvDev {
-  uint2* texels = nullptr;       // RGBA16F, mip-major, 6 faces per mip
+  DevBuf<uint2> texels;          // RGBA16F, mip-major, 6 faces per mip
   uint32_t size = 0, mips = 0;
   uint32_t mipOffset[16] = {};   // texel offset of mip m (face 0)
   uint64_t totalTexels = 0;
@@ -157,45 +164,45 @@ struct FrameParams {
 };
 #define RT_FLAG_VNDF 1u          // rtggx_set_sampler: visible-normal sampling of the reflection lobe instead of the reference's NDF sampling
 
-// One input set: everything stream B's stages write for a frame and the main stream reads (allocated and freed by capi.hip allocSet / freeSet).
+// One input set: everything stream B's stages write for a frame and the main stream reads (allocated by context.hip allocSet).
 struct InputSet {
-  uint32_t *normal = nullptr, *velocity = nullptr, *rtRefl = nullptr, *rtDiff = nullptr;
-  uint16_t* roughMetal = nullptr;
-  uint32_t* depth32 = nullptr;       // the D24 word of visDepth once more, 4 bytes per pixel, for the spatial filters (written by ray generation)
+  DevBuf<uint32_t> normal, velocity, rtRefl, rtDiff;
+  DevBuf<uint16_t> roughMetal;
+  DevBuf<uint32_t> depth32;          // the D24 word of visDepth once more, 4 bytes per pixel, for the spatial filters (written by ray generation)
   // ray bins of the trace pass (rt_queue.h): numBinsMax bins of binSlots ray records and hit keys, and the rays in each bin
-  void *rayQueue = nullptr, *hitQueue = nullptr;
-  uint32_t* binCount = nullptr;
+  DevBuf<void> rayQueue, hitQueue;
+  DevBuf<uint32_t> binCount;
   // Bins whose traversal was expensive in the previous frame are traced by 2, 4 or 8 waves (trace.hip "adaptive split"): [RT_SPLIT_CAP]
   // (shift << 28) | (slice << 24) | bin, one entry per wave of a listed bin.  Per set: the visibility pass of the next frame, which empties
   // its set's list, may run beside this frame's traversal.  The count is a word of largeCountBase (zeroed by the previous frame's ray generation).
-  uint32_t* splitList = nullptr; uint32_t* splitCount = nullptr;
+  DevBuf<uint32_t> splitList; uint32_t* splitCount = nullptr;      // (splitCount: a view)
   // "Still sky" (raytrace.hip rayGenKernel): one word per 16x16 tile of ray generation's grid, epoch << 8 | run.  run: the consecutive frames,
   // this set's included and saturating at RT_SKY_RUN_CAP, in which ray generation found the tile's word 0 under one epoch (rtggx_context
   // skyEpoch).  Written by the set's ray generation, read by the next frame's (earlier on the same stream, like roughMetalPrev) and by the
   // set's own reflection V pass behind the traversal's event; protected by evRead like the set's other members.
-  uint32_t* skyRun = nullptr;
-  hipEvent_t evRead = nullptr;      // the set's last reader done: the HOST waits for it before stream B is given work that overwrites the set
+  DevBuf<uint32_t> skyRun;
+  Event evRead;                     // the set's last reader done: the HOST waits for it before stream B is given work that overwrites the set
   bool readRecorded = false;
 };
 
 // One visibility target (RT_VIS_RING above), by frame number.
 struct VisTarget {
-  unsigned long long* depth = nullptr;      // visDepth
+  DevBuf<unsigned long long> depth;         // visDepth
   // One word per 16x16 tile, set by the rasterisers where they draw: a tile whose word is 0 holds nothing but the clear value, and ray
   // generation neither reads nor re-clears it (three quarters of the bunny frame: 16 bytes per pixel and the first of its dependent
   // fetches).  Tiles are ray generation's, counted from the pass's first row: the words mean something only for the rows they were kept
   // under (flags.rows; another strip: everything is read and cleared, which also resets the words).
-  uint32_t* dirty = nullptr;
+  DevBuf<uint32_t> dirty;
   struct { uint32_t frame = 0, rows[2] = {0, 0}; } cleared;      // a ray generation has cleared the target, over these rows, FOR this frame (0: not)
   struct { uint32_t rows[2] = {0, 0}; uint32_t rasterFrame = 0; } flags;      // word 0 => tile clear, for tiles counted from rows[0]; rasterFrame: the frame whose visibility pass drew into the target last
 };
 
-// What the stages of frame f tell the streams of later frames, by f & 3 (capi.hip rtggx_render_visibility).
+// What the stages of frame f tell the streams of later frames, by f & 3 (frame.hip rtggx_render_visibility).
 struct FrameEvents {
-  hipEvent_t gen = nullptr;          // ray generation of frame f done (C -> B: traversal f; C -> R: the visibility pass of frame f + 2, whose target and lists it cleared)
+  Event gen;                         // ray generation of frame f done (C -> B: traversal f; C -> R: the visibility pass of frame f + 2, whose target and lists it cleared)
   uint32_t genFrame = 0;             // the frame it belongs to (0: none)
-  hipStream_t genStream = nullptr;   // and its stream
-  hipEvent_t trace = nullptr;        // traversal of frame f done (B -> main; B -> C two frames later: binWork)
+  hipStream_t genStream = nullptr;   // and its stream (a view)
+  Event trace;                       // traversal of frame f done (B -> main; B -> C two frames later: binWork)
   bool traceRecorded = false;
 };
 
@@ -213,37 +220,39 @@ struct rtggx_context {
   uint32_t W = 0, H = 0;
   uint32_t rowBegin = 0, rowEnd = 0;
   uint32_t historyApron = 18;           // rows of TemporalSSOut beyond the strip the caller delivers between frames (rtggx_set_history_apron)
-  uint32_t* histReach = nullptr;        // device word: the furthest a history tap reached beyond them, in rows (temporalKernel)
-  hipStream_t streamMain = nullptr, streamAS = nullptr, ownMain = nullptr;
-  hipStream_t streamRefit = nullptr;               // stream R: vertex uploads and tree refits of deforming meshes (rtggx_refit_as)
-  // Frame pipeline (capi.hip): three stages on three streams -- C: visibility + ray generation, B: traversal, main: shading + denoiser +
+  rt::DevBuf<uint32_t> histReach;       // device word: the furthest a history tap reached beyond them, in rows (temporalKernel)
+  // Streams: the four the context creates are owners; streamMain, streamAS, streamVis (and sppStream, shadeStream, diffStream, evVisStream
+  // below) are views -- of one of them, or of the caller's stream (rtggx_set_stream).
+  rt::Stream ownMain; hipStream_t streamMain = nullptr, streamAS = nullptr;
+  rt::Stream streamRefit;                          // stream R: vertex uploads and tree refits of deforming meshes (rtggx_refit_as)
+  // Frame pipeline (frame.hip): three stages on three streams -- C: visibility + ray generation, B: traversal, main: shading + denoiser +
   // tone map -- so that ray generation of frame f + 1 runs beside the traversal of frame f.
-  bool refitIssued = false;                        // per-frame issue state (capi.hip)
+  bool refitIssued = false;                        // per-frame issue state (frame.hip)
   uint32_t frameCounter = 0;                       // frames started (rtggx_render_visibility); parity selects binWork / ray counters
   rt::FrameEvents frames[4];                       // by frame & 3
   rt::FrameEvents& frameEvents(uint32_t f) { return frames[f & 3u]; }
-  hipStream_t ownAS = nullptr, ownVis = nullptr;   // the context's own stream B / stream C; streamAS / streamVis alias streamMain / null while
+  rt::Stream ownAS, ownVis;                        // the context's own stream B / stream C; streamAS / streamVis alias streamMain / null while
   bool asyncCompute = true;                        // rtggx_set_async_compute(0) is in force (the sample's [A] toggle: one queue, submission order)
   // Launches with few rays (thin strips, small frames) leave most of the machine idle and last as long as stream B's chain
   // of dependent kernels: there the visibility pass of frame f+1 runs on a stream of its own (C), beside the traversal
   // of frame f, instead of behind it.  (On full frames the machine is saturated and this gains nothing.)
   hipStream_t streamVis = nullptr;
-  hipEvent_t evVis = nullptr;           // completes with the last kernel of the most recent visibility pass, on either stream
+  rt::Event evVis;                      // completes with the last kernel of the most recent visibility pass, on either stream
   hipStream_t evVisStream = nullptr;    // the stream the most recent visibility pass ran on (null: none yet)
-  hipEvent_t evAS = nullptr;      // constants uploaded (stream B -> main)
-  hipEvent_t evRefit = nullptr;   // vertices of the current set uploaded and the tree refitted (stream B -> stream C)
-  hipEvent_t evRT = nullptr;      // ray trace done (stream B -> main)
-  int setReadDeferred = -1;       // the set whose evRead is still to ride on a later kernel of this frame (capi.hip settleSetRead)
+  rt::Event evAS;                 // constants uploaded (stream B -> main)
+  rt::Event evRefit;              // vertices of the current set uploaded and the tree refitted (stream B -> stream C)
+  rt::Event evRT;                 // ray trace done (stream B -> main)
+  int setReadDeferred = -1;       // the set whose evRead is still to ride on a later kernel of this frame (frame.hip settleSetRead)
   double fenceWaitUs = 0.0; uint32_t fenceWaits = 0;      // host time spent waiting at the frames-in-flight fence (rtggx_render_visibility; rtggx_debug_fence_wait)
   // The temporal pass and the tone map as one kernel (denoise.hip temporalToneKernel): rtggx_denoise then writes the back buffer as well and
-  // the rtggx_tone_map that follows it in the same frame has nothing left to launch.  -1: where it pays -- small launches (capi.hip
+  // the rtggx_tone_map that follows it in the same frame has nothing left to launch.  -1: where it pays -- small launches (frame.hip
   // rtggx_denoise); rtggx_debug_fuse_tone_map(ctx, 0 / 1): never / always.
   int fuseToneMap = -1; bool toneMapDone = false, denoiseIssued = false;
   // Multi-GPU strips: every rank's two history images as mapped into THIS process (rtggx_set_history_peers) -- device table
   // [2][RT_MAX_PEERS] pointers + [RT_MAX_PEERS + 1] row boundaries; a history tap beyond the exchanged apron reads the owner's image.
-  uint32_t* exchangeTokens = nullptr;      // RTGGX_BUF_EXCHANGE_TOKENS
+  rt::DevBuf<uint32_t> exchangeTokens;     // RTGGX_BUF_EXCHANGE_TOKENS
   float collapseWeights[2] = {RT_COLLAPSE_AREA_WEIGHT, RT_COLLAPSE_TRIS_WEIGHT};      // rtggx_debug_collapse_weights
-  uint32_t peerWorld = 0; void* dPeerTable = nullptr; std::vector<void*> ipcMapped;      // (what rtggx_history_ipc_open mapped: unmapped by rtggx_destroy)
+  uint32_t peerWorld = 0; rt::DevBuf<void> dPeerTable; std::vector<rt::IpcMapping> ipcMapped;      // (what rtggx_history_ipc_open mapped: unmapped with the context)
   uint32_t lastPlacement[2] = {0, 0};      // key and placement of the most recent rtggx_ray_trace (rtggx_debug_placement)
   int forcePlacement = -1;       // rtggx_debug_placement: -1 by the ray count; 0 / 1: the placement of a full-size / a small launch whatever the count
   bool fltRflIsFltDff = false;          // the last denoise ran without diffuse passes: FilteredOut == FilteredOut1 and only the latter was written
@@ -253,22 +262,22 @@ struct rtggx_context {
   uint32_t rayRate = 1;          // rtggx_set_ray_rate: pixels per traced ray, 1 or 4 (raytrace.hip rayGenKernel, reconstructKernel)
   uint32_t maxDepth = 1, depthRequested = 1;      // rtggx_set_max_recursion_depth: 1..4 levels of rays per path (raytrace.hip launchShade); the frame's, the next frame's
   // rtggx_set_samples_per_pixel: 1, 2, 4 or 8 samples per covered pixel (raytrace.hip launchShade; DESIGN.md "Samples per pixel"); the
-  // frame's, the next frame's.  Everything below exists from the first N > 1 on (capi.hip allocSamples) and is released by rtggx_destroy:
+  // frame's, the next frame's.  Everything below exists from the first N > 1 on (context.hip allocSamples):
   //   sppAcc     the fp32 sums of RayTracingOut0 / RayTracingOut1, [2][W * H][3] floats, all zero between frames (the resolve leaves them so).
   //              ONE pair for all input sets: the frames' shading passes follow each other in stream order, or by evSpp where the stream changes
   //   sppParams  [RT_SLOTS][RTGGX_MAX_SAMPLES_PER_PIXEL] copies of the slot's frame constants, sample k's with FrameIndex * N + k
   uint32_t samples = 1, samplesRequested = 1;
-  float* sppAcc = nullptr; rt::FrameParams* sppParams = nullptr;
-  hipStream_t sppStream = nullptr; hipEvent_t evSpp = nullptr;      // the stream of the most recent frame that used sppAcc
+  rt::DevBuf<float> sppAcc; rt::DevBuf<rt::FrameParams> sppParams;
+  hipStream_t sppStream = nullptr; rt::Event evSpp;      // (a view:) the stream of the most recent frame that used sppAcc
   // rtggx_set_accumulation (raytrace.hip accumulateKernel; DESIGN.md "Progressive accumulation"): the frame's, the next frame's.  The sums
-  // exist ONCE, from the first enable on (capi.hip allocAccumulation), [W * H] float4 each -- sum r, g, b, Y^2 of RayTracingOut0 / 1 --, and
+  // exist ONCE, from the first enable on (context.hip allocAccumulation), [W * H] float4 each -- sum r, g, b, Y^2 of RayTracingOut0 / 1 --, and
   // are touched by the main stream alone (the kernel behind the hit shading, the reset's clears, the present): stream order is the order of
   // the frames.  accumFrames: frames added since the last reset, counted by the host as it enqueues them.
   bool accumulate = false, accumulateRequested = false;
   uint32_t accumFrames = 0;
-  float4 *accRefl = nullptr, *accDiff = nullptr; uint2* converged = nullptr;      // converged: RTGGX_BUF_CONVERGED (rtggx_present_accumulation)
+  rt::DevBuf<float4> accRefl, accDiff; rt::DevBuf<uint2> converged;      // converged: RTGGX_BUF_CONVERGED (rtggx_present_accumulation)
   // rtggx_set_reference / rtggx_set_scoring (score.hip; DESIGN.md "Scoring against a reference"): the frame's, the next frame's.  Nothing
-  // below exists on a context that never calls them (capi.hip allocReference, allocScoring); all of it is released by rtggx_destroy.
+  // below exists on a context that never calls them (context.hip allocReference, allocScoring).
   //   reference      W * H RGBA16F words, written by rtggx_set_reference (host copy) or rtggx_reference_from_accumulation (main stream)
   //   scorePartial   the tree's levels, ping-pong: [0] RT_SCORE_SUMS x scoreStride doubles -- one per sum and chunk of RT_SCORE_CHUNK pixels,
   //                  sum-major --, [1] half of that; scoreCounts: 3 words per chunk (covered, skipped_out, skipped_raw)
@@ -276,21 +285,21 @@ struct rtggx_context {
   // ONE set of partials for all frames: both stages of every frame run on the main stream, in its order.  scoreIndex: frames scored so
   // far, counted by the host as it enqueues them; scoreRead: the first record rtggx_read_scores has not handed out yet.
   bool scoring = false, scoringRequested = false;
-  uint2* reference = nullptr;
-  double* scorePartial[2] = {nullptr, nullptr}; uint32_t* scoreCounts = nullptr; uint32_t scoreStride = 0;
-  RtggxScore* scoreRing = nullptr;
+  rt::DevBuf<uint2> reference;
+  rt::DevBuf<double> scorePartial[2]; rt::DevBuf<uint32_t> scoreCounts; uint32_t scoreStride = 0;
+  rt::DevBuf<RtggxScore> scoreRing;
   uint64_t scoreIndex = 0, scoreRead = 0;
   uint32_t traceGrid[4] = {};    // the frame's level-0 trace launch -- bins, tile grid x / y, slice shift --, which the later levels repeat
   float rebuildRatio = 1.2f; uint32_t rebuildSteps = 16;      // rtggx_set_refit_policy
   rt::MeshDev mesh[2];
   rt::EnvDev env;
-  float* sh = nullptr;           // 27 floats
-  float* cosSinTab = nullptr;    // 512 floats: cos[256], sin[256]
+  rt::DevBuf<float> sh;          // 27 floats
+  rt::DevBuf<float> cosSinTab;   // 512 floats: cos[256], sin[256]
   // rtggx_set_sample_set (raytrace.hip sampleParamWide; DESIGN.md "Sample-set size"): M of the frame, of the next frame; 256 = the reference's.
-  // One table per size M = 512 << k ever asked for, M {cos, sin} pairs, made by the setter and kept until rtggx_destroy: a frame in flight
+  // One table per size M = 512 << k ever asked for, M {cos, sin} pairs, made by the setter and kept as long as the context: a frame in flight
   // and a frame whose visibility pass has run keep the table they were launched with whatever the caller sets next.
   uint32_t sampleSet = RTGGX_MIN_SAMPLE_SET, sampleSetRequested = RTGGX_MIN_SAMPLE_SET;
-  float* cosSinWide[8] = {};
+  rt::DevBuf<float> cosSinWide[8];
   static uint32_t sampleSetSlot(uint32_t m) { uint32_t k = 0; while ((512u << k) < m) ++k; return k; }
   const float* sampleTable() const { return sampleSet > RTGGX_MIN_SAMPLE_SET ? cosSinWide[sampleSetSlot(sampleSet)] : cosSinTab; }
 
@@ -314,24 +323,24 @@ struct rtggx_context {
     for (auto& m : mesh) { m.verts = m.vertsBuf[i]; m.fat = m.fatBuf[i]; m.nodes = m.nodesBuf[i]; m.nodes4 = m.nodes4Buf[i]; m.top = m.topBuf[i]; m.topCount = m.topCountBuf[i]; m.tris = m.trisBuf[i]; }
     binWork = binWorkBuf[frameCounter & 1u]; rayCounter32 = rayCounterBuf + (frameCounter & 3u) * 256u;
   }
-  uint32_t* backbuffer = nullptr;
-  uint2 *tss[2] = {nullptr, nullptr}, *fltRfl = nullptr, *fltDff = nullptr;
+  rt::DevBuf<uint32_t> backbuffer;
+  rt::DevBuf<uint2> tss[2], fltRfl, fltDff;
   uint32_t frameParity = 0;
 
   // visibility scratch
   // LargeTri records queued by rasterSmall, merged by rasterLarge; twice, by frame parity (ray generation of frame f empties the
   // list of frame f + 1: the count it zeroes must not be the one a consumer of frame f could still read)
-  void* largeTris = nullptr; void* largeTrisBuf[2] = {};
-  uint32_t* largeCount = nullptr;       // the current frame's count (selectSet)
-  uint32_t* largeCountBase = nullptr;   // [0], [1] entries of largeTrisBuf[parity]; [2 + i] sets[i].splitCount
+  void* largeTris = nullptr; rt::DevBuf<void> largeTrisBuf[2];      // (largeTris: a view of the current frame's, selectSet)
+  uint32_t* largeCount = nullptr;       // view: the current frame's count (selectSet)
+  rt::DevBuf<uint32_t> largeCountBase;  // [0], [1] entries of largeTrisBuf[parity]; [2 + i] sets[i].splitCount
   // The adaptive split's record of what each bin cost (InputSet::splitList):
-  uint32_t* binWork = nullptr;          // [numBinsMax] lane-steps the trace kernel spent on the bin (read and zeroed by rayGenKernel)
-  uint32_t* binWorkBuf[2] = {};         // by frame parity: ray generation of frame f reads what the traversal of frame f - 2 recorded
+  uint32_t* binWork = nullptr;          // view (selectSet): [numBinsMax] lane-steps the trace kernel spent on the bin (read and zeroed by rayGenKernel)
+  rt::DevBuf<uint32_t> binWorkBuf[2];   // by frame parity: ray generation of frame f reads what the traversal of frame f - 2 recorded
                                         // (frame f - 1's may still be running beside it) and the traversal of frame f records anew
   // the words of the current frame's target, for the kernels that follow its visibility pass: the target's own where they describe rows [rb, re), else all ones
   const uint32_t* tileWords(uint32_t rb, uint32_t re) {
     const rt::VisTarget& v = curVis();
-    return useTileWords && !traversalBound && v.flags.rasterFrame == frameCounter && v.flags.rows[0] == rb && v.flags.rows[1] == re ? v.dirty : visDirtyOnes;
+    return useTileWords && !traversalBound && v.flags.rasterFrame == frameCounter && v.flags.rows[0] == rb && v.flags.rows[1] == re ? v.dirty.get() : visDirtyOnes.get();
   }
   // Still sky (InputSet::skyRun; raytrace.hip skyEpochForGen is where the epoch is decided).  skyEpoch: 24 bits, bumped
   // whenever something a sky tile's outputs depend on changes or the chain of consecutive ray generations breaks -- by skyEpochForGen from
@@ -349,46 +358,46 @@ struct rtggx_context {
   // (profiles/r04_j_tile_words.txt).  Decided once per frame (launchRayTrace) from the share of the period the traversal's own time stamps
   // measure (trace.hip steerTraceWaves), with hysteresis; the words themselves are kept either way.
   bool traversalBound = false;
-  const uint32_t* traceTileWords = nullptr;      // launchRayTrace -> launchTrace: tileWords() of the frame's G-buffer rows
-  uint32_t* visDirtyOnes = nullptr;      // as many words as a VisTarget's, all ones: "every tile may hold something" (raytrace.hip GenArgs)
+  const uint32_t* traceTileWords = nullptr;      // view; launchRayTrace -> launchTrace: tileWords() of the frame's G-buffer rows
+  rt::DevBuf<uint32_t> visDirtyOnes;     // as many words as a VisTarget's, all ones: "every tile may hold something" (raytrace.hip GenArgs)
   uint32_t splitDemand = 0;             // entries the most recent frame whose count has arrived wanted (hostRayCounters[256])
   uint32_t splitCapForced = 0xFFFFFFFFu;   // rtggx_debug_trace_split: fixed capacity instead of the demand-driven one
   uint32_t splitWork = 0, splitMaxShift = 0;   // set at creation (RT_SPLIT_WORK, or RTGGX_SPLIT_WORK / RTGGX_SPLIT_MAX_SHIFT)
   uint32_t largeCapacity = 0;
 
   uint32_t numBinsMax = 0, binSlots = 64;      // bins per set; ray slots per bin (rt_queue.h RT_BIN_MIN / RT_BIN)
-  void *testRayRange = nullptr, *traceRayRange = nullptr;      // rtggx_trace_rays: the rays' own (TMin, TMax); set only around that entry point's launch
-  int32_t* stackOverflow = nullptr;     // traversal-stack spill area (entries beyond the LDS stack), sized from
+  rt::DevBuf<void> testRayRange; void* traceRayRange = nullptr;      // rtggx_trace_rays: the rays' own (TMin, TMax); the view is set only around that entry point's launch
+  rt::DevBuf<int32_t> stackOverflow;    // traversal-stack spill area (entries beyond the LDS stack), sized from
   uint32_t spillEntries = 0;            // the depth of the built trees: [spillEntries][numBinsMax * 128] words
-  void* dummyRecord = nullptr;          // 128 zero bytes: record base for meshes without nodes / absent meshes
-  uint32_t* dEnvMipOffset = nullptr;    // device copy of env.mipOffset
+  rt::DevBuf<void> dummyRecord;         // 128 zero bytes: record base for meshes without nodes / absent meshes
+  rt::DevBuf<uint32_t> dEnvMipOffset;   // device copy of env.mipOffset
   bool lastTraceSmall = false; uint32_t traceSpillHalf = 0;
-  hipStream_t shadeStream = nullptr;     // the stream the most recent hit shading ran on (capi.hip rtggx_ray_trace: the main stream, or the traversal's for small launches)
+  hipStream_t shadeStream = nullptr;     // view: the stream the most recent hit shading ran on (frame.hip rtggx_ray_trace: the main stream, or the traversal's for small launches)
   // RayTracingOut1 keeps what it held where no diffuse ray is traced: with several input sets, carried over from the previous set -- by ray
   // generation when the previous frame's shading kernel wrote nothing into that set (genCarriesDiff), else by the shading kernel (raytrace.hip)
   bool genCarriesDiff = false, shadeWroteDiff = false, lastFrameDiffuse = false;
   hipStream_t diffStream = nullptr;      // the stream of the most recent frame's last writer of RayTracingOut1: the hit shading's, or at rate 4 the main stream (reconstruction)
   uint32_t numCUs = 256;
   // the trace kernel's workgroup size (full-size launches) and the time stamps it takes of itself (trace.hip): stamps = 3 x (start, end) + (sum of durations, latest start)
-  uint32_t traceWaves = 12, traceWavesForced = 0; float traceShare = 0.0f; unsigned long long* traceStamps = nullptr; uint32_t traceStampLaunch = 0;
+  uint32_t traceWaves = 12, traceWavesForced = 0; float traceShare = 0.0f; rt::DevBuf<unsigned long long> traceStamps; uint32_t traceStampLaunch = 0;
   unsigned long long traceStampSum = 0, traceStampStart = 0; uint32_t traceStampAt = 0, traceSampleLaunch = 0;      // the previous sample; the launch the sample in flight was taken at
   uint32_t traceTrial = 0, traceCooldown = 0, traceWavesSince = 0; float traceTrialBase = 0.0f;      // a trial of two more waves: samples seen, the period to beat
 
   // counters
-  uint32_t* hostRayCounters = nullptr;  // pinned copy of rayCounter32[0..255], refreshed asynchronously after every trace launch
-  hipEvent_t evRayCounters = nullptr; bool rayCountersInFlight = false; uint32_t traceLaunches = 0;
+  rt::PinnedBuf<uint32_t> hostRayCounters;  // pinned copy of rayCounter32[0..255], refreshed asynchronously after every trace launch
+  rt::Event evRayCounters; bool rayCountersInFlight = false; uint32_t traceLaunches = 0;
   uint32_t lastFrameRays = 0xFFFFFFFFu; // rays of the most recent frame whose counters have arrived (unknown: assume a full machine)
-  uint32_t* rayCounter32 = nullptr;     // 256 per-frame partial counts written by the trace kernel (the current frame's half of ...)
-  uint32_t* rayCounterBuf = nullptr;    // ... [4][256] by frame number & 3, then 768 words of RT_TRACE_STATS counters.  (Four, not two like binWork:
+  uint32_t* rayCounter32 = nullptr;     // view: 256 per-frame partial counts written by the trace kernel (the current frame's half of ...)
+  rt::DevBuf<uint32_t> rayCounterBuf;   // ... [4][256] by frame number & 3, then 768 words of RT_TRACE_STATS counters.  (Four, not two like binWork:
                                         // ray generation of frame f zeroes its quarter, and the asynchronous copy of frame f - 2's counters to the
                                         // host, queued behind that frame's traversal, may not have run yet; frame f - 4's has.)
-  uint32_t* lastRayCounter32 = nullptr; // the half of the most recent rtggx_ray_trace (rtggx_ray_count)
-  unsigned long long* rayCounter = nullptr;   // [0..255] last frame, [256..511] running total
+  uint32_t* lastRayCounter32 = nullptr; // view: the half of the most recent rtggx_ray_trace (rtggx_ray_count)
+  rt::DevBuf<unsigned long long> rayCounter;  // [0..255] last frame, [256..511] running total
 
   // per-frame constants: ring of RayTracer::FrameCount slots (host side; kernels take them by value)
   rt::FrameParams slots[RT_SLOTS];
   uint32_t slot = 0;
-  rt::FrameParams* dParams = nullptr;   // device ring, 3 slots; kernels read their constants from here
+  rt::DevBuf<rt::FrameParams> dParams;  // device ring, 3 slots; kernels read their constants from here
   bool slotUploaded = false;
   bool slotRendered = false;     // a frame has been rendered from this slot since rtggx_update_frame filled it: its kernels may still read the device copy
   RtggxCBMaterial material;
@@ -399,9 +408,9 @@ struct rtggx_context {
   bool timing = false;        // all per-pass events (rtggx_get_timings)
   bool kernelRing = false;    // only the ray-trace kernel, one event pair per sampled frame in a ring (rtggx_kernel_times)
   uint32_t ringStride = 1, ringTick = 0;   // every ringStride-th frame is sampled
-  std::vector<hipEvent_t> kevBegin, kevEnd;
+  std::vector<rt::Event> kevBegin, kevEnd;
   uint32_t kevCount = 0;
-  hipEvent_t tev[16] = {};
+  rt::Event tev[16];
   bool timingsPending = false;
 };
 
@@ -442,15 +451,15 @@ int continueRebuild(rtggx_context* c, uint32_t slot, hipStream_t s, uint32_t max
 int prepareRebuild(rtggx_context* c, uint32_t slot);      // the second topology and the build's scratch memory, once, when a mesh begins to deform
 void abandonRebuild(rtggx_context* c, uint32_t slot);      // (synchronises; before the mesh's buffers are freed)
 int refitLbvh(rtggx_context* c, uint32_t slot, uint32_t set, hipStream_t s);      // boxes of the existing tree from the vertices of input set `set`, into that set's BVH arrays: no host round trip
-void freeBuildProducts(MeshDev& m);
+void freeBuildProducts(MeshDev& m);      // (the caller has synchronised)
 int buildFatTris(rtggx_context* c, uint32_t slot, uint32_t set, hipStream_t s);      // mesh.fatBuf[set] from mesh.vertsBuf[set] and the indices
 int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hipStream_t sTrace, hipEvent_t done = nullptr);   // ray generation on sGen, traversal on sTrace (joined by evGen when they differ)
 // `done` (may be null) on the launch functions below: an event that completes with the pass's last kernel.  It rides on that
 // kernel's own completion signal (hipExtLaunchKernelGGL) instead of a marker packet behind it: a marker costs its queue
 // 5-7 us, and the frame's two chains had four of them (rocprofv3 kernel trace, profiles/).
 int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent_t done = nullptr);      // hit / miss shading of the traced bins
-int launchReconstruct(rtggx_context* c, const FrameParams& fp, hipStream_t s);
-int allocSamples(rtggx_context* c);      // what N > 1 samples per pixel need (rtggx_context::sppAcc, sppParams), once      // rate 4: the untraced pixels of RayTracingOut0/1, after the hit shading
+int launchReconstruct(rtggx_context* c, const FrameParams& fp, hipStream_t s);      // rate 4: the untraced pixels of RayTracingOut0/1, after the hit shading
+int allocSamples(rtggx_context* c);      // what N > 1 samples per pixel need (rtggx_context::sppAcc, sppParams), once
 int allocAccumulation(rtggx_context* c);      // what rtggx_set_accumulation needs (rtggx_context::accRefl, accDiff, converged), once
 int launchAccumulate(rtggx_context* c, const FrameParams& fp, hipStream_t s);      // the frame's traced images added to the sums, the strip's own rows
 int launchPresentAccumulation(rtggx_context* c, hipStream_t s);      // RTGGX_BUF_CONVERGED from the sums and accumFrames

@@ -85,7 +85,7 @@ struct TraceArgs {
 // chip full of them (24 waves and 150 KB of LDS stacks per CU).  The kernel is now ONE workgroup of RT_TRACE_WAVES waves per CU
 // (launchTrace) whose waves draw work ITEMS -- what used to be a workgroup id: a (bin, slice) in dispatch order -- until none are
 // left.  Two reasons (profiles/r02_j_resident_trace.txt):
-//   * the frame is a pipeline of three streams (capi.hip), and what the trace kernel occupies is not available to the shading and
+//   * the frame is a pipeline of three streams (frame.hip), and what the trace kernel occupies is not available to the shading and
 //     denoising kernels next to it.  Ten resident waves and 55 KB of LDS per CU make the kernel itself 10 % slower than 24 waves
 //     and 150 KB did (0.117 against 0.105 ms alone) -- and the frame 7 % faster (0.198 against 0.213 ms).  Six waves are too few
 //     (the traversal becomes the longest stage), twelve and more, or more than ~80 KB of LDS, take the gain away again;
@@ -427,7 +427,7 @@ __global__ void stampKernel(uint32_t* stats) { *reinterpret_cast<unsigned long l
 // 8 when they do not (small frames, thin strips of a multi-GPU frame).  The ray count is last frame's, copied back
 // asynchronously.
 // The size of the traversal's one workgroup per CU.  What the traversal keeps resident is not available to the kernels of the other
-// two pipeline stages (capi.hip), so it should be small -- 12 waves are best or within noise of best on seven of eight workloads --
+// two pipeline stages (frame.hip), so it should be small -- 12 waves are best or within noise of best on seven of eight workloads --
 // unless the traversal is what the frame waits for (a large mesh with diffuse rays as well: 0.43 ms per frame with 12 waves, 0.37
 // with 14; profiles/r02_j_resident_trace.txt).  The kernel stamps its own start and end and keeps a running sum of its durations;
 // with the ray counters (every 16th frame) the host gets, for the launches since the last sample, the PERIOD between launches and
@@ -497,10 +497,10 @@ int launchTrace(rtggx_context* c, const FrameParams& fp, hipStream_t s, const Tr
   const uint32_t deepest = (c->mesh[0].stack4 > c->mesh[1].stack4 ? c->mesh[0].stack4 : c->mesh[1].stack4) + 1u;      // what the builds found (lbvh.hip roots4Kernel)
   if (deepest > RT_STACK + c->spillEntries) {
     RT_HIP(hipDeviceSynchronize());
-    if (c->stackOverflow) { RT_HIP(hipFree(c->stackOverflow)); c->stackOverflow = nullptr; }
+    c->stackOverflow.reset();
     c->spillEntries = deepest - RT_STACK;
     // three times: two level-0 traversals can be in flight (traceSpillHalf), and beside them the later levels of a frame's paths on the main stream
-    RT_HIP(hipMalloc(&c->stackOverflow, (size_t)RT_SPILL_PARTS * c->spillEntries * RT_SPILL_WAVES * 64 * 4));
+    RT_HIP(alloc(c->stackOverflow, (size_t)RT_SPILL_PARTS * c->spillEntries * RT_SPILL_WAVES * 64));
   }
   T.overflow = c->stackOverflow + (size_t)(deeper ? (uint32_t)spillPart : c->traceSpillHalf) * c->spillEntries * RT_SPILL_WAVES * 64;
   T.rayTotals = c->rayCounter32; T.stats = c->rayCounterBuf + 1024; T.runTotals = c->rayCounter + 256;
@@ -521,7 +521,7 @@ int launchTrace(rtggx_context* c, const FrameParams& fp, hipStream_t s, const Tr
   T.top1 = (const float4*)c->mesh[1].top; T.topCount1 = have1 && c->mesh[1].top ? c->mesh[1].topCount : 0u;
   if (T.topCount0 > RT_TOP_SLOT0 || T.topCount1 > RT_TOP_SLOT1) { setError("launchTrace: tree tables of %u / %u nodes exceed the LDS slots", T.topCount0, T.topCount1); return -1; }
   // Which variant.  A launch of a frame gets ONE workgroup of traceWaves (12, see steerTraceWaves) waves per CU: see the kernel.
-  // Below RT_WIDE_RAYS rays two such launches are in flight (capi.hip rtggx_ray_trace).  A launch with fewer than RT_TINY_RAYS rays
+  // Below RT_WIDE_RAYS rays two such launches are in flight (frame.hip rtggx_ray_trace).  A launch with fewer than RT_TINY_RAYS rays
   // lasts as long as its longest chain of dependent steps and wants every wave slot at once: single-wave workgroups without the
   // table, one per item, as in round 1 (256x144, 9 000 rays: 0.050 ms per frame against 0.063; 1920x171, 13 000 rays: 0.063 against
   // 0.071; from 40 000 rays on the resident workgroups are as fast or faster -- a strip of the 1080p frame with 70 000-150 000 rays:

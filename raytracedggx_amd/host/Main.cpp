@@ -10,7 +10,7 @@
 #include "Strips.h"
 
 int main(int argc, char* argv[]) {
-  // five streams with the strip exchange of -gpus N (rtggx.h rtggx_get_exchange_stream): HIP's default is four hardware queues.  Read when
+  // a context has four streams of its own and the strip exchange of -gpus N is enqueued on a stream as well (rtggx.h rtggx_get_stream): HIP's default is four hardware queues.  Read when
   // the runtime initialises, which nothing has made it do yet; the ranks the launcher starts inherit it.
   setenv("GPU_MAX_HW_QUEUES", "8", 0);
   RayTracedGGX app(1280, 720, "DXR Ray-Traced GGX");   // Main.cpp:17

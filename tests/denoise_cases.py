@@ -1,7 +1,7 @@
 """Synthetic inputs of the denoise chain -- TEST INFRASTRUCTURE ONLY.  Deterministic (fixed seeds), small, packed as the render targets
 hold them.  Used by tests/test_denoise_ref_host.py (model against oracle) and tests/test_gpu_denoise_synthetic.py (product against model).
 
-What the kernels are entitled to assume (launchDenoise, denoise.hip; rtggx_upload, capi.hip) -- `check` asserts it on every case:
+What the kernels are entitled to assume (launchDenoise, denoise.hip; rtggx_upload, debug.hip) -- `check` asserts it on every case:
   1. the seven inputs and both TemporalSSOut images are whole W x H images of the context's size;
   2. the diffuse passes are launched iff a material of the frame constants has metallic < 1 (denoise.hip launchDenoise: metallic is a
      per-instance constant, Material.hlsli:20-30): a texel may carry a metal code below 255 only if a material says so.  (The converse is
@@ -16,7 +16,7 @@ What the kernels are entitled to assume (launchDenoise, denoise.hip; rtggx_uploa
   7. normals (zero-length and non-unit codes included), their 2-bit alpha, roughness and depth are read per texel by every kernel and may
      vary freely;
   8. on a strip (rtggx_set_strip) a reprojection reads at most the history apron's rows beyond the strip.
-After an upload the tiles' words read "unknown" (capi.hip rtggx_upload), so the tile-word and still-sky early-outs are NOT under test with
+After an upload the tiles' words read "unknown" (debug.hip rtggx_upload), so the tile-word and still-sky early-outs are NOT under test with
 these inputs; they have their own bit-identity tests (tests/test_gpu_static_sky.py).
 One more restriction is the suite's own, not the kernels': normals are either within 6 % of unit length, or the zero-length code, or long
 enough to overflow the 512th power.  In between, a weight falls into fp32's denormal range, which D3D flushes, the oracle's host does not and

@@ -11,7 +11,7 @@ used here reach the deformed meshes, on the host.
 
 A frame is update_frame + update_as + render_visibility + sync (gpu_support.Scene.frame): rtggx_render_visibility is where a staged
 shape is uploaded and the tree refitted; after the sync, readback and trace_rays see the current input set's tree (rtggx_context.h
-selectSet sets MeshDev::nodes / nodes4 / tris / top, which capi.hip bufferInfo and trace.hip launchTrace read)."""
+selectSet sets MeshDev::nodes / nodes4 / tris / top, which debug.hip bufferInfo and trace.hip launchTrace read)."""
 import numpy as np
 import pytest
 

@@ -878,7 +878,7 @@ def test_timing_mode_free_running_equals_synchronised(built):
 
 
 def test_small_frames_two_traversals_in_flight_equal_synchronised(built):
-    """Launches below 200 000 rays send the traversals of odd frames to a second stream, so that two are in flight (capi.hip
+    """Launches below 200 000 rays send the traversals of odd frames to a second stream, so that two are in flight (frame.hip
     rtggx_ray_trace): 48 free-running frames of a turning 640x360 bunny (with diffuse rays: two rays per pixel, both image targets)
     and of a 1920x171 frame against the same frames synchronised one by one -- every target bit-identical, and the free-running
     ray total equal to the synchronised one."""
@@ -902,7 +902,7 @@ def test_small_frames_two_traversals_in_flight_equal_synchronised(built):
 def test_diffuse_image_carry_hands_over_between_ray_generation_and_shading(built):
     """RayTracingOut1 keeps what it held where no diffuse ray is traced; with several input sets that is a carry-over from the previous set,
     done by ray generation while the previous frame's shading kernel wrote nothing into that set and by the shading kernel otherwise
-    (capi.hip rtggx_ray_trace: genCarriesDiff / shadeWroteDiff).  Metal -> diffuse -> metal again, with the camera turning (pixels change
+    (frame.hip rtggx_ray_trace: genCarriesDiff / shadeWroteDiff).  Metal -> diffuse -> metal again, with the camera turning (pixels change
     from sky to covered and back): every frame against the oracle, which has ONE such image -- and the same schedule free-running against
     synchronised at a size that shades on the traversal's streams (640x360) and at one that shades on the main stream (1920x1080)."""
     from raytracedggx_amd import app, capi
@@ -1019,7 +1019,7 @@ def test_copy_bandwidth_leaves_the_context_as_it_found_it(built):
 
 
 def test_every_stream_placement_free_running_equals_synchronised(built):
-    """Where a frame's kernels go is decided in one place from five facts (capi.hip placeFrame: small launch, strip, deforming mesh,
+    """Where a frame's kernels go is decided in one place from five facts (frame.hip placeFrame: small launch, strip, deforming mesh,
     diffuse rays, caller-owned main stream).  Every one of the 32 keys at 320x180: the placement is the table's, and twelve free-running
     frames equal twelve frames synchronised one by one in every target.  (`small` is pinned with rtggx_debug_placement: at this size
     the ray count alone would always say small.)"""

@@ -1,5 +1,5 @@
 // Would ONE graph per frame -- a linear chain of the frame's kernels with external event nodes where a stage must follow the same stage
-// of the frame before -- keep the three-stage pipeline of capi.hip going, and what would it cost the host?
+// of the frame before -- keep the three-stage pipeline of frame.hip going, and what would it cost the host?
 //
 // The frame of a 1920 x 171 strip (durations in us, profiles/r03_c_strip_chain.txt):
 //     stage C   rasterSmall 13, rasterLarge 9, rayGen 10      serial across frames (ray generation reads what the one before wrote)
@@ -116,7 +116,7 @@ int main(int argc, char** argv) {
     CK(hipEventCreateWithFlags(&eGen, hipEventDisableTiming)); for (auto& e : eTr) CK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); for (auto& e : eSet) CK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     unsigned int frameNo = 0;
     for (int variant = 0; variant < 2; ++variant) {
-      char name[96]; snprintf(name, sizeof name, "streams + events (capi.hip today)%s", variant ? ", shade with the traversal" : "");
+      char name[96]; snprintf(name, sizeof name, "streams + events (frame.hip today)%s", variant ? ", shade with the traversal" : "");
       frameNo = 0;
       run(name, [&](int) {
         const int k = (int)(frameNo & 1u);

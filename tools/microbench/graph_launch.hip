@@ -1,8 +1,8 @@
 // What does a frame's submission cost the HOST on this ROCm, launched as individual kernels against replayed as a captured graph?
-// The frame of librtggx on a thin strip is ~10 short kernels over three streams joined by events (capi.hip); the host pays ~4 us per
+// The frame of librtggx on a thin strip is ~10 short kernels over three streams joined by events (frame.hip); the host pays ~4 us per
 // launch (tools/probes/host_cost_probe.py).  This microbenchmark issues a stand-in with the same shape -- chain C (4 kernels) -> chain B
 // (1 kernel) -> chain M (5 kernels), tiny kernels -- in four ways and prints the host time per "frame" and the wall time per frame:
-//   streams     hipLaunchKernelGGL / hipExtLaunchKernelGGL + hipStreamWaitEvent, as capi.hip does today
+//   streams     hipLaunchKernelGGL / hipExtLaunchKernelGGL + hipStreamWaitEvent, as frame.hip does today
 //   graph       the same sequence captured once (hipStreamBeginCapture on C, forked to B and M by events), replayed with hipGraphLaunch
 //   graph+set   as above, with the kernel arguments of K nodes replaced before every launch (hipGraphExecKernelNodeSetParams)
 //   one stream  all ten kernels on one stream, no events (lower bound of the launch path)

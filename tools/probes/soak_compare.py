@@ -1,6 +1,6 @@
 """Long free-running runs against the same frames synchronised one by one (the parity tests do 30-48 frames; this does thousands): every
 target bit-identical at the end, checkpoints on the way.  Material changes on a schedule, so that the diffuse image's carry-over changes
-hands (capi.hip rtggx_ray_trace) many times.   python tools/probes/soak_compare.py [frames]"""
+hands (frame.hip rtggx_ray_trace) many times.   python tools/probes/soak_compare.py [frames]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
