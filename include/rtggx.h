@@ -456,6 +456,15 @@ int  rtggx_debug_static_sky(rtggx_context* ctx, int enable);
 /* ... and the current input set's runs under the current epoch, one word per tile of the most recent ray generation's grid (row-major,
  * *tiles_x by *tiles_y; capacity in words).  *threshold: the run from which that ray generation left a tile alone.  Synchronises. */
 int  rtggx_debug_sky_runs(rtggx_context* ctx, uint32_t* runs, uint32_t capacity, uint32_t* tiles_x, uint32_t* tiles_y, uint32_t* threshold);
+/* Diagnostic (settled sky): over sky that has stopped changing the temporal pass would store the bits it stored two frames ago and the tone
+ * map the bits of the frame before.  The temporal pass keeps one word per 64x4 block, twice by history parity -- epoch << 8 | bit 0: every
+ * texel the block computed equals the one in place in the other history image | bit 1: the block was left alone --, and leaves a block
+ * alone whose window is sky and which was settled, with its eight neighbours, in the frame before; the tone map leaves a 64x16 block alone
+ * over settled blocks.  Whole frames of the two-kernel path only.  enable = 0: no words, nothing left alone.  Same images either way. */
+int  rtggx_debug_settled_sky(rtggx_context* ctx, int enable);
+/* ... and both word arrays (array p belongs to TemporalSSOut[p]), *blocks_x columns of *blocks_y words each, column after column
+ * (capacity in words, per array); *epoch: the epoch that words count under now.  Synchronises. */
+int  rtggx_debug_settled_words(rtggx_context* ctx, uint32_t* words0, uint32_t* words1, uint32_t capacity, uint32_t* blocks_x, uint32_t* blocks_y, uint32_t* epoch);
 /* Diagnostic: the two weights of the 4-wide collapse's objective (lbvh.hip "the 4-wide collapse"): a 4-wide node costs
  * area_weight x (its half-area / the root's) + tris_weight x (its triangles / all triangles) -- the chance that a random ray enters it,
  * and the chance that a ray STARTING on the mesh's surface (every ray of this path does) starts inside it.  set (may be null): weights for

@@ -35,7 +35,7 @@ EXPORTS = ["rtggx_last_error", "rtggx_create", "rtggx_destroy", "rtggx_set_strip
            "rtggx_transform_sh", "rtggx_render_visibility", "rtggx_ray_trace", "rtggx_denoise", "rtggx_tone_map", "rtggx_sync",
            "rtggx_ray_count", "rtggx_get_timings", "rtggx_enable_timing", "rtggx_buffer_size", "rtggx_readback", "rtggx_buffer_ptr",
            "rtggx_upload", "rtggx_frame_parity", "rtggx_bvh_root", "rtggx_trace_rays", "rtggx_ray_total", "rtggx_kernel_times", "rtggx_debug_counters", "rtggx_debug_trace_split", "rtggx_debug_trace_residency", "rtggx_get_stream", "rtggx_set_history_peers", "rtggx_history_ipc_export", "rtggx_history_ipc_open",
-           "rtggx_set_async_compute", "rtggx_set_history_apron", "rtggx_history_overreach", "rtggx_copy_bandwidth", "rtggx_refit_as", "rtggx_refit_as_device", "rtggx_refit_stats", "rtggx_set_refit_policy", "rtggx_set_sampler", "rtggx_set_ray_rate", "rtggx_set_max_recursion_depth", "rtggx_set_samples_per_pixel", "rtggx_debug_fuse_tone_map", "rtggx_debug_placement", "rtggx_debug_tile_words", "rtggx_debug_static_sky", "rtggx_debug_sky_runs", "rtggx_debug_collapse_weights", "rtggx_debug_fence_wait", "rtggx_debug_shader_clock", "rtggx_debug_environment",
+           "rtggx_set_async_compute", "rtggx_set_history_apron", "rtggx_history_overreach", "rtggx_copy_bandwidth", "rtggx_refit_as", "rtggx_refit_as_device", "rtggx_refit_stats", "rtggx_set_refit_policy", "rtggx_set_sampler", "rtggx_set_ray_rate", "rtggx_set_max_recursion_depth", "rtggx_set_samples_per_pixel", "rtggx_debug_fuse_tone_map", "rtggx_debug_placement", "rtggx_debug_tile_words", "rtggx_debug_static_sky", "rtggx_debug_settled_sky", "rtggx_debug_settled_words", "rtggx_debug_sky_runs", "rtggx_debug_collapse_weights", "rtggx_debug_fence_wait", "rtggx_debug_shader_clock", "rtggx_debug_environment",
            "rtggx_set_accumulation", "rtggx_reset_accumulation", "rtggx_accumulated_frames", "rtggx_present_accumulation", "rtggx_set_sample_set",
            "rtggx_set_reference", "rtggx_reference_from_accumulation", "rtggx_set_scoring", "rtggx_read_scores",
            "rtggx_set_env_image", "rtggx_generate_env_mips"]
@@ -229,6 +229,21 @@ class Context:
         self.L.rtggx_debug_sky_runs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         self._check(self.L.rtggx_debug_sky_runs(self.h, _p(runs), tiles, C.byref(tx), C.byref(ty), C.byref(th)))
         return runs[:tx.value * ty.value].reshape(ty.value, tx.value), int(th.value)
+
+    def settled_sky(self, enable):
+        """False: the temporal pass keeps no settled words, and neither it nor the tone map leaves a block over settled sky alone (diagnostic)."""
+        self.L.rtggx_debug_settled_sky.argtypes = [C.c_void_p, C.c_int]
+        self._check(self.L.rtggx_debug_settled_sky(self.h, 1 if enable else 0))
+
+    def settled_words(self):
+        """(words[2, blocks_y, blocks_x], epoch): per history parity and 64x4 block of the temporal pass `epoch << 8 | bit 0 settled | bit 1
+        left alone`, and the epoch words count under now (diagnostic; synchronises)."""
+        n = ((self.W + 63) // 64) * ((self.H + 3) // 4)
+        w = np.zeros((2, n), np.uint32)
+        bx, by, ep = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self.L.rtggx_debug_settled_words.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._check(self.L.rtggx_debug_settled_words(self.h, _p(w[0]), _p(w[1]), n, C.byref(bx), C.byref(by), C.byref(ep)))
+        return np.ascontiguousarray(w.reshape(2, bx.value, by.value).transpose(0, 2, 1)), int(ep.value)
 
     def placement(self, force_small=-1):
         """Pins the `small launch` fact of the stream placement (0 / 1; -1: by the ray count) and returns the key and placement of the most

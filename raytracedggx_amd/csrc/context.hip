@@ -32,6 +32,14 @@ int uploadParams(rtggx_context* c, uint32_t slot, hipStream_t s) {
   RT_HIP(hipGetLastError());
   return 0;
 }
+int resetSettled(rtggx_context* c) {
+  for (auto& w : c->settled) {
+    RT_HIP(hipMemset(w, 0xFF, c->settledWords() * 4));
+    RT_HIP(hipMemset2D(w + c->settledPitch + 1u, (size_t)c->settledPitch * 4, 0, (size_t)c->settledY * 4, c->settledX));
+  }
+  RT_HIP(hipStreamSynchronize(nullptr));
+  return 0;
+}
 // The buffers of input set i (rtggx_context.h InputSet) that it does not have yet: all of them at creation, the ray bins again after
 // growBins has released them.  The G-buffer words and the traced images start cleared.
 int allocSet(rtggx_context* c, uint32_t i) {
@@ -88,6 +96,10 @@ static int initContext(rtggx_context* c, uint32_t width, uint32_t height, int de
   for (uint32_t i = 0; i < RT_SETS; ++i) { const int r = allocSet(c, i); if (r) return r; }
   for (auto& v : c->vis) { RT_HIP(allocFilled(v.depth, n)); RT_HIP(allocFilled(v.dirty, c->skyTiles, 0xFF)); }
   RT_HIP(allocFilled(c->visDirtyOnes, c->skyTiles, 0xFF));
+  c->settledX = (width + 63) / 64; c->settledY = (height + 3) / 4;      // one word per block of the temporal pass and a border (rtggx_context::settled)
+  c->settledPitch = (c->settledY + 3u) / 4u * 4u + 2u;                    // (a tone-map block reads the words of four blocks and one either side)
+  for (auto& w : c->settled) RT_HIP(alloc(w, c->settledWords()));
+  { const int r = resetSettled(c); if (r) return r; }
   RT_HIP(allocFilled(c->backbuffer, n));
   RT_HIP(allocFilled(c->tss[0], n)); RT_HIP(allocFilled(c->tss[1], n)); RT_HIP(allocFilled(c->fltRfl, n)); RT_HIP(allocFilled(c->fltDff, n));
   RT_HIP(allocFilled(c->rayCounter, 512));

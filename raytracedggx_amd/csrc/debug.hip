@@ -79,6 +79,27 @@ int rtggx_debug_sky_runs(rtggx_context* c, uint32_t* runs, uint32_t capacity, ui
   if (threshold) *threshold = RT_SKY_PREV_RUN + 1u;
   return 0;
 }
+// Settled sky (denoise.hip temporalKernel): enable = 0 -- no words are kept and no block of the temporal pass or the tone map is left alone.
+int rtggx_debug_settled_sky(rtggx_context* c, int enable) {
+  RT_CHECK_CTX(c);
+  c->settledSky = enable != 0;
+  c->breakSkyRuns();
+  return 0;
+}
+// Both word arrays as they are (epoch << 8 | flags) without their border, blocksX columns of blocksY words each; *epoch: the epoch words count under now.
+int rtggx_debug_settled_words(rtggx_context* c, uint32_t* words0, uint32_t* words1, uint32_t capacity, uint32_t* blocksX, uint32_t* blocksY, uint32_t* epoch) {
+  RT_CHECK_CTX(c);
+  const uint32_t n = c->settledX * c->settledY;
+  if (!words0 || !words1 || capacity < n) { setError("rtggx_debug_settled_words: room for %u words each", n); return -1; }
+  RT_HIP(syncStreams(c));
+  uint32_t* const out[2] = {words0, words1};
+  for (int p = 0; p < 2 && n; ++p)
+    RT_HIP(hipMemcpy2D(out[p], (size_t)c->settledY * 4, c->settled[p] + c->settledPitch + 1u, (size_t)c->settledPitch * 4, (size_t)c->settledY * 4, c->settledX, hipMemcpyDeviceToHost));
+  if (blocksX) *blocksX = c->settledX;
+  if (blocksY) *blocksY = c->settledY;
+  if (epoch) *epoch = c->skyEpoch;
+  return 0;
+}
 int rtggx_debug_placement(rtggx_context* c, int forceSmall, uint32_t* key, uint32_t* where) {
   RT_CHECK_CTX(c);
   if (forceSmall < -1 || forceSmall > 1) { setError("rtggx_debug_placement: force_small is -1, 0 or 1"); return -1; }

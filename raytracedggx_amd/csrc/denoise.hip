@@ -76,6 +76,10 @@ struct Targets {
   // still sky (rtggx_context.h InputSet::skyRun, RT_SKY_V_RUN): the set's run words, indexed like tileWords, and the epoch they count under;
   // null: the reflection V pass converts every sky texel (launchDenoise decides)
   const uint32_t* skyRun; uint32_t skyEpoch;
+  // settled sky (rtggx_context.h rtggx_context::settled; "Settled sky" below): settledOut -- the temporal pass writes its blocks' words there
+  // (null: it keeps none); settledIn -- the words a block may be left alone for: the other parity's in the temporal pass (with skyRun and
+  // skyEpoch), this frame's in the tone map (null: no block is left alone); settledPitch: words of a column, border included
+  uint32_t* settledOut; const uint32_t* settledIn; uint32_t settledPitch;
 };
 #define RT_SGPR(v) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(v)))      // a workgroup-uniform value the compiler may have computed in vector registers
 // Four of those words OR-ed together: scalar loads, one wait (the indices are uniform over the workgroup).
@@ -103,6 +107,24 @@ RT_DEV uint32_t skyRunMin6(const uint32_t* words, uint32_t epoch, uint32_t i0, u
 #pragma unroll
   for (int k = 0; k < 6; ++k) run = min(run, (w[k] >> 8) == epoch ? w[k] & 0xFFu : 0u);
   return run;
+}
+
+// Settled sky (temporalKernel, toneMapKernel): the words a workgroup decides on, by scalar loads of several words each and ONE wait.
+typedef uint32_t U2 __attribute__((ext_vector_type(2)));
+typedef uint32_t U4 __attribute__((ext_vector_type(4)));
+// six consecutive run words from each of two rows, and three columns of settled words (three consecutive words count of each four)
+RT_DEV void loadTemporalWords(const uint32_t* rowA, const uint32_t* rowB, const uint32_t* col0, const uint32_t* col1, const uint32_t* col2,
+                              U4& a4, U2& a2, U4& b4, U2& b2, U4& c0, U4& c1, U4& c2) {
+  asm volatile("s_load_dwordx4 %0, %7, 0x0\n\ts_load_dwordx2 %1, %7, 0x10\n\ts_load_dwordx4 %2, %8, 0x0\n\ts_load_dwordx2 %3, %8, 0x10\n\t"
+               "s_load_dwordx4 %4, %9, 0x0\n\ts_load_dwordx4 %5, %10, 0x0\n\ts_load_dwordx4 %6, %11, 0x0\n\ts_waitcnt lgkmcnt(0)"
+               : "=&s"(a4), "=&s"(a2), "=&s"(b4), "=&s"(b2), "=&s"(c0), "=&s"(c1), "=&s"(c2)
+               : "s"(rowA), "s"(rowB), "s"(col0), "s"(col1), "s"(col2) : "memory");
+}
+// three columns of six consecutive settled words
+RT_DEV void loadToneMapWords(const uint32_t* col0, const uint32_t* col1, const uint32_t* col2, U4& a4, U2& a2, U4& b4, U2& b2, U4& c4, U2& c2) {
+  asm volatile("s_load_dwordx4 %0, %6, 0x0\n\ts_load_dwordx2 %1, %6, 0x10\n\ts_load_dwordx4 %2, %7, 0x0\n\ts_load_dwordx2 %3, %7, 0x10\n\t"
+               "s_load_dwordx4 %4, %8, 0x0\n\ts_load_dwordx2 %5, %8, 0x10\n\ts_waitcnt lgkmcnt(0)"
+               : "=&s"(a4), "=&s"(a2), "=&s"(b4), "=&s"(b2), "=&s"(c4), "=&s"(c2) : "s"(col0), "s"(col1), "s"(col2) : "memory");
 }
 
 #define RT_LOG2E 1.44269504088896341f
@@ -548,17 +570,85 @@ RT_DEV void stageTemporalTiles(const Targets& T, float4 (&tile)[ROWS][PITCH], ui
     velSq[t / PITCH][t % PITCH] = vx * vx + vy * vy;
   }
 }
+// Settled sky (whole frames, the two-kernel path; launchDenoise / launchToneMap decide).  Over sky that has stopped changing the temporal pass
+// stores, frame after frame, the bits it stored two frames ago, and the tone map the bits of the frame before.  One word per block of the
+// temporal pass (rtggx_context::settled), twice by history parity, says where: epoch << 8 | RT_SETTLED | RT_SETTLED_SKIPPED.
+//   windowSky   every 16x16 tile the block's 66 x 6 window touches has a run of RT_SKY_WINDOW_RUN under the current epoch (rtggx_context.h)
+//   settled     the block computed its texels with windowSky and every one of them equals, bit for bit, the texel at the same place of
+//               the history image -- certified by comparing what was just computed with what is in memory, not by reasoning about how the
+//               history alpha converges: a pixel that never reaches a fixed point leaves its block unsettled for ever
+//   skip        windowSky, and the block and its eight neighbours were settled in the frame before, under the same epoch (a neighbour outside
+//               the grid counts as settled, RT_SETTLED_BORDER: clamped addressing never reads outside the frame).  The block's word becomes settled | skipped.
+// Why the skip is exact.  Frame f + 1, block b, history parity p = parity(f + 1):
+//   * in a block whose window is sky under one epoch the inputs are functions of the pixel and the epoch alone: FilteredOut1 is the converted
+//     environment texel with alpha 0 and the velocity is 0 (the V pass either rewrote the same conversion or validly left it, RT_SKY_V_RUN;
+//     texels outside the frame are staged as zeros) -- the same in frames f and f + 1;
+//   * velocity 0 puts the four history taps within one pixel of the pixel: inside b and its eight neighbours;
+//   * so out(f + 1) on b is the function that gave out(f), applied to the same inputs with history out(f) in place of the image out(f) was
+//     computed from, TSS[p].  The nine words say those two images are bitwise equal over b and its apron: out(f + 1) = out(f) on b;
+//   * and TSS[p] holds, on b, those very bits (b's own word).  Leaving it alone leaves the right bits in both images.  NaNs are covered:
+//     equal bits go in, equal bits come out.
+// The tone map leaves a 64 x 16 block alone when the 18 words under it and its one-pixel apron are settled in THIS frame: the back buffer
+// exists once, the previous tone map wrote it from the other history image, which these words say equals this one over everything the
+// block reads.
+// -DRT_SETTLED_NO_COMPARE sets a windowSky block's word without comparing: tests/test_gpu_settled_sky.py must fail with it (and does).
+RT_DEV bool settledWord(uint32_t w, uint32_t epoch) { return (w & ~RT_SETTLED_SKIPPED) == ((epoch << 8) | RT_SETTLED) || w == RT_SETTLED_BORDER; }
+// WORDS: the variant that keeps words; without it the kernel is the one it was (a camera that moves every frame runs that one).
 #define RT_TP_ROWS 4
+template <bool WORDS>
 __global__ void __launch_bounds__(256) temporalKernel(Targets T) {
   __shared__ float4 tile[RT_TP_ROWS + 2][66];
   __shared__ uint32_t velRaw[RT_TP_ROWS + 2][66];      // the velocity texels of the same window (zero outside the frame) ...
   __shared__ float velSq[RT_TP_ROWS + 2][66];          // ... and their squared lengths: VelocityMax compares five of them per pixel
+  const uint32_t wordAt = (blockIdx.x + 1u) * T.settledPitch + blockIdx.y + 1u;      // (rtggx_context::settled)
+  bool windowSky = false;
+  if (WORDS && T.settledIn != nullptr) {      // (uniform; whole frames of at least six tiles across: rowBegin = tileRow0 = 0)
+    const int bx = (int)blockIdx.x, by = (int)blockIdx.y;
+    // the tiles of the window, texels bx 64 - 1 .. bx 64 + 64 by by 4 - 1 .. by 4 + 4 clamped to the frame: txa .. txb, six across at most, in
+    // rows tya and tyb (mostly the same).  Six consecutive words of each row are loaded from tx0 on, the ones beside the window ignored.
+    const int txa = max(bx * 64 - 1, 0) >> 4, txb = min(bx * 64 + 64, T.W - 1) >> 4, tx0 = min(txa, T.tilesX - 6);
+    const int tya = max(by * RT_TP_ROWS - 1, 0) >> 4, tyb = min(by * RT_TP_ROWS + RT_TP_ROWS, T.H - 1) >> 4;
+    const uint32_t* col = T.settledIn + (uint32_t)bx * T.settledPitch + (uint32_t)by;      // (bx - 1, by - 1) behind the border
+    U4 a4, b4, c0, c1, c2; U2 a2, b2;
+    loadTemporalWords(T.skyRun + tya * T.tilesX + tx0, T.skyRun + tyb * T.tilesX + tx0, col, col + T.settledPitch, col + 2u * T.settledPitch, a4, a2, b4, b2, c0, c1, c2);
+    const uint32_t ra[6] = {a4.x, a4.y, a4.z, a4.w, a2.x, a2.y}, rb[6] = {b4.x, b4.y, b4.z, b4.w, b2.x, b2.y};
+    uint32_t run = RT_SKY_RUN_CAP;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      const bool inWindow = tx0 + k >= txa && tx0 + k <= txb;
+      const uint32_t r = min((ra[k] >> 8) == T.skyEpoch ? ra[k] & 0xFFu : 0u, (rb[k] >> 8) == T.skyEpoch ? rb[k] & 0xFFu : 0u);
+      run = min(run, inWindow ? r : RT_SKY_RUN_CAP);
+    }
+    windowSky = run >= RT_SKY_WINDOW_RUN;
+    const uint32_t w[9] = {c0.x, c0.y, c0.z, c1.x, c1.y, c1.z, c2.x, c2.y, c2.z};
+    bool skip = windowSky;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) skip = skip & settledWord(w[k], T.skyEpoch);
+    if (skip) {
+      if (threadIdx.x == 0) T.settledOut[wordAt] = (T.skyEpoch << 8) | RT_SETTLED | RT_SETTLED_SKIPPED;
+      return;
+    }
+  }
   stageTemporalTiles<RT_TP_ROWS + 2, 66, 256>(T, tile, velRaw, velSq, (int)blockIdx.x * 64 - 1, T.rowBegin + (int)blockIdx.y * RT_TP_ROWS - 1);
   __syncthreads();
   const int lx = (threadIdx.x & 63) + 1, ly = (threadIdx.x >> 6) + 1;
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = T.rowBegin + blockIdx.y * RT_TP_ROWS + (threadIdx.x >> 6);
-  if (x >= T.W || y >= T.rowEnd) return;
-  T.scratch[(size_t)y * T.W + x] = temporalPixel<RT_TP_ROWS + 2, 66>(T, tile, velRaw, velSq, x, y, lx, ly);
+  bool equal = true;
+  if (x < T.W && y < T.rowEnd) {
+    const size_t pix = (size_t)y * T.W + x;
+    // the texel in place at this pixel, where the block may settle: issued in front of the four history taps, whose cache lines it shares
+    uint2 inPlace = make_uint2(0u, 0u);
+    if (WORDS && windowSky) inPlace = T.history[pix];
+    const uint2 out = temporalPixel<RT_TP_ROWS + 2, 66>(T, tile, velRaw, velSq, x, y, lx, ly);
+    T.scratch[pix] = out;
+#ifndef RT_SETTLED_NO_COMPARE
+    equal = inPlace.x == out.x && inPlace.y == out.y;
+#endif
+  }
+  if (!WORDS || T.settledOut == nullptr) return;      // (uniform)
+  // a block that is not windowSky pays the scalar loads above and this store, and no vector load it did not do before
+  const uint32_t flag = windowSky && __syncthreads_and(equal ? 1 : 0) ? RT_SETTLED : 0u;
+  if (threadIdx.x == 0) T.settledOut[wordAt] = (T.skyEpoch << 8) | flag;
 }
 
 // The temporal pass and the tone map in ONE kernel (round 4; CSTemporalSS.hlsl:254-336 + PSToneMap.hlsl:13-41; Denoiser.cpp:66-103 issues
@@ -620,10 +710,22 @@ __global__ void __launch_bounds__(RT_TT_TW * RT_TT_TH) temporalToneKernel(Target
 #ifndef RT_TM_ROWS
 #define RT_TM_ROWS 16
 #endif
+template <bool WORDS>
 __global__ void __launch_bounds__(256) toneMapKernel(Targets T) {
 #pragma clang fp contract(fast)
   __shared__ float4 tile[RT_TM_ROWS + 2][66];          // c / (c + 0.5) of the block's pixels and a one-texel apron, computed once per texel
   const int W = T.W, H = T.H;
+  if (WORDS && T.settledIn != nullptr) {      // settled sky (see temporalKernel): the blocks of the temporal pass under this block and its apron, three columns of six words
+    static_assert(RT_TM_ROWS == 4 * RT_TP_ROWS, "a tone-map block is four blocks of the temporal pass high");
+    const uint32_t* col = T.settledIn + blockIdx.x * T.settledPitch + blockIdx.y * 4u;      // (bx - 1, 4 by - 1) behind the border
+    U4 a4, b4, c4; U2 a2, b2, c2;
+    loadToneMapWords(col, col + T.settledPitch, col + 2u * T.settledPitch, a4, a2, b4, b2, c4, c2);
+    const uint32_t w[18] = {a4.x, a4.y, a4.z, a4.w, a2.x, a2.y, b4.x, b4.y, b4.z, b4.w, b2.x, b2.y, c4.x, c4.y, c4.z, c4.w, c2.x, c2.y};
+    bool skip = true;
+#pragma unroll
+    for (int k = 0; k < 18; ++k) skip = skip & settledWord(w[k], T.skyEpoch);
+    if (skip) return;
+  }
   {
     const int ox = blockIdx.x * 64 - 1, oy = T.rowBegin + blockIdx.y * RT_TM_ROWS - 1;
     constexpr int N = (RT_TM_ROWS + 2) * 66, PER = (N + 255) / 256;
@@ -678,6 +780,7 @@ static Targets makeTargets(rtggx_context* c, const FrameParams& fp, RowPass pass
   { uint32_t gb, ge; passRows(fp, ROWS_GBUFFER, gb, ge);      // the tiles are ray generation's
     T.tileWords = c->tileWords(gb, ge); T.tilesX = (int)((fp.W + 15) / 16); T.tileRow0 = (int)gb; }
   T.skyRun = nullptr; T.skyEpoch = 0u;
+  T.settledOut = nullptr; T.settledIn = nullptr; T.settledPitch = c->settledPitch;
   return T;
 }
 
@@ -699,6 +802,34 @@ static bool skyVPassMaySkip(rtggx_context* c, const Targets& TV, uint32_t gbuffe
                    && was.rows[0] == now.rows[0] && was.rows[1] == now.rows[1] && was.fltRflNull == now.fltRflNull;
   c->skyV = now;
   *epoch = c->skyEpoch;
+  return may;
+}
+
+// Settled sky in the temporal pass (temporalKernel): does this frame's pass keep words, and may it leave blocks alone for the words of the
+// pass before it?  It keeps them on whole frames (no strip: no histReach, no peers, no apron rows) of the two-kernel path, when the pass
+// before it ran under the same epoch.  Under a NEW epoch it stores none and needs none: every word in either array carries an older epoch
+// and reads as unsettled (a camera that moves every frame pays nothing).  The first pass after anything else that breaks the chain
+// -- a fused pass, a frame without the denoiser -- stores `epoch | 0` everywhere, over words that may describe images written since.
+// It may leave blocks alone when, besides,
+//     this frame's ray generation has run under the epoch that is still current, over the rows the run words are indexed by (genValid, as
+//       the reflection V pass requires it);
+//     the temporal pass before this one was the previous frame's, kept words, over the same rows, and wrote the other history image and
+//       word array (frameParity flips even for an empty strip's rtggx_denoise).
+// Records this pass as the previous one of the next, whatever it does.
+static bool skyTemporalMaySkip(rtggx_context* c, const Targets& TT, const FrameParams& fp, bool fused, bool* words) {
+  rtggx_context::SkyT now;
+  const rtggx_context::SkyT& was = c->skyT;
+  const bool whole = fp.rowBegin == 0u && fp.rowEnd == fp.H && fp.W == c->W && fp.H == c->H;
+  const bool genValid = c->skyGen.any && c->skyGen.frame == c->frameCounter && c->skyGen.epoch == c->skyEpoch && c->skyGen.rows[0] == (uint32_t)TT.tileRow0;
+  now.any = true; now.frame = c->frameCounter; now.epoch = c->skyEpoch; now.parity = c->frameParity;
+  now.words = c->staticSky && c->settledSky && !fused && whole && fp.W >= 96u      // (six tiles across: temporalKernel's loads)
+              && was.any && was.epoch == now.epoch;
+  now.rows[0] = (uint32_t)TT.rowBegin; now.rows[1] = (uint32_t)TT.rowEnd;
+  const bool may = now.words && genValid && was.words && was.frame + 1u == now.frame && was.parity == (now.parity ^ 1u)
+                   && was.rows[0] == now.rows[0] && was.rows[1] == now.rows[1];
+  c->skyT = now;
+  ++c->tssWrites[now.parity];
+  *words = now.words;
   return may;
 }
 
@@ -735,10 +866,16 @@ int launchDenoise(rtggx_context* c, const FrameParams& fp, int useLds, hipStream
     hipLaunchKernelGGL(spatialDirectKernel<2>, grid(TH, 64, 4), block, 0, s, TH); mark(6);
     hipLaunchKernelGGL(spatialDirectKernel<3>, grid(TV, 64, 4), block, 0, s, TV); mark(7);
   }
+  Targets TTs = TT;
+  { bool words;
+    const bool may = skyTemporalMaySkip(c, TT, fp, fuseToneMap, &words);
+    if (words) { TTs.settledOut = c->settled[c->frameParity]; TTs.skyEpoch = c->skyEpoch; }
+    if (may) { TTs.settledIn = c->settled[c->frameParity ^ 1u]; TTs.skyRun = c->cur().skyRun; } }
   if (fuseToneMap) {      // the temporal pass and the tone map of its result in one kernel: workgroups of 62 x 14 back-buffer pixels over the strip's own rows
     const dim3 g((fp.W + RT_TT_W - 1) / RT_TT_W, (uint32_t)(TT.outEnd - TT.outBegin + RT_TT_H - 1) / RT_TT_H), b(RT_TT_TW * RT_TT_TH);
     launch(temporalToneKernel, g, b, s, nullptr, done, TT);
-  } else launch(temporalKernel, grid(TT, 64, RT_TP_ROWS), block, s, nullptr, done, TT);
+    c->skyTM.any = false;      // (the back buffer has another writer than the tone map the record describes)
+  } else launch(TTs.settledOut ? temporalKernel<true> : temporalKernel<false>, grid(TT, 64, RT_TP_ROWS), block, s, nullptr, done, TTs);
   mark(8);
   RT_HIP(hipGetLastError());
   return 0;
@@ -751,8 +888,23 @@ int launchToneMap(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEve
   if (fp.rowEnd <= fp.rowBegin) return 0;
   Targets T = makeTargets(c, fp, ROWS_FINAL);
   if (source) T.scratch = const_cast<uint2*>(source);
+  // Settled sky (toneMapKernel): the tone map may leave blocks alone for this frame's words when
+  //     this frame's temporal pass kept words, for the image this tone map reads (TSS[parity], not `source`), under the epoch that is still current;
+  //     the tone map before this one was the previous frame's, under the same epoch, over the same rows, and read the OTHER history image
+  //       as it still is (no temporal pass has written it since): the image this frame's words compare with.
+  // Records this tone map as the previous one of the next.
+  { rtggx_context::SkyTM now;
+    now.any = true; now.fromTss = source == nullptr; now.frame = c->frameCounter; now.epoch = c->skyEpoch; now.parity = c->frameParity; now.writes = c->tssWrites[c->frameParity];
+    now.rows[0] = (uint32_t)T.rowBegin; now.rows[1] = (uint32_t)T.rowEnd;
+    const rtggx_context::SkyTM& was = c->skyTM; const rtggx_context::SkyT& t = c->skyT;
+    const bool whole = fp.rowBegin == 0u && fp.rowEnd == fp.H && fp.W == c->W && fp.H == c->H;
+    const bool may = c->staticSky && c->settledSky && whole && now.fromTss && t.any && t.words && t.frame == now.frame && t.parity == now.parity && t.epoch == now.epoch
+                     && was.any && was.fromTss && was.frame + 1u == now.frame && was.epoch == now.epoch && was.rows[0] == now.rows[0] && was.rows[1] == now.rows[1]
+                     && was.parity == (now.parity ^ 1u) && was.writes == c->tssWrites[now.parity ^ 1u];
+    c->skyTM = now;
+    if (may) { T.settledIn = c->settled[c->frameParity]; T.skyEpoch = c->skyEpoch; } }
   const dim3 grid((fp.W + 63) / 64, (uint32_t)(T.rowEnd - T.rowBegin + RT_TM_ROWS - 1) / RT_TM_ROWS), block(256);
-  launch(toneMapKernel, grid, block, s, nullptr, done, T);
+  launch(T.settledIn ? toneMapKernel<true> : toneMapKernel<false>, grid, block, s, nullptr, done, T);
   RT_HIP(hipGetLastError());
   return 0;
 }

@@ -1048,6 +1048,7 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
   if (c->skyEpochWrapped) {      // once in 2^24 bumps: no word of an earlier time round may meet its epoch again
     RT_HIP(hipDeviceSynchronize());
     for (auto& st : c->sets) RT_HIP(hipMemset(st.skyRun, 0, c->skyTiles * 4));
+    { const int r = resetSettled(c); if (r) return r; }
     RT_HIP(hipStreamSynchronize(nullptr));
     c->skyEpochWrapped = false;
   }

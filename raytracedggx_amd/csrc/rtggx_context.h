@@ -53,8 +53,24 @@
 //     the traversal does not touch the bins of a tile whose word is 0).
 // The reflection V pass (denoise.hip) leaves a block alone when all its tiles have a run of RT_SKY_V_RUN: FilteredOut1 exists once, and the
 // previous frame's V pass stored the same conversion of the same sky texels there.
+// The temporal pass and the tone map (denoise.hip "settled sky") ask for a run of RT_SKY_WINDOW_RUN in every tile their window touches, and
+// for no more: they keep no copy of anything from an earlier frame that a run would have to vouch for -- what is already in place they
+// compare bit by bit (the settled words).  The run only has to say what this frame's INPUTS are over the window:
+//   * a run of 1 under the current epoch: this frame's ray generation found the tile without a surface at rate 1.  It then stored velocity 0
+//     and the environment texel behind the pixel into this set, or validly left them in place (RT_SKY_PREV_RUN); both are functions of the
+//     pixel and the epoch alone (raytrace.hip skyEpochForGen: the camera and the environment are in the epoch, jitter and frame index do
+//     not enter a sky pixel);
+//   * the reflection V pass of this frame stored that texel's conversion, alpha 0, into FilteredOut1 -- every pixel without a surface takes
+//     storeSkipped, in a tile without a surface or beside one -- or validly left it in place (RT_SKY_V_RUN).
+// A longer run would add nothing: the frame before is covered by the settled word, which is set only by a block whose window had these
+// runs in ITS frame, under the same epoch.
 #define RT_SKY_PREV_RUN (RT_SETS + 2)
 #define RT_SKY_V_RUN 2u
+#define RT_SKY_WINDOW_RUN 1u
+// Settled words (rtggx_context::settled): epoch << 8 | flags of one 64 x 4 block of the temporal pass
+#define RT_SETTLED 1u          // the block's texels of this frame are, bit for bit, the ones the other history image holds
+#define RT_SETTLED_SKIPPED 2u  // ... and the block was left alone for it (a mark for tests: readers mask it)
+#define RT_SETTLED_BORDER 0xFFFFFFFFu      // a word outside the grid (no block's word: flags are two bits)
 #define RT_SKY_RUN_CAP 255u
 namespace rt {
 
@@ -351,6 +367,19 @@ struct rtggx_context {
   void breakSkyRuns() { skyEpoch = (skyEpoch + 1u) & 0xFFFFFFu; if (skyEpoch == 0u) skyEpochWrapped = true; }
   struct SkyGen { bool any = false, adaptive = false; uint32_t frame = 0, epoch = 0, rows[2] = {0, 0}, rate = 0, sliceShift = 0, tilesX = 0, tilesY = 0; hipStream_t stream = nullptr; float camera[20] = {}; } skyGen;
   struct SkyV { bool any = false, fltRflNull = false; uint32_t frame = 0, genEpoch = 0, rows[2] = {0, 0}; } skyV;
+  // Settled sky (denoise.hip temporalKernel, toneMapKernel): one word per 64 x 4 block of the temporal pass, twice by
+  // history parity -- array p is written by the temporal pass that writes TSS[p].  Column-major with a border: block (bx, by) of settledX x
+  // settledY at (bx + 1) * settledPitch + by + 1, so that the three words of a block's column of neighbours and the six under a tone-map
+  // block are consecutive and no reader clamps.  The border (a column either side, a word above, the rest of the pitch below) holds
+  // RT_SETTLED_BORDER, which no kernel writes and every reader takes as settled: clamped addressing never reads outside the frame.  Words
+  // count under skyEpoch like the run words.  skyT / skyTM: the facts of the most recent temporal pass and tone map, from which
+  // launchDenoise / launchToneMap decide whether this frame's may leave blocks alone.
+  bool settledSky = true;        // rtggx_debug_settled_sky
+  rt::DevBuf<uint32_t> settled[2]; uint32_t settledX = 0, settledY = 0, settledPitch = 0;
+  size_t settledWords() const { return (size_t)(settledX + 2u) * settledPitch + 8u; }      // (+ 8: a reader's four-word load of three words may end beyond the last column)
+  struct SkyT { bool any = false, words = false; uint32_t frame = 0, epoch = 0, parity = 0, rows[2] = {0, 0}; } skyT;
+  struct SkyTM { bool any = false, fromTss = false; uint32_t frame = 0, epoch = 0, parity = 0, writes = 0, rows[2] = {0, 0}; } skyTM;
+  uint32_t tssWrites[2] = {0, 0};      // temporal passes that have written TSS[p] (skyTM.writes: as many as when that tone map read its image)
   bool useTileWords = true;      // rtggx_debug_tile_words
   // Where the TRAVERSAL is the frame's period (two rays per pixel into a large mesh: it runs 96 % of the time) nobody asks the words:
   // workgroups over empty tiles that leave at once make the other stages' kernels run denser beside the traversal and stretch it -- dragon,
@@ -470,6 +499,7 @@ int launchScore(rtggx_context* c, const FrameParams& fp, hipStream_t s);      //
 int launchReferenceFromAccumulation(rtggx_context* c, hipStream_t s);      // rtggx_context::reference = the mean image of the sums and accumFrames
 int launchTraceRays(rtggx_context* c, const FrameParams& fp, const float* dRays, uint32_t n, float* dOut, hipStream_t s);
 int launchDebugEnvironment(rtggx_context* c, const float* dDirs, const float* dLevels, uint32_t n, int level0, float* dOut, hipStream_t s);      // rtggx_debug_environment: reads the environment only
+int resetSettled(rtggx_context* c);      // both arrays of settled words: blocks 0, border RT_SETTLED_BORDER (context.hip; null stream, the caller has synchronised)
 int launchDenoise(rtggx_context* c, const FrameParams& fp, int useLds, hipStream_t s, hipEvent_t done = nullptr, bool fuseToneMap = false);      // fuseToneMap: the last kernel also writes the back buffer
 int launchToneMap(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent_t done = nullptr, const uint2* source = nullptr);      // source: an RGBA16F image to tone-map instead of TemporalSSOut[parity]
 int decodeEnv(rtggx_context* c, int format, uint32_t size, uint32_t mips, const void* hostData, size_t bytes, hipStream_t s);
