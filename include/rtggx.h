@@ -383,6 +383,33 @@ int  rtggx_reference_from_accumulation(rtggx_context* ctx);
 int  rtggx_set_scoring(rtggx_context* ctx, int enable);
 int  rtggx_read_scores(rtggx_context* ctx, RtggxScore* out, uint32_t capacity, uint32_t* count);
 
+/* Adaptive sampling (opt-in, no counterpart in the reference; DESIGN.md "Adaptive sampling"): with N > 1 samples per pixel
+ * (rtggx_set_samples_per_pixel) a map says how many of the N samples each 8 x 8-pixel block of the full frame traces.  A context that never
+ * calls either of the two functions below allocates and launches exactly what it always did.
+ *   - the map: one count per block, row-major, blocks_x = ceil(W / 8) by blocks_y = ceil(H / 8), each count 1, 2, 4 or 8.  A block is one ray
+ *     bin -- one wave of ray generation --, and the device copy is kept in bin order (RTGGX_BUF_BIN_WORK's: bin = 4 tile + 2 subY + subX);
+ *   - with c = min(count of the pixel's block, N): a covered pixel traces the samples k = 0 .. c - 1 of the N-sample frame -- the same
+ *     samples, indices FrameIndex * N + k, at every recursion level, with both samplers and every sample-set size --, and its word is
+ *     pack_r11g11b10((0 + v_0 + ... + v_{c-1}) * (1 / c)) in fp32, in that order, without contraction; RayTracingOut1 likewise where the
+ *     pixel's metallic < 1.  Everything else is the N-sample frame's bit for bit: G-buffer, visibility and background words, the carry-over
+ *     of RayTracingOut1 at metallic >= 1, tile words, still-sky and settled-sky behaviour, accumulation (it adds the resolved word) and
+ *     scoring.  A map of all N, or no map, is the N-sample frame; a map of all 1 holds at covered pixels the words of a one-sample frame
+ *     with FrameIndex * N as its index;
+ *   - rtggx_ray_count / rtggx_ray_total count the rays actually traced.  The frame still launches the N * D passes of the N-sample frame:
+ *     a wave whose block has had its c samples stores an empty bin and leaves, and the traversal and shading passes find fewer rays;
+ *   - N = 1 ignores the map: the one-sample frame launches what it always did;
+ *   - rtggx_set_sample_map(ctx, NULL, 0, 0) clears the map.  Refused, the context keeping what it had: other dimensions than the frame's,
+ *     a count other than 1, 2, 4 or 8, a map on a context with a strip and a strip on a context with a map (strip tiles count from the
+ *     pass's first row, so a block would no longer be a bin: whole frames only, like ray rate 4).  Synchronises; takes effect from the
+ *     next rtggx_render_visibility.  The first set allocates 2 x 4 bytes per 16 x 16 tile, released by rtggx_destroy;
+ *   - rtggx_read_sample_map: the map most recently set, row-major, read back from the device copy; blocks_x = blocks_y = 0
+ *     and nothing written when there is none.  A capacity below blocks_x * blocks_y is refused (the dimensions are still returned).
+ *     Synchronises.
+ * The library sets no policy: where the counts come from is the caller's (DESIGN.md "Adaptive sampling" records the one that was measured
+ * and left out).  tests/adaptive_ref.py restates the frames. */
+int  rtggx_set_sample_map(rtggx_context* ctx, const uint8_t* counts, uint32_t blocks_x, uint32_t blocks_y);
+int  rtggx_read_sample_map(rtggx_context* ctx, uint8_t* counts, uint32_t capacity, uint32_t* blocks_x, uint32_t* blocks_y);
+
 /* Build of both bottom-level structures (RayTracer::buildAccelerationStructures / BuildAccelerationStructures, RayTracer.cpp:676-716,
  * 158-233; the sample records the builds on the GPU timeline and waits once, RayTracedGGX.cpp:236): every step of the build --
  * Morton codes, sort, PLOC clustering, the refit schedule, the node arrays -- is a kernel launch on the context's build stream

@@ -19,7 +19,8 @@ HOST_EXPORTS = ["rtggx_app_last_error", "rtggx_app_create", "rtggx_app_destroy",
                 "rtggx_host_exchange_plan", "rtggx_host_balanced_bounds", "rtggx_app_set_dump_prefix", "rtggx_app_last_screen_shot", "rtggx_app_save_converged",
                 "rtggx_host_frame_indices", "rtggx_host_accumulation_note",
                 "rtggx_app_save_reference", "rtggx_app_flush_scores", "rtggx_app_set_reference", "rtggx_app_set_scoring", "rtggx_app_read_scores",
-                "rtggx_host_write_pfm", "rtggx_host_read_pfm", "rtggx_host_load_env_image"]
+                "rtggx_host_write_pfm", "rtggx_host_read_pfm", "rtggx_host_load_env_image",
+                "rtggx_app_set_sample_map"]
 
 _lib = None
 
@@ -55,6 +56,7 @@ def load():
         L.rtggx_host_read_pfm.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.rtggx_host_load_env_image.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int),
                                                 C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.rtggx_app_set_sample_map.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         L.rtggx_app_last_screen_shot.argtypes = [C.c_void_p]
         L.rtggx_app_last_screen_shot.restype = C.c_char_p
         L.rtggx_host_obj_import.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p]
@@ -250,6 +252,17 @@ class RayTracedGGX:
 
     def reference_from_accumulation(self):
         self.context.reference_from_accumulation()
+
+    def set_sample_map(self, counts):
+        """RayTracer::SetSampleMap: uint8[ceil(H / 8), ceil(W / 8)] counts (1, 2, 4 or 8) of the -spp N samples each 8x8 block traces, from the
+        next frame on; None clears the map."""
+        if counts is None:
+            rc = self.L.rtggx_app_set_sample_map(self.h, None, 0, 0)
+        else:
+            a = np.ascontiguousarray(counts, np.uint8)
+            rc = self.L.rtggx_app_set_sample_map(self.h, a.ctypes.data_as(C.c_void_p), a.shape[1], a.shape[0])
+        if rc != 0:
+            raise capi.RtggxError(self.L.rtggx_app_last_error().decode())
 
     def set_scoring(self, enable):
         """RayTracer::SetScoring: every frame from the next one on is scored against the reference; refused without one."""

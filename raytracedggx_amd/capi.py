@@ -38,7 +38,8 @@ EXPORTS = ["rtggx_last_error", "rtggx_create", "rtggx_destroy", "rtggx_set_strip
            "rtggx_set_async_compute", "rtggx_set_history_apron", "rtggx_history_overreach", "rtggx_copy_bandwidth", "rtggx_refit_as", "rtggx_refit_as_device", "rtggx_refit_stats", "rtggx_set_refit_policy", "rtggx_set_sampler", "rtggx_set_ray_rate", "rtggx_set_max_recursion_depth", "rtggx_set_samples_per_pixel", "rtggx_debug_fuse_tone_map", "rtggx_debug_placement", "rtggx_debug_tile_words", "rtggx_debug_static_sky", "rtggx_debug_settled_sky", "rtggx_debug_settled_words", "rtggx_debug_sky_runs", "rtggx_debug_collapse_weights", "rtggx_debug_fence_wait", "rtggx_debug_shader_clock", "rtggx_debug_environment",
            "rtggx_set_accumulation", "rtggx_reset_accumulation", "rtggx_accumulated_frames", "rtggx_present_accumulation", "rtggx_set_sample_set",
            "rtggx_set_reference", "rtggx_reference_from_accumulation", "rtggx_set_scoring", "rtggx_read_scores",
-           "rtggx_set_env_image", "rtggx_generate_env_mips"]
+           "rtggx_set_env_image", "rtggx_generate_env_mips",
+           "rtggx_set_sample_map", "rtggx_read_sample_map"]
 SCORE_RING = 256
 
 
@@ -90,6 +91,8 @@ def load():
     L.rtggx_reference_from_accumulation.argtypes = [vp]
     L.rtggx_set_scoring.argtypes = [vp, C.c_int]
     L.rtggx_read_scores.argtypes = [vp, C.POINTER(Score), C.c_uint32, C.POINTER(C.c_uint32)]
+    L.rtggx_set_sample_map.argtypes = [vp, vp, C.c_uint32, C.c_uint32]
+    L.rtggx_read_sample_map.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.rtggx_set_history_apron.argtypes = [vp, C.c_uint32]
     L.rtggx_debug_shader_clock.argtypes = [vp, C.POINTER(C.c_double)]
     L.rtggx_refit_as.argtypes = [vp, C.c_uint32, vp, C.c_uint32]
@@ -360,6 +363,27 @@ class Context:
             if n.value < room:
                 break
         return out
+
+    def set_sample_map(self, counts):
+        """Adaptive sampling (include/rtggx.h): uint8[ceil(H / 8), ceil(W / 8)] counts -- 1, 2, 4 or 8 -- of the N samples each 8x8 block
+        traces, from the next frame on; None clears the map.  Whole frames only; synchronises."""
+        if counts is None:
+            self._check(self.L.rtggx_set_sample_map(self.h, None, 0, 0))
+            return
+        a = np.ascontiguousarray(counts, np.uint8)
+        if a.ndim != 2:
+            raise ValueError("a sample map is a 2-d array of blocks")
+        self._check(self.L.rtggx_set_sample_map(self.h, _p(a), a.shape[1], a.shape[0]))
+
+    def read_sample_map(self):
+        """The map most recently set, uint8[blocks_y, blocks_x], read back from the device; None when there is none."""
+        a = np.zeros(((self.H + 7) // 8, (self.W + 7) // 8), np.uint8)
+        bx, by = C.c_uint32(), C.c_uint32()
+        self._check(self.L.rtggx_read_sample_map(self.h, _p(a), a.size, C.byref(bx), C.byref(by)))
+        if bx.value == 0 and by.value == 0:
+            return None
+        assert (by.value, bx.value) == a.shape
+        return a
 
     def set_refit_policy(self, rebuild_ratio=1.2, steps_per_frame=16):
         self._check(self.L.rtggx_set_refit_policy(self.h, rebuild_ratio, steps_per_frame))

@@ -236,6 +236,7 @@ int rtggx_set_strip(rtggx_context* c, uint32_t rowBegin, uint32_t rowEnd) {
   RT_CHECK_CTX(c);
   if (rowBegin > rowEnd || rowEnd > c->H) { setError("rtggx_set_strip: bad rows [%u,%u) for height %u", rowBegin, rowEnd, c->H); return -1; }
   if (c->rayRate != 1u && (rowBegin > 0u || rowEnd < c->H)) { setError("rtggx_set_strip: rows [%u,%u) of %u: a context tracing one pixel in %u renders whole frames", rowBegin, rowEnd, c->H, c->rayRate); return -1; }
+  if ((c->sampleMap >= 0 || c->sampleMapRequested >= 0) && (rowBegin > 0u || rowEnd < c->H)) { setError("rtggx_set_strip: rows [%u,%u) of %u on a context with a sample map (rtggx_set_sample_map): a strip's tiles count from its first row, a block would no longer be a bin -- whole frames only", rowBegin, rowEnd, c->H); return -1; }
   c->rowBegin = rowBegin; c->rowEnd = rowEnd; c->toneMapDone = false;
   c->breakSkyRuns();
   return 0;
@@ -449,6 +450,64 @@ int rtggx_present_accumulation(rtggx_context* c) {
   return r;
 }
 
+// Adaptive sampling (raytrace.hip launchShadeSamples; DESIGN.md "Adaptive sampling").  The map lives on the device in
+// bin order, a byte per bin (rtggx_context::sampleMapBuf); the host keeps no copy.  Both entry points wait for every stream first: the
+// copy they then write is the one no frame reads -- not the one in force, which a frame whose visibility pass has run will still be
+// traced under --, and the next rtggx_render_visibility takes it over.  No end of the still-sky runs: a tile without a surface has no
+// covered pixel, and a mapped sample pass stores into its bins the count the run vouches for, 0 without a mark.
+namespace rt {
+static uint32_t mapBlocksX(const rtggx_context* c) { return (c->W + 7u) / 8u; }
+static uint32_t mapBlocksY(const rtggx_context* c) { return (c->H + 7u) / 8u; }
+static size_t mapWords(const rtggx_context* c) { return (size_t)((c->W + 15u) / 16u) * ((c->H + 15u) / 16u); }      // one word per tile: its four bins' counts
+static uint32_t mapBinOf(const rtggx_context* c, uint32_t bx, uint32_t by) { return ((by >> 1) * ((c->W + 15u) / 16u) + (bx >> 1)) * 4u + (by & 1u) * 2u + (bx & 1u); }
+// both copies or none; returns the index of the copy a set may write
+static int sampleMapTarget(rtggx_context* c, const char* who) {
+  if (!c->sampleMapBuf[0]) {
+    DevBuf<uint32_t> a, b;
+    hipError_t e = alloc(a, mapWords(c));
+    if (e == hipSuccess) e = alloc(b, mapWords(c));
+    if (e != hipSuccess) { setError("%s: %s (2 x %zu bytes for the map)", who, hipGetErrorString(e), mapWords(c) * 4u); return -2; }
+    c->sampleMapBuf[0] = std::move(a); c->sampleMapBuf[1] = std::move(b);
+  }
+  return c->sampleMap == 0 ? 1 : 0;
+}
+}  // namespace rt
+int rtggx_set_sample_map(rtggx_context* c, const uint8_t* counts, uint32_t blocksX, uint32_t blocksY) {
+  RT_CHECK_CTX(c);
+  if (!counts && blocksX == 0u && blocksY == 0u) { RT_HIP(syncStreams(c)); c->sampleMapRequested = -1; return 0; }
+  if (!counts) { setError("rtggx_set_sample_map: null counts"); return -1; }
+  if (blocksX != mapBlocksX(c) || blocksY != mapBlocksY(c)) { setError("rtggx_set_sample_map: a map of %u x %u blocks for a frame of %u x %u pixels, which has %u x %u blocks of 8 x 8", blocksX, blocksY, c->W, c->H, mapBlocksX(c), mapBlocksY(c)); return -1; }
+  if (c->rowBegin > 0u || c->rowEnd < c->H) { setError("rtggx_set_sample_map: on a strip (rows [%u,%u) of %u): a strip's tiles count from its first row, a block would no longer be a bin -- whole frames only", c->rowBegin, c->rowEnd, c->H); return -1; }
+  std::vector<uint32_t> words(mapWords(c), 0x01010101u);
+  uint8_t* const bins = reinterpret_cast<uint8_t*>(words.data());
+  for (uint32_t by = 0; by < blocksY; ++by)
+    for (uint32_t bx = 0; bx < blocksX; ++bx) {
+      const uint8_t n = counts[(size_t)by * blocksX + bx];
+      if (n != 1u && n != 2u && n != 4u && n != 8u) { setError("rtggx_set_sample_map: a count of %u at block (%u, %u): 1, 2, 4 or 8", (unsigned)n, bx, by); return -1; }
+      bins[mapBinOf(c, bx, by)] = n;
+    }
+  RT_HIP(syncStreams(c));
+  const int t = sampleMapTarget(c, "rtggx_set_sample_map");
+  if (t < 0) return t;
+  RT_HIP(hipMemcpy(c->sampleMapBuf[t], words.data(), words.size() * 4u, hipMemcpyHostToDevice));
+  c->sampleMapRequested = t;
+  return 0;
+}
+int rtggx_read_sample_map(rtggx_context* c, uint8_t* counts, uint32_t capacity, uint32_t* blocksX, uint32_t* blocksY) {
+  RT_CHECK_CTX(c);
+  if (!blocksX || !blocksY) { setError("rtggx_read_sample_map: null result"); return -1; }
+  RT_HIP(syncStreams(c));
+  if (c->sampleMapRequested < 0) { *blocksX = 0u; *blocksY = 0u; return 0; }
+  const uint32_t bX = mapBlocksX(c), bY = mapBlocksY(c);
+  *blocksX = bX; *blocksY = bY;
+  if (!counts || capacity < bX * bY) { setError("rtggx_read_sample_map: room for %u counts, the map has %u x %u", counts ? capacity : 0u, bX, bY); return -1; }
+  std::vector<uint32_t> words(mapWords(c));
+  RT_HIP(hipMemcpy(words.data(), c->sampleMapBuf[c->sampleMapRequested], words.size() * 4u, hipMemcpyDeviceToHost));
+  const uint8_t* const bins = reinterpret_cast<const uint8_t*>(words.data());
+  for (uint32_t by = 0; by < bY; ++by)
+    for (uint32_t bx = 0; bx < bX; ++bx) counts[(size_t)by * bX + bx] = bins[mapBinOf(c, bx, by)];
+  return 0;
+}
 // Scoring against a reference (score.hip; DESIGN.md "Scoring against a reference").  The reference is read by the scoring kernels on the
 // main stream alone.  rtggx_set_reference copies from the host: it waits for every stream first (frames in flight still read the image it
 // replaces or frees) and copies before it returns; rtggx_reference_from_accumulation writes it by a kernel on the main stream, behind the

@@ -196,6 +196,7 @@ int rtggx_render_visibility(rtggx_context* c) {
   ++c->frameCounter;
   c->maxDepth = c->depthRequested; c->samples = c->samplesRequested; c->accumulate = c->accumulateRequested;
   c->scoring = c->scoringRequested && c->reference != nullptr;
+  c->sampleMap = c->sampleMapRequested;      // rtggx_set_sample_map: the setter has waited for every stream and written the copy no frame reads
   bool resendConstants = false;
   if (c->sampleSet != c->sampleSetRequested) {      // rtggx_set_sample_set: the kernels' variant, the table and the constants' mask change together
     // several frames from one rtggx_update_frame share the slot's device copy: the frame before may still read the mask that goes with ITS

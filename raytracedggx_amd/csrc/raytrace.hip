@@ -24,6 +24,7 @@
 // once; shade 64+16 B in, 4 B out per ray.  The BVH (<= 14 MB) is L2/MALL resident, so traversal is
 // bound by L1 request rate, issue and latency, not by HBM (DESIGN.md "Roofline").
 #include <cstring>
+#include <type_traits>
 #include "rt_queue.h"
 #include "rt_traverse.h"
 
@@ -855,13 +856,28 @@ struct SampleGenArgs {
   RayRec* rays; HitKey* hits; uint32_t* binCount; uint32_t binSlots;
   const uint32_t* tileWords; uint32_t tilesX, rowBegin, rowEnd;
 };
-template <bool WIDE>
-__global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) sampleGenKernel(const FrameParams* __restrict__ fpp, SampleGenArgs A) {
+// MAPPED (rtggx_set_sample_map; DESIGN.md "Adaptive sampling"): the wave's block traces the samples k < its count.  The map holds a byte per
+// bin in bin order, so a tile's word holds its four waves' counts: one scalar load, like the tile word.  A wave whose block has had its
+// samples stores the count 0 for its bin and leaves: the bin still holds the previous sample's rays and count (or, at depth D > 1, its last
+// level's), and the traversal and the shading passes of this sample read that one array -- a bin that kept its count would be traced and
+// added again.  (k < N always, so k >= count is k >= min(count, N).)
+struct SampleGenArgsMapped : SampleGenArgs { const uint32_t* sampleMap; uint32_t sample; };
+template <bool WIDE, bool MAPPED = false>
+__global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) sampleGenKernel(const FrameParams* __restrict__ fpp, std::conditional_t<MAPPED, SampleGenArgsMapped, SampleGenArgs> A) {
   const FrameParams& fp = *fpp;
   const uint32_t tile = blockIdx.x;
   { uint32_t word;
     asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(word) : "s"(A.tileWords), "s"(tile * 4u) : "memory");
     if (word == 0u) return; }
+  if constexpr (MAPPED) {
+    uint32_t counts;
+    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(counts) : "s"(A.sampleMap), "s"(tile * 4u) : "memory");
+    const uint32_t w = RT_SGPR(threadIdx.x >> 6);
+    if (A.sample >= ((counts >> (8u * w)) & 0xFFu)) {
+      if ((threadIdx.x & 63u) == 0u) A.binCount[tile * 4u + w] = 0u;
+      return;
+    }
+  }
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
   const uint32_t px = (tile % A.tilesX) * 16 + (wave & 1u) * 8 + (lane & 7u);
   const uint32_t py = A.rowBegin + (tile / A.tilesX) * 16 + (wave >> 1) * 8 + (lane >> 3);
@@ -937,11 +953,15 @@ __global__ void __launch_bounds__(256, RT_GEN_MIN_BLOCKS) sampleGenKernel(const 
 // After the last sample: the word of every covered pixel from its sums, pack_r11g11b10(acc * (1 / N)) -- N is a power of two, the scaling
 // exact --, RayTracingOut1 where the pixel's metallic < 1 (diffMask, bit per instance; elsewhere it keeps what was carried over).  The sums
 // are left zero for the next frame.  Background pixels hold the environment from ray generation: no ray, no averaging.
+// MAPPED (rtggx_set_sample_map): the scale is 1 / c of the pixel's block, c = min(its count, N) -- 1, 2, 4 or 8, as exact.  The 16 x 16
+// lanes span two blocks per wave, so every lane loads the byte of its own bin.
 struct ResolveArgs {
   const unsigned long long* visDepth; float* accRefl; float* accDiff; uint32_t* reflOut; uint32_t* diffOut;
   const uint32_t* tileWords; uint32_t tilesX, rowBegin, rowEnd, diffMask; float scale;
 };
-__global__ void __launch_bounds__(256) resolveSamplesKernel(const FrameParams* __restrict__ fpp, ResolveArgs A) {
+struct ResolveArgsMapped : ResolveArgs { const uint8_t* sampleMap; uint32_t samples; };
+template <bool MAPPED = false>
+__global__ void __launch_bounds__(256) resolveSamplesKernel(const FrameParams* __restrict__ fpp, std::conditional_t<MAPPED, ResolveArgsMapped, ResolveArgs> A) {
   const FrameParams& fp = *fpp;
   const uint32_t tile = blockIdx.x;
   { uint32_t word;
@@ -952,12 +972,14 @@ __global__ void __launch_bounds__(256) resolveSamplesKernel(const FrameParams* _
   const size_t pix = (size_t)py * fp.W + px;
   const uint32_t vis = (uint32_t)A.visDepth[pix];
   if (vis == 0u) return;
+  float scale = A.scale;
+  if constexpr (MAPPED) scale = 1.0f / (float)min((uint32_t)A.sampleMap[tile * 4u + ((threadIdx.x >> 7) & 1u) * 2u + ((threadIdx.x >> 3) & 1u)], A.samples);
   float* r = A.accRefl + 3u * pix;
-  A.reflOut[pix] = packR11G11B10F(mk3(r[0] * A.scale, r[1] * A.scale, r[2] * A.scale));
+  A.reflOut[pix] = packR11G11B10F(mk3(r[0] * scale, r[1] * scale, r[2] * scale));
   r[0] = 0.0f; r[1] = 0.0f; r[2] = 0.0f;
   if ((A.diffMask >> ((vis - 1u) >> 24)) & 1u) {
     float* d = A.accDiff + 3u * pix;
-    A.diffOut[pix] = packR11G11B10F(mk3(d[0] * A.scale, d[1] * A.scale, d[2] * A.scale));
+    A.diffOut[pix] = packR11G11B10F(mk3(d[0] * scale, d[1] * scale, d[2] * scale));
     d[0] = 0.0f; d[1] = 0.0f; d[2] = 0.0f;
   }
 }
@@ -1108,10 +1130,19 @@ static int launchShadeSamples(rtggx_context* c, const FrameParams& fp, hipStream
   G.visDepth = S.visDepth; G.fat0 = S.fat0; G.fat1 = S.fat1; G.cosSin = S.cosSin;
   G.rays = S.spawnRays; G.hits = S.spawnHits; G.binCount = S.spawnCount; G.binSlots = S.binSlots;
   G.tileWords = S.tileWords; G.tilesX = S.tilesX; G.rowBegin = S.rowBegin; G.rowEnd = S.rowEnd;
+  // rtggx_set_sample_map: the frame's map (whole frames only: this pass's tiles are the frame's) selects the MAPPED variants of the sample
+  // generation and of the resolve; the launches stay the N-sample frame's, the traversals and shading passes simply find fewer rays
+  const uint32_t* const map = c->sampleMapWords();
+  if (map && (S.rowBegin != 0u || S.rowEnd != c->H)) { setError("rtggx_ray_trace: a sample map on rows [%u,%u) of %u", S.rowBegin, S.rowEnd, c->H); return -1; }
+  SampleGenArgsMapped GM;
+  static_cast<SampleGenArgs&>(GM) = G; GM.sampleMap = map; GM.sample = 0u;
   const TraceQueue q{S.rays, S.spawnHits, S.binCount};
   for (uint32_t k = 0; k < N; ++k) {
     for (uint32_t level = 0; level < depth; ++level) {
-      if (k > 0 && level == 0) launch(wide ? sampleGenKernel<true> : sampleGenKernel<false>, dim3(numTiles), dim3(256), s, nullptr, nullptr, sp + k, G);
+      if (k > 0 && level == 0) {
+        if (map) { GM.sample = k; launch(wide ? sampleGenKernel<true, true> : sampleGenKernel<false, true>, dim3(numTiles), dim3(256), s, nullptr, nullptr, sp + k, GM); }
+        else launch(wide ? sampleGenKernel<true> : sampleGenKernel<false>, dim3(numTiles), dim3(256), s, nullptr, nullptr, sp + k, G);
+      }
       if (k > 0 || level > 0) {
         const int r = launchTrace(c, fp, s, q, c->traceGrid[0], true, c->traceGrid[1], c->traceGrid[2], c->traceGrid[3], -1, nullptr, nullptr, spillPart);
         if (r) return r;
@@ -1126,7 +1157,11 @@ static int launchShadeSamples(rtggx_context* c, const FrameParams& fp, hipStream
   R.tileWords = S.tileWords; R.tilesX = S.tilesX; R.rowBegin = S.rowBegin; R.rowEnd = S.rowEnd;
   R.diffMask = (fp.mat.RoughMetals[0][1] < 1.0f ? 1u : 0u) | (fp.mat.RoughMetals[1][1] < 1.0f ? 2u : 0u);      // rghMtl.y < 1 (:559) is the instance's constant
   R.scale = 1.0f / (float)N;
-  launch(resolveSamplesKernel, dim3(numTiles), dim3(256), s, nullptr, done, c->dParams + c->slot, R);
+  if (map) {
+    ResolveArgsMapped RM;
+    static_cast<ResolveArgs&>(RM) = R; RM.sampleMap = reinterpret_cast<const uint8_t*>(map); RM.samples = N;
+    launch(resolveSamplesKernel<true>, dim3(numTiles), dim3(256), s, nullptr, done, c->dParams + c->slot, RM);
+  } else launch(resolveSamplesKernel<false>, dim3(numTiles), dim3(256), s, nullptr, done, c->dParams + c->slot, R);
   RT_HIP(hipGetLastError());
   return 0;
 }

@@ -291,6 +291,14 @@ struct rtggx_context {
   // the frames.  accumFrames: frames added since the last reset, counted by the host as it enqueues them.
   bool accumulate = false, accumulateRequested = false;
   uint32_t accumFrames = 0;
+  // rtggx_set_sample_map (raytrace.hip launchShadeSamples; DESIGN.md "Adaptive sampling"): one count per ray bin of the full frame, a byte
+  // each in bin order -- a tile's four counts are one word, read by a wave with one scalar load like the tile word; bins beyond the
+  // frame's blocks hold 1.  Two copies, allocated with the first set: a set writes the one
+  // no frame reads (it has waited for every stream; a frame whose visibility pass has run keeps the one it was launched under), and
+  // rtggx_render_visibility takes the requested one over.  -1: no map.
+  rt::DevBuf<uint32_t> sampleMapBuf[2];
+  int sampleMap = -1, sampleMapRequested = -1;
+  const uint32_t* sampleMapWords() const { return sampleMap < 0 ? nullptr : sampleMapBuf[sampleMap].get(); }
   rt::DevBuf<float4> accRefl, accDiff; rt::DevBuf<uint2> converged;      // converged: RTGGX_BUF_CONVERGED (rtggx_present_accumulation)
   // rtggx_set_reference / rtggx_set_scoring (score.hip; DESIGN.md "Scoring against a reference"): the frame's, the next frame's.  Nothing
   // below exists on a context that never calls them (context.hip allocReference, allocScoring).

@@ -110,6 +110,14 @@ bool RayTracer::SetSampleSetSize(uint32_t size) {
 bool RayTracer::SetAccumulation(bool enable) { return check(rtggx_set_accumulation(m_ctx, enable ? 1 : 0), "rtggx_set_accumulation"); }
 bool RayTracer::ResetAccumulation() { return check(rtggx_reset_accumulation(m_ctx), "rtggx_reset_accumulation"); }
 
+bool RayTracer::SetSampleMap(const uint8_t* counts, uint32_t blocksX, uint32_t blocksY) { return check(rtggx_set_sample_map(m_ctx, counts, blocksX, blocksY), "rtggx_set_sample_map"); }
+bool RayTracer::ReadSampleMap(std::vector<uint8_t>& counts, uint32_t& blocksX, uint32_t& blocksY) {
+  counts.assign((size_t)((m_width + 7u) / 8u) * ((m_height + 7u) / 8u), 0);
+  if (!check(rtggx_read_sample_map(m_ctx, counts.data(), (uint32_t)counts.size(), &blocksX, &blocksY), "rtggx_read_sample_map")) return false;
+  counts.resize((size_t)blocksX * blocksY);
+  return true;
+}
+
 bool RayTracer::SetReference(const void* rgba16f, size_t bytes) { return check(rtggx_set_reference(m_ctx, rgba16f, bytes), "rtggx_set_reference"); }
 bool RayTracer::SetScoring(bool enable) { return check(rtggx_set_scoring(m_ctx, enable ? 1 : 0), "rtggx_set_scoring"); }
 bool RayTracer::ReadScores(std::vector<RtggxScore>& out) {

@@ -57,6 +57,11 @@ class RayTracer {
   // not together with ray rate 4.  A moving camera or a changed material is the caller's to reset.
   bool SetAccumulation(bool enable);
   bool ResetAccumulation();
+  // rtggx_set_sample_map / rtggx_read_sample_map: how many of the N samples each 8 x 8 block of the full frame traces -- ceil(W / 8) x
+  // ceil(H / 8) counts of 1, 2, 4 or 8, row-major; nullptr, 0, 0 clears the map --, and the map most recently set read back (empty: none).
+  // Whole frames only; each call synchronises.
+  bool SetSampleMap(const uint8_t* counts, uint32_t blocksX, uint32_t blocksY);
+  bool ReadSampleMap(std::vector<uint8_t>& counts, uint32_t& blocksX, uint32_t& blocksY);
   // rtggx_set_reference / rtggx_set_scoring / rtggx_read_scores: the image every frame is scored against on the device (W * H RGBA16F
   // words; nullptr, 0 releases it), scoring on from the next frame (refused without a reference), and the records not yet read, oldest
   // first, appended to `out` -- it waits for the main stream alone (-reference, -score)

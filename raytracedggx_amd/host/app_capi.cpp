@@ -155,6 +155,14 @@ extern "C" int rtggx_host_accumulation_note(uint32_t frames, uint32_t samples, u
   return (int)s.size();
 }
 
+// RayTracer::SetSampleMap of the application's ray tracer (counts = NULL, 0, 0 clears)
+extern "C" int rtggx_app_set_sample_map(void* h, const uint8_t* counts, uint32_t blocksX, uint32_t blocksY) {
+  RayTracer* rt = ((RayTracedGGX*)h)->GetRayTracer();
+  if (rt->SetSampleMap(counts, blocksX, blocksY)) return 0;
+  g_appError = rt->GetLastError();
+  return -1;
+}
+
 // The multi-GPU host's plan functions (host/Strips.cpp), for the tests that compare them with raytracedggx_amd/strips.py.
 // bounds: nullptr / 0 for equal strips, else world + 1 row numbers.  ops: 5 int32 per transfer (send, buffer: 1 history / 0 back buffer / 2 token, rowBegin, rowEnd, peer);
 // returns the number of transfers, or -1 with rtggx_app_last_error set.
