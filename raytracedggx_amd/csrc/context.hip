@@ -52,7 +52,7 @@ int allocSet(rtggx_context* c, uint32_t i) {
   if (!s.binCount) RT_HIP(allocFilled(s.binCount, (size_t)c->numBinsMax));
   if (!s.splitList) RT_HIP(alloc(s.splitList, (size_t)RT_SPLIT_CAP));
   if (!s.skyRun) RT_HIP(allocFilled(s.skyRun, c->skyTiles));
-  c->breakSkyRuns();      // (a set with new buffers: nothing is in place in it)
+  c->sky.breakRuns(SkyBreak::SetBuffers);
   s.splitCount = c->largeCountBase + 2 + i;
   if (!s.evRead) RT_HIP(create(s.evRead, RT_EVENT_FLAGS));
   return 0;
@@ -238,7 +238,7 @@ int rtggx_set_strip(rtggx_context* c, uint32_t rowBegin, uint32_t rowEnd) {
   if (c->rayRate != 1u && (rowBegin > 0u || rowEnd < c->H)) { setError("rtggx_set_strip: rows [%u,%u) of %u: a context tracing one pixel in %u renders whole frames", rowBegin, rowEnd, c->H, c->rayRate); return -1; }
   if ((c->sampleMap >= 0 || c->sampleMapRequested >= 0) && (rowBegin > 0u || rowEnd < c->H)) { setError("rtggx_set_strip: rows [%u,%u) of %u on a context with a sample map (rtggx_set_sample_map): a strip's tiles count from its first row, a block would no longer be a bin -- whole frames only", rowBegin, rowEnd, c->H); return -1; }
   c->rowBegin = rowBegin; c->rowEnd = rowEnd; c->toneMapDone = false;
-  c->breakSkyRuns();
+  c->sky.breakRuns(SkyBreak::Strip);
   return 0;
 }
 
@@ -567,7 +567,7 @@ int rtggx_set_env(rtggx_context* c, int format, uint32_t size, uint32_t mips, co
   RT_CHECK_CTX(c);
   if (!data) { setError("rtggx_set_env: null data"); return -1; }
   RT_HIP(syncStreams(c));
-  c->breakSkyRuns();      // the sky behind every pixel is another one
+  c->sky.breakRuns(SkyBreak::Environment);
   return decodeEnv(c, format, size, mips, data, bytes, c->streamMain);
 }
 
@@ -597,7 +597,7 @@ int rtggx_set_env_image(rtggx_context* c, int layout, int pixels, uint32_t width
   if (bytes < need) { setError("rtggx_set_env_image: %zu bytes given, %zu needed", bytes, need); return -1; }
   RT_HIP(syncStreams(c));
   const int r = buildEnvFromImage(c, layout, pixels, width, height, data, size, c->streamMain);
-  if (r == 0) c->breakSkyRuns();      // the sky behind every pixel is another one (a failed build has left the old one)
+  if (r == 0) c->sky.breakRuns(SkyBreak::Environment);      // (a failed build has left the old one)
   return r;
 }
 
@@ -606,7 +606,7 @@ int rtggx_generate_env_mips(rtggx_context* c) {
   if (!c->env.texels) { setError("rtggx_generate_env_mips: no environment map"); return -1; }
   RT_HIP(syncStreams(c));
   const int r = generateEnvMips(c, c->streamMain);
-  if (r == 0) c->breakSkyRuns();      // every level below the first is another one
+  if (r == 0) c->sky.breakRuns(SkyBreak::Environment);
   return r;
 }
 

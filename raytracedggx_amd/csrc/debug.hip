@@ -55,35 +55,33 @@ int rtggx_debug_fuse_tone_map(rtggx_context* c, int mode) {
 int rtggx_debug_tile_words(rtggx_context* c, int enable) {
   RT_CHECK_CTX(c);
   c->useTileWords = enable != 0;
-  c->breakSkyRuns();
+  c->sky.breakRuns(SkyBreak::TileWordsSwitch);
   return 0;
 }
 // Still sky (rtggx_context.h InputSet::skyRun): enable = 0 -- the runs are still counted, but no tile is left alone for them.
 int rtggx_debug_static_sky(rtggx_context* c, int enable) {
   RT_CHECK_CTX(c);
-  c->staticSky = enable != 0;
-  c->breakSkyRuns();
+  c->sky.enableStaticSky(enable != 0);
   return 0;
 }
 // The current set's runs (0 where a word was written under another epoch than the current one), tile by tile of the most recent ray
 // generation's grid; *threshold: the run from which that ray generation left a tile alone.
 int rtggx_debug_sky_runs(rtggx_context* c, uint32_t* runs, uint32_t capacity, uint32_t* tilesX, uint32_t* tilesY, uint32_t* threshold) {
   RT_CHECK_CTX(c);
-  const uint32_t n = c->skyGen.tilesX * c->skyGen.tilesY;
+  const uint32_t n = c->sky.genTilesX() * c->sky.genTilesY();
   if (!runs || capacity < n || n > c->skyTiles) { setError("rtggx_debug_sky_runs: room for %u words", n); return -1; }
   RT_HIP(syncStreams(c));
   if (n) RT_HIP(hipMemcpy(runs, c->cur().skyRun, (size_t)n * 4, hipMemcpyDeviceToHost));
-  for (uint32_t i = 0; i < n; ++i) runs[i] = (runs[i] >> 8) == c->skyEpoch ? runs[i] & 0xFFu : 0u;
-  if (tilesX) *tilesX = c->skyGen.tilesX;
-  if (tilesY) *tilesY = c->skyGen.tilesY;
+  for (uint32_t i = 0; i < n; ++i) runs[i] = (runs[i] >> 8) == c->sky.epoch() ? runs[i] & 0xFFu : 0u;
+  if (tilesX) *tilesX = c->sky.genTilesX();
+  if (tilesY) *tilesY = c->sky.genTilesY();
   if (threshold) *threshold = RT_SKY_PREV_RUN + 1u;
   return 0;
 }
 // Settled sky (denoise.hip temporalKernel): enable = 0 -- no words are kept and no block of the temporal pass or the tone map is left alone.
 int rtggx_debug_settled_sky(rtggx_context* c, int enable) {
   RT_CHECK_CTX(c);
-  c->settledSky = enable != 0;
-  c->breakSkyRuns();
+  c->sky.enableSettledSky(enable != 0);
   return 0;
 }
 // Both word arrays as they are (epoch << 8 | flags) without their border, blocksX columns of blocksY words each; *epoch: the epoch words count under now.
@@ -97,7 +95,7 @@ int rtggx_debug_settled_words(rtggx_context* c, uint32_t* words0, uint32_t* word
     RT_HIP(hipMemcpy2D(out[p], (size_t)c->settledY * 4, c->settled[p] + c->settledPitch + 1u, (size_t)c->settledPitch * 4, (size_t)c->settledY * 4, c->settledX, hipMemcpyDeviceToHost));
   if (blocksX) *blocksX = c->settledX;
   if (blocksY) *blocksY = c->settledY;
-  if (epoch) *epoch = c->skyEpoch;
+  if (epoch) *epoch = c->sky.epoch();
   return 0;
 }
 int rtggx_debug_placement(rtggx_context* c, int forceSmall, uint32_t* key, uint32_t* where) {
@@ -275,7 +273,7 @@ int rtggx_upload(rtggx_context* c, int id, const void* src, size_t bytes) {
   RT_HIP(syncStreams(c));
   c->toneMapDone = false;      // (a tone map after an upload reads what was uploaded)
   c->curVis().flags.rasterFrame = 0u;      // ... and the tiles' words of this frame's visibility pass do not describe it (rtggx_context.h VisTarget::dirty)
-  c->breakSkyRuns();      // ... and what a still-sky tile relies on being in place may just have been replaced
+  c->sky.breakRuns(SkyBreak::Upload);      // ... and what a still-sky tile relies on being in place may just have been replaced
   if (id == RTGGX_BUF_VISIBILITY || id == RTGGX_BUF_DEPTH) {
     // replace one half of the packed buffer
     DevBuf<uint32_t> dVis, dDepth;
@@ -365,7 +363,7 @@ int rtggx_trace_rays(rtggx_context* c, const float* rays, uint32_t n, float* out
   RT_CHECK_CTX(c);
   if (!c->asBuilt || !c->haveConstants) { setError("rtggx_trace_rays: build_as / update_frame / update_as first"); return -1; }
   RT_HIP(syncStreams(c));   // the ray bins are shared with the frame path on stream B
-  c->breakSkyRuns();        // (... and a still-sky tile relies on its bins' counts being 0)
+  c->sky.breakRuns(SkyBreak::TraceRays);        // (... and a still-sky tile relies on its bins' counts being 0)
   { const int r = ensureParams(c); if (r) return r; }
   DevBuf<float> dR, dO;
   RT_HIP(alloc(dR, (size_t)n * 8)); RT_HIP(alloc(dO, (size_t)n * 6));

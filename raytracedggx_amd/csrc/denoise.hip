@@ -784,54 +784,8 @@ static Targets makeTargets(rtggx_context* c, const FrameParams& fp, RowPass pass
   return T;
 }
 
-// Still sky in the reflection V pass (spatialTiledKernel<1>): may this frame's pass leave blocks over still sky alone?  It may when what it
-// would store there is what the PREVIOUS reflection V pass stored, into the same image:
-//     this frame's ray generation has run, under the epoch that is still current (nothing has broken the runs since: an upload, another
-//       environment, ...), over the rows the run words are indexed by -- the words in this set are this frame's;
-//     the previous reflection V pass was this frame's or the frame before's (a frame without rtggx_denoise leaves FilteredOut1 a frame old),
-//       had ray generation's results of its own frame under the same epoch, covered the same rows and wrote the same images
-//       (FilteredOut as well, or FilteredOut1 alone: fltRflIsFltDff).
-// Records this pass as the previous one of the next.
-static bool skyVPassMaySkip(rtggx_context* c, const Targets& TV, uint32_t gbufferRow0, uint32_t* epoch) {
-  rtggx_context::SkyV now;
-  const bool genValid = c->skyGen.any && c->skyGen.frame == c->frameCounter && c->skyGen.epoch == c->skyEpoch && c->skyGen.rows[0] == gbufferRow0;
-  now.any = true; now.fltRflNull = TV.fltRfl == nullptr; now.frame = c->frameCounter; now.genEpoch = genValid ? c->skyGen.epoch : 0xFFFFFFFFu;
-  now.rows[0] = (uint32_t)TV.rowBegin; now.rows[1] = (uint32_t)TV.rowEnd;
-  const rtggx_context::SkyV& was = c->skyV;
-  const bool may = c->staticSky && genValid && was.any && (was.frame == now.frame || was.frame + 1u == now.frame) && was.genEpoch == now.genEpoch
-                   && was.rows[0] == now.rows[0] && was.rows[1] == now.rows[1] && was.fltRflNull == now.fltRflNull;
-  c->skyV = now;
-  *epoch = c->skyEpoch;
-  return may;
-}
-
-// Settled sky in the temporal pass (temporalKernel): does this frame's pass keep words, and may it leave blocks alone for the words of the
-// pass before it?  It keeps them on whole frames (no strip: no histReach, no peers, no apron rows) of the two-kernel path, when the pass
-// before it ran under the same epoch.  Under a NEW epoch it stores none and needs none: every word in either array carries an older epoch
-// and reads as unsettled (a camera that moves every frame pays nothing).  The first pass after anything else that breaks the chain
-// -- a fused pass, a frame without the denoiser -- stores `epoch | 0` everywhere, over words that may describe images written since.
-// It may leave blocks alone when, besides,
-//     this frame's ray generation has run under the epoch that is still current, over the rows the run words are indexed by (genValid, as
-//       the reflection V pass requires it);
-//     the temporal pass before this one was the previous frame's, kept words, over the same rows, and wrote the other history image and
-//       word array (frameParity flips even for an empty strip's rtggx_denoise).
-// Records this pass as the previous one of the next, whatever it does.
-static bool skyTemporalMaySkip(rtggx_context* c, const Targets& TT, const FrameParams& fp, bool fused, bool* words) {
-  rtggx_context::SkyT now;
-  const rtggx_context::SkyT& was = c->skyT;
-  const bool whole = fp.rowBegin == 0u && fp.rowEnd == fp.H && fp.W == c->W && fp.H == c->H;
-  const bool genValid = c->skyGen.any && c->skyGen.frame == c->frameCounter && c->skyGen.epoch == c->skyEpoch && c->skyGen.rows[0] == (uint32_t)TT.tileRow0;
-  now.any = true; now.frame = c->frameCounter; now.epoch = c->skyEpoch; now.parity = c->frameParity;
-  now.words = c->staticSky && c->settledSky && !fused && whole && fp.W >= 96u      // (six tiles across: temporalKernel's loads)
-              && was.any && was.epoch == now.epoch;
-  now.rows[0] = (uint32_t)TT.rowBegin; now.rows[1] = (uint32_t)TT.rowEnd;
-  const bool may = now.words && genValid && was.words && was.frame + 1u == now.frame && was.parity == (now.parity ^ 1u)
-                   && was.rows[0] == now.rows[0] && was.rows[1] == now.rows[1];
-  c->skyT = now;
-  ++c->tssWrites[now.parity];
-  *words = now.words;
-  return may;
-}
+// "Whole frame" for the settled words: no strip (no histReach, no peers, no apron rows) of the size the context was created with
+static bool wholeFrame(const rtggx_context* c, const FrameParams& fp) { return fp.rowBegin == 0u && fp.rowEnd == fp.H && fp.W == c->W && fp.H == c->H; }
 
 int launchDenoise(rtggx_context* c, const FrameParams& fp, int useLds, hipStream_t s, hipEvent_t done, bool fuseToneMap) {
   c->frameParity ^= 1u;   // Denoiser.cpp:69
@@ -848,8 +802,9 @@ int launchDenoise(rtggx_context* c, const FrameParams& fp, int useLds, hipStream
   // images would be identical, 8 bytes per pixel each); rtggx_readback(RTGGX_BUF_FLT_RFL) then returns FilteredOut1 (debug.hip).
   c->fltRflIsFltDff = !anyDiffuse;
   Targets TVr = TV; if (!anyDiffuse) TVr.fltRfl = nullptr;
-  { uint32_t epoch;      // (the direct-access variant converts every sky texel; it counts as the previous pass all the same)
-    if (skyVPassMaySkip(c, TVr, (uint32_t)TV.tileRow0, &epoch) && useLds) { TVr.skyRun = c->cur().skyRun; TVr.skyEpoch = epoch; } }
+  { SkyChain::VFacts now;      // still sky (rt_sky_chain.h reflectionV): the decision selects skyRun and skyEpoch of the tiled variant
+    now.frame = c->frameCounter; now.gbufferRow0 = (uint32_t)TV.tileRow0; now.rows[0] = (uint32_t)TV.rowBegin; now.rows[1] = (uint32_t)TV.rowEnd; now.fltRflNull = TVr.fltRfl == nullptr;
+    if (c->sky.reflectionV(now) && useLds) { TVr.skyRun = c->cur().skyRun; TVr.skyEpoch = c->sky.epoch(); } }
   if (useLds) {
     hipLaunchKernelGGL(spatialTiledKernel<0>, grid(TH, 64, 4), block, 0, s, TH); mark(4);
     hipLaunchKernelGGL(spatialTiledKernel<1>, grid(TV, RT_VBW, RT_VBH), block, 0, s, TVr); mark(5);
@@ -867,14 +822,16 @@ int launchDenoise(rtggx_context* c, const FrameParams& fp, int useLds, hipStream
     hipLaunchKernelGGL(spatialDirectKernel<3>, grid(TV, 64, 4), block, 0, s, TV); mark(7);
   }
   Targets TTs = TT;
-  { bool words;
-    const bool may = skyTemporalMaySkip(c, TT, fp, fuseToneMap, &words);
-    if (words) { TTs.settledOut = c->settled[c->frameParity]; TTs.skyEpoch = c->skyEpoch; }
-    if (may) { TTs.settledIn = c->settled[c->frameParity ^ 1u]; TTs.skyRun = c->cur().skyRun; } }
+  { SkyChain::TemporalFacts now;      // settled sky (rt_sky_chain.h temporal): the decision selects settledOut and skyEpoch, settledIn and skyRun, and the kernel's variant
+    now.frame = c->frameCounter; now.gbufferRow0 = (uint32_t)TT.tileRow0; now.rows[0] = (uint32_t)TT.rowBegin; now.rows[1] = (uint32_t)TT.rowEnd;
+    now.parity = c->frameParity; now.width = fp.W; now.fused = fuseToneMap; now.whole = wholeFrame(c, fp);
+    const SkyChain::TemporalDecision d = c->sky.temporal(now);
+    if (d.keepsWords) { TTs.settledOut = c->settled[c->frameParity]; TTs.skyEpoch = c->sky.epoch(); }
+    if (d.maySkip) { TTs.settledIn = c->settled[c->frameParity ^ 1u]; TTs.skyRun = c->cur().skyRun; } }
   if (fuseToneMap) {      // the temporal pass and the tone map of its result in one kernel: workgroups of 62 x 14 back-buffer pixels over the strip's own rows
     const dim3 g((fp.W + RT_TT_W - 1) / RT_TT_W, (uint32_t)(TT.outEnd - TT.outBegin + RT_TT_H - 1) / RT_TT_H), b(RT_TT_TW * RT_TT_TH);
     launch(temporalToneKernel, g, b, s, nullptr, done, TT);
-    c->skyTM.any = false;      // (the back buffer has another writer than the tone map the record describes)
+    c->sky.backBufferWrittenElsewhere();
   } else launch(TTs.settledOut ? temporalKernel<true> : temporalKernel<false>, grid(TT, 64, RT_TP_ROWS), block, s, nullptr, done, TTs);
   mark(8);
   RT_HIP(hipGetLastError());
@@ -888,21 +845,9 @@ int launchToneMap(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEve
   if (fp.rowEnd <= fp.rowBegin) return 0;
   Targets T = makeTargets(c, fp, ROWS_FINAL);
   if (source) T.scratch = const_cast<uint2*>(source);
-  // Settled sky (toneMapKernel): the tone map may leave blocks alone for this frame's words when
-  //     this frame's temporal pass kept words, for the image this tone map reads (TSS[parity], not `source`), under the epoch that is still current;
-  //     the tone map before this one was the previous frame's, under the same epoch, over the same rows, and read the OTHER history image
-  //       as it still is (no temporal pass has written it since): the image this frame's words compare with.
-  // Records this tone map as the previous one of the next.
-  { rtggx_context::SkyTM now;
-    now.any = true; now.fromTss = source == nullptr; now.frame = c->frameCounter; now.epoch = c->skyEpoch; now.parity = c->frameParity; now.writes = c->tssWrites[c->frameParity];
-    now.rows[0] = (uint32_t)T.rowBegin; now.rows[1] = (uint32_t)T.rowEnd;
-    const rtggx_context::SkyTM& was = c->skyTM; const rtggx_context::SkyT& t = c->skyT;
-    const bool whole = fp.rowBegin == 0u && fp.rowEnd == fp.H && fp.W == c->W && fp.H == c->H;
-    const bool may = c->staticSky && c->settledSky && whole && now.fromTss && t.any && t.words && t.frame == now.frame && t.parity == now.parity && t.epoch == now.epoch
-                     && was.any && was.fromTss && was.frame + 1u == now.frame && was.epoch == now.epoch && was.rows[0] == now.rows[0] && was.rows[1] == now.rows[1]
-                     && was.parity == (now.parity ^ 1u) && was.writes == c->tssWrites[now.parity ^ 1u];
-    c->skyTM = now;
-    if (may) { T.settledIn = c->settled[c->frameParity]; T.skyEpoch = c->skyEpoch; } }
+  { SkyChain::ToneMapFacts now;      // settled sky (rt_sky_chain.h toneMap): the decision selects settledIn and skyEpoch, and the kernel's variant
+    now.frame = c->frameCounter; now.rows[0] = (uint32_t)T.rowBegin; now.rows[1] = (uint32_t)T.rowEnd; now.parity = c->frameParity; now.fromTss = source == nullptr; now.whole = wholeFrame(c, fp);
+    if (c->sky.toneMap(now)) { T.settledIn = c->settled[c->frameParity]; T.skyEpoch = c->sky.epoch(); } }
   const dim3 grid((fp.W + 63) / 64, (uint32_t)(T.rowEnd - T.rowBegin + RT_TM_ROWS - 1) / RT_TM_ROWS), block(256);
   launch(T.settledIn ? toneMapKernel<true> : toneMapKernel<false>, grid, block, s, nullptr, done, T);
   RT_HIP(hipGetLastError());

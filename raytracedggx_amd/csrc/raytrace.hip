@@ -987,36 +987,14 @@ __global__ void __launch_bounds__(256) resolveSamplesKernel(const FrameParams* _
 // =========================================================================================================
 // host side
 // =========================================================================================================
-// Still sky: the epoch this frame's ray generation counts its tiles' runs under (rtggx_context.h InputSet::skyRun, RT_SKY_PREV_RUN).  A run
-// says "the tile had no surface in so many consecutive ray generations, and nothing its outputs depend on changed meanwhile": the epoch is
-// bumped -- every run starts again from 0, every tile is written in full for RT_SKY_PREV_RUN frames -- when this ray generation differs
-// from the one before it in anything that enters a sky pixel's outputs or the bookkeeping the skipped epilogue keeps:
-//     the camera        rg.ProjToWorld, rg.EyePt, compared bit for bit (the sample rebuilds them from the same matrices every frame and
-//                       changes them when the user drags the mouse; the jitter, the frame index and the model's turn do not enter)
-//     the frame before  was not a ray generation's: a set in the ring went by without one (rtggx_render_visibility alone), so "the
-//                       previous set" is not the previous ray generation's
-//     the rows          another strip: tiles count from the pass's first row
-//     the bins          ray rate, adaptive split on / off, slice shift: which bins a tile has, and whether the cost records are kept
-//     the stream        the previous set's words are ordered before this kernel by stream order only
-// and by breakSkyRuns() where an entry point changes the rest: rtggx_set_env, rtggx_upload, rtggx_set_strip, rtggx_trace_rays (it refills a
-// set's bins), growBins, rtggx_debug_tile_words, rtggx_debug_static_sky.  Tile words that fall back to "all ones" (a foreign or uploaded
-// visibility buffer, a traversal-bound frame) need nothing: every tile reads as drawn, which ends its run.
-// -DRT_SKY_NO_CAMERA_CHECK leaves the camera out: tests/test_gpu_static_sky.py must fail with it (and does).
-static uint32_t skyEpochForGen(rtggx_context* c, const FrameParams& fp, uint32_t rb, uint32_t re, hipStream_t sGen, bool adaptive, uint32_t sliceShift) {
-  rtggx_context::SkyGen now;
-  now.any = true; now.adaptive = adaptive; now.frame = c->frameCounter; now.rows[0] = rb; now.rows[1] = re; now.rate = c->rayRate; now.sliceShift = sliceShift; now.stream = sGen;
-  now.tilesX = (fp.W + 15u) / 16u; now.tilesY = (re - rb + 15u) / 16u;
-  memcpy(now.camera, fp.rg.ProjToWorld, 64); memcpy(now.camera + 16, fp.rg.EyePt, 16);
-  const rtggx_context::SkyGen& was = c->skyGen;
-  bool same = was.any && (was.frame == now.frame || was.frame + 1u == now.frame) && was.rows[0] == rb && was.rows[1] == re && was.rate == now.rate
-              && was.adaptive == adaptive && was.sliceShift == sliceShift && was.stream == sGen;
-#ifndef RT_SKY_NO_CAMERA_CHECK
-  same = same && memcmp(was.camera, now.camera, sizeof now.camera) == 0;
-#endif
-  if (!same) c->breakSkyRuns();
-  now.epoch = c->skyEpoch;
-  c->skyGen = now;
-  return now.epoch;
+// Still sky, once in 2^24 bumps of the epoch (rt_sky_chain.h takeWrapped): no word of an earlier time round may meet its epoch again.
+// Every run word and every settled word is cleared, with the device idle before and after.
+static int clearSkyWordsAfterWrap(rtggx_context* c) {
+  RT_HIP(hipDeviceSynchronize());
+  for (auto& st : c->sets) RT_HIP(hipMemset(st.skyRun, 0, c->skyTiles * 4));
+  { const int r = resetSettled(c); if (r) return r; }
+  RT_HIP(hipStreamSynchronize(nullptr));
+  return 0;
 }
 
 int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hipStream_t s, hipEvent_t done) {
@@ -1065,16 +1043,15 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
   G.binWork = adaptive ? c->binWork : nullptr; G.splitList = set.splitList; G.splitCount = set.splitCount;
   G.frontWork = RT_SPLIT_FRONT < splitWork ? RT_SPLIT_FRONT : splitWork;
   G.splitWork = splitWork; G.splitMaxShift = splitMaxShift < 3u ? splitMaxShift : 3u; G.splitCap = splitCap < RT_SPLIT_CAP ? splitCap : RT_SPLIT_CAP;
-  // still sky: the runs are kept either way; with rtggx_debug_static_sky(ctx, 0) no run is ever long enough
-  G.skyEpoch = skyEpochForGen(c, fp, rb, re, sGen, adaptive, sliceShift);
-  if (c->skyEpochWrapped) {      // once in 2^24 bumps: no word of an earlier time round may meet its epoch again
-    RT_HIP(hipDeviceSynchronize());
-    for (auto& st : c->sets) RT_HIP(hipMemset(st.skyRun, 0, c->skyTiles * 4));
-    { const int r = resetSettled(c); if (r) return r; }
-    RT_HIP(hipStreamSynchronize(nullptr));
-    c->skyEpochWrapped = false;
-  }
-  G.skyPrev = c->prev().skyRun; G.skyOut = set.skyRun; G.skyPrevRun = c->staticSky ? RT_SKY_PREV_RUN : RT_SKY_RUN_CAP + 1u;
+  // still sky (rt_sky_chain.h rayGeneration; what else ends the runs: SkyBreak): the decision selects skyEpoch and skyPrevRun.  The runs are
+  // kept either way; with rtggx_debug_static_sky(ctx, 0) no run is ever long enough
+  { SkyChain::GenFacts now;
+    now.frame = c->frameCounter; now.rows[0] = rb; now.rows[1] = re; now.rate = c->rayRate; now.sliceShift = sliceShift; now.tilesX = tilesX; now.tilesY = tilesY;
+    now.adaptive = adaptive; now.stream = sGen;
+    memcpy(now.camera, fp.rg.ProjToWorld, 64); memcpy(now.camera + 16, fp.rg.EyePt, 16);
+    G.skyEpoch = c->sky.rayGeneration(now); }
+  if (c->sky.takeWrapped()) { const int r = clearSkyWordsAfterWrap(c); if (r) return r; }
+  G.skyPrev = c->prev().skyRun; G.skyOut = set.skyRun; G.skyPrevRun = c->sky.prevRunThreshold(RT_SKY_PREV_RUN, RT_SKY_RUN_CAP);
   // ray generation on stream C, the traversal on stream B behind it: the event rides on ray generation
   FrameEvents& ev = c->frameEvents(c->frameCounter);
   // N > 1 samples per pixel: the samples' copies of the frame constants (sampleParamsKernel), and ray generation traces sample 0

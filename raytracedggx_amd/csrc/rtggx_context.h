@@ -22,6 +22,7 @@
 #include <memory>
 #include "rtggx_device.h"
 #include "rt_owned_hip.h"
+#include "rt_sky_chain.h"
 
 // Input sets (G-buffer, traced images, ray bins): RT_SETS of them, used round-robin.  Stream B fills set i while the main stream
 // still consumes the set of the frame before; before stream B is given the work that overwrites a set, the HOST waits
@@ -58,7 +59,7 @@
 // compare bit by bit (the settled words).  The run only has to say what this frame's INPUTS are over the window:
 //   * a run of 1 under the current epoch: this frame's ray generation found the tile without a surface at rate 1.  It then stored velocity 0
 //     and the environment texel behind the pixel into this set, or validly left them in place (RT_SKY_PREV_RUN); both are functions of the
-//     pixel and the epoch alone (raytrace.hip skyEpochForGen: the camera and the environment are in the epoch, jitter and frame index do
+//     pixel and the epoch alone (rt_sky_chain.h rayGeneration: the camera and the environment are in the epoch, jitter and frame index do
 //     not enter a sky pixel);
 //   * the reflection V pass of this frame stored that texel's conversion, alpha 0, into FilteredOut1 -- every pixel without a surface takes
 //     storeSkipped, in a tile without a surface or beside one -- or validly left it in place (RT_SKY_V_RUN).
@@ -193,8 +194,8 @@ struct InputSet {
   // its set's list, may run beside this frame's traversal.  The count is a word of largeCountBase (zeroed by the previous frame's ray generation).
   DevBuf<uint32_t> splitList; uint32_t* splitCount = nullptr;      // (splitCount: a view)
   // "Still sky" (raytrace.hip rayGenKernel): one word per 16x16 tile of ray generation's grid, epoch << 8 | run.  run: the consecutive frames,
-  // this set's included and saturating at RT_SKY_RUN_CAP, in which ray generation found the tile's word 0 under one epoch (rtggx_context
-  // skyEpoch).  Written by the set's ray generation, read by the next frame's (earlier on the same stream, like roughMetalPrev) and by the
+  // this set's included and saturating at RT_SKY_RUN_CAP, in which ray generation found the tile's word 0 under one epoch (rt_sky_chain.h
+  // SkyChain).  Written by the set's ray generation, read by the next frame's (earlier on the same stream, like roughMetalPrev) and by the
   // set's own reflection V pass behind the traversal's event; protected by evRead like the set's other members.
   DevBuf<uint32_t> skyRun;
   Event evRead;                     // the set's last reader done: the HOST waits for it before stream B is given work that overwrites the set
@@ -366,28 +367,18 @@ struct rtggx_context {
     const rt::VisTarget& v = curVis();
     return useTileWords && !traversalBound && v.flags.rasterFrame == frameCounter && v.flags.rows[0] == rb && v.flags.rows[1] == re ? v.dirty.get() : visDirtyOnes.get();
   }
-  // Still sky (InputSet::skyRun; raytrace.hip skyEpochForGen is where the epoch is decided).  skyEpoch: 24 bits, bumped
-  // whenever something a sky tile's outputs depend on changes or the chain of consecutive ray generations breaks -- by skyEpochForGen from
-  // what it can compare frame to frame, by breakSkyRuns() from the entry points that change the rest.  skyGen: the facts of the most recent
-  // ray generation; skyV: of the most recent reflection V pass (denoise.hip launchDenoise decides from them whether this frame's may skip).
-  bool staticSky = true;         // rtggx_debug_static_sky
-  uint32_t skyEpoch = 1u; bool skyEpochWrapped = false; size_t skyTiles = 0;      // (skyTiles: words of a set's skyRun, as many as a VisTarget's)
-  void breakSkyRuns() { skyEpoch = (skyEpoch + 1u) & 0xFFFFFFu; if (skyEpoch == 0u) skyEpochWrapped = true; }
-  struct SkyGen { bool any = false, adaptive = false; uint32_t frame = 0, epoch = 0, rows[2] = {0, 0}, rate = 0, sliceShift = 0, tilesX = 0, tilesY = 0; hipStream_t stream = nullptr; float camera[20] = {}; } skyGen;
-  struct SkyV { bool any = false, fltRflNull = false; uint32_t frame = 0, genEpoch = 0, rows[2] = {0, 0}; } skyV;
+  // Still sky and settled sky (InputSet::skyRun; `settled` below): the epoch, the facts of the most recent ray
+  // generation, reflection V pass, temporal pass and tone map, and every decision taken from them (rt_sky_chain.h).
+  rt::SkyChain sky;
+  size_t skyTiles = 0;           // words of a set's skyRun, as many as a VisTarget's
   // Settled sky (denoise.hip temporalKernel, toneMapKernel): one word per 64 x 4 block of the temporal pass, twice by
   // history parity -- array p is written by the temporal pass that writes TSS[p].  Column-major with a border: block (bx, by) of settledX x
   // settledY at (bx + 1) * settledPitch + by + 1, so that the three words of a block's column of neighbours and the six under a tone-map
   // block are consecutive and no reader clamps.  The border (a column either side, a word above, the rest of the pitch below) holds
   // RT_SETTLED_BORDER, which no kernel writes and every reader takes as settled: clamped addressing never reads outside the frame.  Words
-  // count under skyEpoch like the run words.  skyT / skyTM: the facts of the most recent temporal pass and tone map, from which
-  // launchDenoise / launchToneMap decide whether this frame's may leave blocks alone.
-  bool settledSky = true;        // rtggx_debug_settled_sky
+  // count under the epoch of the run words (sky.epoch()).
   rt::DevBuf<uint32_t> settled[2]; uint32_t settledX = 0, settledY = 0, settledPitch = 0;
   size_t settledWords() const { return (size_t)(settledX + 2u) * settledPitch + 8u; }      // (+ 8: a reader's four-word load of three words may end beyond the last column)
-  struct SkyT { bool any = false, words = false; uint32_t frame = 0, epoch = 0, parity = 0, rows[2] = {0, 0}; } skyT;
-  struct SkyTM { bool any = false, fromTss = false; uint32_t frame = 0, epoch = 0, parity = 0, writes = 0, rows[2] = {0, 0}; } skyTM;
-  uint32_t tssWrites[2] = {0, 0};      // temporal passes that have written TSS[p] (skyTM.writes: as many as when that tone map read its image)
   bool useTileWords = true;      // rtggx_debug_tile_words
   // Where the TRAVERSAL is the frame's period (two rays per pixel into a large mesh: it runs 96 % of the time) nobody asks the words:
   // workgroups over empty tiles that leave at once make the other stages' kernels run denser beside the traversal and stretch it -- dragon,

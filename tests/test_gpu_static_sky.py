@@ -25,7 +25,7 @@ def test_static_sky_changes_no_buffer_through_every_event_that_ends_a_run(built)
     rays appearing and going (the bins grow, FilteredOut appears and goes), a strip whose rows are no multiple of 16, a frame with a
     visibility pass only, a frame without the denoiser, an uploaded G-buffer target, the tile words off and on, ray rate 4 and back, another
     environment.  Every target of both contexts is compared after every frame.
-    The test can fail: built with -DRT_SKY_NO_CAMERA_CHECK (raytrace.hip skyEpochForGen: the camera left out of the epoch; `EXTRA=-DRT_SKY_NO_CAMERA_CHECK`
+    The test can fail: built with -DRT_SKY_NO_CAMERA_CHECK (rt_sky_chain.h rayGeneration: the camera left out of the epoch; `EXTRA=-DRT_SKY_NO_CAMERA_CHECK`
     in the environment of the build) it fails at the first frame of the drag -- `drag 1 (frame 12): buffer 5`, 35 515 of 57 600 texels of
     RayTracingOut0: the sky of the tiles left alone still shows the old view.  Run once that way on an MI355X."""
     from raytracedggx_amd import app, capi
