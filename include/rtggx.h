@@ -213,6 +213,37 @@ enum { RTGGX_PIXELS_RGBE8 = 0, RTGGX_PIXELS_RGB32F = 1 };
 int  rtggx_set_env_image(rtggx_context* ctx, int layout, int pixels, uint32_t width, uint32_t height, const void* data, size_t bytes,
                          uint32_t cube_size);
 int  rtggx_generate_env_mips(rtggx_context* ctx);
+/* GGX-prefiltered environments (opt-in, no counterpart in the reference, whose cubes were filtered offline; DESIGN.md "Prefiltered
+ * environments"): the levels below level 0 rebuilt so that level m holds the radiance convolved with the GGX lobe of the roughness that
+ * selects m -- what the split-sum shading at the end of a path (reflectionDepth1: environment(dir, level) x EnvBRDFApprox) assumes, and a
+ * box chain is not.  A context that never calls it allocates and launches exactly what it always did.  samples: N, a power of two from
+ * RTGGX_ENV_FILTER_MIN_SAMPLES to RTGGX_ENV_FILTER_MAX_SAMPLES, or 0 = 1024.  With S the cube's side and M = floor(log2 S) + 1:
+ *   - source: the cube C that rtggx_generate_env_mips would leave now -- the current level 0 and below it the full box chain, RGBA16F.  The
+ *     result depends on the current level 0 and on N alone: calling twice gives the same cube bit for bit; level 0 of the result is C's;
+ *   - roughness of level m = 1 .. M - 1, in double: r = min(1.0, exp2((m - (M - 4)) / 1.15)) (the inverse of calcCubemapMipFromRoughness
+ *     with M levels), a = r r, a2 = a a;
+ *   - sample table of level m, built on the host, every expression a double operation in the order written with libm sqrt, cos, sin, log2,
+ *     exp2 and pi = 3.14159265358979323846.  For i = 0 .. N - 1:
+ *         u = bitreverse32(i) / 4294967296.0;  c2 = (1 - u) / (1 + (a2 - 1) u);  z = 2 c2 - 1     -- N.L with N = V = R;
+ *     the entry is dropped unless z > 0; for the others
+ *         ct = sqrt(c2);  st = sqrt(1 - c2);  phi = 2.0 pi (double)i / (double)N;  x = 2 ct st cos(phi);  y = 2 ct st sin(phi);
+ *         d = (a2 - 1) c2 + 1;  pdf = a2 / (pi d d) / 4;  lod = 0.5 log2((6.0 S S) / (4 pi N pdf)) + 1.0;  lod = min(max(lod, 0), M - 1).
+ *     The K kept entries stay in order of i, each ((float)x, (float)y, (float)z, (float)lod); invW = (float)(1.0 / sum of (double)(float)z),
+ *     in that order.  Entry i = 0 is always kept (z = 1); at r = 1 -- every level m >= M - 4 -- exactly the even i are, K = N / 2;
+ *   - texel (face f, x, y) of level m, side s = max(S >> m, 1), everything fp32 without contraction, each operation rounded on its own:
+ *         u = ((float)x + 0.5f) / (float)s * 2.0f - 1.0f, v likewise;  R = normalize(cubeFaceDir(f, u, v));
+ *         term_k = environment(C, localToWorld(R, (x_k, y_k, z_k)), lod_k) * z_k per component
+ *     -- the sampler and the tangent frame of the frame's kernels (rtggx_debug_environment; RayTracing.hlsl:129-147, 167-180);
+ *   - THE ORDER OF THE SUM IS FIXED: 64 partials p_j = ((+0 + term_j) + term_{j+64}) + ... over k = j (mod 64) ascending (+0 where there is
+ *     none), added pairwise, adjacent pairs first: q[i] = p[2 i] + p[2 i + 1], level by level, six levels, to t.  The texel is
+ *     pack_rgba16f(min(t.r invW, 65504), min(t.g invW, 65504), min(t.b invW, 65504), 1).  No atomics, no order that depends on
+ *     scheduling: tests/envfilter_ref.cpp restates RTGGX_BUF_ENV bit for bit.  A cube with negative or non-finite texels: not specified.
+ * Refused, the context keeping its environment, still-sky runs and frame: no environment set; samples neither 0 nor a power of two in
+ * range.  Otherwise like rtggx_generate_env_mips: synchronises, builds the new cube beside the old one and installs it when everything
+ * has succeeded, ends the still-sky runs, invalidates the SH coefficients, frees its scratch on return. */
+#define RTGGX_ENV_FILTER_MIN_SAMPLES 64u
+#define RTGGX_ENV_FILTER_MAX_SAMPLES 4096u
+int  rtggx_prefilter_env(rtggx_context* ctx, uint32_t samples);   /* 0 = 1024 */
 int  rtggx_set_material(rtggx_context* ctx, uint32_t mesh, const float base_color[4], float roughness, float metallic);
 int  rtggx_set_metallic(rtggx_context* ctx, uint32_t mesh, float metallic);
 /* Sampler of the reflection lobe.  0 (default): the reference's -- the GGX normal distribution itself, computeLocalDirectionGGX /

@@ -21,6 +21,7 @@ MAX_PEERS, IPC_HANDLE_BYTES = 16, 64
 FORMAT_RGBA32F, FORMAT_RGBA16F, FORMAT_BC6H_UF16, FORMAT_BC6H_SF16 = 2, 10, 95, 96
 ENV_EQUIRECT, ENV_VCROSS, ENV_HCROSS = 0, 1, 2      # layouts and pixel formats of rtggx_set_env_image
 PIXELS_RGBE8, PIXELS_RGB32F = 0, 1
+ENV_FILTER_MIN_SAMPLES, ENV_FILTER_MAX_SAMPLES = 64, 4096      # rtggx_prefilter_env
 
 _BUF_DTYPE = {BUF_VISIBILITY: np.uint32, BUF_DEPTH: np.uint32, BUF_NORMAL: np.uint32, BUF_ROUGH_METAL: np.uint16,
               BUF_VELOCITY: np.uint32, BUF_RT_REFL: np.uint32, BUF_RT_DIFF: np.uint32, BUF_TSS0: np.uint64, BUF_TSS1: np.uint64,
@@ -38,7 +39,7 @@ EXPORTS = ["rtggx_last_error", "rtggx_create", "rtggx_destroy", "rtggx_set_strip
            "rtggx_set_async_compute", "rtggx_set_history_apron", "rtggx_history_overreach", "rtggx_copy_bandwidth", "rtggx_refit_as", "rtggx_refit_as_device", "rtggx_refit_stats", "rtggx_set_refit_policy", "rtggx_set_sampler", "rtggx_set_ray_rate", "rtggx_set_max_recursion_depth", "rtggx_set_samples_per_pixel", "rtggx_debug_fuse_tone_map", "rtggx_debug_placement", "rtggx_debug_tile_words", "rtggx_debug_static_sky", "rtggx_debug_settled_sky", "rtggx_debug_settled_words", "rtggx_debug_sky_runs", "rtggx_debug_collapse_weights", "rtggx_debug_fence_wait", "rtggx_debug_shader_clock", "rtggx_debug_environment",
            "rtggx_set_accumulation", "rtggx_reset_accumulation", "rtggx_accumulated_frames", "rtggx_present_accumulation", "rtggx_set_sample_set",
            "rtggx_set_reference", "rtggx_reference_from_accumulation", "rtggx_set_scoring", "rtggx_read_scores",
-           "rtggx_set_env_image", "rtggx_generate_env_mips",
+           "rtggx_set_env_image", "rtggx_generate_env_mips", "rtggx_prefilter_env",
            "rtggx_set_sample_map", "rtggx_read_sample_map"]
 SCORE_RING = 256
 
@@ -104,6 +105,7 @@ def load():
     L.rtggx_set_env.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, vp, C.c_size_t]
     L.rtggx_set_env_image.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, vp, C.c_size_t, C.c_uint32]
     L.rtggx_generate_env_mips.argtypes = [vp]
+    L.rtggx_prefilter_env.argtypes = [vp, C.c_uint32]
     L.rtggx_set_material.argtypes = [vp, C.c_uint32, vp, C.c_float, C.c_float]
     L.rtggx_set_metallic.argtypes = [vp, C.c_uint32, C.c_float]
     for n in ("rtggx_build_as", "rtggx_update_as", "rtggx_transform_sh", "rtggx_render_visibility", "rtggx_ray_trace",
@@ -410,6 +412,11 @@ class Context:
     def generate_env_mips(self):
         """The full mip chain below the current level 0 of the environment, rebuilt on the device (include/rtggx.h)."""
         self._check(self.L.rtggx_generate_env_mips(self.h))
+
+    def prefilter_env(self, samples=0):
+        """Every level below level 0 of the environment rebuilt on the device as the GGX-prefiltered radiance of the roughness that selects
+        it (include/rtggx.h): `samples` per texel, a power of two from ENV_FILTER_MIN_SAMPLES to ENV_FILTER_MAX_SAMPLES, 0 = 1024."""
+        self._check(self.L.rtggx_prefilter_env(self.h, int(samples)))
 
     def set_material(self, mesh, base_color, roughness, metallic):
         bc = np.asarray(base_color, np.float32)

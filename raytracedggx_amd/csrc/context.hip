@@ -8,6 +8,7 @@
 #include <vector>
 #include "capi_internal.h"
 #include "rt_queue.h"
+#include "rt_env_filter.h"
 
 #ifndef RT_REFIT_REBUILD_RATIO
 #define RT_REFIT_REBUILD_RATIO 1.2f      // a refitted tree whose cost has grown by this factor since its build is rebuilt (rtggx_refit_as)
@@ -606,6 +607,18 @@ int rtggx_generate_env_mips(rtggx_context* c) {
   if (!c->env.texels) { setError("rtggx_generate_env_mips: no environment map"); return -1; }
   RT_HIP(syncStreams(c));
   const int r = generateEnvMips(c, c->streamMain);
+  if (r == 0) c->sky.breakRuns(SkyBreak::Environment);
+  return r;
+}
+
+// Checked before anything is touched, like rtggx_set_env_image: a refusal leaves the environment, the still-sky runs and the frame as they were.
+int rtggx_prefilter_env(rtggx_context* c, uint32_t samples) {
+  RT_CHECK_CTX(c);
+  if (!c->env.texels) { setError("rtggx_prefilter_env: no environment map"); return -1; }
+  uint32_t n = 0;
+  if (!envFilterSamples(samples, n)) { setError("rtggx_prefilter_env: %u samples: a power of two from %u to %u, or 0 for %u", samples, RTGGX_ENV_FILTER_MIN_SAMPLES, RTGGX_ENV_FILTER_MAX_SAMPLES, kEnvFilterDefaultSamples); return -1; }
+  RT_HIP(syncStreams(c));
+  const int r = prefilterEnv(c, n, c->streamMain);
   if (r == 0) c->sky.breakRuns(SkyBreak::Environment);
   return r;
 }

@@ -12,6 +12,7 @@
 #include <vector>
 #include <cstring>
 #include "rtggx_context.h"
+#include "rt_env_filter.h"
 
 namespace rt {
 
@@ -375,23 +376,64 @@ int buildEnvFromImage(rtggx_context* c, int layout, int pixels, uint32_t width, 
   return installEnv(c, texels, size, mips, mipOffset, total);
 }
 
+// The cube rtggx_generate_env_mips leaves, enqueued on `s`: the context's level 0 as it is and the full box chain below it.  The buffers are
+// allocated here; the two fp32 scratch levels must outlive the launches (the caller synchronises `s` before it lets go of them).
+struct BoxChain { DevBuf<uint2> texels; DevBuf<float4> ping, pong; };
+static hipError_t launchBoxChain(rtggx_context* c, BoxChain& b, uint32_t size, uint32_t mips, const uint32_t* mipOffset, uint64_t total, hipStream_t s) {
+  const size_t n0 = 6u * (size_t)size * size, h = size >> 1, n1 = 6u * h * h;
+  hipError_t e = alloc(b.texels, total);
+  if (e == hipSuccess) e = alloc(b.ping, n0);
+  if (e == hipSuccess && n1) e = alloc(b.pong, n1);
+  if (e == hipSuccess) e = hipMemcpyAsync(b.texels, c->env.texels, n0 * sizeof(uint2), hipMemcpyDeviceToDevice, s);      // level 0 stays what it is
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(envWidenKernel, dim3(envBlocks(n0)), dim3(256), 0, s, (const uint2*)c->env.texels, b.ping.get(), n0);
+  launchEnvChain(b.texels, mipOffset, size, mips, b.ping, b.pong, s);
+  return hipGetLastError();
+}
+
 int generateEnvMips(rtggx_context* c, hipStream_t s) {
   const uint32_t size = c->env.size, mips = fullChain(size);
   uint32_t mipOffset[16];
   const uint64_t total = chainOffsets(size, mips, mipOffset);
-  const size_t n0 = 6u * (size_t)size * size, h = size >> 1, n1 = 6u * h * h;
-  DevBuf<uint2> texels; DevBuf<float4> ping, pong;
-  hipError_t e = alloc(texels, total);
-  if (e == hipSuccess) e = alloc(ping, n0);
-  if (e == hipSuccess && n1) e = alloc(pong, n1);
-  if (e == hipSuccess) e = hipMemcpyAsync(texels, c->env.texels, n0 * sizeof(uint2), hipMemcpyDeviceToDevice, s);      // level 0 stays what it is
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(envWidenKernel, dim3(envBlocks(n0)), dim3(256), 0, s, (const uint2*)c->env.texels, ping, n0);
-    launchEnvChain(texels, mipOffset, size, mips, ping, pong, s);
-    e = hipGetLastError();
-  }
+  BoxChain b;
+  hipError_t e = launchBoxChain(c, b, size, mips, mipOffset, total, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) { setError("rtggx_generate_env_mips: %s", hipGetErrorString(e)); return -2; }
+  return installEnv(c, b.texels, size, mips, mipOffset, total);
+}
+
+// rtggx_prefilter_env (include/rtggx.h; rt_env_filter.h builds the tables): the box-chain cube C beside the context's, then every level
+// below level 0 of a third cube from C -- one launch per level, the levels from M - 4 on sharing the table of roughness 1 --, all on `s`
+// with one wait at the end.  C, the tables and the offsets of C are scratch and gone on return; the context's cube is replaced last.
+int prefilterEnv(rtggx_context* c, uint32_t samples, hipStream_t s) {
+  const uint32_t size = c->env.size, mips = fullChain(size);
+  uint32_t mipOffset[16] = {};
+  const uint64_t total = chainOffsets(size, mips, mipOffset);
+  // the tables, one behind the other: level m's starts at first[m] and holds count[m] entries
+  std::vector<EnvFilterEntry> entries;
+  uint32_t first[16] = {}, count[16] = {}; float invW[16] = {};
+  for (uint32_t m = 1; m < mips; ++m) {
+    if (m > 1u && envFilterWidest(m - 1u, mips)) { first[m] = first[m - 1u]; count[m] = count[m - 1u]; invW[m] = invW[m - 1u]; continue; }
+    const EnvFilterTable t = envFilterTable(size, mips, m, samples);
+    first[m] = (uint32_t)entries.size(); count[m] = (uint32_t)t.entries.size(); invW[m] = t.invW;
+    entries.insert(entries.end(), t.entries.begin(), t.entries.end());
+  }
+  BoxChain b; DevBuf<uint2> texels; DevBuf<uint32_t> dOffsets; DevBuf<float4> dTable;
+  static_assert(sizeof(EnvFilterEntry) == sizeof(float4), "a table entry is one 16-byte load");
+  hipError_t e = launchBoxChain(c, b, size, mips, mipOffset, total, s);
+  if (e == hipSuccess) e = alloc(texels, total);
+  if (e == hipSuccess) e = alloc(dOffsets, 16);
+  if (e == hipSuccess && !entries.empty()) e = alloc(dTable, entries.size());
+  if (e == hipSuccess) e = hipMemcpyAsync(texels, c->env.texels, 6u * (size_t)size * size * sizeof(uint2), hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(dOffsets, mipOffset, sizeof mipOffset, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && !entries.empty()) e = hipMemcpyAsync(dTable, entries.data(), entries.size() * sizeof(EnvFilterEntry), hipMemcpyHostToDevice, s);
+  int launched = 0;
+  for (uint32_t m = 1; m < mips && e == hipSuccess && launched == 0; ++m)
+    launched = launchEnvPrefilter(b.texels, size, mips, dOffsets, dTable.get() + first[m], count[m], invW[m], size >> m, texels.get() + mipOffset[m], s);
+  const hipError_t waited = hipStreamSynchronize(s);      // (whatever happened: the host arrays above and the scratch are in use until here)
+  if (launched) return launched;                          // (the launcher has said why)
+  if (e == hipSuccess) e = waited;
+  if (e != hipSuccess) { setError("rtggx_prefilter_env: %s", hipGetErrorString(e)); return -2; }
   return installEnv(c, texels, size, mips, mipOffset, total);
 }
 

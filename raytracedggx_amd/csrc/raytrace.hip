@@ -1270,6 +1270,49 @@ int launchDebugEnvironment(rtggx_context* c, const float* dDirs, const float* dL
   return 0;
 }
 
+// ---- GGX-prefiltered environments (rtggx_prefilter_env; include/rtggx.h, DESIGN.md "Prefiltered environments") --------------------
+// One level of the new cube from the box-chain cube `src`: one wave per destination texel, four waves per workgroup.  Lane j owns the
+// table entries j, j + 64, ... -- one 16-byte load per lane and step, 1 KB contiguous per wave -- and adds its terms in that order;
+// the 64 partial sums meet in a butterfly over lane ^ 1, ^ 2, ... ^ 32, which is the contract's adjacent-first pairwise tree (a + b is
+// commutative) and needs no LDS.  The taps are the frame's own sampler, called as the frame calls it: eight 8-byte gathers and the offset
+// word each, four of them in flight at a time, from a cube whose coarse levels sit in L2 -- latency, not bandwidth, so the kernel stays
+// below 64 VGPRs (57 with the callee) and eight waves per SIMD hide it.  (Two entries per lane in flight through an inlined copy of the
+// sampler: 1-3 % off the call at N = 4096, nothing below, seven times the code; not kept -- DESIGN.md.)  A lane without an entry holds
+// +0.  No atomics: the texel is a pure function of the cube and the table.
+struct EnvFilterArgs {
+  EnvRef src;                            // level 0 and the full box chain (its own offset table)
+  const float4* __restrict__ table;      // K x (x, y, z, lod): rt_env_filter.h
+  uint2* __restrict__ dst;               // the level's texels in the new cube
+  uint32_t K, side;
+  float invW;
+};
+__global__ void __launch_bounds__(256, 8) envPrefilterKernel(EnvFilterArgs A) {
+  const size_t texel = (size_t)blockIdx.x * 4u + (threadIdx.x >> 6), perFace = (size_t)A.side * A.side;
+  if (texel >= 6u * perFace) return;      // (whole waves: the guard is wave-uniform)
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t face = (uint32_t)(texel / perFace), rem = (uint32_t)(texel % perFace), y = rem / A.side, x = rem % A.side;
+  const float u = ((float)x + 0.5f) / (float)A.side * 2.0f - 1.0f, v = ((float)y + 0.5f) / (float)A.side * 2.0f - 1.0f;
+  const f3 R = normalize3(cubeFaceDir((int)face, u, v));
+  f3 sum = mk3(0.0f, 0.0f, 0.0f);
+  for (uint32_t k = lane; k < A.K; k += 64u) {
+    const float4 e = A.table[k];
+    const f3 c = environment(A.src, localToWorld(R, mk3(e.x, e.y, e.z)), e.w);
+    sum = sum + c * e.z;
+  }
+  for (int d = 1; d < 64; d <<= 1) sum = sum + mk3(__shfl_xor(sum.x, d), __shfl_xor(sum.y, d), __shfl_xor(sum.z, d));
+  if (lane == 0u) A.dst[texel] = packRGBA16F(fminf(sum.x * A.invW, 65504.0f), fminf(sum.y * A.invW, 65504.0f), fminf(sum.z * A.invW, 65504.0f), 1.0f);
+}
+int launchEnvPrefilter(const uint2* srcTexels, uint32_t size, uint32_t mips, const uint32_t* dSrcMipOffset, const float4* dTable, uint32_t K, float invW,
+                       uint32_t side, uint2* dst, hipStream_t s) {
+  EnvFilterArgs A;
+  A.src = EnvRef{srcTexels, size, mips, dSrcMipOffset};
+  A.table = dTable; A.dst = dst; A.K = K; A.side = side; A.invW = invW;
+  const size_t waves = 6u * (size_t)side * side;
+  hipLaunchKernelGGL(envPrefilterKernel, dim3((uint32_t)((waves + 3u) / 4u)), dim3(256), 0, s, A);
+  RT_HIP(hipGetLastError());
+  return 0;
+}
+
 // ---- progressive accumulation (rtggx_set_accumulation; include/rtggx.h, DESIGN.md "Progressive accumulation") ---------------------
 // The frame's two traced images added to the running sums: one lane per pixel of the strip's own rows -- whole rows, so the pixels are
 // one contiguous range [first, first + count) of every image --, a streaming pass of 8 + 4 (+ 4) bytes read and 16 (+ 16) read and

@@ -24,8 +24,8 @@ namespace rt {
 enum class SkyBreak : uint8_t {
   None,                // nothing has ended the runs yet
   Generation,          // rayGeneration: this ray generation differs from the one before it (the list is above that method)
-  Environment,         // rtggx_set_env, rtggx_set_env_image, rtggx_generate_env_mips: the sky behind every pixel is another one (of the mips:
-                       //   every level below the first); a failed build has left the old one and ends nothing
+  Environment,         // rtggx_set_env, rtggx_set_env_image, rtggx_generate_env_mips, rtggx_prefilter_env: the sky behind every pixel is another
+                       //   one (of the last two: every level below the first); a failed build has left the old one and ends nothing
   Upload,              // rtggx_upload: what a still-sky tile relies on being in place may just have been replaced (TSS, FilteredOut1 and
                        //   the back buffer included: whatever is written behind the kernels' back)
   Strip,               // rtggx_set_strip: other rows, and tiles count from the pass's first row

@@ -504,6 +504,10 @@ int launchToneMap(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEve
 int decodeEnv(rtggx_context* c, int format, uint32_t size, uint32_t mips, const void* hostData, size_t bytes, hipStream_t s);
 int buildEnvFromImage(rtggx_context* c, int layout, int pixels, uint32_t width, uint32_t height, const void* hostData, uint32_t size, hipStream_t s);   // rtggx_set_env_image, arguments checked
 int generateEnvMips(rtggx_context* c, hipStream_t s);                                                                                                  // rtggx_generate_env_mips
+int prefilterEnv(rtggx_context* c, uint32_t samples, hipStream_t s);                                                                                   // rtggx_prefilter_env, arguments checked: samples is the count itself
+// one level of the prefiltered cube (raytrace.hip, beside the sampler it calls): 6 side^2 texels at dst from the box-chain cube and a table of K entries
+int launchEnvPrefilter(const uint2* srcTexels, uint32_t size, uint32_t mips, const uint32_t* dSrcMipOffset, const float4* dTable, uint32_t K, float invW,
+                       uint32_t side, uint2* dst, hipStream_t s);
 int projectSH(rtggx_context* c, hipStream_t s);
 int unpackVisDepth(rtggx_context* c, uint32_t* dVis, uint32_t* dDepth, hipStream_t s);
 int packVisDepth(rtggx_context* c, const uint32_t* dVis, const uint32_t* dDepth, hipStream_t s);

@@ -25,7 +25,7 @@ RayTracedGGX::~RayTracedGGX() {}
 // LoadPipeline + LoadAssets (RayTracedGGX.cpp:61-279)
 void RayTracedGGX::OnInit() {
   m_rayTracer = std::make_unique<RayTracer>();
-  m_rayTracer->SetEnvOptions(m_envLayout, m_envSize, m_envMips);      // -envlayout, -envsize, -envmips: what Init does with the -env file
+  m_rayTracer->SetEnvOptions(m_envLayout, m_envSize, m_envMips, m_envPrefilter);      // -envlayout, -envsize, -envmips, -envprefilter: what Init does with the -env file
   if (!m_rayTracer->Init(m_width, m_height, m_meshFileName.c_str(), m_envFileName.c_str(), m_meshPosScale, m_device))
     throw std::runtime_error("RayTracer::Init failed: " + m_rayTracer->GetLastError());
   m_denoiser = std::make_unique<Denoiser>();
@@ -206,7 +206,7 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
     return (arg[0] == '-' || arg[0] == '/') && lower(arg + 1) == lower(name);
   };
   // On POSIX an absolute path also starts with '/': such a token is a flag only when it names one.
-  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "recursion", "spp", "accumulate", "sampleset", "savereference", "reference", "score", "envlayout", "envsize", "envmips"};
+  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "recursion", "spp", "accumulate", "sampleset", "savereference", "reference", "score", "envlayout", "envsize", "envmips", "envprefilter"};
   const auto isFlagName = [&](const char* name) { for (const char* f : kFlags) if (lower(name) == f) return true; return false; };
   const auto hasNextArgValue = [&](int i) {
     if (i + 1 >= argc) return false;
@@ -232,6 +232,13 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
       m_envSize = (uint32_t)size;
     }
     else if (isArgMatched(i, "envmips")) m_envMips = true;
+    // -envprefilter [N]: GGX-prefiltered levels below level 0 (rtggx_prefilter_env); the count is checked here, before a device is asked for
+    else if (isArgMatched(i, "envprefilter")) {
+      long samples = 1024;
+      if (hasNextArgValue(i)) { char* end = nullptr; samples = std::strtol(argv[++i], &end, 10); if (end == argv[i] || *end != '\0') samples = -1; }
+      if (samples < (long)RTGGX_ENV_FILTER_MIN_SAMPLES || samples > (long)RTGGX_ENV_FILTER_MAX_SAMPLES || (samples & (samples - 1)) != 0) throw std::runtime_error("-envprefilter: a number of samples that is a power of two from 64 to 4096 (1024 without a number)");
+      m_envPrefilter = (uint32_t)samples;
+    }
     // extensions replacing the window / message loop
     else if (isArgMatched(i, "width")) { if (hasNextArgValue(i)) m_width = (uint32_t)std::atoi(argv[++i]); }
     else if (isArgMatched(i, "height")) { if (hasNextArgValue(i)) m_height = (uint32_t)std::atoi(argv[++i]); }

@@ -2,7 +2,7 @@
 // DXFramework virtuals RayTracedGGX/Common/DXFramework.h:23-26): OnInit / OnUpdate / OnRender /
 // OnDestroy, the same command line (RayTracedGGX.cpp:462-511) and the same defaults
 // (RayTracedGGX.cpp:37-39, camera :19-23, 267-277).  What the window supplied interactively is
-// supplied by extra flags: -width -height -frames -dt -metallic -sharedmem -sync -vndf -rayrate -recursion -spp -sampleset -accumulate -savereference -reference -score -envlayout -envsize -envmips -device -dump -track -deform -gpus -strips -balance.
+// supplied by extra flags: -width -height -frames -dt -metallic -sharedmem -sync -vndf -rayrate -recursion -spp -sampleset -accumulate -savereference -reference -score -envlayout -envsize -envmips -envprefilter -device -dump -track -deform -gpus -strips -balance.
 #pragma once
 #include <vector>
 #include <cstdint>
@@ -113,8 +113,10 @@ class RayTracedGGX {
   std::string m_envFileName = "Assets/rnl_cross.dds";
   // -env takes a DDS cube, a Radiance .hdr or a .pfm image (told by the file's first bytes).  -envlayout <equirect|vcross|hcross>: the layout
   // of an image whose aspect ratio is none of 2:1, 3:4, 4:3; -envsize <1..4096>: the side of the cube a panorama is resampled to (refused
-  // with a cross); -envmips: a DDS cube with fewer levels than a full chain gets it built on the device (RayTracer::SetEnvOptions)
-  int m_envLayout = -1; uint32_t m_envSize = 0; bool m_envMips = false;
+  // with a cross); -envmips: a DDS cube with fewer levels than a full chain gets it built on the device (RayTracer::SetEnvOptions);
+  // -envprefilter [N]: the levels below level 0 rebuilt as the GGX-prefiltered radiance, N samples per texel (a power of two from 64 to 4096,
+  // 1024 without a number; 0 here: off), DDS cube or image, every rank of -gpus / -strips; it implies -envmips
+  int m_envLayout = -1; uint32_t m_envSize = 0; bool m_envMips = false; uint32_t m_envPrefilter = 0;
   float m_meshPosScale[4] = {0.0f, 0.0f, 0.0f, 1.0f};
   uint32_t m_numFrames = 1;
   float m_fixedTimeStep = 1.0f / 60.0f;   // the reference steps by the wall clock (StepTimer); fixed here for reproducible runs

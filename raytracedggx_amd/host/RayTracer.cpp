@@ -62,7 +62,7 @@ bool RayTracer::Init(uint32_t width, uint32_t height, const char* fileName, cons
     if (layout < 0) layout = EnvImage::LayoutFromAspect(image.width, image.height);
     if (layout < 0) return fail(std::string(envFileName) + ": " + std::to_string(image.width) + " x " + std::to_string(image.height) + " pixels are neither 3:4 (vertical cross), 4:3 (horizontal cross) nor 2:1 (panorama): name the layout with -envlayout equirect|vcross|hcross");
     if (layout != EnvImage::EQUIRECT && m_envCubeSize != 0u) return fail("-envsize: a cross is never resampled, its cells are the cube's faces (" + std::string(envFileName) + " is a " + (layout == EnvImage::VCROSS ? "vertical" : "horizontal") + " cross)");
-    if (m_envGenerateMips) std::fprintf(stderr, "RayTracer: -envmips has no effect on %s: an image always gets its full mip chain\n", envFileName);
+    if (m_envGenerateMips && m_envPrefilterSamples == 0u) std::fprintf(stderr, "RayTracer: -envmips has no effect on %s: an image always gets its full mip chain\n", envFileName);
   } else {
     if (!DDS::Loader().LoadCubeFromFile(envFileName, cube, err)) return fail(err);      // (RayTracer.cpp:143-150)
     if (m_envLayout >= 0 || m_envCubeSize != 0u) std::fprintf(stderr, "RayTracer: -envlayout / -envsize have no effect on %s: a DDS cube is taken as it is\n", envFileName);
@@ -78,12 +78,18 @@ bool RayTracer::Init(uint32_t width, uint32_t height, const char* fileName, cons
   if (!check(rtggx_set_mesh(m_ctx, MODEL_OBJ, reinterpret_cast<const float*>(objLoader.GetVertices()), m_numVerts,
                             objLoader.GetIndices(), m_numIndices), "rtggx_set_mesh")) return false;
 
-  if (isImage) return check(rtggx_set_env_image(m_ctx, layout, image.pixels, image.width, image.height, image.data.data(), image.data.size(), m_envCubeSize), "rtggx_set_env_image");
-  if (!check(rtggx_set_env(m_ctx, cube.format, cube.size, cube.mips, cube.payload.data(), cube.payload.size()), "rtggx_set_env")) return false;
-  uint32_t full = 1; while ((cube.size >> full) != 0u) ++full;
-  if (m_envGenerateMips && cube.mips < full && !check(rtggx_generate_env_mips(m_ctx), "rtggx_generate_env_mips")) return false;
-  return true;
+  if (isImage) {
+    if (!check(rtggx_set_env_image(m_ctx, layout, image.pixels, image.width, image.height, image.data.data(), image.data.size(), m_envCubeSize), "rtggx_set_env_image")) return false;
+  } else {
+    if (!check(rtggx_set_env(m_ctx, cube.format, cube.size, cube.mips, cube.payload.data(), cube.payload.size()), "rtggx_set_env")) return false;
+    uint32_t full = 1; while ((cube.size >> full) != 0u) ++full;
+    // (the prefilter starts from the full box chain below the current level 0 whatever levels the cube came with: it implies -envmips)
+    if (m_envGenerateMips && m_envPrefilterSamples == 0u && cube.mips < full && !check(rtggx_generate_env_mips(m_ctx), "rtggx_generate_env_mips")) return false;
+  }
+  return m_envPrefilterSamples == 0u || PrefilterEnvironment(m_envPrefilterSamples);
 }
+
+bool RayTracer::PrefilterEnvironment(uint32_t samples) { return check(rtggx_prefilter_env(m_ctx, samples), "rtggx_prefilter_env"); }
 
 bool RayTracer::BuildAccelerationStructures() { return check(rtggx_build_as(m_ctx), "rtggx_build_as"); }
 

@@ -36,8 +36,12 @@ class RayTracer {
   // What Init does with the environment file (-envlayout, -envsize, -envmips); to be called before it.  layout: RTGGX_ENV_* or -1 = by the
   // image's aspect ratio (3:4 vertical cross, 4:3 horizontal cross, 2:1 panorama; anything else is refused).  cubeSize: the cube's side for a
   // panorama (0: the largest power of two <= width / 4); refused with a cross, whose cells are the faces.  generateMips: a DDS cube with
-  // fewer levels than a full chain gets the chain built on the device (rtggx_generate_env_mips).
-  void SetEnvOptions(int layout, uint32_t cubeSize, bool generateMips) { m_envLayout = layout; m_envCubeSize = cubeSize; m_envGenerateMips = generateMips; }
+  // fewer levels than a full chain gets the chain built on the device (rtggx_generate_env_mips).  prefilterSamples: 0 = off, else the sample
+  // count (a power of two from 64 to 4096) with which Init, once the environment is installed -- DDS cube or image --, rebuilds the levels
+  // below level 0 as the GGX-prefiltered radiance (-envprefilter, rtggx_prefilter_env); it builds the full chain itself, generateMips or not.
+  void SetEnvOptions(int layout, uint32_t cubeSize, bool generateMips, uint32_t prefilterSamples = 0) { m_envLayout = layout; m_envCubeSize = cubeSize; m_envGenerateMips = generateMips; m_envPrefilterSamples = prefilterSamples; }
+  // rtggx_prefilter_env on the current environment: samples 0 = 1024, else a power of two from 64 to 4096; a refusal leaves it as it was
+  bool PrefilterEnvironment(uint32_t samples);
   bool BuildAccelerationStructures();
   bool Postinit();
 
@@ -93,7 +97,7 @@ class RayTracer {
   float m_posScale[4] = {0.0f, 0.0f, 0.0f, 1.0f};
   uint32_t m_numVerts = 0, m_numIndices = 0;
   std::vector<float> m_modelVerts;
-  int m_envLayout = -1; uint32_t m_envCubeSize = 0; bool m_envGenerateMips = false;      // SetEnvOptions
+  int m_envLayout = -1; uint32_t m_envCubeSize = 0; bool m_envGenerateMips = false; uint32_t m_envPrefilterSamples = 0;      // SetEnvOptions
 
   // state UpdateFrame keeps between frames (statics / members in the reference)
   HaltonSequence m_halton;
