@@ -588,6 +588,40 @@ int  rtggx_bvh_root(rtggx_context* ctx, uint32_t slot, int32_t* root);
  * out = n x {t, instance(bits), primitive(bits), b1, b2, valid}. */
 int  rtggx_trace_rays(rtggx_context* ctx, const float* rays, uint32_t n, float* out);
 
+/* Occlusion queries: the same ray list -- rays = n x {o.xyz, d.xyz, tmin, tmax} -- through the ANY-HIT variant of the traversal
+ * (csrc/trace.hip, csrc/rt_queue.h).  occluded = n words, 1 where some triangle of either instance satisfies tmin < t < tmax (both
+ * bounds exclusive) under the traversal's own watertight test, 0 otherwise: by construction the `valid` of the closest-hit query on
+ * the same ray.  Which triangle stopped an occluded ray is unspecified and is not reported: a lane leaves its ray at the first
+ * triangle it accepts, its pending subtrees are dropped, and nothing is ordered by distance.  Like the closest-hit query it refills
+ * a set's ray bins, so it waits for the frames in flight and ends the still-sky runs; the frames after it are what they would have
+ * been without it.  The rays are not added to the frame's ray counters.  Fails on n == 0, on a null pointer and before
+ * rtggx_build_as / the first rtggx_update_frame.  Opt-in: a context that never calls it launches no any-hit kernel. */
+int  rtggx_trace_occlusion(rtggx_context* ctx, const float* rays, uint32_t n, uint32_t* occluded);
+
+/* A sun: one directional light with ray-traced shadows.  Opt-in: a context that never calls this allocates and launches what it always did.
+ * direction: a world-space vector TOWARD the sun, normalised on the host in double and rounded once to fp32 (call it L).  irradiance: E, rgb,
+ * what a surface facing the sun receives, in the units of the environment's radiance x sr.  (NULL, NULL) or E = 0 in every component turns
+ * the sun off.  Takes effect with the next rtggx_render_visibility.  Refused, the context keeping what it had: a non-finite or zero-length
+ * direction; a negative or non-finite E; a sun on a context at ray rate 4, and rate 4 on a context with a sun (three quarters of a rate-4
+ * frame are interpolations).
+ * While the sun is on rtggx_ray_trace runs three more kernels behind the hit shading (and the resolve of N samples), in front of the
+ * accumulation, the scoring and rtggx_denoise; RtggxTimings.ray_trace covers them.  For every covered pixel (visibility word != 0) of the
+ * rows ray generation covers, in fp32 without contraction, each operation rounded on its own:
+ *   1. the primary surface exactly as ray generation derives it: P, N, V, color, (r, m), inst, prim;
+ *   2. NoL = dot(N, L); NoL <= 0: no ray, both words untouched;
+ *   3. a shadow ray from P along L, interval (1e-5, 10000), skipping (inst, prim), through the any-hit traversal; occluded: both words untouched;
+ *   4. r' = max(r, 1/32) (a mirror under a delta light has no finite answer); H = normalize(V + L); NoH, VoH, NoV saturated; a = r' r', a2 = a a;
+ *      d = (NoH a2 - NoH) NoH + 1; D = a2 / ((pi d) d); f0 = lerp(0.04, color, m); F = fSchlick(f0, VoH); vis = visSmith(r', NoV, NoL);
+ *      k = (D vis) NoL; spec_c = (F_c k) E_c; RayTracingOut0 = pack(unpack(RayTracingOut0) + spec);
+ *   5. where m < 1: diff_c = ((color_c (1 - 0.04)) (NoL / pi)) E_c; RayTracingOut1 = pack(unpack(RayTracingOut1) + diff).  Where m >= 1
+ *      RayTracingOut1 is a carry-over and is not touched.
+ * The terms are added to the packed words: one more rounding of at most half a code of an 11-bit float, and the sun is independent of recursion
+ * depth, sample count, sample set and sample map -- one shadow ray per covered, sun-facing pixel per frame, counted by rtggx_ray_count.
+ * Background pixels are untouched.  Setting the sun ends no still-sky run and resets no accumulation (the caller's to do).
+ * Known limit: surfaces seen in reflections are shaded by the environment and the SH irradiance alone -- a reflection shows the ground
+ * without its sun term and without the shadow.  Memory: 56 bytes per pixel and 4 per 8x8 block, from the first call that turns it on. */
+int  rtggx_set_sun(rtggx_context* ctx, const float direction[3], const float irradiance[3]);
+
 #ifdef __cplusplus
 }
 #endif

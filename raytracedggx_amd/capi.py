@@ -40,7 +40,7 @@ EXPORTS = ["rtggx_last_error", "rtggx_create", "rtggx_destroy", "rtggx_set_strip
            "rtggx_set_accumulation", "rtggx_reset_accumulation", "rtggx_accumulated_frames", "rtggx_present_accumulation", "rtggx_set_sample_set",
            "rtggx_set_reference", "rtggx_reference_from_accumulation", "rtggx_set_scoring", "rtggx_read_scores",
            "rtggx_set_env_image", "rtggx_generate_env_mips", "rtggx_prefilter_env",
-           "rtggx_set_sample_map", "rtggx_read_sample_map"]
+           "rtggx_set_sample_map", "rtggx_read_sample_map", "rtggx_trace_occlusion", "rtggx_set_sun"]
 SCORE_RING = 256
 
 
@@ -123,6 +123,8 @@ def load():
     L.rtggx_frame_parity.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.rtggx_bvh_root.argtypes = [vp, C.c_uint32, C.POINTER(C.c_int32)]
     L.rtggx_trace_rays.argtypes = [vp, vp, C.c_uint32, vp]
+    L.rtggx_trace_occlusion.argtypes = [vp, vp, C.c_uint32, vp]
+    L.rtggx_set_sun.argtypes = [vp, vp, vp]
     L.rtggx_ray_total.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
     L.rtggx_kernel_times.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
     _lib = L
@@ -571,3 +573,17 @@ class Context:
         self._check(self.L.rtggx_trace_rays(self.h, _p(r), r.shape[0], _p(out)))
         return {"t": out[:, 0].copy(), "inst": out[:, 1].copy().view(np.uint32), "prim": out[:, 2].copy().view(np.uint32),
                 "b1": out[:, 3].copy(), "b2": out[:, 4].copy(), "valid": out[:, 5] > 0.5}
+
+    def set_sun(self, direction, irradiance):
+        """A directional light with ray-traced shadows from the next frame on; (None, None) or a zero irradiance turns it off."""
+        if direction is None and irradiance is None:
+            return self._check(self.L.rtggx_set_sun(self.h, None, None))
+        d, e = np.ascontiguousarray(direction, np.float32).reshape(3), np.ascontiguousarray(irradiance, np.float32).reshape(3)
+        self._check(self.L.rtggx_set_sun(self.h, _p(d), _p(e)))
+
+    def trace_occlusion(self, rays):
+        """One bool per ray {o.xyz, d.xyz, tmin, tmax}: is there a triangle with tmin < t < tmax (the any-hit traversal)."""
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        out = np.zeros(r.shape[0], np.uint32)
+        self._check(self.L.rtggx_trace_occlusion(self.h, _p(r), r.shape[0], _p(out)))
+        return out != 0

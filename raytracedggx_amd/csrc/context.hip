@@ -357,6 +357,7 @@ int rtggx_set_ray_rate(rtggx_context* c, uint32_t pixelsPerRay) {
   if (pixelsPerRay != 1u && pixelsPerRay != 4u) { setError("rtggx_set_ray_rate: %u pixels per ray: 1 or 4", pixelsPerRay); return -1; }
   if (pixelsPerRay != 1u && c->samplesRequested > 1u) { setError("rtggx_set_ray_rate: rate %u on a context tracing %u samples per pixel (rtggx_set_samples_per_pixel): one asks for fewer rays, the other for more", pixelsPerRay, c->samplesRequested); return -1; }
   if (pixelsPerRay != 1u && c->accumulateRequested) { setError("rtggx_set_ray_rate: rate %u on an accumulating context (rtggx_set_accumulation): three quarters of such a frame are interpolations", pixelsPerRay); return -1; }
+  if (pixelsPerRay != 1u && c->sunRequested.on) { setError("rtggx_set_ray_rate: rate %u on a context with a sun (rtggx_set_sun): three quarters of such a frame are interpolations", pixelsPerRay); return -1; }
   if (pixelsPerRay != 1u && (c->rowBegin > 0u || c->rowEnd < c->H)) { setError("rtggx_set_ray_rate: rate %u on a strip (rows [%u,%u) of %u): whole frames only", pixelsPerRay, c->rowBegin, c->rowEnd, c->H); return -1; }
   if (pixelsPerRay == c->rayRate) return 0;
   RT_HIP(syncStreams(c));
@@ -416,6 +417,33 @@ int rtggx_set_accumulation(rtggx_context* c, int enable) {
   if (enable && c->rayRate != 1u) { setError("rtggx_set_accumulation: on a context tracing one pixel in %u (rtggx_set_ray_rate): three quarters of such a frame are interpolations", c->rayRate); return -1; }
   if (enable) { const int r = allocAccumulation(c); if (r) return r; }
   c->accumulateRequested = enable != 0;
+  return 0;
+}
+// The sun (include/rtggx.h).  The direction is normalised in double and rounded once; (NULL, NULL) or E = 0 turns the sun off.  A refused call
+// leaves what the context had.  The first call that turns it on allocates the queue: local owners first, members when all exist.  No
+// synchronisation, no end of a still-sky run, no reset of an accumulation: no sky texel depends on the sun, and the request takes effect with
+// the next rtggx_render_visibility.
+int rtggx_set_sun(rtggx_context* c, const float direction[3], const float irradiance[3]) {
+  RT_CHECK_CTX(c);
+  if (!direction && !irradiance) { c->sunRequested.on = false; return 0; }
+  if (!direction || !irradiance) { setError("rtggx_set_sun: a direction without an irradiance, or the reverse"); return -1; }
+  const double x = direction[0], y = direction[1], z = direction[2], len = std::sqrt(x * x + y * y + z * z);
+  if (!std::isfinite(len) || !(len > 0.0)) { setError("rtggx_set_sun: the direction (%g, %g, %g) has no finite, non-zero length", x, y, z); return -1; }
+  for (int k = 0; k < 3; ++k) if (!std::isfinite(irradiance[k]) || irradiance[k] < 0.0f) { setError("rtggx_set_sun: irradiance component %d is %g: finite and not negative", k, (double)irradiance[k]); return -1; }
+  const bool on = irradiance[0] > 0.0f || irradiance[1] > 0.0f || irradiance[2] > 0.0f;
+  if (on && c->rayRate != 1u) { setError("rtggx_set_sun: on a context tracing one pixel in %u (rtggx_set_ray_rate): three quarters of such a frame are interpolations", c->rayRate); return -1; }
+  if (on && !c->sunRays) {
+    DevBuf<void> rays, hits; DevBuf<uint32_t> count;
+    RT_HIP(alloc(rays, (size_t)c->numBinsMax * RT_BIN_MIN * sizeof(RayRec)));
+    RT_HIP(alloc(hits, (size_t)c->numBinsMax * RT_BIN_MIN * sizeof(HitKey)));
+    RT_HIP(allocFilled(count, c->numBinsMax));
+    c->sunRays = std::move(rays); c->sunHits = std::move(hits); c->sunCount = std::move(count);
+  }
+  rtggx_context::Sun sun;
+  sun.on = on;
+  sun.L[0] = (float)(x / len); sun.L[1] = (float)(y / len); sun.L[2] = (float)(z / len);
+  for (int k = 0; k < 3; ++k) sun.E[k] = irradiance[k];
+  c->sunRequested = sun;
   return 0;
 }
 // Sums and count back to zero: two clears on the main stream, behind the frames it holds and in front of the next one; nothing waits.

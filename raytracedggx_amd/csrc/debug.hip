@@ -374,7 +374,31 @@ int rtggx_trace_rays(rtggx_context* c, const float* rays, uint32_t n, float* out
     const uint32_t m = n - done < perLaunch ? n - done : perLaunch;
     r = launchTraceRays(c, c->slots[c->slot], dR + (size_t)done * 8, m, dO + (size_t)done * 6, c->streamMain);
   }
-  if (!r) { hipError_t e = hipStreamSynchronize(c->streamMain); if (e == hipSuccess) e = hipMemcpy(out, dO, (size_t)n * 24, hipMemcpyDeviceToHost); if (e != hipSuccess) { setError("trace_rays: %s", hipGetErrorString(e)); r = -2; } }
+  const hipError_t queued = hipStreamSynchronize(c->streamMain);      // also after a failed chunk: the chunks before it still read dR and write dO, which leave with this scope
+  if (!r) { hipError_t e = queued; if (e == hipSuccess) e = hipMemcpy(out, dO, (size_t)n * 24, hipMemcpyDeviceToHost); if (e != hipSuccess) { setError("trace_rays: %s", hipGetErrorString(e)); r = -2; } }
+  return r;
+}
+
+// The list path of rtggx_trace_rays through the any-hit variant of the trace kernel: one word per ray, 1 = occluded.
+int rtggx_trace_occlusion(rtggx_context* c, const float* rays, uint32_t n, uint32_t* occluded) {
+  RT_CHECK_CTX(c);
+  if (!rays || !occluded) { setError("rtggx_trace_occlusion: null rays or result"); return -1; }
+  if (n == 0u) { setError("rtggx_trace_occlusion: no rays"); return -1; }
+  if (!c->asBuilt || !c->haveConstants) { setError("rtggx_trace_occlusion: build_as / update_frame / update_as first"); return -1; }
+  RT_HIP(syncStreams(c));   // the ray bins are shared with the frame path on stream B
+  c->sky.breakRuns(SkyBreak::TraceRays);        // (it refills a set's bins, as rtggx_trace_rays does)
+  { const int r = ensureParams(c); if (r) return r; }
+  DevBuf<float> dR; DevBuf<uint32_t> dO;
+  RT_HIP(alloc(dR, (size_t)n * 8)); RT_HIP(alloc(dO, (size_t)n));
+  RT_HIP(hipMemcpy(dR, rays, (size_t)n * 32, hipMemcpyHostToDevice));
+  int r = 0;
+  const uint32_t perLaunch = c->numBinsMax * c->binSlots;
+  for (uint32_t done = 0; done < n && !r; done += perLaunch) {   // the ray bins' capacity per launch
+    const uint32_t m = n - done < perLaunch ? n - done : perLaunch;
+    r = launchTraceOcclusion(c, c->slots[c->slot], dR + (size_t)done * 8, m, dO + (size_t)done, c->streamMain);
+  }
+  const hipError_t queued = hipStreamSynchronize(c->streamMain);      // also after a failed chunk (see rtggx_trace_rays)
+  if (!r) { hipError_t e = queued; if (e == hipSuccess) e = hipMemcpy(occluded, dO, (size_t)n * 4, hipMemcpyDeviceToHost); if (e != hipSuccess) { setError("trace_occlusion: %s", hipGetErrorString(e)); r = -2; } }
   return r;
 }
 

@@ -194,7 +194,7 @@ int rtggx_render_visibility(rtggx_context* c) {
   if (!c->shDone && c->env.texels) { const int r = projectSH(c, c->streamAS); if (r) return r; }   // first frame only, RayTracer.cpp:345-350
   settleSetRead(c);      // (the previous frame ended without the kernel that would have carried its set's event)
   ++c->frameCounter;
-  c->maxDepth = c->depthRequested; c->samples = c->samplesRequested; c->accumulate = c->accumulateRequested;
+  c->maxDepth = c->depthRequested; c->samples = c->samplesRequested; c->accumulate = c->accumulateRequested; c->sun = c->sunRequested;
   c->scoring = c->scoringRequested && c->reference != nullptr;
   c->sampleMap = c->sampleMapRequested;      // rtggx_set_sample_map: the setter has waited for every stream and written the copy no frame reads
   bool resendConstants = false;
@@ -305,6 +305,14 @@ int rtggx_ray_trace(rtggx_context* c) {
   if (c->rayRate == 4u) {
     if (!r) r = launchReconstruct(c, fp, c->streamMain);
     c->diffStream = c->streamMain;
+  }
+  // the sun (rtggx_set_sun): three kernels on the main stream, where both traced images are complete (see the accumulation below) -- behind the
+  // hit shading and the resolve of N samples, in front of the accumulation, the scoring and the denoiser.  The next frame's carry-over of
+  // RayTracingOut1 and its shading kernels wait for whoever wrote the images last: from here on that is the main stream.  With a deforming
+  // mesh the shadow launch reads this set's tree: the main stream follows the traversal's event, which followed the refit's.
+  if (c->sun.on) {
+    if (!r) r = launchSun(c, fp, c->streamMain);
+    c->shadeStream = c->diffStream = c->streamMain;
   }
   // accumulation (rtggx_set_accumulation): the frame's two traced images into the running sums, on the main stream.  Both images are
   // complete where the main stream stands: it has passed ev.trace, which rides on the traversal with the shading (and the resolve of N

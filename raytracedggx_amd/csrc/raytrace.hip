@@ -1204,6 +1204,139 @@ int launchReconstruct(rtggx_context* c, const FrameParams& fp, hipStream_t s) {
   return 0;
 }
 
+// ---- the sun (rtggx_set_sun; include/rtggx.h has the per-pixel rule, DESIGN.md section 9 "Sun and shadow rays") ------------------------------
+// Three kernels on the stream that has this frame's two traced images complete (frame.hip rtggx_ray_trace): sunGenKernel derives the primary
+// surface once more from the visibility word -- rayGenKernel's arithmetic, as sampleGenKernel does --, and where the surface faces the sun
+// compacts one shadow ray into the wave's bin of the sun's own queue, with everything the add needs: the specular term in the record's weight,
+// NoL in its flags word.  The any-hit variant of the trace kernel (trace.hip) leaves an unoccluded ray's key a miss.  sunAddKernel walks the
+// bins: one lane per slot, and an unoccluded one adds its terms to its pixel's packed words (a pixel has at most one slot: no two lanes meet).
+#ifndef RT_SUN_CLOSEST
+#define RT_SUN_CLOSEST 0      // measurement: 1 traces the shadow queue with the closest-hit kernel (the same images; profiles/r14_d_sun_cost.txt)
+#endif
+struct SunGenArgs {
+  const unsigned long long* visDepth; const float4* fat0; const float4* fat1;
+  RayRec* rays; HitKey* hits; uint32_t* binCount;
+  const uint32_t* tileWords; uint32_t tilesX, rowBegin, rowEnd;
+  float Lx, Ly, Lz, Ex, Ey, Ez;
+};
+__global__ void __launch_bounds__(256) sunGenKernel(const FrameParams* __restrict__ fpp, SunGenArgs A) {
+  const FrameParams& fp = *fpp;
+  const uint32_t tile = blockIdx.x;
+  { uint32_t word;
+    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(word) : "s"(A.tileWords), "s"(tile * 4u) : "memory");
+    if (word == 0u) return; }
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const uint32_t px = (tile % A.tilesX) * 16 + (wave & 1u) * 8 + (lane & 7u);
+  const uint32_t py = A.rowBegin + (tile / A.tilesX) * 16 + (wave >> 1) * 8 + (lane >> 3);
+  bool want = false;
+  RayRec rr;
+  if (px < fp.W && py < A.rowEnd) {
+    const uint32_t W = fp.W, H = fp.H;
+    const size_t pix = (size_t)py * W + px;
+    uint32_t visibility = (uint32_t)A.visDepth[pix];
+    if (visibility > 0) {      // getPrimarySurface :277-333, the covered branch, as in sampleGenKernel
+      --visibility;
+      const uint32_t inst = visibility >> 24;
+      uint32_t prim = visibility & 0xFFFFFFu;
+      asm volatile("" : "+v"(prim));      // see shadeKernel
+      f2 screenPos; screenPos.x = ((float)px + 0.5f) / (float)W * 2.0f - 1.0f; screenPos.y = ((float)py + 0.5f) / (float)H * 2.0f - 1.0f;
+      screenPos.y = -screenPos.y;
+      const f3 eye = mk3(fp.rg.EyePt[0], fp.rg.EyePt[1], fp.rg.EyePt[2]);
+      const Tri3 v = getVertices(inst ? A.fat1 : A.fat0, prim);
+      const M4 wvp = cbLoad4x4(fp.g.WorldViewProjs[inst]);
+      f4 p[3];
+      for (int k = 0; k < 3; ++k) p[k] = mulPoint(v.pos[k], wvp);
+      screenPos.x -= fp.rg.ProjBias[0]; screenPos.y -= fp.rg.ProjBias[1];
+      const f2 bary = calcBarycentrics(p, screenPos);
+      const Attrib a = interpAttrib(v, bary.x, bary.y);
+      const f3 color = mk3(fp.mat.BaseColors[inst][0], fp.mat.BaseColors[inst][1], fp.mat.BaseColors[inst][2]);
+      const f2 rghMtl = getRoughMetal(fp.mat, inst, a.UV);
+      const f4 P4 = mulPoint(a.Pos, cbLoad4x3(fp.g.Worlds[inst]));
+      const f3 P = mk3(P4.x, P4.y, P4.z);
+      const f3 N = normalize3(mulDir(a.Nrm, cbLoad3x3(inst ? fp.g.WorldIT1 : fp.g.WorldITs0)));
+      const f3 V = normalize3(eye - P);
+      const f3 L = mk3(A.Lx, A.Ly, A.Lz);
+      const float NoL = dot3(N, L);
+      if (NoL > 0.0f) {
+        // F D Vis NoL E with the roughness floored at 1/32: a mirror under a delta light has no finite answer
+        const float r = fmaxf(rghMtl.x, 1.0f / 32.0f);
+        const f3 Hh = normalize3(V + L);
+        const float NoH = saturatef(dot3(N, Hh)), VoH = saturatef(dot3(V, Hh)), NoV = saturatef(dot3(N, V));
+        const float al = r * r, a2 = al * al;
+        const float d = (NoH * a2 - NoH) * NoH + 1.0f;
+        const float D = a2 / ((RT_PI * d) * d);
+        const f3 f0 = mk3(lerpf(0.04f, color.x, rghMtl.y), lerpf(0.04f, color.y, rghMtl.y), lerpf(0.04f, color.z, rghMtl.y));
+        const f3 F = fSchlick(f0, VoH);
+        const float vis = visSmith(r, NoV, NoL);
+        const float k = (D * vis) * NoL;
+        want = true;
+        rr.ox = P.x; rr.oy = P.y; rr.oz = P.z; rr.dx = L.x; rr.dy = L.y; rr.dz = L.z;
+        rr.pixel = (uint32_t)pix; rr.skip = (inst << 24) | prim;
+        rr.wx = (F.x * k) * A.Ex; rr.wy = (F.y * k) * A.Ey; rr.wz = (F.z * k) * A.Ez;
+        rr.flags = __float_as_uint(NoL);
+      }
+    }
+  }
+  const uint32_t bin = blockIdx.x * 4u + wave;
+  const unsigned long long mask = __ballot(want), below = (1ull << lane) - 1ull;
+  if (want) { const size_t k = (size_t)bin * RT_BIN_MIN + (uint32_t)__popcll(mask & below); A.rays[k] = rr; A.hits[k] = hitKey(RT_RAY_TMAX, 0xFFFFFFFFu); }
+  if (lane == 0) A.binCount[bin] = (uint32_t)__popcll(mask);
+}
+struct SunAddArgs {
+  const RayRec* rays; const HitKey* hits; const uint32_t* binCount; const uint32_t* tileWords;
+  uint32_t* reflOut; uint32_t* diffOut; float Ex, Ey, Ez;
+};
+__global__ void __launch_bounds__(256) sunAddKernel(const FrameParams* __restrict__ fpp, SunAddArgs A) {
+  const FrameParams& fp = *fpp;
+  { uint32_t word;
+    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(word) : "s"(A.tileWords), "s"(blockIdx.x * 4u) : "memory");
+    if (word == 0u) return; }
+  const uint32_t bin = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (lane >= A.binCount[bin]) return;
+  const size_t k = (size_t)bin * RT_BIN_MIN + lane;
+  if (hitKeyId(A.hits[k]) != 0xFFFFFFFFu) return;      // occluded: both words stay
+  const RayRec rr = A.rays[k];
+  const uint32_t inst = rr.skip >> 24;
+  const f3 spec = mk3(rr.wx, rr.wy, rr.wz);
+  A.reflOut[rr.pixel] = packR11G11B10F(unpackR11G11B10F(A.reflOut[rr.pixel]) + spec);
+  if (fp.mat.RoughMetals[inst][1] < 1.0f) {      // rghMtl.y < 1 is the instance's constant (launchShade); elsewhere RayTracingOut1 is a carry-over and stays
+    const float w = __uint_as_float(rr.flags) / RT_PI;
+    const f3 diff = mk3(((fp.mat.BaseColors[inst][0] * (1.0f - 0.04f)) * w) * A.Ex, ((fp.mat.BaseColors[inst][1] * (1.0f - 0.04f)) * w) * A.Ey,
+                        ((fp.mat.BaseColors[inst][2] * (1.0f - 0.04f)) * w) * A.Ez);
+    A.diffOut[rr.pixel] = packR11G11B10F(unpackR11G11B10F(A.diffOut[rr.pixel]) + diff);
+  }
+}
+int launchSun(rtggx_context* c, const FrameParams& fp, hipStream_t s) {
+  uint32_t rb, re;
+  passRows(fp, ROWS_GBUFFER, rb, re);
+  if (re <= rb) return 0;
+  const uint32_t tilesX = (fp.W + 15) / 16, tilesY = (re - rb + 15) / 16, numTiles = tilesX * tilesY;
+  if (numTiles * 4u > c->numBinsMax || !c->sunRays) { setError("rtggx_ray_trace: the sun's queue does not hold %u bins", numTiles * 4u); return -1; }
+  const InputSet& set = c->cur();
+  const rtggx_context::Sun& sun = c->sun;
+  SunGenArgs G;
+  G.visDepth = c->curVis().depth; G.fat0 = c->mesh[0].fat; G.fat1 = c->mesh[1].fat;
+  G.rays = (RayRec*)c->sunRays.get(); G.hits = (HitKey*)c->sunHits.get(); G.binCount = c->sunCount;
+  G.tileWords = c->tileWords(rb, re); G.tilesX = tilesX; G.rowBegin = rb; G.rowEnd = re;
+  G.Lx = sun.L[0]; G.Ly = sun.L[1]; G.Lz = sun.L[2]; G.Ex = sun.E[0]; G.Ey = sun.E[1]; G.Ez = sun.E[2];
+  const FrameParams* const dfp = c->dParams + c->slot;
+  launch(sunGenKernel, dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, G);
+  // the bins have RT_BIN_MIN slots whatever the frame's have: the launch is told so through the context's slot count for its duration.  Spill part 2
+  // is the main stream's (launchShade): the launches that use it are in this stream's order, and nothing beside the stream touches it
+  const TraceQueue q{(const RayRec*)c->sunRays.get(), (HitKey*)c->sunHits.get(), c->sunCount};
+  const uint32_t frameSlots = c->binSlots;
+  c->binSlots = RT_BIN_MIN;
+  const int r = launchTrace(c, fp, s, q, numTiles * 4u, true, tilesX, tilesY, c->traceGrid[3], -1, nullptr, nullptr, 2, !RT_SUN_CLOSEST);
+  c->binSlots = frameSlots;
+  if (r) return r;
+  SunAddArgs S;
+  S.rays = q.rays; S.hits = q.hits; S.binCount = q.binCount; S.tileWords = G.tileWords;
+  S.reflOut = set.rtRefl; S.diffOut = set.rtDiff; S.Ex = G.Ex; S.Ey = G.Ey; S.Ez = G.Ez;
+  launch(sunAddKernel, dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, S);
+  RT_HIP(hipGetLastError());
+  return 0;
+}
+
 // ---- test entry: closest-hit queries for an explicit ray list (through the same trace kernel) ---------------
 __global__ void fillTestQueue(const float* __restrict__ rays, uint32_t n, uint32_t binSlots, RayRec* q0, HitKey* keys, uint32_t* binCount, float2* tRange) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1251,6 +1384,28 @@ int launchTraceRays(rtggx_context* c, const FrameParams& fp, const float* dRays,
   { const int r = launchTrace(c, fp, s, q, numBins, false, 0u, 0u, chooseSliceShift(c, false, numBins), -1); c->traceRayRange = nullptr; if (r) return r; }
   hipLaunchKernelGGL(exportTestHits, dim3((n + 255) / 256), dim3(256), 0, s, c->dParams + c->slot, (const RayRec*)set.rayQueue.get(), (const HitKey*)set.hitQueue.get(), n,
                      (const float4*)c->mesh[0].fat, (const float4*)c->mesh[1].fat, dOut);
+  RT_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---- occlusion queries for an explicit ray list (rtggx_trace_occlusion): the same list path, through the any-hit variant of the trace kernel ----
+__global__ void exportOcclusion(const HitKey* __restrict__ hits, uint32_t n, uint32_t* __restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  out[i] = hitKeyId(hits[i]) != 0xFFFFFFFFu ? 1u : 0u;      // which triangle an occluded ray's key names is unspecified (rt_queue.h): only this bit leaves
+}
+int launchTraceOcclusion(rtggx_context* c, const FrameParams& fp, const float* dRays, uint32_t n, uint32_t* dOut, hipStream_t s) {
+  if (!n) return 0;
+  if (n > c->numBinsMax * c->binSlots) { setError("rtggx_trace_occlusion: at most %u rays per launch", c->numBinsMax * c->binSlots); return -1; }
+  const uint32_t numBins = (((n + c->binSlots - 1u) / c->binSlots) + 3u) & ~3u;   // whole tiles of four bins
+  const InputSet& set = c->cur();
+  RT_HIP(hipMemsetAsync(set.binCount, 0, (size_t)numBins * 4, s));
+  if (!c->testRayRange) RT_HIP(alloc(c->testRayRange, (size_t)c->numBinsMax * RT_BIN * sizeof(float2)));
+  hipLaunchKernelGGL(fillTestQueue, dim3((n + 255) / 256), dim3(256), 0, s, dRays, n, c->binSlots, (RayRec*)set.rayQueue.get(), (HitKey*)set.hitQueue.get(), set.binCount, (float2*)c->testRayRange.get());
+  c->traceRayRange = c->testRayRange;
+  const TraceQueue q{(const RayRec*)set.rayQueue.get(), (HitKey*)set.hitQueue.get(), set.binCount};
+  { const int r = launchTrace(c, fp, s, q, numBins, false, 0u, 0u, chooseSliceShift(c, false, numBins), -1, nullptr, nullptr, -1, true); c->traceRayRange = nullptr; if (r) return r; }
+  hipLaunchKernelGGL(exportOcclusion, dim3((n + 255) / 256), dim3(256), 0, s, (const HitKey*)set.hitQueue.get(), n, dOut);
   RT_HIP(hipGetLastError());
   return 0;
 }

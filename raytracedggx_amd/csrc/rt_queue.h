@@ -68,9 +68,17 @@ uint32_t chooseSliceShift(rtggx_context* c, bool countRays, uint32_t numBins);
 // set, or the list of rtggx_trace_rays).  spillPart: -1 for a frame's level-0 traversal and for a list -- the part of the stack spill area
 // given by c->traceSpillHalf, the kernel's time stamps and the ray-counter read-backs --; 0..RT_SPILL_PARTS-1 for a later level of the
 // frame's paths (rtggx_set_max_recursion_depth): that part of the spill area, and none of the rest.
+//
+// Any-hit traversal (anyHit = true; trace.hip traceKernel<.., ANY = true>).  The same queue format -- bins of RayRec, binCount, the optional
+// interval array -- and one bit of result: a slot's key is left at the (TMax, miss) it was initialised to iff no triangle other than the
+// ray's `skip` satisfies TMin < t < TMax under the traversal's own watertight test in the instance's object space.  That is by construction
+// the `valid` flag of the closest-hit kernel on the same ray (tests/test_gpu_occlusion.py rests on the equality).  If the ray is occluded,
+// WHICH triangle and t the key names is unspecified: the smallest key among the jobs that happened to reach a triangle, different from run to run.
+// A job leaves its ray at the first accepted triangle and drops its pending subtrees; its interval never shrinks.  The launch never touches
+// the level-0 traversal's cost record (binWork, split list: pass splitCap = -1), its time stamps or its counter read-backs.
 struct TraceQueue { const RayRec* rays; HitKey* hits; const uint32_t* binCount; };
 #define RT_SPILL_PARTS 3u
 int launchTrace(rtggx_context* c, const FrameParams& fp, hipStream_t s, const TraceQueue& q, uint32_t numBins, bool countRays, uint32_t tilesX, uint32_t tilesY, uint32_t sliceShift,
-                int splitCap, hipEvent_t start = nullptr, hipEvent_t stop = nullptr, int spillPart = -1);
+                int splitCap, hipEvent_t start = nullptr, hipEvent_t stop = nullptr, int spillPart = -1, bool anyHit = false);
 
 }  // namespace rt

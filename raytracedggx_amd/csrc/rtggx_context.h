@@ -276,6 +276,12 @@ struct rtggx_context {
   bool externalStream = false;
 
   bool vndf = false;             // rtggx_set_sampler
+  // rtggx_set_sun: a directional light with ray-traced shadows (raytrace.hip launchSun).  Requested values take effect with the next
+  // rtggx_render_visibility, like the other per-frame settings.  The queue is the sun's own -- the frame's bins are still read by the shading of the
+  // frame in flight, and still sky relies on their counts --: one ray slot per pixel of a bin's 8x8 sub-tile, 48 + 8 bytes per pixel and 4 per bin,
+  // allocated by the first call that turns the sun on.
+  struct Sun { bool on = false; float L[3] = {}, E[3] = {}; } sun, sunRequested;
+  rt::DevBuf<void> sunRays, sunHits; rt::DevBuf<uint32_t> sunCount;
   uint32_t rayRate = 1;          // rtggx_set_ray_rate: pixels per traced ray, 1 or 4 (raytrace.hip rayGenKernel, reconstructKernel)
   uint32_t maxDepth = 1, depthRequested = 1;      // rtggx_set_max_recursion_depth: 1..4 levels of rays per path (raytrace.hip launchShade); the frame's, the next frame's
   // rtggx_set_samples_per_pixel: 1, 2, 4 or 8 samples per covered pixel (raytrace.hip launchShade; DESIGN.md "Samples per pixel"); the
@@ -486,6 +492,7 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
 // kernel's own completion signal (hipExtLaunchKernelGGL) instead of a marker packet behind it: a marker costs its queue
 // 5-7 us, and the frame's two chains had four of them (rocprofv3 kernel trace, profiles/).
 int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent_t done = nullptr);      // hit / miss shading of the traced bins
+int launchSun(rtggx_context* c, const FrameParams& fp, hipStream_t s);      // rtggx_set_sun: shadow rays from the primary surface, the any-hit traversal, the add into RayTracingOut0/1
 int launchReconstruct(rtggx_context* c, const FrameParams& fp, hipStream_t s);      // rate 4: the untraced pixels of RayTracingOut0/1, after the hit shading
 int allocSamples(rtggx_context* c);      // what N > 1 samples per pixel need (rtggx_context::sppAcc, sppParams), once
 int allocAccumulation(rtggx_context* c);      // what rtggx_set_accumulation needs (rtggx_context::accRefl, accDiff, converged), once
@@ -497,6 +504,7 @@ int launchPresentAccumulation(rtggx_context* c, hipStream_t s);      // RTGGX_BU
 int launchScore(rtggx_context* c, const FrameParams& fp, hipStream_t s);      // the frame's record into slot scoreIndex % RTGGX_SCORE_RING: two kernels
 int launchReferenceFromAccumulation(rtggx_context* c, hipStream_t s);      // rtggx_context::reference = the mean image of the sums and accumFrames
 int launchTraceRays(rtggx_context* c, const FrameParams& fp, const float* dRays, uint32_t n, float* dOut, hipStream_t s);
+int launchTraceOcclusion(rtggx_context* c, const FrameParams& fp, const float* dRays, uint32_t n, uint32_t* dOut, hipStream_t s);      // the same list through the any-hit traversal (rt_queue.h)
 int launchDebugEnvironment(rtggx_context* c, const float* dDirs, const float* dLevels, uint32_t n, int level0, float* dOut, hipStream_t s);      // rtggx_debug_environment: reads the environment only
 int resetSettled(rtggx_context* c);      // both arrays of settled words: blocks 0, border RT_SETTLED_BORDER (context.hip; null stream, the caller has synchronised)
 int launchDenoise(rtggx_context* c, const FrameParams& fp, int useLds, hipStream_t s, hipEvent_t done = nullptr, bool fuseToneMap = false);      // fuseToneMap: the last kernel also writes the back buffer

@@ -111,7 +111,14 @@ typedef __attribute__((address_space(3))) int32_t LdsInt;
 typedef __attribute__((address_space(3))) uint32_t LdsUint;
 typedef float __attribute__((ext_vector_type(4))) NativeFloat4;      // float4 is a class: it has no copy from another address space
 typedef __attribute__((address_space(3))) NativeFloat4 LdsFloat4;
-template <int TOP> __device__ __forceinline__ void traceItem(const FrameParams& fp, const TraceArgs& A, LdsInt* const stackMem, LdsUint* const victimMem, const LdsFloat4* const topMem, const uint32_t item, const uint32_t waveSlot) {
+// ANY = true: the any-hit variant (rt_queue.h "Any-hit traversal").  The same walk, the same boxes, the same watertight test; what differs
+// is what happens at an accepted triangle: the job writes the ray's key and ENDS, dropping whatever its stack still holds (LDS or spilled:
+// the entries are the wave's own scratch, nothing has to be drained), and a primary job that found its ray occluded in instance 0 does not
+// enter instance 1.  A job's interval therefore never shrinks (myT stays the ray's TMax while the job lives), and a helper never inherits a
+// hit.  Subtrees that helpers took before the hit are walked to their own first hit or to their end: nobody waits for anybody, nobody polls
+// the key, the nearer child still goes first (both measured: profiles/r14_b_anyhit_kernel_times.txt), and the key is (TMax, miss) at the
+// kernel's end iff no job accepted a triangle -- whatever the order.
+template <int TOP, bool ANY> __device__ __forceinline__ void traceItem(const FrameParams& fp, const TraceArgs& A, LdsInt* const stackMem, LdsUint* const victimMem, const LdsFloat4* const topMem, const uint32_t item, const uint32_t waveSlot) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = (item >> 3) & 3u, vblock = ((item >> 5) << 3) | (item & 7u), ldsWave = threadIdx.x >> 6;
   // Workgroup -> tile.  Consecutive workgroup ids go round-robin to the 8 XCDs, each with its own L2; handing every
@@ -204,6 +211,9 @@ template <int TOP> __device__ __forceinline__ void traceItem(const FrameParams& 
   int sp = 0, sb = 0;                                // my stack holds entries [sb, sp)
   // job state: the primary job of my own ray (none for a degenerate interval: the key stays a miss)
   bool job = hasRay && bestT > tmin, helper = false;
+  // a ray found occluded in instance 0 by its own primary job is done.  (One found occluded there by a HELPER is not known to be: reading the ray's key
+  // here to find out was measured and made the kernel no faster -- one more dependent load per ray; profiles/r14_b_anyhit_kernel_times.txt.)
+  if constexpr (ANY) job = job && bestId == 0xFFFFFFFFu;
   uint32_t owner = slot;                             // the ray slot whose key this job's hits go to
   float myT = bestT; uint32_t myId = bestId;         // the best hit of the job in hand (a helper's: its victim's, then its own)
 
@@ -333,7 +343,10 @@ template <int TOP> __device__ __forceinline__ void traceItem(const FrameParams& 
 #ifdef RT_TRACE_STATS
           ++stLeaf;
 #endif
-          popOrFinish();
+          if constexpr (ANY) {
+            if (myId != 0xFFFFFFFFu) { sp = sb = 0; job = false; finished = true; }      // occluded (a living job's myId is a miss until now): the rest of its stack is dropped
+            else popOrFinish();
+          } else popOrFinish();
         }
       }
     }
@@ -384,7 +397,8 @@ template <int TOP> __device__ __forceinline__ void traceItem(const FrameParams& 
 
 // WAVES waves per workgroup; PER_SIMD: the waves per SIMD the register allocation has to leave room for (launchTrace's variants)
 // TOP = 0: no table in LDS (launchTrace passes topCount0 = topCount1 = 0 to such a variant)
-template <int WAVES, int PER_SIMD, int TOP> __global__ void __launch_bounds__(64 * WAVES, PER_SIMD) traceKernel(const FrameParams* __restrict__ fpp, TraceArgs A) {
+// ANY: the any-hit variant (traceItem)
+template <int WAVES, int PER_SIMD, int TOP, bool ANY> __global__ void __launch_bounds__(64 * WAVES, PER_SIMD) traceKernel(const FrameParams* __restrict__ fpp, TraceArgs A) {
   __shared__ TraceLds<WAVES, TOP> lds;
   // the tables: Bvh4Node records (8 x float4, the last one padding) -> field-major
   if (TOP) for (uint32_t i = threadIdx.x; i < A.topCount0 * 8u; i += 64u * WAVES) { const uint32_t k = i >> 3, f = i & 7u; if (f < RT_TOP_FIELDS) lds.top[f * RT_TOP_NODES + k] = A.top0[i]; }
@@ -413,7 +427,7 @@ template <int WAVES, int PER_SIMD, int TOP> __global__ void __launch_bounds__(64
     j = (uint32_t)__builtin_amdgcn_readfirstlane((int)j);
     const uint32_t item = ((blockIdx.x >> 3) + j * groupsPerXcd) * 8u + xcd;
     if (j >= 0x1000000u || item >= A.totalItems) break;
-    traceItem<TOP>(*fpp, A, (LdsInt*)lds.stack, (LdsUint*)lds.victims, (const LdsFloat4*)lds.top, item, blockIdx.x * (uint32_t)WAVES + (threadIdx.x >> 6));
+    traceItem<TOP, ANY>(*fpp, A, (LdsInt*)lds.stack, (LdsUint*)lds.victims, (const LdsFloat4*)lds.top, item, blockIdx.x * (uint32_t)WAVES + (threadIdx.x >> 6));
   }
   // the last wave of the workgroup to leave stamps the end (no barrier: a wave that is done gives its slot back at once)
   if ((threadIdx.x & 63u) == 0u && A.stamps != nullptr && atomicAdd(&lds.done, 1u) == (uint32_t)WAVES - 1u) atomicMax(A.stamps + 2u * (A.launch % 3u) + 1u, wall_clock64());
@@ -475,10 +489,11 @@ uint32_t chooseSliceShift(rtggx_context* c, bool countRays, uint32_t numBins) {
 }
 
 int launchTrace(rtggx_context* c, const FrameParams& fp, hipStream_t s, const TraceQueue& q, uint32_t numBins, bool countRays, uint32_t tilesX, uint32_t tilesY, uint32_t sliceShift,
-                int splitCap, hipEvent_t start, hipEvent_t stop, int spillPart) {
+                int splitCap, hipEvent_t start, hipEvent_t stop, int spillPart, bool anyHit) {
   const bool deeper = spillPart >= 0;      // a later level of the frame's paths: shares no per-launch state with the next frame's level 0 (rt_queue.h)
   TraceArgs T;
   if (numBins == 0) return 0;
+  if (anyHit && tilesX != 0u && !deeper) { setError("launchTrace: an any-hit launch inside a frame names its part of the spill area"); return -1; }      // (the level-0 part belongs to stream B's traversal)
   if (numBins > c->numBinsMax) { setError("launchTrace: %u bins exceed the %u allocated", numBins, c->numBinsMax); return -1; }
   const bool have0 = c->mesh[0].tris != nullptr, have1 = c->mesh[1].tris != nullptr;
   // a mesh with one triangle has no internal nodes; an absent mesh has nothing: point those bases at the dummy record
@@ -511,7 +526,7 @@ int launchTrace(rtggx_context* c, const FrameParams& fp, hipStream_t s, const Tr
 #endif
   T.tilesX = tilesX; T.tilesY = tilesY; T.tileWords = tilesX ? c->traceTileWords : nullptr;
   T.sliceShift = sliceShift;
-  const bool adaptive = splitCap >= 0 && sliceShift == 0u && tilesX != 0u;
+  const bool adaptive = splitCap >= 0 && sliceShift == 0u && tilesX != 0u && !anyHit;      // (an any-hit launch leaves the cost record alone)
   T.splitList = c->cur().splitList; T.splitCount = c->cur().splitCount;
   T.binWork = adaptive ? c->binWork : nullptr; T.splitBlocks = adaptive ? (uint32_t)splitCap / 4u : 0u;
   const uint32_t superTiles = ((tilesX + 7u) / 8u) * ((tilesY + 7u) / 8u);
@@ -531,7 +546,7 @@ int launchTrace(rtggx_context* c, const FrameParams& fp, hipStream_t s, const Tr
   const uint32_t perCu = waves == 1u ? RT_SPILL_WAVES / 256u : 1u;      // single-wave workgroups: one per item, the dispatcher deals them -- up to RT_SPILL_WAVES of them (three times the
                                                                          // wave slots the chip offers this kernel); beyond that they take a second item, a third, ... (the loop in the kernel)
   if (waves == 1u) T.topCount0 = T.topCount1 = 0u;
-  T.stamps = waves == 1u || deeper ? nullptr : c->traceStamps; T.launch = deeper ? 0u : c->traceStampLaunch++;      // (thousands of workgroups stamping one word would take longer than the launch)
+  T.stamps = waves == 1u || deeper || anyHit ? nullptr : c->traceStamps; T.launch = deeper || anyHit ? 0u : c->traceStampLaunch++;      // (thousands of workgroups stamping one word would take longer than the launch)
   // as many workgroups as stay resident, a multiple of 8 so that every XCD gets its share; fewer when there is less to do
   const uint32_t wanted = (T.totalItems + waves - 1u) / waves;
   uint32_t blocks = c->numCUs * perCu < wanted ? c->numCUs * perCu : wanted;
@@ -539,11 +554,11 @@ int launchTrace(rtggx_context* c, const FrameParams& fp, hipStream_t s, const Tr
   if (blocks * waves > RT_SPILL_WAVES) blocks = (RT_SPILL_WAVES / waves) & ~7u;      // (every wave of the launch owns a piece of the spill area)
   void (*kernel)(const FrameParams*, TraceArgs);
   switch (waves) {
-    case 1u: kernel = traceKernel<1, 5, 0>; break;
-    case 10u: kernel = traceKernel<10, 4, 1>; break;
-    case 12u: kernel = traceKernel<12, 4, 1>; break;
-    case 14u: kernel = traceKernel<14, 4, 1>; break;
-    case 16u: kernel = traceKernel<16, 4, 1>; break;
+    case 1u: kernel = anyHit ? traceKernel<1, 5, 0, true> : traceKernel<1, 5, 0, false>; break;
+    case 10u: kernel = anyHit ? traceKernel<10, 4, 1, true> : traceKernel<10, 4, 1, false>; break;
+    case 12u: kernel = anyHit ? traceKernel<12, 4, 1, true> : traceKernel<12, 4, 1, false>; break;
+    case 14u: kernel = anyHit ? traceKernel<14, 4, 1, true> : traceKernel<14, 4, 1, false>; break;
+    case 16u: kernel = anyHit ? traceKernel<16, 4, 1, true> : traceKernel<16, 4, 1, false>; break;
     default: setError("launchTrace: no kernel variant with %u waves", waves); return -1;
   }
   launch(kernel, dim3(blocks), dim3(64 * waves), s, start, stop, c->dParams + c->slot, T);

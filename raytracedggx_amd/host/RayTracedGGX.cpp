@@ -35,6 +35,7 @@ void RayTracedGGX::OnInit() {
   if (m_hasMetallicOverride) for (uint32_t i = 0; i < RayTracer::NUM_MESH; ++i) m_rayTracer->SetMetallic(i, m_metallics[i]);
   if (m_vndf) m_rayTracer->SetSampler(true);            // -vndf: visible-normal sampling of the reflection lobe (opt-in; the reference samples the NDF)
   if (m_rayRate != 1u && !m_rayTracer->SetRayRate(m_rayRate)) throw std::runtime_error("-rayrate: " + m_rayTracer->GetLastError());      // -rayrate 4: one ray per 2x2 quad (opt-in)
+  if (m_hasSun && !m_rayTracer->SetSun(m_sun, m_sun + 3)) throw std::runtime_error("-sun: " + m_rayTracer->GetLastError());      // -sun: a directional light with ray-traced shadows (opt-in)
   if (m_recursionDepth != 1u && !m_rayTracer->SetMaxRecursionDepth(m_recursionDepth)) throw std::runtime_error("-recursion: " + m_rayTracer->GetLastError());      // -recursion N: multi-bounce paths (opt-in)
   if (m_samplesPerPixel != 1u && !m_rayTracer->SetSamplesPerPixel(m_samplesPerPixel)) throw std::runtime_error("-spp: " + m_rayTracer->GetLastError());      // -spp N: multi-sample tracing (opt-in)
   if (m_sampleSet != RTGGX_MIN_SAMPLE_SET && !m_rayTracer->SetSampleSetSize(m_sampleSet)) throw std::runtime_error("-sampleset: " + m_rayTracer->GetLastError());      // -sampleset M: a larger sample set (opt-in)
@@ -206,7 +207,7 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
     return (arg[0] == '-' || arg[0] == '/') && lower(arg + 1) == lower(name);
   };
   // On POSIX an absolute path also starts with '/': such a token is a flag only when it names one.
-  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "recursion", "spp", "accumulate", "sampleset", "savereference", "reference", "score", "envlayout", "envsize", "envmips", "envprefilter"};
+  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "sun", "recursion", "spp", "accumulate", "sampleset", "savereference", "reference", "score", "envlayout", "envsize", "envmips", "envprefilter"};
   const auto isFlagName = [&](const char* name) { for (const char* f : kFlags) if (lower(name) == f) return true; return false; };
   const auto hasNextArgValue = [&](int i) {
     if (i + 1 >= argc) return false;
@@ -248,6 +249,17 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
     else if (isArgMatched(i, "sharedmem")) m_useSharedMem = true;
     else if (isArgMatched(i, "sync")) m_asyncCompute = 0;
     else if (isArgMatched(i, "vndf")) m_vndf = true;
+    // -sun <x> <y> <z> <r> <g> <b>: a directional light toward (x, y, z) with irradiance (r, g, b) and ray-traced shadows (rtggx_set_sun); the
+    // six numbers are checked here, before a device is asked for
+    else if (isArgMatched(i, "sun")) {
+      int got = 0;
+      for (; got < 6 && hasNextArgValue(i); ++got) { char* end = nullptr; m_sun[got] = std::strtof(argv[++i], &end); if (end == argv[i] || *end != '\0') throw std::runtime_error("-sun: six numbers, a direction toward the sun and an irradiance"); }
+      if (got != 6) throw std::runtime_error("-sun: six numbers, a direction toward the sun and an irradiance");
+      const double len = std::sqrt((double)m_sun[0] * m_sun[0] + (double)m_sun[1] * m_sun[1] + (double)m_sun[2] * m_sun[2]);
+      if (!std::isfinite(len) || !(len > 0.0)) throw std::runtime_error("-sun: a direction of finite, non-zero length");
+      for (int k = 3; k < 6; ++k) if (!std::isfinite(m_sun[k]) || m_sun[k] < 0.0f) throw std::runtime_error("-sun: an irradiance that is finite and not negative");
+      m_hasSun = true;
+    }
     else if (isArgMatched(i, "rayrate")) {
       const int rate = hasNextArgValue(i) ? std::atoi(argv[++i]) : 0;
       if (rate != 1 && rate != 4) throw std::runtime_error("-rayrate: 1 or 4 pixels per traced ray");
@@ -302,6 +314,7 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
   if (!m_referenceFile.empty()) { std::string why; if (!ReadPfm(m_referenceFile.c_str(), m_width, m_height, m_referenceImage, why)) throw std::runtime_error("-reference: " + why); }
   // quarter-rate tracing renders whole frames only (rtggx_set_ray_rate): refused here, before anything has touched a GPU
   // one knob asks for fewer rays, the other for more (rtggx_set_samples_per_pixel)
+  if (m_rayRate != 1u && m_hasSun) throw std::runtime_error("-sun together with -rayrate 4: refused");
   if (m_rayRate != 1u && m_samplesPerPixel != 1u) throw std::runtime_error("-spp N > 1 together with -rayrate 4: refused");
   if (m_rayRate != 1u && (m_gpus > 1 || m_strips > 1)) throw std::runtime_error("-rayrate 4: whole frames only, not with -gpus N > 1 or -strips N > 1");
 }
