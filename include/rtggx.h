@@ -619,8 +619,41 @@ int  rtggx_trace_occlusion(rtggx_context* ctx, const float* rays, uint32_t n, ui
  * depth, sample count, sample set and sample map -- one shadow ray per covered, sun-facing pixel per frame, counted by rtggx_ray_count.
  * Background pixels are untouched.  Setting the sun ends no still-sky run and resets no accumulation (the caller's to do).
  * Known limit: surfaces seen in reflections are shaded by the environment and the SH irradiance alone -- a reflection shows the ground
- * without its sun term and without the shadow.  Memory: 56 bytes per pixel and 4 per 8x8 block, from the first call that turns it on. */
+ * without its sun term and without the shadow.  rtggx_set_sun_reflections(ctx, 1) lifts the limit.  Memory: 56 bytes per pixel and 4 per
+ * 8x8 block, from the first call that turns it on. */
 int  rtggx_set_sun(rtggx_context* ctx, const float direction[3], const float irradiance[3]);
+
+/* The sun at the surfaces the paths hit: every surface seen in a reflection (or by a diffuse ray), at every recursion level, gets the sun's
+ * term and its shadow.  enable: 0 (the default) or 1; anything else is refused and the setting kept.  The setting is stored whether or not a
+ * sun is set and does something only in frames where the sun is on (so never at ray rate 4, which the sun excludes); it takes effect with
+ * the next rtggx_render_visibility.  Opt-in: a context that never asks for it allocates and launches exactly what it did.
+ * A path of recursion depth D: its level-d ray (o, dir) carries the throughput T_d, T_0 = w0, T_{d+1} = T_d w_{d+1} -- the weight of the ray's
+ * record, as the hit shading reads it.  The ray TOUCHES A SURFACE when it hits and is not a reflection-group ray whose preset is <= 0 in every
+ * component (that one returns the preset without looking at the surface).  For such a ray, with the hit derived exactly as the hit shading
+ * derives it -- triangle from the hit id, barycentrics from the repeated watertight test, N, (r, m), color, V = -dir, P = o + t dir per
+ * component --, in fp32 without contraction, each operation rounded on its own:
+ *   1. NoL = dot(N, L); NoL <= 0: no shadow ray, no term;
+ *   2. a shadow ray from P along L, interval (1e-5, 10000), skipping the hit's (inst, prim), through the any-hit traversal; occluded: no term.
+ *      rtggx_ray_count / rtggx_ray_total count it;
+ *   3. the lobe the path uses at that surface.  m > 0.5: step 4 of rtggx_set_sun with this hit's N, V, (r, m), color: term_c = (F_c k) E_c.
+ *      Otherwise color' = color (1 - m) for a diffuse-group ray, color for a reflection-group ray; term_c = (color'_c (NoL / pi)) E_c (no
+ *      x 0.96: the rule of the hit shading at depth >= 1);
+ *   4. s_d = T_d term, per component.
+ * One sample per pixel: per (pixel, image the path writes) S = +0, then S = S + s_d for d ascending over the levels that have a term; behind
+ * the last shading pass word = pack(unpack(word) + S) where at least one term exists, the word untouched bit for bit where none does.  N > 1
+ * samples, with or without a sample map: the terms go into the pixel's fp32 sums -- sample after sample, levels ascending, at level d
+ * acc = acc + s_d first and then the value of a path that ends at level d; the resolve and its 1 / c scale are unchanged, and a block that
+ * has had its c samples traces no shadow ray.  No atomics: at most one live path exists per (pixel, image) and pass, and the order of every
+ * sum is the order of the launches.  The pass of rtggx_set_sun still runs afterwards, unchanged, on the packed words.  Background pixels
+ * get no term; where the pixel's metallic is >= 1 RayTracingOut1 gets none (no path writes it).  The rule is independent of sampler,
+ * sample-set size and stream placement.
+ * Per level and sample three more kernels in front of the hit shading pass (one generating the shadow rays from the level's hits, the
+ * any-hit traversal, one adding the unoccluded terms), and one more behind the last pass of a one-sample frame.  Memory, from the first
+ * frame that has both the sun and this on: a queue of the frame's bin size -- 56 bytes per ray slot, i.e. 56 bytes per pixel while both
+ * materials are fully metallic and 112 from the first metallic below 1 -- and 4 bytes per 8x8 block; a one-sample frame adds S, 32 bytes
+ * per pixel (two images of r, g, b and the number of terms).  S is all zero between frames: the pass that adds it to the words clears what it
+ * found set. */
+int  rtggx_set_sun_reflections(rtggx_context* ctx, int enable);
 
 #ifdef __cplusplus
 }

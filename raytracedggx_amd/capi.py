@@ -40,7 +40,7 @@ EXPORTS = ["rtggx_last_error", "rtggx_create", "rtggx_destroy", "rtggx_set_strip
            "rtggx_set_accumulation", "rtggx_reset_accumulation", "rtggx_accumulated_frames", "rtggx_present_accumulation", "rtggx_set_sample_set",
            "rtggx_set_reference", "rtggx_reference_from_accumulation", "rtggx_set_scoring", "rtggx_read_scores",
            "rtggx_set_env_image", "rtggx_generate_env_mips", "rtggx_prefilter_env",
-           "rtggx_set_sample_map", "rtggx_read_sample_map", "rtggx_trace_occlusion", "rtggx_set_sun"]
+           "rtggx_set_sample_map", "rtggx_read_sample_map", "rtggx_trace_occlusion", "rtggx_set_sun", "rtggx_set_sun_reflections"]
 SCORE_RING = 256
 
 
@@ -125,6 +125,7 @@ def load():
     L.rtggx_trace_rays.argtypes = [vp, vp, C.c_uint32, vp]
     L.rtggx_trace_occlusion.argtypes = [vp, vp, C.c_uint32, vp]
     L.rtggx_set_sun.argtypes = [vp, vp, vp]
+    L.rtggx_set_sun_reflections.argtypes = [vp, C.c_int]
     L.rtggx_ray_total.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
     L.rtggx_kernel_times.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
     _lib = L
@@ -580,6 +581,10 @@ class Context:
             return self._check(self.L.rtggx_set_sun(self.h, None, None))
         d, e = np.ascontiguousarray(direction, np.float32).reshape(3), np.ascontiguousarray(irradiance, np.float32).reshape(3)
         self._check(self.L.rtggx_set_sun(self.h, _p(d), _p(e)))
+
+    def set_sun_reflections(self, on):
+        """The sun term and the shadow at the surfaces the paths hit as well (0 / 1), from the next frame on; it acts only while a sun is set."""
+        self._check(self.L.rtggx_set_sun_reflections(self.h, int(on)))
 
     def trace_occlusion(self, rays):
         """One bool per ray {o.xyz, d.xyz, tmin, tmax}: is there a triangle with tmin < t < tmax (the any-hit traversal)."""

@@ -265,7 +265,7 @@ int rtggx_set_stream(rtggx_context* c, void* stream) {
   RT_HIP(syncStreams(c));
   if (stream) { c->streamMain = (hipStream_t)stream; c->externalStream = true; }
   else { c->streamMain = c->ownMain; c->externalStream = false; }
-  c->sppStream = nullptr;      // (everything has ended; the stream given up may not outlive this call)
+  c->sppStream = nullptr; c->sunHitStream = nullptr;      // (everything has ended; the stream given up may not outlive this call)
   if (!c->asyncCompute) c->streamAS = c->streamMain;
   return 0;
 }
@@ -342,7 +342,7 @@ int rtggx_set_async_compute(rtggx_context* c, int enable) {
   RT_CHECK_CTX(c);
   if ((enable != 0) == c->asyncCompute) return 0;
   RT_HIP(syncStreams(c));
-  c->asyncCompute = enable != 0; c->sppStream = nullptr;
+  c->asyncCompute = enable != 0; c->sppStream = nullptr; c->sunHitStream = nullptr;
   c->streamAS = c->asyncCompute ? c->ownAS : c->streamMain;
   c->streamVis = c->asyncCompute ? c->ownVis : nullptr;
   c->evVisStream = nullptr; for (auto& f : c->frames) f.genFrame = 0u;
@@ -444,6 +444,15 @@ int rtggx_set_sun(rtggx_context* c, const float direction[3], const float irradi
   sun.L[0] = (float)(x / len); sun.L[1] = (float)(y / len); sun.L[2] = (float)(z / len);
   for (int k = 0; k < 3; ++k) sun.E[k] = irradiance[k];
   c->sunRequested = sun;
+  return 0;
+}
+// The sun at the surfaces the paths hit (include/rtggx.h).  Only the value is kept: it is stored whether or not a sun is set, allocates nothing
+// here (the first frame that has both on does: raytrace.hip allocSunHits) and takes effect with the next rtggx_render_visibility.  No
+// synchronisation, no end of a still-sky run, no reset of an accumulation, as for the sun itself.
+int rtggx_set_sun_reflections(rtggx_context* c, int enable) {
+  RT_CHECK_CTX(c);
+  if (enable != 0 && enable != 1) { setError("rtggx_set_sun_reflections: %d: 0 or 1", enable); return -1; }
+  c->sunReflectionsRequested = enable == 1;
   return 0;
 }
 // Sums and count back to zero: two clears on the main stream, behind the frames it holds and in front of the next one; nothing waits.

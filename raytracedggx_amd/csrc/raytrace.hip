@@ -1082,6 +1082,186 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
   return 0;
 }
 
+// ---- the sun at the surfaces the paths hit (rtggx_set_sun_reflections; include/rtggx.h has the rule) ---------------------
+// In front of EVERY level's shading pass, on the stream that shades: a spawning pass compacts the next level's rays into the bin in place, so
+// the hits are read first.  sunHitGenKernel walks the wave's bin as shadeKernel does, derives each touched hit as shadeKernel does, and where
+// the surface faces the sun compacts one shadow ray into the same bin of a queue of the feature's own: origin the hit point, direction L,
+// skip the hit triangle, weight the finished term s_d = T_d * term, flags the image the path writes.  The any-hit traversal leaves an
+// unoccluded ray's key a miss; sunHitAddKernel adds such a ray's weight to the pixel's sum -- S (one sample: sunHitSums, resolved into the
+// packed words behind the last shading pass by sunHitResolveKernel) or the sample sums resolveSamplesKernel packs (N > 1).  A pass holds at
+// most one live path per (pixel, image): no two lanes meet, no atomics, and the order of a sum is the order of the launches on the stream.
+struct SunHitGenArgs {
+  const RayRec* rays; const HitKey* hits; const uint32_t* binCount; uint32_t binSlots;      // the frame's bins, this level's rays and their hits
+  const float4* fat0; const float4* fat1;
+  RayRec* outRays; HitKey* outHits; uint32_t* outCount;                                     // the feature's queue: the same bins, binSlots slots each
+  const uint32_t* tileWords;
+  float Lx, Ly, Lz, Ex, Ey, Ez;
+};
+__global__ void __launch_bounds__(256) sunHitGenKernel(const FrameParams* __restrict__ fpp, SunHitGenArgs A) {
+  const FrameParams& fp = *fpp;
+  const uint32_t tile = blockIdx.x;
+  { uint32_t word;
+    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(word) : "s"(A.tileWords), "s"(tile * 4u) : "memory");
+    if (word == 0u) return; }
+  const uint32_t bin = tile * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  const uint32_t count = RT_SGPR(min(A.binCount[bin] & 0xFFu, A.binSlots));
+  const f3 L = mk3(A.Lx, A.Ly, A.Lz);
+  uint32_t written = 0u;      // shadow rays in the front of the bin so far: never more than the records read (a bin of 128 takes two rounds)
+  for (uint32_t base = 0u; base < count; base += 64u) {
+    const uint32_t i = base + lane;
+    bool want = false;
+    RayRec sr;
+    if (i < count) {
+      const size_t slot = (size_t)bin * A.binSlots + i;
+      const float4* rp = reinterpret_cast<const float4*>(A.rays + slot);
+      const float4 q0 = rp[0], q1 = rp[1], q2 = rp[2];
+      const uint32_t pixel = __float_as_uint(q1.z), skip = __float_as_uint(q1.w), flags = __float_as_uint(q2.w);
+      const uint32_t hitId = hitKeyId(A.hits[slot]);
+      const bool diffuseGroup = (flags & 1u) != 0u;
+      const uint32_t srcInst = skip >> 24;
+      // the ray touches a surface: it hits, and it is not a reflection-group ray whose preset is <= 0 (shadeKernel: :573 returns the preset)
+      const float m = fp.mat.RoughMetals[srcInst][1];
+      const bool presetReturn = !diffuseGroup && fp.mat.BaseColors[srcInst][0] * m <= 0.0f && fp.mat.BaseColors[srcInst][1] * m <= 0.0f && fp.mat.BaseColors[srcInst][2] * m <= 0.0f;
+      if (hitId != 0xFFFFFFFFu && !presetReturn) {
+        const uint32_t hInst = hitId >> 24;
+        uint32_t hPrim = hitId & 0xFFFFFFu;
+        asm volatile("" : "+v"(hPrim));      // see shadeKernel
+        const Tri3 v = getVertices(hInst ? A.fat1 : A.fat0, hPrim);
+        float ht, hb1 = 0.0f, hb2 = 0.0f;
+        woopTestVerts(toObject(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, hInst ? fp.invWorld[1] : fp.invWorld[0]), v.pos[0], v.pos[1], v.pos[2], ht, hb1, hb2);
+        const Attrib a = interpAttrib(v, hb1, hb2);
+        const f3 N = normalize3(mulDir(a.Nrm, cbLoad3x3(hInst ? fp.g.WorldIT1 : fp.g.WorldITs0)));
+        const float NoL = dot3(N, L);
+        if (NoL > 0.0f) {
+          const f2 rm = getRoughMetal(fp.mat, hInst, a.UV);
+          f3 color = mk3(fp.mat.BaseColors[hInst][0], fp.mat.BaseColors[hInst][1], fp.mat.BaseColors[hInst][2]);
+          const f3 V = mk3(-q0.w, -q1.x, -q1.y);
+          f3 term;
+          if (rm.y > 0.5f) {      // the lobe the path uses at this surface: the specular term of the primary sun pass (sunGenKernel)
+            const float r = fmaxf(rm.x, 1.0f / 32.0f);
+            const f3 Hh = normalize3(V + L);
+            const float NoH = saturatef(dot3(N, Hh)), VoH = saturatef(dot3(V, Hh)), NoV = saturatef(dot3(N, V));
+            const float al = r * r, a2 = al * al;
+            const float d = (NoH * a2 - NoH) * NoH + 1.0f;
+            const float D = a2 / ((RT_PI * d) * d);
+            const f3 f0 = mk3(lerpf(0.04f, color.x, rm.y), lerpf(0.04f, color.y, rm.y), lerpf(0.04f, color.z, rm.y));
+            const f3 F = fSchlick(f0, VoH);
+            const float vis = visSmith(r, NoV, NoL);
+            const float k = (D * vis) * NoL;
+            term = mk3((F.x * k) * A.Ex, (F.y * k) * A.Ey, (F.z * k) * A.Ez);
+          } else {
+            if (diffuseGroup) color = color * (1.0f - rm.y);                 // :607
+            const float w = NoL / RT_PI;
+            term = mk3((color.x * w) * A.Ex, (color.y * w) * A.Ey, (color.z * w) * A.Ez);      // no x (1 - 0.04) at depth >= 1 (:532)
+          }
+          want = true;
+          sr.ox = q0.x + ht * q0.w; sr.oy = q0.y + ht * q1.x; sr.oz = q0.z + ht * q1.y;      // hitWorldPosition :338-341
+          sr.dx = L.x; sr.dy = L.y; sr.dz = L.z;
+          sr.pixel = pixel; sr.skip = hitId;
+          sr.wx = q2.x * term.x; sr.wy = q2.y * term.y; sr.wz = q2.z * term.z;             // s_d = T_d * term
+          sr.flags = (flags ^ (flags >> 1)) & 1u;                                          // the image the path writes (1: RayTracingOut1)
+        }
+      }
+    }
+    const unsigned long long mask = __ballot(want);
+    if (want) {
+      const size_t k = (size_t)bin * A.binSlots + written + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+      A.outRays[k] = sr; A.outHits[k] = hitKey(RT_RAY_TMAX, 0xFFFFFFFFu);
+    }
+    written += (uint32_t)__popcll(mask);
+  }
+  if (lane == 0u) A.outCount[bin] = written;
+}
+// One lane per slot.  SAMPLES: the sums are the sample sums (three floats per pixel and image); else S, four: the terms and their number.
+struct SunHitAddArgs {
+  const RayRec* rays; const HitKey* hits; const uint32_t* binCount; uint32_t binSlots; const uint32_t* tileWords;
+  float* sumRefl; float* sumDiff;
+};
+template <bool SAMPLES>
+__global__ void __launch_bounds__(256) sunHitAddKernel(SunHitAddArgs A) {
+  { uint32_t word;
+    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(word) : "s"(A.tileWords), "s"(blockIdx.x * 4u) : "memory");
+    if (word == 0u) return; }
+  const uint32_t bin = blockIdx.x * 4u + (threadIdx.x >> 6);
+  const uint32_t count = min(A.binCount[bin], A.binSlots);
+  for (uint32_t i = threadIdx.x & 63u; i < count; i += 64u) {
+    const size_t k = (size_t)bin * A.binSlots + i;
+    if (hitKeyId(A.hits[k]) != 0xFFFFFFFFu) continue;      // occluded: no term
+    const RayRec rr = A.rays[k];
+    float* const sum = (rr.flags & 1u) != 0u ? A.sumDiff : A.sumRefl;
+    if constexpr (SAMPLES) {
+      float* acc = sum + 3u * (size_t)rr.pixel;
+      acc[0] = acc[0] + rr.wx; acc[1] = acc[1] + rr.wy; acc[2] = acc[2] + rr.wz;
+    } else {
+      float4* acc = reinterpret_cast<float4*>(sum) + rr.pixel;
+      const float4 s = *acc;
+      *acc = make_float4(s.x + rr.wx, s.y + rr.wy, s.z + rr.wz, s.w + 1.0f);
+    }
+  }
+}
+// One sample per pixel, behind the last shading pass: word = pack(unpack(word) + S) where a term exists (S.w: their number), the word
+// untouched where none does; S is left zero for the next frame by the lanes that found it set.
+struct SunHitResolveArgs { float4* sumRefl; float4* sumDiff; uint32_t* reflOut; uint32_t* diffOut; const uint32_t* tileWords; uint32_t tilesX, rowBegin, rowEnd; };
+__global__ void __launch_bounds__(256) sunHitResolveKernel(const FrameParams* __restrict__ fpp, SunHitResolveArgs A) {
+  const FrameParams& fp = *fpp;
+  const uint32_t tile = blockIdx.x;
+  { uint32_t word;
+    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(word) : "s"(A.tileWords), "s"(tile * 4u) : "memory");
+    if (word == 0u) return; }
+  const uint32_t px = (tile % A.tilesX) * 16u + (threadIdx.x & 15u), py = A.rowBegin + (tile / A.tilesX) * 16u + (threadIdx.x >> 4);
+  if (px >= fp.W || py >= A.rowEnd) return;
+  const size_t pix = (size_t)py * fp.W + px;
+  const float4 r = A.sumRefl[pix], d = A.sumDiff[pix];
+  if (r.w != 0.0f) { A.reflOut[pix] = packR11G11B10F(unpackR11G11B10F(A.reflOut[pix]) + mk3(r.x, r.y, r.z)); A.sumRefl[pix] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
+  if (d.w != 0.0f) { A.diffOut[pix] = packR11G11B10F(unpackR11G11B10F(A.diffOut[pix]) + mk3(d.x, d.y, d.z)); A.sumDiff[pix] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
+}
+// What the feature needs, from the first frame that has the sun and the toggle on: the queue at the frame's slots per bin (the bins' growth
+// releases it: frame.hip growBins, behind a wait for every stream), its counts, and S for one-sample frames.
+static int allocSunHits(rtggx_context* c, bool wantSums) {
+  bool cleared = false;
+  if (!c->evSunHit) RT_HIP(create(c->evSunHit, hipEventDisableTiming));
+  if (!c->sunHitRays || !c->sunHitHits || c->sunHitSlots != c->binSlots) {
+    c->sunHitRays.reset(); c->sunHitHits.reset();
+    const size_t slots = (size_t)c->numBinsMax * c->binSlots;
+    RT_HIP(alloc(c->sunHitRays, slots * sizeof(RayRec)));
+    RT_HIP(alloc(c->sunHitHits, slots * sizeof(HitKey)));
+    c->sunHitSlots = c->binSlots;
+  }
+  if (!c->sunHitCount) { RT_HIP(allocFilled(c->sunHitCount, (size_t)c->numBinsMax)); cleared = true; }
+  if (wantSums && !c->sunHitSums) { RT_HIP(allocFilled(c->sunHitSums, (size_t)c->W * c->H * 8u)); cleared = true; }
+  if (cleared) RT_HIP(hipStreamSynchronize(nullptr));      // (the clears run on the null stream, which this context's streams are not ordered against)
+  return 0;
+}
+// The frame's first use of the shared queue and sums on stream s: behind the previous frame's, which may have run on another stream (small
+// launches alternate two), as launchShadeSamples orders sppAcc
+static int beginSunHits(rtggx_context* c, hipStream_t s, bool wantSums) {
+  { const int r = allocSunHits(c, wantSums); if (r) return r; }
+  if (c->sunHitStream && c->sunHitStream != s) { RT_HIP(hipEventRecord(c->evSunHit, c->sunHitStream)); RT_HIP(hipStreamWaitEvent(s, c->evSunHit, 0)); }
+  c->sunHitStream = s;
+  return 0;
+}
+// One level's hits: generation from the bins q (their rays traced, not yet shaded), the any-hit traversal on the frame's trace grid with this
+// stream's spill part (launchShade), the add into sumRefl / sumDiff
+static int launchSunHits(rtggx_context* c, const FrameParams& fp, hipStream_t s, const TraceQueue& bins, const float4* fat0, const float4* fat1, const uint32_t* tileWords,
+                         uint32_t numTiles, int spillPart, bool samples, float* sumRefl, float* sumDiff) {
+  if (numTiles * 4u > c->numBinsMax || c->sunHitSlots != c->binSlots) { setError("rtggx_ray_trace: the queue of rtggx_set_sun_reflections does not hold %u bins of %u slots", numTiles * 4u, c->binSlots); return -1; }
+  const rtggx_context::Sun& sun = c->sun;
+  SunHitGenArgs G;
+  G.rays = bins.rays; G.hits = bins.hits; G.binCount = bins.binCount; G.binSlots = c->binSlots;
+  G.fat0 = fat0; G.fat1 = fat1;
+  G.outRays = (RayRec*)c->sunHitRays.get(); G.outHits = (HitKey*)c->sunHitHits.get(); G.outCount = c->sunHitCount;
+  G.tileWords = tileWords;
+  G.Lx = sun.L[0]; G.Ly = sun.L[1]; G.Lz = sun.L[2]; G.Ex = sun.E[0]; G.Ey = sun.E[1]; G.Ez = sun.E[2];
+  launch(sunHitGenKernel, dim3(numTiles), dim3(256), s, nullptr, nullptr, c->dParams + c->slot, G);
+  const TraceQueue q{G.outRays, G.outHits, G.outCount};
+  { const int r = launchTrace(c, fp, s, q, c->traceGrid[0], true, c->traceGrid[1], c->traceGrid[2], c->traceGrid[3], -1, nullptr, nullptr, spillPart, true); if (r) return r; }
+  SunHitAddArgs D;
+  D.rays = q.rays; D.hits = q.hits; D.binCount = q.binCount; D.binSlots = c->binSlots; D.tileWords = tileWords; D.sumRefl = sumRefl; D.sumDiff = sumDiff;
+  launch(samples ? sunHitAddKernel<true> : sunHitAddKernel<false>, dim3(numTiles), dim3(256), s, nullptr, nullptr, D);
+  RT_HIP(hipGetLastError());
+  return 0;
+}
+
 // The shading of the frame's traced bins: at recursion depth D (rtggx_set_max_recursion_depth) D passes, each but the last spawning the next
 // level's rays into the bins they shade and tracing them with the trace kernel on this stream (ShadePass).  `done` rides on the last pass.
 static void (*const kShade[3][2])(const FrameParams*, ShadeArgs) = {      // [ShadePass][rate 4]
@@ -1114,6 +1294,9 @@ static int launchShadeSamples(rtggx_context* c, const FrameParams& fp, hipStream
   SampleGenArgsMapped GM;
   static_cast<SampleGenArgs&>(GM) = G; GM.sampleMap = map; GM.sample = 0u;
   const TraceQueue q{S.rays, S.spawnHits, S.binCount};
+  // rtggx_set_sun_reflections: at every level acc = acc + s_d comes first, then the pass's own add of the paths that end there
+  const bool sunHits = c->sun.on && c->sunReflections;
+  if (sunHits) { const int r = beginSunHits(c, s, false); if (r) return r; }
   for (uint32_t k = 0; k < N; ++k) {
     for (uint32_t level = 0; level < depth; ++level) {
       if (k > 0 && level == 0) {
@@ -1124,6 +1307,7 @@ static int launchShadeSamples(rtggx_context* c, const FrameParams& fp, hipStream
         const int r = launchTrace(c, fp, s, q, c->traceGrid[0], true, c->traceGrid[1], c->traceGrid[2], c->traceGrid[3], -1, nullptr, nullptr, spillPart);
         if (r) return r;
       }
+      if (sunHits) { const int r = launchSunHits(c, fp, s, q, S.fat0, S.fat1, S.tileWords, numTiles, spillPart, true, S.accRefl, S.accDiff); if (r) return r; }
       launch(level + 1u < depth ? (wide ? shadeKernel<1, SHADE_SPAWN_ACCUM, true> : shadeKernel<1, SHADE_SPAWN_ACCUM>) : shadeKernel<1, SHADE_ACCUM>, dim3(numTiles), dim3(256), s, nullptr, nullptr, sp + k, S);
       S.carryMask = 0u;      // (carried over once, by the first pass)
       RT_HIP(hipGetLastError());
@@ -1172,15 +1356,31 @@ int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent
   // spill area of their own on the main stream; on a traversal stream (small launches, frame.hip) that stream's own, in stream order
   const int spillPart = s == c->streamMain ? 2 : (int)c->traceSpillHalf;
   if (c->samples > 1u && !quad) return launchShadeSamples(c, fp, s, done, S, numTiles, spillPart);
+  // rtggx_set_sun_reflections (the sun excludes rate 4): every level's hits add their terms to S in front of the level's shading pass, and
+  // behind the last pass -- which then no longer carries `done` -- sunHitResolveKernel adds S to the packed words
+  const bool sunHits = c->sun.on && c->sunReflections && !quad;
+  float* sums[2] = {nullptr, nullptr};
+  if (sunHits) {
+    const int r = beginSunHits(c, s, true); if (r) return r;
+    sums[0] = c->sunHitSums; sums[1] = c->sunHitSums + 4u * (size_t)c->W * c->H;
+  }
   for (uint32_t level = 0; level < depth; ++level) {
+    const TraceQueue q{S.rays, S.spawnHits, S.binCount};
     if (level > 0) {
-      const TraceQueue q{S.rays, S.spawnHits, S.binCount};
       const int r = launchTrace(c, fp, s, q, c->traceGrid[0], true, c->traceGrid[1], c->traceGrid[2], c->traceGrid[3], -1, nullptr, nullptr, spillPart);
       if (r) return r;
       S.carryMask = 0u;      // (carried over once, by the first pass)
     }
+    if (sunHits) { const int r = launchSunHits(c, fp, s, q, S.fat0, S.fat1, S.tileWords, numTiles, spillPart, false, sums[0], sums[1]); if (r) return r; }
     const int pass = level + 1u < depth ? SHADE_SPAWN : level == 0 ? SHADE_FINAL : SHADE_FINAL_DEEP;
-    launch(pass == SHADE_SPAWN && c->sampleSet > RTGGX_MIN_SAMPLE_SET ? kShadeSpawnWide[quad] : kShade[pass][quad], dim3(grid), dim3(256), s, nullptr, pass == SHADE_SPAWN ? nullptr : done, dfp, S);
+    launch(pass == SHADE_SPAWN && c->sampleSet > RTGGX_MIN_SAMPLE_SET ? kShadeSpawnWide[quad] : kShade[pass][quad], dim3(grid), dim3(256), s, nullptr, pass == SHADE_SPAWN || sunHits ? nullptr : done, dfp, S);
+    RT_HIP(hipGetLastError());
+  }
+  if (sunHits) {
+    SunHitResolveArgs R;
+    R.sumRefl = (float4*)sums[0]; R.sumDiff = (float4*)sums[1]; R.reflOut = set.rtRefl; R.diffOut = set.rtDiff;
+    R.tileWords = S.tileWords; R.tilesX = tilesX; R.rowBegin = rb; R.rowEnd = re;
+    launch(sunHitResolveKernel, dim3(numTiles), dim3(256), s, nullptr, done, dfp, R);
     RT_HIP(hipGetLastError());
   }
   return 0;

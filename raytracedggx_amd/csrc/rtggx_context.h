@@ -282,6 +282,17 @@ struct rtggx_context {
   // allocated by the first call that turns the sun on.
   struct Sun { bool on = false; float L[3] = {}, E[3] = {}; } sun, sunRequested;
   rt::DevBuf<void> sunRays, sunHits; rt::DevBuf<uint32_t> sunCount;
+  // rtggx_set_sun_reflections: the sun term and the shadow at the surfaces the paths hit (raytrace.hip launchSunHits).  Stored whether or not a
+  // sun is set; the frame's, the next frame's.  Everything below exists from the first frame that has both on (raytrace.hip allocSunHits):
+  //   sunHitRays / sunHitHits / sunHitCount   a queue of the feature's own, bins of sunHitSlots = binSlots slots (released when the bins grow)
+  //   sunHitSums   S of the one-sample frame: [2][W * H] float4 -- the sum of the terms r, g, b and the number of terms --, all zero between
+  //                frames (sunHitResolveKernel leaves them so)
+  // ONE of each for all input sets, like sppAcc: consecutive frames' passes follow each other in stream order, or by evSunHit where the
+  // stream changes (sunHitStream: a view, the stream of the most recent frame that used them).
+  bool sunReflections = false, sunReflectionsRequested = false;
+  rt::DevBuf<void> sunHitRays, sunHitHits; rt::DevBuf<uint32_t> sunHitCount; rt::DevBuf<float> sunHitSums;
+  uint32_t sunHitSlots = 0;
+  hipStream_t sunHitStream = nullptr; rt::Event evSunHit;
   uint32_t rayRate = 1;          // rtggx_set_ray_rate: pixels per traced ray, 1 or 4 (raytrace.hip rayGenKernel, reconstructKernel)
   uint32_t maxDepth = 1, depthRequested = 1;      // rtggx_set_max_recursion_depth: 1..4 levels of rays per path (raytrace.hip launchShade); the frame's, the next frame's
   // rtggx_set_samples_per_pixel: 1, 2, 4 or 8 samples per covered pixel (raytrace.hip launchShade; DESIGN.md "Samples per pixel"); the

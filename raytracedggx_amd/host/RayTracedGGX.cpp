@@ -36,6 +36,7 @@ void RayTracedGGX::OnInit() {
   if (m_vndf) m_rayTracer->SetSampler(true);            // -vndf: visible-normal sampling of the reflection lobe (opt-in; the reference samples the NDF)
   if (m_rayRate != 1u && !m_rayTracer->SetRayRate(m_rayRate)) throw std::runtime_error("-rayrate: " + m_rayTracer->GetLastError());      // -rayrate 4: one ray per 2x2 quad (opt-in)
   if (m_hasSun && !m_rayTracer->SetSun(m_sun, m_sun + 3)) throw std::runtime_error("-sun: " + m_rayTracer->GetLastError());      // -sun: a directional light with ray-traced shadows (opt-in)
+  if (m_sunReflections && !m_rayTracer->SetSunReflections(true)) throw std::runtime_error("-sunreflections: " + m_rayTracer->GetLastError());      // -sunreflections: ... at the surfaces the paths hit as well (opt-in)
   if (m_recursionDepth != 1u && !m_rayTracer->SetMaxRecursionDepth(m_recursionDepth)) throw std::runtime_error("-recursion: " + m_rayTracer->GetLastError());      // -recursion N: multi-bounce paths (opt-in)
   if (m_samplesPerPixel != 1u && !m_rayTracer->SetSamplesPerPixel(m_samplesPerPixel)) throw std::runtime_error("-spp: " + m_rayTracer->GetLastError());      // -spp N: multi-sample tracing (opt-in)
   if (m_sampleSet != RTGGX_MIN_SAMPLE_SET && !m_rayTracer->SetSampleSetSize(m_sampleSet)) throw std::runtime_error("-sampleset: " + m_rayTracer->GetLastError());      // -sampleset M: a larger sample set (opt-in)
@@ -207,7 +208,7 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
     return (arg[0] == '-' || arg[0] == '/') && lower(arg + 1) == lower(name);
   };
   // On POSIX an absolute path also starts with '/': such a token is a flag only when it names one.
-  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "sun", "recursion", "spp", "accumulate", "sampleset", "savereference", "reference", "score", "envlayout", "envsize", "envmips", "envprefilter"};
+  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "sun", "sunreflections", "recursion", "spp", "accumulate", "sampleset", "savereference", "reference", "score", "envlayout", "envsize", "envmips", "envprefilter"};
   const auto isFlagName = [&](const char* name) { for (const char* f : kFlags) if (lower(name) == f) return true; return false; };
   const auto hasNextArgValue = [&](int i) {
     if (i + 1 >= argc) return false;
@@ -260,6 +261,7 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
       for (int k = 3; k < 6; ++k) if (!std::isfinite(m_sun[k]) || m_sun[k] < 0.0f) throw std::runtime_error("-sun: an irradiance that is finite and not negative");
       m_hasSun = true;
     }
+    else if (isArgMatched(i, "sunreflections")) m_sunReflections = true;      // (without -sun: refused below, once the whole line is read)
     else if (isArgMatched(i, "rayrate")) {
       const int rate = hasNextArgValue(i) ? std::atoi(argv[++i]) : 0;
       if (rate != 1 && rate != 4) throw std::runtime_error("-rayrate: 1 or 4 pixels per traced ray");
@@ -312,6 +314,8 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
   if (!m_scoreFile.empty() && m_referenceFile.empty()) throw std::runtime_error("-score: needs -reference <file.pfm>");
   if ((!m_scoreFile.empty() || !m_referenceFile.empty()) && (m_gpus > 1 || m_strips > 1)) throw std::runtime_error("-reference / -score: whole frames on one GPU only, not with -gpus N > 1 or -strips N > 1");
   if (!m_referenceFile.empty()) { std::string why; if (!ReadPfm(m_referenceFile.c_str(), m_width, m_height, m_referenceImage, why)) throw std::runtime_error("-reference: " + why); }
+  // the sun in reflections (rtggx_set_sun_reflections) acts only under a sun: asking for it without one is a mistake, refused here
+  if (m_sunReflections && !m_hasSun) throw std::runtime_error("-sunreflections without -sun: there is no light to reflect");
   // quarter-rate tracing renders whole frames only (rtggx_set_ray_rate): refused here, before anything has touched a GPU
   // one knob asks for fewer rays, the other for more (rtggx_set_samples_per_pixel)
   if (m_rayRate != 1u && m_hasSun) throw std::runtime_error("-sun together with -rayrate 4: refused");

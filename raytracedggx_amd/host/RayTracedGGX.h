@@ -2,7 +2,7 @@
 // DXFramework virtuals RayTracedGGX/Common/DXFramework.h:23-26): OnInit / OnUpdate / OnRender /
 // OnDestroy, the same command line (RayTracedGGX.cpp:462-511) and the same defaults
 // (RayTracedGGX.cpp:37-39, camera :19-23, 267-277).  What the window supplied interactively is
-// supplied by extra flags: -width -height -frames -dt -metallic -sharedmem -sync -vndf -rayrate -sun -recursion -spp -sampleset -accumulate -savereference -reference -score -envlayout -envsize -envmips -envprefilter -device -dump -track -deform -gpus -strips -balance.
+// supplied by extra flags: -width -height -frames -dt -metallic -sharedmem -sync -vndf -rayrate -sun -sunreflections -recursion -spp -sampleset -accumulate -savereference -reference -score -envlayout -envsize -envmips -envprefilter -device -dump -track -deform -gpus -strips -balance.
 #pragma once
 #include <vector>
 #include <cstdint>
@@ -135,6 +135,7 @@ class RayTracedGGX {
   std::string m_referenceFile, m_scoreFile, m_saveReferenceFile;
   std::vector<uint16_t> m_referenceImage;
   bool m_scoreFileStarted = false;
+  bool m_sunReflections = false;      // -sunreflections: the sun at the surfaces seen in reflections as well (RayTracer::SetSunReflections); needs -sun
   float m_sun[6] = {}; bool m_hasSun = false;      // -sun <x> <y> <z> <r> <g> <b>: direction toward the sun and irradiance (RayTracer::SetSun); not together with -rayrate 4
   uint32_t m_rayRate = 1;              // -rayrate <1|4>: pixels per traced ray (RayTracer::SetRayRate); 4 renders whole frames only: not with -gpus / -strips
   // -deform <amplitude>: the model breathes -- a travelling sine wave through its vertices, DeformPeriod key shapes computed once

@@ -53,6 +53,8 @@ class RayTracer {
   bool SetRayRate(uint32_t pixelsPerRay);
   // A directional light with ray-traced shadows from the next frame on (rtggx_set_sun): dir toward the sun, e its irradiance; (nullptr, nullptr): off.
   bool SetSun(const float dir[3], const float e[3]);
+  // The sun term and the shadow at the surfaces seen in reflections as well (rtggx_set_sun_reflections); it acts only while a sun is set.
+  bool SetSunReflections(bool enable);
   bool SetSamplesPerPixel(uint32_t samples);   // rtggx_set_samples_per_pixel: 1 (default), 2, 4 or 8 samples per covered pixel (-spp); not together with ray rate 4
   bool SetMaxRecursionDepth(uint32_t depth);   // rtggx_set_max_recursion_depth: 1 (default; RayTracer.cpp:605 SetMaxRecursionDepth(1)) to 4 levels of rays per path (-recursion)   // rtggx_set_ray_rate: 1 (default) or 4 -- one pixel of each 2x2 quad traced per frame, the rest reconstructed (-rayrate)
   // rtggx_set_sample_set: the size of the sample set getSampleParam draws from, 256 (default, the reference's) or a power of two up to
