@@ -655,6 +655,59 @@ int  rtggx_set_sun(rtggx_context* ctx, const float direction[3], const float irr
  * found set. */
 int  rtggx_set_sun_reflections(rtggx_context* ctx, int enable);
 
+/* The sun from the environment: finds the sun in the current cube, measures its direction and irradiance -- what rtggx_set_sun wants -- and,
+ * where asked, takes it out of the cube, so that a probe with a sun in it does not light the scene twice (once analytically, with shadows, and
+ * once more through the environment lookups, the SH irradiance and every level of the chain).  A setup call, not per frame; opt-in: a context
+ * that never calls it allocates and launches exactly what it always did.  It synchronises.  S is the cube's side, level 0 the current RGBA16F
+ * level 0, and everything below is double arithmetic, each operation rounded on its own (no contraction), on values that are exact in a double.
+ *   Texels.  Per channel v = x > 0 ? min(x, 65504) : 0 (NaN and negatives become 0: the image loader's rule); Y(c) = (0.25 c.r + 0.5 c.g) +
+ *     0.25 c.b (exact for binary16 inputs).  Texel (f, x, y) has the index i = (f S + y) S + x and the integer direction D = S cubeFaceDir(f,
+ *     a / S, b / S) with a = 2 x + 1 - S, b = 2 y + 1 - S: face 0 (S, -b, -a), 1 (-S, -b, a), 2 (a, S, b), 3 (a, -S, -b), 4 (a, -b, S),
+ *     5 (-a, -b, -S).  n = D . D.  Sides above 8192 are refused; up to there D, n and every dot product of two directions are exact.
+ *   Peak.  The texel of greatest Y, ties to the lowest i: peak_face, peak_x, peak_y; peak_luma its Y; P its D, nP = P . P.
+ *   Masks.  dot = D . P.  A texel is IN THE CONE iff dot > 0 && dot dot >= (cos2_cone n) nP, IN THE RING iff it is not in the cone and the
+ *     same holds with cos2_ring.  cos2 = c c with c = cos((double)degrees (3.14159265358979323846 / 180.0)), the host's libm; both are
+ *     reported, so that a restatement uses them and not a cosine of its own.
+ *   Weights.  q = sqrt(n), w = (4.0 S) / (n q) (the texel's solid angle up to a constant factor), d = D / q per component.
+ *   Pass B, all texels: weight_all = sum w; sum w Y; weight_ring = sum_ring w; ring_rgb[c] = sum_ring w v_c; texels_cone, texels_ring.  Then
+ *     mean_luma = (sum w Y) / weight_all; background[c] = ring_rgb[c] / weight_ring, 0 with an empty ring; b16[c] = the binary16 nearest
+ *     (ties to even) to (float)background[c] capped at 65504 -- background_half reports it as a float.
+ *   found = 0, and nothing further is done, when peak_luma == 0 or peak_luma < min_contrast mean_luma: an overcast sky has no sun to take out.
+ *   Pass C, the cone: e_c = max(v_c - b16_c, 0); weight_cone = sum w; excess[c] = sum w e_c; moment = sum (w Y(e)) d per component;
+ *     texels_lit counts the texels with e > 0 in some channel.  Then, each quantity rounded to fp32 once: direction = moment / |moment|,
+ *     irradiance[c] = excess[c] (4 pi / weight_all) -- the normalisation of rtggx_transform_sh.  There is no cosine factor inside the cone.
+ *     |moment| zero or not finite: found = 0.  When found == 0 direction and irradiance are 0.
+ *   THE ORDER OF EVERY SUM IS FIXED as in RtggxScore: the terms of ALL texels by i -- a texel outside the sum's mask adds +0.0 --, padded with
+ *     +0.0 to a power of two, added pairwise, adjacent pairs first.  No atomics: the record depends on the cube and the arguments alone (a
+ *     moment component that sums to zero may read +0.0 or -0.0).
+ *   Removal (remove != 0 and found): a new cube beside the old one.  Level 0 is a copy in which, at the texels in the cone, each of r, g, b
+ *     becomes min(v_c, b16_c) -- both are binary16 values, nothing is rounded; alpha is kept --, every other texel bit for bit; below it the
+ *     full box chain of rtggx_generate_env_mips, whatever the cube held there before (a prefiltered cube is to be prefiltered again by the
+ *     caller).  It replaces the context's cube as rtggx_generate_env_mips does -- the still-sky runs end, the SH coefficients are to be
+ *     projected again -- and removed = 1.  original = residual + e holds exactly per texel: what irradiance reports is what left the cube.
+ *   Nothing removed (remove == 0 or found == 0): the context is untouched -- environment, still-sky runs, SH state -- and nothing stays allocated.
+ *   Defaults (0 selects them): cone_degrees 4, ring_degrees 3 x the cone, min_contrast 16.  They are policy defaults for the caller to
+ *     override, not measured values.
+ *   Refused, the context keeping everything: no environment; a null out; a cone outside (0, 45]; a ring outside (cone, 89]; a min_contrast
+ *     that is negative or not finite; a side above 8192.
+ * tests/sunenv_ref.py restates the record and the cube. */
+typedef struct RtggxSunEstimate {          /* 224 bytes: 19 doubles, 9 floats, 9 words */
+  double cos2_cone, cos2_ring;             /* what the masks used */
+  double peak_luma, mean_luma;             /* Y of the peak texel; sum_all(w Y) / weight_all */
+  double weight_all, weight_cone, weight_ring;
+  double ring_rgb[3];                      /* sum_ring(w rgb) */
+  double background[3];                    /* ring_rgb / weight_ring, or 0 where weight_ring == 0 */
+  double excess[3];                        /* sum_cone(w e) */
+  double moment[3];                        /* sum_cone(w Y(e) d) */
+  float  background_half[3];               /* background after its one rounding to binary16, as floats: b16 */
+  float  direction[3], irradiance[3];      /* what to hand to rtggx_set_sun; 0 when found == 0 */
+  uint32_t found, removed;                 /* 0 / 1 */
+  uint32_t peak_face, peak_x, peak_y;
+  uint32_t texels_cone, texels_ring, texels_lit;   /* lit: in the cone with e > 0 in some channel */
+  uint32_t pad;                            /* 0 */
+} RtggxSunEstimate;
+int  rtggx_sun_from_env(rtggx_context* ctx, float cone_degrees, float ring_degrees, float min_contrast, int remove, RtggxSunEstimate* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,7 +40,8 @@ EXPORTS = ["rtggx_last_error", "rtggx_create", "rtggx_destroy", "rtggx_set_strip
            "rtggx_set_accumulation", "rtggx_reset_accumulation", "rtggx_accumulated_frames", "rtggx_present_accumulation", "rtggx_set_sample_set",
            "rtggx_set_reference", "rtggx_reference_from_accumulation", "rtggx_set_scoring", "rtggx_read_scores",
            "rtggx_set_env_image", "rtggx_generate_env_mips", "rtggx_prefilter_env",
-           "rtggx_set_sample_map", "rtggx_read_sample_map", "rtggx_trace_occlusion", "rtggx_set_sun", "rtggx_set_sun_reflections"]
+           "rtggx_set_sample_map", "rtggx_read_sample_map", "rtggx_trace_occlusion", "rtggx_set_sun", "rtggx_set_sun_reflections",
+           "rtggx_sun_from_env"]
 SCORE_RING = 256
 
 
@@ -58,6 +59,24 @@ class Score(C.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad"}
+
+
+class SunEstimate(C.Structure):
+    """RtggxSunEstimate (rtggx.h): what rtggx_sun_from_env found -- the masks' squared cosines, the peak, the fp64 sums in the contract's
+    pairwise order, the background and its binary16 rounding, direction and irradiance for set_sun, the counts."""
+    _fields_ = [(n, C.c_double) for n in ("cos2_cone", "cos2_ring", "peak_luma", "mean_luma", "weight_all", "weight_cone", "weight_ring")] + \
+               [(n, C.c_double * 3) for n in ("ring_rgb", "background", "excess", "moment")] + \
+               [(n, C.c_float * 3) for n in ("background_half", "direction", "irradiance")] + \
+               [(n, C.c_uint32) for n in ("found", "removed", "peak_face", "peak_x", "peak_y", "texels_cone", "texels_ring", "texels_lit", "pad")]
+
+    def as_dict(self):
+        """Scalars as Python numbers, the triples as numpy arrays of their own type; "bytes": the record as it lies in memory."""
+        out = {"bytes": bytes(self)}
+        for n, t in self._fields_:
+            if n != "pad":
+                v = getattr(self, n)
+                out[n] = v if t in (C.c_double, C.c_uint32) else np.array(list(v), np.float64 if t == C.c_double * 3 else np.float32)
+        return out
 
 
 _lib = None
@@ -126,6 +145,7 @@ def load():
     L.rtggx_trace_occlusion.argtypes = [vp, vp, C.c_uint32, vp]
     L.rtggx_set_sun.argtypes = [vp, vp, vp]
     L.rtggx_set_sun_reflections.argtypes = [vp, C.c_int]
+    L.rtggx_sun_from_env.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_int, C.POINTER(SunEstimate)]
     L.rtggx_ray_total.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
     L.rtggx_kernel_times.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
     _lib = L
@@ -585,6 +605,15 @@ class Context:
     def set_sun_reflections(self, on):
         """The sun term and the shadow at the surfaces the paths hit as well (0 / 1), from the next frame on; it acts only while a sun is set."""
         self._check(self.L.rtggx_set_sun_reflections(self.h, int(on)))
+
+    def sun_from_env(self, cone=0, ring=0, min_contrast=0, remove=False):
+        """The sun of the current environment (include/rtggx.h): the record as a dict (SunEstimate.as_dict) -- "direction" and "irradiance" are
+        what set_sun takes, "found" says whether there is a sun at all.  cone, ring: half-angles in degrees (0: 4 and three times the cone);
+        min_contrast: how far the peak must stand above the mean luminance (0: 16); remove: cut the sun out of the cube and rebuild its box
+        chain.  Synchronises."""
+        e = SunEstimate()
+        self._check(self.L.rtggx_sun_from_env(self.h, float(cone), float(ring), float(min_contrast), 1 if remove else 0, C.byref(e)))
+        return e.as_dict()
 
     def trace_occlusion(self, rays):
         """One bool per ray {o.xyz, d.xyz, tmin, tmax}: is there a triangle with tmin < t < tmax (the any-hit traversal)."""

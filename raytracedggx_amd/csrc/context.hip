@@ -9,6 +9,7 @@
 #include "capi_internal.h"
 #include "rt_queue.h"
 #include "rt_env_filter.h"
+#include "rt_sun_env.h"
 
 #ifndef RT_REFIT_REBUILD_RATIO
 #define RT_REFIT_REBUILD_RATIO 1.2f      // a refitted tree whose cost has grown by this factor since its build is rebuilt (rtggx_refit_as)
@@ -657,6 +658,21 @@ int rtggx_prefilter_env(rtggx_context* c, uint32_t samples) {
   RT_HIP(syncStreams(c));
   const int r = prefilterEnv(c, n, c->streamMain);
   if (r == 0) c->sky.breakRuns(SkyBreak::Environment);
+  return r;
+}
+
+// Checked before anything is touched; and a call that takes nothing out -- remove == 0, or no sun found -- leaves the environment, the
+// still-sky runs and the SH state as they were: it has only read level 0.
+int rtggx_sun_from_env(rtggx_context* c, float coneDegrees, float ringDegrees, float minContrast, int remove, RtggxSunEstimate* out) {
+  RT_CHECK_CTX(c);
+  if (!out) { setError("rtggx_sun_from_env: null result"); return -1; }
+  if (!c->env.texels) { setError("rtggx_sun_from_env: no environment map"); return -1; }
+  if (c->env.size > kSunEnvMaxSide) { setError("rtggx_sun_from_env: a cube of side %u, more than %u", c->env.size, kSunEnvMaxSide); return -1; }
+  SunEnvAngles angles;
+  if (const char* why = sunEnvAngles(coneDegrees, ringDegrees, minContrast, angles)) { setError("rtggx_sun_from_env: %s (cone %g, ring %g, contrast %g)", why, coneDegrees, ringDegrees, minContrast); return -1; }
+  RT_HIP(syncStreams(c));
+  const int r = sunFromEnv(c, angles, remove, out, c->streamMain);
+  if (r == 0 && out->removed) c->sky.breakRuns(SkyBreak::Environment);
   return r;
 }
 

@@ -378,15 +378,17 @@ int buildEnvFromImage(rtggx_context* c, int layout, int pixels, uint32_t width, 
 
 // The cube rtggx_generate_env_mips leaves, enqueued on `s`: the context's level 0 as it is and the full box chain below it.  The buffers are
 // allocated here; the two fp32 scratch levels must outlive the launches (the caller synchronises `s` before it lets go of them).
+// `cone` (rtggx_sun_from_env's removal): level 0 is the context's with the sun cut out of the cone's texels (sunenv.hip), and the chain is that one's.
 struct BoxChain { DevBuf<uint2> texels; DevBuf<float4> ping, pong; };
-static hipError_t launchBoxChain(rtggx_context* c, BoxChain& b, uint32_t size, uint32_t mips, const uint32_t* mipOffset, uint64_t total, hipStream_t s) {
+static hipError_t launchBoxChain(rtggx_context* c, BoxChain& b, uint32_t size, uint32_t mips, const uint32_t* mipOffset, uint64_t total, hipStream_t s, const SunCone* cone = nullptr) {
   const size_t n0 = 6u * (size_t)size * size, h = size >> 1, n1 = 6u * h * h;
   hipError_t e = alloc(b.texels, total);
   if (e == hipSuccess) e = alloc(b.ping, n0);
   if (e == hipSuccess && n1) e = alloc(b.pong, n1);
-  if (e == hipSuccess) e = hipMemcpyAsync(b.texels, c->env.texels, n0 * sizeof(uint2), hipMemcpyDeviceToDevice, s);      // level 0 stays what it is
+  if (e == hipSuccess && !cone) e = hipMemcpyAsync(b.texels, c->env.texels, n0 * sizeof(uint2), hipMemcpyDeviceToDevice, s);      // level 0 stays what it is
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(envWidenKernel, dim3(envBlocks(n0)), dim3(256), 0, s, (const uint2*)c->env.texels, b.ping.get(), n0);
+  if (cone) launchSunRemove(c->env.texels, b.texels, size, *cone, s);
+  hipLaunchKernelGGL(envWidenKernel, dim3(envBlocks(n0)), dim3(256), 0, s, cone ? (const uint2*)b.texels : (const uint2*)c->env.texels, b.ping.get(), n0);
   launchEnvChain(b.texels, mipOffset, size, mips, b.ping, b.pong, s);
   return hipGetLastError();
 }
@@ -399,6 +401,18 @@ int generateEnvMips(rtggx_context* c, hipStream_t s) {
   hipError_t e = launchBoxChain(c, b, size, mips, mipOffset, total, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) { setError("rtggx_generate_env_mips: %s", hipGetErrorString(e)); return -2; }
+  return installEnv(c, b.texels, size, mips, mipOffset, total);
+}
+
+// rtggx_sun_from_env's removal (sunenv.hip measures, this replaces): generateEnvMips over the cut level 0.  The caller has waited for every stream.
+int removeSunFromEnv(rtggx_context* c, const SunCone& cone, hipStream_t s) {
+  const uint32_t size = c->env.size, mips = fullChain(size);
+  uint32_t mipOffset[16];
+  const uint64_t total = chainOffsets(size, mips, mipOffset);
+  BoxChain b;
+  hipError_t e = launchBoxChain(c, b, size, mips, mipOffset, total, s, &cone);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) { setError("rtggx_sun_from_env: %s", hipGetErrorString(e)); return -2; }
   return installEnv(c, b.texels, size, mips, mipOffset, total);
 }
 

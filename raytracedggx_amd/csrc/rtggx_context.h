@@ -527,6 +527,13 @@ int prefilterEnv(rtggx_context* c, uint32_t samples, hipStream_t s);            
 // one level of the prefiltered cube (raytrace.hip, beside the sampler it calls): 6 side^2 texels at dst from the box-chain cube and a table of K entries
 int launchEnvPrefilter(const uint2* srcTexels, uint32_t size, uint32_t mips, const uint32_t* dSrcMipOffset, const float4* dTable, uint32_t K, float invW,
                        uint32_t side, uint2* dst, hipStream_t s);
+// The sun from the environment (sunenv.hip; rt_sun_env.h: the host's arithmetic).  SunCone: what tells the cone's texels and what they are cut
+// down to -- the peak texel's integer direction P, P . P, the squared cosine, the background as binary16 codes.
+struct SunEnvAngles;
+struct SunCone { double P[3], nP, cos2Cone; uint32_t b16[3]; };
+int sunFromEnv(rtggx_context* c, const SunEnvAngles& angles, int remove, RtggxSunEstimate* out, hipStream_t s);      // rtggx_sun_from_env, arguments checked, streams waited for
+void launchSunRemove(const uint2* src, uint2* dst, uint32_t size, const SunCone& cone, hipStream_t s);               // level 0 of `size` with the cone's texels cut down
+int removeSunFromEnv(rtggx_context* c, const SunCone& cone, hipStream_t s);                                          // env.hip: the cut level 0, its box chain, installed
 int projectSH(rtggx_context* c, hipStream_t s);
 int unpackVisDepth(rtggx_context* c, uint32_t* dVis, uint32_t* dDepth, hipStream_t s);
 int packVisDepth(rtggx_context* c, const uint32_t* dVis, const uint32_t* dDepth, hipStream_t s);

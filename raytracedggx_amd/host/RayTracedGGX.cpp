@@ -26,6 +26,7 @@ RayTracedGGX::~RayTracedGGX() {}
 void RayTracedGGX::OnInit() {
   m_rayTracer = std::make_unique<RayTracer>();
   m_rayTracer->SetEnvOptions(m_envLayout, m_envSize, m_envMips, m_envPrefilter);      // -envlayout, -envsize, -envmips, -envprefilter: what Init does with the -env file
+  m_rayTracer->SetSunFromEnvironment(m_sunFromEnv, m_sunFromEnvCone);                  // -sunfromenv: ... and the sun it finds there (opt-in)
   if (!m_rayTracer->Init(m_width, m_height, m_meshFileName.c_str(), m_envFileName.c_str(), m_meshPosScale, m_device))
     throw std::runtime_error("RayTracer::Init failed: " + m_rayTracer->GetLastError());
   m_denoiser = std::make_unique<Denoiser>();
@@ -208,7 +209,7 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
     return (arg[0] == '-' || arg[0] == '/') && lower(arg + 1) == lower(name);
   };
   // On POSIX an absolute path also starts with '/': such a token is a flag only when it names one.
-  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "sun", "sunreflections", "recursion", "spp", "accumulate", "sampleset", "savereference", "reference", "score", "envlayout", "envsize", "envmips", "envprefilter"};
+  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "sun", "sunreflections", "sunfromenv", "recursion", "spp", "accumulate", "sampleset", "savereference", "reference", "score", "envlayout", "envsize", "envmips", "envprefilter"};
   const auto isFlagName = [&](const char* name) { for (const char* f : kFlags) if (lower(name) == f) return true; return false; };
   const auto hasNextArgValue = [&](int i) {
     if (i + 1 >= argc) return false;
@@ -262,6 +263,16 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
       m_hasSun = true;
     }
     else if (isArgMatched(i, "sunreflections")) m_sunReflections = true;      // (without -sun: refused below, once the whole line is read)
+    // -sunfromenv [degrees]: the sun measured from the -env cube and taken out of it (rtggx_sun_from_env, RayTracer::Init); the half-angle
+    // of the cone is checked here, before a device is asked for; without a number it is the library's default
+    else if (isArgMatched(i, "sunfromenv")) {
+      float cone = 0.0f;
+      if (hasNextArgValue(i)) {
+        char* end = nullptr; cone = std::strtof(argv[++i], &end);
+        if (end == argv[i] || *end != '\0' || !(cone > 0.0f && cone <= 45.0f)) throw std::runtime_error("-sunfromenv: the half-angle of the sun's cone in degrees, above 0 and at most 45 (4 without a number)");
+      }
+      m_sunFromEnv = true; m_sunFromEnvCone = cone;
+    }
     else if (isArgMatched(i, "rayrate")) {
       const int rate = hasNextArgValue(i) ? std::atoi(argv[++i]) : 0;
       if (rate != 1 && rate != 4) throw std::runtime_error("-rayrate: 1 or 4 pixels per traced ray");
@@ -315,7 +326,10 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
   if ((!m_scoreFile.empty() || !m_referenceFile.empty()) && (m_gpus > 1 || m_strips > 1)) throw std::runtime_error("-reference / -score: whole frames on one GPU only, not with -gpus N > 1 or -strips N > 1");
   if (!m_referenceFile.empty()) { std::string why; if (!ReadPfm(m_referenceFile.c_str(), m_width, m_height, m_referenceImage, why)) throw std::runtime_error("-reference: " + why); }
   // the sun in reflections (rtggx_set_sun_reflections) acts only under a sun: asking for it without one is a mistake, refused here
-  if (m_sunReflections && !m_hasSun) throw std::runtime_error("-sunreflections without -sun: there is no light to reflect");
+  // one sun: the one typed in or the one the environment holds; and a sun excludes rate 4 wherever it comes from (rtggx_set_sun)
+  if (m_sunFromEnv && m_hasSun) throw std::runtime_error("-sunfromenv together with -sun: one sun, measured or given");
+  if (m_sunFromEnv && m_rayRate != 1u) throw std::runtime_error("-sunfromenv together with -rayrate 4: refused");
+  if (m_sunReflections && !m_hasSun && !m_sunFromEnv) throw std::runtime_error("-sunreflections without -sun: there is no light to reflect");
   // quarter-rate tracing renders whole frames only (rtggx_set_ray_rate): refused here, before anything has touched a GPU
   // one knob asks for fewer rays, the other for more (rtggx_set_samples_per_pixel)
   if (m_rayRate != 1u && m_hasSun) throw std::runtime_error("-sun together with -rayrate 4: refused");

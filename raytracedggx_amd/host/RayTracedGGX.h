@@ -2,7 +2,7 @@
 // DXFramework virtuals RayTracedGGX/Common/DXFramework.h:23-26): OnInit / OnUpdate / OnRender /
 // OnDestroy, the same command line (RayTracedGGX.cpp:462-511) and the same defaults
 // (RayTracedGGX.cpp:37-39, camera :19-23, 267-277).  What the window supplied interactively is
-// supplied by extra flags: -width -height -frames -dt -metallic -sharedmem -sync -vndf -rayrate -sun -sunreflections -recursion -spp -sampleset -accumulate -savereference -reference -score -envlayout -envsize -envmips -envprefilter -device -dump -track -deform -gpus -strips -balance.
+// supplied by extra flags: -width -height -frames -dt -metallic -sharedmem -sync -vndf -rayrate -sun -sunreflections -sunfromenv -recursion -spp -sampleset -accumulate -savereference -reference -score -envlayout -envsize -envmips -envprefilter -device -dump -track -deform -gpus -strips -balance.
 #pragma once
 #include <vector>
 #include <cstdint>
@@ -137,6 +137,10 @@ class RayTracedGGX {
   bool m_scoreFileStarted = false;
   bool m_sunReflections = false;      // -sunreflections: the sun at the surfaces seen in reflections as well (RayTracer::SetSunReflections); needs -sun
   float m_sun[6] = {}; bool m_hasSun = false;      // -sun <x> <y> <z> <r> <g> <b>: direction toward the sun and irradiance (RayTracer::SetSun); not together with -rayrate 4
+  // -sunfromenv [degrees]: the sun's direction and irradiance measured from the -env cube, the sun taken out of the cube (before
+  // -envprefilter filters it) and set as the light (RayTracer::SetSunFromEnvironment); degrees: the half-angle of the cone about the brightest
+  // texel, in (0, 45], 0 here = the library's default of 4; not together with -sun or -rayrate 4; -sunreflections is accepted with it
+  bool m_sunFromEnv = false; float m_sunFromEnvCone = 0.0f;
   uint32_t m_rayRate = 1;              // -rayrate <1|4>: pixels per traced ray (RayTracer::SetRayRate); 4 renders whole frames only: not with -gpus / -strips
   // -deform <amplitude>: the model breathes -- a travelling sine wave through its vertices, DeformPeriod key shapes computed once
   // at start-up and handed to RayTracer::UpdateMesh one per frame (per-frame host cost: one copy of the vertex array)

@@ -86,10 +86,25 @@ bool RayTracer::Init(uint32_t width, uint32_t height, const char* fileName, cons
     // (the prefilter starts from the full box chain below the current level 0 whatever levels the cube came with: it implies -envmips)
     if (m_envGenerateMips && m_envPrefilterSamples == 0u && cube.mips < full && !check(rtggx_generate_env_mips(m_ctx), "rtggx_generate_env_mips")) return false;
   }
-  return m_envPrefilterSamples == 0u || PrefilterEnvironment(m_envPrefilterSamples);
+  // -sunfromenv: the sun leaves the cube before the prefilter smears it over the rough levels, and comes back as a light with shadows
+  RtggxSunEstimate sun{};
+  if (m_sunFromEnv && !SunFromEnvironment(m_sunFromEnvCone, 0.0f, 0.0f, true, sun)) return false;
+  if (m_envPrefilterSamples != 0u && !PrefilterEnvironment(m_envPrefilterSamples)) return false;
+  if (m_sunFromEnv) {
+    if (!sun.found) std::printf("-sunfromenv: no sun in %s (peak luminance %g against a mean of %g): rendering without one\n", envFileName, sun.peak_luma, sun.mean_luma);
+    else {
+      std::printf("-sunfromenv: sun toward (%.9g %.9g %.9g), irradiance (%.9g %.9g %.9g), %u texels cut down in %s\n", sun.direction[0], sun.direction[1], sun.direction[2],
+                  sun.irradiance[0], sun.irradiance[1], sun.irradiance[2], sun.texels_lit, envFileName);
+      if (!SetSun(sun.direction, sun.irradiance)) return false;
+    }
+  }
+  return true;
 }
 
 bool RayTracer::PrefilterEnvironment(uint32_t samples) { return check(rtggx_prefilter_env(m_ctx, samples), "rtggx_prefilter_env"); }
+bool RayTracer::SunFromEnvironment(float cone, float ring, float minContrast, bool remove, RtggxSunEstimate& estimate) {
+  return check(rtggx_sun_from_env(m_ctx, cone, ring, minContrast, remove ? 1 : 0, &estimate), "rtggx_sun_from_env");
+}
 
 bool RayTracer::BuildAccelerationStructures() { return check(rtggx_build_as(m_ctx), "rtggx_build_as"); }
 

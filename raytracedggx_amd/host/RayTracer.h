@@ -42,6 +42,14 @@ class RayTracer {
   void SetEnvOptions(int layout, uint32_t cubeSize, bool generateMips, uint32_t prefilterSamples = 0) { m_envLayout = layout; m_envCubeSize = cubeSize; m_envGenerateMips = generateMips; m_envPrefilterSamples = prefilterSamples; }
   // rtggx_prefilter_env on the current environment: samples 0 = 1024, else a power of two from 64 to 4096; a refusal leaves it as it was
   bool PrefilterEnvironment(uint32_t samples);
+  // rtggx_sun_from_env on the current environment: the sun's direction and irradiance measured from the cube (cone, ring in degrees and
+  // minContrast: 0 = the library's defaults) and, with remove, the sun cut out of the cube and its box chain rebuilt.  estimate.found says
+  // whether there is one; a refusal leaves everything as it was.
+  bool SunFromEnvironment(float cone, float ring, float minContrast, bool remove, RtggxSunEstimate& estimate);
+  // -sunfromenv [degrees]: Init, once the -env file is loaded and -envmips has had its turn, takes the sun out of the cube
+  // (SunFromEnvironment with remove), THEN prefilters (-envprefilter sees the sunless cube) and sets the measured sun (SetSun); where no sun
+  // is found it says so in one line and goes on without one.  To be called before Init; coneDegrees 0 = the library's default.
+  void SetSunFromEnvironment(bool enable, float coneDegrees = 0.0f) { m_sunFromEnv = enable; m_sunFromEnvCone = coneDegrees; }
   bool BuildAccelerationStructures();
   bool Postinit();
 
@@ -102,6 +110,7 @@ class RayTracer {
   uint32_t m_numVerts = 0, m_numIndices = 0;
   std::vector<float> m_modelVerts;
   int m_envLayout = -1; uint32_t m_envCubeSize = 0; bool m_envGenerateMips = false; uint32_t m_envPrefilterSamples = 0;      // SetEnvOptions
+  bool m_sunFromEnv = false; float m_sunFromEnvCone = 0.0f;      // SetSunFromEnvironment
 
   // state UpdateFrame keeps between frames (statics / members in the reference)
   HaltonSequence m_halton;
