@@ -619,7 +619,8 @@ int  rtggx_trace_occlusion(rtggx_context* ctx, const float* rays, uint32_t n, ui
  * depth, sample count, sample set and sample map -- one shadow ray per covered, sun-facing pixel per frame, counted by rtggx_ray_count.
  * Background pixels are untouched.  Setting the sun ends no still-sky run and resets no accumulation (the caller's to do).
  * Known limit: surfaces seen in reflections are shaded by the environment and the SH irradiance alone -- a reflection shows the ground
- * without its sun term and without the shadow.  rtggx_set_sun_reflections(ctx, 1) lifts the limit.  Memory: 56 bytes per pixel and 4 per
+ * without its sun term and without the shadow.  rtggx_set_sun_reflections(ctx, 1) lifts the limit.  Known limit: the light is a
+ * direction, so every shadow edge is one pixel hard; rtggx_set_sun_angle gives the sun a size and the shadows a penumbra.  Memory: 56 bytes per pixel and 4 per
  * 8x8 block, from the first call that turns it on. */
 int  rtggx_set_sun(rtggx_context* ctx, const float direction[3], const float irradiance[3]);
 
@@ -654,6 +655,37 @@ int  rtggx_set_sun(rtggx_context* ctx, const float direction[3], const float irr
  * per pixel (two images of r, g, b and the number of terms).  S is all zero between frames: the pass that adds it to the words clears what it
  * found set. */
 int  rtggx_set_sun_reflections(rtggx_context* ctx, int enable);
+
+/* A sun with a size: the shadow rays of rtggx_set_sun and of rtggx_set_sun_reflections point at a point of the sun's disk instead of at its
+ * centre -- a penumbra, one sample per ray and frame, which the temporal pass or rtggx_set_accumulation average.  degrees: the angular
+ * RADIUS of the disk (the real sun: 0.27); 0, the default, is the directional sun.  The value is stored whether or not a sun is set and acts
+ * only in frames where the sun is on; it takes effect with the next rtggx_render_visibility.  Refused, the context keeping what it had: a
+ * NaN, a negative value, more than RTGGX_MAX_SUN_ANGLE_DEGREES.  The cap: the BRDF and NoL are still evaluated at the centre direction L --
+ * the usual approximation for a small disk, and not a good one for a wide source.  Opt-in: a context that never calls this, or calls it with
+ * 0, allocates and launches exactly what it did; no device buffer is added.  rtggx_sun_from_env does not set an angle: its cone is a policy
+ * default, not a measurement of the disk.
+ * Host, once per call of this function (k) or of rtggx_set_sun (T, B), in double on the stored fp32 L, each result rounded once to fp32:
+ *   k = 1 - cos(degrees pi / 180);  a = the coordinate axis of the smallest |L_i|, ties to the lowest index;  T = normalize(cross(a, L));
+ *   B = cross(L, T) (of the unrounded T).
+ * Per shadow ray, in fp32 without contraction, each operation rounded on its own:
+ *   1. h = rng(rng(pixel) + FrameIndex): the word getSampleParam forms before it masks it.  pixel: the full-frame pixel index y W + x (strips
+ *      agree with the whole frame).  FrameIndex: the frame's own for the pass of rtggx_set_sun; for the hits of sample k of an N-sample
+ *      frame sample k's, FrameIndex N + k;
+ *   2. w = rng(h + j 0x9E3779B9), j = 0 for the pass of rtggx_set_sun and 1 + 2 d + i for the hit of a level-d ray of the path that writes
+ *      image i (0: RayTracingOut0, the reflection group's; 1: RayTracingOut1, the diffuse group's);
+ *   3. u = (float)(w & 0xffff) / 65536;  s = w >> 24;  cos(phi), sin(phi) = entry s of the 256-entry table of the default sample set,
+ *      whatever rtggx_set_sample_set is: the sun is independent of the sample set;
+ *   4. e = u k;  cos(theta) = 1 - e;  sin(theta) = sqrt(e (2 - e)), correctly rounded (not 1 - cos^2, which cancels at small angles):
+ *      uniform in solid angle over the cap;
+ *   5. Ls_c = ((T_c (cos(phi) sin(theta))) + (B_c (sin(phi) sin(theta)))) + L_c cos(theta), per component, not renormalised;
+ *   6. a ray exists where NoL = dot(N, L) > 0, as before, AND dot(N, Ls) > 0.  Where the second test fails -- "below the horizon" -- there is
+ *      no ray and no term, and rtggx_ray_count counts nothing.  Otherwise the shadow ray goes from P along Ls over (1e-5, 10000), skipping
+ *      the surface's triangle;
+ *   7. the term added where the ray is unoccluded is the directional sun's bit for bit: BRDF and NoL at L.  Only visibility is sampled -- a
+ *      pixel lit from the whole disk carries the directional sun's word, a penumbra pixel carries it in a fraction of the frames.
+ * Everything else -- the queues, the any-hit traversal, the adds, the order of the sums, the streams -- is that of the two sun passes. */
+#define RTGGX_MAX_SUN_ANGLE_DEGREES 10.0f
+int  rtggx_set_sun_angle(rtggx_context* ctx, float degrees);
 
 /* The sun from the environment: finds the sun in the current cube, measures its direction and irradiance -- what rtggx_set_sun wants -- and,
  * where asked, takes it out of the cube, so that a probe with a sun in it does not light the scene twice (once analytically, with shadows, and

@@ -22,6 +22,7 @@ FORMAT_RGBA32F, FORMAT_RGBA16F, FORMAT_BC6H_UF16, FORMAT_BC6H_SF16 = 2, 10, 95, 
 ENV_EQUIRECT, ENV_VCROSS, ENV_HCROSS = 0, 1, 2      # layouts and pixel formats of rtggx_set_env_image
 PIXELS_RGBE8, PIXELS_RGB32F = 0, 1
 ENV_FILTER_MIN_SAMPLES, ENV_FILTER_MAX_SAMPLES = 64, 4096      # rtggx_prefilter_env
+MAX_SUN_ANGLE_DEGREES = 10.0                                    # rtggx_set_sun_angle
 
 _BUF_DTYPE = {BUF_VISIBILITY: np.uint32, BUF_DEPTH: np.uint32, BUF_NORMAL: np.uint32, BUF_ROUGH_METAL: np.uint16,
               BUF_VELOCITY: np.uint32, BUF_RT_REFL: np.uint32, BUF_RT_DIFF: np.uint32, BUF_TSS0: np.uint64, BUF_TSS1: np.uint64,
@@ -41,7 +42,7 @@ EXPORTS = ["rtggx_last_error", "rtggx_create", "rtggx_destroy", "rtggx_set_strip
            "rtggx_set_reference", "rtggx_reference_from_accumulation", "rtggx_set_scoring", "rtggx_read_scores",
            "rtggx_set_env_image", "rtggx_generate_env_mips", "rtggx_prefilter_env",
            "rtggx_set_sample_map", "rtggx_read_sample_map", "rtggx_trace_occlusion", "rtggx_set_sun", "rtggx_set_sun_reflections",
-           "rtggx_sun_from_env"]
+           "rtggx_sun_from_env", "rtggx_set_sun_angle"]
 SCORE_RING = 256
 
 
@@ -145,6 +146,7 @@ def load():
     L.rtggx_trace_occlusion.argtypes = [vp, vp, C.c_uint32, vp]
     L.rtggx_set_sun.argtypes = [vp, vp, vp]
     L.rtggx_set_sun_reflections.argtypes = [vp, C.c_int]
+    L.rtggx_set_sun_angle.argtypes = [vp, C.c_float]
     L.rtggx_sun_from_env.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_int, C.POINTER(SunEstimate)]
     L.rtggx_ray_total.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
     L.rtggx_kernel_times.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
@@ -605,6 +607,11 @@ class Context:
     def set_sun_reflections(self, on):
         """The sun term and the shadow at the surfaces the paths hit as well (0 / 1), from the next frame on; it acts only while a sun is set."""
         self._check(self.L.rtggx_set_sun_reflections(self.h, int(on)))
+
+    def set_sun_angle(self, degrees):
+        """The angular radius of the sun's disk in degrees, 0 to MAX_SUN_ANGLE_DEGREES, from the next frame on: shadow rays toward a point
+        of the disk (include/rtggx.h has the rule).  0: the directional sun.  It acts only while a sun is set."""
+        self._check(self.L.rtggx_set_sun_angle(self.h, float(degrees)))
 
     def sun_from_env(self, cone=0, ring=0, min_contrast=0, remove=False):
         """The sun of the current environment (include/rtggx.h): the record as a dict (SunEstimate.as_dict) -- "direction" and "irradiance" are

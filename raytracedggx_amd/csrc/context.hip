@@ -444,7 +444,28 @@ int rtggx_set_sun(rtggx_context* c, const float direction[3], const float irradi
   sun.on = on;
   sun.L[0] = (float)(x / len); sun.L[1] = (float)(y / len); sun.L[2] = (float)(z / len);
   for (int k = 0; k < 3; ++k) sun.E[k] = irradiance[k];
+  {  // the disk's frame (rtggx_set_sun_angle): double arithmetic on the stored fp32 L, T and B each rounded once
+    const double l[3] = {sun.L[0], sun.L[1], sun.L[2]};
+    int a = 0;
+    for (int k = 1; k < 3; ++k) if (std::fabs(l[k]) < std::fabs(l[a])) a = k;      // the axis of the smallest |L_i|, ties to the lowest index
+    const int a1 = (a + 1) % 3, a2 = (a + 2) % 3;
+    double t[3]; t[a] = 0.0; t[a1] = -l[a2]; t[a2] = l[a1];                         // cross(e_a, L)
+    const double tl = std::sqrt(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);
+    for (int k = 0; k < 3; ++k) t[k] /= tl;
+    const double b[3] = {l[1] * t[2] - l[2] * t[1], l[2] * t[0] - l[0] * t[2], l[0] * t[1] - l[1] * t[0]};      // cross(L, T)
+    for (int k = 0; k < 3; ++k) { sun.T[k] = (float)t[k]; sun.B[k] = (float)b[k]; }
+  }
   c->sunRequested = sun;
+  return 0;
+}
+// The sun's angular radius (include/rtggx.h).  Only the value and k = 1 - cos of it are kept, whether or not a sun is set; nothing is
+// allocated, and it takes effect with the next rtggx_render_visibility.  No synchronisation, no end of a still-sky run, no reset of an
+// accumulation, as for the sun itself.
+int rtggx_set_sun_angle(rtggx_context* c, float degrees) {
+  RT_CHECK_CTX(c);
+  if (!(degrees >= 0.0f && degrees <= RTGGX_MAX_SUN_ANGLE_DEGREES)) { setError("rtggx_set_sun_angle: %g degrees: the radius of the disk, 0 to %g", (double)degrees, (double)RTGGX_MAX_SUN_ANGLE_DEGREES); return -1; }
+  c->sunAngleRequested.degrees = degrees;
+  c->sunAngleRequested.k = (float)(1.0 - std::cos((double)degrees * 3.14159265358979323846 / 180.0));
   return 0;
 }
 // The sun at the surfaces the paths hit (include/rtggx.h).  Only the value is kept: it is stored whether or not a sun is set, allocates nothing

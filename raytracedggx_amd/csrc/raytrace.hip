@@ -1097,7 +1097,26 @@ struct SunHitGenArgs {
   const uint32_t* tileWords;
   float Lx, Ly, Lz, Ex, Ey, Ez;
 };
-__global__ void __launch_bounds__(256) sunHitGenKernel(const FrameParams* __restrict__ fpp, SunHitGenArgs A) {
+// A sun with a size (rtggx_set_sun_angle; include/rtggx.h has the rule): what the SOFT variants of the two generating kernels are given on top
+// of their arguments -- the disk's frame, k = 1 - cos(radius), the 256-entry cos/sin table whatever the sample set is, and (the hits) the
+// frame index of the sample the pass belongs to with the level's slot base 1 + 2d.  SOFT = false is the kernel as it was, body and
+// arguments (profiles/r17_a_sun_soft_isa.txt).
+struct SunDiskArgs { float Tx, Ty, Tz, Bx, By, Bz, k; const float* cosSin; uint32_t frameIndex, slotBase; };
+struct SunHitGenArgsSoft : SunHitGenArgs { SunDiskArgs disk; };
+// Steps 1-5 of the rule: the direction toward a point of the disk, uniform in solid angle over the cap; not renormalised.
+RT_DEV f3 sunDiskDirection(const SunDiskArgs& K, f3 L, uint32_t pixel, uint32_t frameIndex, uint32_t j) {
+  uint32_t h = rng(pixel); h += frameIndex; h = rng(h);      // getSampleParam's word before its mask
+  const uint32_t w = rng(h + j * 0x9E3779B9u);
+  const float u = (float)(w & 0xffffu) / 65536.0f;
+  const uint32_t s = w >> 24;
+  const float cosPhi = K.cosSin[s], sinPhi = K.cosSin[256u + s];
+  const float e = u * K.k;
+  const float cosTheta = 1.0f - e, sinTheta = sqrtf(e * (2.0f - e));      // (not 1 - cos^2: it cancels at small angles)
+  const float ct = cosPhi * sinTheta, st = sinPhi * sinTheta;
+  return mk3((K.Tx * ct + K.Bx * st) + L.x * cosTheta, (K.Ty * ct + K.By * st) + L.y * cosTheta, (K.Tz * ct + K.Bz * st) + L.z * cosTheta);
+}
+template <bool SOFT>
+__global__ void __launch_bounds__(256) sunHitGenKernel(const FrameParams* __restrict__ fpp, std::conditional_t<SOFT, SunHitGenArgsSoft, SunHitGenArgs> A) {
   const FrameParams& fp = *fpp;
   const uint32_t tile = blockIdx.x;
   { uint32_t word;
@@ -1132,7 +1151,10 @@ __global__ void __launch_bounds__(256) sunHitGenKernel(const FrameParams* __rest
         const Attrib a = interpAttrib(v, hb1, hb2);
         const f3 N = normalize3(mulDir(a.Nrm, cbLoad3x3(hInst ? fp.g.WorldIT1 : fp.g.WorldITs0)));
         const float NoL = dot3(N, L);
-        if (NoL > 0.0f) {
+        f3 Ls = L;      // SOFT: toward the point of the disk this hit's slot draws; below the horizon there is no ray and no term
+        bool facing = NoL > 0.0f;
+        if constexpr (SOFT) { if (facing) { Ls = sunDiskDirection(A.disk, L, pixel, A.disk.frameIndex, A.disk.slotBase + ((flags ^ (flags >> 1)) & 1u)); facing = dot3(N, Ls) > 0.0f; } }
+        if (facing) {
           const f2 rm = getRoughMetal(fp.mat, hInst, a.UV);
           f3 color = mk3(fp.mat.BaseColors[hInst][0], fp.mat.BaseColors[hInst][1], fp.mat.BaseColors[hInst][2]);
           const f3 V = mk3(-q0.w, -q1.x, -q1.y);
@@ -1156,7 +1178,7 @@ __global__ void __launch_bounds__(256) sunHitGenKernel(const FrameParams* __rest
           }
           want = true;
           sr.ox = q0.x + ht * q0.w; sr.oy = q0.y + ht * q1.x; sr.oz = q0.z + ht * q1.y;      // hitWorldPosition :338-341
-          sr.dx = L.x; sr.dy = L.y; sr.dz = L.z;
+          sr.dx = Ls.x; sr.dy = Ls.y; sr.dz = Ls.z;
           sr.pixel = pixel; sr.skip = hitId;
           sr.wx = q2.x * term.x; sr.wy = q2.y * term.y; sr.wz = q2.z * term.z;             // s_d = T_d * term
           sr.flags = (flags ^ (flags >> 1)) & 1u;                                          // the image the path writes (1: RayTracingOut1)
@@ -1243,7 +1265,7 @@ static int beginSunHits(rtggx_context* c, hipStream_t s, bool wantSums) {
 // One level's hits: generation from the bins q (their rays traced, not yet shaded), the any-hit traversal on the frame's trace grid with this
 // stream's spill part (launchShade), the add into sumRefl / sumDiff
 static int launchSunHits(rtggx_context* c, const FrameParams& fp, hipStream_t s, const TraceQueue& bins, const float4* fat0, const float4* fat1, const uint32_t* tileWords,
-                         uint32_t numTiles, int spillPart, bool samples, float* sumRefl, float* sumDiff) {
+                         uint32_t numTiles, int spillPart, bool samples, float* sumRefl, float* sumDiff, uint32_t frameIndex, uint32_t level) {
   if (numTiles * 4u > c->numBinsMax || c->sunHitSlots != c->binSlots) { setError("rtggx_ray_trace: the queue of rtggx_set_sun_reflections does not hold %u bins of %u slots", numTiles * 4u, c->binSlots); return -1; }
   const rtggx_context::Sun& sun = c->sun;
   SunHitGenArgs G;
@@ -1252,7 +1274,12 @@ static int launchSunHits(rtggx_context* c, const FrameParams& fp, hipStream_t s,
   G.outRays = (RayRec*)c->sunHitRays.get(); G.outHits = (HitKey*)c->sunHitHits.get(); G.outCount = c->sunHitCount;
   G.tileWords = tileWords;
   G.Lx = sun.L[0]; G.Ly = sun.L[1]; G.Lz = sun.L[2]; G.Ex = sun.E[0]; G.Ey = sun.E[1]; G.Ez = sun.E[2];
-  launch(sunHitGenKernel, dim3(numTiles), dim3(256), s, nullptr, nullptr, c->dParams + c->slot, G);
+  if (c->sunAngle.degrees > 0.0f) {      // rtggx_set_sun_angle: the slot base of the level, the frame index of the sample the pass belongs to
+    SunHitGenArgsSoft GS;
+    static_cast<SunHitGenArgs&>(GS) = G;
+    GS.disk = SunDiskArgs{sun.T[0], sun.T[1], sun.T[2], sun.B[0], sun.B[1], sun.B[2], c->sunAngle.k, c->cosSinTab, frameIndex, 1u + 2u * level};
+    launch(sunHitGenKernel<true>, dim3(numTiles), dim3(256), s, nullptr, nullptr, c->dParams + c->slot, GS);
+  } else launch(sunHitGenKernel<false>, dim3(numTiles), dim3(256), s, nullptr, nullptr, c->dParams + c->slot, G);
   const TraceQueue q{G.outRays, G.outHits, G.outCount};
   { const int r = launchTrace(c, fp, s, q, c->traceGrid[0], true, c->traceGrid[1], c->traceGrid[2], c->traceGrid[3], -1, nullptr, nullptr, spillPart, true); if (r) return r; }
   SunHitAddArgs D;
@@ -1307,7 +1334,7 @@ static int launchShadeSamples(rtggx_context* c, const FrameParams& fp, hipStream
         const int r = launchTrace(c, fp, s, q, c->traceGrid[0], true, c->traceGrid[1], c->traceGrid[2], c->traceGrid[3], -1, nullptr, nullptr, spillPart);
         if (r) return r;
       }
-      if (sunHits) { const int r = launchSunHits(c, fp, s, q, S.fat0, S.fat1, S.tileWords, numTiles, spillPart, true, S.accRefl, S.accDiff); if (r) return r; }
+      if (sunHits) { const int r = launchSunHits(c, fp, s, q, S.fat0, S.fat1, S.tileWords, numTiles, spillPart, true, S.accRefl, S.accDiff, fp.g.FrameIndex * N + k, level); if (r) return r; }
       launch(level + 1u < depth ? (wide ? shadeKernel<1, SHADE_SPAWN_ACCUM, true> : shadeKernel<1, SHADE_SPAWN_ACCUM>) : shadeKernel<1, SHADE_ACCUM>, dim3(numTiles), dim3(256), s, nullptr, nullptr, sp + k, S);
       S.carryMask = 0u;      // (carried over once, by the first pass)
       RT_HIP(hipGetLastError());
@@ -1371,7 +1398,7 @@ int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent
       if (r) return r;
       S.carryMask = 0u;      // (carried over once, by the first pass)
     }
-    if (sunHits) { const int r = launchSunHits(c, fp, s, q, S.fat0, S.fat1, S.tileWords, numTiles, spillPart, false, sums[0], sums[1]); if (r) return r; }
+    if (sunHits) { const int r = launchSunHits(c, fp, s, q, S.fat0, S.fat1, S.tileWords, numTiles, spillPart, false, sums[0], sums[1], fp.g.FrameIndex, level); if (r) return r; }
     const int pass = level + 1u < depth ? SHADE_SPAWN : level == 0 ? SHADE_FINAL : SHADE_FINAL_DEEP;
     launch(pass == SHADE_SPAWN && c->sampleSet > RTGGX_MIN_SAMPLE_SET ? kShadeSpawnWide[quad] : kShade[pass][quad], dim3(grid), dim3(256), s, nullptr, pass == SHADE_SPAWN || sunHits ? nullptr : done, dfp, S);
     RT_HIP(hipGetLastError());
@@ -1419,7 +1446,9 @@ struct SunGenArgs {
   const uint32_t* tileWords; uint32_t tilesX, rowBegin, rowEnd;
   float Lx, Ly, Lz, Ex, Ey, Ez;
 };
-__global__ void __launch_bounds__(256) sunGenKernel(const FrameParams* __restrict__ fpp, SunGenArgs A) {
+struct SunGenArgsSoft : SunGenArgs { SunDiskArgs disk; };      // rtggx_set_sun_angle: slot 0, the frame's own index (the constants')
+template <bool SOFT>
+__global__ void __launch_bounds__(256) sunGenKernel(const FrameParams* __restrict__ fpp, std::conditional_t<SOFT, SunGenArgsSoft, SunGenArgs> A) {
   const FrameParams& fp = *fpp;
   const uint32_t tile = blockIdx.x;
   { uint32_t word;
@@ -1457,7 +1486,10 @@ __global__ void __launch_bounds__(256) sunGenKernel(const FrameParams* __restric
       const f3 V = normalize3(eye - P);
       const f3 L = mk3(A.Lx, A.Ly, A.Lz);
       const float NoL = dot3(N, L);
-      if (NoL > 0.0f) {
+      f3 Ls = L;      // SOFT: toward the point of the disk the pixel draws this frame; below the horizon there is no ray and no term
+      bool facing = NoL > 0.0f;
+      if constexpr (SOFT) { if (facing) { Ls = sunDiskDirection(A.disk, L, (uint32_t)pix, fp.g.FrameIndex, 0u); facing = dot3(N, Ls) > 0.0f; } }
+      if (facing) {
         // F D Vis NoL E with the roughness floored at 1/32: a mirror under a delta light has no finite answer
         const float r = fmaxf(rghMtl.x, 1.0f / 32.0f);
         const f3 Hh = normalize3(V + L);
@@ -1470,7 +1502,7 @@ __global__ void __launch_bounds__(256) sunGenKernel(const FrameParams* __restric
         const float vis = visSmith(r, NoV, NoL);
         const float k = (D * vis) * NoL;
         want = true;
-        rr.ox = P.x; rr.oy = P.y; rr.oz = P.z; rr.dx = L.x; rr.dy = L.y; rr.dz = L.z;
+        rr.ox = P.x; rr.oy = P.y; rr.oz = P.z; rr.dx = Ls.x; rr.dy = Ls.y; rr.dz = Ls.z;
         rr.pixel = (uint32_t)pix; rr.skip = (inst << 24) | prim;
         rr.wx = (F.x * k) * A.Ex; rr.wy = (F.y * k) * A.Ey; rr.wz = (F.z * k) * A.Ez;
         rr.flags = __float_as_uint(NoL);
@@ -1520,7 +1552,12 @@ int launchSun(rtggx_context* c, const FrameParams& fp, hipStream_t s) {
   G.tileWords = c->tileWords(rb, re); G.tilesX = tilesX; G.rowBegin = rb; G.rowEnd = re;
   G.Lx = sun.L[0]; G.Ly = sun.L[1]; G.Lz = sun.L[2]; G.Ex = sun.E[0]; G.Ey = sun.E[1]; G.Ez = sun.E[2];
   const FrameParams* const dfp = c->dParams + c->slot;
-  launch(sunGenKernel, dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, G);
+  if (c->sunAngle.degrees > 0.0f) {      // rtggx_set_sun_angle
+    SunGenArgsSoft GS;
+    static_cast<SunGenArgs&>(GS) = G;
+    GS.disk = SunDiskArgs{sun.T[0], sun.T[1], sun.T[2], sun.B[0], sun.B[1], sun.B[2], c->sunAngle.k, c->cosSinTab, 0u, 0u};
+    launch(sunGenKernel<true>, dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, GS);
+  } else launch(sunGenKernel<false>, dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, G);
   // the bins have RT_BIN_MIN slots whatever the frame's have: the launch is told so through the context's slot count for its duration.  Spill part 2
   // is the main stream's (launchShade): the launches that use it are in this stream's order, and nothing beside the stream touches it
   const TraceQueue q{(const RayRec*)c->sunRays.get(), (HitKey*)c->sunHits.get(), c->sunCount};

@@ -280,8 +280,11 @@ struct rtggx_context {
   // rtggx_render_visibility, like the other per-frame settings.  The queue is the sun's own -- the frame's bins are still read by the shading of the
   // frame in flight, and still sky relies on their counts --: one ray slot per pixel of a bin's 8x8 sub-tile, 48 + 8 bytes per pixel and 4 per bin,
   // allocated by the first call that turns the sun on.
-  struct Sun { bool on = false; float L[3] = {}, E[3] = {}; } sun, sunRequested;
+  struct Sun { bool on = false; float L[3] = {}, E[3] = {}, T[3] = {}, B[3] = {}; } sun, sunRequested;      // T, B: the disk's frame about L (rtggx_set_sun_angle), made with L
   rt::DevBuf<void> sunRays, sunHits; rt::DevBuf<uint32_t> sunCount;
+  // rtggx_set_sun_angle: the angular radius of the sun's disk in degrees and k = 1 - cos of it.  Stored whether or not a sun is set; the
+  // frame's, the next frame's.  0: the directional sun, and the SOFT = false kernels (raytrace.hip launchSun, launchSunHits).  No buffer.
+  struct SunAngle { float degrees = 0.0f, k = 0.0f; } sunAngle, sunAngleRequested;
   // rtggx_set_sun_reflections: the sun term and the shadow at the surfaces the paths hit (raytrace.hip launchSunHits).  Stored whether or not a
   // sun is set; the frame's, the next frame's.  Everything below exists from the first frame that has both on (raytrace.hip allocSunHits):
   //   sunHitRays / sunHitHits / sunHitCount   a queue of the feature's own, bins of sunHitSlots = binSlots slots (released when the bins grow)

@@ -38,6 +38,7 @@ void RayTracedGGX::OnInit() {
   if (m_rayRate != 1u && !m_rayTracer->SetRayRate(m_rayRate)) throw std::runtime_error("-rayrate: " + m_rayTracer->GetLastError());      // -rayrate 4: one ray per 2x2 quad (opt-in)
   if (m_hasSun && !m_rayTracer->SetSun(m_sun, m_sun + 3)) throw std::runtime_error("-sun: " + m_rayTracer->GetLastError());      // -sun: a directional light with ray-traced shadows (opt-in)
   if (m_sunReflections && !m_rayTracer->SetSunReflections(true)) throw std::runtime_error("-sunreflections: " + m_rayTracer->GetLastError());      // -sunreflections: ... at the surfaces the paths hit as well (opt-in)
+  if (m_sunAngle != 0.0f && !m_rayTracer->SetSunAngle(m_sunAngle)) throw std::runtime_error("-sunangle: " + m_rayTracer->GetLastError());      // -sunangle: a sun with a size, soft shadows (opt-in)
   if (m_recursionDepth != 1u && !m_rayTracer->SetMaxRecursionDepth(m_recursionDepth)) throw std::runtime_error("-recursion: " + m_rayTracer->GetLastError());      // -recursion N: multi-bounce paths (opt-in)
   if (m_samplesPerPixel != 1u && !m_rayTracer->SetSamplesPerPixel(m_samplesPerPixel)) throw std::runtime_error("-spp: " + m_rayTracer->GetLastError());      // -spp N: multi-sample tracing (opt-in)
   if (m_sampleSet != RTGGX_MIN_SAMPLE_SET && !m_rayTracer->SetSampleSetSize(m_sampleSet)) throw std::runtime_error("-sampleset: " + m_rayTracer->GetLastError());      // -sampleset M: a larger sample set (opt-in)
@@ -209,7 +210,7 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
     return (arg[0] == '-' || arg[0] == '/') && lower(arg + 1) == lower(name);
   };
   // On POSIX an absolute path also starts with '/': such a token is a flag only when it names one.
-  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "sun", "sunreflections", "sunfromenv", "recursion", "spp", "accumulate", "sampleset", "savereference", "reference", "score", "envlayout", "envsize", "envmips", "envprefilter"};
+  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "sun", "sunreflections", "sunfromenv", "sunangle", "recursion", "spp", "accumulate", "sampleset", "savereference", "reference", "score", "envlayout", "envsize", "envmips", "envprefilter"};
   const auto isFlagName = [&](const char* name) { for (const char* f : kFlags) if (lower(name) == f) return true; return false; };
   const auto hasNextArgValue = [&](int i) {
     if (i + 1 >= argc) return false;
@@ -273,6 +274,13 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
       }
       m_sunFromEnv = true; m_sunFromEnvCone = cone;
     }
+    // -sunangle <degrees>: the angular radius of the sun's disk (rtggx_set_sun_angle); checked here, before a device is asked for
+    else if (isArgMatched(i, "sunangle")) {
+      float angle = -1.0f;
+      if (hasNextArgValue(i)) { char* end = nullptr; angle = std::strtof(argv[++i], &end); if (end == argv[i] || *end != '\0') angle = -1.0f; }
+      if (!(angle >= 0.0f && angle <= RTGGX_MAX_SUN_ANGLE_DEGREES)) throw std::runtime_error("-sunangle: the angular radius of the sun's disk in degrees, 0 to 10");
+      m_sunAngle = angle; m_hasSunAngle = true;
+    }
     else if (isArgMatched(i, "rayrate")) {
       const int rate = hasNextArgValue(i) ? std::atoi(argv[++i]) : 0;
       if (rate != 1 && rate != 4) throw std::runtime_error("-rayrate: 1 or 4 pixels per traced ray");
@@ -330,6 +338,7 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
   if (m_sunFromEnv && m_hasSun) throw std::runtime_error("-sunfromenv together with -sun: one sun, measured or given");
   if (m_sunFromEnv && m_rayRate != 1u) throw std::runtime_error("-sunfromenv together with -rayrate 4: refused");
   if (m_sunReflections && !m_hasSun && !m_sunFromEnv) throw std::runtime_error("-sunreflections without -sun: there is no light to reflect");
+  if (m_hasSunAngle && !m_hasSun && !m_sunFromEnv) throw std::runtime_error("-sunangle without -sun or -sunfromenv: there is no sun to give a size");
   // quarter-rate tracing renders whole frames only (rtggx_set_ray_rate): refused here, before anything has touched a GPU
   // one knob asks for fewer rays, the other for more (rtggx_set_samples_per_pixel)
   if (m_rayRate != 1u && m_hasSun) throw std::runtime_error("-sun together with -rayrate 4: refused");

@@ -2,7 +2,7 @@
 // DXFramework virtuals RayTracedGGX/Common/DXFramework.h:23-26): OnInit / OnUpdate / OnRender /
 // OnDestroy, the same command line (RayTracedGGX.cpp:462-511) and the same defaults
 // (RayTracedGGX.cpp:37-39, camera :19-23, 267-277).  What the window supplied interactively is
-// supplied by extra flags: -width -height -frames -dt -metallic -sharedmem -sync -vndf -rayrate -sun -sunreflections -sunfromenv -recursion -spp -sampleset -accumulate -savereference -reference -score -envlayout -envsize -envmips -envprefilter -device -dump -track -deform -gpus -strips -balance.
+// supplied by extra flags: -width -height -frames -dt -metallic -sharedmem -sync -vndf -rayrate -sun -sunreflections -sunfromenv -sunangle -recursion -spp -sampleset -accumulate -savereference -reference -score -envlayout -envsize -envmips -envprefilter -device -dump -track -deform -gpus -strips -balance.
 #pragma once
 #include <vector>
 #include <cstdint>
@@ -141,6 +141,9 @@ class RayTracedGGX {
   // -envprefilter filters it) and set as the light (RayTracer::SetSunFromEnvironment); degrees: the half-angle of the cone about the brightest
   // texel, in (0, 45], 0 here = the library's default of 4; not together with -sun or -rayrate 4; -sunreflections is accepted with it
   bool m_sunFromEnv = false; float m_sunFromEnvCone = 0.0f;
+  // -sunangle <degrees>: the angular radius of the sun's disk, 0 to 10 -- soft shadows (RayTracer::SetSunAngle); needs -sun or -sunfromenv,
+  // and -sunfromenv sets none by itself: its cone is a policy default, not a measurement of the disk
+  float m_sunAngle = 0.0f; bool m_hasSunAngle = false;
   uint32_t m_rayRate = 1;              // -rayrate <1|4>: pixels per traced ray (RayTracer::SetRayRate); 4 renders whole frames only: not with -gpus / -strips
   // -deform <amplitude>: the model breathes -- a travelling sine wave through its vertices, DeformPeriod key shapes computed once
   // at start-up and handed to RayTracer::UpdateMesh one per frame (per-frame host cost: one copy of the vertex array)
