@@ -687,6 +687,59 @@ int  rtggx_set_sun_reflections(rtggx_context* ctx, int enable);
 #define RTGGX_MAX_SUN_ANGLE_DEGREES 10.0f
 int  rtggx_set_sun_angle(rtggx_context* ctx, float degrees);
 
+/* Local lights: up to RTGGX_MAX_LIGHTS point and spot lights inside the scene, each with a range, an optional cone, an optional radius (an
+ * emitting sphere: soft shadows) and ray-traced shadows.  Opt-in: (NULL, 0) turns the lights off, and a context that never calls this, or has
+ * count == 0, allocates and launches exactly what it did.  The lights are copied before the call returns and take effect with the next
+ * rtggx_render_visibility, like the sun.  With a cone the axis is normalised on the host in double and rounded once to fp32 (call it A), the
+ * rule of the sun's direction.  Refused, the context keeping what it had: count > RTGGX_MAX_LIGHTS; a null pointer with count > 0; in any
+ * light a non-finite position; a range that is not finite or not above 0; a non-finite or negative intensity component; a radius that is not
+ * finite, is negative, or is >= the range; with cos_outer > -1 an axis that is non-finite or zero, or cosines that do not satisfy
+ * -1 < cos_outer < cos_inner <= 1; lights on a context at ray rate 4, and rate 4 on a context with lights (the sun's rule, for the sun's
+ * reason).  A light whose intensity is 0 in every component stays in the list and casts no ray: it keeps its index i, and so the hash slots
+ * of the lights behind it.
+ * While count > 0 rtggx_ray_trace runs the lights' pass on the main stream: behind the hit shading, the resolve of N samples and the sun's
+ * pass where there is one; in front of the accumulation, the scoring and rtggx_denoise; RtggxTimings.ray_trace covers it.  For every covered
+ * pixel (visibility word != 0) of the rows ray generation covers, in fp32 without contraction, each operation rounded on its own (sqrt and /
+ * correctly rounded; dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z; normalize(v) = v (1 / sqrt(dot(v, v)))):
+ *   0. the primary surface exactly as in step 1 of rtggx_set_sun: P, N, V, color, (r, m), inst, prim.  S0 = S1 = (+0, +0, +0), n = 0.
+ * Per light i = 0 .. count - 1, ascending, whose intensity I is not 0 in every component; Pl its position, R its range, rho its radius:
+ *   1. D = Pl - P per component; d2 = dot(D, D).  d2 < 1e-6 or d2 >= R R: no ray, no term ("out of range");
+ *   2. L = normalize(D); NoL = dot(N, L); NoL <= 0: no ray, no term ("facing away");
+ *   3. only where cos_outer > -1: c = -dot(L, A); c <= cos_outer: no ray, no term ("outside the cone");
+ *      s = saturate((c - cos_outer) / (cos_inner - cos_outer)); spot = s s.  Without a cone spot = 1;
+ *   4. q = d2 / (R R); win = saturate(1 - q q), then win = win win; m2 = max(rho rho, 1e-4); att = (win spot) / max(d2, m2); E_c = I_c att;
+ *   5. the target.  rho = 0: Ds = D.  rho > 0: h = rng(rng(pixel) + FrameIndex) -- pixel: the full-frame index y W + x (strips agree with
+ *      the whole frame); FrameIndex: the constants' own, whatever N, the map or the sample set are --; w = rng(h + (16 + i) 0x9E3779B9) with
+ *      32-bit wraparound (the sun's passes use the slots 0 .. 8; the lights start at 16); u = (float)(w & 0xffff) / 65536; s = w >> 24;
+ *      cos(phi), sin(phi) = entry s of the 256-entry table of the default sample set, as in step 3 of rtggx_set_sun_angle; z = 1 - 2 u
+ *      (exact); rho' = sqrt(1 - z z); o = (rho' cos(phi), rho' sin(phi), z), uniform on the sphere; Ds_c = D_c + rho o_c.  In both cases
+ *      ds2 = dot(Ds, Ds); ds2 < 1e-6: no ray, no term; Ls = normalize(Ds); tmax = sqrt(ds2).  With rho = 0 Ls and L are the same bits;
+ *   6. dot(N, Ls) <= 0: no ray, no term ("below the horizon"; with rho = 0 it cannot differ from step 2);
+ *   7. a shadow ray from P along Ls over (1e-5, tmax), both bounds exclusive, skipping (inst, prim), through the any-hit traversal: the light
+ *      is not geometry, and nothing behind the target occludes.  rtggx_ray_count / rtggx_ray_total count it.  Occluded: no term;
+ *   8. the term, as in step 4 of rtggx_set_sun with this L and E, evaluated at the centre direction L (only visibility is sampled, as with
+ *      the sun's disk): r' = max(r, 1/32); H, NoH, VoH, NoV, D, f0, F, vis as there; k = (D vis) NoL; spec_c = (F_c k) E_c; S0 = S0 + spec.
+ *      Where m < 1: g = (NoL / pi) att; diff_c = ((color_c (1 - 0.04)) g) I_c; S1 = S1 + diff.  n = n + 1.
+ * Behind the last light, where n > 0: RayTracingOut0 = pack(unpack(RayTracingOut0) + S0), and where also m < 1 RayTracingOut1 =
+ * pack(unpack(RayTracingOut1) + S1).  Where n = 0 both words stay bit for bit; where m >= 1 RayTracingOut1 is a carry-over and is never
+ * touched; background pixels are untouched.  The order of every sum is the order of the lights; there are no atomics, and the image is a pure
+ * function of the inputs.  The pass is independent of recursion depth, sample count, sample map, sample set and sampler; it ends no still-sky
+ * run and resets no accumulation; it works on strips, with a deforming mesh, a caller-owned stream and rtggx_set_async_compute(0).
+ * Known limit: surfaces seen in reflections get no light term -- a reflection shows the ground without the lamp and without its shadow; the
+ * sun's rtggx_set_sun_reflections has no counterpart for the lights yet.
+ * Per light three kernels (one generating the shadow rays, the any-hit traversal, one adding the unoccluded terms to S), and one more behind
+ * the last light.  Memory, from the first frame with lights until rtggx_destroy: ONE queue for all lights with the rays' intervals beside it --
+ * 56 + 8 bytes per pixel and 4 per 8x8 block -- and S, 32 bytes per pixel (two images of r, g, b and the number of terms), all zero between
+ * frames.  tests/lights_ref.cpp restates the rule. */
+typedef struct RtggxLight {                 /* 64 bytes */
+  float position[3];  float range;          /* world space; R > 0: at and beyond R the light does nothing */
+  float intensity[3]; float radius;         /* I, rgb: radiant intensity, E = I / d^2 in the units of rtggx_set_sun's E; rho >= 0: radius of the emitting sphere */
+  float axis[3];      float cos_outer;      /* spot: axis points FROM the light INTO the scene; cos_outer <= -1: no cone (a point light), axis not read */
+  float cos_inner;    float pad[3];         /* pad is not read */
+} RtggxLight;
+#define RTGGX_MAX_LIGHTS 8u
+int  rtggx_set_lights(rtggx_context* ctx, const RtggxLight* lights, uint32_t count);
+
 /* The sun from the environment: finds the sun in the current cube, measures its direction and irradiance -- what rtggx_set_sun wants -- and,
  * where asked, takes it out of the cube, so that a probe with a sun in it does not light the scene twice (once analytically, with shadows, and
  * once more through the environment lookups, the SH irradiance and every level of the chain).  A setup call, not per frame; opt-in: a context

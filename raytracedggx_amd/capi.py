@@ -23,6 +23,7 @@ ENV_EQUIRECT, ENV_VCROSS, ENV_HCROSS = 0, 1, 2      # layouts and pixel formats 
 PIXELS_RGBE8, PIXELS_RGB32F = 0, 1
 ENV_FILTER_MIN_SAMPLES, ENV_FILTER_MAX_SAMPLES = 64, 4096      # rtggx_prefilter_env
 MAX_SUN_ANGLE_DEGREES = 10.0                                    # rtggx_set_sun_angle
+MAX_LIGHTS = 8                                                  # rtggx_set_lights
 
 _BUF_DTYPE = {BUF_VISIBILITY: np.uint32, BUF_DEPTH: np.uint32, BUF_NORMAL: np.uint32, BUF_ROUGH_METAL: np.uint16,
               BUF_VELOCITY: np.uint32, BUF_RT_REFL: np.uint32, BUF_RT_DIFF: np.uint32, BUF_TSS0: np.uint64, BUF_TSS1: np.uint64,
@@ -42,7 +43,7 @@ EXPORTS = ["rtggx_last_error", "rtggx_create", "rtggx_destroy", "rtggx_set_strip
            "rtggx_set_reference", "rtggx_reference_from_accumulation", "rtggx_set_scoring", "rtggx_read_scores",
            "rtggx_set_env_image", "rtggx_generate_env_mips", "rtggx_prefilter_env",
            "rtggx_set_sample_map", "rtggx_read_sample_map", "rtggx_trace_occlusion", "rtggx_set_sun", "rtggx_set_sun_reflections",
-           "rtggx_sun_from_env", "rtggx_set_sun_angle"]
+           "rtggx_sun_from_env", "rtggx_set_sun_angle", "rtggx_set_lights"]
 SCORE_RING = 256
 
 
@@ -78,6 +79,16 @@ class SunEstimate(C.Structure):
                 v = getattr(self, n)
                 out[n] = v if t in (C.c_double, C.c_uint32) else np.array(list(v), np.float64 if t == C.c_double * 3 else np.float32)
         return out
+
+
+class Light(C.Structure):
+    """RtggxLight (rtggx.h), 64 bytes: a point light, or with cos_outer > -1 a spot along `axis`; radius > 0: an emitting sphere."""
+    _fields_ = [("position", C.c_float * 3), ("range", C.c_float), ("intensity", C.c_float * 3), ("radius", C.c_float),
+                ("axis", C.c_float * 3), ("cos_outer", C.c_float), ("cos_inner", C.c_float), ("pad", C.c_float * 3)]
+
+    @classmethod
+    def of(cls, position, intensity, range, radius=0.0, axis=(0.0, 0.0, 0.0), cos_outer=-1.0, cos_inner=1.0):
+        return cls((C.c_float * 3)(*position), range, (C.c_float * 3)(*intensity), radius, (C.c_float * 3)(*axis), cos_outer, cos_inner)
 
 
 _lib = None
@@ -147,6 +158,7 @@ def load():
     L.rtggx_set_sun.argtypes = [vp, vp, vp]
     L.rtggx_set_sun_reflections.argtypes = [vp, C.c_int]
     L.rtggx_set_sun_angle.argtypes = [vp, C.c_float]
+    L.rtggx_set_lights.argtypes = [vp, C.POINTER(Light), C.c_uint32]
     L.rtggx_sun_from_env.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_int, C.POINTER(SunEstimate)]
     L.rtggx_ray_total.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
     L.rtggx_kernel_times.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
@@ -612,6 +624,14 @@ class Context:
         """The angular radius of the sun's disk in degrees, 0 to MAX_SUN_ANGLE_DEGREES, from the next frame on: shadow rays toward a point
         of the disk (include/rtggx.h has the rule).  0: the directional sun.  It acts only while a sun is set."""
         self._check(self.L.rtggx_set_sun_angle(self.h, float(degrees)))
+
+    def set_lights(self, lights):
+        """Point and spot lights with ray-traced shadows from the next frame on (include/rtggx.h has the rule): a sequence of Light, or of
+        dicts with Light.of's arguments; None or an empty sequence turns them off."""
+        lights = [l if isinstance(l, Light) else Light.of(**l) for l in (lights or ())]
+        if not lights:
+            return self._check(self.L.rtggx_set_lights(self.h, None, 0))
+        self._check(self.L.rtggx_set_lights(self.h, (Light * len(lights))(*lights), len(lights)))
 
     def sun_from_env(self, cone=0, ring=0, min_contrast=0, remove=False):
         """The sun of the current environment (include/rtggx.h): the record as a dict (SunEstimate.as_dict) -- "direction" and "irradiance" are

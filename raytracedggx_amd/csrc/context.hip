@@ -359,6 +359,7 @@ int rtggx_set_ray_rate(rtggx_context* c, uint32_t pixelsPerRay) {
   if (pixelsPerRay != 1u && c->samplesRequested > 1u) { setError("rtggx_set_ray_rate: rate %u on a context tracing %u samples per pixel (rtggx_set_samples_per_pixel): one asks for fewer rays, the other for more", pixelsPerRay, c->samplesRequested); return -1; }
   if (pixelsPerRay != 1u && c->accumulateRequested) { setError("rtggx_set_ray_rate: rate %u on an accumulating context (rtggx_set_accumulation): three quarters of such a frame are interpolations", pixelsPerRay); return -1; }
   if (pixelsPerRay != 1u && c->sunRequested.on) { setError("rtggx_set_ray_rate: rate %u on a context with a sun (rtggx_set_sun): three quarters of such a frame are interpolations", pixelsPerRay); return -1; }
+  if (pixelsPerRay != 1u && c->lightsRequested.count) { setError("rtggx_set_ray_rate: rate %u on a context with lights (rtggx_set_lights): three quarters of such a frame are interpolations", pixelsPerRay); return -1; }
   if (pixelsPerRay != 1u && (c->rowBegin > 0u || c->rowEnd < c->H)) { setError("rtggx_set_ray_rate: rate %u on a strip (rows [%u,%u) of %u): whole frames only", pixelsPerRay, c->rowBegin, c->rowEnd, c->H); return -1; }
   if (pixelsPerRay == c->rayRate) return 0;
   RT_HIP(syncStreams(c));
@@ -475,6 +476,34 @@ int rtggx_set_sun_reflections(rtggx_context* c, int enable) {
   RT_CHECK_CTX(c);
   if (enable != 0 && enable != 1) { setError("rtggx_set_sun_reflections: %d: 0 or 1", enable); return -1; }
   c->sunReflectionsRequested = enable == 1;
+  return 0;
+}
+// Local lights (include/rtggx.h).  The list is checked as a whole and copied; a cone's axis is normalised in double and rounded once, the sun's
+// rule.  (NULL, 0) turns the lights off.  A refused call leaves what the context had.  Nothing is allocated here (the first frame with lights
+// does: raytrace.hip allocLights).  No synchronisation, no end of a still-sky run, no reset of an accumulation, as for the sun.
+int rtggx_set_lights(rtggx_context* c, const RtggxLight* lights, uint32_t count) {
+  RT_CHECK_CTX(c);
+  if (count > RTGGX_MAX_LIGHTS) { setError("rtggx_set_lights: %u lights: at most %u", count, RTGGX_MAX_LIGHTS); return -1; }
+  if (count && !lights) { setError("rtggx_set_lights: %u lights at a null pointer", count); return -1; }
+  if (count && c->rayRate != 1u) { setError("rtggx_set_lights: on a context tracing one pixel in %u (rtggx_set_ray_rate): three quarters of such a frame are interpolations", c->rayRate); return -1; }
+  rtggx_context::Lights next;
+  for (uint32_t i = 0; i < count; ++i) {
+    RtggxLight l = lights[i];
+    for (int k = 0; k < 3; ++k) if (!std::isfinite(l.position[k])) { setError("rtggx_set_lights: light %u: position component %d is %g: finite", i, k, (double)l.position[k]); return -1; }
+    if (!std::isfinite(l.range) || !(l.range > 0.0f)) { setError("rtggx_set_lights: light %u: a range of %g: finite and above 0", i, (double)l.range); return -1; }
+    for (int k = 0; k < 3; ++k) if (!std::isfinite(l.intensity[k]) || l.intensity[k] < 0.0f) { setError("rtggx_set_lights: light %u: intensity component %d is %g: finite and not negative", i, k, (double)l.intensity[k]); return -1; }
+    if (!std::isfinite(l.radius) || l.radius < 0.0f || !(l.radius < l.range)) { setError("rtggx_set_lights: light %u: a radius of %g: finite, not negative and below the range %g", i, (double)l.radius, (double)l.range); return -1; }
+    if (l.cos_outer > -1.0f) {      // a cone; (a NaN here is no cone by this test and is refused with the cosines below)
+      const double x = l.axis[0], y = l.axis[1], z = l.axis[2], len = std::sqrt(x * x + y * y + z * z);
+      if (!std::isfinite(len) || !(len > 0.0)) { setError("rtggx_set_lights: light %u: the axis (%g, %g, %g) has no finite, non-zero length", i, x, y, z); return -1; }
+      if (!(l.cos_outer < l.cos_inner && l.cos_inner <= 1.0f)) { setError("rtggx_set_lights: light %u: cosines %g (outer) and %g (inner): -1 < outer < inner <= 1", i, (double)l.cos_outer, (double)l.cos_inner); return -1; }
+      l.axis[0] = (float)(x / len); l.axis[1] = (float)(y / len); l.axis[2] = (float)(z / len);
+    } else if (!(l.cos_outer <= -1.0f)) { setError("rtggx_set_lights: light %u: cos_outer is %g: at most -1 (no cone), or -1 < outer < inner <= 1", i, (double)l.cos_outer); return -1; }
+    l.pad[0] = l.pad[1] = l.pad[2] = 0.0f;
+    next.l[i] = l;
+  }
+  next.count = count;
+  c->lightsRequested = next;
   return 0;
 }
 // Sums and count back to zero: two clears on the main stream, behind the frames it holds and in front of the next one; nothing waits.

@@ -195,7 +195,7 @@ int rtggx_render_visibility(rtggx_context* c) {
   if (!c->shDone && c->env.texels) { const int r = projectSH(c, c->streamAS); if (r) return r; }   // first frame only, RayTracer.cpp:345-350
   settleSetRead(c);      // (the previous frame ended without the kernel that would have carried its set's event)
   ++c->frameCounter;
-  c->maxDepth = c->depthRequested; c->samples = c->samplesRequested; c->accumulate = c->accumulateRequested; c->sun = c->sunRequested; c->sunAngle = c->sunAngleRequested; c->sunReflections = c->sunReflectionsRequested;
+  c->maxDepth = c->depthRequested; c->samples = c->samplesRequested; c->accumulate = c->accumulateRequested; c->sun = c->sunRequested; c->sunAngle = c->sunAngleRequested; c->sunReflections = c->sunReflectionsRequested; c->lights = c->lightsRequested;
   c->scoring = c->scoringRequested && c->reference != nullptr;
   c->sampleMap = c->sampleMapRequested;      // rtggx_set_sample_map: the setter has waited for every stream and written the copy no frame reads
   bool resendConstants = false;
@@ -313,6 +313,12 @@ int rtggx_ray_trace(rtggx_context* c) {
   // mesh the shadow launch reads this set's tree: the main stream follows the traversal's event, which followed the refit's.
   if (c->sun.on) {
     if (!r) r = launchSun(c, fp, c->streamMain);
+    c->shadeStream = c->diffStream = c->streamMain;
+  }
+  // local lights (rtggx_set_lights): per light three kernels and one resolve behind the last, on the main stream behind the sun's pass, for
+  // the sun's reasons -- both traced images are complete here, and from here on the main stream is who wrote them last
+  if (c->lights.count) {
+    if (!r) r = launchLights(c, fp, c->streamMain);
     c->shadeStream = c->diffStream = c->streamMain;
   }
   // accumulation (rtggx_set_accumulation): the frame's two traced images into the running sums, on the main stream.  Both images are

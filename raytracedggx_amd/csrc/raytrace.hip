@@ -1574,6 +1574,203 @@ int launchSun(rtggx_context* c, const FrameParams& fp, hipStream_t s) {
   return 0;
 }
 
+// ---- local lights (rtggx_set_lights; include/rtggx.h has the per-pixel rule, DESIGN.md section 9 "Local lights") -----------------------------
+// The sun's pass with a light inside the scene: per light, in index order on the main stream, lightGenKernel derives the primary surface as
+// sunGenKernel does, runs steps 1-6 of the rule and compacts one shadow ray into the wave's bin of ONE queue all lights share -- the specular
+// term in the record's weight, g = (NoL / pi) att in its flags word, the ray's own interval (1e-5, tmax) in a float2 array beside the queue --;
+// the any-hit traversal reads that interval through TraceArgs::tRange; lightAddKernel, one lane per slot, adds an unoccluded ray's terms to the
+// pixel's fp32 sums (a pixel has at most one slot per light and the lights follow each other in stream order: no two lanes meet, no atomics,
+// the order of a sum is the order of the lights).  Behind the last light sunHitResolveKernel packs the sums into the words and leaves them zero.
+// CONE and SOFT change the instruction stream: a context with point lights of radius 0 pays for neither the cone nor the hash.
+struct LightGenArgs {
+  const unsigned long long* visDepth; const float4* fat0; const float4* fat1;
+  RayRec* rays; HitKey* hits; uint32_t* binCount; float2* tRange;
+  const uint32_t* tileWords; uint32_t tilesX, rowBegin, rowEnd;
+  float Px, Py, Pz, range, Ix, Iy, Iz, radius, Ax, Ay, Az, cosOuter, cosInner;
+  const float* cosSin; uint32_t slot;      // SOFT: the 256-entry table, and 16 + i
+};
+template <bool CONE, bool SOFT>
+__global__ void __launch_bounds__(256) lightGenKernel(const FrameParams* __restrict__ fpp, LightGenArgs A) {
+  const FrameParams& fp = *fpp;
+  const uint32_t tile = blockIdx.x;
+  { uint32_t word;
+    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(word) : "s"(A.tileWords), "s"(tile * 4u) : "memory");
+    if (word == 0u) return; }
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const uint32_t px = (tile % A.tilesX) * 16 + (wave & 1u) * 8 + (lane & 7u);
+  const uint32_t py = A.rowBegin + (tile / A.tilesX) * 16 + (wave >> 1) * 8 + (lane >> 3);
+  bool want = false;
+  RayRec rr;
+  float tmax = 0.0f;
+  if (px < fp.W && py < A.rowEnd) {
+    const uint32_t W = fp.W, H = fp.H;
+    const size_t pix = (size_t)py * W + px;
+    uint32_t visibility = (uint32_t)A.visDepth[pix];
+    if (visibility > 0) {      // step 0: getPrimarySurface :277-333, the covered branch, as in sunGenKernel
+      --visibility;
+      const uint32_t inst = visibility >> 24;
+      uint32_t prim = visibility & 0xFFFFFFu;
+      asm volatile("" : "+v"(prim));      // see shadeKernel
+      f2 screenPos; screenPos.x = ((float)px + 0.5f) / (float)W * 2.0f - 1.0f; screenPos.y = ((float)py + 0.5f) / (float)H * 2.0f - 1.0f;
+      screenPos.y = -screenPos.y;
+      const f3 eye = mk3(fp.rg.EyePt[0], fp.rg.EyePt[1], fp.rg.EyePt[2]);
+      const Tri3 v = getVertices(inst ? A.fat1 : A.fat0, prim);
+      const M4 wvp = cbLoad4x4(fp.g.WorldViewProjs[inst]);
+      f4 p[3];
+      for (int k = 0; k < 3; ++k) p[k] = mulPoint(v.pos[k], wvp);
+      screenPos.x -= fp.rg.ProjBias[0]; screenPos.y -= fp.rg.ProjBias[1];
+      const f2 bary = calcBarycentrics(p, screenPos);
+      const Attrib a = interpAttrib(v, bary.x, bary.y);
+      const f3 color = mk3(fp.mat.BaseColors[inst][0], fp.mat.BaseColors[inst][1], fp.mat.BaseColors[inst][2]);
+      const f2 rghMtl = getRoughMetal(fp.mat, inst, a.UV);
+      const f4 P4 = mulPoint(a.Pos, cbLoad4x3(fp.g.Worlds[inst]));
+      const f3 P = mk3(P4.x, P4.y, P4.z);
+      const f3 N = normalize3(mulDir(a.Nrm, cbLoad3x3(inst ? fp.g.WorldIT1 : fp.g.WorldITs0)));
+      const f3 V = normalize3(eye - P);
+      // steps 1 and 2: in range, facing
+      const f3 D = mk3(A.Px - P.x, A.Py - P.y, A.Pz - P.z);
+      const float d2 = dot3(D, D), RR = A.range * A.range;
+      const f3 L = normalize3(D);
+      const float NoL = dot3(N, L);
+      bool lit = d2 >= 1e-6f && d2 < RR && NoL > 0.0f;
+      float spot = 1.0f;
+      if constexpr (CONE) {      // step 3
+        const float c = -dot3(L, mk3(A.Ax, A.Ay, A.Az));
+        const float t = saturatef((c - A.cosOuter) / (A.cosInner - A.cosOuter));
+        spot = t * t;
+        lit = lit && c > A.cosOuter;
+      }
+      f3 Ds = D;
+      if constexpr (SOFT) {      // step 5: a point of the emitting sphere, uniform over its surface
+        if (lit) {
+          uint32_t h = rng((uint32_t)pix); h += fp.g.FrameIndex; h = rng(h);
+          const uint32_t w = rng(h + A.slot * 0x9E3779B9u);
+          const float u = (float)(w & 0xffffu) / 65536.0f;
+          const uint32_t s = w >> 24;
+          const float z = 1.0f - 2.0f * u, rho = sqrtf(1.0f - z * z);
+          Ds = mk3(D.x + A.radius * (rho * A.cosSin[s]), D.y + A.radius * (rho * A.cosSin[256u + s]), D.z + A.radius * z);
+        }
+      }
+      const float ds2 = dot3(Ds, Ds);
+      const f3 Ls = normalize3(Ds);
+      lit = lit && ds2 >= 1e-6f && dot3(N, Ls) > 0.0f;      // step 6
+      if (lit) {
+        // step 4: the window, the floor, E = I att
+        const float q = d2 / RR;
+        float win = saturatef(1.0f - q * q); win = win * win;
+        const float m2 = fmaxf(A.radius * A.radius, 1e-4f);
+        const float att = (win * spot) / fmaxf(d2, m2);
+        // step 8: sunGenKernel's term at the centre direction L
+        const float r = fmaxf(rghMtl.x, 1.0f / 32.0f);
+        const f3 Hh = normalize3(V + L);
+        const float NoH = saturatef(dot3(N, Hh)), VoH = saturatef(dot3(V, Hh)), NoV = saturatef(dot3(N, V));
+        const float al = r * r, a2 = al * al;
+        const float d = (NoH * a2 - NoH) * NoH + 1.0f;
+        const float Dg = a2 / ((RT_PI * d) * d);
+        const f3 f0 = mk3(lerpf(0.04f, color.x, rghMtl.y), lerpf(0.04f, color.y, rghMtl.y), lerpf(0.04f, color.z, rghMtl.y));
+        const f3 F = fSchlick(f0, VoH);
+        const float vis = visSmith(r, NoV, NoL);
+        const float k = (Dg * vis) * NoL;
+        want = true;
+        tmax = sqrtf(ds2);
+        rr.ox = P.x; rr.oy = P.y; rr.oz = P.z; rr.dx = Ls.x; rr.dy = Ls.y; rr.dz = Ls.z;
+        rr.pixel = (uint32_t)pix; rr.skip = (inst << 24) | prim;
+        rr.wx = (F.x * k) * (A.Ix * att); rr.wy = (F.y * k) * (A.Iy * att); rr.wz = (F.z * k) * (A.Iz * att);
+        rr.flags = __float_as_uint((NoL / RT_PI) * att);
+      }
+    }
+  }
+  const uint32_t bin = blockIdx.x * 4u + wave;
+  const unsigned long long mask = __ballot(want), below = (1ull << lane) - 1ull;
+  if (want) {
+    const size_t k = (size_t)bin * RT_BIN_MIN + (uint32_t)__popcll(mask & below);
+    A.rays[k] = rr; A.hits[k] = hitKey(tmax, 0xFFFFFFFFu); A.tRange[k] = make_float2(RT_RAY_TMIN, tmax);
+  }
+  if (lane == 0) A.binCount[bin] = (uint32_t)__popcll(mask);
+}
+struct LightAddArgs {
+  const RayRec* rays; const HitKey* hits; const uint32_t* binCount; const uint32_t* tileWords;
+  float4* sumRefl; float4* sumDiff; float Ix, Iy, Iz;
+};
+__global__ void __launch_bounds__(256) lightAddKernel(const FrameParams* __restrict__ fpp, LightAddArgs A) {
+  const FrameParams& fp = *fpp;
+  { uint32_t word;
+    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(word) : "s"(A.tileWords), "s"(blockIdx.x * 4u) : "memory");
+    if (word == 0u) return; }
+  const uint32_t bin = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (lane >= A.binCount[bin]) return;
+  const size_t k = (size_t)bin * RT_BIN_MIN + lane;
+  if (hitKeyId(A.hits[k]) != 0xFFFFFFFFu) return;      // occluded: no term
+  const RayRec rr = A.rays[k];
+  const uint32_t inst = rr.skip >> 24;
+  const float4 s0 = A.sumRefl[rr.pixel];
+  A.sumRefl[rr.pixel] = make_float4(s0.x + rr.wx, s0.y + rr.wy, s0.z + rr.wz, s0.w + 1.0f);
+  if (fp.mat.RoughMetals[inst][1] < 1.0f) {      // rghMtl.y < 1 is the instance's constant (launchShade); elsewhere RayTracingOut1 is a carry-over and stays
+    const float g = __uint_as_float(rr.flags);
+    const float4 s1 = A.sumDiff[rr.pixel];
+    A.sumDiff[rr.pixel] = make_float4(s1.x + ((fp.mat.BaseColors[inst][0] * (1.0f - 0.04f)) * g) * A.Ix, s1.y + ((fp.mat.BaseColors[inst][1] * (1.0f - 0.04f)) * g) * A.Iy,
+                                      s1.z + ((fp.mat.BaseColors[inst][2] * (1.0f - 0.04f)) * g) * A.Iz, s1.w + 1.0f);
+  }
+}
+// What the lights need, from the first frame that has some: the queue, its intervals and counts, the sums
+static int allocLights(rtggx_context* c) {
+  bool cleared = false;
+  const size_t slots = (size_t)c->numBinsMax * RT_BIN_MIN;
+  if (!c->lightRays) RT_HIP(alloc(c->lightRays, slots * sizeof(RayRec)));
+  if (!c->lightHits) RT_HIP(alloc(c->lightHits, slots * sizeof(HitKey)));
+  if (!c->lightRange) RT_HIP(alloc(c->lightRange, slots * sizeof(float2)));
+  if (!c->lightCount) { RT_HIP(allocFilled(c->lightCount, (size_t)c->numBinsMax)); cleared = true; }
+  if (!c->lightSums) { RT_HIP(allocFilled(c->lightSums, (size_t)c->W * c->H * 8u)); cleared = true; }
+  if (cleared) RT_HIP(hipStreamSynchronize(nullptr));      // (the clears run on the null stream, which this context's streams are not ordered against)
+  return 0;
+}
+int launchLights(rtggx_context* c, const FrameParams& fp, hipStream_t s) {
+  uint32_t rb, re;
+  passRows(fp, ROWS_GBUFFER, rb, re);
+  if (re <= rb) return 0;
+  const uint32_t tilesX = (fp.W + 15) / 16, tilesY = (re - rb + 15) / 16, numTiles = tilesX * tilesY;
+  if (numTiles * 4u > c->numBinsMax) { setError("rtggx_ray_trace: the lights' queue does not hold %u bins", numTiles * 4u); return -1; }
+  { const int r = allocLights(c); if (r) return r; }
+  const InputSet& set = c->cur();
+  const FrameParams* const dfp = c->dParams + c->slot;
+  LightGenArgs G;
+  G.visDepth = c->curVis().depth; G.fat0 = c->mesh[0].fat; G.fat1 = c->mesh[1].fat;
+  G.rays = (RayRec*)c->lightRays.get(); G.hits = (HitKey*)c->lightHits.get(); G.binCount = c->lightCount; G.tRange = (float2*)c->lightRange.get();
+  G.tileWords = c->tileWords(rb, re); G.tilesX = tilesX; G.rowBegin = rb; G.rowEnd = re;
+  G.cosSin = c->cosSinTab;
+  const TraceQueue q{G.rays, G.hits, G.binCount};
+  LightAddArgs D;
+  D.rays = q.rays; D.hits = q.hits; D.binCount = q.binCount; D.tileWords = G.tileWords;
+  D.sumRefl = (float4*)c->lightSums.get(); D.sumDiff = D.sumRefl + (size_t)c->W * c->H;
+  for (uint32_t i = 0; i < c->lights.count; ++i) {
+    const RtggxLight& l = c->lights.l[i];
+    if (!(l.intensity[0] > 0.0f || l.intensity[1] > 0.0f || l.intensity[2] > 0.0f)) continue;      // keeps its index, casts no ray
+    G.Px = l.position[0]; G.Py = l.position[1]; G.Pz = l.position[2]; G.range = l.range;
+    G.Ix = l.intensity[0]; G.Iy = l.intensity[1]; G.Iz = l.intensity[2]; G.radius = l.radius;
+    G.Ax = l.axis[0]; G.Ay = l.axis[1]; G.Az = l.axis[2]; G.cosOuter = l.cos_outer; G.cosInner = l.cos_inner;
+    G.slot = 16u + i;
+    const bool cone = l.cos_outer > -1.0f, soft = l.radius > 0.0f;
+    launch(cone ? (soft ? lightGenKernel<true, true> : lightGenKernel<true, false>) : (soft ? lightGenKernel<false, true> : lightGenKernel<false, false>),
+           dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, G);
+    // the sun's launch (launchSun): bins of RT_BIN_MIN slots and spill part 2, told through the context for the launch's duration -- and the
+    // rays' own intervals beside them
+    const uint32_t frameSlots = c->binSlots;
+    c->binSlots = RT_BIN_MIN; c->traceRayRange = c->lightRange.get();
+    const int r = launchTrace(c, fp, s, q, numTiles * 4u, true, tilesX, tilesY, c->traceGrid[3], -1, nullptr, nullptr, 2, true);
+    c->binSlots = frameSlots; c->traceRayRange = nullptr;
+    if (r) return r;
+    D.Ix = G.Ix; D.Iy = G.Iy; D.Iz = G.Iz;
+    launch(lightAddKernel, dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, D);
+    RT_HIP(hipGetLastError());
+  }
+  SunHitResolveArgs R;
+  R.sumRefl = D.sumRefl; R.sumDiff = D.sumDiff; R.reflOut = set.rtRefl; R.diffOut = set.rtDiff;
+  R.tileWords = G.tileWords; R.tilesX = tilesX; R.rowBegin = rb; R.rowEnd = re;
+  launch(sunHitResolveKernel, dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, R);
+  RT_HIP(hipGetLastError());
+  return 0;
+}
+
 // ---- test entry: closest-hit queries for an explicit ray list (through the same trace kernel) ---------------
 __global__ void fillTestQueue(const float* __restrict__ rays, uint32_t n, uint32_t binSlots, RayRec* q0, HitKey* keys, uint32_t* binCount, float2* tRange) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -296,6 +296,15 @@ struct rtggx_context {
   rt::DevBuf<void> sunHitRays, sunHitHits; rt::DevBuf<uint32_t> sunHitCount; rt::DevBuf<float> sunHitSums;
   uint32_t sunHitSlots = 0;
   hipStream_t sunHitStream = nullptr; rt::Event evSunHit;
+  // rtggx_set_lights: point and spot lights with ray-traced shadows (raytrace.hip launchLights).  The requested list takes effect with the next
+  // rtggx_render_visibility, like the sun.  Everything below exists from the first frame with count > 0 (raytrace.hip allocLights):
+  //   lightRays / lightHits / lightCount   ONE queue in the sun's format for all lights -- bins of RT_BIN_MIN slots --, refilled light by light
+  //   lightRange   the rays' own (tmin, tmax), one float2 per slot of that queue (launchTrace's traceRayRange for the launch's duration)
+  //   lightSums    S0 and S1: [2][W * H] float4 -- the sum of the terms r, g, b and the number of terms --, all zero between frames (the
+  //                resolve leaves them so)
+  // The pass runs on the main stream only: consecutive frames' kernels follow each other there.
+  struct Lights { uint32_t count = 0; RtggxLight l[RTGGX_MAX_LIGHTS] = {}; } lights, lightsRequested;
+  rt::DevBuf<void> lightRays, lightHits, lightRange; rt::DevBuf<uint32_t> lightCount; rt::DevBuf<float> lightSums;
   uint32_t rayRate = 1;          // rtggx_set_ray_rate: pixels per traced ray, 1 or 4 (raytrace.hip rayGenKernel, reconstructKernel)
   uint32_t maxDepth = 1, depthRequested = 1;      // rtggx_set_max_recursion_depth: 1..4 levels of rays per path (raytrace.hip launchShade); the frame's, the next frame's
   // rtggx_set_samples_per_pixel: 1, 2, 4 or 8 samples per covered pixel (raytrace.hip launchShade; DESIGN.md "Samples per pixel"); the
@@ -507,6 +516,7 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
 // 5-7 us, and the frame's two chains had four of them (rocprofv3 kernel trace, profiles/).
 int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent_t done = nullptr);      // hit / miss shading of the traced bins
 int launchSun(rtggx_context* c, const FrameParams& fp, hipStream_t s);      // rtggx_set_sun: shadow rays from the primary surface, the any-hit traversal, the add into RayTracingOut0/1
+int launchLights(rtggx_context* c, const FrameParams& fp, hipStream_t s);   // rtggx_set_lights: per light generate -> any-hit -> add into the sums, one resolve into RayTracingOut0/1
 int launchReconstruct(rtggx_context* c, const FrameParams& fp, hipStream_t s);      // rate 4: the untraced pixels of RayTracingOut0/1, after the hit shading
 int allocSamples(rtggx_context* c);      // what N > 1 samples per pixel need (rtggx_context::sppAcc, sppParams), once
 int allocAccumulation(rtggx_context* c);      // what rtggx_set_accumulation needs (rtggx_context::accRefl, accDiff, converged), once

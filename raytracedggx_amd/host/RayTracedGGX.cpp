@@ -38,6 +38,7 @@ void RayTracedGGX::OnInit() {
   if (m_rayRate != 1u && !m_rayTracer->SetRayRate(m_rayRate)) throw std::runtime_error("-rayrate: " + m_rayTracer->GetLastError());      // -rayrate 4: one ray per 2x2 quad (opt-in)
   if (m_hasSun && !m_rayTracer->SetSun(m_sun, m_sun + 3)) throw std::runtime_error("-sun: " + m_rayTracer->GetLastError());      // -sun: a directional light with ray-traced shadows (opt-in)
   if (m_sunReflections && !m_rayTracer->SetSunReflections(true)) throw std::runtime_error("-sunreflections: " + m_rayTracer->GetLastError());      // -sunreflections: ... at the surfaces the paths hit as well (opt-in)
+  if (!m_lights.empty() && !m_rayTracer->SetLights(m_lights.data(), (uint32_t)m_lights.size())) throw std::runtime_error("-light / -spot: " + m_rayTracer->GetLastError());      // -light, -spot: local lights with ray-traced shadows (opt-in)
   if (m_sunAngle != 0.0f && !m_rayTracer->SetSunAngle(m_sunAngle)) throw std::runtime_error("-sunangle: " + m_rayTracer->GetLastError());      // -sunangle: a sun with a size, soft shadows (opt-in)
   if (m_recursionDepth != 1u && !m_rayTracer->SetMaxRecursionDepth(m_recursionDepth)) throw std::runtime_error("-recursion: " + m_rayTracer->GetLastError());      // -recursion N: multi-bounce paths (opt-in)
   if (m_samplesPerPixel != 1u && !m_rayTracer->SetSamplesPerPixel(m_samplesPerPixel)) throw std::runtime_error("-spp: " + m_rayTracer->GetLastError());      // -spp N: multi-sample tracing (opt-in)
@@ -210,7 +211,7 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
     return (arg[0] == '-' || arg[0] == '/') && lower(arg + 1) == lower(name);
   };
   // On POSIX an absolute path also starts with '/': such a token is a flag only when it names one.
-  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "sun", "sunreflections", "sunfromenv", "sunangle", "recursion", "spp", "accumulate", "sampleset", "savereference", "reference", "score", "envlayout", "envsize", "envmips", "envprefilter"};
+  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "sun", "sunreflections", "sunfromenv", "sunangle", "light", "spot", "recursion", "spp", "accumulate", "sampleset", "savereference", "reference", "score", "envlayout", "envsize", "envmips", "envprefilter"};
   const auto isFlagName = [&](const char* name) { for (const char* f : kFlags) if (lower(name) == f) return true; return false; };
   const auto hasNextArgValue = [&](int i) {
     if (i + 1 >= argc) return false;
@@ -281,6 +282,36 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
       if (!(angle >= 0.0f && angle <= RTGGX_MAX_SUN_ANGLE_DEGREES)) throw std::runtime_error("-sunangle: the angular radius of the sun's disk in degrees, 0 to 10");
       m_sunAngle = angle; m_hasSunAngle = true;
     }
+    // -light <x> <y> <z> <r> <g> <b> <range> [<radius>] and -spot <x> <y> <z> <r> <g> <b> <range> <radius> <ax> <ay> <az> <outer degrees>
+    // <inner degrees>: a point or a spot light (rtggx_set_lights), repeatable, in the order typed; everything the library would refuse is
+    // refused here, before a device is asked for.  The cosines: cos(degrees pi / 180) in double, rounded once.
+    else if (isArgMatched(i, "light") || isArgMatched(i, "spot")) {
+      const bool spot = isArgMatched(i, "spot");
+      const std::string what = spot ? "-spot" : "-light";
+      const std::string usage = spot ? "-spot: thirteen numbers -- position, intensity, range, radius, axis, outer and inner half-angle in degrees"
+                                     : "-light: seven or eight numbers -- position, intensity, range and, optionally, radius";
+      float v[13] = {};
+      int got = 0;
+      for (; got < (spot ? 13 : 8) && hasNextArgValue(i); ++got) { char* end = nullptr; v[got] = std::strtof(argv[++i], &end); if (end == argv[i] || *end != '\0') throw std::runtime_error(usage); }
+      if (spot ? got != 13 : got < 7) throw std::runtime_error(usage);
+      if (m_lights.size() >= RTGGX_MAX_LIGHTS) throw std::runtime_error(what + ": at most 8 lights (-light and -spot together)");
+      RtggxLight l{};
+      for (int k = 0; k < 3; ++k) { l.position[k] = v[k]; l.intensity[k] = v[3 + k]; }
+      l.range = v[6]; l.radius = v[7]; l.cos_outer = -1.0f; l.cos_inner = 1.0f;
+      for (int k = 0; k < 3; ++k) if (!std::isfinite(l.position[k])) throw std::runtime_error(what + ": a finite position");
+      for (int k = 0; k < 3; ++k) if (!std::isfinite(l.intensity[k]) || l.intensity[k] < 0.0f) throw std::runtime_error(what + ": an intensity that is finite and not negative");
+      if (!std::isfinite(l.range) || !(l.range > 0.0f)) throw std::runtime_error(what + ": a range that is finite and above 0");
+      if (!std::isfinite(l.radius) || l.radius < 0.0f || !(l.radius < l.range)) throw std::runtime_error(what + ": a radius that is finite, not negative and below the range");
+      if (spot) {
+        for (int k = 0; k < 3; ++k) l.axis[k] = v[8 + k];
+        const double len = std::sqrt((double)v[8] * v[8] + (double)v[9] * v[9] + (double)v[10] * v[10]);
+        if (!std::isfinite(len) || !(len > 0.0)) throw std::runtime_error("-spot: an axis of finite, non-zero length");
+        if (!(v[12] > 0.0f && v[12] < v[11] && v[11] < 180.0f)) throw std::runtime_error("-spot: half-angles in degrees with 0 < inner < outer < 180");
+        l.cos_outer = (float)std::cos((double)v[11] * 3.14159265358979323846 / 180.0); l.cos_inner = (float)std::cos((double)v[12] * 3.14159265358979323846 / 180.0);
+        if (!(l.cos_outer > -1.0f && l.cos_outer < l.cos_inner && l.cos_inner <= 1.0f)) throw std::runtime_error("-spot: half-angles in degrees with 0 < inner < outer < 180, apart by more than fp32 tells");
+      }
+      m_lights.push_back(l);
+    }
     else if (isArgMatched(i, "rayrate")) {
       const int rate = hasNextArgValue(i) ? std::atoi(argv[++i]) : 0;
       if (rate != 1 && rate != 4) throw std::runtime_error("-rayrate: 1 or 4 pixels per traced ray");
@@ -342,6 +373,7 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
   // quarter-rate tracing renders whole frames only (rtggx_set_ray_rate): refused here, before anything has touched a GPU
   // one knob asks for fewer rays, the other for more (rtggx_set_samples_per_pixel)
   if (m_rayRate != 1u && m_hasSun) throw std::runtime_error("-sun together with -rayrate 4: refused");
+  if (m_rayRate != 1u && !m_lights.empty()) throw std::runtime_error("-light / -spot together with -rayrate 4: refused");
   if (m_rayRate != 1u && m_samplesPerPixel != 1u) throw std::runtime_error("-spp N > 1 together with -rayrate 4: refused");
   if (m_rayRate != 1u && (m_gpus > 1 || m_strips > 1)) throw std::runtime_error("-rayrate 4: whole frames only, not with -gpus N > 1 or -strips N > 1");
 }

@@ -66,6 +66,9 @@ class RayTracer {
   // The angular radius of the sun's disk in degrees, 0 to RTGGX_MAX_SUN_ANGLE_DEGREES (rtggx_set_sun_angle): shadow rays toward a point of
   // the disk, a penumbra.  0: the directional sun.  It acts only while a sun is set.
   bool SetSunAngle(float degrees);
+  // Point and spot lights inside the scene with ray-traced shadows from the next frame on (rtggx_set_lights): up to RTGGX_MAX_LIGHTS, copied;
+  // (nullptr, 0): off.
+  bool SetLights(const RtggxLight* lights, uint32_t count);
   bool SetSamplesPerPixel(uint32_t samples);   // rtggx_set_samples_per_pixel: 1 (default), 2, 4 or 8 samples per covered pixel (-spp); not together with ray rate 4
   bool SetMaxRecursionDepth(uint32_t depth);   // rtggx_set_max_recursion_depth: 1 (default; RayTracer.cpp:605 SetMaxRecursionDepth(1)) to 4 levels of rays per path (-recursion)   // rtggx_set_ray_rate: 1 (default) or 4 -- one pixel of each 2x2 quad traced per frame, the rest reconstructed (-rayrate)
   // rtggx_set_sample_set: the size of the sample set getSampleParam draws from, 256 (default, the reference's) or a power of two up to
