@@ -725,8 +725,8 @@ int  rtggx_set_sun_angle(rtggx_context* ctx, float degrees);
  * touched; background pixels are untouched.  The order of every sum is the order of the lights; there are no atomics, and the image is a pure
  * function of the inputs.  The pass is independent of recursion depth, sample count, sample map, sample set and sampler; it ends no still-sky
  * run and resets no accumulation; it works on strips, with a deforming mesh, a caller-owned stream and rtggx_set_async_compute(0).
- * Known limit: surfaces seen in reflections get no light term -- a reflection shows the ground without the lamp and without its shadow; the
- * sun's rtggx_set_sun_reflections has no counterpart for the lights yet.
+ * Known limit: surfaces seen in reflections get no light term -- a reflection shows the ground without the lamp and without its shadow.
+ * rtggx_set_light_reflections(ctx, 1) lifts the limit.
  * Per light three kernels (one generating the shadow rays, the any-hit traversal, one adding the unoccluded terms to S), and one more behind
  * the last light.  Memory, from the first frame with lights until rtggx_destroy: ONE queue for all lights with the rays' intervals beside it --
  * 56 + 8 bytes per pixel and 4 per 8x8 block -- and S, 32 bytes per pixel (two images of r, g, b and the number of terms), all zero between
@@ -739,6 +739,50 @@ typedef struct RtggxLight {                 /* 64 bytes */
 } RtggxLight;
 #define RTGGX_MAX_LIGHTS 8u
 int  rtggx_set_lights(rtggx_context* ctx, const RtggxLight* lights, uint32_t count);
+
+/* The lights at the surfaces the paths hit: every surface seen in a reflection (or by a diffuse ray), at every recursion level, gets the
+ * lights' terms and their shadows -- the counterpart of rtggx_set_sun_reflections.  enable: 0 (the default) or 1; anything else is refused and
+ * the setting kept.  The setting is stored whether or not lights are set and acts only in frames that have count > 0 lights (so never at ray
+ * rate 4, which lights exclude); it takes effect with the next rtggx_render_visibility.  Opt-in: a context that never enables it, or has no
+ * lights, allocates and launches exactly what it did.
+ * A level-d ray (o, dir) of a path carries the throughput T_d as in rtggx_set_sun_reflections, and TOUCHES A SURFACE under that function's
+ * definition: it hits, and it is not a reflection-group ray whose preset is <= 0 in every component.  For such a ray the hit is derived exactly
+ * as the hit shading and rtggx_set_sun_reflections derive it -- triangle from the hit id, barycentrics from the repeated watertight test, N,
+ * (r, m) and color of the hit's instance, V = -dir, P = o + t dir per component.  Then per light i = 0 .. count - 1, ascending, whose intensity
+ * I is not 0 in every component, in fp32 without contraction, each operation rounded on its own, with the operator definitions of
+ * rtggx_set_lights:
+ *   1. steps 1-4 of rtggx_set_lights with this P and N: out of range (d2 < 1e-6 or d2 >= R R), facing away (NoL <= 0), outside the cone
+ *      (c <= cos_outer) -- each: no ray, no term --; spot; att = (win spot) / max(d2, m2);
+ *   2. step 5, the target Ds, with h = rng(rng(pixel) + F) and w = rng(h + j 0x9E3779B9).  pixel: the path's pixel as a full-frame index
+ *      y W + x.  F: the frame's FrameIndex at one sample; for sample k of an N-sample frame FrameIndex N + k, the sun hits' rule.
+ *      j = 32 + 16 d + 8 img + i, img the image the path writes (0: RayTracingOut0, 1: RayTracingOut1): the sun's passes use the slots 0 .. 8
+ *      and the primary lights 16 .. 23, so 32 .. 95 collide with neither.  u, s, z, rho', o and Ds_c = D_c + rho o_c as there; ds2 < 1e-6: no
+ *      ray, no term.  With rho = 0 there is no hash, and Ls and L are the same bits;
+ *   3. steps 6-7: dot(N, Ls) <= 0: no ray, no term ("below the horizon"); else a shadow ray from P along Ls over (1e-5, tmax), tmax =
+ *      sqrt(ds2), both bounds exclusive, skipping the hit's (inst, prim), through the any-hit traversal.  rtggx_ray_count / rtggx_ray_total
+ *      count it.  Occluded: no term;
+ *   4. the term of the lobe the path uses at that surface (step 3 of rtggx_set_sun_reflections), at the centre direction L.  m > 0.5:
+ *      r' = max(r, 1/32); H, NoH, VoH, NoV, D, f0, F, vis and k = (D vis) NoL as in step 8 of rtggx_set_lights; term_c = (F_c k) (I_c att).
+ *      Otherwise color' = color (1 - m) for a diffuse-group ray, color for a reflection-group ray; g = (NoL / pi) att; term_c = (color'_c g) I_c
+ *      (no x 0.96: the rule of the hit shading at depth >= 1);
+ *   5. s = T_d term, per component.
+ * The sums.  There is ONE S per (pixel, image); where rtggx_set_sun_reflections is active as well the two features share it.  One sample per
+ * pixel: S = +0; for d ascending first the sun's s_d (where that feature is active and has a term), then the lights' terms for i ascending;
+ * behind the last shading pass word = pack(unpack(word) + S) where at least one term of either feature exists, the word untouched bit for bit
+ * where none does -- one rounding whichever features are on.  N > 1 samples, with or without a sample map: the terms go into the pixel's fp32
+ * sample sums in the same order -- sun, then lights ascending --, at each level in front of the value of a path that ends there; the resolve
+ * and its 1 / c scale are unchanged, and a block that has had its c samples traces no shadow ray.  The primary passes of rtggx_set_sun and
+ * rtggx_set_lights still run afterwards, unchanged, on the packed words.  Background pixels get no term; where the pixel's metallic is >= 1
+ * RayTracingOut1 gets none.  No atomics; the image is a pure function of the inputs, independent of sampler, sample-set size and stream
+ * placement.
+ * Per light with an intensity, level and sample three more kernels in front of the hit shading pass (one generating the shadow rays from the
+ * level's hits, the any-hit traversal in the frame's launch shape, one adding the unoccluded terms), and one more behind the last pass of a
+ * one-sample frame unless the sun's hit pass already runs it: the cost grows with lights x levels x samples and is not shaped by the number
+ * of shadow rays (DESIGN.md section 9 "The lights in reflections" has the measurements).  Memory, from the first frame that has lights and
+ * this on: a queue of the frame's bin size with the rays' intervals beside it -- 56 + 8 + 8 bytes per ray slot -- and 4 bytes per 8x8 block;
+ * a one-sample frame adds S, 32 bytes per pixel, unless rtggx_set_sun_reflections already allocated it.  S is all zero between frames.
+ * tests/light_hit_ref.cpp restates the rule. */
+int  rtggx_set_light_reflections(rtggx_context* ctx, int enable);
 
 /* The sun from the environment: finds the sun in the current cube, measures its direction and irradiance -- what rtggx_set_sun wants -- and,
  * where asked, takes it out of the cube, so that a probe with a sun in it does not light the scene twice (once analytically, with shadows, and

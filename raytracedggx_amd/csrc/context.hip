@@ -506,6 +506,15 @@ int rtggx_set_lights(rtggx_context* c, const RtggxLight* lights, uint32_t count)
   c->lightsRequested = next;
   return 0;
 }
+// The lights at the surfaces the paths hit (include/rtggx.h).  Only the value is kept: it is stored whether or not lights are set, allocates
+// nothing here (the first frame that has both does: raytrace.hip allocSunHits) and takes effect with the next rtggx_render_visibility.  No
+// synchronisation, no end of a still-sky run, no reset of an accumulation, as for the lights themselves.
+int rtggx_set_light_reflections(rtggx_context* c, int enable) {
+  RT_CHECK_CTX(c);
+  if (enable != 0 && enable != 1) { setError("rtggx_set_light_reflections: %d: 0 or 1", enable); return -1; }
+  c->lightReflectionsRequested = enable == 1;
+  return 0;
+}
 // Sums and count back to zero: two clears on the main stream, behind the frames it holds and in front of the next one; nothing waits.
 int rtggx_reset_accumulation(rtggx_context* c) {
   RT_CHECK_CTX(c);

@@ -77,6 +77,7 @@ static int growBins(rtggx_context* c) {
   for (uint32_t i = 0; i < RT_SETS; ++i) { const int r = allocSet(c, i); if (r) return r; }      // (the bins, at the new size)
   c->testRayRange.reset();
   c->sunHitRays.reset(); c->sunHitHits.reset(); c->sunHitSlots = 0u;      // (rtggx_set_sun_reflections: its bins follow the frame's, at the next lit frame)
+  c->lightHitRays.reset(); c->lightHitHits.reset(); c->lightHitRange.reset(); c->lightHitSlots = 0u;      // (rtggx_set_light_reflections: likewise)
   return 0;
 }
 int rtggx_update_frame(rtggx_context* c, const RtggxFrameConstants* k) {
@@ -195,7 +196,7 @@ int rtggx_render_visibility(rtggx_context* c) {
   if (!c->shDone && c->env.texels) { const int r = projectSH(c, c->streamAS); if (r) return r; }   // first frame only, RayTracer.cpp:345-350
   settleSetRead(c);      // (the previous frame ended without the kernel that would have carried its set's event)
   ++c->frameCounter;
-  c->maxDepth = c->depthRequested; c->samples = c->samplesRequested; c->accumulate = c->accumulateRequested; c->sun = c->sunRequested; c->sunAngle = c->sunAngleRequested; c->sunReflections = c->sunReflectionsRequested; c->lights = c->lightsRequested;
+  c->maxDepth = c->depthRequested; c->samples = c->samplesRequested; c->accumulate = c->accumulateRequested; c->sun = c->sunRequested; c->sunAngle = c->sunAngleRequested; c->sunReflections = c->sunReflectionsRequested; c->lights = c->lightsRequested; c->lightReflections = c->lightReflectionsRequested;
   c->scoring = c->scoringRequested && c->reference != nullptr;
   c->sampleMap = c->sampleMapRequested;      // rtggx_set_sample_map: the setter has waited for every stream and written the copy no frame reads
   bool resendConstants = false;

@@ -1237,27 +1237,37 @@ __global__ void __launch_bounds__(256) sunHitResolveKernel(const FrameParams* __
   if (r.w != 0.0f) { A.reflOut[pix] = packR11G11B10F(unpackR11G11B10F(A.reflOut[pix]) + mk3(r.x, r.y, r.z)); A.sumRefl[pix] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
   if (d.w != 0.0f) { A.diffOut[pix] = packR11G11B10F(unpackR11G11B10F(A.diffOut[pix]) + mk3(d.x, d.y, d.z)); A.sumDiff[pix] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
 }
-// What the feature needs, from the first frame that has the sun and the toggle on: the queue at the frame's slots per bin (the bins' growth
-// releases it: frame.hip growBins, behind a wait for every stream), its counts, and S for one-sample frames.
-static int allocSunHits(rtggx_context* c, bool wantSums) {
+// What the two hit passes need (rtggx_set_sun_reflections, rtggx_set_light_reflections), from the first frame that has the sun or lights and
+// the respective toggle on: per feature its queue at the frame's slots per bin (the bins' growth releases it: frame.hip growBins, behind a
+// wait for every stream) and its counts -- the lights' also the rays' intervals --, and for one-sample frames S, which the two share.
+static int allocSunHits(rtggx_context* c, bool wantSums, bool sunQueue, bool lightQueue) {
   bool cleared = false;
   if (!c->evSunHit) RT_HIP(create(c->evSunHit, hipEventDisableTiming));
-  if (!c->sunHitRays || !c->sunHitHits || c->sunHitSlots != c->binSlots) {
+  if (sunQueue && (!c->sunHitRays || !c->sunHitHits || c->sunHitSlots != c->binSlots)) {
     c->sunHitRays.reset(); c->sunHitHits.reset();
     const size_t slots = (size_t)c->numBinsMax * c->binSlots;
     RT_HIP(alloc(c->sunHitRays, slots * sizeof(RayRec)));
     RT_HIP(alloc(c->sunHitHits, slots * sizeof(HitKey)));
     c->sunHitSlots = c->binSlots;
   }
-  if (!c->sunHitCount) { RT_HIP(allocFilled(c->sunHitCount, (size_t)c->numBinsMax)); cleared = true; }
+  if (sunQueue && !c->sunHitCount) { RT_HIP(allocFilled(c->sunHitCount, (size_t)c->numBinsMax)); cleared = true; }
+  if (lightQueue && (!c->lightHitRays || !c->lightHitHits || !c->lightHitRange || c->lightHitSlots != c->binSlots)) {
+    c->lightHitRays.reset(); c->lightHitHits.reset(); c->lightHitRange.reset();
+    const size_t slots = (size_t)c->numBinsMax * c->binSlots;
+    RT_HIP(alloc(c->lightHitRays, slots * sizeof(RayRec)));
+    RT_HIP(alloc(c->lightHitHits, slots * sizeof(HitKey)));
+    RT_HIP(alloc(c->lightHitRange, slots * sizeof(float2)));
+    c->lightHitSlots = c->binSlots;
+  }
+  if (lightQueue && !c->lightHitCount) { RT_HIP(allocFilled(c->lightHitCount, (size_t)c->numBinsMax)); cleared = true; }
   if (wantSums && !c->sunHitSums) { RT_HIP(allocFilled(c->sunHitSums, (size_t)c->W * c->H * 8u)); cleared = true; }
   if (cleared) RT_HIP(hipStreamSynchronize(nullptr));      // (the clears run on the null stream, which this context's streams are not ordered against)
   return 0;
 }
-// The frame's first use of the shared queue and sums on stream s: behind the previous frame's, which may have run on another stream (small
+// The frame's first use of the queues and sums on stream s: behind the previous frame's, which may have run on another stream (small
 // launches alternate two), as launchShadeSamples orders sppAcc
-static int beginSunHits(rtggx_context* c, hipStream_t s, bool wantSums) {
-  { const int r = allocSunHits(c, wantSums); if (r) return r; }
+static int beginSunHits(rtggx_context* c, hipStream_t s, bool wantSums, bool sunQueue, bool lightQueue) {
+  { const int r = allocSunHits(c, wantSums, sunQueue, lightQueue); if (r) return r; }
   if (c->sunHitStream && c->sunHitStream != s) { RT_HIP(hipEventRecord(c->evSunHit, c->sunHitStream)); RT_HIP(hipStreamWaitEvent(s, c->evSunHit, 0)); }
   c->sunHitStream = s;
   return 0;
@@ -1286,6 +1296,166 @@ static int launchSunHits(rtggx_context* c, const FrameParams& fp, hipStream_t s,
   D.rays = q.rays; D.hits = q.hits; D.binCount = q.binCount; D.binSlots = c->binSlots; D.tileWords = tileWords; D.sumRefl = sumRefl; D.sumDiff = sumDiff;
   launch(samples ? sunHitAddKernel<true> : sunHitAddKernel<false>, dim3(numTiles), dim3(256), s, nullptr, nullptr, D);
   RT_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---- the local lights at the surfaces the paths hit (rtggx_set_light_reflections; include/rtggx.h has the rule) ------------
+// The sun's hit pass with a light inside the scene: per light, in index order, directly behind the sun's hit pass of the level and in front of
+// the level's shading pass.  lightHitGenKernel is sunHitGenKernel's walk over the wave's bin and its derivation of the touched hit, then
+// lightGenKernel's steps 1-6 with the hit's P, N and V and the lobe the path uses there; it compacts one shadow ray into the same bin of a
+// queue of the feature's own, the finished s = T_d * term in the record's weight, the image bit in its flags, the ray's interval (1e-5, tmax)
+// in a float2 array beside the queue.  The any-hit traversal is the frame's launch shape reading that interval; the add is sunHitAddKernel
+// (a record carries all it reads) into the sums the sun's hit pass uses -- S or the sample sums --, so the order of a sum is sun, then the
+// lights ascending, and a one-sample frame has one resolve.  CONE and SOFT change the instruction stream as in lightGenKernel.
+struct LightHitGenArgs {
+  const RayRec* rays; const HitKey* hits; const uint32_t* binCount; uint32_t binSlots;      // the frame's bins, this level's rays and their hits
+  const float4* fat0; const float4* fat1;
+  RayRec* outRays; HitKey* outHits; uint32_t* outCount; float2* outRange;                   // the feature's queue: the same bins, binSlots slots each
+  const uint32_t* tileWords;
+  float Px, Py, Pz, range, Ix, Iy, Iz, radius, Ax, Ay, Az, cosOuter, cosInner;
+  const float* cosSin; uint32_t frameIndex, slotBase;      // SOFT: the 256-entry table, the frame index of the sample the pass belongs to, 32 + 16 d + i
+};
+template <bool CONE, bool SOFT>
+__global__ void __launch_bounds__(256) lightHitGenKernel(const FrameParams* __restrict__ fpp, LightHitGenArgs A) {
+  const FrameParams& fp = *fpp;
+  const uint32_t tile = blockIdx.x;
+  { uint32_t word;
+    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(word) : "s"(A.tileWords), "s"(tile * 4u) : "memory");
+    if (word == 0u) return; }
+  const uint32_t bin = tile * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  const uint32_t count = RT_SGPR(min(A.binCount[bin] & 0xFFu, A.binSlots));
+  uint32_t written = 0u;      // shadow rays in the front of the bin so far: never more than the records read (a bin of 128 takes two rounds)
+  for (uint32_t base = 0u; base < count; base += 64u) {
+    const uint32_t i = base + lane;
+    bool want = false;
+    RayRec sr;
+    float tmax = 0.0f;
+    if (i < count) {
+      const size_t slot = (size_t)bin * A.binSlots + i;
+      const float4* rp = reinterpret_cast<const float4*>(A.rays + slot);
+      const float4 q0 = rp[0], q1 = rp[1], q2 = rp[2];
+      const uint32_t pixel = __float_as_uint(q1.z), skip = __float_as_uint(q1.w), flags = __float_as_uint(q2.w);
+      const uint32_t hitId = hitKeyId(A.hits[slot]);
+      const bool diffuseGroup = (flags & 1u) != 0u;
+      const uint32_t image = (flags ^ (flags >> 1)) & 1u;      // the image the path writes (1: RayTracingOut1)
+      const uint32_t srcInst = skip >> 24;
+      // the ray touches a surface: sunHitGenKernel's test
+      const float m = fp.mat.RoughMetals[srcInst][1];
+      const bool presetReturn = !diffuseGroup && fp.mat.BaseColors[srcInst][0] * m <= 0.0f && fp.mat.BaseColors[srcInst][1] * m <= 0.0f && fp.mat.BaseColors[srcInst][2] * m <= 0.0f;
+      if (hitId != 0xFFFFFFFFu && !presetReturn) {
+        const uint32_t hInst = hitId >> 24;
+        uint32_t hPrim = hitId & 0xFFFFFFu;
+        asm volatile("" : "+v"(hPrim));      // see shadeKernel
+        const Tri3 v = getVertices(hInst ? A.fat1 : A.fat0, hPrim);
+        float ht, hb1 = 0.0f, hb2 = 0.0f;
+        woopTestVerts(toObject(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, hInst ? fp.invWorld[1] : fp.invWorld[0]), v.pos[0], v.pos[1], v.pos[2], ht, hb1, hb2);
+        const Attrib a = interpAttrib(v, hb1, hb2);
+        const f3 N = normalize3(mulDir(a.Nrm, cbLoad3x3(hInst ? fp.g.WorldIT1 : fp.g.WorldITs0)));
+        const f3 P = mk3(q0.x + ht * q0.w, q0.y + ht * q1.x, q0.z + ht * q1.y);      // hitWorldPosition :338-341
+        // steps 1 and 2 of rtggx_set_lights: in range, facing
+        const f3 D = mk3(A.Px - P.x, A.Py - P.y, A.Pz - P.z);
+        const float d2 = dot3(D, D), RR = A.range * A.range;
+        const f3 L = normalize3(D);
+        const float NoL = dot3(N, L);
+        bool lit = d2 >= 1e-6f && d2 < RR && NoL > 0.0f;
+        float spot = 1.0f;
+        if constexpr (CONE) {      // step 3
+          const float c = -dot3(L, mk3(A.Ax, A.Ay, A.Az));
+          const float t = saturatef((c - A.cosOuter) / (A.cosInner - A.cosOuter));
+          spot = t * t;
+          lit = lit && c > A.cosOuter;
+        }
+        f3 Ds = D;
+        if constexpr (SOFT) {      // step 5: a point of the emitting sphere, the slot of this level, image and light
+          if (lit) {
+            uint32_t h = rng(pixel); h += A.frameIndex; h = rng(h);
+            const uint32_t w = rng(h + (A.slotBase + 8u * image) * 0x9E3779B9u);
+            const float u = (float)(w & 0xffffu) / 65536.0f;
+            const uint32_t s = w >> 24;
+            const float z = 1.0f - 2.0f * u, rho = sqrtf(1.0f - z * z);
+            Ds = mk3(D.x + A.radius * (rho * A.cosSin[s]), D.y + A.radius * (rho * A.cosSin[256u + s]), D.z + A.radius * z);
+          }
+        }
+        const float ds2 = dot3(Ds, Ds);
+        const f3 Ls = normalize3(Ds);
+        lit = lit && ds2 >= 1e-6f && dot3(N, Ls) > 0.0f;      // step 6
+        if (lit) {
+          // step 4: the window, the floor
+          const float q = d2 / RR;
+          float win = saturatef(1.0f - q * q); win = win * win;
+          const float m2 = fmaxf(A.radius * A.radius, 1e-4f);
+          const float att = (win * spot) / fmaxf(d2, m2);
+          const f2 rm = getRoughMetal(fp.mat, hInst, a.UV);
+          f3 color = mk3(fp.mat.BaseColors[hInst][0], fp.mat.BaseColors[hInst][1], fp.mat.BaseColors[hInst][2]);
+          f3 term;
+          if (rm.y > 0.5f) {      // the lobe the path uses at this surface: the specular term of the primary lights' pass (lightGenKernel) at the centre direction L
+            const f3 V = mk3(-q0.w, -q1.x, -q1.y);
+            const float r = fmaxf(rm.x, 1.0f / 32.0f);
+            const f3 Hh = normalize3(V + L);
+            const float NoH = saturatef(dot3(N, Hh)), VoH = saturatef(dot3(V, Hh)), NoV = saturatef(dot3(N, V));
+            const float al = r * r, a2 = al * al;
+            const float d = (NoH * a2 - NoH) * NoH + 1.0f;
+            const float Dg = a2 / ((RT_PI * d) * d);
+            const f3 f0 = mk3(lerpf(0.04f, color.x, rm.y), lerpf(0.04f, color.y, rm.y), lerpf(0.04f, color.z, rm.y));
+            const f3 F = fSchlick(f0, VoH);
+            const float vis = visSmith(r, NoV, NoL);
+            const float k = (Dg * vis) * NoL;
+            term = mk3((F.x * k) * (A.Ix * att), (F.y * k) * (A.Iy * att), (F.z * k) * (A.Iz * att));
+          } else {
+            if (diffuseGroup) color = color * (1.0f - rm.y);                 // :607
+            const float g = (NoL / RT_PI) * att;
+            term = mk3((color.x * g) * A.Ix, (color.y * g) * A.Iy, (color.z * g) * A.Iz);      // no x (1 - 0.04) at depth >= 1 (:532)
+          }
+          want = true;
+          tmax = sqrtf(ds2);
+          sr.ox = P.x; sr.oy = P.y; sr.oz = P.z;
+          sr.dx = Ls.x; sr.dy = Ls.y; sr.dz = Ls.z;
+          sr.pixel = pixel; sr.skip = hitId;
+          sr.wx = q2.x * term.x; sr.wy = q2.y * term.y; sr.wz = q2.z * term.z;             // s = T_d * term
+          sr.flags = image;
+        }
+      }
+    }
+    const unsigned long long mask = __ballot(want);
+    if (want) {
+      const size_t k = (size_t)bin * A.binSlots + written + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+      A.outRays[k] = sr; A.outHits[k] = hitKey(tmax, 0xFFFFFFFFu); A.outRange[k] = make_float2(RT_RAY_TMIN, tmax);
+    }
+    written += (uint32_t)__popcll(mask);
+  }
+  if (lane == 0u) A.outCount[bin] = written;
+}
+// One level's hits under the lights: per light with an intensity the generation from the bins q (their rays traced, not yet shaded), the
+// any-hit traversal on the frame's trace grid with this stream's spill part and the rays' own intervals, sunHitAddKernel into sumRefl / sumDiff
+static int launchLightHits(rtggx_context* c, const FrameParams& fp, hipStream_t s, const TraceQueue& bins, const float4* fat0, const float4* fat1, const uint32_t* tileWords,
+                           uint32_t numTiles, int spillPart, bool samples, float* sumRefl, float* sumDiff, uint32_t frameIndex, uint32_t level) {
+  if (numTiles * 4u > c->numBinsMax || c->lightHitSlots != c->binSlots) { setError("rtggx_ray_trace: the queue of rtggx_set_light_reflections does not hold %u bins of %u slots", numTiles * 4u, c->binSlots); return -1; }
+  LightHitGenArgs G;
+  G.rays = bins.rays; G.hits = bins.hits; G.binCount = bins.binCount; G.binSlots = c->binSlots;
+  G.fat0 = fat0; G.fat1 = fat1;
+  G.outRays = (RayRec*)c->lightHitRays.get(); G.outHits = (HitKey*)c->lightHitHits.get(); G.outCount = c->lightHitCount; G.outRange = (float2*)c->lightHitRange.get();
+  G.tileWords = tileWords;
+  G.cosSin = c->cosSinTab; G.frameIndex = frameIndex;
+  const TraceQueue q{G.outRays, G.outHits, G.outCount};
+  SunHitAddArgs D;
+  D.rays = q.rays; D.hits = q.hits; D.binCount = q.binCount; D.binSlots = c->binSlots; D.tileWords = tileWords; D.sumRefl = sumRefl; D.sumDiff = sumDiff;
+  for (uint32_t i = 0; i < c->lights.count; ++i) {
+    const RtggxLight& l = c->lights.l[i];
+    if (!(l.intensity[0] > 0.0f || l.intensity[1] > 0.0f || l.intensity[2] > 0.0f)) continue;      // keeps its index, casts no ray
+    G.Px = l.position[0]; G.Py = l.position[1]; G.Pz = l.position[2]; G.range = l.range;
+    G.Ix = l.intensity[0]; G.Iy = l.intensity[1]; G.Iz = l.intensity[2]; G.radius = l.radius;
+    G.Ax = l.axis[0]; G.Ay = l.axis[1]; G.Az = l.axis[2]; G.cosOuter = l.cos_outer; G.cosInner = l.cos_inner;
+    G.slotBase = 32u + 16u * level + i;
+    const bool cone = l.cos_outer > -1.0f, soft = l.radius > 0.0f;
+    launch(cone ? (soft ? lightHitGenKernel<true, true> : lightHitGenKernel<true, false>) : (soft ? lightHitGenKernel<false, true> : lightHitGenKernel<false, false>),
+           dim3(numTiles), dim3(256), s, nullptr, nullptr, c->dParams + c->slot, G);
+    c->traceRayRange = c->lightHitRange.get();      // (the rays' own intervals, for the launch's duration: launchLights)
+    const int r = launchTrace(c, fp, s, q, c->traceGrid[0], true, c->traceGrid[1], c->traceGrid[2], c->traceGrid[3], -1, nullptr, nullptr, spillPart, true);
+    c->traceRayRange = nullptr;
+    if (r) return r;
+    launch(samples ? sunHitAddKernel<true> : sunHitAddKernel<false>, dim3(numTiles), dim3(256), s, nullptr, nullptr, D);
+    RT_HIP(hipGetLastError());
+  }
   return 0;
 }
 
@@ -1322,8 +1492,9 @@ static int launchShadeSamples(rtggx_context* c, const FrameParams& fp, hipStream
   static_cast<SampleGenArgs&>(GM) = G; GM.sampleMap = map; GM.sample = 0u;
   const TraceQueue q{S.rays, S.spawnHits, S.binCount};
   // rtggx_set_sun_reflections: at every level acc = acc + s_d comes first, then the pass's own add of the paths that end there
-  const bool sunHits = c->sun.on && c->sunReflections;
-  if (sunHits) { const int r = beginSunHits(c, s, false); if (r) return r; }
+  // rtggx_set_light_reflections: then the lights' terms, i ascending, still in front of the pass's own add
+  const bool sunHits = c->sun.on && c->sunReflections, lightHits = c->lights.count > 0u && c->lightReflections;
+  if (sunHits || lightHits) { const int r = beginSunHits(c, s, false, sunHits, lightHits); if (r) return r; }
   for (uint32_t k = 0; k < N; ++k) {
     for (uint32_t level = 0; level < depth; ++level) {
       if (k > 0 && level == 0) {
@@ -1335,6 +1506,7 @@ static int launchShadeSamples(rtggx_context* c, const FrameParams& fp, hipStream
         if (r) return r;
       }
       if (sunHits) { const int r = launchSunHits(c, fp, s, q, S.fat0, S.fat1, S.tileWords, numTiles, spillPart, true, S.accRefl, S.accDiff, fp.g.FrameIndex * N + k, level); if (r) return r; }
+      if (lightHits) { const int r = launchLightHits(c, fp, s, q, S.fat0, S.fat1, S.tileWords, numTiles, spillPart, true, S.accRefl, S.accDiff, fp.g.FrameIndex * N + k, level); if (r) return r; }
       launch(level + 1u < depth ? (wide ? shadeKernel<1, SHADE_SPAWN_ACCUM, true> : shadeKernel<1, SHADE_SPAWN_ACCUM>) : shadeKernel<1, SHADE_ACCUM>, dim3(numTiles), dim3(256), s, nullptr, nullptr, sp + k, S);
       S.carryMask = 0u;      // (carried over once, by the first pass)
       RT_HIP(hipGetLastError());
@@ -1385,10 +1557,12 @@ int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent
   if (c->samples > 1u && !quad) return launchShadeSamples(c, fp, s, done, S, numTiles, spillPart);
   // rtggx_set_sun_reflections (the sun excludes rate 4): every level's hits add their terms to S in front of the level's shading pass, and
   // behind the last pass -- which then no longer carries `done` -- sunHitResolveKernel adds S to the packed words
-  const bool sunHits = c->sun.on && c->sunReflections && !quad;
+  // rtggx_set_light_reflections (the lights exclude rate 4 as well): the lights' terms follow the sun's into the same S, i ascending, and
+  // the one resolve packs what either feature left there
+  const bool sunHits = c->sun.on && c->sunReflections && !quad, lightHits = c->lights.count > 0u && c->lightReflections && !quad, anyHits = sunHits || lightHits;
   float* sums[2] = {nullptr, nullptr};
-  if (sunHits) {
-    const int r = beginSunHits(c, s, true); if (r) return r;
+  if (anyHits) {
+    const int r = beginSunHits(c, s, true, sunHits, lightHits); if (r) return r;
     sums[0] = c->sunHitSums; sums[1] = c->sunHitSums + 4u * (size_t)c->W * c->H;
   }
   for (uint32_t level = 0; level < depth; ++level) {
@@ -1399,11 +1573,12 @@ int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent
       S.carryMask = 0u;      // (carried over once, by the first pass)
     }
     if (sunHits) { const int r = launchSunHits(c, fp, s, q, S.fat0, S.fat1, S.tileWords, numTiles, spillPart, false, sums[0], sums[1], fp.g.FrameIndex, level); if (r) return r; }
+    if (lightHits) { const int r = launchLightHits(c, fp, s, q, S.fat0, S.fat1, S.tileWords, numTiles, spillPart, false, sums[0], sums[1], fp.g.FrameIndex, level); if (r) return r; }
     const int pass = level + 1u < depth ? SHADE_SPAWN : level == 0 ? SHADE_FINAL : SHADE_FINAL_DEEP;
-    launch(pass == SHADE_SPAWN && c->sampleSet > RTGGX_MIN_SAMPLE_SET ? kShadeSpawnWide[quad] : kShade[pass][quad], dim3(grid), dim3(256), s, nullptr, pass == SHADE_SPAWN || sunHits ? nullptr : done, dfp, S);
+    launch(pass == SHADE_SPAWN && c->sampleSet > RTGGX_MIN_SAMPLE_SET ? kShadeSpawnWide[quad] : kShade[pass][quad], dim3(grid), dim3(256), s, nullptr, pass == SHADE_SPAWN || anyHits ? nullptr : done, dfp, S);
     RT_HIP(hipGetLastError());
   }
-  if (sunHits) {
+  if (anyHits) {
     SunHitResolveArgs R;
     R.sumRefl = (float4*)sums[0]; R.sumDiff = (float4*)sums[1]; R.reflOut = set.rtRefl; R.diffOut = set.rtDiff;
     R.tileWords = S.tileWords; R.tilesX = tilesX; R.rowBegin = rb; R.rowEnd = re;

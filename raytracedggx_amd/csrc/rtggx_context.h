@@ -305,6 +305,15 @@ struct rtggx_context {
   // The pass runs on the main stream only: consecutive frames' kernels follow each other there.
   struct Lights { uint32_t count = 0; RtggxLight l[RTGGX_MAX_LIGHTS] = {}; } lights, lightsRequested;
   rt::DevBuf<void> lightRays, lightHits, lightRange; rt::DevBuf<uint32_t> lightCount; rt::DevBuf<float> lightSums;
+  // rtggx_set_light_reflections: the lights' terms and shadows at the surfaces the paths hit (raytrace.hip launchLightHits).  Stored whether or
+  // not lights are set; the frame's, the next frame's.  From the first frame that has lights and the toggle on (raytrace.hip allocSunHits):
+  //   lightHitRays / lightHitHits / lightHitRange / lightHitCount   a queue of the feature's own with the rays' intervals beside it, bins of
+  //                lightHitSlots = binSlots slots (released when the bins grow), refilled light by light and level by level
+  // S of the one-sample frame, the event and the stream view are the sun's hit pass's (sunHitSums, evSunHit, sunHitStream): the two features
+  // add into one sum per (pixel, image) and one resolve packs it.
+  bool lightReflections = false, lightReflectionsRequested = false;
+  rt::DevBuf<void> lightHitRays, lightHitHits, lightHitRange; rt::DevBuf<uint32_t> lightHitCount;
+  uint32_t lightHitSlots = 0;
   uint32_t rayRate = 1;          // rtggx_set_ray_rate: pixels per traced ray, 1 or 4 (raytrace.hip rayGenKernel, reconstructKernel)
   uint32_t maxDepth = 1, depthRequested = 1;      // rtggx_set_max_recursion_depth: 1..4 levels of rays per path (raytrace.hip launchShade); the frame's, the next frame's
   // rtggx_set_samples_per_pixel: 1, 2, 4 or 8 samples per covered pixel (raytrace.hip launchShade; DESIGN.md "Samples per pixel"); the
