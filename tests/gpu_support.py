@@ -334,15 +334,17 @@ BVH_SETS = ((("BUF_BVH_NODES0", "BUF_BVH_TRIS0", "BUF_BVH4_NODES0", "BUF_BVH4_TO
 class Scene:
     """A capi.Context and an oracle holding the same two meshes and instance transforms.  camera: the frame constants are an ordinary
     camera's (the oracle's default one) with the scene's Worlds, for the tests that run frames (frame): the visibility pass then sees
-    ordinary input.  built_shape: see check_trees, for the check of the build."""
+    ordinary input.  built_shape: see check_trees, for the check of the build.  size: (W, H) of both (default: the BVH tests' 64 x 64);
+    oracle: a callable (W, H) -> Oracle in place of O.Oracle."""
 
-    def __init__(self, mesh0, mesh1, world0=None, world1=None, camera=False, built_shape=True):
+    def __init__(self, mesh0, mesh1, world0=None, world1=None, camera=False, built_shape=True, size=None, oracle=None):
         from raytracedggx_amd import capi
         self.capi = capi
         self.meshes = [mesh0, mesh1]
         self.worlds = [bvh_cases.world(4.0, (0.0, -6.0, 0.0)) if world0 is None else world0, bvh_cases.world() if world1 is None else world1]
-        self.ctx = capi.Context(bvh_cases.W, bvh_cases.H)
-        self.o = O.Oracle(bvh_cases.W, bvh_cases.H)
+        self.W, self.H = size or (bvh_cases.W, bvh_cases.H)
+        self.ctx = capi.Context(self.W, self.H)
+        self.o = (oracle or O.Oracle)(self.W, self.H)
         try:
             for slot, (v, i) in enumerate(self.meshes):
                 self.ctx.set_mesh(slot, v, i)
@@ -350,7 +352,7 @@ class Scene:
             self.ctx.build_as()
             base = None
             if camera:
-                self.o.update_frame((10, 10, -24), O.camera_view_proj(bvh_cases.W, bvh_cases.H), 0.0)
+                self.o.update_frame((10, 10, -24), O.camera_view_proj(self.W, self.H), 0.0)
                 base = self.o.get_frame_constants()
             self.fc = bvh_cases.frame_constants(*self.worlds, base=base)
             self.ctx.update_frame(self.fc); self.ctx.update_as()
@@ -392,6 +394,35 @@ class Scene:
             self.ctx.refit_as(slot, v)
             self.set_shape(slot, v)
         self.ctx.update_frame(self.fc); self.ctx.update_as(); self.ctx.render_visibility(); self.ctx.sync()
+
+    def set_cube(self, cube, vndf=False):
+        """The same environment (an env_cases.Cube) and sampler on both sides.  The nine SH coefficients are projected on each side by its own
+        code (tests/test_gpu_env.py holds the device's to the float64 projection); the oracle then takes the device's, so that a frame's words
+        compare bit for bit whatever the last bit of a coefficient."""
+        self.ctx.set_env(self.capi.FORMAT_RGBA16F, cube.size, cube.mips, cube.dds_order())
+        self.o.set_env_rgba16f(cube.size, cube.mips, cube.mip_major())
+        np.testing.assert_array_equal(self.ctx.readback(self.capi.BUF_ENV), cube.mip_major())
+        self.ctx.transform_sh(); self.o.transform_sh()
+        dev, own = self.ctx.readback(self.capi.BUF_SH_COEFFS).reshape(9, 3), self.o.buffer(O.BUF_SH_COEFFS)
+        np.testing.assert_allclose(dev, own, rtol=1e-5, atol=1e-6)      # (gross errors only, the frames' own tolerance in tests/test_gpu_parity.py; the bound that
+        # holds the projection is tests/test_gpu_env.py's: 2^-23 of each coefficient's magnitude against the float64 sum)
+        self.o.set_sh(dev)
+        self.ctx.set_sampler(bool(vndf)); self.o.set_sampler(bool(vndf))
+
+    def shaded_frame(self, constants, materials, strip=None):
+        """One frame up to the traced images on both sides: materials ((colour, roughness, metallic) per instance), the 768 bytes, the
+        instance transforms, visibility, ray generation and tracing.  strip: (first row, end row) of the device's frame.
+        -> (the device's words by the names of gbuffer() and RAW, its ray count, the oracle's ray count)."""
+        for slot, (colour, rough, metal) in enumerate(materials):
+            self.ctx.set_material(slot, colour, rough, metal)
+        if strip:
+            self.ctx.set_strip(*strip)
+        self.fc = bytes(constants)
+        self.ctx.update_frame(self.fc); self.ctx.update_as(); self.ctx.render_visibility(); self.ctx.ray_trace(); self.ctx.sync()
+        self.o.set_frame_constants(self.fc); self.o.update_as(); self.o.render_visibility()
+        rays = self.o.ray_trace()
+        words = {n: self.ctx.readback(getattr(self.capi, _IMAGE_IDS[n])) for n in GBUFFER + RAW}
+        return words, self.ctx.ray_count(), rays
 
     def set_shape(self, slot, v):
         """The oracle's (and the checks') copy of a slot's vertices."""

@@ -52,6 +52,7 @@ def lib():
                 ("orc_ray_trace_depth", C.c_uint64, [C.c_void_p, u32]),
                 ("orc_ray_trace_spp", C.c_uint64, [C.c_void_p, u32, u32]),
                 ("orc_ray_trace_spp_f32", C.c_uint64, [C.c_void_p, u32, u32, C.c_void_p, C.c_void_p]),
+                ("orc_ray_trace_spp_primary_f32", C.c_uint64, [C.c_void_p, u32, u32, C.c_void_p, C.c_void_p, C.c_void_p]),
                 ("orc_ray_trace_sampleset", C.c_uint64, [C.c_void_p, u32, u32, u32]),
                 ("orc_sample_param_m", None, [u32, u32, u32, u32, u32, C.POINTER(u32), C.c_void_p]),
                 ("orc_sample_table_m", None, [u32, C.c_void_p]),
@@ -122,6 +123,16 @@ class Oracle(O.Oracle):
         diff = np.full((self.H, self.W, 3), np.nan, np.float32)
         rays = int(self.L.orc_ray_trace_spp_f32(self.h, C.c_uint32(self.depth), C.c_uint32(n), refl.ctypes.data_as(C.c_void_p), diff.ctypes.data_as(C.c_void_p)))
         return rays, refl, diff
+
+    def ray_trace_primary_f32(self):
+        """ray_trace_f32 at the setting, and the primary surface in front of the G-buffer's packs: fp32 [H, W, 6] of N * 0.5 + 0.5, the velocity
+        and the roughness."""
+        refl = np.full((self.H, self.W, 3), np.nan, np.float32)
+        diff = np.full((self.H, self.W, 3), np.nan, np.float32)
+        primary = np.zeros((self.H, self.W, 6), np.float32)
+        rays = int(self.L.orc_ray_trace_spp_primary_f32(self.h, C.c_uint32(self.depth), C.c_uint32(self.samples), refl.ctypes.data_as(C.c_void_p),
+                                                        diff.ctypes.data_as(C.c_void_p), primary.ctypes.data_as(C.c_void_p)))
+        return rays, refl, diff, primary
 
     def ray_trace_depth_restatement(self):
         """tests/recursion_ref.cpp's orc_ray_trace_depth, for comparison with the spp entry at one sample."""

@@ -1,0 +1,377 @@
+"""Synthetic scenes for the per-pixel tests of the shading path (tests/shading_ref.py the model, tests/test_shading_ref_host.py on the CPU,
+tests/test_gpu_shading_synthetic.py on the device).  Pure numpy: two small meshes, two World matrices, a camera, materials, a cube from
+tests/env_cases.py.  Each case builds its own 768-byte frame constants by the layout of include/rtggx.h -- every matrix computed in float64
+and rounded once -- and the model reads World, the view-projection and the materials from those bytes: the kernel's inputs are the
+model's inputs.
+
+Frames are at most 96 x 64 and ragged (75 x 53), meshes stay below 512 triangles, cubes have sides 5, 12 and 16.  Every case runs the
+frame indices FRAMES; its camera (and, where said, its second instance) moves from frame to frame, so the velocity word is nowhere a
+rounding residue around zero, where binary16's denormals are finer than fp32's error of a difference of two numbers near 1.
+
+Families (the smallest set that reaches each branch):
+  transforms   non-uniform scale x rotation about a skew axis x translation on both instances (the inverse transpose matters), the same
+               mirrored (negative determinant) with a ProjBias, a moving instance, previous positions off screen
+  normals      vertex normals that sweep |n.y| through 0.999 on both sides of it and on both signs, exactly +-y, shading normals at
+               grazing angles to the eye and turned away from it
+  materials    a closed room (instance 0: the checkerboard under all three dominant axes) around a ball: 13 roughness codes from 0 to 1,
+               metallic 0, 0.25, 0.75 and 1 on both instances in the four combinations of "hit side above or below 0.5", colours with a
+               zero channel, a zero green, all zero and above 1, cubes of 1, 3 and 5 mips
+  hits         open sky; a cone whose apex lies on a pixel centre (a ray leaves a vertex shared by 16 triangles); two coincident sheets
+  vndf         normals and materials once more under rtggx_set_sampler
+  sun, lights  a slab under an occluder, lit by rtggx_set_sun (angle 0) and by rtggx_set_lights (radius 0); see all_cases"""
+import functools
+
+import numpy as np
+
+import bvh_cases
+import env_cases
+import env_ref
+
+FRAMES = (0, 1, 255)
+
+
+# ---- cubes ---------------------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def smooth_cube(size=16, mips=5):
+    """A low-order polynomial radiance of the direction, every level sampled at its own texel centres: slopes of a few percent per texel,
+    so the rounding of a direction is not what the measured floor shows."""
+    codes = []
+    for m in range(mips):
+        s = env_cases.side(size, m)
+        d, _, _, _ = env_ref.texel_centre_dirs(s)
+        d = d / np.sqrt((d * d).sum(axis=1))[:, None]
+        x, y, z = d[:, 0], d[:, 1], d[:, 2]
+        rgb = np.stack([2.0 + 0.75 * y + 0.5 * x * z, 1.5 + 0.5 * x - 0.25 * y * y, 1.0 + 0.5 * z + 0.25 * x * y], axis=1)
+        t = np.ones((6 * s * s, 4), np.float16)
+        t[:, :3] = rgb.astype(np.float16)
+        codes.append(t.reshape(6, s, s, 4).view(np.uint16).copy())
+    return env_cases.Cube(size, mips, codes, "smooth_%d_%dmips" % (size, mips))
+
+
+@functools.lru_cache(maxsize=None)
+def signed_cube(size=12, mips=3):
+    """Signed values, binary16 denormals of both signs and both zeros among ordinary texels (the recipe of env_cases.special_cube without
+    its +-65504 texels)."""
+    rng = np.random.default_rng(4242)
+    codes = []
+    for m in range(mips):
+        s = env_cases.side(size, m)
+        t = rng.uniform(-2.0, 8.0, (6, s, s, 4)).astype(np.float16).view(np.uint16).copy()
+        kind = rng.integers(0, 10, (6, s, s, 3))
+        den = rng.integers(1, 0x400, (6, s, s, 3)).astype(np.uint16) | (rng.integers(0, 2, (6, s, s, 3)).astype(np.uint16) << 15)
+        rgb = t[..., :3]
+        rgb[kind == 0] = den[kind == 0]
+        rgb[kind == 1] = 0x0000
+        rgb[kind == 2] = 0x8000
+        t[..., 3] = 0x3C00
+        codes.append(t)
+    return env_cases.Cube(size, mips, codes, "signed_%d_%dmips" % (size, mips))
+
+
+@functools.lru_cache(maxsize=None)
+def constant_cube():
+    return env_cases.constant_cube(5, 1.5)
+
+
+# ---- matrices, float64, row vectors ---------------------------------------------------------------------------------------------------
+def scale(x, y, z):
+    return np.diag([x, y, z, 1.0])
+
+
+def translate(x, y, z):
+    m = np.eye(4); m[3, :3] = (x, y, z)
+    return m
+
+
+def rotate(axis, angle):
+    a = np.asarray(axis, np.float64); a = a / np.linalg.norm(a)
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    m = np.eye(4)
+    m[:3, :3] = (np.eye(3) + np.sin(angle) * K + (1 - np.cos(angle)) * K @ K).T
+    return m
+
+
+def look_at(eye, focus, up=(0.0, 1.0, 0.0)):
+    eye, focus = np.asarray(eye, np.float64), np.asarray(focus, np.float64)
+    z = focus - eye; z /= np.linalg.norm(z)
+    x = np.cross(up, z); x /= np.linalg.norm(x)
+    y = np.cross(z, x)
+    m = np.eye(4)
+    m[:3, 0], m[:3, 1], m[:3, 2] = x, y, z
+    m[3, :3] = (-x @ eye, -y @ eye, -z @ eye)
+    return m
+
+
+def perspective(fov_y, aspect, zn, zf):
+    h = 1.0 / np.tan(0.5 * fov_y)
+    m = np.zeros((4, 4))
+    m[0, 0], m[1, 1], m[2, 2], m[2, 3], m[3, 2] = h / aspect, h, zf / (zf - zn), 1.0, -zn * zf / (zf - zn)
+    return m
+
+
+# ---- meshes: (verts [nv 6] float32, idx [3 n] uint32) -----------------------------------------------------------------------------------
+def _mesh(pos, nrm, idx):
+    v = np.concatenate([np.asarray(pos, np.float64), np.asarray(nrm, np.float64)], axis=1).astype(np.float32)
+    return v, np.asarray(idx, np.uint32).reshape(-1)
+
+
+def join(*meshes):
+    vs, is_, at = [], [], 0
+    for v, i in meshes:
+        vs.append(v); is_.append(i + np.uint32(at)); at += len(v)
+    return np.concatenate(vs), np.concatenate(is_)
+
+
+def grid(nx, nz, x0, x1, z0, z1, y=0.0, normal=None):
+    """nx x nz quads in the plane y, two triangles each, shared vertices; normal: a function of the positions [n 3] -> normals [n 3]
+    (default +y)."""
+    gx, gz = np.meshgrid(np.linspace(x0, x1, nx + 1), np.linspace(z0, z1, nz + 1), indexing="ij")
+    pos = np.stack([gx.reshape(-1), np.full(gx.size, y), gz.reshape(-1)], axis=1)
+    nrm = np.tile([0.0, 1.0, 0.0], (len(pos), 1)) if normal is None else normal(pos)
+    a = (np.arange(nx)[:, None] * (nz + 1) + np.arange(nz)[None, :]).reshape(-1)
+    idx = np.stack([a, a + 1, a + nz + 1, a + 1, a + nz + 2, a + nz + 1], axis=1)
+    return _mesh(pos, nrm, idx)
+
+
+def sphere_cap(n_ring, n_seg, radius, half_angle, centre=(0.0, 0.0, 0.0)):
+    """A cap of a sphere around +y with smooth normals: an apex fan and n_ring - 1 rings of quads."""
+    pos, idx = [[0.0, 1.0, 0.0]], []
+    for r in range(1, n_ring + 1):
+        th = half_angle * r / n_ring
+        for s in range(n_seg):
+            ps = 2.0 * np.pi * s / n_seg
+            pos.append([np.sin(th) * np.cos(ps), np.cos(th), np.sin(th) * np.sin(ps)])
+    ring = lambda r, s: 1 + (r - 1) * n_seg + s % n_seg
+    for s in range(n_seg):
+        idx.append([0, ring(1, s), ring(1, s + 1)])
+    for r in range(1, n_ring):
+        for s in range(n_seg):
+            idx.append([ring(r, s), ring(r + 1, s), ring(r + 1, s + 1)]); idx.append([ring(r, s), ring(r + 1, s + 1), ring(r, s + 1)])
+    nrm = np.array(pos)
+    return _mesh(nrm * radius + np.asarray(centre), nrm, idx)
+
+
+def closed_ball(n_ring=6, n_seg=10, radius=1.0):
+    """A UV sphere with both poles as fans and smooth normals."""
+    pos = [[0.0, 1.0, 0.0]]
+    for r in range(1, n_ring):
+        th = np.pi * r / n_ring
+        for s in range(n_seg):
+            ps = 2.0 * np.pi * s / n_seg
+            pos.append([np.sin(th) * np.cos(ps), np.cos(th), np.sin(th) * np.sin(ps)])
+    pos.append([0.0, -1.0, 0.0])
+    last = len(pos) - 1
+    ring = lambda r, s: 1 + (r - 1) * n_seg + s % n_seg
+    idx = []
+    for s in range(n_seg):
+        idx.append([0, ring(1, s), ring(1, s + 1)]); idx.append([last, ring(n_ring - 1, s + 1), ring(n_ring - 1, s)])
+    for r in range(1, n_ring - 1):
+        for s in range(n_seg):
+            idx.append([ring(r, s), ring(r + 1, s), ring(r + 1, s + 1)]); idx.append([ring(r, s), ring(r + 1, s + 1), ring(r, s + 1)])
+    nrm = np.array(pos)
+    return _mesh(nrm * radius, nrm, idx)
+
+
+def room():
+    """The inside of the box [-1, 1]^3: 12 triangles, per face its own four vertices with the inward axis normal."""
+    pos, nrm, idx = [], [], []
+    for axis in range(3):
+        for sign in (-1.0, 1.0):
+            u, w = (axis + 1) % 3, (axis + 2) % 3
+            base = len(pos)
+            for a, b in ((-1, -1), (1, -1), (1, 1), (-1, 1)):
+                p = np.zeros(3); p[axis], p[u], p[w] = sign, a, b
+                n = np.zeros(3); n[axis] = -sign
+                pos.append(p); nrm.append(n)
+            idx += [[base, base + 1, base + 2], [base, base + 2, base + 3]]
+    return _mesh(pos, nrm, idx)
+
+
+def cone(apex, base_centre, base_radius, n=16):
+    """n triangles around an apex they all share, smooth normals."""
+    apex, c = np.asarray(apex, np.float64), np.asarray(base_centre, np.float64)
+    ax = apex - c; h = np.linalg.norm(ax); ax /= h
+    u = np.cross(ax, [0.3, 0.5, 0.8]); u /= np.linalg.norm(u); w = np.cross(ax, u)
+    pos, nrm = [apex], [ax]
+    for s in range(n):
+        ps = 2.0 * np.pi * s / n
+        r = np.cos(ps) * u + np.sin(ps) * w
+        pos.append(c + base_radius * r)
+        nn = h * r + base_radius * ax
+        nrm.append(nn / np.linalg.norm(nn))
+    idx = [[0, 1 + s, 1 + (s + 1) % n] for s in range(n)]
+    return _mesh(pos, nrm, idx)
+
+
+def oriented(mesh, world, eye):
+    """The mesh with every triangle wound so that it faces `eye` under `world` (the rasteriser culls the others): clockwise on the
+    screen, which is cross(v1 - v0, v2 - v0) towards the eye."""
+    v, i = mesh
+    i = i.reshape(-1, 3).copy()
+    p = (np.concatenate([v[:, :3].astype(np.float64), np.ones((len(v), 1))], axis=1) @ world)[:, :3]
+    t = p[i]
+    n = np.cross(t[:, 1] - t[:, 0], t[:, 2] - t[:, 0])
+    away = ((np.asarray(eye) - t.mean(axis=1)) * n).sum(axis=1) < 0.0
+    i[away] = i[away][:, [0, 2, 1]]
+    return v, i.reshape(-1).astype(np.uint32)
+
+
+# ---- a case --------------------------------------------------------------------------------------------------------------------------
+class Case:
+    """meshes, worlds (float64 4 x 4; world1_step: translation per frame of the second instance), camera (eye, focus, eye_step per frame; pan: the focus moves with the eye),
+    materials per frame position: a function k -> ((colour, rough, metal), (colour, rough, metal)), the cube, the sampler."""
+
+    def __init__(self, name, family, W, H, mesh0, mesh1, world0, world1, eye, focus, cube, materials, vndf=False, eye_step=(0.5, 0.5, 0.0),
+                 world1_step=(0.0, 0.0, 0.0), proj_bias=(0.0, 0.0), fov=0.9, pan=True, sun=None, lights=None):
+        self.name, self.family, self.W, self.H = name, family, W, H
+        self.world0, self.world1 = np.asarray(world0, np.float64), np.asarray(world1, np.float64)
+        self.eye, self.focus, self.eye_step, self.world1_step = np.asarray(eye, np.float64), np.asarray(focus, np.float64), np.asarray(eye_step), np.asarray(world1_step)
+        self.meshes = [oriented(mesh0, self.world0, self.eye), oriented(mesh1, self.world1, self.eye)]
+        assert all(i.size // 3 <= 512 for _, i in self.meshes) and W <= 96 and H <= 64 and cube.size <= 16
+        self.cube, self.materials, self.vndf, self.proj_bias, self.fov, self.pan = cube, materials, vndf, proj_bias, fov, pan
+        self.sun, self.lights = sun, lights      # functions of the frame position: (direction, irradiance) / a list of lights as dicts (capi.Light.of's arguments), or None
+
+    def view_proj(self, k):
+        return look_at(self.eye + k * self.eye_step, self.focus + (k * self.eye_step if self.pan else 0.0)) @ perspective(self.fov, self.W / self.H, 0.1, 100.0)
+
+    def worlds(self, k):
+        return self.world0, self.world1 @ translate(*(k * self.world1_step))
+
+    def constants(self, k):
+        """The 768 bytes of frame position k (frame index FRAMES[k]); the previous matrices are those of position k - 1."""
+        f = np.zeros(192, np.float32)
+        vp, vp_prev = self.view_proj(k), self.view_proj(k - 1)
+        for i, (w, wp) in enumerate(zip(self.worlds(k), self.worlds(k - 1))):
+            f[16 * i:16 * i + 16] = (w @ vp).T.reshape(-1)
+            f[32 + 16 * i:48 + 16 * i] = (wp @ vp_prev).T.reshape(-1)
+            it = np.zeros((3, 4)); it[:, :3] = np.linalg.inv(w[:3, :3])      # rows of the transpose of the inverse transpose
+            f[88 + 12 * i:88 + 12 * i + (12 if i == 0 else 11)] = it.reshape(-1)[:12 if i == 0 else 11]
+            f[136 + 20 * i:152 + 20 * i] = (w @ vp).T.reshape(-1)
+            f[152 + 20 * i:154 + 20 * i] = self.proj_bias
+        f[111:112] = np.array([FRAMES[k]], np.uint32).view(np.float32)
+        f[112:128] = np.linalg.inv(vp).T.reshape(-1)
+        f[128:131] = self.eye + k * self.eye_step
+        f[132:134] = self.proj_bias
+        for i, (colour, rough, metal) in enumerate(self.materials(k)):
+            f[176 + 4 * i:179 + 4 * i] = colour; f[179 + 4 * i] = 1.0
+            f[184 + 4 * i:186 + 4 * i] = (rough, metal)
+        return bvh_cases.frame_constants(*self.worlds(k), base=f.tobytes())
+
+
+def _fixed(m0, m1):
+    return lambda k: (m0, m1)
+
+
+SKEW0 = scale(2.0, 0.5, 1.25) @ rotate((1.0, 2.0, 0.5), 0.35) @ translate(0.2, -1.0, 0.3)
+SKEW1 = scale(1.25, 2.0, 0.5) @ rotate((0.5, -1.0, 2.0), 0.6) @ translate(-0.3, 0.4, 0.1)
+MIRROR = np.diag([-1.0, 1.0, 1.0, 1.0])
+ROUGH_CODES = (1.0 / 255.0, 0.02, 0.05, 0.1, 0.16, 0.25, 0.35, 0.5, 0.62, 0.8, 0.9, 1.0)      # ... and 0 on instance 0
+# (metallic of instance 0, of instance 1): a hit on either side of 0.5 from either side; every value on both instances
+METALS = ((0.0, 0.25), (0.25, 1.0), (0.75, 0.0), (1.0, 0.75))
+COLOURS = (((0.9, 0.0, 0.5), (1.5, 1.2, 0.7)), ((0.0, 0.8, 0.6), (0.0, 0.0, 0.0)), ((0.95, 0.93, 0.88), (0.3, 0.0, 0.9)), ((0.0, 0.0, 0.0), (1.0, 0.71, 0.29)))
+
+
+def _sweep_normals(eye_obj):
+    """Vertex normals of the `normals` family's grid (x in [-2, 2], z in [-2, 2]):
+      z < -0.7      tilted from +y by theta with cos(theta) from 0.998 (x = -2) to 1 exactly (x = 2): |n.y| crosses 0.999 inside
+      -0.7 .. 0.7   the same about -y: shading normals that face away from the eye
+      z > 0.7       perpendicular to the direction to the eye but for sin(beta), beta from -0.06 to 0.06 along x: NoV crosses zero"""
+    def f(p):
+        n = np.zeros_like(p)
+        c = 0.998 + 0.002 * (p[:, 0] + 2.0) / 4.0
+        c[p[:, 0] >= 2.0] = 1.0
+        s = np.sqrt(np.maximum(1.0 - c * c, 0.0))
+        psi = 2.5 * p[:, 2] + 0.3
+        tilt = np.stack([s * np.cos(psi), c, s * np.sin(psi)], axis=1)
+        down = tilt * [1.0, -1.0, 1.0]
+        v = eye_obj - p; v /= np.linalg.norm(v, axis=1)[:, None]
+        t = np.cross(v, [1.0, 0.0, 0.0]); t /= np.linalg.norm(t, axis=1)[:, None]
+        beta = 0.06 * p[:, 0] / 2.0
+        graze = np.cos(beta)[:, None] * t + np.sin(beta)[:, None] * v
+        n[:] = np.where((p[:, 2] < -0.7)[:, None], tilt, np.where((p[:, 2] <= 0.7)[:, None], down, graze))
+        return n
+    return f
+
+
+@functools.lru_cache(maxsize=None)
+def all_cases():
+    cases = []
+    slab = grid(2, 2, -2.0, 2.0, -2.0, 2.0)
+    cap = sphere_cap(5, 12, 1.0, 1.2)
+    mats = _fixed(((0.95, 0.93, 0.88), 0.5, 0.25), ((1.0, 0.71, 0.29), 0.16, 0.75))
+    # ---- transforms
+    cases.append(Case("skew_75x53", "transforms", 75, 53, slab, cap, SKEW0, SKEW1, (1.5, 3.0, -6.0), (0.0, -0.3, 0.0), smooth_cube(), mats,
+                      eye_step=(1.5, 0.4, 0.0), world1_step=(0.05, 0.02, -0.04), pan=True))
+    # ... under open sky with F0's green below 0.2 on both instances (0.03 and 0.085): where sat(50 F0.g) is 1 and a smaller factor would not be
+    dark_green = _fixed(((0.9, 0.0, 0.5), 0.5, 0.25), ((1.0, 0.1, 0.29), 0.16, 0.75))
+    cases.append(Case("mirrored_bias_75x53", "transforms", 75, 53, slab, cap, SKEW0 @ MIRROR, MIRROR @ SKEW1, (1.5, 3.0, -6.0), (0.0, -0.3, 0.0), smooth_cube(), dark_green,
+                      proj_bias=(0.3 / 75, -0.4 / 53)))
+    # ---- normals
+    eye = np.array([0.5, 4.0, -5.0])
+    w1 = translate(0.0, 0.0, 0.0)
+    # three strips with vertices of their own: an interpolated normal never runs from one rule to the next (through zero, between +y and -y)
+    sweep = join(*(grid(16, 4, -2.0, 2.0, z0, z1, normal=_sweep_normals(eye)) for z0, z1 in ((-2.0, -0.75), (-0.65, 0.65), (0.75, 2.0))))
+    under = grid(1, 1, -3.0, 3.0, -3.0, 3.0, y=-0.5)
+    nmats = _fixed(((0.95, 0.93, 0.88), 0.5, 0.25), ((1.0, 0.71, 0.29), 0.3, 0.75))
+    for vndf in (False, True):
+        cases.append(Case("normals_75x53" + ("_vndf" if vndf else ""), "vndf" if vndf else "normals", 75, 53, under, sweep, translate(0, 0, 0), w1, eye, (0.0, 0.0, 0.0),
+                          smooth_cube(), nmats, vndf=vndf))
+    # ---- materials: a closed room around a ball
+    room0 = scale(3.0, 1.5, 2.5) @ rotate((0.3, 1.0, 0.2), 0.2) @ translate(0.0, 0.5, 0.0)
+    ball1 = scale(0.8, 0.6, 0.7) @ rotate((1.0, 0.2, 0.4), 0.5) @ translate(0.3, 0.0, 0.4)
+    # (the last one, where both instances are metallic and the ball's roughness is 0.8 to 1: a cube whose levels differ, so that the level a
+    # roughness selects shows in the value)
+    cubes = (smooth_cube(), signed_cube(), constant_cube(), env_cases.random_cube(16, 5))
+    for vndf in (False, True):
+        for c in range(4):
+            def m(k, c=c):
+                r1 = ROUGH_CODES[3 * c + k]
+                r0 = 0.0 if (c, k) == (2, 1) else ROUGH_CODES[(3 * c + k + 5) % 12]
+                return (COLOURS[c][0], r0, METALS[c][0]), (COLOURS[c][1], r1, METALS[c][1])
+            cases.append(Case("materials_%d_64x48" % c + ("_vndf" if vndf else ""), "vndf" if vndf else "materials", 64, 48, room(), closed_ball(), room0, ball1,
+                              (-2.0, 1.2, -1.6), (0.3, 0.0, 0.4), cubes[c], m, vndf=vndf, eye_step=(0.3, 0.35, 0.1)))
+    # ---- hits: open sky, a shared vertex on a pixel centre, coincident sheets
+    hc = Case("sheets_vertex_96x64", "hits", 96, 64, slab, slab, scale(1.5, 1.0, 1.5) @ translate(0.0, -1.0, 0.0), np.eye(4), (0.0, 2.5, -6.0), (0.0, -0.2, 0.0), smooth_cube(),
+              _fixed(((0.95, 0.93, 0.88), 0.3, 0.75), ((1.0, 0.71, 0.29), 0.2, 0.25)))
+    # the apex: pixel (40, 22)'s centre of frame position 0, a third of the way into the depth range, unprojected
+    ndc = np.array([(40 + 0.5) / 96 * 2 - 1, -((22 + 0.5) / 64 * 2 - 1), 0.975, 1.0])
+    p = ndc @ np.linalg.inv(hc.view_proj(0)); apex = p[:3] / p[3]
+    sheet = grid(1, 1, -1.2, 0.2, -0.5, 1.0, y=0.6)
+    mesh1 = join(sheet, sheet, cone(apex, apex + np.array([0.1, -0.5, 0.9]), 0.6))
+    cases.append(Case(hc.name, "hits", 96, 64, slab, mesh1, hc.world0, np.eye(4), hc.eye, hc.focus, smooth_cube(), hc.materials))
+    # ---- sun: a slab with an occluder above it; the sun at the zenith, just above the slab's horizon (NoL 0.01) and slanted, so that the cap's
+    # far side lies below its own horizon; metallic 1 below (RayTracingOut1 is a carry-over there) and 0.75 above, then 0.25 and 1;
+    # roughness 0.1 x 0.25 on the checkerboard's odd cells and 0.02 on the cap: both below 1 / 32
+    slab0 = scale(1.5, 1.0, 1.5) @ translate(0.0, -1.0, 0.0)
+    over = join(grid(2, 2, -1.3, 0.3, -1.0, 0.6, y=-0.3), sphere_cap(3, 8, 0.5, 1.3, centre=(1.2, -0.9, 0.6)))
+    suns = (((0.0, 1.0, 0.0), (3.0, 2.5, 2.0)), ((1.0, 0.01, 0.2), (3.0, 2.5, 2.0)), ((0.4, 0.8, -0.3), (0.0, 2.0, 4.0)))
+
+    def sun_mats(k):
+        return (((0.95, 0.93, 0.88), 0.1, (1.0, 1.0, 0.25)[k]), ((1.0, 0.71, 0.29), 0.02, (0.75, 0.75, 1.0)[k]))
+    cases.append(Case("sun_75x53", "sun", 75, 53, slab, over, slab0, np.eye(4), (0.5, 2.0, -6.0), (0.0, -0.8, 0.0), smooth_cube(), sun_mats, sun=lambda k: suns[k]))
+    # ---- lights: the same scene.  A and B: point lights 0.4 and 0.25 above the slab with ranges 2.5 and 5 (pixels from 0.05 R to beyond R);
+    # a spot whose two cones cross the slab; a light 0.005 above the surface (the floor m2); one above the occluder and one between it and
+    # the slab (the interval ends at the light); two lights, then eight with one of zero intensity in the middle, then three
+    cone_cos = lambda deg: float(np.cos(np.radians(deg)))
+    spot_axis = np.array([0.1, -1.0, 0.2]) / np.linalg.norm([0.1, -1.0, 0.2])
+    A = dict(position=(0.5, -0.6, 0.3), intensity=(2.0, 1.5, 1.0), range=2.5)
+    B = dict(position=(-1.0, -0.75, -0.5), intensity=(0.5, 1.0, 2.0), range=5.0)
+    spot = dict(position=(0.3, 1.5, -0.2), intensity=(20.0, 20.0, 16.0), range=8.0, axis=tuple(spot_axis), cos_outer=cone_cos(35.0), cos_inner=cone_cos(15.0))
+    dark = dict(position=(0.0, 0.0, 0.0), intensity=(0.0, 0.0, 0.0), range=10.0)
+    low = dict(position=(0.7, -0.995, -0.8), intensity=(0.002, 0.002, 0.001), range=1.0)
+    above = dict(position=(-0.4, 0.5, -0.1), intensity=(6.0, 6.0, 6.0), range=6.0)
+    under = dict(position=(-0.4, -0.6, -0.1), intensity=(1.0, 0.5, 0.25), range=3.0)
+    far = dict(position=(2.0, 0.5, 2.0), intensity=(4.0, 8.0, 4.0), range=4.0)
+    light_sets = ([A, spot], [A, B, spot, dark, low, above, under, far], [above, dark, under])
+    cases.append(Case("lights_75x53", "lights", 75, 53, slab, over, slab0, np.eye(4), (0.5, 2.0, -6.0), (0.0, -0.8, 0.0), smooth_cube(),
+                      _fixed(((0.95, 0.93, 0.88), 0.5, 0.25), ((1.0, 0.71, 0.29), 0.3, 1.0)), lights=lambda k: light_sets[k]))
+    assert len({c.name for c in cases}) == len(cases)
+    return tuple(cases)
+
+
+NAMES = tuple(c.name for c in all_cases())
+FAMILIES = tuple(sorted({c.family for c in all_cases()}))
+
+
+def by_name(name):
+    return next(c for c in all_cases() if c.name == name)

@@ -1,0 +1,686 @@
+"""Float64 model of one frame's depth-1 shading path per pixel, numpy only: the primary surface ray generation derives from the visibility
+word, the GGX half vector (NDF map, and the VNDF map of rtggx_set_sampler), the ray's weight, the closest hit, the hit's shading and the
+miss.  It is the second witness of raytrace.hip next to the CPU oracle (oracle/orc_raytrace.h), which follows the kernel function by
+function; this file shares no code with either and derives each step by another route wherever one exists:
+
+  primary surface  the pixel centre's eye ray (ProjToWorld, ProjBias) meets the plane of the world-space triangle the visibility word names;
+                   barycentrics are solved in world space (no screen-space gradients); N = n inverse-transpose(World), the inverse transpose
+                   computed here from World, never read from the constants; velocity from WorldViewProjsPrev by definition
+  sample           the integer hash in Python integers (exact); phi = 2 pi s / 256
+  weight           BRDF NoL / pdf written from the definitions
+  closest hit      Moeller-Trumbore over every triangle of both instances in world space, no tree, no object space
+  hit shading      cube map and the nine SH coefficients from tests/env_ref.py; irradiance as sum A_l L_lm Y_lm(N)
+
+A rounding is taken only where a typed texel is stored.  Every decision fp32 and float64 may take differently is FLAGGED per pixel, not
+guessed (FLAG_* below); flagged pixels are compared with the oracle bit for bit like all others, but not with this model.
+
+The sun's (angle 0) and the local lights' (radius 0) terms of the primary surface are sun_pass and lights_pass, from include/rtggx.h.
+Out of scope: recursion depth 2 to 4, more than one sample per pixel, sample sets above 256, ray rate 4, the sun's disk,
+the lights' radii and both in reflections.
+
+Conventions: row vectors (p' = p M); the frame constants are the 768 bytes of RtggxFrameConstants (include/rtggx.h), 4x4 matrices stored
+transposed, 3x4 blocks as three rows of the transpose."""
+import numpy as np
+
+import env_ref as E
+
+RAY_TMIN, RAY_TMAX = 1e-5, 10000.0      # the product's interval (rt_queue.h), both ends exclusive
+REL_T, EDGE, NOL_EPS, UV_EPS, UP_EPS = 1e-5, 1e-5, 1e-5, 1e-4, 1e-5
+UP_SWITCH = 0.999
+FLAG_T_TIE, FLAG_EDGE, FLAG_NOL, FLAG_CHECKER, FLAG_UP, FLAG_TMIN, FLAG_CANCEL, FLAG_GRAZING, FLAG_RANGE, FLAG_CONE = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512
+FLAG_NAMES = {FLAG_RANGE: "range", FLAG_CONE: "cone", FLAG_T_TIE: "t_tie", FLAG_EDGE: "edge", FLAG_NOL: "nol", FLAG_CHECKER: "checker", FLAG_UP: "up", FLAG_TMIN: "tmin", FLAG_CANCEL: "cancel",
+              FLAG_GRAZING: "grazing"}
+# The reflection's weight is proportional to NoL (the other factors stay bounded: Vis's NoL + sqrt(...) is at least alpha), so the pixel's
+# RELATIVE error is the absolute error of NoL over NoL.  That absolute error is a few 1e-6 in fp32 -- the primary surface's barycentrics come
+# from screen-space gradients, P and V inherit their error, the reflection doubles it -- so below NoL = 2^-8 a faithful fp32 value is
+# off by more than 1e-3 of itself, which is two codes of R11G11B10F.  Such pixels are ill-conditioned in the distance this test uses (ulps of
+# the pixel's own largest channel) and are flagged, like a decision; nothing else about them is special.
+GRAZING_NOL = 2.0 ** -8
+# The one ill-conditioned step of the path: each sampler takes the root of a difference of two numbers near 1 -- 1 - cos^2 theta (NDF map, and
+# the diffuse ray's sphere point), 1 - t1^2 - t2^2 (VNDF map) -- and fp32 rounds that difference with an ABSOLUTE error of a few 2^-24 however
+# small it is: the direction is then off by up to sqrt(2^-22), far beyond every other threshold here.  The model cannot know which way fp32
+# rounds, so it evaluates the pixel three times -- the difference as it is, and with CANCEL_SLACK taken from and added to it -- and returns
+# the hull of the three as the pixel's interval; where the three take different decisions (another triangle, a miss, another checker
+# cell, another side of NoL = 0) the pixel is flagged FLAG_CANCEL.  4 x 2^-24: the roundings of cos^2 theta (a quotient of two rounded
+# numbers near 1, three half-ulps of 1) and one for the difference.
+CANCEL_SLACK = 4.0 * 2.0 ** -24
+
+
+# ---- frame constants ---------------------------------------------------------------------------------------------------------------
+def read_constants(fc_bytes):
+    f = np.frombuffer(bytes(fc_bytes), np.float32)
+    assert f.size == 192
+    d = f.astype(np.float64)
+    m4 = lambda a: d[a:a + 16].reshape(4, 4).T.copy()
+
+    def m43(a):
+        m = np.eye(4)
+        m[:, :3] = d[a:a + 12].reshape(3, 4).T
+        return m
+    return {"wvp": [m4(0), m4(16)], "wvp_prev": [m4(32), m4(48)], "world": [m43(64), m43(76)],
+            "frame_index": int(f[111:112].view(np.uint32)[0]), "proj_to_world": m4(112), "eye": d[128:131].copy(), "proj_bias": d[132:134].copy(),
+            "colour": [d[176:179].copy(), d[180:183].copy()], "rough": [d[184], d[188]], "metal": [d[185], d[189]]}
+
+
+def inverse_transpose(world):
+    return np.linalg.inv(world[:3, :3]).T
+
+
+# ---- stores --------------------------------------------------------------------------------------------------------------------------
+def unorm_code(x, maxv):
+    x = np.asarray(x, np.float64)
+    return np.where(x > 0.0, np.floor(np.minimum(x, 1.0) * maxv + 0.5), 0.0).astype(np.int64)
+
+
+def ufloat_values(mbits):
+    """Every finite value of the unsigned small float with `mbits` mantissa bits, by code."""
+    c = np.arange(31 << mbits)
+    e, m = c >> mbits, (c & ((1 << mbits) - 1)).astype(np.float64)
+    return np.where(e == 0, m * 2.0 ** (-14 - mbits), (1.0 + m / (1 << mbits)) * 2.0 ** (e - 15.0))
+
+
+def ufloat_code(x, mbits):
+    """float64 -> code of the unsigned small float: negatives to 0, round to nearest even, saturating at the largest finite value; NaN to
+    the format's NaN, +inf to its inf."""
+    x = np.asarray(x, np.float64)
+    tab = ufloat_values(mbits)
+    v = np.clip(np.where(np.isnan(x), 0.0, x), 0.0, tab[-1])
+    hi = np.clip(np.searchsorted(tab, v, side="left"), 1, tab.size - 1)
+    lo = hi - 1
+    dl, dh = v - tab[lo], tab[hi] - v
+    c = np.where(dl < dh, lo, np.where(dh < dl, hi, np.where(lo % 2 == 0, lo, hi)))
+    c = np.where(np.isposinf(x), 31 << mbits, c)
+    return np.where(np.isnan(x), (31 << mbits) | 1, c).astype(np.int64)
+
+
+def r11g11b10_codes(rgb):
+    rgb = np.asarray(rgb, np.float64)
+    return np.stack([ufloat_code(rgb[..., 0], 6), ufloat_code(rgb[..., 1], 6), ufloat_code(rgb[..., 2], 5)], axis=-1)
+
+
+def r11g11b10_split(words):
+    w = np.asarray(words).astype(np.int64)
+    return np.stack([w & 0x7FF, (w >> 11) & 0x7FF, w >> 22], axis=-1)
+
+
+def f16_ordered(x):
+    """float64 -> binary16 (round to nearest even) as an integer that orders like the value; both zeros map to 0."""
+    with np.errstate(over="ignore"):
+        h = np.asarray(x, np.float64).astype(np.float16)
+    c = h.view(np.uint16).astype(np.int64)
+    return np.where(c & 0x8000, -(c & 0x7FFF), c)
+
+
+def f16_words_ordered(words16):
+    c = np.asarray(words16).astype(np.int64)
+    return np.where(c & 0x8000, -(c & 0x7FFF), c)
+
+
+def ulp32(x):
+    x = np.maximum(np.abs(np.asarray(x, np.float64)), 2.0 ** -126)
+    return 2.0 ** (np.floor(np.log2(x)) - 23.0)
+
+
+# ---- the sample ----------------------------------------------------------------------------------------------------------------------
+def _hash(seed):
+    seed = (seed * 747796405 + 1) & 0xFFFFFFFF
+    seed = (((seed >> ((seed >> 28) + 4)) ^ seed) * 277803737) & 0xFFFFFFFF
+    return ((seed >> 22) ^ seed) & 0xFFFFFFFF
+
+
+def sample_params(W, H, frame_index):
+    """-> (s [H W] int, xi_y [H W]): the slot of the 256-member set and the second coordinate."""
+    s = np.zeros(W * H, np.int64); y = np.zeros(W * H)
+    for i in range(W * H):
+        k = _hash((_hash(i) + frame_index) & 0xFFFFFFFF) % 256
+        s[i] = k; y[i] = (_hash(k) & 0xFFFF) / 65536.0
+    return s, y
+
+
+# ---- vectors ---------------------------------------------------------------------------------------------------------------------------
+def _dot(a, b):
+    return (a * b).sum(axis=-1)
+
+
+def _unit(a):
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return a / np.sqrt(_dot(a, a))[..., None]
+
+
+def _sat(x):
+    return np.clip(x, 0.0, 1.0)
+
+
+def tangent_frame(N):
+    """The stated rule: up = y unless |n.y| >= 0.999, then x; T = unit(up x N), B = N x T.  -> (T, B, near the switch)."""
+    up = np.where((np.abs(N[:, 1]) < UP_SWITCH)[:, None], [0.0, 1.0, 0.0], [1.0, 0.0, 0.0])
+    T = _unit(np.cross(up, N))
+    return T, np.cross(N, T), np.abs(np.abs(N[:, 1]) - UP_SWITCH) <= UP_EPS
+
+
+def ndf_half_vector(N, alpha, phi, xi, slack=0.0):
+    """GGX NDF map: cos^2 theta = (1 - xi) / (1 + (alpha^2 - 1) xi).  slack: added to 1 - cos^2 theta before its root (CANCEL_SLACK)."""
+    c2 = (1.0 - xi) / (1.0 + (alpha * alpha - 1.0) * xi)
+    st, ct = np.sqrt(np.maximum(1.0 - c2 + slack, 0.0)), np.sqrt(c2)
+    T, B, near = tangent_frame(N)
+    return T * (st * np.cos(phi))[:, None] + B * (st * np.sin(phi))[:, None] + N * ct[:, None], near
+
+
+def vndf_half_vector(N, V, alpha, phi, u, slack=0.0):
+    """Heitz 2018, "Sampling the GGX Distribution of Visible Normals", listing 1 (isotropic): U1 = u, the angle phi = 2 pi U2.
+    slack: added to 1 - t1^2 - t2^2 before its root (CANCEL_SLACK)."""
+    T, B, near = tangent_frame(N)
+    al = alpha[:, None] if np.ndim(alpha) else alpha
+    ve = np.stack([_dot(V, T), _dot(V, B), _dot(V, N)], axis=1)
+    vh = _unit(ve * np.concatenate([np.broadcast_to(al, (len(N), 1))] * 2 + [np.ones((len(N), 1))], axis=1))
+    lensq = vh[:, 0] ** 2 + vh[:, 1] ** 2
+    with np.errstate(invalid="ignore", divide="ignore"):
+        t1v = np.where((lensq > 0)[:, None], np.stack([-vh[:, 1], vh[:, 0], np.zeros(len(N))], axis=1) / np.sqrt(lensq)[:, None], [1.0, 0.0, 0.0])
+    t2v = np.cross(vh, t1v)
+    r = np.sqrt(u)
+    t1, t2 = r * np.cos(phi), r * np.sin(phi)
+    s = 0.5 * (1.0 + vh[:, 2])
+    t2 = (1.0 - s) * np.sqrt(1.0 - t1 * t1) + s * t2
+    nh = t1[:, None] * t1v + t2[:, None] * t2v + np.sqrt(np.maximum(0.0, 1.0 - t1 * t1 - t2 * t2 + slack))[:, None] * vh
+    ne = _unit(np.stack([alpha * nh[:, 0], alpha * nh[:, 1], np.maximum(0.0, nh[:, 2])], axis=1))
+    return T * ne[:, :1] + B * ne[:, 1:2] + N * ne[:, 2:3], near
+
+
+# ---- BRDF terms, from the definitions -----------------------------------------------------------------------------------------------
+def ggx_d(alpha, NoH):
+    a2 = alpha * alpha
+    return a2 / (np.pi * (NoH * NoH * (a2 - 1.0) + 1.0) ** 2)
+
+
+def smith_lambda_term(alpha, c):
+    """c + sqrt(c (c - c a^2) + a^2): one factor of the separable Smith visibility's denominator."""
+    a2 = alpha * alpha
+    return c + np.sqrt(c * (c - c * a2) + a2)
+
+
+def vis_smith(alpha, NoV, NoL):
+    return 1.0 / (smith_lambda_term(alpha, NoV) * smith_lambda_term(alpha, NoL))
+
+
+def g1(alpha, c):
+    return 2.0 * c / smith_lambda_term(alpha, c)
+
+
+def f0_of(colour, metal):
+    return 0.04 + (colour - 0.04) * np.asarray(metal)[..., None]
+
+
+def fresnel(f0, VoH):
+    return f0 + (_sat(50.0 * f0[..., 1:2]) - f0) * ((1.0 - VoH) ** 5)[..., None]
+
+
+def env_brdf_approx(f0, rough, NoV):
+    """The mobile approximation of the pre-integrated environment BRDF, from its stated coefficients."""
+    r = rough[:, None] * np.array([-1.0, -0.0275, -0.572, 0.022]) + np.array([1.0, 0.0425, 1.04, -0.04])
+    a004 = np.minimum(r[:, 0] ** 2, 2.0 ** (-9.28 * NoV)) * r[:, 0] + r[:, 1]
+    A, Bt = -1.04 * a004 + r[:, 2], (1.04 * a004 + r[:, 3]) * _sat(50.0 * f0[:, 1])
+    return f0 * A[:, None] + Bt[:, None]
+
+
+def ndf_weight(f0, alpha, NoV, NoL, VoH, NoH):
+    """BRDF NoL / pdf_L with BRDF = D F Vis and pdf_L = D NoH / (4 VoH)."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return fresnel(f0, VoH) * (vis_smith(alpha, NoV, NoL) * NoL * 4.0 * VoH / NoH)[..., None]
+
+
+def vndf_weight(f0, alpha, NoL, VoH):
+    return fresnel(f0, VoH) * g1(alpha, NoL)[..., None]
+
+
+SH_BAND_FACTORS = np.array([np.pi] + [2.0 * np.pi / 3.0] * 3 + [np.pi / 4.0] * 5)      # the clamped cosine's zonal coefficients A_l
+
+
+def sh_irradiance(coeffs, N):
+    """E(N) = sum A_l L_lm Y_lm(N), not below zero; Y in env_ref's frame (x, y, z) = (-N.x, -N.y, N.z)."""
+    return np.maximum((E.sh_basis(N) * SH_BAND_FACTORS) @ coeffs, 0.0)
+
+
+# ---- the scene the model traces ------------------------------------------------------------------------------------------------------
+class Scene:
+    """Two meshes ((verts [nv 6], idx) in object space), the cube (env_cases.Cube) and what is derived once: the SH coefficients."""
+
+    def __init__(self, meshes, cube):
+        self.meshes = [(np.asarray(v, np.float64), np.asarray(i).reshape(-1, 3).astype(np.int64)) for v, i in meshes]
+        self.cube = cube
+        self.sh = E.sh_project(cube.levels[0], cube.size)[0]
+
+    def environment(self, d, level):
+        return E.environment(self.cube.levels, self.cube.size, d, level)
+
+
+def _world_triangles(scene, fc):
+    """-> (tris [m 3 3] world space, inst [m], prim [m]) in the order of the ids: the first of several minima is the lower id."""
+    tris, inst, prim = [], [], []
+    for k, (v, i) in enumerate(scene.meshes):
+        p = np.concatenate([v[:, :3], np.ones((len(v), 1))], axis=1) @ fc["world"][k]
+        tris.append(p[i][:, :, :3]); inst.append(np.full(len(i), k)); prim.append(np.arange(len(i)))
+    return np.concatenate(tris), np.concatenate(inst), np.concatenate(prim)
+
+
+def closest_hit(tris, org, d, skip, tmin=RAY_TMIN, tmax=RAY_TMAX):
+    """Brute force over every triangle.  org, d [n 3]; skip [n]: index into tris of the origin's primitive.  -> dict: valid, tri, t, b [n 3]
+    (weights of the three vertices), flags."""
+    n, m = len(org), len(tris)
+    out = {"valid": np.zeros(n, bool), "tri": np.zeros(n, np.int64), "t": np.full(n, np.inf), "b": np.zeros((n, 3)), "flags": np.zeros(n, np.int64)}
+    e1, e2 = tris[:, 1] - tris[:, 0], tris[:, 2] - tris[:, 0]
+    same = (tris[:, None] == tris[None]).all(axis=(2, 3))          # coincident triangles: their t is equal exactly, on every side
+    step = max(1, 400000 // max(m, 1))
+    for a in range(0, n, step):
+        o, dd, sk = org[a:a + step], d[a:a + step], skip[a:a + step]
+        k = len(o)
+        p = np.cross(dd[:, None, :], e2[None])
+        det = _dot(e1[None], p)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            inv = 1.0 / det
+            s = o[:, None, :] - tris[None, :, 0]
+            u = _dot(s, p) * inv
+            q = np.cross(s, e1[None])
+            v = _dot(dd[:, None, :], q) * inv
+            t = _dot(e2[None], q) * inv
+        w = 1.0 - u - v
+        lo = np.minimum(np.minimum(u, v), w)
+        usable = (det != 0.0) & (np.arange(m)[None] != sk[:, None]) & np.isfinite(t)
+        tm = np.asarray(tmax, np.float64)[a:a + step][:, None] if np.ndim(tmax) else tmax
+        inside = usable & (lo >= 0.0) & (t > tmin) & (t < tm)
+        tt = np.where(inside, t, np.inf)
+        best = np.argmin(tt, axis=1)
+        r = np.arange(k)
+        tb = tt[r, best]
+        valid = np.isfinite(tb)
+        flags = np.zeros(k, np.int64)
+        # a second candidate as close as rounding: a tie, unless it is the same triangle once more (equal t on every side, the lower id wins)
+        reach = np.where(valid, tb * (1.0 + REL_T), np.inf)
+        other = inside & (tt <= reach[:, None]) & (np.arange(m)[None] != best[:, None]) & ~(same[best] & (tt == tb[:, None]))
+        flags |= np.where(other.any(axis=1), FLAG_T_TIE, 0)
+        # a barycentric within EDGE of zero, on either side, on anything that is or could become the closest hit
+        edge = usable & (np.abs(lo) <= EDGE) & (t > 0.5 * tmin) & (t < tm) & (t <= reach[:, None])
+        flags |= np.where(edge.any(axis=1), FLAG_EDGE, 0)
+        ends = usable & (lo >= -EDGE) & (((t > 0.5 * tmin) & (t < 2.0 * tmin)) | (np.abs(t - tm) < 1e-3 * tm))
+        flags |= np.where(ends.any(axis=1), FLAG_TMIN, 0)
+        sl = slice(a, a + k)
+        out["valid"][sl], out["tri"][sl], out["t"][sl], out["flags"][sl] = valid, best, tb, flags
+        out["b"][sl] = np.stack([w[r, best], u[r, best], v[r, best]], axis=1)
+    return out
+
+
+def _checker_roughness(inst, uv, rough):
+    """Instance 0's checkerboard: a quarter of the roughness where the two integer parts of 5 uv differ in parity (negative: 0).
+    -> (roughness, within UV_EPS of a step)."""
+    g = 5.0 * uv
+    cell = np.floor(np.maximum(g, 0.0)).astype(np.int64)
+    odd = ((cell[:, 0] ^ cell[:, 1]) & 1) == 1
+    near = (np.abs(g - np.round(g)) <= UV_EPS).any(axis=1) & (np.round(g) >= 0.0).any(axis=1)
+    return np.where((inst == 0) & odd, 0.25 * rough, rough), near & (inst == 0)
+
+
+def _uv(n, p):
+    """Tri-planar coordinates from the object-space normal and position, scales (1, 0.2, 1)."""
+    a = np.abs(n)
+    s = p * np.array([1.0, 0.2, 1.0])
+    uv = a[:, :1] * s[:, [1, 2]] + a[:, 1:2] * s[:, [2, 0]] + a[:, 2:3] * s[:, [0, 1]]
+    return 0.5 * uv + 0.5
+
+
+def _attributes(scene, fc, inst, prim, b):
+    """Object-space attributes at barycentric weights b [n 3] of (inst, prim) -> dict: pos_obj, N (world), rough, metal, colour, flags."""
+    n = len(inst)
+    pos, nrm = np.zeros((n, 3)), np.zeros((n, 3))
+    for k, (v, i) in enumerate(scene.meshes):
+        at = inst == k
+        if at.any():
+            vv = v[i[prim[at]]]                       # [k 3 6]
+            pos[at] = (b[at][:, :, None] * vv[:, :, :3]).sum(axis=1)
+            nrm[at] = (b[at][:, :, None] * vv[:, :, 3:]).sum(axis=1)
+    it = np.stack([inverse_transpose(fc["world"][0]), inverse_transpose(fc["world"][1])])
+    N = _unit(np.einsum("ni,nij->nj", nrm, it[inst]))
+    rough0 = np.array(fc["rough"])[inst]
+    rough, near = _checker_roughness(inst, _uv(nrm, pos), rough0)
+    return {"pos_obj": pos, "N": N, "rough": rough, "metal": np.array(fc["metal"])[inst], "colour": np.stack(fc["colour"])[inst],
+            "flags": np.where(near, FLAG_CHECKER, 0)}
+
+
+def _scale(lo, hi, f):
+    a, b = lo * f, hi * f
+    return np.minimum(a, b), np.maximum(a, b)
+
+
+def shade_ray(scene, fc, tris, tri_inst, tri_prim, org, d, skip, diffuse_group, preset):
+    """What a depth-0 ray brings back -> (lo, hi [n 3], flags [n]).  preset [n 3]: the payload's colour x metallic; a reflection-group ray
+    whose preset has no positive channel returns the preset from a hit."""
+    n = len(org)
+    h = closest_hit(tris, org, d, skip)
+    lo, hi = np.zeros((n, 3)), np.zeros((n, 3))
+    flags = h["flags"].copy()
+    miss = ~h["valid"]
+    if miss.any():
+        lo[miss], hi[miss] = scene.environment(d[miss], 0.0)
+    hit = h["valid"]
+    if not diffuse_group:
+        dark = hit & (preset <= 0.0).all(axis=1)
+        lo[dark] = hi[dark] = preset[dark]
+        hit = hit & ~dark
+    if hit.any():
+        k = np.nonzero(hit)[0]
+        a = _attributes(scene, fc, tri_inst[h["tri"][k]], tri_prim[h["tri"][k]], h["b"][k])
+        # m = 0.5 decides between the two shadings; the constant is the same fp32 number on every side, so the decision is too -- but a case
+        # that sits on the threshold tests nothing, and none may (m = 1 is a legitimate material: it only zeroes a factor)
+        assert not (a["metal"] == 0.5).any(), "a hit's metallic is exactly 0.5"
+        flags[k] |= a["flags"]
+        N, V = a["N"], -d[k]
+        mirror = a["metal"] > 0.5
+        l, u = np.zeros((len(k), 3)), np.zeros((len(k), 3))
+        if mirror.any():
+            j = mirror
+            r, al = a["rough"][j], a["rough"][j] ** 2
+            Nj, Vj = N[j], V[j]
+            R = 2.0 * _dot(Nj, Vj)[:, None] * Nj - Vj
+            with np.errstate(invalid="ignore"):
+                w = (1.0 - al) * (np.sqrt(1.0 - al) + al)
+            dr = Nj + w[:, None] * (R - Nj)
+            NoL = _dot(Nj, dr)
+            with np.errstate(divide="ignore"):
+                level = (len(scene.cube.levels) - 1.0) - (3.0 - 1.15 * np.log2(r))
+            el, eh = scene.environment(dr, np.where(np.isnan(level), 0.0, level))
+            f = env_brdf_approx(f0_of(a["colour"][j], a["metal"][j]), r, _sat(_dot(Nj, Vj)))
+            el, eh = _scale(el, eh, f)
+            dark = NoL <= 0.0
+            el[dark] = eh[dark] = 0.0
+            l[j], u[j] = el, eh
+            fl = np.zeros(len(k), np.int64); fl[j] = np.where(np.abs(NoL) <= NOL_EPS, FLAG_NOL, 0)
+            flags[k] |= fl
+        if (~mirror).any():
+            j = ~mirror
+            c = a["colour"][j] * ((1.0 - a["metal"][j])[:, None] if diffuse_group else 1.0)
+            l[j] = u[j] = sh_irradiance(scene.sh, N[j]) / np.pi * c
+        lo[k], hi[k] = l, u
+    sig = np.stack([np.where(h["valid"], h["tri"], -1).astype(np.float64), np.zeros(n)], axis=1)
+    if h["valid"].any() and hit.any():
+        sig[k, 1] = a["rough"]
+    return lo, hi, flags, sig
+
+
+def eye_ray_barycentrics(proj_to_world, T, ndc):
+    """Weights of the three vertices of the world-space triangles T [n 3 3] where the eye rays through ndc [n 2] meet their planes: the ray
+    joins the unprojected points at depth 0 and 1; the weights solve the 2 x 2 normal equations of P - v0 = b1 e1 + b2 e2."""
+    n = len(ndc)
+
+    def unproject(z):
+        p = np.concatenate([ndc, np.full((n, 1), z), np.ones((n, 1))], axis=1) @ proj_to_world
+        return p[:, :3] / p[:, 3:]
+    p0, p1 = unproject(0.0), unproject(1.0)
+    e1, e2 = T[:, 1] - T[:, 0], T[:, 2] - T[:, 0]
+    nrm = np.cross(e1, e2)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        s = _dot(T[:, 0] - p0, nrm) / _dot(p1 - p0, nrm)
+        r = p0 + s[:, None] * (p1 - p0) - T[:, 0]
+        g11, g12, g22 = _dot(e1, e1), _dot(e1, e2), _dot(e2, e2)
+        den = g11 * g22 - g12 * g12
+        b1 = (g22 * _dot(r, e1) - g12 * _dot(r, e2)) / den
+        b2 = (g11 * _dot(r, e2) - g12 * _dot(r, e1)) / den
+    return np.stack([1.0 - b1 - b2, b1, b2], axis=1)
+
+
+def frame(scene, fc_bytes, vis, W, H, vndf=False, prev=None):
+    """One frame.  vis [H W] uint32: the visibility words (the rasteriser's, taken as input).  prev: the previous frame's result, for the
+    words a frame carries over (RayTracingOut1 where no diffuse ray is traced, the rough-metal word where nothing is drawn).
+    -> dict over [H W]: covered, flags, normal_value [.. 3], rm_value [.. 2], velocity_value [.. 2], refl_lo/hi, diff_lo/hi [.. 3],
+       refl_traced, diff_traced, diff_written, rm_written, rays."""
+    fc = read_constants(fc_bytes)
+    n = W * H
+    vis = np.asarray(vis).reshape(-1).astype(np.int64)
+    covered = vis > 0
+    word = np.where(covered, vis - 1, 0)
+    inst, prim = word >> 24, word & 0xFFFFFF
+    tris, tri_inst, tri_prim = _world_triangles(scene, fc)
+    first = np.array([0, len(scene.meshes[0][1])])
+    tri_of = first[np.minimum(inst, 1)] + prim
+    py, px = np.divmod(np.arange(n), W)
+    ndc = np.stack([(px + 0.5) / W * 2.0 - 1.0, -((py + 0.5) / H * 2.0 - 1.0)], axis=1)
+
+    def unproject(xy, z):
+        p = np.concatenate([xy, np.full((n, 1), z), np.ones((n, 1))], axis=1) @ fc["proj_to_world"]
+        return p[:, :3] / p[:, 3:]
+
+    # ---- primary surface: the eye ray through the pixel centre (less the jitter) meets the triangle's plane
+    ndc_b = ndc - fc["proj_bias"]
+    b = eye_ray_barycentrics(fc["proj_to_world"], tris[tri_of], ndc_b)
+    b[~covered] = [1.0, 0.0, 0.0]
+    a = _attributes(scene, fc, np.minimum(inst, 1), np.where(covered, prim, 0), b)
+    flags = np.where(covered, a["flags"], 0)
+    N, rough, metal, colour = a["N"], a["rough"], a["metal"], a["colour"]
+    P = np.concatenate([a["pos_obj"], np.ones((n, 1))], axis=1)
+    P = np.einsum("ni,nij->nj", P, np.stack(fc["world"])[np.minimum(inst, 1)])[:, :3]
+    V = _unit(fc["eye"] - P)
+    hp = np.einsum("ni,nij->nj", np.concatenate([a["pos_obj"], np.ones((n, 1))], axis=1), np.stack(fc["wvp_prev"])[np.minimum(inst, 1)])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        velocity = (ndc_b - hp[:, :2] / hp[:, 3:]) * [0.5, -0.5]
+    velocity[~covered] = 0.0
+    N[~covered] = 0.0
+
+    out = {"covered": covered.reshape(H, W), "normal_value": (N * 0.5 + 0.5).reshape(H, W, 3), "rm_value": np.stack([rough, metal], axis=1).reshape(H, W, 2),
+           "velocity_value": velocity.reshape(H, W, 2), "rm_written": covered.reshape(H, W)}
+
+    refl_lo, refl_hi = np.zeros((n, 3)), np.zeros((n, 3))
+    diff_lo, diff_hi = np.full((n, 3), np.nan), np.full((n, 3), np.nan)
+    # ---- nothing drawn: the environment along the pixel's eye ray (no jitter) into both images
+    sky = ~covered
+    if sky.any():
+        Vs = _unit(fc["eye"] - unproject(ndc, 0.0))
+        l, h = scene.environment(-Vs[sky], 0.0)
+        refl_lo[sky], refl_hi[sky] = l, h
+        diff_lo[sky], diff_hi[sky] = l, h
+
+    s_slot, xi = sample_params(W, H, fc["frame_index"])
+    phi = 2.0 * np.pi * s_slot / 256.0
+    c = np.nonzero(covered)[0]
+    refl_traced = np.zeros(n, bool); diff_traced = np.zeros(n, bool); refl_nol = np.zeros(n)
+    if c.size:
+        Nc, Vc, Pc, al = N[c], V[c], P[c], rough[c] ** 2
+        f0 = f0_of(colour[c], metal[c])
+        preset = colour[c] * metal[c][:, None]
+        res = []
+        for slack in (0.0, -CANCEL_SLACK, CANCEL_SLACK):
+            Hh, near_up = vndf_half_vector(Nc, Vc, al, phi[c], xi[c], slack) if vndf else ndf_half_vector(Nc, al, phi[c], xi[c], slack)
+            R = 2.0 * _dot(Vc, Hh)[:, None] * Hh - Vc
+            NoL = _dot(Nc, R)
+            fl = np.where(near_up, FLAG_UP, 0) | np.where(np.abs(NoL) <= NOL_EPS, FLAG_NOL, 0) | np.where((NoL > 0.0) & (NoL < GRAZING_NOL), FLAG_GRAZING, 0)
+            go = NoL > 0.0
+            l, h, sig = np.zeros((c.size, 3)), np.zeros((c.size, 3)), np.full((c.size, 2), -2.0)
+            if go.any():
+                rl, rh, rf, rs = shade_ray(scene, fc, tris, tri_inst, tri_prim, Pc[go], R[go], tri_of[c[go]], False, preset[go])
+                VoH, NoH, NoV = _sat(_dot(Vc[go], Hh[go])), _sat(_dot(Nc[go], Hh[go])), _sat(_dot(Nc[go], Vc[go]))
+                wgt = vndf_weight(f0[go], al[go], NoL[go], VoH) if vndf else ndf_weight(f0[go], al[go], NoV, NoL[go], VoH, NoH)
+                l[go], h[go] = _scale(rl, rh, wgt)
+                fl[go] |= rf; sig[go] = rs
+            res.append((l, h, fl, sig, go, NoL))
+        refl_lo[c], refl_hi[c] = np.minimum.reduce([r[0] for r in res]), np.maximum.reduce([r[1] for r in res])
+        moved = (res[0][3] != res[1][3]).any(axis=1) | (res[0][3] != res[2][3]).any(axis=1)
+        flags[c] |= res[0][2] | res[1][2] | res[2][2] | np.where(moved, FLAG_CANCEL, 0)
+        refl_traced[c] = res[0][4]
+        refl_nol[c] = res[0][5]
+        # ---- the diffuse ray
+        dk = c[metal[c] < 1.0]
+        if dk.size:
+            ct = 1.0 - 2.0 * xi[dk]
+            res = []
+            for slack in (0.0, -CANCEL_SLACK, CANCEL_SLACK):
+                st = np.sqrt(np.maximum(1.0 - ct * ct + slack, 0.0))
+                dd = _unit(N[dk] + np.stack([np.cos(phi[dk]) * st, np.sin(phi[dk]) * st, ct], axis=1))
+                l, h, fl, sig = shade_ray(scene, fc, tris, tri_inst, tri_prim, P[dk], dd, tri_of[dk], True, colour[dk] * metal[dk][:, None])
+                res.append(_scale(l, h, colour[dk] * 0.96) + (fl, sig))
+            diff_traced[dk] = True
+            diff_lo[dk], diff_hi[dk] = np.minimum.reduce([r[0] for r in res]), np.maximum.reduce([r[1] for r in res])
+            moved = (res[0][3] != res[1][3]).any(axis=1) | (res[0][3] != res[2][3]).any(axis=1)
+            flags[dk] |= res[0][2] | res[1][2] | res[2][2] | np.where(moved, FLAG_CANCEL, 0)
+    diff_written = sky | diff_traced
+    if prev is not None:      # what this frame does not write stays
+        keep = ~diff_written
+        diff_lo[keep], diff_hi[keep] = prev["diff_lo"].reshape(n, 3)[keep], prev["diff_hi"].reshape(n, 3)[keep]
+        rmv = out["rm_value"].reshape(n, 2)
+        rmv[sky] = prev["rm_value"].reshape(n, 2)[sky]
+    out["surface"] = {"P": P, "N": N, "V": V, "rough": rough, "metal": metal, "colour": colour, "tri_of": tri_of, "covered": covered, "flags": np.where(covered, a["flags"], 0)}
+    out.update(flags=flags.reshape(H, W), refl_lo=refl_lo.reshape(H, W, 3), refl_hi=refl_hi.reshape(H, W, 3), diff_lo=diff_lo.reshape(H, W, 3),
+               diff_hi=diff_hi.reshape(H, W, 3), refl_traced=refl_traced.reshape(H, W), diff_traced=diff_traced.reshape(H, W),
+               diff_written=diff_written.reshape(H, W), refl_nol=refl_nol.reshape(H, W), rays=int(refl_traced.sum() + diff_traced.sum()))
+    return out
+
+
+# ---- the sun and the local lights on the primary surface (include/rtggx.h: rtggx_set_sun at angle 0, rtggx_set_lights at radius 0) --------
+MIN_LIGHT_ROUGHNESS = 1.0 / 32.0
+D_SLACK = 4.0 * 2.0 ** -24      # the GGX denominator NoH^2 (a^2 - 1) + 1 is a difference of numbers near 1: fp32 leaves it an absolute error of this order
+
+
+def _direct_term(s, k, L, NoL):
+    """Specular term per unit irradiance as an interval, and the diffuse one, at the pixels k with the unit direction L to the light:
+    F D Vis NoL with r' = max(r, 1/32) and H = unit(V + L); colour 0.96 NoL / pi where m < 1 (0 elsewhere).  D is monotone in its
+    denominator, which is taken D_SLACK lower (not below its least value a^2) and higher: a true interval of that rounding."""
+    N, V = s["N"][k], s["V"][k]
+    al = np.maximum(s["rough"][k], MIN_LIGHT_ROUGHNESS) ** 2
+    Hh = _unit(V + L)
+    NoH, VoH, NoV = _sat(_dot(N, Hh)), _sat(_dot(V, Hh)), _sat(_dot(N, V))
+    a2 = al * al
+    d = NoH * NoH * (a2 - 1.0) + 1.0
+    base = fresnel(f0_of(s["colour"][k], s["metal"][k]), VoH) * (vis_smith(al, NoV, NoL) * NoL)[:, None]
+    hi = base * (a2 / (np.pi * np.maximum(d - D_SLACK, a2) ** 2))[:, None]
+    lo = base * (a2 / (np.pi * (d + D_SLACK) ** 2))[:, None]
+    diff = s["colour"][k] * 0.96 * (NoL / np.pi)[:, None] * (s["metal"][k] < 1.0)[:, None]
+    return lo, hi, diff
+
+
+def _shadowed(tris, s, k, L, tmax):
+    """Any triangle but the pixel's own on the ray from P along L over (RAY_TMIN, tmax) -> (occluded, flags)."""
+    h = closest_hit(tris, s["P"][k], L, s["tri_of"][k], tmax=tmax)
+    return h["valid"], h["flags"] & (FLAG_EDGE | FLAG_TMIN)
+
+
+def sun_pass(scene, fc_bytes, m, direction, irradiance):
+    """The sun's terms of one frame m (frame()'s result).  direction: L as the host hands it on (unit, fp32); irradiance E.
+    -> dict over [H W]: spec_lo / spec_hi / diff [.. 3] (zero where there is no term), term (a term is added), flags, rays."""
+    fc = read_constants(fc_bytes)
+    s = m["surface"]
+    n = len(s["P"])
+    L, E = np.asarray(direction, np.float64), np.asarray(irradiance, np.float64)
+    tris, _, _ = _world_triangles(scene, fc)
+    lo, hi, df = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 3))
+    flags, term = np.zeros(n, np.int64), np.zeros(n, bool)
+    NoL = _dot(s["N"], L)
+    flags |= np.where(s["covered"] & (np.abs(NoL) <= NOL_EPS), FLAG_NOL, 0) | np.where(s["covered"] & (NoL > 0) & (NoL < GRAZING_NOL), FLAG_GRAZING, 0)
+    k = np.nonzero(s["covered"] & (NoL > 0.0))[0]
+    rays = k.size
+    if k.size:
+        occ, fl = _shadowed(tris, s, k, np.broadcast_to(L, (k.size, 3)), RAY_TMAX)
+        flags[k] |= fl
+        k = k[~occ]
+        l, h, d = _direct_term(s, k, np.broadcast_to(L, (k.size, 3)), NoL[k])
+        lo[k], hi[k], df[k], term[k] = l * E, h * E, d * E, True
+    flags |= s["flags"]
+    shape = m["covered"].shape
+    return {"spec_lo": lo.reshape(shape + (3,)), "spec_hi": hi.reshape(shape + (3,)), "diff": df.reshape(shape + (3,)), "term": term.reshape(shape),
+            "diffuse": (term & (s["metal"] < 1.0)).reshape(shape), "flags": flags.reshape(shape), "rays": int(rays)}
+
+
+def light_window(d2, R):
+    """sat(1 - (d / R)^4)^2."""
+    return _sat(1.0 - (d2 / (R * R)) ** 2) ** 2
+
+
+def light_spot(c, cos_outer, cos_inner):
+    """The cone's factor s^2, s = sat((c - cos_outer) / (cos_inner - cos_outer))."""
+    return _sat((c - cos_outer) / (cos_inner - cos_outer)) ** 2
+
+
+def light_attenuation(d2, R, radius=0.0, spot=1.0):
+    """window x spot / max(d^2, m2) with the floor m2 = max(radius^2, 1e-4)."""
+    return light_window(d2, R) * spot / np.maximum(d2, max(radius * radius, 1e-4))
+
+
+def lights_pass(scene, fc_bytes, m, lights):
+    """The local lights' sums of one frame, radius 0: lights as dicts (position, intensity, range, axis, cos_outer, cos_inner; the axis a
+    unit vector), summed in their order.  -> like sun_pass."""
+    fc = read_constants(fc_bytes)
+    s = m["surface"]
+    n = len(s["P"])
+    tris, _, _ = _world_triangles(scene, fc)
+    lo, hi, df = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 3))
+    flags, term, rays = np.zeros(n, np.int64), np.zeros(n, bool), 0
+    for lt in lights:
+        I = np.asarray(lt["intensity"], np.float64)
+        if not (I > 0).any():
+            continue
+        assert lt.get("radius", 0.0) == 0.0
+        R = float(np.float32(lt["range"]))
+        D = np.asarray(lt["position"], np.float32).astype(np.float64) - s["P"]
+        d2 = _dot(D, D)
+        cov = s["covered"]
+        flags |= np.where(cov & ((np.abs(d2 - R * R) <= 1e-5 * R * R) | (np.abs(d2 - 1e-6) <= 1e-11)), FLAG_RANGE, 0)
+        live = cov & (d2 >= 1e-6) & (d2 < R * R)
+        L = _unit(D)
+        NoL = _dot(s["N"], L)
+        flags |= np.where(live & (np.abs(NoL) <= NOL_EPS), FLAG_NOL, 0) | np.where(live & (NoL > 0) & (NoL < GRAZING_NOL), FLAG_GRAZING, 0)
+        live &= NoL > 0.0
+        spot = np.ones(n)
+        co = float(np.float32(lt.get("cos_outer", -1.0)))
+        if co > -1.0:
+            ci = float(np.float32(lt["cos_inner"]))
+            c = -_dot(L, np.asarray(lt["axis"], np.float32).astype(np.float64))
+            flags |= np.where(live & (np.abs(c - co) <= 1e-5), FLAG_CONE, 0)
+            live &= c > co
+            spot = light_spot(c, co, ci)
+        k = np.nonzero(live)[0]
+        rays += k.size
+        if not k.size:
+            continue
+        occ, fl = _shadowed(tris, s, k, L[k], np.sqrt(d2[k]))
+        flags[k] |= fl
+        k = k[~occ]
+        att = light_attenuation(d2[k], R, 0.0, spot[k])
+        l, h, d = _direct_term(s, k, L[k], NoL[k])
+        lo[k] += l * (I * att[:, None]); hi[k] += h * (I * att[:, None]); df[k] += d * (I * att[:, None]); term[k] = True
+    flags |= s["flags"]
+    shape = m["covered"].shape
+    return {"spec_lo": lo.reshape(shape + (3,)), "spec_hi": hi.reshape(shape + (3,)), "diff": df.reshape(shape + (3,)), "term": term.reshape(shape),
+            "diffuse": (term & (s["metal"] < 1.0)).reshape(shape), "flags": flags.reshape(shape), "rays": int(rays)}
+
+
+def unpack_r11g11b10(words):
+    c = r11g11b10_split(words)
+    return np.stack([ufloat_values(6)[np.minimum(c[..., 0], 1983)], ufloat_values(6)[np.minimum(c[..., 1], 1983)], ufloat_values(5)[np.minimum(c[..., 2], 991)]], axis=-1)
+
+
+# ---- distances and the code rule ------------------------------------------------------------------------------------------------------
+def ulp_distance(got, lo, hi):
+    """Distance of fp32 values got [.. 3] from the interval [lo, hi], in fp32 ulps of the pixel's largest channel -> [..]."""
+    got = np.asarray(got, np.float64)
+    d = np.maximum(np.maximum(lo - got, got - hi), 0.0)
+    scale = np.maximum(np.abs(lo), np.abs(hi)).max(axis=-1)
+    return d.max(axis=-1) / ulp32(scale)
+
+
+def quantiles(e):
+    e = np.asarray(e, np.float64).reshape(-1)
+    if e.size == 0:
+        return {"n": 0, "max": 0.0, "q99": 0.0, "median": 0.0}
+    return {"n": int(e.size), "max": float(e.max()), "q99": float(np.quantile(e, 0.99)), "median": float(np.median(e))}
+
+
+def code_rule(code_of, stored, lo, hi, delta, one_code=True):
+    """A stored code may differ from the code of the model's value by at most one, and only where that value lies within delta of a
+    rounding boundary: stored in [code(lo - delta), code(hi + delta)] and within one of [code(lo), code(hi)].  code_of is monotone.
+    one_code: where the limit of one code holds (binary16 near zero is finer than delta: there "within delta" is all that can be asked).
+    -> (violations, uses of the allowance), boolean arrays."""
+    stored = np.asarray(stored).astype(np.int64)
+    c_lo, c_hi = code_of(lo), code_of(hi)
+    ok = (stored >= np.minimum(code_of(lo - delta), c_lo)) & (stored <= np.maximum(code_of(hi + delta), c_hi))
+    ok &= ((stored >= c_lo - 1) & (stored <= c_hi + 1)) | ~np.broadcast_to(one_code, ok.shape)
+    return ~ok, ok & ((stored < c_lo) | (stored > c_hi))
+
+
+def f16_spacing(x):
+    """The distance between neighbouring binary16 values at |x| (2^-24 below the normal range)."""
+    x = np.maximum(np.abs(np.asarray(x, np.float64)), 2.0 ** -14)
+    return 2.0 ** (np.floor(np.log2(x)) - 10.0)

@@ -10,7 +10,7 @@ namespace orc {
 
 // Returns the rays traced.  sumRefl / sumDiff (may be null): the pixel's fp32 results before packing, 3 floats per pixel (tests of the
 // averaging itself; there N may be any count, and 1 / N is then rounded once).
-static inline uint32_t raygen_pixel_spp(Ctx& c, uint32_t px, uint32_t py, uint32_t D, uint32_t N, float* sumRefl, float* sumDiff) {
+static inline uint32_t raygen_pixel_spp(Ctx& c, uint32_t px, uint32_t py, uint32_t D, uint32_t N, float* sumRefl, float* sumDiff, float* primary = nullptr) {
   const uint32_t W = c.W, H = c.H; const size_t pix = (size_t)py * W + px;
   const FrameConstants& fc = c.fc;
   uint32_t rays = 0;
@@ -49,6 +49,10 @@ static inline uint32_t raygen_pixel_spp(Ctx& c, uint32_t px, uint32_t py, uint32
   c.normal[pix] = pack_r10g10b10a2(s.N.x * 0.5f + 0.5f, s.N.y * 0.5f + 0.5f, s.N.z * 0.5f + 0.5f, s.hit ? 1.0f : 0.0f);
   if (s.hit) c.roughMetal[pix] = pack_r8g8(s.rghMtl.x, s.rghMtl.y);
   c.velocity[pix] = pack_r16g16f(s.velocity.x, s.velocity.y);
+  if (primary) {      // the primary surface in front of the G-buffer's packs: N * 0.5 + 0.5, the velocity, the roughness
+    float* g = primary + 6 * pix;
+    g[0] = s.N.x * 0.5f + 0.5f; g[1] = s.N.y * 0.5f + 0.5f; g[2] = s.N.z * 0.5f + 0.5f; g[3] = s.velocity.x; g[4] = s.velocity.y; g[5] = s.rghMtl.x;
+  }
 
   if (!s.hit) {      // background: the environment along -V into both images, no ray and no averaging
     const float3 e = environment(c, -s.V, 0.0f);
@@ -121,6 +125,14 @@ extern "C" uint64_t orc_ray_trace_spp_f32(void* h, uint32_t depth, uint32_t samp
   Ctx* c = (Ctx*)h;
   std::atomic<uint64_t> rays{0};
   parallel_rows(c->threads, c->H, [&](uint32_t y) { uint64_t r = 0; for (uint32_t x = 0; x < c->W; ++x) r += raygen_pixel_spp(*c, x, y, depth, samples, sumRefl, sumDiff); rays += r; });
+  c->rayCount = rays.load();
+  return c->rayCount;
+}
+// ... and the primary surface's values in front of the G-buffer's packs (tests/test_shading_ref_host.py measures the model's distance from them)
+extern "C" uint64_t orc_ray_trace_spp_primary_f32(void* h, uint32_t depth, uint32_t samples, float* sumRefl, float* sumDiff, float* primary) {
+  Ctx* c = (Ctx*)h;
+  std::atomic<uint64_t> rays{0};
+  parallel_rows(c->threads, c->H, [&](uint32_t y) { uint64_t r = 0; for (uint32_t x = 0; x < c->W; ++x) r += raygen_pixel_spp(*c, x, y, depth, samples, sumRefl, sumDiff, primary); rays += r; });
   c->rayCount = rays.load();
   return c->rayCount;
 }
