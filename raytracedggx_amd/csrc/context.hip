@@ -434,13 +434,7 @@ int rtggx_set_sun(rtggx_context* c, const float direction[3], const float irradi
   for (int k = 0; k < 3; ++k) if (!std::isfinite(irradiance[k]) || irradiance[k] < 0.0f) { setError("rtggx_set_sun: irradiance component %d is %g: finite and not negative", k, (double)irradiance[k]); return -1; }
   const bool on = irradiance[0] > 0.0f || irradiance[1] > 0.0f || irradiance[2] > 0.0f;
   if (on && c->rayRate != 1u) { setError("rtggx_set_sun: on a context tracing one pixel in %u (rtggx_set_ray_rate): three quarters of such a frame are interpolations", c->rayRate); return -1; }
-  if (on && !c->sunRays) {
-    DevBuf<void> rays, hits; DevBuf<uint32_t> count;
-    RT_HIP(alloc(rays, (size_t)c->numBinsMax * RT_BIN_MIN * sizeof(RayRec)));
-    RT_HIP(alloc(hits, (size_t)c->numBinsMax * RT_BIN_MIN * sizeof(HitKey)));
-    RT_HIP(allocFilled(count, c->numBinsMax));
-    c->sunRays = std::move(rays); c->sunHits = std::move(hits); c->sunCount = std::move(count);
-  }
+  if (on) { bool filled = false; const int r = c->sunQueue.ensure(c->numBinsMax, RT_BIN_MIN, false, filled); if (r) return r; }      // (the call does not synchronise: see above)
   rtggx_context::Sun sun;
   sun.on = on;
   sun.L[0] = (float)(x / len); sun.L[1] = (float)(y / len); sun.L[2] = (float)(z / len);
@@ -470,7 +464,7 @@ int rtggx_set_sun_angle(rtggx_context* c, float degrees) {
   return 0;
 }
 // The sun at the surfaces the paths hit (include/rtggx.h).  Only the value is kept: it is stored whether or not a sun is set, allocates nothing
-// here (the first frame that has both on does: raytrace.hip allocSunHits) and takes effect with the next rtggx_render_visibility.  No
+// here (the first frame that has both on does: lighting.hip beginSunHits) and takes effect with the next rtggx_render_visibility.  No
 // synchronisation, no end of a still-sky run, no reset of an accumulation, as for the sun itself.
 int rtggx_set_sun_reflections(rtggx_context* c, int enable) {
   RT_CHECK_CTX(c);
@@ -480,7 +474,7 @@ int rtggx_set_sun_reflections(rtggx_context* c, int enable) {
 }
 // Local lights (include/rtggx.h).  The list is checked as a whole and copied; a cone's axis is normalised in double and rounded once, the sun's
 // rule.  (NULL, 0) turns the lights off.  A refused call leaves what the context had.  Nothing is allocated here (the first frame with lights
-// does: raytrace.hip allocLights).  No synchronisation, no end of a still-sky run, no reset of an accumulation, as for the sun.
+// does: lighting.hip launchLights).  No synchronisation, no end of a still-sky run, no reset of an accumulation, as for the sun.
 int rtggx_set_lights(rtggx_context* c, const RtggxLight* lights, uint32_t count) {
   RT_CHECK_CTX(c);
   if (count > RTGGX_MAX_LIGHTS) { setError("rtggx_set_lights: %u lights: at most %u", count, RTGGX_MAX_LIGHTS); return -1; }
@@ -507,7 +501,7 @@ int rtggx_set_lights(rtggx_context* c, const RtggxLight* lights, uint32_t count)
   return 0;
 }
 // The lights at the surfaces the paths hit (include/rtggx.h).  Only the value is kept: it is stored whether or not lights are set, allocates
-// nothing here (the first frame that has both does: raytrace.hip allocSunHits) and takes effect with the next rtggx_render_visibility.  No
+// nothing here (the first frame that has both does: lighting.hip beginSunHits) and takes effect with the next rtggx_render_visibility.  No
 // synchronisation, no end of a still-sky run, no reset of an accumulation, as for the lights themselves.
 int rtggx_set_light_reflections(rtggx_context* c, int enable) {
   RT_CHECK_CTX(c);

@@ -76,8 +76,7 @@ static int growBins(rtggx_context* c) {
   c->binSlots = RT_BIN;
   for (uint32_t i = 0; i < RT_SETS; ++i) { const int r = allocSet(c, i); if (r) return r; }      // (the bins, at the new size)
   c->testRayRange.reset();
-  c->sunHitRays.reset(); c->sunHitHits.reset(); c->sunHitSlots = 0u;      // (rtggx_set_sun_reflections: its bins follow the frame's, at the next lit frame)
-  c->lightHitRays.reset(); c->lightHitHits.reset(); c->lightHitRange.reset(); c->lightHitSlots = 0u;      // (rtggx_set_light_reflections: likewise)
+  c->sunHitQueue.release(); c->lightHitQueue.release();      // (rtggx_set_sun_reflections, rtggx_set_light_reflections: their bins follow the frame's, at the next lit frame)
   return 0;
 }
 int rtggx_update_frame(rtggx_context* c, const RtggxFrameConstants* k) {

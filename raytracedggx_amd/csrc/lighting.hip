@@ -1,0 +1,628 @@
+// Direct lighting: the sun (rtggx_set_sun, rtggx_set_sun_angle), the local lights (rtggx_set_lights) and both at the surfaces the paths hit
+// (rtggx_set_sun_reflections, rtggx_set_light_reflections).  include/rtggx.h has the per-pixel rules, DESIGN.md section 9 the structure.
+//
+// Every pass is the same three launches around a queue of its own (rt::ShadowQueue, rt_queue.h): a generating kernel derives a surface --
+// the primary one from the visibility word, or the hit of a traced ray -- and, where a light reaches it, compacts ONE shadow ray into the
+// wave's bin, with the finished term in the record; the any-hit traversal (trace.hip) leaves an unoccluded ray's key a miss; an adding
+// kernel, one lane per slot, adds the unoccluded terms.  No two lanes meet at a pixel and nothing is atomic: the order of a sum is the order
+// of the launches on the stream.
+//
+//   the step, written once below           who runs it
+//   tileIsEmpty                            every kernel here
+//   atPrimarySurface                       sunGenKernel, lightGenKernel
+//   atTracedHit, hitLobeTerm               sunHitGenKernel, lightHitGenKernel
+//   deltaLightSpecular                     all four
+//   shadowSample + the slot numbering      the SOFT variants of all four
+//   evalLight                              lightGenKernel, lightHitGenKernel
+//   compactShadowRay                       all four
+//
+// SOFT and CONE are compile-time: a directional sun, and a context with point lights of radius 0, pay for neither the hash nor the cone.
+#include <type_traits>
+#include "rt_queue.h"
+#include "rt_traverse.h"
+#include "rt_surface.h"
+
+namespace rt {
+
+// The guard of every kernel here: one word per 16x16 tile (rtggx_context::tileWords), 0 = nothing drawn there; a scalar load and its own
+// wait, so that an empty workgroup leaves before it has touched a vector register.
+RT_DEV bool tileIsEmpty(const uint32_t* tileWords, uint32_t tile) {
+  uint32_t word;
+  asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(word) : "s"(tileWords), "s"(tile * 4u) : "memory");
+  return word == 0u;
+}
+
+struct Surface { f3 P, N, V, color; f2 rm; };      // rm: (roughness, metallic)
+
+// Step 1 of rtggx_set_sun, step 0 of rtggx_set_lights: the primary surface from the visibility word -- getPrimarySurface :277-333, the covered
+// branch, ray generation's arithmetic.  Where a surface covers the pixel, lit(surface) runs -- inside the branch that found it, so that a
+// kernel's control flow is the one of the steps written out.  pixel: the full-frame index y W + x.
+struct PrimarySurface : Surface { uint32_t pixel, inst, prim; };
+template <class Lit>
+RT_DEV void atPrimarySurface(const FrameParams& fp, const unsigned long long* visDepth, const float4* fat0, const float4* fat1, uint32_t px, uint32_t py, Lit lit) {
+  const uint32_t W = fp.W, H = fp.H;
+  const size_t pix = (size_t)py * W + px;
+  uint32_t visibility = (uint32_t)visDepth[pix];
+  if (visibility == 0) return;
+  --visibility;
+  const uint32_t inst = visibility >> 24;
+  uint32_t prim = visibility & 0xFFFFFFu;
+  asm volatile("" : "+v"(prim));      // see shadeKernel
+  f2 screenPos; screenPos.x = ((float)px + 0.5f) / (float)W * 2.0f - 1.0f; screenPos.y = ((float)py + 0.5f) / (float)H * 2.0f - 1.0f;
+  screenPos.y = -screenPos.y;
+  const f3 eye = mk3(fp.rg.EyePt[0], fp.rg.EyePt[1], fp.rg.EyePt[2]);
+  const Tri3 v = getVertices(inst ? fat1 : fat0, prim);
+  const M4 wvp = cbLoad4x4(fp.g.WorldViewProjs[inst]);
+  f4 p[3];
+  for (int k = 0; k < 3; ++k) p[k] = mulPoint(v.pos[k], wvp);
+  screenPos.x -= fp.rg.ProjBias[0]; screenPos.y -= fp.rg.ProjBias[1];
+  const f2 bary = calcBarycentrics(p, screenPos);
+  const Attrib a = interpAttrib(v, bary.x, bary.y);
+  PrimarySurface s;
+  s.color = mk3(fp.mat.BaseColors[inst][0], fp.mat.BaseColors[inst][1], fp.mat.BaseColors[inst][2]);
+  s.rm = getRoughMetal(fp.mat, inst, a.UV);
+  const f4 P4 = mulPoint(a.Pos, cbLoad4x3(fp.g.Worlds[inst]));
+  s.P = mk3(P4.x, P4.y, P4.z);
+  s.N = normalize3(mulDir(a.Nrm, cbLoad3x3(inst ? fp.g.WorldIT1 : fp.g.WorldITs0)));
+  s.V = normalize3(eye - s.P);
+  s.pixel = (uint32_t)pix; s.inst = inst; s.prim = prim;
+  lit(s);
+}
+
+// A traced ray of the frame's bins that TOUCHES A SURFACE (rtggx_set_sun_reflections): it hits, and it is not a reflection-group ray whose
+// preset is <= 0 in every component (shadeKernel: :573 returns the preset).  The hit as shadeKernel derives it: triangle from the hit id,
+// barycentrics from the repeated watertight test, P = o + t dir (hitWorldPosition :338-341), V = -dir.  image: the image the path writes
+// (1: RayTracingOut1); q2.xyz: the throughput T the record carries.  What only a lit hit needs is computed where it is asked for.
+// Where the ray touches, lit(hit) runs, inside the branch that found it (atPrimarySurface).
+struct TracedHit {
+  float4 q0, q1, q2;      // the record's three words
+  uint32_t pixel, hitId, image; bool diffuseGroup;
+  float t; f3 N; f2 UV;
+  RT_DEV f3 P() const { return mk3(q0.x + t * q0.w, q0.y + t * q1.x, q0.z + t * q1.y); }
+  RT_DEV f3 V() const { return mk3(-q0.w, -q1.x, -q1.y); }
+  RT_DEV f2 rm(const FrameParams& fp) const { return getRoughMetal(fp.mat, hitId >> 24, UV); }
+  RT_DEV f3 color(const FrameParams& fp) const { return mk3(fp.mat.BaseColors[hitId >> 24][0], fp.mat.BaseColors[hitId >> 24][1], fp.mat.BaseColors[hitId >> 24][2]); }
+};
+template <class Lit>
+RT_DEV void atTracedHit(const FrameParams& fp, const RayRec* rays, const HitKey* hits, const float4* fat0, const float4* fat1, size_t slot, Lit lit) {
+  TracedHit h;
+  const float4* rp = reinterpret_cast<const float4*>(rays + slot);
+  h.q0 = rp[0]; h.q1 = rp[1]; h.q2 = rp[2];
+  const uint32_t skip = __float_as_uint(h.q1.w), flags = __float_as_uint(h.q2.w);
+  h.pixel = __float_as_uint(h.q1.z); h.hitId = hitKeyId(hits[slot]);
+  h.diffuseGroup = (flags & 1u) != 0u;
+  h.image = (flags ^ (flags >> 1)) & 1u;
+  const uint32_t srcInst = skip >> 24;
+  const float m = fp.mat.RoughMetals[srcInst][1];
+  const bool presetReturn = !h.diffuseGroup && fp.mat.BaseColors[srcInst][0] * m <= 0.0f && fp.mat.BaseColors[srcInst][1] * m <= 0.0f && fp.mat.BaseColors[srcInst][2] * m <= 0.0f;
+  if (h.hitId == 0xFFFFFFFFu || presetReturn) return;
+  const uint32_t hInst = h.hitId >> 24;
+  uint32_t hPrim = h.hitId & 0xFFFFFFu;
+  asm volatile("" : "+v"(hPrim));      // see shadeKernel
+  const Tri3 v = getVertices(hInst ? fat1 : fat0, hPrim);
+  float hb1 = 0.0f, hb2 = 0.0f;
+  woopTestVerts(toObject(h.q0.x, h.q0.y, h.q0.z, h.q0.w, h.q1.x, h.q1.y, hInst ? fp.invWorld[1] : fp.invWorld[0]), v.pos[0], v.pos[1], v.pos[2], h.t, hb1, hb2);
+  const Attrib a = interpAttrib(v, hb1, hb2);
+  h.N = normalize3(mulDir(a.Nrm, cbLoad3x3(hInst ? fp.g.WorldIT1 : fp.g.WorldITs0)));
+  h.UV = a.UV;
+  lit(h);
+}
+
+// The specular term under a delta light (step 4 of rtggx_set_sun, step 8 of rtggx_set_lights, the m > 0.5 lobe of the two hit rules):
+// F D Vis NoL with the roughness floored at 1/32 -- a mirror under a delta light has no finite answer.  Returns F k, k = (D vis) NoL; the
+// caller multiplies by the light's E.
+RT_DEV f3 deltaLightSpecular(f3 N, f3 V, f3 L, float NoL, f3 color, f2 rm) {
+  const float r = fmaxf(rm.x, 1.0f / 32.0f);
+  const f3 Hh = normalize3(V + L);
+  const float NoH = saturatef(dot3(N, Hh)), VoH = saturatef(dot3(V, Hh)), NoV = saturatef(dot3(N, V));
+  const float al = r * r, a2 = al * al;
+  const float d = (NoH * a2 - NoH) * NoH + 1.0f;
+  const float D = a2 / ((RT_PI * d) * d);
+  const f3 f0 = mk3(lerpf(0.04f, color.x, rm.y), lerpf(0.04f, color.y, rm.y), lerpf(0.04f, color.z, rm.y));
+  const f3 F = fSchlick(f0, VoH);
+  const float vis = visSmith(r, NoV, NoL);
+  const float k = (D * vis) * NoL;
+  return mk3(F.x * k, F.y * k, F.z * k);
+}
+// The diffuse colour of a hit: color (1 - m) for a diffuse-group ray (:607), color for a reflection-group ray
+RT_DEV f3 hitDiffuseColor(f3 color, f2 rm, bool diffuseGroup) { return diffuseGroup ? color * (1.0f - rm.y) : color; }
+// The term of the lobe the path uses at a hit (step 3 of rtggx_set_sun_reflections, step 4 of rtggx_set_light_reflections) at the centre
+// direction L, under the irradiance E att (the sun: att = 1, which multiplies away).  m > 0.5: (F k) (E att); else (color' g) E with
+// g = (NoL / pi) att -- no x (1 - 0.04) at depth >= 1 (:532).
+RT_DEV f3 hitLobeTerm(const FrameParams& fp, const TracedHit& h, f3 L, float NoL, f3 E, float att) {
+  const f2 rm = h.rm(fp);
+  const f3 color = h.color(fp);
+  if (rm.y > 0.5f) {
+    const f3 Fk = deltaLightSpecular(h.N, h.V(), L, NoL, color, rm);
+    return mk3(Fk.x * (E.x * att), Fk.y * (E.y * att), Fk.z * (E.z * att));
+  }
+  const f3 diffuse = hitDiffuseColor(color, rm, h.diffuseGroup);
+  const float g = (NoL / RT_PI) * att;
+  return mk3((diffuse.x * g) * E.x, (diffuse.y * g) * E.y, (diffuse.z * g) * E.z);
+}
+
+// The slots of the soft shadows' hash, all of them (include/rtggx.h): 0 the sun at the primary surface; 1 + 2 d + img the sun at a level-d
+// hit of a path that writes image img; 16 + i light i at the primary surface; 32 + 16 d + 8 img + i light i at a level-d hit.  The host
+// hands a kernel the slot at img = 0, the kernel adds the image's stride.
+#define RT_SLOT_SUN 0u
+#define RT_SLOT_SUN_HIT(d) (1u + 2u * (d))
+#define RT_SLOT_SUN_HIT_IMAGE 1u
+#define RT_SLOT_LIGHT(i) (16u + (i))
+#define RT_SLOT_LIGHT_HIT(d, i) (32u + 16u * (d) + (i))
+#define RT_SLOT_LIGHT_HIT_IMAGE 8u
+// What a soft shadow draws its target from (step 2 of rtggx_set_sun_angle, step 5 of rtggx_set_lights): w = rng(h + j 0x9E3779B9) with
+// h = rng(rng(pixel) + frameIndex), getSampleParam's word before its mask; u = the low 16 bits in [0, 1), s = the top 8, an entry of the
+// 256-entry cos/sin table whatever the sample set is.  frameIndex: of the sample the pass belongs to.
+struct ShadowSample { float u; uint32_t s; };
+RT_DEV ShadowSample shadowSample(uint32_t pixel, uint32_t frameIndex, uint32_t j) {
+  uint32_t h = rng(pixel); h += frameIndex; h = rng(h);
+  const uint32_t w = rng(h + j * 0x9E3779B9u);
+  ShadowSample o; o.u = (float)(w & 0xffffu) / 65536.0f; o.s = w >> 24;
+  return o;
+}
+
+// A shadow ray's record: from P along dir, skipping the triangle it starts on; weight and flags are what the pass's adding kernel reads
+RT_DEV RayRec shadowRay(f3 P, f3 dir, uint32_t pixel, uint32_t skip, f3 weight, uint32_t flags) {
+  RayRec r;
+  r.ox = P.x; r.oy = P.y; r.oz = P.z; r.dx = dir.x; r.dy = dir.y; r.dz = dir.z;
+  r.pixel = pixel; r.skip = skip;
+  r.wx = weight.x; r.wy = weight.y; r.wz = weight.z;
+  r.flags = flags;
+  return r;
+}
+// One shadow ray per wanting lane into the front of the wave's bin, in lane order behind the `written` records of the wave's earlier
+// rounds (a single-round kernel: 0, and RT_BIN_MIN slots): the record, the key the traversal starts from -- (tmax, miss) -- and, where
+// the queue has them (RANGE), the ray's interval (1e-5, tmax).  Returns how many the wave wrote.
+template <bool RANGE>
+RT_DEV uint32_t compactShadowRay(bool want, const RayRec& r, float tmax, RayRec* rays, HitKey* hits, float2* range, uint32_t bin, uint32_t binSlots, uint32_t written, uint32_t lane) {
+  const unsigned long long mask = __ballot(want);
+  if (want) {
+    const size_t k = (size_t)bin * binSlots + written + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+    rays[k] = r; hits[k] = hitKey(tmax, 0xFFFFFFFFu);
+    if constexpr (RANGE) range[k] = make_float2(RT_RAY_TMIN, tmax);
+  }
+  return (uint32_t)__popcll(mask);
+}
+
+// ---- the sun (rtggx_set_sun; DESIGN.md section 9 "Sun and shadow rays") ----------------------------------------------------------------------
+// Three kernels on the stream that has this frame's two traced images complete (frame.hip rtggx_ray_trace): sunGenKernel puts the specular
+// term in the record's weight and NoL in its flags word; sunAddKernel adds an unoccluded slot's terms to its pixel's packed words (a pixel
+// has at most one slot).
+#ifndef RT_SUN_CLOSEST
+#define RT_SUN_CLOSEST 0      // measurement: 1 traces the shadow queue with the closest-hit kernel (the same images; profiles/r14_d_sun_cost.txt)
+#endif
+// A sun with a size (rtggx_set_sun_angle): what the SOFT variants of the two generating kernels are given on top of their arguments -- the
+// disk's frame, k = 1 - cos(radius), the 256-entry cos/sin table, and (the hits) the frame index of the sample the pass belongs to with the
+// level's slot.  SOFT = false is the kernel without any of it, body and arguments.
+struct SunDiskArgs { float Tx, Ty, Tz, Bx, By, Bz, k; const float* cosSin; uint32_t frameIndex, slotBase; };
+// Steps 1-5 of rtggx_set_sun_angle: the direction toward a point of the disk, uniform in solid angle over the cap; not renormalised.
+RT_DEV f3 sunDiskDirection(const SunDiskArgs& K, f3 L, uint32_t pixel, uint32_t frameIndex, uint32_t j) {
+  const ShadowSample x = shadowSample(pixel, frameIndex, j);
+  const float cosPhi = K.cosSin[x.s], sinPhi = K.cosSin[256u + x.s];
+  const float e = x.u * K.k;
+  const float cosTheta = 1.0f - e, sinTheta = sqrtf(e * (2.0f - e));      // (not 1 - cos^2: it cancels at small angles)
+  const float ct = cosPhi * sinTheta, st = sinPhi * sinTheta;
+  return mk3((K.Tx * ct + K.Bx * st) + L.x * cosTheta, (K.Ty * ct + K.By * st) + L.y * cosTheta, (K.Tz * ct + K.Bz * st) + L.z * cosTheta);
+}
+struct SunGenArgs {
+  const unsigned long long* visDepth; const float4* fat0; const float4* fat1;
+  RayRec* rays; HitKey* hits; uint32_t* binCount;
+  const uint32_t* tileWords; uint32_t tilesX, rowBegin, rowEnd;
+  float Lx, Ly, Lz, Ex, Ey, Ez;
+};
+struct SunGenArgsSoft : SunGenArgs { SunDiskArgs disk; };      // slot RT_SLOT_SUN, the frame's own index (the constants')
+template <bool SOFT>
+__global__ void __launch_bounds__(256) sunGenKernel(const FrameParams* __restrict__ fpp, std::conditional_t<SOFT, SunGenArgsSoft, SunGenArgs> A) {
+  const FrameParams& fp = *fpp;
+  const uint32_t tile = blockIdx.x;
+  if (tileIsEmpty(A.tileWords, tile)) return;
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const uint32_t px = (tile % A.tilesX) * 16 + (wave & 1u) * 8 + (lane & 7u);
+  const uint32_t py = A.rowBegin + (tile / A.tilesX) * 16 + (wave >> 1) * 8 + (lane >> 3);
+  bool want = false;
+  RayRec rr;
+  if (px < fp.W && py < A.rowEnd) atPrimarySurface(fp, A.visDepth, A.fat0, A.fat1, px, py, [&](const PrimarySurface& s) {
+    const f3 L = mk3(A.Lx, A.Ly, A.Lz);
+    const float NoL = dot3(s.N, L);
+    f3 Ls = L;      // SOFT: toward the point of the disk the pixel draws this frame; below the horizon there is no ray and no term
+    bool facing = NoL > 0.0f;
+    if constexpr (SOFT) { if (facing) { Ls = sunDiskDirection(A.disk, L, s.pixel, fp.g.FrameIndex, RT_SLOT_SUN); facing = dot3(s.N, Ls) > 0.0f; } }
+    if (facing) {
+      const f3 Fk = deltaLightSpecular(s.N, s.V, L, NoL, s.color, s.rm);
+      want = true;
+      rr = shadowRay(s.P, Ls, s.pixel, (s.inst << 24) | s.prim, mk3(Fk.x * A.Ex, Fk.y * A.Ey, Fk.z * A.Ez), __float_as_uint(NoL));
+    }
+  });
+  const uint32_t bin = blockIdx.x * 4u + wave;
+  const uint32_t n = compactShadowRay<false>(want, rr, RT_RAY_TMAX, A.rays, A.hits, nullptr, bin, RT_BIN_MIN, 0u, lane);
+  if (lane == 0) A.binCount[bin] = n;
+}
+struct SunAddArgs {
+  const RayRec* rays; const HitKey* hits; const uint32_t* binCount; const uint32_t* tileWords;
+  uint32_t* reflOut; uint32_t* diffOut; float Ex, Ey, Ez;
+};
+__global__ void __launch_bounds__(256) sunAddKernel(const FrameParams* __restrict__ fpp, SunAddArgs A) {
+  const FrameParams& fp = *fpp;
+  if (tileIsEmpty(A.tileWords, blockIdx.x)) return;
+  const uint32_t bin = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (lane >= A.binCount[bin]) return;
+  const size_t k = (size_t)bin * RT_BIN_MIN + lane;
+  if (hitKeyId(A.hits[k]) != 0xFFFFFFFFu) return;      // occluded: both words stay
+  const RayRec rr = A.rays[k];
+  const uint32_t inst = rr.skip >> 24;
+  const f3 spec = mk3(rr.wx, rr.wy, rr.wz);
+  A.reflOut[rr.pixel] = packR11G11B10F(unpackR11G11B10F(A.reflOut[rr.pixel]) + spec);
+  if (fp.mat.RoughMetals[inst][1] < 1.0f) {      // rghMtl.y < 1 is the instance's constant (launchShade); elsewhere RayTracingOut1 is a carry-over and stays
+    const float w = __uint_as_float(rr.flags) / RT_PI;
+    const f3 diff = mk3(((fp.mat.BaseColors[inst][0] * (1.0f - 0.04f)) * w) * A.Ex, ((fp.mat.BaseColors[inst][1] * (1.0f - 0.04f)) * w) * A.Ey,
+                        ((fp.mat.BaseColors[inst][2] * (1.0f - 0.04f)) * w) * A.Ez);
+    A.diffOut[rr.pixel] = packR11G11B10F(unpackR11G11B10F(A.diffOut[rr.pixel]) + diff);
+  }
+}
+static SunDiskArgs sunDisk(const rtggx_context* c, uint32_t frameIndex, uint32_t slotBase) {
+  const rtggx_context::Sun& sun = c->sun;
+  return SunDiskArgs{sun.T[0], sun.T[1], sun.T[2], sun.B[0], sun.B[1], sun.B[2], c->sunAngle.k, c->cosSinTab, frameIndex, slotBase};
+}
+int launchSun(rtggx_context* c, const FrameParams& fp, hipStream_t s) {
+  uint32_t rb, re;
+  passRows(fp, ROWS_GBUFFER, rb, re);
+  if (re <= rb) return 0;
+  const uint32_t tilesX = (fp.W + 15) / 16, tilesY = (re - rb + 15) / 16, numTiles = tilesX * tilesY;
+  if (numTiles * 4u > c->numBinsMax || !c->sunQueue.rays) { setError("rtggx_ray_trace: the sun's queue does not hold %u bins", numTiles * 4u); return -1; }
+  const InputSet& set = c->cur();
+  const rtggx_context::Sun& sun = c->sun;
+  const TraceQueue q = c->sunQueue.view();      // bins of RT_BIN_MIN slots whatever the frame's have
+  SunGenArgs G;
+  G.visDepth = c->curVis().depth; G.fat0 = c->mesh[0].fat; G.fat1 = c->mesh[1].fat;
+  G.rays = (RayRec*)q.rays; G.hits = q.hits; G.binCount = c->sunQueue.count;
+  G.tileWords = c->tileWords(rb, re); G.tilesX = tilesX; G.rowBegin = rb; G.rowEnd = re;
+  G.Lx = sun.L[0]; G.Ly = sun.L[1]; G.Lz = sun.L[2]; G.Ex = sun.E[0]; G.Ey = sun.E[1]; G.Ez = sun.E[2];
+  const FrameParams* const dfp = c->dParams + c->slot;
+  if (c->sunAngle.degrees > 0.0f) {      // rtggx_set_sun_angle
+    SunGenArgsSoft GS;
+    static_cast<SunGenArgs&>(GS) = G;
+    GS.disk = sunDisk(c, 0u, 0u);
+    launch(sunGenKernel<true>, dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, GS);
+  } else launch(sunGenKernel<false>, dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, G);
+  // Spill part 2 is the main stream's (launchShade): the launches that use it are in this stream's order, and nothing beside the stream touches it
+  { const int r = launchTrace(c, fp, s, q, numTiles * 4u, true, tilesX, tilesY, c->traceGrid[3], -1, nullptr, nullptr, 2, !RT_SUN_CLOSEST); if (r) return r; }
+  SunAddArgs S;
+  S.rays = q.rays; S.hits = q.hits; S.binCount = q.binCount; S.tileWords = G.tileWords;
+  S.reflOut = set.rtRefl; S.diffOut = set.rtDiff; S.Ex = G.Ex; S.Ey = G.Ey; S.Ez = G.Ez;
+  launch(sunAddKernel, dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, S);
+  RT_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---- local lights (rtggx_set_lights; DESIGN.md section 9 "Local lights") -----------------------------------------------------------------------
+// The sun's pass with a light inside the scene: per light, in index order on the main stream, into ONE queue all lights share, the ray's own
+// interval (1e-5, tmax) in a float2 array beside it, which the any-hit traversal reads (TraceQueue::tRange).  lightGenKernel puts the specular
+// term in the record's weight and g = (NoL / pi) att in its flags word; lightAddKernel adds an unoccluded slot's terms to the pixel's fp32 sums
+// (a pixel has at most one slot per light: the order of a sum is the order of the lights).  Behind the last light sunHitResolveKernel packs
+// the sums into the words and leaves them zero.
+struct LightArgs { float Px, Py, Pz, range, Ix, Iy, Iz, radius, Ax, Ay, Az, cosOuter, cosInner; };
+struct LightSample { f3 L, Ls; float NoL, tmax, att; };      // L: toward the centre (the term's direction); Ls, tmax: the shadow ray's
+// Steps 1-6 of rtggx_set_lights at the surface point P with normal N: where none of them says 'no ray, no term', onLit(sample) runs
+// (atPrimarySurface).  j: the hash slot (SOFT only).
+template <bool CONE, bool SOFT, class Lit>
+RT_DEV void evalLight(const LightArgs& K, const float* cosSin, f3 P, f3 N, uint32_t pixel, uint32_t frameIndex, uint32_t j, Lit onLit) {
+  // steps 1 and 2: in range, facing
+  const f3 D = mk3(K.Px - P.x, K.Py - P.y, K.Pz - P.z);
+  const float d2 = dot3(D, D), RR = K.range * K.range;
+  const f3 L = normalize3(D);
+  const float NoL = dot3(N, L);
+  bool lit = d2 >= 1e-6f && d2 < RR && NoL > 0.0f;
+  float spot = 1.0f;
+  if constexpr (CONE) {      // step 3
+    const float c = -dot3(L, mk3(K.Ax, K.Ay, K.Az));
+    const float t = saturatef((c - K.cosOuter) / (K.cosInner - K.cosOuter));
+    spot = t * t;
+    lit = lit && c > K.cosOuter;
+  }
+  f3 Ds = D;
+  if constexpr (SOFT) {      // step 5: a point of the emitting sphere, uniform over its surface
+    if (lit) {
+      const ShadowSample x = shadowSample(pixel, frameIndex, j);
+      const float z = 1.0f - 2.0f * x.u, rho = sqrtf(1.0f - z * z);
+      Ds = mk3(D.x + K.radius * (rho * cosSin[x.s]), D.y + K.radius * (rho * cosSin[256u + x.s]), D.z + K.radius * z);
+    }
+  }
+  const float ds2 = dot3(Ds, Ds);
+  const f3 Ls = normalize3(Ds);
+  lit = lit && ds2 >= 1e-6f && dot3(N, Ls) > 0.0f;      // step 6
+  if (!lit) return;
+  // step 4: the window, the floor; E = I att
+  const float q = d2 / RR;
+  float win = saturatef(1.0f - q * q); win = win * win;
+  const float m2 = fmaxf(K.radius * K.radius, 1e-4f);
+  LightSample o;
+  o.att = (win * spot) / fmaxf(d2, m2);
+  o.L = L; o.Ls = Ls; o.NoL = NoL; o.tmax = sqrtf(ds2);
+  onLit(o);
+}
+struct LightGenArgs {
+  const unsigned long long* visDepth; const float4* fat0; const float4* fat1;
+  RayRec* rays; HitKey* hits; uint32_t* binCount; float2* tRange;
+  const uint32_t* tileWords; uint32_t tilesX, rowBegin, rowEnd;
+  LightArgs light;
+  const float* cosSin; uint32_t slot;      // SOFT: the 256-entry table, and RT_SLOT_LIGHT(i)
+};
+template <bool CONE, bool SOFT>
+__global__ void __launch_bounds__(256) lightGenKernel(const FrameParams* __restrict__ fpp, LightGenArgs A) {
+  const FrameParams& fp = *fpp;
+  const uint32_t tile = blockIdx.x;
+  if (tileIsEmpty(A.tileWords, tile)) return;
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const uint32_t px = (tile % A.tilesX) * 16 + (wave & 1u) * 8 + (lane & 7u);
+  const uint32_t py = A.rowBegin + (tile / A.tilesX) * 16 + (wave >> 1) * 8 + (lane >> 3);
+  bool want = false;
+  RayRec rr;
+  float tmax = 0.0f;
+  if (px < fp.W && py < A.rowEnd) atPrimarySurface(fp, A.visDepth, A.fat0, A.fat1, px, py, [&](const PrimarySurface& s) {
+    evalLight<CONE, SOFT>(A.light, A.cosSin, s.P, s.N, s.pixel, fp.g.FrameIndex, A.slot, [&](const LightSample& l) {      // step 8: the sun's term at the centre direction L
+    const f3 Fk = deltaLightSpecular(s.N, s.V, l.L, l.NoL, s.color, s.rm);
+    want = true;
+    tmax = l.tmax;
+    rr = shadowRay(s.P, l.Ls, s.pixel, (s.inst << 24) | s.prim, mk3(Fk.x * (A.light.Ix * l.att), Fk.y * (A.light.Iy * l.att), Fk.z * (A.light.Iz * l.att)),
+                   __float_as_uint((l.NoL / RT_PI) * l.att));
+  }); });
+  const uint32_t bin = blockIdx.x * 4u + wave;
+  const uint32_t n = compactShadowRay<true>(want, rr, tmax, A.rays, A.hits, A.tRange, bin, RT_BIN_MIN, 0u, lane);
+  if (lane == 0) A.binCount[bin] = n;
+}
+struct LightAddArgs {
+  const RayRec* rays; const HitKey* hits; const uint32_t* binCount; const uint32_t* tileWords;
+  float4* sumRefl; float4* sumDiff; float Ix, Iy, Iz;
+};
+__global__ void __launch_bounds__(256) lightAddKernel(const FrameParams* __restrict__ fpp, LightAddArgs A) {
+  const FrameParams& fp = *fpp;
+  if (tileIsEmpty(A.tileWords, blockIdx.x)) return;
+  const uint32_t bin = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (lane >= A.binCount[bin]) return;
+  const size_t k = (size_t)bin * RT_BIN_MIN + lane;
+  if (hitKeyId(A.hits[k]) != 0xFFFFFFFFu) return;      // occluded: no term
+  const RayRec rr = A.rays[k];
+  const uint32_t inst = rr.skip >> 24;
+  const float4 s0 = A.sumRefl[rr.pixel];
+  A.sumRefl[rr.pixel] = make_float4(s0.x + rr.wx, s0.y + rr.wy, s0.z + rr.wz, s0.w + 1.0f);
+  if (fp.mat.RoughMetals[inst][1] < 1.0f) {      // rghMtl.y < 1 is the instance's constant (launchShade); elsewhere RayTracingOut1 is a carry-over and stays
+    const float g = __uint_as_float(rr.flags);
+    const float4 s1 = A.sumDiff[rr.pixel];
+    A.sumDiff[rr.pixel] = make_float4(s1.x + ((fp.mat.BaseColors[inst][0] * (1.0f - 0.04f)) * g) * A.Ix, s1.y + ((fp.mat.BaseColors[inst][1] * (1.0f - 0.04f)) * g) * A.Iy,
+                                      s1.z + ((fp.mat.BaseColors[inst][2] * (1.0f - 0.04f)) * g) * A.Iz, s1.w + 1.0f);
+  }
+}
+// A light of the context's list as the kernels take it; whether it casts rays at all (intensity 0 in every component: it keeps its index and
+// casts none); which <CONE, SOFT> instance it runs, as an index [2 cone + soft] into a table of the four
+static LightArgs lightArgs(const RtggxLight& l) {
+  return LightArgs{l.position[0], l.position[1], l.position[2], l.range, l.intensity[0], l.intensity[1], l.intensity[2], l.radius,
+                   l.axis[0], l.axis[1], l.axis[2], l.cos_outer, l.cos_inner};
+}
+static bool lightCastsRays(const RtggxLight& l) { return l.intensity[0] > 0.0f || l.intensity[1] > 0.0f || l.intensity[2] > 0.0f; }
+static uint32_t lightVariant(const RtggxLight& l) { return (l.cos_outer > -1.0f ? 2u : 0u) | (l.radius > 0.0f ? 1u : 0u); }
+static void (*const kLightGen[4])(const FrameParams*, LightGenArgs) = {lightGenKernel<false, false>, lightGenKernel<false, true>, lightGenKernel<true, false>, lightGenKernel<true, true>};
+
+// One level's unoccluded terms into the sums of the two hit passes.  One lane per slot.  SAMPLES: the sums are the sample sums (three floats
+// per pixel and image); else S, four: the terms and their number.
+struct SunHitAddArgs {
+  const RayRec* rays; const HitKey* hits; const uint32_t* binCount; uint32_t binSlots; const uint32_t* tileWords;
+  float* sumRefl; float* sumDiff;
+};
+template <bool SAMPLES>
+__global__ void __launch_bounds__(256) sunHitAddKernel(SunHitAddArgs A) {
+  if (tileIsEmpty(A.tileWords, blockIdx.x)) return;
+  const uint32_t bin = blockIdx.x * 4u + (threadIdx.x >> 6);
+  const uint32_t count = min(A.binCount[bin], A.binSlots);
+  for (uint32_t i = threadIdx.x & 63u; i < count; i += 64u) {
+    const size_t k = (size_t)bin * A.binSlots + i;
+    if (hitKeyId(A.hits[k]) != 0xFFFFFFFFu) continue;      // occluded: no term
+    const RayRec rr = A.rays[k];
+    float* const sum = (rr.flags & 1u) != 0u ? A.sumDiff : A.sumRefl;
+    if constexpr (SAMPLES) {
+      float* acc = sum + 3u * (size_t)rr.pixel;
+      acc[0] = acc[0] + rr.wx; acc[1] = acc[1] + rr.wy; acc[2] = acc[2] + rr.wz;
+    } else {
+      float4* acc = reinterpret_cast<float4*>(sum) + rr.pixel;
+      const float4 s = *acc;
+      *acc = make_float4(s.x + rr.wx, s.y + rr.wy, s.z + rr.wz, s.w + 1.0f);
+    }
+  }
+}
+// One sample per pixel, behind the last shading pass or the last light: word = pack(unpack(word) + S) where a term exists (S.w: their
+// number), the word untouched where none does; S is left zero for the next frame by the lanes that found it set.
+struct SunHitResolveArgs { float4* sumRefl; float4* sumDiff; uint32_t* reflOut; uint32_t* diffOut; const uint32_t* tileWords; uint32_t tilesX, rowBegin, rowEnd; };
+__global__ void __launch_bounds__(256) sunHitResolveKernel(const FrameParams* __restrict__ fpp, SunHitResolveArgs A) {
+  const FrameParams& fp = *fpp;
+  const uint32_t tile = blockIdx.x;
+  if (tileIsEmpty(A.tileWords, tile)) return;
+  const uint32_t px = (tile % A.tilesX) * 16u + (threadIdx.x & 15u), py = A.rowBegin + (tile / A.tilesX) * 16u + (threadIdx.x >> 4);
+  if (px >= fp.W || py >= A.rowEnd) return;
+  const size_t pix = (size_t)py * fp.W + px;
+  const float4 r = A.sumRefl[pix], d = A.sumDiff[pix];
+  if (r.w != 0.0f) { A.reflOut[pix] = packR11G11B10F(unpackR11G11B10F(A.reflOut[pix]) + mk3(r.x, r.y, r.z)); A.sumRefl[pix] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
+  if (d.w != 0.0f) { A.diffOut[pix] = packR11G11B10F(unpackR11G11B10F(A.diffOut[pix]) + mk3(d.x, d.y, d.z)); A.sumDiff[pix] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
+}
+// S = sums: [2][W * H] float4, RayTracingOut0's then RayTracingOut1's; `done` (may be null) rides on the kernel
+int launchSunHitResolve(rtggx_context* c, hipStream_t s, float* sums, const uint32_t* tileWords, uint32_t tilesX, uint32_t rowBegin, uint32_t rowEnd, hipEvent_t done) {
+  const InputSet& set = c->cur();
+  const SunHitResolveArgs R{(float4*)sums, (float4*)sums + (size_t)c->W * c->H, set.rtRefl, set.rtDiff, tileWords, tilesX, rowBegin, rowEnd};
+  launch(sunHitResolveKernel, dim3(tilesX * ((rowEnd - rowBegin + 15u) / 16u)), dim3(256), s, nullptr, done, c->dParams + c->slot, R);
+  RT_HIP(hipGetLastError());
+  return 0;
+}
+// (a fill runs on the null stream, which this context's streams are not ordered against: one synchronise behind all of a call's fills)
+static int syncFills(bool filled) { if (filled) RT_HIP(hipStreamSynchronize(nullptr)); return 0; }
+int launchLights(rtggx_context* c, const FrameParams& fp, hipStream_t s) {
+  uint32_t rb, re;
+  passRows(fp, ROWS_GBUFFER, rb, re);
+  if (re <= rb) return 0;
+  const uint32_t tilesX = (fp.W + 15) / 16, tilesY = (re - rb + 15) / 16, numTiles = tilesX * tilesY;
+  if (numTiles * 4u > c->numBinsMax) { setError("rtggx_ray_trace: the lights' queue does not hold %u bins", numTiles * 4u); return -1; }
+  { // what the lights need, from the first frame that has some: the queue with its intervals, the sums
+    bool filled = false;
+    { const int r = c->lightQueue.ensure(c->numBinsMax, RT_BIN_MIN, true, filled); if (r) return r; }
+    if (!c->lightSums) { RT_HIP(allocFilled(c->lightSums, (size_t)c->W * c->H * 8u)); filled = true; }
+    { const int r = syncFills(filled); if (r) return r; } }
+  const InputSet& set = c->cur();
+  const FrameParams* const dfp = c->dParams + c->slot;
+  const TraceQueue q = c->lightQueue.view();      // bins of RT_BIN_MIN slots, as the sun's, and the rays' own intervals
+  LightGenArgs G;
+  G.visDepth = c->curVis().depth; G.fat0 = c->mesh[0].fat; G.fat1 = c->mesh[1].fat;
+  G.rays = (RayRec*)q.rays; G.hits = q.hits; G.binCount = c->lightQueue.count; G.tRange = (float2*)q.tRange;
+  G.tileWords = c->tileWords(rb, re); G.tilesX = tilesX; G.rowBegin = rb; G.rowEnd = re;
+  G.cosSin = c->cosSinTab;
+  LightAddArgs D;
+  D.rays = q.rays; D.hits = q.hits; D.binCount = q.binCount; D.tileWords = G.tileWords;
+  D.sumRefl = (float4*)c->lightSums.get(); D.sumDiff = D.sumRefl + (size_t)c->W * c->H;
+  for (uint32_t i = 0; i < c->lights.count; ++i) {
+    const RtggxLight& l = c->lights.l[i];
+    if (!lightCastsRays(l)) continue;
+    G.light = lightArgs(l); G.slot = RT_SLOT_LIGHT(i);
+    launch(kLightGen[lightVariant(l)], dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, G);
+    // the sun's launch (launchSun): spill part 2
+    { const int r = launchTrace(c, fp, s, q, numTiles * 4u, true, tilesX, tilesY, c->traceGrid[3], -1, nullptr, nullptr, 2, true); if (r) return r; }
+    D.Ix = G.light.Ix; D.Iy = G.light.Iy; D.Iz = G.light.Iz;
+    launch(lightAddKernel, dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, D);
+    RT_HIP(hipGetLastError());
+  }
+  return launchSunHitResolve(c, s, c->lightSums, G.tileWords, tilesX, rb, re, nullptr);
+}
+
+// ---- the sun and the lights at the surfaces the paths hit (rtggx_set_sun_reflections, rtggx_set_light_reflections) -----------------------------
+// In front of EVERY level's shading pass, on the stream that shades: a spawning pass compacts the next level's rays into the bin in place, so
+// the hits are read first -- the sun's pass, then per light, in index order, the lights'.  A generating kernel walks the wave's bin as
+// shadeKernel does (a bin of 128 takes two rounds) and compacts one shadow ray per lit hit into the same bin of a queue of the feature's own:
+// origin the hit point, skip the hit triangle, weight the finished s = T_d term, flags the image the path writes.  sunHitAddKernel (a record
+// carries all it reads) adds an unoccluded ray's weight to the pixel's sum -- S (one sample: sunHitSums, resolved into the packed words
+// behind the last shading pass by sunHitResolveKernel) or the sample sums resolveSamplesKernel packs (N > 1).  A pass holds at most one
+// live path per (pixel, image): the order of a sum is sun, then the lights ascending, level by level.
+struct HitBinArgs {
+  const RayRec* rays; const HitKey* hits; const uint32_t* binCount; uint32_t binSlots;      // the frame's bins, this level's rays and their hits
+  const float4* fat0; const float4* fat1;
+};
+struct SunHitGenArgs : HitBinArgs {
+  RayRec* outRays; HitKey* outHits; uint32_t* outCount;                                     // the feature's queue: the same bins, binSlots slots each
+  const uint32_t* tileWords;
+  float Lx, Ly, Lz, Ex, Ey, Ez;
+};
+struct SunHitGenArgsSoft : SunHitGenArgs { SunDiskArgs disk; };      // the frame index of the sample the pass belongs to, RT_SLOT_SUN_HIT(d)
+template <bool SOFT>
+__global__ void __launch_bounds__(256) sunHitGenKernel(const FrameParams* __restrict__ fpp, std::conditional_t<SOFT, SunHitGenArgsSoft, SunHitGenArgs> A) {
+  const FrameParams& fp = *fpp;
+  const uint32_t tile = blockIdx.x;
+  if (tileIsEmpty(A.tileWords, tile)) return;
+  const uint32_t bin = tile * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  const uint32_t count = RT_SGPR(min(A.binCount[bin] & 0xFFu, A.binSlots));
+  const f3 L = mk3(A.Lx, A.Ly, A.Lz);
+  uint32_t written = 0u;      // shadow rays in the front of the bin so far: never more than the records read
+  for (uint32_t base = 0u; base < count; base += 64u) {
+    const uint32_t i = base + lane;
+    bool want = false;
+    RayRec sr;
+    if (i < count) atTracedHit(fp, A.rays, A.hits, A.fat0, A.fat1, (size_t)bin * A.binSlots + i, [&](const TracedHit& h) {
+      const float NoL = dot3(h.N, L);
+      f3 Ls = L;      // SOFT: toward the point of the disk this hit's slot draws
+      bool facing = NoL > 0.0f;
+      if constexpr (SOFT) { if (facing) { Ls = sunDiskDirection(A.disk, L, h.pixel, A.disk.frameIndex, A.disk.slotBase + RT_SLOT_SUN_HIT_IMAGE * h.image); facing = dot3(h.N, Ls) > 0.0f; } }
+      if (facing) {
+        const f3 term = hitLobeTerm(fp, h, L, NoL, mk3(A.Ex, A.Ey, A.Ez), 1.0f);
+        want = true;
+        sr = shadowRay(h.P(), Ls, h.pixel, h.hitId, mk3(h.q2.x * term.x, h.q2.y * term.y, h.q2.z * term.z), h.image);      // s_d = T_d * term
+      }
+    });
+    written += compactShadowRay<false>(want, sr, RT_RAY_TMAX, A.outRays, A.outHits, nullptr, bin, A.binSlots, written, lane);
+  }
+  if (lane == 0u) A.outCount[bin] = written;
+}
+struct LightHitGenArgs : HitBinArgs {
+  RayRec* outRays; HitKey* outHits; uint32_t* outCount; float2* outRange;                   // the feature's queue: the same bins, binSlots slots each
+  const uint32_t* tileWords;
+  LightArgs light;
+  const float* cosSin; uint32_t frameIndex, slotBase;      // SOFT: the 256-entry table, the frame index of the sample the pass belongs to, RT_SLOT_LIGHT_HIT(d, i)
+};
+template <bool CONE, bool SOFT>
+__global__ void __launch_bounds__(256) lightHitGenKernel(const FrameParams* __restrict__ fpp, LightHitGenArgs A) {
+  const FrameParams& fp = *fpp;
+  const uint32_t tile = blockIdx.x;
+  if (tileIsEmpty(A.tileWords, tile)) return;
+  const uint32_t bin = tile * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  const uint32_t count = RT_SGPR(min(A.binCount[bin] & 0xFFu, A.binSlots));
+  uint32_t written = 0u;      // shadow rays in the front of the bin so far: never more than the records read
+  for (uint32_t base = 0u; base < count; base += 64u) {
+    const uint32_t i = base + lane;
+    bool want = false;
+    RayRec sr;
+    float tmax = 0.0f;
+    if (i < count) atTracedHit(fp, A.rays, A.hits, A.fat0, A.fat1, (size_t)bin * A.binSlots + i, [&](const TracedHit& h) {
+      evalLight<CONE, SOFT>(A.light, A.cosSin, h.P(), h.N, h.pixel, A.frameIndex, A.slotBase + RT_SLOT_LIGHT_HIT_IMAGE * h.image, [&](const LightSample& l) {
+      const f3 term = hitLobeTerm(fp, h, l.L, l.NoL, mk3(A.light.Ix, A.light.Iy, A.light.Iz), l.att);
+      want = true;
+      tmax = l.tmax;
+      sr = shadowRay(h.P(), l.Ls, h.pixel, h.hitId, mk3(h.q2.x * term.x, h.q2.y * term.y, h.q2.z * term.z), h.image);      // s = T_d * term
+    }); });
+    written += compactShadowRay<true>(want, sr, tmax, A.outRays, A.outHits, A.outRange, bin, A.binSlots, written, lane);
+  }
+  if (lane == 0u) A.outCount[bin] = written;
+}
+static void (*const kLightHitGen[4])(const FrameParams*, LightHitGenArgs) = {lightHitGenKernel<false, false>, lightHitGenKernel<false, true>, lightHitGenKernel<true, false>, lightHitGenKernel<true, true>};
+
+// The frame's first use of the hit passes' queues and sums on stream s.  They exist from the first frame that has the sun or lights and the
+// respective toggle on: per feature its queue at the frame's slots per bin (the bins' growth releases it: frame.hip growBins, behind a wait
+// for every stream) -- the lights' with the rays' intervals --, and for one-sample frames S, which the two share.  The use is ordered behind
+// the previous frame's, which may have run on another stream (small launches alternate two), as launchShadeSamples orders sppAcc.
+int beginSunHits(rtggx_context* c, hipStream_t s, bool wantSums, bool sunQueue, bool lightQueue) {
+  bool filled = false;
+  if (!c->evSunHit) RT_HIP(create(c->evSunHit, hipEventDisableTiming));
+  if (sunQueue) { const int r = c->sunHitQueue.ensure(c->numBinsMax, c->binSlots, false, filled); if (r) return r; }
+  if (lightQueue) { const int r = c->lightHitQueue.ensure(c->numBinsMax, c->binSlots, true, filled); if (r) return r; }
+  if (wantSums && !c->sunHitSums) { RT_HIP(allocFilled(c->sunHitSums, (size_t)c->W * c->H * 8u)); filled = true; }
+  { const int r = syncFills(filled); if (r) return r; }
+  if (c->sunHitStream && c->sunHitStream != s) { RT_HIP(hipEventRecord(c->evSunHit, c->sunHitStream)); RT_HIP(hipStreamWaitEvent(s, c->evSunHit, 0)); }
+  c->sunHitStream = s;
+  return 0;
+}
+// One level's hits (HitPass, rt_queue.h: the bins, their rays traced and not yet shaded) under the sun, and under the lights: the generation,
+// the any-hit traversal of the feature's queue on the frame's trace grid with this stream's spill part (launchShade) -- the lights' reading
+// the rays' own intervals --, the add into sumRefl / sumDiff
+static int traceAndAddHits(rtggx_context* c, const FrameParams& fp, const HitPass& p, const TraceQueue& q) {
+  { const int r = launchTrace(c, fp, p.s, q, c->traceGrid[0], true, c->traceGrid[1], c->traceGrid[2], c->traceGrid[3], -1, nullptr, nullptr, p.spillPart, true); if (r) return r; }
+  const SunHitAddArgs D{q.rays, q.hits, q.binCount, q.binSlots, p.tileWords, p.sumRefl, p.sumDiff};
+  launch(p.samples ? sunHitAddKernel<true> : sunHitAddKernel<false>, dim3(p.numTiles), dim3(256), p.s, nullptr, nullptr, D);
+  RT_HIP(hipGetLastError());
+  return 0;
+}
+int launchSunHits(rtggx_context* c, const FrameParams& fp, const HitPass& p) {
+  const TraceQueue q = c->sunHitQueue.view();
+  if (p.numTiles * 4u > c->numBinsMax || q.binSlots != p.bins.binSlots) { setError("rtggx_ray_trace: the queue of rtggx_set_sun_reflections does not hold %u bins of %u slots", p.numTiles * 4u, p.bins.binSlots); return -1; }
+  SunHitGenArgs G;
+  static_cast<HitBinArgs&>(G) = HitBinArgs{p.bins.rays, p.bins.hits, p.bins.binCount, p.bins.binSlots, p.fat0, p.fat1};
+  G.outRays = (RayRec*)q.rays; G.outHits = q.hits; G.outCount = c->sunHitQueue.count;
+  G.tileWords = p.tileWords;
+  G.Lx = c->sun.L[0]; G.Ly = c->sun.L[1]; G.Lz = c->sun.L[2]; G.Ex = c->sun.E[0]; G.Ey = c->sun.E[1]; G.Ez = c->sun.E[2];
+  if (c->sunAngle.degrees > 0.0f) {      // rtggx_set_sun_angle
+    SunHitGenArgsSoft GS;
+    static_cast<SunHitGenArgs&>(GS) = G;
+    GS.disk = sunDisk(c, p.frameIndex, RT_SLOT_SUN_HIT(p.level));
+    launch(sunHitGenKernel<true>, dim3(p.numTiles), dim3(256), p.s, nullptr, nullptr, c->dParams + c->slot, GS);
+  } else launch(sunHitGenKernel<false>, dim3(p.numTiles), dim3(256), p.s, nullptr, nullptr, c->dParams + c->slot, G);
+  return traceAndAddHits(c, fp, p, q);
+}
+int launchLightHits(rtggx_context* c, const FrameParams& fp, const HitPass& p) {
+  const TraceQueue q = c->lightHitQueue.view();
+  if (p.numTiles * 4u > c->numBinsMax || q.binSlots != p.bins.binSlots) { setError("rtggx_ray_trace: the queue of rtggx_set_light_reflections does not hold %u bins of %u slots", p.numTiles * 4u, p.bins.binSlots); return -1; }
+  LightHitGenArgs G;
+  static_cast<HitBinArgs&>(G) = HitBinArgs{p.bins.rays, p.bins.hits, p.bins.binCount, p.bins.binSlots, p.fat0, p.fat1};
+  G.outRays = (RayRec*)q.rays; G.outHits = q.hits; G.outCount = c->lightHitQueue.count; G.outRange = (float2*)q.tRange;
+  G.tileWords = p.tileWords;
+  G.cosSin = c->cosSinTab; G.frameIndex = p.frameIndex;
+  for (uint32_t i = 0; i < c->lights.count; ++i) {
+    const RtggxLight& l = c->lights.l[i];
+    if (!lightCastsRays(l)) continue;
+    G.light = lightArgs(l); G.slotBase = RT_SLOT_LIGHT_HIT(p.level, i);
+    launch(kLightHitGen[lightVariant(l)], dim3(p.numTiles), dim3(256), p.s, nullptr, nullptr, c->dParams + c->slot, G);
+    { const int r = traceAndAddHits(c, fp, p, q); if (r) return r; }
+  }
+  return 0;
+}
+
+}  // namespace rt

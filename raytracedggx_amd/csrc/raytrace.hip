@@ -1,6 +1,6 @@
 // Ray-tracing pass: the gfx950 replacement of DispatchRays(W,H,1) over RayTracing.cso
 // (RayTracer::rayTrace, RayTracedGGX/Content/RayTracer.cpp:793-810).  The four DXR shaders of
-// RayTracedGGX/Content/Shaders/RayTracing.hlsl become three kernels around a ray queue:
+// RayTracedGGX/Content/Shaders/RayTracing.hlsl become three kernels around a ray queue (and, since, the variants and passes listed below):
 //
 //   rayGenKernel   raygenMain :541-565 up to the TraceRay calls: G-buffer reconstruction from the
 //                  visibility buffer (getPrimarySurface :277-333), GGX / uniform-sphere sampling
@@ -18,6 +18,12 @@
 //                  the tail of computeReflection / computeDiffuse, with Material.hlsli,
 //                  BRDFModels.hlsli, SHIrradianceTypeless.hlsli:16-37; writes RayTracingOut0/1.
 //
+// Beside them here: sampleParamsKernel / sampleGenKernel / resolveSamplesKernel (N samples per pixel), reconstructKernel (quarter rate),
+// accumulateKernel / presentAccumulationKernel, envPrefilterKernel, and the test entries (fillTestQueue, exportTestHits, exportOcclusion,
+// debugEnvironmentKernel).  Direct lighting -- the sun, the local lights, both at the surfaces the paths hit -- is lighting.hip; launchShade
+// calls its hit passes in front of every level's shading pass.  What both files' kernels call (Material.hlsli, BRDF terms, rng, triangle and
+// attribute helpers) is rt_surface.h.
+//
 // rayGenKernel and traceKernel run on stream B, shadeKernel on the main stream one frame behind (frame.hip).
 // Roofline: HBM by decree of the metric (no MFMA work exists here).  Algorithmic bytes:
 // rayGen 18 B/pixel (+64 B per queued ray); trace 64 B ray + 16 B hit per ray + the scene arrays
@@ -27,11 +33,10 @@
 #include <type_traits>
 #include "rt_queue.h"
 #include "rt_traverse.h"
+#include "rt_surface.h"
 
 namespace rt {
 
-#define RT_PI 3.1415926535897f   // BRDFModels.hlsli:5
-#define RT_SGPR(v) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(v)))      // a workgroup-uniform value the compiler may have computed in vector registers
 
 // ---- environment (RayTracing.hlsl:167-180; D3D cube sampling restated) --------------
 struct EnvRef { const uint2* __restrict__ texels; uint32_t size, mips; const uint32_t* __restrict__ mipOffset; };
@@ -110,54 +115,7 @@ RT_DEV f3 evaluateSHIrradiance(const float* __restrict__ sh, f3 norm) {
   return mk3(fmaxf(0.0f, irr.x), fmaxf(0.0f, irr.y), fmaxf(0.0f, irr.z));
 }
 
-// ---- Material.hlsli -----------------------------------------------------------------------------------
-RT_DEV f2 getUV(f3 n, f3 p, f3 scl) {   // :16-23
-  f2 uv; uv.x = fabsf(n.x) * p.y * scl.y; uv.y = fabsf(n.x) * p.z * scl.z;
-  uv.x += fabsf(n.y) * p.z * scl.z; uv.y += fabsf(n.y) * p.x * scl.x;
-  uv.x += fabsf(n.z) * p.x * scl.x; uv.y += fabsf(n.z) * p.y * scl.y;
-  uv.x = uv.x * 0.5f + 0.5f; uv.y = uv.y * 0.5f + 0.5f;
-  return uv;
-}
-RT_DEV f2 getRoughMetal(const RtggxCBMaterial& mat, uint32_t inst, f2 uv) {   // :30-48
-  float rough = mat.RoughMetals[inst][0];
-  if (inst == 0) {
-    const uint32_t px = ftou(uv.x * 5.0f) & 1u, py = ftou(uv.y * 5.0f) & 1u;
-    rough = (px ^ py) ? rough * 0.25f : rough;
-  }
-  f2 r; r.x = rough; r.y = mat.RoughMetals[inst][1];
-  return r;
-}
-
-// ---- BRDFModels.hlsli ---------------------------------------------------------------------------------
-RT_DEV float visSmith(float roughness, float NoV, float NoL) {   // :30-39
-  const float a = roughness * roughness, a2 = a * a;
-  const float v = NoV + sqrtf(NoV * (NoV - NoV * a2) + a2);
-  const float l = NoL + sqrtf(NoL * (NoL - NoL * a2) + a2);
-  return 1.0f / (v * l);
-}
-RT_DEV f3 fSchlick(f3 spec, float VoH) {   // :54-62, pow(x,5) by multiplication
-  const float x = 1.0f - VoH, x2 = x * x;
-  const float fc = (x2 * x2) * x;
-  const float s = saturatef(50.0f * spec.y) * fc;
-  return mk3(s + (1.0f - fc) * spec.x, s + (1.0f - fc) * spec.y, s + (1.0f - fc) * spec.z);
-}
-RT_DEV f3 envBRDFApprox(f3 spec, float roughness, float NoV) {   // :64-77
-  const float rx = roughness * -1.0f + 1.0f, ry = roughness * -0.0275f + 0.0425f;
-  const float rz = roughness * -0.572f + 1.04f, rw = roughness * 0.022f + -0.04f;
-  const float a004 = fminf(rx * rx, exp2Contract(-9.28f * NoV)) * rx + ry;
-  const float ABx = -1.04f * a004 + rz;
-  float ABy = 1.04f * a004 + rw;
-  ABy *= saturatef(50.0f * spec.y);
-  return mk3(spec.x * ABx + ABy, spec.y * ABx + ABy, spec.z * ABx + ABy);
-}
-
 // ---- RayTracing.hlsl helpers ---------------------------------------------------------------------------
-RT_DEV uint32_t rng(uint32_t seed) {   // :379-387
-  seed = seed * 747796405u + 1u;
-  seed = ((seed >> ((seed >> 28) + 4u)) ^ seed) * 277803737u;
-  seed = (seed >> 22) ^ seed;
-  return seed;
-}
 RT_DEV float calcMipFromRoughness(float rgh, float mipCount) {   // :416-422
   const float level = 3.0f - 1.15f * log2Contract(rgh);
   return mipCount - 1.0f - level;
@@ -221,41 +179,6 @@ RT_DEV f3 diffuseDirection(f3 N, float cosPhi, float sinPhi, float xiY) {
   const float cosTheta = 1.0f - 2.0f * xiY;
   const float sinTheta = sqrtf(1.0f - cosTheta * cosTheta);
   return normalize3(N + mk3(cosPhi * sinTheta, sinPhi * sinTheta, cosTheta));
-}
-struct Tri3 { f3 pos[3], nrm[3]; };
-RT_DEV Tri3 getVertices(const float4* __restrict__ fat, uint32_t prim) {   // :230-244, from the primitive's fat triangle (rtggx_context.h): five 16-byte loads, one dependent step
-  const float4* p = fat + 5 * (size_t)prim;
-  const float4 a = p[0], b = p[1], c = p[2], d = p[3], e = p[4];
-  Tri3 v;
-  v.pos[0] = mk3(a.x, a.y, a.z); v.nrm[0] = mk3(a.w, b.x, b.y);
-  v.pos[1] = mk3(b.z, b.w, c.x); v.nrm[1] = mk3(c.y, c.z, c.w);
-  v.pos[2] = mk3(d.x, d.y, d.z); v.nrm[2] = mk3(d.w, e.x, e.y);
-  return v;
-}
-struct Attrib { f3 Pos, Nrm; f2 UV; };
-RT_DEV Attrib interpAttrib(const Tri3& v, float b1, float b2) {   // :249-271
-  const float w0 = 1.0f - (b1 + b2);
-  Attrib a;
-  a.Pos = (w0 * v.pos[0] + b1 * v.pos[1]) + b2 * v.pos[2];
-  a.Nrm = (w0 * v.nrm[0] + b1 * v.nrm[1]) + b2 * v.nrm[2];
-  a.UV = getUV(a.Nrm, a.Pos, mk3(1.0f, 0.2f, 1.0f));
-  return a;
-}
-RT_DEV f2 calcBarycentrics(const f4 p[3], f2 ndc) {   // :204-225
-  const f3 invW = mk3(1.0f / p[0].w, 1.0f / p[1].w, 1.0f / p[2].w);
-  f2 ndc0, ndc1, ndc2;
-  ndc0.x = p[0].x * invW.x; ndc0.y = p[0].y * invW.x; ndc1.x = p[1].x * invW.y; ndc1.y = p[1].y * invW.y; ndc2.x = p[2].x * invW.z; ndc2.y = p[2].y * invW.z;
-  const float det = (ndc2.x - ndc1.x) * (ndc0.y - ndc1.y) - (ndc2.y - ndc1.y) * (ndc0.x - ndc1.x);
-  const float invDet = 1.0f / det;
-  const f3 dPdx = mk3(ndc1.y - ndc2.y, ndc2.y - ndc0.y, ndc0.y - ndc1.y) * invDet;
-  const f3 dPdy = mk3(ndc2.x - ndc1.x, ndc0.x - ndc2.x, ndc1.x - ndc0.x) * invDet;
-  f2 dv; dv.x = ndc.x - ndc0.x; dv.y = ndc.y - ndc0.y;
-  const float interpInvW = (invW.x + dv.x * dot3(invW, dPdx)) + dv.y * dot3(invW, dPdy);
-  const float interpW = 1.0f / interpInvW;
-  f2 b;
-  b.x = interpW * (dv.x * dPdx.y * invW.y + dv.y * dPdy.y * invW.y);
-  b.y = interpW * (dv.x * dPdx.z * invW.z + dv.y * dPdy.z * invW.z);
-  return b;
 }
 
 // =========================================================================================================
@@ -1071,7 +994,7 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
   if (c->timing) hipEventRecord(c->tev[11], s);
   const bool ring = c->kernelRing && c->kevCount < c->kevBegin.size() && (c->ringTick++ % c->ringStride) == 0u;
   // a sampled frame: the event pair of the kernel ring rides on the dispatch (and `done` is recorded behind it)
-  const TraceQueue q{G.rays, G.hits, G.binCount};
+  const TraceQueue q{G.rays, G.hits, G.binCount, G.binSlots, nullptr};
   c->traceGrid[0] = numBins; c->traceGrid[1] = quad ? quadX : tilesX; c->traceGrid[2] = quad ? quadY : tilesY; c->traceGrid[3] = sliceShift;      // (the later levels' launches: launchShade)
   { const int r = launchTrace(c, fp, s, q, numBins, true, quad ? quadX : tilesX, quad ? quadY : tilesY, sliceShift, adaptive ? (int)G.splitCap : -1,
                               ring ? c->kevBegin[c->kevCount] : nullptr, ring ? c->kevEnd[c->kevCount] : done); if (r) return r; }
@@ -1079,383 +1002,6 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
   if (ring) ++c->kevCount;
   if (done && ring) hipEventRecord(done, s);
   RT_HIP(hipGetLastError());
-  return 0;
-}
-
-// ---- the sun at the surfaces the paths hit (rtggx_set_sun_reflections; include/rtggx.h has the rule) ---------------------
-// In front of EVERY level's shading pass, on the stream that shades: a spawning pass compacts the next level's rays into the bin in place, so
-// the hits are read first.  sunHitGenKernel walks the wave's bin as shadeKernel does, derives each touched hit as shadeKernel does, and where
-// the surface faces the sun compacts one shadow ray into the same bin of a queue of the feature's own: origin the hit point, direction L,
-// skip the hit triangle, weight the finished term s_d = T_d * term, flags the image the path writes.  The any-hit traversal leaves an
-// unoccluded ray's key a miss; sunHitAddKernel adds such a ray's weight to the pixel's sum -- S (one sample: sunHitSums, resolved into the
-// packed words behind the last shading pass by sunHitResolveKernel) or the sample sums resolveSamplesKernel packs (N > 1).  A pass holds at
-// most one live path per (pixel, image): no two lanes meet, no atomics, and the order of a sum is the order of the launches on the stream.
-struct SunHitGenArgs {
-  const RayRec* rays; const HitKey* hits; const uint32_t* binCount; uint32_t binSlots;      // the frame's bins, this level's rays and their hits
-  const float4* fat0; const float4* fat1;
-  RayRec* outRays; HitKey* outHits; uint32_t* outCount;                                     // the feature's queue: the same bins, binSlots slots each
-  const uint32_t* tileWords;
-  float Lx, Ly, Lz, Ex, Ey, Ez;
-};
-// A sun with a size (rtggx_set_sun_angle; include/rtggx.h has the rule): what the SOFT variants of the two generating kernels are given on top
-// of their arguments -- the disk's frame, k = 1 - cos(radius), the 256-entry cos/sin table whatever the sample set is, and (the hits) the
-// frame index of the sample the pass belongs to with the level's slot base 1 + 2d.  SOFT = false is the kernel as it was, body and
-// arguments (profiles/r17_a_sun_soft_isa.txt).
-struct SunDiskArgs { float Tx, Ty, Tz, Bx, By, Bz, k; const float* cosSin; uint32_t frameIndex, slotBase; };
-struct SunHitGenArgsSoft : SunHitGenArgs { SunDiskArgs disk; };
-// Steps 1-5 of the rule: the direction toward a point of the disk, uniform in solid angle over the cap; not renormalised.
-RT_DEV f3 sunDiskDirection(const SunDiskArgs& K, f3 L, uint32_t pixel, uint32_t frameIndex, uint32_t j) {
-  uint32_t h = rng(pixel); h += frameIndex; h = rng(h);      // getSampleParam's word before its mask
-  const uint32_t w = rng(h + j * 0x9E3779B9u);
-  const float u = (float)(w & 0xffffu) / 65536.0f;
-  const uint32_t s = w >> 24;
-  const float cosPhi = K.cosSin[s], sinPhi = K.cosSin[256u + s];
-  const float e = u * K.k;
-  const float cosTheta = 1.0f - e, sinTheta = sqrtf(e * (2.0f - e));      // (not 1 - cos^2: it cancels at small angles)
-  const float ct = cosPhi * sinTheta, st = sinPhi * sinTheta;
-  return mk3((K.Tx * ct + K.Bx * st) + L.x * cosTheta, (K.Ty * ct + K.By * st) + L.y * cosTheta, (K.Tz * ct + K.Bz * st) + L.z * cosTheta);
-}
-template <bool SOFT>
-__global__ void __launch_bounds__(256) sunHitGenKernel(const FrameParams* __restrict__ fpp, std::conditional_t<SOFT, SunHitGenArgsSoft, SunHitGenArgs> A) {
-  const FrameParams& fp = *fpp;
-  const uint32_t tile = blockIdx.x;
-  { uint32_t word;
-    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(word) : "s"(A.tileWords), "s"(tile * 4u) : "memory");
-    if (word == 0u) return; }
-  const uint32_t bin = tile * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-  const uint32_t count = RT_SGPR(min(A.binCount[bin] & 0xFFu, A.binSlots));
-  const f3 L = mk3(A.Lx, A.Ly, A.Lz);
-  uint32_t written = 0u;      // shadow rays in the front of the bin so far: never more than the records read (a bin of 128 takes two rounds)
-  for (uint32_t base = 0u; base < count; base += 64u) {
-    const uint32_t i = base + lane;
-    bool want = false;
-    RayRec sr;
-    if (i < count) {
-      const size_t slot = (size_t)bin * A.binSlots + i;
-      const float4* rp = reinterpret_cast<const float4*>(A.rays + slot);
-      const float4 q0 = rp[0], q1 = rp[1], q2 = rp[2];
-      const uint32_t pixel = __float_as_uint(q1.z), skip = __float_as_uint(q1.w), flags = __float_as_uint(q2.w);
-      const uint32_t hitId = hitKeyId(A.hits[slot]);
-      const bool diffuseGroup = (flags & 1u) != 0u;
-      const uint32_t srcInst = skip >> 24;
-      // the ray touches a surface: it hits, and it is not a reflection-group ray whose preset is <= 0 (shadeKernel: :573 returns the preset)
-      const float m = fp.mat.RoughMetals[srcInst][1];
-      const bool presetReturn = !diffuseGroup && fp.mat.BaseColors[srcInst][0] * m <= 0.0f && fp.mat.BaseColors[srcInst][1] * m <= 0.0f && fp.mat.BaseColors[srcInst][2] * m <= 0.0f;
-      if (hitId != 0xFFFFFFFFu && !presetReturn) {
-        const uint32_t hInst = hitId >> 24;
-        uint32_t hPrim = hitId & 0xFFFFFFu;
-        asm volatile("" : "+v"(hPrim));      // see shadeKernel
-        const Tri3 v = getVertices(hInst ? A.fat1 : A.fat0, hPrim);
-        float ht, hb1 = 0.0f, hb2 = 0.0f;
-        woopTestVerts(toObject(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, hInst ? fp.invWorld[1] : fp.invWorld[0]), v.pos[0], v.pos[1], v.pos[2], ht, hb1, hb2);
-        const Attrib a = interpAttrib(v, hb1, hb2);
-        const f3 N = normalize3(mulDir(a.Nrm, cbLoad3x3(hInst ? fp.g.WorldIT1 : fp.g.WorldITs0)));
-        const float NoL = dot3(N, L);
-        f3 Ls = L;      // SOFT: toward the point of the disk this hit's slot draws; below the horizon there is no ray and no term
-        bool facing = NoL > 0.0f;
-        if constexpr (SOFT) { if (facing) { Ls = sunDiskDirection(A.disk, L, pixel, A.disk.frameIndex, A.disk.slotBase + ((flags ^ (flags >> 1)) & 1u)); facing = dot3(N, Ls) > 0.0f; } }
-        if (facing) {
-          const f2 rm = getRoughMetal(fp.mat, hInst, a.UV);
-          f3 color = mk3(fp.mat.BaseColors[hInst][0], fp.mat.BaseColors[hInst][1], fp.mat.BaseColors[hInst][2]);
-          const f3 V = mk3(-q0.w, -q1.x, -q1.y);
-          f3 term;
-          if (rm.y > 0.5f) {      // the lobe the path uses at this surface: the specular term of the primary sun pass (sunGenKernel)
-            const float r = fmaxf(rm.x, 1.0f / 32.0f);
-            const f3 Hh = normalize3(V + L);
-            const float NoH = saturatef(dot3(N, Hh)), VoH = saturatef(dot3(V, Hh)), NoV = saturatef(dot3(N, V));
-            const float al = r * r, a2 = al * al;
-            const float d = (NoH * a2 - NoH) * NoH + 1.0f;
-            const float D = a2 / ((RT_PI * d) * d);
-            const f3 f0 = mk3(lerpf(0.04f, color.x, rm.y), lerpf(0.04f, color.y, rm.y), lerpf(0.04f, color.z, rm.y));
-            const f3 F = fSchlick(f0, VoH);
-            const float vis = visSmith(r, NoV, NoL);
-            const float k = (D * vis) * NoL;
-            term = mk3((F.x * k) * A.Ex, (F.y * k) * A.Ey, (F.z * k) * A.Ez);
-          } else {
-            if (diffuseGroup) color = color * (1.0f - rm.y);                 // :607
-            const float w = NoL / RT_PI;
-            term = mk3((color.x * w) * A.Ex, (color.y * w) * A.Ey, (color.z * w) * A.Ez);      // no x (1 - 0.04) at depth >= 1 (:532)
-          }
-          want = true;
-          sr.ox = q0.x + ht * q0.w; sr.oy = q0.y + ht * q1.x; sr.oz = q0.z + ht * q1.y;      // hitWorldPosition :338-341
-          sr.dx = Ls.x; sr.dy = Ls.y; sr.dz = Ls.z;
-          sr.pixel = pixel; sr.skip = hitId;
-          sr.wx = q2.x * term.x; sr.wy = q2.y * term.y; sr.wz = q2.z * term.z;             // s_d = T_d * term
-          sr.flags = (flags ^ (flags >> 1)) & 1u;                                          // the image the path writes (1: RayTracingOut1)
-        }
-      }
-    }
-    const unsigned long long mask = __ballot(want);
-    if (want) {
-      const size_t k = (size_t)bin * A.binSlots + written + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-      A.outRays[k] = sr; A.outHits[k] = hitKey(RT_RAY_TMAX, 0xFFFFFFFFu);
-    }
-    written += (uint32_t)__popcll(mask);
-  }
-  if (lane == 0u) A.outCount[bin] = written;
-}
-// One lane per slot.  SAMPLES: the sums are the sample sums (three floats per pixel and image); else S, four: the terms and their number.
-struct SunHitAddArgs {
-  const RayRec* rays; const HitKey* hits; const uint32_t* binCount; uint32_t binSlots; const uint32_t* tileWords;
-  float* sumRefl; float* sumDiff;
-};
-template <bool SAMPLES>
-__global__ void __launch_bounds__(256) sunHitAddKernel(SunHitAddArgs A) {
-  { uint32_t word;
-    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(word) : "s"(A.tileWords), "s"(blockIdx.x * 4u) : "memory");
-    if (word == 0u) return; }
-  const uint32_t bin = blockIdx.x * 4u + (threadIdx.x >> 6);
-  const uint32_t count = min(A.binCount[bin], A.binSlots);
-  for (uint32_t i = threadIdx.x & 63u; i < count; i += 64u) {
-    const size_t k = (size_t)bin * A.binSlots + i;
-    if (hitKeyId(A.hits[k]) != 0xFFFFFFFFu) continue;      // occluded: no term
-    const RayRec rr = A.rays[k];
-    float* const sum = (rr.flags & 1u) != 0u ? A.sumDiff : A.sumRefl;
-    if constexpr (SAMPLES) {
-      float* acc = sum + 3u * (size_t)rr.pixel;
-      acc[0] = acc[0] + rr.wx; acc[1] = acc[1] + rr.wy; acc[2] = acc[2] + rr.wz;
-    } else {
-      float4* acc = reinterpret_cast<float4*>(sum) + rr.pixel;
-      const float4 s = *acc;
-      *acc = make_float4(s.x + rr.wx, s.y + rr.wy, s.z + rr.wz, s.w + 1.0f);
-    }
-  }
-}
-// One sample per pixel, behind the last shading pass: word = pack(unpack(word) + S) where a term exists (S.w: their number), the word
-// untouched where none does; S is left zero for the next frame by the lanes that found it set.
-struct SunHitResolveArgs { float4* sumRefl; float4* sumDiff; uint32_t* reflOut; uint32_t* diffOut; const uint32_t* tileWords; uint32_t tilesX, rowBegin, rowEnd; };
-__global__ void __launch_bounds__(256) sunHitResolveKernel(const FrameParams* __restrict__ fpp, SunHitResolveArgs A) {
-  const FrameParams& fp = *fpp;
-  const uint32_t tile = blockIdx.x;
-  { uint32_t word;
-    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(word) : "s"(A.tileWords), "s"(tile * 4u) : "memory");
-    if (word == 0u) return; }
-  const uint32_t px = (tile % A.tilesX) * 16u + (threadIdx.x & 15u), py = A.rowBegin + (tile / A.tilesX) * 16u + (threadIdx.x >> 4);
-  if (px >= fp.W || py >= A.rowEnd) return;
-  const size_t pix = (size_t)py * fp.W + px;
-  const float4 r = A.sumRefl[pix], d = A.sumDiff[pix];
-  if (r.w != 0.0f) { A.reflOut[pix] = packR11G11B10F(unpackR11G11B10F(A.reflOut[pix]) + mk3(r.x, r.y, r.z)); A.sumRefl[pix] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
-  if (d.w != 0.0f) { A.diffOut[pix] = packR11G11B10F(unpackR11G11B10F(A.diffOut[pix]) + mk3(d.x, d.y, d.z)); A.sumDiff[pix] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
-}
-// What the two hit passes need (rtggx_set_sun_reflections, rtggx_set_light_reflections), from the first frame that has the sun or lights and
-// the respective toggle on: per feature its queue at the frame's slots per bin (the bins' growth releases it: frame.hip growBins, behind a
-// wait for every stream) and its counts -- the lights' also the rays' intervals --, and for one-sample frames S, which the two share.
-static int allocSunHits(rtggx_context* c, bool wantSums, bool sunQueue, bool lightQueue) {
-  bool cleared = false;
-  if (!c->evSunHit) RT_HIP(create(c->evSunHit, hipEventDisableTiming));
-  if (sunQueue && (!c->sunHitRays || !c->sunHitHits || c->sunHitSlots != c->binSlots)) {
-    c->sunHitRays.reset(); c->sunHitHits.reset();
-    const size_t slots = (size_t)c->numBinsMax * c->binSlots;
-    RT_HIP(alloc(c->sunHitRays, slots * sizeof(RayRec)));
-    RT_HIP(alloc(c->sunHitHits, slots * sizeof(HitKey)));
-    c->sunHitSlots = c->binSlots;
-  }
-  if (sunQueue && !c->sunHitCount) { RT_HIP(allocFilled(c->sunHitCount, (size_t)c->numBinsMax)); cleared = true; }
-  if (lightQueue && (!c->lightHitRays || !c->lightHitHits || !c->lightHitRange || c->lightHitSlots != c->binSlots)) {
-    c->lightHitRays.reset(); c->lightHitHits.reset(); c->lightHitRange.reset();
-    const size_t slots = (size_t)c->numBinsMax * c->binSlots;
-    RT_HIP(alloc(c->lightHitRays, slots * sizeof(RayRec)));
-    RT_HIP(alloc(c->lightHitHits, slots * sizeof(HitKey)));
-    RT_HIP(alloc(c->lightHitRange, slots * sizeof(float2)));
-    c->lightHitSlots = c->binSlots;
-  }
-  if (lightQueue && !c->lightHitCount) { RT_HIP(allocFilled(c->lightHitCount, (size_t)c->numBinsMax)); cleared = true; }
-  if (wantSums && !c->sunHitSums) { RT_HIP(allocFilled(c->sunHitSums, (size_t)c->W * c->H * 8u)); cleared = true; }
-  if (cleared) RT_HIP(hipStreamSynchronize(nullptr));      // (the clears run on the null stream, which this context's streams are not ordered against)
-  return 0;
-}
-// The frame's first use of the queues and sums on stream s: behind the previous frame's, which may have run on another stream (small
-// launches alternate two), as launchShadeSamples orders sppAcc
-static int beginSunHits(rtggx_context* c, hipStream_t s, bool wantSums, bool sunQueue, bool lightQueue) {
-  { const int r = allocSunHits(c, wantSums, sunQueue, lightQueue); if (r) return r; }
-  if (c->sunHitStream && c->sunHitStream != s) { RT_HIP(hipEventRecord(c->evSunHit, c->sunHitStream)); RT_HIP(hipStreamWaitEvent(s, c->evSunHit, 0)); }
-  c->sunHitStream = s;
-  return 0;
-}
-// One level's hits: generation from the bins q (their rays traced, not yet shaded), the any-hit traversal on the frame's trace grid with this
-// stream's spill part (launchShade), the add into sumRefl / sumDiff
-static int launchSunHits(rtggx_context* c, const FrameParams& fp, hipStream_t s, const TraceQueue& bins, const float4* fat0, const float4* fat1, const uint32_t* tileWords,
-                         uint32_t numTiles, int spillPart, bool samples, float* sumRefl, float* sumDiff, uint32_t frameIndex, uint32_t level) {
-  if (numTiles * 4u > c->numBinsMax || c->sunHitSlots != c->binSlots) { setError("rtggx_ray_trace: the queue of rtggx_set_sun_reflections does not hold %u bins of %u slots", numTiles * 4u, c->binSlots); return -1; }
-  const rtggx_context::Sun& sun = c->sun;
-  SunHitGenArgs G;
-  G.rays = bins.rays; G.hits = bins.hits; G.binCount = bins.binCount; G.binSlots = c->binSlots;
-  G.fat0 = fat0; G.fat1 = fat1;
-  G.outRays = (RayRec*)c->sunHitRays.get(); G.outHits = (HitKey*)c->sunHitHits.get(); G.outCount = c->sunHitCount;
-  G.tileWords = tileWords;
-  G.Lx = sun.L[0]; G.Ly = sun.L[1]; G.Lz = sun.L[2]; G.Ex = sun.E[0]; G.Ey = sun.E[1]; G.Ez = sun.E[2];
-  if (c->sunAngle.degrees > 0.0f) {      // rtggx_set_sun_angle: the slot base of the level, the frame index of the sample the pass belongs to
-    SunHitGenArgsSoft GS;
-    static_cast<SunHitGenArgs&>(GS) = G;
-    GS.disk = SunDiskArgs{sun.T[0], sun.T[1], sun.T[2], sun.B[0], sun.B[1], sun.B[2], c->sunAngle.k, c->cosSinTab, frameIndex, 1u + 2u * level};
-    launch(sunHitGenKernel<true>, dim3(numTiles), dim3(256), s, nullptr, nullptr, c->dParams + c->slot, GS);
-  } else launch(sunHitGenKernel<false>, dim3(numTiles), dim3(256), s, nullptr, nullptr, c->dParams + c->slot, G);
-  const TraceQueue q{G.outRays, G.outHits, G.outCount};
-  { const int r = launchTrace(c, fp, s, q, c->traceGrid[0], true, c->traceGrid[1], c->traceGrid[2], c->traceGrid[3], -1, nullptr, nullptr, spillPart, true); if (r) return r; }
-  SunHitAddArgs D;
-  D.rays = q.rays; D.hits = q.hits; D.binCount = q.binCount; D.binSlots = c->binSlots; D.tileWords = tileWords; D.sumRefl = sumRefl; D.sumDiff = sumDiff;
-  launch(samples ? sunHitAddKernel<true> : sunHitAddKernel<false>, dim3(numTiles), dim3(256), s, nullptr, nullptr, D);
-  RT_HIP(hipGetLastError());
-  return 0;
-}
-
-// ---- the local lights at the surfaces the paths hit (rtggx_set_light_reflections; include/rtggx.h has the rule) ------------
-// The sun's hit pass with a light inside the scene: per light, in index order, directly behind the sun's hit pass of the level and in front of
-// the level's shading pass.  lightHitGenKernel is sunHitGenKernel's walk over the wave's bin and its derivation of the touched hit, then
-// lightGenKernel's steps 1-6 with the hit's P, N and V and the lobe the path uses there; it compacts one shadow ray into the same bin of a
-// queue of the feature's own, the finished s = T_d * term in the record's weight, the image bit in its flags, the ray's interval (1e-5, tmax)
-// in a float2 array beside the queue.  The any-hit traversal is the frame's launch shape reading that interval; the add is sunHitAddKernel
-// (a record carries all it reads) into the sums the sun's hit pass uses -- S or the sample sums --, so the order of a sum is sun, then the
-// lights ascending, and a one-sample frame has one resolve.  CONE and SOFT change the instruction stream as in lightGenKernel.
-struct LightHitGenArgs {
-  const RayRec* rays; const HitKey* hits; const uint32_t* binCount; uint32_t binSlots;      // the frame's bins, this level's rays and their hits
-  const float4* fat0; const float4* fat1;
-  RayRec* outRays; HitKey* outHits; uint32_t* outCount; float2* outRange;                   // the feature's queue: the same bins, binSlots slots each
-  const uint32_t* tileWords;
-  float Px, Py, Pz, range, Ix, Iy, Iz, radius, Ax, Ay, Az, cosOuter, cosInner;
-  const float* cosSin; uint32_t frameIndex, slotBase;      // SOFT: the 256-entry table, the frame index of the sample the pass belongs to, 32 + 16 d + i
-};
-template <bool CONE, bool SOFT>
-__global__ void __launch_bounds__(256) lightHitGenKernel(const FrameParams* __restrict__ fpp, LightHitGenArgs A) {
-  const FrameParams& fp = *fpp;
-  const uint32_t tile = blockIdx.x;
-  { uint32_t word;
-    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(word) : "s"(A.tileWords), "s"(tile * 4u) : "memory");
-    if (word == 0u) return; }
-  const uint32_t bin = tile * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-  const uint32_t count = RT_SGPR(min(A.binCount[bin] & 0xFFu, A.binSlots));
-  uint32_t written = 0u;      // shadow rays in the front of the bin so far: never more than the records read (a bin of 128 takes two rounds)
-  for (uint32_t base = 0u; base < count; base += 64u) {
-    const uint32_t i = base + lane;
-    bool want = false;
-    RayRec sr;
-    float tmax = 0.0f;
-    if (i < count) {
-      const size_t slot = (size_t)bin * A.binSlots + i;
-      const float4* rp = reinterpret_cast<const float4*>(A.rays + slot);
-      const float4 q0 = rp[0], q1 = rp[1], q2 = rp[2];
-      const uint32_t pixel = __float_as_uint(q1.z), skip = __float_as_uint(q1.w), flags = __float_as_uint(q2.w);
-      const uint32_t hitId = hitKeyId(A.hits[slot]);
-      const bool diffuseGroup = (flags & 1u) != 0u;
-      const uint32_t image = (flags ^ (flags >> 1)) & 1u;      // the image the path writes (1: RayTracingOut1)
-      const uint32_t srcInst = skip >> 24;
-      // the ray touches a surface: sunHitGenKernel's test
-      const float m = fp.mat.RoughMetals[srcInst][1];
-      const bool presetReturn = !diffuseGroup && fp.mat.BaseColors[srcInst][0] * m <= 0.0f && fp.mat.BaseColors[srcInst][1] * m <= 0.0f && fp.mat.BaseColors[srcInst][2] * m <= 0.0f;
-      if (hitId != 0xFFFFFFFFu && !presetReturn) {
-        const uint32_t hInst = hitId >> 24;
-        uint32_t hPrim = hitId & 0xFFFFFFu;
-        asm volatile("" : "+v"(hPrim));      // see shadeKernel
-        const Tri3 v = getVertices(hInst ? A.fat1 : A.fat0, hPrim);
-        float ht, hb1 = 0.0f, hb2 = 0.0f;
-        woopTestVerts(toObject(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, hInst ? fp.invWorld[1] : fp.invWorld[0]), v.pos[0], v.pos[1], v.pos[2], ht, hb1, hb2);
-        const Attrib a = interpAttrib(v, hb1, hb2);
-        const f3 N = normalize3(mulDir(a.Nrm, cbLoad3x3(hInst ? fp.g.WorldIT1 : fp.g.WorldITs0)));
-        const f3 P = mk3(q0.x + ht * q0.w, q0.y + ht * q1.x, q0.z + ht * q1.y);      // hitWorldPosition :338-341
-        // steps 1 and 2 of rtggx_set_lights: in range, facing
-        const f3 D = mk3(A.Px - P.x, A.Py - P.y, A.Pz - P.z);
-        const float d2 = dot3(D, D), RR = A.range * A.range;
-        const f3 L = normalize3(D);
-        const float NoL = dot3(N, L);
-        bool lit = d2 >= 1e-6f && d2 < RR && NoL > 0.0f;
-        float spot = 1.0f;
-        if constexpr (CONE) {      // step 3
-          const float c = -dot3(L, mk3(A.Ax, A.Ay, A.Az));
-          const float t = saturatef((c - A.cosOuter) / (A.cosInner - A.cosOuter));
-          spot = t * t;
-          lit = lit && c > A.cosOuter;
-        }
-        f3 Ds = D;
-        if constexpr (SOFT) {      // step 5: a point of the emitting sphere, the slot of this level, image and light
-          if (lit) {
-            uint32_t h = rng(pixel); h += A.frameIndex; h = rng(h);
-            const uint32_t w = rng(h + (A.slotBase + 8u * image) * 0x9E3779B9u);
-            const float u = (float)(w & 0xffffu) / 65536.0f;
-            const uint32_t s = w >> 24;
-            const float z = 1.0f - 2.0f * u, rho = sqrtf(1.0f - z * z);
-            Ds = mk3(D.x + A.radius * (rho * A.cosSin[s]), D.y + A.radius * (rho * A.cosSin[256u + s]), D.z + A.radius * z);
-          }
-        }
-        const float ds2 = dot3(Ds, Ds);
-        const f3 Ls = normalize3(Ds);
-        lit = lit && ds2 >= 1e-6f && dot3(N, Ls) > 0.0f;      // step 6
-        if (lit) {
-          // step 4: the window, the floor
-          const float q = d2 / RR;
-          float win = saturatef(1.0f - q * q); win = win * win;
-          const float m2 = fmaxf(A.radius * A.radius, 1e-4f);
-          const float att = (win * spot) / fmaxf(d2, m2);
-          const f2 rm = getRoughMetal(fp.mat, hInst, a.UV);
-          f3 color = mk3(fp.mat.BaseColors[hInst][0], fp.mat.BaseColors[hInst][1], fp.mat.BaseColors[hInst][2]);
-          f3 term;
-          if (rm.y > 0.5f) {      // the lobe the path uses at this surface: the specular term of the primary lights' pass (lightGenKernel) at the centre direction L
-            const f3 V = mk3(-q0.w, -q1.x, -q1.y);
-            const float r = fmaxf(rm.x, 1.0f / 32.0f);
-            const f3 Hh = normalize3(V + L);
-            const float NoH = saturatef(dot3(N, Hh)), VoH = saturatef(dot3(V, Hh)), NoV = saturatef(dot3(N, V));
-            const float al = r * r, a2 = al * al;
-            const float d = (NoH * a2 - NoH) * NoH + 1.0f;
-            const float Dg = a2 / ((RT_PI * d) * d);
-            const f3 f0 = mk3(lerpf(0.04f, color.x, rm.y), lerpf(0.04f, color.y, rm.y), lerpf(0.04f, color.z, rm.y));
-            const f3 F = fSchlick(f0, VoH);
-            const float vis = visSmith(r, NoV, NoL);
-            const float k = (Dg * vis) * NoL;
-            term = mk3((F.x * k) * (A.Ix * att), (F.y * k) * (A.Iy * att), (F.z * k) * (A.Iz * att));
-          } else {
-            if (diffuseGroup) color = color * (1.0f - rm.y);                 // :607
-            const float g = (NoL / RT_PI) * att;
-            term = mk3((color.x * g) * A.Ix, (color.y * g) * A.Iy, (color.z * g) * A.Iz);      // no x (1 - 0.04) at depth >= 1 (:532)
-          }
-          want = true;
-          tmax = sqrtf(ds2);
-          sr.ox = P.x; sr.oy = P.y; sr.oz = P.z;
-          sr.dx = Ls.x; sr.dy = Ls.y; sr.dz = Ls.z;
-          sr.pixel = pixel; sr.skip = hitId;
-          sr.wx = q2.x * term.x; sr.wy = q2.y * term.y; sr.wz = q2.z * term.z;             // s = T_d * term
-          sr.flags = image;
-        }
-      }
-    }
-    const unsigned long long mask = __ballot(want);
-    if (want) {
-      const size_t k = (size_t)bin * A.binSlots + written + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-      A.outRays[k] = sr; A.outHits[k] = hitKey(tmax, 0xFFFFFFFFu); A.outRange[k] = make_float2(RT_RAY_TMIN, tmax);
-    }
-    written += (uint32_t)__popcll(mask);
-  }
-  if (lane == 0u) A.outCount[bin] = written;
-}
-// One level's hits under the lights: per light with an intensity the generation from the bins q (their rays traced, not yet shaded), the
-// any-hit traversal on the frame's trace grid with this stream's spill part and the rays' own intervals, sunHitAddKernel into sumRefl / sumDiff
-static int launchLightHits(rtggx_context* c, const FrameParams& fp, hipStream_t s, const TraceQueue& bins, const float4* fat0, const float4* fat1, const uint32_t* tileWords,
-                           uint32_t numTiles, int spillPart, bool samples, float* sumRefl, float* sumDiff, uint32_t frameIndex, uint32_t level) {
-  if (numTiles * 4u > c->numBinsMax || c->lightHitSlots != c->binSlots) { setError("rtggx_ray_trace: the queue of rtggx_set_light_reflections does not hold %u bins of %u slots", numTiles * 4u, c->binSlots); return -1; }
-  LightHitGenArgs G;
-  G.rays = bins.rays; G.hits = bins.hits; G.binCount = bins.binCount; G.binSlots = c->binSlots;
-  G.fat0 = fat0; G.fat1 = fat1;
-  G.outRays = (RayRec*)c->lightHitRays.get(); G.outHits = (HitKey*)c->lightHitHits.get(); G.outCount = c->lightHitCount; G.outRange = (float2*)c->lightHitRange.get();
-  G.tileWords = tileWords;
-  G.cosSin = c->cosSinTab; G.frameIndex = frameIndex;
-  const TraceQueue q{G.outRays, G.outHits, G.outCount};
-  SunHitAddArgs D;
-  D.rays = q.rays; D.hits = q.hits; D.binCount = q.binCount; D.binSlots = c->binSlots; D.tileWords = tileWords; D.sumRefl = sumRefl; D.sumDiff = sumDiff;
-  for (uint32_t i = 0; i < c->lights.count; ++i) {
-    const RtggxLight& l = c->lights.l[i];
-    if (!(l.intensity[0] > 0.0f || l.intensity[1] > 0.0f || l.intensity[2] > 0.0f)) continue;      // keeps its index, casts no ray
-    G.Px = l.position[0]; G.Py = l.position[1]; G.Pz = l.position[2]; G.range = l.range;
-    G.Ix = l.intensity[0]; G.Iy = l.intensity[1]; G.Iz = l.intensity[2]; G.radius = l.radius;
-    G.Ax = l.axis[0]; G.Ay = l.axis[1]; G.Az = l.axis[2]; G.cosOuter = l.cos_outer; G.cosInner = l.cos_inner;
-    G.slotBase = 32u + 16u * level + i;
-    const bool cone = l.cos_outer > -1.0f, soft = l.radius > 0.0f;
-    launch(cone ? (soft ? lightHitGenKernel<true, true> : lightHitGenKernel<true, false>) : (soft ? lightHitGenKernel<false, true> : lightHitGenKernel<false, false>),
-           dim3(numTiles), dim3(256), s, nullptr, nullptr, c->dParams + c->slot, G);
-    c->traceRayRange = c->lightHitRange.get();      // (the rays' own intervals, for the launch's duration: launchLights)
-    const int r = launchTrace(c, fp, s, q, c->traceGrid[0], true, c->traceGrid[1], c->traceGrid[2], c->traceGrid[3], -1, nullptr, nullptr, spillPart, true);
-    c->traceRayRange = nullptr;
-    if (r) return r;
-    launch(samples ? sunHitAddKernel<true> : sunHitAddKernel<false>, dim3(numTiles), dim3(256), s, nullptr, nullptr, D);
-    RT_HIP(hipGetLastError());
-  }
   return 0;
 }
 
@@ -1490,7 +1036,7 @@ static int launchShadeSamples(rtggx_context* c, const FrameParams& fp, hipStream
   if (map && (S.rowBegin != 0u || S.rowEnd != c->H)) { setError("rtggx_ray_trace: a sample map on rows [%u,%u) of %u", S.rowBegin, S.rowEnd, c->H); return -1; }
   SampleGenArgsMapped GM;
   static_cast<SampleGenArgs&>(GM) = G; GM.sampleMap = map; GM.sample = 0u;
-  const TraceQueue q{S.rays, S.spawnHits, S.binCount};
+  const TraceQueue q{S.rays, S.spawnHits, S.binCount, S.binSlots, nullptr};
   // rtggx_set_sun_reflections: at every level acc = acc + s_d comes first, then the pass's own add of the paths that end there
   // rtggx_set_light_reflections: then the lights' terms, i ascending, still in front of the pass's own add
   const bool sunHits = c->sun.on && c->sunReflections, lightHits = c->lights.count > 0u && c->lightReflections;
@@ -1505,8 +1051,9 @@ static int launchShadeSamples(rtggx_context* c, const FrameParams& fp, hipStream
         const int r = launchTrace(c, fp, s, q, c->traceGrid[0], true, c->traceGrid[1], c->traceGrid[2], c->traceGrid[3], -1, nullptr, nullptr, spillPart);
         if (r) return r;
       }
-      if (sunHits) { const int r = launchSunHits(c, fp, s, q, S.fat0, S.fat1, S.tileWords, numTiles, spillPart, true, S.accRefl, S.accDiff, fp.g.FrameIndex * N + k, level); if (r) return r; }
-      if (lightHits) { const int r = launchLightHits(c, fp, s, q, S.fat0, S.fat1, S.tileWords, numTiles, spillPart, true, S.accRefl, S.accDiff, fp.g.FrameIndex * N + k, level); if (r) return r; }
+      const HitPass hp{s, q, S.fat0, S.fat1, S.tileWords, numTiles, spillPart, true, S.accRefl, S.accDiff, fp.g.FrameIndex * N + k, level};
+      if (sunHits) { const int r = launchSunHits(c, fp, hp); if (r) return r; }
+      if (lightHits) { const int r = launchLightHits(c, fp, hp); if (r) return r; }
       launch(level + 1u < depth ? (wide ? shadeKernel<1, SHADE_SPAWN_ACCUM, true> : shadeKernel<1, SHADE_SPAWN_ACCUM>) : shadeKernel<1, SHADE_ACCUM>, dim3(numTiles), dim3(256), s, nullptr, nullptr, sp + k, S);
       S.carryMask = 0u;      // (carried over once, by the first pass)
       RT_HIP(hipGetLastError());
@@ -1566,25 +1113,20 @@ int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent
     sums[0] = c->sunHitSums; sums[1] = c->sunHitSums + 4u * (size_t)c->W * c->H;
   }
   for (uint32_t level = 0; level < depth; ++level) {
-    const TraceQueue q{S.rays, S.spawnHits, S.binCount};
+    const TraceQueue q{S.rays, S.spawnHits, S.binCount, S.binSlots, nullptr};
     if (level > 0) {
       const int r = launchTrace(c, fp, s, q, c->traceGrid[0], true, c->traceGrid[1], c->traceGrid[2], c->traceGrid[3], -1, nullptr, nullptr, spillPart);
       if (r) return r;
       S.carryMask = 0u;      // (carried over once, by the first pass)
     }
-    if (sunHits) { const int r = launchSunHits(c, fp, s, q, S.fat0, S.fat1, S.tileWords, numTiles, spillPart, false, sums[0], sums[1], fp.g.FrameIndex, level); if (r) return r; }
-    if (lightHits) { const int r = launchLightHits(c, fp, s, q, S.fat0, S.fat1, S.tileWords, numTiles, spillPart, false, sums[0], sums[1], fp.g.FrameIndex, level); if (r) return r; }
+    const HitPass hp{s, q, S.fat0, S.fat1, S.tileWords, numTiles, spillPart, false, sums[0], sums[1], fp.g.FrameIndex, level};
+    if (sunHits) { const int r = launchSunHits(c, fp, hp); if (r) return r; }
+    if (lightHits) { const int r = launchLightHits(c, fp, hp); if (r) return r; }
     const int pass = level + 1u < depth ? SHADE_SPAWN : level == 0 ? SHADE_FINAL : SHADE_FINAL_DEEP;
     launch(pass == SHADE_SPAWN && c->sampleSet > RTGGX_MIN_SAMPLE_SET ? kShadeSpawnWide[quad] : kShade[pass][quad], dim3(grid), dim3(256), s, nullptr, pass == SHADE_SPAWN || anyHits ? nullptr : done, dfp, S);
     RT_HIP(hipGetLastError());
   }
-  if (anyHits) {
-    SunHitResolveArgs R;
-    R.sumRefl = (float4*)sums[0]; R.sumDiff = (float4*)sums[1]; R.reflOut = set.rtRefl; R.diffOut = set.rtDiff;
-    R.tileWords = S.tileWords; R.tilesX = tilesX; R.rowBegin = rb; R.rowEnd = re;
-    launch(sunHitResolveKernel, dim3(numTiles), dim3(256), s, nullptr, done, dfp, R);
-    RT_HIP(hipGetLastError());
-  }
+  if (anyHits) return launchSunHitResolve(c, s, c->sunHitSums, S.tileWords, tilesX, rb, re, done);
   return 0;
 }
 
@@ -1602,346 +1144,6 @@ int launchReconstruct(rtggx_context* c, const FrameParams& fp, hipStream_t s) {
   R.carryMask = c->genCarriesDiff ? 0u : metal; R.diffMask = ~metal & 3u;
   R.tileWords = c->tileWords(rb, re); R.tilesX = tilesX; R.rowBegin = rb; R.rowEnd = re;
   hipLaunchKernelGGL(reconstructKernel, dim3(numTiles), dim3(256), 0, s, c->dParams + c->slot, R);
-  RT_HIP(hipGetLastError());
-  return 0;
-}
-
-// ---- the sun (rtggx_set_sun; include/rtggx.h has the per-pixel rule, DESIGN.md section 9 "Sun and shadow rays") ------------------------------
-// Three kernels on the stream that has this frame's two traced images complete (frame.hip rtggx_ray_trace): sunGenKernel derives the primary
-// surface once more from the visibility word -- rayGenKernel's arithmetic, as sampleGenKernel does --, and where the surface faces the sun
-// compacts one shadow ray into the wave's bin of the sun's own queue, with everything the add needs: the specular term in the record's weight,
-// NoL in its flags word.  The any-hit variant of the trace kernel (trace.hip) leaves an unoccluded ray's key a miss.  sunAddKernel walks the
-// bins: one lane per slot, and an unoccluded one adds its terms to its pixel's packed words (a pixel has at most one slot: no two lanes meet).
-#ifndef RT_SUN_CLOSEST
-#define RT_SUN_CLOSEST 0      // measurement: 1 traces the shadow queue with the closest-hit kernel (the same images; profiles/r14_d_sun_cost.txt)
-#endif
-struct SunGenArgs {
-  const unsigned long long* visDepth; const float4* fat0; const float4* fat1;
-  RayRec* rays; HitKey* hits; uint32_t* binCount;
-  const uint32_t* tileWords; uint32_t tilesX, rowBegin, rowEnd;
-  float Lx, Ly, Lz, Ex, Ey, Ez;
-};
-struct SunGenArgsSoft : SunGenArgs { SunDiskArgs disk; };      // rtggx_set_sun_angle: slot 0, the frame's own index (the constants')
-template <bool SOFT>
-__global__ void __launch_bounds__(256) sunGenKernel(const FrameParams* __restrict__ fpp, std::conditional_t<SOFT, SunGenArgsSoft, SunGenArgs> A) {
-  const FrameParams& fp = *fpp;
-  const uint32_t tile = blockIdx.x;
-  { uint32_t word;
-    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(word) : "s"(A.tileWords), "s"(tile * 4u) : "memory");
-    if (word == 0u) return; }
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  const uint32_t px = (tile % A.tilesX) * 16 + (wave & 1u) * 8 + (lane & 7u);
-  const uint32_t py = A.rowBegin + (tile / A.tilesX) * 16 + (wave >> 1) * 8 + (lane >> 3);
-  bool want = false;
-  RayRec rr;
-  if (px < fp.W && py < A.rowEnd) {
-    const uint32_t W = fp.W, H = fp.H;
-    const size_t pix = (size_t)py * W + px;
-    uint32_t visibility = (uint32_t)A.visDepth[pix];
-    if (visibility > 0) {      // getPrimarySurface :277-333, the covered branch, as in sampleGenKernel
-      --visibility;
-      const uint32_t inst = visibility >> 24;
-      uint32_t prim = visibility & 0xFFFFFFu;
-      asm volatile("" : "+v"(prim));      // see shadeKernel
-      f2 screenPos; screenPos.x = ((float)px + 0.5f) / (float)W * 2.0f - 1.0f; screenPos.y = ((float)py + 0.5f) / (float)H * 2.0f - 1.0f;
-      screenPos.y = -screenPos.y;
-      const f3 eye = mk3(fp.rg.EyePt[0], fp.rg.EyePt[1], fp.rg.EyePt[2]);
-      const Tri3 v = getVertices(inst ? A.fat1 : A.fat0, prim);
-      const M4 wvp = cbLoad4x4(fp.g.WorldViewProjs[inst]);
-      f4 p[3];
-      for (int k = 0; k < 3; ++k) p[k] = mulPoint(v.pos[k], wvp);
-      screenPos.x -= fp.rg.ProjBias[0]; screenPos.y -= fp.rg.ProjBias[1];
-      const f2 bary = calcBarycentrics(p, screenPos);
-      const Attrib a = interpAttrib(v, bary.x, bary.y);
-      const f3 color = mk3(fp.mat.BaseColors[inst][0], fp.mat.BaseColors[inst][1], fp.mat.BaseColors[inst][2]);
-      const f2 rghMtl = getRoughMetal(fp.mat, inst, a.UV);
-      const f4 P4 = mulPoint(a.Pos, cbLoad4x3(fp.g.Worlds[inst]));
-      const f3 P = mk3(P4.x, P4.y, P4.z);
-      const f3 N = normalize3(mulDir(a.Nrm, cbLoad3x3(inst ? fp.g.WorldIT1 : fp.g.WorldITs0)));
-      const f3 V = normalize3(eye - P);
-      const f3 L = mk3(A.Lx, A.Ly, A.Lz);
-      const float NoL = dot3(N, L);
-      f3 Ls = L;      // SOFT: toward the point of the disk the pixel draws this frame; below the horizon there is no ray and no term
-      bool facing = NoL > 0.0f;
-      if constexpr (SOFT) { if (facing) { Ls = sunDiskDirection(A.disk, L, (uint32_t)pix, fp.g.FrameIndex, 0u); facing = dot3(N, Ls) > 0.0f; } }
-      if (facing) {
-        // F D Vis NoL E with the roughness floored at 1/32: a mirror under a delta light has no finite answer
-        const float r = fmaxf(rghMtl.x, 1.0f / 32.0f);
-        const f3 Hh = normalize3(V + L);
-        const float NoH = saturatef(dot3(N, Hh)), VoH = saturatef(dot3(V, Hh)), NoV = saturatef(dot3(N, V));
-        const float al = r * r, a2 = al * al;
-        const float d = (NoH * a2 - NoH) * NoH + 1.0f;
-        const float D = a2 / ((RT_PI * d) * d);
-        const f3 f0 = mk3(lerpf(0.04f, color.x, rghMtl.y), lerpf(0.04f, color.y, rghMtl.y), lerpf(0.04f, color.z, rghMtl.y));
-        const f3 F = fSchlick(f0, VoH);
-        const float vis = visSmith(r, NoV, NoL);
-        const float k = (D * vis) * NoL;
-        want = true;
-        rr.ox = P.x; rr.oy = P.y; rr.oz = P.z; rr.dx = Ls.x; rr.dy = Ls.y; rr.dz = Ls.z;
-        rr.pixel = (uint32_t)pix; rr.skip = (inst << 24) | prim;
-        rr.wx = (F.x * k) * A.Ex; rr.wy = (F.y * k) * A.Ey; rr.wz = (F.z * k) * A.Ez;
-        rr.flags = __float_as_uint(NoL);
-      }
-    }
-  }
-  const uint32_t bin = blockIdx.x * 4u + wave;
-  const unsigned long long mask = __ballot(want), below = (1ull << lane) - 1ull;
-  if (want) { const size_t k = (size_t)bin * RT_BIN_MIN + (uint32_t)__popcll(mask & below); A.rays[k] = rr; A.hits[k] = hitKey(RT_RAY_TMAX, 0xFFFFFFFFu); }
-  if (lane == 0) A.binCount[bin] = (uint32_t)__popcll(mask);
-}
-struct SunAddArgs {
-  const RayRec* rays; const HitKey* hits; const uint32_t* binCount; const uint32_t* tileWords;
-  uint32_t* reflOut; uint32_t* diffOut; float Ex, Ey, Ez;
-};
-__global__ void __launch_bounds__(256) sunAddKernel(const FrameParams* __restrict__ fpp, SunAddArgs A) {
-  const FrameParams& fp = *fpp;
-  { uint32_t word;
-    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(word) : "s"(A.tileWords), "s"(blockIdx.x * 4u) : "memory");
-    if (word == 0u) return; }
-  const uint32_t bin = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-  if (lane >= A.binCount[bin]) return;
-  const size_t k = (size_t)bin * RT_BIN_MIN + lane;
-  if (hitKeyId(A.hits[k]) != 0xFFFFFFFFu) return;      // occluded: both words stay
-  const RayRec rr = A.rays[k];
-  const uint32_t inst = rr.skip >> 24;
-  const f3 spec = mk3(rr.wx, rr.wy, rr.wz);
-  A.reflOut[rr.pixel] = packR11G11B10F(unpackR11G11B10F(A.reflOut[rr.pixel]) + spec);
-  if (fp.mat.RoughMetals[inst][1] < 1.0f) {      // rghMtl.y < 1 is the instance's constant (launchShade); elsewhere RayTracingOut1 is a carry-over and stays
-    const float w = __uint_as_float(rr.flags) / RT_PI;
-    const f3 diff = mk3(((fp.mat.BaseColors[inst][0] * (1.0f - 0.04f)) * w) * A.Ex, ((fp.mat.BaseColors[inst][1] * (1.0f - 0.04f)) * w) * A.Ey,
-                        ((fp.mat.BaseColors[inst][2] * (1.0f - 0.04f)) * w) * A.Ez);
-    A.diffOut[rr.pixel] = packR11G11B10F(unpackR11G11B10F(A.diffOut[rr.pixel]) + diff);
-  }
-}
-int launchSun(rtggx_context* c, const FrameParams& fp, hipStream_t s) {
-  uint32_t rb, re;
-  passRows(fp, ROWS_GBUFFER, rb, re);
-  if (re <= rb) return 0;
-  const uint32_t tilesX = (fp.W + 15) / 16, tilesY = (re - rb + 15) / 16, numTiles = tilesX * tilesY;
-  if (numTiles * 4u > c->numBinsMax || !c->sunRays) { setError("rtggx_ray_trace: the sun's queue does not hold %u bins", numTiles * 4u); return -1; }
-  const InputSet& set = c->cur();
-  const rtggx_context::Sun& sun = c->sun;
-  SunGenArgs G;
-  G.visDepth = c->curVis().depth; G.fat0 = c->mesh[0].fat; G.fat1 = c->mesh[1].fat;
-  G.rays = (RayRec*)c->sunRays.get(); G.hits = (HitKey*)c->sunHits.get(); G.binCount = c->sunCount;
-  G.tileWords = c->tileWords(rb, re); G.tilesX = tilesX; G.rowBegin = rb; G.rowEnd = re;
-  G.Lx = sun.L[0]; G.Ly = sun.L[1]; G.Lz = sun.L[2]; G.Ex = sun.E[0]; G.Ey = sun.E[1]; G.Ez = sun.E[2];
-  const FrameParams* const dfp = c->dParams + c->slot;
-  if (c->sunAngle.degrees > 0.0f) {      // rtggx_set_sun_angle
-    SunGenArgsSoft GS;
-    static_cast<SunGenArgs&>(GS) = G;
-    GS.disk = SunDiskArgs{sun.T[0], sun.T[1], sun.T[2], sun.B[0], sun.B[1], sun.B[2], c->sunAngle.k, c->cosSinTab, 0u, 0u};
-    launch(sunGenKernel<true>, dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, GS);
-  } else launch(sunGenKernel<false>, dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, G);
-  // the bins have RT_BIN_MIN slots whatever the frame's have: the launch is told so through the context's slot count for its duration.  Spill part 2
-  // is the main stream's (launchShade): the launches that use it are in this stream's order, and nothing beside the stream touches it
-  const TraceQueue q{(const RayRec*)c->sunRays.get(), (HitKey*)c->sunHits.get(), c->sunCount};
-  const uint32_t frameSlots = c->binSlots;
-  c->binSlots = RT_BIN_MIN;
-  const int r = launchTrace(c, fp, s, q, numTiles * 4u, true, tilesX, tilesY, c->traceGrid[3], -1, nullptr, nullptr, 2, !RT_SUN_CLOSEST);
-  c->binSlots = frameSlots;
-  if (r) return r;
-  SunAddArgs S;
-  S.rays = q.rays; S.hits = q.hits; S.binCount = q.binCount; S.tileWords = G.tileWords;
-  S.reflOut = set.rtRefl; S.diffOut = set.rtDiff; S.Ex = G.Ex; S.Ey = G.Ey; S.Ez = G.Ez;
-  launch(sunAddKernel, dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, S);
-  RT_HIP(hipGetLastError());
-  return 0;
-}
-
-// ---- local lights (rtggx_set_lights; include/rtggx.h has the per-pixel rule, DESIGN.md section 9 "Local lights") -----------------------------
-// The sun's pass with a light inside the scene: per light, in index order on the main stream, lightGenKernel derives the primary surface as
-// sunGenKernel does, runs steps 1-6 of the rule and compacts one shadow ray into the wave's bin of ONE queue all lights share -- the specular
-// term in the record's weight, g = (NoL / pi) att in its flags word, the ray's own interval (1e-5, tmax) in a float2 array beside the queue --;
-// the any-hit traversal reads that interval through TraceArgs::tRange; lightAddKernel, one lane per slot, adds an unoccluded ray's terms to the
-// pixel's fp32 sums (a pixel has at most one slot per light and the lights follow each other in stream order: no two lanes meet, no atomics,
-// the order of a sum is the order of the lights).  Behind the last light sunHitResolveKernel packs the sums into the words and leaves them zero.
-// CONE and SOFT change the instruction stream: a context with point lights of radius 0 pays for neither the cone nor the hash.
-struct LightGenArgs {
-  const unsigned long long* visDepth; const float4* fat0; const float4* fat1;
-  RayRec* rays; HitKey* hits; uint32_t* binCount; float2* tRange;
-  const uint32_t* tileWords; uint32_t tilesX, rowBegin, rowEnd;
-  float Px, Py, Pz, range, Ix, Iy, Iz, radius, Ax, Ay, Az, cosOuter, cosInner;
-  const float* cosSin; uint32_t slot;      // SOFT: the 256-entry table, and 16 + i
-};
-template <bool CONE, bool SOFT>
-__global__ void __launch_bounds__(256) lightGenKernel(const FrameParams* __restrict__ fpp, LightGenArgs A) {
-  const FrameParams& fp = *fpp;
-  const uint32_t tile = blockIdx.x;
-  { uint32_t word;
-    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(word) : "s"(A.tileWords), "s"(tile * 4u) : "memory");
-    if (word == 0u) return; }
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  const uint32_t px = (tile % A.tilesX) * 16 + (wave & 1u) * 8 + (lane & 7u);
-  const uint32_t py = A.rowBegin + (tile / A.tilesX) * 16 + (wave >> 1) * 8 + (lane >> 3);
-  bool want = false;
-  RayRec rr;
-  float tmax = 0.0f;
-  if (px < fp.W && py < A.rowEnd) {
-    const uint32_t W = fp.W, H = fp.H;
-    const size_t pix = (size_t)py * W + px;
-    uint32_t visibility = (uint32_t)A.visDepth[pix];
-    if (visibility > 0) {      // step 0: getPrimarySurface :277-333, the covered branch, as in sunGenKernel
-      --visibility;
-      const uint32_t inst = visibility >> 24;
-      uint32_t prim = visibility & 0xFFFFFFu;
-      asm volatile("" : "+v"(prim));      // see shadeKernel
-      f2 screenPos; screenPos.x = ((float)px + 0.5f) / (float)W * 2.0f - 1.0f; screenPos.y = ((float)py + 0.5f) / (float)H * 2.0f - 1.0f;
-      screenPos.y = -screenPos.y;
-      const f3 eye = mk3(fp.rg.EyePt[0], fp.rg.EyePt[1], fp.rg.EyePt[2]);
-      const Tri3 v = getVertices(inst ? A.fat1 : A.fat0, prim);
-      const M4 wvp = cbLoad4x4(fp.g.WorldViewProjs[inst]);
-      f4 p[3];
-      for (int k = 0; k < 3; ++k) p[k] = mulPoint(v.pos[k], wvp);
-      screenPos.x -= fp.rg.ProjBias[0]; screenPos.y -= fp.rg.ProjBias[1];
-      const f2 bary = calcBarycentrics(p, screenPos);
-      const Attrib a = interpAttrib(v, bary.x, bary.y);
-      const f3 color = mk3(fp.mat.BaseColors[inst][0], fp.mat.BaseColors[inst][1], fp.mat.BaseColors[inst][2]);
-      const f2 rghMtl = getRoughMetal(fp.mat, inst, a.UV);
-      const f4 P4 = mulPoint(a.Pos, cbLoad4x3(fp.g.Worlds[inst]));
-      const f3 P = mk3(P4.x, P4.y, P4.z);
-      const f3 N = normalize3(mulDir(a.Nrm, cbLoad3x3(inst ? fp.g.WorldIT1 : fp.g.WorldITs0)));
-      const f3 V = normalize3(eye - P);
-      // steps 1 and 2: in range, facing
-      const f3 D = mk3(A.Px - P.x, A.Py - P.y, A.Pz - P.z);
-      const float d2 = dot3(D, D), RR = A.range * A.range;
-      const f3 L = normalize3(D);
-      const float NoL = dot3(N, L);
-      bool lit = d2 >= 1e-6f && d2 < RR && NoL > 0.0f;
-      float spot = 1.0f;
-      if constexpr (CONE) {      // step 3
-        const float c = -dot3(L, mk3(A.Ax, A.Ay, A.Az));
-        const float t = saturatef((c - A.cosOuter) / (A.cosInner - A.cosOuter));
-        spot = t * t;
-        lit = lit && c > A.cosOuter;
-      }
-      f3 Ds = D;
-      if constexpr (SOFT) {      // step 5: a point of the emitting sphere, uniform over its surface
-        if (lit) {
-          uint32_t h = rng((uint32_t)pix); h += fp.g.FrameIndex; h = rng(h);
-          const uint32_t w = rng(h + A.slot * 0x9E3779B9u);
-          const float u = (float)(w & 0xffffu) / 65536.0f;
-          const uint32_t s = w >> 24;
-          const float z = 1.0f - 2.0f * u, rho = sqrtf(1.0f - z * z);
-          Ds = mk3(D.x + A.radius * (rho * A.cosSin[s]), D.y + A.radius * (rho * A.cosSin[256u + s]), D.z + A.radius * z);
-        }
-      }
-      const float ds2 = dot3(Ds, Ds);
-      const f3 Ls = normalize3(Ds);
-      lit = lit && ds2 >= 1e-6f && dot3(N, Ls) > 0.0f;      // step 6
-      if (lit) {
-        // step 4: the window, the floor, E = I att
-        const float q = d2 / RR;
-        float win = saturatef(1.0f - q * q); win = win * win;
-        const float m2 = fmaxf(A.radius * A.radius, 1e-4f);
-        const float att = (win * spot) / fmaxf(d2, m2);
-        // step 8: sunGenKernel's term at the centre direction L
-        const float r = fmaxf(rghMtl.x, 1.0f / 32.0f);
-        const f3 Hh = normalize3(V + L);
-        const float NoH = saturatef(dot3(N, Hh)), VoH = saturatef(dot3(V, Hh)), NoV = saturatef(dot3(N, V));
-        const float al = r * r, a2 = al * al;
-        const float d = (NoH * a2 - NoH) * NoH + 1.0f;
-        const float Dg = a2 / ((RT_PI * d) * d);
-        const f3 f0 = mk3(lerpf(0.04f, color.x, rghMtl.y), lerpf(0.04f, color.y, rghMtl.y), lerpf(0.04f, color.z, rghMtl.y));
-        const f3 F = fSchlick(f0, VoH);
-        const float vis = visSmith(r, NoV, NoL);
-        const float k = (Dg * vis) * NoL;
-        want = true;
-        tmax = sqrtf(ds2);
-        rr.ox = P.x; rr.oy = P.y; rr.oz = P.z; rr.dx = Ls.x; rr.dy = Ls.y; rr.dz = Ls.z;
-        rr.pixel = (uint32_t)pix; rr.skip = (inst << 24) | prim;
-        rr.wx = (F.x * k) * (A.Ix * att); rr.wy = (F.y * k) * (A.Iy * att); rr.wz = (F.z * k) * (A.Iz * att);
-        rr.flags = __float_as_uint((NoL / RT_PI) * att);
-      }
-    }
-  }
-  const uint32_t bin = blockIdx.x * 4u + wave;
-  const unsigned long long mask = __ballot(want), below = (1ull << lane) - 1ull;
-  if (want) {
-    const size_t k = (size_t)bin * RT_BIN_MIN + (uint32_t)__popcll(mask & below);
-    A.rays[k] = rr; A.hits[k] = hitKey(tmax, 0xFFFFFFFFu); A.tRange[k] = make_float2(RT_RAY_TMIN, tmax);
-  }
-  if (lane == 0) A.binCount[bin] = (uint32_t)__popcll(mask);
-}
-struct LightAddArgs {
-  const RayRec* rays; const HitKey* hits; const uint32_t* binCount; const uint32_t* tileWords;
-  float4* sumRefl; float4* sumDiff; float Ix, Iy, Iz;
-};
-__global__ void __launch_bounds__(256) lightAddKernel(const FrameParams* __restrict__ fpp, LightAddArgs A) {
-  const FrameParams& fp = *fpp;
-  { uint32_t word;
-    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(word) : "s"(A.tileWords), "s"(blockIdx.x * 4u) : "memory");
-    if (word == 0u) return; }
-  const uint32_t bin = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-  if (lane >= A.binCount[bin]) return;
-  const size_t k = (size_t)bin * RT_BIN_MIN + lane;
-  if (hitKeyId(A.hits[k]) != 0xFFFFFFFFu) return;      // occluded: no term
-  const RayRec rr = A.rays[k];
-  const uint32_t inst = rr.skip >> 24;
-  const float4 s0 = A.sumRefl[rr.pixel];
-  A.sumRefl[rr.pixel] = make_float4(s0.x + rr.wx, s0.y + rr.wy, s0.z + rr.wz, s0.w + 1.0f);
-  if (fp.mat.RoughMetals[inst][1] < 1.0f) {      // rghMtl.y < 1 is the instance's constant (launchShade); elsewhere RayTracingOut1 is a carry-over and stays
-    const float g = __uint_as_float(rr.flags);
-    const float4 s1 = A.sumDiff[rr.pixel];
-    A.sumDiff[rr.pixel] = make_float4(s1.x + ((fp.mat.BaseColors[inst][0] * (1.0f - 0.04f)) * g) * A.Ix, s1.y + ((fp.mat.BaseColors[inst][1] * (1.0f - 0.04f)) * g) * A.Iy,
-                                      s1.z + ((fp.mat.BaseColors[inst][2] * (1.0f - 0.04f)) * g) * A.Iz, s1.w + 1.0f);
-  }
-}
-// What the lights need, from the first frame that has some: the queue, its intervals and counts, the sums
-static int allocLights(rtggx_context* c) {
-  bool cleared = false;
-  const size_t slots = (size_t)c->numBinsMax * RT_BIN_MIN;
-  if (!c->lightRays) RT_HIP(alloc(c->lightRays, slots * sizeof(RayRec)));
-  if (!c->lightHits) RT_HIP(alloc(c->lightHits, slots * sizeof(HitKey)));
-  if (!c->lightRange) RT_HIP(alloc(c->lightRange, slots * sizeof(float2)));
-  if (!c->lightCount) { RT_HIP(allocFilled(c->lightCount, (size_t)c->numBinsMax)); cleared = true; }
-  if (!c->lightSums) { RT_HIP(allocFilled(c->lightSums, (size_t)c->W * c->H * 8u)); cleared = true; }
-  if (cleared) RT_HIP(hipStreamSynchronize(nullptr));      // (the clears run on the null stream, which this context's streams are not ordered against)
-  return 0;
-}
-int launchLights(rtggx_context* c, const FrameParams& fp, hipStream_t s) {
-  uint32_t rb, re;
-  passRows(fp, ROWS_GBUFFER, rb, re);
-  if (re <= rb) return 0;
-  const uint32_t tilesX = (fp.W + 15) / 16, tilesY = (re - rb + 15) / 16, numTiles = tilesX * tilesY;
-  if (numTiles * 4u > c->numBinsMax) { setError("rtggx_ray_trace: the lights' queue does not hold %u bins", numTiles * 4u); return -1; }
-  { const int r = allocLights(c); if (r) return r; }
-  const InputSet& set = c->cur();
-  const FrameParams* const dfp = c->dParams + c->slot;
-  LightGenArgs G;
-  G.visDepth = c->curVis().depth; G.fat0 = c->mesh[0].fat; G.fat1 = c->mesh[1].fat;
-  G.rays = (RayRec*)c->lightRays.get(); G.hits = (HitKey*)c->lightHits.get(); G.binCount = c->lightCount; G.tRange = (float2*)c->lightRange.get();
-  G.tileWords = c->tileWords(rb, re); G.tilesX = tilesX; G.rowBegin = rb; G.rowEnd = re;
-  G.cosSin = c->cosSinTab;
-  const TraceQueue q{G.rays, G.hits, G.binCount};
-  LightAddArgs D;
-  D.rays = q.rays; D.hits = q.hits; D.binCount = q.binCount; D.tileWords = G.tileWords;
-  D.sumRefl = (float4*)c->lightSums.get(); D.sumDiff = D.sumRefl + (size_t)c->W * c->H;
-  for (uint32_t i = 0; i < c->lights.count; ++i) {
-    const RtggxLight& l = c->lights.l[i];
-    if (!(l.intensity[0] > 0.0f || l.intensity[1] > 0.0f || l.intensity[2] > 0.0f)) continue;      // keeps its index, casts no ray
-    G.Px = l.position[0]; G.Py = l.position[1]; G.Pz = l.position[2]; G.range = l.range;
-    G.Ix = l.intensity[0]; G.Iy = l.intensity[1]; G.Iz = l.intensity[2]; G.radius = l.radius;
-    G.Ax = l.axis[0]; G.Ay = l.axis[1]; G.Az = l.axis[2]; G.cosOuter = l.cos_outer; G.cosInner = l.cos_inner;
-    G.slot = 16u + i;
-    const bool cone = l.cos_outer > -1.0f, soft = l.radius > 0.0f;
-    launch(cone ? (soft ? lightGenKernel<true, true> : lightGenKernel<true, false>) : (soft ? lightGenKernel<false, true> : lightGenKernel<false, false>),
-           dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, G);
-    // the sun's launch (launchSun): bins of RT_BIN_MIN slots and spill part 2, told through the context for the launch's duration -- and the
-    // rays' own intervals beside them
-    const uint32_t frameSlots = c->binSlots;
-    c->binSlots = RT_BIN_MIN; c->traceRayRange = c->lightRange.get();
-    const int r = launchTrace(c, fp, s, q, numTiles * 4u, true, tilesX, tilesY, c->traceGrid[3], -1, nullptr, nullptr, 2, true);
-    c->binSlots = frameSlots; c->traceRayRange = nullptr;
-    if (r) return r;
-    D.Ix = G.Ix; D.Iy = G.Iy; D.Iz = G.Iz;
-    launch(lightAddKernel, dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, D);
-    RT_HIP(hipGetLastError());
-  }
-  SunHitResolveArgs R;
-  R.sumRefl = D.sumRefl; R.sumDiff = D.sumDiff; R.reflOut = set.rtRefl; R.diffOut = set.rtDiff;
-  R.tileWords = G.tileWords; R.tilesX = tilesX; R.rowBegin = rb; R.rowEnd = re;
-  launch(sunHitResolveKernel, dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, R);
   RT_HIP(hipGetLastError());
   return 0;
 }
@@ -1988,9 +1190,8 @@ int launchTraceRays(rtggx_context* c, const FrameParams& fp, const float* dRays,
   // the rays' own (TMin, TMax): one float2 per slot, kept for the context's lifetime once a caller has used this entry point
   if (!c->testRayRange) RT_HIP(alloc(c->testRayRange, (size_t)c->numBinsMax * RT_BIN * sizeof(float2)));
   hipLaunchKernelGGL(fillTestQueue, dim3((n + 255) / 256), dim3(256), 0, s, dRays, n, c->binSlots, (RayRec*)set.rayQueue.get(), (HitKey*)set.hitQueue.get(), set.binCount, (float2*)c->testRayRange.get());
-  c->traceRayRange = c->testRayRange;
-  const TraceQueue q{(const RayRec*)set.rayQueue.get(), (HitKey*)set.hitQueue.get(), set.binCount};
-  { const int r = launchTrace(c, fp, s, q, numBins, false, 0u, 0u, chooseSliceShift(c, false, numBins), -1); c->traceRayRange = nullptr; if (r) return r; }
+  const TraceQueue q{(const RayRec*)set.rayQueue.get(), (HitKey*)set.hitQueue.get(), set.binCount, c->binSlots, (const float2*)c->testRayRange.get()};
+  { const int r = launchTrace(c, fp, s, q, numBins, false, 0u, 0u, chooseSliceShift(c, false, numBins), -1); if (r) return r; }
   hipLaunchKernelGGL(exportTestHits, dim3((n + 255) / 256), dim3(256), 0, s, c->dParams + c->slot, (const RayRec*)set.rayQueue.get(), (const HitKey*)set.hitQueue.get(), n,
                      (const float4*)c->mesh[0].fat, (const float4*)c->mesh[1].fat, dOut);
   RT_HIP(hipGetLastError());
@@ -2011,9 +1212,8 @@ int launchTraceOcclusion(rtggx_context* c, const FrameParams& fp, const float* d
   RT_HIP(hipMemsetAsync(set.binCount, 0, (size_t)numBins * 4, s));
   if (!c->testRayRange) RT_HIP(alloc(c->testRayRange, (size_t)c->numBinsMax * RT_BIN * sizeof(float2)));
   hipLaunchKernelGGL(fillTestQueue, dim3((n + 255) / 256), dim3(256), 0, s, dRays, n, c->binSlots, (RayRec*)set.rayQueue.get(), (HitKey*)set.hitQueue.get(), set.binCount, (float2*)c->testRayRange.get());
-  c->traceRayRange = c->testRayRange;
-  const TraceQueue q{(const RayRec*)set.rayQueue.get(), (HitKey*)set.hitQueue.get(), set.binCount};
-  { const int r = launchTrace(c, fp, s, q, numBins, false, 0u, 0u, chooseSliceShift(c, false, numBins), -1, nullptr, nullptr, -1, true); c->traceRayRange = nullptr; if (r) return r; }
+  const TraceQueue q{(const RayRec*)set.rayQueue.get(), (HitKey*)set.hitQueue.get(), set.binCount, c->binSlots, (const float2*)c->testRayRange.get()};
+  { const int r = launchTrace(c, fp, s, q, numBins, false, 0u, 0u, chooseSliceShift(c, false, numBins), -1, nullptr, nullptr, -1, true); if (r) return r; }
   hipLaunchKernelGGL(exportOcclusion, dim3((n + 255) / 256), dim3(256), 0, s, (const HitKey*)set.hitQueue.get(), n, dOut);
   RT_HIP(hipGetLastError());
   return 0;

@@ -39,7 +39,7 @@ namespace rt {
 
 // 48-byte ray record (three 16-byte words; the traversal reads the first two).  Every ray of a frame has the shader's interval
 // (TMin, TMax) = (1e-5, 10000) (RayTracing.hlsl:183-198 with the literals of :441,:504): it is not stored.  Rays handed in through
-// rtggx_trace_rays bring their own interval in a side array (TraceArgs::tRange).  Round 1's record was 64 bytes: written by ray
+// rtggx_trace_rays, and the shadow rays of the local lights, bring their own interval in a side array (TraceQueue::tRange).  Round 1's record was 64 bytes: written by ray
 // generation, read by the traversal and by shading, a sixth of the frame's memory traffic.
 #define RT_RAY_TMIN 1e-5f
 #define RT_RAY_TMAX 10000.0f
@@ -76,9 +76,37 @@ uint32_t chooseSliceShift(rtggx_context* c, bool countRays, uint32_t numBins);
 // WHICH triangle and t the key names is unspecified: the smallest key among the jobs that happened to reach a triangle, different from run to run.
 // A job leaves its ray at the first accepted triangle and drops its pending subtrees; its interval never shrinks.  The launch never touches
 // the level-0 traversal's cost record (binWork, split list: pass splitCap = -1), its time stamps or its counter read-backs.
-struct TraceQueue { const RayRec* rays; HitKey* hits; const uint32_t* binCount; };
+// binSlots: the slots of each of the queue's bins; tRange: the rays' own (TMin, TMax), one float2 per slot, or null -- every ray has the frame's.
+struct TraceQueue { const RayRec* rays; HitKey* hits; const uint32_t* binCount; uint32_t binSlots; const float2* tRange; };
 #define RT_SPILL_PARTS 3u
 int launchTrace(rtggx_context* c, const FrameParams& fp, hipStream_t s, const TraceQueue& q, uint32_t numBins, bool countRays, uint32_t tilesX, uint32_t tilesY, uint32_t sliceShift,
                 int splitCap, hipEvent_t start = nullptr, hipEvent_t stop = nullptr, int spillPart = -1, bool anyHit = false);
+
+// rt::ShadowQueue (rtggx_context.h).  ensure: the queue holds numBins bins of binSlots slots -- what it held at another size is released
+// first; locals, then members when all exist (rt_owned_hip.h) -- and its counts are zero when new: `filled` is then set, and the caller owes the
+// null stream one synchronise behind all his fills.  release: the arrays sized by slots (the counts depend on the bins alone and stay).
+inline int ShadowQueue::ensure(uint32_t numBins, uint32_t binSlots, bool withRange, bool& filled) {
+  if (!rays || !hits || (withRange && !range) || slots != binSlots) {
+    release();
+    const size_t n = (size_t)numBins * binSlots;
+    DevBuf<void> r, h, g;
+    RT_HIP(alloc(r, n * sizeof(RayRec)));
+    RT_HIP(alloc(h, n * sizeof(HitKey)));
+    if (withRange) RT_HIP(alloc(g, n * sizeof(float2)));
+    rays = std::move(r); hits = std::move(h); range = std::move(g); slots = binSlots;
+  }
+  if (!count) { RT_HIP(allocFilled(count, (size_t)numBins)); filled = true; }
+  return 0;
+}
+inline void ShadowQueue::release() { rays.reset(); hits.reset(); range.reset(); slots = 0u; }
+inline TraceQueue ShadowQueue::view() const { return TraceQueue{(const RayRec*)rays.get(), (HitKey*)hits.get(), count, slots, (const float2*)range.get()}; }
+
+// One level of a frame's paths as the hit passes of lighting.hip take it (launchSunHits, launchLightHits): the stream that shades, the
+// frame's bins -- this level's rays traced, not yet shaded --, the tiles, that stream's spill part, the sums the terms go to (samples: the
+// sample sums, else S), the frame index of the sample the pass belongs to
+struct HitPass {
+  hipStream_t s; TraceQueue bins; const float4* fat0; const float4* fat1; const uint32_t* tileWords; uint32_t numTiles; int spillPart;
+  bool samples; float* sumRefl; float* sumDiff; uint32_t frameIndex, level;
+};
 
 }  // namespace rt

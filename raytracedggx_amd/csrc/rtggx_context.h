@@ -75,6 +75,17 @@
 #define RT_SKY_RUN_CAP 255u
 namespace rt {
 
+// A queue of shadow rays with its owners: what one pass of direct lighting (lighting.hip) fills, traces through the any-hit traversal and adds
+// from.  The format of an input set's bins (rt_queue.h, where the methods are): numBins bins of `slots` ray records and hit keys, a count
+// per bin, and -- the local lights -- the rays' own (tmin, tmax) per slot.  view(): what launchTrace takes, the queue's own shape in it.
+struct TraceQueue;
+struct ShadowQueue {
+  DevBuf<void> rays, hits, range; DevBuf<uint32_t> count; uint32_t slots = 0;
+  int ensure(uint32_t numBins, uint32_t binSlots, bool withRange, bool& filled);
+  void release();
+  TraceQueue view() const;
+};
+
 // What a build tells the host: written by the build's kernels, copied to pinned memory behind its last one.
 #define RT_TREELET_LEVELS 3
 struct BuildResult {
@@ -276,44 +287,42 @@ struct rtggx_context {
   bool externalStream = false;
 
   bool vndf = false;             // rtggx_set_sampler
-  // rtggx_set_sun: a directional light with ray-traced shadows (raytrace.hip launchSun).  Requested values take effect with the next
+  // rtggx_set_sun: a directional light with ray-traced shadows (lighting.hip launchSun).  Requested values take effect with the next
   // rtggx_render_visibility, like the other per-frame settings.  The queue is the sun's own -- the frame's bins are still read by the shading of the
   // frame in flight, and still sky relies on their counts --: one ray slot per pixel of a bin's 8x8 sub-tile, 48 + 8 bytes per pixel and 4 per bin,
   // allocated by the first call that turns the sun on.
   struct Sun { bool on = false; float L[3] = {}, E[3] = {}, T[3] = {}, B[3] = {}; } sun, sunRequested;      // T, B: the disk's frame about L (rtggx_set_sun_angle), made with L
-  rt::DevBuf<void> sunRays, sunHits; rt::DevBuf<uint32_t> sunCount;
+  rt::ShadowQueue sunQueue;
   // rtggx_set_sun_angle: the angular radius of the sun's disk in degrees and k = 1 - cos of it.  Stored whether or not a sun is set; the
-  // frame's, the next frame's.  0: the directional sun, and the SOFT = false kernels (raytrace.hip launchSun, launchSunHits).  No buffer.
+  // frame's, the next frame's.  0: the directional sun, and the SOFT = false kernels (lighting.hip launchSun, launchSunHits).  No buffer.
   struct SunAngle { float degrees = 0.0f, k = 0.0f; } sunAngle, sunAngleRequested;
-  // rtggx_set_sun_reflections: the sun term and the shadow at the surfaces the paths hit (raytrace.hip launchSunHits).  Stored whether or not a
-  // sun is set; the frame's, the next frame's.  Everything below exists from the first frame that has both on (raytrace.hip allocSunHits):
-  //   sunHitRays / sunHitHits / sunHitCount   a queue of the feature's own, bins of sunHitSlots = binSlots slots (released when the bins grow)
+  // rtggx_set_sun_reflections: the sun term and the shadow at the surfaces the paths hit (lighting.hip launchSunHits).  Stored whether or not a
+  // sun is set; the frame's, the next frame's.  Everything below exists from the first frame that has both on (lighting.hip beginSunHits):
+  //   sunHitQueue  a queue of the feature's own, bins of binSlots slots (released when the bins grow)
   //   sunHitSums   S of the one-sample frame: [2][W * H] float4 -- the sum of the terms r, g, b and the number of terms --, all zero between
   //                frames (sunHitResolveKernel leaves them so)
   // ONE of each for all input sets, like sppAcc: consecutive frames' passes follow each other in stream order, or by evSunHit where the
   // stream changes (sunHitStream: a view, the stream of the most recent frame that used them).
   bool sunReflections = false, sunReflectionsRequested = false;
-  rt::DevBuf<void> sunHitRays, sunHitHits; rt::DevBuf<uint32_t> sunHitCount; rt::DevBuf<float> sunHitSums;
-  uint32_t sunHitSlots = 0;
+  rt::ShadowQueue sunHitQueue; rt::DevBuf<float> sunHitSums;
   hipStream_t sunHitStream = nullptr; rt::Event evSunHit;
-  // rtggx_set_lights: point and spot lights with ray-traced shadows (raytrace.hip launchLights).  The requested list takes effect with the next
-  // rtggx_render_visibility, like the sun.  Everything below exists from the first frame with count > 0 (raytrace.hip allocLights):
-  //   lightRays / lightHits / lightCount   ONE queue in the sun's format for all lights -- bins of RT_BIN_MIN slots --, refilled light by light
-  //   lightRange   the rays' own (tmin, tmax), one float2 per slot of that queue (launchTrace's traceRayRange for the launch's duration)
+  // rtggx_set_lights: point and spot lights with ray-traced shadows (lighting.hip launchLights).  The requested list takes effect with the next
+  // rtggx_render_visibility, like the sun.  Everything below exists from the first frame with count > 0 (lighting.hip launchLights):
+  //   lightQueue   ONE queue in the sun's format for all lights -- bins of RT_BIN_MIN slots --, refilled light by light, with the rays' own
+  //                (tmin, tmax) beside it
   //   lightSums    S0 and S1: [2][W * H] float4 -- the sum of the terms r, g, b and the number of terms --, all zero between frames (the
   //                resolve leaves them so)
   // The pass runs on the main stream only: consecutive frames' kernels follow each other there.
   struct Lights { uint32_t count = 0; RtggxLight l[RTGGX_MAX_LIGHTS] = {}; } lights, lightsRequested;
-  rt::DevBuf<void> lightRays, lightHits, lightRange; rt::DevBuf<uint32_t> lightCount; rt::DevBuf<float> lightSums;
-  // rtggx_set_light_reflections: the lights' terms and shadows at the surfaces the paths hit (raytrace.hip launchLightHits).  Stored whether or
-  // not lights are set; the frame's, the next frame's.  From the first frame that has lights and the toggle on (raytrace.hip allocSunHits):
-  //   lightHitRays / lightHitHits / lightHitRange / lightHitCount   a queue of the feature's own with the rays' intervals beside it, bins of
-  //                lightHitSlots = binSlots slots (released when the bins grow), refilled light by light and level by level
+  rt::ShadowQueue lightQueue; rt::DevBuf<float> lightSums;
+  // rtggx_set_light_reflections: the lights' terms and shadows at the surfaces the paths hit (lighting.hip launchLightHits).  Stored whether or
+  // not lights are set; the frame's, the next frame's.  From the first frame that has lights and the toggle on (lighting.hip beginSunHits):
+  //   lightHitQueue  a queue of the feature's own with the rays' intervals beside it, bins of binSlots slots (released when the bins grow),
+  //                refilled light by light and level by level
   // S of the one-sample frame, the event and the stream view are the sun's hit pass's (sunHitSums, evSunHit, sunHitStream): the two features
   // add into one sum per (pixel, image) and one resolve packs it.
   bool lightReflections = false, lightReflectionsRequested = false;
-  rt::DevBuf<void> lightHitRays, lightHitHits, lightHitRange; rt::DevBuf<uint32_t> lightHitCount;
-  uint32_t lightHitSlots = 0;
+  rt::ShadowQueue lightHitQueue;
   uint32_t rayRate = 1;          // rtggx_set_ray_rate: pixels per traced ray, 1 or 4 (raytrace.hip rayGenKernel, reconstructKernel)
   uint32_t maxDepth = 1, depthRequested = 1;      // rtggx_set_max_recursion_depth: 1..4 levels of rays per path (raytrace.hip launchShade); the frame's, the next frame's
   // rtggx_set_samples_per_pixel: 1, 2, 4 or 8 samples per covered pixel (raytrace.hip launchShade; DESIGN.md "Samples per pixel"); the
@@ -432,7 +441,7 @@ struct rtggx_context {
   uint32_t largeCapacity = 0;
 
   uint32_t numBinsMax = 0, binSlots = 64;      // bins per set; ray slots per bin (rt_queue.h RT_BIN_MIN / RT_BIN)
-  rt::DevBuf<void> testRayRange; void* traceRayRange = nullptr;      // rtggx_trace_rays: the rays' own (TMin, TMax); the view is set only around that entry point's launch
+  rt::DevBuf<void> testRayRange;      // rtggx_trace_rays: the rays' own (TMin, TMax), one float2 per slot of an input set's bins
   rt::DevBuf<int32_t> stackOverflow;    // traversal-stack spill area (entries beyond the LDS stack), sized from
   uint32_t spillEntries = 0;            // the depth of the built trees: [spillEntries][numBinsMax * 128] words
   rt::DevBuf<void> dummyRecord;         // 128 zero bytes: record base for meshes without nodes / absent meshes
@@ -526,6 +535,14 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
 int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent_t done = nullptr);      // hit / miss shading of the traced bins
 int launchSun(rtggx_context* c, const FrameParams& fp, hipStream_t s);      // rtggx_set_sun: shadow rays from the primary surface, the any-hit traversal, the add into RayTracingOut0/1
 int launchLights(rtggx_context* c, const FrameParams& fp, hipStream_t s);   // rtggx_set_lights: per light generate -> any-hit -> add into the sums, one resolve into RayTracingOut0/1
+// rtggx_set_sun_reflections, rtggx_set_light_reflections (lighting.hip; called by launchShade in front of every level's shading pass): the frame's
+// first use of their queues and sums on stream s, then per level the sun's pass and the lights' (HitPass: rt_queue.h), then for a
+// one-sample frame the resolve
+struct HitPass;
+int beginSunHits(rtggx_context* c, hipStream_t s, bool wantSums, bool sunQueue, bool lightQueue);
+int launchSunHits(rtggx_context* c, const FrameParams& fp, const HitPass& p);
+int launchLightHits(rtggx_context* c, const FrameParams& fp, const HitPass& p);
+int launchSunHitResolve(rtggx_context* c, hipStream_t s, float* sums, const uint32_t* tileWords, uint32_t tilesX, uint32_t rowBegin, uint32_t rowEnd, hipEvent_t done);      // behind the last shading pass: S into the packed words
 int launchReconstruct(rtggx_context* c, const FrameParams& fp, hipStream_t s);      // rate 4: the untraced pixels of RayTracingOut0/1, after the hit shading
 int allocSamples(rtggx_context* c);      // what N > 1 samples per pixel need (rtggx_context::sppAcc, sppParams), once
 int allocAccumulation(rtggx_context* c);      // what rtggx_set_accumulation needs (rtggx_context::accRefl, accDiff, converged), once

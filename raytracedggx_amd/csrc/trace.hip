@@ -502,8 +502,8 @@ int launchTrace(rtggx_context* c, const FrameParams& fp, hipStream_t s, const Tr
   T.nodes1 = (const float4*)(have1 && c->mesh[1].nodes4 ? (const void*)c->mesh[1].nodes4 : c->dummyRecord);
   T.tris1 = (const float4*)(have1 ? (const void*)c->mesh[1].tris : c->dummyRecord);
   T.root0 = c->mesh[0].root; T.root1 = c->mesh[1].root; T.haveMesh0 = have0; T.haveMesh1 = have1;
-  T.rays = q.rays; T.hits = q.hits; T.tRange = (const float2*)c->traceRayRange;
-  T.binCount = q.binCount; T.numBins = numBins; T.binSlots = c->binSlots;
+  T.rays = q.rays; T.hits = q.hits; T.tRange = q.tRange;
+  T.binCount = q.binCount; T.numBins = numBins; T.binSlots = q.binSlots;
   // Stacks deeper than the LDS part spill to global memory; the built trees say how deep they can get (a 4-wide node leaves its other
   // entries behind: the build adds them up along every path, BuildResult::stack4).  The spill area belongs to the launch's WAVES, not to the bins
   // (round 3; per bin it was 2 x 20 entries x 32 640 bins x 2 KB = 2.7 GB for the bunny at 1080p, 4.3 GB for the dragon, four times

@@ -1,4 +1,4 @@
-"""The local lights at the surfaces the paths hit, on the GPU (rtggx_set_light_reflections; raytrace.hip lightHitGenKernel, the any-hit
+"""The local lights at the surfaces the paths hit, on the GPU (rtggx_set_light_reflections; lighting.hip lightHitGenKernel, the any-hit
 traversal with the rays' own intervals, sunHitAddKernel, sunHitResolveKernel): frames bit for bit against the restatement
 (tests/light_hit_ref.cpp) at depth 1 to 3, with several samples, a sample map, the other sampler and a larger sample set; behind the sun's
 hit pass in the shared sums; the lights without radii; both bin sizes; preset returns; twins; refusals; accumulation; strips; a deforming
@@ -368,3 +368,43 @@ def test_the_resident_launch_shape_equals_the_restatement(built):
         assert not key["small"] and where["shade"] == "main", (key, where)
     finally:
         p.close()
+
+
+def query_rays(n=300, seed=31):
+    """A short list through the scene's box, every ray with an interval of its own: (tmin, tmax) in (0 .. 0.5, 1 .. 30)."""
+    rng = np.random.default_rng(seed)
+    r = np.zeros((n, 8), np.float32)
+    r[:, 0:3] = rng.uniform((-8.0, -2.0, -8.0), (8.0, 8.0, 8.0), (n, 3))
+    d = rng.normal(size=(n, 3)); r[:, 3:6] = d / np.linalg.norm(d, axis=1, keepdims=True)
+    r[:, 6] = rng.uniform(0.0, 0.5, n); r[:, 7] = rng.uniform(1.0, 30.0, n)
+    return r
+
+
+@pytest.mark.parametrize("at", [0, 2], ids=["queries before the first frame", "queries between frames"])
+def test_ray_queries_and_the_lit_frames_leave_each_other_alone(built, at):
+    """Every queue of a frame states its own shape to the traversal -- the frame's 128-slot bins, the sun's and the lights' 64-slot bins with
+    and without the rays' intervals, the two hit passes' queues -- and so does the list of rtggx_trace_rays / rtggx_trace_occlusion, which
+    borrows a set's bins and brings intervals of its own.  Metallic below 1, the three lights, the sun, both toggles: the frames of a context
+    that makes both queries equal those of a twin that makes none, in every buffer and the ray count, and the queries' results equal those
+    of a fresh context -- default materials (64-slot bins), no sun, no lights -- brought to the same frame."""
+    extra = METAL_ARGS + light_args(LIGHTS) + SUN_ARGS + ["-sunreflections", "-lightreflections"]
+    a, b, fresh = G.app(W, H, extra), G.app(W, H, extra), G.app(W, H)
+    rays = query_rays()
+    try:
+        for f in range(at + 2):
+            for x in (a, b) + ((fresh,) if f <= at else ()):
+                x.OnUpdate()
+            if f == at:      # (the constants of frame `at` are in place, its kernels are not launched yet)
+                got, occ = a.context.trace_rays(rays), a.context.trace_occlusion(rays)
+                want, occ_fresh = fresh.context.trace_rays(rays), fresh.context.trace_occlusion(rays)
+                G.assert_same(got, want, "trace_rays at frame %d" % f)
+                np.testing.assert_array_equal(occ, occ_fresh, err_msg="trace_occlusion at frame %d" % f)
+                np.testing.assert_array_equal(occ, got["valid"])
+                assert occ.any() and not occ.all()
+            for x in (a, b) + ((fresh,) if f < at else ()):
+                x.OnRender()
+            ia = G.images(a, IMAGES)
+            G.assert_same(ia, G.images(b, IMAGES), "frame %d" % f)
+            assert ia["rays"][0] > 0
+    finally:
+        a.OnDestroy(); b.OnDestroy(); fresh.OnDestroy()

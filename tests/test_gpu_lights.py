@@ -1,4 +1,4 @@
-"""Local lights on the GPU (rtggx_set_lights; raytrace.hip lightGenKernel, lightAddKernel): frames bit for bit against the restatement
+"""Local lights on the GPU (rtggx_set_lights; lighting.hip lightGenKernel, lightAddKernel): frames bit for bit against the restatement
 (tests/lights_ref.cpp) at depth 1, at depth 2 with two samples and behind the sun's passes; the three lights without their radii; all-metal
 materials; twins; refusals; the command line; accumulation; strips; a deforming mesh; still sky; the resident launch shape.  Scene and lights
 are those of tests/golden/lights_classes.json, whose class conditions tests/test_lights_host.py establishes on the CPU; the tests that

@@ -1,4 +1,4 @@
-"""The sun on the GPU (rtggx_set_sun; raytrace.hip sunGenKernel, the any-hit traversal, sunAddKernel): frames bit for bit against the
+"""The sun on the GPU (rtggx_set_sun; lighting.hip sunGenKernel, the any-hit traversal, sunAddKernel): frames bit for bit against the
 restatement (tests/sun_ref.cpp) behind the depth, sample-count, sampler and sample-set restatements; all-metal carry-over; a 1080p frame; the
 sun turned off again against a twin; still sky; refusals; strips; accumulation.  Direction and irradiance are those of
 tests/golden/sun_classes.json, whose class shares tests/test_sun_host.py establishes on the CPU."""

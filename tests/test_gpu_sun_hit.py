@@ -1,4 +1,4 @@
-"""The sun at the surfaces the paths hit, on the GPU (rtggx_set_sun_reflections; raytrace.hip sunHitGenKernel, the any-hit traversal,
+"""The sun at the surfaces the paths hit, on the GPU (rtggx_set_sun_reflections; lighting.hip sunHitGenKernel, the any-hit traversal,
 sunHitAddKernel, sunHitResolveKernel): frames bit for bit against the restatement (tests/sun_hit_ref.cpp) at every depth, with several
 samples, a sample map, the other sampler and a larger sample set; both bin sizes; preset returns; a 1080p frame; twins; refusals; strips;
 accumulation and scoring; a deforming mesh; still sky.  Scene, direction and irradiance are those of tests/golden/sun_hit_classes.json,

@@ -1,4 +1,4 @@
-"""A sun with a size, on the GPU (rtggx_set_sun_angle; raytrace.hip sunGenKernel<true>, sunHitGenKernel<true>): frames bit for bit against
+"""A sun with a size, on the GPU (rtggx_set_sun_angle; lighting.hip sunGenKernel<true>, sunHitGenKernel<true>): frames bit for bit against
 the restatement (tests/sun_soft_ref.cpp) at depth 1 and 2, with several samples, a sample map, the other sampler and a larger sample set; a
 small disk; all-metal materials; twins; refusals; accumulation and the penumbra in its mean; strips; a deforming mesh; still sky; a 1080p
 frame.  Scene, direction, irradiance and angle are those of tests/golden/sun_soft_classes.json, whose class conditions
