@@ -784,6 +784,52 @@ int  rtggx_set_lights(rtggx_context* ctx, const RtggxLight* lights, uint32_t cou
  * tests/light_hit_ref.cpp restates the rule. */
 int  rtggx_set_light_reflections(rtggx_context* ctx, int enable);
 
+/* One shadow ray per surface point for ALL local lights: the pass picks one light per point, in proportion to the luminance that light would
+ * contribute unshadowed, traces its one shadow ray and divides the term by the probability of the pick.  The expectation over the draw is
+ * the sum rtggx_set_lights computes; the cost is noise where lights of different visibility overlap, which the temporal pass and
+ * rtggx_set_accumulation average as they average penumbrae.
+ * mode 0 (default): every light traces its own shadow ray (rtggx_set_lights as it is).
+ * mode 1: one shadow ray per surface point for all lights.
+ * Any other mode is refused and the setting kept.  The mode is stored whether or not lights are set and acts only in frames that have
+ * count > 0 lights (so never at ray rate 4, which lights exclude); it takes effect with the next rtggx_render_visibility.  Opt-in: a context
+ * in mode 0 allocates and launches exactly what it did.  RTGGX_MAX_LIGHTS and rtggx_set_lights with its refusals are unchanged.
+ * The primary pass in mode 1, in place of the per-light steps of rtggx_set_lights; per covered pixel of the rows ray generation covers, in
+ * fp32 without contraction, each operation rounded on its own, with the operator definitions of rtggx_set_lights:
+ *   0. the primary surface, as in step 0 of rtggx_set_lights;
+ *   1. the candidates.  For the lights in ascending index i, skipping any whose intensity is 0 in every component: steps 1-4 of
+ *      rtggx_set_lights -- a light that is out of range, facing away or outside the cone is not a candidate.  spec_i is step 8 as computed
+ *      there: spec_i,c = (F_c k) (I_c att).  Where m < 1: diff_i,c = ((color_c (1 - 0.04)) g) I_c with g = (NoL / pi) att.
+ *      Y(c) = (0.25 c.r + 0.5 c.g) + 0.25 c.b.  w_i = Y(spec_i) + Y(diff_i); where m >= 1 w_i = Y(spec_i) alone.  A light is a candidate
+ *      iff w_i > 0 (a NaN is not a candidate);
+ *   2. W = ((+0 + w_a) + w_b) + ... over the candidates, ascending.  With no candidate there is no ray, and both words stay bit for bit;
+ *   3. the draw.  h = rng(rng(pixel) + FrameIndex) as in step 5 of rtggx_set_lights; v = rng(h + 96 * 0x9E3779B9) with 32-bit wraparound
+ *      (slot 96 is free: the sun uses the slots 0 .. 8, the primary lights 16 .. 23, the hits 32 .. 95); x = (float)(v >> 8) / 16777216,
+ *      which is exact; t = x W;
+ *   4. the pick.  c = +0; over the candidates, ascending, c = c + w_i; the chosen light is the first with t < c; if none qualifies, the last
+ *      candidate;
+ *   5. f = W / w_i, correctly rounded.  With a single candidate f is exactly 1;
+ *   6. steps 5-7 of rtggx_set_lights for the chosen light alone, with its own slot 16 + i: the target Ds; ds2 < 1e-6, or below the horizon:
+ *      no ray, no term; the shadow ray over (1e-5, tmax), skipping (inst, prim), through the any-hit traversal.  rtggx_ray_count /
+ *      rtggx_ray_total count it.  Occluded: no term;
+ *   7. where the ray is unoccluded: S0_c = spec_i,c f, one more multiplication; where m < 1 S1_c = diff_i,c f; n = 1; and the words are
+ *      written as they are behind the last light of rtggx_set_lights: pack(unpack(word) + S), one rounding.
+ * Everything else of rtggx_set_lights holds: background pixels are untouched, RayTracingOut1 at m >= 1 is a carry-over and is never touched,
+ * the pass is independent of recursion depth, sample count, sample map, sample set and sampler, and it works on strips (pixel is the
+ * full-frame index), with a deforming mesh, a caller-owned stream and rtggx_set_async_compute(0).  With one casting light the two images
+ * are those of mode 0 bit for bit.
+ * The hits in mode 1, under rtggx_set_light_reflections(ctx, 1), in place of that function's per-light steps; per level d, sample and
+ * level-d ray that touches a surface, the hit derived as there: the candidates from its step 1; term_i from its step 4 and s_i = T_d term_i
+ * per component; w_i = Y(s_i), a candidate iff w_i > 0; W, t, the pick and f as above, with the draw v = rng(h + (104 + 2 d + img) *
+ * 0x9E3779B9), h from the path's pixel and the sample's frame index (FrameIndex N + k) -- the slots 104 .. 111 --; the chosen light's target
+ * from its own slot 32 + 16 d + 8 img + i; the term added is s_i f.  The order of a pixel's sum becomes: the sun's s_d first, then this one
+ * term, level by level; the sample sums, the resolve and its 1 / c scale are unchanged.
+ * Per frame three kernels in place of three per light (one generating the shadow rays, the any-hit traversal, one adding the unoccluded
+ * terms), and per level and sample of the hits likewise three, whatever the number of lights.  Memory in mode 1, on top of rtggx_set_lights',
+ * from the first mode-1 frame with lights until rtggx_destroy: the finished diffuse term beside the lights' queue, 16 bytes per ray slot
+ * (per pixel).  Known limits: the BRDF and NoL are still evaluated at the centre direction; the pick ignores visibility, so a light that is
+ * mostly occluded still draws its share of rays.  tests/light_pick_ref.cpp restates the rule. */
+int  rtggx_set_light_sampling(rtggx_context* ctx, int mode);
+
 /* The sun from the environment: finds the sun in the current cube, measures its direction and irradiance -- what rtggx_set_sun wants -- and,
  * where asked, takes it out of the cube, so that a probe with a sun in it does not light the scene twice (once analytically, with shadows, and
  * once more through the environment lookups, the SH irradiance and every level of the chain).  A setup call, not per frame; opt-in: a context

@@ -43,7 +43,7 @@ EXPORTS = ["rtggx_last_error", "rtggx_create", "rtggx_destroy", "rtggx_set_strip
            "rtggx_set_reference", "rtggx_reference_from_accumulation", "rtggx_set_scoring", "rtggx_read_scores",
            "rtggx_set_env_image", "rtggx_generate_env_mips", "rtggx_prefilter_env",
            "rtggx_set_sample_map", "rtggx_read_sample_map", "rtggx_trace_occlusion", "rtggx_set_sun", "rtggx_set_sun_reflections",
-           "rtggx_sun_from_env", "rtggx_set_sun_angle", "rtggx_set_lights", "rtggx_set_light_reflections"]
+           "rtggx_sun_from_env", "rtggx_set_sun_angle", "rtggx_set_lights", "rtggx_set_light_reflections", "rtggx_set_light_sampling"]
 SCORE_RING = 256
 
 
@@ -160,6 +160,7 @@ def load():
     L.rtggx_set_sun_angle.argtypes = [vp, C.c_float]
     L.rtggx_set_lights.argtypes = [vp, C.POINTER(Light), C.c_uint32]
     L.rtggx_set_light_reflections.argtypes = [vp, C.c_int]
+    L.rtggx_set_light_sampling.argtypes = [vp, C.c_int]
     L.rtggx_sun_from_env.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_int, C.POINTER(SunEstimate)]
     L.rtggx_ray_total.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
     L.rtggx_kernel_times.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
@@ -637,6 +638,11 @@ class Context:
     def set_light_reflections(self, on):
         """The lights' terms and shadows at the surfaces the paths hit as well (0 / 1), from the next frame on; it acts only while lights are set."""
         self._check(self.L.rtggx_set_light_reflections(self.h, int(on)))
+
+    def set_light_sampling(self, mode):
+        """0: every light traces its own shadow ray; 1: one shadow ray per surface point for all lights, the light picked by the luminance it
+        would contribute unshadowed (include/rtggx.h has the rule).  From the next frame on; it acts only while lights are set."""
+        self._check(self.L.rtggx_set_light_sampling(self.h, int(mode)))
 
     def sun_from_env(self, cone=0, ring=0, min_contrast=0, remove=False):
         """The sun of the current environment (include/rtggx.h): the record as a dict (SunEstimate.as_dict) -- "direction" and "irradiance" are

@@ -509,6 +509,15 @@ int rtggx_set_light_reflections(rtggx_context* c, int enable) {
   c->lightReflectionsRequested = enable == 1;
   return 0;
 }
+// One shadow ray per surface point for all lights (include/rtggx.h).  Only the value is kept: it is stored whether or not lights are set,
+// allocates nothing here (the first mode-1 frame with lights does: lighting.hip launchLights) and takes effect with the next
+// rtggx_render_visibility.  No synchronisation, no end of a still-sky run, no reset of an accumulation, as for the lights themselves.
+int rtggx_set_light_sampling(rtggx_context* c, int mode) {
+  RT_CHECK_CTX(c);
+  if (mode != 0 && mode != 1) { setError("rtggx_set_light_sampling: mode %d: 0 (a shadow ray per light) or 1 (one for all lights)", mode); return -1; }
+  c->lightSamplingRequested = (uint32_t)mode;
+  return 0;
+}
 // Sums and count back to zero: two clears on the main stream, behind the frames it holds and in front of the next one; nothing waits.
 int rtggx_reset_accumulation(rtggx_context* c) {
   RT_CHECK_CTX(c);

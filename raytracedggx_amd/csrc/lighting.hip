@@ -1,5 +1,6 @@
 // Direct lighting: the sun (rtggx_set_sun, rtggx_set_sun_angle), the local lights (rtggx_set_lights) and both at the surfaces the paths hit
-// (rtggx_set_sun_reflections, rtggx_set_light_reflections).  include/rtggx.h has the per-pixel rules, DESIGN.md section 9 the structure.
+// (rtggx_set_sun_reflections, rtggx_set_light_reflections); one shadow ray for all lights (rtggx_set_light_sampling: the two picking kernels
+// further down, with a table of their own).  include/rtggx.h has the per-pixel rules, DESIGN.md section 9 the structure.
 //
 // Every pass is the same three launches around a queue of its own (rt::ShadowQueue, rt_queue.h): a generating kernel derives a surface --
 // the primary one from the visibility word, or the hit of a traced ray -- and, where a light reaches it, compacts ONE shadow ray into the
@@ -452,16 +453,190 @@ int launchSunHitResolve(rtggx_context* c, hipStream_t s, float* sums, const uint
 }
 // (a fill runs on the null stream, which this context's streams are not ordered against: one synchronise behind all of a call's fills)
 static int syncFills(bool filled) { if (filled) RT_HIP(hipStreamSynchronize(nullptr)); return 0; }
+
+// ---- one shadow ray for all lights (rtggx_set_light_sampling(ctx, 1); DESIGN.md section 9 "One ray for all lights") -----------------------------
+// In place of the per-light loops of launchLights and launchLightHits: ONE generating kernel takes the whole list as a kernel argument -- the
+// walk over the lights is wave-uniform and fed by scalar loads --, weighs every light by the luminance w_i its unshadowed term would have at
+// the surface (a first loop, unrolled to the constant bound 8, so that the w_i stay in registers), picks one light per surface point with
+// one draw of the pixel's hash, evaluates that light once more -- now with its target -- and compacts its ONE shadow ray with the finished
+// term times f = W / w_i.  One any-hit traversal and one add follow, whatever the number of lights.
+//   the step, written once below           who runs it
+//   pickLuminance, pickDraw, pickLight     lightPickGenKernel, lightHitPickGenKernel
+//   chosenLight                            both: the chosen light's record out of the kernel argument, by selects
+// CONE and SOFT are compile-time here as well, but per LIST: does any casting light have a cone, a radius.  In a CONE instance a light
+// without a cone runs the cone's arithmetic on A = 0, cos_outer = -2, cos_inner = -1 (pickList), which gives spot = 1 exactly and refuses
+// nothing; in a SOFT instance a chosen light without a radius takes the branch without the hash, so that Ds is D bit for bit.
+#define RT_SLOT_LIGHT_PICK 96u
+#define RT_SLOT_LIGHT_PICK_HIT(d) (104u + 2u * (d))
+#define RT_SLOT_LIGHT_PICK_HIT_IMAGE 1u
+struct LightListArgs { LightArgs light[RTGGX_MAX_LIGHTS]; uint32_t castMask; const float* cosSin; };      // castMask: bit i, light i has an intensity
+RT_DEV float pickLuminance(f3 c) { return (0.25f * c.x + 0.5f * c.y) + 0.25f * c.z; }
+// Step 3: x in [0, 1) from the top 24 bits of the slot's word
+RT_DEV float pickDraw(uint32_t pixel, uint32_t frameIndex, uint32_t j) {
+  uint32_t h = rng(pixel); h += frameIndex; h = rng(h);
+  const uint32_t v = rng(h + j * 0x9E3779B9u);
+  return (float)(v >> 8) / 16777216.0f;
+}
+// Step 4 over the eight weights (0: not a candidate): the first candidate with t < c, else the last one; wOut: its weight
+RT_DEV uint32_t pickLight(const float (&w)[RTGGX_MAX_LIGHTS], float t, float& wOut) {
+  float c = 0.0f;
+  uint32_t chosen = 0u;
+  bool found = false;
+#pragma unroll
+  for (uint32_t i = 0; i < RTGGX_MAX_LIGHTS; ++i) {
+    if (w[i] > 0.0f) {
+      c = c + w[i];
+      if (!found) { chosen = i; wOut = w[i]; found = t < c; }
+    }
+  }
+  return chosen;
+}
+RT_DEV LightArgs chosenLight(const LightListArgs& list, uint32_t chosen) {
+  LightArgs K = list.light[0];
+#pragma unroll
+  for (uint32_t i = 1; i < RTGGX_MAX_LIGHTS; ++i) {
+    const LightArgs& o = list.light[i];
+    const bool is = chosen == i;
+    K.Px = is ? o.Px : K.Px; K.Py = is ? o.Py : K.Py; K.Pz = is ? o.Pz : K.Pz; K.range = is ? o.range : K.range;
+    K.Ix = is ? o.Ix : K.Ix; K.Iy = is ? o.Iy : K.Iy; K.Iz = is ? o.Iz : K.Iz; K.radius = is ? o.radius : K.radius;
+    K.Ax = is ? o.Ax : K.Ax; K.Ay = is ? o.Ay : K.Ay; K.Az = is ? o.Az : K.Az; K.cosOuter = is ? o.cosOuter : K.cosOuter; K.cosInner = is ? o.cosInner : K.cosInner;
+  }
+  return K;
+}
+// Steps 1-4 and 8 of rtggx_set_lights for one light at the primary surface, without the target: spec and (diffuse: m < 1) diff
+struct PickTerms { f3 spec, diff; float w; };
+template <bool CONE>
+RT_DEV PickTerms primaryPickTerms(const LightArgs& K, const PrimarySurface& s, bool diffuse) {
+  PickTerms o;
+  o.spec = o.diff = mk3(0.0f, 0.0f, 0.0f); o.w = 0.0f;
+  evalLight<CONE, false>(K, nullptr, s.P, s.N, 0u, 0u, 0u, [&](const LightSample& l) {
+    const f3 Fk = deltaLightSpecular(s.N, s.V, l.L, l.NoL, s.color, s.rm);
+    o.spec = mk3(Fk.x * (K.Ix * l.att), Fk.y * (K.Iy * l.att), Fk.z * (K.Iz * l.att));
+    o.w = pickLuminance(o.spec);
+    if (diffuse) {
+      const float g = (l.NoL / RT_PI) * l.att;
+      o.diff = mk3(((s.color.x * (1.0f - 0.04f)) * g) * K.Ix, ((s.color.y * (1.0f - 0.04f)) * g) * K.Iy, ((s.color.z * (1.0f - 0.04f)) * g) * K.Iz);
+      o.w = o.w + pickLuminance(o.diff);
+    }
+  });
+  if (!(o.w > 0.0f)) o.w = 0.0f;      // not a candidate (a NaN is none)
+  return o;
+}
+// Step 6: the chosen light's target.  A light without a radius in a SOFT instance: the branch without the hash
+template <bool CONE, bool SOFT>
+RT_DEV bool chosenLightSample(const LightArgs& K, const float* cosSin, f3 P, f3 N, uint32_t pixel, uint32_t frameIndex, uint32_t j, LightSample& out) {
+  bool lit = false;
+  const auto onLit = [&](const LightSample& l) { out = l; lit = true; };
+  if constexpr (SOFT) {
+    if (K.radius > 0.0f) evalLight<CONE, true>(K, cosSin, P, N, pixel, frameIndex, j, onLit);
+    else evalLight<CONE, false>(K, cosSin, P, N, pixel, frameIndex, j, onLit);
+  } else evalLight<CONE, false>(K, cosSin, P, N, pixel, frameIndex, j, onLit);
+  return lit;
+}
+struct LightPickGenArgs {
+  const unsigned long long* visDepth; const float4* fat0; const float4* fat1;
+  RayRec* rays; HitKey* hits; uint32_t* binCount; float2* tRange; float4* diffTerm;      // diffTerm: S1 of the slot's ray, where m < 1
+  const uint32_t* tileWords; uint32_t tilesX, rowBegin, rowEnd;
+  LightListArgs list;
+};
+template <bool CONE, bool SOFT>
+__global__ void __launch_bounds__(256) lightPickGenKernel(const FrameParams* __restrict__ fpp, LightPickGenArgs A) {
+  const FrameParams& fp = *fpp;
+  const uint32_t tile = blockIdx.x;
+  if (tileIsEmpty(A.tileWords, tile)) return;
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const uint32_t px = (tile % A.tilesX) * 16 + (wave & 1u) * 8 + (lane & 7u);
+  const uint32_t py = A.rowBegin + (tile / A.tilesX) * 16 + (wave >> 1) * 8 + (lane >> 3);
+  bool want = false, wantDiff = false;
+  RayRec rr;
+  float tmax = 0.0f;
+  f3 S1 = mk3(0.0f, 0.0f, 0.0f);
+  if (px < fp.W && py < A.rowEnd) atPrimarySurface(fp, A.visDepth, A.fat0, A.fat1, px, py, [&](const PrimarySurface& s) {
+    const bool diffuse = s.rm.y < 1.0f;
+    // steps 1 and 2: the eight weights, W
+    float w[RTGGX_MAX_LIGHTS];
+    float W = 0.0f;
+#pragma unroll
+    for (uint32_t i = 0; i < RTGGX_MAX_LIGHTS; ++i) {
+      w[i] = 0.0f;
+      if ((A.list.castMask >> i) & 1u) w[i] = primaryPickTerms<CONE>(A.list.light[i], s, diffuse).w;
+      W = W + w[i];      // (a weight of +0 leaves W as it is)
+    }
+    if (!(W > 0.0f)) return;      // no candidate
+    // steps 3-5
+    const float t = pickDraw(s.pixel, fp.g.FrameIndex, RT_SLOT_LIGHT_PICK) * W;
+    float wc = 0.0f;
+    const uint32_t chosen = pickLight(w, t, wc);
+    const float f = W / wc;
+    // steps 6 and 7: the chosen light once more, with its target
+    const LightArgs K = chosenLight(A.list, chosen);
+    LightSample l;
+    if (!chosenLightSample<CONE, SOFT>(K, A.list.cosSin, s.P, s.N, s.pixel, fp.g.FrameIndex, RT_SLOT_LIGHT(chosen), l)) return;
+    const PickTerms x = primaryPickTerms<CONE>(K, s, diffuse);
+    want = true; wantDiff = diffuse;
+    tmax = l.tmax;
+    rr = shadowRay(s.P, l.Ls, s.pixel, (s.inst << 24) | s.prim, mk3(x.spec.x * f, x.spec.y * f, x.spec.z * f), 0u);
+    S1 = mk3(x.diff.x * f, x.diff.y * f, x.diff.z * f);
+  });
+  const uint32_t bin = blockIdx.x * 4u + wave;
+  const unsigned long long wanting = __ballot(want);      // (the slot compactShadowRay gives the lane)
+  if (wantDiff) A.diffTerm[(size_t)bin * RT_BIN_MIN + (uint32_t)__popcll(wanting & ((1ull << lane) - 1ull))] = make_float4(S1.x, S1.y, S1.z, 0.0f);
+  const uint32_t n = compactShadowRay<true>(want, rr, tmax, A.rays, A.hits, A.tRange, bin, RT_BIN_MIN, 0u, lane);
+  if (lane == 0) A.binCount[bin] = n;
+}
+// lightAddKernel for a queue whose rays belong to different lights: the slot's own S1 beside the record
+struct LightPickAddArgs {
+  const RayRec* rays; const HitKey* hits; const uint32_t* binCount; const uint32_t* tileWords; const float4* diffTerm;
+  float4* sumRefl; float4* sumDiff;
+};
+__global__ void __launch_bounds__(256) lightPickAddKernel(const FrameParams* __restrict__ fpp, LightPickAddArgs A) {
+  const FrameParams& fp = *fpp;
+  if (tileIsEmpty(A.tileWords, blockIdx.x)) return;
+  const uint32_t bin = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (lane >= A.binCount[bin]) return;
+  const size_t k = (size_t)bin * RT_BIN_MIN + lane;
+  if (hitKeyId(A.hits[k]) != 0xFFFFFFFFu) return;      // occluded: no term
+  const RayRec rr = A.rays[k];
+  const uint32_t inst = rr.skip >> 24;
+  const float4 s0 = A.sumRefl[rr.pixel];
+  A.sumRefl[rr.pixel] = make_float4(s0.x + rr.wx, s0.y + rr.wy, s0.z + rr.wz, s0.w + 1.0f);
+  if (fp.mat.RoughMetals[inst][1] < 1.0f) {      // (lightAddKernel)
+    const float4 d = A.diffTerm[k], s1 = A.sumDiff[rr.pixel];
+    A.sumDiff[rr.pixel] = make_float4(s1.x + d.x, s1.y + d.y, s1.z + d.z, s1.w + 1.0f);
+  }
+}
+// The context's list as the picking kernels take it, and the instance [2 cone + soft] the list runs (see above)
+static uint32_t pickVariant(const rtggx_context* c) {
+  uint32_t v = 0u;
+  for (uint32_t i = 0; i < c->lights.count; ++i) if (lightCastsRays(c->lights.l[i])) v |= lightVariant(c->lights.l[i]);
+  return v;
+}
+static LightListArgs pickList(const rtggx_context* c) {
+  LightListArgs L = {};
+  for (uint32_t i = 0; i < c->lights.count; ++i) {
+    const RtggxLight& l = c->lights.l[i];
+    if (!lightCastsRays(l)) continue;
+    L.castMask |= 1u << i;
+    L.light[i] = lightArgs(l);
+    if (!(l.cos_outer > -1.0f)) { L.light[i].Ax = L.light[i].Ay = L.light[i].Az = 0.0f; L.light[i].cosOuter = -2.0f; L.light[i].cosInner = -1.0f; }
+  }
+  L.cosSin = c->cosSinTab;
+  return L;
+}
+static void (*const kLightPickGen[4])(const FrameParams*, LightPickGenArgs) = {lightPickGenKernel<false, false>, lightPickGenKernel<false, true>, lightPickGenKernel<true, false>, lightPickGenKernel<true, true>};
+
 int launchLights(rtggx_context* c, const FrameParams& fp, hipStream_t s) {
   uint32_t rb, re;
   passRows(fp, ROWS_GBUFFER, rb, re);
   if (re <= rb) return 0;
   const uint32_t tilesX = (fp.W + 15) / 16, tilesY = (re - rb + 15) / 16, numTiles = tilesX * tilesY;
   if (numTiles * 4u > c->numBinsMax) { setError("rtggx_ray_trace: the lights' queue does not hold %u bins", numTiles * 4u); return -1; }
-  { // what the lights need, from the first frame that has some: the queue with its intervals, the sums
+  const bool pick = c->lightSampling == 1u;      // rtggx_set_light_sampling
+  { // what the lights need, from the first frame that has some: the queue with its intervals, the sums -- and in mode 1 the diffuse terms
     bool filled = false;
     { const int r = c->lightQueue.ensure(c->numBinsMax, RT_BIN_MIN, true, filled); if (r) return r; }
     if (!c->lightSums) { RT_HIP(allocFilled(c->lightSums, (size_t)c->W * c->H * 8u)); filled = true; }
+    if (pick && !c->lightPickDiff) RT_HIP(alloc(c->lightPickDiff, (size_t)c->numBinsMax * RT_BIN_MIN * 4u));
     { const int r = syncFills(filled); if (r) return r; } }
   const InputSet& set = c->cur();
   const FrameParams* const dfp = c->dParams + c->slot;
@@ -474,6 +649,21 @@ int launchLights(rtggx_context* c, const FrameParams& fp, hipStream_t s) {
   LightAddArgs D;
   D.rays = q.rays; D.hits = q.hits; D.binCount = q.binCount; D.tileWords = G.tileWords;
   D.sumRefl = (float4*)c->lightSums.get(); D.sumDiff = D.sumRefl + (size_t)c->W * c->H;
+  if (pick) {      // one generating launch, one traversal, one add for the whole list (none where no light has an intensity)
+    LightPickGenArgs P;
+    P.visDepth = G.visDepth; P.fat0 = G.fat0; P.fat1 = G.fat1;
+    P.rays = G.rays; P.hits = G.hits; P.binCount = G.binCount; P.tRange = G.tRange; P.diffTerm = (float4*)c->lightPickDiff.get();
+    P.tileWords = G.tileWords; P.tilesX = tilesX; P.rowBegin = rb; P.rowEnd = re;
+    P.list = pickList(c);
+    if (P.list.castMask) {
+      launch(kLightPickGen[pickVariant(c)], dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, P);
+      { const int r = launchTrace(c, fp, s, q, numTiles * 4u, true, tilesX, tilesY, c->traceGrid[3], -1, nullptr, nullptr, 2, true); if (r) return r; }
+      const LightPickAddArgs PD{q.rays, q.hits, q.binCount, G.tileWords, P.diffTerm, D.sumRefl, D.sumDiff};
+      launch(lightPickAddKernel, dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, PD);
+      RT_HIP(hipGetLastError());
+    }
+    return launchSunHitResolve(c, s, c->lightSums, G.tileWords, tilesX, rb, re, nullptr);
+  }
   for (uint32_t i = 0; i < c->lights.count; ++i) {
     const RtggxLight& l = c->lights.l[i];
     if (!lightCastsRays(l)) continue;
@@ -565,6 +755,68 @@ __global__ void __launch_bounds__(256) lightHitGenKernel(const FrameParams* __re
   if (lane == 0u) A.outCount[bin] = written;
 }
 static void (*const kLightHitGen[4])(const FrameParams*, LightHitGenArgs) = {lightHitGenKernel<false, false>, lightHitGenKernel<false, true>, lightHitGenKernel<true, false>, lightHitGenKernel<true, true>};
+// rtggx_set_light_sampling(ctx, 1) at the hits: lightHitGenKernel's walk of the bin with lightPickGenKernel's pick -- the weight of light i is
+// the luminance of the finished s_i = T_d term_i, the draw's slot RT_SLOT_LIGHT_PICK_HIT(level) + img, the record's weight s_i f
+struct LightHitPickGenArgs : HitBinArgs {
+  RayRec* outRays; HitKey* outHits; uint32_t* outCount; float2* outRange;                   // the feature's queue: the same bins, binSlots slots each
+  const uint32_t* tileWords;
+  uint32_t frameIndex, level;      // the frame index of the sample the pass belongs to
+  LightListArgs list;
+};
+// Steps 1 and 4-5 of rtggx_set_light_reflections for one light at a hit, without the target: s = T_d term (0 where the light does not reach)
+template <bool CONE>
+RT_DEV f3 hitPickTerm(const FrameParams& fp, const LightArgs& K, const TracedHit& h, f3 P) {
+  f3 s = mk3(0.0f, 0.0f, 0.0f);
+  evalLight<CONE, false>(K, nullptr, P, h.N, 0u, 0u, 0u, [&](const LightSample& l) {
+    const f3 term = hitLobeTerm(fp, h, l.L, l.NoL, mk3(K.Ix, K.Iy, K.Iz), l.att);
+    s = mk3(h.q2.x * term.x, h.q2.y * term.y, h.q2.z * term.z);
+  });
+  return s;
+}
+template <bool CONE, bool SOFT>
+__global__ void __launch_bounds__(256) lightHitPickGenKernel(const FrameParams* __restrict__ fpp, LightHitPickGenArgs A) {
+  const FrameParams& fp = *fpp;
+  const uint32_t tile = blockIdx.x;
+  if (tileIsEmpty(A.tileWords, tile)) return;
+  const uint32_t bin = tile * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  const uint32_t count = RT_SGPR(min(A.binCount[bin] & 0xFFu, A.binSlots));
+  uint32_t written = 0u;      // shadow rays in the front of the bin so far: never more than the records read
+  for (uint32_t base = 0u; base < count; base += 64u) {
+    const uint32_t i = base + lane;
+    bool want = false;
+    RayRec sr;
+    float tmax = 0.0f;
+    if (i < count) atTracedHit(fp, A.rays, A.hits, A.fat0, A.fat1, (size_t)bin * A.binSlots + i, [&](const TracedHit& h) {
+      const f3 P = h.P();
+      float w[RTGGX_MAX_LIGHTS];
+      float W = 0.0f;
+#pragma unroll
+      for (uint32_t k = 0; k < RTGGX_MAX_LIGHTS; ++k) {
+        w[k] = 0.0f;
+        if ((A.list.castMask >> k) & 1u) {
+          const float y = pickLuminance(hitPickTerm<CONE>(fp, A.list.light[k], h, P));
+          w[k] = y > 0.0f ? y : 0.0f;      // (a NaN is no candidate)
+        }
+        W = W + w[k];
+      }
+      if (!(W > 0.0f)) return;
+      const float t = pickDraw(h.pixel, A.frameIndex, RT_SLOT_LIGHT_PICK_HIT(A.level) + RT_SLOT_LIGHT_PICK_HIT_IMAGE * h.image) * W;
+      float wc = 0.0f;
+      const uint32_t chosen = pickLight(w, t, wc);
+      const float f = W / wc;
+      const LightArgs K = chosenLight(A.list, chosen);
+      LightSample l;
+      if (!chosenLightSample<CONE, SOFT>(K, A.list.cosSin, P, h.N, h.pixel, A.frameIndex, RT_SLOT_LIGHT_HIT(A.level, chosen) + RT_SLOT_LIGHT_HIT_IMAGE * h.image, l)) return;
+      const f3 s = hitPickTerm<CONE>(fp, K, h, P);
+      want = true;
+      tmax = l.tmax;
+      sr = shadowRay(P, l.Ls, h.pixel, h.hitId, mk3(s.x * f, s.y * f, s.z * f), h.image);
+    });
+    written += compactShadowRay<true>(want, sr, tmax, A.outRays, A.outHits, A.outRange, bin, A.binSlots, written, lane);
+  }
+  if (lane == 0u) A.outCount[bin] = written;
+}
+static void (*const kLightHitPickGen[4])(const FrameParams*, LightHitPickGenArgs) = {lightHitPickGenKernel<false, false>, lightHitPickGenKernel<false, true>, lightHitPickGenKernel<true, false>, lightHitPickGenKernel<true, true>};
 
 // The frame's first use of the hit passes' queues and sums on stream s.  They exist from the first frame that has the sun or lights and the
 // respective toggle on: per feature its queue at the frame's slots per bin (the bins' growth releases it: frame.hip growBins, behind a wait
@@ -615,6 +867,17 @@ int launchLightHits(rtggx_context* c, const FrameParams& fp, const HitPass& p) {
   G.outRays = (RayRec*)q.rays; G.outHits = q.hits; G.outCount = c->lightHitQueue.count; G.outRange = (float2*)q.tRange;
   G.tileWords = p.tileWords;
   G.cosSin = c->cosSinTab; G.frameIndex = p.frameIndex;
+  if (c->lightSampling == 1u) {      // rtggx_set_light_sampling: one generating launch, one traversal, one add for the whole list
+    LightHitPickGenArgs P;
+    static_cast<HitBinArgs&>(P) = G;
+    P.outRays = G.outRays; P.outHits = G.outHits; P.outCount = G.outCount; P.outRange = G.outRange;
+    P.tileWords = G.tileWords;
+    P.frameIndex = p.frameIndex; P.level = p.level;
+    P.list = pickList(c);
+    if (!P.list.castMask) return 0;
+    launch(kLightHitPickGen[pickVariant(c)], dim3(p.numTiles), dim3(256), p.s, nullptr, nullptr, c->dParams + c->slot, P);
+    return traceAndAddHits(c, fp, p, q);
+  }
   for (uint32_t i = 0; i < c->lights.count; ++i) {
     const RtggxLight& l = c->lights.l[i];
     if (!lightCastsRays(l)) continue;

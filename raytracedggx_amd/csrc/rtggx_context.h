@@ -323,7 +323,13 @@ struct rtggx_context {
   // add into one sum per (pixel, image) and one resolve packs it.
   bool lightReflections = false, lightReflectionsRequested = false;
   rt::ShadowQueue lightHitQueue;
-  uint32_t rayRate = 1;          // rtggx_set_ray_rate: pixels per traced ray, 1 or 4 (raytrace.hip rayGenKernel, reconstructKernel)
+  // rtggx_set_light_sampling: 0 a shadow ray per light, 1 one per surface point for all lights (lighting.hip launchLights, launchLightHits:
+  // the picking kernels in place of the per-light loops).  Stored whether or not lights are set; the frame's, the next frame's.  From the
+  // first mode-1 frame with lights:
+  //   lightPickDiff  the chosen light's finished diffuse term beside lightQueue, one float4 per ray slot
+  uint32_t lightSampling = 0, lightSamplingRequested = 0;
+  rt::DevBuf<float> lightPickDiff;
+  uint32_t rayRate = 1;         // rtggx_set_ray_rate: pixels per traced ray, 1 or 4 (raytrace.hip rayGenKernel, reconstructKernel)
   uint32_t maxDepth = 1, depthRequested = 1;      // rtggx_set_max_recursion_depth: 1..4 levels of rays per path (raytrace.hip launchShade); the frame's, the next frame's
   // rtggx_set_samples_per_pixel: 1, 2, 4 or 8 samples per covered pixel (raytrace.hip launchShade; DESIGN.md "Samples per pixel"); the
   // frame's, the next frame's.  Everything below exists from the first N > 1 on (context.hip allocSamples):
