@@ -830,6 +830,54 @@ int  rtggx_set_light_reflections(rtggx_context* ctx, int enable);
  * mostly occluded still draws its share of rays.  tests/light_pick_ref.cpp restates the rule. */
 int  rtggx_set_light_sampling(rtggx_context* ctx, int mode);
 
+/* The pick of mode 1 weighted by what the pixel remembers: one visibility estimate per light per pixel, carried from frame to frame along the
+ * velocity buffer, updated with the outcome of the one shadow ray the pixel traces anyway, and multiplied into each light's pick weight, above
+ * a floor.  Every candidate keeps a non-zero probability and the term is divided by that probability: the expectation is the sum of mode 0
+ * whatever the history holds, stale or wrong -- a bad reprojection costs variance, never bias.  One more 16-byte load and store per pixel, no
+ * new ray and no new launch.
+ * enable 0 (default) / 1; anything else is refused and the setting kept.  The setting is stored always.  It acts only in frames that run the
+ * primary pass of mode 1 (rtggx_set_light_sampling(ctx, 1)) with at least one casting light -- an acting frame --, and takes effect with the
+ * next rtggx_render_visibility.  The hit passes under rtggx_set_light_reflections keep mode 1's rule unchanged.  Opt-in: a context that never
+ * enables it allocates and launches exactly what it did.  Whole frames only, because a reprojected tap may lie in another rank's rows:
+ * enabling on a context with a strip is refused, and so is rtggx_set_strip with a strip on an enabled context.  The first acting frame
+ * allocates two images of W x H records (RtggxLightVisRecord, 16 bytes), zeroed, released by rtggx_destroy.
+ * The sequence.  s counts the acting frames of the context and starts at 0; an acting frame first does s = s + 1.  s0 is the value of s at
+ * the last reset; resets are: the allocation, every successful rtggx_set_lights, every successful rtggx_set_light_sampling, and every change
+ * of this setting.  The frame writes image s & 1 and reads image (s - 1) & 1.  Behaviour after s passes 2^24 is not specified.
+ * Per covered pixel (x, y) of the pass, in fp32 without contraction, each operation rounded on its own, with the operator definitions of
+ * rtggx_set_lights:
+ *   1. step 0 and the candidates w_i exactly as in step 1 of mode 1's primary pass;
+ *   2. the history.  (vx, vy) are the two halves of the frame's own RTGGX_BUF_VELOCITY word (binary16, vx the low one); qx = floor(((float)x + 0.5f) - vx (float)W),
+ *      qy likewise with H.  R is the record at (qx, qy) of the image read.  The history is valid iff s - 1 > s0; 0 <= qx < W and
+ *      0 <= qy < H; R.stamp >> 8 == (s - 1) & 0xFFFFFF; (R.stamp & 0xFF) == inst + 1; and dot(n(R.normal), n(this pixel's normal word)) >=
+ *      0.9f, where n() is the decode the spatial filters use: n(word)_k = (float)(2 q_k - 1023) / 1023 of the word's three 10-bit fields --
+ *      evaluated as I >= 0.9f * 1046529.0f (the constant rounded once) with I the dot of the integers 2 q_k - 1023, which is exact.  If
+ *      valid v_i = R.v[i]; otherwise v_i = 255 for every i;
+ *   3. the weights.  u_i = w_i (float)max(v_i, RTGGX_LIGHT_VIS_FLOOR) for the candidates; a light that is not a candidate has no weight.
+ *      U = ((+0 + u_a) + u_b) + ..., ascending.  With no candidate there is no ray and no term.  The record is written in every case: the
+ *      carried v, this pixel's normal word, and stamp = (s & 0xFFFFFF) << 8 | (inst + 1);
+ *   4. draw, pick and f are mode 1's steps 3-5 with u in place of w and U in place of W: the same slot 96, the same "first candidate with
+ *      t < c, else the last", and f = U / u_i.  With a single candidate f is exactly 1;
+ *   5. target, ray and term are mode 1's steps 6-7 unchanged: S0 = spec_i f, S1 = diff_i f;
+ *   6. the update, only where a shadow ray was traced ("no ray" -- below the horizon, ds2 < 1e-6 -- leaves v as carried).  For the chosen
+ *      light, in integers: unoccluded v' = v + ((255 - v + 3) >> 2); occluded v' = v - ((v + 3) >> 2).  0 and 255 are reached exactly and
+ *      are fixed points.  The other seven bytes keep the carried value.
+ * Pixels that are not covered write nothing, and neither do waves that leave on a zero tile word; the stamp is what keeps their old records
+ * from being read as history.  There are no atomics: a pixel writes only its own record and reads only the other image; the two images and
+ * both traced images are a pure function of the frame sequence.
+ * Known limits: the hits are not covered (a path's hit has no velocity to follow); the floor means a light that leaves shadow is noticed
+ * only at 1/16 of its share; the estimates are per pixel and not filtered over neighbours.  tests/light_vis_ref.cpp restates the rule. */
+#define RTGGX_LIGHT_VIS_FLOOR 16u      /* policy default, not a measurement */
+typedef struct RtggxLightVisRecord {   /* 16 bytes */
+  uint8_t  v[8];      /* v[i]: visibility estimate of light i, 0 .. 255 */
+  uint32_t normal;    /* the frame's RTGGX_BUF_NORMAL word of the pixel */
+  uint32_t stamp;     /* (s & 0xFFFFFF) << 8 | (inst + 1); 0: never written */
+} RtggxLightVisRecord;
+int  rtggx_set_light_pick_visibility(rtggx_context* ctx, int enable);   /* 0 (default) / 1; anything else refused, setting kept */
+/* Synchronises and copies image 0 or 1 of the records (W x H, row by row) to out; *sequence (may be NULL) receives the context's s.  It fails
+ * before anything is allocated (before the first acting frame), for an image other than 0 or 1, and when bytes is not W H 16. */
+int  rtggx_read_light_visibility(rtggx_context* ctx, uint32_t image /* 0, 1 */, RtggxLightVisRecord* out, size_t bytes, uint32_t* sequence);
+
 /* The sun from the environment: finds the sun in the current cube, measures its direction and irradiance -- what rtggx_set_sun wants -- and,
  * where asked, takes it out of the cube, so that a probe with a sun in it does not light the scene twice (once analytically, with shadows, and
  * once more through the environment lookups, the SH irradiance and every level of the chain).  A setup call, not per frame; opt-in: a context

@@ -43,7 +43,8 @@ EXPORTS = ["rtggx_last_error", "rtggx_create", "rtggx_destroy", "rtggx_set_strip
            "rtggx_set_reference", "rtggx_reference_from_accumulation", "rtggx_set_scoring", "rtggx_read_scores",
            "rtggx_set_env_image", "rtggx_generate_env_mips", "rtggx_prefilter_env",
            "rtggx_set_sample_map", "rtggx_read_sample_map", "rtggx_trace_occlusion", "rtggx_set_sun", "rtggx_set_sun_reflections",
-           "rtggx_sun_from_env", "rtggx_set_sun_angle", "rtggx_set_lights", "rtggx_set_light_reflections", "rtggx_set_light_sampling"]
+           "rtggx_sun_from_env", "rtggx_set_sun_angle", "rtggx_set_lights", "rtggx_set_light_reflections", "rtggx_set_light_sampling",
+           "rtggx_set_light_pick_visibility", "rtggx_read_light_visibility"]
 SCORE_RING = 256
 
 
@@ -90,6 +91,10 @@ class Light(C.Structure):
     def of(cls, position, intensity, range, radius=0.0, axis=(0.0, 0.0, 0.0), cos_outer=-1.0, cos_inner=1.0):
         return cls((C.c_float * 3)(*position), range, (C.c_float * 3)(*intensity), radius, (C.c_float * 3)(*axis), cos_outer, cos_inner)
 
+
+LIGHT_VIS_FLOOR = 16      # RTGGX_LIGHT_VIS_FLOOR
+# RtggxLightVisRecord (rtggx.h), 16 bytes: eight visibility bytes, the pixel's normal word, the stamp
+LIGHT_VIS_RECORD = np.dtype([("v", np.uint8, 8), ("normal", np.uint32), ("stamp", np.uint32)])
 
 _lib = None
 
@@ -161,6 +166,8 @@ def load():
     L.rtggx_set_lights.argtypes = [vp, C.POINTER(Light), C.c_uint32]
     L.rtggx_set_light_reflections.argtypes = [vp, C.c_int]
     L.rtggx_set_light_sampling.argtypes = [vp, C.c_int]
+    L.rtggx_set_light_pick_visibility.argtypes = [vp, C.c_int]
+    L.rtggx_read_light_visibility.argtypes = [vp, C.c_uint32, vp, C.c_size_t, C.POINTER(C.c_uint32)]
     L.rtggx_sun_from_env.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_int, C.POINTER(SunEstimate)]
     L.rtggx_ray_total.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
     L.rtggx_kernel_times.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
@@ -643,6 +650,19 @@ class Context:
         """0: every light traces its own shadow ray; 1: one shadow ray per surface point for all lights, the light picked by the luminance it
         would contribute unshadowed (include/rtggx.h has the rule).  From the next frame on; it acts only while lights are set."""
         self._check(self.L.rtggx_set_light_sampling(self.h, int(mode)))
+
+    def set_light_pick_visibility(self, enable):
+        """Mode 1's pick weighted by the visibility each pixel remembers per light (0 / 1; include/rtggx.h has the rule).  From the next
+        frame on; it acts only in mode-1 frames with a casting light; whole frames only."""
+        self._check(self.L.rtggx_set_light_pick_visibility(self.h, int(enable)))
+
+    def read_light_visibility(self, image):
+        """(records, sequence): image 0 or 1 of the records as a LIGHT_VIS_RECORD array [H, W], and the context's s.  Raises before the
+        first acting frame."""
+        a = np.zeros((self.H, self.W), LIGHT_VIS_RECORD)
+        seq = C.c_uint32()
+        self._check(self.L.rtggx_read_light_visibility(self.h, int(image), _p(a), a.nbytes, C.byref(seq)))
+        return a, seq.value
 
     def sun_from_env(self, cone=0, ring=0, min_contrast=0, remove=False):
         """The sun of the current environment (include/rtggx.h): the record as a dict (SunEstimate.as_dict) -- "direction" and "irradiance" are

@@ -239,6 +239,7 @@ int rtggx_set_strip(rtggx_context* c, uint32_t rowBegin, uint32_t rowEnd) {
   if (rowBegin > rowEnd || rowEnd > c->H) { setError("rtggx_set_strip: bad rows [%u,%u) for height %u", rowBegin, rowEnd, c->H); return -1; }
   if (c->rayRate != 1u && (rowBegin > 0u || rowEnd < c->H)) { setError("rtggx_set_strip: rows [%u,%u) of %u: a context tracing one pixel in %u renders whole frames", rowBegin, rowEnd, c->H, c->rayRate); return -1; }
   if ((c->sampleMap >= 0 || c->sampleMapRequested >= 0) && (rowBegin > 0u || rowEnd < c->H)) { setError("rtggx_set_strip: rows [%u,%u) of %u on a context with a sample map (rtggx_set_sample_map): a strip's tiles count from its first row, a block would no longer be a bin -- whole frames only", rowBegin, rowEnd, c->H); return -1; }
+  if ((c->lightVis || c->lightVisRequested) && (rowBegin > 0u || rowEnd < c->H)) { setError("rtggx_set_strip: rows [%u,%u) of %u on a context with the pick's visibility records (rtggx_set_light_pick_visibility): a reprojected tap may lie in another rank's rows -- whole frames only", rowBegin, rowEnd, c->H); return -1; }
   c->rowBegin = rowBegin; c->rowEnd = rowEnd; c->toneMapDone = false;
   c->sky.breakRuns(SkyBreak::Strip);
   return 0;
@@ -498,6 +499,7 @@ int rtggx_set_lights(rtggx_context* c, const RtggxLight* lights, uint32_t count)
   }
   next.count = count;
   c->lightsRequested = next;
+  c->lightVisSeq0 = c->lightVisSeq;      // rtggx_set_light_pick_visibility: a reset -- the next acting frame has no valid history
   return 0;
 }
 // The lights at the surfaces the paths hit (include/rtggx.h).  Only the value is kept: it is stored whether or not lights are set, allocates
@@ -516,6 +518,30 @@ int rtggx_set_light_sampling(rtggx_context* c, int mode) {
   RT_CHECK_CTX(c);
   if (mode != 0 && mode != 1) { setError("rtggx_set_light_sampling: mode %d: 0 (a shadow ray per light) or 1 (one for all lights)", mode); return -1; }
   c->lightSamplingRequested = (uint32_t)mode;
+  c->lightVisSeq0 = c->lightVisSeq;      // rtggx_set_light_pick_visibility: a reset
+  return 0;
+}
+// The pick weighted by the pixel's remembered visibility (include/rtggx.h).  Only the value is kept: it allocates nothing here (the first
+// acting frame does: lighting.hip launchLights) and takes effect with the next rtggx_render_visibility.  A change of the setting is a reset
+// of the sequence.  No synchronisation, no end of a still-sky run, no reset of an accumulation, as for the mode.
+int rtggx_set_light_pick_visibility(rtggx_context* c, int enable) {
+  RT_CHECK_CTX(c);
+  if (enable != 0 && enable != 1) { setError("rtggx_set_light_pick_visibility: %d: 0 or 1", enable); return -1; }
+  if (enable == 1 && (c->rowBegin > 0u || c->rowEnd < c->H)) { setError("rtggx_set_light_pick_visibility: on a strip (rows [%u,%u) of %u): a reprojected tap may lie in another rank's rows -- whole frames only", c->rowBegin, c->rowEnd, c->H); return -1; }
+  if ((enable == 1) != c->lightVisRequested) c->lightVisSeq0 = c->lightVisSeq;
+  c->lightVisRequested = enable == 1;
+  return 0;
+}
+// One of the two images of records, behind everything the context has enqueued
+int rtggx_read_light_visibility(rtggx_context* c, uint32_t image, RtggxLightVisRecord* out, size_t bytes, uint32_t* sequence) {
+  RT_CHECK_CTX(c);
+  if (image > 1u) { setError("rtggx_read_light_visibility: image %u: 0 or 1", image); return -1; }
+  if (!c->lightVisImg[image]) { setError("rtggx_read_light_visibility: no records yet: they exist from the first frame of mode 1 with a casting light and rtggx_set_light_pick_visibility(ctx, 1)"); return -1; }
+  const size_t want = (size_t)c->W * c->H * sizeof(RtggxLightVisRecord);
+  if (!out || bytes != want) { setError("rtggx_read_light_visibility: %zu bytes at %p: %u x %u records of 16 bytes are %zu", bytes, (void*)out, c->W, c->H, want); return -1; }
+  RT_HIP(syncStreams(c));
+  RT_HIP(hipMemcpy(out, c->lightVisImg[image], want, hipMemcpyDeviceToHost));
+  if (sequence) *sequence = c->lightVisSeq;
   return 0;
 }
 // Sums and count back to zero: two clears on the main stream, behind the frames it holds and in front of the next one; nothing waits.

@@ -195,7 +195,7 @@ int rtggx_render_visibility(rtggx_context* c) {
   if (!c->shDone && c->env.texels) { const int r = projectSH(c, c->streamAS); if (r) return r; }   // first frame only, RayTracer.cpp:345-350
   settleSetRead(c);      // (the previous frame ended without the kernel that would have carried its set's event)
   ++c->frameCounter;
-  c->maxDepth = c->depthRequested; c->samples = c->samplesRequested; c->accumulate = c->accumulateRequested; c->sun = c->sunRequested; c->sunAngle = c->sunAngleRequested; c->sunReflections = c->sunReflectionsRequested; c->lights = c->lightsRequested; c->lightReflections = c->lightReflectionsRequested; c->lightSampling = c->lightSamplingRequested;
+  c->maxDepth = c->depthRequested; c->samples = c->samplesRequested; c->accumulate = c->accumulateRequested; c->sun = c->sunRequested; c->sunAngle = c->sunAngleRequested; c->sunReflections = c->sunReflectionsRequested; c->lights = c->lightsRequested; c->lightReflections = c->lightReflectionsRequested; c->lightSampling = c->lightSamplingRequested; c->lightVis = c->lightVisRequested;
   c->scoring = c->scoringRequested && c->reference != nullptr;
   c->sampleMap = c->sampleMapRequested;      // rtggx_set_sample_map: the setter has waited for every stream and written the copy no frame reads
   bool resendConstants = false;

@@ -1,6 +1,7 @@
 // Direct lighting: the sun (rtggx_set_sun, rtggx_set_sun_angle), the local lights (rtggx_set_lights) and both at the surfaces the paths hit
 // (rtggx_set_sun_reflections, rtggx_set_light_reflections); one shadow ray for all lights (rtggx_set_light_sampling: the two picking kernels
-// further down, with a table of their own).  include/rtggx.h has the per-pixel rules, DESIGN.md section 9 the structure.
+// further down, with a table of their own; rtggx_set_light_pick_visibility: the primary pair of them once more, with a record per pixel).
+// include/rtggx.h has the per-pixel rules, DESIGN.md section 9 the structure.
 //
 // Every pass is the same three launches around a queue of its own (rt::ShadowQueue, rt_queue.h): a generating kernel derives a surface --
 // the primary one from the visibility word, or the hit of a traced ray -- and, where a light reaches it, compacts ONE shadow ray into the
@@ -605,6 +606,108 @@ __global__ void __launch_bounds__(256) lightPickAddKernel(const FrameParams* __r
     A.sumDiff[rr.pixel] = make_float4(s1.x + d.x, s1.y + d.y, s1.z + d.z, s1.w + 1.0f);
   }
 }
+// ---- the pick and what the pixel remembers (rtggx_set_light_pick_visibility; DESIGN.md section 9 under that title) -----------------------------
+// The picking pair of the primary pass once more, with a record per pixel (RtggxLightVisRecord: eight visibility bytes, the normal word, a
+// stamp) in two images that alternate by the sequence number s: lightPickVisGenKernel follows the frame's velocity word to the record the
+// previous acting frame wrote, takes its eight bytes where the record is that frame's, that instance's and of a like normal (255 each
+// otherwise), writes the pixel's own record with them and multiplies every candidate's weight by max(v_i, RTGGX_LIGHT_VIS_FLOOR) before the
+// draw; the chosen index travels in the shadow ray's flags word.  lightPickVisAddKernel moves the chosen light's byte a quarter of the way
+// to 255 or to 0 by what the ray met -- a read-modify-write of one word of the pixel's own record -- and adds as lightPickAddKernel does.
+// The eight bytes stay two registers: the unrolled loop shifts them out by constants.
+struct LightVisArgs {
+  const uint32_t* normal; const uint32_t* velocity;      // the frame's own G-buffer words (the current input set)
+  const uint4* prev; uint4* next;                        // the image read ((s - 1) & 1) and the image written (s & 1)
+  uint32_t prevSeq, stampHigh, history;                  // (s - 1) & 0xFFFFFF; (s & 0xFFFFFF) << 8; s - 1 > s0
+};
+RT_DEV float visByteWeight(uint32_t lo, uint32_t hi, uint32_t i) {      // (float)max(v_i, floor); i is a constant where this is inlined
+  const uint32_t v = ((i < 4u ? lo : hi) >> (8u * (i & 3u))) & 0xFFu;
+  return (float)max(v, RTGGX_LIGHT_VIS_FLOOR);
+}
+RT_DEV int visNormalDot(uint32_t a, uint32_t b) {      // the dot of the spatial filters' decode (denoise.hip loadG): integers, 1023^2 is one
+  const int ax = 2 * (int)(a & 1023u) - 1023, ay = 2 * (int)((a >> 10) & 1023u) - 1023, az = 2 * (int)((a >> 20) & 1023u) - 1023;
+  const int bx = 2 * (int)(b & 1023u) - 1023, by = 2 * (int)((b >> 10) & 1023u) - 1023, bz = 2 * (int)((b >> 20) & 1023u) - 1023;
+  return ax * bx + ay * by + az * bz;
+}
+template <bool CONE, bool SOFT>
+__global__ void __launch_bounds__(256) lightPickVisGenKernel(const FrameParams* __restrict__ fpp, LightPickGenArgs A, LightVisArgs R) {
+  const FrameParams& fp = *fpp;
+  const uint32_t tile = blockIdx.x;
+  if (tileIsEmpty(A.tileWords, tile)) return;
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const uint32_t px = (tile % A.tilesX) * 16 + (wave & 1u) * 8 + (lane & 7u);
+  const uint32_t py = A.rowBegin + (tile / A.tilesX) * 16 + (wave >> 1) * 8 + (lane >> 3);
+  bool want = false, wantDiff = false;
+  RayRec rr;
+  float tmax = 0.0f;
+  f3 S1 = mk3(0.0f, 0.0f, 0.0f);
+  if (px < fp.W && py < A.rowEnd && py < fp.H) atPrimarySurface(fp, A.visDepth, A.fat0, A.fat1, px, py, [&](const PrimarySurface& s) {
+    const bool diffuse = s.rm.y < 1.0f;
+    // step 2: the history, along the frame's own velocity
+    const uint32_t nrm = R.normal[s.pixel], vel = R.velocity[s.pixel];
+    const float qx = floorf(((float)px + 0.5f) - f16ToF32(vel & 0xFFFFu) * (float)fp.W), qy = floorf(((float)py + 0.5f) - f16ToF32(vel >> 16) * (float)fp.H);
+    uint32_t lo = 0xFFFFFFFFu, hi = 0xFFFFFFFFu;
+    if (R.history != 0u && qx >= 0.0f && qx < (float)fp.W && qy >= 0.0f && qy < (float)fp.H) {
+      const uint4 rec = R.prev[(size_t)(uint32_t)qy * fp.W + (uint32_t)qx];
+      if ((rec.w >> 8) == R.prevSeq && (rec.w & 0xFFu) == s.inst + 1u && (float)visNormalDot(rec.z, nrm) >= 0.9f * 1046529.0f) { lo = rec.x; hi = rec.y; }
+    }
+    R.next[s.pixel] = make_uint4(lo, hi, nrm, R.stampHigh | (s.inst + 1u));
+    // steps 1 and 3: the eight weights times what the pixel remembers, U
+    float u[RTGGX_MAX_LIGHTS];
+    float U = 0.0f;
+#pragma unroll
+    for (uint32_t i = 0; i < RTGGX_MAX_LIGHTS; ++i) {
+      u[i] = 0.0f;
+      if ((A.list.castMask >> i) & 1u) {
+        const float w = primaryPickTerms<CONE>(A.list.light[i], s, diffuse).w;
+        if (w > 0.0f) u[i] = w * visByteWeight(lo, hi, i);
+      }
+      U = U + u[i];      // (a weight of +0 leaves U as it is)
+    }
+    if (!(U > 0.0f)) return;      // no candidate
+    // step 4: mode 1's draw, pick and f on u
+    const float t = pickDraw(s.pixel, fp.g.FrameIndex, RT_SLOT_LIGHT_PICK) * U;
+    float uc = 0.0f;
+    const uint32_t chosen = pickLight(u, t, uc);
+    const float f = U / uc;
+    // step 5: mode 1's steps 6 and 7; the chosen index in the record's flags word, for the update
+    const LightArgs K = chosenLight(A.list, chosen);
+    LightSample l;
+    if (!chosenLightSample<CONE, SOFT>(K, A.list.cosSin, s.P, s.N, s.pixel, fp.g.FrameIndex, RT_SLOT_LIGHT(chosen), l)) return;
+    const PickTerms x = primaryPickTerms<CONE>(K, s, diffuse);
+    want = true; wantDiff = diffuse;
+    tmax = l.tmax;
+    rr = shadowRay(s.P, l.Ls, s.pixel, (s.inst << 24) | s.prim, mk3(x.spec.x * f, x.spec.y * f, x.spec.z * f), chosen);
+    S1 = mk3(x.diff.x * f, x.diff.y * f, x.diff.z * f);
+  });
+  const uint32_t bin = blockIdx.x * 4u + wave;
+  const unsigned long long wanting = __ballot(want);      // (the slot compactShadowRay gives the lane)
+  if (wantDiff) A.diffTerm[(size_t)bin * RT_BIN_MIN + (uint32_t)__popcll(wanting & ((1ull << lane) - 1ull))] = make_float4(S1.x, S1.y, S1.z, 0.0f);
+  const uint32_t n = compactShadowRay<true>(want, rr, tmax, A.rays, A.hits, A.tRange, bin, RT_BIN_MIN, 0u, lane);
+  if (lane == 0) A.binCount[bin] = n;
+}
+// lightPickAddKernel with step 6: every slot below the bin's count updates its pixel's record, occluded or not
+__global__ void __launch_bounds__(256) lightPickVisAddKernel(const FrameParams* __restrict__ fpp, LightPickAddArgs A, uint32_t* records) {
+  const FrameParams& fp = *fpp;
+  if (tileIsEmpty(A.tileWords, blockIdx.x)) return;
+  const uint32_t bin = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (lane >= A.binCount[bin]) return;
+  const size_t k = (size_t)bin * RT_BIN_MIN + lane;
+  const bool occluded = hitKeyId(A.hits[k]) != 0xFFFFFFFFu;
+  const RayRec rr = A.rays[k];
+  const uint32_t chosen = rr.flags & 7u, shift = 8u * (chosen & 3u);
+  uint32_t* const word = records + 4u * (size_t)rr.pixel + (chosen >> 2);      // the pixel's own record: no other lane has this pixel
+  const uint32_t old = *word, v = (old >> shift) & 0xFFu;
+  const uint32_t next = occluded ? v - ((v + 3u) >> 2) : v + ((255u - v + 3u) >> 2);
+  *word = (old & ~(0xFFu << shift)) | (next << shift);
+  if (occluded) return;      // no term
+  const uint32_t inst = rr.skip >> 24;
+  const float4 s0 = A.sumRefl[rr.pixel];
+  A.sumRefl[rr.pixel] = make_float4(s0.x + rr.wx, s0.y + rr.wy, s0.z + rr.wz, s0.w + 1.0f);
+  if (fp.mat.RoughMetals[inst][1] < 1.0f) {      // (lightAddKernel)
+    const float4 d = A.diffTerm[k], s1 = A.sumDiff[rr.pixel];
+    A.sumDiff[rr.pixel] = make_float4(s1.x + d.x, s1.y + d.y, s1.z + d.z, s1.w + 1.0f);
+  }
+}
 // The context's list as the picking kernels take it, and the instance [2 cone + soft] the list runs (see above)
 static uint32_t pickVariant(const rtggx_context* c) {
   uint32_t v = 0u;
@@ -624,6 +727,7 @@ static LightListArgs pickList(const rtggx_context* c) {
   return L;
 }
 static void (*const kLightPickGen[4])(const FrameParams*, LightPickGenArgs) = {lightPickGenKernel<false, false>, lightPickGenKernel<false, true>, lightPickGenKernel<true, false>, lightPickGenKernel<true, true>};
+static void (*const kLightPickVisGen[4])(const FrameParams*, LightPickGenArgs, LightVisArgs) = {lightPickVisGenKernel<false, false>, lightPickVisGenKernel<false, true>, lightPickVisGenKernel<true, false>, lightPickVisGenKernel<true, true>};
 
 int launchLights(rtggx_context* c, const FrameParams& fp, hipStream_t s) {
   uint32_t rb, re;
@@ -655,7 +759,24 @@ int launchLights(rtggx_context* c, const FrameParams& fp, hipStream_t s) {
     P.rays = G.rays; P.hits = G.hits; P.binCount = G.binCount; P.tRange = G.tRange; P.diffTerm = (float4*)c->lightPickDiff.get();
     P.tileWords = G.tileWords; P.tilesX = tilesX; P.rowBegin = rb; P.rowEnd = re;
     P.list = pickList(c);
-    if (P.list.castMask) {
+    if (P.list.castMask && c->lightVis) {      // rtggx_set_light_pick_visibility: an acting frame -- the same three launches with the records
+      if (rb > 0u || re < fp.H) { setError("rtggx_ray_trace: the pick's visibility records on rows [%u,%u) of %u: whole frames only", rb, re, fp.H); return -1; }
+      if (!c->lightVisImg[0] || !c->lightVisImg[1]) {      // the allocation is a reset
+        for (auto& img : c->lightVisImg) if (!img) RT_HIP(allocFilled(img, (size_t)c->W * c->H * 4u));
+        { const int r = syncFills(true); if (r) return r; }
+        c->lightVisSeq0 = c->lightVisSeq;
+      }
+      const uint32_t seq = ++c->lightVisSeq;
+      LightVisArgs R;
+      R.normal = set.normal; R.velocity = set.velocity;
+      R.prev = (const uint4*)c->lightVisImg[(seq - 1u) & 1u].get(); R.next = (uint4*)c->lightVisImg[seq & 1u].get();
+      R.prevSeq = (seq - 1u) & 0xFFFFFFu; R.stampHigh = (seq & 0xFFFFFFu) << 8; R.history = seq - 1u > c->lightVisSeq0 ? 1u : 0u;
+      launch(kLightPickVisGen[pickVariant(c)], dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, P, R);
+      { const int r = launchTrace(c, fp, s, q, numTiles * 4u, true, tilesX, tilesY, c->traceGrid[3], -1, nullptr, nullptr, 2, true); if (r) return r; }
+      const LightPickAddArgs PD{q.rays, q.hits, q.binCount, G.tileWords, P.diffTerm, D.sumRefl, D.sumDiff};
+      launch(lightPickVisAddKernel, dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, PD, (uint32_t*)R.next);
+      RT_HIP(hipGetLastError());
+    } else if (P.list.castMask) {
       launch(kLightPickGen[pickVariant(c)], dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, P);
       { const int r = launchTrace(c, fp, s, q, numTiles * 4u, true, tilesX, tilesY, c->traceGrid[3], -1, nullptr, nullptr, 2, true); if (r) return r; }
       const LightPickAddArgs PD{q.rays, q.hits, q.binCount, G.tileWords, P.diffTerm, D.sumRefl, D.sumDiff};

@@ -329,6 +329,15 @@ struct rtggx_context {
   //   lightPickDiff  the chosen light's finished diffuse term beside lightQueue, one float4 per ray slot
   uint32_t lightSampling = 0, lightSamplingRequested = 0;
   rt::DevBuf<float> lightPickDiff;
+  // rtggx_set_light_pick_visibility: the pick weighted by the pixel's remembered visibility (lighting.hip launchLights: the Vis kernels in
+  // place of the picking pair of the primary pass).  Stored always; the frame's, the next frame's.  From the first acting frame (mode 1, a
+  // casting light, the setting on):
+  //   lightVisImg    two images of W x H RtggxLightVisRecord (four words each); frame s writes [s & 1] and reads [(s - 1) & 1]
+  //   lightVisSeq    s, the number of acting frames; lightVisSeq0: s at the last reset (the setters, the allocation)
+  // The records are not per input set: consecutive frames' passes follow each other on the main stream.
+  bool lightVis = false, lightVisRequested = false;
+  uint32_t lightVisSeq = 0, lightVisSeq0 = 0;
+  rt::DevBuf<uint32_t> lightVisImg[2];
   uint32_t rayRate = 1;         // rtggx_set_ray_rate: pixels per traced ray, 1 or 4 (raytrace.hip rayGenKernel, reconstructKernel)
   uint32_t maxDepth = 1, depthRequested = 1;      // rtggx_set_max_recursion_depth: 1..4 levels of rays per path (raytrace.hip launchShade); the frame's, the next frame's
   // rtggx_set_samples_per_pixel: 1, 2, 4 or 8 samples per covered pixel (raytrace.hip launchShade; DESIGN.md "Samples per pixel"); the

@@ -41,6 +41,7 @@ void RayTracedGGX::OnInit() {
   if (!m_lights.empty() && !m_rayTracer->SetLights(m_lights.data(), (uint32_t)m_lights.size())) throw std::runtime_error("-light / -spot: " + m_rayTracer->GetLastError());      // -light, -spot: local lights with ray-traced shadows (opt-in)
   if (m_lightReflections && !m_rayTracer->SetLightReflections(true)) throw std::runtime_error("-lightreflections: " + m_rayTracer->GetLastError());      // -lightreflections: ... at the surfaces the paths hit as well (opt-in)
   if (m_lightPick && !m_rayTracer->SetLightSampling(1)) throw std::runtime_error("-lightpick: " + m_rayTracer->GetLastError());      // -lightpick: one shadow ray per surface point for all lights (opt-in)
+  if (m_lightVisibility && !m_rayTracer->SetLightPickVisibility(true)) throw std::runtime_error("-lightvisibility: " + m_rayTracer->GetLastError());      // -lightvisibility: the pick weighted by what the pixel remembers (opt-in)
   if (m_sunAngle != 0.0f && !m_rayTracer->SetSunAngle(m_sunAngle)) throw std::runtime_error("-sunangle: " + m_rayTracer->GetLastError());      // -sunangle: a sun with a size, soft shadows (opt-in)
   if (m_recursionDepth != 1u && !m_rayTracer->SetMaxRecursionDepth(m_recursionDepth)) throw std::runtime_error("-recursion: " + m_rayTracer->GetLastError());      // -recursion N: multi-bounce paths (opt-in)
   if (m_samplesPerPixel != 1u && !m_rayTracer->SetSamplesPerPixel(m_samplesPerPixel)) throw std::runtime_error("-spp: " + m_rayTracer->GetLastError());      // -spp N: multi-sample tracing (opt-in)
@@ -213,7 +214,7 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
     return (arg[0] == '-' || arg[0] == '/') && lower(arg + 1) == lower(name);
   };
   // On POSIX an absolute path also starts with '/': such a token is a flag only when it names one.
-  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "sun", "sunreflections", "sunfromenv", "sunangle", "light", "spot", "lightreflections", "lightpick", "recursion", "spp", "accumulate", "sampleset", "savereference", "reference", "score", "envlayout", "envsize", "envmips", "envprefilter"};
+  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "sun", "sunreflections", "sunfromenv", "sunangle", "light", "spot", "lightreflections", "lightpick", "lightvisibility", "recursion", "spp", "accumulate", "sampleset", "savereference", "reference", "score", "envlayout", "envsize", "envmips", "envprefilter"};
   const auto isFlagName = [&](const char* name) { for (const char* f : kFlags) if (lower(name) == f) return true; return false; };
   const auto hasNextArgValue = [&](int i) {
     if (i + 1 >= argc) return false;
@@ -269,6 +270,7 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
     else if (isArgMatched(i, "sunreflections")) m_sunReflections = true;      // (without -sun: refused below, once the whole line is read)
     else if (isArgMatched(i, "lightreflections")) m_lightReflections = true;      // (without -light / -spot: refused below, once the whole line is read)
     else if (isArgMatched(i, "lightpick")) m_lightPick = true;      // (without -light / -spot: refused below, once the whole line is read)
+    else if (isArgMatched(i, "lightvisibility")) m_lightVisibility = true;      // (without -lightpick, or with strips: refused below, once the whole line is read)
     // -sunfromenv [degrees]: the sun measured from the -env cube and taken out of it (rtggx_sun_from_env, RayTracer::Init); the half-angle
     // of the cone is checked here, before a device is asked for; without a number it is the library's default
     else if (isArgMatched(i, "sunfromenv")) {
@@ -381,6 +383,9 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
   if (m_lightReflections && m_lights.empty()) throw std::runtime_error("-lightreflections without -light or -spot: there is no light to reflect");
   // one ray for all lights (rtggx_set_light_sampling) acts only under lights: the same rule
   if (m_lightPick && m_lights.empty()) throw std::runtime_error("-lightpick without -light or -spot: there is no light to pick");
+  // the pick's visibility records (rtggx_set_light_pick_visibility) act only in mode 1, and on whole frames
+  if (m_lightVisibility && !m_lightPick) throw std::runtime_error("-lightvisibility without -lightpick: there is no pick to weight");
+  if (m_lightVisibility && (m_gpus > 1 || m_strips > 1)) throw std::runtime_error("-lightvisibility: whole frames only, not with -gpus N > 1 or -strips N > 1");
   if (m_rayRate != 1u && !m_lights.empty()) throw std::runtime_error("-light / -spot together with -rayrate 4: refused");
   if (m_rayRate != 1u && m_samplesPerPixel != 1u) throw std::runtime_error("-spp N > 1 together with -rayrate 4: refused");
   if (m_rayRate != 1u && (m_gpus > 1 || m_strips > 1)) throw std::runtime_error("-rayrate 4: whole frames only, not with -gpus N > 1 or -strips N > 1");

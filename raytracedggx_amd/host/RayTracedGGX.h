@@ -2,7 +2,7 @@
 // DXFramework virtuals RayTracedGGX/Common/DXFramework.h:23-26): OnInit / OnUpdate / OnRender /
 // OnDestroy, the same command line (RayTracedGGX.cpp:462-511) and the same defaults
 // (RayTracedGGX.cpp:37-39, camera :19-23, 267-277).  What the window supplied interactively is
-// supplied by extra flags: -width -height -frames -dt -metallic -sharedmem -sync -vndf -rayrate -sun -sunreflections -sunfromenv -sunangle -light -spot -lightreflections -lightpick -recursion -spp -sampleset -accumulate -savereference -reference -score -envlayout -envsize -envmips -envprefilter -device -dump -track -deform -gpus -strips -balance.
+// supplied by extra flags: -width -height -frames -dt -metallic -sharedmem -sync -vndf -rayrate -sun -sunreflections -sunfromenv -sunangle -light -spot -lightreflections -lightpick -lightvisibility -recursion -spp -sampleset -accumulate -savereference -reference -score -envlayout -envsize -envmips -envprefilter -device -dump -track -deform -gpus -strips -balance.
 #pragma once
 #include <vector>
 #include <cstdint>
@@ -150,6 +150,7 @@ class RayTracedGGX {
   std::vector<RtggxLight> m_lights;
   bool m_lightReflections = false;    // -lightreflections: the lights at the surfaces seen in reflections as well (RayTracer::SetLightReflections); needs -light or -spot
   bool m_lightPick = false;           // -lightpick: one shadow ray per surface point for all lights (RayTracer::SetLightSampling(1)); needs -light or -spot
+  bool m_lightVisibility = false;     // -lightvisibility: the pick weighted by the visibility each pixel remembers (RayTracer::SetLightPickVisibility); needs -lightpick; whole frames only
   uint32_t m_rayRate = 1;              // -rayrate <1|4>: pixels per traced ray (RayTracer::SetRayRate); 4 renders whole frames only: not with -gpus / -strips
   // -deform <amplitude>: the model breathes -- a travelling sine wave through its vertices, DeformPeriod key shapes computed once
   // at start-up and handed to RayTracer::UpdateMesh one per frame (per-frame host cost: one copy of the vertex array)

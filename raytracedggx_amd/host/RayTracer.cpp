@@ -120,6 +120,7 @@ bool RayTracer::SetSunAngle(float degrees) { return check(rtggx_set_sun_angle(m_
 bool RayTracer::SetLights(const RtggxLight* lights, uint32_t count) { return check(rtggx_set_lights(m_ctx, lights, count), "rtggx_set_lights"); }
 bool RayTracer::SetLightReflections(bool enable) { return check(rtggx_set_light_reflections(m_ctx, enable ? 1 : 0), "rtggx_set_light_reflections"); }
 bool RayTracer::SetLightSampling(int mode) { return check(rtggx_set_light_sampling(m_ctx, mode), "rtggx_set_light_sampling"); }
+bool RayTracer::SetLightPickVisibility(bool enable) { return check(rtggx_set_light_pick_visibility(m_ctx, enable ? 1 : 0), "rtggx_set_light_pick_visibility"); }
 bool RayTracer::SetSunReflections(bool enable) { return check(rtggx_set_sun_reflections(m_ctx, enable ? 1 : 0), "rtggx_set_sun_reflections"); }
 
 bool RayTracer::SetSamplesPerPixel(uint32_t samples) { return check(rtggx_set_samples_per_pixel(m_ctx, samples), "rtggx_set_samples_per_pixel"); }

@@ -74,6 +74,9 @@ class RayTracer {
   // One shadow ray per surface point for all lights (rtggx_set_light_sampling): 0 a ray per light (default), 1 one light picked per point; it
   // acts only while lights are set.
   bool SetLightSampling(int mode);
+  // The pick of mode 1 weighted by the visibility each pixel remembers per light (rtggx_set_light_pick_visibility); it acts only in mode 1
+  // while a light casts rays; whole frames only.
+  bool SetLightPickVisibility(bool enable);
   bool SetSamplesPerPixel(uint32_t samples);   // rtggx_set_samples_per_pixel: 1 (default), 2, 4 or 8 samples per covered pixel (-spp); not together with ray rate 4
   bool SetMaxRecursionDepth(uint32_t depth);   // rtggx_set_max_recursion_depth: 1 (default; RayTracer.cpp:605 SetMaxRecursionDepth(1)) to 4 levels of rays per path (-recursion)   // rtggx_set_ray_rate: 1 (default) or 4 -- one pixel of each 2x2 quad traced per frame, the rest reconstructed (-rayrate)
   // rtggx_set_sample_set: the size of the sample set getSampleParam draws from, 256 (default, the reference's) or a power of two up to
