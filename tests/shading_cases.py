@@ -375,3 +375,117 @@ FAMILIES = tuple(sorted({c.family for c in all_cases()}))
 
 def by_name(name):
     return next(c for c in all_cases() if c.name == name)
+
+
+# ---- runs of D levels and N samples (tests/test_shading_paths_host.py, tests/test_gpu_shading_paths.py) --------------------------------
+class PathRun:
+    """A case at recursion depth D with N samples per pixel, at the frame positions `positions` (indices into FRAMES, in order: a frame's
+    carry-over is of the one run before it)."""
+
+    def __init__(self, case, depth, samples, positions=(0, 1, 2)):
+        self.case, self.depth, self.samples, self.positions = case, depth, samples, tuple(positions)
+        self.name = "%s_d%dn%d" % (case.name, depth, samples)
+
+
+@functools.lru_cache(maxsize=None)
+def room_2_path_case():
+    """materials_2_64x48 for paths: at frame position 2 its room is a mirror (metallic 0.75) of roughness 0.02, 0.005 on the checkerboard's odd
+    cells, and at depth 2 the second bounce off such a wall takes the cancelling root twice: 2.6 % of the covered pixels are flagged, above
+    the cap.  Here the room's roughness at that position is 0.35; everything else is materials_2's (its position 1 keeps roughness 0)."""
+    base = by_name("materials_2_64x48")
+
+    def m(k):
+        (c0, r0, m0), one = base.materials(k)
+        return (c0, 0.35 if k == 2 else r0, m0), one
+    case = Case("room_2_64x48", "materials", 64, 48, room(), closed_ball(), base.world0, base.world1, base.eye, base.focus, base.cube, m, eye_step=base.eye_step)
+    return case
+
+
+@functools.lru_cache(maxsize=None)
+def path_cases():
+    """The smallest set that reaches every branch of a path (a list of its own: NAMES, FAMILIES and the depth-1 floor file do not change):
+      depth in a closed room, where every path runs to the last level          materials_0, 1, 3 and room_2 (for materials_2) at D = 2
+      all levels, both samplers                                                materials_3 and its VNDF twin at D = 3 and 4; materials_0 and 1
+                                                                               at D = 3 and 4 under either sampler; room_2 at D = 3
+      open sky: misses at level >= 1, the coincident sheets hit by a deeper ray, the apex                sheets_vertex at D = 2
+      hits on non-uniformly scaled, skewed and mirrored instances (the hit's own inverse transpose)      skew, mirrored_bias at D = 2
+      samples: 8 (frame index 255 reaches FrameIndex N + k = 2047), 4 and 2; samples x depth             sheets_vertex, materials_3, skew; materials_3 at D = 2, N = 2
+    A run of several samples uses the frame positions 0 and 2 (indices 0 and 255).  The last four are the scenes of hit_cases(): their floor
+    at the hit runs' depth is the delta of the hit stages."""
+    runs = [PathRun(by_name("materials_%d_64x48" % c), 2, 1) for c in (0, 1, 3)] + [PathRun(room_2_path_case(), 2, 1)]
+    runs += [PathRun(by_name("materials_3_64x48" + v), d, 1) for d in (3, 4) for v in ("", "_vndf")]
+    # materials_3's room is black and fully metallic: its paths end at level 1 with the preset or carry the throughput 0 -- the preset rule, and
+    # nothing else.  The levels 2 and 3 of both samplers are reached in the rooms whose walls reflect:
+    runs += [PathRun(by_name("materials_0_64x48"), 3, 1, (0, 2)), PathRun(by_name("materials_1_64x48"), 4, 1, (0, 2)),
+             PathRun(by_name("materials_1_64x48_vndf"), 3, 1, (0, 2)), PathRun(by_name("materials_0_64x48_vndf"), 4, 1, (0, 2)),
+             PathRun(by_name("materials_1_64x48"), 2, 2, (0, 2))]
+    # ... and a reflection that ends under the surface (NoL <= 0) at a level >= 1 needs a metallic wall two bounces deep
+    runs += [PathRun(room_2_path_case(), 3, 1, (0, 2))]
+    # the scenes of the hit passes (hit_cases): their floor at depth 2 is the hit stages' delta
+    runs += [PathRun(by_name("sun_75x53"), 2, 1), PathRun(by_name("lights_75x53"), 2, 1), PathRun(court_case(), 2, 1), PathRun(court_case(), 1, 1)]
+    runs += [PathRun(by_name(n), 2, 1) for n in ("sheets_vertex_96x64", "skew_75x53", "mirrored_bias_75x53")]
+    runs += [PathRun(by_name("sheets_vertex_96x64"), 1, 8, (0, 2)), PathRun(by_name("materials_3_64x48"), 1, 4, (0, 2)), PathRun(by_name("skew_75x53"), 1, 2, (0, 2)),
+             PathRun(by_name("materials_3_64x48"), 2, 2, (0, 2))]
+    assert len({r.name for r in runs}) == len(runs)
+    return tuple(runs)
+
+
+def courtyard():
+    """room() without its ceiling (the face y = +1): walls that second rays meet, under open sky for a sun."""
+    v, i = room()
+    return v, np.delete(i.reshape(-1, 3), (6, 7), axis=0).reshape(-1)
+
+
+@functools.lru_cache(maxsize=None)
+def court_case():
+    """The walled scene of the hit passes: the materials family's room without its ceiling around the ball, walls and floor with metallic 0.25
+    (the diffuse lobe, on reflection-group and on diffuse-group rays), the ball with metallic 0.75 (the mirror lobe); suns a little off
+    the zenith (no wall at NoL = 0 exactly), slanted and low (the walls' and the ball's shadows); a point light under the open top, a
+    small-range one behind the ball, a spot whose cones cross the floor, one of zero intensity."""
+    base = by_name("materials_0_64x48")
+    suns = (((0.1, 1.0, 0.05), (3.0, 2.5, 2.0)), ((0.5, 0.8, -0.3), (2.0, 2.0, 1.5)), ((1.0, 0.45, 0.2), (0.0, 2.0, 4.0)))
+    axis = np.array([0.15, -1.0, 0.1]) / np.linalg.norm([0.15, -1.0, 0.1])
+    top = dict(position=(-0.5, 1.6, 0.3), intensity=(6.0, 5.0, 4.0), range=7.0)
+    small = dict(position=(1.2, -0.2, 1.3), intensity=(1.0, 2.0, 3.0), range=1.6)
+    spot = dict(position=(0.4, 1.8, 0.2), intensity=(20.0, 20.0, 16.0), range=8.0, axis=tuple(axis), cos_outer=float(np.cos(np.radians(40.0))), cos_inner=float(np.cos(np.radians(15.0))))
+    dark = dict(position=(0.0, 0.0, 0.0), intensity=(0.0, 0.0, 0.0), range=10.0)
+    sets = ([top, spot], [top, small, dark, spot], [small, spot])
+    return Case("court_64x48", "materials", 64, 48, courtyard(), closed_ball(), base.world0, base.world1, base.eye, base.focus, smooth_cube(),
+                _fixed(((0.9, 0.8, 0.6), 0.5, 0.25), ((1.0, 0.71, 0.29), 0.3, 0.75)), eye_step=base.eye_step, sun=lambda k: suns[k], lights=lambda k: sets[k])
+
+
+class HitRun:
+    """A case at depth D, one sample, with the sun (kind "sun": rtggx_set_sun_reflections), the lights ("lights":
+    rtggx_set_light_reflections) or both at the surfaces its paths hit.  sun, lights: functions of the frame position."""
+
+    def __init__(self, case, depth, kind, sun=None, lights=None):
+        self.case, self.depth, self.samples, self.kind, self.positions = case, depth, 1, kind, (0, 1, 2)
+        self.sun = sun if kind != "lights" else None
+        self.lights = lights if kind != "sun" else None
+        self.name = "%s_d%d_%s_hits" % (case.name, depth, kind)
+
+
+@functools.lru_cache(maxsize=None)
+def hit_cases():
+    """sun_75x53 and lights_75x53 at D = 1 and 2, the sun scene with its sun and the list [A, spot] at D = 2 -- under open sky few second rays
+    meet anything there and both instances are metallic -- and the walled court at D = 2 with each and with both, which supplies every
+    class at both levels."""
+    sun, lights, court = by_name("sun_75x53"), by_name("lights_75x53"), court_case()
+    runs = [HitRun(sun, d, "sun", sun=sun.sun) for d in (1, 2)] + [HitRun(lights, d, "lights", lights=lights.lights) for d in (1, 2)]
+    runs += [HitRun(sun, 2, "both", sun=sun.sun, lights=lambda k: lights.lights(0))]
+    runs += [HitRun(court, 2, kind, sun=court.sun, lights=court.lights) for kind in ("sun", "lights", "both")]
+    return tuple(runs)
+
+
+HIT_NAMES = tuple(r.name for r in hit_cases())
+
+
+def hit_by_name(name):
+    return next(r for r in hit_cases() if r.name == name)
+
+
+PATH_NAMES = tuple(r.name for r in path_cases())
+
+
+def path_by_name(name):
+    return next(r for r in path_cases() if r.name == name)

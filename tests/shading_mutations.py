@@ -3,10 +3,11 @@ a scratch copy of the CPU oracle -- the twin line of the kernel's -- which is co
 tests/test_shading_ref_host.py (check_words against the float64 model on unflagged pixels, the GPU test's own assertion).  Bit equality with
 itself would pass every one of them; a mutation no case catches means a missing case.  Run by hand, it writes the report:
 
-    python tests/shading_mutations.py profiles/r20_shading_mutations.txt
+    python tests/shading_mutations.py depth1 profiles/r20_shading_mutations.txt
 
 The last two are lines of the sun's and the lights' restatements (tests/sun_ref.cpp, tests/lights_ref.cpp) and are judged by the stage check
-of those passes (check_direct)."""
+of those passes (check_direct).  PATH_MUTATIONS (the second report, profiles/r22_shading_path_mutations.txt) are lines of the path
+follower and the sample loop."""
 import ctypes as C
 import os
 import re
@@ -17,9 +18,11 @@ import tempfile
 
 sys.path[:0] = [os.path.dirname(os.path.abspath(__file__)), os.path.dirname(os.path.dirname(os.path.abspath(__file__)))]
 
+import light_hit_ref as LH
 import lights_ref as LR
 import restatement as RS
 import shading_cases as SC
+import test_shading_paths_host as PATHS
 import test_shading_ref_host as HOST
 from oracle import oracle as O
 
@@ -42,9 +45,40 @@ MUTATIONS = (
     ("the sun's max(r, 1/32) dropped", [("const float r = std::fmax(rghMtl.x, 1.0f / 32.0f);", "const float r = rghMtl.x;")], "sun_ref.cpp"),
 )
 
+# Lines of the path follower and the sample loop (tests/recursion_ref.cpp, tests/spp_ref.cpp: the twins of raytrace.hip's levels and samples),
+# judged by the runs of shading_cases.path_cases() against the model's paths (tests/test_shading_paths_host.py): the code rule on unflagged
+# pixels and the model's ray count.  Written by the second argument:
+#
+#     python tests/shading_mutations.py paths profiles/r22_shading_path_mutations.txt
+PATH_MUTATIONS = (
+    ("T * w -> w alone", [("T = f3(T.x * w.x, T.y * w.y, T.z * w.z);", "T = w;")], "recursion_ref.cpp"),
+    ("w = color -> color (1 - 0.04) at depth >= 1", [("w = color;  ", "w = color * (1.0f - 0.04f);  ")], "recursion_ref.cpp"),
+    ("the diffuse group's (1 - m) dropped", [("if (diffuseGroup) color = color * (1.0f - rm.y);", ";")], "recursion_ref.cpp"),
+    ("the last level's (1 - m) dropped", [("diffuseGroup ? color * (1.0f - rm.y) : color", "color")], "recursion_ref.cpp"),
+    ("the preset test with || instead of &&", [("preset.x <= 0.0f && preset.y <= 0.0f && preset.z <= 0.0f", "preset.x <= 0.0f || preset.y <= 0.0f || preset.z <= 0.0f")], "recursion_ref.cpp"),
+    ("the preset of the previous surface", [("    preset = color * rm.y;\n", "")], "recursion_ref.cpp"),
+    ("the skip id left at the primary's", [("o = P; dir = L; skipInst = h.inst; skipPrim = h.prim;", "o = P; dir = L;")], "recursion_ref.cpp"),
+    ("d + 1 == D -> d == D", [("if (d + 1 == D) {", "if (d == D) {")], "recursion_ref.cpp"),
+    ("V = -dir -> the first ray's V", [("    const float3 V = -dir;\n", "    static thread_local float3 V0; if (d == 0) V0 = -dir; const float3 V = V0;\n")], "recursion_ref.cpp"),
+    ("FrameIndex N + k -> FrameIndex + k", [("fc.g.FrameIndex * N + k", "fc.g.FrameIndex + k")], "spp_ref.cpp"),
+    ("1 / N -> 1 / (N - 1)", [("const float scale = 1.0f / (float)N;", "const float scale = 1.0f / (float)(N > 1 ? N - 1 : 1);")], "spp_ref.cpp"),
+    ("the sum started at sample 1", [("for (uint32_t k = 0; k < N; ++k) {", "for (uint32_t k = (N > 1 ? 1 : 0); k < N; ++k) {")], "spp_ref.cpp"),
+)
 
-def mutated_library(edits, work, file=None):
-    """The whole oracle and every restatement (tests/lights_ref.cpp includes them all) from a scratch copy with the edits applied."""
+
+# Lines of the lights' and the sun's terms at the hits (tests/light_hit_ref.cpp), judged by the stage check of the hit runs (measure_hits)
+HIT_MUTATIONS = (
+    ("the hit term's color' without (1 - m)", [("    if (diffuseGroup) color = color * (1.0f - rm.y);\n    const float g = (NoL / kPI) * att;", "    const float g = (NoL / kPI) * att;")]),
+    ("the hit term with x 0.96", [("const float g = (NoL / kPI) * att;", "const float g = ((NoL / kPI) * att) * (1.0f - 0.04f);")]),
+    ("s_d without T_d (a light's)", [("  S = f3(S.x + T.x * term.x, S.y + T.y * term.y, S.z + T.z * term.z);\n  return LC_LIT;", "  S = f3(S.x + term.x, S.y + term.y, S.z + term.z);\n  return LC_LIT;")]),
+    ("s_d without T_d (the sun's)", [("            S = f3(S.x + T.x * term.x, S.y + T.y * term.y, S.z + T.z * term.z);\n            any = true;", "            S = f3(S.x + term.x, S.y + term.y, S.z + term.z);\n            any = true;")]),
+    ("a light's hit interval to 1e4 instead of tmax", [("trace_closest(c, P, Ls, 1e-5f, tmax, hInst, hPrim)", "trace_closest(c, P, Ls, 1e-5f, 10000.0f, hInst, hPrim)")]),
+)
+
+
+def mutated_library(edits, work, file=None, source="lights_ref.cpp", signatures=None):
+    """The whole oracle and every restatement (tests/lights_ref.cpp includes them all; source: another top file) from a scratch copy with the
+    edits applied."""
     for d in ("oracle", "tests"):
         if os.path.exists(os.path.join(work, d)):
             shutil.rmtree(os.path.join(work, d))
@@ -60,9 +94,9 @@ def mutated_library(edits, work, file=None):
         text = text.replace(old, new)
     open(path, "w").write(text)
     out = os.path.join(work, "libmutant_%d.so" % len(os.listdir(work)))
-    subprocess.check_call([os.environ.get("CXX", "g++")] + RS._FLAGS + ["-shared", "-pthread", "-o", out, os.path.join(work, "tests", "lights_ref.cpp")])
+    subprocess.check_call([os.environ.get("CXX", "g++")] + RS._FLAGS + ["-shared", "-pthread", "-o", out, os.path.join(work, "tests", source)])
     L = C.CDLL(out)
-    for name, fn in list(vars(LR.lib()).items()):
+    for name, fn in list(vars(signatures or LR.lib()).items()):
         if name.startswith("orc_"):
             mine = getattr(L, name)
             mine.restype, mine.argtypes = fn.restype, fn.argtypes
@@ -95,6 +129,63 @@ def first_failure(lib):
     return None
 
 
+def first_path_failure(lib):
+    """(run, message) of the first run of path_cases() whose words break the code rule against the model's paths or whose ray count leaves the
+    model's, or None."""
+    import numpy as np
+    for run in SC.path_cases():
+        frames = PATHS.run_restatement(run, lib=lib)
+        models = PATHS.model_frames(run, [f["vis"] for f in frames])
+        prev, bounds = None, PATHS.bounds_of(run)
+        for k, f, m in zip(run.positions, frames, models):
+            label = "%s frame %d" % (run.name, SC.FRAMES[k])
+            try:
+                HOST.check_words(label, f, m, prev, bounds)
+                flagged = int((m["flags"] != 0).sum())
+                assert abs(f["rays"] - m["rays"]) <= 2 * flagged * run.samples * run.depth, "%s: %d rays, the model traces %d" % (label, f["rays"], m["rays"])
+            except AssertionError as e:
+                return run.name, re.sub(r"\s+", " ", str(e).split(", first")[0])
+            prev = f
+    return None
+
+
+def first_hit_failure(lib):
+    """(run, message) of the first run of hit_cases() whose words in front of the primary passes break the hit stage's check, or None."""
+    for run in SC.hit_cases():
+        try:
+            PATHS.measure_hits(run, PATHS.run_hit_restatement(run, lib=lib))
+        except AssertionError as e:
+            return run.name, re.sub(r"\s+", " ", str(e).split(", first")[0])
+    return None
+
+
+def path_main(path):
+    lines = ["Mutations of the CPU restatements' path follower and sample loop (the twin lines of raytrace.hip's levels and samples) against the float64",
+             "model's paths: the code rule on unflagged pixels and the model's ray count, on the runs of shading_cases.path_cases()",
+             "(tests/shading_mutations.py; the unmutated restatement passes every run: tests/test_shading_paths_host.py).", ""]
+    with tempfile.TemporaryDirectory() as work:
+        clean = first_path_failure(mutated_library([], work))
+        assert clean is None, "the unmutated copy fails: %s" % (clean,)
+        lines.append("%-48s passes all %d runs" % ("(no mutation)", len(SC.PATH_NAMES)))
+        missed = []
+        for name, edits, file in PATH_MUTATIONS:
+            got = first_path_failure(mutated_library(edits, work, file))
+            lines.append("%-48s %s" % (name, "NOT CAUGHT" if got is None else "caught, first by %s" % got[1]))
+            if got is None:
+                missed.append(name)
+        lines += ["", "The sun's and the lights' terms at the hits (tests/light_hit_ref.cpp), judged by the stage check of shading_cases.hit_cases():", ""]
+        for name, edits in HIT_MUTATIONS:
+            got = first_hit_failure(mutated_library(edits, work, "light_hit_ref.cpp", "light_hit_ref.cpp", LH.lib()))
+            lines.append("%-48s %s" % (name, "NOT CAUGHT" if got is None else "caught, first by %s" % got[1]))
+            if got is None:
+                missed.append(name)
+    total = len(PATH_MUTATIONS) + len(HIT_MUTATIONS)
+    lines += ["", "%d of %d caught" % (total - len(missed), total)]
+    open(path, "w").write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+    return 1 if missed else 0
+
+
 def main(path):
     lines = ["Mutations of the CPU oracle's shading path (the kernel's twin lines) against the float64 model's code rule on unflagged pixels",
              "(tests/shading_mutations.py; the unmutated oracle passes every case: tests/test_shading_ref_host.py).", ""]
@@ -115,4 +206,6 @@ def main(path):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1]))
+    if len(sys.argv) != 3 or sys.argv[1] not in ("depth1", "paths"):
+        sys.exit("usage: shading_mutations.py depth1 <report> | paths <report>")
+    sys.exit((main if sys.argv[1] == "depth1" else path_main)(sys.argv[2]))

@@ -1,6 +1,7 @@
-"""Float64 model of one frame's depth-1 shading path per pixel, numpy only: the primary surface ray generation derives from the visibility
+"""Float64 model of one frame's shading paths per pixel, numpy only: the primary surface ray generation derives from the visibility
 word, the GGX half vector (NDF map, and the VNDF map of rtggx_set_sampler), the ray's weight, the closest hit, the hit's shading and the
-miss.  It is the second witness of raytrace.hip next to the CPU oracle (oracle/orc_raytrace.h), which follows the kernel function by
+miss; paths of 1 to 4 levels (rtggx_set_max_recursion_depth) and 1 to 8 samples per pixel (rtggx_set_samples_per_pixel), written from the
+rule texts of include/rtggx.h (follow_paths, frame).  It is the second witness of raytrace.hip next to the CPU oracle (oracle/orc_raytrace.h), which follows the kernel function by
 function; this file shares no code with either and derives each step by another route wherever one exists:
 
   primary surface  the pixel centre's eye ray (ProjToWorld, ProjBias) meets the plane of the world-space triangle the visibility word names;
@@ -15,8 +16,8 @@ A rounding is taken only where a typed texel is stored.  Every decision fp32 and
 guessed (FLAG_* below); flagged pixels are compared with the oracle bit for bit like all others, but not with this model.
 
 The sun's (angle 0) and the local lights' (radius 0) terms of the primary surface are sun_pass and lights_pass, from include/rtggx.h.
-Out of scope: recursion depth 2 to 4, more than one sample per pixel, sample sets above 256, ray rate 4, the sun's disk,
-the lights' radii and both in reflections.
+The sun's and the lights' terms at the surfaces the paths hit (rtggx_set_sun_reflections, rtggx_set_light_reflections; one sample) are hits_pass.
+Out of scope: hit terms at N > 1, the sun's disk, the lights' radii, the light pick, sample sets above 256, ray rate 4.
 
 Conventions: row vectors (p' = p M); the frame constants are the 768 bytes of RtggxFrameConstants (include/rtggx.h), 4x4 matrices stored
 transposed, 3x4 blocks as three rows of the transpose."""
@@ -30,6 +31,8 @@ UP_SWITCH = 0.999
 FLAG_T_TIE, FLAG_EDGE, FLAG_NOL, FLAG_CHECKER, FLAG_UP, FLAG_TMIN, FLAG_CANCEL, FLAG_GRAZING, FLAG_RANGE, FLAG_CONE = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512
 FLAG_NAMES = {FLAG_RANGE: "range", FLAG_CONE: "cone", FLAG_T_TIE: "t_tie", FLAG_EDGE: "edge", FLAG_NOL: "nol", FLAG_CHECKER: "checker", FLAG_UP: "up", FLAG_TMIN: "tmin", FLAG_CANCEL: "cancel",
               FLAG_GRAZING: "grazing"}
+FLAG_GRAZING_DEEP = 1024      # NoL < GRAZING_NOL of a reflection at level >= 1 (no absolute side rule there: the pixel is just not compared)
+FLAG_NAMES[FLAG_GRAZING_DEEP] = "grazing_deep"
 # The reflection's weight is proportional to NoL (the other factors stay bounded: Vis's NoL + sqrt(...) is at least alpha), so the pixel's
 # RELATIVE error is the absolute error of NoL over NoL.  That absolute error is a few 1e-6 in fp32 -- the primary surface's barycentrics come
 # from screen-space gradients, P and V inherit their error, the reflection doubles it -- so below NoL = 2^-8 a faithful fp32 value is
@@ -44,6 +47,7 @@ GRAZING_NOL = 2.0 ** -8
 # cell, another side of NoL = 0) the pixel is flagged FLAG_CANCEL.  4 x 2^-24: the roundings of cos^2 theta (a quotient of two rounded
 # numbers near 1, three half-ulps of 1) and one for the difference.
 CANCEL_SLACK = 4.0 * 2.0 ** -24
+SLACK_RUNS = (0.0, -1.0, 1.0)      # the three runs of a path by the sign of the slack; a segment's "run" is its index here
 
 
 # ---- frame constants ---------------------------------------------------------------------------------------------------------------
@@ -262,9 +266,9 @@ def _world_triangles(scene, fc):
     return np.concatenate(tris), np.concatenate(inst), np.concatenate(prim)
 
 
-def closest_hit(tris, org, d, skip, tmin=RAY_TMIN, tmax=RAY_TMAX):
-    """Brute force over every triangle.  org, d [n 3]; skip [n]: index into tris of the origin's primitive.  -> dict: valid, tri, t, b [n 3]
-    (weights of the three vertices), flags."""
+def closest_hit(tris, org, d, skip, tmin=RAY_TMIN, tmax=RAY_TMAX, widen=None):
+    """Brute force over every triangle.  org, d [n 3]; skip [n]: index into tris of the origin's primitive.  widen [n]: a factor on EDGE per
+    ray (follow_paths: the error a deeper ray's origin carries).  -> dict: valid, tri, t, b [n 3] (weights of the three vertices), flags."""
     n, m = len(org), len(tris)
     out = {"valid": np.zeros(n, bool), "tri": np.zeros(n, np.int64), "t": np.full(n, np.inf), "b": np.zeros((n, 3)), "flags": np.zeros(n, np.int64)}
     e1, e2 = tris[:, 1] - tris[:, 0], tris[:, 2] - tris[:, 0]
@@ -272,6 +276,7 @@ def closest_hit(tris, org, d, skip, tmin=RAY_TMIN, tmax=RAY_TMAX):
     step = max(1, 400000 // max(m, 1))
     for a in range(0, n, step):
         o, dd, sk = org[a:a + step], d[a:a + step], skip[a:a + step]
+        band = EDGE if widen is None else (EDGE * widen[a:a + step])[:, None]
         k = len(o)
         p = np.cross(dd[:, None, :], e2[None])
         det = _dot(e1[None], p)
@@ -298,9 +303,9 @@ def closest_hit(tris, org, d, skip, tmin=RAY_TMIN, tmax=RAY_TMAX):
         other = inside & (tt <= reach[:, None]) & (np.arange(m)[None] != best[:, None]) & ~(same[best] & (tt == tb[:, None]))
         flags |= np.where(other.any(axis=1), FLAG_T_TIE, 0)
         # a barycentric within EDGE of zero, on either side, on anything that is or could become the closest hit
-        edge = usable & (np.abs(lo) <= EDGE) & (t > 0.5 * tmin) & (t < tm) & (t <= reach[:, None])
+        edge = usable & (np.abs(lo) <= band) & (t > 0.5 * tmin) & (t < tm) & (t <= reach[:, None])
         flags |= np.where(edge.any(axis=1), FLAG_EDGE, 0)
-        ends = usable & (lo >= -EDGE) & (((t > 0.5 * tmin) & (t < 2.0 * tmin)) | (np.abs(t - tm) < 1e-3 * tm))
+        ends = usable & (lo >= -band) & (((t > 0.5 * tmin) & (t < 2.0 * tmin)) | (np.abs(t - tm) < 1e-3 * tm))
         flags |= np.where(ends.any(axis=1), FLAG_TMIN, 0)
         sl = slice(a, a + k)
         out["valid"][sl], out["tri"][sl], out["t"][sl], out["flags"][sl] = valid, best, tb, flags
@@ -308,13 +313,13 @@ def closest_hit(tris, org, d, skip, tmin=RAY_TMIN, tmax=RAY_TMAX):
     return out
 
 
-def _checker_roughness(inst, uv, rough):
+def _checker_roughness(inst, uv, rough, widen=1.0):
     """Instance 0's checkerboard: a quarter of the roughness where the two integer parts of 5 uv differ in parity (negative: 0).
     -> (roughness, within UV_EPS of a step)."""
     g = 5.0 * uv
     cell = np.floor(np.maximum(g, 0.0)).astype(np.int64)
     odd = ((cell[:, 0] ^ cell[:, 1]) & 1) == 1
-    near = (np.abs(g - np.round(g)) <= UV_EPS).any(axis=1) & (np.round(g) >= 0.0).any(axis=1)
+    near = (np.abs(g - np.round(g)) <= np.reshape(UV_EPS * widen, (-1, 1))).any(axis=1) & (np.round(g) >= 0.0).any(axis=1)
     return np.where((inst == 0) & odd, 0.25 * rough, rough), near & (inst == 0)
 
 
@@ -326,7 +331,7 @@ def _uv(n, p):
     return 0.5 * uv + 0.5
 
 
-def _attributes(scene, fc, inst, prim, b):
+def _attributes(scene, fc, inst, prim, b, widen=1.0):
     """Object-space attributes at barycentric weights b [n 3] of (inst, prim) -> dict: pos_obj, N (world), rough, metal, colour, flags."""
     n = len(inst)
     pos, nrm = np.zeros((n, 3)), np.zeros((n, 3))
@@ -339,7 +344,7 @@ def _attributes(scene, fc, inst, prim, b):
     it = np.stack([inverse_transpose(fc["world"][0]), inverse_transpose(fc["world"][1])])
     N = _unit(np.einsum("ni,nij->nj", nrm, it[inst]))
     rough0 = np.array(fc["rough"])[inst]
-    rough, near = _checker_roughness(inst, _uv(nrm, pos), rough0)
+    rough, near = _checker_roughness(inst, _uv(nrm, pos), rough0, widen)
     return {"pos_obj": pos, "N": N, "rough": rough, "metal": np.array(fc["metal"])[inst], "colour": np.stack(fc["colour"])[inst],
             "flags": np.where(near, FLAG_CHECKER, 0)}
 
@@ -349,59 +354,159 @@ def _scale(lo, hi, f):
     return np.minimum(a, b), np.maximum(a, b)
 
 
-def shade_ray(scene, fc, tris, tri_inst, tri_prim, org, d, skip, diffuse_group, preset):
-    """What a depth-0 ray brings back -> (lo, hi [n 3], flags [n]).  preset [n 3]: the payload's colour x metallic; a reflection-group ray
-    whose preset has no positive channel returns the preset from a hit."""
+# ---- a path of D levels (include/rtggx.h: rtggx_set_max_recursion_depth) ---------------------------------------------------------------
+TERM_NONE, TERM_MISS, TERM_PRESET, TERM_NOL, TERM_MIRROR, TERM_DIFFUSE = 0, 1, 2, 3, 4, 5      # how a path ended (TERM_NONE: no level-0 ray)
+TERM_NAMES = {TERM_MISS: "miss", TERM_PRESET: "preset", TERM_NOL: "nol", TERM_MIRROR: "last_mirror", TERM_DIFFUSE: "last_diffuse"}
+EVENTS = ("refl_to_diff", "diff_to_refl", "one_minus_m")
+
+
+def _last_level(scene, a, d, diffuse_group):
+    """The depth-1 shading of a hit with the attributes a, reached along d: metallic > 0.5 the cube along the dominant direction of the
+    lobe times EnvBRDFApprox (0 where that direction lies under the surface), otherwise SH irradiance / pi x colour, the colour x (1 - m)
+    for a diffuse-group ray.  diffuse_group [n] bool.  -> (lo, hi [n 3], flags [n])."""
+    n = len(d)
+    N, V = a["N"], -d
+    mirror = a["metal"] > 0.5
+    l, u, fl = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros(n, np.int64)
+    if mirror.any():
+        j = mirror
+        r, al = a["rough"][j], a["rough"][j] ** 2
+        Nj, Vj = N[j], V[j]
+        R = 2.0 * _dot(Nj, Vj)[:, None] * Nj - Vj
+        with np.errstate(invalid="ignore"):
+            w = (1.0 - al) * (np.sqrt(1.0 - al) + al)
+        dr = Nj + w[:, None] * (R - Nj)
+        NoL = _dot(Nj, dr)
+        with np.errstate(divide="ignore"):
+            level = (len(scene.cube.levels) - 1.0) - (3.0 - 1.15 * np.log2(r))
+        el, eh = scene.environment(dr, np.where(np.isnan(level), 0.0, level))
+        f = env_brdf_approx(f0_of(a["colour"][j], a["metal"][j]), r, _sat(_dot(Nj, Vj)))
+        el, eh = _scale(el, eh, f)
+        dark = NoL <= 0.0
+        el[dark] = eh[dark] = 0.0
+        l[j], u[j] = el, eh
+        fl[j] = np.where(np.abs(NoL) <= NOL_EPS, FLAG_NOL, 0)
+    if (~mirror).any():
+        j = ~mirror
+        c = a["colour"][j] * np.where(diffuse_group[j], 1.0 - a["metal"][j], 1.0)[:, None]
+        l[j] = u[j] = sh_irradiance(scene.sh, N[j]) / np.pi * c
+    return l, u, fl
+
+
+def sphere_direction(N, phi, xi, slack=0.0):
+    """The diffuse ray: unit(N + the point of the unit sphere at height 1 - 2 xi and azimuth phi).  slack: added to 1 - cos^2 before its root."""
+    ct = 1.0 - 2.0 * xi
+    st = np.sqrt(np.maximum(1.0 - ct * ct + slack, 0.0))
+    return _unit(N + np.stack([np.cos(phi) * st, np.sin(phi) * st, ct], axis=1))
+
+
+def follow_paths(scene, fc, geo, org, d, skip, T, diffuse_group, preset, phi, xi, depth=1, vndf=False, slack=0.0, segments=None, ident=None):
+    """n paths of `depth` levels from their level-0 rays (org, d; skip: the index of the origin's triangle), as rtggx_set_max_recursion_depth
+    states them.  T [n 3]: the level-0 weight w0; T_{d+1} = T_d w_{d+1}, and the value is c T with c what the path ends with:
+      a miss                               environment(dir, level 0)
+      a hit of a reflection-group ray whose preset (colour x metallic of the surface it left) is <= 0 everywhere: the preset
+      a hit of the last level              its depth-1 shading (_last_level)
+      a hit with metallic > 0.5            computeReflection with the path's (phi, xi) at every level: H by the sampler at the hit's N and
+                                           V = -dir, R = reflect(-V, H); NoL <= 0 ends with 0; else a reflection-group ray from
+                                           P = o + t dir along R, skipping the hit's triangle, of weight BRDF NoL / pdf (ndf_weight, vndf_weight)
+      any other hit                        computeDiffuse: colour' = colour (1 - m) for a diffuse-group ray, colour for a reflection-group
+                                           one; a diffuse-group ray along unit(N + sphere(xi)) of weight colour' (no 0.96)
+    slack: CANCEL_SLACK's sign for every sampler root of the path, all levels together.  segments: a list that receives one dict per level
+    of the rays that touch a surface (for the sun's and the lights' terms at the hits); ident [n]: what it names the paths by.
+    -> dict: lo, hi [n 3]; flags [n]; sig [n, 3 depth] (per level: triangle or -1, roughness, how the path ended there) for the cancel rule;
+       kind, level [n]: how and where each path ended; rays [depth]; events {name: count}."""
+    tris, tri_inst, tri_prim = geo
     n = len(org)
-    h = closest_hit(tris, org, d, skip)
     lo, hi = np.zeros((n, 3)), np.zeros((n, 3))
-    flags = h["flags"].copy()
-    miss = ~h["valid"]
-    if miss.any():
-        lo[miss], hi[miss] = scene.environment(d[miss], 0.0)
-    hit = h["valid"]
-    if not diffuse_group:
-        dark = hit & (preset <= 0.0).all(axis=1)
-        lo[dark] = hi[dark] = preset[dark]
+    flags, kind, level = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int64)
+    sig = np.full((n, depth, 3), -3.0)
+    rays = np.zeros(depth, np.int64)
+    events = dict.fromkeys(EVENTS, 0)
+    at = np.arange(n)                      # the paths that have a ray at this level
+    grp = np.broadcast_to(np.asarray(diffuse_group, bool), (n,)).copy()
+    T, preset = np.array(T, np.float64), np.array(preset, np.float64)
+    # The error a ray's origin carries: a level-0 ray leaves the primary surface (EDGE and UV_EPS are sized for that); a deeper ray leaves the hit
+    # point P = o + t dir, whose error along the surface is the ray's own over the cosine of incidence on the triangle's plane.  Every edge
+    # band and checkerboard band of a level is widened by the product of those factors over the hits before it (1 at level 0).
+    amp = np.ones(n)
+    geo_n = _unit(np.cross(tris[:, 1] - tris[:, 0], tris[:, 2] - tris[:, 0]))
+
+    def end(which, lev, k, c_lo, c_hi):
+        lo[at[which]], hi[at[which]] = _scale(c_lo, c_hi, T[which])
+        kind[at[which]], level[at[which]] = k, lev
+
+    for lev in range(depth):
+        rays[lev] = at.size
+        if not at.size:
+            break
+        h = closest_hit(tris, org, d, skip, widen=None if lev == 0 else amp)
+        flags[at] |= h["flags"]
+        sig[at, lev, 0], sig[at, lev, 1] = np.where(h["valid"], h["tri"], -1), 0.0
+        miss = ~h["valid"]
+        if miss.any():
+            end(miss, lev, TERM_MISS, *scene.environment(d[miss], 0.0))
+        hit = h["valid"]
+        dark = hit & ~grp & (preset <= 0.0).all(axis=1)
+        if dark.any():
+            end(dark, lev, TERM_PRESET, preset[dark], preset[dark])
         hit = hit & ~dark
-    if hit.any():
         k = np.nonzero(hit)[0]
-        a = _attributes(scene, fc, tri_inst[h["tri"][k]], tri_prim[h["tri"][k]], h["b"][k])
-        # m = 0.5 decides between the two shadings; the constant is the same fp32 number on every side, so the decision is too -- but a case
-        # that sits on the threshold tests nothing, and none may (m = 1 is a legitimate material: it only zeroes a factor)
-        assert not (a["metal"] == 0.5).any(), "a hit's metallic is exactly 0.5"
-        flags[k] |= a["flags"]
-        N, V = a["N"], -d[k]
-        mirror = a["metal"] > 0.5
-        l, u = np.zeros((len(k), 3)), np.zeros((len(k), 3))
-        if mirror.any():
-            j = mirror
-            r, al = a["rough"][j], a["rough"][j] ** 2
-            Nj, Vj = N[j], V[j]
-            R = 2.0 * _dot(Nj, Vj)[:, None] * Nj - Vj
-            with np.errstate(invalid="ignore"):
-                w = (1.0 - al) * (np.sqrt(1.0 - al) + al)
-            dr = Nj + w[:, None] * (R - Nj)
-            NoL = _dot(Nj, dr)
-            with np.errstate(divide="ignore"):
-                level = (len(scene.cube.levels) - 1.0) - (3.0 - 1.15 * np.log2(r))
-            el, eh = scene.environment(dr, np.where(np.isnan(level), 0.0, level))
-            f = env_brdf_approx(f0_of(a["colour"][j], a["metal"][j]), r, _sat(_dot(Nj, Vj)))
-            el, eh = _scale(el, eh, f)
-            dark = NoL <= 0.0
-            el[dark] = eh[dark] = 0.0
-            l[j], u[j] = el, eh
-            fl = np.zeros(len(k), np.int64); fl[j] = np.where(np.abs(NoL) <= NOL_EPS, FLAG_NOL, 0)
-            flags[k] |= fl
-        if (~mirror).any():
-            j = ~mirror
-            c = a["colour"][j] * ((1.0 - a["metal"][j])[:, None] if diffuse_group else 1.0)
-            l[j] = u[j] = sh_irradiance(scene.sh, N[j]) / np.pi * c
-        lo[k], hi[k] = l, u
-    sig = np.stack([np.where(h["valid"], h["tri"], -1).astype(np.float64), np.zeros(n)], axis=1)
-    if h["valid"].any() and hit.any():
-        sig[k, 1] = a["rough"]
-    return lo, hi, flags, sig
+        keep = np.zeros(at.size, bool)
+        if k.size:
+            a = _attributes(scene, fc, tri_inst[h["tri"][k]], tri_prim[h["tri"][k]], h["b"][k], 1.0 if lev == 0 else amp[k])
+            # m = 0.5 decides between the two shadings; the constant is the same fp32 number on every side, so the decision is too -- but a case
+            # that sits on the threshold tests nothing, and none may (m = 1 is a legitimate material: it only zeroes a factor)
+            assert not (a["metal"] == 0.5).any(), "a hit's metallic is exactly 0.5"
+            flags[at[k]] |= a["flags"]
+            sig[at[k], lev, 1] = a["rough"]
+            Pk = org[k] + h["t"][k][:, None] * d[k]
+            mirror = a["metal"] > 0.5
+            events["one_minus_m"] += int((~mirror & grp[k] & (a["metal"] > 0.0)).sum())
+            if segments is not None:
+                segments.append({"level": lev, "path": (at if ident is None else ident[at])[k], "P": Pk, "N": a["N"], "V": -d[k], "rough": a["rough"], "metal": a["metal"],
+                                 "colour": a["colour"], "T": T[k].copy(), "diffuse_group": grp[k].copy(), "tri_of": h["tri"][k], "flags": a["flags"],
+                                 "amp": amp[k] / np.maximum(np.abs(_dot(geo_n[h["tri"][k]], d[k])), 2.0 ** -20)})
+            if lev + 1 == depth:
+                l, u, fl = _last_level(scene, a, d[k], grp[k])
+                flags[at[k]] |= fl
+                lo[at[k]], hi[at[k]] = _scale(l, u, T[k])
+                kind[at[k]], level[at[k]] = np.where(mirror, TERM_MIRROR, TERM_DIFFUSE), lev
+            else:
+                nd, w = np.zeros((k.size, 3)), np.zeros((k.size, 3))
+                go = np.ones(k.size, bool)
+                if mirror.any():
+                    j = mirror
+                    Nj, Vj, al = a["N"][j], -d[k][j], a["rough"][j] ** 2
+                    Hh, near_up = vndf_half_vector(Nj, Vj, al, phi[k][j], xi[k][j], slack) if vndf else ndf_half_vector(Nj, al, phi[k][j], xi[k][j], slack)
+                    R = 2.0 * _dot(Vj, Hh)[:, None] * Hh - Vj
+                    NoL = _dot(Nj, R)
+                    fl = np.where(near_up, FLAG_UP, 0) | np.where(np.abs(NoL) <= NOL_EPS, FLAG_NOL, 0) | np.where((NoL > 0.0) & (NoL < GRAZING_NOL), FLAG_GRAZING_DEEP, 0)
+                    flags[at[k[j]]] |= fl
+                    VoH, NoH, NoV = _sat(_dot(Vj, Hh)), _sat(_dot(Nj, Hh)), _sat(_dot(Nj, Vj))
+                    f0 = f0_of(a["colour"][j], a["metal"][j])
+                    w[j] = vndf_weight(f0, al, NoL, VoH) if vndf else ndf_weight(f0, al, NoV, NoL, VoH, NoH)
+                    nd[j] = R
+                    g = go[j]; g[NoL <= 0.0] = False; go[j] = g
+                    events["diff_to_refl"] += int((grp[k][j] & (NoL > 0.0)).sum())
+                if (~mirror).any():
+                    j = ~mirror
+                    w[j] = a["colour"][j] * np.where(grp[k][j], 1.0 - a["metal"][j], 1.0)[:, None]
+                    nd[j] = sphere_direction(a["N"][j], phi[k][j], xi[k][j], slack)
+                    events["refl_to_diff"] += int((~grp[k][j]).sum())
+                stop = k[~go]
+                lo[at[stop]] = hi[at[stop]] = 0.0
+                kind[at[stop]], level[at[stop]] = TERM_NOL, lev
+                keep[k[go]] = True
+                nxt = {"org": Pk[go], "d": nd[go], "skip": h["tri"][k][go], "T": T[k][go] * w[go], "grp": ~mirror[go],
+                       "preset": a["colour"][go] * a["metal"][go][:, None],
+                       "amp": amp[k][go] / np.maximum(np.abs(_dot(geo_n[h["tri"][k]], d[k]))[go], 2.0 ** -20)}
+        sig[at, lev, 2] = np.where(keep, -1.0, kind[at])
+        if not keep.any():
+            at = at[:0]
+            continue
+        at, phi, xi = at[keep], phi[keep], xi[keep]
+        org, d, skip, T, grp, preset, amp = nxt["org"], nxt["d"], nxt["skip"], nxt["T"], nxt["grp"], nxt["preset"], nxt["amp"]
+    return {"lo": lo, "hi": hi, "flags": flags, "sig": sig.reshape(n, 3 * depth), "kind": kind, "level": level, "rays": rays, "events": events}
 
 
 def eye_ray_barycentrics(proj_to_world, T, ndc):
@@ -425,11 +530,20 @@ def eye_ray_barycentrics(proj_to_world, T, ndc):
     return np.stack([1.0 - b1 - b2, b1, b2], axis=1)
 
 
-def frame(scene, fc_bytes, vis, W, H, vndf=False, prev=None):
+def frame(scene, fc_bytes, vis, W, H, vndf=False, prev=None, depth=1, samples=1):
     """One frame.  vis [H W] uint32: the visibility words (the rasteriser's, taken as input).  prev: the previous frame's result, for the
     words a frame carries over (RayTracingOut1 where no diffuse ray is traced, the rough-metal word where nothing is drawn).
+    depth: levels of rays per path (follow_paths).  samples: N; sample k draws sample_params(W, H, FrameIndex N + k), not wrapped, and
+    carries it through every level of its two paths; the pixel's interval is (sum_k v_k) / N with v_k the hull of sample k's three runs
+    (0 where it traces nothing).  At depth 1 and one sample this is the depth-1 model, bit for bit (tests/test_shading_paths_host.py).
+    Flags: a pixel is flagged if any segment of either path of any sample is.  The cancel rule: each whole path is evaluated three times,
+    with CANCEL_SLACK as it is, taken from and added to EVERY sampler root of the path, all levels together (fp32 rounds each root on its
+    own, so the three runs are a sample of the 3^D combinations, not their hull: the measured floor is the judge of that choice); the
+    pixel's interval is the hull, and it is flagged FLAG_CANCEL where the three runs differ at any level in the hit triangle, the hit's
+    roughness or how the path ended there.  A level >= 1 reflection with NoL < GRAZING_NOL is flagged FLAG_GRAZING_DEEP; level 0's stays
+    FLAG_GRAZING with its absolute side rule (refl_graze: sum over the grazing samples of |value| / NoL, over N).
     -> dict over [H W]: covered, flags, normal_value [.. 3], rm_value [.. 2], velocity_value [.. 2], refl_lo/hi, diff_lo/hi [.. 3],
-       refl_traced, diff_traced, diff_written, rm_written, rays."""
+       refl_traced (by any sample), diff_traced, diff_written, rm_written, rays (all samples and levels), and the bookkeeping at the end."""
     fc = read_constants(fc_bytes)
     n = W * H
     vis = np.asarray(vis).reshape(-1).astype(np.int64)
@@ -475,48 +589,89 @@ def frame(scene, fc_bytes, vis, W, H, vndf=False, prev=None):
         refl_lo[sky], refl_hi[sky] = l, h
         diff_lo[sky], diff_hi[sky] = l, h
 
-    s_slot, xi = sample_params(W, H, fc["frame_index"])
-    phi = 2.0 * np.pi * s_slot / 256.0
     c = np.nonzero(covered)[0]
-    refl_traced = np.zeros(n, bool); diff_traced = np.zeros(n, bool); refl_nol = np.zeros(n)
-    if c.size:
+    geo = (tris, tri_inst, tri_prim)
+    refl_traced = np.zeros(n, bool); diff_traced = np.zeros(n, bool); refl_nol = np.zeros(n); refl_graze = np.zeros(n)
+    term = {"refl": np.zeros((samples, n), np.int64), "diff": np.zeros((samples, n), np.int64)}
+    term_level = {"refl": np.zeros((samples, n), np.int64), "diff": np.zeros((samples, n), np.int64)}
+    rays_levels, events, segs = np.zeros(depth, np.int64), dict.fromkeys(EVENTS, 0), []
+    n_rays = 0
+
+    def three_runs(run):
+        """A path three times, CANCEL_SLACK as it is, taken from and added to every sampler root of the path, all levels together ->
+        (hull lo, hull hi, flags, the run without slack)."""
+        res = [run(slack) for slack in (0.0, -CANCEL_SLACK, CANCEL_SLACK)]
+        moved = (res[0]["sig"] != res[1]["sig"]).any(axis=1) | (res[0]["sig"] != res[2]["sig"]).any(axis=1)
+        return (np.minimum.reduce([r["lo"] for r in res]), np.maximum.reduce([r["hi"] for r in res]),
+                res[0]["flags"] | res[1]["flags"] | res[2]["flags"] | np.where(moved, FLAG_CANCEL, 0), res[0])
+
+    def note(image, k, r, idx):
+        term[image][k, idx], term_level[image][k, idx] = r["kind"], r["level"]
+        rays_levels[:] += r["rays"]
+        for e in EVENTS:
+            events[e] += r["events"][e]
+
+    dk = c[metal[c] < 1.0]
+    tot = {}
+    for k in range(samples if c.size else 0):
+        s_slot, xi = sample_params(W, H, fc["frame_index"] * samples + k)
+        phi = 2.0 * np.pi * s_slot / 256.0
         Nc, Vc, Pc, al = N[c], V[c], P[c], rough[c] ** 2
         f0 = f0_of(colour[c], metal[c])
         preset = colour[c] * metal[c][:, None]
-        res = []
-        for slack in (0.0, -CANCEL_SLACK, CANCEL_SLACK):
+
+        def reflection(slack):
             Hh, near_up = vndf_half_vector(Nc, Vc, al, phi[c], xi[c], slack) if vndf else ndf_half_vector(Nc, al, phi[c], xi[c], slack)
             R = 2.0 * _dot(Vc, Hh)[:, None] * Hh - Vc
             NoL = _dot(Nc, R)
             fl = np.where(near_up, FLAG_UP, 0) | np.where(np.abs(NoL) <= NOL_EPS, FLAG_NOL, 0) | np.where((NoL > 0.0) & (NoL < GRAZING_NOL), FLAG_GRAZING, 0)
             go = NoL > 0.0
-            l, h, sig = np.zeros((c.size, 3)), np.zeros((c.size, 3)), np.full((c.size, 2), -2.0)
+            r = {"lo": np.zeros((c.size, 3)), "hi": np.zeros((c.size, 3)), "flags": fl, "sig": np.full((c.size, 3 * depth), -2.0), "go": go, "NoL": NoL,
+                 "kind": np.zeros(c.size, np.int64), "level": np.zeros(c.size, np.int64), "rays": np.zeros(depth, np.int64), "events": dict.fromkeys(EVENTS, 0)}
             if go.any():
-                rl, rh, rf, rs = shade_ray(scene, fc, tris, tri_inst, tri_prim, Pc[go], R[go], tri_of[c[go]], False, preset[go])
                 VoH, NoH, NoV = _sat(_dot(Vc[go], Hh[go])), _sat(_dot(Nc[go], Hh[go])), _sat(_dot(Nc[go], Vc[go]))
                 wgt = vndf_weight(f0[go], al[go], NoL[go], VoH) if vndf else ndf_weight(f0[go], al[go], NoV, NoL[go], VoH, NoH)
-                l[go], h[go] = _scale(rl, rh, wgt)
-                fl[go] |= rf; sig[go] = rs
-            res.append((l, h, fl, sig, go, NoL))
-        refl_lo[c], refl_hi[c] = np.minimum.reduce([r[0] for r in res]), np.maximum.reduce([r[1] for r in res])
-        moved = (res[0][3] != res[1][3]).any(axis=1) | (res[0][3] != res[2][3]).any(axis=1)
-        flags[c] |= res[0][2] | res[1][2] | res[2][2] | np.where(moved, FLAG_CANCEL, 0)
-        refl_traced[c] = res[0][4]
-        refl_nol[c] = res[0][5]
+                at = len(segs)
+                p = follow_paths(scene, fc, geo, Pc[go], R[go], tri_of[c[go]], wgt, False, preset[go], phi[c[go]], xi[c[go]], depth, vndf, slack,
+                                 segs, c[go])
+                for sg in segs[at:]:
+                    sg.update(image=0, sample=k, run=SLACK_RUNS.index(np.sign(slack)))
+                r["lo"][go], r["hi"][go] = p["lo"], p["hi"]
+                r["flags"][go] |= p["flags"]; r["sig"][go] = p["sig"]
+                r["kind"][go], r["level"][go], r["rays"], r["events"] = p["kind"], p["level"], p["rays"], p["events"]
+            return r
+        l, h, fl, r0 = three_runs(reflection)
+        flags[c] |= fl
+        note("refl", k, r0, c)
+        n_rays += int(r0["go"].sum())
+        gz = (r0["NoL"] > 0.0) & (r0["NoL"] < GRAZING_NOL)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            refl_graze[c] += np.where(gz, np.maximum(np.abs(l), np.abs(h)).max(axis=-1) / r0["NoL"], 0.0) / samples
+        if k == 0:
+            tot["refl"] = [l, h]
+            refl_nol[c] = r0["NoL"]
+        else:
+            tot["refl"] = [tot["refl"][0] + l, tot["refl"][1] + h]
+        refl_traced[c] |= r0["go"]
         # ---- the diffuse ray
-        dk = c[metal[c] < 1.0]
         if dk.size:
-            ct = 1.0 - 2.0 * xi[dk]
-            res = []
-            for slack in (0.0, -CANCEL_SLACK, CANCEL_SLACK):
-                st = np.sqrt(np.maximum(1.0 - ct * ct + slack, 0.0))
-                dd = _unit(N[dk] + np.stack([np.cos(phi[dk]) * st, np.sin(phi[dk]) * st, ct], axis=1))
-                l, h, fl, sig = shade_ray(scene, fc, tris, tri_inst, tri_prim, P[dk], dd, tri_of[dk], True, colour[dk] * metal[dk][:, None])
-                res.append(_scale(l, h, colour[dk] * 0.96) + (fl, sig))
+            def diffuse(slack):
+                at = len(segs)
+                p = follow_paths(scene, fc, geo, P[dk], sphere_direction(N[dk], phi[dk], xi[dk], slack), tri_of[dk], colour[dk] * 0.96, True,
+                                 colour[dk] * metal[dk][:, None], phi[dk], xi[dk], depth, vndf, slack, segs, dk)
+                for sg in segs[at:]:
+                    sg.update(image=1, sample=k, run=SLACK_RUNS.index(np.sign(slack)))
+                return p
+            l, h, fl, r0 = three_runs(diffuse)
+            flags[dk] |= fl
+            note("diff", k, r0, dk)
+            n_rays += dk.size
             diff_traced[dk] = True
-            diff_lo[dk], diff_hi[dk] = np.minimum.reduce([r[0] for r in res]), np.maximum.reduce([r[1] for r in res])
-            moved = (res[0][3] != res[1][3]).any(axis=1) | (res[0][3] != res[2][3]).any(axis=1)
-            flags[dk] |= res[0][2] | res[1][2] | res[2][2] | np.where(moved, FLAG_CANCEL, 0)
+            tot["diff"] = [l, h] if k == 0 else [tot["diff"][0] + l, tot["diff"][1] + h]
+    if c.size:
+        refl_lo[c], refl_hi[c] = tot["refl"][0] / samples, tot["refl"][1] / samples
+        if dk.size:
+            diff_lo[dk], diff_hi[dk] = tot["diff"][0] / samples, tot["diff"][1] / samples
     diff_written = sky | diff_traced
     if prev is not None:      # what this frame does not write stays
         keep = ~diff_written
@@ -526,7 +681,13 @@ def frame(scene, fc_bytes, vis, W, H, vndf=False, prev=None):
     out["surface"] = {"P": P, "N": N, "V": V, "rough": rough, "metal": metal, "colour": colour, "tri_of": tri_of, "covered": covered, "flags": np.where(covered, a["flags"], 0)}
     out.update(flags=flags.reshape(H, W), refl_lo=refl_lo.reshape(H, W, 3), refl_hi=refl_hi.reshape(H, W, 3), diff_lo=diff_lo.reshape(H, W, 3),
                diff_hi=diff_hi.reshape(H, W, 3), refl_traced=refl_traced.reshape(H, W), diff_traced=diff_traced.reshape(H, W),
-               diff_written=diff_written.reshape(H, W), refl_nol=refl_nol.reshape(H, W), rays=int(refl_traced.sum() + diff_traced.sum()))
+               diff_written=diff_written.reshape(H, W), refl_nol=refl_nol.reshape(H, W), rays=int(rays_levels.sum()))
+    # how every sample's path ended and at which level (TERM_*; [samples H W]), the rays per level, what happened on the way, and the rays that
+    # touched a surface, level by level (of all three runs: "run" indexes SLACK_RUNS)
+    out.update(depth=depth, samples=samples, rays_levels=rays_levels, events=events, segments=segs, refl_graze=refl_graze.reshape(H, W),
+               refl_term=term["refl"].reshape(samples, H, W), refl_term_level=term_level["refl"].reshape(samples, H, W),
+               diff_term=term["diff"].reshape(samples, H, W), diff_term_level=term_level["diff"].reshape(samples, H, W))
+    assert int(rays_levels[0]) == n_rays
     return out
 
 
@@ -535,7 +696,7 @@ MIN_LIGHT_ROUGHNESS = 1.0 / 32.0
 D_SLACK = 4.0 * 2.0 ** -24      # the GGX denominator NoH^2 (a^2 - 1) + 1 is a difference of numbers near 1: fp32 leaves it an absolute error of this order
 
 
-def _direct_term(s, k, L, NoL):
+def _direct_term(s, k, L, NoL, d_slack=None):
     """Specular term per unit irradiance as an interval, and the diffuse one, at the pixels k with the unit direction L to the light:
     F D Vis NoL with r' = max(r, 1/32) and H = unit(V + L); colour 0.96 NoL / pi where m < 1 (0 elsewhere).  D is monotone in its
     denominator, which is taken D_SLACK lower (not below its least value a^2) and higher: a true interval of that rounding."""
@@ -546,8 +707,9 @@ def _direct_term(s, k, L, NoL):
     a2 = al * al
     d = NoH * NoH * (a2 - 1.0) + 1.0
     base = fresnel(f0_of(s["colour"][k], s["metal"][k]), VoH) * (vis_smith(al, NoV, NoL) * NoL)[:, None]
-    hi = base * (a2 / (np.pi * np.maximum(d - D_SLACK, a2) ** 2))[:, None]
-    lo = base * (a2 / (np.pi * (d + D_SLACK) ** 2))[:, None]
+    d_slack = D_SLACK if d_slack is None else d_slack      # (hits_pass: the hit's carried error on top)
+    hi = base * (a2 / (np.pi * np.maximum(d - d_slack, a2) ** 2))[:, None]
+    lo = base * (a2 / (np.pi * (d + d_slack) ** 2))[:, None]
     diff = s["colour"][k] * 0.96 * (NoL / np.pi)[:, None] * (s["metal"][k] < 1.0)[:, None]
     return lo, hi, diff
 
@@ -645,6 +807,126 @@ def lights_pass(scene, fc_bytes, m, lights):
     shape = m["covered"].shape
     return {"spec_lo": lo.reshape(shape + (3,)), "spec_hi": hi.reshape(shape + (3,)), "diff": df.reshape(shape + (3,)), "term": term.reshape(shape),
             "diffuse": (term & (s["metal"] < 1.0)).reshape(shape), "flags": flags.reshape(shape), "rays": int(rays)}
+
+
+# ---- the sun and the lights at the surfaces the paths hit (include/rtggx.h: rtggx_set_sun_reflections, rtggx_set_light_reflections) ----------
+# A cosine formed at a hit -- NoL, NoH, the cone's c -- inherits the error of the hit point and of V = -dir: the primary surface's few 1e-6,
+# doubled by a reflection (test_shading_ref_host.GRAZING_NOL_ERROR has the same figure for level 0's NoL), times the factor the hit point
+# carries (follow_paths: 1 / cosine of incidence over the hits so far).  The terms are monotone in each of them, so the model takes each
+# that much lower and higher: a true interval, like D_SLACK.  It matters where a factor is small: NoL just above the grazing flag, the
+# cone's s^2 near cos_outer, the GGX denominator away from its peak at small roughness.
+HIT_COSINE_ERROR = 1e-5
+LOBES = ("mirror", "diffuse_on_reflection_ray", "diffuse_on_diffuse_ray")
+HIT_CLASSES = ("facing_away", "occluded", "out_of_range", "outside_cone")
+
+
+def hits_pass(scene, fc_bytes, m, sun=None, lights=()):
+    """The sum S of one one-sample frame m (frame()'s result at any depth): for every level-d ray that touches a surface (m["segments"]) the
+    term of the lobe the path uses there -- metallic > 0.5: the specular term of _direct_term with the hit's N, V = -dir, (r, m) and colour,
+    its D_SLACK interval kept; otherwise colour' NoL / pi with colour' = colour (1 - m) for a diffuse-group ray and colour for a
+    reflection-group one, no 0.96 -- times E (the sun: sun = (L, E), angle 0) or I att (a light of radius 0: window, cone and floor as in
+    lights_pass), unless the hit faces away (NoL <= 0), lies out of range or outside the cone, or anything but the hit's own triangle
+    lies on the ray from the hit point over (RAY_TMIN, RAY_TMAX) for the sun and (RAY_TMIN, |D|) for a light; s_d = T_d term; S per
+    (pixel, image) over d ascending, the sun first, then the lights in their order.
+    -> dict: lo, hi [2 H W 3] (image 0: RayTracingOut0), mid (the unslacked run's value with no error carried), term [2 H W], flags [H W] (the frame's and the pass's own), rays,
+       counts {(level, lobe or class): terms or hits}."""
+    assert m["samples"] == 1, "with several samples the terms go into the fp32 sample sums: no stage to observe"
+    fc = read_constants(fc_bytes)
+    tris = _world_triangles(scene, fc)[0]
+    shape = m["covered"].shape
+    n = shape[0] * shape[1]
+    flags, rays, counts = m["flags"].reshape(-1).copy(), 0, {}
+    nol0 = m["refl_nol"].reshape(-1)
+    runs = [(np.zeros((2, n, 3)), np.zeros((2, n, 3)), np.zeros((2, n), bool)) for _ in SLACK_RUNS]
+    mid = np.zeros((2, n, 3))
+
+    def count(lev, name, k):
+        if sg["run"] == 0:
+            counts[(lev, name)] = counts.get((lev, name), 0) + int(k)
+
+    for sg in sorted(m["segments"], key=lambda g: g["level"]):
+        img, px, lev = sg["image"], sg["path"], sg["level"]
+        lo, hi, term = runs[sg["run"]]
+        # the throughput: the reflection path's w0 is proportional to level 0's NoL and carries its error (the grazing rule of level 0)
+        t_err = HIT_COSINE_ERROR / nol0[px] if img == 0 else np.zeros(len(px))
+        mirror = sg["metal"] > 0.5
+        cprime = sg["colour"] * np.where(sg["diffuse_group"], 1.0 - sg["metal"], 1.0)[:, None]
+        lobe = np.where(mirror, 0, np.where(sg["diffuse_group"], 2, 1))
+
+        def facing(L, live):
+            NoL = _dot(sg["N"], L)
+            fl = np.where(live & (np.abs(NoL) <= NOL_EPS), FLAG_NOL, 0) | np.where(live & (NoL > 0) & (NoL < GRAZING_NOL), FLAG_GRAZING_DEEP, 0)
+            flags[px] |= fl
+            count(lev, "facing_away", (live & (NoL <= 0.0)).sum())
+            return NoL, live & (NoL > 0.0)
+
+        def lit(k, L, NoL, tmax, scale):
+            """Shadow rays of the hits k along L [len(k) 3]; the unoccluded ones' terms x scale x T into S."""
+            nonlocal rays
+            rays += k.size if sg["run"] == 0 else 0
+            if not k.size:
+                return
+            h = closest_hit(tris, sg["P"][k], L, sg["tri_of"][k], tmax=tmax, widen=sg["amp"][k])
+            flags[px[k]] |= h["flags"] & (FLAG_EDGE | FLAG_TMIN)
+            count(lev, "occluded", h["valid"].sum())
+            keep = ~h["valid"]
+            k, L, NoL, scale = k[keep], L[keep], NoL[keep], (scale[0][keep], scale[1][keep])
+            err = HIT_COSINE_ERROR * sg["amp"][k]
+            sl, sh, _ = _direct_term(sg, k, L, NoL, D_SLACK + 2.0 * err / np.maximum(np.sqrt(_dot(sg["V"][k] + L, sg["V"][k] + L)), 2.0 ** -10))
+            dt = cprime[k] * (NoL / np.pi)[:, None]
+            nl, nh = (np.maximum(NoL - err, 0.0) / NoL)[:, None], ((NoL + err) / NoL)[:, None]
+            tl = np.where(mirror[k][:, None], sl, dt) * nl * scale[0] * sg["T"][k] * np.maximum(1.0 - t_err[k], 0.0)[:, None]
+            th = np.where(mirror[k][:, None], sh, dt) * nh * scale[1] * sg["T"][k] * (1.0 + t_err[k])[:, None]
+            lo[img, px[k]] += np.minimum(tl, th); hi[img, px[k]] += np.maximum(tl, th); term[img, px[k]] = True
+            if sg["run"] == 0:      # the value itself, no error carried (the specular lobe: the middle of its D_SLACK interval)
+                mid[img, px[k]] += np.where(mirror[k][:, None], 0.5 * (sl + sh), dt) * (0.5 * (scale[0] + scale[1])) * sg["T"][k]
+            for c, name in enumerate(LOBES):
+                count(lev, name, (lobe[k] == c).sum())
+
+        every = np.ones(len(px), bool)
+        if sun is not None:
+            L, E = np.asarray(sun[0], np.float64), np.asarray(sun[1], np.float64)
+            NoL, live = facing(np.broadcast_to(L, (len(px), 3)), every)
+            k = np.nonzero(live)[0]
+            lit(k, np.broadcast_to(L, (k.size, 3)), NoL[k], RAY_TMAX, (np.broadcast_to(E, (k.size, 3)),) * 2)
+        for lt in lights:
+            I = np.asarray(lt["intensity"], np.float64)
+            if not (I > 0).any():
+                continue
+            assert lt.get("radius", 0.0) == 0.0
+            R = float(np.float32(lt["range"]))
+            D = np.asarray(lt["position"], np.float32).astype(np.float64) - sg["P"]
+            d2 = _dot(D, D)
+            flags[px] |= np.where((np.abs(d2 - R * R) <= 1e-5 * R * R) | (np.abs(d2 - 1e-6) <= 1e-11), FLAG_RANGE, 0)
+            live = (d2 >= 1e-6) & (d2 < R * R)
+            count(lev, "out_of_range", (~live).sum())
+            L = _unit(D)
+            NoL, live = facing(L, live)
+            spot = (np.ones(len(px)),) * 2
+            co = float(np.float32(lt.get("cos_outer", -1.0)))
+            if co > -1.0:
+                c = -_dot(L, np.asarray(lt["axis"], np.float32).astype(np.float64))
+                err = HIT_COSINE_ERROR * sg["amp"]
+                flags[px] |= np.where(live & (np.abs(c - co) <= err), FLAG_CONE, 0)
+                count(lev, "outside_cone", (live & (c <= co)).sum())
+                live = live & (c > co)
+                ci = float(np.float32(lt["cos_inner"]))
+                spot = (light_spot(c - err, co, ci), light_spot(c + err, co, ci))
+            k = np.nonzero(live)[0]
+            lit(k, L[k], NoL[k], np.sqrt(d2[k]), tuple(I * light_attenuation(d2[k], R, 0.0, sp[k])[:, None] for sp in spot))
+    # the hull of the three runs (frame(): the sampler roots' slack 0, -, +), flagged where they do not agree on which terms exist
+    lo, hi, term = np.minimum.reduce([r[0] for r in runs]), np.maximum.reduce([r[1] for r in runs]), runs[0][2]
+    flags |= np.where(((runs[1][2] != term) | (runs[2][2] != term)).any(axis=0), FLAG_CANCEL, 0)
+    return {"lo": lo.reshape((2,) + shape + (3,)), "hi": hi.reshape((2,) + shape + (3,)), "term": term.reshape((2,) + shape), "flags": flags.reshape(shape),
+            "mid": mid.reshape((2,) + shape + (3,)), "rays": int(rays), "counts": counts}
+
+
+def sun_hits_pass(scene, fc_bytes, m, direction, irradiance):
+    return hits_pass(scene, fc_bytes, m, sun=(direction, irradiance))
+
+
+def light_hits_pass(scene, fc_bytes, m, lights):
+    return hits_pass(scene, fc_bytes, m, lights=lights)
 
 
 def unpack_r11g11b10(words):
