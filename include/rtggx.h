@@ -866,7 +866,8 @@ int  rtggx_set_light_sampling(rtggx_context* ctx, int mode);
  * from being read as history.  There are no atomics: a pixel writes only its own record and reads only the other image; the two images and
  * both traced images are a pure function of the frame sequence.
  * Known limits: the hits are not covered (a path's hit has no velocity to follow); the floor means a light that leaves shadow is noticed
- * only at 1/16 of its share; the estimates are per pixel and not filtered over neighbours.  tests/light_vis_ref.cpp restates the rule. */
+ * only at 1/16 of its share; the estimates are per pixel and not filtered over neighbours.  tests/light_vis_ref.cpp restates the rule.
+ * It does not act on a light list (rtggx_set_light_list): a record has eight bytes, a list up to 1024 lights. */
 #define RTGGX_LIGHT_VIS_FLOOR 16u      /* policy default, not a measurement */
 typedef struct RtggxLightVisRecord {   /* 16 bytes */
   uint8_t  v[8];      /* v[i]: visibility estimate of light i, 0 .. 255 */
@@ -877,6 +878,55 @@ int  rtggx_set_light_pick_visibility(rtggx_context* ctx, int enable);   /* 0 (de
 /* Synchronises and copies image 0 or 1 of the records (W x H, row by row) to out; *sequence (may be NULL) receives the context's s.  It fails
  * before anything is allocated (before the first acting frame), for an image other than 0 or 1, and when bytes is not W H 16. */
 int  rtggx_read_light_visibility(rtggx_context* ctx, uint32_t image /* 0, 1 */, RtggxLightVisRecord* out, size_t bytes, uint32_t* sequence);
+
+/* Local lights beyond eight: a list of up to RTGGX_MAX_LIGHT_LIST lights in device memory, one shadow ray per surface point for all of them,
+ * and per 8x8 block only the lights whose range reaches the block are looked at.  The same RtggxLight, checked as rtggx_set_lights checks it,
+ * with the same refusals: a null pointer with count > 0; in any light a non-finite position; a range that is not finite or not above 0; a
+ * non-finite or negative intensity component; a radius that is not finite, is negative, or is >= the range; with cos_outer > -1 an axis that
+ * is non-finite or zero, or cosines that do not satisfy -1 < cos_outer < cos_inner <= 1; a list on a context at ray rate 4, and rate 4 on a
+ * context with a list.  The axis is normalised in double and rounded once.  Refused as well: count > RTGGX_MAX_LIGHT_LIST; count > 0 while
+ * rtggx_set_lights holds count > 0, and rtggx_set_lights with count > 0 while a list is held -- the context holds one or the other.  A
+ * refused call leaves what the context had.  The list is copied before the call returns and takes effect with the next
+ * rtggx_render_visibility, which uploads it; (NULL, 0) clears the list.  Opt-in: a context that never calls this, or has cleared the list,
+ * allocates and launches exactly what it did.  A light whose intensity is 0 in every component stays in the list, keeps its index and casts
+ * no ray.
+ * The rule with a list of n lights is mode 1's rule, whatever rtggx_set_light_sampling says.  The primary pass, and under
+ * rtggx_set_light_reflections(ctx, 1) the hit passes, are rtggx_set_light_sampling's steps 0-7 and its hit rule, word for word, with i
+ * running 0 .. n - 1: the candidates, w_i, W summed ascending, the draw from slot 96 (the hits: 104 + 2 d + img), "the first candidate with
+ * t < c, else the last", f = W / w_i, the chosen light's target, ray and term.  The only new number is the hash slot of the target of a
+ * light i >= 8; below 8 the slots of rtggx_set_lights hold:
+ *   primary: 16 + i for i < 8, 4096 + i for i >= 8;
+ *   hits:    32 + 16 d + 8 img + i for i < 8, 8192 + 1024 (2 d + img) + i for i >= 8 (with d <= 3 it meets nothing in use).
+ * The sums, the resolve, the order (the sun first, then this one term, level by level), the queue formats, strips (pixel is the full-frame
+ * index), deforming meshes, caller-owned streams and rtggx_set_async_compute(0) are mode 1's.  With n <= 8 the images and the ray count
+ * are those of the same lights through rtggx_set_lights in mode 1.  rtggx_set_light_pick_visibility does not act on a list: its records
+ * have eight bytes.
+ * The cull.  Per 8x8 block of the primary pass, over the block's covered pixels in the pass's rows: lo_c / hi_c are the fp32 minimum /
+ * maximum of P_c, the P of step 0.  Per light k that casts rays (an intensity component is not 0), in fp32 without contraction, each
+ * operation rounded on its own:
+ *   e_c = max(max(lo_c - Pl_c, Pl_c - hi_c), 0);  dist2 = (e_x e_x + e_y e_y) + e_z e_z;  RRm = (R R) 1.000244140625f (that is 1 + 2^-12);
+ *   light k is KEPT iff dist2 < RRm.
+ * A light without intensity is never kept.  Lanes evaluate kept lights only.  At the hits the box is taken over the lanes of one 64-slot
+ * round of a bin that hold a touched hit, from P = o + t dir.
+ * The cull is invisible: for P in the box every |Pl_c - P_c| >= e_c exactly, each quantity a single rounding of an exact difference, and
+ * rounding is monotonic; squares and sums of non-negative terms carry at most (1 + 2^-24)^k with k <= 8; so d2 < R R at any pixel implies
+ * dist2 < R R (1 + 2^-20) < RRm.  A light that is not kept is out of range at every point of the block: its w_i is +0 there, which leaves
+ * W and c as they are, and it cannot be chosen.  The images and the ray count are those of the walk over all n lights, bit for bit
+ * (DESIGN.md section 9 "A culled light list"; tests/light_list_ref.cpp restates the rule without a cull and asserts the implication).
+ * Per frame one generating launch, one any-hit traversal and one add, and per level and sample of the hits likewise, whatever n.  Memory: 80
+ * bytes per light, mode 1's queue, sums and diffuse terms, and 4 bytes per 8x8 block for the counts below.
+ * Known limits: no culling by cone or by facing; no world-space grid for the hits, whose points are incoherent (a round's box can be large:
+ * the cull there saves less); no visibility records for lists; lights that move need a new call; no more than 1024 lights. */
+#define RTGGX_MAX_LIGHT_LIST 1024u
+int  rtggx_set_light_list(rtggx_context* ctx, const RtggxLight* lights, uint32_t count);
+/* Synchronises and copies, row-major by 8x8 block, the number of kept lights of the last frame's primary pass: ceil(H/8) rows of ceil(W/8)
+ * words.  A block with no covered pixel, or in a 16x16 tile in which nothing is drawn, reads 0 (and so does every block under a list
+ * without a casting light).  Whole frames only: it fails on a context with a strip; it fails before the first frame with a list, and
+ * when bytes != ceil(H/8) ceil(W/8) 4. */
+int  rtggx_read_light_list_counts(rtggx_context* ctx, uint32_t* out, size_t bytes);
+/* 1 (default): the cull.  0: every casting light is kept in every block that has a covered pixel (the hits: a touched hit) -- the same
+ * images and ray counts, the counts equal to the number of casting lights, the time of a walk over all lights.  Anything else is refused. */
+int  rtggx_debug_light_list_cull(rtggx_context* ctx, int enable);   /* 1 (default) / 0: keep every casting light */
 
 /* The sun from the environment: finds the sun in the current cube, measures its direction and irradiance -- what rtggx_set_sun wants -- and,
  * where asked, takes it out of the cube, so that a probe with a sun in it does not light the scene twice (once analytically, with shadows, and

@@ -21,7 +21,7 @@ HOST_EXPORTS = ["rtggx_app_last_error", "rtggx_app_create", "rtggx_app_destroy",
                 "rtggx_app_save_reference", "rtggx_app_flush_scores", "rtggx_app_set_reference", "rtggx_app_set_scoring", "rtggx_app_read_scores",
                 "rtggx_host_write_pfm", "rtggx_host_read_pfm", "rtggx_host_load_env_image",
                 "rtggx_app_set_sample_map", "rtggx_app_set_lights", "rtggx_app_set_light_reflections", "rtggx_app_set_light_sampling",
-                "rtggx_app_set_light_pick_visibility"]
+                "rtggx_app_set_light_pick_visibility", "rtggx_app_set_light_list"]
 
 _lib = None
 
@@ -62,6 +62,7 @@ def load():
         L.rtggx_app_set_light_reflections.argtypes = [C.c_void_p, C.c_int]
         L.rtggx_app_set_light_sampling.argtypes = [C.c_void_p, C.c_int]
         L.rtggx_app_set_light_pick_visibility.argtypes = [C.c_void_p, C.c_int]
+        L.rtggx_app_set_light_list.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.rtggx_app_last_screen_shot.argtypes = [C.c_void_p]
         L.rtggx_app_last_screen_shot.restype = C.c_char_p
         L.rtggx_host_obj_import.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p]
@@ -284,6 +285,14 @@ class RayTracedGGX:
     def set_light_sampling(self, mode):
         """RayTracer::SetLightSampling: 0 a shadow ray per light, 1 one per surface point for all lights, from the next frame on."""
         if self.L.rtggx_app_set_light_sampling(self.h, int(mode)) != 0:
+            raise capi.RtggxError(self.L.rtggx_app_last_error().decode())
+
+    def set_light_list(self, lights):
+        """RayTracer::SetLightList: a list of up to capi.MAX_LIGHT_LIST lights (capi.Light, or dicts with its arguments) under mode 1's
+        rule from the next frame on; None or an empty sequence clears it."""
+        lights = [l if isinstance(l, capi.Light) else capi.Light.of(**l) for l in (lights or ())]
+        a = (capi.Light * len(lights))(*lights) if lights else None
+        if self.L.rtggx_app_set_light_list(self.h, a, len(lights)) != 0:
             raise capi.RtggxError(self.L.rtggx_app_last_error().decode())
 
     def set_light_pick_visibility(self, enable):

@@ -24,6 +24,7 @@ PIXELS_RGBE8, PIXELS_RGB32F = 0, 1
 ENV_FILTER_MIN_SAMPLES, ENV_FILTER_MAX_SAMPLES = 64, 4096      # rtggx_prefilter_env
 MAX_SUN_ANGLE_DEGREES = 10.0                                    # rtggx_set_sun_angle
 MAX_LIGHTS = 8                                                  # rtggx_set_lights
+MAX_LIGHT_LIST = 1024                                           # rtggx_set_light_list
 
 _BUF_DTYPE = {BUF_VISIBILITY: np.uint32, BUF_DEPTH: np.uint32, BUF_NORMAL: np.uint32, BUF_ROUGH_METAL: np.uint16,
               BUF_VELOCITY: np.uint32, BUF_RT_REFL: np.uint32, BUF_RT_DIFF: np.uint32, BUF_TSS0: np.uint64, BUF_TSS1: np.uint64,
@@ -44,7 +45,8 @@ EXPORTS = ["rtggx_last_error", "rtggx_create", "rtggx_destroy", "rtggx_set_strip
            "rtggx_set_env_image", "rtggx_generate_env_mips", "rtggx_prefilter_env",
            "rtggx_set_sample_map", "rtggx_read_sample_map", "rtggx_trace_occlusion", "rtggx_set_sun", "rtggx_set_sun_reflections",
            "rtggx_sun_from_env", "rtggx_set_sun_angle", "rtggx_set_lights", "rtggx_set_light_reflections", "rtggx_set_light_sampling",
-           "rtggx_set_light_pick_visibility", "rtggx_read_light_visibility"]
+           "rtggx_set_light_pick_visibility", "rtggx_read_light_visibility",
+           "rtggx_set_light_list", "rtggx_read_light_list_counts", "rtggx_debug_light_list_cull"]
 SCORE_RING = 256
 
 
@@ -168,6 +170,9 @@ def load():
     L.rtggx_set_light_sampling.argtypes = [vp, C.c_int]
     L.rtggx_set_light_pick_visibility.argtypes = [vp, C.c_int]
     L.rtggx_read_light_visibility.argtypes = [vp, C.c_uint32, vp, C.c_size_t, C.POINTER(C.c_uint32)]
+    L.rtggx_set_light_list.argtypes = [vp, C.POINTER(Light), C.c_uint32]
+    L.rtggx_read_light_list_counts.argtypes = [vp, vp, C.c_size_t]
+    L.rtggx_debug_light_list_cull.argtypes = [vp, C.c_int]
     L.rtggx_sun_from_env.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_int, C.POINTER(SunEstimate)]
     L.rtggx_ray_total.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
     L.rtggx_kernel_times.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
@@ -663,6 +668,26 @@ class Context:
         seq = C.c_uint32()
         self._check(self.L.rtggx_read_light_visibility(self.h, int(image), _p(a), a.nbytes, C.byref(seq)))
         return a, seq.value
+
+    def set_light_list(self, lights):
+        """A list of up to MAX_LIGHT_LIST lights under mode 1's rule, culled per 8x8 block, from the next frame on (include/rtggx.h has the
+        rule): a sequence of Light, or of dicts with Light.of's arguments; None or an empty sequence clears the list.  In place of
+        set_lights, not beside it."""
+        lights = [l if isinstance(l, Light) else Light.of(**l) for l in (lights or ())]
+        if not lights:
+            return self._check(self.L.rtggx_set_light_list(self.h, None, 0))
+        self._check(self.L.rtggx_set_light_list(self.h, (Light * len(lights))(*lights), len(lights)))
+
+    def read_light_list_counts(self):
+        """The kept lights per 8x8 block of the last frame's primary pass with a list, uint32 [ceil(H/8), ceil(W/8)].  Synchronises.  Raises
+        before the first frame with a list, and on a strip."""
+        a = np.zeros(((self.H + 7) // 8, (self.W + 7) // 8), np.uint32)
+        self._check(self.L.rtggx_read_light_list_counts(self.h, _p(a), a.nbytes))
+        return a
+
+    def debug_light_list_cull(self, enable):
+        """1 (default): the list's cull; 0: every casting light is kept in every block that has a point -- the same images, the walk's time."""
+        self._check(self.L.rtggx_debug_light_list_cull(self.h, int(enable)))
 
     def sun_from_env(self, cone=0, ring=0, min_contrast=0, remove=False):
         """The sun of the current environment (include/rtggx.h): the record as a dict (SunEstimate.as_dict) -- "direction" and "irradiance" are

@@ -361,6 +361,7 @@ int rtggx_set_ray_rate(rtggx_context* c, uint32_t pixelsPerRay) {
   if (pixelsPerRay != 1u && c->accumulateRequested) { setError("rtggx_set_ray_rate: rate %u on an accumulating context (rtggx_set_accumulation): three quarters of such a frame are interpolations", pixelsPerRay); return -1; }
   if (pixelsPerRay != 1u && c->sunRequested.on) { setError("rtggx_set_ray_rate: rate %u on a context with a sun (rtggx_set_sun): three quarters of such a frame are interpolations", pixelsPerRay); return -1; }
   if (pixelsPerRay != 1u && c->lightsRequested.count) { setError("rtggx_set_ray_rate: rate %u on a context with lights (rtggx_set_lights): three quarters of such a frame are interpolations", pixelsPerRay); return -1; }
+  if (pixelsPerRay != 1u && c->lightListRequested.count) { setError("rtggx_set_ray_rate: rate %u on a context with a light list (rtggx_set_light_list): three quarters of such a frame are interpolations", pixelsPerRay); return -1; }
   if (pixelsPerRay != 1u && (c->rowBegin > 0u || c->rowEnd < c->H)) { setError("rtggx_set_ray_rate: rate %u on a strip (rows [%u,%u) of %u): whole frames only", pixelsPerRay, c->rowBegin, c->rowEnd, c->H); return -1; }
   if (pixelsPerRay == c->rayRate) return 0;
   RT_HIP(syncStreams(c));
@@ -473,6 +474,22 @@ int rtggx_set_sun_reflections(rtggx_context* c, int enable) {
   c->sunReflectionsRequested = enable == 1;
   return 0;
 }
+// One light of a list as both setters check it (rtggx_set_lights, rtggx_set_light_list: fn names the caller in the message): l is the copy the
+// context keeps, its axis normalised in double and rounded once, its pad zero
+static int checkLight(const char* fn, uint32_t i, RtggxLight& l) {
+  for (int k = 0; k < 3; ++k) if (!std::isfinite(l.position[k])) { setError("%s: light %u: position component %d is %g: finite", fn, i, k, (double)l.position[k]); return -1; }
+  if (!std::isfinite(l.range) || !(l.range > 0.0f)) { setError("%s: light %u: a range of %g: finite and above 0", fn, i, (double)l.range); return -1; }
+  for (int k = 0; k < 3; ++k) if (!std::isfinite(l.intensity[k]) || l.intensity[k] < 0.0f) { setError("%s: light %u: intensity component %d is %g: finite and not negative", fn, i, k, (double)l.intensity[k]); return -1; }
+  if (!std::isfinite(l.radius) || l.radius < 0.0f || !(l.radius < l.range)) { setError("%s: light %u: a radius of %g: finite, not negative and below the range %g", fn, i, (double)l.radius, (double)l.range); return -1; }
+  if (l.cos_outer > -1.0f) {      // a cone; (a NaN here is no cone by this test and is refused with the cosines below)
+    const double x = l.axis[0], y = l.axis[1], z = l.axis[2], len = std::sqrt(x * x + y * y + z * z);
+    if (!std::isfinite(len) || !(len > 0.0)) { setError("%s: light %u: the axis (%g, %g, %g) has no finite, non-zero length", fn, i, x, y, z); return -1; }
+    if (!(l.cos_outer < l.cos_inner && l.cos_inner <= 1.0f)) { setError("%s: light %u: cosines %g (outer) and %g (inner): -1 < outer < inner <= 1", fn, i, (double)l.cos_outer, (double)l.cos_inner); return -1; }
+    l.axis[0] = (float)(x / len); l.axis[1] = (float)(y / len); l.axis[2] = (float)(z / len);
+  } else if (!(l.cos_outer <= -1.0f)) { setError("%s: light %u: cos_outer is %g: at most -1 (no cone), or -1 < outer < inner <= 1", fn, i, (double)l.cos_outer); return -1; }
+  l.pad[0] = l.pad[1] = l.pad[2] = 0.0f;
+  return 0;
+}
 // Local lights (include/rtggx.h).  The list is checked as a whole and copied; a cone's axis is normalised in double and rounded once, the sun's
 // rule.  (NULL, 0) turns the lights off.  A refused call leaves what the context had.  Nothing is allocated here (the first frame with lights
 // does: lighting.hip launchLights).  No synchronisation, no end of a still-sky run, no reset of an accumulation, as for the sun.
@@ -480,26 +497,57 @@ int rtggx_set_lights(rtggx_context* c, const RtggxLight* lights, uint32_t count)
   RT_CHECK_CTX(c);
   if (count > RTGGX_MAX_LIGHTS) { setError("rtggx_set_lights: %u lights: at most %u", count, RTGGX_MAX_LIGHTS); return -1; }
   if (count && !lights) { setError("rtggx_set_lights: %u lights at a null pointer", count); return -1; }
+  if (count && c->lightListRequested.count) { setError("rtggx_set_lights: %u lights on a context that holds a light list of %u (rtggx_set_light_list): the context holds one or the other", count, c->lightListRequested.count); return -1; }
   if (count && c->rayRate != 1u) { setError("rtggx_set_lights: on a context tracing one pixel in %u (rtggx_set_ray_rate): three quarters of such a frame are interpolations", c->rayRate); return -1; }
   rtggx_context::Lights next;
   for (uint32_t i = 0; i < count; ++i) {
     RtggxLight l = lights[i];
-    for (int k = 0; k < 3; ++k) if (!std::isfinite(l.position[k])) { setError("rtggx_set_lights: light %u: position component %d is %g: finite", i, k, (double)l.position[k]); return -1; }
-    if (!std::isfinite(l.range) || !(l.range > 0.0f)) { setError("rtggx_set_lights: light %u: a range of %g: finite and above 0", i, (double)l.range); return -1; }
-    for (int k = 0; k < 3; ++k) if (!std::isfinite(l.intensity[k]) || l.intensity[k] < 0.0f) { setError("rtggx_set_lights: light %u: intensity component %d is %g: finite and not negative", i, k, (double)l.intensity[k]); return -1; }
-    if (!std::isfinite(l.radius) || l.radius < 0.0f || !(l.radius < l.range)) { setError("rtggx_set_lights: light %u: a radius of %g: finite, not negative and below the range %g", i, (double)l.radius, (double)l.range); return -1; }
-    if (l.cos_outer > -1.0f) {      // a cone; (a NaN here is no cone by this test and is refused with the cosines below)
-      const double x = l.axis[0], y = l.axis[1], z = l.axis[2], len = std::sqrt(x * x + y * y + z * z);
-      if (!std::isfinite(len) || !(len > 0.0)) { setError("rtggx_set_lights: light %u: the axis (%g, %g, %g) has no finite, non-zero length", i, x, y, z); return -1; }
-      if (!(l.cos_outer < l.cos_inner && l.cos_inner <= 1.0f)) { setError("rtggx_set_lights: light %u: cosines %g (outer) and %g (inner): -1 < outer < inner <= 1", i, (double)l.cos_outer, (double)l.cos_inner); return -1; }
-      l.axis[0] = (float)(x / len); l.axis[1] = (float)(y / len); l.axis[2] = (float)(z / len);
-    } else if (!(l.cos_outer <= -1.0f)) { setError("rtggx_set_lights: light %u: cos_outer is %g: at most -1 (no cone), or -1 < outer < inner <= 1", i, (double)l.cos_outer); return -1; }
-    l.pad[0] = l.pad[1] = l.pad[2] = 0.0f;
+    if (checkLight("rtggx_set_lights", i, l)) return -1;
     next.l[i] = l;
   }
   next.count = count;
   c->lightsRequested = next;
   c->lightVisSeq0 = c->lightVisSeq;      // rtggx_set_light_pick_visibility: a reset -- the next acting frame has no valid history
+  return 0;
+}
+// A light list beyond eight (include/rtggx.h): rtggx_set_lights' checks over up to RTGGX_MAX_LIGHT_LIST lights, copied; (NULL, 0) clears the
+// list.  A refused call leaves what the context had.  Nothing is allocated here: the next rtggx_render_visibility uploads the list
+// (lighting.hip uploadLightList).  No end of a still-sky run, no reset of an accumulation, as for the lights.
+int rtggx_set_light_list(rtggx_context* c, const RtggxLight* lights, uint32_t count) {
+  RT_CHECK_CTX(c);
+  if (count > RTGGX_MAX_LIGHT_LIST) { setError("rtggx_set_light_list: %u lights: at most %u", count, RTGGX_MAX_LIGHT_LIST); return -1; }
+  if (count && !lights) { setError("rtggx_set_light_list: %u lights at a null pointer", count); return -1; }
+  if (count && c->lightsRequested.count) { setError("rtggx_set_light_list: a list of %u on a context that holds %u lights (rtggx_set_lights): the context holds one or the other", count, c->lightsRequested.count); return -1; }
+  if (count && c->rayRate != 1u) { setError("rtggx_set_light_list: on a context tracing one pixel in %u (rtggx_set_ray_rate): three quarters of such a frame are interpolations", c->rayRate); return -1; }
+  rtggx_context::LightList next;
+  next.l.resize(count);
+  for (uint32_t i = 0; i < count; ++i) {
+    RtggxLight l = lights[i];
+    if (checkLight("rtggx_set_light_list", i, l)) return -1;
+    next.l[i] = l;
+  }
+  if (!count && !c->lightListRequested.count) return 0;      // nothing held, nothing asked for: the context stays as it is
+  next.count = count;
+  next.version = ++c->lightListVersions;
+  c->lightListRequested = std::move(next);
+  return 0;
+}
+// The kept lights per 8x8 block of the last frame's primary pass with a list, behind everything the context has enqueued
+int rtggx_read_light_list_counts(rtggx_context* c, uint32_t* out, size_t bytes) {
+  RT_CHECK_CTX(c);
+  if (c->rowBegin > 0u || c->rowEnd < c->H) { setError("rtggx_read_light_list_counts: on a strip (rows [%u,%u) of %u): whole frames only", c->rowBegin, c->rowEnd, c->H); return -1; }
+  if (!c->lightListKept || !c->lightListFrame) { setError("rtggx_read_light_list_counts: no counts yet: they exist from the first frame with a list (rtggx_set_light_list)"); return -1; }
+  const size_t want = (size_t)((c->H + 7u) / 8u) * ((c->W + 7u) / 8u) * 4u;
+  if (!out || bytes != want) { setError("rtggx_read_light_list_counts: %zu bytes at %p: %u x %u blocks of 4 bytes are %zu", bytes, (void*)out, (c->W + 7u) / 8u, (c->H + 7u) / 8u, want); return -1; }
+  RT_HIP(syncStreams(c));
+  RT_HIP(hipMemcpy(out, c->lightListKept, want, hipMemcpyDeviceToHost));
+  return 0;
+}
+// 1 (default): the cull; 0: every casting light is kept wherever a block has a point -- the same images, the time of the walk over all lights
+int rtggx_debug_light_list_cull(rtggx_context* c, int enable) {
+  RT_CHECK_CTX(c);
+  if (enable != 0 && enable != 1) { setError("rtggx_debug_light_list_cull: %d: 0 or 1", enable); return -1; }
+  c->lightListCullOn = enable == 1;
   return 0;
 }
 // The lights at the surfaces the paths hit (include/rtggx.h).  Only the value is kept: it is stored whether or not lights are set, allocates

@@ -196,6 +196,11 @@ int rtggx_render_visibility(rtggx_context* c) {
   settleSetRead(c);      // (the previous frame ended without the kernel that would have carried its set's event)
   ++c->frameCounter;
   c->maxDepth = c->depthRequested; c->samples = c->samplesRequested; c->accumulate = c->accumulateRequested; c->sun = c->sunRequested; c->sunAngle = c->sunAngleRequested; c->sunReflections = c->sunReflectionsRequested; c->lights = c->lightsRequested; c->lightReflections = c->lightReflectionsRequested; c->lightSampling = c->lightSamplingRequested; c->lightVis = c->lightVisRequested;
+  if (c->lightList.version != c->lightListRequested.version) {      // rtggx_set_light_list: the new list, and its copy on the device
+    RT_HIP(syncStreams(c));      // (a frame in flight may read the list the upload replaces)
+    c->lightList = c->lightListRequested;
+    const int r = uploadLightList(c); if (r) return r;
+  }
   c->scoring = c->scoringRequested && c->reference != nullptr;
   c->sampleMap = c->sampleMapRequested;      // rtggx_set_sample_map: the setter has waited for every stream and written the copy no frame reads
   bool resendConstants = false;
@@ -317,7 +322,7 @@ int rtggx_ray_trace(rtggx_context* c) {
   }
   // local lights (rtggx_set_lights): per light three kernels and one resolve behind the last, on the main stream behind the sun's pass, for
   // the sun's reasons -- both traced images are complete here, and from here on the main stream is who wrote them last
-  if (c->lights.count) {
+  if (c->lights.count || c->lightList.count) {      // (rtggx_set_light_list: the same pass over the list)
     if (!r) r = launchLights(c, fp, c->streamMain);
     c->shadeStream = c->diffStream = c->streamMain;
   }

@@ -1,6 +1,7 @@
 // Direct lighting: the sun (rtggx_set_sun, rtggx_set_sun_angle), the local lights (rtggx_set_lights) and both at the surfaces the paths hit
 // (rtggx_set_sun_reflections, rtggx_set_light_reflections); one shadow ray for all lights (rtggx_set_light_sampling: the two picking kernels
-// further down, with a table of their own; rtggx_set_light_pick_visibility: the primary pair of them once more, with a record per pixel).
+// further down, with a table of their own; rtggx_set_light_pick_visibility: the primary pair of them once more, with a record per pixel);
+// a list of up to 1024 lights in device memory, culled per block (rtggx_set_light_list: the last pair of generating kernels).
 // include/rtggx.h has the per-pixel rules, DESIGN.md section 9 the structure.
 //
 // Every pass is the same three launches around a queue of its own (rt::ShadowQueue, rt_queue.h): a generating kernel derives a surface --
@@ -728,6 +729,8 @@ static LightListArgs pickList(const rtggx_context* c) {
 }
 static void (*const kLightPickGen[4])(const FrameParams*, LightPickGenArgs) = {lightPickGenKernel<false, false>, lightPickGenKernel<false, true>, lightPickGenKernel<true, false>, lightPickGenKernel<true, true>};
 static void (*const kLightPickVisGen[4])(const FrameParams*, LightPickGenArgs, LightVisArgs) = {lightPickVisGenKernel<false, false>, lightPickVisGenKernel<false, true>, lightPickVisGenKernel<true, false>, lightPickVisGenKernel<true, true>};
+static int clearLightListCounts(rtggx_context* c, hipStream_t s);      // rtggx_set_light_list, further down
+static int launchLightListGen(rtggx_context* c, hipStream_t s, const LightPickGenArgs& P, uint32_t numTiles);
 
 int launchLights(rtggx_context* c, const FrameParams& fp, hipStream_t s) {
   uint32_t rb, re;
@@ -735,7 +738,8 @@ int launchLights(rtggx_context* c, const FrameParams& fp, hipStream_t s) {
   if (re <= rb) return 0;
   const uint32_t tilesX = (fp.W + 15) / 16, tilesY = (re - rb + 15) / 16, numTiles = tilesX * tilesY;
   if (numTiles * 4u > c->numBinsMax) { setError("rtggx_ray_trace: the lights' queue does not hold %u bins", numTiles * 4u); return -1; }
-  const bool pick = c->lightSampling == 1u;      // rtggx_set_light_sampling
+  const bool list = c->lightList.count > 0u;      // rtggx_set_light_list: mode 1's launches, the generating kernel the list's (further down)
+  const bool pick = c->lightSampling == 1u || list;      // rtggx_set_light_sampling
   { // what the lights need, from the first frame that has some: the queue with its intervals, the sums -- and in mode 1 the diffuse terms
     bool filled = false;
     { const int r = c->lightQueue.ensure(c->numBinsMax, RT_BIN_MIN, true, filled); if (r) return r; }
@@ -758,6 +762,17 @@ int launchLights(rtggx_context* c, const FrameParams& fp, hipStream_t s) {
     P.visDepth = G.visDepth; P.fat0 = G.fat0; P.fat1 = G.fat1;
     P.rays = G.rays; P.hits = G.hits; P.binCount = G.binCount; P.tRange = G.tRange; P.diffTerm = (float4*)c->lightPickDiff.get();
     P.tileWords = G.tileWords; P.tilesX = tilesX; P.rowBegin = rb; P.rowEnd = re;
+    if (list) {      // rtggx_set_light_list: the same three launches (none where no light of the list has an intensity) and the resolve
+      { const int r = clearLightListCounts(c, s); if (r) return r; }
+      if (c->lightListCasting) {
+        { const int r = launchLightListGen(c, s, P, numTiles); if (r) return r; }
+        { const int r = launchTrace(c, fp, s, q, numTiles * 4u, true, tilesX, tilesY, c->traceGrid[3], -1, nullptr, nullptr, 2, true); if (r) return r; }
+        const LightPickAddArgs PD{q.rays, q.hits, q.binCount, G.tileWords, P.diffTerm, D.sumRefl, D.sumDiff};
+        launch(lightPickAddKernel, dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, PD);
+        RT_HIP(hipGetLastError());
+      }
+      return launchSunHitResolve(c, s, c->lightSums, G.tileWords, tilesX, rb, re, nullptr);
+    }
     P.list = pickList(c);
     if (P.list.castMask && c->lightVis) {      // rtggx_set_light_pick_visibility: an acting frame -- the same three launches with the records
       if (rb > 0u || re < fp.H) { setError("rtggx_ray_trace: the pick's visibility records on rows [%u,%u) of %u: whole frames only", rb, re, fp.H); return -1; }
@@ -939,6 +954,251 @@ __global__ void __launch_bounds__(256) lightHitPickGenKernel(const FrameParams* 
 }
 static void (*const kLightHitPickGen[4])(const FrameParams*, LightHitPickGenArgs) = {lightHitPickGenKernel<false, false>, lightHitPickGenKernel<false, true>, lightHitPickGenKernel<true, false>, lightHitPickGenKernel<true, true>};
 
+// ---- a light list beyond eight (rtggx_set_light_list; DESIGN.md section 9 "A culled light list") ---------------------------------------------
+// Mode 1's rule over up to RTGGX_MAX_LIGHT_LIST lights that live in device memory: 64-byte records (LightArgs, pickList's neutral cone where a
+// light has none) and a packed (Pl, R) per light for the cull, R = 0 where the light casts nothing.  A wave owns an 8x8 block (the hits: one
+// 64-slot round of its bin), reduces the box of its points' P across the wave and tests 64 lights per step against it, a light per lane;
+// the ballot is a wave-uniform mask of the lights that are KEPT, and the wave walks its set bits -- the index is uniform, the record arrives
+// by scalar loads -- while every lane adds its w_i to W.  A second walk recomputes the weights until every lane has found its light: no
+// array of weights, in registers or LDS, indexed by a lane's value.  A light out of range of the whole box has w_i = +0 at each of its
+// points, which leaves W and c as they are: the images are those of the walk over all lights, bit for bit (include/rtggx.h has the argument).
+//   the step, written once below           who runs it
+//   waveBox, keptLights                    lightListGenKernel, lightListHitGenKernel
+// and from above: evalLight, primaryPickTerms, hitPickTerm, chosenLightSample, pickDraw, compactShadowRay; the adds and the resolve are mode 1's.
+struct LightRecord { LightArgs k; float pad[3]; };
+static_assert(sizeof(LightRecord) == 64 && sizeof(LightRecord) == sizeof(RtggxLight), "a light's record is 64 bytes");
+#define RT_SLOT_LIST_FIRST 8u      // below it a light's target draws from the slots of rtggx_set_lights
+#define RT_SLOT_LIST_LIGHT(i) ((i) < RT_SLOT_LIST_FIRST ? RT_SLOT_LIGHT(i) : 4096u + (i))
+#define RT_SLOT_LIST_LIGHT_HIT(d, img, i) ((i) < RT_SLOT_LIST_FIRST ? RT_SLOT_LIGHT_HIT(d, i) + RT_SLOT_LIGHT_HIT_IMAGE * (img) : 8192u + 1024u * (2u * (d) + (img)) + (i))
+RT_DEV float waveUniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+RT_DEV float waveMin(float v) { for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o)); return waveUniform(v); }
+RT_DEV float waveMax(float v) { for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o)); return waveUniform(v); }
+// The box of the points P of the wave's lanes that have one; none: (+inf, -inf), which keeps nothing
+struct WaveBox { float lox, loy, loz, hix, hiy, hiz; };
+RT_DEV WaveBox waveBox(bool has, f3 P) {
+  const float inf = __int_as_float(0x7F800000);
+  WaveBox b;
+  b.lox = waveMin(has ? P.x : inf); b.loy = waveMin(has ? P.y : inf); b.loz = waveMin(has ? P.z : inf);
+  b.hix = waveMax(has ? P.x : -inf); b.hiy = waveMax(has ? P.y : -inf); b.hiz = waveMax(has ? P.z : -inf);
+  return b;
+}
+// The cull's test of lights 64 chunk .. 64 chunk + 63, a light per lane: bit l is set iff light 64 chunk + l is kept.  any: the wave has a
+// point at all; cullOn = 0 (rtggx_debug_light_list_cull): every casting light is kept where it has.
+RT_DEV unsigned long long keptLights(const float4* __restrict__ cull, uint32_t count, uint32_t chunk, uint32_t lane, const WaveBox& b, bool any, uint32_t cullOn) {
+  const uint32_t i = chunk * 64u + lane;
+  bool keep = false;
+  if (i < count) {
+    const float4 c = cull[i];
+    const float ex = fmaxf(fmaxf(b.lox - c.x, c.x - b.hix), 0.0f), ey = fmaxf(fmaxf(b.loy - c.y, c.y - b.hiy), 0.0f), ez = fmaxf(fmaxf(b.loz - c.z, c.z - b.hiz), 0.0f);
+    const float dist2 = (ex * ex + ey * ey) + ez * ez;
+    const float RRm = (c.w * c.w) * 1.000244140625f;
+    keep = cullOn != 0u ? dist2 < RRm : any && c.w > 0.0f;
+  }
+  return __ballot(keep);
+}
+struct LightListGenArgs {
+  const unsigned long long* visDepth; const float4* fat0; const float4* fat1;
+  RayRec* rays; HitKey* hits; uint32_t* binCount; float2* tRange; float4* diffTerm;      // (LightPickGenArgs)
+  const uint32_t* tileWords; uint32_t tilesX, rowBegin, rowEnd;
+  const float* cosSin; uint32_t* kept; uint32_t blocksX, count, cullOn;      // kept: per 8x8 block of the frame, row-major, blocksX a row
+};
+template <bool CONE, bool SOFT>
+__global__ void __launch_bounds__(256) lightListGenKernel(const FrameParams* __restrict__ fpp, const LightRecord* __restrict__ recs, const float4* __restrict__ cull, LightListGenArgs A) {
+  const FrameParams& fp = *fpp;
+  const uint32_t tile = blockIdx.x;
+  if (tileIsEmpty(A.tileWords, tile)) return;
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const uint32_t px = (tile % A.tilesX) * 16 + (wave & 1u) * 8 + (lane & 7u);
+  const uint32_t py = A.rowBegin + (tile / A.tilesX) * 16 + (wave >> 1) * 8 + (lane >> 3);
+  PrimarySurface S = {};
+  bool covered = false;
+  if (px < fp.W && py < A.rowEnd) atPrimarySurface(fp, A.visDepth, A.fat0, A.fat1, px, py, [&](const PrimarySurface& s) { S = s; covered = true; });
+  const bool diffuse = S.rm.y < 1.0f;
+  const WaveBox box = waveBox(covered, S.P);
+  const bool any = __ballot(covered) != 0ull;
+  const uint32_t chunks = (A.count + 63u) >> 6;
+  // steps 1 and 2 over the kept lights, ascending: W
+  float W = 0.0f;
+  uint32_t kept = 0u;
+  for (uint32_t chunk = 0u; chunk < chunks; ++chunk) {
+    unsigned long long m = keptLights(cull, A.count, chunk, lane, box, any, A.cullOn);
+    kept += (uint32_t)__popcll(m);
+    while (m != 0ull) {
+      const uint32_t i = RT_SGPR(chunk * 64u + (uint32_t)__builtin_ctzll(m));
+      m &= m - 1ull;
+      const LightArgs K = recs[i].k;
+      if (covered) W = W + primaryPickTerms<CONE>(K, S, diffuse).w;      // (a weight of +0 leaves W as it is)
+    }
+  }
+  if (lane == 0u && px < fp.W && py < A.rowEnd) A.kept[(size_t)(py >> 3) * A.blocksX + (px >> 3)] = kept;
+  const bool active = covered && W > 0.0f;      // a candidate
+  bool want = false, wantDiff = false;
+  RayRec rr;
+  float tmax = 0.0f;
+  f3 S1 = mk3(0.0f, 0.0f, 0.0f);
+  if (__ballot(active) != 0ull) {
+    // steps 3-5: the same walk once more, until every lane has its light
+    const float t = pickDraw(S.pixel, fp.g.FrameIndex, RT_SLOT_LIGHT_PICK) * W;
+    float c = 0.0f, wc = 0.0f;
+    uint32_t chosen = 0u;
+    bool found = !active;
+    for (uint32_t chunk = 0u; chunk < chunks && __ballot(!found) != 0ull; ++chunk) {
+      unsigned long long m = keptLights(cull, A.count, chunk, lane, box, any, A.cullOn);
+      while (m != 0ull && __ballot(!found) != 0ull) {
+        const uint32_t i = RT_SGPR(chunk * 64u + (uint32_t)__builtin_ctzll(m));
+        m &= m - 1ull;
+        const LightArgs K = recs[i].k;
+        if (!found) {
+          const float w = primaryPickTerms<CONE>(K, S, diffuse).w;
+          if (w > 0.0f) { c = c + w; chosen = i; wc = w; found = t < c; }
+        }
+      }
+    }
+    if (active) {      // steps 6 and 7: the chosen light once more, with its target; its record is the lane's own load
+      const float f = W / wc;
+      const LightArgs K = recs[chosen].k;
+      LightSample l;
+      if (chosenLightSample<CONE, SOFT>(K, A.cosSin, S.P, S.N, S.pixel, fp.g.FrameIndex, RT_SLOT_LIST_LIGHT(chosen), l)) {
+        const PickTerms x = primaryPickTerms<CONE>(K, S, diffuse);
+        want = true; wantDiff = diffuse;
+        tmax = l.tmax;
+        rr = shadowRay(S.P, l.Ls, S.pixel, (S.inst << 24) | S.prim, mk3(x.spec.x * f, x.spec.y * f, x.spec.z * f), 0u);
+        S1 = mk3(x.diff.x * f, x.diff.y * f, x.diff.z * f);
+      }
+    }
+  }
+  const uint32_t bin = blockIdx.x * 4u + wave;
+  const unsigned long long wanting = __ballot(want);      // (the slot compactShadowRay gives the lane)
+  if (wantDiff) A.diffTerm[(size_t)bin * RT_BIN_MIN + (uint32_t)__popcll(wanting & ((1ull << lane) - 1ull))] = make_float4(S1.x, S1.y, S1.z, 0.0f);
+  const uint32_t n = compactShadowRay<true>(want, rr, tmax, A.rays, A.hits, A.tRange, bin, RT_BIN_MIN, 0u, lane);
+  if (lane == 0) A.binCount[bin] = n;
+}
+// The hits (rtggx_set_light_reflections with a list): lightHitPickGenKernel's walk of the bin, the box over the touched hits of one round
+struct LightListHitGenArgs : HitBinArgs {
+  RayRec* outRays; HitKey* outHits; uint32_t* outCount; float2* outRange;                   // the feature's queue: the same bins, binSlots slots each
+  const uint32_t* tileWords;
+  const float* cosSin; uint32_t frameIndex, level, count, cullOn;      // the frame index of the sample the pass belongs to
+};
+template <bool CONE, bool SOFT>
+__global__ void __launch_bounds__(256) lightListHitGenKernel(const FrameParams* __restrict__ fpp, const LightRecord* __restrict__ recs, const float4* __restrict__ cull, LightListHitGenArgs A) {
+  const FrameParams& fp = *fpp;
+  const uint32_t tile = blockIdx.x;
+  if (tileIsEmpty(A.tileWords, tile)) return;
+  const uint32_t bin = tile * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  const uint32_t count = RT_SGPR(min(A.binCount[bin] & 0xFFu, A.binSlots));
+  const uint32_t chunks = (A.count + 63u) >> 6;
+  uint32_t written = 0u;      // shadow rays in the front of the bin so far: never more than the records read
+  for (uint32_t base = 0u; base < count; base += 64u) {
+    const uint32_t slot = base + lane;
+    TracedHit H = {};
+    bool touched = false;
+    if (slot < count) atTracedHit(fp, A.rays, A.hits, A.fat0, A.fat1, (size_t)bin * A.binSlots + slot, [&](const TracedHit& h) { H = h; touched = true; });
+    const f3 P = H.P();
+    const WaveBox box = waveBox(touched, P);
+    const bool any = __ballot(touched) != 0ull;
+    float W = 0.0f;
+    for (uint32_t chunk = 0u; chunk < chunks; ++chunk) {
+      unsigned long long m = keptLights(cull, A.count, chunk, lane, box, any, A.cullOn);
+      while (m != 0ull) {
+        const uint32_t i = RT_SGPR(chunk * 64u + (uint32_t)__builtin_ctzll(m));
+        m &= m - 1ull;
+        const LightArgs K = recs[i].k;
+        if (touched) {
+          const float y = pickLuminance(hitPickTerm<CONE>(fp, K, H, P));
+          W = W + (y > 0.0f ? y : 0.0f);      // (a NaN is no candidate)
+        }
+      }
+    }
+    const bool active = touched && W > 0.0f;
+    bool want = false;
+    RayRec sr;
+    float tmax = 0.0f;
+    if (__ballot(active) != 0ull) {
+      const float t = pickDraw(H.pixel, A.frameIndex, RT_SLOT_LIGHT_PICK_HIT(A.level) + RT_SLOT_LIGHT_PICK_HIT_IMAGE * H.image) * W;
+      float c = 0.0f, wc = 0.0f;
+      uint32_t chosen = 0u;
+      bool found = !active;
+      for (uint32_t chunk = 0u; chunk < chunks && __ballot(!found) != 0ull; ++chunk) {
+        unsigned long long m = keptLights(cull, A.count, chunk, lane, box, any, A.cullOn);
+        while (m != 0ull && __ballot(!found) != 0ull) {
+          const uint32_t i = RT_SGPR(chunk * 64u + (uint32_t)__builtin_ctzll(m));
+          m &= m - 1ull;
+          const LightArgs K = recs[i].k;
+          if (!found) {
+            const float w = pickLuminance(hitPickTerm<CONE>(fp, K, H, P));
+            if (w > 0.0f) { c = c + w; chosen = i; wc = w; found = t < c; }
+          }
+        }
+      }
+      if (active) {
+        const float f = W / wc;
+        const LightArgs K = recs[chosen].k;
+        LightSample l;
+        if (chosenLightSample<CONE, SOFT>(K, A.cosSin, P, H.N, H.pixel, A.frameIndex, RT_SLOT_LIST_LIGHT_HIT(A.level, H.image, chosen), l)) {
+          const f3 s = hitPickTerm<CONE>(fp, K, H, P);
+          want = true;
+          tmax = l.tmax;
+          sr = shadowRay(P, l.Ls, H.pixel, H.hitId, mk3(s.x * f, s.y * f, s.z * f), H.image);
+        }
+      }
+    }
+    written += compactShadowRay<true>(want, sr, tmax, A.outRays, A.outHits, A.outRange, bin, A.binSlots, written, lane);
+  }
+  if (lane == 0u) A.outCount[bin] = written;
+}
+static void (*const kLightListGen[4])(const FrameParams*, const LightRecord*, const float4*, LightListGenArgs) = {lightListGenKernel<false, false>, lightListGenKernel<false, true>, lightListGenKernel<true, false>, lightListGenKernel<true, true>};
+static void (*const kLightListHitGen[4])(const FrameParams*, const LightRecord*, const float4*, LightListHitGenArgs) = {lightListHitGenKernel<false, false>, lightListHitGenKernel<false, true>, lightListHitGenKernel<true, false>, lightListHitGenKernel<true, true>};
+// The list to the device when the setting takes effect (frame.hip rtggx_render_visibility): the records with pickList's neutral cone, the
+// cull's (Pl, R) with R = 0 where a light casts nothing; how many cast, and the instance [2 cone + soft] the list runs.  A frame that still
+// reads the previous list may be in flight: the caller has waited for the streams (a change of the list is a setup step, not a per-frame one).
+int uploadLightList(rtggx_context* c) {
+  const std::vector<RtggxLight>& list = c->lightList.l;
+  c->lightListCasting = 0u; c->lightListVariant = 0u;
+  c->lightListFrame = false;
+  if (list.empty()) return 0;
+  std::vector<LightRecord> recs(list.size());
+  std::vector<float4> cull(list.size());
+  for (size_t i = 0; i < list.size(); ++i) {
+    const RtggxLight& l = list[i];
+    LightRecord r = {};
+    r.k = lightArgs(l);
+    if (!(l.cos_outer > -1.0f)) { r.k.Ax = r.k.Ay = r.k.Az = 0.0f; r.k.cosOuter = -2.0f; r.k.cosInner = -1.0f; }
+    recs[i] = r;
+    const bool casts = lightCastsRays(l);
+    cull[i] = make_float4(l.position[0], l.position[1], l.position[2], casts ? l.range : 0.0f);
+    if (casts) { ++c->lightListCasting; c->lightListVariant |= lightVariant(l); }
+  }
+  if (c->lightListCapacity < list.size()) {
+    c->lightListRecs.reset(); c->lightListCull.reset();
+    RT_HIP(alloc(c->lightListRecs, list.size() * 16u)); RT_HIP(alloc(c->lightListCull, list.size() * 4u));
+    c->lightListCapacity = (uint32_t)list.size();
+  }
+  RT_HIP(hipMemcpy(c->lightListRecs, recs.data(), recs.size() * sizeof(LightRecord), hipMemcpyHostToDevice));
+  RT_HIP(hipMemcpy(c->lightListCull, cull.data(), cull.size() * sizeof(float4), hipMemcpyHostToDevice));
+  return 0;
+}
+// The blocks' kept counts (rtggx_read_light_list_counts) exist from the first frame with a list and are cleared in front of every such
+// frame's primary pass: a wave that leaves on a zero tile word writes none, and a list without a casting light launches nothing.
+static int clearLightListCounts(rtggx_context* c, hipStream_t s) {
+  const uint32_t blocks = ((c->W + 7u) / 8u) * ((c->H + 7u) / 8u);
+  if (!c->lightListKept) { RT_HIP(allocFilled(c->lightListKept, (size_t)blocks)); const int r = syncFills(true); if (r) return r; }
+  RT_HIP(hipMemsetAsync(c->lightListKept, 0, (size_t)blocks * 4u, s));
+  c->lightListFrame = true;
+  return 0;
+}
+// The generating launch of the primary pass with a list, in lightPickGenKernel's place (launchLights): P's queue, rows and tiles
+static int launchLightListGen(rtggx_context* c, hipStream_t s, const LightPickGenArgs& P, uint32_t numTiles) {
+  const uint32_t blocksX = (c->W + 7u) / 8u;
+  LightListGenArgs A;
+  A.visDepth = P.visDepth; A.fat0 = P.fat0; A.fat1 = P.fat1;
+  A.rays = P.rays; A.hits = P.hits; A.binCount = P.binCount; A.tRange = P.tRange; A.diffTerm = P.diffTerm;
+  A.tileWords = P.tileWords; A.tilesX = P.tilesX; A.rowBegin = P.rowBegin; A.rowEnd = P.rowEnd;
+  A.cosSin = c->cosSinTab; A.kept = c->lightListKept; A.blocksX = blocksX; A.count = c->lightList.count; A.cullOn = c->lightListCullOn ? 1u : 0u;
+  launch(kLightListGen[c->lightListVariant], dim3(numTiles), dim3(256), s, nullptr, nullptr, c->dParams + c->slot,
+         (const LightRecord*)c->lightListRecs.get(), (const float4*)c->lightListCull.get(), A);
+  return 0;
+}
+
 // The frame's first use of the hit passes' queues and sums on stream s.  They exist from the first frame that has the sun or lights and the
 // respective toggle on: per feature its queue at the frame's slots per bin (the bins' growth releases it: frame.hip growBins, behind a wait
 // for every stream) -- the lights' with the rays' intervals --, and for one-sample frames S, which the two share.  The use is ordered behind
@@ -988,6 +1248,17 @@ int launchLightHits(rtggx_context* c, const FrameParams& fp, const HitPass& p) {
   G.outRays = (RayRec*)q.rays; G.outHits = q.hits; G.outCount = c->lightHitQueue.count; G.outRange = (float2*)q.tRange;
   G.tileWords = p.tileWords;
   G.cosSin = c->cosSinTab; G.frameIndex = p.frameIndex;
+  if (c->lightList.count) {      // rtggx_set_light_list: mode 1's launches, the generating kernel the list's
+    if (!c->lightListCasting) return 0;
+    LightListHitGenArgs P;
+    static_cast<HitBinArgs&>(P) = G;
+    P.outRays = G.outRays; P.outHits = G.outHits; P.outCount = G.outCount; P.outRange = G.outRange;
+    P.tileWords = G.tileWords;
+    P.cosSin = G.cosSin; P.frameIndex = p.frameIndex; P.level = p.level; P.count = c->lightList.count; P.cullOn = c->lightListCullOn ? 1u : 0u;
+    launch(kLightListHitGen[c->lightListVariant], dim3(p.numTiles), dim3(256), p.s, nullptr, nullptr, c->dParams + c->slot,
+           (const LightRecord*)c->lightListRecs.get(), (const float4*)c->lightListCull.get(), P);
+    return traceAndAddHits(c, fp, p, q);
+  }
   if (c->lightSampling == 1u) {      // rtggx_set_light_sampling: one generating launch, one traversal, one add for the whole list
     LightHitPickGenArgs P;
     static_cast<HitBinArgs&>(P) = G;

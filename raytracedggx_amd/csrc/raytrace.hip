@@ -1039,7 +1039,7 @@ static int launchShadeSamples(rtggx_context* c, const FrameParams& fp, hipStream
   const TraceQueue q{S.rays, S.spawnHits, S.binCount, S.binSlots, nullptr};
   // rtggx_set_sun_reflections: at every level acc = acc + s_d comes first, then the pass's own add of the paths that end there
   // rtggx_set_light_reflections: then the lights' terms, i ascending, still in front of the pass's own add
-  const bool sunHits = c->sun.on && c->sunReflections, lightHits = c->lights.count > 0u && c->lightReflections;
+  const bool sunHits = c->sun.on && c->sunReflections, lightHits = (c->lights.count > 0u || c->lightList.count > 0u) && c->lightReflections;
   if (sunHits || lightHits) { const int r = beginSunHits(c, s, false, sunHits, lightHits); if (r) return r; }
   for (uint32_t k = 0; k < N; ++k) {
     for (uint32_t level = 0; level < depth; ++level) {
@@ -1106,7 +1106,7 @@ int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent
   // behind the last pass -- which then no longer carries `done` -- sunHitResolveKernel adds S to the packed words
   // rtggx_set_light_reflections (the lights exclude rate 4 as well): the lights' terms follow the sun's into the same S, i ascending, and
   // the one resolve packs what either feature left there
-  const bool sunHits = c->sun.on && c->sunReflections && !quad, lightHits = c->lights.count > 0u && c->lightReflections && !quad, anyHits = sunHits || lightHits;
+  const bool sunHits = c->sun.on && c->sunReflections && !quad, lightHits = (c->lights.count > 0u || c->lightList.count > 0u) && c->lightReflections && !quad, anyHits = sunHits || lightHits;
   float* sums[2] = {nullptr, nullptr};
   if (anyHits) {
     const int r = beginSunHits(c, s, true, sunHits, lightHits); if (r) return r;

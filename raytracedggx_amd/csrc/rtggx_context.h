@@ -338,6 +338,22 @@ struct rtggx_context {
   bool lightVis = false, lightVisRequested = false;
   uint32_t lightVisSeq = 0, lightVisSeq0 = 0;
   rt::DevBuf<uint32_t> lightVisImg[2];
+  // rtggx_set_light_list: up to RTGGX_MAX_LIGHT_LIST lights in device memory under mode 1's rule, culled per 8x8 block (lighting.hip
+  // lightListGenKernel, lightListHitGenKernel).  The context holds this list or rtggx_set_lights' (the setters refuse the other); the
+  // requested list takes effect with the next rtggx_render_visibility, which uploads it where its version differs (lighting.hip
+  // uploadLightList).  From that upload:
+  //   lightListRecs  the 64-byte records (LightArgs, the neutral cone where a light has none), lightListCapacity of them
+  //   lightListCull  (Pl, R) per light, R = 0 where it casts nothing
+  //   lightListCasting, lightListVariant  how many lights cast rays, and the instance [2 cone + soft] the list runs
+  // and from the first frame with a list:
+  //   lightListKept  the kept lights per 8x8 block of the last such frame's primary pass (rtggx_read_light_list_counts); lightListFrame:
+  //                  such a frame has run since the last upload
+  // lightQueue, lightSums, lightPickDiff and lightHitQueue are used as in mode 1.
+  struct LightList { uint32_t count = 0; uint64_t version = 0; std::vector<RtggxLight> l; } lightList, lightListRequested;
+  rt::DevBuf<float> lightListRecs, lightListCull; uint32_t lightListCapacity = 0, lightListCasting = 0, lightListVariant = 0;
+  rt::DevBuf<uint32_t> lightListKept; bool lightListFrame = false;
+  bool lightListCullOn = true;      // rtggx_debug_light_list_cull
+  uint64_t lightListVersions = 0;      // successful rtggx_set_light_list calls that changed what is held: the next list's version
   uint32_t rayRate = 1;         // rtggx_set_ray_rate: pixels per traced ray, 1 or 4 (raytrace.hip rayGenKernel, reconstructKernel)
   uint32_t maxDepth = 1, depthRequested = 1;      // rtggx_set_max_recursion_depth: 1..4 levels of rays per path (raytrace.hip launchShade); the frame's, the next frame's
   // rtggx_set_samples_per_pixel: 1, 2, 4 or 8 samples per covered pixel (raytrace.hip launchShade; DESIGN.md "Samples per pixel"); the
@@ -549,6 +565,7 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
 // 5-7 us, and the frame's two chains had four of them (rocprofv3 kernel trace, profiles/).
 int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent_t done = nullptr);      // hit / miss shading of the traced bins
 int launchSun(rtggx_context* c, const FrameParams& fp, hipStream_t s);      // rtggx_set_sun: shadow rays from the primary surface, the any-hit traversal, the add into RayTracingOut0/1
+int uploadLightList(rtggx_context* c);      // rtggx_set_light_list: c->lightList to the device, behind a wait for every stream
 int launchLights(rtggx_context* c, const FrameParams& fp, hipStream_t s);   // rtggx_set_lights: per light generate -> any-hit -> add into the sums, one resolve into RayTracingOut0/1
 // rtggx_set_sun_reflections, rtggx_set_light_reflections (lighting.hip; called by launchShade in front of every level's shading pass): the frame's
 // first use of their queues and sums on stream s, then per level the sun's pass and the lights' (HitPass: rt_queue.h), then for a

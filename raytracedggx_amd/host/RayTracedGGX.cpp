@@ -39,6 +39,7 @@ void RayTracedGGX::OnInit() {
   if (m_hasSun && !m_rayTracer->SetSun(m_sun, m_sun + 3)) throw std::runtime_error("-sun: " + m_rayTracer->GetLastError());      // -sun: a directional light with ray-traced shadows (opt-in)
   if (m_sunReflections && !m_rayTracer->SetSunReflections(true)) throw std::runtime_error("-sunreflections: " + m_rayTracer->GetLastError());      // -sunreflections: ... at the surfaces the paths hit as well (opt-in)
   if (!m_lights.empty() && !m_rayTracer->SetLights(m_lights.data(), (uint32_t)m_lights.size())) throw std::runtime_error("-light / -spot: " + m_rayTracer->GetLastError());      // -light, -spot: local lights with ray-traced shadows (opt-in)
+  if (!m_lightList.empty() && !m_rayTracer->SetLightList(m_lightList.data(), (uint32_t)m_lightList.size())) throw std::runtime_error("-lightlist: " + m_rayTracer->GetLastError());      // -lightlist: a light list beyond eight, one shadow ray per point (opt-in)
   if (m_lightReflections && !m_rayTracer->SetLightReflections(true)) throw std::runtime_error("-lightreflections: " + m_rayTracer->GetLastError());      // -lightreflections: ... at the surfaces the paths hit as well (opt-in)
   if (m_lightPick && !m_rayTracer->SetLightSampling(1)) throw std::runtime_error("-lightpick: " + m_rayTracer->GetLastError());      // -lightpick: one shadow ray per surface point for all lights (opt-in)
   if (m_lightVisibility && !m_rayTracer->SetLightPickVisibility(true)) throw std::runtime_error("-lightvisibility: " + m_rayTracer->GetLastError());      // -lightvisibility: the pick weighted by what the pixel remembers (opt-in)
@@ -207,6 +208,28 @@ bool RayTracedGGX::LoadTrack(const std::string& fileName) {
 
 // RayTracedGGX.cpp:462-511: '-' or '/' prefix, case-insensitive names; a following token is a value
 // unless it starts with '/' or with '-' not followed by a digit or '.'.
+// A light from the numbers of -light / -spot or of a line of -lightlist: v = position, intensity, range, radius and (spot) axis, outer and
+// inner half-angle in degrees.  Everything the library would refuse is refused here; what / whatSpot lead the message.  The cosines:
+// cos(degrees pi / 180) in double, rounded once.
+static RtggxLight lightFromNumbers(const std::string& what, const std::string& whatSpot, bool spot, const float v[13]) {
+  RtggxLight l{};
+  for (int k = 0; k < 3; ++k) { l.position[k] = v[k]; l.intensity[k] = v[3 + k]; }
+  l.range = v[6]; l.radius = v[7]; l.cos_outer = -1.0f; l.cos_inner = 1.0f;
+  for (int k = 0; k < 3; ++k) if (!std::isfinite(l.position[k])) throw std::runtime_error(what + ": a finite position");
+  for (int k = 0; k < 3; ++k) if (!std::isfinite(l.intensity[k]) || l.intensity[k] < 0.0f) throw std::runtime_error(what + ": an intensity that is finite and not negative");
+  if (!std::isfinite(l.range) || !(l.range > 0.0f)) throw std::runtime_error(what + ": a range that is finite and above 0");
+  if (!std::isfinite(l.radius) || l.radius < 0.0f || !(l.radius < l.range)) throw std::runtime_error(what + ": a radius that is finite, not negative and below the range");
+  if (spot) {
+    for (int k = 0; k < 3; ++k) l.axis[k] = v[8 + k];
+    const double len = std::sqrt((double)v[8] * v[8] + (double)v[9] * v[9] + (double)v[10] * v[10]);
+    if (!std::isfinite(len) || !(len > 0.0)) throw std::runtime_error(whatSpot + ": an axis of finite, non-zero length");
+    if (!(v[12] > 0.0f && v[12] < v[11] && v[11] < 180.0f)) throw std::runtime_error(whatSpot + ": half-angles in degrees with 0 < inner < outer < 180");
+    l.cos_outer = (float)std::cos((double)v[11] * 3.14159265358979323846 / 180.0); l.cos_inner = (float)std::cos((double)v[12] * 3.14159265358979323846 / 180.0);
+    if (!(l.cos_outer > -1.0f && l.cos_outer < l.cos_inner && l.cos_inner <= 1.0f)) throw std::runtime_error(whatSpot + ": half-angles in degrees with 0 < inner < outer < 180, apart by more than fp32 tells");
+  }
+  return l;
+}
+
 void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
   const auto lower = [](std::string s) { std::transform(s.begin(), s.end(), s.begin(), [](unsigned char ch) { return (char)std::tolower(ch); }); return s; };
   const auto isArgMatched = [&](int i, const char* name) {
@@ -214,7 +237,7 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
     return (arg[0] == '-' || arg[0] == '/') && lower(arg + 1) == lower(name);
   };
   // On POSIX an absolute path also starts with '/': such a token is a flag only when it names one.
-  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "sun", "sunreflections", "sunfromenv", "sunangle", "light", "spot", "lightreflections", "lightpick", "lightvisibility", "recursion", "spp", "accumulate", "sampleset", "savereference", "reference", "score", "envlayout", "envsize", "envmips", "envprefilter"};
+  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "sun", "sunreflections", "sunfromenv", "sunangle", "light", "spot", "lightreflections", "lightpick", "lightvisibility", "lightlist", "recursion", "spp", "accumulate", "sampleset", "savereference", "reference", "score", "envlayout", "envsize", "envmips", "envprefilter"};
   const auto isFlagName = [&](const char* name) { for (const char* f : kFlags) if (lower(name) == f) return true; return false; };
   const auto hasNextArgValue = [&](int i) {
     if (i + 1 >= argc) return false;
@@ -301,22 +324,38 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
       for (; got < (spot ? 13 : 8) && hasNextArgValue(i); ++got) { char* end = nullptr; v[got] = std::strtof(argv[++i], &end); if (end == argv[i] || *end != '\0') throw std::runtime_error(usage); }
       if (spot ? got != 13 : got < 7) throw std::runtime_error(usage);
       if (m_lights.size() >= RTGGX_MAX_LIGHTS) throw std::runtime_error(what + ": at most 8 lights (-light and -spot together)");
-      RtggxLight l{};
-      for (int k = 0; k < 3; ++k) { l.position[k] = v[k]; l.intensity[k] = v[3 + k]; }
-      l.range = v[6]; l.radius = v[7]; l.cos_outer = -1.0f; l.cos_inner = 1.0f;
-      for (int k = 0; k < 3; ++k) if (!std::isfinite(l.position[k])) throw std::runtime_error(what + ": a finite position");
-      for (int k = 0; k < 3; ++k) if (!std::isfinite(l.intensity[k]) || l.intensity[k] < 0.0f) throw std::runtime_error(what + ": an intensity that is finite and not negative");
-      if (!std::isfinite(l.range) || !(l.range > 0.0f)) throw std::runtime_error(what + ": a range that is finite and above 0");
-      if (!std::isfinite(l.radius) || l.radius < 0.0f || !(l.radius < l.range)) throw std::runtime_error(what + ": a radius that is finite, not negative and below the range");
-      if (spot) {
-        for (int k = 0; k < 3; ++k) l.axis[k] = v[8 + k];
-        const double len = std::sqrt((double)v[8] * v[8] + (double)v[9] * v[9] + (double)v[10] * v[10]);
-        if (!std::isfinite(len) || !(len > 0.0)) throw std::runtime_error("-spot: an axis of finite, non-zero length");
-        if (!(v[12] > 0.0f && v[12] < v[11] && v[11] < 180.0f)) throw std::runtime_error("-spot: half-angles in degrees with 0 < inner < outer < 180");
-        l.cos_outer = (float)std::cos((double)v[11] * 3.14159265358979323846 / 180.0); l.cos_inner = (float)std::cos((double)v[12] * 3.14159265358979323846 / 180.0);
-        if (!(l.cos_outer > -1.0f && l.cos_outer < l.cos_inner && l.cos_inner <= 1.0f)) throw std::runtime_error("-spot: half-angles in degrees with 0 < inner < outer < 180, apart by more than fp32 tells");
+      m_lights.push_back(lightFromNumbers(what, spot ? "-spot" : what, spot, v));
+    }
+    // -lightlist <file>: a light list beyond eight (rtggx_set_light_list).  Plain text, a light per line, blank lines and # comments allowed:
+    //   light x y z r g b range [radius]
+    //   spot x y z r g b range radius ax ay az outer inner      (the angles in degrees, as for -spot)
+    // read and checked here, with the line number in the message, before a device is asked for
+    else if (isArgMatched(i, "lightlist")) {
+      if (!hasNextArgValue(i)) throw std::runtime_error("-lightlist: a file name");
+      m_lightListFile = argv[++i];
+      FILE* f = std::fopen(m_lightListFile.c_str(), "r");
+      if (!f) throw std::runtime_error("-lightlist: cannot open " + m_lightListFile);
+      std::vector<std::string> lines;
+      { std::string line; int ch; while ((ch = std::fgetc(f)) != EOF) { if (ch == '\n') { lines.push_back(line); line.clear(); } else line.push_back((char)ch); } if (!line.empty()) lines.push_back(line); }
+      std::fclose(f);
+      m_lightList.clear();
+      for (size_t n = 0; n < lines.size(); ++n) {
+        std::string text = lines[n].substr(0, lines[n].find('#'));
+        std::vector<std::string> words;
+        { size_t at = 0; while (at < text.size()) { while (at < text.size() && std::isspace((unsigned char)text[at])) ++at; size_t end = at; while (end < text.size() && !std::isspace((unsigned char)text[end])) ++end; if (end > at) words.push_back(text.substr(at, end - at)); at = end; } }
+        if (words.empty()) continue;
+        const std::string where = "-lightlist: " + m_lightListFile + ", line " + std::to_string(n + 1);
+        const bool spot = words[0] == "spot";
+        if (!spot && words[0] != "light") throw std::runtime_error(where + ": '" + words[0] + "': a line begins with light or spot");
+        const std::string usage = where + (spot ? ": spot and thirteen numbers -- position, intensity, range, radius, axis, outer and inner half-angle in degrees"
+                                                : ": light and seven or eight numbers -- position, intensity, range and, optionally, radius");
+        float v[13] = {};
+        const size_t got = words.size() - 1;
+        if (spot ? got != 13 : (got != 7 && got != 8)) throw std::runtime_error(usage);
+        for (size_t k = 0; k < got; ++k) { char* end = nullptr; v[k] = std::strtof(words[k + 1].c_str(), &end); if (end == words[k + 1].c_str() || *end != '\0') throw std::runtime_error(usage); }
+        if (m_lightList.size() >= RTGGX_MAX_LIGHT_LIST) throw std::runtime_error(where + ": at most 1024 lights");
+        m_lightList.push_back(lightFromNumbers(where, where, spot, v));
       }
-      m_lights.push_back(l);
     }
     else if (isArgMatched(i, "rayrate")) {
       const int rate = hasNextArgValue(i) ? std::atoi(argv[++i]) : 0;
@@ -380,13 +419,16 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
   // one knob asks for fewer rays, the other for more (rtggx_set_samples_per_pixel)
   if (m_rayRate != 1u && m_hasSun) throw std::runtime_error("-sun together with -rayrate 4: refused");
   // the lights in reflections (rtggx_set_light_reflections) act only under lights: the rule of -sunreflections without -sun
-  if (m_lightReflections && m_lights.empty()) throw std::runtime_error("-lightreflections without -light or -spot: there is no light to reflect");
+  if (m_lightReflections && m_lights.empty() && m_lightList.empty()) throw std::runtime_error("-lightreflections without -light or -spot: there is no light to reflect");
   // one ray for all lights (rtggx_set_light_sampling) acts only under lights: the same rule
   if (m_lightPick && m_lights.empty()) throw std::runtime_error("-lightpick without -light or -spot: there is no light to pick");
   // the pick's visibility records (rtggx_set_light_pick_visibility) act only in mode 1, and on whole frames
   if (m_lightVisibility && !m_lightPick) throw std::runtime_error("-lightvisibility without -lightpick: there is no pick to weight");
   if (m_lightVisibility && (m_gpus > 1 || m_strips > 1)) throw std::runtime_error("-lightvisibility: whole frames only, not with -gpus N > 1 or -strips N > 1");
   if (m_rayRate != 1u && !m_lights.empty()) throw std::runtime_error("-light / -spot together with -rayrate 4: refused");
+  // a light list (rtggx_set_light_list) is held in place of the lights, not beside them, and excludes rate 4 as they do
+  if (!m_lightListFile.empty() && !m_lights.empty()) throw std::runtime_error("-lightlist together with -light / -spot: the context holds one or the other");
+  if (!m_lightListFile.empty() && m_rayRate != 1u) throw std::runtime_error("-lightlist together with -rayrate 4: refused");
   if (m_rayRate != 1u && m_samplesPerPixel != 1u) throw std::runtime_error("-spp N > 1 together with -rayrate 4: refused");
   if (m_rayRate != 1u && (m_gpus > 1 || m_strips > 1)) throw std::runtime_error("-rayrate 4: whole frames only, not with -gpus N > 1 or -strips N > 1");
 }

@@ -2,7 +2,7 @@
 // DXFramework virtuals RayTracedGGX/Common/DXFramework.h:23-26): OnInit / OnUpdate / OnRender /
 // OnDestroy, the same command line (RayTracedGGX.cpp:462-511) and the same defaults
 // (RayTracedGGX.cpp:37-39, camera :19-23, 267-277).  What the window supplied interactively is
-// supplied by extra flags: -width -height -frames -dt -metallic -sharedmem -sync -vndf -rayrate -sun -sunreflections -sunfromenv -sunangle -light -spot -lightreflections -lightpick -lightvisibility -recursion -spp -sampleset -accumulate -savereference -reference -score -envlayout -envsize -envmips -envprefilter -device -dump -track -deform -gpus -strips -balance.
+// supplied by extra flags: -width -height -frames -dt -metallic -sharedmem -sync -vndf -rayrate -sun -sunreflections -sunfromenv -sunangle -light -spot -lightreflections -lightpick -lightvisibility -lightlist -recursion -spp -sampleset -accumulate -savereference -reference -score -envlayout -envsize -envmips -envprefilter -device -dump -track -deform -gpus -strips -balance.
 #pragma once
 #include <vector>
 #include <cstdint>
@@ -151,6 +151,10 @@ class RayTracedGGX {
   bool m_lightReflections = false;    // -lightreflections: the lights at the surfaces seen in reflections as well (RayTracer::SetLightReflections); needs -light or -spot
   bool m_lightPick = false;           // -lightpick: one shadow ray per surface point for all lights (RayTracer::SetLightSampling(1)); needs -light or -spot
   bool m_lightVisibility = false;     // -lightvisibility: the pick weighted by the visibility each pixel remembers (RayTracer::SetLightPickVisibility); needs -lightpick; whole frames only
+  // -lightlist <file>: a light list beyond eight -- up to RTGGX_MAX_LIGHT_LIST lines "light x y z r g b range [radius]" or "spot x y z r g b
+  // range radius ax ay az outer inner" (RayTracer::SetLightList); not together with -light / -spot or -rayrate 4; -lightreflections is
+  // accepted with it
+  std::string m_lightListFile; std::vector<RtggxLight> m_lightList;
   uint32_t m_rayRate = 1;              // -rayrate <1|4>: pixels per traced ray (RayTracer::SetRayRate); 4 renders whole frames only: not with -gpus / -strips
   // -deform <amplitude>: the model breathes -- a travelling sine wave through its vertices, DeformPeriod key shapes computed once
   // at start-up and handed to RayTracer::UpdateMesh one per frame (per-frame host cost: one copy of the vertex array)

@@ -119,6 +119,7 @@ bool RayTracer::SetSun(const float dir[3], const float e[3]) { return check(rtgg
 bool RayTracer::SetSunAngle(float degrees) { return check(rtggx_set_sun_angle(m_ctx, degrees), "rtggx_set_sun_angle"); }
 bool RayTracer::SetLights(const RtggxLight* lights, uint32_t count) { return check(rtggx_set_lights(m_ctx, lights, count), "rtggx_set_lights"); }
 bool RayTracer::SetLightReflections(bool enable) { return check(rtggx_set_light_reflections(m_ctx, enable ? 1 : 0), "rtggx_set_light_reflections"); }
+bool RayTracer::SetLightList(const RtggxLight* lights, uint32_t count) { return check(rtggx_set_light_list(m_ctx, lights, count), "rtggx_set_light_list"); }
 bool RayTracer::SetLightSampling(int mode) { return check(rtggx_set_light_sampling(m_ctx, mode), "rtggx_set_light_sampling"); }
 bool RayTracer::SetLightPickVisibility(bool enable) { return check(rtggx_set_light_pick_visibility(m_ctx, enable ? 1 : 0), "rtggx_set_light_pick_visibility"); }
 bool RayTracer::SetSunReflections(bool enable) { return check(rtggx_set_sun_reflections(m_ctx, enable ? 1 : 0), "rtggx_set_sun_reflections"); }

@@ -171,6 +171,14 @@ extern "C" int rtggx_app_set_lights(void* h, const RtggxLight* lights, uint32_t 
   return -1;
 }
 
+// RayTracer::SetLightList of the application's ray tracer (lights = NULL, 0 clears the list)
+extern "C" int rtggx_app_set_light_list(void* h, const RtggxLight* lights, uint32_t count) {
+  RayTracer* rt = ((RayTracedGGX*)h)->GetRayTracer();
+  if (rt->SetLightList(lights, count)) return 0;
+  g_appError = rt->GetLastError();
+  return -1;
+}
+
 // RayTracer::SetLightReflections of the application's ray tracer
 extern "C" int rtggx_app_set_light_reflections(void* h, int enable) {
   RayTracer* rt = ((RayTracedGGX*)h)->GetRayTracer();
