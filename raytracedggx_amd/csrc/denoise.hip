@@ -14,9 +14,13 @@
 //   direct access (0): every tap fetches and unpacks its texel from global memory (L1/L2 hits).
 // Both evaluate the same weights, to the bit (tests/test_gpu_denoise_synthetic.py compares their words): pow(x, 512) / pow(x, 32) as
 // exp2(n log2 x) on an exact dot product (log2OfDot below), with the Gaussian and the depth exponential folded into the same
-// v_exp_f32 -- ~35 VALU instructions per tap instead of ~400 with libm calls.  The passes
-// are VALU-bound (33 taps per covered pixel); their HBM traffic (22-30 B/pixel/pass) is ~5% of the
-// time.  Out-of-range texels are the zeros D3D returns.
+// v_exp_f32 -- ~35 VALU instructions per tap instead of ~400 with libm calls.  The passes are
+// NOT VALU-bound, whatever earlier rounds wrote here (profiles/r04_q_pmc_report.txt): the H pass issues 11.2 M wave-level VALU instructions,
+// 7-9 us of issue over 1024 SIMDs against 22 us alone on the chip, and waits for an instruction's operands (SQ_WAIT_INST_ANY) in 19 M of its
+// 64 M wave quad-cycles; their HBM traffic (22-30 B/pixel/pass) is ~5% of the time.  A wave over drawn tiles lives as long as
+// its memory round trips take (500-900 cycles each under load) plus ~1 200 VALU instructions of taps, so the tiled kernels and the temporal
+// pass make ONE round trip of their head: every load of a thread's texels is issued before any is used (spatialTiledKernel,
+// stageTemporalTiles; profiles/r23_a_denoise_staging_isa.txt).  Out-of-range texels are the zeros D3D returns.
 #include <cstring>
 #include <type_traits>
 #include "rtggx_context.h"
@@ -40,20 +44,23 @@ RT_DEV float rcpFast(float x) { return __builtin_amdgcn_rcpf(x); }
 // filters' dot products are then exact in fp32 (tapWeight)
 struct GTexel { float nx, ny, nz, nw, rough, metal, depth; };
 
-RT_DEV GTexel loadG(const uint32_t* __restrict__ normal, const uint16_t* __restrict__ roughMetal, const uint32_t* __restrict__ depth32,
-                    int x, int y, int W, int H) {
+// The texel of the three G-buffer words.  Words of zero give what a texel outside the frame reads: normal -1023 (the reference's -1), flag,
+// roughness, metallic and depth 0 -- by the same operations, so a caller may replace the words instead of the seven results.
+RT_DEV GTexel unpackG(uint32_t n, uint32_t rm, uint32_t d) {
   GTexel g;
-  if (x < 0 || y < 0 || x >= W || y >= H) { g.nx = g.ny = g.nz = -1023.0f; g.nw = 0.0f; g.rough = 0.0f; g.metal = 0.0f; g.depth = 0.0f; return g; }      // (zeros: the normal reads -1)
-  const size_t i = (size_t)y * W + x;
-  const uint32_t n = normal[i];
   g.nx = (float)(2 * (int)(n & 1023u) - 1023);
   g.ny = (float)(2 * (int)((n >> 10) & 1023u) - 1023);
   g.nz = (float)(2 * (int)((n >> 20) & 1023u) - 1023);
   g.nw = (float)(n >> 30) * (1.0f / 3.0f);
-  const uint32_t rm = roughMetal[i];
   g.rough = (float)(rm & 0xFFu) * (1.0f / 255.0f); g.metal = (rm >> 8) == 255u ? 1.0f : (float)(rm >> 8) * (1.0f / 255.0f);
-  g.depth = (float)depth32[i] * (1.0f / 16777215.0f);
+  g.depth = (float)d * (1.0f / 16777215.0f);
   return g;
+}
+RT_DEV GTexel loadG(const uint32_t* __restrict__ normal, const uint16_t* __restrict__ roughMetal, const uint32_t* __restrict__ depth32,
+                    int x, int y, int W, int H) {
+  if (x < 0 || y < 0 || x >= W || y >= H) { GTexel g; g.nx = g.ny = g.nz = -1023.0f; g.nw = 0.0f; g.rough = 0.0f; g.metal = 0.0f; g.depth = 0.0f; return g; }      // (zeros: the normal reads -1)
+  const size_t i = (size_t)y * W + x;
+  return unpackG(normal[i], roughMetal[i], depth32[i]);
 }
 RT_DEV f3 TM3(f3 c) { const float r = rcpFast(1.0f + ((c.x * 0.25f + c.y * 0.5f) + c.z * 0.25f)); return mk3(c.x * r, c.y * r, c.z * r); }     // FilterCommon.hlsli:14-19
 RT_DEV f3 ITM3(f3 c) { const float r = rcpFast(1.0f - ((c.x * 0.25f + c.y * 0.5f) + c.z * 0.25f)); return mk3(c.x * r, c.y * r, c.z * r); }    // :24-27
@@ -207,12 +214,20 @@ template <int MODE>
 RT_DEV void storeSkipped(const Targets& T, size_t pix) {
   if (MODE == 1) { const f3 s = unpackR11G11B10F(T.rtRefl[pix]); const uint2 v = packRGBA16F(s.x, s.y, s.z, 0.0f); if (T.fltRfl) T.fltRfl[pix] = v; T.fltDff[pix] = v; }
 }
-// Source colour of a tap: the ray-traced result tone-mapped (H passes) or the H pass's scratch (V passes).
+// Source colour of a tap: the ray-traced result tone-mapped (H passes) or the H pass's scratch (V passes).  In two steps for the tiled
+// kernels, which issue the loads of all their texels before they use one: the word(s) as loaded (.y unused by the H passes), then the colour.
 template <int MODE>
-RT_DEV f3 tapColour(const Targets& T, size_t ti) {
-  if (MODE & 1) { const f4 v = unpackRGBA16F(T.scratch[ti]); return mk3(v.x, v.y, v.z); }
-  return TM3(unpackR11G11B10F(MODE >= 2 ? T.rtDiff[ti] : T.rtRefl[ti]));
+RT_DEV uint2 tapColourWords(const Targets& T, size_t ti) {
+  if (MODE & 1) return T.scratch[ti];
+  return make_uint2(MODE >= 2 ? T.rtDiff[ti] : T.rtRefl[ti], 0u);
 }
+template <int MODE>
+RT_DEV f3 tapColourOf(uint2 w) {
+  if (MODE & 1) { const f4 v = unpackRGBA16F(w); return mk3(v.x, v.y, v.z); }
+  return TM3(unpackR11G11B10F(w.x));
+}
+template <int MODE>
+RT_DEV f3 tapColour(const Targets& T, size_t ti) { return tapColourOf<MODE>(tapColourWords<MODE>(T, ti)); }
 
 // mode 0: H_Refl  1: V_Refl  2: H_Diff  3: V_Diff -- direct-access variant
 template <int MODE>
@@ -281,6 +296,32 @@ __global__ void __launch_bounds__(256) spatialTiledKernel(Targets T) {
     }
     return;
   }
+  // Every global load of the workgroup's head is issued here, back to back, before the result of any is used: the own pixels' words (the
+  // decision below needs only these, the OLDEST loads -- the counters return in order, so it waits with vmcnt(k), not for the tile), then
+  // the G-buffer words and the colour of each of the thread's NT texels.  No load depends on another (the addresses come from threadIdx,
+  // blockIdx and the arguments), so none is behind a branch: an address is clamped into the frame and into t < N, and what a texel outside
+  // them stages is selected afterwards.  ONE memory round trip where the rolled loop with its branches made five (H) and seven (V).
+  constexpr int NT = (N + 255) / 256;      // texels per thread: 2 (H; the second for half the threads), 3 (V)
+  uint32_t ownN[PER], ownRM[PER];
+#pragma unroll
+  for (int k = 0; k < PER; ++k) {
+    const size_t pix = (size_t)min(by0 + ly + k * ROWSTEP, T.rowEnd - 1) * T.W + min(x, T.W - 1);
+    ownN[k] = T.normal[pix]; ownRM[k] = diffuse ? T.roughMetal[pix] : 0u;
+  }
+  const int ox = vertical ? bx0 : bx0 - RT_RADIUS, oy = vertical ? by0 - RT_RADIUS : by0;
+  uint32_t tn[NT], trm[NT], td[NT]; uint2 tc[NT]; bool inside[NT];
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    const int t = min((int)threadIdx.x + 256 * j, N - 1);
+    const int tx = ox + t % TW, ty = oy + t / TW;
+#ifdef RT_STAGING_MUTANT_KEEP_CLAMPED      // a deliberate fault (profiles/r23_denoise_staging_mutation.txt): the new tests must fail with it
+    inside[j] = true;
+#else
+    inside[j] = tx >= 0 && ty >= 0 && tx < T.W && ty < T.H;
+#endif
+    const size_t ti = (size_t)min(max(ty, 0), T.H - 1) * T.W + min(max(tx, 0), T.W - 1);
+    tn[j] = T.normal[ti]; trm[j] = T.roughMetal[ti]; td[j] = T.depth32[ti]; tc[j] = tapColourWords<MODE>(T, ti);
+  }
   // which of my pixels are filtered at all; the others get their pass-through value now
   bool todo[PER]; bool any = false;
 #pragma unroll
@@ -289,31 +330,31 @@ __global__ void __launch_bounds__(256) spatialTiledKernel(Targets T) {
     todo[k] = false;
     if (x < T.W && y < T.rowEnd) {
       const size_t pix = (size_t)y * T.W + x;
-      const bool skip = (T.normal[pix] >> 30) == 0u || (diffuse && (T.roughMetal[pix] >> 8) == 255u);
+      const bool skip = (ownN[k] >> 30) == 0u || (diffuse && (ownRM[k] >> 8) == 255u);
       if (skip) storeSkipped<MODE>(T, pix); else { todo[k] = true; any = true; }
     }
   }
-  if (!__syncthreads_or(any ? 1 : 0)) return;
+  if (!__syncthreads_or(any ? 1 : 0)) return;      // (nothing has been written to LDS)
 
-  // stage the tile
-  const int ox = vertical ? bx0 : bx0 - RT_RADIUS, oy = vertical ? by0 - RT_RADIUS : by0;
+  // stage the tile: a texel outside the frame is the zeros D3D returns (unpackG of zero words), never the texel its address was clamped to
   uint32_t myLo = 0xFFFFFFFFu, myHi = 0u, myUnflagged = 0u;
-  for (int t = threadIdx.x; t < N; t += 256) {
-    const int tx = ox + t % TW, ty = oy + t / TW;
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    const int t = (int)threadIdx.x + 256 * j;
+    if (NT * 256 != N && t >= N) continue;
     float v[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    const bool inside = tx >= 0 && ty >= 0 && tx < T.W && ty < T.H;
-    const GTexel g = loadG(T.normal, T.roughMetal, T.depth32, tx, ty, T.W, T.H);       // zeros outside
+    const GTexel g = unpackG(inside[j] ? tn[j] : 0u, inside[j] ? trm[j] : 0u, inside[j] ? td[j] : 0u);
     v[3] = g.depth; v[4] = g.rough;
     if (diffuse) {
       if (g.nw > 0.0f && g.metal < 1.0f) {
-        const f3 src = tapColour<MODE>(T, (size_t)ty * T.W + tx);
+        const f3 src = tapColourOf<MODE>(tc[j]);
         v[0] = g.nx; v[1] = g.ny; v[2] = g.nz; v[5] = src.x; v[6] = src.y; v[7] = src.z;
       }
     } else {
       v[0] = g.nx; v[1] = g.ny; v[2] = g.nz;
       if (g.nw <= 0.0f) { v[4] = __uint_as_float(__float_as_uint(g.rough) | 0x80000000u); myUnflagged = 1u; }
       else { myLo = min(myLo, __float_as_uint(g.rough)); myHi = max(myHi, __float_as_uint(g.rough)); }
-      if (inside) { const f3 src = tapColour<MODE>(T, (size_t)ty * T.W + tx); v[5] = src.x; v[6] = src.y; v[7] = src.z; }
+      if (inside[j]) { const f3 src = tapColourOf<MODE>(tc[j]); v[5] = src.x; v[6] = src.y; v[7] = src.z; }
     }
     smA[t] = V4{v[0], v[1], v[2], v[3]}; smB[t] = V4{v[4], v[5], v[6], v[7]};
   }
@@ -553,16 +594,32 @@ RT_DEV uint2 temporalPixel(const Targets& T, const float4 (&tile)[ROWS][PITCH], 
   }
   return packRGBA16F(result.x, result.y, result.z, hw);   // :335 (TSS[parity])
 }
-// Stages the tiles of a (ROWS - 2) x (PITCH - 2) pixel block whose first pixel is (ox + 1, oy + 1).
+// Stages the tiles of a (ROWS - 2) x (PITCH - 2) pixel block whose first pixel is (ox + 1, oy + 1).  As in the tiled spatial kernels, both
+// loads of every texel of the thread are issued before one is used, at addresses clamped into the frame and into t < ROWS * PITCH: one
+// memory round trip in front of the barrier instead of one per load and trip.  A texel outside the frame is staged as zeros.
 template <int ROWS, int PITCH, int THREADS>
 RT_DEV void stageTemporalTiles(const Targets& T, float4 (&tile)[ROWS][PITCH], uint32_t (&velRaw)[ROWS][PITCH], float (&velSq)[ROWS][PITCH], int ox, int oy) {
   const int W = T.W, H = T.H;
-  for (int t = threadIdx.x; t < ROWS * PITCH; t += THREADS) {
+  constexpr int N = ROWS * PITCH, NT = (N + THREADS - 1) / THREADS;
+  uint2 colour[NT]; uint32_t vel[NT]; bool inside[NT];
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    const int t = min((int)threadIdx.x + THREADS * j, N - 1);
     const int tx = ox + t % PITCH, ty = oy + t / PITCH;
-    const bool inside = tx >= 0 && ty >= 0 && tx < W && ty < H;
-    const size_t ti = inside ? (size_t)ty * W + tx : 0;
-    const f4 raw = inside ? unpackRGBA16F(T.fltDff[ti]) : f4{0.0f, 0.0f, 0.0f, 0.0f};
-    const uint32_t vr = inside ? T.velocity[ti] : 0u;
+#ifdef RT_STAGING_MUTANT_KEEP_CLAMPED
+    inside[j] = true;
+#else
+    inside[j] = tx >= 0 && ty >= 0 && tx < W && ty < H;
+#endif
+    const size_t ti = (size_t)min(max(ty, 0), H - 1) * W + min(max(tx, 0), W - 1);
+    colour[j] = T.fltDff[ti]; vel[j] = T.velocity[ti];
+  }
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    const int t = (int)threadIdx.x + THREADS * j;
+    if (NT * THREADS != N && t >= N) continue;
+    const f4 raw = inside[j] ? unpackRGBA16F(colour[j]) : f4{0.0f, 0.0f, 0.0f, 0.0f};
+    const uint32_t vr = inside[j] ? vel[j] : 0u;
     const f3 tm = tssTM(mk3(raw.x, raw.y, raw.z));
     tile[t / PITCH][t % PITCH] = make_float4(tm.x, tm.y, tm.z, raw.w);
     const float vx = f16ToF32(vr & 0xFFFFu), vy = f16ToF32(vr >> 16);
