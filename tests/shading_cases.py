@@ -18,7 +18,9 @@ Families (the smallest set that reaches each branch):
                zero channel, a zero green, all zero and above 1, cubes of 1, 3 and 5 mips
   hits         open sky; a cone whose apex lies on a pixel centre (a ray leaves a vertex shared by 16 triangles); two coincident sheets
   vndf         normals and materials once more under rtggx_set_sampler
-  sun, lights  a slab under an occluder, lit by rtggx_set_sun (angle 0) and by rtggx_set_lights (radius 0); see all_cases"""
+  sun, lights  a slab under an occluder, lit by rtggx_set_sun (angle 0) and by rtggx_set_lights (radius 0); see all_cases
+The sampled lights (the sun's disk, radii, the pick, the records, the list, their targets at the hits) have lists of their own:
+sampled_cases, record_cases, sampled_hit_cases."""
 import functools
 
 import numpy as np
@@ -237,8 +239,8 @@ class Case:
     def worlds(self, k):
         return self.world0, self.world1 @ translate(*(k * self.world1_step))
 
-    def constants(self, k):
-        """The 768 bytes of frame position k (frame index FRAMES[k]); the previous matrices are those of position k - 1."""
+    def constants(self, k, frame_index=None):
+        """The 768 bytes of frame position k (frame index FRAMES[k], or frame_index); the previous matrices are those of position k - 1."""
         f = np.zeros(192, np.float32)
         vp, vp_prev = self.view_proj(k), self.view_proj(k - 1)
         for i, (w, wp) in enumerate(zip(self.worlds(k), self.worlds(k - 1))):
@@ -248,7 +250,7 @@ class Case:
             f[88 + 12 * i:88 + 12 * i + (12 if i == 0 else 11)] = it.reshape(-1)[:12 if i == 0 else 11]
             f[136 + 20 * i:152 + 20 * i] = (w @ vp).T.reshape(-1)
             f[152 + 20 * i:154 + 20 * i] = self.proj_bias
-        f[111:112] = np.array([FRAMES[k]], np.uint32).view(np.float32)
+        f[111:112] = np.array([FRAMES[k] if frame_index is None else frame_index], np.uint32).view(np.float32)
         f[112:128] = np.linalg.inv(vp).T.reshape(-1)
         f[128:131] = self.eye + k * self.eye_step
         f[132:134] = self.proj_bias
@@ -482,6 +484,172 @@ HIT_NAMES = tuple(r.name for r in hit_cases())
 
 def hit_by_name(name):
     return next(r for r in hit_cases() if r.name == name)
+
+
+# ---- the sampled lights (tests/test_shading_sampled_host.py, tests/test_gpu_shading_sampled.py) ---------------------------------------------
+class SampledRun:
+    """A case whose one direct pass samples visibility, at the three frame positions.  kind "sun": the case's suns under
+    rtggx_set_sun_angle, every frame position once per angle of `angles`; "lights": lights(k) with radii, every light its own ray; "pick":
+    lights(k) under rtggx_set_light_sampling(ctx, 1); "list": lights(k) through rtggx_set_light_list."""
+
+    def __init__(self, name, case, kind, angles=None, lights=None):
+        self.name, self.case, self.kind, self.angles, self.lights, self.positions = name, case, kind, angles, lights, (0, 1, 2)
+        self.family = {"sun": "sun_disk", "lights": "radii", "pick": "pick", "list": "list"}[kind]
+
+    def passes(self, k):
+        """The passes of frame position k, each on the frame as it stands in front of it: [(label, angle or None)]."""
+        return [("sun at %g degrees" % a, a) for a in self.angles] if self.kind == "sun" else [(self.kind, None)]
+
+
+def slats(n, x0, width, gap, z0, z1, y):
+    """n strips along z, `width` wide and `gap` apart from x0 on: 2 n edges over the slab."""
+    return join(*(grid(1, 1, x0 + i * (width + gap), x0 + i * (width + gap) + width, z0, z1, y=y) for i in range(n)))
+
+
+@functools.lru_cache(maxsize=None)
+def slat_cases():
+    """sun_75x53's and lights_75x53's scene with the occluder's one square replaced by eight slats 0.2 wide and 0.2 apart, 1 above the slab: 16
+    long edges.  A single square's penumbra is a few pixels at this size -- a 10 degree disk meets about twenty pixels whose sampled ray
+    differs from the centre ray --; under the slats every gap is penumbra.  The slab, the cap, the camera, the materials, the suns and the
+    lights are the two cases' own, so the terms are theirs and the floor their ray-traced path records is these passes' delta."""
+    sun, lights = by_name("sun_75x53"), by_name("lights_75x53")
+    slab = grid(2, 2, -2.0, 2.0, -2.0, 2.0)
+    over = join(slats(8, -2.4, 0.2, 0.2, -2.0, 1.5, 0.0), sphere_cap(3, 8, 0.5, 1.3, centre=(1.2, -0.9, 0.6)))
+    make = lambda name, fam, base: Case(name, fam, 75, 53, slab, over, base.world0, base.world1, base.eye, base.focus, smooth_cube(), base.materials,
+                                        sun=base.sun, lights=base.lights)
+    return make("slats_sun_75x53", "sun", sun), make("slats_lights_75x53", "lights", lights)
+
+
+@functools.lru_cache(maxsize=None)
+def many_lights(n, seed=7):
+    """n small lights 0.2 to 0.9 above the slab (under the slats), ranges 0.7 to 1.5 -- a block of 8 x 8 pixels is reached by a few of them --;
+    every seventh dark (it keeps its index), every third with a radius of 0.2 to 0.6 (8 and 11 among them, the first slots beyond 4096; many spheres dip into the slab: targets below the horizon), every eleventh a spot that points down."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for i in range(n):
+        x, y, z, r, a, b, c, rho = [float(np.round(v, 3)) for v in rng.uniform((-2.8, -0.8, -2.8, 0.7, 0.2, 0.2, 0.2, 0.2), (2.8, -0.1, 2.8, 1.5, 2.0, 2.0, 2.0, 0.6))]
+        lt = dict(position=(x, y, z), range=r, intensity=(0.0, 0.0, 0.0) if i % 7 == 3 else (a, b, c))
+        if i % 3 == 2:
+            lt["radius"] = rho
+        if i % 11 == 6:
+            lt.update(axis=(0.1, -1.0, 0.05), cos_outer=float(np.cos(np.radians(50.0))), cos_inner=float(np.cos(np.radians(20.0))))
+        out.append(lt)
+    return tuple(out)
+
+
+@functools.lru_cache(maxsize=None)
+def sampled_cases():
+    """The slab under the slats (slat_cases: 75 x 53, ragged 8 x 8 blocks at the right and bottom edges), frames FRAMES.
+      sun disk   the three suns of sun_75x53 -- zenith, NoL 0.01 above the slab's horizon (the below-horizon targets), slanted -- each at
+                 0.27, 5 and 10 degrees
+      radii      the three lists of lights_75x53 with radii: small (A, 0.05), near the light's height above the slab (B: 0.25 above it,
+                 radius 0.3: the sphere dips into the slab, targets below the horizon), the spot with a radius, the lights above and under
+                 the slats with wide ones (their penumbrae), the dark light still in the middle of its list (the slots keep their index)
+      list       12, 65 and 200 small lights (many_lights) through rtggx_set_light_list: mode 1's rule with the list's slots, and the cull
+      pick       two lights and eight, with the radii above and without any, over the slab (metallic 0.25: w_i = Y(spec_i) + Y(diff_i))
+                 and the slats (metallic 1: Y(spec_i) alone).  The light 0.005 above the slab is lifted to 0.2 and made brighter: where
+                 it stands in lights_75x53 it would be chosen at no pixel"""
+    sun, lights = slat_cases()
+    runs = [SampledRun("sun_disk_75x53", sun, "sun", angles=(0.27, 5.0, 10.0))]
+    radius = {(0.5, -0.6, 0.3): 0.05, (-1.0, -0.75, -0.5): 0.3, (0.3, 1.5, -0.2): 0.2, (-0.4, 0.5, -0.1): 0.4, (-0.4, -0.6, -0.1): 0.2, (2.0, 0.5, 2.0): 0.5}
+
+    def soft(k):
+        return [dict(l, radius=radius.get(tuple(l["position"]), 0.0)) for l in lights.lights(k)]
+
+    def lifted(of, a_radius=None):
+        """The lists for the pick: the light 0.005 above the slab lifted and brighter, the one under the slats brighter (each is chosen 20
+        times or more); a_radius: A's radius -- above its height of 0.4, so that the light the pick takes half of the time at position 0
+        has targets below the horizon."""
+        change = {(0.7, -0.995, -0.8): dict(position=(0.7, -0.8, -0.8), intensity=(0.5, 0.5, 0.25), range=1.5), (-0.4, -0.6, -0.1): dict(intensity=(2.0, 1.0, 0.5))}
+        if a_radius is not None:
+            change[(0.5, -0.6, 0.3)] = dict(radius=a_radius)
+        return lambda k: [dict(l, **change.get(tuple(l["position"]), {})) for l in of(k)]
+    runs.append(SampledRun("radii_75x53", lights, "lights", lights=soft))
+    # the pick: position 0 two lights, position 1 eight (one dark), position 2 the three around the slats (one dark)
+    runs.append(SampledRun("pick_75x53", lights, "pick", lights=lifted(lights.lights)))
+    runs.append(SampledRun("pick_radii_75x53", lights, "pick", lights=lifted(soft, a_radius=0.6)))
+    # the list: 12 lights cross the slot change at 8, 65 and 200 a 64-light chunk
+    for n in (12, 65, 200):
+        runs.append(SampledRun("list_%d_75x53" % n, lights, "list", lights=lambda k, n=n: list(many_lights(n))))
+    assert len({r.name for r in runs}) == len(runs)
+    return tuple(runs)
+
+
+class RecordRun:
+    """A sequence of acting frames of rtggx_set_light_pick_visibility, judged one frame at a time: frame j at camera position j with the
+    frame index indices[j]; lights(j): the list rtggx_set_lights is called with in front of frame j (a reset), or None; scramble: the
+    frames in front of which the test overwrites the image read (where the side under test has a way to write the records)."""
+
+    def __init__(self, name, case, indices, lights, scramble=()):
+        self.name, self.case, self.indices, self.lights, self.scramble, self.family = name, case, tuple(indices), lights, tuple(scramble), "records"
+
+
+@functools.lru_cache(maxsize=None)
+def record_cases():
+    """The slab under four wide slats and a dome (both instance 1, at different depths: under a moving camera a point of the dome that a
+    slat hid a frame ago finds the slat's record -- the same instance, another normal); the camera pans by (0.6, 0.3, 0) a frame and the
+    second instance moves by (0.12, 0, 0.05), so pixels change their instance, previous positions leave the frame and land on sky.  Seven
+    frames (indices 0, 1, 2, 3, 255, 256, 257); four lights with radii from the start, another four from frame 4 on (a reset in the middle);
+    the image frame 3 reads is overwritten: every byte v random, the stamps and normals of the left quarter as well."""
+    _, lights = slat_cases()
+    slab = grid(2, 2, -2.0, 2.0, -2.0, 2.0)
+    # (three more slats high up, seen against the sky: a covered pixel whose tap lands beside the silhouette finds a record nobody wrote a frame ago)
+    over = join(slats(4, -2.2, 0.5, 0.4, -1.6, 1.2, 0.0), sphere_cap(5, 12, 1.0, 1.3, centre=(0.4, -1.1, 0.1)), slats(3, -1.8, 0.3, 0.9, 0.5, 3.0, 1.6))
+    # (the slab twice as wide as in slat_cases: it leaves the frame on three sides, so panning brings in points whose previous position is outside)
+    case = Case("records_75x53", "lights", 75, 53, slab, over, scale(3.0, 1.0, 3.0) @ translate(0.0, -1.0, 0.0), np.eye(4), lights.eye, lights.focus, smooth_cube(), lights.materials,
+                eye_step=(0.6, 0.3, 0.0), world1_step=(0.12, 0.0, 0.05))
+    A = dict(position=(0.5, -0.6, 0.3), intensity=(2.0, 1.5, 1.0), range=3.5, radius=0.2)
+    B = dict(position=(-1.0, -0.75, -0.5), intensity=(0.5, 1.0, 2.0), range=5.0, radius=0.3)
+    above = dict(position=(-0.4, 0.8, -0.1), intensity=(6.0, 6.0, 6.0), range=6.0, radius=0.4)
+    far = dict(position=(2.0, 0.5, 2.0), intensity=(4.0, 8.0, 4.0), range=5.0, radius=0.5)
+    dark = dict(position=(0.0, 0.0, 0.0), intensity=(0.0, 0.0, 0.0), range=10.0)
+    under = dict(position=(-0.4, -0.6, -0.1), intensity=(2.0, 1.0, 0.5), range=3.0, radius=0.2)
+    sets = {0: [A, B, dark, above, far], 4: [above, under, dark, A, far]}
+    return (RecordRun("records_75x53", case, (0, 1, 2, 3, 255, 256, 257), lambda j: sets.get(j), scramble=(3,)),)
+
+
+class SampledHitRun:
+    """The court at depth D, one sample, with sampled targets at the surfaces its paths hit: the sun under an angle, lights with radii in
+    mode 1 (rtggx_set_light_sampling), or a list (rtggx_set_light_list)."""
+
+    def __init__(self, name, case, depth, sun=None, angle=0.0, lights=None, mode=0, as_list=False):
+        self.name, self.case, self.depth, self.samples, self.positions = name, case, depth, 1, (0, 1, 2)
+        self.sun, self.angle, self.lights, self.mode, self.as_list, self.family = sun, angle, lights, mode, as_list, "hits"
+
+
+@functools.lru_cache(maxsize=None)
+def court_lights(n, seed=11):
+    """n lights inside the court's walls, ranges 2 to 5, every fourth with a radius, every seventh dark."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for i in range(n):
+        x, y, z, r, a, b, c, rho = [float(np.round(v, 3)) for v in rng.uniform((-2.4, -0.6, -1.9, 2.0, 0.5, 0.5, 0.5, 0.1), (2.4, 1.6, 1.9, 5.0, 4.0, 4.0, 4.0, 0.4))]
+        lt = dict(position=(x, y, z), range=r, intensity=(0.0, 0.0, 0.0) if i % 7 == 5 else (a, b, c))
+        if i % 4 == 1:
+            lt["radius"] = rho
+        out.append(lt)
+    return tuple(out)
+
+
+@functools.lru_cache(maxsize=None)
+def sampled_hit_cases():
+    """The court at D = 2: its suns at 5 degrees (slots 1 + 2 d + i); its lights with radii in mode 1 (targets 32 + 16 d + 8 img + i, draws
+    104 + 2 d + img); a list of 12 (targets 8192 + 1024 (2 d + img) + i from light 8 on)."""
+    court = court_case()
+    radius = {(-0.5, 1.6, 0.3): 0.3, (1.2, -0.2, 1.3): 0.15, (0.4, 1.8, 0.2): 0.25}
+
+    def soft(k):
+        return [dict(l, radius=radius.get(tuple(l["position"]), 0.0)) for l in court.lights(k)]
+    return (SampledHitRun("court_d2_sun_5_degrees", court, 2, sun=court.sun, angle=5.0),
+            SampledHitRun("court_d2_pick_radii", court, 2, lights=soft, mode=1),
+            SampledHitRun("court_d2_list_12", court, 2, lights=lambda k: list(court_lights(12)), mode=1, as_list=True))
+
+
+SAMPLED_NAMES = tuple(r.name for r in sampled_cases())
+
+
+def sampled_by_name(name):
+    return next(r for r in sampled_cases() if r.name == name)
 
 
 PATH_NAMES = tuple(r.name for r in path_cases())

@@ -15,9 +15,13 @@ function; this file shares no code with either and derives each step by another 
 A rounding is taken only where a typed texel is stored.  Every decision fp32 and float64 may take differently is FLAGGED per pixel, not
 guessed (FLAG_* below); flagged pixels are compared with the oracle bit for bit like all others, but not with this model.
 
-The sun's (angle 0) and the local lights' (radius 0) terms of the primary surface are sun_pass and lights_pass, from include/rtggx.h.
-The sun's and the lights' terms at the surfaces the paths hit (rtggx_set_sun_reflections, rtggx_set_light_reflections; one sample) are hits_pass.
-Out of scope: hit terms at N > 1, the sun's disk, the lights' radii, the light pick, sample sets above 256, ray rate 4.
+The sun's and the local lights' terms of the primary surface are sun_pass and lights_pass, from include/rtggx.h -- with the sun's disk
+(rtggx_set_sun_angle) and the lights' radii: the hashes are integer and the draws exact, so the sampled target is computed, not guessed.
+The light pick (rtggx_set_light_sampling) is pick_pass, its visibility records (rtggx_set_light_pick_visibility) records_pass one frame
+at a time, the light list (rtggx_set_light_list) list_pass and cull_counts.
+The sun's and the lights' terms at the surfaces the paths hit (rtggx_set_sun_reflections, rtggx_set_light_reflections; one sample) are
+hits_pass, with the same sampled targets and mode 1's hit rule.
+Out of scope: hit terms at N > 1, sample sets above 256, ray rate 4, the traversal's visiting order.
 
 Conventions: row vectors (p' = p M); the frame constants are the 768 bytes of RtggxFrameConstants (include/rtggx.h), 4x4 matrices stored
 transposed, 3x4 blocks as three rows of the transpose."""
@@ -679,6 +683,8 @@ def frame(scene, fc_bytes, vis, W, H, vndf=False, prev=None, depth=1, samples=1)
         rmv = out["rm_value"].reshape(n, 2)
         rmv[sky] = prev["rm_value"].reshape(n, 2)[sky]
     out["surface"] = {"P": P, "N": N, "V": V, "rough": rough, "metal": metal, "colour": colour, "tri_of": tri_of, "covered": covered, "flags": np.where(covered, a["flags"], 0)}
+    t3 = tris[tri_of]      # the error P carries in fp32: the barycentrics' (BARY_EPS) times the longest edge of the pixel's triangle
+    out["surface"]["p_eps"] = BARY_EPS * np.sqrt(np.maximum.reduce([_dot(t3[:, a] - t3[:, b], t3[:, a] - t3[:, b]) for a, b in ((0, 1), (1, 2), (2, 0))]))
     out.update(flags=flags.reshape(H, W), refl_lo=refl_lo.reshape(H, W, 3), refl_hi=refl_hi.reshape(H, W, 3), diff_lo=diff_lo.reshape(H, W, 3),
                diff_hi=diff_hi.reshape(H, W, 3), refl_traced=refl_traced.reshape(H, W), diff_traced=diff_traced.reshape(H, W),
                diff_written=diff_written.reshape(H, W), refl_nol=refl_nol.reshape(H, W), rays=int(rays_levels.sum()))
@@ -720,9 +726,125 @@ def _shadowed(tris, s, k, L, tmax):
     return h["valid"], h["flags"] & (FLAG_EDGE | FLAG_TMIN)
 
 
-def sun_pass(scene, fc_bytes, m, direction, irradiance):
+# ---- the sampled targets (include/rtggx.h: rtggx_set_sun_angle steps 1-5, rtggx_set_lights step 5, rtggx_set_light_sampling step 3) ----------
+# All of it integer up to the two draws u = (w & 0xffff) / 65536 and x = (v >> 8) / 2^24, which are exact in fp32 and here.
+SLOT_STRIDE = 0x9E3779B9
+SLOT_SUN, SLOT_LIGHTS, SLOT_PICK = 0, 16, 96
+OUTCOME_NONE, OUTCOME_NO_RAY, OUTCOME_OCCLUDED, OUTCOME_LIT = 0, 1, 2, 3      # of a pixel's one sampled ray: no candidate / not facing, no ray, occluded, lit
+FLAG_PICK, FLAG_WEIGHT, FLAG_TARGET = 2048, 4096, 8192
+FLAG_NAMES.update({FLAG_PICK: "pick_boundary", FLAG_WEIGHT: "tiny_weight", FLAG_TARGET: "target_in_surface"})
+# The pick compares t = x W with the running sums c_j, i.e. x with c_j / W.  Each w_i is a product of about ten fp32 factors formed from P, N
+# and V, whose own error is a few 1e-6 (NOL_EPS's reason), so c_j / W is known to a few 1e-6 relative, and it is at most 1: a draw within
+# PICK_EPS of a boundary may fall on either side in fp32.  (The GGX denominator's D_SLACK interval is taken on top: the boundaries are
+# formed from the terms' lower and upper ends, and x is held against their hull.)
+PICK_EPS = 1e-5
+# A weight fp32 may flush to zero on the way (its least normal number is 1.2e-38, and a weight is a product whose factors are formed one
+# by one: a partial product may underflow where the whole does not): such a light's candidacy is uncertain.
+TINY_WEIGHT = 1e-30
+# ds2 against 1e-6: Ds = D + rho o carries the primary surface's few 1e-6 per component, so ds2 = |Ds|^2 is off by 2 |Ds| x that, 2e-9 x a
+# few at |Ds| = 1e-3: within DS2_EPS of the threshold the step may go either way.
+DS2_EPS = 1e-8
+# The primary surface's P in fp32: the barycentrics come from screen-space gradients and are off by a few 1e-6 -- BARY_EPS,
+# with room: the worst pixels of the list and record cases show 1e-6 and 4e-6 of their triangles' 4 and 8 units --, and P by that times the
+# longest edge of the pixel's triangle: frame() hands it on per pixel as surface["p_eps"].
+BARY_EPS = 5e-6
+
+
+def sun_slot(level=None, image=0):
+    """The sun's slot: 0 for the primary pass, 1 + 2 d + i at the hit of a level-d ray of the path that writes image i."""
+    return SLOT_SUN if level is None else 1 + 2 * level + image
+
+
+def light_slot(i):
+    """The primary target slot of light i: 16 + i below 8, 4096 + i from 8 on (rtggx_set_light_list)."""
+    return SLOT_LIGHTS + i if i < 8 else 4096 + i
+
+
+def light_hit_slot(level, image, i):
+    return 32 + 16 * level + 8 * image + i if i < 8 else 8192 + 1024 * (2 * level + image) + i
+
+
+def pick_hit_slot(level, image):
+    return 104 + 2 * level + image
+
+
+VIS_FLOOR = 16      # RTGGX_LIGHT_VIS_FLOOR
+
+
+def visibility_weights(w, v):
+    """u_i = w_i max(v_i, RTGGX_LIGHT_VIS_FLOOR) (rtggx_set_light_pick_visibility, step 3); v: the carried bytes, shaped like w."""
+    return np.asarray(w, np.float64) * np.maximum(np.asarray(v, np.int64), VIS_FLOOR)
+
+
+def visibility_update(v, lit):
+    """Step 6, in integers: unoccluded v + ((255 - v + 3) >> 2), occluded v - ((v + 3) >> 2)."""
+    v = np.asarray(v, np.int64)
+    return np.where(lit, v + ((255 - v + 3) >> 2), v - ((v + 3) >> 2))
+
+
+def _hash_array(seed):
+    """_hash over an array of 32-bit words held in uint64."""
+    seed = (np.asarray(seed, np.uint64) * np.uint64(747796405) + np.uint64(1)) & np.uint64(0xFFFFFFFF)
+    seed = (((seed >> ((seed >> np.uint64(28)) + np.uint64(4))) ^ seed) * np.uint64(277803737)) & np.uint64(0xFFFFFFFF)
+    return ((seed >> np.uint64(22)) ^ seed) & np.uint64(0xFFFFFFFF)
+
+
+def slot_words(pixels, frame_index, slot):
+    """h = rng(rng(pixel) + FrameIndex), w = rng(h + slot 0x9E3779B9), with 32-bit wraparound at every step; pixels: full-frame indices
+    y W + x; slot: a number or one per pixel.  -> int64."""
+    h = _hash_array((_hash_array(pixels) + np.uint64(frame_index)) & np.uint64(0xFFFFFFFF))
+    step = (np.asarray(slot, np.uint64) * np.uint64(SLOT_STRIDE)) & np.uint64(0xFFFFFFFF)
+    return _hash_array((h + step) & np.uint64(0xFFFFFFFF)).astype(np.int64)
+
+
+def target_draw(w):
+    """(u, phi) of a target's word: u = (w & 0xffff) / 65536, s = w >> 24, phi = 2 pi s / 256 (entry s of the 256-entry table)."""
+    w = np.asarray(w, np.int64)
+    return (w & 0xFFFF) / 65536.0, 2.0 * np.pi * (w >> 24) / 256.0
+
+
+def pick_draw(v):
+    """x = (v >> 8) / 2^24."""
+    return (np.asarray(v, np.int64) >> 8) / 16777216.0
+
+
+def sun_disk_host(direction, degrees):
+    """The host's (k, T, B): in double on the fp32 L, each result rounded once to fp32 (returned as float64).  a: the axis of the smallest
+    |L_i|, ties to the lowest index; T = unit(a x L); B = L x T of the unrounded T."""
+    L = np.asarray(direction, np.float32).astype(np.float64)
+    k = 1.0 - np.cos(float(np.float32(degrees)) * np.pi / 180.0)
+    a = np.zeros(3); a[int(np.argmin(np.abs(L)))] = 1.0
+    T = np.cross(a, L); T = T / np.sqrt(T @ T)
+    B = np.cross(L, T)
+    r = lambda x: np.asarray(x, np.float64).astype(np.float32).astype(np.float64)
+    return float(r(k)), r(T), r(B)
+
+
+def sun_disk_direction(L, k, T, B, u, phi):
+    """Steps 4 and 5: e = u k, cos(theta) = 1 - e, sin(theta) = sqrt(e (2 - e)); Ls = T cos(phi) sin(theta) + B sin(phi) sin(theta) + L cos(theta)."""
+    e = np.asarray(u) * k
+    ct, st = 1.0 - e, np.sqrt(e * (2.0 - e))
+    return T * (np.cos(phi) * st)[..., None] + B * (np.sin(phi) * st)[..., None] + np.asarray(L, np.float64) * ct[..., None]
+
+
+def sphere_point(u, phi):
+    """z = 1 - 2 u; rho' = sqrt(1 - z z); o = (rho' cos(phi), rho' sin(phi), z)."""
+    z = 1.0 - 2.0 * np.asarray(u)
+    r = np.sqrt(1.0 - z * z)
+    return np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=-1)
+
+
+def _facing_flags(live, c):
+    """A cosine against zero: within NOL_EPS either way is a decision fp32 may take differently."""
+    return np.where(live & (np.abs(c) <= NOL_EPS), FLAG_NOL, 0)
+
+
+def sun_pass(scene, fc_bytes, m, direction, irradiance, angle_degrees=0.0, slot=SLOT_SUN):
     """The sun's terms of one frame m (frame()'s result).  direction: L as the host hands it on (unit, fp32); irradiance E.
-    -> dict over [H W]: spec_lo / spec_hi / diff [.. 3] (zero where there is no term), term (a term is added), flags, rays."""
+    angle_degrees > 0: rtggx_set_sun_angle -- the shadow ray points at Ls, a point of the disk drawn per pixel from `slot` with the
+    frame's own index; a ray exists where dot(N, L) > 0 and dot(N, Ls) > 0; the term is the directional sun's (at L).
+    -> dict over [H W]: spec_lo / spec_hi / diff [.. 3] (zero where there is no term), term (a term is added), flags, rays; with an angle
+       also outcome (OUTCOME_*, by the sampled ray), centre_outcome (by the ray along L) and below (facing L, but Ls below the horizon)."""
     fc = read_constants(fc_bytes)
     s = m["surface"]
     n = len(s["P"])
@@ -730,20 +852,36 @@ def sun_pass(scene, fc_bytes, m, direction, irradiance):
     tris, _, _ = _world_triangles(scene, fc)
     lo, hi, df = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 3))
     flags, term = np.zeros(n, np.int64), np.zeros(n, bool)
+    outcome, centre, below = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, bool)
     NoL = _dot(s["N"], L)
     flags |= np.where(s["covered"] & (np.abs(NoL) <= NOL_EPS), FLAG_NOL, 0) | np.where(s["covered"] & (NoL > 0) & (NoL < GRAZING_NOL), FLAG_GRAZING, 0)
     k = np.nonzero(s["covered"] & (NoL > 0.0))[0]
+    Ls = np.broadcast_to(L, (k.size, 3))
+    if angle_degrees > 0.0 and k.size:
+        kk, T, B = sun_disk_host(L, angle_degrees)
+        u, phi = target_draw(slot_words(k, fc["frame_index"], slot))
+        Ls = sun_disk_direction(L, kk, T, B, u, phi)
+        # dot(N, Ls): N's few 1e-6 as at L; Ls itself adds three rounded products and two sums of magnitude <= 1, under 1e-6: NOL_EPS holds both
+        up = _dot(s["N"][k], Ls)
+        flags[k] |= _facing_flags(np.ones(k.size, bool), up)
+        centre[k] = np.where(_shadowed(tris, s, k, np.broadcast_to(L, (k.size, 3)), RAY_TMAX)[0], OUTCOME_OCCLUDED, OUTCOME_LIT)
+        below[k[up <= 0.0]] = True
+        outcome[k[up <= 0.0]] = OUTCOME_NO_RAY
+        k, Ls = k[up > 0.0], Ls[up > 0.0]
     rays = k.size
     if k.size:
-        occ, fl = _shadowed(tris, s, k, np.broadcast_to(L, (k.size, 3)), RAY_TMAX)
+        # (the ray's edge flags are the sampled ray's: EDGE is sized for the origin's error; Ls adds under 1e-6 of direction)
+        occ, fl = _shadowed(tris, s, k, Ls, RAY_TMAX)
         flags[k] |= fl
+        outcome[k] = np.where(occ, OUTCOME_OCCLUDED, OUTCOME_LIT)
         k = k[~occ]
         l, h, d = _direct_term(s, k, np.broadcast_to(L, (k.size, 3)), NoL[k])
         lo[k], hi[k], df[k], term[k] = l * E, h * E, d * E, True
     flags |= s["flags"]
     shape = m["covered"].shape
     return {"spec_lo": lo.reshape(shape + (3,)), "spec_hi": hi.reshape(shape + (3,)), "diff": df.reshape(shape + (3,)), "term": term.reshape(shape),
-            "diffuse": (term & (s["metal"] < 1.0)).reshape(shape), "flags": flags.reshape(shape), "rays": int(rays)}
+            "diffuse": (term & (s["metal"] < 1.0)).reshape(shape), "flags": flags.reshape(shape), "rays": int(rays),
+            "outcome": outcome.reshape(shape), "centre_outcome": centre.reshape(shape), "below": below.reshape(shape)}
 
 
 def light_window(d2, R):
@@ -761,52 +899,326 @@ def light_attenuation(d2, R, radius=0.0, spot=1.0):
     return light_window(d2, R) * spot / np.maximum(d2, max(radius * radius, 1e-4))
 
 
-def lights_pass(scene, fc_bytes, m, lights):
-    """The local lights' sums of one frame, radius 0: lights as dicts (position, intensity, range, axis, cos_outer, cos_inner; the axis a
-    unit vector), summed in their order.  -> like sun_pass."""
+def _light_reach(s, lt):
+    """Steps 1-4 of rtggx_set_lights for one light at every pixel -> (live [n]: in range, facing, inside the cone; D, d2, L, NoL, att, flags,
+    (att_lo, att_hi)).  The interval of att: the window's 1 - q^2 cancels towards the range's end -- d2 carries 2 d p_eps of the primary
+    surface, q^2 = (d2 / R^2)^2 so 4 q d p_eps / R^2 <= 4 d p_eps / R^2, an ABSOLUTE error of the difference however small it is -- and the
+    cone's s = (c - cos_outer) / (...) does towards cos_outer, by the 1e-5 of FLAG_CONE's band; both factors are monotone, so att with each
+    taken that much lower and higher is a true interval, as D_SLACK's is.  lights_pass, whose terms are added to a word that is seldom zero,
+    uses the value; pick_pass, whose one term may be all a pixel has, the interval."""
+    n = len(s["P"])
+    R = float(np.float32(lt["range"]))
+    D = np.asarray(lt["position"], np.float32).astype(np.float64) - s["P"]
+    d2 = _dot(D, D)
+    cov = s["covered"]
+    flags = np.where(cov & ((np.abs(d2 - R * R) <= 1e-5 * R * R) | (np.abs(d2 - 1e-6) <= 1e-11)), FLAG_RANGE, 0)
+    live = cov & (d2 >= 1e-6) & (d2 < R * R)
+    L = _unit(D)
+    NoL = _dot(s["N"], L)
+    flags |= np.where(live & (np.abs(NoL) <= NOL_EPS), FLAG_NOL, 0) | np.where(live & (NoL > 0) & (NoL < GRAZING_NOL), FLAG_GRAZING, 0)
+    live = live & (NoL > 0.0)
+    spot = spot_lo = spot_hi = np.ones(n)
+    co = float(np.float32(lt.get("cos_outer", -1.0)))
+    if co > -1.0:
+        ci = float(np.float32(lt["cos_inner"]))
+        c = -_dot(L, np.asarray(lt["axis"], np.float32).astype(np.float64))
+        flags |= np.where(live & (np.abs(c - co) <= 1e-5), FLAG_CONE, 0)
+        live = live & (c > co)
+        spot, spot_lo, spot_hi = light_spot(c, co, ci), light_spot(c - 1e-5, co, ci), light_spot(c + 1e-5, co, ci)
+    rho = float(np.float32(lt.get("radius", 0.0)))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        att = light_attenuation(d2, R, rho, spot)
+        q2, slack = (d2 / (R * R)) ** 2, 4.0 * np.sqrt(d2) * s["p_eps"] / (R * R)
+        floor = np.maximum(d2, max(rho * rho, 1e-4))
+        att_lo, att_hi = _sat(1.0 - q2 - slack) ** 2 * spot_lo / floor, _sat(1.0 - q2 + slack) ** 2 * spot_hi / floor
+    return live, D, d2, L, NoL, att, flags, (att_lo, att_hi)
+
+
+def _light_target(s, lt, k, D, slot, frame_index):
+    """Steps 5 and 6 at the pixels k: the target Ds = D + rho o with o drawn from `slot` (one per pixel or one for all), ds2, Ls, tmax and
+    the test dot(N, Ls) > 0.  With rho = 0 there is no hash and Ds = D.  -> (ray exists [len k], Ls, tmax, below the horizon, flags)."""
+    rho = float(np.float32(lt.get("radius", 0.0)))
+    Ds = D[k]
+    if rho > 0.0:
+        u, phi = target_draw(slot_words(k, frame_index, slot))
+        Ds = Ds + rho * sphere_point(u, phi)
+    ds2 = _dot(Ds, Ds)
+    flags = np.where(np.abs(ds2 - 1e-6) <= DS2_EPS, FLAG_TARGET, 0)
+    some = ds2 >= 1e-6
+    with np.errstate(invalid="ignore", divide="ignore"):
+        Ls = _unit(Ds)
+    up = np.where(some, _dot(s["N"][k], Ls), 0.0)
+    # dot(N, Ls): N's error as at L, and Ls's: the few 1e-6 of Ds over |Ds| (no target of a case lies nearer than the range test's 1e-3
+    # ... which NOL_EPS does not hold below |Ds| = 0.1: there the band widens in proportion)
+    flags |= np.where(some & (np.abs(up) <= NOL_EPS * np.maximum(1.0, 0.1 / np.sqrt(np.maximum(ds2, 1e-12)))), FLAG_NOL, 0)
+    below = some & (up <= 0.0)
+    return some & ~below, Ls, np.sqrt(ds2), below, flags
+
+
+def lights_pass(scene, fc_bytes, m, lights, first_slot=SLOT_LIGHTS):
+    """The local lights' sums of one frame: lights as dicts (position, intensity, range, radius, axis, cos_outer, cos_inner; the axis a
+    unit vector), summed in their order.  A light of radius rho > 0 aims its shadow ray at a point of its sphere, drawn per pixel from the
+    slot first_slot + i (i: the light's index in the list, dark lights counted) with the frame's own index; the interval ends at the target;
+    the term is the centre direction's.  The ray's t within 1e-3 of tmax is closest_hit's FLAG_TMIN, as at radius 0.
+    -> like sun_pass; outcome, centre_outcome, below: [count H W] per light (centre: the ray at D over (RAY_TMIN, |D|))."""
     fc = read_constants(fc_bytes)
     s = m["surface"]
     n = len(s["P"])
     tris, _, _ = _world_triangles(scene, fc)
     lo, hi, df = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 3))
     flags, term, rays = np.zeros(n, np.int64), np.zeros(n, bool), 0
-    for lt in lights:
+    outcome, centre, below = np.zeros((len(lights), n), np.int64), np.zeros((len(lights), n), np.int64), np.zeros((len(lights), n), bool)
+    for i, lt in enumerate(lights):
         I = np.asarray(lt["intensity"], np.float64)
         if not (I > 0).any():
             continue
-        assert lt.get("radius", 0.0) == 0.0
-        R = float(np.float32(lt["range"]))
-        D = np.asarray(lt["position"], np.float32).astype(np.float64) - s["P"]
-        d2 = _dot(D, D)
-        cov = s["covered"]
-        flags |= np.where(cov & ((np.abs(d2 - R * R) <= 1e-5 * R * R) | (np.abs(d2 - 1e-6) <= 1e-11)), FLAG_RANGE, 0)
-        live = cov & (d2 >= 1e-6) & (d2 < R * R)
-        L = _unit(D)
-        NoL = _dot(s["N"], L)
-        flags |= np.where(live & (np.abs(NoL) <= NOL_EPS), FLAG_NOL, 0) | np.where(live & (NoL > 0) & (NoL < GRAZING_NOL), FLAG_GRAZING, 0)
-        live &= NoL > 0.0
-        spot = np.ones(n)
-        co = float(np.float32(lt.get("cos_outer", -1.0)))
-        if co > -1.0:
-            ci = float(np.float32(lt["cos_inner"]))
-            c = -_dot(L, np.asarray(lt["axis"], np.float32).astype(np.float64))
-            flags |= np.where(live & (np.abs(c - co) <= 1e-5), FLAG_CONE, 0)
-            live &= c > co
-            spot = light_spot(c, co, ci)
+        live, D, d2, L, NoL, att, fl, _ = _light_reach(s, lt)
+        flags |= fl
         k = np.nonzero(live)[0]
+        if not k.size:
+            continue
+        go, Ls, tmax, bel, fl = _light_target(s, lt, k, D, first_slot + i, fc["frame_index"])
+        flags[k] |= fl
+        below[i, k] = bel
+        outcome[i, k] = OUTCOME_NO_RAY
+        if float(np.float32(lt.get("radius", 0.0))) > 0.0:
+            centre[i, k] = np.where(_shadowed(tris, s, k, L[k], np.sqrt(d2[k]))[0], OUTCOME_OCCLUDED, OUTCOME_LIT)
+        k, Ls, tmax = k[go], Ls[go], tmax[go]
         rays += k.size
         if not k.size:
             continue
-        occ, fl = _shadowed(tris, s, k, L[k], np.sqrt(d2[k]))
+        occ, fl = _shadowed(tris, s, k, Ls, tmax)
         flags[k] |= fl
+        outcome[i, k] = np.where(occ, OUTCOME_OCCLUDED, OUTCOME_LIT)
         k = k[~occ]
-        att = light_attenuation(d2[k], R, 0.0, spot[k])
         l, h, d = _direct_term(s, k, L[k], NoL[k])
-        lo[k] += l * (I * att[:, None]); hi[k] += h * (I * att[:, None]); df[k] += d * (I * att[:, None]); term[k] = True
+        lo[k] += l * (I * att[k][:, None]); hi[k] += h * (I * att[k][:, None]); df[k] += d * (I * att[k][:, None]); term[k] = True
     flags |= s["flags"]
     shape = m["covered"].shape
     return {"spec_lo": lo.reshape(shape + (3,)), "spec_hi": hi.reshape(shape + (3,)), "diff": df.reshape(shape + (3,)), "term": term.reshape(shape),
-            "diffuse": (term & (s["metal"] < 1.0)).reshape(shape), "flags": flags.reshape(shape), "rays": int(rays)}
+            "diffuse": (term & (s["metal"] < 1.0)).reshape(shape), "flags": flags.reshape(shape), "rays": int(rays),
+            "outcome": outcome.reshape((-1,) + shape), "centre_outcome": centre.reshape((-1,) + shape), "below": below.reshape((-1,) + shape)}
+
+
+def luminance(c):
+    """Y(c) = 0.25 r + 0.5 g + 0.25 b."""
+    return 0.25 * c[..., 0] + 0.5 * c[..., 1] + 0.25 * c[..., 2]
+
+
+def pick_choice(x, weights):
+    """Steps 2-5 of mode 1 for weights [n_lights, n] (0: not a candidate) and draws x [n]: W summed ascending, t = x W, the first candidate
+    with t < c, else the last candidate.  -> (chosen [n] or -1, W [n], c [n_lights n] the running sums)."""
+    w = np.asarray(weights, np.float64)
+    cand = w > 0.0
+    c = np.cumsum(np.where(cand, w, 0.0), axis=0)
+    W = c[-1]
+    t = x * W
+    hit = cand & (t[None] < c)
+    first = np.argmax(hit, axis=0)
+    last = w.shape[0] - 1 - np.argmax(cand[::-1], axis=0)
+    chosen = np.where(hit.any(axis=0), first, last)
+    return np.where(cand.any(axis=0), chosen, -1), W, c
+
+
+def pick_pass(scene, fc_bytes, m, lights, weights=None, slots=None, draw_slot=SLOT_PICK):
+    """Mode 1's primary pass (rtggx_set_light_sampling, steps 0-7): per pixel the candidates' spec_i and diff_i (lights_pass's terms, before
+    any ray), w_i = Y(spec_i) + Y(diff_i) -- Y(spec_i) alone at metallic >= 1 --, a candidate iff w_i > 0; W ascending; x from draw_slot,
+    t = x W; the first candidate with t < c, else the last; f = W / w_i; the chosen light's target from its own slot (slots[i], default
+    16 + i), one ray; unoccluded: S0 = spec_i f, S1 = diff_i f.
+    weights: a function (w [n_lights n], pixel info) -> u of the same shape, the pick weights in place of w (the visibility records' u_i).
+    -> like sun_pass, and chosen [H W] (-1: no candidate), outcome [H W] (OUTCOME_*), centre_outcome, below, candidates [H W] (their number),
+       later [H W] (the chosen light is not the first candidate), w [count H W]."""
+    fc = read_constants(fc_bytes)
+    s = m["surface"]
+    n, nl = len(s["P"]), len(lights)
+    tris, _, _ = _world_triangles(scene, fc)
+    slots = [SLOT_LIGHTS + i for i in range(nl)] if slots is None else list(slots)
+    flags = np.zeros(n, np.int64)
+    sp_lo, sp_hi, sp_mid, dfs, df_lo, df_hi = [np.zeros((nl, n, 3)) for _ in range(6)]
+    reach = []
+    metal1 = s["metal"] >= 1.0
+    for i, lt in enumerate(lights):
+        I = np.asarray(lt["intensity"], np.float64)
+        if not (I > 0).any():
+            reach.append(None)
+            continue
+        live, D, d2, L, NoL, att, fl, (att_lo, att_hi) = _light_reach(s, lt)
+        flags |= fl
+        reach.append((D, d2, L))
+        k = np.nonzero(live)[0]
+        l, h, d = _direct_term(s, k, L[k], NoL[k])
+        sp_lo[i, k], sp_hi[i, k], dfs[i, k] = l * (I * att_lo[k][:, None]), h * (I * att_hi[k][:, None]), d * (I * att[k][:, None])
+        df_lo[i, k], df_hi[i, k] = d * (I * att_lo[k][:, None]), d * (I * att_hi[k][:, None])
+        sp_mid[i, k] = 0.5 * (l + h) * (I * att[k][:, None])
+    w_lo, w_hi = luminance(sp_lo) + np.where(metal1[None], 0.0, luminance(df_lo)), luminance(sp_hi) + np.where(metal1[None], 0.0, luminance(df_hi))
+    w_mid = luminance(sp_mid) + np.where(metal1[None], 0.0, luminance(dfs))
+    flags |= np.where(((w_hi > 0.0) & (w_lo < TINY_WEIGHT)).any(axis=0), FLAG_WEIGHT, 0)
+    if weights is not None:
+        w_lo, w_hi, w_mid = weights(w_lo), weights(w_hi), weights(w_mid)
+    x = pick_draw(slot_words(np.arange(n), fc["frame_index"], draw_slot))
+    chosen, W, c = pick_choice(x, w_mid)
+    # the boundaries c_j / W from the terms' lower ends, upper ends and middles: x within PICK_EPS of their hull is a decision
+    flags |= np.where(_pick_boundary_flags(x, w_lo, w_mid, w_hi), FLAG_PICK, 0)
+    lo, hi, df, d_lo, d_hi = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 3))
+    term, rays = np.zeros(n, bool), 0
+    outcome, centre, below = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, bool)
+    cand = w_mid > 0.0
+    first_cand = np.argmax(cand, axis=0)
+    for i, lt in enumerate(lights):
+        k = np.nonzero(chosen == i)[0]
+        if not k.size:
+            continue
+        D, d2, L = reach[i]
+        go, Ls, tmax, bel, fl = _light_target(s, lt, k, D, slots[i], fc["frame_index"])
+        flags[k] |= fl
+        below[k] = bel
+        outcome[k] = OUTCOME_NO_RAY
+        if float(np.float32(lt.get("radius", 0.0))) > 0.0:
+            centre[k] = np.where(_shadowed(tris, s, k, L[k], np.sqrt(d2[k]))[0], OUTCOME_OCCLUDED, OUTCOME_LIT)
+        k, Ls, tmax = k[go], Ls[go], tmax[go]
+        rays += k.size
+        if not k.size:
+            continue
+        occ, fl = _shadowed(tris, s, k, Ls, tmax)
+        flags[k] |= fl
+        outcome[k] = np.where(occ, OUTCOME_OCCLUDED, OUTCOME_LIT)
+        k = k[~occ]
+        # f = W / w_i = 1 + sum over the others of w_j / w_i: exactly 1 with a single candidate; its interval from the terms' ends
+        others_lo, others_hi = w_lo[:, k].sum(axis=0) - w_lo[i, k], w_hi[:, k].sum(axis=0) - w_hi[i, k]
+        f_lo, f_hi = 1.0 + others_lo / w_hi[i, k], 1.0 + others_hi / w_lo[i, k]
+        f_mid = W[k] / w_mid[i, k]
+        lo[k], hi[k], df[k], term[k] = sp_lo[i, k] * f_lo[:, None], sp_hi[i, k] * f_hi[:, None], dfs[i, k] * f_mid[:, None], True
+        d_lo[k], d_hi[k] = df_lo[i, k] * f_lo[:, None], df_hi[i, k] * f_hi[:, None]
+    flags |= s["flags"]
+    shape = m["covered"].shape
+    return {"spec_lo": lo.reshape(shape + (3,)), "spec_hi": hi.reshape(shape + (3,)), "diff": df.reshape(shape + (3,)), "term": term.reshape(shape),
+            "diff_lo": d_lo.reshape(shape + (3,)), "diff_hi": d_hi.reshape(shape + (3,)),      # (f's interval on the diffuse term too)
+            "diffuse": (term & (s["metal"] < 1.0)).reshape(shape), "flags": flags.reshape(shape), "rays": int(rays),
+            "chosen": chosen.reshape(shape), "outcome": outcome.reshape(shape), "centre_outcome": centre.reshape(shape), "below": below.reshape(shape),
+            "candidates": cand.sum(axis=0).reshape(shape), "later": ((chosen >= 0) & (chosen != first_cand)).reshape(shape),
+            "w": w_mid.reshape((nl,) + shape), "W": W.reshape(shape), "x": x.reshape(shape)}
+
+
+# ---- the visibility records (include/rtggx.h: rtggx_set_light_pick_visibility), one frame at a time ----------------------------------------
+RECORD = np.dtype([("v", np.uint8, 8), ("normal", np.uint32), ("stamp", np.uint32)])      # RtggxLightVisRecord
+HISTORY_VALID, HISTORY_SEQUENCE, HISTORY_OFF_FRAME, HISTORY_STAMP, HISTORY_INSTANCE, HISTORY_NORMAL = range(6)      # valid, or the first condition of step 2 that fails
+HISTORY_NAMES = {HISTORY_SEQUENCE: "sequence", HISTORY_OFF_FRAME: "off_frame", HISTORY_STAMP: "stamp", HISTORY_INSTANCE: "instance", HISTORY_NORMAL: "normal"}
+NORMAL_LIMIT = float(np.float32(0.9) * np.float32(1046529.0))      # 0.9f * 1046529.0f, the product rounded once
+FLAG_HISTORY = 16384
+FLAG_NAMES[FLAG_HISTORY] = "history_tap"
+# ((float)x + 0.5f) - vx (float)W: the product is rounded once and the difference once more, 2 x 2^-24 x 96 at most -- 1.2e-5 --, and vx is the
+# frame's own binary16 word, an input.  Within HISTORY_EPS of an integer floor() may land on either side.
+HISTORY_EPS = 1e-4
+
+
+class RecordSequence:
+    """s and s0 from the call history: s counts the acting frames; s0 is s at the last reset -- the allocation (the first acting frame),
+    every successful rtggx_set_lights and rtggx_set_light_sampling, every change of the setting."""
+
+    def __init__(self):
+        self.s = self.s0 = 0
+        self.allocated = False
+
+    def reset(self):
+        self.s0 = self.s
+
+    def acting_frame(self):
+        """-> (s, s0) of the frame: it writes image s & 1 and reads image (s - 1) & 1."""
+        if not self.allocated:
+            self.allocated = True
+            self.reset()
+        self.s += 1
+        return self.s, self.s0
+
+
+def _half_words(w):
+    return np.asarray(w).astype(np.uint16).view(np.float16).astype(np.float64)
+
+
+def _normal_integers(words):
+    w = np.asarray(words).astype(np.int64)
+    return np.stack([2 * (w & 1023) - 1023, 2 * ((w >> 10) & 1023) - 1023, 2 * ((w >> 20) & 1023) - 1023], axis=-1)
+
+
+def records_pass(scene, fc_bytes, m, lights, read, normal_words, velocity_words, s, s0):
+    """One acting frame of rtggx_set_light_pick_visibility.  read: RECORD [H W], the image (s - 1) & 1 as the context holds it in front of
+    the frame; normal_words, velocity_words: the frame's own G-buffer words; (s, s0): RecordSequence.acting_frame's.
+    Steps 2-6: the tap (qx, qy) = floor((x + 0.5) - vx W, (y + 0.5) - vy H); valid iff s - 1 > s0, the tap inside the frame, the record's
+    stamp >> 8 == (s - 1) & 0xFFFFFF, its stamp & 0xFF == inst + 1, and the integer dot of the two normal words' 2 q - 1023 >= NORMAL_LIMIT;
+    v_i the record's bytes, or 255; u_i = w_i max(v_i, 16) in place of w_i in mode 1's pick (pick_pass); where a ray was traced the chosen
+    light's byte is updated (visibility_update); the record written at every covered pixel: the bytes, the normal word, (s & 0xFFFFFF) << 8
+    | (inst + 1).
+    -> pick_pass's result, and records (RECORD [H W], what the frame writes at covered pixels), history [H W] (HISTORY_*), carried [H W 8]."""
+    H, W = m["covered"].shape
+    n = H * W
+    vis = m["vis"].reshape(-1).astype(np.int64)
+    cov = vis > 0
+    inst = np.where(cov, (vis - 1) >> 24, 0)
+    py, px = np.divmod(np.arange(n), W)
+    vw = np.asarray(velocity_words).reshape(-1).astype(np.int64)
+    fx, fy = (px + 0.5) - _half_words(vw & 0xFFFF) * W, (py + 0.5) - _half_words(vw >> 16) * H
+    flags = np.where(cov & ((np.abs(fx - np.round(fx)) <= HISTORY_EPS) | (np.abs(fy - np.round(fy)) <= HISTORY_EPS)), FLAG_HISTORY, 0)
+    qx, qy = np.floor(fx).astype(np.int64), np.floor(fy).astype(np.int64)
+    inside = (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H)
+    tap = np.asarray(read).reshape(-1)[np.where(inside, qy * W + qx, 0)]
+    stamp = tap["stamp"].astype(np.int64)
+    dots = (_normal_integers(tap["normal"]) * _normal_integers(np.asarray(normal_words).reshape(-1))).sum(axis=-1)
+    fails = [np.full(n, not (s - 1 > s0)), ~inside, (stamp >> 8) != ((s - 1) & 0xFFFFFF), (stamp & 0xFF) != inst + 1, dots < NORMAL_LIMIT]
+    history = np.full(n, HISTORY_VALID)
+    for cls, f in reversed(list(zip((HISTORY_SEQUENCE, HISTORY_OFF_FRAME, HISTORY_STAMP, HISTORY_INSTANCE, HISTORY_NORMAL), fails))):
+        history[f] = cls
+    carried = np.where((history == HISTORY_VALID)[:, None], tap["v"].astype(np.int64), 255)
+    nl = len(lights)
+    p = pick_pass(scene, fc_bytes, m, lights, weights=lambda w: visibility_weights(w, carried.T[:nl]))
+    chosen, outcome = p["chosen"].reshape(-1), p["outcome"].reshape(-1)
+    traced = (outcome == OUTCOME_OCCLUDED) | (outcome == OUTCOME_LIT)
+    v = carried.copy()
+    k = np.nonzero(traced)[0]
+    v[k, chosen[k]] = visibility_update(carried[k, chosen[k]], outcome[k] == OUTCOME_LIT)
+    rec = np.zeros(n, RECORD)
+    rec["v"], rec["normal"], rec["stamp"] = v, np.asarray(normal_words).reshape(-1), ((s & 0xFFFFFF) << 8) | (inst + 1)
+    p["flags"] = p["flags"] | flags.reshape(H, W)
+    p.update(records=rec.reshape(H, W), history=np.where(cov, history, -1).reshape(H, W), carried=carried.reshape(H, W, 8))
+    return p
+
+
+def list_pass(scene, fc_bytes, m, lights):
+    """rtggx_set_light_list's primary pass: mode 1's rule over all n lights, the target of light i from light_slot(i)."""
+    return pick_pass(scene, fc_bytes, m, lights, slots=[light_slot(i) for i in range(len(lights))])
+
+
+# The cull's box is made of the primary surface's P in fp32 (p_eps, the block's largest), so e_c is off by as much and dist2 = |e|^2 by 2 |e| sqrt(3) p_eps; the
+# squares and sums add (1 + 2^-24)^8.  Within that of RRm the comparison dist2 < RRm may go either way.
+
+
+def cull_counts(m, lights):
+    """The cull of rtggx_set_light_list per 8 x 8 block, in float64: lo / hi of the covered pixels' P; per casting light
+    e_c = max(max(lo_c - Pl_c, Pl_c - hi_c), 0), dist2 = |e|^2, RRm = R R (1 + 2^-12); kept iff dist2 < RRm.
+    -> (certain [by bx]: lights kept whatever fp32 does, uncertain [by bx]: lights whose |dist2 - RRm| is within the slack of P's error,
+        covered [by bx]: the block has a covered pixel).  A block without a covered pixel keeps nothing."""
+    s = m["surface"]
+    H, W = m["covered"].shape
+    by, bx = -(-H // 8), -(-W // 8)
+    P, cov = s["P"].reshape(H, W, 3), m["covered"]
+    certain, uncertain, some = np.zeros((by, bx), np.int64), np.zeros((by, bx), np.int64), np.zeros((by, bx), bool)
+    cast = [lt for lt in lights if (np.asarray(lt["intensity"], np.float64) > 0).any()]
+    Pl = np.array([np.asarray(lt["position"], np.float32).astype(np.float64) for lt in cast]).reshape(-1, 3)
+    RRm = np.array([float(np.float32(lt["range"])) ** 2 * (1.0 + 2.0 ** -12) for lt in cast])
+    for j in range(by):
+        for i in range(bx):
+            c = cov[8 * j:8 * j + 8, 8 * i:8 * i + 8]
+            if not c.any():
+                continue
+            some[j, i] = True
+            p = P[8 * j:8 * j + 8, 8 * i:8 * i + 8][c]
+            p_eps = float(s["p_eps"].reshape(H, W)[8 * j:8 * j + 8, 8 * i:8 * i + 8][c].max())
+            lo, hi = p.min(axis=0), p.max(axis=0)
+            e = np.maximum(np.maximum(lo - Pl, Pl - hi), 0.0)
+            dist2 = (e * e).sum(axis=1)
+            slack = 2.0 * np.sqrt(3.0 * dist2) * p_eps + 3.0 * p_eps * p_eps + 8.0 * 2.0 ** -24 * RRm
+            unsure = np.abs(dist2 - RRm) <= slack
+            certain[j, i], uncertain[j, i] = int(((dist2 < RRm) & ~unsure).sum()), int(unsure.sum())
+    return certain, uncertain, some
 
 
 # ---- the sun and the lights at the surfaces the paths hit (include/rtggx.h: rtggx_set_sun_reflections, rtggx_set_light_reflections) ----------
@@ -820,18 +1232,32 @@ LOBES = ("mirror", "diffuse_on_reflection_ray", "diffuse_on_diffuse_ray")
 HIT_CLASSES = ("facing_away", "occluded", "out_of_range", "outside_cone")
 
 
-def hits_pass(scene, fc_bytes, m, sun=None, lights=()):
+def _pick_boundary_flags(x, w_lo, w_mid, w_hi):
+    """x within PICK_EPS of the hull of an inner boundary c_j / W formed from the weights' lower ends, middles and upper ends -> [n] bool."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        fr = np.stack([np.cumsum(w, axis=0) / w.sum(axis=0) for w in (w_lo, w_mid, w_hi)])
+    inner = (w_mid > 0.0) & (np.cumsum(w_mid, axis=0) < w_mid.sum(axis=0)[None])      # (the last candidate's boundary is 1: x < 1 always, and "else the last" is the same light)
+    return (inner & (x[None] >= fr.min(axis=0) - PICK_EPS) & (x[None] <= fr.max(axis=0) + PICK_EPS)).any(axis=0)
+
+
+def hits_pass(scene, fc_bytes, m, sun=None, lights=(), sun_angle=0.0, mode=0):
     """The sum S of one one-sample frame m (frame()'s result at any depth): for every level-d ray that touches a surface (m["segments"]) the
     term of the lobe the path uses there -- metallic > 0.5: the specular term of _direct_term with the hit's N, V = -dir, (r, m) and colour,
     its D_SLACK interval kept; otherwise colour' NoL / pi with colour' = colour (1 - m) for a diffuse-group ray and colour for a
-    reflection-group one, no 0.96 -- times E (the sun: sun = (L, E), angle 0) or I att (a light of radius 0: window, cone and floor as in
-    lights_pass), unless the hit faces away (NoL <= 0), lies out of range or outside the cone, or anything but the hit's own triangle
-    lies on the ray from the hit point over (RAY_TMIN, RAY_TMAX) for the sun and (RAY_TMIN, |D|) for a light; s_d = T_d term; S per
-    (pixel, image) over d ascending, the sun first, then the lights in their order.
+    reflection-group one, no 0.96 -- times E (the sun: sun = (L, E)) or I att (a light: window, cone and floor as in lights_pass), unless the
+    hit faces away (NoL <= 0), lies out of range or outside the cone, or anything but the hit's own triangle lies on the shadow ray from the
+    hit point over (RAY_TMIN, RAY_TMAX) for the sun and (RAY_TMIN, tmax) for a light; s_d = T_d term; S per (pixel, image) over d ascending,
+    the sun first, then the lights in their order.
+    The sampled targets: sun_angle > 0 aims the sun's ray at the point of the disk drawn from sun_slot(d, img); a light of radius > 0 aims
+    at the point of its sphere drawn from light_hit_slot(d, img, i), tmax the target's distance; both with the path's pixel and the frame's
+    index, both with the second test dot(N, Ls) > 0, the term the centre direction's.  mode 1 (rtggx_set_light_sampling, or a list): per hit
+    the candidates' s_i = T_d term_i, w_i = Y(s_i), the draw from pick_hit_slot(d, img), the pick and f of pick_choice, one ray at the
+    chosen light's target, the term s_i f.
     -> dict: lo, hi [2 H W 3] (image 0: RayTracingOut0), mid (the unslacked run's value with no error carried), term [2 H W], flags [H W] (the frame's and the pass's own), rays,
        counts {(level, lobe or class): terms or hits}."""
     assert m["samples"] == 1, "with several samples the terms go into the fp32 sample sums: no stage to observe"
     fc = read_constants(fc_bytes)
+    F = fc["frame_index"]
     tris = _world_triangles(scene, fc)[0]
     shape = m["covered"].shape
     n = shape[0] * shape[1]
@@ -860,40 +1286,52 @@ def hits_pass(scene, fc_bytes, m, sun=None, lights=()):
             count(lev, "facing_away", (live & (NoL <= 0.0)).sum())
             return NoL, live & (NoL > 0.0)
 
-        def lit(k, L, NoL, tmax, scale):
-            """Shadow rays of the hits k along L [len(k) 3]; the unoccluded ones' terms x scale x T into S."""
-            nonlocal rays
-            rays += k.size if sg["run"] == 0 else 0
-            if not k.size:
-                return
-            h = closest_hit(tris, sg["P"][k], L, sg["tri_of"][k], tmax=tmax, widen=sg["amp"][k])
-            flags[px[k]] |= h["flags"] & (FLAG_EDGE | FLAG_TMIN)
-            count(lev, "occluded", h["valid"].sum())
-            keep = ~h["valid"]
-            k, L, NoL, scale = k[keep], L[keep], NoL[keep], (scale[0][keep], scale[1][keep])
+        def above(k, Ls):
+            """The second test dot(N, Ls) > 0 at the hits k: the cosine carries the hit's error (HIT_COSINE_ERROR x amp) -> keep [len k]."""
+            up = _dot(sg["N"][k], Ls)
+            flags[px[k]] |= np.where(np.abs(up) <= np.maximum(NOL_EPS, HIT_COSINE_ERROR * sg["amp"][k]), FLAG_NOL, 0)
+            count(lev, "below_horizon", (up <= 0.0).sum())
+            return up > 0.0
+
+        def terms(k, L, NoL, scale):
+            """s_d = T_d term at the hits k, centre direction L, as an interval and a middle -> (lo, hi, mid [len k, 3])."""
             err = HIT_COSINE_ERROR * sg["amp"][k]
             sl, sh, _ = _direct_term(sg, k, L, NoL, D_SLACK + 2.0 * err / np.maximum(np.sqrt(_dot(sg["V"][k] + L, sg["V"][k] + L)), 2.0 ** -10))
             dt = cprime[k] * (NoL / np.pi)[:, None]
             nl, nh = (np.maximum(NoL - err, 0.0) / NoL)[:, None], ((NoL + err) / NoL)[:, None]
             tl = np.where(mirror[k][:, None], sl, dt) * nl * scale[0] * sg["T"][k] * np.maximum(1.0 - t_err[k], 0.0)[:, None]
             th = np.where(mirror[k][:, None], sh, dt) * nh * scale[1] * sg["T"][k] * (1.0 + t_err[k])[:, None]
-            lo[img, px[k]] += np.minimum(tl, th); hi[img, px[k]] += np.maximum(tl, th); term[img, px[k]] = True
+            tm = np.where(mirror[k][:, None], 0.5 * (sl + sh), dt) * (0.5 * (scale[0] + scale[1])) * sg["T"][k]
+            return np.minimum(tl, th), np.maximum(tl, th), tm
+
+        def shadow(k, ray, tmax):
+            """Shadow rays of the hits k along `ray` -> unoccluded [len k]."""
+            nonlocal rays
+            rays += k.size if sg["run"] == 0 else 0
+            if not k.size:
+                return np.zeros(0, bool)
+            h = closest_hit(tris, sg["P"][k], ray, sg["tri_of"][k], tmax=tmax, widen=sg["amp"][k])
+            flags[px[k]] |= h["flags"] & (FLAG_EDGE | FLAG_TMIN)
+            count(lev, "occluded", h["valid"].sum())
+            return ~h["valid"]
+
+        def add(k, tl, th, tm):
+            lo[img, px[k]] += tl; hi[img, px[k]] += th; term[img, px[k]] = True
             if sg["run"] == 0:      # the value itself, no error carried (the specular lobe: the middle of its D_SLACK interval)
-                mid[img, px[k]] += np.where(mirror[k][:, None], 0.5 * (sl + sh), dt) * (0.5 * (scale[0] + scale[1])) * sg["T"][k]
+                mid[img, px[k]] += tm
             for c, name in enumerate(LOBES):
                 count(lev, name, (lobe[k] == c).sum())
 
-        every = np.ones(len(px), bool)
-        if sun is not None:
-            L, E = np.asarray(sun[0], np.float64), np.asarray(sun[1], np.float64)
-            NoL, live = facing(np.broadcast_to(L, (len(px), 3)), every)
-            k = np.nonzero(live)[0]
-            lit(k, np.broadcast_to(L, (k.size, 3)), NoL[k], RAY_TMAX, (np.broadcast_to(E, (k.size, 3)),) * 2)
-        for lt in lights:
+        def lit(k, L, NoL, tmax, scale, ray=None):
+            """Shadow rays of the hits k along `ray` (default: the centre direction L); the unoccluded ones' terms x scale x T into S."""
+            keep = shadow(k, L if ray is None else ray, tmax)
+            if k.size:
+                k, L, NoL, scale = k[keep], L[keep], NoL[keep], (scale[0][keep], scale[1][keep])
+                add(k, *terms(k, L, NoL, scale))
+
+        def reach(lt):
+            """Steps 1-4 of a light at the segment's hits -> (live, D, d2, L, NoL, (scale_lo, scale_hi) [n 3])."""
             I = np.asarray(lt["intensity"], np.float64)
-            if not (I > 0).any():
-                continue
-            assert lt.get("radius", 0.0) == 0.0
             R = float(np.float32(lt["range"]))
             D = np.asarray(lt["position"], np.float32).astype(np.float64) - sg["P"]
             d2 = _dot(D, D)
@@ -912,8 +1350,80 @@ def hits_pass(scene, fc_bytes, m, sun=None, lights=()):
                 live = live & (c > co)
                 ci = float(np.float32(lt["cos_inner"]))
                 spot = (light_spot(c - err, co, ci), light_spot(c + err, co, ci))
+            rho = float(np.float32(lt.get("radius", 0.0)))
+            with np.errstate(invalid="ignore", divide="ignore"):
+                scale = tuple(I * light_attenuation(d2, R, rho, sp)[:, None] for sp in spot)
+            return live, D, d2, L, NoL, scale
+
+        def target(lt, i, k, D, d2):
+            """Steps 5-6 at the hits k: the target from the light's own slot -> (ray exists [len k], Ls, tmax)."""
+            rho = float(np.float32(lt.get("radius", 0.0)))
+            Ds = D[k]
+            if rho > 0.0:
+                u, phi = target_draw(slot_words(px[k], F, light_hit_slot(lev, img, i)))
+                Ds = Ds + rho * sphere_point(u, phi)
+            ds2 = _dot(Ds, Ds)
+            flags[px[k]] |= np.where(np.abs(ds2 - 1e-6) <= DS2_EPS, FLAG_TARGET, 0)
+            some = ds2 >= 1e-6
+            with np.errstate(invalid="ignore", divide="ignore"):
+                Ls = _unit(Ds)
+            go = some.copy()
+            if rho > 0.0 and some.any():
+                go[some] = above(k[some], Ls[some])
+            return go, Ls, np.sqrt(ds2)
+
+        every = np.ones(len(px), bool)
+        if sun is not None:
+            L, E = np.asarray(sun[0], np.float64), np.asarray(sun[1], np.float64)
+            NoL, live = facing(np.broadcast_to(L, (len(px), 3)), every)
             k = np.nonzero(live)[0]
-            lit(k, L[k], NoL[k], np.sqrt(d2[k]), tuple(I * light_attenuation(d2[k], R, 0.0, sp[k])[:, None] for sp in spot))
+            ray = None
+            if sun_angle > 0.0 and k.size:
+                kk, T, B = sun_disk_host(L, sun_angle)
+                u, phi = target_draw(slot_words(px[k], F, sun_slot(lev, img)))
+                ray = sun_disk_direction(L, kk, T, B, u, phi)
+                keep = above(k, ray)
+                k, ray = k[keep], ray[keep]
+            lit(k, np.broadcast_to(L, (k.size, 3)), NoL[k], RAY_TMAX, (np.broadcast_to(E, (k.size, 3)),) * 2, ray)
+        cast = [(i, lt) for i, lt in enumerate(lights) if (np.asarray(lt["intensity"], np.float64) > 0).any()]
+        if mode == 0:
+            for i, lt in cast:
+                live, D, d2, L, NoL, scale = reach(lt)
+                k = np.nonzero(live)[0]
+                go, Ls, tmax = target(lt, i, k, D, d2)
+                k = k[go]
+                lit(k, L[k], NoL[k], tmax[go], (scale[0][k], scale[1][k]), Ls[go])
+        elif cast:
+            ns = len(px)
+            s_lo, s_hi, s_mid = [np.zeros((len(lights), ns, 3)) for _ in range(3)]
+            held = {}
+            for i, lt in cast:
+                live, D, d2, L, NoL, scale = reach(lt)
+                k = np.nonzero(live)[0]
+                held[i] = (D, d2)
+                if k.size:
+                    s_lo[i, k], s_hi[i, k], s_mid[i, k] = terms(k, L[k], NoL[k], (scale[0][k], scale[1][k]))
+            w_lo, w_hi, w_mid = luminance(s_lo), luminance(s_hi), luminance(s_mid)
+            flags[px] |= np.where(((w_hi > 0.0) & (w_lo < TINY_WEIGHT)).any(axis=0), FLAG_WEIGHT, 0)
+            x = pick_draw(slot_words(px, F, pick_hit_slot(lev, img)))
+            chosen, W, _ = pick_choice(x, w_mid)
+            flags[px] |= np.where(_pick_boundary_flags(x, w_lo, w_mid, w_hi), FLAG_PICK, 0)
+            count(lev, "candidates", (chosen >= 0).sum())
+            count(lev, "two_candidates", ((w_mid > 0).sum(axis=0) >= 2).sum())
+            for i, lt in cast:
+                k = np.nonzero(chosen == i)[0]
+                if not k.size:
+                    continue
+                go, Ls, tmax = target(lt, i, k, *held[i])
+                k, Ls, tmax = k[go], Ls[go], tmax[go]
+                keep = shadow(k, Ls, tmax)
+                if k.size:
+                    k = k[keep]
+                    others_lo, others_hi = w_lo[:, k].sum(axis=0) - w_lo[i, k], w_hi[:, k].sum(axis=0) - w_hi[i, k]
+                    with np.errstate(invalid="ignore", divide="ignore"):      # (a lower end of 0: flagged FLAG_WEIGHT above)
+                        f_lo, f_hi, f_mid = 1.0 + others_lo / w_hi[i, k], 1.0 + others_hi / w_lo[i, k], W[k] / w_mid[i, k]
+                    add(k, s_lo[i, k] * f_lo[:, None], s_hi[i, k] * f_hi[:, None], s_mid[i, k] * f_mid[:, None])
+                    count(lev, "chosen_from_8", (i >= 8) * k.size)
     # the hull of the three runs (frame(): the sampler roots' slack 0, -, +), flagged where they do not agree on which terms exist
     lo, hi, term = np.minimum.reduce([r[0] for r in runs]), np.maximum.reduce([r[1] for r in runs]), runs[0][2]
     flags |= np.where(((runs[1][2] != term) | (runs[2][2] != term)).any(axis=0), FLAG_CANCEL, 0)

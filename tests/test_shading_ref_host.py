@@ -158,7 +158,8 @@ def check_direct_stage(label, before, after, p, bounds):
     """One pass against the model: the words `after` it from the words `before` it.  -> {image: (allowance used, values compared)}."""
     ok = p["flags"] == 0
     used = {}
-    for name, key, lo_t, hi_t, where in (("RayTracingOut0", "refl", p["spec_lo"], p["spec_hi"], p["term"]), ("RayTracingOut1", "diff", p["diff"], p["diff"], p["diffuse"])):
+    for name, key, lo_t, hi_t, where in (("RayTracingOut0", "refl", p["spec_lo"], p["spec_hi"], p["term"]),
+                                         ("RayTracingOut1", "diff", p.get("diff_lo", p["diff"]), p.get("diff_hi", p["diff"]), p["diffuse"])):
         base = R.unpack_r11g11b10(before[key])
         lo, hi = base + lo_t, base + hi_t
         delta = bounds[key]["max"] * MARGIN * R.ulp32(np.maximum(np.abs(lo), np.abs(hi)).max(axis=-1))
