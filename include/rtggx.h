@@ -867,7 +867,8 @@ int  rtggx_set_light_sampling(rtggx_context* ctx, int mode);
  * both traced images are a pure function of the frame sequence.
  * Known limits: the hits are not covered (a path's hit has no velocity to follow); the floor means a light that leaves shadow is noticed
  * only at 1/16 of its share; the estimates are per pixel and not filtered over neighbours.  tests/light_vis_ref.cpp restates the rule.
- * It does not act on a light list (rtggx_set_light_list): a record has eight bytes, a list up to 1024 lights. */
+ * It does not act on a light list (rtggx_set_light_list): a record has eight bytes, a list up to 1024 lights --
+ * rtggx_set_light_list_visibility is the list's own, with a sparse record. */
 #define RTGGX_LIGHT_VIS_FLOOR 16u      /* policy default, not a measurement */
 typedef struct RtggxLightVisRecord {   /* 16 bytes */
   uint8_t  v[8];      /* v[i]: visibility estimate of light i, 0 .. 255 */
@@ -900,7 +901,7 @@ int  rtggx_read_light_visibility(rtggx_context* ctx, uint32_t image /* 0, 1 */, 
  * The sums, the resolve, the order (the sun first, then this one term, level by level), the queue formats, strips (pixel is the full-frame
  * index), deforming meshes, caller-owned streams and rtggx_set_async_compute(0) are mode 1's.  With n <= 8 the images and the ray count
  * are those of the same lights through rtggx_set_lights in mode 1.  rtggx_set_light_pick_visibility does not act on a list: its records
- * have eight bytes.
+ * have eight bytes; rtggx_set_light_list_visibility, further down, does.
  * The cull.  Per 8x8 block of the primary pass, over the block's covered pixels in the pass's rows: lo_c / hi_c are the fp32 minimum /
  * maximum of P_c, the P of step 0.  Per light k that casts rays (an intensity component is not 0), in fp32 without contraction, each
  * operation rounded on its own:
@@ -916,7 +917,7 @@ int  rtggx_read_light_visibility(rtggx_context* ctx, uint32_t image /* 0, 1 */, 
  * Per frame one generating launch, one any-hit traversal and one add, and per level and sample of the hits likewise, whatever n.  Memory: 80
  * bytes per light, mode 1's queue, sums and diffuse terms, and 4 bytes per 8x8 block for the counts below.
  * Known limits: no culling by cone or by facing; no world-space grid for the hits, whose points are incoherent (a round's box can be large:
- * the cull there saves less); no visibility records for lists; lights that move need a new call; no more than 1024 lights. */
+ * the cull there saves less); visibility records at the primary pass only (rtggx_set_light_list_visibility); lights that move need a new call; no more than 1024 lights. */
 #define RTGGX_MAX_LIGHT_LIST 1024u
 int  rtggx_set_light_list(rtggx_context* ctx, const RtggxLight* lights, uint32_t count);
 /* Synchronises and copies, row-major by 8x8 block, the number of kept lights of the last frame's primary pass: ceil(H/8) rows of ceil(W/8)
@@ -927,6 +928,65 @@ int  rtggx_read_light_list_counts(rtggx_context* ctx, uint32_t* out, size_t byte
 /* 1 (default): the cull.  0: every casting light is kept in every block that has a covered pixel (the hits: a touched hit) -- the same
  * images and ray counts, the counts equal to the number of casting lights, the time of a walk over all lights.  Anything else is refused. */
 int  rtggx_debug_light_list_cull(rtggx_context* ctx, int enable);   /* 1 (default) / 0: keep every casting light */
+
+/* A list's pick weighted by what the pixel remembers: rtggx_set_light_pick_visibility for a light list.  A record cannot hold a value per
+ * light of a list of 1024, so it is sparse: the few lights the pixel has learned are hidden, four entries, and nothing for the rest -- a
+ * light without an entry is believed visible.  Every candidate keeps a non-zero probability and the term is divided by that probability: the
+ * expectation is the list's own sum whatever the history holds, stale, wrong or arbitrary bytes -- a bad record costs variance, never bias.
+ * One more 16-byte load and store per pixel, no new ray and no new launch.
+ * enable 0 (default) / 1; anything else is refused and the setting kept.  The setting is stored always.  It acts only in frames whose primary
+ * pass runs a list (rtggx_set_light_list) with at least one casting light -- an acting frame --, and takes effect with the next
+ * rtggx_render_visibility.  The hit passes under rtggx_set_light_reflections keep the list's rule unchanged.  rtggx_set_lights (modes 0 and
+ * 1) and rtggx_set_light_pick_visibility are untouched: this setting does not act on them, nor that one on a list.  Opt-in: a context that
+ * never enables it allocates and launches exactly what it did.  Whole frames only, because a reprojected tap may lie in another rank's rows:
+ * enabling on a context with a strip is refused, and so is rtggx_set_strip with a strip on an enabled context.  The first acting frame
+ * allocates two images of W x H records (RtggxLightListVisRecord, 16 bytes), zeroed, released by rtggx_destroy.
+ * The sequence.  s counts this setting's acting frames and starts at 0 (it is not rtggx_set_light_pick_visibility's s); an acting frame
+ * first does s = s + 1.  s0 is the value of s at the last reset; resets are: the allocation, every successful rtggx_set_light_list, and every
+ * change of this setting.  The frame writes image s & 1 and reads image (s - 1) & 1.  Behaviour after s passes 2^24 is not specified.
+ * An entry is 16 bits: (v << 10) | light with v in 0 .. 62 and light in 0 .. 1023; 0xFFFF is a free entry (v = 63 is never stored by the
+ * update: a light that reaches 63 leaves the record).  An entry other than 0xFFFF whose v field reads 63 -- arbitrary bytes can hold one --
+ * is an entry like any other.
+ * Per covered pixel (x, y) of the primary pass, in fp32 without contraction, each operation rounded on its own, with the operator definitions
+ * of rtggx_set_lights:
+ *   1. step 0 and the candidates w_i exactly as the list's primary pass has them (rtggx_set_light_sampling's steps 0-1 with i running over
+ *      the list);
+ *   2. the history, word for word step 2 of rtggx_set_light_pick_visibility: qx = floor(((float)x + 0.5f) - vx (float)W), qy likewise with H,
+ *      from the frame's own RTGGX_BUF_VELOCITY word; R is the record at (qx, qy) of the image read.  The history is valid iff s - 1 > s0;
+ *      0 <= qx < W and 0 <= qy < H; R.stamp >> 8 == (s - 1) & 0xFFFFFF; (R.stamp & 0xFF) == inst + 1; and I >= 0.9f * 1046529.0f with I the
+ *      integer dot of the two normal words' 2 q_k - 1023.  If valid the four entries are R's; otherwise all four are free;
+ *   3. the weights.  v_i is the v of the entry, not free, whose light field equals i -- the one of lowest index k, should two name the same
+ *      light, which the update never produces -- and 63 where there is none.  u_i = w_i (float)max(v_i, RTGGX_LIGHT_LIST_VIS_FLOOR) for the
+ *      candidates.  U = ((+0 + u_a) + u_b) + ..., ascending.  The record is written in every case, whether or not there is a candidate: the
+ *      carried entries, this pixel's normal word, and stamp = (s & 0xFFFFFF) << 8 | (inst + 1).  With no candidate there is no ray and no term;
+ *   4. draw, pick and f are the list's with u in place of w and U in place of W: slot 96, "the first candidate with t < c, else the last",
+ *      f = U / u_i.  With a single candidate f is exactly 1;
+ *   5. target, ray and term are the list's, unchanged, with the list's hash slots: S0 = spec_i f, S1 = diff_i f;
+ *   6. the update, only where a shadow ray was traced ("no ray" -- below the horizon, ds2 < 1e-6 -- leaves the entries as carried).  For the
+ *      chosen light i, in integers: k is the slot whose entry, not free, holds i (the lowest such k); v is that entry's, or 63 if there is no
+ *      such slot.  unoccluded v' = v + ((63 - v + 3) >> 2); occluded v' = v - ((v + 3) >> 2).  0 and 63 are reached exactly and are fixed
+ *      points.  If the slot exists it becomes 0xFFFF when v' == 63, else (v' << 10) | i.  If no slot exists and the ray is occluded (v' =
+ *      47), the entry (47 << 10) | i is inserted: into the free slot of lowest k; with no free slot, in place of the entry of greatest v,
+ *      ties to the lowest k.  If no slot exists and the ray is unoccluded nothing changes.  The other slots keep the carried value.
+ * Pixels that are not covered write nothing, and neither do waves that leave on a zero tile word; the stamp keeps their old records from
+ * being read as history.  There are no atomics: a pixel writes only its own record and reads only the other image; records and images are a
+ * pure function of the frame sequence.  The cull stays invisible: a light that is not kept has w_i = +0 and is no candidate, its entry, if
+ * any, is simply carried; images, ray counts AND records are those of the walk over all lights, bit for bit, with
+ * rtggx_debug_light_list_cull(ctx, 0) as with the cull on.  With one casting light the images are the list's own.
+ * Known limits: the hits are not covered; four entries per pixel -- a fifth hidden light evicts the least hidden; the floor means a light
+ * that leaves shadow is noticed at 1/16 of its share; records are per pixel and not filtered over neighbours; strips are refused; lights
+ * that move need a new rtggx_set_light_list, which is a reset.  tests/light_list_vis_ref.cpp restates the rule over all lights. */
+#define RTGGX_LIGHT_LIST_VIS_ENTRIES 4u
+#define RTGGX_LIGHT_LIST_VIS_FLOOR   4u      /* policy default, not a measurement: 1/16 of 63, as RTGGX_LIGHT_VIS_FLOOR is of 255 */
+typedef struct RtggxLightListVisRecord {     /* 16 bytes */
+  uint16_t entry[4];   /* (v << 10) | light: v 0..62, light 0..1023; 0xFFFF: free */
+  uint32_t normal;     /* the frame's RTGGX_BUF_NORMAL word of the pixel */
+  uint32_t stamp;      /* (s & 0xFFFFFF) << 8 | (inst + 1); 0: never written */
+} RtggxLightListVisRecord;
+int  rtggx_set_light_list_visibility(rtggx_context* ctx, int enable);      /* 0 (default) / 1; anything else refused, setting kept */
+/* Synchronises and copies image 0 or 1 of the records (W x H, row by row) to out; *sequence (may be NULL) receives this setting's s.  It
+ * fails before anything is allocated (before the first acting frame), for an image other than 0 or 1, and when bytes is not W H 16. */
+int  rtggx_read_light_list_visibility(rtggx_context* ctx, uint32_t image /* 0, 1 */, RtggxLightListVisRecord* out, size_t bytes, uint32_t* sequence);
 
 /* The sun from the environment: finds the sun in the current cube, measures its direction and irradiance -- what rtggx_set_sun wants -- and,
  * where asked, takes it out of the cube, so that a probe with a sun in it does not light the scene twice (once analytically, with shadows, and

@@ -21,7 +21,8 @@ HOST_EXPORTS = ["rtggx_app_last_error", "rtggx_app_create", "rtggx_app_destroy",
                 "rtggx_app_save_reference", "rtggx_app_flush_scores", "rtggx_app_set_reference", "rtggx_app_set_scoring", "rtggx_app_read_scores",
                 "rtggx_host_write_pfm", "rtggx_host_read_pfm", "rtggx_host_load_env_image",
                 "rtggx_app_set_sample_map", "rtggx_app_set_lights", "rtggx_app_set_light_reflections", "rtggx_app_set_light_sampling",
-                "rtggx_app_set_light_pick_visibility", "rtggx_app_set_light_list"]
+                "rtggx_app_set_light_pick_visibility", "rtggx_app_set_light_list",
+                "rtggx_app_set_light_list_visibility"]
 
 _lib = None
 
@@ -63,6 +64,7 @@ def load():
         L.rtggx_app_set_light_sampling.argtypes = [C.c_void_p, C.c_int]
         L.rtggx_app_set_light_pick_visibility.argtypes = [C.c_void_p, C.c_int]
         L.rtggx_app_set_light_list.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.rtggx_app_set_light_list_visibility.argtypes = [C.c_void_p, C.c_int]
         L.rtggx_app_last_screen_shot.argtypes = [C.c_void_p]
         L.rtggx_app_last_screen_shot.restype = C.c_char_p
         L.rtggx_host_obj_import.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p]
@@ -298,6 +300,11 @@ class RayTracedGGX:
     def set_light_pick_visibility(self, enable):
         """RayTracer::SetLightPickVisibility: the pick of mode 1 weighted by the visibility each pixel remembers (0 / 1), from the next frame on."""
         if self.L.rtggx_app_set_light_pick_visibility(self.h, int(enable)) != 0:
+            raise capi.RtggxError(self.L.rtggx_app_last_error().decode())
+
+    def set_light_list_visibility(self, enable):
+        """RayTracer::SetLightListVisibility: the list's pick weighted by the sparse record each pixel keeps (0 / 1), from the next frame on."""
+        if self.L.rtggx_app_set_light_list_visibility(self.h, int(enable)) != 0:
             raise capi.RtggxError(self.L.rtggx_app_last_error().decode())
 
     def set_scoring(self, enable):

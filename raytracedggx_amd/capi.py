@@ -46,7 +46,8 @@ EXPORTS = ["rtggx_last_error", "rtggx_create", "rtggx_destroy", "rtggx_set_strip
            "rtggx_set_sample_map", "rtggx_read_sample_map", "rtggx_trace_occlusion", "rtggx_set_sun", "rtggx_set_sun_reflections",
            "rtggx_sun_from_env", "rtggx_set_sun_angle", "rtggx_set_lights", "rtggx_set_light_reflections", "rtggx_set_light_sampling",
            "rtggx_set_light_pick_visibility", "rtggx_read_light_visibility",
-           "rtggx_set_light_list", "rtggx_read_light_list_counts", "rtggx_debug_light_list_cull"]
+           "rtggx_set_light_list", "rtggx_read_light_list_counts", "rtggx_debug_light_list_cull",
+           "rtggx_set_light_list_visibility", "rtggx_read_light_list_visibility"]
 SCORE_RING = 256
 
 
@@ -97,6 +98,9 @@ class Light(C.Structure):
 LIGHT_VIS_FLOOR = 16      # RTGGX_LIGHT_VIS_FLOOR
 # RtggxLightVisRecord (rtggx.h), 16 bytes: eight visibility bytes, the pixel's normal word, the stamp
 LIGHT_VIS_RECORD = np.dtype([("v", np.uint8, 8), ("normal", np.uint32), ("stamp", np.uint32)])
+LIGHT_LIST_VIS_ENTRIES, LIGHT_LIST_VIS_FLOOR = 4, 4      # RTGGX_LIGHT_LIST_VIS_ENTRIES, RTGGX_LIGHT_LIST_VIS_FLOOR
+# RtggxLightListVisRecord (rtggx.h), 16 bytes: four entries (v << 10) | light (0xFFFF: free), the pixel's normal word, the stamp
+LIGHT_LIST_VIS_RECORD = np.dtype([("entry", np.uint16, 4), ("normal", np.uint32), ("stamp", np.uint32)])
 
 _lib = None
 
@@ -173,6 +177,8 @@ def load():
     L.rtggx_set_light_list.argtypes = [vp, C.POINTER(Light), C.c_uint32]
     L.rtggx_read_light_list_counts.argtypes = [vp, vp, C.c_size_t]
     L.rtggx_debug_light_list_cull.argtypes = [vp, C.c_int]
+    L.rtggx_set_light_list_visibility.argtypes = [vp, C.c_int]
+    L.rtggx_read_light_list_visibility.argtypes = [vp, C.c_uint32, vp, C.c_size_t, C.POINTER(C.c_uint32)]
     L.rtggx_sun_from_env.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_int, C.POINTER(SunEstimate)]
     L.rtggx_ray_total.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
     L.rtggx_kernel_times.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
@@ -688,6 +694,19 @@ class Context:
     def debug_light_list_cull(self, enable):
         """1 (default): the list's cull; 0: every casting light is kept in every block that has a point -- the same images, the walk's time."""
         self._check(self.L.rtggx_debug_light_list_cull(self.h, int(enable)))
+
+    def set_light_list_visibility(self, enable):
+        """A list's pick weighted by the sparse record each pixel keeps of the lights it found hidden (0 / 1; include/rtggx.h has the rule).
+        From the next frame on; it acts only in frames with a list that has a casting light; whole frames only."""
+        self._check(self.L.rtggx_set_light_list_visibility(self.h, int(enable)))
+
+    def read_light_list_visibility(self, image):
+        """(records, sequence): image 0 or 1 of the list's records as a LIGHT_LIST_VIS_RECORD array [H, W], and the setting's s.  Raises
+        before the first acting frame."""
+        a = np.zeros((self.H, self.W), LIGHT_LIST_VIS_RECORD)
+        seq = C.c_uint32()
+        self._check(self.L.rtggx_read_light_list_visibility(self.h, int(image), _p(a), a.nbytes, C.byref(seq)))
+        return a, seq.value
 
     def sun_from_env(self, cone=0, ring=0, min_contrast=0, remove=False):
         """The sun of the current environment (include/rtggx.h): the record as a dict (SunEstimate.as_dict) -- "direction" and "irradiance" are

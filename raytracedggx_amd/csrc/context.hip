@@ -240,6 +240,7 @@ int rtggx_set_strip(rtggx_context* c, uint32_t rowBegin, uint32_t rowEnd) {
   if (c->rayRate != 1u && (rowBegin > 0u || rowEnd < c->H)) { setError("rtggx_set_strip: rows [%u,%u) of %u: a context tracing one pixel in %u renders whole frames", rowBegin, rowEnd, c->H, c->rayRate); return -1; }
   if ((c->sampleMap >= 0 || c->sampleMapRequested >= 0) && (rowBegin > 0u || rowEnd < c->H)) { setError("rtggx_set_strip: rows [%u,%u) of %u on a context with a sample map (rtggx_set_sample_map): a strip's tiles count from its first row, a block would no longer be a bin -- whole frames only", rowBegin, rowEnd, c->H); return -1; }
   if ((c->lightVis || c->lightVisRequested) && (rowBegin > 0u || rowEnd < c->H)) { setError("rtggx_set_strip: rows [%u,%u) of %u on a context with the pick's visibility records (rtggx_set_light_pick_visibility): a reprojected tap may lie in another rank's rows -- whole frames only", rowBegin, rowEnd, c->H); return -1; }
+  if ((c->lightListVis || c->lightListVisRequested) && (rowBegin > 0u || rowEnd < c->H)) { setError("rtggx_set_strip: rows [%u,%u) of %u on a context with a list's visibility records (rtggx_set_light_list_visibility): a reprojected tap may lie in another rank's rows -- whole frames only", rowBegin, rowEnd, c->H); return -1; }
   c->rowBegin = rowBegin; c->rowEnd = rowEnd; c->toneMapDone = false;
   c->sky.breakRuns(SkyBreak::Strip);
   return 0;
@@ -526,6 +527,7 @@ int rtggx_set_light_list(rtggx_context* c, const RtggxLight* lights, uint32_t co
     if (checkLight("rtggx_set_light_list", i, l)) return -1;
     next.l[i] = l;
   }
+  c->lightListVisSeq0 = c->lightListVisSeq;      // rtggx_set_light_list_visibility: a reset -- the next acting frame has no valid history
   if (!count && !c->lightListRequested.count) return 0;      // nothing held, nothing asked for: the context stays as it is
   next.count = count;
   next.version = ++c->lightListVersions;
@@ -590,6 +592,27 @@ int rtggx_read_light_visibility(rtggx_context* c, uint32_t image, RtggxLightVisR
   RT_HIP(syncStreams(c));
   RT_HIP(hipMemcpy(out, c->lightVisImg[image], want, hipMemcpyDeviceToHost));
   if (sequence) *sequence = c->lightVisSeq;
+  return 0;
+}
+// A list's pick weighted by the pixel's sparse record (include/rtggx.h): rtggx_set_light_pick_visibility's setter and reader for the list's
+// own setting, sequence and images (the first acting frame allocates them: lighting.hip launchLights)
+int rtggx_set_light_list_visibility(rtggx_context* c, int enable) {
+  RT_CHECK_CTX(c);
+  if (enable != 0 && enable != 1) { setError("rtggx_set_light_list_visibility: %d: 0 or 1", enable); return -1; }
+  if (enable == 1 && (c->rowBegin > 0u || c->rowEnd < c->H)) { setError("rtggx_set_light_list_visibility: on a strip (rows [%u,%u) of %u): a reprojected tap may lie in another rank's rows -- whole frames only", c->rowBegin, c->rowEnd, c->H); return -1; }
+  if ((enable == 1) != c->lightListVisRequested) c->lightListVisSeq0 = c->lightListVisSeq;
+  c->lightListVisRequested = enable == 1;
+  return 0;
+}
+int rtggx_read_light_list_visibility(rtggx_context* c, uint32_t image, RtggxLightListVisRecord* out, size_t bytes, uint32_t* sequence) {
+  RT_CHECK_CTX(c);
+  if (image > 1u) { setError("rtggx_read_light_list_visibility: image %u: 0 or 1", image); return -1; }
+  if (!c->lightListVisImg[image]) { setError("rtggx_read_light_list_visibility: no records yet: they exist from the first frame of a list with a casting light and rtggx_set_light_list_visibility(ctx, 1)"); return -1; }
+  const size_t want = (size_t)c->W * c->H * sizeof(RtggxLightListVisRecord);
+  if (!out || bytes != want) { setError("rtggx_read_light_list_visibility: %zu bytes at %p: %u x %u records of 16 bytes are %zu", bytes, (void*)out, c->W, c->H, want); return -1; }
+  RT_HIP(syncStreams(c));
+  RT_HIP(hipMemcpy(out, c->lightListVisImg[image], want, hipMemcpyDeviceToHost));
+  if (sequence) *sequence = c->lightListVisSeq;
   return 0;
 }
 // Sums and count back to zero: two clears on the main stream, behind the frames it holds and in front of the next one; nothing waits.

@@ -195,7 +195,7 @@ int rtggx_render_visibility(rtggx_context* c) {
   if (!c->shDone && c->env.texels) { const int r = projectSH(c, c->streamAS); if (r) return r; }   // first frame only, RayTracer.cpp:345-350
   settleSetRead(c);      // (the previous frame ended without the kernel that would have carried its set's event)
   ++c->frameCounter;
-  c->maxDepth = c->depthRequested; c->samples = c->samplesRequested; c->accumulate = c->accumulateRequested; c->sun = c->sunRequested; c->sunAngle = c->sunAngleRequested; c->sunReflections = c->sunReflectionsRequested; c->lights = c->lightsRequested; c->lightReflections = c->lightReflectionsRequested; c->lightSampling = c->lightSamplingRequested; c->lightVis = c->lightVisRequested;
+  c->maxDepth = c->depthRequested; c->samples = c->samplesRequested; c->accumulate = c->accumulateRequested; c->sun = c->sunRequested; c->sunAngle = c->sunAngleRequested; c->sunReflections = c->sunReflectionsRequested; c->lights = c->lightsRequested; c->lightReflections = c->lightReflectionsRequested; c->lightSampling = c->lightSamplingRequested; c->lightVis = c->lightVisRequested; c->lightListVis = c->lightListVisRequested;
   if (c->lightList.version != c->lightListRequested.version) {      // rtggx_set_light_list: the new list, and its copy on the device
     RT_HIP(syncStreams(c));      // (a frame in flight may read the list the upload replaces)
     c->lightList = c->lightListRequested;

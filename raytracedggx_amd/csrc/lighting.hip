@@ -1,7 +1,8 @@
 // Direct lighting: the sun (rtggx_set_sun, rtggx_set_sun_angle), the local lights (rtggx_set_lights) and both at the surfaces the paths hit
 // (rtggx_set_sun_reflections, rtggx_set_light_reflections); one shadow ray for all lights (rtggx_set_light_sampling: the two picking kernels
 // further down, with a table of their own; rtggx_set_light_pick_visibility: the primary pair of them once more, with a record per pixel);
-// a list of up to 1024 lights in device memory, culled per block (rtggx_set_light_list: the last pair of generating kernels).
+// a list of up to 1024 lights in device memory, culled per block (rtggx_set_light_list: the last pair of generating kernels; its primary
+// kernel once more with a sparse record per pixel: rtggx_set_light_list_visibility).
 // include/rtggx.h has the per-pixel rules, DESIGN.md section 9 the structure.
 //
 // Every pass is the same three launches around a queue of its own (rt::ShadowQueue, rt_queue.h): a generating kernel derives a surface --
@@ -730,7 +731,8 @@ static LightListArgs pickList(const rtggx_context* c) {
 static void (*const kLightPickGen[4])(const FrameParams*, LightPickGenArgs) = {lightPickGenKernel<false, false>, lightPickGenKernel<false, true>, lightPickGenKernel<true, false>, lightPickGenKernel<true, true>};
 static void (*const kLightPickVisGen[4])(const FrameParams*, LightPickGenArgs, LightVisArgs) = {lightPickVisGenKernel<false, false>, lightPickVisGenKernel<false, true>, lightPickVisGenKernel<true, false>, lightPickVisGenKernel<true, true>};
 static int clearLightListCounts(rtggx_context* c, hipStream_t s);      // rtggx_set_light_list, further down
-static int launchLightListGen(rtggx_context* c, hipStream_t s, const LightPickGenArgs& P, uint32_t numTiles);
+static int launchLightListGen(rtggx_context* c, hipStream_t s, const LightPickGenArgs& P, uint32_t numTiles, const LightVisArgs* records);
+__global__ void __launch_bounds__(256) lightListVisAddKernel(const FrameParams* __restrict__ fpp, LightPickAddArgs A, uint32_t* records);      // rtggx_set_light_list_visibility, further down
 
 int launchLights(rtggx_context* c, const FrameParams& fp, hipStream_t s) {
   uint32_t rb, re;
@@ -764,8 +766,25 @@ int launchLights(rtggx_context* c, const FrameParams& fp, hipStream_t s) {
     P.tileWords = G.tileWords; P.tilesX = tilesX; P.rowBegin = rb; P.rowEnd = re;
     if (list) {      // rtggx_set_light_list: the same three launches (none where no light of the list has an intensity) and the resolve
       { const int r = clearLightListCounts(c, s); if (r) return r; }
-      if (c->lightListCasting) {
-        { const int r = launchLightListGen(c, s, P, numTiles); if (r) return r; }
+      if (c->lightListCasting && c->lightListVis) {      // rtggx_set_light_list_visibility: an acting frame -- the same three launches with the records
+        if (rb > 0u || re < fp.H) { setError("rtggx_ray_trace: the list's visibility records on rows [%u,%u) of %u: whole frames only", rb, re, fp.H); return -1; }
+        if (!c->lightListVisImg[0] || !c->lightListVisImg[1]) {      // the allocation is a reset
+          for (auto& img : c->lightListVisImg) if (!img) RT_HIP(allocFilled(img, (size_t)c->W * c->H * 4u));
+          { const int r = syncFills(true); if (r) return r; }
+          c->lightListVisSeq0 = c->lightListVisSeq;
+        }
+        const uint32_t seq = ++c->lightListVisSeq;
+        LightVisArgs R;
+        R.normal = set.normal; R.velocity = set.velocity;
+        R.prev = (const uint4*)c->lightListVisImg[(seq - 1u) & 1u].get(); R.next = (uint4*)c->lightListVisImg[seq & 1u].get();
+        R.prevSeq = (seq - 1u) & 0xFFFFFFu; R.stampHigh = (seq & 0xFFFFFFu) << 8; R.history = seq - 1u > c->lightListVisSeq0 ? 1u : 0u;
+        { const int r = launchLightListGen(c, s, P, numTiles, &R); if (r) return r; }
+        { const int r = launchTrace(c, fp, s, q, numTiles * 4u, true, tilesX, tilesY, c->traceGrid[3], -1, nullptr, nullptr, 2, true); if (r) return r; }
+        const LightPickAddArgs PD{q.rays, q.hits, q.binCount, G.tileWords, P.diffTerm, D.sumRefl, D.sumDiff};
+        launch(lightListVisAddKernel, dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, PD, (uint32_t*)R.next);
+        RT_HIP(hipGetLastError());
+      } else if (c->lightListCasting) {
+        { const int r = launchLightListGen(c, s, P, numTiles, nullptr); if (r) return r; }
         { const int r = launchTrace(c, fp, s, q, numTiles * 4u, true, tilesX, tilesY, c->traceGrid[3], -1, nullptr, nullptr, 2, true); if (r) return r; }
         const LightPickAddArgs PD{q.rays, q.hits, q.binCount, G.tileWords, P.diffTerm, D.sumRefl, D.sumDiff};
         launch(lightPickAddKernel, dim3(numTiles), dim3(256), s, nullptr, nullptr, dfp, PD);
@@ -1148,6 +1167,157 @@ __global__ void __launch_bounds__(256) lightListHitGenKernel(const FrameParams* 
 }
 static void (*const kLightListGen[4])(const FrameParams*, const LightRecord*, const float4*, LightListGenArgs) = {lightListGenKernel<false, false>, lightListGenKernel<false, true>, lightListGenKernel<true, false>, lightListGenKernel<true, true>};
 static void (*const kLightListHitGen[4])(const FrameParams*, const LightRecord*, const float4*, LightListHitGenArgs) = {lightListHitGenKernel<false, false>, lightListHitGenKernel<false, true>, lightListHitGenKernel<true, false>, lightListHitGenKernel<true, true>};
+// ---- a list's pick and what the pixel remembers (rtggx_set_light_list_visibility; DESIGN.md section 9 "What a pixel remembers of a list") ------
+// lightListGenKernel and lightPickAddKernel once more, with a sparse record per pixel (RtggxLightListVisRecord: four 16-bit entries
+// (v << 10) | light, 0xFFFF free, the normal word, a stamp) in two images that alternate by the feature's own sequence number:
+// lightListVisGenKernel follows the frame's velocity word as lightPickVisGenKernel does, carries the four entries where the record is the
+// previous acting frame's, that instance's and of a like normal (all free otherwise), writes the pixel's own record and multiplies every
+// candidate's weight by max(v_i, RTGGX_LIGHT_LIST_VIS_FLOOR), v_i = 63 where no entry names light i.  The walk's index is the wave's scalar:
+// a lane finds v_i with four compares of it against the fields of its own two entry words -- nothing is indexed by a lane's value.  The
+// chosen index (10 bits) travels in the shadow ray's flags word; lightListVisAddKernel moves the chosen light's v a quarter of the way to 63
+// or to 0, frees the entry at 63, inserts one at 47 on the first occlusion (the lowest free slot, else in place of the greatest v), and
+// adds as lightPickAddKernel does.
+#define RT_LIST_VIS_FREE 0xFFFFu
+// v of the entry that names light i (the lowest slot, should two name it), 63 where none does; e0: entries 0 and 1, e1: entries 2 and 3
+RT_DEV uint32_t listVisOf(uint32_t e0, uint32_t e1, uint32_t i) {
+  const uint32_t a = e0 & 0xFFFFu, b = e0 >> 16, c = e1 & 0xFFFFu, d = e1 >> 16;
+  uint32_t v = 63u;
+  v = (d != RT_LIST_VIS_FREE && (d & 1023u) == i) ? d >> 10 : v;
+  v = (c != RT_LIST_VIS_FREE && (c & 1023u) == i) ? c >> 10 : v;
+  v = (b != RT_LIST_VIS_FREE && (b & 1023u) == i) ? b >> 10 : v;
+  v = (a != RT_LIST_VIS_FREE && (a & 1023u) == i) ? a >> 10 : v;
+  return v;
+}
+RT_DEV float listVisWeight(uint32_t e0, uint32_t e1, uint32_t i) { return (float)max(listVisOf(e0, e1, i), RTGGX_LIGHT_LIST_VIS_FLOOR); }
+// Step 6 on the two entry words for the chosen light; the four entries stay registers: every loop below has constant bounds
+RT_DEV void listVisUpdate(uint32_t& e0, uint32_t& e1, uint32_t chosen, bool occluded) {
+  uint32_t ent[4] = {e0 & 0xFFFFu, e0 >> 16, e1 & 0xFFFFu, e1 >> 16};
+  uint32_t k = 4u, v = 63u;
+#pragma unroll
+  for (uint32_t j = 4u; j-- > 0u;) if (ent[j] != RT_LIST_VIS_FREE && (ent[j] & 1023u) == chosen) { k = j; v = ent[j] >> 10; }
+  const uint32_t next = occluded ? v - ((v + 3u) >> 2) : v + ((63u - v + 3u) >> 2);
+  uint32_t put = next == 63u ? RT_LIST_VIS_FREE : (next << 10) | chosen;
+  if (k == 4u) {
+    if (!occluded) return;      // believed visible and seen: nothing to record
+    put = (47u << 10) | chosen;
+    uint32_t most = 0u;
+    bool free = false;
+#pragma unroll
+    for (uint32_t j = 0u; j < 4u; ++j) {
+      if (free) continue;
+      if (ent[j] == RT_LIST_VIS_FREE) { k = j; free = true; }
+      else if (k == 4u || (ent[j] >> 10) > most) { k = j; most = ent[j] >> 10; }
+    }
+  }
+#pragma unroll
+  for (uint32_t j = 0u; j < 4u; ++j) ent[j] = j == k ? put : ent[j];
+  e0 = ent[0] | (ent[1] << 16); e1 = ent[2] | (ent[3] << 16);
+}
+template <bool CONE, bool SOFT>
+__global__ void __launch_bounds__(256) lightListVisGenKernel(const FrameParams* __restrict__ fpp, const LightRecord* __restrict__ recs, const float4* __restrict__ cull, LightListGenArgs A, LightVisArgs R) {
+  const FrameParams& fp = *fpp;
+  const uint32_t tile = blockIdx.x;
+  if (tileIsEmpty(A.tileWords, tile)) return;
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const uint32_t px = (tile % A.tilesX) * 16 + (wave & 1u) * 8 + (lane & 7u);
+  const uint32_t py = A.rowBegin + (tile / A.tilesX) * 16 + (wave >> 1) * 8 + (lane >> 3);
+  PrimarySurface S = {};
+  bool covered = false;
+  if (px < fp.W && py < A.rowEnd && py < fp.H) atPrimarySurface(fp, A.visDepth, A.fat0, A.fat1, px, py, [&](const PrimarySurface& s) { S = s; covered = true; });
+  const bool diffuse = S.rm.y < 1.0f;
+  // step 2: the history, along the frame's own velocity; the record is written whether or not a light reaches the pixel
+  uint32_t e0 = 0xFFFFFFFFu, e1 = 0xFFFFFFFFu;
+  if (covered) {
+    const uint32_t nrm = R.normal[S.pixel], vel = R.velocity[S.pixel];
+    const float qx = floorf(((float)px + 0.5f) - f16ToF32(vel & 0xFFFFu) * (float)fp.W), qy = floorf(((float)py + 0.5f) - f16ToF32(vel >> 16) * (float)fp.H);
+    if (R.history != 0u && qx >= 0.0f && qx < (float)fp.W && qy >= 0.0f && qy < (float)fp.H) {
+      const uint4 rec = R.prev[(size_t)(uint32_t)qy * fp.W + (uint32_t)qx];
+      if ((rec.w >> 8) == R.prevSeq && (rec.w & 0xFFu) == S.inst + 1u && (float)visNormalDot(rec.z, nrm) >= 0.9f * 1046529.0f) { e0 = rec.x; e1 = rec.y; }
+    }
+    R.next[S.pixel] = make_uint4(e0, e1, nrm, R.stampHigh | (S.inst + 1u));
+  }
+  const WaveBox box = waveBox(covered, S.P);
+  const bool any = __ballot(covered) != 0ull;
+  const uint32_t chunks = (A.count + 63u) >> 6;
+  // steps 1 and 3 over the kept lights, ascending: U
+  float U = 0.0f;
+  uint32_t kept = 0u;
+  for (uint32_t chunk = 0u; chunk < chunks; ++chunk) {
+    unsigned long long m = keptLights(cull, A.count, chunk, lane, box, any, A.cullOn);
+    kept += (uint32_t)__popcll(m);
+    while (m != 0ull) {
+      const uint32_t i = RT_SGPR(chunk * 64u + (uint32_t)__builtin_ctzll(m));
+      m &= m - 1ull;
+      const LightArgs K = recs[i].k;
+      if (covered) U = U + primaryPickTerms<CONE>(K, S, diffuse).w * listVisWeight(e0, e1, i);      // (a weight of +0 leaves U as it is)
+    }
+  }
+  if (lane == 0u && px < fp.W && py < A.rowEnd) A.kept[(size_t)(py >> 3) * A.blocksX + (px >> 3)] = kept;
+  const bool active = covered && U > 0.0f;      // a candidate
+  bool want = false, wantDiff = false;
+  RayRec rr;
+  float tmax = 0.0f;
+  f3 S1 = mk3(0.0f, 0.0f, 0.0f);
+  if (__ballot(active) != 0ull) {
+    // step 4: the same walk once more on u, until every lane has its light
+    const float t = pickDraw(S.pixel, fp.g.FrameIndex, RT_SLOT_LIGHT_PICK) * U;
+    float c = 0.0f, uc = 0.0f;
+    uint32_t chosen = 0u;
+    bool found = !active;
+    for (uint32_t chunk = 0u; chunk < chunks && __ballot(!found) != 0ull; ++chunk) {
+      unsigned long long m = keptLights(cull, A.count, chunk, lane, box, any, A.cullOn);
+      while (m != 0ull && __ballot(!found) != 0ull) {
+        const uint32_t i = RT_SGPR(chunk * 64u + (uint32_t)__builtin_ctzll(m));
+        m &= m - 1ull;
+        const LightArgs K = recs[i].k;
+        if (!found) {
+          const float w = primaryPickTerms<CONE>(K, S, diffuse).w;
+          if (w > 0.0f) { const float u = w * listVisWeight(e0, e1, i); c = c + u; chosen = i; uc = u; found = t < c; }
+        }
+      }
+    }
+    if (active) {      // step 5: the list's steps 6 and 7; the chosen index in the record's flags word, for the update
+      const float f = U / uc;
+      const LightArgs K = recs[chosen].k;
+      LightSample l;
+      if (chosenLightSample<CONE, SOFT>(K, A.cosSin, S.P, S.N, S.pixel, fp.g.FrameIndex, RT_SLOT_LIST_LIGHT(chosen), l)) {
+        const PickTerms x = primaryPickTerms<CONE>(K, S, diffuse);
+        want = true; wantDiff = diffuse;
+        tmax = l.tmax;
+        rr = shadowRay(S.P, l.Ls, S.pixel, (S.inst << 24) | S.prim, mk3(x.spec.x * f, x.spec.y * f, x.spec.z * f), chosen);
+        S1 = mk3(x.diff.x * f, x.diff.y * f, x.diff.z * f);
+      }
+    }
+  }
+  const uint32_t bin = blockIdx.x * 4u + wave;
+  const unsigned long long wanting = __ballot(want);      // (the slot compactShadowRay gives the lane)
+  if (wantDiff) A.diffTerm[(size_t)bin * RT_BIN_MIN + (uint32_t)__popcll(wanting & ((1ull << lane) - 1ull))] = make_float4(S1.x, S1.y, S1.z, 0.0f);
+  const uint32_t n = compactShadowRay<true>(want, rr, tmax, A.rays, A.hits, A.tRange, bin, RT_BIN_MIN, 0u, lane);
+  if (lane == 0) A.binCount[bin] = n;
+}
+// lightPickAddKernel with step 6: every slot below the bin's count updates the two entry words of its pixel's own record, occluded or not
+__global__ void __launch_bounds__(256) lightListVisAddKernel(const FrameParams* __restrict__ fpp, LightPickAddArgs A, uint32_t* records) {
+  const FrameParams& fp = *fpp;
+  if (tileIsEmpty(A.tileWords, blockIdx.x)) return;
+  const uint32_t bin = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (lane >= A.binCount[bin]) return;
+  const size_t k = (size_t)bin * RT_BIN_MIN + lane;
+  const bool occluded = hitKeyId(A.hits[k]) != 0xFFFFFFFFu;
+  const RayRec rr = A.rays[k];
+  uint2* const entries = reinterpret_cast<uint2*>(records + 4u * (size_t)rr.pixel);      // the pixel's own record: no other lane has this pixel
+  uint2 e = *entries;
+  listVisUpdate(e.x, e.y, rr.flags & 1023u, occluded);
+  *entries = e;
+  if (occluded) return;      // no term
+  const uint32_t inst = rr.skip >> 24;
+  const float4 s0 = A.sumRefl[rr.pixel];
+  A.sumRefl[rr.pixel] = make_float4(s0.x + rr.wx, s0.y + rr.wy, s0.z + rr.wz, s0.w + 1.0f);
+  if (fp.mat.RoughMetals[inst][1] < 1.0f) {      // (lightAddKernel)
+    const float4 d = A.diffTerm[k], s1 = A.sumDiff[rr.pixel];
+    A.sumDiff[rr.pixel] = make_float4(s1.x + d.x, s1.y + d.y, s1.z + d.z, s1.w + 1.0f);
+  }
+}
+static void (*const kLightListVisGen[4])(const FrameParams*, const LightRecord*, const float4*, LightListGenArgs, LightVisArgs) = {lightListVisGenKernel<false, false>, lightListVisGenKernel<false, true>, lightListVisGenKernel<true, false>, lightListVisGenKernel<true, true>};
 // The list to the device when the setting takes effect (frame.hip rtggx_render_visibility): the records with pickList's neutral cone, the
 // cull's (Pl, R) with R = 0 where a light casts nothing; how many cast, and the instance [2 cone + soft] the list runs.  A frame that still
 // reads the previous list may be in flight: the caller has waited for the streams (a change of the list is a setup step, not a per-frame one).
@@ -1186,16 +1356,19 @@ static int clearLightListCounts(rtggx_context* c, hipStream_t s) {
   c->lightListFrame = true;
   return 0;
 }
-// The generating launch of the primary pass with a list, in lightPickGenKernel's place (launchLights): P's queue, rows and tiles
-static int launchLightListGen(rtggx_context* c, hipStream_t s, const LightPickGenArgs& P, uint32_t numTiles) {
+// The generating launch of the primary pass with a list, in lightPickGenKernel's place (launchLights): P's queue, rows and tiles; records:
+// rtggx_set_light_list_visibility's images and sequence in an acting frame, null otherwise
+static int launchLightListGen(rtggx_context* c, hipStream_t s, const LightPickGenArgs& P, uint32_t numTiles, const LightVisArgs* records) {
   const uint32_t blocksX = (c->W + 7u) / 8u;
   LightListGenArgs A;
   A.visDepth = P.visDepth; A.fat0 = P.fat0; A.fat1 = P.fat1;
   A.rays = P.rays; A.hits = P.hits; A.binCount = P.binCount; A.tRange = P.tRange; A.diffTerm = P.diffTerm;
   A.tileWords = P.tileWords; A.tilesX = P.tilesX; A.rowBegin = P.rowBegin; A.rowEnd = P.rowEnd;
   A.cosSin = c->cosSinTab; A.kept = c->lightListKept; A.blocksX = blocksX; A.count = c->lightList.count; A.cullOn = c->lightListCullOn ? 1u : 0u;
-  launch(kLightListGen[c->lightListVariant], dim3(numTiles), dim3(256), s, nullptr, nullptr, c->dParams + c->slot,
-         (const LightRecord*)c->lightListRecs.get(), (const float4*)c->lightListCull.get(), A);
+  if (records) launch(kLightListVisGen[c->lightListVariant], dim3(numTiles), dim3(256), s, nullptr, nullptr, c->dParams + c->slot,
+                      (const LightRecord*)c->lightListRecs.get(), (const float4*)c->lightListCull.get(), A, *records);
+  else launch(kLightListGen[c->lightListVariant], dim3(numTiles), dim3(256), s, nullptr, nullptr, c->dParams + c->slot,
+              (const LightRecord*)c->lightListRecs.get(), (const float4*)c->lightListCull.get(), A);
   return 0;
 }
 

@@ -338,6 +338,12 @@ struct rtggx_context {
   bool lightVis = false, lightVisRequested = false;
   uint32_t lightVisSeq = 0, lightVisSeq0 = 0;
   rt::DevBuf<uint32_t> lightVisImg[2];
+  // rtggx_set_light_list_visibility: the same for a list (lighting.hip launchLights: lightListVisGenKernel, lightListVisAddKernel in the
+  // list's branch), with a sequence and two images of W x H RtggxLightListVisRecord of its own, from the first acting frame (a list with a
+  // casting light, the setting on).  Resets: the allocation, every successful rtggx_set_light_list, every change of the setting.
+  bool lightListVis = false, lightListVisRequested = false;
+  uint32_t lightListVisSeq = 0, lightListVisSeq0 = 0;
+  rt::DevBuf<uint32_t> lightListVisImg[2];
   // rtggx_set_light_list: up to RTGGX_MAX_LIGHT_LIST lights in device memory under mode 1's rule, culled per 8x8 block (lighting.hip
   // lightListGenKernel, lightListHitGenKernel).  The context holds this list or rtggx_set_lights' (the setters refuse the other); the
   // requested list takes effect with the next rtggx_render_visibility, which uploads it where its version differs (lighting.hip

@@ -42,6 +42,7 @@ void RayTracedGGX::OnInit() {
   if (!m_lightList.empty() && !m_rayTracer->SetLightList(m_lightList.data(), (uint32_t)m_lightList.size())) throw std::runtime_error("-lightlist: " + m_rayTracer->GetLastError());      // -lightlist: a light list beyond eight, one shadow ray per point (opt-in)
   if (m_lightReflections && !m_rayTracer->SetLightReflections(true)) throw std::runtime_error("-lightreflections: " + m_rayTracer->GetLastError());      // -lightreflections: ... at the surfaces the paths hit as well (opt-in)
   if (m_lightPick && !m_rayTracer->SetLightSampling(1)) throw std::runtime_error("-lightpick: " + m_rayTracer->GetLastError());      // -lightpick: one shadow ray per surface point for all lights (opt-in)
+  if (m_lightListVisibility && !m_rayTracer->SetLightListVisibility(true)) throw std::runtime_error("-lightlistvisibility: " + m_rayTracer->GetLastError());      // -lightlistvisibility: the list's pick weighted by what the pixel remembers (opt-in)
   if (m_lightVisibility && !m_rayTracer->SetLightPickVisibility(true)) throw std::runtime_error("-lightvisibility: " + m_rayTracer->GetLastError());      // -lightvisibility: the pick weighted by what the pixel remembers (opt-in)
   if (m_sunAngle != 0.0f && !m_rayTracer->SetSunAngle(m_sunAngle)) throw std::runtime_error("-sunangle: " + m_rayTracer->GetLastError());      // -sunangle: a sun with a size, soft shadows (opt-in)
   if (m_recursionDepth != 1u && !m_rayTracer->SetMaxRecursionDepth(m_recursionDepth)) throw std::runtime_error("-recursion: " + m_rayTracer->GetLastError());      // -recursion N: multi-bounce paths (opt-in)
@@ -237,7 +238,7 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
     return (arg[0] == '-' || arg[0] == '/') && lower(arg + 1) == lower(name);
   };
   // On POSIX an absolute path also starts with '/': such a token is a flag only when it names one.
-  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "sun", "sunreflections", "sunfromenv", "sunangle", "light", "spot", "lightreflections", "lightpick", "lightvisibility", "lightlist", "recursion", "spp", "accumulate", "sampleset", "savereference", "reference", "score", "envlayout", "envsize", "envmips", "envprefilter"};
+  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "sun", "sunreflections", "sunfromenv", "sunangle", "light", "spot", "lightreflections", "lightpick", "lightvisibility", "lightlistvisibility", "lightlist", "recursion", "spp", "accumulate", "sampleset", "savereference", "reference", "score", "envlayout", "envsize", "envmips", "envprefilter"};
   const auto isFlagName = [&](const char* name) { for (const char* f : kFlags) if (lower(name) == f) return true; return false; };
   const auto hasNextArgValue = [&](int i) {
     if (i + 1 >= argc) return false;
@@ -293,6 +294,7 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
     else if (isArgMatched(i, "sunreflections")) m_sunReflections = true;      // (without -sun: refused below, once the whole line is read)
     else if (isArgMatched(i, "lightreflections")) m_lightReflections = true;      // (without -light / -spot: refused below, once the whole line is read)
     else if (isArgMatched(i, "lightpick")) m_lightPick = true;      // (without -light / -spot: refused below, once the whole line is read)
+    else if (isArgMatched(i, "lightlistvisibility")) m_lightListVisibility = true;      // (without -lightlist, or with strips: refused below, once the whole line is read)
     else if (isArgMatched(i, "lightvisibility")) m_lightVisibility = true;      // (without -lightpick, or with strips: refused below, once the whole line is read)
     // -sunfromenv [degrees]: the sun measured from the -env cube and taken out of it (rtggx_sun_from_env, RayTracer::Init); the half-angle
     // of the cone is checked here, before a device is asked for; without a number it is the library's default
@@ -427,6 +429,9 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
   if (m_lightVisibility && (m_gpus > 1 || m_strips > 1)) throw std::runtime_error("-lightvisibility: whole frames only, not with -gpus N > 1 or -strips N > 1");
   if (m_rayRate != 1u && !m_lights.empty()) throw std::runtime_error("-light / -spot together with -rayrate 4: refused");
   // a light list (rtggx_set_light_list) is held in place of the lights, not beside them, and excludes rate 4 as they do
+  // the list's visibility records (rtggx_set_light_list_visibility) act only on a list, and on whole frames
+  if (m_lightListVisibility && m_lightListFile.empty()) throw std::runtime_error("-lightlistvisibility without -lightlist: there is no list whose pick to weight");
+  if (m_lightListVisibility && (m_gpus > 1 || m_strips > 1)) throw std::runtime_error("-lightlistvisibility: whole frames only, not with -gpus N > 1 or -strips N > 1");
   if (!m_lightListFile.empty() && !m_lights.empty()) throw std::runtime_error("-lightlist together with -light / -spot: the context holds one or the other");
   if (!m_lightListFile.empty() && m_rayRate != 1u) throw std::runtime_error("-lightlist together with -rayrate 4: refused");
   if (m_rayRate != 1u && m_samplesPerPixel != 1u) throw std::runtime_error("-spp N > 1 together with -rayrate 4: refused");

@@ -121,6 +121,7 @@ bool RayTracer::SetLights(const RtggxLight* lights, uint32_t count) { return che
 bool RayTracer::SetLightReflections(bool enable) { return check(rtggx_set_light_reflections(m_ctx, enable ? 1 : 0), "rtggx_set_light_reflections"); }
 bool RayTracer::SetLightList(const RtggxLight* lights, uint32_t count) { return check(rtggx_set_light_list(m_ctx, lights, count), "rtggx_set_light_list"); }
 bool RayTracer::SetLightSampling(int mode) { return check(rtggx_set_light_sampling(m_ctx, mode), "rtggx_set_light_sampling"); }
+bool RayTracer::SetLightListVisibility(bool enable) { return check(rtggx_set_light_list_visibility(m_ctx, enable ? 1 : 0), "rtggx_set_light_list_visibility"); }
 bool RayTracer::SetLightPickVisibility(bool enable) { return check(rtggx_set_light_pick_visibility(m_ctx, enable ? 1 : 0), "rtggx_set_light_pick_visibility"); }
 bool RayTracer::SetSunReflections(bool enable) { return check(rtggx_set_sun_reflections(m_ctx, enable ? 1 : 0), "rtggx_set_sun_reflections"); }
 

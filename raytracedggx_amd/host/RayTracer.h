@@ -80,6 +80,9 @@ class RayTracer {
   // A list of up to RTGGX_MAX_LIGHT_LIST lights under mode 1's rule, culled per 8x8 block, from the next frame on (rtggx_set_light_list):
   // copied; (nullptr, 0) clears it.  In place of SetLights, not beside it.
   bool SetLightList(const RtggxLight* lights, uint32_t count);
+  // The list's pick weighted by the sparse record each pixel keeps of the lights it found hidden (rtggx_set_light_list_visibility); it acts
+  // only on a list while a light casts rays; whole frames only.
+  bool SetLightListVisibility(bool enable);
   bool SetSamplesPerPixel(uint32_t samples);   // rtggx_set_samples_per_pixel: 1 (default), 2, 4 or 8 samples per covered pixel (-spp); not together with ray rate 4
   bool SetMaxRecursionDepth(uint32_t depth);   // rtggx_set_max_recursion_depth: 1 (default; RayTracer.cpp:605 SetMaxRecursionDepth(1)) to 4 levels of rays per path (-recursion)   // rtggx_set_ray_rate: 1 (default) or 4 -- one pixel of each 2x2 quad traced per frame, the rest reconstructed (-rayrate)
   // rtggx_set_sample_set: the size of the sample set getSampleParam draws from, 256 (default, the reference's) or a power of two up to

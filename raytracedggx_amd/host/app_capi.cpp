@@ -206,6 +206,15 @@ extern "C" int rtggx_app_set_light_pick_visibility(void* h, int enable) {
   return -1;
 }
 
+// RayTracer::SetLightListVisibility of the application's ray tracer
+extern "C" int rtggx_app_set_light_list_visibility(void* h, int enable) {
+  RayTracer* rt = ((RayTracedGGX*)h)->GetRayTracer();
+  if (enable != 0 && enable != 1) { g_appError = "rtggx_app_set_light_list_visibility: 0 or 1"; return -1; }
+  if (rt->SetLightListVisibility(enable == 1)) return 0;
+  g_appError = rt->GetLastError();
+  return -1;
+}
+
 // The multi-GPU host's plan functions (host/Strips.cpp), for the tests that compare them with raytracedggx_amd/strips.py.
 // bounds: nullptr / 0 for equal strips, else world + 1 row numbers.  ops: 5 int32 per transfer (send, buffer: 1 history / 0 back buffer / 2 token, rowBegin, rowEnd, peer);
 // returns the number of transfers, or -1 with rtggx_app_last_error set.
