@@ -917,7 +917,8 @@ int  rtggx_read_light_visibility(rtggx_context* ctx, uint32_t image /* 0, 1 */, 
  * Per frame one generating launch, one any-hit traversal and one add, and per level and sample of the hits likewise, whatever n.  Memory: 80
  * bytes per light, mode 1's queue, sums and diffuse terms, and 4 bytes per 8x8 block for the counts below.
  * Known limits: no culling by cone or by facing; no world-space grid for the hits, whose points are incoherent (a round's box can be large:
- * the cull there saves less); visibility records at the primary pass only (rtggx_set_light_list_visibility); lights that move need a new call; no more than 1024 lights. */
+ * the cull there saves less); visibility records at the primary pass only (rtggx_set_light_list_visibility); no more than 1024 lights; the count of a list is fixed
+ * (rtggx_update_light_list moves its lights, not their number). */
 #define RTGGX_MAX_LIGHT_LIST 1024u
 int  rtggx_set_light_list(rtggx_context* ctx, const RtggxLight* lights, uint32_t count);
 /* Synchronises and copies, row-major by 8x8 block, the number of kept lights of the last frame's primary pass: ceil(H/8) rows of ceil(W/8)
@@ -974,8 +975,9 @@ int  rtggx_debug_light_list_cull(rtggx_context* ctx, int enable);   /* 1 (defaul
  * any, is simply carried; images, ray counts AND records are those of the walk over all lights, bit for bit, with
  * rtggx_debug_light_list_cull(ctx, 0) as with the cull on.  With one casting light the images are the list's own.
  * Known limits: the hits are not covered; four entries per pixel -- a fifth hidden light evicts the least hidden; the floor means a light
- * that leaves shadow is noticed at 1/16 of its share; records are per pixel and not filtered over neighbours; strips are refused; lights
- * that move need a new rtggx_set_light_list, which is a reset.  tests/light_list_vis_ref.cpp restates the rule over all lights. */
+ * that leaves shadow is noticed at 1/16 of its share; records are per pixel and not filtered over neighbours; strips are refused; a light
+ * that moves (rtggx_update_light_list) keeps its entries, stale as they may be, until the outcomes of new rays correct them -- unbiased,
+ * variance only.  tests/light_list_vis_ref.cpp restates the rule over all lights. */
 #define RTGGX_LIGHT_LIST_VIS_ENTRIES 4u
 #define RTGGX_LIGHT_LIST_VIS_FLOOR   4u      /* policy default, not a measurement: 1/16 of 63, as RTGGX_LIGHT_VIS_FLOOR is of 255 */
 typedef struct RtggxLightListVisRecord {     /* 16 bytes */
@@ -987,6 +989,56 @@ int  rtggx_set_light_list_visibility(rtggx_context* ctx, int enable);      /* 0 
 /* Synchronises and copies image 0 or 1 of the records (W x H, row by row) to out; *sequence (may be NULL) receives this setting's s.  It
  * fails before anything is allocated (before the first acting frame), for an image other than 0 or 1, and when bytes is not W H 16. */
 int  rtggx_read_light_list_visibility(rtggx_context* ctx, uint32_t image /* 0, 1 */, RtggxLightListVisRecord* out, size_t bytes, uint32_t* sequence);
+
+/* Lights of a list that move: per-frame updates without a drain, the records kept.  rtggx_set_light_list stays the way to give a context
+ * a NEW list -- its next rtggx_render_visibility waits for every stream and resets the records' history --; the two calls below replace
+ * lights first .. first + count - 1 of the list the context holds: the list that will be in effect at the next rtggx_render_visibility,
+ * including one set by a rtggx_set_light_list that has not taken effect yet.  The number of lights never changes: indices keep their
+ * meaning, and with it the hash slots and the light field of the sparse records.  Calls apply in call order and take effect with the next
+ * rtggx_render_visibility.  Refused, everything staying as it was: no list held; first + count above the list's count; a null pointer with
+ * count > 0.  count == 0 succeeds and does nothing.  Neither call waits for the GPU in the steady state (the first update of a context's
+ * life allocates: a ring of eight versions of the list, 80 bytes per light of RTGGX_MAX_LIGHT_LIST each, and as much pinned memory);
+ * neither ends a still-sky run, resets an accumulation or resets rtggx_set_light_list_visibility's history: s0 stays.  Once an update has
+ * taken effect the frame's images, ray count, kept counts and records are exactly those of the list's rule above applied to the updated
+ * list: the cull, the pick, the slots and the records' update are untouched, only WHICH list a frame reads is new.  Frames already in
+ * flight keep reading the list they started with: a version of the list is written once, read by every frame until the next update takes
+ * effect, and written again only when the last frame that read it has ended.  A frame without an update launches and copies nothing
+ * beyond what it did.  Opt-in: a context that never calls these allocates and launches exactly what it did.
+ * rtggx_update_light_list (a host array): every light is checked exactly as rtggx_set_light_list checks it, a cone's axis normalised in
+ * double and rounded once; one invalid light refuses the whole call.  The lights are copied before the call returns; they reach the device
+ * through pinned memory and an asynchronous copy on the stream of the next frame's visibility pass.  The list's kernel variant (cone,
+ * radius) and whether it casts at all are recomputed from what the host knows.
+ * rtggx_update_light_list_device (a device pointer, aligned to 16 bytes): ordered like hipMemcpyAsync on hip_stream (NULL means the null
+ * stream), as rtggx_refit_as_device is: the read of device_lights is ordered behind what the stream holds at the call, and what the caller
+ * enqueues there afterwards is ordered behind the read.  No host copy and no wait.  The host cannot see the values, so a kernel on the
+ * device applies the same checks per light.  An invalid light is a REJECT: any refusal reason above, and a radius > 0 or a cone
+ * (cos_outer > -1) whose kind is not declared in `kinds` (RTGGX_LIGHT_KIND_RADIUS | RTGGX_LIGHT_KIND_CONE; anything else is refused).  A
+ * reject becomes a light that casts nothing -- position 0, range 1, intensity 0, no radius, no cone, cull radius 0 --, is never kept and
+ * never evaluated, keeps its index, and is counted in a 64-bit counter on the device.  `kinds` is ORed into the list's variant and never
+ * shrinks until the next rtggx_set_light_list; the variants are bit-identical in what they compute (a point light runs the cone variant
+ * with the neutral cone (-2, -1)): a matter of speed only.
+ * The one place where the semantics differ from a host-known list: from the first device update until the next rtggx_set_light_list the
+ * list is PRESUMED CASTING.  The frame launches the list's three kernels, and with rtggx_set_light_list_visibility(ctx, 1) it is an
+ * acting frame (s advances, records are written), whether or not any light has an intensity.  If a rtggx_set_light_list is still pending
+ * when the device call comes, that list is uploaded then and there (through the staging; the call may wait as a set-up step does).
+ * A host update of lights that a device update wrote, and the reverse, apply in call order.
+ * rtggx_read_light_list synchronises and returns the list the last frame read, as the kernels see it: 64 bytes per light in RtggxLight's
+ * layout, axis normalised (zero where there is no cone), the neutral cone (-2, -1) where there is none, pad 0, rejects in their sanitised
+ * form.  It fails before the first frame with a list, and when bytes != count 64.
+ * rtggx_read_light_list_rejects synchronises (the streams the device updates were given included) and returns the number of rejects since
+ * the last reset; reset 1 clears it.
+ * rtggx_debug_visibility_drains: how often rtggx_render_visibility has waited for every stream of the context since the last reset (a host
+ * counter, one increment per wait): a rtggx_set_light_list that takes effect is one, an update is none.
+ * Known limits: the count is fixed; a moved light keeps its stale record entries until the outcomes of new rays correct them -- unbiased,
+ * variance only; a device-updated list is presumed casting; the frame that takes an update records one more event on the main stream.
+ * DESIGN.md section 9 "Moving light lists"; tests/light_list_moving_ref.py restates the semantics on the records' restatement. */
+#define RTGGX_LIGHT_KIND_RADIUS 1u   /* some light has radius > 0 */
+#define RTGGX_LIGHT_KIND_CONE   2u   /* some light has cos_outer > -1 */
+int  rtggx_update_light_list(rtggx_context* ctx, const RtggxLight* lights, uint32_t first, uint32_t count);
+int  rtggx_update_light_list_device(rtggx_context* ctx, const RtggxLight* device_lights, uint32_t first, uint32_t count, uint32_t kinds, void* hip_stream);
+int  rtggx_read_light_list(rtggx_context* ctx, RtggxLight* out, size_t bytes);
+int  rtggx_read_light_list_rejects(rtggx_context* ctx, uint64_t* rejects, int reset);
+int  rtggx_debug_visibility_drains(rtggx_context* ctx, uint32_t* drains, int reset);
 
 /* The sun from the environment: finds the sun in the current cube, measures its direction and irradiance -- what rtggx_set_sun wants -- and,
  * where asked, takes it out of the cube, so that a probe with a sun in it does not light the scene twice (once analytically, with shadows, and

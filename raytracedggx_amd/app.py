@@ -22,7 +22,8 @@ HOST_EXPORTS = ["rtggx_app_last_error", "rtggx_app_create", "rtggx_app_destroy",
                 "rtggx_host_write_pfm", "rtggx_host_read_pfm", "rtggx_host_load_env_image",
                 "rtggx_app_set_sample_map", "rtggx_app_set_lights", "rtggx_app_set_light_reflections", "rtggx_app_set_light_sampling",
                 "rtggx_app_set_light_pick_visibility", "rtggx_app_set_light_list",
-                "rtggx_app_set_light_list_visibility"]
+                "rtggx_app_set_light_list_visibility", "rtggx_app_update_light_list", "rtggx_app_update_light_list_device",
+                "rtggx_app_read_light_list"]
 
 _lib = None
 
@@ -65,6 +66,9 @@ def load():
         L.rtggx_app_set_light_pick_visibility.argtypes = [C.c_void_p, C.c_int]
         L.rtggx_app_set_light_list.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.rtggx_app_set_light_list_visibility.argtypes = [C.c_void_p, C.c_int]
+        L.rtggx_app_update_light_list.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        L.rtggx_app_update_light_list_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.rtggx_app_read_light_list.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.rtggx_app_last_screen_shot.argtypes = [C.c_void_p]
         L.rtggx_app_last_screen_shot.restype = C.c_char_p
         L.rtggx_host_obj_import.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p]
@@ -296,6 +300,25 @@ class RayTracedGGX:
         a = (capi.Light * len(lights))(*lights) if lights else None
         if self.L.rtggx_app_set_light_list(self.h, a, len(lights)) != 0:
             raise capi.RtggxError(self.L.rtggx_app_last_error().decode())
+
+    def update_light_list(self, lights, first=0):
+        """RayTracer::UpdateLightList: lights first .. of the list replaced from the next frame on; no wait, the records' history kept."""
+        lights = [l if isinstance(l, capi.Light) else capi.Light.of(**l) for l in lights]
+        a = (capi.Light * len(lights))(*lights) if lights else None
+        if self.L.rtggx_app_update_light_list(self.h, a, int(first), len(lights)) != 0:
+            raise capi.RtggxError(self.L.rtggx_app_last_error().decode())
+
+    def update_light_list_device(self, ptr, first, count, kinds, stream=0):
+        """RayTracer::UpdateLightListDevice: the same from device memory, read in the order of `stream` and checked on the device."""
+        if self.L.rtggx_app_update_light_list_device(self.h, C.c_void_p(int(ptr)), int(first), int(count), int(kinds), C.c_void_p(int(stream) or None)) != 0:
+            raise capi.RtggxError(self.L.rtggx_app_last_error().decode())
+
+    def read_light_list(self, count):
+        """RayTracer::ReadLightList: the `count` lights the last frame read as the kernels see them, float32 [count, 16].  Synchronises."""
+        a = np.zeros((int(count), 16), np.float32)
+        if self.L.rtggx_app_read_light_list(self.h, a.ctypes.data_as(C.c_void_p), a.nbytes) != 0:
+            raise capi.RtggxError(self.L.rtggx_app_last_error().decode())
+        return a
 
     def set_light_pick_visibility(self, enable):
         """RayTracer::SetLightPickVisibility: the pick of mode 1 weighted by the visibility each pixel remembers (0 / 1), from the next frame on."""

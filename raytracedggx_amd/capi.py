@@ -6,6 +6,7 @@ when no HIP device is present.
 """
 import ctypes as C
 import os
+import re
 
 import numpy as np
 
@@ -25,6 +26,7 @@ ENV_FILTER_MIN_SAMPLES, ENV_FILTER_MAX_SAMPLES = 64, 4096      # rtggx_prefilter
 MAX_SUN_ANGLE_DEGREES = 10.0                                    # rtggx_set_sun_angle
 MAX_LIGHTS = 8                                                  # rtggx_set_lights
 MAX_LIGHT_LIST = 1024                                           # rtggx_set_light_list
+LIGHT_KIND_RADIUS, LIGHT_KIND_CONE = 1, 2                       # rtggx_update_light_list_device's kinds
 
 _BUF_DTYPE = {BUF_VISIBILITY: np.uint32, BUF_DEPTH: np.uint32, BUF_NORMAL: np.uint32, BUF_ROUGH_METAL: np.uint16,
               BUF_VELOCITY: np.uint32, BUF_RT_REFL: np.uint32, BUF_RT_DIFF: np.uint32, BUF_TSS0: np.uint64, BUF_TSS1: np.uint64,
@@ -47,7 +49,9 @@ EXPORTS = ["rtggx_last_error", "rtggx_create", "rtggx_destroy", "rtggx_set_strip
            "rtggx_sun_from_env", "rtggx_set_sun_angle", "rtggx_set_lights", "rtggx_set_light_reflections", "rtggx_set_light_sampling",
            "rtggx_set_light_pick_visibility", "rtggx_read_light_visibility",
            "rtggx_set_light_list", "rtggx_read_light_list_counts", "rtggx_debug_light_list_cull",
-           "rtggx_set_light_list_visibility", "rtggx_read_light_list_visibility"]
+           "rtggx_set_light_list_visibility", "rtggx_read_light_list_visibility",
+           "rtggx_update_light_list", "rtggx_update_light_list_device", "rtggx_read_light_list", "rtggx_read_light_list_rejects",
+           "rtggx_debug_visibility_drains"]
 SCORE_RING = 256
 
 
@@ -179,6 +183,11 @@ def load():
     L.rtggx_debug_light_list_cull.argtypes = [vp, C.c_int]
     L.rtggx_set_light_list_visibility.argtypes = [vp, C.c_int]
     L.rtggx_read_light_list_visibility.argtypes = [vp, C.c_uint32, vp, C.c_size_t, C.POINTER(C.c_uint32)]
+    L.rtggx_update_light_list.argtypes = [vp, C.POINTER(Light), C.c_uint32, C.c_uint32]
+    L.rtggx_update_light_list_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+    L.rtggx_read_light_list.argtypes = [vp, vp, C.c_size_t]
+    L.rtggx_read_light_list_rejects.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
+    L.rtggx_debug_visibility_drains.argtypes = [vp, C.POINTER(C.c_uint32), C.c_int]
     L.rtggx_sun_from_env.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_int, C.POINTER(SunEstimate)]
     L.rtggx_ray_total.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
     L.rtggx_kernel_times.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
@@ -707,6 +716,50 @@ class Context:
         seq = C.c_uint32()
         self._check(self.L.rtggx_read_light_list_visibility(self.h, int(image), _p(a), a.nbytes, C.byref(seq)))
         return a, seq.value
+
+    def update_light_list(self, lights, first=0):
+        """Lights first .. first + len(lights) - 1 of the list the context holds, replaced from the next frame on (include/rtggx.h has
+        the rule): a sequence of Light, or of dicts with Light.of's arguments, or a float32 array [n, 16] in RtggxLight's layout.  No wait,
+        no reset of the records' history."""
+        if isinstance(lights, np.ndarray):
+            a = np.ascontiguousarray(lights, np.float32).reshape(-1, 16)
+            return self._check(self.L.rtggx_update_light_list(self.h, C.cast(_p(a), C.POINTER(Light)) if len(a) else None, int(first), len(a)))
+        lights = [l if isinstance(l, Light) else Light.of(**l) for l in lights]
+        self._check(self.L.rtggx_update_light_list(self.h, (Light * len(lights))(*lights) if lights else None, int(first), len(lights)))
+
+    def update_light_list_device(self, ptr, first, count, kinds, stream=0):
+        """The same from `count` RtggxLight in device memory at `ptr` (16-byte aligned), read on `stream` (0: the null stream) in stream
+        order; kinds: LIGHT_KIND_RADIUS | LIGHT_KIND_CONE, what the lights may have.  An invalid light becomes one that casts nothing
+        and is counted (read_light_list_rejects)."""
+        self._check(self.L.rtggx_update_light_list_device(self.h, C.c_void_p(int(ptr)), int(first), int(count), int(kinds), C.c_void_p(int(stream) or None)))
+
+    def read_light_list(self):
+        """The list the last frame read as the kernels see it: float32 [count, 16] in RtggxLight's layout.  Synchronises.  Raises before
+        the first frame with a list."""
+        a = np.zeros((self._light_list_count(), 16), np.float32)
+        self._check(self.L.rtggx_read_light_list(self.h, _p(a), a.nbytes))
+        return a
+
+    def _light_list_count(self):
+        """The count rtggx_read_light_list wants: its message names it (the ABI has no getter of its own)."""
+        if self.L.rtggx_read_light_list(self.h, None, 0) == 0:
+            return 0
+        m = re.search(r"(\d+) lights of 64 bytes", self.L.rtggx_last_error().decode())
+        if not m:
+            self._check(-1)
+        return int(m.group(1))
+
+    def read_light_list_rejects(self, reset=False):
+        """The lights the device path has refused since the last reset.  Synchronises."""
+        n = C.c_uint64()
+        self._check(self.L.rtggx_read_light_list_rejects(self.h, C.byref(n), 1 if reset else 0))
+        return n.value
+
+    def debug_visibility_drains(self, reset=False):
+        """How often rtggx_render_visibility has waited for every stream of the context since the last reset."""
+        n = C.c_uint32()
+        self._check(self.L.rtggx_debug_visibility_drains(self.h, C.byref(n), 1 if reset else 0))
+        return n.value
 
     def sun_from_env(self, cone=0, ring=0, min_contrast=0, remove=False):
         """The sun of the current environment (include/rtggx.h): the record as a dict (SunEstimate.as_dict) -- "direction" and "irradiance" are

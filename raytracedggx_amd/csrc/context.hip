@@ -6,10 +6,12 @@
 #include <cstring>
 #include <cmath>
 #include <vector>
+#include <algorithm>
 #include "capi_internal.h"
 #include "rt_queue.h"
 #include "rt_env_filter.h"
 #include "rt_sun_env.h"
+#include "rt_light_check.h"
 
 #ifndef RT_REFIT_REBUILD_RATIO
 #define RT_REFIT_REBUILD_RATIO 1.2f      // a refitted tree whose cost has grown by this factor since its build is rebuilt (rtggx_refit_as)
@@ -478,16 +480,22 @@ int rtggx_set_sun_reflections(rtggx_context* c, int enable) {
 // One light of a list as both setters check it (rtggx_set_lights, rtggx_set_light_list: fn names the caller in the message): l is the copy the
 // context keeps, its axis normalised in double and rounded once, its pad zero
 static int checkLight(const char* fn, uint32_t i, RtggxLight& l) {
-  for (int k = 0; k < 3; ++k) if (!std::isfinite(l.position[k])) { setError("%s: light %u: position component %d is %g: finite", fn, i, k, (double)l.position[k]); return -1; }
-  if (!std::isfinite(l.range) || !(l.range > 0.0f)) { setError("%s: light %u: a range of %g: finite and above 0", fn, i, (double)l.range); return -1; }
-  for (int k = 0; k < 3; ++k) if (!std::isfinite(l.intensity[k]) || l.intensity[k] < 0.0f) { setError("%s: light %u: intensity component %d is %g: finite and not negative", fn, i, k, (double)l.intensity[k]); return -1; }
-  if (!std::isfinite(l.radius) || l.radius < 0.0f || !(l.radius < l.range)) { setError("%s: light %u: a radius of %g: finite, not negative and below the range %g", fn, i, (double)l.radius, (double)l.range); return -1; }
-  if (l.cos_outer > -1.0f) {      // a cone; (a NaN here is no cone by this test and is refused with the cosines below)
-    const double x = l.axis[0], y = l.axis[1], z = l.axis[2], len = std::sqrt(x * x + y * y + z * z);
-    if (!std::isfinite(len) || !(len > 0.0)) { setError("%s: light %u: the axis (%g, %g, %g) has no finite, non-zero length", fn, i, x, y, z); return -1; }
-    if (!(l.cos_outer < l.cos_inner && l.cos_inner <= 1.0f)) { setError("%s: light %u: cosines %g (outer) and %g (inner): -1 < outer < inner <= 1", fn, i, (double)l.cos_outer, (double)l.cos_inner); return -1; }
-    l.axis[0] = (float)(x / len); l.axis[1] = (float)(y / len); l.axis[2] = (float)(z / len);
-  } else if (!(l.cos_outer <= -1.0f)) { setError("%s: light %u: cos_outer is %g: at most -1 (no cone), or -1 < outer < inner <= 1", fn, i, (double)l.cos_outer); return -1; }
+  static_assert(sizeof(RtggxLight) == sizeof(LightWords), "RtggxLight is sixteen floats");
+  LightWords w; memcpy(&w, &l, sizeof w);
+  const uint32_t reason = lightCheck(w, LIGHT_KINDS_ALL);      // rt_light_check.h: the one statement of the rule, the device's as well
+  const int k = (int)(reason >> 8);
+  switch (reason & 0xFFu) {
+    case LIGHT_OK: break;
+    case LIGHT_BAD_POSITION: setError("%s: light %u: position component %d is %g: finite", fn, i, k, (double)l.position[k]); return -1;
+    case LIGHT_BAD_RANGE: setError("%s: light %u: a range of %g: finite and above 0", fn, i, (double)l.range); return -1;
+    case LIGHT_BAD_INTENSITY: setError("%s: light %u: intensity component %d is %g: finite and not negative", fn, i, k, (double)l.intensity[k]); return -1;
+    case LIGHT_BAD_RADIUS: setError("%s: light %u: a radius of %g: finite, not negative and below the range %g", fn, i, (double)l.radius, (double)l.range); return -1;
+    case LIGHT_BAD_AXIS: setError("%s: light %u: the axis (%g, %g, %g) has no finite, non-zero length", fn, i, (double)l.axis[0], (double)l.axis[1], (double)l.axis[2]); return -1;
+    case LIGHT_BAD_COSINES: setError("%s: light %u: cosines %g (outer) and %g (inner): -1 < outer < inner <= 1", fn, i, (double)l.cos_outer, (double)l.cos_inner); return -1;
+    default: setError("%s: light %u: cos_outer is %g: at most -1 (no cone), or -1 < outer < inner <= 1", fn, i, (double)l.cos_outer); return -1;
+  }
+  lightNormaliseAxis(w);
+  memcpy(&l, &w, sizeof w);
   l.pad[0] = l.pad[1] = l.pad[2] = 0.0f;
   return 0;
 }
@@ -532,6 +540,36 @@ int rtggx_set_light_list(rtggx_context* c, const RtggxLight* lights, uint32_t co
   next.count = count;
   next.version = ++c->lightListVersions;
   c->lightListRequested = std::move(next);
+  return 0;
+}
+// Lights that move, the host path (include/rtggx.h): the range is checked as rtggx_set_light_list checks it and copied into the list the
+// context holds; nothing reaches the device here -- the next rtggx_render_visibility (or an rtggx_update_light_list_device in front of
+// it) stages what has changed and copies it asynchronously into a version no frame in flight reads (lighting.hip "Moving light
+// lists").  No wait, no end of a still-sky run, no reset of an accumulation, and s0 stays: the records' history is kept.
+int rtggx_update_light_list(rtggx_context* c, const RtggxLight* lights, uint32_t first, uint32_t count) {
+  RT_CHECK_CTX(c);
+  rtggx_context::LightList& L = c->lightListRequested;
+  if (!L.count) { setError("rtggx_update_light_list: the context holds no light list (rtggx_set_light_list)"); return -1; }
+  if (first > L.count || count > L.count - first) { setError("rtggx_update_light_list: lights %u .. %u of a list of %u: the count of a list never changes", first, first + count, L.count); return -1; }
+  if (!count) return 0;
+  if (!lights) { setError("rtggx_update_light_list: %u lights at a null pointer", count); return -1; }
+  std::vector<RtggxLight> next(lights, lights + count);
+  for (uint32_t i = 0; i < count; ++i) if (checkLight("rtggx_update_light_list", first + i, next[i])) return -1;
+  std::copy(next.begin(), next.end(), L.l.begin() + first);
+  if (L.version == c->lightListStored) {      // (a list set and not yet uploaded carries them in its own upload)
+    const bool none = c->lightListDirtyLo >= c->lightListDirtyHi;
+    c->lightListDirtyLo = none ? first : std::min(c->lightListDirtyLo, first);
+    c->lightListDirtyHi = none ? first + count : std::max(c->lightListDirtyHi, first + count);
+  }
+  return 0;
+}
+// How often rtggx_render_visibility has waited for every stream of the context since the last reset: what makes "no drain" testable
+int rtggx_debug_visibility_drains(rtggx_context* c, uint32_t* drains, int reset) {
+  RT_CHECK_CTX(c);
+  if (!drains) { setError("rtggx_debug_visibility_drains: a null pointer"); return -1; }
+  if (reset != 0 && reset != 1) { setError("rtggx_debug_visibility_drains: reset %d: 0 or 1", reset); return -1; }
+  *drains = c->visibilityDrains;
+  if (reset) c->visibilityDrains = 0u;
   return 0;
 }
 // The kept lights per 8x8 block of the last frame's primary pass with a list, behind everything the context has enqueued

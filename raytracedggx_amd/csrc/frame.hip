@@ -196,10 +196,15 @@ int rtggx_render_visibility(rtggx_context* c) {
   settleSetRead(c);      // (the previous frame ended without the kernel that would have carried its set's event)
   ++c->frameCounter;
   c->maxDepth = c->depthRequested; c->samples = c->samplesRequested; c->accumulate = c->accumulateRequested; c->sun = c->sunRequested; c->sunAngle = c->sunAngleRequested; c->sunReflections = c->sunReflectionsRequested; c->lights = c->lightsRequested; c->lightReflections = c->lightReflectionsRequested; c->lightSampling = c->lightSamplingRequested; c->lightVis = c->lightVisRequested; c->lightListVis = c->lightListVisRequested;
-  if (c->lightList.version != c->lightListRequested.version) {      // rtggx_set_light_list: the new list, and its copy on the device
-    RT_HIP(syncStreams(c));      // (a frame in flight may read the list the upload replaces)
+  bool takeLightList = false;      // rtggx_update_light_list[_device]: what the calls left is taken further down, on the frame's first stream
+  if (c->lightList.version != c->lightListRequested.version && !(c->lightListPend >= 0 && c->lightListStored == c->lightListRequested.version)) {      // rtggx_set_light_list: the new list, and its copy on the device
+    dropLightListUpdates(c);      // (updates of the list this one replaces)
+    RT_HIP(syncStreams(c)); ++c->visibilityDrains;      // (a frame in flight may read the list the upload replaces)
     c->lightList = c->lightListRequested;
     const int r = uploadLightList(c); if (r) return r;
+  } else {
+    if (c->lightList.version != c->lightListRequested.version) c->lightListFrame = false;      // (a new list that a device update has uploaded already)
+    takeLightList = true;
   }
   c->scoring = c->scoringRequested && c->reference != nullptr;
   c->sampleMap = c->sampleMapRequested;      // rtggx_set_sample_map: the setter has waited for every stream and written the copy no frame reads
@@ -207,7 +212,7 @@ int rtggx_render_visibility(rtggx_context* c) {
   if (c->sampleSet != c->sampleSetRequested) {      // rtggx_set_sample_set: the kernels' variant, the table and the constants' mask change together
     // several frames from one rtggx_update_frame share the slot's device copy: the frame before may still read the mask that goes with ITS
     // table (a larger mask on a smaller table would read beyond it) -- wait for it.  One update per frame, the normal order, never waits.
-    if (c->slotRendered) RT_HIP(syncStreams(c));
+    if (c->slotRendered) { RT_HIP(syncStreams(c)); ++c->visibilityDrains; }
     c->sampleSet = c->sampleSetRequested;
     c->slots[c->slot].sampleMask = c->sampleSet - 1u;
     resendConstants = c->slotUploaded;      // constants already on their way (timing mode) go again behind this pass, as after a late rtggx_update_as
@@ -224,6 +229,7 @@ int rtggx_render_visibility(rtggx_context* c) {
   c->refitIssued = false;
   { const int r = issuePendingRefits(c, &c->refitIssued); if (r) return r; }
   const hipStream_t s = P.raster;
+  if (takeLightList) { const int r = takeLightListUpdates(c, s); if (r) return r; }      // (nothing where no update call came: no launch, no copy)
   if (c->evVisStream && c->evVisStream != s) RT_HIP(hipStreamWaitEvent(s, c->evVis, 0));      // the previous pass ran on another stream
   // this frame's target and list of large triangles were cleared by the ray generation two frames back: on another stream, mostly
   { const FrameEvents& g = c->frameEvents(c->frameCounter + 2u);
@@ -269,6 +275,13 @@ int rtggx_ray_trace(rtggx_context* c) {
     if (c->slotUploaded) RT_HIP(hipStreamWaitEvent(sGen, c->evAS, 0));
   }
   if (c->refitIssued && c->asyncCompute) RT_HIP(hipStreamWaitEvent(sTrace, c->evRefit, 0));      // this set's tree
+  // rtggx_update_light_list[_device]: the frame's version of the list was written on another stream (the visibility pass's, the
+  // caller's) -- the two streams whose kernels read it wait for that write, until it is seen to have ended
+  if (c->lightListAwaitWritten && c->lightListCur >= 0 && c->lightList.count) {
+    rtggx_context::LightListVersion& v = c->lightListRing[c->lightListCur];
+    if (hipEventQuery(v.evWritten) == hipSuccess) c->lightListAwaitWritten = false;
+    else { RT_HIP(hipStreamWaitEvent(c->streamMain, v.evWritten, 0)); if (sTrace != c->streamMain) RT_HIP(hipStreamWaitEvent(sTrace, v.evWritten, 0)); }
+  }
   if (c->timing) hipEventRecord(c->tev[3], sGen);
   FrameEvents& ev = c->frameEvents(f);
   const bool shadeWithTrace = P.shadeWithTrace && sGen != sTrace && sTrace != c->streamMain;
@@ -325,6 +338,12 @@ int rtggx_ray_trace(rtggx_context* c) {
   if (c->lights.count || c->lightList.count) {      // (rtggx_set_light_list: the same pass over the list)
     if (!r) r = launchLights(c, fp, c->streamMain);
     c->shadeStream = c->diffStream = c->streamMain;
+  }
+  // rtggx_update_light_list[_device]: the frame's version of the list has been read for the last time where the main stream stands --
+  // launchLights ran on it, and it has passed ev.trace, which rides behind the hit passes (launchShade's `done`)
+  if (c->lightListCur >= 0 && c->lightList.count) {
+    rtggx_context::LightListVersion& v = c->lightListRing[c->lightListCur];
+    RT_HIP(hipEventRecord(v.evRead, c->streamMain)); v.readRecorded = true;
   }
   // accumulation (rtggx_set_accumulation): the frame's two traced images into the running sums, on the main stream.  Both images are
   // complete where the main stream stands: it has passed ev.trace, which rides on the traversal with the shading (and the resolve of N

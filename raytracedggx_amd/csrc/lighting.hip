@@ -22,9 +22,12 @@
 //
 // SOFT and CONE are compile-time: a directional sun, and a context with point lights of radius 0, pay for neither the hash nor the cone.
 #include <type_traits>
+#include <cstring>
+#include "capi_internal.h"
 #include "rt_queue.h"
 #include "rt_traverse.h"
 #include "rt_surface.h"
+#include "rt_light_check.h"
 
 namespace rt {
 
@@ -1320,23 +1323,24 @@ __global__ void __launch_bounds__(256) lightListVisAddKernel(const FrameParams* 
 static void (*const kLightListVisGen[4])(const FrameParams*, const LightRecord*, const float4*, LightListGenArgs, LightVisArgs) = {lightListVisGenKernel<false, false>, lightListVisGenKernel<false, true>, lightListVisGenKernel<true, false>, lightListVisGenKernel<true, true>};
 // The list to the device when the setting takes effect (frame.hip rtggx_render_visibility): the records with pickList's neutral cone, the
 // cull's (Pl, R) with R = 0 where a light casts nothing; how many cast, and the instance [2 cone + soft] the list runs.  A frame that still
-// reads the previous list may be in flight: the caller has waited for the streams (a change of the list is a setup step, not a per-frame one).
+// reads the previous list may be in flight: the caller has waited for the streams (a NEW list is a setup step; lights that move are updated in place: "moving light lists" below).
 int uploadLightList(rtggx_context* c) {
   const std::vector<RtggxLight>& list = c->lightList.l;
   c->lightListCasting = 0u; c->lightListVariant = 0u;
   c->lightListFrame = false;
+  c->lightListCur = c->lightListNewest = -1; c->lightListStored = c->lightList.version; c->lightListAwaitWritten = false;      // (rtggx_update_light_list: the frames read this copy again)
+  c->lightListRecsCur = c->lightListCullCur = nullptr;
   if (list.empty()) return 0;
+  static_assert(sizeof(LightRecord) == sizeof(LightWords) && sizeof(LightCull) == sizeof(float4), "rt_light_check.h converts into the kernels' records");
   std::vector<LightRecord> recs(list.size());
   std::vector<float4> cull(list.size());
   for (size_t i = 0; i < list.size(); ++i) {
     const RtggxLight& l = list[i];
-    LightRecord r = {};
-    r.k = lightArgs(l);
-    if (!(l.cos_outer > -1.0f)) { r.k.Ax = r.k.Ay = r.k.Az = 0.0f; r.k.cosOuter = -2.0f; r.k.cosInner = -1.0f; }
-    recs[i] = r;
-    const bool casts = lightCastsRays(l);
-    cull[i] = make_float4(l.position[0], l.position[1], l.position[2], casts ? l.range : 0.0f);
-    if (casts) { ++c->lightListCasting; c->lightListVariant |= lightVariant(l); }
+    LightWords w, r; LightCull q;
+    memcpy(&w, &l, sizeof w);
+    lightConvert(w, r, q);      // (the list was checked when it was set: context.hip checkLight)
+    memcpy(&recs[i], &r, sizeof r); memcpy(&cull[i], &q, sizeof q);
+    if (lightCastsRays(l)) { ++c->lightListCasting; c->lightListVariant |= lightVariant(l); }
   }
   if (c->lightListCapacity < list.size()) {
     c->lightListRecs.reset(); c->lightListCull.reset();
@@ -1345,6 +1349,7 @@ int uploadLightList(rtggx_context* c) {
   }
   RT_HIP(hipMemcpy(c->lightListRecs, recs.data(), recs.size() * sizeof(LightRecord), hipMemcpyHostToDevice));
   RT_HIP(hipMemcpy(c->lightListCull, cull.data(), cull.size() * sizeof(float4), hipMemcpyHostToDevice));
+  c->lightListRecsCur = c->lightListRecs; c->lightListCullCur = c->lightListCull;
   return 0;
 }
 // The blocks' kept counts (rtggx_read_light_list_counts) exist from the first frame with a list and are cleared in front of every such
@@ -1366,9 +1371,9 @@ static int launchLightListGen(rtggx_context* c, hipStream_t s, const LightPickGe
   A.tileWords = P.tileWords; A.tilesX = P.tilesX; A.rowBegin = P.rowBegin; A.rowEnd = P.rowEnd;
   A.cosSin = c->cosSinTab; A.kept = c->lightListKept; A.blocksX = blocksX; A.count = c->lightList.count; A.cullOn = c->lightListCullOn ? 1u : 0u;
   if (records) launch(kLightListVisGen[c->lightListVariant], dim3(numTiles), dim3(256), s, nullptr, nullptr, c->dParams + c->slot,
-                      (const LightRecord*)c->lightListRecs.get(), (const float4*)c->lightListCull.get(), A, *records);
+                      (const LightRecord*)c->lightListRecsCur, (const float4*)c->lightListCullCur, A, *records);
   else launch(kLightListGen[c->lightListVariant], dim3(numTiles), dim3(256), s, nullptr, nullptr, c->dParams + c->slot,
-              (const LightRecord*)c->lightListRecs.get(), (const float4*)c->lightListCull.get(), A);
+              (const LightRecord*)c->lightListRecsCur, (const float4*)c->lightListCullCur, A);
   return 0;
 }
 
@@ -1429,7 +1434,7 @@ int launchLightHits(rtggx_context* c, const FrameParams& fp, const HitPass& p) {
     P.tileWords = G.tileWords;
     P.cosSin = G.cosSin; P.frameIndex = p.frameIndex; P.level = p.level; P.count = c->lightList.count; P.cullOn = c->lightListCullOn ? 1u : 0u;
     launch(kLightListHitGen[c->lightListVariant], dim3(p.numTiles), dim3(256), p.s, nullptr, nullptr, c->dParams + c->slot,
-           (const LightRecord*)c->lightListRecs.get(), (const float4*)c->lightListCull.get(), P);
+           (const LightRecord*)c->lightListRecsCur, (const float4*)c->lightListCullCur, P);
     return traceAndAddHits(c, fp, p, q);
   }
   if (c->lightSampling == 1u) {      // rtggx_set_light_sampling: one generating launch, one traversal, one add for the whole list
@@ -1453,4 +1458,192 @@ int launchLightHits(rtggx_context* c, const FrameParams& fp, const HitPass& p) {
   return 0;
 }
 
+
+// ---- moving light lists (rtggx_update_light_list, rtggx_update_light_list_device; DESIGN.md section 9 "Moving light lists") -----------------
+// Only WHICH list a frame reads is new: the cull, the pick, the slots and the records' update above are untouched, and take their recs /
+// cull pointers from the frame's version (rtggx_context::lightListRecsCur / CullCur).  A version is written once, in call order, on
+// whatever streams the calls name; every write waits for the version's previous write where that ran on another stream and records
+// evWritten behind itself.  The frame that takes a version lets the streams that read it wait for evWritten (frame.hip
+// rtggx_ray_trace) and records evRead behind its last pass over the list; the ring's next write into the version waits for that on the
+// host -- with eight versions and at most four frames in flight it has long happened.
+//
+// lightListPrepareKernel: the device path.  One lane per light: the 64 bytes as four 16-byte loads, rt_light_check.h's check and
+// conversion, the record as four 16-byte stores and the cull entry as one.  A refused light is written in its sanitised form and counted:
+// one ballot and one atomic add per wave (a workgroup is one wave).  No LDS, at most 16 workgroups.
+struct LightPrepareArgs { const float4* in; float4* recs; float4* cull; unsigned long long* rejects; uint32_t count, kinds; };
+__global__ void __launch_bounds__(64) lightListPrepareKernel(LightPrepareArgs A) {
+  const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+  bool reject = false;
+  if (i < A.count) {
+    const float4 a = A.in[4u * i], b = A.in[4u * i + 1u], c = A.in[4u * i + 2u], d = A.in[4u * i + 3u];
+    const LightWords l = {{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w}};
+    LightWords r; LightCull q;
+    reject = lightCheck(l, A.kinds) != LIGHT_OK;
+    if (reject) lightSanitise(r, q); else lightConvert(l, r, q);
+    A.recs[4u * i] = make_float4(r.w[0], r.w[1], r.w[2], r.w[3]); A.recs[4u * i + 1u] = make_float4(r.w[4], r.w[5], r.w[6], r.w[7]);
+    A.recs[4u * i + 2u] = make_float4(r.w[8], r.w[9], r.w[10], r.w[11]); A.recs[4u * i + 3u] = make_float4(r.w[12], r.w[13], r.w[14], r.w[15]);
+    A.cull[i] = make_float4(q.x, q.y, q.z, q.R);
+  }
+  const unsigned long long m = __ballot(reject);
+  if (m != 0ull && threadIdx.x == 0u) atomicAdd(A.rejects, (unsigned long long)__popcll(m));
+}
+// casting count and variant of the frame's list: what the host knows of it, and what the device path's callers declared
+static void lightListState(rtggx_context* c) {
+  c->lightListCasting = 0u; c->lightListVariant = c->lightList.kinds;
+  for (const RtggxLight& l : c->lightList.l) if (lightCastsRays(l)) { ++c->lightListCasting; c->lightListVariant |= lightVariant(l); }
+  if (c->lightList.presumed && !c->lightListCasting) c->lightListCasting = 1u;      // presumed casting: the frame launches the list's kernels
+}
+static float* versionRecs(rtggx_context::LightListVersion& v) { return v.buf.get(); }
+static float* versionCull(rtggx_context::LightListVersion& v, uint32_t count) { return v.buf.get() + (size_t)count * 16u; }
+// The ring, at the first update of a context's life (a setup step: eight allocations of 80 KB, as many pinned, the events)
+static int ensureLightListRing(rtggx_context* c) {
+  if (c->lightListRingReady) return 0;
+  for (auto& v : c->lightListRing) {
+    RT_HIP(alloc(v.buf, (size_t)RTGGX_MAX_LIGHT_LIST * 20u)); RT_HIP(alloc(v.stage, (size_t)RTGGX_MAX_LIGHT_LIST * 20u));
+    RT_HIP(create(v.evWritten, hipEventDisableTiming)); RT_HIP(create(v.evRead, hipEventDisableTiming)); RT_HIP(create(v.evCopied, hipEventDisableTiming));
+  }
+  c->lightListRingReady = true;
+  return 0;
+}
+// every write into a version: behind its previous write
+static int beginVersionWrite(rtggx_context::LightListVersion& v, hipStream_t s) {
+  if (v.written && v.writeStream != s) RT_HIP(hipStreamWaitEvent(s, v.evWritten, 0));
+  return 0;
+}
+static int endVersionWrite(rtggx_context::LightListVersion& v, hipStream_t s) {
+  RT_HIP(hipEventRecord(v.evWritten, s));
+  v.written = true; v.writeStream = s;
+  return 0;
+}
+// The version the updates since the last rtggx_render_visibility write into, opened by the first of them on its stream s: the next of
+// the ring that neither the current frame reads nor holds the newest list.  merge: it begins as a copy of the newest list (a partial
+// range on a list whose values the host does not know).
+static int openLightListVersion(rtggx_context* c, hipStream_t s, bool merge) {
+  { const int r = ensureLightListRing(c); if (r) return r; }
+  uint32_t k = c->lightListRingNext;
+  while ((int)k == c->lightListCur || (int)k == c->lightListNewest) k = (k + 1u) % rtggx_context::kLightListVersions;
+  c->lightListRingNext = (k + 1u) % rtggx_context::kLightListVersions;
+  rtggx_context::LightListVersion& v = c->lightListRing[k];
+  // its last reader, or -- a version no frame took -- its last write, has ended: in the steady state long ago
+  if (v.readRecorded) RT_HIP(hipEventSynchronize(v.evRead));
+  if (v.written) RT_HIP(hipEventSynchronize(v.evWritten));
+  if (v.copied) RT_HIP(hipEventSynchronize(v.evCopied));
+  v.written = v.readRecorded = v.copied = v.staged = false; v.writeStream = nullptr;
+  const uint32_t n = c->lightListRequested.count;
+  if (merge) {
+    if (c->lightListNewest >= 0) {
+      rtggx_context::LightListVersion& src = c->lightListRing[c->lightListNewest];
+      if (src.written && src.writeStream != s) RT_HIP(hipStreamWaitEvent(s, src.evWritten, 0));
+      RT_HIP(hipMemcpyAsync(v.buf.get(), src.buf.get(), (size_t)n * 80u, hipMemcpyDeviceToDevice, s));
+      RT_HIP(hipEventRecord(src.evCopied, s)); src.copied = true;
+    } else {      // rtggx_set_light_list's copy, written behind a wait for every stream
+      RT_HIP(hipMemcpyAsync(versionRecs(v), c->lightListRecs.get(), (size_t)n * 64u, hipMemcpyDeviceToDevice, s));
+      RT_HIP(hipMemcpyAsync(versionCull(v, n), c->lightListCull.get(), (size_t)n * 16u, hipMemcpyDeviceToDevice, s));
+    }
+    { const int r = endVersionWrite(v, s); if (r) return r; }
+  }
+  c->lightListPend = (int)k;
+  return 0;
+}
+// The host path's lights that are not yet on the device (rtggx_context::lightListDirtyLo / Hi of lightListRequested), into the open
+// version through its pinned staging, on s.  Where none is open one is opened: with the whole list from the host where the host knows
+// it, as a copy of the newest with the range on top where it does not.
+static int flushLightListUpdates(rtggx_context* c, hipStream_t s) {
+  const rtggx_context::LightList& L = c->lightListRequested;
+  uint32_t lo = c->lightListDirtyLo, hi = c->lightListDirtyHi;
+  if (lo >= hi) return 0;
+  if (c->lightListPend < 0) {
+    if (!L.presumed) { lo = 0u; hi = L.count; }
+    const int r = openLightListVersion(c, s, !(lo == 0u && hi == L.count)); if (r) return r;
+  }
+  rtggx_context::LightListVersion& v = c->lightListRing[c->lightListPend];
+  if (v.staged) RT_HIP(hipEventSynchronize(v.evWritten));      // (host, device and host again between two frames: the staging is still the first copy's)
+  LightWords* recs = (LightWords*)v.stage.get(); LightCull* cull = (LightCull*)(v.stage.get() + (size_t)L.count * 16u);
+  for (uint32_t i = lo; i < hi; ++i) { LightWords w; memcpy(&w, &L.l[i], sizeof w); lightConvert(w, recs[i], cull[i]); }
+  { const int r = beginVersionWrite(v, s); if (r) return r; }
+  if (lo == 0u && hi == L.count) RT_HIP(hipMemcpyAsync(v.buf.get(), v.stage.get(), (size_t)L.count * 80u, hipMemcpyHostToDevice, s));
+  else {
+    RT_HIP(hipMemcpyAsync(versionRecs(v) + (size_t)lo * 16u, recs + lo, (size_t)(hi - lo) * 64u, hipMemcpyHostToDevice, s));
+    RT_HIP(hipMemcpyAsync(versionCull(v, L.count) + (size_t)lo * 4u, cull + lo, (size_t)(hi - lo) * 16u, hipMemcpyHostToDevice, s));
+  }
+  v.staged = true;
+  c->lightListDirtyLo = c->lightListDirtyHi = 0u;
+  c->lightListStored = L.version;
+  return endVersionWrite(v, s);
+}
+void dropLightListUpdates(rtggx_context* c) {      // (a version that was opened and is not taken: its writes are waited for when the ring comes round)
+  c->lightListPend = -1; c->lightListDirtyLo = c->lightListDirtyHi = 0u;
+}
+// rtggx_render_visibility: the frame takes what the update calls since the last frame left -- the host's copy of the list, the version
+// they opened (the host path's upload goes on s, the frame's first stream) --, or nothing: then it launches and copies nothing.
+int takeLightListUpdates(rtggx_context* c, hipStream_t s) {
+  if (c->lightListPend < 0 && c->lightListDirtyLo >= c->lightListDirtyHi) return 0;
+  { const int r = flushLightListUpdates(c, s); if (r) return r; }
+  c->lightList = c->lightListRequested;
+  lightListState(c);
+  rtggx_context::LightListVersion& v = c->lightListRing[c->lightListPend];
+  c->lightListCur = c->lightListNewest = c->lightListPend; c->lightListPend = -1;
+  c->lightListRecsCur = versionRecs(v); c->lightListCullCur = versionCull(v, c->lightList.count);
+  c->lightListAwaitWritten = true;
+  return 0;
+}
 }  // namespace rt
+using namespace rt;
+
+extern "C" {
+// The device path (include/rtggx.h): ordered like hipMemcpyAsync on the caller's stream -- the merge copy, where the range is partial,
+// and lightListPrepareKernel run ON that stream, so what it holds precedes the read and what follows is behind it.  No host copy, no
+// wait in the steady state.  A rtggx_set_light_list that has not taken effect yet is uploaded here (its whole list through the staging).
+int rtggx_update_light_list_device(rtggx_context* c, const RtggxLight* device_lights, uint32_t first, uint32_t count, uint32_t kinds, void* hip_stream) {
+  RT_CHECK_CTX(c);
+  rtggx_context::LightList& L = c->lightListRequested;
+  if (!L.count) { setError("rtggx_update_light_list_device: the context holds no light list (rtggx_set_light_list)"); return -1; }
+  if (first > L.count || count > L.count - first) { setError("rtggx_update_light_list_device: lights %u .. %u of a list of %u: the count of a list never changes", first, first + count, L.count); return -1; }
+  if (kinds > (RTGGX_LIGHT_KIND_RADIUS | RTGGX_LIGHT_KIND_CONE)) { setError("rtggx_update_light_list_device: kinds %u: RTGGX_LIGHT_KIND_RADIUS | RTGGX_LIGHT_KIND_CONE at the most", kinds); return -1; }
+  if (!count) return 0;
+  if (!device_lights) { setError("rtggx_update_light_list_device: %u lights at a null pointer", count); return -1; }
+  if (((uintptr_t)device_lights & 15u) != 0u) { setError("rtggx_update_light_list_device: the lights at %p: aligned to 16 bytes", (const void*)device_lights); return -1; }
+  const hipStream_t s = (hipStream_t)hip_stream;
+  if (!c->lightListRejects) { RT_HIP(allocFilled(c->lightListRejects, 1)); const int r = syncFills(true); if (r) return r; }
+  if (L.version != c->lightListStored) { dropLightListUpdates(c); c->lightListDirtyLo = 0u; c->lightListDirtyHi = L.count; }      // a list set and not yet taken: its upload, now
+  { const int r = flushLightListUpdates(c, s); if (r) return r; }      // (the host path's earlier calls: call order)
+  if (c->lightListPend < 0) { const int r = openLightListVersion(c, s, !(first == 0u && count == L.count)); if (r) return r; }
+  rtggx_context::LightListVersion& v = c->lightListRing[c->lightListPend];
+  { const int r = beginVersionWrite(v, s); if (r) return r; }
+  LightPrepareArgs A;
+  A.in = (const float4*)device_lights; A.recs = (float4*)versionRecs(v) + (size_t)first * 4u; A.cull = (float4*)versionCull(v, L.count) + first;
+  A.rejects = c->lightListRejects.get(); A.count = count; A.kinds = kinds;
+  launch(lightListPrepareKernel, dim3((count + 63u) / 64u), dim3(64), s, nullptr, nullptr, A);
+  RT_HIP(hipGetLastError());
+  { const int r = endVersionWrite(v, s); if (r) return r; }
+  L.kinds |= kinds; L.presumed = true;
+  c->lightListStored = L.version;
+  return 0;
+}
+// The list the last frame read, as the kernels see it, behind everything the context has enqueued and behind the version's last write
+int rtggx_read_light_list(rtggx_context* c, RtggxLight* out, size_t bytes) {
+  RT_CHECK_CTX(c);
+  if (!c->lightList.count || !c->lightListRecsCur) { setError("rtggx_read_light_list: no list yet: it exists from the first frame with a list (rtggx_set_light_list)"); return -1; }
+  const size_t want = (size_t)c->lightList.count * sizeof(RtggxLight);
+  if (!out || bytes != want) { setError("rtggx_read_light_list: %zu bytes at %p: %u lights of 64 bytes are %zu", bytes, (void*)out, c->lightList.count, want); return -1; }
+  RT_HIP(syncStreams(c));
+  if (c->lightListCur >= 0 && c->lightListRing[c->lightListCur].written) RT_HIP(hipEventSynchronize(c->lightListRing[c->lightListCur].evWritten));
+  RT_HIP(hipMemcpy(out, c->lightListRecsCur, want, hipMemcpyDeviceToHost));
+  return 0;
+}
+// The device path's refused lights since the last reset, behind every lightListPrepareKernel enqueued so far
+int rtggx_read_light_list_rejects(rtggx_context* c, uint64_t* rejects, int reset) {
+  RT_CHECK_CTX(c);
+  if (!rejects) { setError("rtggx_read_light_list_rejects: a null pointer"); return -1; }
+  if (reset != 0 && reset != 1) { setError("rtggx_read_light_list_rejects: reset %d: 0 or 1", reset); return -1; }
+  RT_HIP(syncStreams(c));
+  unsigned long long n = 0ull;
+  if (c->lightListRejects) {
+    for (auto& v : c->lightListRing) if (v.written) RT_HIP(hipEventSynchronize(v.evWritten));      // (the callers' streams are not the context's)
+    RT_HIP(hipMemcpy(&n, c->lightListRejects.get(), sizeof n, hipMemcpyDeviceToHost));
+    if (reset && n) { const unsigned long long zero = 0ull; RT_HIP(hipMemcpy(c->lightListRejects.get(), &zero, sizeof zero, hipMemcpyHostToDevice)); }
+  }
+  *rejects = (uint64_t)n;
+  return 0;
+}
+}  // extern "C"

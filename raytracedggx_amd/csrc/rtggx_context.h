@@ -355,11 +355,37 @@ struct rtggx_context {
   //   lightListKept  the kept lights per 8x8 block of the last such frame's primary pass (rtggx_read_light_list_counts); lightListFrame:
   //                  such a frame has run since the last upload
   // lightQueue, lightSums, lightPickDiff and lightHitQueue are used as in mode 1.
-  struct LightList { uint32_t count = 0; uint64_t version = 0; std::vector<RtggxLight> l; } lightList, lightListRequested;
+  struct LightList { uint32_t count = 0; uint64_t version = 0; std::vector<RtggxLight> l; uint32_t kinds = 0; bool presumed = false; } lightList, lightListRequested;
   rt::DevBuf<float> lightListRecs, lightListCull; uint32_t lightListCapacity = 0, lightListCasting = 0, lightListVariant = 0;
   rt::DevBuf<uint32_t> lightListKept; bool lightListFrame = false;
   bool lightListCullOn = true;      // rtggx_debug_light_list_cull
   uint64_t lightListVersions = 0;      // successful rtggx_set_light_list calls that changed what is held: the next list's version
+  // rtggx_update_light_list, rtggx_update_light_list_device: lights that move (lighting.hip "Moving light lists").
+  // Nothing below exists before the first update.  The list's device storage becomes a ring of VERSIONS: a version is written once --
+  // by the host path's staged copy, by lightListPrepareKernel, by both in call order --, read by every frame from the
+  // rtggx_render_visibility that takes it until the next that takes another, and written again only when the last frame that read it
+  // has ended (evRead, recorded on the main stream behind the frame's last pass over the list).  A LightList's kinds / presumed: what
+  // the device path's callers declared, and that its values are no longer the host's to know (the list is presumed casting).
+  //   buf        count records of 64 bytes, then count cull entries of 16 (capacity RTGGX_MAX_LIGHT_LIST: any list fits any version)
+  //   stage      the same, pinned: the host path's staging; staged: a copy out of it has been enqueued since the version was opened
+  //   evWritten  behind the last write, on writeStream; evCopied: behind the last copy out of it into a newer version
+  //   lightListRecsCur / CullCur  what the frame's kernels read: a version's, or lightListRecs / lightListCull (lightListCur = -1)
+  //   lightListNewest  where the newest complete list lies (-1: lightListRecs / lightListCull); lightListPend: the version the updates
+  //                    since the last rtggx_render_visibility have opened (-1: none); lightListStored: the LightList::version it holds
+  //   lightListDirtyLo / Hi  the host path's lights not yet on the device
+  struct LightListVersion {
+    rt::DevBuf<float> buf; rt::PinnedBuf<float> stage; rt::Event evWritten, evRead, evCopied;
+    hipStream_t writeStream = nullptr; bool written = false, readRecorded = false, copied = false, staged = false;
+  };
+  static constexpr uint32_t kLightListVersions = 8u;      // more than the frames in flight (RT_SETS) plus the one being written
+  LightListVersion lightListRing[kLightListVersions]; bool lightListRingReady = false;
+  const float* lightListRecsCur = nullptr; const float* lightListCullCur = nullptr;
+  int lightListCur = -1, lightListNewest = -1, lightListPend = -1; uint32_t lightListRingNext = 0;
+  bool lightListAwaitWritten = false;      // the frame's version may still be on its way: the streams that read it wait for evWritten
+  uint64_t lightListStored = 0;
+  uint32_t lightListDirtyLo = 0, lightListDirtyHi = 0;
+  rt::DevBuf<unsigned long long> lightListRejects;      // rtggx_read_light_list_rejects: the device path's refused lights, one word
+  uint32_t visibilityDrains = 0;      // rtggx_debug_visibility_drains: rtggx_render_visibility's waits for every stream
   uint32_t rayRate = 1;         // rtggx_set_ray_rate: pixels per traced ray, 1 or 4 (raytrace.hip rayGenKernel, reconstructKernel)
   uint32_t maxDepth = 1, depthRequested = 1;      // rtggx_set_max_recursion_depth: 1..4 levels of rays per path (raytrace.hip launchShade); the frame's, the next frame's
   // rtggx_set_samples_per_pixel: 1, 2, 4 or 8 samples per covered pixel (raytrace.hip launchShade; DESIGN.md "Samples per pixel"); the
@@ -572,6 +598,8 @@ int launchRayTrace(rtggx_context* c, const FrameParams& fp, hipStream_t sGen, hi
 int launchShade(rtggx_context* c, const FrameParams& fp, hipStream_t s, hipEvent_t done = nullptr);      // hit / miss shading of the traced bins
 int launchSun(rtggx_context* c, const FrameParams& fp, hipStream_t s);      // rtggx_set_sun: shadow rays from the primary surface, the any-hit traversal, the add into RayTracingOut0/1
 int uploadLightList(rtggx_context* c);      // rtggx_set_light_list: c->lightList to the device, behind a wait for every stream
+int takeLightListUpdates(rtggx_context* c, hipStream_t s);      // rtggx_update_light_list[_device]: what the calls since the last frame left, taken by this frame (uploads on s)
+void dropLightListUpdates(rtggx_context* c);      // a new list replaces them
 int launchLights(rtggx_context* c, const FrameParams& fp, hipStream_t s);   // rtggx_set_lights: per light generate -> any-hit -> add into the sums, one resolve into RayTracingOut0/1
 // rtggx_set_sun_reflections, rtggx_set_light_reflections (lighting.hip; called by launchShade in front of every level's shading pass): the frame's
 // first use of their queues and sums on stream s, then per level the sun's pass and the lights' (HitPass: rt_queue.h), then for a

@@ -99,6 +99,19 @@ void RayTracedGGX::OnUpdate() {
     const std::vector<float>& shape = m_deformShapes[m_frameNumber % DeformPeriod];
     m_rayTracer->UpdateMesh(shape.data(), (uint32_t)(shape.size() / 6));
   }
+  // -lightlistorbit d: before frame n every position and spot axis of the FILE's list turned about the world y axis by n d degrees --
+  // x' = x cos a + z sin a, z' = z cos a - x sin a, from the originals in double and rounded once, so nothing drifts --, handed over
+  // without a wait and without a reset of the records (RayTracer::UpdateLightList)
+  if (m_lightListOrbit != 0.0 && !m_lightList.empty()) {
+    const double a = (double)m_frameNumber * m_lightListOrbit * 3.14159265358979323846 / 180.0, ca = std::cos(a), sa = std::sin(a);
+    m_lightListMoved = m_lightList;
+    for (RtggxLight& l : m_lightListMoved) {
+      const double px = l.position[0], pz = l.position[2], ax = l.axis[0], az = l.axis[2];
+      l.position[0] = (float)(px * ca + pz * sa); l.position[2] = (float)(pz * ca - px * sa);
+      l.axis[0] = (float)(ax * ca + az * sa); l.axis[2] = (float)(az * ca - ax * sa);
+    }
+    if (!m_rayTracer->UpdateLightList(m_lightListMoved.data(), 0u, (uint32_t)m_lightListMoved.size())) throw std::runtime_error("-lightlistorbit: " + m_rayTracer->GetLastError());
+  }
   ++m_frameNumber;
   const float timeStep = m_isPaused ? 0.0f : m_fixedTimeStep;
   m_rayTracer->UpdateFrame(m_frameIndex, m_eyePt, m_view * m_proj, timeStep);
@@ -238,7 +251,7 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
     return (arg[0] == '-' || arg[0] == '/') && lower(arg + 1) == lower(name);
   };
   // On POSIX an absolute path also starts with '/': such a token is a flag only when it names one.
-  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "sun", "sunreflections", "sunfromenv", "sunangle", "light", "spot", "lightreflections", "lightpick", "lightvisibility", "lightlistvisibility", "lightlist", "recursion", "spp", "accumulate", "sampleset", "savereference", "reference", "score", "envlayout", "envsize", "envmips", "envprefilter"};
+  static const char* const kFlags[] = {"warp", "uma", "mesh", "env", "width", "height", "frames", "dt", "metallic", "sharedmem", "sync", "vndf", "device", "dump", "gpus", "track", "deform", "rank", "idfile", "strips", "balance", "rayrate", "sun", "sunreflections", "sunfromenv", "sunangle", "light", "spot", "lightreflections", "lightpick", "lightvisibility", "lightlistvisibility", "lightlistorbit", "lightlist", "recursion", "spp", "accumulate", "sampleset", "savereference", "reference", "score", "envlayout", "envsize", "envmips", "envprefilter"};
   const auto isFlagName = [&](const char* name) { for (const char* f : kFlags) if (lower(name) == f) return true; return false; };
   const auto hasNextArgValue = [&](int i) {
     if (i + 1 >= argc) return false;
@@ -294,6 +307,12 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
     else if (isArgMatched(i, "sunreflections")) m_sunReflections = true;      // (without -sun: refused below, once the whole line is read)
     else if (isArgMatched(i, "lightreflections")) m_lightReflections = true;      // (without -light / -spot: refused below, once the whole line is read)
     else if (isArgMatched(i, "lightpick")) m_lightPick = true;      // (without -light / -spot: refused below, once the whole line is read)
+    else if (isArgMatched(i, "lightlistorbit")) {      // (without -lightlist: refused below, once the whole line is read)
+      if (i + 1 >= argc) throw std::runtime_error("-lightlistorbit: degrees per frame");
+      char* end = nullptr; m_lightListOrbit = std::strtod(argv[++i], &end);
+      if (end == argv[i] || *end || !std::isfinite(m_lightListOrbit)) throw std::runtime_error(std::string("-lightlistorbit: ") + argv[i] + ": degrees per frame, a finite number");
+      m_lightListOrbitGiven = true;
+    }
     else if (isArgMatched(i, "lightlistvisibility")) m_lightListVisibility = true;      // (without -lightlist, or with strips: refused below, once the whole line is read)
     else if (isArgMatched(i, "lightvisibility")) m_lightVisibility = true;      // (without -lightpick, or with strips: refused below, once the whole line is read)
     // -sunfromenv [degrees]: the sun measured from the -env cube and taken out of it (rtggx_sun_from_env, RayTracer::Init); the half-angle
@@ -430,6 +449,7 @@ void RayTracedGGX::ParseCommandLineArgs(char* argv[], int argc) {
   if (m_rayRate != 1u && !m_lights.empty()) throw std::runtime_error("-light / -spot together with -rayrate 4: refused");
   // a light list (rtggx_set_light_list) is held in place of the lights, not beside them, and excludes rate 4 as they do
   // the list's visibility records (rtggx_set_light_list_visibility) act only on a list, and on whole frames
+  if (m_lightListOrbitGiven && m_lightListFile.empty()) throw std::runtime_error("-lightlistorbit without -lightlist: there is no list to turn");
   if (m_lightListVisibility && m_lightListFile.empty()) throw std::runtime_error("-lightlistvisibility without -lightlist: there is no list whose pick to weight");
   if (m_lightListVisibility && (m_gpus > 1 || m_strips > 1)) throw std::runtime_error("-lightlistvisibility: whole frames only, not with -gpus N > 1 or -strips N > 1");
   if (!m_lightListFile.empty() && !m_lights.empty()) throw std::runtime_error("-lightlist together with -light / -spot: the context holds one or the other");

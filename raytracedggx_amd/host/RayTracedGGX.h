@@ -2,7 +2,7 @@
 // DXFramework virtuals RayTracedGGX/Common/DXFramework.h:23-26): OnInit / OnUpdate / OnRender /
 // OnDestroy, the same command line (RayTracedGGX.cpp:462-511) and the same defaults
 // (RayTracedGGX.cpp:37-39, camera :19-23, 267-277).  What the window supplied interactively is
-// supplied by extra flags: -width -height -frames -dt -metallic -sharedmem -sync -vndf -rayrate -sun -sunreflections -sunfromenv -sunangle -light -spot -lightreflections -lightpick -lightvisibility -lightlist -lightlistvisibility -recursion -spp -sampleset -accumulate -savereference -reference -score -envlayout -envsize -envmips -envprefilter -device -dump -track -deform -gpus -strips -balance.
+// supplied by extra flags: -width -height -frames -dt -metallic -sharedmem -sync -vndf -rayrate -sun -sunreflections -sunfromenv -sunangle -light -spot -lightreflections -lightpick -lightvisibility -lightlist -lightlistvisibility -lightlistorbit -recursion -spp -sampleset -accumulate -savereference -reference -score -envlayout -envsize -envmips -envprefilter -device -dump -track -deform -gpus -strips -balance.
 #pragma once
 #include <vector>
 #include <cstdint>
@@ -155,6 +155,9 @@ class RayTracedGGX {
   // range radius ax ay az outer inner" (RayTracer::SetLightList); not together with -light / -spot or -rayrate 4; -lightreflections is
   // accepted with it
   std::string m_lightListFile; std::vector<RtggxLight> m_lightList;
+  // -lightlistorbit <degrees per frame>: before frame n the file's list turned about the world y axis by n x degrees, positions and spot
+  // axes, computed from the originals in double (RayTracer::UpdateLightList: no wait, the records' history kept); needs -lightlist
+  double m_lightListOrbit = 0.0; bool m_lightListOrbitGiven = false; std::vector<RtggxLight> m_lightListMoved;
   bool m_lightListVisibility = false; // -lightlistvisibility: the list's pick weighted by the sparse record each pixel keeps (RayTracer::SetLightListVisibility); needs -lightlist; whole frames only
   uint32_t m_rayRate = 1;              // -rayrate <1|4>: pixels per traced ray (RayTracer::SetRayRate); 4 renders whole frames only: not with -gpus / -strips
   // -deform <amplitude>: the model breathes -- a travelling sine wave through its vertices, DeformPeriod key shapes computed once

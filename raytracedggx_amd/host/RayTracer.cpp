@@ -122,6 +122,9 @@ bool RayTracer::SetLightReflections(bool enable) { return check(rtggx_set_light_
 bool RayTracer::SetLightList(const RtggxLight* lights, uint32_t count) { return check(rtggx_set_light_list(m_ctx, lights, count), "rtggx_set_light_list"); }
 bool RayTracer::SetLightSampling(int mode) { return check(rtggx_set_light_sampling(m_ctx, mode), "rtggx_set_light_sampling"); }
 bool RayTracer::SetLightListVisibility(bool enable) { return check(rtggx_set_light_list_visibility(m_ctx, enable ? 1 : 0), "rtggx_set_light_list_visibility"); }
+bool RayTracer::UpdateLightList(const RtggxLight* lights, uint32_t first, uint32_t count) { return check(rtggx_update_light_list(m_ctx, lights, first, count), "rtggx_update_light_list"); }
+bool RayTracer::UpdateLightListDevice(const RtggxLight* deviceLights, uint32_t first, uint32_t count, uint32_t kinds, void* stream) { return check(rtggx_update_light_list_device(m_ctx, deviceLights, first, count, kinds, stream), "rtggx_update_light_list_device"); }
+bool RayTracer::ReadLightList(RtggxLight* out, size_t bytes) { return check(rtggx_read_light_list(m_ctx, out, bytes), "rtggx_read_light_list"); }
 bool RayTracer::SetLightPickVisibility(bool enable) { return check(rtggx_set_light_pick_visibility(m_ctx, enable ? 1 : 0), "rtggx_set_light_pick_visibility"); }
 bool RayTracer::SetSunReflections(bool enable) { return check(rtggx_set_sun_reflections(m_ctx, enable ? 1 : 0), "rtggx_set_sun_reflections"); }
 

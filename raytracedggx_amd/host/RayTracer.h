@@ -83,6 +83,13 @@ class RayTracer {
   // The list's pick weighted by the sparse record each pixel keeps of the lights it found hidden (rtggx_set_light_list_visibility); it acts
   // only on a list while a light casts rays; whole frames only.
   bool SetLightListVisibility(bool enable);
+  // Lights first .. first + count - 1 of the list replaced from the next frame on, without a wait and without a reset of the records'
+  // history: from a host array, checked and copied (rtggx_update_light_list), or from device memory in the order of `stream`, checked on
+  // the device (rtggx_update_light_list_device; kinds: RTGGX_LIGHT_KIND_*).  ReadLightList: the list the last frame read, as the kernels
+  // see it (rtggx_read_light_list; synchronises).
+  bool UpdateLightList(const RtggxLight* lights, uint32_t first, uint32_t count);
+  bool UpdateLightListDevice(const RtggxLight* deviceLights, uint32_t first, uint32_t count, uint32_t kinds, void* stream);
+  bool ReadLightList(RtggxLight* out, size_t bytes);
   bool SetSamplesPerPixel(uint32_t samples);   // rtggx_set_samples_per_pixel: 1 (default), 2, 4 or 8 samples per covered pixel (-spp); not together with ray rate 4
   bool SetMaxRecursionDepth(uint32_t depth);   // rtggx_set_max_recursion_depth: 1 (default; RayTracer.cpp:605 SetMaxRecursionDepth(1)) to 4 levels of rays per path (-recursion)   // rtggx_set_ray_rate: 1 (default) or 4 -- one pixel of each 2x2 quad traced per frame, the rest reconstructed (-rayrate)
   // rtggx_set_sample_set: the size of the sample set getSampleParam draws from, 256 (default, the reference's) or a power of two up to

@@ -215,6 +215,26 @@ extern "C" int rtggx_app_set_light_list_visibility(void* h, int enable) {
   return -1;
 }
 
+// RayTracer::UpdateLightList, UpdateLightListDevice and ReadLightList of the application's ray tracer
+extern "C" int rtggx_app_update_light_list(void* h, const RtggxLight* lights, uint32_t first, uint32_t count) {
+  RayTracer* rt = ((RayTracedGGX*)h)->GetRayTracer();
+  if (rt->UpdateLightList(lights, first, count)) return 0;
+  g_appError = rt->GetLastError();
+  return -1;
+}
+extern "C" int rtggx_app_update_light_list_device(void* h, const RtggxLight* deviceLights, uint32_t first, uint32_t count, uint32_t kinds, void* stream) {
+  RayTracer* rt = ((RayTracedGGX*)h)->GetRayTracer();
+  if (rt->UpdateLightListDevice(deviceLights, first, count, kinds, stream)) return 0;
+  g_appError = rt->GetLastError();
+  return -1;
+}
+extern "C" int rtggx_app_read_light_list(void* h, RtggxLight* out, size_t bytes) {
+  RayTracer* rt = ((RayTracedGGX*)h)->GetRayTracer();
+  if (rt->ReadLightList(out, bytes)) return 0;
+  g_appError = rt->GetLastError();
+  return -1;
+}
+
 // The multi-GPU host's plan functions (host/Strips.cpp), for the tests that compare them with raytracedggx_amd/strips.py.
 // bounds: nullptr / 0 for equal strips, else world + 1 row numbers.  ops: 5 int32 per transfer (send, buffer: 1 history / 0 back buffer / 2 token, rowBegin, rowEnd, peer);
 // returns the number of transfers, or -1 with rtggx_app_last_error set.
